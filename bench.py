@@ -16,6 +16,12 @@ communication is the one-off RCCL broadcast of the source catalog from rank 0 in
 HBM before the timed region, plus the barriers / MAX-reduce of the timing contract.  Total work
 is fixed as N grows: "scaling": "strong".
 
+A plain run sets up, warms up, times --steps steps and prints the headline (`metric`, `value`, `unit`,
+`ms_per_step`, `dtype`, ...).  `--full` adds everything else the line can carry: the kernels' rooflines and the
+per-family breakdown step (HIP events in the timed region), the PMC traffic check, the host-to-host calls (`e2e`,
+`e2e_sharded`), the side runs of the default workload and the CPU baseline.  `--dump-outputs DIR` writes what the
+timed path left on the device after its last step (dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 
@@ -89,6 +95,11 @@ def parse():
     p.add_argument("--no-breakdown", action="store_true",
                    help="skip the extra single-stream step that times every kernel family (profiling runs)")
     p.add_argument("--cpu-seconds", type=float, default=20.0)
+    p.add_argument("--full", action="store_true",
+                   help="also the rooflines, breakdown step, PMC check, e2e calls, side runs and CPU baseline "
+                        "(the --no-* switches above act inside --full)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the visibilities of the last timed step as float .npy files into DIR")
     a = p.parse_args()
     a.base = "C3" if a.workload == "C3z" else a.workload
     if a.workload == "C3z":
@@ -101,6 +112,8 @@ def parse():
         a.steps = 50 if a.light else 3
     if a.warmup is None:
         a.warmup = 20 if a.light else 1
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     return a
 
 
@@ -364,6 +377,31 @@ def mini_run(cfg, device_index, path="type3", upsample=2.0, steps=2, warmup=1, s
     return res
 
 
+DUMP_BYTES = 48 << 20  # what --dump-outputs writes in all, over every rank and block, sample indices included
+
+
+def dump_outputs(d, named, budget):
+    """--dump-outputs: the visibilities the timed path left on the device after its last step, one entry of
+    ``named`` (name, device tensor in the engine's layout, SimHandle.out_shape) at a time, complex as a trailing
+    (re, im) axis in the engine's real type.  A block that fits ``budget`` bytes is written whole as <name>.npy; a
+    larger one as a fixed, seeded sample of its flattened elements: <name>_sample.npy (K, 2) at the sorted flat
+    indices <name>_sample_index.npy (float64, exact) -- the same indices whenever the block's size is the same, so
+    two builds' outputs can be compared element for element."""
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    for name, o in named:
+        flat = torch.view_as_real(o).reshape(-1, 2)
+        if flat.numel() * flat.element_size() <= budget:
+            np.save(os.path.join(d, name + ".npy"), torch.view_as_real(o).cpu().numpy())
+            continue
+        k = budget // (2 * flat.element_size() + 8)
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.shape[0], size=k))
+        sample = flat.index_select(0, torch.from_numpy(idx).to(o.device))
+        np.save(os.path.join(d, name + "_sample.npy"), sample.cpu().numpy())
+        np.save(os.path.join(d, name + "_sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and a.as_rank is None:
@@ -470,7 +508,9 @@ def main():
     # (a launch is hundreds of us) on EVERY launch (level 3); on C2-sized grids on the launches of one
     # time step in 16 (level 1), because even attached events idle the queue for 5-8 us around a 50 us
     # launch.  The other kernel families are timed in one extra, untimed step afterwards (level 2).
-    h.enable_timing(1 if a.light else 3)
+    # Only --full reports these: a plain run times the steps without events.
+    if a.full:
+        h.enable_timing(1 if a.light else 3)
 
     if dist is not None:
         dist.barrier()
@@ -494,7 +534,10 @@ def main():
 
     st, tm = h.stats(), h.timing()
     h.reset_stats()
-    breakdown = not a.no_breakdown and rank == 0 and len(mine) > 0
+    if a.dump_outputs:
+        named = [("vis" if len(mine) == 1 and world == 1 else f"vis_rank{rank}_block{i}", o) for i, o in enumerate(outs)]
+        dump_outputs(a.dump_outputs, named, DUMP_BYTES // max(world * len(outs), 1))
+    breakdown = a.full and not a.no_breakdown and rank == 0 and len(mine) > 0
     if breakdown:
         h.enable_timing(2)
         step()
@@ -503,20 +546,54 @@ def main():
     else:  # profiling runs: only launches shaped like the timed region's
         tm_all, st_all = None, st
     h.enable_timing(0)
-    finite = all(bool(torch.isfinite(torch.view_as_real(o)).all().item()) for o in outs)
+    finite = all(bool(torch.isfinite(torch.view_as_real(o)).all().item()) for o in outs) if a.full else None
     vis_per_step = nbls * nfreq * ntimes  # the whole observation, all ranks together
     if a.as_rank is not None:
         vis_per_step = nbls * sum((t.stop - t.start) * (f.stop - f.start) for t, f in mine)
     value = vis_per_step * a.steps / elapsed
 
     if rank == 0:
+        hterms = int(st.get("height_terms", 0))
+        own_ms = [1e3 * t / a.steps for t in per_rank]
+        res = {
+            "metric": "simulated visibilities/sec (baselines x freqs x times) at eps="
+                      + ("6e-8" if a.eps == 6e-8 else f"{a.eps:g}"),
+            "value": value,
+            "unit": "visibilities/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "settle_steps": extra,  # untimed repeats beyond --warmup (small workloads only, see above)
+            "ms_per_step": 1e3 * elapsed / a.steps,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32" if precision == 1 else "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": f"{a.workload}: {('scattered350 (no lattice, no repeated baseline vectors)' if a.array == 'scattered' else synth.CONFIGS[a.base][0])}"
+                            f"{(' + %g m height scatter (non-coplanar: %s)' % (a.z_scatter, ('%d height terms, 2-D transforms' % hterms) if hterms else '3-D transform')) if a.z_scatter else ''}, {nsrc} sources, "
+                            f"{nfreq} freqs, {ntimes} times, {nbls} baselines, "
+                            f"{('%d basis beams (eigenbeam path), polarized' % len(blist)) if 'beam_coefs' in cfg else 'polarized table beam' if pol else 'unpolarized Airy beam'}, "
+                            f"{a.path} NUFFT eps={a.eps:g} upsampfac={st.get('upsample_used', a.upsample):g}"
+                            + (" (chosen by the engine)" if a.upsample == 0 else ""),
+                "slices_per_step": nfreq * ntimes,
+                "sharding": (f"ONLY the block of rank {a.as_rank} of {a.of_ranks}: " if a.as_rank is not None else "")
+                            + "one observation, (time x freq) blocks per rank: "
+                            + "; ".join(f"r{r}: t[{b[0][0].start}:{b[0][0].stop}) f[{b[0][1].start}:{b[0][1].stop})" if b else f"r{r}: -"
+                                        for r, b in enumerate(blocks)),
+                "per_rank_ms_per_step": own_ms,
+                "imbalance_max_over_mean": max(own_ms) / (sum(own_ms) / len(own_ms)),
+            },
+        }
+
+    if rank == 0 and a.full:
         # ---- roofline of the spread kernel (the kernel BASELINE.json's metric names) ----------
         launches = max(st["spread_launches"], 1.0)
         timed = max(tm.get("spread_launches_timed", 0.0), 1.0)
         R8 = RB
         # transforms are 2-D for coplanar arrays AND for nearly flat ones, which run as K 2-D transforms per slice
         # (height terms, fv_sim.h wt_K); 3-D otherwise
-        hterms = int(st.get("height_terms", 0))
         d = 2 if coplanar or hterms else 3
         my_times = sum(t.stop - t.start for t, _ in mine)
         # algorithmic bytes:  M (d R + T 2R)  +  T G1 2R   summed over launches
@@ -639,39 +716,9 @@ def main():
                     "algorithmic_bytes_per_step": gb,
                     "note": "footprint rows are w-element pieces of 128-B lines: the lines fetched are about twice these bytes",
                 }
-        own_ms = [1e3 * t / a.steps for t in per_rank]
         h_closed = False
-        res = {
-            "metric": "simulated visibilities/sec (baselines x freqs x times) at eps="
-                      + ("6e-8" if a.eps == 6e-8 else f"{a.eps:g}"),
-            "value": value,
-            "unit": "visibilities/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "settle_steps": extra,  # untimed repeats beyond --warmup (small workloads only, see above)
-            "ms_per_step": 1e3 * elapsed / a.steps,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32" if precision == 1 else "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": f"{a.workload}: {('scattered350 (no lattice, no repeated baseline vectors)' if a.array == 'scattered' else synth.CONFIGS[a.base][0])}"
-                            f"{(' + %g m height scatter (non-coplanar: %s)' % (a.z_scatter, ('%d height terms, 2-D transforms' % hterms) if hterms else '3-D transform')) if a.z_scatter else ''}, {nsrc} sources, "
-                            f"{nfreq} freqs, {ntimes} times, {nbls} baselines, "
-                            f"{('%d basis beams (eigenbeam path), polarized' % len(blist)) if 'beam_coefs' in cfg else 'polarized table beam' if pol else 'unpolarized Airy beam'}, "
-                            f"{a.path} NUFFT eps={a.eps:g} upsampfac={st.get('upsample_used', a.upsample):g}"
-                            + (" (chosen by the engine)" if a.upsample == 0 else ""),
-                "slices_per_step": nfreq * ntimes,
-                "sharding": (f"ONLY the block of rank {a.as_rank} of {a.of_ranks}: " if a.as_rank is not None else "")
-                            + "one observation, (time x freq) blocks per rank: "
-                            + "; ".join(f"r{r}: t[{b[0][0].start}:{b[0][0].stop}) f[{b[0][1].start}:{b[0][1].stop})" if b else f"r{r}: -"
-                                        for r, b in enumerate(blocks)),
-                "per_rank_ms_per_step": own_ms,
-                "imbalance_max_over_mean": max(own_ms) / (sum(own_ms) / len(own_ms)),
-                "finite_output": finite,
-            },
+        res["config"]["finite_output"] = finite
+        res.update({
             "roofline": {
                 "kernel": spread_kernel,
                 "bound": "hbm",
@@ -694,7 +741,7 @@ def main():
             "roofline_fft": fft,
             "roofline_interp": interp_rf,
             "kernels": kern,
-        }
+        })
         if breakdown and tm_all["spread"] > 0 and a.path == "type3":
             # the spread kernel with the chip to itself (the extra single-stream step): same launches, same bytes
             l2 = max(st_all["spread_launches"], 1.0)
@@ -763,7 +810,7 @@ def main():
     # ---- N > 1, host to host: what a caller of the sharded simulate_vis waits for (never `value`) -----------------
     # every rank: catalog broadcast from rank 0 into device memory, its block through the engine, delivered straight
     # into its slice of ONE shared-memory result while later time steps compute (parallel.simulate_vis_sharded)
-    if dist is not None and not a.no_e2e and a.as_rank is None:
+    if a.full and dist is not None and not a.no_e2e and a.as_rank is None:
         # (a safety net around a part no 8-GPU node has run yet: if the host-to-host calls have not finished after
         # FFTVIS_BENCH_E2E_TIMEOUT seconds -- a collective stuck on some rank -- every rank leaves, rank 0 after printing
         # the line it already has, with the timeout recorded instead of `e2e_sharded`)
@@ -814,7 +861,7 @@ def main():
                 "finite_output": fin,
             }
     if rank == 0:
-        if dist is not None and not a.no_cpu_baseline:
+        if a.full and dist is not None and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg, a.cpu_seconds)  # rank 0's host cores, as at N = 1 (the others wait)
         print(json.dumps(res), flush=True)
     h.close()  # (idempotent)

@@ -311,7 +311,7 @@ def test_bench_gpus_n_starts_its_own_ranks(gpu):
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "C2", "--steps", "5",
-           "--warmup", "2", "--no-cpu-baseline"]
+           "--warmup", "2", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -323,6 +323,28 @@ def test_bench_gpus_n_starts_its_own_ranks(gpu):
                          env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True,
                          timeout=300)
     assert bad.returncode != 0 and "rank(s) joined" in bad.stderr + bad.stdout
+
+
+def test_plain_bench_line_and_dumped_outputs(gpu, tmp_path):
+    """`bench.py` without --full prints the headline only (no roofline, breakdown, e2e or CPU baseline), times exactly
+    --steps steps, and `--dump-outputs DIR` writes the last timed step's visibilities: configs[0] in full, against the
+    CPU oracle."""
+    import json
+
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "C1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["value"] > 0 and res["dtype"] == "f64"
+    assert res["unit"] == "visibilities/s" and res["higher_is_better"] is True and res["metric"].endswith("eps=6e-8")
+    assert not {"roofline", "kernels", "e2e", "cpu_baseline", "generic_array"} & set(res), sorted(res)
+    assert sorted(os.listdir(tmp_path)) == ["vis.npy"]
+    d = np.load(tmp_path / "vis.npy")
+    assert d.dtype == np.float64 and d.shape == (8, 2, 21, 2)
+    assert rel_l2(d[..., 0] + 1j * d[..., 1], oracle_simulate(synth.make_config("C1"))) < TOL
 
 
 def _band_block(name, f0, f1, ntimes, seed=0):
@@ -700,7 +722,7 @@ def test_bench_takes_the_rccl_code_path_with_one_rank(gpu):
     env = dict(os.environ, FFTVIS_BENCH_FORCE_DIST="1", FFTVIS_BENCH_NO_PMC_CHECK="1")
     env.pop("FFTVIS_BENCH_BACKEND", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--nsrc", "3000", "--nfreq", "8",
-                        "--ntimes", "2", "--steps", "1", "--warmup", "1", "--cpu-seconds", "1"],
+                        "--ntimes", "2", "--steps", "1", "--warmup", "1", "--full", "--cpu-seconds", "1"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

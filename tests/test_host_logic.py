@@ -196,6 +196,32 @@ def test_benchmark_arrays_are_lattices():
         assert len(ants) == nant and ok
 
 
+def test_bench_dumped_outputs_are_whole_or_a_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs`: a block within the budget is written whole (complex -> trailing (re, im) axis, the
+    engine's real type); a larger one as a seeded sample whose flat indices are written beside it, the same on every
+    run, and the files stay within the budget.  CPU tensors stand in for the device's."""
+    import torch
+
+    import bench
+
+    small = torch.randn(8, 2, 21, dtype=torch.complex128)
+    big = torch.randn(16, 4, 2, 2, 1021, dtype=torch.complex128)
+    f32 = torch.randn(3, 5, dtype=torch.complex64)
+    budget = 1 << 20
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), [("vis", small), ("big", big), ("f32", f32)], budget)
+    assert sorted(os.listdir(tmp_path / "a")) == ["big_sample.npy", "big_sample_index.npy", "f32.npy", "vis.npy"]
+    v = np.load(tmp_path / "a" / "vis.npy")
+    assert v.dtype == np.float64 and np.array_equal(v[..., 0] + 1j * v[..., 1], small.numpy())
+    f = np.load(tmp_path / "a" / "f32.npy")
+    assert f.dtype == np.float32 and f.shape == (3, 5, 2)
+    s, i = np.load(tmp_path / "a" / "big_sample.npy"), np.load(tmp_path / "a" / "big_sample_index.npy")
+    assert i.dtype == np.float64 and np.all(np.diff(i) > 0) and len(i) > 0.9 * budget // 24
+    assert np.array_equal(torch.view_as_real(big).reshape(-1, 2).numpy()[i.astype(np.int64)], s)
+    assert (s.nbytes + i.nbytes) <= budget
+    assert np.array_equal(i, np.load(tmp_path / "b" / "big_sample_index.npy"))
+
+
 def test_round4_bench_arrays_are_what_their_names_say():
     """`bench.py --array scattered` / `--workload C3z`: the scattered array has 350 antennas inside HERA-350's
     footprint, is flat, is NOT a lattice and repeats no baseline vector; the height-scattered HERA-350 exceeds the

@@ -3,7 +3,7 @@
 # python tools/refresh_profiles.py rNN copies the summaries into profiles/).
 R=$GRAFT_REPO_ROOT; cd /tmp; export TMPDIR=/tmp
 O=$R/gpurun_out/final; rm -rf $O; mkdir -p $O
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 Q="--no-cpu-baseline --no-e2e --no-extras"
 # ---- bench lines: the default (driver) workload C3, then the others, clearly named -----------------------
 FFTVIS_BENCH_NO_PMC_CHECK=1 $B > $O/bench_c3.json 2>$O/bench_c3.err &&
@@ -31,7 +31,7 @@ echo rank-blocks rc=$?
 # ---- rocprofv3 kernel stats of the same commands (no breakdown step: only launches shaped like the timed region) --
 prof() { # tag, [env...] -- bench args...
   t=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$t -- python3 $R/bench.py "$@" --no-breakdown $Q > $O/prof_$t.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$t -- $B "$@" --no-breakdown $Q > $O/prof_$t.log 2>&1
 }
 prof c3 --steps 2 --warmup 1 && prof c2 --workload C2 && prof c4slice --workload C4 --nfreq 32 --ntimes 2 --steps 1 --warmup 1 &&
 prof c3type1 --path type1 --steps 1 --warmup 1 && prof c3scattered --array scattered --steps 1 --warmup 1 && prof c3z --workload C3z --steps 2 --warmup 1
@@ -45,7 +45,7 @@ echo prof-one-lane rc=$?
 # ---- HBM traffic: FETCH_SIZE and WRITE_SIZE in separate passes (kernel trace only), full-size launches, ONE stream ----
 pmc() { # tag, counter, bench args...
   t=$1; c=$2; shift; shift
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_${c}_$t -- python3 $R/bench.py "$@" --steps 1 --warmup 1 --no-breakdown $Q > $O/pmc_${c}_$t.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_${c}_$t -- $B "$@" --steps 1 --warmup 1 --no-breakdown $Q > $O/pmc_${c}_$t.log 2>&1
 }
 for c in FETCH_SIZE WRITE_SIZE; do
   pmc c3 $c --ntimes 1 && pmc c2 $c --workload C2 && pmc c4slice $c --workload C4 --nfreq 32 --ntimes 1 && pmc c3type1 $c --path type1 --ntimes 1 &&

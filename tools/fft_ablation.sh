@@ -15,7 +15,7 @@ done
 echo "# bench.py (C3) --steps 2 --warmup 1: ms per step and per-launch family times, product build vs diagnostic builds"
 for a in 0 1 2 3 7; do
   L=""; [ $a != 0 ] && L=$R/scratch/lib_abl$a.so
-  FFTVIS_HIP_LIB=$L python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-e2e > $O/abl_$a.json 2>/dev/null
+  FFTVIS_HIP_LIB=$L python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-e2e > $O/abl_$a.json 2>/dev/null
   python3 - <<P
 import json
 d = json.load(open("$O/abl_$a.json"))
