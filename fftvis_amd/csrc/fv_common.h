@@ -77,6 +77,13 @@ struct DevBuf {
         dev_bytes_held() += cap;
         dev_bytes_on(dev) += cap;
     }
+    void release() {  // gives the memory back now (a later reserve allocates again)
+        if (p) FV_HIP(hipFree(p));
+        dev_bytes_held() -= cap;
+        if (cap) dev_bytes_on(dev) -= cap;
+        p = nullptr;
+        cap = 0;
+    }
     template <typename U>
     U *as() const {
         return reinterpret_cast<U *>(p);

@@ -712,6 +712,155 @@ __global__ void k_strengths(StrengthArgs a, const int *__restrict__ Mp, const in
 }
 
 // ---------------------------------------------------------------------------------------------
+// Adjoint (fv_sim_run_adjoint; DESIGN.md "Adjoint").  Per (time, frequency group, beam pair) the forward writes
+//     out[k, r] = cj_k( sum_j c_jr exp(i nu s_k b_k . x_j) ),   s_k = -1 and cj_k = conj for a flipped baseline,
+// so with H = cj_k(G) the transpose is a type-3 transform with the roles swapped:
+//     Z_jr = sum_u q_ur exp(i (s_u b_u) . (nu x_j)),   q_ur = sum of conj(H_kr) over the baselines k of run u,
+// sources at the pair's distinct sign-adjusted vectors, targets at the directions scaled per channel, and
+//     Re <A F, G> = sum_j Re sum_r c_jr(F) Z_jr.
+// ---------------------------------------------------------------------------------------------
+struct AdjStrengthArgs {
+    int64_t nu;           // runs of the pair's list (NUFFT sources)
+    int nfg, tpol;
+    int64_t g_f_stride;   // elements between two channels of the G block
+    int64_t pol_off[4];   // output slot of product r (the forward's layout)
+    int transpose_flipped;
+};
+
+// 16 lanes <-> (run u, channel fg), u fastest: q is (nfg tpol, nu) row-major, the layout Nufft3::load_strengths reads.
+// The run's members are dealt over the 16 lanes (a redundant vector of HERA-350 has up to a few hundred) and the lanes'
+// sums combined in a fixed butterfly: the result does not depend on timing.
+constexpr int ADJ_GROUP = 16;
+template <typename T>
+__global__ void k_adj_strengths(AdjStrengthArgs a, const cplx<T> *__restrict__ g, const int *__restrict__ idx,
+                                const signed char *__restrict__ flip, const int *__restrict__ ustart,
+                                cplx<T> *__restrict__ q, int *__restrict__ err_nan) {
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ADJ_GROUP;
+    const int lg = threadIdx.x & (ADJ_GROUP - 1);
+    if (i >= a.nu * a.nfg) return;  // (whole groups exit together)
+    const int64_t u = i % a.nu;
+    const int fg = (int)(i / a.nu);
+    const int64_t m0 = ustart ? ustart[u] : u, m1 = ustart ? ustart[u + 1] : u + 1;
+    const cplx<T> *gf = g + (int64_t)fg * a.g_f_stride;
+    double sr[4] = {0.0, 0.0, 0.0, 0.0}, si[4] = {0.0, 0.0, 0.0, 0.0};
+    int bad = 0;
+    for (int64_t m = m0 + lg; m < m1; m += ADJ_GROUP) {  // the baselines that share this vector
+        const int64_t k = idx ? idx[m] : m;
+        const bool neg = flip && flip[m];
+        for (int r = 0; r < a.tpol; ++r) {
+            const int rt = a.transpose_flipped && neg && a.tpol == 4 ? (r & 1) * 2 + (r >> 1) : r;
+            const cplx<T> v = gf[a.pol_off[rt] + k];
+            bad += !(v.re == v.re && v.im == v.im);
+            sr[r] += (double)v.re;                      // conj(H): G itself when flipped, conj(G) otherwise
+            si[r] += neg ? (double)v.im : -(double)v.im;
+        }
+    }
+    for (int r = 0; r < a.tpol; ++r)
+        for (int off = ADJ_GROUP / 2; off > 0; off >>= 1) {
+            sr[r] += __shfl_xor(sr[r], off, 64);
+            si[r] += __shfl_xor(si[r], off, 64);
+        }
+    if (lg < a.tpol) {
+        const int r = lg;
+        double vr = sr[0], vi = si[0];
+        for (int rr = 1; rr < 4; ++rr)
+            if (r == rr) {
+                vr = sr[rr];
+                vi = si[rr];
+            }
+        q[((int64_t)fg * a.tpol + r) * a.nu + u] = {(T)vr, (T)vi};
+    }
+    if (bad) atomicAdd(err_nan, bad);
+}
+
+struct AdjAccArgs {
+    int64_t M;           // capacity of the per-time arrays (stride of z); live count is *Mp
+    int nfg, f_first;    // channels of the group, catalog index of its first
+    int f_base, nfa;     // first channel of the run and channels the accumulator holds
+    int polarized, pol_sky, same_beam;
+    BeamDesc bi, bj;
+};
+
+// Transpose of strength_eval, thread <-> (compacted source jc, channel fg), jc fastest.  acc (fp64, this lane's) is
+// (nsrc, nfa) for Stokes I skies, (nsrc, nfa, 2, 2) complex for coherency skies: the gradient with respect to the
+// coherency, Re <A C, G> = Re sum conj(acc) C.  src_idx is injective within a slice: plain read-modify-write.
+template <typename T, int ORD>
+__global__ void k_adj_accumulate(AdjAccArgs a, const int *__restrict__ Mp, const int *__restrict__ src_idx,
+                                 const T *__restrict__ az, const T *__restrict__ za, const double *__restrict__ freqs,
+                                 const cplx<T> *__restrict__ z, double *__restrict__ acc) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.M * a.nfg) return;
+    const int64_t jc = i % a.M;
+    const int fg = (int)(i / a.M);
+    if (jc >= (int64_t)*Mp) return;
+    const int fidx = a.f_first + fg;
+    const double freq = freqs[fidx];
+    const int64_t js = src_idx[jc];
+    const double azv = az[jc], zav = za[jc];
+    const int tp = a.polarized ? 4 : 1;
+    cplx<double> Z[4];
+    for (int r = 0; r < tp; ++r) {
+        const cplx<T> v = z[((int64_t)fg * tp + r) * a.M + jc];
+        Z[r] = {(double)v.re, (double)v.im};
+    }
+    const int64_t slot = js * a.nfa + (fidx - a.f_base);
+    if (!a.polarized) {  // c = sqrt(B_i B_j) I, principal root as in the forward
+        const double bi = eval_power<ORD>(a.bi, fidx, freq, azv, zav);
+        const double bj = a.same_beam ? bi : eval_power<ORD>(a.bj, fidx, freq, azv, zav);
+        const cplx<double> beta = csqrt_principal(cplx<double>{bi * bj, 0.0});
+        acc[slot] += beta.re * Z[0].re - beta.im * Z[0].im;
+        return;
+    }
+    cplx<double> Ai[4], Aj[4];
+    eval_jones<ORD>(a.bi, fidx, freq, azv, zav, Ai);
+    if (a.same_beam) {
+        for (int r = 0; r < 4; ++r) Aj[r] = Ai[r];
+    } else {
+        eval_jones<ORD>(a.bj, fidx, freq, azv, zav, Aj);
+    }
+    if (!a.pol_sky) {  // c_r = I (Ai^H Aj)_r
+        cplx<double> o[4];
+        coh_AhB_flux(Ai, Aj, 1.0, o);
+        double s = 0.0;
+        for (int r = 0; r < 4; ++r) s += o[r].re * Z[r].re - o[r].im * Z[r].im;
+        acc[slot] += s;
+        return;
+    }
+    // c_ap = sum_{b,k} conj(Fi[b][a]) C[b][k] Fj[k][p] on the flipped Jones F:  sum_ap c_ap Z_ap = sum_bk C_bk W_bk,
+    // W_bk = sum_ap conj(Fi[b][a]) Fj[k][p] Z_ap;  the coherency gradient is conj(W)
+    const cplx<double> Fi[4] = {Ai[2], Ai[3], Ai[0], Ai[1]};
+    const cplx<double> Fj[4] = {Aj[2], Aj[3], Aj[0], Aj[1]};
+    double *o = acc + slot * 8;
+    for (int b = 0; b < 2; ++b)
+        for (int k = 0; k < 2; ++k) {
+            cplx<double> W = {0.0, 0.0};
+            for (int a_ = 0; a_ < 2; ++a_)
+                for (int p = 0; p < 2; ++p) W = cadd(W, cmul(cmul(cconj(Fi[b * 2 + a_]), Fj[k * 2 + p]), Z[a_ * 2 + p]));
+            o[2 * (b * 2 + k)] += W.re;
+            o[2 * (b * 2 + k) + 1] -= W.im;
+        }
+}
+
+// The lanes' accumulators summed in lane order (bitwise reproducible for a given lane count) and added to gflux
+// (nsrc, nfreq[, 2, 2]) in the run's precision, channels [f_base, f_base + nfa).
+struct AdjReduceArgs {
+    const double *acc[4];
+    int nl, nfa, f_base, nfreq, comps;  // comps: reals per (source, channel), 1 or 8
+    int64_t nsrc;
+};
+template <typename T>
+__global__ void k_adj_reduce(AdjReduceArgs a, T *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= a.nsrc * a.nfa * a.comps) return;
+    double s = 0.0;
+    for (int l = 0; l < a.nl; ++l) s += a.acc[l][e];
+    const int64_t js = e / ((int64_t)a.nfa * a.comps);
+    const int64_t rem = e - js * a.nfa * a.comps;
+    const int64_t o = (js * a.nfreq + a.f_base) * a.comps + rem;
+    out[o] = (T)((double)out[o] + s);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Type-1 path (lattice arrays): cpu_nufft2d_type1 (cpu/nufft.py:120-175), set-up
 // cpu_simulate.py:661-681, per-slice :964-965,990-992,259-269.
 // Visibility of the integer baseline (bx, by) at frequency nu is mode (bx, by) of a type-1
@@ -1192,6 +1341,8 @@ struct SimBase {
                            const int *ant2) = 0;
     virtual void set_chunking(int nchunks, double source_buffer) = 0;
     virtual void run(int t0, int t1, int f0, int f1, void *out, int out_on_device) = 0;
+    virtual void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                             int gflux_on_device, int accumulate) = 0;
     // Host destination of the next run (fv_sim_run_into): `out` is then a block INSIDE a larger array -- channel f of
     // the block starts f * out_f_stride elements after `out` (0: the block is contiguous) -- and with out_shared other
     // processes write the rest of that array (a sharded run's ranks filling one shared result): the pinning helper must
@@ -1273,6 +1424,10 @@ class Sim : public SimBase {
         bool mirror = false;   // this run also gathers at the mirror targets -b (exact eigenbeam (l, k) terms)
         const double *box_c() const { return herm || mirror ? zero3 : btc; }
         const double *box_B() const { return herm || mirror ? Bs : B; }
+        // the adjoint's NUFFT sources: the first member's sign-adjusted vector of every run, (dim, nu) T, built for
+        // target-data version adj_serial
+        std::unique_ptr<DevBuf> adj_pos;
+        int64_t adj_serial = -1;
     };
     static constexpr double zero3[3] = {0.0, 0.0, 0.0};
     std::vector<Pair> pairs;
@@ -1306,6 +1461,10 @@ class Sim : public SimBase {
         int64_t binned_serial = -1;
         int binned_ti_l[2] = {-1, -1};  // the same for nufft_l
         int64_t binned_serial_l[2] = {-1, -1};
+        // adjoint (run_adjoint): the transform with the roles swapped, its strengths, its values at the directions and
+        // this lane's fp64 gradient accumulator
+        std::unique_ptr<Nufft3<T>> adj;
+        DevBuf d_adj_q, d_adj_z, d_adj_acc;
     };
     Lane lanes[4];  // [2], [3]: second pair of the gang mode (see run())
     int lane_mode = -1;       // 0 one stream per lane, 1 pipelined, 2 pipelined gangs: what the lanes last ran as
@@ -1321,11 +1480,14 @@ class Sim : public SimBase {
     };
     hipEvent_t ev_start = nullptr;
     DevBuf d_out, d_mhist;
+    DevBuf d_adj_g, d_adj_gf;  // adjoint: host G block / host gradient staged on the device
     // sticky device-side error counters, read at every host synchronisation point (check_errors):
     // [0] sources outside the planned box or with NaN coordinates (k_bin_count), [1] type-1 entries
     // dropped because the entry buffers overflowed (k_t1_bin), [2] above-horizon sources that did not
-    // fit source_buffer x chunk size (k_horizon_compact), [3] footprint columns missing from a column plan (k_interp)
+    // fit source_buffer x chunk size (k_horizon_compact), [3] footprint columns missing from a column plan (k_interp),
+    // [4] NaN entries of the adjoint's visibility-shaped input (k_adj_strengths)
     DevBuf d_err;
+    static constexpr int NERR = 5;
     std::vector<std::pair<int, double>> mhist_log;  // (time index, transforms spread) per processed time
 
     // stats / timing
@@ -1433,14 +1595,15 @@ class Sim : public SimBase {
             FV_HIP(hipEventCreateWithFlags(&L.heavy_done, hipEventDisableTiming));
         }
         FV_HIP(hipEventCreateWithFlags(&ev_start, hipEventDisableTiming));
-        d_err.reserve(4 * sizeof(int));
-        FV_HIP(hipMemsetAsync(d_err.p, 0, 4 * sizeof(int), stream));
+        d_err.reserve(NERR * sizeof(int));
+        FV_HIP(hipMemsetAsync(d_err.p, 0, NERR * sizeof(int), stream));
         for (int i = 0; i < 9; ++i) rplane.m[i] = (i % 4 == 0) ? 1.0 : 0.0;
     }
     ~Sim() override {
         (void)hipSetDevice(device);
         for (Lane &L : lanes) {
             L.nufft.reset();
+            L.adj.reset();
             L.nufft_l[0].reset();
             L.nufft_l[1].reset();
             if (L.done) (void)hipEventDestroy(L.done);
@@ -2256,6 +2419,42 @@ class Sim : public SimBase {
         }
     }
 
+    // Fine-grid cells per transform at sigma = 2 for channels [f0, f1): source box X, and in every dimension the largest
+    // target box half-width over the pairs, box_B(p)[d] (the grid depends on the product of the two extents only, so the
+    // adjoint, whose roles are swapped, sizes its grids from the same product).
+    template <class BoxOf>
+    double cells_at_sigma2(const double *X, int D, int f0, int f1, BoxOf box_B) const {
+        const KerParams k2 = make_kernel(eps, 2.0);
+        double fmax = 0, cells2 = 1.0;
+        for (int f = f0; f < f1; ++f) fmax = std::max(fmax, std::fabs(freqs[f]));
+        for (int d = 0; d < D; ++d) {
+            DimGeom g;
+            g.X = X[d];
+            double Bm = 0;
+            for (const Pair &p : pairs) Bm = std::max(Bm, box_B(p)[d]);
+            g.B = Bm;
+            set_dim_geom(g, 2.0, k2.w, fmax, d == D - 1);
+            cells2 *= g.n2;
+        }
+        return cells2;
+    }
+    // The "auto" upsampling factor (fv_sim_create upsampfac = 0) of a run whose grid has cells2 cells at sigma = 2 and
+    // whose transforms spread and gather `points` points.
+    double auto_sigma(double cells2, double points, int D) const {
+        // accuracy floor of sigma = 1.25: the kernel transform falls by ~e^{-w/2} per dimension across
+        // the band and rounding is amplified by that factor at band-edge targets -- ~1e-8 in fp64; in
+        // fp32 it matches sigma = 2 down to eps = 1e-4 (HERA-350, top of the band: worst baseline
+        // 5.8e-4 vs 9.9e-4, rel. l2 4.1e-5 vs 6.4e-5) and falls behind at 1e-5
+        // (3-D: one more dimension of amplification -- 4e-8 seen at eps 2.5e-9 -- so ten times higher)
+        const double eps_floor = (sizeof(T) == 8 ? 1e-8 : 1e-4) * (D == 3 ? 10.0 : 1.0);
+        // measured (2-D): 8192^2 grids win with 1.25 from 1e5 sources (3.06 -> 1.57 s) up to 4e6 per
+        // time step (31.1 -> 29.7 ms per 16-channel slice, ~30 cells per point); a 1024 x 512 grid
+        // loses slightly even with 1e3 sources (its kernels are latency-bound, a smaller grid buys
+        // little): so large grids only, and not when points outnumber the cells they save
+        const double per_point = D == 2 ? 30.0 : 200.0;
+        return eps >= eps_floor && cells2 >= 4.0e6 && cells2 >= per_point * points ? 1.25 : 2.0;
+    }
+
     // Split [f0, f1) into groups of consecutive channels sharing one fine-grid geometry (sized
     // for the group's top frequency).  Small grids are launch-bound, so they tolerate a wide
     // frequency ratio (more wasted cells, far fewer launches); large grids are HBM-bound and get
@@ -2659,33 +2858,10 @@ class Sim : public SimBase {
             if (p.n) tg_max = std::max(tg_max, p.herm ? 2 : tpol);
         double sigma = this->sigma;
         if (sigma == 0.0) {
-            const KerParams k2 = make_kernel(eps, 2.0);
-            double fmax = 0, cells2 = 1.0;
-            for (int f = f0; f < f1; ++f) fmax = std::max(fmax, std::fabs(freqs[f]));
             int64_t nmax = 0;
             for (const Pair &p : pairs) nmax = std::max<int64_t>(nmax, p.n);
-            for (int d = 0; d < D; ++d) {
-                DimGeom g;
-                g.X = X[d];
-                double Bm = 0;
-                for (const Pair &p : pairs) Bm = std::max(Bm, p.box_B()[d]);
-                g.B = Bm;
-                set_dim_geom(g, 2.0, k2.w, fmax, d == D - 1);
-                cells2 *= g.n2;
-            }
-            const double points = 0.5 * (double)nsrc + (double)nmax;
-            // accuracy floor of sigma = 1.25: the kernel transform falls by ~e^{-w/2} per dimension across
-            // the band and rounding is amplified by that factor at band-edge targets -- ~1e-8 in fp64; in
-            // fp32 it matches sigma = 2 down to eps = 1e-4 (HERA-350, top of the band: worst baseline
-            // 5.8e-4 vs 9.9e-4, rel. l2 4.1e-5 vs 6.4e-5) and falls behind at 1e-5
-            // (3-D: one more dimension of amplification -- 4e-8 seen at eps 2.5e-9 -- so ten times higher)
-            const double eps_floor = (sizeof(T) == 8 ? 1e-8 : 1e-4) * (D == 3 ? 10.0 : 1.0);
-            // measured (2-D): 8192^2 grids win with 1.25 from 1e5 sources (3.06 -> 1.57 s) up to 4e6 per
-            // time step (31.1 -> 29.7 ms per 16-channel slice, ~30 cells per point); a 1024 x 512 grid
-            // loses slightly even with 1e3 sources (its kernels are latency-bound, a smaller grid buys
-            // little): so large grids only, and not when points outnumber the cells they save
-            const double per_point = D == 2 ? 30.0 : 200.0;
-            sigma = eps >= eps_floor && cells2 >= 4.0e6 && cells2 >= per_point * points ? 1.25 : 2.0;
+            const double cells2 = cells_at_sigma2(X, D, f0, f1, [](const Pair &p) { return p.box_B(); });
+            sigma = auto_sigma(cells2, 0.5 * (double)nsrc + (double)nmax, D);
         }
         sigma_run = sigma;
         st[10] = sigma;
@@ -3185,6 +3361,258 @@ class Sim : public SimBase {
         }
     }
 
+    // ---- adjoint: gflux += A^T G, A = this handle's forward map (run) from fluxes to visibilities -------------------
+    // One transposed slice per (time, frequency group, beam pair): k_adj_strengths folds the pair's baselines of the G
+    // block onto its distinct vectors, a type-3 transform with the roles swapped takes them to the directions (2-D, or the
+    // plain 3-D transform for non-coplanar arrays; lattice arrays take it too), k_adj_accumulate contracts with the beams.
+    // Time steps alternate between the lanes (FFTVIS_HIP_LANES, 1 or 2), each with its own fp64 accumulator.
+    void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux, int gflux_on_device,
+                     int accumulate) override {
+        FV_HIP(hipSetDevice(device));
+        FV_REQUIRE(nbasis == 0, "the adjoint does not cover basis beams (set_basis / beam_coefs)");
+        FV_REQUIRE(nsrc >= 0 && !rots.empty() && !freqs.empty() && nbls > 0 && !pairs.empty(),
+                   "engine not fully configured");
+        FV_REQUIRE(0 <= t0 && t0 <= t1 && t1 <= (int)rots.size(), "time range");
+        FV_REQUIRE(0 <= f0 && f0 <= f1 && f1 <= (int)freqs.size(), "freq range");
+        FV_REQUIRE((int)freqs.size() == nfreq_cat, "flux frequency axis != freqs");
+        for (const Beam &b : beams) FV_REQUIRE(b.kind >= 0, "beam not set");
+        const int nt = t1 - t0, nf = f1 - f0;
+        const int64_t per_tf = (int64_t)tpol * nbls;
+        // whatever an earlier run queued (a device-output forward run leaves its lanes busy) is finished first: the lanes'
+        // scratch is reused here; the next forward run starts its lane rotation afresh
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipStreamSynchronize(prep_stream));
+        if (copy_stream) FV_HIP(hipStreamSynchronize(copy_stream));
+        for (int li = 1; li < 4; ++li)
+            if (lanes[li].stream && lanes[li].own_stream) FV_HIP(hipStreamSynchronize(lanes[li].stream));
+        for (Lane &L : lanes) {
+            L.heavy_pending = false;
+            L.binned_ti = -1;
+            L.binned_ti_l[0] = L.binned_ti_l[1] = -1;
+        }
+        lane_mode = -1;
+        // the forward's redundant-baseline runs, compared in all three components (a run's vector is its first member's)
+        wt_K = 0;
+        {
+            double fall = 0;
+            for (double f : freqs) fall = std::max(fall, std::fabs(f));
+            const double tol = 1e-3 * eps / (2.0 * M_PI * std::max(fall, 1.0));
+            for (Pair &p : pairs) build_unique(p, tol);
+        }
+        const int D = dim();
+        run_D = D;
+        // box of the directions x = 2 pi R topo (R: the plane rotation, or the lattice basis^T of a type-1 array)
+        double xc[3], X[3];
+        if (type1) {
+            for (int d = 0; d < 3; ++d) {
+                const double *r = rplane.m + 3 * d;
+                xc[d] = 0.0;
+                X[d] = 2.0 * M_PI * std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]) * (1.0 + 1e-9) + 1e-300;
+            }
+        } else {
+            source_box(xc, X);
+        }
+        // the NUFFT sources of every pair
+        for (Pair &p : pairs) {
+            if (p.n == 0 || (p.adj_pos && p.adj_serial == targets_serial)) continue;
+            const int64_t nu = p.ustart ? p.nu : p.n;
+            std::vector<T> pos((size_t)D * nu);
+            for (int64_t u = 0; u < nu; ++u) {
+                const int64_t m = p.ustart ? p.h_ustart[u] : u;
+                const double sg = p.h_flip[m] ? -1.0 : 1.0;
+                for (int d = 0; d < D; ++d) pos[(size_t)d * nu + u] = (T)(sg * h_bls[(size_t)d * nbls + p.h_idx[m]]);
+            }
+            p.adj_pos.reset(new DevBuf());
+            upload(*p.adj_pos, pos.data(), sizeof(T) * pos.size(), 0);
+            p.adj_serial = targets_serial;
+        }
+        // the G block on the device
+        const size_t g_bytes = sizeof(cplx<T>) * (size_t)nf * nt * per_tf;
+        const cplx<T> *dg = (const cplx<T> *)gvis;
+        if (!gvis_on_device) {
+            upload(d_adj_g, gvis, g_bytes, 0);
+            dg = d_adj_g.as<cplx<T>>();
+        }
+        // grid size (same product of extents as the forward's), upsampling factor and frequency groups
+        // (the forward's rule for "auto", with the adjoint's own point count: its sources are the distinct vectors)
+        int64_t nu_max = 1;
+        for (const Pair &p : pairs) nu_max = std::max<int64_t>(nu_max, p.ustart ? p.nu : p.n);
+        const double cells2 = cells_at_sigma2(X, D, f0, f1, [](const Pair &p) { return (const double *)p.B; });
+        const double sigma_a = this->sigma != 0.0 ? this->sigma : auto_sigma(cells2, 0.5 * (double)nsrc + (double)nu_max, D);
+        const double cells_top = 2.0 * cells2 * (sigma_a == 2.0 ? 1.0 : std::pow(1.25 / 2.0, D));
+        const int nch = (int)std::max<int64_t>(1, std::min<int64_t>(src_chunks, nsrc));
+        const int64_t csz = std::max<int64_t>(cdiv(nsrc, nch), 1);
+        const int64_t cap = std::max<int64_t>((int64_t)std::ceil(csz * source_buffer), 1);
+        const int nblk = (int)cdiv(csz, 256);
+        reserve_mhist(sizeof(int) * rots.size() * std::max(1, src_chunks));
+        const char *el = std::getenv("FFTVIS_HIP_LANES");
+        const int nlanes = std::max(1, std::min(2, std::min(el ? std::atoi(el) : 2, std::max(nt, 1))));
+        const int comps = pol_sky ? 8 : 1;
+        // Channel blocks: a lane's accumulator holds nsrc x (channels of a block) x comps doubles, at most
+        // FFTVIS_HIP_ADJ_ACC_BYTES (default 256 MiB); every block walks the time steps once and is reduced into gflux.
+        const char *eab = std::getenv("FFTVIS_HIP_ADJ_ACC_BYTES");
+        const double acc_max = eab ? std::atof(eab) : 256.0 * 1024 * 1024;
+        const int nfb = (int)std::max<double>(1.0, std::min<double>(nf, std::floor(acc_max / (8.0 * comps * std::max<int64_t>(nsrc, 1)))));
+        struct FBlock {
+            int b0, b1;
+            std::vector<std::pair<int, int>> groups;
+        };
+        std::vector<FBlock> fblocks;
+        int nfg_max = 1;
+        for (int b0 = f0; b0 < f1; b0 += nfb) {
+            FBlock fb{b0, std::min(f1, b0 + nfb), {}};
+            fb.groups = freq_groups(fb.b0, fb.b1, cells_top, tpol);
+            for (const auto &grp : fb.groups) nfg_max = std::max(nfg_max, grp.second - grp.first);
+            fblocks.push_back(std::move(fb));
+        }
+        const size_t acc_bytes = sizeof(double) * (size_t)std::max<int64_t>(nsrc * std::min(nf, nfb) * comps, 1);
+        for (int li = 0; li < nlanes; ++li) {
+            Lane &L = lanes[li];
+            if (!L.adj || L.adj->dim != D || L.adj->sigma != sigma_a || L.adj->eps != eps)
+                L.adj.reset(new Nufft3<T>(D, eps, sigma_a, L.stream));
+            L.adj->stream = L.stream;
+            L.adj->err_oob = d_err.as<int>();
+            L.adj->disc_radius = 0.0;  // its sources are baselines
+            L.adj->transpose_flipped = false;
+            L.adj->arm_columns(nullptr, nullptr, tpol, 0);
+            L.d_xyz.reserve(sizeof(T) * 3 * cap);
+            L.d_az.reserve(sizeof(T) * cap);
+            L.d_za.reserve(sizeof(T) * cap);
+            L.d_srcidx.reserve(sizeof(int) * cap);
+            L.d_blockcnt.reserve(sizeof(int) * (nblk + 1));
+            L.d_blockoff.reserve(sizeof(int) * (nblk + 1));
+            L.d_adj_q.reserve(sizeof(cplx<T>) * (size_t)nu_max * nfg_max * tpol);
+            L.d_adj_z.reserve(sizeof(cplx<T>) * (size_t)cap * nfg_max * tpol);
+            L.d_adj_acc.reserve(acc_bytes);
+        }
+        // gflux on the device, zeroed or holding what the call adds to (main stream: before every reduction)
+        const size_t gf_bytes = sizeof(T) * (size_t)nsrc * nfreq_cat * comps;
+        T *dgf = (T *)gflux;
+        if (!gflux_on_device) {
+            d_adj_gf.reserve(std::max<size_t>(gf_bytes, 16));
+            dgf = d_adj_gf.as<T>();
+            if (accumulate && gf_bytes) FV_HIP(hipMemcpyAsync(dgf, gflux, gf_bytes, hipMemcpyHostToDevice, stream));
+        }
+        if (!accumulate && gf_bytes) FV_HIP(hipMemsetAsync(dgf, 0, gf_bytes, stream));
+        int64_t pol_off[4] = {0, 0, 0, 0}, z_off[16] = {0};
+        for (int r = 0; r < tpol; ++r) {
+            pol_off[r] = (int64_t)((r % 2) * 2 + r / 2) * nbls;  // the forward's output slots
+            z_off[r] = (int64_t)r * cap;
+        }
+        const int ord = beam_order == 3 ? 3 : beam_order == 1 ? 1 : 0;
+        for (size_t bi = 0; bi < fblocks.size(); ++bi) {
+            const FBlock &fb = fblocks[bi];
+            const int nfa = fb.b1 - fb.b0;
+            for (int li = 0; li < nlanes; ++li) {
+                if (bi > 0) {  // the previous block's reduction has read this accumulator
+                    FV_HIP(hipEventRecord(ev_start, stream));
+                    FV_HIP(hipStreamWaitEvent(lanes[li].stream, ev_start, 0));
+                }
+                FV_HIP(hipMemsetAsync(lanes[li].d_adj_acc.p, 0, sizeof(double) * (size_t)std::max<int64_t>(nsrc * nfa * comps, 1),
+                                      lanes[li].stream));
+            }
+            for (int t = t0; t < t1; ++t) {
+                Lane &L = lanes[(t - t0) % nlanes];
+                const hipStream_t ls = L.stream;
+                Nufft3<T> &P = *L.adj;
+                for (int ch = 0; ch < nch; ++ch) {
+                    const int64_t s0 = (int64_t)ch * csz, sn = std::min<int64_t>(csz, nsrc - s0);
+                    if (nsrc == 0 || sn <= 0) continue;  // nothing above the horizon: nothing to add
+                    const int *Mp = horizon_step(L, t, cap, nblk, ls, s0, sn, (int64_t)t * nch + ch);
+                    const T *xyz = L.d_xyz.template as<T>();
+                    for (const auto &grp : fb.groups) {
+                        const int fa = grp.first, nfg = grp.second - grp.first;
+                        double smax = 0;
+                        for (int f = fa; f < grp.second; ++f) smax = std::max(smax, std::fabs(freqs[f]));
+                        for (const Pair &pr : pairs) {
+                            if (pr.n == 0) continue;
+                            const int64_t nu = pr.ustart ? pr.nu : pr.n;
+                            const T *pos = pr.adj_pos->template as<T>();
+                            // sources: the pair's distinct vectors; targets: the directions, scaled per channel
+                            P.set_geometry(pr.btc, pr.B, xc, X, smax);
+                            P.set_sources(nu, pos, pos + nu, D > 2 ? pos + 2 * nu : nullptr);
+                            AdjStrengthArgs sa{};
+                            sa.nu = nu;
+                            sa.nfg = nfg;
+                            sa.tpol = tpol;
+                            sa.g_f_stride = (int64_t)nt * per_tf;
+                            for (int r = 0; r < 4; ++r) sa.pol_off[r] = pol_off[r];
+                            sa.transpose_flipped = !reference_compat;
+                            cplx<T> *q = L.d_adj_q.template as<cplx<T>>();
+                            hipLaunchKernelGGL(k_adj_strengths<T>, dim3((unsigned)cdiv(nu * nfg * ADJ_GROUP, 256)), dim3(256), 0, ls, sa,
+                                               dg + ((int64_t)(fa - f0) * nt + (t - t0)) * per_tf,
+                                               pr.trivial ? nullptr : pr.idx->template as<int>(),
+                                               pr.trivial ? nullptr : pr.flip->template as<signed char>(),
+                                               pr.ustart ? pr.ustart->template as<int>() : nullptr, q, d_err.as<int>() + 4);
+                            P.load_strengths(q, nfg * tpol, tpol, d_freqs.as<double>() + fa);
+                            P.spread(nfg * tpol);
+                            P.fft(nfg * tpol);
+                            cplx<T> *zb = L.d_adj_z.template as<cplx<T>>();
+                            // every slot of the compacted arrays is a target (the live count stays on the device): slots
+                            // past it are computed and never read
+                            P.interp(cap, xyz, xyz + cap, D > 2 ? xyz + 2 * cap : nullptr, nullptr, nullptr,
+                                     d_freqs.as<double>() + fa, nfg, tpol, zb, (int64_t)tpol * cap, 1, z_off, false);
+                            AdjAccArgs aa{};
+                            aa.M = cap;
+                            aa.nfg = nfg;
+                            aa.f_first = fa;
+                            aa.f_base = fb.b0;
+                            aa.nfa = nfa;
+                            aa.polarized = polarized;
+                            aa.pol_sky = pol_sky;
+                            aa.same_beam = pr.bi == pr.bj;
+                            aa.bi = desc(pr.bi);
+                            aa.bj = desc(pr.bj);
+                            hipLaunchKernelGGL((ord == 3 ? k_adj_accumulate<T, 3> : ord == 1 ? k_adj_accumulate<T, 1> : k_adj_accumulate<T, 0>),
+                                               dim3((unsigned)cdiv(cap * nfg, 256)), dim3(256), 0, ls, aa, Mp,
+                                               L.d_srcidx.template as<int>(), L.d_az.template as<T>(), L.d_za.template as<T>(),
+                                               d_freqs.as<double>(), zb, L.d_adj_acc.template as<double>());
+                        }
+                    }
+                }
+            }
+            for (int li = 1; li < nlanes; ++li) {  // join: the reduction on the main stream sees every lane
+                FV_HIP(hipEventRecord(lanes[li].done, lanes[li].stream));
+                FV_HIP(hipStreamWaitEvent(stream, lanes[li].done, 0));
+            }
+            AdjReduceArgs ra{};
+            for (int li = 0; li < nlanes; ++li) ra.acc[li] = lanes[li].d_adj_acc.template as<double>();
+            ra.nl = nlanes;
+            ra.nfa = nfa;
+            ra.f_base = fb.b0;
+            ra.nfreq = nfreq_cat;
+            ra.comps = comps;
+            ra.nsrc = nsrc;
+            const int64_t ne = nsrc * nfa * comps;
+            if (ne > 0) hipLaunchKernelGGL(k_adj_reduce<T>, dim3((unsigned)cdiv(ne, 256)), dim3(256), 0, stream, ra, dgf);
+        }
+        if (!gflux_on_device && gf_bytes) FV_HIP(hipMemcpyAsync(gflux, dgf, gf_bytes, hipMemcpyDeviceToHost, stream));
+        // The call ends synchronised.  Its own bulk device memory -- the second transforms' grids, their values at the
+        // directions, the accumulators, the staged G and gflux -- is given back when it exceeds FFTVIS_HIP_ADJ_KEEP_BYTES
+        // (default 256 MiB): a cached handle then holds for its next forward run what it held before, but for the adjoint
+        // plans' tables and per-baseline arrays.  Smaller sets stay for the next call (freeing and reallocating them
+        // doubled a C2 adjoint step).
+        FV_HIP(hipStreamSynchronize(stream));
+        {
+            size_t bulk = d_adj_g.cap + d_adj_gf.cap;
+            for (Lane &L : lanes) bulk += L.d_adj_z.cap + L.d_adj_acc.cap + (L.adj ? L.adj->buf0.cap + L.adj->buf1.cap : 0);
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            if ((double)bulk > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
+                for (Lane &L : lanes) {
+                    if (L.adj) {
+                        L.adj->buf0.release();
+                        L.adj->buf1.release();
+                    }
+                    L.d_adj_z.release();
+                    L.d_adj_acc.release();
+                }
+                d_adj_g.release();
+                d_adj_gf.release();
+            }
+        }
+        check_errors();
+    }
+
     // beam x coherency strengths of one (frequency group, beam pair) for the lane's current sources
     void launch_strengths(Lane &L, const Pair &pr, int fa, int nfg, int64_t M, const int *Mp, hipStream_t on, int wt_k = 0,
                           Nufft3<T> *plan = nullptr) {
@@ -3243,11 +3671,13 @@ class Sim : public SimBase {
     // Called where the host has just synchronised with the main stream: a run that met bad input fails
     // here instead of returning finite, wrong visibilities (finufft rejects such points up front).
     void check_errors() {
-        int e[4] = {0, 0, 0, 0};
+        int e[NERR] = {0, 0, 0, 0, 0};
         FV_HIP(hipMemcpyAsync(e, d_err.p, sizeof(e), hipMemcpyDeviceToHost, stream));
         FV_HIP(hipStreamSynchronize(stream));
-        if (!e[0] && !e[1] && !e[2] && !e[3]) return;
+        if (!e[0] && !e[1] && !e[2] && !e[3] && !e[4]) return;
         FV_HIP(hipMemsetAsync(d_err.p, 0, sizeof(e), stream));
+        if (e[4])
+            throw Error(FV_ERR_ARG, std::to_string(e[4]) + " entries of the adjoint's visibility-shaped input are NaN");
         if (e[3])
             throw Error(FV_ERR_INTERNAL, "the gather met " + std::to_string(e[3]) + " transform columns its column plan had left "
                                          "out: the visibilities of this run are invalid (FFTVIS_HIP_NO_COLUMN_PLAN=1 avoids the plan)");

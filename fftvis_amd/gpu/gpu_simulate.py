@@ -228,6 +228,20 @@ class SimHandle:
                                                out.strides[0] // out.itemsize, int(bool(shared))))
         return out
 
+    def run_adjoint(self, t0, t1, f0, f1, g, gflux, accumulate: bool):
+        """``gflux += A^T g`` for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_adjoint``).  ``g``: C-contiguous block of
+        ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype; ``gflux``: C-contiguous (nsrc, nfreq) real or
+        (nsrc, nfreq, 2, 2) complex.  numpy arrays are host buffers, torch tensors device buffers (ready when the call
+        is made: the library's streams do not follow torch's).  The call synchronises."""
+        def addr(a):
+            if isinstance(a, np.ndarray):
+                return ctypes.c_void_p(a.ctypes.data), 0
+            return ctypes.c_void_p(a.data_ptr()), 1
+
+        gp, g_dev = addr(g)
+        fp, f_dev = addr(gflux)
+        _lib.check(self._L.fv_sim_run_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, fp, f_dev, int(bool(accumulate))))
+
     def run_device(self, t0, t1, f0, f1, out_ptr):
         """Enqueue only; ``out_ptr`` is a device buffer of out_shape() complex elements."""
         _lib.check(self._L.fv_sim_run(self._h, t0, t1, f0, f1, _lib.ptr(out_ptr), 1))
@@ -348,6 +362,7 @@ class GPUSimulationEngine(SimulationEngine):
         device_astrometry: bool = False,
         out: np.ndarray = None,
         out_shared: bool = False,
+        adjoint_of: tuple = None,
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -406,6 +421,10 @@ class GPUSimulationEngine(SimulationEngine):
           of the block's shape and dtype, only its channel axis strided; it is pinned in place and filled while the
           run computes.  ``out_shared`` (extra): the underlying array is shared memory that other ranks fill too
           (``parallel.simulate_vis_sharded``).
+        * ``adjoint_of`` (extra; what ``simulate_vis_adjoint`` passes): a pair ``(g, gflux)`` -- instead of simulating,
+          the engine configured by these arguments adds the adjoint of its map from ``fluxes`` (which then only give
+          the catalog's shape) to visibilities, applied to ``g`` (the result's shape, this precision's complex dtype),
+          into ``gflux`` (``SimHandle.run_adjoint``) and returns ``gflux``.
         """
         beam_order = checked_spline_order(beam_spline_opts)
         if interpolation_function not in ("az_za_map_coordinates", "az_za_simple"):
@@ -532,6 +551,10 @@ class GPUSimulationEngine(SimulationEngine):
                                  nsrc if coord_mgr is not None else 0)
             if coord_mgr is not None:
                 coord_mgr.setup()
+            if adjoint_of is not None:
+                result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr)
+                ok = True
+                return result
             if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != complex_dtype):
                 raise ValueError(f"out must be a {np.dtype(complex_dtype).name} array of shape "
                                  f"{h.out_shape(t1 - t0, f1 - f0)}, got {out.dtype} {out.shape}")
@@ -636,6 +659,33 @@ def _topo_from_coord_mgr(coord_mgr, time_indices):
         coord_mgr.rotate(ti)
         out.append(np.array(coord_mgr.all_coords_topo, dtype=float))
     return np.stack(out)
+
+
+def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr):
+    """The adjoint's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors), each block's
+    contribution added to ``gflux``.  Every ``run_adjoint`` call ends synchronised."""
+    on_device = not isinstance(g, np.ndarray)
+    step = max(nblk_t, 1)
+    first = True
+    for tb in range(t0, t1, step):
+        te = min(t1, tb + step)
+        blk = g[:, tb - t0:te - t0]
+        if on_device:
+            import torch
+
+            blk = blk.contiguous()
+            torch.cuda.synchronize(blk.device)  # a copy .contiguous() queued on torch's stream is done before the library reads
+        else:
+            blk = np.ascontiguousarray(blk)
+        if coord_mgr is not None:
+            h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
+            h.run_adjoint(0, te - tb, f0, f1, blk, gflux, not first)
+        else:
+            h.run_adjoint(tb, te, f0, f1, blk, gflux, not first)
+        first = False
+    if first:  # no time steps: nothing contributes
+        gflux[...] = 0
+    return gflux
 
 
 def _time_block(device, nt, nf, nbls, polarized, precision, nsrc_topo=0):

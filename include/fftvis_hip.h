@@ -234,6 +234,22 @@ int fv_sim_run(fv_sim *h, int t0, int t1, int f0, int f1, void *out, int out_on_
  * shared != 0: other processes write the rest of the array (one result in shared memory for all ranks of a node): the
  * pinning helper then only reads the block's pages when it touches them and registers nothing beyond its runs.        */
 int fv_sim_run_into(fv_sim *h, int t0, int t1, int f0, int f1, void *out, int64_t out_f_stride, int shared);
+/* Adjoint of fv_sim_run with everything the fv_sim_set_* calls configured: gflux += A^T G for times [t0, t1) x freqs
+ * [f0, f1), where A maps the catalog's fluxes to the visibilities fv_sim_run computes and A^T is taken for the real inner
+ * products, Re <A F, G> = <F, A^T G> (flipped baselines are conjugated: the map is real-linear).  gvis: G, complex of
+ * the handle's precision in fv_sim_run's output layout for that block.  gflux: (nsrc, nfreq) of the precision's real
+ * type for a Stokes-I catalog, (nsrc, nfreq, 2, 2) complex for a coherency catalog (the gradient Gc with
+ * Re <A C, G> = Re sum conj(Gc) C); only channels [f0, f1) receive a contribution.  accumulate = 0: gflux is zeroed
+ * first.  The *_on_device flags as in fv_sim_run (device buffers must be complete when the call is made); the call
+ * synchronises.  The bulk device memory it uses beyond what fv_sim_run holds (the grids of a second transform per
+ * lane, fp64 accumulators of at most FFTVIS_HIP_ADJ_ACC_BYTES per lane -- channel blocks --, staged host buffers) is
+ * given back when it exceeds FFTVIS_HIP_ADJ_KEEP_BYTES (default 256 MiB); the second transforms' tables and
+ * per-baseline arrays stay with the handle.  Lattice
+ * arrays use the type-3 transform here as well.  A handle with basis beams (fv_sim_set_basis) and NaN in G fail with
+ * FV_ERR_ARG.  Sums run in fp64, per lane in a fixed order, so that a run is
+ * bitwise reproducible for a given FFTVIS_HIP_LANES.                                                                   */
+int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                       int gflux_on_device, int accumulate);
 int fv_sim_sync(fv_sim *h);
 
 /* Introspection for bench/roofline: fills up to n doubles:

@@ -58,6 +58,7 @@ int main() {
     EXPECT(fv_astrom_topo(0, 9, d9, 1, d9, v) == FV_ERR_ARG);
     EXPECT(fv_sim_set_beam_airy_scaled(nullptr, 0, 14.0, d9, 1.0) == FV_ERR_ARG);
     EXPECT(fv_sim_run(nullptr, 0, 1, 0, 1, v, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_sync(nullptr) == FV_ERR_ARG);
     EXPECT(fv_sim_stats(nullptr, v, 12) == FV_ERR_ARG);
     EXPECT(fv_sim_reset_stats(nullptr) == FV_ERR_ARG);
@@ -97,6 +98,10 @@ int main() {
         EXPECT(fv_scatter_flux_columns(nullptr, 0, 1, 1, 8, v, i2, v) == FV_ERR_ARG);
     }
     EXPECT(fv_release_workspaces() == FV_OK);
+    // the adjoint refuses null buffers and bad flags before touching the handle
+    EXPECT(fv_sim_run_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, nullptr, 0, v, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 0, nullptr, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 2, v, 0, 0) == FV_ERR_ARG);
     // a call that gets past the argument checks reports the missing device as a HIP error, not a crash
     if (ndev == 0) {
         EXPECT(fv_sim_create(&h, 0, 2, 1e-6, 2.0, 1) == FV_ERR_HIP && h == nullptr);

@@ -1,0 +1,26 @@
+#!/bin/bash
+# Forward vs adjoint ms per time step at C2 and C3 (2 channels x 2 times), then one kernel-trace profile of a C3 adjoint
+# call (rocprofv3 --kernel-trace --stats; k_adj_strengths / k_adj_accumulate appear in its kernel statistics).
+# Every GPU step has its own time limit, and the script stops at the first step that fails (its exit status is the
+# step's: 124 / 137 a time limit, 134 an abort, 139 a segmentation fault).
+# Usage: tools/adjoint_timing.sh [output directory, default profiles/adjoint]
+set -uo pipefail
+cd "$(dirname "$0")/.."
+OUT=${1:-profiles/adjoint}
+mkdir -p "$OUT"
+step() {  # output file, seconds, command...
+    local out=$1 secs=$2
+    shift 2
+    timeout -k 10 "$secs" "$@" > "$out"
+    local rc=$?
+    cat "$out"
+    if [ $rc -ne 0 ]; then
+        echo "adjoint_timing: '$*' failed with status $rc; nothing more is started" >&2
+        exit $rc
+    fi
+}
+step "$OUT/timing_c2.json" 300 python tools/adjoint_timing.py --config C2
+step "$OUT/timing_c3.json" 600 python tools/adjoint_timing.py --config C3
+step "$OUT/rocprof.log" 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o adj_c3 -- \
+    python tools/adjoint_timing.py --config C3 --adjoint-only
+find "$OUT/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/c3_adjoint_kernel_stats.csv" \;
