@@ -15,6 +15,7 @@
 #include <unordered_map>
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <memory>
 
@@ -1357,6 +1358,12 @@ struct SimBase {
 };
 
 enum { TM_SPREAD = 0, TM_FFT, TM_INTERP, TM_STRENGTHS, TM_PREP, TM_COUNT };
+// slots of fv_sim_stats, in the order include/fftvis_hip.h documents them
+enum {
+    ST_SPREAD_LAUNCHES = 0, ST_SPREAD_CELLS, ST_SOURCE_VISITS, ST_FFT_CELLS, ST_GATHERED, ST_ABOVE_HORIZON, ST_N2X, ST_N2Y,
+    ST_NA_XY, ST_W, ST_SIGMA, ST_MAX_ABOVE_HORIZON, ST_FFT_FLOPS, ST_N2_3, ST_NA_3, ST_HEIGHT_TERMS, ST_LANES, ST_LANE_MODE,
+    ST_LIGHT_FROM, ST_LIGHTER_FROM
+};
 
 template <typename T>
 class Sim : public SimBase {
@@ -1448,19 +1455,19 @@ class Sim : public SimBase {
 
     // Per-time scratch lives in a lane.  Small problems run consecutive time steps on two lanes
     // (two streams) so that one step's launch ramps and tails overlap the other's kernels.
+    static constexpr int NCLS = 3;  // plan classes of a lane
     struct Lane {
         hipStream_t stream = nullptr;
         bool own_stream = false;
         hipEvent_t done = nullptr;
         hipEvent_t prep_done = nullptr, heavy_done = nullptr;  // pipelined mode (see run())
         bool heavy_pending = false;
-        std::unique_ptr<Nufft3<T>> nufft;
-        std::unique_ptr<Nufft3<T>> nufft_l[2];  // the plans of the LIGHT height terms (see Sim::wt_k0): looser tolerances, sigma = 1.25
+        // the type-3 plans by class: 0 the run's own, 1 and 2 the LIGHT height terms' (see light_classes): looser
+        // tolerances, sigma = 1.25; with the (time, chunk) and geometry their sources were last binned for
+        std::unique_ptr<Nufft3<T>> plan[NCLS];
+        int binned_ti[NCLS] = {-1, -1, -1};
+        int64_t binned_serial[NCLS] = {-1, -1, -1};
         DevBuf d_xyz, d_az, d_za, d_srcidx, d_blockcnt, d_blockoff, d_scan_tot, d_scan_off, d_enu;
-        int binned_ti = -1;
-        int64_t binned_serial = -1;
-        int binned_ti_l[2] = {-1, -1};  // the same for nufft_l
-        int64_t binned_serial_l[2] = {-1, -1};
         // adjoint (run_adjoint): the transform with the roles swapped, its strengths, its values at the directions and
         // this lane's fp64 gradient accumulator
         std::unique_ptr<Nufft3<T>> adj;
@@ -1509,30 +1516,6 @@ class Sim : public SimBase {
     double spread_timed = 0;
 
     int dim() const { return coplanar ? 2 : 3; }
-    // Height terms ("w-term expansion", run()): a non-coplanar array whose heights are small against the wavelength --
-    // every surveyed real array: centimetres to decimetres after the plane fit -- does not need a third grid dimension.
-    // exp(i z s_z), z the sources' height coordinate in [zc - zh, zc + zh], s_z = nu b_z, is expanded in Chebyshev
-    // polynomials of t = (z - zc) / zh (Jacobi - Anger: exp(i a t) = J_0(a) + 2 sum_k i^k J_k(a) T_k(t)):
-    //     V(s) = sum_k  exp(i zc s_z) c_k(zh s_z)  F_k(s_x, s_y),   c_0 = J_0, c_k = 2 i^k J_k,   F_k = 2-D transform of c_j T_k(t_j),
-    // K terms with 2 (a / 2)^K / K! <= eps / 10, a = zh max|s_z| (|J_k(a)| <= (a / 2)^k / k!): K 2-D transforms (7 for 3 cm of
-    // scatter at 200 MHz; the Taylor series about zc this replaced needed a^K / K! <= eps / 10: 8) with all of the 2-D
-    // machinery (Hermitian packing, column plan, source disc) instead of a 3-D grid whose third dimension is all kernel
-    // width (16 planes for a source range of 1.4 cells) plus a z-pass.  The terms carry the transform's relative error
-    // each, |T_k| <= 1, summed with weights |c_k| (sum <= 2 e^{a/2} - 1): the 2-D plans run at eps / (2 e^{a/2} - 1).
-    // Taken while K <= 16 (|b_z| up to metres); beyond, or with FFTVIS_HIP_NO_WTERM=1, the 3-D transform runs.
-    int wt_K = 0;   // terms of the current run (0: no expansion)
-    double wt_zc = 0.0, wt_zh = 0.0, wt_a = 0.0;
-    // Light terms: term k enters with weight |c_k| <= 2 (a / 2)^k / k!, so the higher terms need far less than the run's
-    // tolerance -- with a = 0.35 (3 cm of scatter at 200 MHz) |c_2| = 0.03, |c_4| = 8e-5.  The terms k >= wt_k0 run on a
-    // second plan at wt_eps_l = 0.3 eps / sum_{k >= k0} |c_k| and sigma = 1.25 (a grid of 0.39 x the cells: the FFT passes
-    // are the bulk of a term), chosen as the smallest k0 whose tolerance is above that sigma's floor by a decade; fp64,
-    // runs at sigma = 2 on large grids only.  wt_k0 = 0: every term on the run's own plan.  FFTVIS_HIP_NO_WTERM_LIGHT=1.
-    // Where the tail of the light terms can take a tolerance of 1e-4 or looser (a kernel of 8 cells instead of 12: the
-    // gather of a light term is most of its time) the light terms split in two classes, [k0, k1) and [k1, K), with half
-    // of the budget each; wt_k1 = wt_K: one class.
-    int wt_k0 = 0, wt_k1 = 0;
-    double wt_eps_l[2] = {0.0, 0.0};
-    int run_D = 2;  // dimensions of the current run's transforms
 
     size_t ev_slot(int kind) {
         if (ev_used == ev_pool.size()) {
@@ -1547,16 +1530,9 @@ class Sim : public SimBase {
     }
     size_t ev_begin(int kind, hipStream_t st_) {
         if (timing_level != 2) return (size_t)-1;
-        if (ev_used == ev_pool.size()) {
-            Ev e;
-            FV_HIP(hipEventCreate(&e.a));
-            FV_HIP(hipEventCreate(&e.b));
-            e.kind = kind;
-            ev_pool.push_back(e);
-        }
-        ev_pool[ev_used].kind = kind;
-        FV_HIP(hipEventRecord(ev_pool[ev_used].a, st_));
-        return ev_used++;
+        const size_t i = ev_slot(kind);
+        FV_HIP(hipEventRecord(ev_pool[i].a, st_));
+        return i;
     }
     void ev_end(size_t i, hipStream_t st_) {
         if (i == (size_t)-1) return;
@@ -1602,10 +1578,8 @@ class Sim : public SimBase {
     ~Sim() override {
         (void)hipSetDevice(device);
         for (Lane &L : lanes) {
-            L.nufft.reset();
+            for (auto &P : L.plan) P.reset();
             L.adj.reset();
-            L.nufft_l[0].reset();
-            L.nufft_l[1].reset();
             if (L.done) (void)hipEventDestroy(L.done);
             if (L.prep_done) (void)hipEventDestroy(L.prep_done);
             if (L.heavy_done) (void)hipEventDestroy(L.heavy_done);
@@ -1880,11 +1854,11 @@ class Sim : public SimBase {
     // agree to `tol` seconds in every component -- tol = what moves the phase 2 pi nu b . x by at most 1e-3 eps at the
     // run's highest frequency, i.e. far below the transform's own error; exact duplicates always qualify -- are gathered
     // once (k_interp walks the run for the output slots).  Compared with the run's FIRST entry, so runs cannot drift.
-    // FFTVIS_HIP_NO_TARGET_DEDUP=1 turns it off.
-    void build_unique(Pair &p, double tol) {
+    // FFTVIS_HIP_NO_TARGET_DEDUP=1 turns it off.  nd: components compared (2 under height terms: a run shares (u, v)
+    // only, every member brings its own b_z).
+    void build_unique(Pair &p, double tol, int nd) {
         const bool off = std::getenv("FFTVIS_HIP_NO_TARGET_DEDUP") != nullptr;  // read per run: tests flip it
         if (off) tol = -2.0;
-        const int nd = wt_K ? 2 : 3;  // height terms: a run shares (u, v) only, every member brings its own b_z
         if (p.utol == tol && p.udims == nd) return;
         p.utol = tol;
         p.udims = nd;
@@ -1996,8 +1970,7 @@ class Sim : public SimBase {
         double out_cells = 0;  // cells of C per transform the masked y-pass stores
     };
     std::vector<std::unique_ptr<ColPlan>> col_plans;
-    std::vector<ColPlan *> col_plan_of;  // [group * pairs + pair] of the current run
-    std::vector<ColPlan *> col_plan_of_l[2];  // the same for the light height terms' plans (wt_k0, wt_k1)
+    std::vector<ColPlan *> col_plan_of[NCLS];  // [plan class][group * pairs + pair] of the current run
     ColPlan *column_plan(int pi, const Pair &pr, int fa, int fb, Nufft3<T> *n0) {
         const DimGeom &x = n0->geo.d[0], &y = n0->geo.d[1];
         const int w = n0->ker.w;
@@ -2163,251 +2136,6 @@ class Sim : public SimBase {
         return Mp;
     }
 
-    // ---- type-1 run: per time, per frequency batch: bin (source, freq) entries on periodic
-    // n2 x n2 planes, strengths, gather-spread, pruned FFT to the n_modes central modes, pick.
-    void run_type1(int t0, int t1, int f0, int f1, void *out, int out_on_device) {
-        const int nt = t1 - t0, nf = f1 - f0;
-        const int64_t per_tf = (int64_t)tpol * nbls;
-        const size_t out_bytes = sizeof(cplx<T>) * (size_t)nf * nt * per_tf;
-        cplx<T> *dout;
-        if (out_on_device) {
-            dout = (cplx<T> *)out;
-        } else {
-            d_out.reserve(std::max<size_t>(out_bytes, 16));
-            dout = d_out.as<cplx<T>>();
-        }
-        FV_HIP(hipMemsetAsync(dout, 0, out_bytes, stream));
-        // host output: the lattice path computes a C3 block in 65 ms, so the 10-GB copy IS the call -- the caller's array
-        // is touched in parallel and pinned while the kernels run (HostPin), then one copy at PCIe rate (0.72 -> 0.3 s)
-        const bool drain = !out_on_device && out_bytes >= drain_min_bytes();
-        HostPin pin;
-        pin.drain_on = &stream;  // copy_block_pinned below rides on the main stream
-        // destination layout of this run (fv_sim_run_into), consumed here
-        const int64_t out_fs = out_f_stride ? out_f_stride : (int64_t)nt * per_tf;
-        const bool shared = out_shared != 0;
-        out_f_stride = 0;
-        out_shared = 0;
-        FV_REQUIRE(out_fs >= (int64_t)nt * per_tf, "fv_sim_run_into: the channel stride is shorter than a channel's run");
-        const size_t run_bytes = sizeof(cplx<T>) * (size_t)nt * per_tf;
-        // (a block inside a larger array is pinned run by run: only worth it -- and only safe against two runs meeting in
-        // one page -- when the runs are long)
-        const bool pinnable = out_fs == (int64_t)nt * per_tf || (run_bytes >= ((size_t)1 << 20) && (size_t)(out_fs - (int64_t)nt * per_tf) * sizeof(cplx<T>) >= 8192);
-        if (drain && pinnable) pin.start(device, out, (size_t)nf, run_bytes, sizeof(cplx<T>) * (size_t)out_fs, shared);
-        const double sigma = this->sigma == 0.0 ? 2.0 : this->sigma;  // "auto" is a type-3 matter
-        sigma_run = sigma;
-        if (!t1fft) t1fft.reset(new Nufft3<T>(2, eps, sigma, stream));
-        const KerParams &ker = t1fft->ker;
-        // grid: n2 = P Q >= sigma n_modes (and >= 2 w), all n2 inputs live, n_modes + 1 outputs kept
-        DimGeom g;
-        g.n1 = t1_nmodes;
-        choose_pq(std::max((int)std::ceil(sigma * t1_nmodes), 2 * ker.w + 16), g);
-        g.na = g.n2;
-        g.no = t1_nmodes + 1;
-        t1fft->set_fft_geometry(g, g);
-        t1_dec.reserve(sizeof(T) * g.no);
-        hipLaunchKernelGGL(k_deconv_table<T>, dim3(cdiv(g.no, 256)), dim3(256), 0, stream, g.no,
-                           g.n2, ker, t1_dec.as<T>());
-        const int nb1 = (g.n2 + T1_PAD) >> BINLOG;
-        int64_t pol_off[4] = {0, 0, 0, 0};
-        if (polarized)
-            for (int r = 0; r < 4; ++r) pol_off[r] = (int64_t)((r % 2) * 2 + r / 2) * nbls;
-
-        const int nch = (int)std::max<int64_t>(1, std::min<int64_t>(src_chunks, nsrc));
-        const int64_t csz = std::max<int64_t>(cdiv(nsrc, nch), 1);
-        const int64_t cap = std::max<int64_t>((int64_t)std::ceil(csz * source_buffer), 1);
-        const int nblk = (int)cdiv(csz, 256);
-        for (Lane &Lr : lanes) {
-            Lr.d_xyz.reserve(sizeof(T) * 3 * cap);
-            Lr.d_az.reserve(sizeof(T) * cap);
-            Lr.d_za.reserve(sizeof(T) * cap);
-            Lr.d_srcidx.reserve(sizeof(int) * cap);
-            Lr.d_blockcnt.reserve(sizeof(int) * (nblk + 1));
-            Lr.d_blockoff.reserve(sizeof(int) * (nblk + 1));
-        }
-        reserve_mhist(sizeof(int) * rots.size() * std::max(1, src_chunks));
-        // frequencies per batch: bounded by entries (~1.3 per (source, freq)) and by grid bytes
-        const char *eb = std::getenv("FFTVIS_HIP_GRID_BYTES");
-        const double budget = eb ? std::atof(eb) : 8.0 * 1024 * 1024 * 1024;
-        const double plane_bytes = 2.0 * g.n2 * (double)g.n2 * tpol * sizeof(cplx<T>);
-        // entries per live (source, frequency) pair: 1 + the periodic images of footprints that cross an
-        // edge of the n2 x n2 plane -- (1 + (w + 1) / n2)^2 on average for uniformly placed sources (1.52
-        // at w = 16 on the smallest, 64-cell planes); 5 % head-room on top, and a catalog that still
-        // overflows (sources piled on a plane edge) fails the run (t1 overflow flag), never silently
-        const double img = (1.0 + (ker.w + 1.0) / g.n2) * (1.0 + (ker.w + 1.0) / g.n2) * 1.05;
-        int nfb = (int)std::max(1.0, std::min({(double)nf, budget / plane_bytes, 24.0e6 / (img * cap)}));
-        const int64_t ecap = (int64_t)(img * cap * nfb) + 4096;
-        const int nbins = nfb * nb1 * nb1;
-        const int rec = t1_record_bytes(ker.w, sizeof(T));
-        // Pipelined like the type-3 loop: the entry sort of unit (time, batch) u+1 (three kernels over
-        // every (source, frequency) pair, ~25 % of a step) runs on the low-priority stream beside the
-        // strengths / spread / FFT / pick of unit u; two sets of sort buffers and two sets of
-        // per-time source arrays alternate.
-        const char *ep = std::getenv("FFTVIS_HIP_PIPE");
-        const int nunits = nt * nch * (int)cdiv(nf, nfb);
-        const bool pipe = timing_level != 2 && nunits > 1 && !(ep && std::atoi(ep) == 0);
-        const hipStream_t ps = pipe ? prep_stream : stream;
-        for (int sset = 0; sset < (pipe ? 2 : 1); ++sset) {
-            t1_meta[sset].reserve(sizeof(int) * (2 * (size_t)(nbins + 1) + 2));
-            t1_binstart[sset].reserve(sizeof(int) * (nbins + 1));
-            t1_rec[sset].reserve((size_t)rec * ecap);
-        }
-        t1_cs.reserve(sizeof(cplx<T>) * ecap * tpol);
-        bool set_pending[2] = {false, false}, lane_pending[2] = {false, false};
-        lane_mode = -1;  // a type-3 run after this one drains the streams before it reuses the lanes
-        if (pipe) {  // the sort may start once the set-up queued on the main stream is done
-            FV_HIP(hipEventRecord(ev_start, stream));
-            FV_HIP(hipStreamWaitEvent(ps, ev_start, 0));
-        }
-        int unit = 0;
-
-        for (int tc = 0; tc < nt * nch; ++tc) {  // (time, source chunk), chunks innermost (cpu_simulate.py:936-939)
-            const int ti = t0 + tc / nch, chunk = tc % nch;
-            const int64_t s0 = (int64_t)chunk * csz, sn = std::min<int64_t>(csz, nsrc - s0);
-            if (nsrc == 0 || sn <= 0) continue;
-            const int li = pipe ? tc % 2 : 0;
-            Lane &L = lanes[li];
-            DevBuf &d_xyz = L.d_xyz, &d_az = L.d_az, &d_za = L.d_za, &d_srcidx = L.d_srcidx;
-            if (pipe && lane_pending[li]) FV_HIP(hipStreamWaitEvent(ps, L.done, 0));  // its strengths are done
-            size_t e0 = ev_begin(TM_PREP, ps);
-            const int *Mp = horizon_step(L, ti, cap, nblk, ps, s0, sn, (int64_t)ti * nch + chunk);
-            ev_end(e0, ps);
-            mhist_log.push_back({ti * nch + chunk, 0.0});
-            const size_t hist_slot = mhist_log.size() - 1;
-            for (int fa = f0; fa < f1; fa += nfb, ++unit) {
-                const int nfg = std::min(nfb, f1 - fa);
-                const int ss = pipe ? unit % 2 : 0;
-                DevBuf &meta = t1_meta[ss], &binstart = t1_binstart[ss], &recs = t1_rec[ss];
-                T1Args a{};
-                a.n2 = g.n2;
-                a.nb1 = nb1;
-                a.w = ker.w;
-                a.nfg = nfg;
-                a.f_first = fa;
-                a.cap = cap;
-                a.ecap = ecap;
-                a.rec = rec;
-                const int nbn = nfg * nb1 * nb1;
-                int *counts_p = meta.as<int>(), *cursor_p = counts_p + (nbins + 1), *ovf_p = d_err.as<int>() + 1;
-                if (pipe && set_pending[ss]) FV_HIP(hipStreamWaitEvent(ps, lanes[ss].heavy_done, 0));
-                size_t e1 = ev_begin(TM_PREP, ps);
-                FV_HIP(hipMemsetAsync(meta.p, 0, sizeof(int) * (2 * (size_t)(nbins + 1) + 2), ps));
-                const dim3 gb((unsigned)cdiv(cap * nfg, 256));
-                hipLaunchKernelGGL((k_t1_bin<T, true>), gb, dim3(256), 0, ps, a, Mp, d_xyz.as<T>(),
-                                   d_freqs.as<double>(), counts_p, (const int *)nullptr, cursor_p,
-                                   (unsigned char *)nullptr, (T)ker.beta, (T)ker.c, ovf_p);
-                t1fft->stream = ps;
-                t1fft->exclusive_scan(counts_p, binstart.as<int>(), nbn);
-                t1fft->stream = stream;
-                hipLaunchKernelGGL((ker.w == 9 ? k_t1_bin<T, false, 9> : ker.w == 5 ? k_t1_bin<T, false, 5> : ker.w == 7 ? k_t1_bin<T, false, 7> : k_t1_bin<T, false, 0>), gb, dim3(256), 0, ps, a, Mp,
-                                   d_xyz.as<T>(), d_freqs.as<double>(), counts_p, (const int *)binstart.as<int>(),
-                                   cursor_p, recs.as<unsigned char>(), (T)ker.beta, (T)ker.c, ovf_p);
-                ev_end(e1, ps);
-                if (pipe) {
-                    FV_HIP(hipEventRecord(lanes[ss].prep_done, ps));
-                    FV_HIP(hipStreamWaitEvent(stream, lanes[ss].prep_done, 0));
-                }
-                const int *nent = binstart.as<int>() + nbn;
-                for (const Pair &pr : pairs) {
-                    if (pr.n == 0) continue;
-                    size_t e2 = ev_begin(TM_STRENGTHS, stream);
-                    StrengthArgs sa{};
-                    sa.M = cap;
-                    sa.nfg = nfg;
-                    sa.f_first = fa;
-                    sa.nfreq = nfreq_cat;
-                    sa.polarized = polarized;
-                    sa.pol_sky = pol_sky;
-                    sa.same_beam = pr.bi == pr.bj;
-                    // Hermitian packing: two planes per frequency instead of four for a single-beam pair
-                    const bool herm1 = polarized && pr.bi == pr.bj && std::getenv("FFTVIS_HIP_NO_HERMITIAN") == nullptr;
-                    const int tg = herm1 ? 2 : tpol;
-                    sa.herm = herm1;
-                    sa.dim = 2;
-                    sa.bi = desc(pr.bi);
-                    sa.bj = desc(pr.bj);
-                    hipLaunchKernelGGL((beam_order == 3 ? k_t1_strengths<T, 3> : beam_order == 1 ? k_t1_strengths<T, 1> : k_t1_strengths<T, 0>),
-                                       dim3(cdiv(ecap, 256)), dim3(256), 0, stream,
-                                       sa, nent, ecap, (const unsigned char *)recs.as<unsigned char>(), rec,
-                                       d_srcidx.as<int>(),
-                                       d_az.as<T>(), d_za.as<T>(), d_flux.p, d_freqs.as<double>(),
-                                       t1_cs.as<cplx<T>>());
-                    ev_end(e2, stream);
-                    const int nplanes = nfg * tg;
-                    cplx<T> *A = t1fft->fft_input(nplanes);
-                    size_t e3 = ev_begin(TM_SPREAD, stream);
-                    const dim3 gs((unsigned)cdiv(g.n2 >> (BINLOG + 1), 4), (unsigned)(g.n2 >> (BINLOG + 1)), (unsigned)nfg);  // 16 x 16 cells per wave
-                    // fp64: the accumulation on the matrix pipe (FFTVIS_HIP_T1_MM=0: the vector version)
-                    static const bool t1_mm = !(std::getenv("FFTVIS_HIP_T1_MM") && std::atoi(std::getenv("FFTVIS_HIP_T1_MM")) == 0);
-                    bool spread_done = false;
-                    if constexpr (sizeof(T) == 8) {
-                        if (t1_mm) {
-                            auto kmm = herm1 ? k_t1_spread_mm<2> : polarized ? k_t1_spread_mm<4> : k_t1_spread_mm<1>;
-                            hipLaunchKernelGGL(kmm, gs, dim3(SPREAD_THREADS), 0, stream, a,
-                                               (const unsigned char *)recs.as<unsigned char>(), (const int *)binstart.as<int>(),
-                                               (const cplx<double> *)t1_cs.as<cplx<double>>(), (cplx<double> *)A);
-                            spread_done = true;
-                        }
-                    }
-                    if (spread_done) {
-                    } else if (herm1)
-                        hipLaunchKernelGGL((k_t1_spread<T, 2>), gs, dim3(SPREAD_THREADS), 0, stream, a,
-                                           (const unsigned char *)recs.as<unsigned char>(),
-                                           (const int *)binstart.as<int>(),
-                                           (const cplx<T> *)t1_cs.as<cplx<T>>(), A);
-                    else if (polarized)
-                        hipLaunchKernelGGL((k_t1_spread<T, 4>), gs, dim3(SPREAD_THREADS), 0, stream, a,
-                                           (const unsigned char *)recs.as<unsigned char>(),
-                                           (const int *)binstart.as<int>(),
-                                           (const cplx<T> *)t1_cs.as<cplx<T>>(), A);
-                    else
-                        hipLaunchKernelGGL((k_t1_spread<T, 1>), gs, dim3(SPREAD_THREADS), 0, stream, a,
-                                           (const unsigned char *)recs.as<unsigned char>(),
-                                           (const int *)binstart.as<int>(),
-                                           (const cplx<T> *)t1_cs.as<cplx<T>>(), A);
-                    ev_end(e3, stream);
-                    st[0] += 1;
-                    st[1] += (double)g.n2 * g.n2 * nplanes;
-                    mhist_log[hist_slot].second += nplanes;
-                    size_t e4 = ev_begin(TM_FFT, stream);
-                    t1fft->fft(nplanes);
-                    ev_end(e4, stream);
-                    st[3] += ((double)g.n2 * g.n2 + 2.0 * g.no * g.n2 + (double)g.no * g.no) * nplanes;
-                    size_t e5 = ev_begin(TM_INTERP, stream);
-                    cplx<T> *obase = dout + ((int64_t)(fa - f0) * nt + (ti - t0)) * per_tf;
-                    hipLaunchKernelGGL(k_t1_pick<T>, dim3(cdiv(pr.n * nfg, 256)), dim3(256), 0, stream,
-                                       t1fft->fft_output(), g.no, g.P, g.cnt(), nfg, tg,
-                                       (const int *)d_blint.as<int>(),
-                                       (const int *)d_blint.as<int>() + nbls, pr.n,
-                                       pr.trivial0 ? (const int *)nullptr : (const int *)(pr.idx0 ? pr.idx0 : pr.idx)->template as<int>(),
-                                       pr.trivial0 ? (const signed char *)nullptr
-                                                   : (const signed char *)(pr.flip0 ? pr.flip0 : pr.flip)->template as<signed char>(),
-                                       (const T *)t1_dec.as<T>(), obase, (int64_t)nt * per_tf, pol_off[0],
-                                       pol_off[1], pol_off[2], pol_off[3], chunk > 0, herm1, !reference_compat);
-                    ev_end(e5, stream);
-                    st[4] += (double)pr.n * nplanes;
-                    st[6] = g.n2;
-                    st[7] = g.n2;
-                    st[8] = g.n2 * 65536.0 + g.n2;
-                    st[9] = ker.w;
-                }
-                if (pipe) {
-                    FV_HIP(hipEventRecord(lanes[ss].heavy_done, stream));
-                    set_pending[ss] = true;
-                }
-            }
-            if (pipe) {
-                FV_HIP(hipEventRecord(L.done, stream));
-                lane_pending[li] = true;
-            }
-        }
-        if (!out_on_device) {
-            copy_block_to_host(out, dout, nf, (int64_t)nt * per_tf, out_fs, drain && pinnable && pin.wait(), stream);
-            FV_HIP(hipStreamSynchronize(stream));
-            if (timing_level) ev_collect();
-            check_errors();
-        }
-    }
-
     // Tight box of {2 pi R_plane v : |v| = 1, v_up >= 0} per coordinate.
     void source_box(double *xc, double *X) const {
         for (int d = 0; d < 3; ++d) {
@@ -2425,8 +2153,8 @@ class Sim : public SimBase {
     template <class BoxOf>
     double cells_at_sigma2(const double *X, int D, int f0, int f1, BoxOf box_B) const {
         const KerParams k2 = make_kernel(eps, 2.0);
-        double fmax = 0, cells2 = 1.0;
-        for (int f = f0; f < f1; ++f) fmax = std::max(fmax, std::fabs(freqs[f]));
+        const double fmax = fmax_of(f0, f1);
+        double cells2 = 1.0;
         for (int d = 0; d < D; ++d) {
             DimGeom g;
             g.X = X[d];
@@ -2466,8 +2194,7 @@ class Sim : public SimBase {
         // time steps, 8 GiB 362, 2 GiB 364, 1 GiB 369; round 2 (two per frequency, groups of whole eights):
         // 6 GiB 416.7 ms per four time steps (spread at 0.64 of the HBM roofline), 4 GiB 421.7 (0.54), 3 GiB 422.7
         const double budget = eb ? std::atof(eb) : 6.0 * 1024 * 1024 * 1024;
-        double fmax = 1.0;
-        for (int f = f0; f < f1; ++f) fmax = std::max(fmax, std::fabs(freqs[f]));
+        const double fmax = fmax_of(f0, f1, 1.0);
         const double mb = cells_top * sizeof(cplx<T>) / (1024.0 * 1024.0);
         double ratio = 0.5 + 0.4 * std::min(1.0, std::max(0.0, std::log2(mb / 16.0) / 4.0));
         if (er) ratio = std::atof(er);
@@ -2619,51 +2346,94 @@ class Sim : public SimBase {
             for (auto &pc : pieces) (void)hipHostUnregister(pc.first);
         }
     };
-    // queue the copies of the finished time steps items[done ...) behind their events
-    void drain_flush(void *out, const cplx<T> *dout, int nt, int nf, int64_t per_tf, const std::vector<DrainItem> &items,
-                     size_t &done, int64_t out_fs) {
+    // The output block of a forward run, (nf, nt, tpol, nbls), on the device and zeroed: baselines not covered by any pair
+    // stay zero (reference zero-initialises, :909-911).  At a host destination channel f of the block starts f * fs
+    // elements after `out` (fv_sim_run_into's layout, consumed here).
+    struct OutBlock {
+        void *out;
+        bool on_device;
+        int nt, nf;
+        cplx<T> *dout;
+        int64_t per_tf, run, fs;  // elements per (frequency, time), per channel, between channels at the destination
+        size_t bytes, run_bytes;
+        bool shared;  // other processes write the rest of the destination array
+        bool drain;   // the block leaves through the pinned caller array (drain_*)
+    };
+    OutBlock out_block(int nt, int nf, void *out, int out_on_device) {
+        OutBlock o;
+        o.out = out;
+        o.on_device = out_on_device != 0;
+        o.nt = nt;
+        o.nf = nf;
+        o.per_tf = (int64_t)tpol * nbls;
+        o.run = (int64_t)nt * o.per_tf;
+        o.fs = out_f_stride ? out_f_stride : o.run;
+        o.shared = out_shared != 0;
+        out_f_stride = 0;
+        out_shared = 0;
+        FV_REQUIRE(o.fs >= o.run, "fv_sim_run_into: the channel stride is shorter than a channel's run");
+        o.bytes = sizeof(cplx<T>) * (size_t)nf * o.run;
+        o.run_bytes = sizeof(cplx<T>) * (size_t)o.run;
+        if (o.on_device) {
+            o.dout = (cplx<T> *)out;
+        } else {
+            d_out.reserve(std::max<size_t>(o.bytes, 16));
+            o.dout = d_out.as<cplx<T>>();
+        }
+        FV_HIP(hipMemsetAsync(o.dout, 0, o.bytes, stream));
+        // (a block inside a larger array is pinned run by run: only worth it -- and only safe against two runs meeting in
+        // one page -- when the runs are long)
+        const bool pinnable = o.fs == o.run || (o.run_bytes >= ((size_t)1 << 20) && (size_t)(o.fs - o.run) * sizeof(cplx<T>) >= 8192);
+        o.drain = !o.on_device && o.bytes >= drain_min_bytes() && pinnable;
+        return o;
+    }
+    void pin_block(const OutBlock &o, HostPin &pin, bool keep_clock) {
+        pin.start(device, o.out, (size_t)o.nf, o.run_bytes, sizeof(cplx<T>) * (size_t)o.fs, o.shared, keep_clock);
+    }
+    // the drained host output of a type-3 run: the pinning helper, the finished time steps and how many of them left
+    struct Drain {
+        HostPin pin;
+        bool started = false;
+        std::vector<DrainItem> items;
+        size_t done = 0;
+        const bool dbg = std::getenv("FFTVIS_HIP_DEBUG_DRAIN") != nullptr;
+    };
+    void pin_output(const OutBlock &o, Drain &dr) {
+        pin_block(o, dr.pin, true);
+        dr.started = true;
+    }
+    // queue the copies of the finished time steps dr.items[dr.done ...) behind their events
+    void drain_flush(const OutBlock &o, Drain &dr) {
         if (!copy_stream) FV_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-        cplx<T> *hout = static_cast<cplx<T> *>(out);
-        for (; done < items.size(); ++done) {
-            const DrainItem &it = items[done];
+        cplx<T> *hout = static_cast<cplx<T> *>(o.out);
+        for (; dr.done < dr.items.size(); ++dr.done) {
+            const DrainItem &it = dr.items[dr.done];
             FV_HIP(hipStreamWaitEvent(copy_stream, it.ev, 0));
-            for (int f = 0; f < nf; ++f) {
-                const int64_t off = ((int64_t)f * nt + it.t) * per_tf;
-                // split where the pinned pieces meet (HostPin): a copy must lie inside one registration
-                char *dst = reinterpret_cast<char *>(hout + (int64_t)f * out_fs + (int64_t)it.t * per_tf);
-                const char *src = reinterpret_cast<const char *>(dout + off);
-                size_t left = sizeof(cplx<T>) * (size_t)it.n * per_tf;
-                while (left) {
-                    const uintptr_t stop = (reinterpret_cast<uintptr_t>(dst) / HostPin::PIECE + 1) * HostPin::PIECE;
-                    const size_t n = std::min<size_t>(left, stop - reinterpret_cast<uintptr_t>(dst));
-                    FV_HIP(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, copy_stream));
-                    dst += n;
-                    src += n;
-                    left -= n;
-                }
-            }
+            for (int f = 0; f < o.nf; ++f)
+                copy_block_pinned(hout + (int64_t)f * o.fs + (int64_t)it.t * o.per_tf, o.dout + ((int64_t)f * o.nt + it.t) * o.per_tf,
+                                  sizeof(cplx<T>) * (size_t)it.n * o.per_tf, copy_stream);
         }
     }
 
     // one asynchronous copy of a whole block into a pinned caller array, split where the pinned pieces meet
-    // the same for a block whose channels are out_fs elements apart at the destination: one run per channel
-    void copy_block_to_host(void *out, const cplx<T> *dout, int nf, int64_t run_elems, int64_t out_fs, bool pinned, hipStream_t on) {
-        if (out_fs == run_elems) {
+    // the same for a block whose channels are o.fs elements apart at the destination: one run per channel
+    void copy_block_to_host(const OutBlock &o, bool pinned, hipStream_t on) {
+        if (o.fs == o.run) {
             if (pinned)
-                copy_block_pinned(out, dout, sizeof(cplx<T>) * (size_t)nf * run_elems, on);
+                copy_block_pinned(o.out, o.dout, o.bytes, on);
             else
-                FV_HIP(hipMemcpyAsync(out, dout, sizeof(cplx<T>) * (size_t)nf * run_elems, hipMemcpyDeviceToHost, on));
+                FV_HIP(hipMemcpyAsync(o.out, o.dout, o.bytes, hipMemcpyDeviceToHost, on));
             return;
         }
         if (!pinned) {
-            FV_HIP(hipMemcpy2DAsync(out, sizeof(cplx<T>) * (size_t)out_fs, dout, sizeof(cplx<T>) * (size_t)run_elems,
-                                    sizeof(cplx<T>) * (size_t)run_elems, (size_t)nf, hipMemcpyDeviceToHost, on));
+            FV_HIP(hipMemcpy2DAsync(o.out, sizeof(cplx<T>) * (size_t)o.fs, o.dout, o.run_bytes, o.run_bytes, (size_t)o.nf,
+                                    hipMemcpyDeviceToHost, on));
             return;
         }
-        for (int f = 0; f < nf; ++f)
-            copy_block_pinned(static_cast<cplx<T> *>(out) + (int64_t)f * out_fs, dout + (int64_t)f * run_elems,
-                              sizeof(cplx<T>) * (size_t)run_elems, on);
+        for (int f = 0; f < o.nf; ++f)
+            copy_block_pinned(static_cast<cplx<T> *>(o.out) + (int64_t)f * o.fs, o.dout + (int64_t)f * o.run, o.run_bytes, on);
     }
+    // split where the pinned pieces meet (HostPin): a copy must lie inside one registration
     void copy_block_pinned(void *out, const void *dout, size_t bytes, hipStream_t on) {
         char *dst = static_cast<char *>(out);
         const char *src = static_cast<const char *>(dout);
@@ -2677,37 +2447,326 @@ class Sim : public SimBase {
         }
     }
 
-    void run(int t0, int t1, int f0, int f1, void *out, int out_on_device) override {
+    // ---- what the forward, type-1 and adjoint runs decide alike ----------------------------------------------------------
+    void check_run(int t0, int t1, int f0, int f1) {
         FV_HIP(hipSetDevice(device));
         FV_REQUIRE(nsrc >= 0 && !rots.empty() && !freqs.empty() && nbls > 0 && !pairs.empty(),
                    "engine not fully configured");
         FV_REQUIRE(0 <= t0 && t0 <= t1 && t1 <= (int)rots.size(), "time range");
         FV_REQUIRE(0 <= f0 && f0 <= f1 && f1 <= (int)freqs.size(), "freq range");
-        if (mhist_log.size() > 65536) mhist_log.clear();  // nobody asked for the statistics of those runs
         FV_REQUIRE((int)freqs.size() == nfreq_cat, "flux frequency axis != freqs");
         for (const Beam &b : beams) FV_REQUIRE(b.kind >= 0, "beam not set");
+    }
+    // largest |frequency| of channels [fa, fb), at least `lo`
+    double fmax_of(int fa, int fb, double lo = 0.0) const {
+        for (int f = fa; f < fb; ++f) lo = std::max(lo, std::fabs(freqs[f]));
+        return lo;
+    }
+    // redundant baselines -> one gather target each (build_unique); the tolerance follows the engine's eps and the highest
+    // frequency it knows (not the block's: blocks of a sharded run then agree on the runs)
+    double dedup_tol() const { return 1e-3 * eps / (2.0 * M_PI * std::max(fmax_of(0, (int)freqs.size()), 1.0)); }
+    // where polarisation product r of a baseline lands in a (frequency, time) slice of the output
+    std::array<int64_t, 16> pol_offsets() const {
+        std::array<int64_t, 16> po{};
+        if (polarized)
+            for (int r = 0; r < 4; ++r) po[r] = (int64_t)((r % 2) * 2 + r / 2) * nbls;
+        return po;
+    }
+    // Source chunks (reference cpu_simulate.py:939): chunk c covers catalog sources [c csz, min(nsrc, (c + 1) csz)); the
+    // compacted per-time arrays hold cap = source_buffer x csz sources.  Reserves those arrays in lanes [0, nl) and the
+    // above-horizon count of every (time, chunk).
+    struct Chunks {
+        int n;
+        int64_t csz, cap;
+        int nblk;  // horizon-cut blocks of a chunk
+    };
+    Chunks source_chunks(int nl) {
+        Chunks c;
+        c.n = (int)std::max<int64_t>(1, std::min<int64_t>(src_chunks, nsrc));
+        c.csz = std::max<int64_t>(cdiv(nsrc, c.n), 1);
+        c.cap = std::max<int64_t>((int64_t)std::ceil(c.csz * source_buffer), 1);
+        c.nblk = (int)cdiv(c.csz, 256);
+        for (int li = 0; li < nl; ++li) {
+            Lane &L = lanes[li];
+            L.d_xyz.reserve(sizeof(T) * 3 * c.cap);
+            L.d_az.reserve(sizeof(T) * c.cap);
+            L.d_za.reserve(sizeof(T) * c.cap);
+            L.d_srcidx.reserve(sizeof(int) * c.cap);
+            L.d_blockcnt.reserve(sizeof(int) * (c.nblk + 1));
+            L.d_blockoff.reserve(sizeof(int) * (c.nblk + 1));
+        }
+        reserve_mhist(sizeof(int) * rots.size() * std::max(1, src_chunks));
+        return c;
+    }
+
+    // ---- type-1 run: per time, per frequency batch: bin (source, freq) entries on periodic
+    // n2 x n2 planes, strengths, gather-spread, pruned FFT to the n_modes central modes, pick.
+    void run_type1(int t0, int t1, int f0, int f1, const OutBlock &o) {
+        const int nt = t1 - t0, nf = f1 - f0;
+        const int64_t per_tf = o.per_tf;
+        // host output: the lattice path computes a C3 block in 65 ms, so the 10-GB copy IS the call -- the caller's array
+        // is touched in parallel and pinned while the kernels run (HostPin), then one copy at PCIe rate (0.72 -> 0.3 s)
+        HostPin pin;
+        pin.drain_on = &stream;  // copy_block_pinned below rides on the main stream
+        if (o.drain) pin_block(o, pin, false);
+        const double sigma = this->sigma == 0.0 ? 2.0 : this->sigma;  // "auto" is a type-3 matter
+        sigma_run = sigma;
+        if (!t1fft) t1fft.reset(new Nufft3<T>(2, eps, sigma, stream));
+        const KerParams &ker = t1fft->ker;
+        // grid: n2 = P Q >= sigma n_modes (and >= 2 w), all n2 inputs live, n_modes + 1 outputs kept
+        DimGeom g;
+        g.n1 = t1_nmodes;
+        choose_pq(std::max((int)std::ceil(sigma * t1_nmodes), 2 * ker.w + 16), g);
+        g.na = g.n2;
+        g.no = t1_nmodes + 1;
+        t1fft->set_fft_geometry(g, g);
+        t1_dec.reserve(sizeof(T) * g.no);
+        hipLaunchKernelGGL(k_deconv_table<T>, dim3(cdiv(g.no, 256)), dim3(256), 0, stream, g.no,
+                           g.n2, ker, t1_dec.as<T>());
+        const int nb1 = (g.n2 + T1_PAD) >> BINLOG;
+        const std::array<int64_t, 16> pol_off = pol_offsets();
+        const Chunks ch = source_chunks(4);
+        const int nch = ch.n;
+        const int64_t csz = ch.csz, cap = ch.cap;
+        // frequencies per batch: bounded by entries (~1.3 per (source, freq)) and by grid bytes
+        const char *eb = std::getenv("FFTVIS_HIP_GRID_BYTES");
+        const double budget = eb ? std::atof(eb) : 8.0 * 1024 * 1024 * 1024;
+        const double plane_bytes = 2.0 * g.n2 * (double)g.n2 * tpol * sizeof(cplx<T>);
+        // entries per live (source, frequency) pair: 1 + the periodic images of footprints that cross an
+        // edge of the n2 x n2 plane -- (1 + (w + 1) / n2)^2 on average for uniformly placed sources (1.52
+        // at w = 16 on the smallest, 64-cell planes); 5 % head-room on top, and a catalog that still
+        // overflows (sources piled on a plane edge) fails the run (t1 overflow flag), never silently
+        const double img = (1.0 + (ker.w + 1.0) / g.n2) * (1.0 + (ker.w + 1.0) / g.n2) * 1.05;
+        int nfb = (int)std::max(1.0, std::min({(double)nf, budget / plane_bytes, 24.0e6 / (img * cap)}));
+        const int64_t ecap = (int64_t)(img * cap * nfb) + 4096;
+        const int nbins = nfb * nb1 * nb1;
+        const int rec = t1_record_bytes(ker.w, sizeof(T));
+        // Pipelined like the type-3 loop: the entry sort of unit (time, batch) u+1 (three kernels over
+        // every (source, frequency) pair, ~25 % of a step) runs on the low-priority stream beside the
+        // strengths / spread / FFT / pick of unit u; two sets of sort buffers and two sets of
+        // per-time source arrays alternate.
+        const char *ep = std::getenv("FFTVIS_HIP_PIPE");
+        const int nunits = nt * nch * (int)cdiv(nf, nfb);
+        const bool pipe = timing_level != 2 && nunits > 1 && !(ep && std::atoi(ep) == 0);
+        const hipStream_t ps = pipe ? prep_stream : stream;
+        for (int sset = 0; sset < (pipe ? 2 : 1); ++sset) {
+            t1_meta[sset].reserve(sizeof(int) * (2 * (size_t)(nbins + 1) + 2));
+            t1_binstart[sset].reserve(sizeof(int) * (nbins + 1));
+            t1_rec[sset].reserve((size_t)rec * ecap);
+        }
+        t1_cs.reserve(sizeof(cplx<T>) * ecap * tpol);
+        bool set_pending[2] = {false, false}, lane_pending[2] = {false, false};
+        lane_mode = -1;  // a type-3 run after this one drains the streams before it reuses the lanes
+        if (pipe) {  // the sort may start once the set-up queued on the main stream is done
+            FV_HIP(hipEventRecord(ev_start, stream));
+            FV_HIP(hipStreamWaitEvent(ps, ev_start, 0));
+        }
+        int unit = 0;
+
+        for (int tc = 0; tc < nt * nch; ++tc) {  // (time, source chunk), chunks innermost (cpu_simulate.py:936-939)
+            const int ti = t0 + tc / nch, chunk = tc % nch;
+            const int64_t s0 = (int64_t)chunk * csz, sn = std::min<int64_t>(csz, nsrc - s0);
+            if (nsrc == 0 || sn <= 0) continue;
+            const int li = pipe ? tc % 2 : 0;
+            Lane &L = lanes[li];
+            DevBuf &d_xyz = L.d_xyz, &d_az = L.d_az, &d_za = L.d_za, &d_srcidx = L.d_srcidx;
+            if (pipe && lane_pending[li]) FV_HIP(hipStreamWaitEvent(ps, L.done, 0));  // its strengths are done
+            size_t e0 = ev_begin(TM_PREP, ps);
+            const int *Mp = horizon_step(L, ti, cap, ch.nblk, ps, s0, sn, (int64_t)ti * nch + chunk);
+            ev_end(e0, ps);
+            mhist_log.push_back({ti * nch + chunk, 0.0});
+            const size_t hist_slot = mhist_log.size() - 1;
+            for (int fa = f0; fa < f1; fa += nfb, ++unit) {
+                const int nfg = std::min(nfb, f1 - fa);
+                const int ss = pipe ? unit % 2 : 0;
+                DevBuf &meta = t1_meta[ss], &binstart = t1_binstart[ss], &recs = t1_rec[ss];
+                T1Args a{};
+                a.n2 = g.n2;
+                a.nb1 = nb1;
+                a.w = ker.w;
+                a.nfg = nfg;
+                a.f_first = fa;
+                a.cap = cap;
+                a.ecap = ecap;
+                a.rec = rec;
+                const int nbn = nfg * nb1 * nb1;
+                int *counts_p = meta.as<int>(), *cursor_p = counts_p + (nbins + 1), *ovf_p = d_err.as<int>() + 1;
+                if (pipe && set_pending[ss]) FV_HIP(hipStreamWaitEvent(ps, lanes[ss].heavy_done, 0));
+                size_t e1 = ev_begin(TM_PREP, ps);
+                FV_HIP(hipMemsetAsync(meta.p, 0, sizeof(int) * (2 * (size_t)(nbins + 1) + 2), ps));
+                const dim3 gb((unsigned)cdiv(cap * nfg, 256));
+                hipLaunchKernelGGL((k_t1_bin<T, true>), gb, dim3(256), 0, ps, a, Mp, d_xyz.as<T>(),
+                                   d_freqs.as<double>(), counts_p, (const int *)nullptr, cursor_p,
+                                   (unsigned char *)nullptr, (T)ker.beta, (T)ker.c, ovf_p);
+                t1fft->stream = ps;
+                t1fft->exclusive_scan(counts_p, binstart.as<int>(), nbn);
+                t1fft->stream = stream;
+                hipLaunchKernelGGL((ker.w == 9 ? k_t1_bin<T, false, 9> : ker.w == 5 ? k_t1_bin<T, false, 5> : ker.w == 7 ? k_t1_bin<T, false, 7> : k_t1_bin<T, false, 0>), gb, dim3(256), 0, ps, a, Mp,
+                                   d_xyz.as<T>(), d_freqs.as<double>(), counts_p, (const int *)binstart.as<int>(),
+                                   cursor_p, recs.as<unsigned char>(), (T)ker.beta, (T)ker.c, ovf_p);
+                ev_end(e1, ps);
+                if (pipe) {
+                    FV_HIP(hipEventRecord(lanes[ss].prep_done, ps));
+                    FV_HIP(hipStreamWaitEvent(stream, lanes[ss].prep_done, 0));
+                }
+                const int *nent = binstart.as<int>() + nbn;
+                for (const Pair &pr : pairs) {
+                    if (pr.n == 0) continue;
+                    size_t e2 = ev_begin(TM_STRENGTHS, stream);
+                    StrengthArgs sa{};
+                    sa.M = cap;
+                    sa.nfg = nfg;
+                    sa.f_first = fa;
+                    sa.nfreq = nfreq_cat;
+                    sa.polarized = polarized;
+                    sa.pol_sky = pol_sky;
+                    sa.same_beam = pr.bi == pr.bj;
+                    // Hermitian packing: two planes per frequency instead of four for a single-beam pair
+                    const bool herm1 = polarized && pr.bi == pr.bj && std::getenv("FFTVIS_HIP_NO_HERMITIAN") == nullptr;
+                    const int tg = herm1 ? 2 : tpol;
+                    sa.herm = herm1;
+                    sa.dim = 2;
+                    sa.bi = desc(pr.bi);
+                    sa.bj = desc(pr.bj);
+                    hipLaunchKernelGGL((beam_order == 3 ? k_t1_strengths<T, 3> : beam_order == 1 ? k_t1_strengths<T, 1> : k_t1_strengths<T, 0>),
+                                       dim3(cdiv(ecap, 256)), dim3(256), 0, stream,
+                                       sa, nent, ecap, (const unsigned char *)recs.as<unsigned char>(), rec,
+                                       d_srcidx.as<int>(),
+                                       d_az.as<T>(), d_za.as<T>(), d_flux.p, d_freqs.as<double>(),
+                                       t1_cs.as<cplx<T>>());
+                    ev_end(e2, stream);
+                    const int nplanes = nfg * tg;
+                    cplx<T> *A = t1fft->fft_input(nplanes);
+                    size_t e3 = ev_begin(TM_SPREAD, stream);
+                    const dim3 gs((unsigned)cdiv(g.n2 >> (BINLOG + 1), 4), (unsigned)(g.n2 >> (BINLOG + 1)), (unsigned)nfg);  // 16 x 16 cells per wave
+                    // fp64: the accumulation on the matrix pipe (FFTVIS_HIP_T1_MM=0: the vector version)
+                    static const bool t1_mm = !(std::getenv("FFTVIS_HIP_T1_MM") && std::atoi(std::getenv("FFTVIS_HIP_T1_MM")) == 0);
+                    void (*kspread)(T1Args, const unsigned char *, const int *, const cplx<T> *, cplx<T> *) = nullptr;
+                    if constexpr (sizeof(T) == 8)
+                        if (t1_mm) kspread = herm1 ? k_t1_spread_mm<2> : polarized ? k_t1_spread_mm<4> : k_t1_spread_mm<1>;
+                    if (!kspread) kspread = herm1 ? k_t1_spread<T, 2> : polarized ? k_t1_spread<T, 4> : k_t1_spread<T, 1>;
+                    hipLaunchKernelGGL(kspread, gs, dim3(SPREAD_THREADS), 0, stream, a, (const unsigned char *)recs.as<unsigned char>(),
+                                       (const int *)binstart.as<int>(), (const cplx<T> *)t1_cs.as<cplx<T>>(), A);
+                    ev_end(e3, stream);
+                    st[ST_SPREAD_LAUNCHES] += 1;
+                    st[ST_SPREAD_CELLS] += (double)g.n2 * g.n2 * nplanes;
+                    mhist_log[hist_slot].second += nplanes;
+                    size_t e4 = ev_begin(TM_FFT, stream);
+                    t1fft->fft(nplanes);
+                    ev_end(e4, stream);
+                    st[ST_FFT_CELLS] += ((double)g.n2 * g.n2 + 2.0 * g.no * g.n2 + (double)g.no * g.no) * nplanes;
+                    size_t e5 = ev_begin(TM_INTERP, stream);
+                    cplx<T> *obase = o.dout + ((int64_t)(fa - f0) * nt + (ti - t0)) * per_tf;
+                    hipLaunchKernelGGL(k_t1_pick<T>, dim3(cdiv(pr.n * nfg, 256)), dim3(256), 0, stream,
+                                       t1fft->fft_output(), g.no, g.P, g.cnt(), nfg, tg,
+                                       (const int *)d_blint.as<int>(),
+                                       (const int *)d_blint.as<int>() + nbls, pr.n,
+                                       pr.trivial0 ? (const int *)nullptr : (const int *)(pr.idx0 ? pr.idx0 : pr.idx)->template as<int>(),
+                                       pr.trivial0 ? (const signed char *)nullptr
+                                                   : (const signed char *)(pr.flip0 ? pr.flip0 : pr.flip)->template as<signed char>(),
+                                       (const T *)t1_dec.as<T>(), obase, (int64_t)nt * per_tf, pol_off[0],
+                                       pol_off[1], pol_off[2], pol_off[3], chunk > 0, herm1, !reference_compat);
+                    ev_end(e5, stream);
+                    st[ST_GATHERED] += (double)pr.n * nplanes;
+                    st[ST_N2X] = g.n2;
+                    st[ST_N2Y] = g.n2;
+                    st[ST_NA_XY] = g.n2 * 65536.0 + g.n2;
+                    st[ST_W] = ker.w;
+                }
+                if (pipe) {
+                    FV_HIP(hipEventRecord(lanes[ss].heavy_done, stream));
+                    set_pending[ss] = true;
+                }
+            }
+            if (pipe) {
+                FV_HIP(hipEventRecord(L.done, stream));
+                lane_pending[li] = true;
+            }
+        }
+        if (!o.on_device) {
+            copy_block_to_host(o, o.drain && pin.wait(), stream);
+            FV_HIP(hipStreamSynchronize(stream));
+            if (timing_level) ev_collect();
+            check_errors();
+        }
+    }
+
+
+    // ---- type-3 run ---------------------------------------------------------------------------------------------------
+    // What a run decides, stage by stage (the functions below, in the order run() calls them); launch_strengths and the
+    // unit loop read it.
+    struct RunPlan {
+        int t0, t1, f0, f1, nt, nf;
+        double xc[3], X[3];  // box of the sources (source_box)
+        int D = 2;           // dimensions of the transforms
+        // height terms (height_terms, light_classes)
+        int K = 0;  // terms (0: no expansion)
+        double zc = 0.0, zh = 0.0, a = 0.0;
+        int k0 = 0, k1 = 0;
+        double eps_l[2] = {0.0, 0.0};
+        int ncls = 1;  // plan classes in use (Lane::plan)
+        // transforms per frequency on the grid (largest over the pairs), upsampling factor, grid-buffer cells per
+        // transform at the top frequency, frequency groups (grid_and_groups)
+        int tg_max = 1;
+        double sigma = 2.0, cells_top = 1.0;
+        std::vector<std::pair<int, int>> groups;
+        // lane schedule (lane_schedule)
+        int nlanes = 1, nlanes_used = 1;
+        bool pipe = false, gang = false;
+        Chunks ch{};
+        // the plan class of height term kt: the run's own plan, or a light class's
+        int cls(int kt) const { return k0 > 0 && kt >= k0 ? (kt >= k1 ? 2 : 1) : 0; }
+    };
+
+    void run(int t0, int t1, int f0, int f1, void *out, int out_on_device) override {
+        check_run(t0, t1, f0, f1);
+        if (mhist_log.size() > 65536) mhist_log.clear();  // nobody asked for the statistics of those runs
+        const OutBlock o = out_block(t1 - t0, f1 - f0, out, out_on_device);
         if (type1) {
-            run_type1(t0, t1, f0, f1, out, out_on_device);
+            run_type1(t0, t1, f0, f1, o);
             return;
         }
-        const int nt = t1 - t0, nf = f1 - f0;
-        // destination layout of this run (fv_sim_run_into), consumed here
-        const int64_t out_fs = out_f_stride ? out_f_stride : (int64_t)nt * tpol * nbls;
-        const bool shared = out_shared != 0;
-        out_f_stride = 0;
-        out_shared = 0;
-        FV_REQUIRE(out_fs >= (int64_t)nt * tpol * nbls, "fv_sim_run_into: the channel stride is shorter than a channel's run");
-        // height terms instead of a third grid dimension (see wt_K)
-        double xc[3], X[3];
-        source_box(xc, X);
-        wt_K = 0;
-        wt_a = 0.0;
+        // the helper touches and pins the caller's array once the first unit is queued: started at once, its sixteen page-
+        // faulting threads slowed the main thread's set-up and first launches (first unit queued after 95 ms instead of 50)
+        Drain dr;
+        dr.pin.drain_on = &copy_stream;
+        dr.pin.mark();
+        static const bool pin_early = std::getenv("FFTVIS_HIP_PIN_EARLY") != nullptr;
+        if (o.drain && pin_early) pin_output(o, dr);
+
+        RunPlan r{t0, t1, f0, f1, t1 - t0, f1 - f0};
+        source_box(r.xc, r.X);
+        height_terms(r);
+        pair_setup(r);
+        grid_and_groups(r);
+        light_classes(r);
+        lane_schedule(r);
+        lane_plans(r);
+        r.ch = source_chunks(r.nlanes_used);
+        if (dr.dbg) std::fprintf(stderr, "run: set-up done %.3f s (lanes, unique targets, groups)\n", dr.pin.since());
+        lane_buffers(r);
+        if (dr.dbg) std::fprintf(stderr, "run: buffers and column plans %.3f s\n", dr.pin.since());
+        queue_units(r, o, dr);
+        finish_output(o, dr);
+    }
+
+    // Height terms ("w-term expansion"): a non-coplanar array whose heights are small against the wavelength -- every
+    // surveyed real array: centimetres to decimetres after the plane fit -- does not need a third grid dimension.
+    // exp(i z s_z), z the sources' height coordinate in [zc - zh, zc + zh], s_z = nu b_z, is expanded in Chebyshev
+    // polynomials of t = (z - zc) / zh (Jacobi - Anger: exp(i a t) = J_0(a) + 2 sum_k i^k J_k(a) T_k(t)):
+    //     V(s) = sum_k  exp(i zc s_z) c_k(zh s_z)  F_k(s_x, s_y),   c_0 = J_0, c_k = 2 i^k J_k,   F_k = 2-D transform of c_j T_k(t_j),
+    // K terms with 2 (a / 2)^K / K! <= eps / 10, a = zh max|s_z| (|J_k(a)| <= (a / 2)^k / k!): K 2-D transforms (7 for 3 cm of
+    // scatter at 200 MHz; the Taylor series about zc this replaced needed a^K / K! <= eps / 10: 8) with all of the 2-D
+    // machinery (Hermitian packing, column plan, source disc) instead of a 3-D grid whose third dimension is all kernel
+    // width (16 planes for a source range of 1.4 cells) plus a z-pass.  The terms carry the transform's relative error
+    // each, |T_k| <= 1, summed with weights |c_k| (sum <= 2 e^{a/2} - 1): the 2-D plans run at eps / (2 e^{a/2} - 1).
+    // Taken while K <= 16 (|b_z| up to metres); beyond, or with FFTVIS_HIP_NO_WTERM=1, the 3-D transform runs.
+    void height_terms(RunPlan &r) {
         if (!coplanar && !std::getenv("FFTVIS_HIP_NO_WTERM")) {
-            double fmax = 0, bz = 0;
-            for (int f = f0; f < f1; ++f) fmax = std::max(fmax, std::fabs(freqs[f]));
+            double bz = 0;
             for (const Pair &p : pairs)
                 if (p.n) bz = std::max(bz, p.Bs[2]);
-            const double a = X[2] * fmax * bz;  // largest |(z - zc) s_z|
+            const double a = r.X[2] * fmax_of(r.f0, r.f1) * bz;  // largest |(z - zc) s_z|
             int K = 1;
             double term = a;  // 2 (a / 2)^K / K!: bound of the first neglected coefficient 2 |J_K|
             while (term > 0.1 * eps && K < 64) {
@@ -2716,222 +2775,190 @@ class Sim : public SimBase {
             }
             const char *ek = std::getenv("FFTVIS_HIP_WTERM_MAX");
             if (K <= (ek ? std::atoi(ek) : 16)) {
-                wt_K = K;
-                wt_zc = xc[2];
-                wt_zh = X[2];
-                wt_a = a;
+                r.K = K;
+                r.zc = r.xc[2];
+                r.zh = r.X[2];
+                r.a = a;
             }
         }
-        wt_k0 = 0;
-        wt_k1 = wt_K;
-        wt_eps_l[0] = wt_eps_l[1] = 0.0;
-        if (wt_K >= 3 && sizeof(T) == 8 && this->sigma == 2.0 && !std::getenv("FFTVIS_HIP_NO_WTERM_LIGHT")) {
-            std::vector<double> ck(wt_K);
+        r.D = r.K ? 2 : dim();
+        st[ST_HEIGHT_TERMS] = r.K;
+    }
+    // Light terms: term k enters with weight |c_k| <= 2 (a / 2)^k / k!, so the higher terms need far less than the run's
+    // tolerance -- with a = 0.35 (3 cm of scatter at 200 MHz) |c_2| = 0.03, |c_4| = 8e-5.  The terms k >= k0 run on a
+    // second plan at eps_l = 0.3 eps / sum_{k >= k0} |c_k| and sigma = 1.25 (a grid of 0.39 x the cells: the FFT passes
+    // are the bulk of a term), chosen as the smallest k0 whose tolerance is above that sigma's floor by a decade; fp64,
+    // runs at sigma = 2 on large grids only.  k0 = 0: every term on the run's own plan.  FFTVIS_HIP_NO_WTERM_LIGHT=1.
+    // Where the tail of the light terms can take a tolerance of 1e-4 or looser (a kernel of 8 cells instead of 12: the
+    // gather of a light term is most of its time) the light terms split in two classes, [k0, k1) and [k1, K), with half
+    // of the budget each; k1 = K: one class.
+    void light_classes(RunPlan &r) {
+        r.k0 = 0;
+        r.k1 = r.K;
+        if (r.K >= 3 && sizeof(T) == 8 && this->sigma == 2.0 && !std::getenv("FFTVIS_HIP_NO_WTERM_LIGHT")) {
+            std::vector<double> ck(r.K);
             double c = 1.0;  // (a / 2)^k / k!
-            for (int k = 0; k < wt_K; ++k) {
+            for (int k = 0; k < r.K; ++k) {
                 ck[k] = (k ? 2.0 : 1.0) * c;
-                c *= 0.5 * wt_a / (k + 1);
+                c *= 0.5 * r.a / (k + 1);
             }
-            for (int k0 = 1; k0 + 2 <= wt_K; ++k0) {  // at least two light terms
+            for (int k0 = 1; k0 + 2 <= r.K; ++k0) {  // at least two light terms
                 double sl = 0;
-                for (int k = k0; k < wt_K; ++k) sl += ck[k];
+                for (int k = k0; k < r.K; ++k) sl += ck[k];
                 const double el = 0.3 * eps / sl;
                 if (el >= 1e-7) {
-                    wt_k0 = k0;
-                    wt_eps_l[0] = std::min(el, 1e-2);
+                    r.k0 = k0;
+                    r.eps_l[0] = std::min(el, 1e-2);
                     break;
                 }
             }
             // a second class for the tail, where it can run at 1e-4 or looser: half of the light budget each
-            if (wt_k0 > 0 && !std::getenv("FFTVIS_HIP_WTERM_ONE_LIGHT_CLASS")) {
-                for (int k1 = wt_k0 + 1; k1 + 2 <= wt_K; ++k1) {
+            if (r.k0 > 0 && !std::getenv("FFTVIS_HIP_WTERM_ONE_LIGHT_CLASS")) {
+                for (int k1 = r.k0 + 1; k1 + 2 <= r.K; ++k1) {
                     double s2 = 0, s1 = 0;
-                    for (int k = k1; k < wt_K; ++k) s2 += ck[k];
-                    for (int k = wt_k0; k < k1; ++k) s1 += ck[k];
+                    for (int k = k1; k < r.K; ++k) s2 += ck[k];
+                    for (int k = r.k0; k < k1; ++k) s1 += ck[k];
                     const double e2 = 0.15 * eps / s2, e1 = 0.15 * eps / s1;
                     if (e2 >= 1e-4 && e1 >= 1e-7) {
-                        wt_k1 = k1;
-                        wt_eps_l[0] = std::min(e1, 1e-2);
-                        wt_eps_l[1] = std::min(e2, 1e-2);
+                        r.k1 = k1;
+                        r.eps_l[0] = std::min(e1, 1e-2);
+                        r.eps_l[1] = std::min(e2, 1e-2);
                         break;
                     }
                 }
             }
         }
-        const int D = wt_K ? 2 : dim();
-        run_D = D;
-        st[15] = wt_K;
-        const int64_t per_tf = (int64_t)tpol * nbls;   // elements per (freq, time)
-        const size_t out_bytes = sizeof(cplx<T>) * (size_t)nf * nt * per_tf;
-        cplx<T> *dout;
-        if (out_on_device) {
-            dout = (cplx<T> *)out;
-        } else {
-            d_out.reserve(std::max<size_t>(out_bytes, 16));
-            dout = d_out.as<cplx<T>>();
-        }
-        // Baselines not covered by any pair stay zero (reference zero-initialises, :909-911).
-        FV_HIP(hipMemsetAsync(dout, 0, out_bytes, stream));
-        reserve_mhist(sizeof(int) * rots.size() * std::max(1, src_chunks));
-        const size_t run_bytes = sizeof(cplx<T>) * (size_t)nt * per_tf;
-        // (a block inside a larger array is pinned run by run: only worth it -- and only safe against two runs meeting in
-        // one page -- when the runs are long)
-        const bool pinnable = out_fs == (int64_t)nt * per_tf || (run_bytes >= ((size_t)1 << 20) && (size_t)(out_fs - (int64_t)nt * per_tf) * sizeof(cplx<T>) >= 8192);
-        const bool drain = !out_on_device && out_bytes >= drain_min_bytes() && pinnable;
-        std::vector<DrainItem> drain_items;
-        size_t drained = 0;
-        // the helper touches and pins the caller's array once the first unit is queued: started at once, its sixteen page-
-        // faulting threads slowed the main thread's set-up and first launches (first unit queued after 95 ms instead of 50)
-        HostPin pin;
-        pin.drain_on = &copy_stream;
-        pin.mark();
-        bool pin_started = false;
-        static const bool pin_early = std::getenv("FFTVIS_HIP_PIN_EARLY") != nullptr;
-        if (drain && pin_early) {
-            pin.start(device, out, (size_t)nf, run_bytes, sizeof(cplx<T>) * (size_t)out_fs, shared, true);
-            pin_started = true;
-        }
+        // (sigma = 1.25 pays on large grids only, as in the automatic choice; FFTVIS_HIP_WTERM_LIGHT_CELLS moves the bound: tests)
+        const char *elc = std::getenv("FFTVIS_HIP_WTERM_LIGHT_CELLS");
+        if (r.k0 > 0 && r.cells_top < (elc ? std::atof(elc) : 4.0e6)) r.k0 = 0;
+        if (r.k0 == 0) r.k1 = r.K;
+        r.ncls = r.k0 == 0 ? 1 : r.k1 < r.K ? 3 : 2;
+        st[ST_LIGHT_FROM] = r.k0;
+        st[ST_LIGHTER_FROM] = r.k0 > 0 && r.k1 < r.K ? r.k1 : 0;
+    }
 
-        int64_t pol_off[16] = {0};
-        if (polarized)
-            for (int r = 0; r < 4; ++r) pol_off[r] = (int64_t)((r % 2) * 2 + r / 2) * nbls;
-
-        // source chunks: chunk c covers catalog sources [c csz, min(nsrc, (c + 1) csz)); the compacted
-        // per-time arrays hold source_buffer x csz sources
-        const int nch = (int)std::max<int64_t>(1, std::min<int64_t>(src_chunks, nsrc));
-        const int64_t csz = std::max<int64_t>(cdiv(nsrc, nch), 1);
-        const int64_t cap = std::max<int64_t>((int64_t)std::ceil(csz * source_buffer), 1);
-        const int nblk = (int)cdiv(csz, 256);
-
-        // Upsampling factor "auto" (fv_sim_create upsampfac = 0): sigma = 1.25 shrinks the fine grid and
-        // all FFT work by (2 / 1.25)^D at the price of a kernel 13-14 cells wide instead of 9 (every
-        // source and target costs ~2x in 2-D), with NUFFT errors at or below sigma = 2's down to
-        // eps ~ 1e-8 (fv_eskernel.h).  It pays when the FFT dominates: C3 (8192^2 cells, 1.1e5 points
-        // per transform) 3.06 -> 1.57 s per step; C2 (1024 x 512, 5.7e3) would lose, 1.38 -> 1.58 ms.
-        // Hermitian packing (k_interp<.., HERM>): a pair whose two beams are the same has Hermitian
-        // strengths -- c_00, c_11 real, c_10 = conj(c_01) -- so two transforms per frequency (c_00 + i c_11,
-        // c_01) evaluated at the baseline and at its mirror image give all four products: half the
-        // spread, FFT and grid traffic of a polarized run.  The mirror targets need a box that is
-        // symmetric about 0; taken when that box costs at most 1.5x the cells of the tight one and
-        // the grid is large (small grids keep four transforms and the fused gather).  In eigenbeam mode the
-        // diagonal (k, k) terms qualify.  FFTVIS_HIP_NO_HERMITIAN=1 turns it off.
-        {
-            const bool herm_off = std::getenv("FFTVIS_HIP_NO_HERMITIAN") != nullptr;  // read per run: tests flip it
-            const KerParams k2 = make_kernel(eps, 2.0);
-            double fmax = 0;
-            for (int f = f0; f < f1; ++f) fmax = std::max(fmax, std::fabs(freqs[f]));
-            for (Pair &p : pairs) {
-                p.herm = 0;
-                if (!polarized || herm_off || p.n == 0) continue;
-                // 1: same beam on both sides (Hermitian strengths; eigenbeams: the (k, k) terms);
-                // 2: two different beams whose Jones matrices are real, unpolarized sky (all products real)
-                const int mode = p.bi == p.bj ? 1 : (!pol_sky && beams[p.bi].real_valued && beams[p.bj].real_valued ? 2 : 0);
-                if (!mode) continue;
-                double cs = 1.0, ct = 1.0;
-                for (int d = 0; d < D; ++d) {
-                    DimGeom gs, gt;
-                    gs.X = gt.X = X[d];
-                    gs.B = p.Bs[d];
-                    gt.B = p.B[d];
-                    set_dim_geom(gs, 2.0, k2.w, fmax, d == D - 1);
-                    set_dim_geom(gt, 2.0, k2.w, fmax, d == D - 1);
-                    cs *= gs.n2;
-                    ct *= gt.n2;
-                }
-                p.herm = cs >= 4.0e6 && cs <= 1.5 * ct ? mode : 0;
+    // Hermitian packing (k_interp<.., HERM>): a pair whose two beams are the same has Hermitian
+    // strengths -- c_00, c_11 real, c_10 = conj(c_01) -- so two transforms per frequency (c_00 + i c_11,
+    // c_01) evaluated at the baseline and at its mirror image give all four products: half the
+    // spread, FFT and grid traffic of a polarized run.  The mirror targets need a box that is
+    // symmetric about 0; taken when that box costs at most 1.5x the cells of the tight one and
+    // the grid is large (small grids keep four transforms and the fused gather).  In eigenbeam mode the
+    // diagonal (k, k) terms qualify.  FFTVIS_HIP_NO_HERMITIAN=1 turns it off.
+    void pair_setup(RunPlan &r) {
+        const bool herm_off = std::getenv("FFTVIS_HIP_NO_HERMITIAN") != nullptr;  // read per run: tests flip it
+        const KerParams k2 = make_kernel(eps, 2.0);
+        const double fmax = fmax_of(r.f0, r.f1);
+        for (Pair &p : pairs) {
+            p.herm = 0;
+            if (!polarized || herm_off || p.n == 0) continue;
+            // 1: same beam on both sides (Hermitian strengths; eigenbeams: the (k, k) terms);
+            // 2: two different beams whose Jones matrices are real, unpolarized sky (all products real)
+            const int mode = p.bi == p.bj ? 1 : (!pol_sky && beams[p.bi].real_valued && beams[p.bj].real_valued ? 2 : 0);
+            if (!mode) continue;
+            double cs = 1.0, ct = 1.0;
+            for (int d = 0; d < r.D; ++d) {
+                DimGeom gs, gt;
+                gs.X = gt.X = r.X[d];
+                gs.B = p.Bs[d];
+                gt.B = p.B[d];
+                set_dim_geom(gs, 2.0, k2.w, fmax, d == r.D - 1);
+                set_dim_geom(gt, 2.0, k2.w, fmax, d == r.D - 1);
+                cs *= gs.n2;
+                ct *= gt.n2;
             }
-            // reference_compat off, eigenbeams: an off-diagonal pair that is not packed gathers its (l, k) term
-            // at -b: its targets need the symmetric box too
-            for (Pair &p : pairs) p.mirror = nbasis && !reference_compat && p.bi != p.bj && !p.herm && p.n > 0;
-            // redundant baselines -> one gather target each; the tolerance follows the engine's eps and the highest
-            // frequency it knows (not the block's: blocks of a sharded run then agree on the runs)
-            double fall = 0;
-            for (double f : freqs) fall = std::max(fall, std::fabs(f));
-            const double tol = 1e-3 * eps / (2.0 * M_PI * std::max(fall, 1.0));
-            for (Pair &p : pairs) {
-                build_unique(p, tol);
-                pair_mirror_runs(p, tol);
-            }
+            p.herm = cs >= 4.0e6 && cs <= 1.5 * ct ? mode : 0;
         }
-        int tg_max = 1;  // transforms per frequency on the grid, largest over the pairs
+        // reference_compat off, eigenbeams: an off-diagonal pair that is not packed gathers its (l, k) term
+        // at -b: its targets need the symmetric box too
+        for (Pair &p : pairs) p.mirror = nbasis && !reference_compat && p.bi != p.bj && !p.herm && p.n > 0;
+        const double tol = dedup_tol();
+        for (Pair &p : pairs) {
+            build_unique(p, tol, r.K ? 2 : 3);
+            pair_mirror_runs(p, tol);
+        }
         for (const Pair &p : pairs)
-            if (p.n) tg_max = std::max(tg_max, p.herm ? 2 : tpol);
-        double sigma = this->sigma;
-        if (sigma == 0.0) {
+            if (p.n) r.tg_max = std::max(r.tg_max, p.herm ? 2 : tpol);
+    }
+
+    // Upsampling factor "auto" (fv_sim_create upsampfac = 0): sigma = 1.25 shrinks the fine grid and
+    // all FFT work by (2 / 1.25)^D at the price of a kernel 13-14 cells wide instead of 9 (every
+    // source and target costs ~2x in 2-D), with NUFFT errors at or below sigma = 2's down to
+    // eps ~ 1e-8 (fv_eskernel.h).  It pays when the FFT dominates: C3 (8192^2 cells, 1.1e5 points
+    // per transform) 3.06 -> 1.57 s per step; C2 (1024 x 512, 5.7e3) would lose, 1.38 -> 1.58 ms.
+    // Then the grid-buffer cells per transform at the top frequency, for the grouping heuristic, and the groups.
+    void grid_and_groups(RunPlan &r) {
+        r.sigma = this->sigma;
+        if (r.sigma == 0.0) {
             int64_t nmax = 0;
             for (const Pair &p : pairs) nmax = std::max<int64_t>(nmax, p.n);
-            const double cells2 = cells_at_sigma2(X, D, f0, f1, [](const Pair &p) { return p.box_B(); });
-            sigma = auto_sigma(cells2, 0.5 * (double)nsrc + (double)nmax, D);
+            const double cells2 = cells_at_sigma2(r.X, r.D, r.f0, r.f1, [](const Pair &p) { return p.box_B(); });
+            r.sigma = auto_sigma(cells2, 0.5 * (double)nsrc + (double)nmax, r.D);
         }
-        sigma_run = sigma;
-        st[10] = sigma;
-        // grid-buffer cells per transform at the top frequency, for the grouping heuristic
-        double cells_top = 1.0;
-        {
-            KerParams k = make_kernel(eps, sigma);
-            double fmax = 0;
-            for (int f = f0; f < f1; ++f) fmax = std::max(fmax, std::fabs(freqs[f]));
-            double na[3] = {1, 1, 1}, no[3] = {1, 1, 1};
-            for (int d = 0; d < D; ++d) {
-                DimGeom g;
-                g.X = X[d];
-                double Bm = 0;
-                for (const Pair &p : pairs) Bm = std::max(Bm, p.box_B()[d]);
-                g.B = Bm;
-                set_dim_geom(g, sigma, k.w, fmax, d == D - 1);
-                na[d] = g.na;
-                no[d] = g.no;
-            }
-            cells_top = 2.0 * std::max({na[2] * na[1] * na[0], na[2] * na[1] * no[0], na[2] * no[0] * no[1],
-                                         no[2] * no[0] * no[1]});
+        sigma_run = r.sigma;
+        st[ST_SIGMA] = r.sigma;
+        const KerParams k = make_kernel(eps, r.sigma);
+        const double fmax = fmax_of(r.f0, r.f1);
+        double na[3] = {1, 1, 1}, no[3] = {1, 1, 1};
+        for (int d = 0; d < r.D; ++d) {
+            DimGeom g;
+            g.X = r.X[d];
+            double Bm = 0;
+            for (const Pair &p : pairs) Bm = std::max(Bm, p.box_B()[d]);
+            g.B = Bm;
+            set_dim_geom(g, r.sigma, k.w, fmax, d == r.D - 1);
+            na[d] = g.na;
+            no[d] = g.no;
         }
-        const auto groups = freq_groups(f0, f1, cells_top, tg_max);
+        r.cells_top = 2.0 * std::max({na[2] * na[1] * na[0], na[2] * na[1] * no[0], na[2] * no[0] * no[1], no[2] * no[0] * no[1]});
+        r.groups = freq_groups(r.f0, r.f1, r.cells_top, r.tg_max);
+    }
 
-        // two lanes while a group's grid buffers are small (launch-bound regime), else one
+    // Two lanes always (two sets of per-time scratch and grid buffers; consecutive time steps alternate), memory
+    // permitting.  Small grids (launch-bound) run them pipelined, see below.  Large grids (C3: 6 GiB of grid per
+    // launch) run them FREELY on two streams of equal priority: the kernels of two time steps then share the
+    // dispatcher like the kernels of two processes do -- a row pass of one step beside the spread or the gather of
+    // the other, compute-bound waves beside memory-bound ones -- which is what two ranks on one GPU had over one
+    // (843 against 883 ms per C3 step): 883 -> 844 ms in-process.  (With the second stream at a lower priority it
+    // only ever filled the first one's tails: 868.)  Kernel durations measured in this mode are those of kernels
+    // sharing the GPU.  FFTVIS_HIP_LANES=1: one stream.
+    void lane_schedule(RunPlan &r) {
         int max_ntrans = 1;
-        for (const auto &grp : groups) max_ntrans = std::max(max_ntrans, (grp.second - grp.first) * tg_max);
-        // Two lanes always (two sets of per-time scratch and grid buffers; consecutive time steps alternate), memory
-        // permitting.  Small grids (launch-bound) run them pipelined, see below.  Large grids (C3: 6 GiB of grid per
-        // launch) run them FREELY on two streams of equal priority: the kernels of two time steps then share the
-        // dispatcher like the kernels of two processes do -- a row pass of one step beside the spread or the gather of
-        // the other, compute-bound waves beside memory-bound ones -- which is what two ranks on one GPU had over one
-        // (843 against 883 ms per C3 step): 883 -> 844 ms in-process.  (With the second stream at a lower priority it
-        // only ever filled the first one's tails: 868.)  Kernel durations measured in this mode are those of kernels
-        // sharing the GPU.  FFTVIS_HIP_LANES=1: one stream.
-        const bool big_grids = cells_top * sizeof(cplx<T>) * max_ntrans > 1.5 * 1024 * 1024 * 1024;
+        for (const auto &grp : r.groups) max_ntrans = std::max(max_ntrans, (grp.second - grp.first) * r.tg_max);
+        const bool big_grids = r.cells_top * sizeof(cplx<T>) * max_ntrans > 1.5 * 1024 * 1024 * 1024;
         const char *el = std::getenv("FFTVIS_HIP_LANES");
         int nlanes = el ? std::atoi(el) : 2;
         if (!el && big_grids) {  // a second set of grid buffers must fit comfortably
             size_t mfree = 0, mtotal = 0;
             FV_HIP(hipMemGetInfo(&mfree, &mtotal));
-            if (4.0 * cells_top * sizeof(cplx<T>) * max_ntrans > 0.5 * (double)mtotal) nlanes = 1;
+            if (4.0 * r.cells_top * sizeof(cplx<T>) * max_ntrans > 0.5 * (double)mtotal) nlanes = 1;
         }
         const char *ep = std::getenv("FFTVIS_HIP_PIPE");
         const bool pipe_wanted = ep ? std::atoi(ep) != 0 : !big_grids;
-        nlanes = std::max(1, std::min(pipe_wanted ? 2 : 4, std::min(nlanes, nt)));
+        nlanes = std::max(1, std::min(pipe_wanted ? 2 : 4, std::min(nlanes, r.nt)));
         if (timing_level == 2) nlanes = 1;  // per-family event brackets only make sense on one stream
+        r.nlanes = nlanes;
         // Two lanes, pipelined (default): every big kernel runs on the main (high-priority) stream,
         // one time step after the other, so kernel durations stay uncontended; the dozen tiny
         // latency-bound preparation kernels of step t+1 (rotation, horizon cut, bin sort, weight
         // tables) run on a low-priority stream beside step t's big kernels and fill their ramps
         // and tails.  FFTVIS_HIP_PIPE=0: the two lanes run freely on two streams instead.
-        const bool pipe = nlanes > 1 && pipe_wanted;
+        r.pipe = nlanes > 1 && pipe_wanted;
         // Gang mode (pipelined 2-D runs): two consecutive time steps share one launch each of the
         // spread and of every FFT pass (grid.y = 2: same geometry, their own sources and grids), which
         // halves the kernel boundaries per time step and doubles the workgroups that hide each other's
         // latency chains and tails.  Two pairs of lanes alternate, so that the preparation of the next
         // pair still runs beside this pair's big kernels.  FFTVIS_HIP_GANG=0 turns it off.
         const char *eg = std::getenv("FFTVIS_HIP_GANG");
-        const bool gang = pipe && D == 2 && nt >= 2 && timing_level != 2 && !(eg && std::atoi(eg) == 0);
-        const int nlanes_used = gang ? 4 : nlanes;
+        r.gang = r.pipe && r.D == 2 && r.nt >= 2 && timing_level != 2 && !(eg && std::atoi(eg) == 0);
+        r.nlanes_used = r.gang ? 4 : nlanes;
         // Lane scratch outlives a run: with a device-side output buffer nothing synchronises between
         // two fv_sim_run calls, so the "last big kernels of this lane" events carry over (the next
         // run's first preparation waits for them) and the lane rotation continues where the previous
         // run stopped -- its first unit then takes the lanes that have been idle longest and prepares
         // beside the previous run's last big kernels.  A change of mode drains the streams instead.
-        const int mode = gang ? 2 : pipe ? 1 : 0;
-        st[16] = nlanes;
-        st[17] = mode;
+        const int mode = r.gang ? 2 : r.pipe ? 1 : 0;
+        st[ST_LANES] = nlanes;
+        st[ST_LANE_MODE] = mode;
         if (mode != lane_mode) {
             FV_HIP(hipStreamSynchronize(stream));
             FV_HIP(hipStreamSynchronize(prep_stream));
@@ -2941,7 +2968,7 @@ class Sim : public SimBase {
             lane_mode = mode;
             lane_serial = 0;
         }
-        if (nlanes > 2 && !pipe) {  // FFTVIS_HIP_LANES = 3 | 4: their streams, at the main stream's priority
+        if (nlanes > 2 && !r.pipe) {  // FFTVIS_HIP_LANES = 3 | 4: their streams, at the main stream's priority
             int prio_least = 0, prio_greatest = 0;
             FV_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
             for (int li = 2; li < nlanes; ++li)
@@ -2950,134 +2977,99 @@ class Sim : public SimBase {
                     lanes[li].own_stream = true;
                 }
         }
-        {  // (sigma = 1.25 pays on large grids only, as in the automatic choice; FFTVIS_HIP_WTERM_LIGHT_CELLS moves the bound: tests)
-            const char *elc = std::getenv("FFTVIS_HIP_WTERM_LIGHT_CELLS");
-            if (wt_k0 > 0 && cells_top < (elc ? std::atof(elc) : 4.0e6)) wt_k0 = 0;
-        }
-        if (wt_k0 == 0) wt_k1 = wt_K;
-        st[18] = wt_k0;
-        st[19] = wt_k0 > 0 && wt_k1 < wt_K ? wt_k1 : 0;
-        const int nlc = wt_k0 == 0 ? 0 : wt_k1 < wt_K ? 2 : 1;  // light classes of this run
-        for (int li = 0; li < nlanes_used; ++li) {
+    }
+
+    // The type-3 plans of every lane in use, one per plan class (Lane::plan), made anew when their dimensions,
+    // upsampling factor or tolerance change.
+    void lane_plans(const RunPlan &r) {
+        // height terms: term k enters with weight |c_k| <= 2 (a / 2)^k / k! (sum <= 2 e^{a/2} - 1), each with the
+        // transform's relative error -- the run's own plan takes eps / (2 e^{a/2} - 1) so that the sum keeps eps
+        const double eps_plan = r.K ? std::max(eps / (2.0 * std::exp(0.5 * r.a) - 1.0), sizeof(T) == 8 ? 1e-14 : 1e-7) : eps;
+        for (int li = 0; li < r.nlanes_used; ++li) {
             Lane &L = lanes[li];
-            // height terms: term k enters with weight |c_k| <= 2 (a / 2)^k / k! (sum <= 2 e^{a/2} - 1), each with the
-            // transform's relative error -- the run's own plan takes eps / (2 e^{a/2} - 1) so that the sum keeps eps
-            const double eps_plan = wt_K ? std::max(eps / (2.0 * std::exp(0.5 * wt_a) - 1.0), sizeof(T) == 8 ? 1e-14 : 1e-7) : eps;
-            if (!L.nufft || L.nufft->dim != D || L.nufft->sigma != sigma || L.nufft->eps != eps_plan)
-                L.nufft.reset(new Nufft3<T>(D, eps_plan, sigma, li < 2 || !pipe ? L.stream : stream));
-            L.nufft->err_oob = d_err.as<int>();
-            // the sources are 2 pi x (projections of unit vectors onto the array plane): inside a disc whatever the box
-            L.nufft->disc_radius = (D == 2 || L.nufft->zdirect) && !std::getenv("FFTVIS_HIP_NO_DISC") ? 2.0 * M_PI : 0.0;
-            L.nufft->transpose_flipped = !reference_compat;
-            if (li > 0) L.nufft->order_cache = lanes[0].nufft->order_cache;  // one table per grid size for all lanes
-            for (int c = 0; c < nlc; ++c) {  // the light height terms' plans
-                if (!L.nufft_l[c] || L.nufft_l[c]->eps != wt_eps_l[c])
-                    L.nufft_l[c].reset(new Nufft3<T>(2, wt_eps_l[c], 1.25, li < 2 || !pipe ? L.stream : stream));
-                L.nufft_l[c]->err_oob = d_err.as<int>();
-                L.nufft_l[c]->disc_radius = L.nufft->disc_radius;
-                L.nufft_l[c]->transpose_flipped = !reference_compat;
-                if (li > 0) L.nufft_l[c]->order_cache = lanes[0].nufft_l[c]->order_cache;
-                L.binned_ti_l[c] = -1;
+            for (int c = 0; c < r.ncls; ++c) {
+                const int D = c ? 2 : r.D;
+                const double e = c ? r.eps_l[c - 1] : eps_plan, sg = c ? 1.25 : r.sigma;
+                std::unique_ptr<Nufft3<T>> &P = L.plan[c];
+                if (!P || P->dim != D || P->sigma != sg || P->eps != e)
+                    P.reset(new Nufft3<T>(D, e, sg, li < 2 || !r.pipe ? L.stream : stream));
+                P->err_oob = d_err.as<int>();
+                // the sources are 2 pi x (projections of unit vectors onto the array plane): inside a disc whatever the box
+                P->disc_radius = (D == 2 || P->zdirect) && !std::getenv("FFTVIS_HIP_NO_DISC") ? 2.0 * M_PI : 0.0;
+                P->transpose_flipped = !reference_compat;
+                if (li > 0) P->order_cache = lanes[0].plan[c]->order_cache;  // one table per grid size for all lanes
+                L.binned_ti[c] = -1;
             }
-            L.d_xyz.reserve(sizeof(T) * 3 * cap);
-            L.d_az.reserve(sizeof(T) * cap);
-            L.d_za.reserve(sizeof(T) * cap);
-            L.d_srcidx.reserve(sizeof(int) * cap);
-            L.d_blockcnt.reserve(sizeof(int) * (nblk + 1));
-            L.d_blockoff.reserve(sizeof(int) * (nblk + 1));
-            L.binned_ti = -1;
         }
-        const bool dbg_t = std::getenv("FFTVIS_HIP_DEBUG_DRAIN") != nullptr;
-        if (dbg_t) std::fprintf(stderr, "run: set-up done %.3f s (lanes, unique targets, groups)\n", pin.since());
-        // Size every lane's grid and strength buffers for the largest (frequency group, beam pair) of this run now,
-        // before anything is queued (Nufft3::plan_buffer_cells): no reallocation -- a device synchronisation each --
-        // while the first time step runs.
-        {
-            int64_t need = 0, need_str = 0;
+    }
+
+    // Size every lane's grid and strength buffers for the largest (frequency group, beam pair) of this run now,
+    // before anything is queued (Nufft3::plan_buffer_cells): no reallocation -- a device synchronisation each --
+    // while the first time step runs.  Then the column plans of every (class, group, pair), from the geometry the run
+    // will set (large 2-D grids only).
+    void lane_buffers(const RunPlan &r) {
+        int64_t need_str = 0;
+        for (const auto &grp : r.groups)
+            for (const Pair &pr : pairs)
+                if (pr.n) need_str = std::max<int64_t>(need_str, (grp.second - grp.first) * (pr.herm ? 2 : tpol));
+        for (int c = 0; c < r.ncls; ++c) {  // the light height terms' plans have their own (smaller) grids
+            Nufft3<T> *n0 = lanes[0].plan[c].get();
+            int64_t need = 0;
             int na_max[3] = {8, 8, 8}, n2_max[3] = {64, 64, 64};
-            for (const auto &grp : groups) {
-                double smax = 0;
-                for (int f = grp.first; f < grp.second; ++f) smax = std::max(smax, std::fabs(freqs[f]));
+            for (const auto &grp : r.groups) {
+                const double smax = fmax_of(grp.first, grp.second);
                 for (const Pair &pr : pairs) {
                     if (pr.n == 0) continue;
                     const int ntrans = (grp.second - grp.first) * (pr.herm ? 2 : tpol);
                     for (double sl : {0.0, -1.0}) {  // with and without a column plan (its geometry takes no grid slack)
-                        lanes[0].nufft->grid_slack = sl;
-                        need = std::max(need, lanes[0].nufft->plan_buffer_cells(X, pr.box_B(), smax, na_max, n2_max) * ntrans);
-                    }
-                    need_str = std::max<int64_t>(need_str, ntrans);
-                }
-            }
-            for (int li = 0; li < nlanes_used; ++li) {
-                lanes[li].nufft->reserve_buffers(need, na_max, n2_max);
-                lanes[li].nufft->strengths_buffer_reserve(cap, (int)need_str);
-            }
-            for (int c = 0; c < nlc; ++c) {  // the light height terms' plans: their own (smaller) grids
-                int64_t need_l = 0;
-                int na_l[3] = {8, 8, 8}, n2_l[3] = {64, 64, 64};
-                for (const auto &grp : groups) {
-                    double smax = 0;
-                    for (int f = grp.first; f < grp.second; ++f) smax = std::max(smax, std::fabs(freqs[f]));
-                    for (const Pair &pr : pairs) {
-                        if (pr.n == 0) continue;
-                        const int ntrans = (grp.second - grp.first) * (pr.herm ? 2 : tpol);
-                        for (double sl : {0.0, -1.0}) {
-                            lanes[0].nufft_l[c]->grid_slack = sl;
-                            need_l = std::max(need_l, lanes[0].nufft_l[c]->plan_buffer_cells(X, pr.box_B(), smax, na_l, n2_l) * ntrans);
-                        }
+                        n0->grid_slack = sl;
+                        need = std::max(need, n0->plan_buffer_cells(r.X, pr.box_B(), smax, na_max, n2_max) * ntrans);
                     }
                 }
-                for (int li = 0; li < nlanes_used; ++li) {
-                    lanes[li].nufft_l[c]->reserve_buffers(need_l, na_l, n2_l);
-                    lanes[li].nufft_l[c]->strengths_buffer_reserve(cap, (int)need_str);
-                }
             }
-            // column plans of every (group, pair), from the geometry the run will set (large 2-D grids only)
-            col_plan_of.assign(groups.size() * pairs.size(), nullptr);
-            // plans of earlier target sets / groupings pile up in a long-lived handle: start over now and then (here,
-            // before this run takes pointers into the list, and after everything an earlier run queued has finished)
-            if (col_plans.size() > 512) {
-                FV_HIP(hipDeviceSynchronize());
-                col_plans.clear();
-            }
-            if ((D == 2 || lanes[0].nufft->zdirect) && !std::getenv("FFTVIS_HIP_NO_COLUMN_PLAN")) {
-                Nufft3<T> *n0 = lanes[0].nufft.get();
-                for (size_t gi = 0; gi < groups.size(); ++gi) {
-                    double smax = 0;
-                    for (int f = groups[gi].first; f < groups[gi].second; ++f) smax = std::max(smax, std::fabs(freqs[f]));
-                    for (size_t pi = 0; pi < pairs.size(); ++pi) {
-                        const Pair &pr = pairs[pi];
-                        if (pr.n == 0) continue;
-                        n0->grid_slack = 0.0;  // a plan's geometry: no grid slack (set_dim_geom)
-                        n0->set_geometry(xc, X, pr.box_c(), pr.box_B(), smax);
-                        if (!n0->columns_possible() || n0->geo.cells_o() < 4000000) continue;
-                        col_plan_of[gi * pairs.size() + pi] = column_plan((int)pi, pr, groups[gi].first, groups[gi].second, n0);
-                    }
-                }
-                FV_HIP(hipStreamSynchronize(n0->stream));  // the table kernels of these set_geometry calls are done before the run's own
-            }
-            for (int c = 0; c < 2; ++c) col_plan_of_l[c].assign(groups.size() * pairs.size(), nullptr);
-            for (int c = 0; c < nlc && !std::getenv("FFTVIS_HIP_NO_COLUMN_PLAN"); ++c) {
-                Nufft3<T> *n0 = lanes[0].nufft_l[c].get();
-                for (size_t gi = 0; gi < groups.size(); ++gi) {
-                    double smax = 0;
-                    for (int f = groups[gi].first; f < groups[gi].second; ++f) smax = std::max(smax, std::fabs(freqs[f]));
-                    for (size_t pi = 0; pi < pairs.size(); ++pi) {
-                        const Pair &pr = pairs[pi];
-                        if (pr.n == 0) continue;
-                        n0->grid_slack = 0.0;
-                        n0->set_geometry(xc, X, pr.box_c(), pr.box_B(), smax);
-                        if (!n0->columns_possible() || n0->geo.cells_o() < 4000000) continue;
-                        col_plan_of_l[c][gi * pairs.size() + pi] = column_plan((int)pi, pr, groups[gi].first, groups[gi].second, n0);
-                    }
-                }
-                FV_HIP(hipStreamSynchronize(n0->stream));
+            for (int li = 0; li < r.nlanes_used; ++li) {
+                lanes[li].plan[c]->reserve_buffers(need, na_max, n2_max);
+                lanes[li].plan[c]->strengths_buffer_reserve(r.ch.cap, (int)need_str);
             }
         }
-        if (dbg_t) std::fprintf(stderr, "run: buffers and column plans %.3f s\n", pin.since());
-        if (nlanes > 1 && !pipe) {  // the other lanes start after the output memset queued on the main stream
+        for (auto &cpo : col_plan_of) cpo.assign(r.groups.size() * pairs.size(), nullptr);
+        // plans of earlier target sets / groupings pile up in a long-lived handle: start over now and then (here,
+        // before this run takes pointers into the list, and after everything an earlier run queued has finished)
+        if (col_plans.size() > 512) {
+            FV_HIP(hipDeviceSynchronize());
+            col_plans.clear();
+        }
+        if (std::getenv("FFTVIS_HIP_NO_COLUMN_PLAN")) return;
+        for (int c = 0; c < r.ncls; ++c) {
+            Nufft3<T> *n0 = lanes[0].plan[c].get();
+            if (n0->dim != 2 && !n0->zdirect) continue;
+            for (size_t gi = 0; gi < r.groups.size(); ++gi) {
+                const double smax = fmax_of(r.groups[gi].first, r.groups[gi].second);
+                for (size_t pi = 0; pi < pairs.size(); ++pi) {
+                    const Pair &pr = pairs[pi];
+                    if (pr.n == 0) continue;
+                    n0->grid_slack = 0.0;  // a plan's geometry: no grid slack (set_dim_geom)
+                    n0->set_geometry(r.xc, r.X, pr.box_c(), pr.box_B(), smax);
+                    if (!n0->columns_possible() || n0->geo.cells_o() < 4000000) continue;
+                    col_plan_of[c][gi * pairs.size() + pi] = column_plan((int)pi, pr, r.groups[gi].first, r.groups[gi].second, n0);
+                }
+            }
+            FV_HIP(hipStreamSynchronize(n0->stream));  // the table kernels of these set_geometry calls are done before the run's own
+        }
+    }
+
+    // The unit loop: per (one or two time steps, source chunk) the per-time preparation, then per (frequency group, beam
+    // pair, height term) strengths -> spread -> FFT -> gather.
+    void queue_units(const RunPlan &r, const OutBlock &o, Drain &dr) {
+        const int t0 = r.t0, t1 = r.t1, f0 = r.f0, nt = r.nt, D = r.D, nch = r.ch.n;
+        const int64_t csz = r.ch.csz, cap = r.ch.cap;
+        const bool pipe = r.pipe, gang = r.gang;
+        const auto &groups = r.groups;
+        const int64_t per_tf = o.per_tf;
+        const std::array<int64_t, 16> pol_off = pol_offsets();
+        if (r.nlanes > 1 && !pipe) {  // the other lanes start after the output memset queued on the main stream
             FV_HIP(hipEventRecord(ev_start, stream));
-            for (int li = 1; li < nlanes; ++li) FV_HIP(hipStreamWaitEvent(lanes[li].stream, ev_start, 0));
+            for (int li = 1; li < r.nlanes; ++li) FV_HIP(hipStreamWaitEvent(lanes[li].stream, ev_start, 0));
         }
 
         const int sample_step = std::min(TIMING_STRIDE / 2, nt - 1);  // level-1 timing: this step of every 16
@@ -3104,14 +3096,14 @@ class Sim : public SimBase {
             // host output: once the last chunk of these time steps is queued, an event marks them finished
             hipStream_t unit_stream = stream;  // where this unit's big kernels run (free-running lanes: the lane's own)
             auto close_time = [&]() {
-                if (!drain || chunk != nch - 1) return;
-                const hipEvent_t ev = drain_event(drain_items.size());
+                if (!o.drain || chunk != nch - 1) return;
+                const hipEvent_t ev = drain_event(dr.items.size());
                 // pipelined and single-lane runs: every big kernel is on `stream`; free-running lanes: all chunks of a time
                 // step ran, in order, on its lane's stream -- the copy stream waits for THAT (the lanes never wait for
                 // each other)
                 FV_HIP(hipEventRecord(ev, unit_stream));
-                drain_items.push_back({ev, tu - t0, nm});
-                if (pin.pinned()) drain_flush(out, dout, nt, nf, per_tf, drain_items, drained, out_fs);
+                dr.items.push_back({ev, tu - t0, nm});
+                if (dr.pin.pinned()) drain_flush(o, dr);
             };
             if (nsrc == 0 || sn <= 0) {  // nothing above the horizon: the block stays zero (:945-946)
                 close_time();
@@ -3123,11 +3115,11 @@ class Sim : public SimBase {
                 Ls[0] = &lanes[(unit % 2) * 2];
                 Ls[1] = &lanes[(unit % 2) * 2 + 1];
             } else if (pipe) {
-                Ls[0] = Ls[1] = &lanes[unit % nlanes];
+                Ls[0] = Ls[1] = &lanes[unit % r.nlanes];
             } else {
                 // free-running lanes: the source chunks of one time step ADD to one another's visibilities, so they stay
                 // on one stream, in order
-                Ls[0] = Ls[1] = &lanes[tu % nlanes];
+                Ls[0] = Ls[1] = &lanes[tu % r.nlanes];
                 unit_stream = Ls[0]->stream;
             }
             Lane &L0 = *Ls[0];
@@ -3146,27 +3138,22 @@ class Sim : public SimBase {
             for (int m = 0; m < nm; ++m) {
                 RoctxRange rr("prep");
                 Lane &L = *Ls[m];
-                Nufft3<T> *nufft = L.nufft.get();
+                Nufft3<T> *nufft = L.plan[0].get();
                 nufft->stream = ps;
-                Mps[m] = horizon_step(L, tu + m, cap, nblk, ps, s0, sn, (int64_t)(tu + m) * nch + chunk);
+                Mps[m] = horizon_step(L, tu + m, cap, r.ch.nblk, ps, s0, sn, (int64_t)(tu + m) * nch + chunk);
                 if (pipe) {  // the first (group, pair)'s bin sort belongs to the preparation as well
                     for (const Pair &pr : pairs) {
                         if (pr.n == 0 || groups.empty()) continue;
-                        double smax0 = 0;
-                        for (int f = groups[0].first; f < groups[0].second; ++f)
-                            smax0 = std::max(smax0, std::fabs(freqs[f]));
-                        {
-                            const ColPlan *cpq = col_plan_of[(size_t)(&pr - pairs.data())];  // group 0
-                            nufft->grid_slack = cpq && cpq->use ? 0.0 : -1.0;
-                        }
-                        nufft->set_geometry(xc, X, pr.box_c(), pr.box_B(), smax0);
+                        const ColPlan *cpq = col_plan_of[0][(size_t)(&pr - pairs.data())];  // group 0
+                        nufft->grid_slack = cpq && cpq->use ? 0.0 : -1.0;
+                        nufft->set_geometry(r.xc, r.X, pr.box_c(), pr.box_B(), fmax_of(groups[0].first, groups[0].second));
                         nufft->set_sources(M, L.d_xyz.template as<T>(), L.d_xyz.template as<T>() + cap,
                                            D > 2 ? L.d_xyz.template as<T>() + 2 * cap : nullptr, Mps[m]);
-                        L.binned_ti = (tu + m) * nch + chunk;
-                        L.binned_serial = nufft->geom_serial;
+                        L.binned_ti[0] = (tu + m) * nch + chunk;
+                        L.binned_serial[0] = nufft->geom_serial;
                         // ... and so do its strengths (beam x coherency, pre-phase): they depend on this
                         // step's sources only, not on the previous step's big kernels
-                        launch_strengths(L, pr, groups[0].first, groups[0].second - groups[0].first, M, Mps[m], ps);
+                        launch_strengths(L, r, pr, groups[0].first, groups[0].second - groups[0].first, M, Mps[m], ps);
                         first_pair = &pr;
                         strengths_ahead = true;
                         break;
@@ -3180,64 +3167,50 @@ class Sim : public SimBase {
                 FV_HIP(hipEventRecord(L0.prep_done, ps));
                 FV_HIP(hipStreamWaitEvent(ls, L0.prep_done, 0));
             }
-            for (int m = 0; m < nm; ++m) {
-                Ls[m]->nufft->stream = ls;
-                for (int c = 0; c < nlc; ++c) Ls[m]->nufft_l[c]->stream = ls;
-            }
+            for (int m = 0; m < nm; ++m)
+                for (int c = 0; c < r.ncls; ++c) Ls[m]->plan[c]->stream = ls;
 
             for (const auto &grp : groups) {
                 const int fa = grp.first, fb = grp.second, nfg = fb - fa;
-                double smax = 0;
-                for (int f = fa; f < fb; ++f) smax = std::max(smax, std::fabs(freqs[f]));
+                const double smax = fmax_of(fa, fb);
                 for (const Pair &pr : pairs) {
                     if (pr.n == 0) continue;
                     const int tg = pr.herm ? 2 : tpol;  // transforms per frequency on the grid
                     const int ntrans = nfg * tg;
-                    // height terms (wt_K): one round of strengths -> spread -> FFT -> gather per term, the gather adding
+                    // height terms (r.K): one round of strengths -> spread -> FFT -> gather per term, the gather adding
                     // term k with every baseline's own factor; otherwise a single round
-                    for (int kt = 0; kt < std::max(1, wt_K); ++kt) {
-                    // the plan of this term: the run's own, or the light terms' (wt_k0)
-                    const bool light = wt_k0 > 0 && kt >= wt_k0;
-                    const int lc = light && kt >= wt_k1 ? 1 : 0;  // its class
-                    auto plan_of = [&](Lane &L) { return light ? L.nufft_l[lc].get() : L.nufft.get(); };
-                    const std::vector<ColPlan *> &cplans = light ? col_plan_of_l[lc] : col_plan_of;
-                    Nufft3<T> *nufft = plan_of(L0);
-                    Nufft3<T> *mate = nm == 2 ? plan_of(*Ls[1]) : nullptr;
+                    for (int kt = 0; kt < std::max(1, r.K); ++kt) {
+                    const int c = r.cls(kt);  // the plan of this term: the run's own, or a light class's
+                    ColPlan *cp = col_plan_of[c][(size_t)(&grp - groups.data()) * pairs.size() + (size_t)(&pr - pairs.data())];
+                    const bool on = cp && cp->use;
+                    Nufft3<T> *nufft = L0.plan[c].get();
+                    Nufft3<T> *mate = nm == 2 ? Ls[1]->plan[c].get() : nullptr;
                     for (int m = 0; m < nm; ++m) {
                         Lane &L = *Ls[m];
-                        Nufft3<T> *nf_ = plan_of(L);
-                        int &b_ti = light ? L.binned_ti_l[lc] : L.binned_ti;
-                        int64_t &b_serial = light ? L.binned_serial_l[lc] : L.binned_serial;
+                        Nufft3<T> *nf_ = L.plan[c].get();
                         // ---- geometry + bin sort (skipped when unchanged since last set) -------
                         RoctxRange rr("prep");
                         size_t e1 = ev_begin(TM_PREP, ls);
-                        {
-                            const ColPlan *cpq = cplans[(size_t)(&grp - groups.data()) * pairs.size() + (size_t)(&pr - pairs.data())];
-                            nf_->grid_slack = cpq && cpq->use ? 0.0 : -1.0;
-                        }
-                        nf_->set_geometry(xc, X, pr.box_c(), pr.box_B(), smax);
-                        if (b_ti != (tu + m) * nch + chunk || b_serial != nf_->geom_serial || nf_->M != M) {
+                        nf_->grid_slack = on ? 0.0 : -1.0;
+                        nf_->set_geometry(r.xc, r.X, pr.box_c(), pr.box_B(), smax);
+                        if (L.binned_ti[c] != (tu + m) * nch + chunk || L.binned_serial[c] != nf_->geom_serial || nf_->M != M) {
                             nf_->set_sources(M, L.d_xyz.template as<T>(), L.d_xyz.template as<T>() + cap,
                                              D > 2 ? L.d_xyz.template as<T>() + 2 * cap : nullptr, Mps[m]);
-                            b_ti = (tu + m) * nch + chunk;
-                            b_serial = nf_->geom_serial;
+                            L.binned_ti[c] = (tu + m) * nch + chunk;
+                            L.binned_serial[c] = nf_->geom_serial;
                         }
                         ev_end(e1, ls);
                         // ---- strengths (already queued with the preparation for the first pair) -------
                         if (!(strengths_ahead && &grp == &groups.front() && &pr == first_pair && kt == 0))
-                            launch_strengths(L, pr, fa, nfg, M, Mps[m], ls, kt, nf_);
+                            launch_strengths(L, r, pr, fa, nfg, M, Mps[m], ls, kt, nf_);
                     }
                     // ---- NUFFT ----------------------------------------------------------
-                    {
-                        ColPlan *cp = cplans[(size_t)(&grp - groups.data()) * pairs.size() + (size_t)(&pr - pairs.data())];
-                        const bool on = cp && cp->use;
-                        for (int m = 0; m < nm; ++m) {
-                            plan_of(*Ls[m])->arm_columns(on ? cp->tab.template as<int>() : nullptr, on ? cp->xtab.template as<int>() : nullptr, tg,
-                                                      on ? cp->ncc : 0, d_err.as<int>() + 3,
-                                                      on && cp->omask.p ? cp->omask.template as<unsigned long long>() : nullptr,
-                                                      on ? cp->nblk : 0);
-                            plan_of(*Ls[m])->col_out_cells = on && cp->omask.p ? cp->out_cells : 0.0;
-                        }
+                    for (int m = 0; m < nm; ++m) {
+                        Nufft3<T> *P = Ls[m]->plan[c].get();
+                        P->arm_columns(on ? cp->tab.template as<int>() : nullptr, on ? cp->xtab.template as<int>() : nullptr, tg,
+                                       on ? cp->ncc : 0, d_err.as<int>() + 3,
+                                       on && cp->omask.p ? cp->omask.template as<unsigned long long>() : nullptr, on ? cp->nblk : 0);
+                        P->col_out_cells = on && cp->omask.p ? cp->out_cells : 0.0;
                     }
                     {
                     RoctxRange rr("spread");
@@ -3245,7 +3218,7 @@ class Sim : public SimBase {
                         const size_t e3 = ev_slot(TM_SPREAD);
                         nufft->spread(ntrans, ev_pool[e3].a, ev_pool[e3].b, mate);
                         spread_timed += nm;  // a gang launch serves nm time steps: counted per time step
-                    } else if (ride_heavy_done && pipe && &grp == &groups.back() && &pr == last_pair && kt + 1 >= std::max(1, wt_K)) {
+                    } else if (ride_heavy_done && pipe && &grp == &groups.back() && &pr == last_pair && kt + 1 >= std::max(1, r.K)) {
                         // the unit's last spread is the last reader of the lanes' per-time arrays (the FFT
                         // passes and the gather work on the grids): its dispatch carries the "lane scratch
                         // is free" event, which saves the main stream a marker packet per unit
@@ -3255,19 +3228,19 @@ class Sim : public SimBase {
                         nufft->spread(ntrans, nullptr, nullptr, mate);
                     }
                     }
-                    st[0] += nm;  // launches are counted per (time, frequency group, beam pair)
-                    st[1] += (double)nufft->spread_cells() * ntrans * nm;  // cells written (2-D: the blocks inside the source disc)
+                    st[ST_SPREAD_LAUNCHES] += nm;  // launches are counted per (time, frequency group, beam pair)
+                    st[ST_SPREAD_CELLS] += (double)nufft->spread_cells() * ntrans * nm;  // cells written (2-D: the blocks inside the source disc)
                     for (int m = 0; m < nm; ++m) mhist_log[hist_slot[m]].second += ntrans;
-                    cplx<T> *obase = dout + ((int64_t)(fa - f0) * nt + (tu - t0)) * per_tf;
+                    cplx<T> *obase = o.dout + ((int64_t)(fa - f0) * nt + (tu - t0)) * per_tf;
                     // small 2-D grids: the last FFT pass serves the targets from its LDS tiles (no C
                     // buffer, no gather kernel); the output block was zeroed at the start of the run
                     const bool fused =
-                        !nbasis && !pr.herm && !wt_K &&
+                        !nbasis && !pr.herm && !r.K &&
                         nufft->prepare_fused_gather(pr.n, d_bls.as<T>(), d_bls.as<T>() + nbls,
                                                     pr.trivial ? nullptr : pr.idx->template as<int>(),
                                                     pr.trivial ? nullptr : pr.flip->template as<signed char>(),
                                                     d_freqs.as<double>() + fa, nfg, tpol, obase,
-                                                    (int64_t)nt * per_tf, 1, pol_off, targets_serial,
+                                                    o.run, 1, pol_off.data(), targets_serial,
                                                     mate ? obase + per_tf : nullptr);
                     size_t e4 = ev_begin(TM_FFT, ls);
                     {
@@ -3275,8 +3248,8 @@ class Sim : public SimBase {
                         nufft->fft(ntrans, mate);
                     }
                     ev_end(e4, ls);
-                    st[3] += nufft->fft_traffic_cells() * ntrans * nm;
-                    st[12] += nufft->fft_flops() * ntrans * nm;
+                    st[ST_FFT_CELLS] += nufft->fft_traffic_cells() * ntrans * nm;
+                    st[ST_FFT_FLOPS] += nufft->fft_flops() * ntrans * nm;
                     RoctxRange rg("gather");
                     size_t e5 = ev_begin(TM_INTERP, ls);
                     BasisTerm bt{d_coefs.p, d_ant1.as<int>(), d_ant2.as<int>(), pr.bi, pr.bj, nbasis,
@@ -3284,30 +3257,30 @@ class Sim : public SimBase {
                     // exact eigenbeam symmetry (reference_compat off): the (l, k) term of an off-diagonal pair of
                     // complex basis beams comes from a second gather at -b (all-real pairs: packed, exact already)
                     const int nparts = nbasis && !reference_compat && pr.bi != pr.bj && !pr.herm ? 2 : 1;
-                    const WTerm wterm{kt, wt_zc, wt_zh, (const void *)(d_bls.as<T>() + 2 * nbls)};
+                    const WTerm wterm{kt, r.zc, r.zh, (const void *)(d_bls.as<T>() + 2 * nbls)};
                     if (!fused)
                         for (int m = 0; m < nm; ++m)
                             for (int part = 1; part <= nparts; ++part) {
                                 bt.part = nparts == 2 ? part : 0;
                                 bt.negate = nparts == 2 && part == 2;
-                                plan_of(*Ls[m])->interp(pr.n, d_bls.as<T>(), d_bls.as<T>() + nbls,
+                                Ls[m]->plan[c]->interp(pr.n, d_bls.as<T>(), d_bls.as<T>() + nbls,
                                       D > 2 ? d_bls.as<T>() + 2 * nbls : nullptr,
                                       pr.trivial ? nullptr : pr.idx->template as<int>(),
                                       pr.trivial ? nullptr : pr.flip->template as<signed char>(),
                                       d_freqs.as<double>() + fa, nfg, tg, obase + (int64_t)m * per_tf,
-                                      (int64_t)nt * per_tf, 1, pol_off, accumulate || kt > 0, nbasis ? &bt : nullptr, pr.herm,
+                                      o.run, 1, pol_off.data(), accumulate || kt > 0, nbasis ? &bt : nullptr, pr.herm,
                                       pr.ustart ? pr.ustart->template as<int>() : nullptr, pr.upairs ? pr.nitems : pr.nu,
-                                      pr.upairs ? pr.upairs->template as<int>() : nullptr, wt_K ? &wterm : nullptr);
+                                      pr.upairs ? pr.upairs->template as<int>() : nullptr, r.K ? &wterm : nullptr);
                             }
                     ev_end(e5, ls);
-                    st[4] += (double)(pr.upairs ? pr.nitems : pr.ustart ? pr.nu : pr.n) * ntrans * nm * (pr.herm ? 2 : 1);  // footprints gathered: distinct targets; packed transforms are read at s and -s
-                    if (!light) {  // (the run's own plan describes the run)
-                        st[6] = nufft->geo.d[0].n2;
-                        st[7] = nufft->geo.d[1].n2;
-                        st[8] = nufft->geo.d[0].na * 65536.0 + nufft->geo.d[1].na;
-                        st[13] = D > 2 ? nufft->geo.d[2].n2 : 1;
-                        st[14] = D > 2 ? nufft->geo.d[2].na : 1;
-                        st[9] = nufft->ker.w;
+                    st[ST_GATHERED] += (double)(pr.upairs ? pr.nitems : pr.ustart ? pr.nu : pr.n) * ntrans * nm * (pr.herm ? 2 : 1);  // footprints gathered: distinct targets; packed transforms are read at s and -s
+                    if (c == 0) {  // (the run's own plan describes the run)
+                        st[ST_N2X] = nufft->geo.d[0].n2;
+                        st[ST_N2Y] = nufft->geo.d[1].n2;
+                        st[ST_NA_XY] = nufft->geo.d[0].na * 65536.0 + nufft->geo.d[1].na;
+                        st[ST_N2_3] = D > 2 ? nufft->geo.d[2].n2 : 1;
+                        st[ST_NA_3] = D > 2 ? nufft->geo.d[2].na : 1;
+                        st[ST_W] = nufft->ker.w;
                     }
                     }  // height terms
                 }
@@ -3316,49 +3289,49 @@ class Sim : public SimBase {
                 if (!heavy_recorded) FV_HIP(hipEventRecord(L0.heavy_done, ls));
                 L0.heavy_pending = true;
             }
-            if (dbg_t && tu == t0 && chunk == 0) std::fprintf(stderr, "run: first unit queued %.3f s\n", pin.since());
-            if (drain && !pin_started) {
-                pin.start(device, out, (size_t)nf, run_bytes, sizeof(cplx<T>) * (size_t)out_fs, shared, true);
-                pin_started = true;
-            }
+            if (dr.dbg && tu == t0 && chunk == 0) std::fprintf(stderr, "run: first unit queued %.3f s\n", dr.pin.since());
+            if (o.drain && !dr.started) pin_output(o, dr);
             close_time();
         }
-        if (nlanes > 1 && !pipe) {  // join: everything queued on the main stream afterwards sees every lane
-            for (int li = 1; li < nlanes; ++li) {
+        if (r.nlanes > 1 && !pipe) {  // join: everything queued on the main stream afterwards sees every lane
+            for (int li = 1; li < r.nlanes; ++li) {
                 FV_HIP(hipEventRecord(lanes[li].done, lanes[li].stream));
                 FV_HIP(hipStreamWaitEvent(stream, lanes[li].done, 0));
             }
         }
-        if (!out_on_device) {
-            if (drain && pin.wait()) {
-                const bool dbg = std::getenv("FFTVIS_HIP_DEBUG_DRAIN") != nullptr;
-                const double t_queued = pin.since();
-                const size_t early = drained;
-                drain_flush(out, dout, nt, nf, per_tf, drain_items, drained, out_fs);
-                if (dbg) {
-                    FV_HIP(hipStreamSynchronize(stream));
-                    std::fprintf(stderr, "drain: run queued %.3f s, pinned %.3f s, kernels done %.3f s, ", t_queued,
-                                 pin.t_pinned, pin.since());
-                }
-                FV_HIP(hipStreamSynchronize(copy_stream));
+    }
+
+    // The end of a forward run with a host destination: the time steps not yet drained, or the whole block, leave for the
+    // caller's array; the call returns synchronised.
+    void finish_output(const OutBlock &o, Drain &dr) {
+        if (o.on_device) return;
+        if (o.drain && dr.pin.wait()) {
+            const double t_queued = dr.pin.since();
+            const size_t early = dr.done;
+            drain_flush(o, dr);
+            if (dr.dbg) {
                 FV_HIP(hipStreamSynchronize(stream));
-                if (dbg) {
-                    std::fprintf(stderr, "copies done %.3f s (%zu of %zu time-step items queued before the end)\n",
-                                 pin.since(), early, drain_items.size());
-                    std::fprintf(stderr, "drain: time steps finished at [ms after the first]:");
-                    for (size_t i = 1; i < drain_items.size(); ++i) {
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, drain_items[0].ev, drain_items[i].ev) == hipSuccess) std::fprintf(stderr, " %.0f", ms);
-                    }
-                    std::fprintf(stderr, "\n");
-                }
-            } else {
-                copy_block_to_host(out, dout, nf, (int64_t)nt * per_tf, out_fs, false, stream);
-                FV_HIP(hipStreamSynchronize(stream));
+                std::fprintf(stderr, "drain: run queued %.3f s, pinned %.3f s, kernels done %.3f s, ", t_queued,
+                             dr.pin.t_pinned, dr.pin.since());
             }
-            if (timing_level) ev_collect();
-            check_errors();
+            FV_HIP(hipStreamSynchronize(copy_stream));
+            FV_HIP(hipStreamSynchronize(stream));
+            if (dr.dbg) {
+                std::fprintf(stderr, "copies done %.3f s (%zu of %zu time-step items queued before the end)\n",
+                             dr.pin.since(), early, dr.items.size());
+                std::fprintf(stderr, "drain: time steps finished at [ms after the first]:");
+                for (size_t i = 1; i < dr.items.size(); ++i) {
+                    float ms = 0;
+                    if (hipEventElapsedTime(&ms, dr.items[0].ev, dr.items[i].ev) == hipSuccess) std::fprintf(stderr, " %.0f", ms);
+                }
+                std::fprintf(stderr, "\n");
+            }
+        } else {
+            copy_block_to_host(o, false, stream);
+            FV_HIP(hipStreamSynchronize(stream));
         }
+        if (timing_level) ev_collect();
+        check_errors();
     }
 
     // ---- adjoint: gflux += A^T G, A = this handle's forward map (run) from fluxes to visibilities -------------------
@@ -3370,12 +3343,7 @@ class Sim : public SimBase {
                      int accumulate) override {
         FV_HIP(hipSetDevice(device));
         FV_REQUIRE(nbasis == 0, "the adjoint does not cover basis beams (set_basis / beam_coefs)");
-        FV_REQUIRE(nsrc >= 0 && !rots.empty() && !freqs.empty() && nbls > 0 && !pairs.empty(),
-                   "engine not fully configured");
-        FV_REQUIRE(0 <= t0 && t0 <= t1 && t1 <= (int)rots.size(), "time range");
-        FV_REQUIRE(0 <= f0 && f0 <= f1 && f1 <= (int)freqs.size(), "freq range");
-        FV_REQUIRE((int)freqs.size() == nfreq_cat, "flux frequency axis != freqs");
-        for (const Beam &b : beams) FV_REQUIRE(b.kind >= 0, "beam not set");
+        check_run(t0, t1, f0, f1);
         const int nt = t1 - t0, nf = f1 - f0;
         const int64_t per_tf = (int64_t)tpol * nbls;
         // whatever an earlier run queued (a device-output forward run leaves its lanes busy) is finished first: the lanes'
@@ -3387,20 +3355,13 @@ class Sim : public SimBase {
             if (lanes[li].stream && lanes[li].own_stream) FV_HIP(hipStreamSynchronize(lanes[li].stream));
         for (Lane &L : lanes) {
             L.heavy_pending = false;
-            L.binned_ti = -1;
-            L.binned_ti_l[0] = L.binned_ti_l[1] = -1;
+            for (int &b : L.binned_ti) b = -1;
         }
         lane_mode = -1;
         // the forward's redundant-baseline runs, compared in all three components (a run's vector is its first member's)
-        wt_K = 0;
-        {
-            double fall = 0;
-            for (double f : freqs) fall = std::max(fall, std::fabs(f));
-            const double tol = 1e-3 * eps / (2.0 * M_PI * std::max(fall, 1.0));
-            for (Pair &p : pairs) build_unique(p, tol);
-        }
+        const double tol = dedup_tol();
+        for (Pair &p : pairs) build_unique(p, tol, 3);
         const int D = dim();
-        run_D = D;
         // box of the directions x = 2 pi R topo (R: the plane rotation, or the lattice basis^T of a type-1 array)
         double xc[3], X[3];
         if (type1) {
@@ -3440,13 +3401,11 @@ class Sim : public SimBase {
         const double cells2 = cells_at_sigma2(X, D, f0, f1, [](const Pair &p) { return (const double *)p.B; });
         const double sigma_a = this->sigma != 0.0 ? this->sigma : auto_sigma(cells2, 0.5 * (double)nsrc + (double)nu_max, D);
         const double cells_top = 2.0 * cells2 * (sigma_a == 2.0 ? 1.0 : std::pow(1.25 / 2.0, D));
-        const int nch = (int)std::max<int64_t>(1, std::min<int64_t>(src_chunks, nsrc));
-        const int64_t csz = std::max<int64_t>(cdiv(nsrc, nch), 1);
-        const int64_t cap = std::max<int64_t>((int64_t)std::ceil(csz * source_buffer), 1);
-        const int nblk = (int)cdiv(csz, 256);
-        reserve_mhist(sizeof(int) * rots.size() * std::max(1, src_chunks));
         const char *el = std::getenv("FFTVIS_HIP_LANES");
         const int nlanes = std::max(1, std::min(2, std::min(el ? std::atoi(el) : 2, std::max(nt, 1))));
+        const Chunks sc = source_chunks(nlanes);
+        const int nch = sc.n;
+        const int64_t csz = sc.csz, cap = sc.cap;
         const int comps = pol_sky ? 8 : 1;
         // Channel blocks: a lane's accumulator holds nsrc x (channels of a block) x comps doubles, at most
         // FFTVIS_HIP_ADJ_ACC_BYTES (default 256 MiB); every block walks the time steps once and is reduced into gflux.
@@ -3475,12 +3434,6 @@ class Sim : public SimBase {
             L.adj->disc_radius = 0.0;  // its sources are baselines
             L.adj->transpose_flipped = false;
             L.adj->arm_columns(nullptr, nullptr, tpol, 0);
-            L.d_xyz.reserve(sizeof(T) * 3 * cap);
-            L.d_az.reserve(sizeof(T) * cap);
-            L.d_za.reserve(sizeof(T) * cap);
-            L.d_srcidx.reserve(sizeof(int) * cap);
-            L.d_blockcnt.reserve(sizeof(int) * (nblk + 1));
-            L.d_blockoff.reserve(sizeof(int) * (nblk + 1));
             L.d_adj_q.reserve(sizeof(cplx<T>) * (size_t)nu_max * nfg_max * tpol);
             L.d_adj_z.reserve(sizeof(cplx<T>) * (size_t)cap * nfg_max * tpol);
             L.d_adj_acc.reserve(acc_bytes);
@@ -3494,11 +3447,9 @@ class Sim : public SimBase {
             if (accumulate && gf_bytes) FV_HIP(hipMemcpyAsync(dgf, gflux, gf_bytes, hipMemcpyHostToDevice, stream));
         }
         if (!accumulate && gf_bytes) FV_HIP(hipMemsetAsync(dgf, 0, gf_bytes, stream));
-        int64_t pol_off[4] = {0, 0, 0, 0}, z_off[16] = {0};
-        for (int r = 0; r < tpol; ++r) {
-            pol_off[r] = (int64_t)((r % 2) * 2 + r / 2) * nbls;  // the forward's output slots
-            z_off[r] = (int64_t)r * cap;
-        }
+        const std::array<int64_t, 16> pol_off = pol_offsets();  // the forward's output slots
+        int64_t z_off[16] = {0};
+        for (int r = 0; r < tpol; ++r) z_off[r] = (int64_t)r * cap;
         const int ord = beam_order == 3 ? 3 : beam_order == 1 ? 1 : 0;
         for (size_t bi = 0; bi < fblocks.size(); ++bi) {
             const FBlock &fb = fblocks[bi];
@@ -3518,12 +3469,11 @@ class Sim : public SimBase {
                 for (int ch = 0; ch < nch; ++ch) {
                     const int64_t s0 = (int64_t)ch * csz, sn = std::min<int64_t>(csz, nsrc - s0);
                     if (nsrc == 0 || sn <= 0) continue;  // nothing above the horizon: nothing to add
-                    const int *Mp = horizon_step(L, t, cap, nblk, ls, s0, sn, (int64_t)t * nch + ch);
+                    const int *Mp = horizon_step(L, t, cap, sc.nblk, ls, s0, sn, (int64_t)t * nch + ch);
                     const T *xyz = L.d_xyz.template as<T>();
                     for (const auto &grp : fb.groups) {
                         const int fa = grp.first, nfg = grp.second - grp.first;
-                        double smax = 0;
-                        for (int f = fa; f < grp.second; ++f) smax = std::max(smax, std::fabs(freqs[f]));
+                        const double smax = fmax_of(fa, grp.second);
                         for (const Pair &pr : pairs) {
                             if (pr.n == 0) continue;
                             const int64_t nu = pr.ustart ? pr.nu : pr.n;
@@ -3614,10 +3564,10 @@ class Sim : public SimBase {
     }
 
     // beam x coherency strengths of one (frequency group, beam pair) for the lane's current sources
-    void launch_strengths(Lane &L, const Pair &pr, int fa, int nfg, int64_t M, const int *Mp, hipStream_t on, int wt_k = 0,
-                          Nufft3<T> *plan = nullptr) {
-        Nufft3<T> *nufft = plan ? plan : L.nufft.get();
-        const int D = run_D;
+    void launch_strengths(Lane &L, const RunPlan &r, const Pair &pr, int fa, int nfg, int64_t M, const int *Mp, hipStream_t on,
+                          int wt_k = 0, Nufft3<T> *plan = nullptr) {
+        Nufft3<T> *nufft = plan ? plan : L.plan[0].get();
+        const int D = r.D;
         RoctxRange rr("strengths");
         size_t e2 = ev_begin(TM_STRENGTHS, on);
         StrengthArgs sa{};
@@ -3638,9 +3588,9 @@ class Sim : public SimBase {
         }
         sa.bi = desc(pr.bi);
         sa.bj = desc(pr.bj);
-        sa.wt_k = wt_K ? wt_k : 0;
-        sa.wt_zc = wt_zc;
-        sa.wt_inv = wt_zh > 0 ? 1.0 / wt_zh : 0.0;
+        sa.wt_k = r.K ? wt_k : 0;
+        sa.wt_zc = r.zc;
+        sa.wt_inv = r.zh > 0 ? 1.0 / r.zh : 0.0;
         cplx<T> *cs = nufft->strengths_buffer(nfg * (pr.herm ? 2 : tpol));
         hipLaunchKernelGGL((beam_order == 3 ? k_strengths<T, 3> : beam_order == 1 ? k_strengths<T, 1> : k_strengths<T, 0>),
                            dim3(cdiv((int64_t)M * nfg, 256)), dim3(256), 0, on, sa, Mp,
@@ -3711,16 +3661,16 @@ class Sim : public SimBase {
             FV_HIP(hipStreamSynchronize(stream));
             for (const auto &e : mhist_log) {
                 if (e.first < 0 || e.first >= (int)mh.size()) continue;
-                st[5] += mh[e.first];
-                st[2] += (double)mh[e.first] * e.second;
-                st[11] = std::max(st[11], (double)mh[e.first]);
+                st[ST_ABOVE_HORIZON] += mh[e.first];
+                st[ST_SOURCE_VISITS] += (double)mh[e.first] * e.second;
+                st[ST_MAX_ABOVE_HORIZON] = std::max(st[ST_MAX_ABOVE_HORIZON], (double)mh[e.first]);
             }
             mhist_log.clear();
         }
     }
     void stats(double *v, int n) override {
         fold_mhist();
-        for (int i = 0; i < n && i < 24; ++i) v[i] = st[i];
+        for (int i = 0; i < n && i < (int)(sizeof st / sizeof *st); ++i) v[i] = st[i];
     }
     void reset_stats() override {
         for (double &x : st) x = 0;

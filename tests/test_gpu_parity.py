@@ -555,7 +555,8 @@ def test_sim_gang_launches_match_single_steps(gpu, monkeypatch):
     FFT pass (gang mode).  With an odd number of times (a single-step tail), several frequency groups
     (a small grid budget), three beam pairs with flips, a polarized sky, fp32, and the eigenbeam path
     (whose gather is not fused), the result must equal the one-step-per-launch result up to the order
-    of the gather's atomic additions -- and the oracle."""
+    of the gather's atomic additions -- and the oracle.  So must the one-lane and the free-running
+    (FFTVIS_HIP_PIPE=0) schedules."""
     cfg = synth.make_config("C2", nsrc=1500, nfreq=6, ntimes=5)
     freqs = cfg["freqs"]
     tab = fftvis_amd.TabulatedBeam(synth.synthetic_efield_table(freqs, nza=91, naz=180), freqs)
@@ -571,13 +572,20 @@ def test_sim_gang_launches_match_single_steps(gpu, monkeypatch):
              "basis": dict(cfg, polarized=True, beam=[tab, tab2], beam_coefs=coefs, baselines=bls, eps=1e-9),
              "fp32": dict(pol, precision=1, eps=1e-4)}
     monkeypatch.setenv("FFTVIS_HIP_GRID_BYTES", str(48 * 1024 * 1024))  # a few channels per launch
+    modes = {"single": {"FFTVIS_HIP_GANG": "0"}, "one lane": {"FFTVIS_HIP_LANES": "1"},
+             "free-running": {"FFTVIS_HIP_PIPE": "0"}}
     for name, c in cases.items():
         monkeypatch.setenv("FFTVIS_HIP_GANG", "1")
         ganged = fftvis_amd.simulate_vis(**c)
-        monkeypatch.setenv("FFTVIS_HIP_GANG", "0")
-        single = fftvis_amd.simulate_vis(**c)
+        monkeypatch.delenv("FFTVIS_HIP_GANG")
         tol = 1e-5 if name == "fp32" else 1e-13
-        assert rel_l2(ganged, single) < tol, name
+        for mode, env in modes.items():
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            other = fftvis_amd.simulate_vis(**c)
+            for k in env:
+                monkeypatch.delenv(k)
+            assert rel_l2(ganged, other) < tol, (name, mode)
         if name != "fp32":
             assert rel_l2(ganged, oracle_simulate(c)) < 1e-8, name
 
