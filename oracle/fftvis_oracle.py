@@ -804,3 +804,124 @@ def simulate(
     if polarized:
         return np.transpose(vis, (4, 0, 2, 3, 1))  # :851
     return np.moveaxis(vis[..., 0, 0, :], 2, 0)  # :853
+
+
+# ---------------------------------------------------------------------------
+# The exact transpose of ``simulate`` (test infrastructure for the adjoint)
+# ---------------------------------------------------------------------------
+def _unit_stokes_coherencies(nsel, nfreqs, polarized, full_stokes):
+    """The catalog ``prepare_source_catalog`` makes of each unit Stokes vector, as a list over the Stokes
+    components k: Stokes I alone ((nsel, nfreqs) of ones), or e_k for k = I, Q, U, V ((nsel, nfreqs, 4))."""
+    if not full_stokes:
+        return [prepare_source_catalog(np.ones((nsel, nfreqs)), polarized)]
+    out = []
+    for k in range(4):
+        unit = np.zeros((nsel, nfreqs, 4))
+        unit[..., k] = 1.0
+        out.append(prepare_source_catalog(unit, True))
+    return out
+
+
+def _topo_of(coord_mgr, ti):
+    """Topocentric unit vectors (3, nsrc) of every catalog source at time ti: the oracle's own rotation, or a
+    matvis-style manager's ``all_coords_topo`` after ``rotate(ti)``."""
+    coord_mgr.rotate(ti)
+    topo = getattr(coord_mgr, "all_coords_topo", None)
+    return np.array(coord_mgr._topo if topo is None else topo, dtype=float)
+
+
+def simulate_adjoint(
+    G, ants, freqs, beam_list, ra, dec, times, telescope_loc, baselines=None, beam_idx=None,
+    polarized=False, full_stokes=False, coord_mgr=None, force_use_type3=True, reference_compat=True,
+    nchunks=1, sources=None, flat_array_tol=1e-6,
+):
+    """Exact A^T G for the map A that ``simulate`` computes from real Stokes fluxes, taken for the real inner
+    products:  Re <A F, G> = <F, A^T G>.
+
+    ``G`` has ``simulate``'s output shape.  Returns (n, nfreqs) for a Stokes I sky, (n, nfreqs, 4) with
+    ``full_stokes=True`` (polarized only), fp64, n = nsrc or len(sources): ``sources`` restricts the result to those
+    catalog rows (the others are not computed).  Built from this module's pieces alone:
+      * each source's real-linear map from its Stokes vector to the strengths handed to the transform is
+        ``compute_apparent_coherency`` of the catalog ``prepare_source_catalog`` makes of a unit Stokes vector;
+      * ``run_nufft``'s rules: a flipped baseline takes -b and is conjugated, the output block is the transpose
+        of the reshaped strengths (swapaxes), and with ``reference_compat=False`` a flipped block is transposed
+        back.  Hence Re sum conj(G_b) out_b = Re sum_r H_br v_rb with H_b = conj(G_b) (G_b when flipped) in the
+        strengths' row order r, and v_rb = sum_j c_rj exp(+i b . x_j);
+      * the direct sums: Z_rj = sum_b H_br exp(+i b . x_j) in fp64, then A^T G[j, f, k] = Re sum_r c_k,rj Z_rj.
+    Lattice arrays (``force_use_type3=False``) take the type-3 sum too: the type-1 forward evaluates the same
+    phases (integer baselines times the lattice basis), so both are one map to rounding.
+    """
+    freqs = np.asarray(freqs, dtype=float)
+    G = np.asarray(G)
+    if full_stokes and not polarized:
+        raise ValueError("full_stokes=True needs polarized=True")
+    nfeeds = 2 if polarized else 1
+    ntp = nfeeds * nfeeds
+    if baselines is None:
+        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
+    nbls, nfreqs = len(baselines), len(freqs)
+    ntimes = len(np.atleast_1d(times))
+    want = (nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls)
+    if G.shape != want:
+        raise ValueError(f"G must have simulate's output shape {want}, got {G.shape}")
+    nsrc = int(np.size(ra))
+    antnums = list(ants.keys())
+    key2idx = {a: i for i, a in enumerate(antnums)}
+    antvecs = np.array([ants[a] for a in ants], dtype=float)
+    # the type-3 geometry of simulate (:642-658), whatever branch the forward takes
+    R = np.ascontiguousarray(get_plane_to_xy_rotation_matrix(antvecs).T)
+    rot = R @ antvecs.T
+    bls = np.array([rot[:, key2idx[b[1]]] - rot[:, key2idx[b[0]]] for b in baselines]).T.reshape(3, nbls)
+    is_coplanar = bool(np.all(np.abs(bls[2]) <= flat_array_tol))
+    if not force_use_type3 and np.abs(antvecs[:, -1]).max() <= flat_array_tol:
+        is_coplanar = is_coplanar or check_antpos_griddability(ants)[0]  # the type-1 branch is 2-D
+    bls = bls / speed_of_light
+    D = 2 if is_coplanar else 3
+    if beam_idx is None:
+        pairs, pair_idx, pair_flip = [(0, 0)], {(0, 0): np.arange(nbls)}, {(0, 0): [False] * nbls}
+    else:
+        pairs, pair_idx, pair_flip = prepare_beam_evaluation(antnums, baselines, beam_idx)
+    # H of every baseline in the strengths' row order r = f1 nfeeds + f2 (out[b, x, y] = v[y nfeeds + x, b])
+    if polarized:
+        gt = np.transpose(G, (0, 1, 4, 3, 2)).reshape(nfreqs, ntimes, nbls, ntp)  # [.., b, y nf + x]
+        gn = np.transpose(G, (0, 1, 4, 2, 3)).reshape(nfreqs, ntimes, nbls, ntp)  # [.., b, x nf + y]
+    else:
+        gt = gn = G.reshape(nfreqs, ntimes, nbls, 1)
+    rows = np.arange(nsrc) if sources is None else np.asarray(sources, dtype=int)
+    where = np.full(nsrc, -1)
+    where[rows] = np.arange(len(rows))
+    nk = 4 if full_stokes else 1
+    out = np.zeros((len(rows), nfreqs, nk))
+    if coord_mgr is None:
+        coord_mgr = SimpleCoordinateRotation(np.arange(nsrc), times, telescope_loc, ra, dec)
+    coord_mgr.setup()
+    csz = int(np.ceil(nsrc / nchunks))
+    for ti in range(ntimes):
+        topo_all = _topo_of(coord_mgr, ti)
+        for chunk in range(nchunks):
+            js = np.arange(chunk * csz, min(nsrc, (chunk + 1) * csz))
+            js = js[(topo_all[2, js] > 0) & (where[js] >= 0)]
+            if js.size == 0:
+                continue
+            topo = topo_all[:, js]
+            az, za = enu_to_az_za(topo[0], topo[1], orientation="uvbeam")
+            x = 2 * np.pi * (R @ topo)
+            units = _unit_stokes_coherencies(js.size, nfreqs, polarized, full_stokes)
+            for fi, freq in enumerate(freqs):
+                bev = [evaluate_beam(b, az, za, polarized, freq).astype(complex) for b in beam_list]
+                for bi, bj in pairs:
+                    idxs = np.asarray(pair_idx[(bi, bj)], dtype=int)
+                    if idxs.size == 0:
+                        continue
+                    fl = np.asarray(pair_flip[(bi, bj)], dtype=bool)
+                    uvw = np.where(fl, -1.0, 1.0) * bls[:, idxs] * freq
+                    phase = uvw[:D].T @ x[:D]  # (nb, nsel)
+                    E = np.cos(phase) + 1j * np.sin(phase)
+                    use_n = fl & (not reference_compat) & (nfeeds > 1)
+                    Gb = np.where(use_n[:, None], gn[fi, ti, idxs], gt[fi, ti, idxs])
+                    H = np.where(fl[:, None], Gb, np.conj(Gb))
+                    Z = H.T @ E  # (ntp, nsel)
+                    for k, (unit, pol_sky) in enumerate(units):
+                        c = compute_apparent_coherency(bev, bi, bj, unit, fi, polarized, pol_sky, nfeeds)
+                        out[where[js], fi, k] += np.sum(c * Z, axis=0).real
+    return out if full_stokes else out[..., 0]

@@ -143,3 +143,17 @@ def install_reference_dependency_stubs(monkeypatch):
     for name, m in mods.items():
         monkeypatch.setitem(sys.modules, name, m)
     return made, Time
+
+
+def oracle_adjoint(cfg, G, full_stokes=False, sources=None, coord_mgr=None):
+    """The oracle's exact A^T G (``orc.simulate_adjoint``) for simulate_vis-style keyword arguments, with the same beam
+    twins as ``oracle_simulate``: (n, nfreqs) or (n, nfreqs, 4), n = nsrc or len(sources)."""
+    beams = cfg["beam"] if isinstance(cfg["beam"], list) else [cfg["beam"]]
+    order = spline_order(cfg.get("beam_spline_opts"))
+    ob = [oracle_beam(b, cfg["polarized"], cfg["freqs"], order, cfg.get("use_feed", "x")) for b in beams]
+    return orc.simulate_adjoint(
+        G, cfg["ants"], cfg["freqs"], ob, cfg["ra"], cfg["dec"], cfg["times"], cfg["telescope_loc"],
+        baselines=cfg.get("baselines"), beam_idx=cfg.get("beam_idx"), polarized=cfg["polarized"],
+        full_stokes=full_stokes, coord_mgr=coord_mgr, force_use_type3=cfg.get("force_use_type3", True),
+        reference_compat=cfg.get("reference_compat", True), nchunks=cfg.get("min_chunks", 1), sources=sources,
+    )
