@@ -39,6 +39,16 @@ speed_of_light = 299792458.0  # core/utils.py:9
 default_accuracy_dict = {1: 6e-8, 2: 1e-13}  # core/simulate.py:16-19
 
 
+def fp32_rounded(a):
+    """``a`` rounded to float32, as fp64 values: what ``precision=1`` makes of an input (cpu_simulate.py:601-606, 631)."""
+    return np.asarray(a).astype(np.float32).astype(np.float64)
+
+
+def fp32_coherency(coherency):
+    """The coherency as ``precision=1`` hands it on (cpu_simulate.py:625-626): rounded to complex64, as complex128."""
+    return np.asarray(coherency).astype(np.complex64).astype(complex)
+
+
 # ---------------------------------------------------------------------------
 # Catalog / rotation helpers                                   cpu/utils.py
 # ---------------------------------------------------------------------------
@@ -232,15 +242,21 @@ def cpu_nufft2d_type1(x, y, weights, n_modes, index, eps=None, **_):
 
 def run_nufft(
     apparent_coherency, topo, uvw, bls, flipped, bls_idxs, use_type1, is_coplanar,
-    tx, ty, type1_n_modes, nfeeds, reference_compat=True,
+    tx, ty, type1_n_modes, nfeeds, reference_compat=True, scale=False,
 ):
     """Dispatch + flip/conj + reshape/swapaxes (cpu_simulate.py:205-300).
 
     ``reference_compat=False``: a flipped baseline of a two-beam pair is V_ji(b) =
-    V_ij(-b)^H -- conjugated AND its feed block transposed; the reference conjugates only (:298)."""
+    V_ij(-b)^H -- conjugated AND its feed block transposed; the reference conjugates only (:298).
+
+    ``scale=True`` replaces the sum at every target by the squared l2 norm over sources of the strength row
+    that feeds it (``simulate``'s ``mode="scale"``); flips, conjugation and transpositions apply as to the sum."""
     nbls_here = len(bls_idxs)
     flipped = np.asarray(flipped, dtype=bool)
-    if use_type1:
+    if scale:
+        sq = np.sum(np.abs(np.atleast_2d(apparent_coherency)) ** 2, axis=-1)
+        v = np.repeat(sq[:, None], nbls_here, axis=1).astype(complex)
+    elif use_type1:
         bls_here = np.where(flipped, -bls[:, bls_idxs], bls[:, bls_idxs])  # :259
         v = cpu_nufft2d_type1(tx, ty, apparent_coherency, type1_n_modes, bls_here)
     else:
@@ -261,12 +277,15 @@ def run_nufft(
 def compute_basis_visibilities(
     beam_evaluations, flux_here, ant1_idxs, ant2_idxs, beam_coefs, freqidx, topo, uvw,
     bls, tx, ty, nbls, nfeeds, use_type1, is_coplanar, type1_n_modes,
-    polarized=False, polarized_sky_model=False, reference_compat=True,
+    polarized=False, polarized_sky_model=False, reference_compat=True, scale=False,
 ):
     """Eigenbeam path (cpu_simulate.py:303-470).
 
     ``reference_compat=False``: the (l, k) term is V_lk(b) = conj(V_kl(-b))^T, exact for
-    complex basis beams; the reference reuses V_kl(b)^T (:464-468), exact only for real-valued ones."""
+    complex basis beams; the reference reuses V_kl(b)^T (:464-468), exact only for real-valued ones.
+
+    ``scale=True``: the terms' row norms add with weights |a1 a2| (each term is a transform of its own); returns the
+    square of that sum, which ``evaluate_vis_chunk`` accumulates over source chunks."""
     K = len(beam_evaluations)
     vis_out = np.zeros((nbls, nfeeds, nfeeds), dtype=complex)
     flipped = np.zeros(nbls, dtype=bool)  # :403
@@ -281,8 +300,14 @@ def compute_basis_visibilities(
             )
             vkl = run_nufft(
                 phi, topo, uvw, bls, flipped, bls_idxs, use_type1, is_coplanar,
-                tx, ty, type1_n_modes, nfeeds,
+                tx, ty, type1_n_modes, nfeeds, scale=scale,
             )
+            if scale:  # the (l, k) term has the same row norms, in the transposed slots, in both forms
+                r = np.sqrt(vkl.real)
+                vis_out += np.abs(a1[:, k] * a2[:, l])[:, None, None] * r
+                if l != k:
+                    vis_out += np.abs(a1[:, l] * a2[:, k])[:, None, None] * r.swapaxes(1, 2)
+                continue
             vis_out += (a1[:, k] * a2[:, l])[:, None, None] * vkl  # :461-462
             if l != k and reference_compat:
                 vis_out += (a1[:, l] * a2[:, k])[:, None, None] * vkl.swapaxes(1, 2)  # :464-468
@@ -292,7 +317,7 @@ def compute_basis_visibilities(
                     tx, ty, type1_n_modes, nfeeds,
                 )  # conj(V_kl(-b)), every baseline "flipped"
                 vis_out += (a1[:, l] * a2[:, k])[:, None, None] * vm.swapaxes(1, 2)
-    return vis_out
+    return vis_out.real ** 2 + 0j if scale else vis_out
 
 
 # ---------------------------------------------------------------------------
@@ -688,12 +713,14 @@ def evaluate_vis_chunk(
     time_idx, freq_idx, beam_list, coord_mgr, rotation_matrix, antnums, baselines, bls,
     freqs, nfeeds, beam_idx=None, polarized=False, polarized_sky_model=False,
     is_coplanar=False, nchunks=1, beam_coefs=None, use_type1=False, basis_matrix=None,
-    type1_n_modes=None, reference_compat=True,
+    type1_n_modes=None, reference_compat=True, mode="exact",
 ):
     """_evaluate_vis_chunk (cpu_simulate.py:856-1071), type-3 and type-1 branches.
 
-    Returns the reference's scratch layout (nt_here, nbls, nfeeds, nfeeds, nf_here).
+    Returns the reference's scratch layout (nt_here, nbls, nfeeds, nfeeds, nf_here); ``mode="scale"``: the squared
+    error scales of ``simulate``'s scale mode, summed over source chunks, in that layout.
     """
+    scale = mode == "scale"
     nbls = bls.shape[1]
     ntimes, nfreqs = len(coord_mgr.times), len(freqs)
     t_range = range(ntimes)[time_idx]
@@ -734,7 +761,7 @@ def evaluate_vis_chunk(
                     vis[tloc, :, :, :, floc] += compute_basis_visibilities(
                         bev, flux, a1, a2, beam_coefs, fi, topo, uvw, bls, tx, ty,
                         nbls, nfeeds, use_type1, is_coplanar, type1_n_modes, polarized,
-                        polarized_sky_model, reference_compat,
+                        polarized_sky_model, reference_compat, scale,
                     )  # :998-1024
                 else:
                     for bi, bj in pairs:  # :1030
@@ -746,7 +773,7 @@ def evaluate_vis_chunk(
                         )
                         v = run_nufft(
                             c, topo, uvw, bls, pair_flip[(bi, bj)], idxs, use_type1,
-                            is_coplanar, tx, ty, type1_n_modes, nfeeds, reference_compat,
+                            is_coplanar, tx, ty, type1_n_modes, nfeeds, reference_compat, scale,
                         )
                         vis[tloc, idxs, :, :, floc] += v  # :1069
     return vis
@@ -755,19 +782,34 @@ def evaluate_vis_chunk(
 def simulate(
     ants, freqs, fluxes, beam_list, ra, dec, times, telescope_loc, baselines=None,
     beam_idx=None, polarized=False, flat_array_tol=1e-6, nchunks=1, beam_coefs=None,
-    coord_mgr=None, force_use_type3=True, reference_compat=True,
+    coord_mgr=None, force_use_type3=True, reference_compat=True, mode="exact", precision=2,
 ):
-    """CPUSimulationEngine.simulate (cpu_simulate.py:537-854), nprocesses=1, precision=2;
+    """CPUSimulationEngine.simulate (cpu_simulate.py:537-854), nprocesses=1;
     ``force_use_type3=False`` takes the reference's type-1 branch for griddable flat arrays
-    (:634-637, :661-681).  Returns (nf, nt, nbls) or (nf, nt, 2, 2, nbls)."""
+    (:634-637, :661-681).  Returns (nf, nt, nbls) or (nf, nt, 2, 2, nbls).
+
+    ``precision=1`` rounds the inputs as the reference does before it computes anything -- ra, dec, freqs
+    (:601-606), the coherency (:625-626) and the antenna positions (:631) to float32 -- and then sums exactly in
+    fp64 like ``precision=2``.
+
+    ``mode="scale"`` returns, in the same layout, an error scale instead of the visibilities: for each output
+    element the l2 norm over sources of the strength row that feeds it (the row of ``compute_apparent_coherency``
+    that ``run_nufft``'s flips and transpositions route there).  Eigenbeam terms add with weights |a1 a2|, source
+    chunks add in squares.  With one source it is |the visibility| (at least that for eigenbeams)."""
     freqs = np.asarray(freqs, dtype=float)
     nfeeds = 2 if polarized else 1
     if baselines is None:
         baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]  # :614-616
+    if precision == 1:
+        freqs, ra, dec = (fp32_rounded(a) for a in (freqs, ra, dec))
     coherency, pol_sky = prepare_source_catalog(np.asarray(fluxes), polarized)  # :622
+    if precision == 1:
+        coherency = fp32_coherency(coherency)
     antnums = list(ants.keys())
     key2idx = {a: i for i, a in enumerate(antnums)}
     antvecs = np.array([ants[a] for a in ants], dtype=float)
+    if precision == 1:  # the griddability test (below) reads the unrounded ``ants``, as the reference's does
+        antvecs = fp32_rounded(antvecs)
     if np.abs(antvecs[:, -1]).max() > flat_array_tol or force_use_type3:  # :634-637
         is_gridded = False
     else:
@@ -799,8 +841,10 @@ def simulate(
         nfeeds, beam_idx=beam_idx, polarized=polarized, polarized_sky_model=pol_sky,
         is_coplanar=is_coplanar, nchunks=nchunks, beam_coefs=beam_coefs,
         use_type1=is_gridded, basis_matrix=basis_matrix, type1_n_modes=n_modes,
-        reference_compat=reference_compat,
+        reference_compat=reference_compat, mode=mode,
     )
+    if mode == "scale":
+        vis = np.sqrt(vis.real)
     if polarized:
         return np.transpose(vis, (4, 0, 2, 3, 1))  # :851
     return np.moveaxis(vis[..., 0, 0, :], 2, 0)  # :853

@@ -13,7 +13,7 @@ import pytest
 import fftvis_amd
 from fftvis_amd import _lib, synth
 from oracle import fftvis_oracle as orc
-from tests.helpers import oracle_adjoint, oracle_beam, oracle_simulate, rel_l2
+from tests.helpers import floored_rel, oracle_adjoint, oracle_beam, oracle_simulate, rel_l2, worst_part
 
 pytestmark = pytest.mark.gpu
 
@@ -87,14 +87,10 @@ def _adjoint_errors(got, exact):
     got = np.asarray(got, dtype=np.float64)
     err = got - exact
     floor = 1e-3 * np.linalg.norm(exact)
-
-    def rel(e, x):
-        return float(np.linalg.norm(e) / max(np.linalg.norm(x), floor, 1e-300))
-
-    m = {"rel_l2": rel(err, exact), "channel": max(rel(err[:, f], exact[:, f]) for f in range(exact.shape[1])),
+    m = {"rel_l2": floored_rel(err, exact, floor), "channel": worst_part(err, exact, 1, floor),
          "max_abs": float(np.abs(err).max() / max(np.abs(exact).max(), 1e-300))}
     if exact.ndim == 3:
-        m["stokes"] = max(rel(err[..., k], exact[..., k]) for k in range(4))
+        m["stokes"] = worst_part(err, exact, 2, floor)
     return m
 
 

@@ -15,7 +15,7 @@ from fftvis_amd.gpu.nufft import gpu_nudft_direct
 from fftvis_amd.gpu.utils import inplace_rot
 from oracle import fftvis_oracle as orc
 from oracle import nudft
-from tests.helpers import oracle_beam, oracle_simulate, rel_l2
+from tests.helpers import check_forward, oracle_beam, oracle_scale, oracle_simulate, rel_l2
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -357,9 +357,13 @@ def test_sim_c1_against_committed_fixture(gpu):
     vp = fftvis_amd.simulate_vis(**kw, polarized=True)
     assert vp.shape == (8, 2, 2, 2, 21)
     assert rel_l2(vp, z["vis_polarized"]) < TOL
+    check_forward(v, dict(kw, polarized=False), z["vis_unpolarized"], label="unpolarized")
+    check_forward(vp, dict(kw, polarized=True), z["vis_polarized"], label="polarized")
     # tighter eps tightens the agreement; fp64 default eps of the reference
     v13 = fftvis_amd.simulate_vis(**dict(kw, eps=None), polarized=False)
     assert rel_l2(v13, z["vis_unpolarized"]) < 1e-11
+    check_forward(v13, dict(kw, eps=None, polarized=False), z["vis_unpolarized"], label="default eps",
+                  family="lattice, eps 1e-13")
 
 
 def _variants():
@@ -391,13 +395,57 @@ def _variants():
     }
 
 
-@pytest.mark.parametrize("name", list(_variants()))
-def test_sim_variants_match_oracle(gpu, name):
-    cfg = _variants()[name]
+def _longest(ants, baselines, n):
+    """Indices of the n longest of ``baselines``."""
+    length = [np.linalg.norm(np.asarray(ants[j], float) - np.asarray(ants[i], float)) for i, j in baselines]
+    return list(np.argsort(length)[-n:])
+
+
+def _group_variant(name):
+    """A run cut into frequency groups (FFTVIS_HIP_GROUP_RATIO 0.99: a group per channel; 0.85: groups of a few
+    channels, each with a last channel of its own; a small FFTVIS_HIP_GRID_BYTES) over 100 - 170 MHz, a frequency ratio
+    of 1.7: the Hermitian-packed 2-D path (HERA-350, polarized table beam, its 8 longest baselines among ~50, so the top
+    channel gathers at the edge of the target box), height terms (HERA-37 with 5 cm of height scatter, every baseline)
+    and the type-1 lattice path (HERA-7).  Returns the configuration and its environment."""
+    freqs = np.linspace(100e6, 170e6, 6)
+    ratio = "0.99" if "0p99" in name else "0.85"
+    if name.startswith("groups_packed"):
+        cfg = synth.make_config("C3", nsrc=3000, nfreq=6, ntimes=1)
+        bl = cfg["baselines"]
+        keep = sorted(set(range(0, len(bl), 1500)) | set(_longest(cfg["ants"], bl, 8)))
+        cfg["baselines"] = [bl[i] for i in keep]
+        cfg["beam"] = fftvis_amd.TabulatedBeam(synth.synthetic_efield_table(freqs, nza=91, naz=180), freqs)
+        grid_bytes = 2**31 if ratio == "0.99" else 2**32
+    elif name.startswith("groups_height_terms"):
+        cfg = synth.make_config("C2", nsrc=700, nfreq=6, ntimes=2)
+        cfg["ants"] = synth.with_z_scatter(cfg["ants"], 0.05, seed=3)
+        grid_bytes = 48 * 1024 * 1024
+    else:
+        cfg = synth.make_config("C1", nfreq=6)
+        cfg["force_use_type3"] = False
+        grid_bytes = 4 * 1024 * 1024
+    cfg["freqs"] = freqs
+    cfg["ra"], cfg["dec"], cfg["fluxes"] = synth.catalog(len(cfg["ra"]), freqs, 0)
+    return cfg, {"FFTVIS_HIP_GROUP_RATIO": ratio, "FFTVIS_HIP_GRID_BYTES": str(grid_bytes)}
+
+
+GROUP_VARIANTS = ["groups_packed_0p99", "groups_packed_0p85", "groups_height_terms_0p99", "groups_height_terms_0p85",
+                  "groups_lattice_0p99", "groups_lattice_0p85"]
+
+
+@pytest.mark.parametrize("name", list(_variants()) + GROUP_VARIANTS)
+def test_sim_variants_match_oracle(gpu, monkeypatch, name):
+    if name in GROUP_VARIANTS:
+        cfg, env = _group_variant(name)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+    else:
+        cfg = _variants()[name]
     got = fftvis_amd.simulate_vis(**cfg)
     exp = oracle_simulate(cfg)
     assert got.shape == exp.shape
     assert rel_l2(got, exp) < (4 * TOL if name == "upsample_1p25" else TOL)
+    check_forward(got, cfg, exp, label=name)
 
 
 def test_sim_basis_beams(gpu):
@@ -415,10 +463,15 @@ def test_sim_basis_beams(gpu):
     exp = oracle_simulate(cfg)
     assert got.shape == exp.shape == (8, 2, 2, 2, 23)
     assert rel_l2(got, exp) < TOL
-    # polarized sky through the basis path
+    check_forward(got, cfg, exp, label="basis")
+    # polarized sky through the basis path, both forms of the off-diagonal terms
     _, _, fl4 = synth.catalog(100, freqs, 0, polarized_sky=True)
     cfg4 = dict(cfg, fluxes=fl4)
-    assert rel_l2(fftvis_amd.simulate_vis(**cfg4), oracle_simulate(cfg4)) < TOL
+    g4, e4 = fftvis_amd.simulate_vis(**cfg4), oracle_simulate(cfg4)
+    assert rel_l2(g4, e4) < TOL
+    check_forward(g4, cfg4, e4, label="basis, polarized sky")
+    cfgx = dict(cfg4, reference_compat=False)
+    check_forward(fftvis_amd.simulate_vis(**cfgx), cfgx, oracle_simulate(cfgx), label="basis, exact symmetries")
     # one-hot coefficients == per-antenna beams
     bidx = np.array([0, 1, 2, 0, 1, 2, 0])
     onehot = np.zeros((7, 3, len(freqs)), dtype=complex)
@@ -447,26 +500,39 @@ def test_sim_beam_spline_order3(gpu):
     bls = c1["baselines"] + [(3, 0), (6, 1), (2, 2)]
     pol = dict(c1, polarized=True, beam=[tab, tab2], beam_idx=bidx, fluxes=fl4, baselines=bls, beam_spline_opts=opts)
     v3 = fftvis_amd.simulate_vis(**pol)
-    assert rel_l2(v3, oracle_simulate(pol)) < TOL
+    e3 = oracle_simulate(pol)
+    assert rel_l2(v3, e3) < TOL
+    check_forward(v3, pol, e3, label="pairs")
     v1 = fftvis_amd.simulate_vis(**dict(pol, beam_spline_opts={"order": 1}))
     assert 1e-6 < rel_l2(v3, v1) < 0.3  # coarse (4 degree) tables: the two interpolants differ visibly
     unp = dict(c1, beam=tab, beam_spline_opts={"kx": 3, "ky": 3})
-    assert rel_l2(fftvis_amd.simulate_vis(**unp), oracle_simulate(unp)) < TOL
-    lat = dict(pol, force_use_type3=False)
-    assert rel_l2(fftvis_amd.simulate_vis(**lat), oracle_simulate(lat)) < TOL
+    for name, c in (("unpolarized", unp), ("lattice", dict(pol, force_use_type3=False))):
+        g, e = fftvis_amd.simulate_vis(**c), oracle_simulate(c)
+        assert rel_l2(g, e) < TOL
+        check_forward(g, c, e, label=name)
     rng = np.random.default_rng(4)
     coefs = rng.normal(size=(7, 2, len(freqs))) + 1j * rng.normal(size=(7, 2, len(freqs)))
     bas = dict(c1, polarized=True, beam=[tab, tab2], beam_coefs=coefs, beam_spline_opts=opts)
-    assert rel_l2(fftvis_amd.simulate_vis(**bas), oracle_simulate(bas)) < TOL
+    g, e = fftvis_amd.simulate_vis(**bas), oracle_simulate(bas)
+    assert rel_l2(g, e) < TOL
+    check_forward(g, bas, e, label="eigenbeams")
     airy = dict(c1, beam_spline_opts=opts)
     np.testing.assert_array_equal(fftvis_amd.simulate_vis(**airy), fftvis_amd.simulate_vis(**c1))
 
 
 def test_sim_fp32(gpu):
+    """fp32 against the oracle on the unrounded inputs (the reference's own test's tolerance) and, element by element,
+    against the oracle on the inputs as precision = 1 rounds them: C1 and its variants at eps 1e-4 and 1e-5."""
     cfg = dict(synth.make_config("C1"), precision=1, eps=1e-4)
     got = fftvis_amd.simulate_vis(**cfg)
     assert got.dtype == np.complex64
     assert rel_l2(got, oracle_simulate(cfg)) < 2e-3  # tests/test_cpu_simulate.py:195 uses atol 1e-4
+    check_forward(got, cfg, oracle_simulate(cfg, fp32_inputs=True), label="C1")
+    variants = _variants()
+    for name in ("pol_table_pol_sky", "two_beams_pol", "two_airy_unpol", "non_coplanar_pol_table"):
+        for eps in (1e-4, 1e-5):
+            c = dict(variants[name], precision=1, eps=eps)
+            check_forward(fftvis_amd.simulate_vis(**c), c, oracle_simulate(c, fp32_inputs=True), label=(name, eps))
 
 
 def test_sim_blocks_and_chunk_layout(gpu):
@@ -489,6 +555,7 @@ def test_sim_blocks_and_chunk_layout(gpu):
                                atol=1e-13 * np.abs(full).max())
     exp = oracle_simulate(dict(cfg, beam=cfg["beam"]))
     assert rel_l2(full, exp) < TOL
+    check_forward(full, cfg, exp)
 
 
 def test_sim_c2_size_properties(gpu):
@@ -500,7 +567,9 @@ def test_sim_c2_size_properties(gpu):
     rng = np.random.default_rng(0)
     sub = sorted(rng.choice(666, 40, replace=False))
     sub_cfg = dict(cfg, baselines=[cfg["baselines"][i] for i in sub])
-    assert rel_l2(v[..., sub], oracle_simulate(sub_cfg)) < TOL
+    exact = oracle_simulate(sub_cfg)
+    assert rel_l2(v[..., sub], exact) < TOL
+    check_forward(v, cfg, exact, sub=sub)
     _, _, fl2 = synth.catalog(3000, cfg["freqs"], 5)
     v2 = fftvis_amd.simulate_vis(**dict(cfg, fluxes=fl2))
     v12 = fftvis_amd.simulate_vis(**dict(cfg, fluxes=2.0 * cfg["fluxes"] + 0.5 * fl2))
@@ -519,7 +588,9 @@ def test_sim_c2_full_size(gpu):
     rng = np.random.default_rng(7)
     sub = sorted(rng.choice(666, 12, replace=False))
     sub_cfg = dict(cfg, baselines=[cfg["baselines"][i] for i in sub])
-    assert rel_l2(v[..., sub], oracle_simulate(sub_cfg)) < TOL
+    exact = oracle_simulate(sub_cfg)
+    assert rel_l2(v[..., sub], exact) < TOL
+    check_forward(v, cfg, exact, sub=sub)
     rev = dict(cfg, baselines=[(b, a) for (a, b) in cfg["baselines"]])
     assert rel_l2(fftvis_amd.simulate_vis(**rev), np.conj(v)) < 1e-9
     perm = rng.permutation(len(cfg["ra"]))
@@ -545,9 +616,13 @@ def test_sim_c2_geometry_polarized_pairs_fused_gather(gpu):
     pol = dict(cfg, polarized=True, beam=[tab, tab2], beam_idx=bidx, fluxes=fl4, baselines=bls, eps=1e-9)
     got = fftvis_amd.simulate_vis(**pol)
     assert got.shape == (4, 2, 2, 2, len(bls))
-    assert rel_l2(got, oracle_simulate(pol)) < 1e-8
-    g32 = fftvis_amd.simulate_vis(**dict(pol, precision=1, eps=1e-4))   # float atomics in the gather
+    exact = oracle_simulate(pol)
+    assert rel_l2(got, exact) < 1e-8
+    check_forward(got, pol, exact)
+    p32 = dict(pol, precision=1, eps=1e-4)
+    g32 = fftvis_amd.simulate_vis(**p32)   # float atomics in the gather
     assert g32.dtype == np.complex64 and rel_l2(g32, got) < 5e-3
+    check_forward(g32, p32, oracle_simulate(p32, fp32_inputs=True), label="fp32")
 
 
 def test_sim_gang_launches_match_single_steps(gpu, monkeypatch):
@@ -556,7 +631,10 @@ def test_sim_gang_launches_match_single_steps(gpu, monkeypatch):
     (a small grid budget), three beam pairs with flips, a polarized sky, fp32, and the eigenbeam path
     (whose gather is not fused), the result must equal the one-step-per-launch result up to the order
     of the gather's atomic additions -- and the oracle.  So must the one-lane and the free-running
-    (FFTVIS_HIP_PIPE=0) schedules."""
+    (FFTVIS_HIP_PIPE=0) schedules on 2, 3 and 4 streams and the engine's own time blocks (forced to 2 steps); every one of
+    them is checked per time step against the oracle, with source chunks whose sources rise or set between steps too."""
+    from fftvis_amd.gpu import gpu_simulate
+
     cfg = synth.make_config("C2", nsrc=1500, nfreq=6, ntimes=5)
     freqs = cfg["freqs"]
     tab = fftvis_amd.TabulatedBeam(synth.synthetic_efield_table(freqs, nza=91, naz=180), freqs)
@@ -570,11 +648,20 @@ def test_sim_gang_launches_match_single_steps(gpu, monkeypatch):
     coefs = rng.normal(size=(len(cfg["ants"]), 2, len(freqs))) + 1j * rng.normal(size=(len(cfg["ants"]), 2, len(freqs)))
     cases = {"unpolarized": dict(cfg, eps=1e-9), "pairs": pol,
              "basis": dict(cfg, polarized=True, beam=[tab, tab2], beam_coefs=coefs, baselines=bls, eps=1e-9),
-             "fp32": dict(pol, precision=1, eps=1e-4)}
+             "fp32": dict(pol, precision=1, eps=1e-4),
+             "chunks": dict(cfg, eps=1e-9, min_chunks=3)}   # 5 steps over 72 minutes: sources rise and set
     monkeypatch.setenv("FFTVIS_HIP_GRID_BYTES", str(48 * 1024 * 1024))  # a few channels per launch
     modes = {"single": {"FFTVIS_HIP_GANG": "0"}, "one lane": {"FFTVIS_HIP_LANES": "1"},
-             "free-running": {"FFTVIS_HIP_PIPE": "0"}}
+             "free-running": {"FFTVIS_HIP_PIPE": "0"},
+             "three free lanes": {"FFTVIS_HIP_PIPE": "0", "FFTVIS_HIP_LANES": "3"},
+             "four free lanes": {"FFTVIS_HIP_PIPE": "0", "FFTVIS_HIP_LANES": "4"}, "time blocks of 2": {}}
+    time_block = gpu_simulate._time_block
     for name, c in cases.items():
+        if name != "fp32":
+            exact = oracle_simulate(c)
+        else:
+            exact = oracle_simulate(c, fp32_inputs=True)
+        scale = oracle_scale(c)
         monkeypatch.setenv("FFTVIS_HIP_GANG", "1")
         ganged = fftvis_amd.simulate_vis(**c)
         monkeypatch.delenv("FFTVIS_HIP_GANG")
@@ -582,12 +669,17 @@ def test_sim_gang_launches_match_single_steps(gpu, monkeypatch):
         for mode, env in modes.items():
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
+            if mode == "time blocks of 2":
+                monkeypatch.setattr(gpu_simulate, "_time_block", lambda *a, **k: 2)
             other = fftvis_amd.simulate_vis(**c)
+            monkeypatch.setattr(gpu_simulate, "_time_block", time_block)
             for k in env:
                 monkeypatch.delenv(k)
             assert rel_l2(ganged, other) < tol, (name, mode)
+            check_forward(other, c, exact, scale=scale, label=(name, mode))
         if name != "fp32":
-            assert rel_l2(ganged, oracle_simulate(c)) < 1e-8, name
+            assert rel_l2(ganged, exact) < 1e-8, name
+        check_forward(ganged, c, exact, scale=scale, label=name)
 
 
 @pytest.mark.filterwarnings("ignore:upsample_factor=1.25 delivers")  # the "other factor" runs below ask for it on purpose
@@ -608,9 +700,12 @@ def test_sim_auto_upsample_factor(gpu):
         assert np.array_equal(auto, same) or rel_l2(auto, same) < 1e-14
         assert 0 < rel_l2(auto, other) < 20 * max(cfg["eps"], 1e-9)  # a different grid, the same answer
     sub = dict(wide, baselines=wide["baselines"][:40])
-    assert rel_l2(fftvis_amd.simulate_vis(**dict(sub, upsample_factor=None)), oracle_simulate(sub)) < TOL
-    # fp32: 1.25 from eps = 1e-4 upwards (where it is as accurate as 2), 2 below
     exact = oracle_simulate(sub)
+    g = fftvis_amd.simulate_vis(**dict(sub, upsample_factor=None))
+    assert rel_l2(g, exact) < TOL
+    check_forward(g, sub, exact, label="2")
+    # fp32: 1.25 from eps = 1e-4 upwards (where it is as accurate as 2), 2 below
+    exact32 = oracle_simulate(dict(sub, precision=1), fp32_inputs=True)
     for eps, expect in ((1e-4, 1.25), (1e-5, 2)):
         c32 = dict(sub, precision=1, eps=eps)
         auto = fftvis_amd.simulate_vis(**dict(c32, upsample_factor="auto"))
@@ -618,6 +713,7 @@ def test_sim_auto_upsample_factor(gpu):
         other = fftvis_amd.simulate_vis(**dict(c32, upsample_factor=2 if expect == 1.25 else 1.25))
         assert rel_l2(auto, same) < 1e-6 < rel_l2(auto, other)  # fp32 atomics: equal up to summation order
         assert auto.dtype == np.complex64 and rel_l2(auto, exact) < 1e-3
+        check_forward(auto, dict(c32, upsample_factor=expect), exact32, label=("fp32", eps))
 
 
 def test_sim_c3_full_catalog_two_grids_agree(gpu):
@@ -635,6 +731,8 @@ def test_sim_c3_full_catalog_two_grids_agree(gpu):
     sub = sorted(rng.choice(61075, 24, replace=False))
     exact = oracle_simulate(dict(cfg, baselines=[cfg["baselines"][i] for i in sub]))
     assert rel_l2(v2[..., sub], exact) < TOL and rel_l2(va[..., sub], exact) < TOL
+    check_forward(v2, cfg, exact, sub=sub, label="sigma 2")
+    check_forward(va, dict(cfg, upsample_factor=1.25), exact, sub=sub, label="sigma 1.25")
 
 
 def test_sim_idle_handles_are_reused_safely(gpu, monkeypatch):
@@ -770,6 +868,7 @@ def test_sim_type1_lattice_path(gpu):
     t1 = fftvis_amd.simulate_vis(**c1)  # griddable hex -> type 1
     exp = oracle_simulate(dict(c1, force_use_type3=False))
     assert rel_l2(t1, exp) < TOL and rel_l2(t1, t3) < 2 * TOL
+    check_forward(t1, c1, exp, label="hex-7")
     # polarized table beam + polarized sky + two beams with a flipped baseline and an auto
     tab = fftvis_amd.TabulatedBeam(synth.synthetic_efield_table(freqs), freqs)
     tab2 = fftvis_amd.TabulatedBeam(synth.synthetic_efield_table(freqs, diameter=12.0), freqs)
@@ -778,21 +877,29 @@ def test_sim_type1_lattice_path(gpu):
     cfg = dict(c1, polarized=True, beam=[tab, tab2], beam_idx=bidx, fluxes=fl4,
                baselines=c1["baselines"] + [(3, 0), (6, 1), (2, 2)])
     got = fftvis_amd.simulate_vis(**cfg)
-    assert rel_l2(got, oracle_simulate(dict(cfg, force_use_type3=False))) < TOL
+    exact = oracle_simulate(dict(cfg, force_use_type3=False))
+    assert rel_l2(got, exact) < TOL
+    check_forward(got, cfg, exact, label="two beams")
     # 3x3 square grid, sheared, one antenna removed
     shear = np.array([[1.0, 0.3, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]])
     sq = {i * 3 + j: shear @ np.array([14.6 * i, 14.6 * j, 0.0]) for i in range(3) for j in range(3)}
     sq.pop(4)
     cfgs = dict(c1, ants=sq, baselines=[(a, b) for a in sq for b in sq if a <= b])
     got = fftvis_amd.simulate_vis(**cfgs)
-    assert rel_l2(got, oracle_simulate(dict(cfgs, force_use_type3=False))) < TOL
+    exact = oracle_simulate(dict(cfgs, force_use_type3=False))
+    assert rel_l2(got, exact) < TOL
+    check_forward(got, cfgs, exact, label="square")
     assert rel_l2(got, fftvis_amd.simulate_vis(**cfgs, force_use_type3=True)) < 2 * TOL
     # fp32 and the larger HERA-37 lattice on a reduced catalog
     c2 = dict(synth.make_config("C2", nsrc=2000, nfreq=6, ntimes=2))
     c2.pop("force_use_type3")
-    assert rel_l2(fftvis_amd.simulate_vis(**c2), oracle_simulate(dict(c2, force_use_type3=False))) < TOL
-    g32 = fftvis_amd.simulate_vis(**dict(c1, precision=1, eps=1e-4))
+    g2, e2 = fftvis_amd.simulate_vis(**c2), oracle_simulate(dict(c2, force_use_type3=False))
+    assert rel_l2(g2, e2) < TOL
+    check_forward(g2, c2, e2, label="HERA-37")
+    c32 = dict(c1, precision=1, eps=1e-4)
+    g32 = fftvis_amd.simulate_vis(**c32)
     assert g32.dtype == np.complex64 and rel_l2(g32, exp) < 5e-3
+    check_forward(g32, c32, oracle_simulate(dict(c32, force_use_type3=False), fp32_inputs=True), label="fp32")
 
 
 def _ref_hex_grid():
@@ -842,6 +949,12 @@ def test_simulate_gridded_type1_vs_type3(gpu, polarized, precision, shear_array,
     if precision == 2:
         exp = oracle_simulate(dict(kw, force_use_type3=False))
         assert rel_l2(t1, exp) < 1e-8 and rel_l2(t3, exp) < 1e-8
+    else:  # the rounded-input oracle
+        exp = oracle_simulate(dict(kw, force_use_type3=False), fp32_inputs=True)
+    check_forward(t1, dict(kw, force_use_type3=False), exp, label="type 1")
+    # (fp64: the type-3 runs of these 1 - 30 m lattices at eps 1e-10 measure higher than every other 2-D run)
+    check_forward(t3, dict(kw, force_use_type3=True), exp, label="type 3",
+                  family="2-D, gridded matrix type 3" if precision == 2 else None)
 
 
 def _random_sim_config(rng, lattice=False):
@@ -890,17 +1003,23 @@ def test_sim_fuzz_random_configurations(gpu):
     rng = np.random.default_rng(2024)
     for it in range(32):
         cfg = _random_sim_config(rng)
-        err = rel_l2(fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg))
+        got, exact = fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg)
+        err = rel_l2(got, exact)
         assert err < 10 * cfg["eps"] + 1e-12, (it, err, cfg["eps"], cfg["polarized"], len(cfg["ants"]))
+        check_forward(got, cfg, exact, label=it)
     for it in range(16):
         cfg = _random_sim_config(rng, lattice=True)
-        err = rel_l2(fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg))
+        got, exact = fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg)
+        err = rel_l2(got, exact)
         assert err < 10 * cfg["eps"] + 1e-12, ("lattice", it, err, cfg["eps"], cfg["polarized"], len(cfg["ants"]))
+        check_forward(got, cfg, exact, label=("lattice", it))
     for it in range(24):  # low upsampling (sigma = 1.25: eps floor ~1e-8 in fp64, see fv_eskernel.h)
         cfg = _random_sim_config(rng, lattice=it % 4 == 3)
         cfg.update(upsample_factor=1.25, eps=max(cfg["eps"], 1e-8))
-        err = rel_l2(fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg))
+        got, exact = fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg)
+        err = rel_l2(got, exact)
         assert err < 10 * cfg["eps"] + 1e-12, ("sigma 1.25", it, err, cfg["eps"], cfg["polarized"], len(cfg["ants"]))
+        check_forward(got, cfg, exact, label=("sigma 1.25", it))
 
 
 def test_sim_c3_geometry_subset_and_paths(gpu):
@@ -913,7 +1032,9 @@ def test_sim_c3_geometry_subset_and_paths(gpu):
     rng = np.random.default_rng(1)
     sub = sorted(rng.choice(61075, 48, replace=False))
     sub_cfg = dict(cfg, baselines=[cfg["baselines"][i] for i in sub])
-    assert rel_l2(v3[..., sub], oracle_simulate(sub_cfg)) < TOL
+    exact = oracle_simulate(sub_cfg)
+    assert rel_l2(v3[..., sub], exact) < TOL
+    check_forward(v3, cfg, exact, sub=sub)
     v1 = fftvis_amd.simulate_vis(**dict(cfg, force_use_type3=False))
     assert rel_l2(v1, v3) < 2 * TOL
     _, _, fl2 = synth.catalog(20_000, cfg["freqs"], 9)
@@ -945,6 +1066,7 @@ def test_third_party_analytic_beams_closed_form_and_sampled(gpu, monkeypatch):
                 got = fftvis_amd.simulate_vis(**c)
                 exp = oracle_simulate(c)
                 assert rel_l2(got, exp) < TOL, (type(beam).__name__, pol, feed, rel_l2(got, exp))
+                check_forward(got, c, exp, label=(type(beam).__name__, pol, feed))
             want = orc.evaluate_beam(oracle_beam(beam, pol, cfg["freqs"]), az, za, pol, 240e6)
             have = ev.evaluate_beam(beam, az, za, pol, 240e6)
             assert np.abs(have - want).max() <= 1e-7 * np.abs(want).max(), (type(beam).__name__, pol)
@@ -978,9 +1100,14 @@ def test_reference_compat_off_gives_the_exact_symmetries(gpu):
              "lattice": dict(two, force_use_type3=False)}
     for name, c in cases.items():
         ex = fftvis_amd.simulate_vis(**c, reference_compat=False)
-        assert rel_l2(ex, oracle_simulate(dict(c, reference_compat=False))) < TOL, name
+        cx = dict(c, reference_compat=False)
+        e_ex = oracle_simulate(cx)
+        assert rel_l2(ex, e_ex) < TOL, name
+        check_forward(ex, cx, e_ex, label=(name, "exact"))
         ref = fftvis_amd.simulate_vis(**c)
-        assert rel_l2(ref, oracle_simulate(c)) < TOL and rel_l2(ex, ref) > 1e-3, name  # the two forms do differ
+        e_ref = oracle_simulate(c)
+        assert rel_l2(ref, e_ref) < TOL and rel_l2(ex, ref) > 1e-3, name  # the two forms do differ
+        check_forward(ref, c, e_ref, label=(name, "reference"))
         # the direct computation: the same two antennas with their beams listed (first, second): never flipped
         for n, (a1, a2) in enumerate(bls):
             if bidx[a1] > bidx[a2]:
@@ -1000,16 +1127,26 @@ def test_reference_compat_off_gives_the_exact_symmetries(gpu):
                                           [fftvis_amd.TabulatedBeam(b.data.real.astype(complex), f3) for b in b3])):
         c = dict(c3, beam=beams, beam_idx=idx3, baselines=bl3)
         ex = fftvis_amd.simulate_vis(**c, reference_compat=False)
-        assert rel_l2(ex, oracle_simulate(dict(c, reference_compat=False))) < TOL, name
-        assert rel_l2(fftvis_amd.simulate_vis(**c), oracle_simulate(c)) < TOL, name
+        cx = dict(c, reference_compat=False)
+        e_ex = oracle_simulate(cx)
+        assert rel_l2(ex, e_ex) < TOL, name
+        check_forward(ex, cx, e_ex, label=(name, "exact"))
+        ref, e_ref = fftvis_amd.simulate_vis(**c), oracle_simulate(c)
+        assert rel_l2(ref, e_ref) < TOL, name
+        check_forward(ref, c, e_ref, label=(name, "reference"))
     # Q2: complex basis beams
     rng = np.random.default_rng(4)
     coefs = 0.3 * (rng.normal(size=(7, 2, len(freqs))) + 1j * rng.normal(size=(7, 2, len(freqs))))
     coefs[:, 0] += 1.0
     bas = dict(c1, polarized=True, beam=[ta, tb], beam_coefs=coefs, baselines=bls, fluxes=fl4)
     ex = fftvis_amd.simulate_vis(**bas, reference_compat=False)
-    assert rel_l2(ex, oracle_simulate(dict(bas, reference_compat=False))) < TOL
-    assert rel_l2(fftvis_amd.simulate_vis(**bas), oracle_simulate(bas)) < TOL
+    bx = dict(bas, reference_compat=False)
+    e_ex = oracle_simulate(bx)
+    assert rel_l2(ex, e_ex) < TOL
+    check_forward(ex, bx, e_ex, label="eigenbeams, exact")
+    ref, e_ref = fftvis_amd.simulate_vis(**bas), oracle_simulate(bas)
+    assert rel_l2(ref, e_ref) < TOL
+    check_forward(ref, bas, e_ref, label="eigenbeams, reference")
     per_ant = [fftvis_amd.TabulatedBeam(sum(coefs[a, k][:, None, None, None, None] * [ta, tb][k].data for k in range(2)),
                                         freqs) for a in range(7)]
     direct = fftvis_amd.simulate_vis(**dict(c1, polarized=True, beam=per_ant, beam_idx=np.arange(7), baselines=bls,

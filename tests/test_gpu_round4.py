@@ -11,7 +11,7 @@ import pytest
 import fftvis_amd
 from fftvis_amd import synth
 from oracle import fftvis_oracle as orc
-from tests.helpers import oracle_beam, oracle_simulate, rel_l2
+from tests.helpers import check_forward, oracle_beam, oracle_simulate, rel_l2
 
 pytestmark = pytest.mark.gpu
 TOL = 5 * 6e-8
@@ -42,6 +42,7 @@ def test_bench_workload_c3z_three_dimensional_transform_matches_the_oracle(gpu):
     sel = dict(cfg, baselines=[cfg["baselines"][i] for i in sub])
     exact = oracle_simulate(sel)
     assert rel_l2(v[..., sub], exact) < TOL
+    check_forward(v, cfg, exact, sub=sub)
     flat = oracle_simulate(dict(sel, ants={k: np.array([p[0], p[1], 0.0]) for k, p in cfg["ants"].items()}))
     assert rel_l2(flat, exact) > 100 * TOL  # the z term is not noise
 
@@ -69,6 +70,7 @@ def test_bench_workload_scattered_array_matches_the_oracle(gpu, monkeypatch):
     sub = sorted(np.random.default_rng(5).choice(61075, 16, replace=False))
     exact = oracle_simulate(dict(cfg, baselines=[cfg["baselines"][i] for i in sub]))
     assert rel_l2(v[..., sub], exact) < TOL
+    check_forward(v, cfg, exact, sub=sub)
 
 
 def test_partial_pin_refusal_leaves_nothing_pinned_and_the_result_intact(gpu, monkeypatch):
@@ -133,6 +135,10 @@ def test_float32_rounded_unit_vectors_at_the_horizon_run_in_fp64(gpu):
                          coord_mgr=OMgr(coh, cfg["times"], cfg["telescope_loc"], cfg["ra"], cfg["dec"]))
     idx = [cfg["baselines"].index(b) for b in sub]
     assert rel_l2(got[..., idx], exact) < TOL
+    scale = orc.simulate(cfg["ants"], cfg["freqs"], cfg["fluxes"], beams, cfg["ra"], cfg["dec"], cfg["times"],
+                         cfg["telescope_loc"], baselines=sub, polarized=True, force_use_type3=True, mode="scale",
+                         coord_mgr=OMgr(coh, cfg["times"], cfg["telescope_loc"], cfg["ra"], cfg["dec"]))
+    check_forward(got, cfg, exact, scale=scale, sub=idx)
 
 
 def _last_handle_stats():
@@ -186,6 +192,7 @@ def test_height_terms_replace_the_third_grid_dimension(gpu, monkeypatch, name):
     gpu_simulate.release_handles()
     exact = oracle_simulate(cfg)
     assert got.shape == exact.shape and rel_l2(got, exact) < 5 * eps
+    check_forward(got, cfg, oracle_simulate(cfg, fp32_inputs=True) if cfg.get("precision") == 1 else exact, label=name)
     monkeypatch.setenv("FFTVIS_HIP_NO_WTERM", "1")
     grid3 = fftvis_amd.simulate_vis(**cfg)
     st3 = _last_handle_stats()
@@ -211,7 +218,9 @@ def test_height_terms_at_decimetres_and_their_limit(gpu, monkeypatch):
         gpu_simulate.release_handles()
         got = fftvis_amd.simulate_vis(**cfg)
         terms.append(int(_last_handle_stats()["height_terms"]))
-        assert rel_l2(got, oracle_simulate(cfg)) < TOL, sigma_m
+        exact = oracle_simulate(cfg)
+        assert rel_l2(got, exact) < TOL, sigma_m
+        check_forward(got, cfg, exact, label=sigma_m)
     gpu_simulate.release_handles()
     assert 2 <= terms[0] < terms[1] <= 16 and terms[2] == 0, terms
 
@@ -315,6 +324,7 @@ def test_direct_third_dimension_equals_the_three_pass_transform(gpu, monkeypatch
         for mode, v in got.items():
             vs = v if sub is None else v[..., sub]
             assert rel_l2(vs, exact) < TOL, (name, mode)
+            check_forward(v, cfg, exact, sub=sub, label=(name, mode))
         assert rel_l2(got["direct"], got["three-pass"]) < 2 * TOL, name
 
 
@@ -366,8 +376,10 @@ def test_fuzz_heights_from_millimetres_to_metres(gpu, monkeypatch):
         st = _last_handle_stats()
         kinds.add("K" if st["height_terms"] else "3-D" if st["n2_3"] > 1 else "2-D")
         light += st["height_terms_light_from"] > 0
-        err = rel_l2(got, oracle_simulate(cfg))
+        exact = oracle_simulate(cfg)
+        err = rel_l2(got, exact)
         assert err < 10 * eps + 1e-12, (it, err, eps, zs, st["height_terms"], st["height_terms_light_from"], pol, nbeam)
+        check_forward(got, cfg, exact, label=(it, zs, st["height_terms"]))
     gpu_simulate.release_handles()
     assert kinds == {"K", "3-D", "2-D"} or kinds == {"K", "3-D"}, kinds
     assert light >= 10, light  # (18 000 configurations of scratch/fuzz_r4.py with this switch: half took the light plan, 2 beyond 10 eps -- a plain 2-D run and an fp32 one)
@@ -380,8 +392,14 @@ def test_light_height_terms_on_a_large_grid(gpu, monkeypatch):
     inside the tolerance, and both agree with the oracle's exact 3-D sums on a subset of the baselines."""
     from fftvis_amd.gpu import gpu_simulate
 
+    from fftvis_amd.gpu.gpu_simulate import prepare_array
+
     cfg = synth.make_config("C3", nsrc=3000, nfreq=2, ntimes=1, z_scatter=0.03)
-    sub = sorted(np.random.default_rng(1).choice(61075, 64, replace=False))
+    # a random subset, the 8 baselines of largest |b_z| (the highest height terms weigh most there) and the 8 longest
+    _, bls, _ = prepare_array(cfg["ants"], cfg["baselines"], 1e-6, np.float64)
+    length = np.linalg.norm(bls[:2], axis=0)
+    sub = sorted(set(np.random.default_rng(1).choice(61075, 64, replace=False)) | set(np.argsort(np.abs(bls[2]))[-8:])
+                 | set(np.argsort(length)[-8:]))
     gpu_simulate.release_handles()
     got = fftvis_amd.simulate_vis(**cfg)
     st = _last_handle_stats()
@@ -389,6 +407,7 @@ def test_light_height_terms_on_a_large_grid(gpu, monkeypatch):
     assert st["height_terms_light_from"] < st["height_terms_lighter_from"] <= st["height_terms"] - 2, st  # two light classes here
     exp = oracle_simulate(dict(cfg, baselines=[cfg["baselines"][i] for i in sub]))
     assert rel_l2(got[..., sub], exp) < TOL
+    check_forward(got, cfg, exp, sub=sub)
     monkeypatch.setenv("FFTVIS_HIP_NO_WTERM_LIGHT", "1")
     gpu_simulate.release_handles()
     full = fftvis_amd.simulate_vis(**cfg)
@@ -437,6 +456,7 @@ def test_beam_spline_orders_other_than_1_and_3(gpu, order):
         got = fftvis_amd.simulate_vis(**c)
         exp = oracle_simulate(c)
         assert rel_l2(got, exp) < 2e-9, (order, path, rel_l2(got, exp))
+        check_forward(got, c, exp, label=(order, path))
     if order in (2, 5):  # and it IS a different interpolant from its neighbours
         other = fftvis_amd.simulate_vis(**dict(cfg, beam_spline_opts={"order": 3}))
         assert rel_l2(other, exp) > 1e-7
@@ -451,12 +471,16 @@ def test_fp32_low_upsampling_does_not_degrade_below_its_floor(gpu):
     for cfg, floor in ((synth.make_config("C1", nsrc=300, nfreq=3, ntimes=2), 1e-5),
                        (synth.make_config("C1", nsrc=300, nfreq=3, ntimes=2, z_scatter=2.0), 1e-4)):
         exp = oracle_simulate(dict(cfg, precision=2))
+        exp32 = oracle_simulate(dict(cfg, precision=1), fp32_inputs=True)
         errs = {}
         for eps in (1e-4, 6e-8, 1e-9):
+            c = dict(cfg, precision=1, upsample_factor=1.25, eps=eps)
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)  # (the engine says so itself: test_upsample_1p25_...)
-                got = fftvis_amd.simulate_vis(**dict(cfg, precision=1, upsample_factor=1.25, eps=eps))
+                got = fftvis_amd.simulate_vis(**c)
             errs[eps] = rel_l2(got, exp)
+            # asked below the fp32 floor of sigma = 1.25 (1e-4, the engine warns): the error follows that floor, not eps
+            check_forward(got, c, exp32, label=(floor, eps), family="fp32 sigma 1.25, eps below its floor" if eps < 1e-4 else None)
         assert errs[6e-8] < floor and errs[1e-9] < floor, errs
         assert errs[1e-9] < 3 * errs[1e-4] + 1e-6, errs
 
@@ -486,9 +510,11 @@ def test_fuzz_with_every_spline_order(gpu):
                 cfg["eps"] = max(cfg["eps"], 1e-4 if flat else 1e-3)
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)
-            err = rel_l2(fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg))
+            got, exact = fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg)
+            err = rel_l2(got, exact)
         lim = 10 * cfg["eps"] + (1e-12 if cfg.get("precision", 2) == 2 else 2e-6)
         assert err < lim, (it, err, cfg["eps"], cfg.get("beam_spline_opts"), cfg.get("precision", 2), cfg.get("upsample_factor"))
+        check_forward(got, cfg, exact if cfg.get("precision", 2) == 2 else oracle_simulate(cfg, fp32_inputs=True), label=it)
 
 
 def test_c_abi_catalog_exchange_over_rccl_one_rank(gpu):
@@ -613,4 +639,6 @@ def test_integration_stub_call_sequence_with_raw_ctypes(gpu):
         ck(L.fv_sim_run(h, 0, ntimes, 0, nfreqs, vp(vis), 0))
     finally:
         L.fv_sim_destroy(h)
-    assert rel_l2(vis, oracle_simulate(dict(cfg, eps=eps))) < 5 * eps
+    exact = oracle_simulate(dict(cfg, eps=eps))
+    assert rel_l2(vis, exact) < 5 * eps
+    check_forward(vis, dict(cfg, eps=eps), exact)

@@ -17,7 +17,7 @@ from fftvis_amd._lib import FftvisHipError
 from fftvis_amd.gpu import gpu_nufft2d
 from fftvis_amd.gpu.nufft import gpu_nudft_direct
 from oracle import fftvis_oracle as orc
-from tests.helpers import oracle_simulate, rel_l2
+from tests.helpers import check_forward, oracle_simulate, rel_l2
 
 pytestmark = pytest.mark.gpu
 TOL = 5 * 6e-8
@@ -39,12 +39,14 @@ def test_sim_c4_million_sources(gpu, monkeypatch):
     s16 = sub[:16]
     exact = oracle_simulate(dict(cfg, baselines=[cfg["baselines"][i] for i in s16]))
     assert rel_l2(v[..., s16], exact) < TOL
+    check_forward(v, cfg, exact, sub=s16)
     # the oracle's per-source strengths summed by brute force on the GPU for all 64
     monkeypatch.setattr(orc, "nudft_type3", lambda coords, c, targets, **kw: gpu_nudft_direct(coords, c, targets))
     brute = oracle_simulate(dict(cfg, baselines=[cfg["baselines"][i] for i in sub]))
     monkeypatch.undo()
     assert rel_l2(v[..., sub], brute) < TOL
     assert rel_l2(brute[..., :16], exact) < 1e-10  # the two checkers agree with each other
+    check_forward(v, cfg, brute, sub=sub, label="brute force")
     # linearity at full size: V(a - 2 b) = V(a) - 2 V(b)
     _, _, fl2 = synth.catalog(1_000_000, cfg["freqs"], 9)
     vb = fftvis_amd.simulate_vis(**dict(cfg, fluxes=fl2))
@@ -68,8 +70,10 @@ def test_sim_c5_eigenbeams_fp32(gpu, monkeypatch):
     assert v.dtype == np.complex64 and v.shape == (2, 1, 2, 2, 61075) and np.isfinite(v).all()
     rng = np.random.default_rng(5)
     sub = sorted(rng.choice(61075, 24, replace=False))
-    exact = oracle_simulate(dict(cfg, baselines=[cfg["baselines"][i] for i in sub]))
+    sub_cfg = dict(cfg, baselines=[cfg["baselines"][i] for i in sub])
+    exact = oracle_simulate(sub_cfg)
     assert rel_l2(v[..., sub], exact) < 2e-3
+    check_forward(v, cfg, oracle_simulate(sub_cfg, fp32_inputs=True), sub=sub)
     # the diagonal (k, k) terms ride the Hermitian packing (two transforms instead of four): same answer without it
     monkeypatch.setenv("FFTVIS_HIP_NO_HERMITIAN", "1")
     plain = fftvis_amd.simulate_vis(**cfg)
@@ -109,7 +113,9 @@ def test_sim_source_chunks_and_memory_knobs(gpu):
     ref = fftvis_amd.simulate_vis(**c1)
     for n in (2, 3, 100, 1000):  # more chunks than sources is clipped (wrapper.py: min(..., nsrc))
         assert rel_l2(fftvis_amd.simulate_vis(**dict(c1, min_chunks=n)), ref) < 1e-12, n
-    assert rel_l2(ref, oracle_simulate(c1)) < TOL
+    exact = oracle_simulate(c1)
+    assert rel_l2(ref, exact) < TOL
+    check_forward(ref, c1, exact)
     c2 = synth.make_config("C2", nsrc=3000, nfreq=16, ntimes=5)
     r2 = fftvis_amd.simulate_vis(**c2)
     assert rel_l2(fftvis_amd.simulate_vis(**dict(c2, min_chunks=3)), r2) < 1e-12
@@ -223,7 +229,9 @@ def test_type1_entry_buffers_hold_a_sky_that_is_all_up(gpu):
     t3 = fftvis_amd.simulate_vis(**cfg, force_use_type3=True)
     assert np.isfinite(t1).all() and rel_l2(t1, t3) < 1e-11
     sub = cfg["baselines"][::40]
-    assert rel_l2(fftvis_amd.simulate_vis(**dict(cfg, baselines=sub)), oracle_simulate(dict(cfg, baselines=sub, force_use_type3=False))) < 1e-11
+    g, e = fftvis_amd.simulate_vis(**dict(cfg, baselines=sub)), oracle_simulate(dict(cfg, baselines=sub, force_use_type3=False))
+    assert rel_l2(g, e) < 1e-11
+    check_forward(g, dict(cfg, baselines=sub), e, family="lattice, eps 1e-13")
 
 
 def test_bad_coordinates_fail_loudly(gpu):
@@ -254,7 +262,9 @@ def test_bad_coordinates_fail_loudly(gpu):
 
     with pytest.raises(FftvisHipError, match="outside"):
         fftvis_amd.simulate_vis(**cfg, coord_mgr=Mgr())
-    assert rel_l2(fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg)) < TOL
+    g, e = fftvis_amd.simulate_vis(**cfg), oracle_simulate(cfg)
+    assert rel_l2(g, e) < TOL
+    check_forward(g, cfg, e)
 
 
 def test_runs_are_bitwise_reproducible_without_the_fused_gather(gpu):
@@ -344,7 +354,10 @@ def test_plain_bench_line_and_dumped_outputs(gpu, tmp_path):
     assert sorted(os.listdir(tmp_path)) == ["vis.npy"]
     d = np.load(tmp_path / "vis.npy")
     assert d.dtype == np.float64 and d.shape == (8, 2, 21, 2)
-    assert rel_l2(d[..., 0] + 1j * d[..., 1], oracle_simulate(synth.make_config("C1"))) < TOL
+    c1 = synth.make_config("C1")
+    exact = oracle_simulate(c1)
+    assert rel_l2(d[..., 0] + 1j * d[..., 1], exact) < TOL
+    check_forward(d[..., 0] + 1j * d[..., 1], c1, exact)
 
 
 def _band_block(name, f0, f1, ntimes, seed=0):
@@ -382,6 +395,7 @@ def test_launches_the_bench_times_are_parity_checked(gpu, monkeypatch, name, f0,
     sub = sorted(np.random.default_rng(17).choice(61075, nsub, replace=False))
     exact = oracle_simulate(dict(cfg, baselines=[cfg["baselines"][i] for i in sub]))
     assert rel_l2(v[..., sub], exact) < TOL
+    check_forward(v, cfg, exact, sub=sub)
     monkeypatch.setenv("FFTVIS_HIP_NO_HERMITIAN", "1")
     plain = fftvis_amd.simulate_vis(**cfg)
     monkeypatch.delenv("FFTVIS_HIP_NO_HERMITIAN")
@@ -413,7 +427,6 @@ def test_hermitian_packing_matches_four_transforms(gpu, monkeypatch):
              "real and complex beam": dict(two_real, beam=[real_a, cfg["beam"]]),   # (0,1) keeps four transforms
              "non-coplanar": dict(cfg, ants=tilted, baselines=bl[::9]),
              "chunks": dict(cfg, min_chunks=3), "fp32": dict(cfg, precision=1, eps=1e-4)}
-    sub = list(range(0, len(bl), 40)) + [len(bl) - 3, len(bl) - 2, len(bl) - 1]
     for name, c in cases.items():
         monkeypatch.delenv("FFTVIS_HIP_NO_HERMITIAN", raising=False)
         packed = fftvis_amd.simulate_vis(**c)
@@ -426,9 +439,14 @@ def test_hermitian_packing_matches_four_transforms(gpu, monkeypatch):
         for a in range(2):
             for b in range(2):
                 assert rel_l2(packed[:, :, a, b], plain[:, :, a, b]) < 4 * tol, (name, a, b)
+        # every case and every product group against the oracle (fp32: its rounded inputs), not only against the
+        # four-transform run; every 40th baseline and the last three (autos, pairs given "backwards")
+        n = len(c["baselines"])
+        sub = list(range(0, n, 40)) + [n - 3, n - 2, n - 1]
+        exact = oracle_simulate(dict(c, baselines=[c["baselines"][i] for i in sub]), fp32_inputs=True)
         if name in ("unpolarized sky", "polarized sky", "two real beams"):
-            cs = dict(c, baselines=[c["baselines"][i] for i in sub])
-            assert rel_l2(packed[..., sub], oracle_simulate(cs)) < TOL, name
+            assert rel_l2(packed[..., sub], exact) < TOL, name
+        check_forward(packed, c, exact, sub=sub, label=name)
     monkeypatch.delenv("FFTVIS_HIP_NO_HERMITIAN", raising=False)
 
 
@@ -485,7 +503,14 @@ def test_redundant_baselines_are_gathered_once(gpu, monkeypatch):
             assert np.array_equal(once[..., n - 4], once[..., n - 3]) and np.array_equal(once[..., n - 4], once[..., 7])
             sub = sorted(set(rng.choice(n - 4, 12, replace=False)) | {int(back[0]), int(back[1]), n - 4, n - 2, n - 1})
             cs = dict(c, baselines=[c["baselines"][i] for i in sub])
-            assert rel_l2(once[..., sub], oracle_simulate(cs)) < TOL, name
+            exact = oracle_simulate(cs)
+            assert rel_l2(once[..., sub], exact) < TOL, name
+            check_forward(once, c, exact, sub=sub, label=name)
+        if name in ("two beams, exact symmetries", "fp32"):  # flipped members of mirror runs, exact form; fp32
+            n = len(c["baselines"])
+            sub = sorted(set(rng.choice(n - 4, 12, replace=False)) | {int(back[0]), int(back[1]), n - 4, n - 2, n - 1})
+            cs = dict(c, baselines=[c["baselines"][i] for i in sub])
+            check_forward(once, c, oracle_simulate(cs, fp32_inputs=True), sub=sub, label=name)
     gpu_simulate.release_handles()
 
 
@@ -652,6 +677,7 @@ def test_prunings_fuzz_on_large_regular_arrays(gpu, monkeypatch):
         assert np.isfinite(v).all()
         assert rel_l2(v, w) < 10 * cfg["eps"], (it, rel_l2(v, w), cfg["eps"])
         assert rel_l2(v[..., sub], exact) < 10 * cfg["eps"] + 1e-12, (it, rel_l2(v[..., sub], exact), cfg["eps"])
+        check_forward(v, cfg, exact, sub=sub, label=it)
     assert planned >= 5, planned  # the generator does reach the planned regime
     gpu_simulate.release_handles()
 
