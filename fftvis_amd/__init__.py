@@ -3,7 +3,8 @@
 Mirrors the reference package's public surface for the gpu backend
 (src/fftvis/__init__.py:1-31): ``simulate_vis``, the engine / evaluator factories and the
 ``gpu`` sub-package; beyond it, the adjoint of ``simulate_vis`` with respect to the fluxes
-(``simulate_vis_adjoint``) and a torch autograd entry point (``torch_simulate_vis``).
+(``simulate_vis_adjoint``) and a torch autograd entry point (``torch_simulate_vis``), and for basis beams the gradients
+with respect to the fluxes and the coefficients (``simulate_vis_basis_adjoint``, ``torch_simulate_vis_basis``).
 """
 
 __version__ = "0.1.0"
@@ -12,4 +13,9 @@ from .core.beams import AiryBeam, TabulatedBeam  # noqa: F401
 from .core.beam_basis import compute_beam_basis, compute_beam_basis_per_freq  # noqa: F401
 from .core.simulate import SimulationEngine, default_accuracy_dict  # noqa: F401
 from .wrapper import create_beam_evaluator, create_simulation_engine, simulate_vis  # noqa: F401
-from .adjoint import simulate_vis_adjoint, torch_simulate_vis  # noqa: F401
+from .adjoint import (  # noqa: F401
+    simulate_vis_adjoint,
+    simulate_vis_basis_adjoint,
+    torch_simulate_vis,
+    torch_simulate_vis_basis,
+)

@@ -7,6 +7,10 @@
 because the map is real-linear, not complex-linear (flipped two-beam baselines are conjugated, fluxes are real Stokes
 parameters).  ``A^T G`` has the shape of ``fluxes``.  The device computes it per (time, frequency group, beam pair)
 with the roles of the forward's type-3 transform swapped (``fv_sim_run_adjoint``, DESIGN.md "Adjoint").
+
+Basis beams (``beam_coefs``) have entry points of their own, ``simulate_vis_basis_adjoint`` and ``torch_simulate_vis_basis``:
+the same adjoint with respect to the fluxes, and the gradient with respect to the coefficients, in which the map is
+sesquilinear (``fv_sim_run_basis_adjoint``).
 """
 
 from __future__ import annotations
@@ -200,3 +204,209 @@ def torch_simulate_vis(fluxes, **kwargs):
     if kwargs.get("beam_coefs") is not None:
         raise NotImplementedError("torch_simulate_vis does not support basis beams (beam_coefs)")
     return _FN.apply(fluxes, kwargs)
+
+
+def simulate_vis_basis_adjoint(
+    vis,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    beam_coefs,
+    telescope_loc,
+    *,
+    wrt=("fluxes", "beam_coefs"),
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = True,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """Gradients of the basis-beam simulation ``simulate_vis(..., beam=<K basis beams>, beam_coefs=C)`` with respect to
+    ``fluxes`` and to ``beam_coefs``, for a visibility-shaped ``vis`` (G = dL/dV, dL = Re sum conj(G) dV).
+
+    * ``"fluxes"``: ``A^T vis`` as ``simulate_vis_adjoint`` defines it, A the map from the fluxes to the visibilities for
+      the given coefficients: Re <simulate_vis(F), vis> = <F, result> for every real F; shape and dtype of the fluxes
+      ((nsrc, nfreqs), or (nsrc, nfreqs, 4) for a full-Stokes sky).
+    * ``"beam_coefs"``: the complex ``gcoefs`` (nant, nbasis, nfreqs) with Re <dV[C; D], vis> = Re <D, gcoefs> for every
+      complex direction D, dV[C; D] the derivative of the visibilities along D (they are sesquilinear in C): what torch
+      returns for a complex leaf.  It needs ``fluxes``, the forward's input.
+
+    ``wrt`` names the gradients wanted -- a name, or a tuple of names; the result is that gradient, or a tuple in
+    ``wrt``'s order.  Only the passes asked for run; a gradient computed alone equals the one from a joint call bit for
+    bit.  ``full_stokes`` defaults to what ``fluxes``' shape says.  ``vis`` is a numpy array or a torch tensor on the run's
+    device (handed over by pointer; the results are then tensors on that device); every other argument means what it
+    means for ``simulate_vis``, ``reference_compat`` included.  ``polarized`` must be True and ``beam_idx`` None, as for
+    the forward."""
+    single = isinstance(wrt, str)
+    names = (wrt,) if single else tuple(wrt)
+    if not names or any(n not in ("fluxes", "beam_coefs") for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"wrt must name 'fluxes', 'beam_coefs' or both, got {wrt!r}")
+    if backend != "gpu":
+        raise ValueError(f"Unsupported backend: {backend}")
+    if beam_coefs is None:
+        raise ValueError("simulate_vis_basis_adjoint needs beam_coefs (simulate_vis_adjoint covers per-antenna beam_idx)")
+    if not polarized:  # the forward's message
+        raise ValueError(
+            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
+        )
+    if eps is None:
+        eps = default_accuracy_dict[precision]
+    ants = {k: np.array(v) for k, v in ants.items()}
+    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
+    if _is_tensor(beam_coefs):
+        beam_coefs = beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy()
+    beam_coefs = np.asarray(beam_coefs)
+    validate_beam_idx(beam_idx, beam_coefs, len(beam_list), len(ants))
+    feed_index(use_feed)
+    if baselines is None:
+        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
+    nsrc = int(np.size(ra))
+    nfreqs = int(np.size(freqs))
+    ntimes = len(julian_dates(times))
+    nbls = len(baselines)
+    if beam_coefs.shape != (len(ants), len(beam_list), nfreqs):
+        raise ValueError("beam_coefs must have shape (nant, nbasis, nfreqs)")
+    if _is_tensor(fluxes):
+        fluxes = fluxes.detach().cpu().numpy()
+    fluxes = np.asarray(fluxes)
+    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
+        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
+    if full_stokes is None:
+        full_stokes = fluxes.ndim == 3
+    if bool(full_stokes) != (fluxes.ndim == 3):
+        raise ValueError(f"full_stokes={full_stokes} does not match fluxes of shape {fluxes.shape}")
+    want = (nfreqs, ntimes, 2, 2, nbls)
+    if tuple(vis.shape) != want:
+        raise ValueError(f"vis must have simulate_vis's output shape {want}, got {tuple(vis.shape)}")
+    rdt = np.float32 if precision == 1 else np.float64
+    cdt = np.complex64 if precision == 1 else np.complex128
+    want_f, want_c = "fluxes" in names, "beam_coefs" in names
+    f_shape = (nsrc, nfreqs, 2, 2) if full_stokes else (nsrc, nfreqs)
+    c_shape = (len(ants), len(beam_list), nfreqs)
+    on_device = _is_tensor(vis) and vis.device.type == "cuda"
+    gflux = gcoefs = None
+    if on_device:
+        import torch
+
+        if (vis.device.index or 0) != int(device):
+            raise ValueError(f"vis lives on {vis.device}, the run is on cuda:{int(device)}")
+        tc = torch.complex64 if precision == 1 else torch.complex128
+        g = vis.detach().to(tc).resolve_conj().resolve_neg()  # (a lazily conjugated view's memory is not G)
+        if want_f:
+            gflux = torch.zeros(f_shape, dtype=tc if full_stokes else (torch.float32 if precision == 1 else torch.float64),
+                                device=vis.device)
+        if want_c:
+            gcoefs = torch.zeros(c_shape, dtype=tc, device=vis.device)
+        torch.cuda.synchronize(vis.device)  # the library's streams do not follow torch's: g and the outputs are complete
+    else:
+        g = vis.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(vis) else vis
+        g = np.asarray(g).astype(cdt, copy=False)
+        if want_f:
+            gflux = np.zeros(f_shape, dtype=cdt if full_stokes else rdt)
+        if want_c:
+            gcoefs = np.zeros(c_shape, dtype=cdt)
+
+    from .wrapper import create_simulation_engine, device_chunks
+
+    engine = create_simulation_engine(backend=backend, device=device)
+    nchunks = device_chunks(device, max_memory, min_chunks, beam_list, 2, 2, len(ants), nsrc, precision,
+                            source_buffer, nfreqs)
+    gc, gk = engine.simulate(
+        ants=ants, freqs=np.asarray(freqs), fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=None,
+        ra=ra, dec=dec, times=times, telescope_loc=telescope_loc, baselines=baselines,
+        precision=precision, polarized=True, eps=eps, upsample_factor=upsample_factor,
+        beam_spline_opts=beam_spline_opts, flat_array_tol=flat_array_tol,
+        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
+        coord_method=coord_method, coord_method_params=coord_method_params,
+        force_use_type3=force_use_type3, force_use_ray=force_use_ray, trace_mem=trace_mem,
+        nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
+        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
+        beam_coefs=beam_coefs.astype(cdt, copy=False), adjoint_of=(g, gflux, gcoefs),
+    )
+    res = {}
+    if want_f:
+        res["fluxes"] = stokes_adjoint(gc, full_stokes)
+    if want_c:
+        res["beam_coefs"] = gk
+    if _is_tensor(vis) and not on_device:  # a host tensor in, host tensors out
+        import torch
+
+        res = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in res.items()}
+    return res[names[0]] if single else tuple(res[n] for n in names)
+
+
+def _basis_autograd_function():
+    import torch
+
+    class _SimulateVisBasis(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fluxes, beam_coefs, kwargs):
+            from .wrapper import simulate_vis
+
+            ctx.kwargs = kwargs
+            ctx.flux_dtype, ctx.coef_dtype = fluxes.dtype, beam_coefs.dtype
+            ctx.coef_device = beam_coefs.device
+            ctx.save_for_backward(fluxes, beam_coefs)
+            vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(),
+                               beam_coefs=beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy(), **kwargs)
+            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            fluxes, beam_coefs = ctx.saved_tensors
+            wrt = tuple(n for n, need in zip(("fluxes", "beam_coefs"), ctx.needs_input_grad[:2]) if need)
+            if not wrt:
+                return None, None, None
+            got = dict(zip(wrt, simulate_vis_basis_adjoint(grad_output, fluxes=fluxes, beam_coefs=beam_coefs, wrt=wrt,
+                                                           **ctx.kwargs)))
+            out = []
+            for name, dt, dev in (("fluxes", ctx.flux_dtype, grad_output.device), ("beam_coefs", ctx.coef_dtype, ctx.coef_device)):
+                g = got.get(name)
+                if g is not None and not _is_tensor(g):
+                    g = torch.from_numpy(g)
+                out.append(None if g is None else g.to(device=dev, dtype=dt))
+            return out[0], out[1], None
+
+    return _SimulateVisBasis
+
+
+_FN_BASIS = None
+
+
+def torch_simulate_vis_basis(fluxes, beam_coefs, **kwargs):
+    """The basis-beam simulation ``simulate_vis(fluxes=, beam_coefs=, beam=<K basis beams>, polarized=True, ...)`` as a torch
+    operation differentiable in both tensors: ``fluxes`` real, (nsrc, nfreqs) or (nsrc, nfreqs, 4); ``beam_coefs`` complex,
+    (nant, nbasis, nfreqs).  Every other argument is a keyword of ``simulate_vis``.  Returns the visibilities as a complex
+    tensor on ``fluxes``' device.  The backward pass is ``simulate_vis_basis_adjoint`` of the incoming gradient, with only
+    the gradients autograd asks for (``ctx.needs_input_grad``): Re(A^H g) for the real fluxes, and for the complex
+    coefficients torch's convention for a complex leaf, dL = Re sum conj(grad) dC."""
+    global _FN_BASIS
+    if _FN_BASIS is None:
+        _FN_BASIS = _basis_autograd_function()
+    return _FN_BASIS.apply(fluxes, beam_coefs, kwargs)

@@ -2432,6 +2432,14 @@ struct InterpArgs {
     // (bt2 = the targets' third coordinate).  0: off.
     int zd_n;
     double zd_h, zd_btc, zd_xc;
+    // Gradient epilogue (k_interp<.., GRAD>; Sim::run_basis_adjoint, the coefficient pass): `out` is then the READ-ONLY
+    // visibility-shaped G, and instead of adding w V into the output block every member adds the inner products
+    //   S[kk, ll] += sum_r conj(G_r) V_r      and (kk != ll)      S[ll, kk] += sum_r conj(G_rs) V_r,   rs the feed-transposed slot,
+    // to its own slot of gs: (nbasis^2, gs_nf, gs_nbls) complex fp64, slot ((term gs_nf + gs_f0 + fg) gs_nbls + baseline).
+    // A pair's list holds every baseline once, so a slot has one owner thread per launch: plain read-modify-write.
+    void *gs;
+    int gs_nf, gs_f0;
+    int64_t gs_nbls;
 };
 
 // Bessel function of the first kind and integer order k >= 0 by its power series, (x / 2)^k / k! sum_m (-x^2 / 4)^m /
@@ -2481,7 +2489,7 @@ __device__ inline cplx<double> wterm_factor(int k, double zc, double zh, double 
 // gather spent 70 % of its time waiting for them one at a time.)
 // ZD (direct third dimension, InterpArgs::zd_n) and WT (height terms, InterpArgs::wt_k) are compile-time: carried as run-time
 // branches they cost the plain 2-D gather 47 registers (146 -> 193 fp64, 98 -> 177 fp32: a wave per SIMD, 11-24 % of its time).
-template <typename T, int DIM, bool HERM, int NR, bool ZD = false, bool WT = false>
+template <typename T, int DIM, bool HERM, int NR, bool ZD = false, bool WT = false, bool GRAD = false>
 __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
     const cplx<T> *__restrict__ grid, int64_t N, const T *__restrict__ bt0,
     const T *__restrict__ bt1, const T *__restrict__ bt2, const int *__restrict__ bl_idx,
@@ -2705,6 +2713,23 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                 const int64_t po = rt < 16 ? a.out_pol_off[rt] : (int64_t)rt * a.out_pol_off[1];
                 cplx<T> *ob = out + (int64_t)fg * a.out_fg_stride + km * a.out_k_stride;
                 cplx<T> *o = ob + po;
+                if constexpr (GRAD) {  // inner products with G at the slots the basis epilogue below adds to
+                    cplx<double> *gs = (cplx<double> *)a.gs + ((int64_t)(a.gs_f0 + fg)) * a.gs_nbls + km;
+                    const int64_t ts = (int64_t)a.gs_nf * a.gs_nbls;
+                    if (a.basis_part != 2) {
+                        const cplx<T> g1 = *o;
+                        cplx<double> *s1 = gs + (int64_t)(a.kk * a.nbasis + a.ll) * ts;
+                        s1->re += (double)g1.re * vr + (double)g1.im * vim_;
+                        s1->im += (double)g1.re * vim_ - (double)g1.im * vr;
+                    }
+                    if (a.kk != a.ll && a.basis_part != 1) {
+                        const cplx<T> g2 = ob[a.out_pol_off[(r & 1) * 2 + (r >> 1)]];
+                        cplx<double> *s2 = gs + (int64_t)(a.ll * a.nbasis + a.kk) * ts;
+                        s2->re += (double)g2.re * vr + (double)g2.im * vim_;
+                        s2->im += (double)g2.re * vim_ - (double)g2.im * vr;
+                    }
+                    continue;
+                }
                 if (a.basis) {
                     const int f = a.f_first + fg;
                     const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
@@ -2766,7 +2791,8 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
             const bool neg = (flip && flip[m]) != (a.negate_all != 0);
             cplx<T> *ob = out + (int64_t)fg * a.out_fg_stride + km * a.out_k_stride;
             cplx<double> w1 = {1.0, 0.0}, w2 = {0.0, 0.0};
-            if (a.basis) {  // eigenbeam term (k, l): vis += conj(C[a1,k]) C[a2,l] V  (+ the transposed (l, k) term)
+            cplx<double> s1 = {0.0, 0.0}, s2 = {0.0, 0.0};  // GRAD: this member's inner products over the four products
+            if (a.basis && !GRAD) {  // eigenbeam term (k, l): vis += conj(C[a1,k]) C[a2,l] V  (+ the transposed (l, k) term)
                 const int f = a.f_first + fg;
                 const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
                 const cplx<T> c1k = coef[(cs1 + a.kk) * a.ncoef_freq + f];
@@ -2786,6 +2812,17 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                 const double xr = o_re[r] * wf.re - o_im[r] * wf.im, xi = o_re[r] * wf.im + o_im[r] * wf.re;
                 const double vr = xr, vi = neg ? -xi : xi;  // conj for flipped baselines
                 cplx<T> *o = ob + a.out_pol_off[a.transpose_flipped && neg ? (r & 1) * 2 + (r >> 1) : r];
+                if constexpr (GRAD) {
+                    const cplx<T> g1 = *o;
+                    s1.re += (double)g1.re * vr + (double)g1.im * vi;
+                    s1.im += (double)g1.re * vi - (double)g1.im * vr;
+                    if (a.kk != a.ll) {
+                        const cplx<T> g2 = ob[a.out_pol_off[(r & 1) * 2 + (r >> 1)]];
+                        s2.re += (double)g2.re * vr + (double)g2.im * vi;
+                        s2.im += (double)g2.re * vi - (double)g2.im * vr;
+                    }
+                    continue;
+                }
                 if (a.basis) {
                     const cplx<double> v1 = cmul(w1, cplx<double>{vr, vi});
                     o->re += (T)v1.re;
@@ -2801,6 +2838,18 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                     o->im += (T)vi;
                 } else {
                     *o = {(T)vr, (T)vi};
+                }
+            }
+            if constexpr (GRAD) {
+                const int64_t ts = (int64_t)a.gs_nf * a.gs_nbls;
+                cplx<double> *gs = (cplx<double> *)a.gs + ((int64_t)(a.gs_f0 + fg)) * a.gs_nbls + km;
+                cplx<double> *d1 = gs + (int64_t)(a.kk * a.nbasis + a.ll) * ts;
+                d1->re += s1.re;
+                d1->im += s1.im;
+                if (a.kk != a.ll) {
+                    cplx<double> *d2 = gs + (int64_t)(a.ll * a.nbasis + a.kk) * ts;
+                    d2->re += s2.re;
+                    d2->im += s2.im;
                 }
             }
         }
@@ -2875,6 +2924,10 @@ struct BasisTerm {
     const int *ant1, *ant2;  // device (nbls) antenna index of each baseline
     int kk, ll, nbasis, nfreq, f_first;
     int part = 0, negate = 0;  // InterpArgs::basis_part / negate_all
+    // gradient epilogue (InterpArgs::gs): `out` is G, the inner products go to gs; nullptr: the forward's epilogue
+    void *gs = nullptr;
+    int gs_nf = 0, gs_f0 = 0;
+    int64_t gs_nbls = 0;
 };
 
 // Height term handed to Nufft3::interp (InterpArgs::wt_*)
@@ -3918,6 +3971,10 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
         coef = (const cplx<T> *)basis->coef;
         ant1 = basis->ant1;
         ant2 = basis->ant2;
+        a.gs = basis->gs;
+        a.gs_nf = basis->gs_nf;
+        a.gs_f0 = basis->gs_f0;
+        a.gs_nbls = basis->gs_nbls;
     }
     a.w = ker.w;
     a.tpol = tpol;
@@ -3989,6 +4046,19 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
     if (wt)
         kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true> : k_interp<T, 2, true, 16, false, true>)
                     : (r9 ? k_interp<T, 2, false, 9, false, true> : k_interp<T, 2, false, 16, false, true>);
+    if (a.gs) {  // the gradient epilogue's instantiations (basis mode: never the direct third dimension's 2-D form with height terms)
+        FV_REQUIRE(basis && a.gs_nbls > 0 && a.gs_nf >= a.gs_f0 + nfg, "gradient epilogue: a basis term and its S block");
+        kern = gdim == 2 ? (herm ? (r9 ? k_interp<T, 2, true, 9, false, false, true> : k_interp<T, 2, true, 16, false, false, true>)
+                                 : (r9 ? k_interp<T, 2, false, 9, false, false, true> : k_interp<T, 2, false, 16, false, false, true>))
+                         : (herm ? (r9 ? k_interp<T, 3, true, 9, false, false, true> : k_interp<T, 3, true, 16, false, false, true>)
+                                 : (r9 ? k_interp<T, 3, false, 9, false, false, true> : k_interp<T, 3, false, 16, false, false, true>));
+        if (zd)
+            kern = herm ? (r9 ? k_interp<T, 2, true, 9, true, false, true> : k_interp<T, 2, true, 16, true, false, true>)
+                        : (r9 ? k_interp<T, 2, false, 9, true, false, true> : k_interp<T, 2, false, 16, true, false, true>);
+        if (wt)
+            kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true, true> : k_interp<T, 2, true, 16, false, true, true>)
+                        : (r9 ? k_interp<T, 2, false, 9, false, true, true> : k_interp<T, 2, false, 16, false, true, true>);
+    }
     hipLaunchKernelGGL(kern, grid, dim3(INTERP_THREADS), 0, stream, (const cplx<T> *)grid_out, N, bt[0], bt[1], bt[2],
                        bl_idx, flip, scale_dev, a, ker, out, coef, ant1, ant2, ustart, upairs);
 }

@@ -774,6 +774,147 @@ __global__ void k_adj_strengths(AdjStrengthArgs a, const cplx<T> *__restrict__ g
     if (bad) atomicAdd(err_nan, bad);
 }
 
+// Basis beams (fv_sim_run_basis_adjoint, flux pass): per (k <= l) term the forward's basis epilogue adds
+//     V_b[r] += w1_b M_r(b),   V_b[rs] += w2_b X_r(b)  (k != l; rs the feed-transposed slot),
+//     w1 = conj(C[a1,k]) C[a2,l],  w2 = conj(C[a1,l]) C[a2,k],   X_r(b) = M_r(b)  or (exact form)  conj(M_r(-b)),
+// M_r the transform of the (k, l) strengths.  So every member of a run enters with its own weights:
+//     q_ur  = sum_b conj(G_b[r]) w1_b  (+ conj(G_b[rs]) w2_b, reference form)       at the run's vector b_u,
+//     q'_ur = sum_b G_b[rs] conj(w2_b)                                             at -b_u (exact form: mirror != 0),
+// the mirrored sources following the nu plain ones.  Same fold and butterfly as k_adj_strengths.
+struct AdjBasisArgs {
+    int kk, ll, nbasis, ncoef_freq, f_first, mirror;
+};
+template <typename T>
+__global__ void k_adj_strengths_basis(AdjStrengthArgs a, AdjBasisArgs ba, const cplx<T> *__restrict__ g,
+                                      const int *__restrict__ idx, const int *__restrict__ ustart,
+                                      const cplx<T> *__restrict__ coef, const int *__restrict__ ant1,
+                                      const int *__restrict__ ant2, cplx<T> *__restrict__ q, int *__restrict__ err_nan) {
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / ADJ_GROUP;
+    const int lg = threadIdx.x & (ADJ_GROUP - 1);
+    if (i >= a.nu * a.nfg) return;  // (whole groups exit together)
+    const int64_t u = i % a.nu;
+    const int fg = (int)(i / a.nu);
+    const int f = ba.f_first + fg;
+    const int64_t m0 = ustart ? ustart[u] : u, m1 = ustart ? ustart[u + 1] : u + 1;
+    const cplx<T> *gf = g + (int64_t)fg * a.g_f_stride;
+    const bool offd = ba.kk != ba.ll;
+    double sr[4] = {0.0, 0.0, 0.0, 0.0}, si[4] = {0.0, 0.0, 0.0, 0.0};  // at b
+    double tr[4] = {0.0, 0.0, 0.0, 0.0}, ti[4] = {0.0, 0.0, 0.0, 0.0};  // at -b
+    int bad = 0;
+    for (int64_t m = m0 + lg; m < m1; m += ADJ_GROUP) {  // the baselines that share this vector (basis lists: none flipped)
+        const int64_t k = idx ? idx[m] : m;
+        const int64_t cs1 = (int64_t)ant1[k] * ba.nbasis, cs2 = (int64_t)ant2[k] * ba.nbasis;
+        const cplx<T> c1k = coef[(cs1 + ba.kk) * ba.ncoef_freq + f], c2l = coef[(cs2 + ba.ll) * ba.ncoef_freq + f];
+        const cplx<double> w1 = cmul(cplx<double>{(double)c1k.re, -(double)c1k.im}, cplx<double>{(double)c2l.re, (double)c2l.im});
+        cplx<double> w2 = {0.0, 0.0};
+        if (offd) {
+            const cplx<T> c1l = coef[(cs1 + ba.ll) * ba.ncoef_freq + f], c2k = coef[(cs2 + ba.kk) * ba.ncoef_freq + f];
+            w2 = cmul(cplx<double>{(double)c1l.re, -(double)c1l.im}, cplx<double>{(double)c2k.re, (double)c2k.im});
+        }
+        for (int r = 0; r < 4; ++r) {
+            const cplx<T> v = gf[a.pol_off[r] + k];
+            bad += !(v.re == v.re && v.im == v.im);
+            const cplx<double> x1 = cmul(cplx<double>{(double)v.re, -(double)v.im}, w1);
+            sr[r] += x1.re;
+            si[r] += x1.im;
+            if (offd) {
+                const cplx<T> vt = gf[a.pol_off[(r & 1) * 2 + (r >> 1)] + k];
+                if (ba.mirror) {
+                    const cplx<double> x2 = cmul(cplx<double>{(double)vt.re, (double)vt.im}, cplx<double>{w2.re, -w2.im});
+                    tr[r] += x2.re;
+                    ti[r] += x2.im;
+                } else {
+                    const cplx<double> x2 = cmul(cplx<double>{(double)vt.re, -(double)vt.im}, w2);
+                    sr[r] += x2.re;
+                    si[r] += x2.im;
+                }
+            }
+        }
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int off = ADJ_GROUP / 2; off > 0; off >>= 1) {
+            sr[r] += __shfl_xor(sr[r], off, 64);
+            si[r] += __shfl_xor(si[r], off, 64);
+            tr[r] += __shfl_xor(tr[r], off, 64);
+            ti[r] += __shfl_xor(ti[r], off, 64);
+        }
+    if (lg < 8) {
+        const int r = lg & 3, side = lg >> 2;
+        double vr = side ? tr[0] : sr[0], vi = side ? ti[0] : si[0];
+        for (int rr = 1; rr < 4; ++rr)
+            if (r == rr) {
+                vr = side ? tr[rr] : sr[rr];
+                vi = side ? ti[rr] : si[rr];
+            }
+        const int64_t np = a.nu * (ba.mirror ? 2 : 1);  // sources of the transform
+        if (!side || ba.mirror) q[((int64_t)fg * 4 + r) * np + side * a.nu + u] = {(T)vr, (T)vi};
+    }
+    if (bad) atomicAdd(err_nan, bad);
+}
+
+// NaN entries of a visibility-shaped input, counted where k_adj_strengths counts them (a call that runs only the
+// coefficient pass has no strengths kernel to meet them)
+template <typename T>
+__global__ void k_count_nan(const cplx<T> *__restrict__ g, int64_t n, int *__restrict__ err_nan) {
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const cplx<T> v = g[i];
+        bad += !(v.re == v.re && v.im == v.im);
+    }
+    if (bad) atomicAdd(err_nan, bad);
+}
+
+// Coefficient gradient from the inner products S (k_interp<.., GRAD>): one wave per (antenna a, basis index k, channel f),
+//     gcoefs[a,k,f] += sum_{b: a1(b) = a} sum_l C[a2(b),l,f] S_kl(b)  +  sum_{b: a2(b) = a} sum_l C[a1(b),l,f] conj(S_lk(b)),
+// over the antenna's baselines in the order of the host's list (csr: 2 b + role, role 1 = second antenna; an
+// auto-correlation is in it twice), dealt over the 64 lanes; the S lanes are summed in lane order, the 64 partial sums
+// in a fixed butterfly: no atomics, the bits do not depend on timing.
+struct CoefReduceArgs {
+    const cplx<double> *S[4];
+    int nl, K, nfa, f_base, nfreq, nant;
+    int64_t nbls;
+};
+template <typename T>
+__global__ void k_coef_reduce(CoefReduceArgs a, const int *__restrict__ csr_start, const int *__restrict__ csr,
+                              const int *__restrict__ ant1, const int *__restrict__ ant2, const cplx<T> *__restrict__ coef,
+                              cplx<T> *__restrict__ out) {
+    const int64_t item = (int64_t)blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
+    const int lane = threadIdx.x & 63;
+    if (item >= (int64_t)a.nant * a.K * a.nfa) return;  // (whole waves exit together)
+    const int f = (int)(item % a.nfa);
+    const int k = (int)((item / a.nfa) % a.K);
+    const int an = (int)(item / ((int64_t)a.nfa * a.K));
+    double ar = 0.0, ai = 0.0;
+    for (int e = csr_start[an] + lane; e < csr_start[an + 1]; e += 64) {
+        const int code = csr[e];
+        const int64_t b = code >> 1;
+        const bool second = code & 1;
+        const int64_t other = second ? ant1[b] : ant2[b];
+        for (int l = 0; l < a.K; ++l) {
+            const int term = second ? l * a.K + k : k * a.K + l;
+            const int64_t slot = ((int64_t)term * a.nfa + f) * a.nbls + b;
+            double xr = 0.0, xi = 0.0;
+            for (int li = 0; li < a.nl; ++li) {
+                const cplx<double> v = a.S[li][slot];
+                xr += v.re;
+                xi += v.im;
+            }
+            if (second) xi = -xi;
+            const cplx<T> c = coef[(other * a.K + l) * a.nfreq + a.f_base + f];
+            ar += (double)c.re * xr - (double)c.im * xi;
+            ai += (double)c.re * xi + (double)c.im * xr;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        ar += __shfl_xor(ar, off, 64);
+        ai += __shfl_xor(ai, off, 64);
+    }
+    if (lane == 0) {
+        cplx<T> *o = out + ((int64_t)an * a.K + k) * a.nfreq + a.f_base + f;
+        *o = {(T)((double)o->re + ar), (T)((double)o->im + ai)};
+    }
+}
+
 struct AdjAccArgs {
     int64_t M;           // capacity of the per-time arrays (stride of z); live count is *Mp
     int nfg, f_first;    // channels of the group, catalog index of its first
@@ -1344,6 +1485,8 @@ struct SimBase {
     virtual void run(int t0, int t1, int f0, int f1, void *out, int out_on_device) = 0;
     virtual void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, int accumulate) = 0;
+    virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                                   int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate) = 0;
     // Host destination of the next run (fv_sim_run_into): `out` is then a block INSIDE a larger array -- channel f of
     // the block starts f * out_f_stride elements after `out` (0: the block is contiguous) -- and with out_shared other
     // processes write the rest of that array (a sharded run's ranks filling one shared result): the pinning helper must
@@ -1435,6 +1578,7 @@ class Sim : public SimBase {
         // target-data version adj_serial
         std::unique_ptr<DevBuf> adj_pos;
         int64_t adj_serial = -1;
+        int64_t adj_np = 0;  // sources in adj_pos: nu, or 2 nu with the mirrored set of the exact basis form
     };
     static constexpr double zero3[3] = {0.0, 0.0, 0.0};
     std::vector<Pair> pairs;
@@ -1472,6 +1616,7 @@ class Sim : public SimBase {
         // this lane's fp64 gradient accumulator
         std::unique_ptr<Nufft3<T>> adj;
         DevBuf d_adj_q, d_adj_z, d_adj_acc;
+        DevBuf d_gs;  // basis adjoint, coefficient pass: this lane's inner products S (k_interp<.., GRAD>)
     };
     Lane lanes[4];  // [2], [3]: second pair of the gang mode (see run())
     int lane_mode = -1;       // 0 one stream per lane, 1 pipelined, 2 pipelined gangs: what the lanes last ran as
@@ -1488,6 +1633,9 @@ class Sim : public SimBase {
     hipEvent_t ev_start = nullptr;
     DevBuf d_out, d_mhist;
     DevBuf d_adj_g, d_adj_gf;  // adjoint: host G block / host gradient staged on the device
+    DevBuf d_adj_gc;           // basis adjoint: host coefficient gradient staged on the device
+    DevBuf d_csr_start, d_csr;  // basis mode: per antenna, its baselines as 2 b + role (k_coef_reduce)
+    int nant_basis = 0;
     // sticky device-side error counters, read at every host synchronisation point (check_errors):
     // [0] sources outside the planned box or with NaN coordinates (k_bin_count), [1] type-1 entries
     // dropped because the entry buffers overflowed (k_t1_bin), [2] above-horizon sources that did not
@@ -2064,6 +2212,22 @@ class Sim : public SimBase {
         for (int64_t b = 0; b < nbls; ++b)
             FV_REQUIRE(ant1[b] >= 0 && ant1[b] < nant && ant2[b] >= 0 && ant2[b] < nant, "antenna index out of range");
         nbasis = K;
+        nant_basis = nant;
+        {  // the coefficient gradient's reduction walks every antenna's baselines in this order: by baseline, first role first
+            std::vector<int> start(nant + 1, 0), list((size_t)2 * nbls);
+            for (int64_t b = 0; b < nbls; ++b) {
+                ++start[ant1[b] + 1];
+                ++start[ant2[b] + 1];
+            }
+            for (int a = 0; a < nant; ++a) start[a + 1] += start[a];
+            std::vector<int> fill(start.begin(), start.end() - 1);
+            for (int64_t b = 0; b < nbls; ++b) {
+                list[fill[ant1[b]]++] = (int)(2 * b);
+                list[fill[ant2[b]]++] = (int)(2 * b + 1);
+            }
+            upload(d_csr_start, start.data(), sizeof(int) * start.size(), 0);
+            upload(d_csr, list.data(), sizeof(int) * list.size(), 0);
+        }
         upload(d_coefs, coefs, sizeof(cplx<T>) * (size_t)nant * K * nfreq, 0);
         upload(d_ant1, ant1, sizeof(int) * nbls, 0);
         upload(d_ant2, ant2, sizeof(int) * nbls, 0);
@@ -3060,7 +3224,9 @@ class Sim : public SimBase {
 
     // The unit loop: per (one or two time steps, source chunk) the per-time preparation, then per (frequency group, beam
     // pair, height term) strengths -> spread -> FFT -> gather.
-    void queue_units(const RunPlan &r, const OutBlock &o, Drain &dr) {
+    // gs != nullptr (the basis adjoint's coefficient pass): o is the READ-ONLY G block and every gather adds its inner
+    // products to the S buffer of its stream -- gs[0] when all big kernels share the main stream, else the lane's.
+    void queue_units(const RunPlan &r, const OutBlock &o, Drain &dr, cplx<double> *const *gs = nullptr) {
         const int t0 = r.t0, t1 = r.t1, f0 = r.f0, nt = r.nt, D = r.D, nch = r.ch.n;
         const int64_t csz = r.ch.csz, cap = r.ch.cap;
         const bool pipe = r.pipe, gang = r.gang;
@@ -3253,7 +3419,13 @@ class Sim : public SimBase {
                     RoctxRange rg("gather");
                     size_t e5 = ev_begin(TM_INTERP, ls);
                     BasisTerm bt{d_coefs.p, d_ant1.as<int>(), d_ant2.as<int>(), pr.bi, pr.bj, nbasis,
-                                 (int)freqs.size(), fa};
+                                 (int)freqs.size(), fa, 0, 0, nullptr, 0, 0, 0};
+                    if (gs) {
+                        bt.gs = gs[pipe ? 0 : tu % r.nlanes];
+                        bt.gs_nf = r.nf;
+                        bt.gs_f0 = fa - f0;
+                        bt.gs_nbls = nbls;
+                    }
                     // exact eigenbeam symmetry (reference_compat off): the (l, k) term of an off-diagonal pair of
                     // complex basis beams comes from a second gather at -b (all-real pairs: packed, exact already)
                     const int nparts = nbasis && !reference_compat && pr.bi != pr.bj && !pr.herm ? 2 : 1;
@@ -3342,7 +3514,17 @@ class Sim : public SimBase {
     void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux, int gflux_on_device,
                      int accumulate) override {
         FV_HIP(hipSetDevice(device));
-        FV_REQUIRE(nbasis == 0, "the adjoint does not cover basis beams (set_basis / beam_coefs)");
+        FV_REQUIRE(nbasis == 0, "the adjoint does not cover basis beams (set_basis / beam_coefs): fv_sim_run_basis_adjoint does");
+        adjoint_flux(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, accumulate);
+        adjoint_release();
+        check_errors();
+    }
+
+    // The loop of run_adjoint.  Basis mode (run_basis_adjoint's flux pass): the pairs are the (k <= l) terms over all
+    // baselines, the strengths carry every member's coefficient weights (k_adj_strengths_basis) and, in the exact form
+    // (reference_compat off), an off-diagonal term has a second set of sources at -b.  Ends synchronised.
+    void adjoint_flux(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux, int gflux_on_device,
+                      int accumulate) {
         check_run(t0, t1, f0, f1);
         const int nt = t1 - t0, nf = f1 - f0;
         const int64_t per_tf = (int64_t)tpol * nbls;
@@ -3373,19 +3555,27 @@ class Sim : public SimBase {
         } else {
             source_box(xc, X);
         }
-        // the NUFFT sources of every pair
+        // the NUFFT sources of every pair; exact basis form: an off-diagonal term's sources at b, then the same at -b
+        auto mirrored = [&](const Pair &p) { return nbasis && !reference_compat && p.bi != p.bj; };
+        auto adj_c = [&](const Pair &p) { return mirrored(p) ? (const double *)zero3 : (const double *)p.btc; };
+        auto adj_B = [&](const Pair &p) { return mirrored(p) ? (const double *)p.Bs : (const double *)p.B; };
         for (Pair &p : pairs) {
-            if (p.n == 0 || (p.adj_pos && p.adj_serial == targets_serial)) continue;
             const int64_t nu = p.ustart ? p.nu : p.n;
-            std::vector<T> pos((size_t)D * nu);
+            const int64_t np = nu * (mirrored(p) ? 2 : 1);
+            if (p.n == 0 || (p.adj_pos && p.adj_serial == targets_serial && p.adj_np == np)) continue;
+            std::vector<T> pos((size_t)D * np);
             for (int64_t u = 0; u < nu; ++u) {
                 const int64_t m = p.ustart ? p.h_ustart[u] : u;
                 const double sg = p.h_flip[m] ? -1.0 : 1.0;
-                for (int d = 0; d < D; ++d) pos[(size_t)d * nu + u] = (T)(sg * h_bls[(size_t)d * nbls + p.h_idx[m]]);
+                for (int d = 0; d < D; ++d) {
+                    pos[(size_t)d * np + u] = (T)(sg * h_bls[(size_t)d * nbls + p.h_idx[m]]);
+                    if (np > nu) pos[(size_t)d * np + nu + u] = -pos[(size_t)d * np + u];
+                }
             }
             p.adj_pos.reset(new DevBuf());
             upload(*p.adj_pos, pos.data(), sizeof(T) * pos.size(), 0);
             p.adj_serial = targets_serial;
+            p.adj_np = np;
         }
         // the G block on the device
         const size_t g_bytes = sizeof(cplx<T>) * (size_t)nf * nt * per_tf;
@@ -3397,8 +3587,8 @@ class Sim : public SimBase {
         // grid size (same product of extents as the forward's), upsampling factor and frequency groups
         // (the forward's rule for "auto", with the adjoint's own point count: its sources are the distinct vectors)
         int64_t nu_max = 1;
-        for (const Pair &p : pairs) nu_max = std::max<int64_t>(nu_max, p.ustart ? p.nu : p.n);
-        const double cells2 = cells_at_sigma2(X, D, f0, f1, [](const Pair &p) { return (const double *)p.B; });
+        for (const Pair &p : pairs) nu_max = std::max<int64_t>(nu_max, p.n ? p.adj_np : 0);
+        const double cells2 = cells_at_sigma2(X, D, f0, f1, adj_B);
         const double sigma_a = this->sigma != 0.0 ? this->sigma : auto_sigma(cells2, 0.5 * (double)nsrc + (double)nu_max, D);
         const double cells_top = 2.0 * cells2 * (sigma_a == 2.0 ? 1.0 : std::pow(1.25 / 2.0, D));
         const char *el = std::getenv("FFTVIS_HIP_LANES");
@@ -3476,11 +3666,11 @@ class Sim : public SimBase {
                         const double smax = fmax_of(fa, grp.second);
                         for (const Pair &pr : pairs) {
                             if (pr.n == 0) continue;
-                            const int64_t nu = pr.ustart ? pr.nu : pr.n;
+                            const int64_t nu = pr.ustart ? pr.nu : pr.n, np = pr.adj_np;
                             const T *pos = pr.adj_pos->template as<T>();
                             // sources: the pair's distinct vectors; targets: the directions, scaled per channel
-                            P.set_geometry(pr.btc, pr.B, xc, X, smax);
-                            P.set_sources(nu, pos, pos + nu, D > 2 ? pos + 2 * nu : nullptr);
+                            P.set_geometry(adj_c(pr), adj_B(pr), xc, X, smax);
+                            P.set_sources(np, pos, pos + np, D > 2 ? pos + 2 * np : nullptr);
                             AdjStrengthArgs sa{};
                             sa.nu = nu;
                             sa.nfg = nfg;
@@ -3489,11 +3679,20 @@ class Sim : public SimBase {
                             for (int r = 0; r < 4; ++r) sa.pol_off[r] = pol_off[r];
                             sa.transpose_flipped = !reference_compat;
                             cplx<T> *q = L.d_adj_q.template as<cplx<T>>();
-                            hipLaunchKernelGGL(k_adj_strengths<T>, dim3((unsigned)cdiv(nu * nfg * ADJ_GROUP, 256)), dim3(256), 0, ls, sa,
-                                               dg + ((int64_t)(fa - f0) * nt + (t - t0)) * per_tf,
-                                               pr.trivial ? nullptr : pr.idx->template as<int>(),
-                                               pr.trivial ? nullptr : pr.flip->template as<signed char>(),
-                                               pr.ustart ? pr.ustart->template as<int>() : nullptr, q, d_err.as<int>() + 4);
+                            if (nbasis) {
+                                const AdjBasisArgs ba{pr.bi, pr.bj, nbasis, (int)freqs.size(), fa, np > nu ? 1 : 0};
+                                hipLaunchKernelGGL(k_adj_strengths_basis<T>, dim3((unsigned)cdiv(nu * nfg * ADJ_GROUP, 256)), dim3(256), 0,
+                                                   ls, sa, ba, dg + ((int64_t)(fa - f0) * nt + (t - t0)) * per_tf,
+                                                   pr.trivial ? nullptr : pr.idx->template as<int>(),
+                                                   pr.ustart ? pr.ustart->template as<int>() : nullptr,
+                                                   d_coefs.as<cplx<T>>(), d_ant1.as<int>(), d_ant2.as<int>(), q, d_err.as<int>() + 4);
+                            } else {
+                                hipLaunchKernelGGL(k_adj_strengths<T>, dim3((unsigned)cdiv(nu * nfg * ADJ_GROUP, 256)), dim3(256), 0, ls, sa,
+                                                   dg + ((int64_t)(fa - f0) * nt + (t - t0)) * per_tf,
+                                                   pr.trivial ? nullptr : pr.idx->template as<int>(),
+                                                   pr.trivial ? nullptr : pr.flip->template as<signed char>(),
+                                                   pr.ustart ? pr.ustart->template as<int>() : nullptr, q, d_err.as<int>() + 4);
+                            }
                             P.load_strengths(q, nfg * tpol, tpol, d_freqs.as<double>() + fa);
                             P.spread(nfg * tpol);
                             P.fft(nfg * tpol);
@@ -3537,15 +3736,20 @@ class Sim : public SimBase {
             if (ne > 0) hipLaunchKernelGGL(k_adj_reduce<T>, dim3((unsigned)cdiv(ne, 256)), dim3(256), 0, stream, ra, dgf);
         }
         if (!gflux_on_device && gf_bytes) FV_HIP(hipMemcpyAsync(gflux, dgf, gf_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+    }
+
+    void adjoint_release() {
         // The call ends synchronised.  Its own bulk device memory -- the second transforms' grids, their values at the
         // directions, the accumulators, the staged G and gflux -- is given back when it exceeds FFTVIS_HIP_ADJ_KEEP_BYTES
         // (default 256 MiB): a cached handle then holds for its next forward run what it held before, but for the adjoint
         // plans' tables and per-baseline arrays.  Smaller sets stay for the next call (freeing and reallocating them
-        // doubled a C2 adjoint step).
+        // doubled a C2 adjoint step).  The basis adjoint's inner products S and staged gcoefs count and go likewise.
         FV_HIP(hipStreamSynchronize(stream));
         {
-            size_t bulk = d_adj_g.cap + d_adj_gf.cap;
-            for (Lane &L : lanes) bulk += L.d_adj_z.cap + L.d_adj_acc.cap + (L.adj ? L.adj->buf0.cap + L.adj->buf1.cap : 0);
+            size_t bulk = d_adj_g.cap + d_adj_gf.cap + d_adj_gc.cap;
+            for (Lane &L : lanes)
+                bulk += L.d_adj_z.cap + L.d_adj_acc.cap + L.d_gs.cap + (L.adj ? L.adj->buf0.cap + L.adj->buf1.cap : 0);
             const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
             if ((double)bulk > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
                 for (Lane &L : lanes) {
@@ -3555,12 +3759,122 @@ class Sim : public SimBase {
                     }
                     L.d_adj_z.release();
                     L.d_adj_acc.release();
+                    L.d_gs.release();
                 }
                 d_adj_g.release();
                 d_adj_gf.release();
+                d_adj_gc.release();
             }
         }
+    }
+
+    // ---- basis beams: gradients with respect to the fluxes (gflux += A^T G, as run_adjoint defines it) and to the
+    // coefficients, Re <dV[C; D], G> = Re <D, gcoefs> for every complex direction D (DESIGN.md "Adjoint") ------------------
+    // Flux pass: adjoint_flux.  Coefficient pass: the forward run's own stages with the gather's gradient epilogue
+    // (k_interp<.., GRAD>), which reads G where the forward writes V and adds the inner products S_kl(b) to the fp64 S
+    // buffer of its stream, across time steps, source chunks and height terms; k_coef_reduce then sums the buffers in lane
+    // order and contracts with C.  S is (K^2, channels of a block, nbls) complex fp64: channel blocks keep one buffer under
+    // FFTVIS_HIP_ADJ_ACC_BYTES (default 256 MiB), each block a forward run over its channels.
+    void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                           int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate) override {
+        FV_HIP(hipSetDevice(device));
+        FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_adjoint needs a handle with basis beams (fv_sim_set_basis)");
+        FV_REQUIRE(!type1, "basis beams never take the lattice path");
+        check_run(t0, t1, f0, f1);
+        const int nt = t1 - t0, nf = f1 - f0;
+        const int64_t per_tf = (int64_t)tpol * nbls;
+        // a host G is staged once for both passes
+        FV_HIP(hipStreamSynchronize(stream));
+        const int64_t g_elems = (int64_t)nf * nt * per_tf;
+        const cplx<T> *dg = (const cplx<T> *)gvis;
+        if (!gvis_on_device) {
+            upload(d_adj_g, gvis, sizeof(cplx<T>) * (size_t)g_elems, 0);
+            dg = d_adj_g.as<cplx<T>>();
+        }
+        if (g_elems > 0) {  // NaN in G fails the call before either pass runs
+            hipLaunchKernelGGL(k_count_nan<T>, dim3((unsigned)std::min<int64_t>(cdiv(g_elems, 256), 4096)), dim3(256), 0, stream, dg,
+                               g_elems, d_err.as<int>() + 4);
+            check_errors();
+        }
+        if (gflux) adjoint_flux(t0, t1, f0, f1, dg, 1, gflux, gflux_on_device, accumulate);
+        if (gcoefs) coef_pass(t0, t1, f0, f1, dg, gcoefs, gcoefs_on_device, accumulate);
+        adjoint_release();
         check_errors();
+    }
+
+    void coef_pass(int t0, int t1, int f0, int f1, const cplx<T> *dg, void *gcoefs, int gcoefs_on_device, int accumulate) {
+        const int nt = t1 - t0, nf = f1 - f0, K = nbasis, nfreq = (int)freqs.size();
+        const int64_t per_tf = (int64_t)tpol * nbls;
+        // the adjoint's transforms (or an earlier run) may have the lanes busy, and its runs were built on three components
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipStreamSynchronize(prep_stream));
+        for (int li = 1; li < 4; ++li)
+            if (lanes[li].stream && lanes[li].own_stream) FV_HIP(hipStreamSynchronize(lanes[li].stream));
+        const size_t gc_bytes = sizeof(cplx<T>) * (size_t)nant_basis * K * nfreq;
+        cplx<T> *dgc = (cplx<T> *)gcoefs;
+        if (!gcoefs_on_device) {
+            d_adj_gc.reserve(std::max<size_t>(gc_bytes, 16));
+            dgc = d_adj_gc.as<cplx<T>>();
+            if (accumulate) FV_HIP(hipMemcpyAsync(dgc, gcoefs, gc_bytes, hipMemcpyHostToDevice, stream));
+        }
+        if (!accumulate) FV_HIP(hipMemsetAsync(dgc, 0, gc_bytes, stream));
+        const char *eab = std::getenv("FFTVIS_HIP_ADJ_ACC_BYTES");
+        const double acc_max = eab ? std::atof(eab) : 256.0 * 1024 * 1024;
+        const double per_chan = 16.0 * K * K * (double)std::max<int64_t>(nbls, 1);
+        const int nfb = (int)std::max<double>(1.0, std::min<double>(nf, std::floor(acc_max / per_chan)));
+        for (int b0 = f0; b0 < f1 && nt > 0; b0 += nfb) {
+            const int b1 = std::min(f1, b0 + nfb), nfa = b1 - b0;
+            if (mhist_log.size() > 65536) mhist_log.clear();
+            RunPlan r{t0, t1, b0, b1, nt, nfa};
+            source_box(r.xc, r.X);
+            height_terms(r);
+            pair_setup(r);
+            grid_and_groups(r);
+            light_classes(r);
+            lane_schedule(r);
+            lane_plans(r);
+            r.ch = source_chunks(r.nlanes_used);
+            lane_buffers(r);
+            // one S buffer per stream that runs gathers: the main stream's when the lanes are pipelined, else one per lane
+            const int ns = r.pipe ? 1 : r.nlanes;
+            const size_t s_bytes = sizeof(cplx<double>) * (size_t)K * K * nfa * (size_t)std::max<int64_t>(nbls, 1);
+            cplx<double> *gs[4] = {nullptr, nullptr, nullptr, nullptr};
+            for (int li = 0; li < ns; ++li) {
+                lanes[li].d_gs.reserve(s_bytes);
+                gs[li] = lanes[li].d_gs.template as<cplx<double>>();
+                FV_HIP(hipMemsetAsync(gs[li], 0, s_bytes, stream));  // (the lanes start after what the main stream holds now)
+            }
+            OutBlock o{};
+            o.out = nullptr;
+            o.on_device = true;
+            o.nt = nt;
+            o.nf = nfa;
+            o.dout = const_cast<cplx<T> *>(dg) + (int64_t)(b0 - f0) * nt * per_tf;  // read only: the gradient epilogue never writes it
+            o.per_tf = per_tf;
+            o.run = (int64_t)nt * per_tf;
+            o.fs = o.run;
+            o.bytes = sizeof(cplx<T>) * (size_t)nfa * o.run;
+            o.run_bytes = sizeof(cplx<T>) * (size_t)o.run;
+            o.shared = false;
+            o.drain = false;
+            Drain dr;
+            queue_units(r, o, dr, gs);
+            CoefReduceArgs ca{};
+            for (int li = 0; li < ns; ++li) ca.S[li] = gs[li];
+            ca.nl = ns;
+            ca.K = K;
+            ca.nfa = nfa;
+            ca.f_base = b0;
+            ca.nfreq = nfreq;
+            ca.nant = nant_basis;
+            ca.nbls = nbls;
+            const int64_t items = (int64_t)nant_basis * K * nfa;
+            hipLaunchKernelGGL(k_coef_reduce<T>, dim3((unsigned)cdiv(items, 4)), dim3(256), 0, stream, ca, d_csr_start.as<int>(),
+                               d_csr.as<int>(), d_ant1.as<int>(), d_ant2.as<int>(), d_coefs.as<cplx<T>>(), dgc);
+        }
+        if (!gcoefs_on_device) FV_HIP(hipMemcpyAsync(gcoefs, dgc, gc_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+        if (timing_level) ev_collect();
     }
 
     // beam x coherency strengths of one (frequency group, beam pair) for the lane's current sources

@@ -84,6 +84,16 @@ def _return_handle(key, h):
     _IDLE_HANDLES[key] = h
 
 
+def _buffer_addr(a):
+    """(address, on_device flag) of an adjoint buffer: a numpy array is a host buffer, a torch tensor a device buffer,
+    None a null pointer (an output that is not wanted)."""
+    if a is None:
+        return None, 0
+    if isinstance(a, np.ndarray):
+        return ctypes.c_void_p(a.ctypes.data), 0
+    return ctypes.c_void_p(a.data_ptr()), 1
+
+
 class SimHandle:
     """RAII wrapper of one ``fv_sim`` handle (one GPU context)."""
 
@@ -233,14 +243,19 @@ class SimHandle:
         ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype; ``gflux``: C-contiguous (nsrc, nfreq) real or
         (nsrc, nfreq, 2, 2) complex.  numpy arrays are host buffers, torch tensors device buffers (ready when the call
         is made: the library's streams do not follow torch's).  The call synchronises."""
-        def addr(a):
-            if isinstance(a, np.ndarray):
-                return ctypes.c_void_p(a.ctypes.data), 0
-            return ctypes.c_void_p(a.data_ptr()), 1
-
-        gp, g_dev = addr(g)
-        fp, f_dev = addr(gflux)
+        gp, g_dev = _buffer_addr(g)
+        fp, f_dev = _buffer_addr(gflux)
         _lib.check(self._L.fv_sim_run_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, fp, f_dev, int(bool(accumulate))))
+
+    def run_basis_adjoint(self, t0, t1, f0, f1, g, gflux, gcoefs, accumulate: bool):
+        """Basis beams (``set_basis``): ``gflux += A^T g`` and ``gcoefs +=`` the coefficient gradient for times [t0,t1) x
+        freqs [f0,f1) (``fv_sim_run_basis_adjoint``).  ``g`` and ``gflux`` as for ``run_adjoint``; ``gcoefs``: C-contiguous
+        (nant, nbasis, nfreq) of this engine's complex dtype.  Either output may be None (its pass does not run)."""
+        gp, g_dev = _buffer_addr(g)
+        fp, f_dev = _buffer_addr(gflux)
+        cp, c_dev = _buffer_addr(gcoefs)
+        _lib.check(self._L.fv_sim_run_basis_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, fp, f_dev, cp, c_dev,
+                                                    int(bool(accumulate))))
 
     def run_device(self, t0, t1, f0, f1, out_ptr):
         """Enqueue only; ``out_ptr`` is a device buffer of out_shape() complex elements."""
@@ -424,7 +439,10 @@ class GPUSimulationEngine(SimulationEngine):
         * ``adjoint_of`` (extra; what ``simulate_vis_adjoint`` passes): a pair ``(g, gflux)`` -- instead of simulating,
           the engine configured by these arguments adds the adjoint of its map from ``fluxes`` (which then only give
           the catalog's shape) to visibilities, applied to ``g`` (the result's shape, this precision's complex dtype),
-          into ``gflux`` (``SimHandle.run_adjoint``) and returns ``gflux``.
+          into ``gflux`` (``SimHandle.run_adjoint``) and returns ``gflux``.  With ``beam_coefs`` (what
+          ``simulate_vis_basis_adjoint`` passes) a triple ``(g, gflux, gcoefs)``, either output None when not wanted:
+          ``SimHandle.run_basis_adjoint`` adds both gradients (``fluxes`` are then the forward's) and the call returns
+          ``(gflux, gcoefs)``.
         """
         beam_order = checked_spline_order(beam_spline_opts)
         if interpolation_function not in ("az_za_map_coordinates", "az_za_simple"):
@@ -552,7 +570,10 @@ class GPUSimulationEngine(SimulationEngine):
             if coord_mgr is not None:
                 coord_mgr.setup()
             if adjoint_of is not None:
-                result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr)
+                if use_basis != (len(adjoint_of) == 3):
+                    raise ValueError("adjoint_of: (g, gflux, gcoefs) with beam_coefs, (g, gflux) without")
+                result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr,
+                                      gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis)
                 ok = True
                 return result
             if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != complex_dtype):
@@ -661,9 +682,10 @@ def _topo_from_coord_mgr(coord_mgr, time_indices):
     return np.stack(out)
 
 
-def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr):
+def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False):
     """The adjoint's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors), each block's
-    contribution added to ``gflux``.  Every ``run_adjoint`` call ends synchronised."""
+    contribution added to ``gflux`` (``basis``: and to ``gcoefs``; returns the pair).  Every ``run_adjoint`` call ends
+    synchronised."""
     on_device = not isinstance(g, np.ndarray)
     step = max(nblk_t, 1)
     first = True
@@ -679,13 +701,19 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr):
             blk = np.ascontiguousarray(blk)
         if coord_mgr is not None:
             h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
-            h.run_adjoint(0, te - tb, f0, f1, blk, gflux, not first)
+            ta, te_ = 0, te - tb
         else:
-            h.run_adjoint(tb, te, f0, f1, blk, gflux, not first)
+            ta, te_ = tb, te
+        if basis:
+            h.run_basis_adjoint(ta, te_, f0, f1, blk, gflux, gcoefs, not first)
+        else:
+            h.run_adjoint(ta, te_, f0, f1, blk, gflux, not first)
         first = False
     if first:  # no time steps: nothing contributes
-        gflux[...] = 0
-    return gflux
+        for out in (gflux, gcoefs):
+            if out is not None:
+                out[...] = 0
+    return (gflux, gcoefs) if basis else gflux
 
 
 def _time_block(device, nt, nf, nbls, polarized, precision, nsrc_topo=0):

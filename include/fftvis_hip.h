@@ -250,6 +250,22 @@ int fv_sim_run_into(fv_sim *h, int t0, int t1, int f0, int f1, void *out, int64_
  * bitwise reproducible for a given FFTVIS_HIP_LANES.                                                                   */
 int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                        int gflux_on_device, int accumulate);
+/* The same for a handle with basis beams (fv_sim_set_basis), plus the gradient with respect to the coefficients.
+ * gflux += A^T G as above, A the basis-beam map from the catalog's fluxes to the visibilities (linear in the fluxes for
+ * fixed coefficients C).  gcoefs += the gradient of the map's sesquilinear dependence on C: with dV[C; D] the derivative
+ * of the visibilities along a complex direction D of the coefficients, Re <dV[C; D], G> = Re <D, gcoefs> for every D
+ * (dL = Re sum conj(gcoefs) dC when G = dL/dV: what torch returns for a complex leaf).  gcoefs: (nant, nbasis, nfreq)
+ * complex of the handle's precision, the layout of fv_sim_set_basis' coefs; only channels [f0, f1) receive a
+ * contribution.  Either output may be NULL (not wanted, its pass does not run), not both.  accumulate = 0: the outputs
+ * are zeroed first.  fv_sim_set_reference_compat selects the form of the (l, k) terms as in fv_sim_run.  The flux pass is
+ * fv_sim_run_adjoint's with per-baseline coefficient weights; the coefficient pass is a forward run whose gather forms
+ * the inner products of G with the basis visibilities in fp64 -- (nbasis^2, channels, nbls) complex per lane, at most
+ * FFTVIS_HIP_ADJ_ACC_BYTES per lane (channel blocks) -- followed by a per-(antenna, basis index, channel) sum over the
+ * antenna's baselines in a fixed order.  No atomics: bitwise reproducible for a given FFTVIS_HIP_LANES.  Memory is given
+ * back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule above.  The call synchronises.  A handle without fv_sim_set_basis, both
+ * outputs NULL, *_on_device flags other than 0 or 1 and NaN in G fail with FV_ERR_ARG.                                  */
+int fv_sim_run_basis_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                             int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate);
 int fv_sim_sync(fv_sim *h);
 
 /* Introspection for bench/roofline: fills up to n doubles:

@@ -59,6 +59,7 @@ int main() {
     EXPECT(fv_sim_set_beam_airy_scaled(nullptr, 0, 14.0, d9, 1.0) == FV_ERR_ARG);
     EXPECT(fv_sim_run(nullptr, 0, 1, 0, 1, v, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_basis_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_sync(nullptr) == FV_ERR_ARG);
     EXPECT(fv_sim_stats(nullptr, v, 12) == FV_ERR_ARG);
     EXPECT(fv_sim_reset_stats(nullptr) == FV_ERR_ARG);
@@ -102,6 +103,12 @@ int main() {
     EXPECT(fv_sim_run_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, nullptr, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 0, nullptr, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 2, v, 0, 0) == FV_ERR_ARG);
+    // so does the basis adjoint; either of its outputs may be null, not both
+    EXPECT(fv_sim_run_basis_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, nullptr, 0, v, 0, v, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_basis_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 0, nullptr, 0, nullptr, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_basis_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 2, v, 0, v, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_basis_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 0, v, 0, v, 3, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_basis_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 0, nullptr, -1, v, 0, 0) == FV_ERR_ARG);
     // a call that gets past the argument checks reports the missing device as a HIP error, not a crash
     if (ndev == 0) {
         EXPECT(fv_sim_create(&h, 0, 2, 1e-6, 2.0, 1) == FV_ERR_HIP && h == nullptr);
