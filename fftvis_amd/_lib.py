@@ -64,6 +64,8 @@ SYMBOLS = {
     "fv_sim_run": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int]),
     "fv_sim_run_into": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int]),
     "fv_sim_run_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int]),
+    "fv_sim_set_adjoint_path": (c_int, [c_void_p, c_int]),
+    "fv_sim_last_adjoint_path": (c_int, [c_void_p]),
     "fv_sim_run_basis_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                          c_int, c_int]),
     "fv_comm_unique_id": (c_int, [c_void_p]),

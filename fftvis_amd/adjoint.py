@@ -6,7 +6,8 @@
 
 because the map is real-linear, not complex-linear (flipped two-beam baselines are conjugated, fluxes are real Stokes
 parameters).  ``A^T G`` has the shape of ``fluxes``.  The device computes it per (time, frequency group, beam pair)
-with the roles of the forward's type-3 transform swapped (``fv_sim_run_adjoint``, DESIGN.md "Adjoint").
+with the roles of the forward's type-3 transform swapped (``fv_sim_run_adjoint``, DESIGN.md "Adjoint"); on lattice arrays
+``adjoint_path="type2"`` takes the transpose of the type-1 slice instead, a type-2 transform.
 
 Basis beams (``beam_coefs``) have entry points of their own, ``simulate_vis_basis_adjoint`` and ``torch_simulate_vis_basis``:
 the same adjoint with respect to the fluxes, and the gradient with respect to the coefficients, in which the map is
@@ -68,6 +69,7 @@ def simulate_vis_adjoint(
     reference_compat: bool = True,
     astrom: np.ndarray = None,
     device_astrometry: bool = False,
+    adjoint_path: str = "type3",
 ):
     """``A^T vis``: the transpose of ``simulate_vis``'s map from ``fluxes`` to visibilities, for the same arguments.
 
@@ -76,10 +78,16 @@ def simulate_vis_adjoint(
     F satisfies Re <simulate_vis(fluxes), vis> = <fluxes, F> for every real ``fluxes`` and has their shape: (nsrc, nfreqs)
     for Stokes I, (nsrc, nfreqs, 4) with ``full_stokes=True`` (polarized runs only); real, of the run's precision,
     numpy for numpy input and a tensor on ``vis``' device for a tensor.  Every other keyword means what it means for
-    ``simulate_vis``, ``reference_compat`` included; on lattice arrays, where ``simulate_vis`` takes the type-1 transform,
-    the adjoint uses the type-3 transform (both compute the same map to ``eps``).  Sources below the horizon at every
-    time get exactly 0.  Not covered: ``beam_coefs`` (NotImplementedError), a sharded multi-GPU adjoint.
+    ``simulate_vis``, ``reference_compat`` included.  ``adjoint_path`` chooses the transform on lattice arrays, where
+    ``simulate_vis`` takes the type-1 transform: ``"type3"`` (default) the type-3 transform with the roles swapped, as on
+    every other array; ``"type2"`` the transpose of the type-1 slice itself, a type-2 transform (ValueError when the same
+    arguments would not take the lattice path -- not griddable, not flat, ``force_use_type3=True`` -- never a silent
+    fall-back); ``"auto"`` type 2 exactly where the forward takes type 1 and type 3 elsewhere.  All compute the same map
+    to ``eps``.  Sources below the horizon at every time get exactly 0.  Not covered: ``beam_coefs``
+    (NotImplementedError), a sharded multi-GPU adjoint.
     """
+    if adjoint_path not in ("type3", "type2", "auto"):
+        raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {adjoint_path!r}")
     if beam_coefs is not None:
         raise NotImplementedError("simulate_vis_adjoint does not support basis beams (beam_coefs)")
     if backend != "gpu":
@@ -138,7 +146,7 @@ def simulate_vis_adjoint(
         force_use_type3=force_use_type3, force_use_ray=force_use_ray, trace_mem=trace_mem,
         nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
         reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
-        adjoint_of=(g, gflux),
+        adjoint_of=(g, gflux), adjoint_path=adjoint_path,
     )
     out = stokes_adjoint(gc, full_stokes)
     if _is_tensor(vis) and not on_device:  # a host tensor in, a host tensor out
@@ -174,7 +182,8 @@ def _autograd_function():
             ctx.kwargs = kwargs
             ctx.full_stokes = fluxes.ndim == 3
             ctx.flux_dtype = fluxes.dtype
-            vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(), **kwargs)
+            # adjoint_path belongs to the backward pass alone
+            vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(), **{k: v for k, v in kwargs.items() if k != "adjoint_path"})
             return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
 
         @staticmethod
@@ -197,12 +206,15 @@ def torch_simulate_vis(fluxes, **kwargs):
     (nsrc, nfreqs, 4)); every other argument is a keyword of ``simulate_vis`` (``ants``, ``ra``, ``dec``, ``freqs``,
     ``times``, ``beam``, ``telescope_loc``, ...).  Returns the visibilities as a complex tensor on ``fluxes``' device.
     The backward pass is ``simulate_vis_adjoint`` of the incoming gradient: under torch's convention for a real input
-    and a complex output the gradient is Re(A^H g), the adjoint defined there."""
+    and a complex output the gradient is Re(A^H g), the adjoint defined there.  ``adjoint_path`` ("type3" | "type2" |
+    "auto", see ``simulate_vis_adjoint``) goes to the backward pass only; ``simulate_vis`` never sees it."""
     global _FN
     if _FN is None:
         _FN = _autograd_function()
     if kwargs.get("beam_coefs") is not None:
         raise NotImplementedError("torch_simulate_vis does not support basis beams (beam_coefs)")
+    if kwargs.get("adjoint_path", "type3") not in ("type3", "type2", "auto"):
+        raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {kwargs['adjoint_path']!r}")
     return _FN.apply(fluxes, kwargs)
 
 

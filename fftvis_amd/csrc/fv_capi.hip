@@ -594,6 +594,17 @@ int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gv
         h->impl->run_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, accumulate != 0);
     });
 }
+int fv_sim_set_adjoint_path(fv_sim *h, int path) {
+    FV_SIM_CALL(FV_REQUIRE(path == 0 || path == 1, "adjoint path must be 0 (type 3) or 1 (type 2)"); h->impl->adjoint_path = path);
+}
+int fv_sim_last_adjoint_path(fv_sim *h) {
+    int path = 0;
+    const int status = guarded([&] {
+        FV_REQUIRE(h && h->impl, "null handle");
+        path = h->impl->last_adjoint_path;
+    });
+    return status ? status : path;
+}
 int fv_sim_run_basis_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)

@@ -1047,7 +1047,9 @@ __device__ inline void t1_origin(const T1Args &a, const T *__restrict__ xyz, int
 // COUNT = true: histogram of entries per (frequency, bin); false: scatter + tabulate weights.
 // W: the kernel width at compile time (9: the default tolerance in fp64; 0: any) -- with it the record is built
 // in registers and leaves as 16-byte stores (12 for w = 9) instead of 2 w + padding scattered 8-byte ones.
-template <typename T, bool COUNT, int W = 0>
+// IMG = false (the type-2 adjoint's gather, k_t2_gather): one entry per (source, frequency) and no periodic images --
+// the gather loads its tile with wrapped indices.
+template <typename T, bool COUNT, int W = 0, bool IMG = true>
 __global__ void k_t1_bin(T1Args a, const int *__restrict__ Mp, const T *__restrict__ xyz,
                          const double *__restrict__ freqs, int *__restrict__ counts,
                          const int *__restrict__ bin_start, int *__restrict__ cursor,
@@ -1060,8 +1062,8 @@ __global__ void k_t1_bin(T1Args a, const int *__restrict__ Mp, const T *__restri
     double fx, fy;
     t1_origin<T>(a, xyz, p, freqs[a.f_first + f], i0x, i0y, fx, fy);
     // periodic images: every origin congruent mod n2 whose footprint reaches [0, n2)
-    const int ox[2] = {0, i0x < 0 ? a.n2 : (i0x + a.w > a.n2 ? -a.n2 : 0)};
-    const int oy[2] = {0, i0y < 0 ? a.n2 : (i0y + a.w > a.n2 ? -a.n2 : 0)};
+    const int ox[2] = {0, !IMG ? 0 : i0x < 0 ? a.n2 : (i0x + a.w > a.n2 ? -a.n2 : 0)};
+    const int oy[2] = {0, !IMG ? 0 : i0y < 0 ? a.n2 : (i0y + a.w > a.n2 ? -a.n2 : 0)};
     for (int iy = 0; iy < (oy[1] ? 2 : 1); ++iy)
         for (int ix = 0; ix < (ox[1] ? 2 : 1); ++ix) {
             const int jx = i0x + ox[ix], jy = i0y + oy[iy];
@@ -1424,6 +1426,109 @@ __global__ void k_t1_pick(const cplx<T> *__restrict__ X, int no, int P, int cnt,
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Type-2 adjoint of the type-1 path (Sim::adjoint_flux_type2; DESIGN.md "Adjoint").  The transpose of the slice above:
+//     Z_jr = sum_m q_mr exp(+i m . theta_j),   q_mr = sum of conj(H_kr) over the baselines at (sign-adjusted) mode m,
+// H the flip-adjusted conj(G) of k_adj_strengths.  Mode fill (deconvolved, exact zeros elsewhere), the pruned FFT the
+// other way round (na = n_modes + 1 inputs, all n2 outputs), periodic gather at the (source, frequency) entries.
+// ---------------------------------------------------------------------------------------------
+
+// Thread <-> (cell ix fastest, iy, plane = (channel, product)) of the FFT's input planes A [plane][iy][ix], mode =
+// index - na / 2.  cell_start / cell_runs: the runs (k_adj_strengths' u) at each cell of ONE plane -- one run for a
+// pair's list in (u, v) order, every member of its own when the list was left as given; summed in list order.  Every
+// cell is written once: no memset, no atomics.
+template <typename T>
+__global__ void k_t2_fill(int na, int nplanes, int64_t nu, const int *__restrict__ cell_start,
+                          const int *__restrict__ cell_runs, const cplx<T> *__restrict__ q, const T *__restrict__ dec,
+                          cplx<T> *__restrict__ A) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t cells = (int64_t)na * na;
+    if (idx >= cells * nplanes) return;
+    const int c = (int)(idx % cells);
+    const int64_t plane = idx / cells;
+    const int ix = c % na, iy = c / na;
+    double sr = 0.0, si = 0.0;
+    for (int k = cell_start[c]; k < cell_start[c + 1]; ++k) {
+        const cplx<T> v = q[plane * nu + cell_runs[k]];
+        sr += (double)v.re;
+        si += (double)v.im;
+    }
+    const double d = (double)dec[ix] * (double)dec[iy];
+    A[idx] = {(T)(sr * d), (T)(si * d)};
+}
+
+// One workgroup of four waves per (frequency, 8 x 8-cell bin of footprint origins) of k_t1_bin<.., IMG = false>'s
+// entry order; TP = transforms per plane (1 or 4).  The bin's entries all read one (8 + w - 1)^2 tile of the
+// transform's output X [plane][out_pos(lx)][ly]: the workgroup stages it in LDS once, with wrapped indices (the planes
+// are periodic), as tile[r][tx][ty] -- ty contiguous as in memory, and a transform's plane on its own so that the 16
+// lanes of an entry read 16 consecutive values.  (Four waves on one tile, not one: the tile's 16 KiB per workgroup
+// bound a CU to ten single waves, too few to cover the staging loads -- 1.24 -> 1.00 ms per 32-channel C3 launch.)
+// Then sixteen entries at a time, 16 lanes each: lane g < w owns the footprint's row
+// y = i0y + g, walks the w columns with wx[k] handed round by shuffles, scales by wy[g]; a fixed
+// butterfly combines the 16 lanes.  Every entry's Z goes once to the slot k_adj_accumulate reads: no atomics, and the
+// result does not depend on the order of the entries inside a bin.
+constexpr int T2_THREADS = 256;
+template <typename T, int TP>
+__global__ __launch_bounds__(T2_THREADS) void k_t2_gather(T1Args a, int P, int cnt, const unsigned char *__restrict__ recs,
+                                                  const int *__restrict__ bin_start, const cplx<T> *__restrict__ grid,
+                                                  cplx<T> *__restrict__ z) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char t2_smem[];
+    cplx<T> *tile = reinterpret_cast<cplx<T> *>(t2_smem);
+    const int bin = blockIdx.x;
+    const int s = bin_start[bin], e1 = (int)min((int64_t)bin_start[bin + 1], a.ecap);
+    if (s >= e1) return;  // (the whole workgroup)
+    const int bx = bin % a.nb1, by = (bin / a.nb1) % a.nb1, f = bin / (a.nb1 * a.nb1);
+    const int Tt = (1 << BINLOG) + a.w - 1, TT = Tt * Tt;
+    const int x0 = (bx << BINLOG) - T1_PAD, y0 = (by << BINLOG) - T1_PAD;  // origins of the bin: [x0, x0 + 8)
+    const int tid = threadIdx.x;
+    for (int i = tid; i < TP * TT; i += T2_THREADS) {
+        const int ty = i % Tt, tx = (i / Tt) % Tt, r = i / TT;
+        int gx = x0 + tx, gy = y0 + ty;  // in [-PAD, n2 + 8 + w): one wrap either way
+        gx += gx < 0 ? a.n2 : 0;
+        gx -= gx >= a.n2 ? a.n2 : 0;
+        gy += gy < 0 ? a.n2 : 0;
+        gy -= gy >= a.n2 ? a.n2 : 0;
+        tile[i] = grid[(((int64_t)f * TP + r) * a.n2 + out_pos(gx, P, cnt)) * a.n2 + gy];
+    }
+    __syncthreads();
+    const int g = tid & 15, grp = tid >> 4;
+    const int gc = min(g, a.w - 1);  // lanes beyond the kernel width carry zero weights
+    for (int it = s; it < e1; it += T2_THREADS / 16) {
+        const bool ok = it + grp < e1;
+        const unsigned char *rec = recs + (int64_t)(ok ? it + grp : e1 - 1) * a.rec;
+        const int4 h = *reinterpret_cast<const int4 *>(rec);
+        const T *wr = reinterpret_cast<const T *>(rec + T1_HDR);
+        const T wxg = g < a.w ? wr[g] : T(0), wyg = g < a.w ? wr[a.w + g] : T(0);
+        const cplx<T> *t0 = tile + (h.x - x0) * Tt + (h.y - y0) + gc;
+        cplx<T> acc[TP];
+#pragma unroll
+        for (int r = 0; r < TP; ++r) acc[r] = {T(0), T(0)};
+        for (int k = 0; k < a.w; ++k) {
+            const T wxk = __shfl(wxg, (tid & 48) + k, 64);  // (of this wave's lanes: the entry's group starts at lane tid & 48)
+#pragma unroll
+            for (int r = 0; r < TP; ++r) {
+                const cplx<T> v = t0[r * TT + k * Tt];
+                acc[r].re += wxk * v.re;
+                acc[r].im += wxk * v.im;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < TP; ++r) {
+            acc[r].re *= wyg;
+            acc[r].im *= wyg;
+            for (int off = 8; off > 0; off >>= 1) {
+                acc[r].re += __shfl_xor(acc[r].re, off, 64);
+                acc[r].im += __shfl_xor(acc[r].im, off, 64);
+            }
+        }
+        if (ok && g == 0) {
+            const int64_t p = h.z / a.nfg;  // ent = p nfg + f
+#pragma unroll
+            for (int r = 0; r < TP; ++r) z[((int64_t)f * TP + r) * a.cap + p] = acc[r];
+        }
+    }
+}
+
 // Brute-force type-3 sum on the device (independent checker; fp64 accumulation).
 template <typename T>
 __global__ void k_nudft_direct(int dim, int64_t M, const T *__restrict__ x, const T *__restrict__ y,
@@ -1493,6 +1598,10 @@ struct SimBase {
     // then neither write to it nor register more than the block's own runs.  Reset by every run.
     int64_t out_f_stride = 0;
     int out_shared = 0;
+    // fv_sim_set_adjoint_path (0: the swapped type-3 transform, 1: the type-2 transform of a lattice handle) and what the
+    // last run_adjoint took (fv_sim_last_adjoint_path: 0 none yet, 2, 3)
+    int adjoint_path = 0;
+    int last_adjoint_path = 0;
     virtual void sync() = 0;
     virtual void stats(double *v, int n) = 0;
     virtual void reset_stats() = 0;
@@ -1579,6 +1688,10 @@ class Sim : public SimBase {
         std::unique_ptr<DevBuf> adj_pos;
         int64_t adj_serial = -1;
         int64_t adj_np = 0;  // sources in adj_pos: nu, or 2 nu with the mirrored set of the exact basis form
+        // the type-2 adjoint's mode -> run table (mode_cells): na^2 + 1 cell starts, then the runs cell by cell
+        std::unique_ptr<DevBuf> t2_cells;
+        int64_t t2_serial = -1;
+        int t2_na = 0;
     };
     static constexpr double zero3[3] = {0.0, 0.0, 0.0};
     std::vector<Pair> pairs;
@@ -1617,6 +1730,10 @@ class Sim : public SimBase {
         std::unique_ptr<Nufft3<T>> adj;
         DevBuf d_adj_q, d_adj_z, d_adj_acc;
         DevBuf d_gs;  // basis adjoint, coefficient pass: this lane's inner products S (k_interp<.., GRAD>)
+        // type-2 adjoint (lattice handles): the pruned FFT the other way round, its deconvolution table over the input
+        // modes, and this lane's entry-sort buffers (t1_sort)
+        std::unique_ptr<Nufft3<T>> adj2;
+        DevBuf d_t2_dec, d_t2_meta, d_t2_binstart, d_t2_rec;
     };
     Lane lanes[4];  // [2], [3]: second pair of the gang mode (see run())
     int lane_mode = -1;       // 0 one stream per lane, 1 pipelined, 2 pipelined gangs: what the lanes last ran as
@@ -1728,6 +1845,7 @@ class Sim : public SimBase {
         for (Lane &L : lanes) {
             for (auto &P : L.plan) P.reset();
             L.adj.reset();
+            L.adj2.reset();
             if (L.done) (void)hipEventDestroy(L.done);
             if (L.prep_done) (void)hipEventDestroy(L.prep_done);
             if (L.heavy_done) (void)hipEventDestroy(L.heavy_done);
@@ -2663,6 +2781,60 @@ class Sim : public SimBase {
         return c;
     }
 
+    // ---- what the type-1 run and the type-2 adjoint share: planes, frequency batches, the entry sort ----------------
+    struct T1Plan {
+        DimGeom g;     // n2 = P Q (na and no are the caller's: the two transforms prune opposite ends)
+        int nb1;       // bins per dimension
+        int nfb;       // frequencies per batch
+        int64_t ecap;  // entry capacity of a batch
+        int nbins;     // bins of a full batch
+        int rec;       // bytes per entry record
+    };
+    // nf: channels the run walks; cap: slots of the compacted per-time arrays; images: the spread's periodic images
+    // are entries too (the gather of the type-2 adjoint wraps its tile instead: exactly one entry per pair).
+    T1Plan t1_plan(const KerParams &ker, double sigma, int nf, int64_t cap, bool images) const {
+        T1Plan p;
+        p.g.n1 = t1_nmodes;
+        choose_pq(std::max((int)std::ceil(sigma * t1_nmodes), 2 * ker.w + 16), p.g);
+        p.nb1 = (p.g.n2 + T1_PAD) >> BINLOG;
+        // frequencies per batch: bounded by entries (~1.3 per (source, freq)) and by grid bytes
+        const char *eb = std::getenv("FFTVIS_HIP_GRID_BYTES");
+        const double budget = eb ? std::atof(eb) : 8.0 * 1024 * 1024 * 1024;
+        const double plane_bytes = 2.0 * p.g.n2 * (double)p.g.n2 * tpol * sizeof(cplx<T>);
+        // entries per live (source, frequency) pair: 1 + the periodic images of footprints that cross an
+        // edge of the n2 x n2 plane -- (1 + (w + 1) / n2)^2 on average for uniformly placed sources (1.52
+        // at w = 16 on the smallest, 64-cell planes); 5 % head-room on top, and a catalog that still
+        // overflows (sources piled on a plane edge) fails the run (t1 overflow flag), never silently
+        const double img = images ? (1.0 + (ker.w + 1.0) / p.g.n2) * (1.0 + (ker.w + 1.0) / p.g.n2) * 1.05 : 1.0;
+        p.nfb = (int)std::max(1.0, std::min({(double)nf, budget / plane_bytes, 24.0e6 / (img * cap)}));
+        p.ecap = (int64_t)(img * cap * p.nfb) + 4096;
+        p.nbins = p.nfb * p.nb1 * p.nb1;
+        p.rec = t1_record_bytes(ker.w, sizeof(T));
+        return p;
+    }
+    // Counting sort of the (source, frequency) entries of one batch into 8 x 8-cell bins of their footprint origin, with
+    // tabulated weights (k_t1_bin), on stream ps.  meta: 2 (nbins + 1) + 2 ints (counts, cursors), binstart: nbins + 1,
+    // recs: a.ecap records; `scan` lends its scan buffers.
+    template <bool IMG>
+    void t1_sort(const T1Args &a, int nbins, const int *Mp, const T *xyz, DevBuf &meta, DevBuf &binstart, DevBuf &recs,
+                 Nufft3<T> &scan, hipStream_t ps) {
+        const KerParams &ker = scan.ker;
+        const int nbn = a.nfg * a.nb1 * a.nb1;
+        int *counts_p = meta.as<int>(), *cursor_p = counts_p + (nbins + 1), *ovf_p = d_err.as<int>() + 1;
+        FV_HIP(hipMemsetAsync(meta.p, 0, sizeof(int) * (2 * (size_t)(nbins + 1) + 2), ps));
+        const dim3 gb((unsigned)cdiv(a.cap * a.nfg, 256));
+        hipLaunchKernelGGL((k_t1_bin<T, true, 0, IMG>), gb, dim3(256), 0, ps, a, Mp, xyz,
+                           d_freqs.as<double>(), counts_p, (const int *)nullptr, cursor_p,
+                           (unsigned char *)nullptr, (T)ker.beta, (T)ker.c, ovf_p);
+        const hipStream_t own = scan.stream;
+        scan.stream = ps;
+        scan.exclusive_scan(counts_p, binstart.as<int>(), nbn);
+        scan.stream = own;
+        hipLaunchKernelGGL((ker.w == 9 ? k_t1_bin<T, false, 9, IMG> : ker.w == 5 ? k_t1_bin<T, false, 5, IMG> : ker.w == 7 ? k_t1_bin<T, false, 7, IMG> : k_t1_bin<T, false, 0, IMG>), gb, dim3(256), 0, ps, a, Mp,
+                           xyz, d_freqs.as<double>(), counts_p, (const int *)binstart.as<int>(),
+                           cursor_p, recs.as<unsigned char>(), (T)ker.beta, (T)ker.c, ovf_p);
+    }
+
     // ---- type-1 run: per time, per frequency batch: bin (source, freq) entries on periodic
     // n2 x n2 planes, strengths, gather-spread, pruned FFT to the n_modes central modes, pick.
     void run_type1(int t0, int t1, int f0, int f1, const OutBlock &o) {
@@ -2677,34 +2849,21 @@ class Sim : public SimBase {
         sigma_run = sigma;
         if (!t1fft) t1fft.reset(new Nufft3<T>(2, eps, sigma, stream));
         const KerParams &ker = t1fft->ker;
+        const std::array<int64_t, 16> pol_off = pol_offsets();
+        const Chunks ch = source_chunks(4);
+        const int nch = ch.n;
+        const int64_t csz = ch.csz, cap = ch.cap;
         // grid: n2 = P Q >= sigma n_modes (and >= 2 w), all n2 inputs live, n_modes + 1 outputs kept
-        DimGeom g;
-        g.n1 = t1_nmodes;
-        choose_pq(std::max((int)std::ceil(sigma * t1_nmodes), 2 * ker.w + 16), g);
+        const T1Plan tp = t1_plan(ker, sigma, nf, cap, true);
+        DimGeom g = tp.g;
         g.na = g.n2;
         g.no = t1_nmodes + 1;
         t1fft->set_fft_geometry(g, g);
         t1_dec.reserve(sizeof(T) * g.no);
         hipLaunchKernelGGL(k_deconv_table<T>, dim3(cdiv(g.no, 256)), dim3(256), 0, stream, g.no,
                            g.n2, ker, t1_dec.as<T>());
-        const int nb1 = (g.n2 + T1_PAD) >> BINLOG;
-        const std::array<int64_t, 16> pol_off = pol_offsets();
-        const Chunks ch = source_chunks(4);
-        const int nch = ch.n;
-        const int64_t csz = ch.csz, cap = ch.cap;
-        // frequencies per batch: bounded by entries (~1.3 per (source, freq)) and by grid bytes
-        const char *eb = std::getenv("FFTVIS_HIP_GRID_BYTES");
-        const double budget = eb ? std::atof(eb) : 8.0 * 1024 * 1024 * 1024;
-        const double plane_bytes = 2.0 * g.n2 * (double)g.n2 * tpol * sizeof(cplx<T>);
-        // entries per live (source, frequency) pair: 1 + the periodic images of footprints that cross an
-        // edge of the n2 x n2 plane -- (1 + (w + 1) / n2)^2 on average for uniformly placed sources (1.52
-        // at w = 16 on the smallest, 64-cell planes); 5 % head-room on top, and a catalog that still
-        // overflows (sources piled on a plane edge) fails the run (t1 overflow flag), never silently
-        const double img = (1.0 + (ker.w + 1.0) / g.n2) * (1.0 + (ker.w + 1.0) / g.n2) * 1.05;
-        int nfb = (int)std::max(1.0, std::min({(double)nf, budget / plane_bytes, 24.0e6 / (img * cap)}));
-        const int64_t ecap = (int64_t)(img * cap * nfb) + 4096;
-        const int nbins = nfb * nb1 * nb1;
-        const int rec = t1_record_bytes(ker.w, sizeof(T));
+        const int nb1 = tp.nb1, nfb = tp.nfb, nbins = tp.nbins, rec = tp.rec;
+        const int64_t ecap = tp.ecap;
         // Pipelined like the type-3 loop: the entry sort of unit (time, batch) u+1 (three kernels over
         // every (source, frequency) pair, ~25 % of a step) runs on the low-priority stream beside the
         // strengths / spread / FFT / pick of unit u; two sets of sort buffers and two sets of
@@ -2754,20 +2913,9 @@ class Sim : public SimBase {
                 a.ecap = ecap;
                 a.rec = rec;
                 const int nbn = nfg * nb1 * nb1;
-                int *counts_p = meta.as<int>(), *cursor_p = counts_p + (nbins + 1), *ovf_p = d_err.as<int>() + 1;
                 if (pipe && set_pending[ss]) FV_HIP(hipStreamWaitEvent(ps, lanes[ss].heavy_done, 0));
                 size_t e1 = ev_begin(TM_PREP, ps);
-                FV_HIP(hipMemsetAsync(meta.p, 0, sizeof(int) * (2 * (size_t)(nbins + 1) + 2), ps));
-                const dim3 gb((unsigned)cdiv(cap * nfg, 256));
-                hipLaunchKernelGGL((k_t1_bin<T, true>), gb, dim3(256), 0, ps, a, Mp, d_xyz.as<T>(),
-                                   d_freqs.as<double>(), counts_p, (const int *)nullptr, cursor_p,
-                                   (unsigned char *)nullptr, (T)ker.beta, (T)ker.c, ovf_p);
-                t1fft->stream = ps;
-                t1fft->exclusive_scan(counts_p, binstart.as<int>(), nbn);
-                t1fft->stream = stream;
-                hipLaunchKernelGGL((ker.w == 9 ? k_t1_bin<T, false, 9> : ker.w == 5 ? k_t1_bin<T, false, 5> : ker.w == 7 ? k_t1_bin<T, false, 7> : k_t1_bin<T, false, 0>), gb, dim3(256), 0, ps, a, Mp,
-                                   d_xyz.as<T>(), d_freqs.as<double>(), counts_p, (const int *)binstart.as<int>(),
-                                   cursor_p, recs.as<unsigned char>(), (T)ker.beta, (T)ker.c, ovf_p);
+                t1_sort<true>(a, nbins, Mp, d_xyz.as<T>(), meta, binstart, recs, *t1fft, ps);
                 ev_end(e1, ps);
                 if (pipe) {
                     FV_HIP(hipEventRecord(lanes[ss].prep_done, ps));
@@ -3515,17 +3663,51 @@ class Sim : public SimBase {
                      int accumulate) override {
         FV_HIP(hipSetDevice(device));
         FV_REQUIRE(nbasis == 0, "the adjoint does not cover basis beams (set_basis / beam_coefs): fv_sim_run_basis_adjoint does");
-        adjoint_flux(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, accumulate);
+        FV_REQUIRE(adjoint_path == 0 || type1,
+                   "the type-2 adjoint (fv_sim_set_adjoint_path 1) needs a lattice handle (fv_sim_set_array_type1)");
+        adjoint_flux(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, accumulate, adjoint_path == 1);
+        last_adjoint_path = adjoint_path == 1 ? 2 : 3;
         adjoint_release();
         check_errors();
+    }
+
+    // Mode -> run table of a pair for the type-2 adjoint's fill: cell (my + na / 2) na + (mx + na / 2) of a plane lists the
+    // runs (build_unique, three components) whose sign-adjusted integer vector is (mx, my) -- one per mode when the list
+    // is visited in (u, v) order, one per member otherwise.  Counting sort in run order: the fill's sums have a fixed order.
+    void mode_cells(Pair &p, int na) {
+        if (p.n == 0 || (p.t2_cells && p.t2_serial == targets_serial && p.t2_na == na)) return;
+        const int64_t nu = p.ustart ? p.nu : p.n;
+        const size_t cells = (size_t)na * na;
+        std::vector<int> tab(cells + 1 + (size_t)nu, 0), cell((size_t)nu);
+        for (int64_t u = 0; u < nu; ++u) {
+            const int64_t m = p.ustart ? p.h_ustart[u] : u;
+            const double sg = p.h_flip[m] ? -1.0 : 1.0;
+            const int mx = (int)std::lround(sg * h_bls[p.h_idx[m]]), my = (int)std::lround(sg * h_bls[(size_t)nbls + p.h_idx[m]]);
+            FV_REQUIRE(std::abs(mx) < na / 2 && std::abs(my) < na / 2, "integer baseline outside the mode planes");
+            cell[u] = (my + na / 2) * na + (mx + na / 2);
+            ++tab[cell[u] + 1];
+        }
+        for (size_t c = 0; c < cells; ++c) tab[c + 1] += tab[c];
+        std::vector<int> fill(tab.begin(), tab.begin() + cells);
+        for (int64_t u = 0; u < nu; ++u) tab[cells + 1 + fill[cell[u]]++] = (int)u;
+        p.t2_cells.reset(new DevBuf());
+        upload(*p.t2_cells, tab.data(), sizeof(int) * tab.size(), 0);
+        p.t2_serial = targets_serial;
+        p.t2_na = na;
     }
 
     // The loop of run_adjoint.  Basis mode (run_basis_adjoint's flux pass): the pairs are the (k <= l) terms over all
     // baselines, the strengths carry every member's coefficient weights (k_adj_strengths_basis) and, in the exact form
     // (reference_compat off), an off-diagonal term has a second set of sources at -b.  Ends synchronised.
+    // t2 (lattice handles, fv_sim_set_adjoint_path 1): the transpose of run_type1's slice instead of the swapped type-3
+    // transform -- per (time, chunk, frequency batch) one entry sort without periodic images, per beam pair the runs'
+    // strengths filled into the n_modes + 1 central modes (k_t2_fill), run_type1's planes transformed the other way
+    // round (few inputs, all n2 outputs) and gathered at the entries (k_t2_gather).  Strengths, accumulators, channel
+    // blocks, lanes and the reduction are the same code.
     void adjoint_flux(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux, int gflux_on_device,
-                      int accumulate) {
+                      int accumulate, bool t2 = false) {
         check_run(t0, t1, f0, f1);
+        FV_REQUIRE(!t2 || (type1 && nbasis == 0), "the type-2 adjoint needs a lattice handle (fv_sim_set_array_type1)");
         const int nt = t1 - t0, nf = f1 - f0;
         const int64_t per_tf = (int64_t)tpol * nbls;
         // whatever an earlier run queued (a device-output forward run leaves its lanes busy) is finished first: the lanes'
@@ -3545,8 +3727,10 @@ class Sim : public SimBase {
         for (Pair &p : pairs) build_unique(p, tol, 3);
         const int D = dim();
         // box of the directions x = 2 pi R topo (R: the plane rotation, or the lattice basis^T of a type-1 array)
-        double xc[3], X[3];
-        if (type1) {
+        double xc[3] = {0.0, 0.0, 0.0}, X[3] = {0.0, 0.0, 0.0};
+        if (t2) {
+            // no box: the planes are periodic
+        } else if (type1) {
             for (int d = 0; d < 3; ++d) {
                 const double *r = rplane.m + 3 * d;
                 xc[d] = 0.0;
@@ -3562,6 +3746,10 @@ class Sim : public SimBase {
         for (Pair &p : pairs) {
             const int64_t nu = p.ustart ? p.nu : p.n;
             const int64_t np = nu * (mirrored(p) ? 2 : 1);
+            if (t2) {
+                p.adj_np = nu;
+                continue;
+            }
             if (p.n == 0 || (p.adj_pos && p.adj_serial == targets_serial && p.adj_np == np)) continue;
             std::vector<T> pos((size_t)D * np);
             for (int64_t u = 0; u < nu; ++u) {
@@ -3588,8 +3776,9 @@ class Sim : public SimBase {
         // (the forward's rule for "auto", with the adjoint's own point count: its sources are the distinct vectors)
         int64_t nu_max = 1;
         for (const Pair &p : pairs) nu_max = std::max<int64_t>(nu_max, p.n ? p.adj_np : 0);
-        const double cells2 = cells_at_sigma2(X, D, f0, f1, adj_B);
-        const double sigma_a = this->sigma != 0.0 ? this->sigma : auto_sigma(cells2, 0.5 * (double)nsrc + (double)nu_max, D);
+        // (t2: run_type1's factor -- "auto" is a type-3 matter -- and its frequency batches instead of groups)
+        const double cells2 = t2 ? 0.0 : cells_at_sigma2(X, D, f0, f1, adj_B);
+        const double sigma_a = this->sigma != 0.0 ? this->sigma : t2 ? 2.0 : auto_sigma(cells2, 0.5 * (double)nsrc + (double)nu_max, D);
         const double cells_top = 2.0 * cells2 * (sigma_a == 2.0 ? 1.0 : std::pow(1.25 / 2.0, D));
         const char *el = std::getenv("FFTVIS_HIP_LANES");
         const int nlanes = std::max(1, std::min(2, std::min(el ? std::atoi(el) : 2, std::max(nt, 1))));
@@ -3602,6 +3791,23 @@ class Sim : public SimBase {
         const char *eab = std::getenv("FFTVIS_HIP_ADJ_ACC_BYTES");
         const double acc_max = eab ? std::atof(eab) : 256.0 * 1024 * 1024;
         const int nfb = (int)std::max<double>(1.0, std::min<double>(nf, std::floor(acc_max / (8.0 * comps * std::max<int64_t>(nsrc, 1)))));
+        // t2: the lanes' FFT plans (their kernel parameters size the entry records), run_type1's planes with the pruned
+        // ends swapped -- na = n_modes + 1 inputs in whole 8-cell units, every one of the n2 outputs kept -- and its batches
+        T1Plan tp{};
+        DimGeom g2;
+        if (t2) {
+            for (int li = 0; li < nlanes; ++li) {
+                Lane &L = lanes[li];
+                if (!L.adj2 || L.adj2->sigma != sigma_a || L.adj2->eps != eps) L.adj2.reset(new Nufft3<T>(2, eps, sigma_a, L.stream));
+                L.adj2->stream = L.stream;
+            }
+            tp = t1_plan(lanes[0].adj2->ker, sigma_a, std::min(nf, nfb), cap, false);
+            g2 = tp.g;
+            g2.na = (int)cdiv(t1_nmodes + 1, 1 << BINLOG) << BINLOG;
+            g2.no = g2.n2;
+            FV_REQUIRE(g2.na <= g2.n2, "type-2 adjoint: more modes than grid cells");
+            for (Pair &p : pairs) mode_cells(p, g2.na);
+        }
         struct FBlock {
             int b0, b1;
             std::vector<std::pair<int, int>> groups;
@@ -3610,20 +3816,34 @@ class Sim : public SimBase {
         int nfg_max = 1;
         for (int b0 = f0; b0 < f1; b0 += nfb) {
             FBlock fb{b0, std::min(f1, b0 + nfb), {}};
-            fb.groups = freq_groups(fb.b0, fb.b1, cells_top, tpol);
+            if (t2) {
+                for (int fa = fb.b0; fa < fb.b1; fa += tp.nfb) fb.groups.push_back({fa, std::min(fb.b1, fa + tp.nfb)});
+            } else {
+                fb.groups = freq_groups(fb.b0, fb.b1, cells_top, tpol);
+            }
             for (const auto &grp : fb.groups) nfg_max = std::max(nfg_max, grp.second - grp.first);
             fblocks.push_back(std::move(fb));
         }
         const size_t acc_bytes = sizeof(double) * (size_t)std::max<int64_t>(nsrc * std::min(nf, nfb) * comps, 1);
         for (int li = 0; li < nlanes; ++li) {
             Lane &L = lanes[li];
-            if (!L.adj || L.adj->dim != D || L.adj->sigma != sigma_a || L.adj->eps != eps)
-                L.adj.reset(new Nufft3<T>(D, eps, sigma_a, L.stream));
-            L.adj->stream = L.stream;
-            L.adj->err_oob = d_err.as<int>();
-            L.adj->disc_radius = 0.0;  // its sources are baselines
-            L.adj->transpose_flipped = false;
-            L.adj->arm_columns(nullptr, nullptr, tpol, 0);
+            if (t2) {
+                L.adj2->set_fft_geometry(g2, g2);
+                L.d_t2_dec.reserve(sizeof(T) * g2.na);
+                hipLaunchKernelGGL(k_deconv_table<T>, dim3(cdiv(g2.na, 256)), dim3(256), 0, L.stream, g2.na, g2.n2, L.adj2->ker,
+                                   L.d_t2_dec.template as<T>());
+                L.d_t2_meta.reserve(sizeof(int) * (2 * (size_t)(tp.nbins + 1) + 2));
+                L.d_t2_binstart.reserve(sizeof(int) * (tp.nbins + 1));
+                L.d_t2_rec.reserve((size_t)tp.rec * tp.ecap);
+            } else {
+                if (!L.adj || L.adj->dim != D || L.adj->sigma != sigma_a || L.adj->eps != eps)
+                    L.adj.reset(new Nufft3<T>(D, eps, sigma_a, L.stream));
+                L.adj->stream = L.stream;
+                L.adj->err_oob = d_err.as<int>();
+                L.adj->disc_radius = 0.0;  // its sources are baselines
+                L.adj->transpose_flipped = false;
+                L.adj->arm_columns(nullptr, nullptr, tpol, 0);
+            }
             L.d_adj_q.reserve(sizeof(cplx<T>) * (size_t)nu_max * nfg_max * tpol);
             L.d_adj_z.reserve(sizeof(cplx<T>) * (size_t)cap * nfg_max * tpol);
             L.d_adj_acc.reserve(acc_bytes);
@@ -3655,7 +3875,7 @@ class Sim : public SimBase {
             for (int t = t0; t < t1; ++t) {
                 Lane &L = lanes[(t - t0) % nlanes];
                 const hipStream_t ls = L.stream;
-                Nufft3<T> &P = *L.adj;
+                Nufft3<T> &P = t2 ? *L.adj2 : *L.adj;
                 for (int ch = 0; ch < nch; ++ch) {
                     const int64_t s0 = (int64_t)ch * csz, sn = std::min<int64_t>(csz, nsrc - s0);
                     if (nsrc == 0 || sn <= 0) continue;  // nothing above the horizon: nothing to add
@@ -3664,13 +3884,27 @@ class Sim : public SimBase {
                     for (const auto &grp : fb.groups) {
                         const int fa = grp.first, nfg = grp.second - grp.first;
                         const double smax = fmax_of(fa, grp.second);
+                        T1Args ta{};
+                        if (t2) {  // the batch's (source, channel) entries in bin order, one each, for every pair
+                            ta.n2 = g2.n2;
+                            ta.nb1 = tp.nb1;
+                            ta.w = P.ker.w;
+                            ta.nfg = nfg;
+                            ta.f_first = fa;
+                            ta.cap = cap;
+                            ta.ecap = tp.ecap;
+                            ta.rec = tp.rec;
+                            t1_sort<false>(ta, tp.nbins, Mp, xyz, L.d_t2_meta, L.d_t2_binstart, L.d_t2_rec, P, ls);
+                        }
                         for (const Pair &pr : pairs) {
                             if (pr.n == 0) continue;
                             const int64_t nu = pr.ustart ? pr.nu : pr.n, np = pr.adj_np;
-                            const T *pos = pr.adj_pos->template as<T>();
-                            // sources: the pair's distinct vectors; targets: the directions, scaled per channel
-                            P.set_geometry(adj_c(pr), adj_B(pr), xc, X, smax);
-                            P.set_sources(np, pos, pos + np, D > 2 ? pos + 2 * np : nullptr);
+                            if (!t2) {
+                                const T *pos = pr.adj_pos->template as<T>();
+                                // sources: the pair's distinct vectors; targets: the directions, scaled per channel
+                                P.set_geometry(adj_c(pr), adj_B(pr), xc, X, smax);
+                                P.set_sources(np, pos, pos + np, D > 2 ? pos + 2 * np : nullptr);
+                            }
                             AdjStrengthArgs sa{};
                             sa.nu = nu;
                             sa.nfg = nfg;
@@ -3693,14 +3927,36 @@ class Sim : public SimBase {
                                                    pr.trivial ? nullptr : pr.flip->template as<signed char>(),
                                                    pr.ustart ? pr.ustart->template as<int>() : nullptr, q, d_err.as<int>() + 4);
                             }
-                            P.load_strengths(q, nfg * tpol, tpol, d_freqs.as<double>() + fa);
-                            P.spread(nfg * tpol);
-                            P.fft(nfg * tpol);
                             cplx<T> *zb = L.d_adj_z.template as<cplx<T>>();
-                            // every slot of the compacted arrays is a target (the live count stays on the device): slots
-                            // past it are computed and never read
-                            P.interp(cap, xyz, xyz + cap, D > 2 ? xyz + 2 * cap : nullptr, nullptr, nullptr,
-                                     d_freqs.as<double>() + fa, nfg, tpol, zb, (int64_t)tpol * cap, 1, z_off, false);
+                            if (t2) {
+                                const int nplanes = nfg * tpol;
+                                cplx<T> *A = P.fft_input(nplanes);
+                                const int *cells = pr.t2_cells->template as<int>();
+                                hipLaunchKernelGGL(k_t2_fill<T>, dim3((unsigned)cdiv((int64_t)g2.na * g2.na * nplanes, 256)), dim3(256), 0,
+                                                   ls, g2.na, nplanes, nu, cells, cells + (size_t)g2.na * g2.na + 1, (const cplx<T> *)q,
+                                                   (const T *)L.d_t2_dec.template as<T>(), A);
+                                P.fft(nplanes);
+                                // entries past the live count do not exist: their slots of z are never read
+                                const int Tt = (1 << BINLOG) + ta.w - 1;
+                                const size_t lds = sizeof(cplx<T>) * (size_t)tpol * Tt * Tt;
+                                hipLaunchKernelGGL((polarized ? k_t2_gather<T, 4> : k_t2_gather<T, 1>), dim3((unsigned)(nfg * tp.nb1 * tp.nb1)),
+                                                   dim3(T2_THREADS), lds, ls, ta, g2.P, g2.cnt(), (const unsigned char *)L.d_t2_rec.template as<unsigned char>(),
+                                                   (const int *)L.d_t2_binstart.template as<int>(), P.fft_output(), zb);
+                                st[ST_SPREAD_LAUNCHES] += 1;
+                                st[ST_GATHERED] += (double)cap * nplanes;
+                                st[ST_N2X] = st[ST_N2Y] = g2.n2;
+                                st[ST_NA_XY] = g2.na * 65536.0 + g2.na;
+                                st[ST_W] = ta.w;
+                                st[ST_SIGMA] = sigma_a;
+                            } else {
+                                P.load_strengths(q, nfg * tpol, tpol, d_freqs.as<double>() + fa);
+                                P.spread(nfg * tpol);
+                                P.fft(nfg * tpol);
+                                // every slot of the compacted arrays is a target (the live count stays on the device): slots
+                                // past it are computed and never read
+                                P.interp(cap, xyz, xyz + cap, D > 2 ? xyz + 2 * cap : nullptr, nullptr, nullptr,
+                                         d_freqs.as<double>() + fa, nfg, tpol, zb, (int64_t)tpol * cap, 1, z_off, false);
+                            }
                             AdjAccArgs aa{};
                             aa.M = cap;
                             aa.nfg = nfg;
@@ -3744,12 +4000,14 @@ class Sim : public SimBase {
         // directions, the accumulators, the staged G and gflux -- is given back when it exceeds FFTVIS_HIP_ADJ_KEEP_BYTES
         // (default 256 MiB): a cached handle then holds for its next forward run what it held before, but for the adjoint
         // plans' tables and per-baseline arrays.  Smaller sets stay for the next call (freeing and reallocating them
-        // doubled a C2 adjoint step).  The basis adjoint's inner products S and staged gcoefs count and go likewise.
+        // doubled a C2 adjoint step).  The basis adjoint's inner products S and staged gcoefs count and go likewise, and so
+        // do the type-2 path's planes and entry records.
         FV_HIP(hipStreamSynchronize(stream));
         {
             size_t bulk = d_adj_g.cap + d_adj_gf.cap + d_adj_gc.cap;
             for (Lane &L : lanes)
-                bulk += L.d_adj_z.cap + L.d_adj_acc.cap + L.d_gs.cap + (L.adj ? L.adj->buf0.cap + L.adj->buf1.cap : 0);
+                bulk += L.d_adj_z.cap + L.d_adj_acc.cap + L.d_gs.cap + (L.adj ? L.adj->buf0.cap + L.adj->buf1.cap : 0) +
+                        L.d_t2_rec.cap + L.d_t2_meta.cap + L.d_t2_binstart.cap + (L.adj2 ? L.adj2->buf0.cap + L.adj2->buf1.cap : 0);
             const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
             if ((double)bulk > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
                 for (Lane &L : lanes) {
@@ -3757,6 +4015,13 @@ class Sim : public SimBase {
                         L.adj->buf0.release();
                         L.adj->buf1.release();
                     }
+                    if (L.adj2) {
+                        L.adj2->buf0.release();
+                        L.adj2->buf1.release();
+                    }
+                    L.d_t2_rec.release();
+                    L.d_t2_meta.release();
+                    L.d_t2_binstart.release();
                     L.d_adj_z.release();
                     L.d_adj_acc.release();
                     L.d_gs.release();

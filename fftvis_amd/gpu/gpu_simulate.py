@@ -84,6 +84,9 @@ def _return_handle(key, h):
     _IDLE_HANDLES[key] = h
 
 
+ADJOINT_PATHS = ("type3", "type2", "auto")
+
+
 def _buffer_addr(a):
     """(address, on_device flag) of an adjoint buffer: a numpy array is a host buffer, a torch tensor a device buffer,
     None a null pointer (an output that is not wanted)."""
@@ -247,6 +250,15 @@ class SimHandle:
         fp, f_dev = _buffer_addr(gflux)
         _lib.check(self._L.fv_sim_run_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, fp, f_dev, int(bool(accumulate))))
 
+    def set_adjoint_path(self, path: str = "type3"):
+        """The transform ``run_adjoint`` uses on a lattice handle (``fv_sim_set_adjoint_path``): ``"type3"`` the type-3
+        transform with the roles swapped, ``"type2"`` the transpose of the type-1 slice."""
+        _lib.check(self._L.fv_sim_set_adjoint_path(self._h, {"type3": 0, "type2": 1}[path]))
+
+    def last_adjoint_path(self) -> int:
+        """What this handle's last ``run_adjoint`` took (``fv_sim_last_adjoint_path``): 0 none yet, 2 or 3."""
+        return int(self._L.fv_sim_last_adjoint_path(self._h))
+
     def run_basis_adjoint(self, t0, t1, f0, f1, g, gflux, gcoefs, accumulate: bool):
         """Basis beams (``set_basis``): ``gflux += A^T g`` and ``gcoefs +=`` the coefficient gradient for times [t0,t1) x
         freqs [f0,f1) (``fv_sim_run_basis_adjoint``).  ``g`` and ``gflux`` as for ``run_adjoint``; ``gcoefs``: C-contiguous
@@ -378,6 +390,7 @@ class GPUSimulationEngine(SimulationEngine):
         out: np.ndarray = None,
         out_shared: bool = False,
         adjoint_of: tuple = None,
+        adjoint_path: str = "type3",
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -443,7 +456,13 @@ class GPUSimulationEngine(SimulationEngine):
           ``simulate_vis_basis_adjoint`` passes) a triple ``(g, gflux, gcoefs)``, either output None when not wanted:
           ``SimHandle.run_basis_adjoint`` adds both gradients (``fluxes`` are then the forward's) and the call returns
           ``(gflux, gcoefs)``.
+        * ``adjoint_path`` (extra; with ``adjoint_of``, no basis beams): ``"type3"`` (default) the type-3 transform with
+          the roles swapped; ``"type2"`` the transpose of the lattice path's type-1 slice -- ValueError when these
+          arguments do not take the lattice path (not griddable, not flat, ``force_use_type3``, basis beams);
+          ``"auto"`` type 2 exactly where the forward takes type 1, type 3 elsewhere.
         """
+        if adjoint_path not in ADJOINT_PATHS:
+            raise ValueError(f"adjoint_path must be one of {ADJOINT_PATHS}, got {adjoint_path!r}")
         beam_order = checked_spline_order(beam_spline_opts)
         if interpolation_function not in ("az_za_map_coordinates", "az_za_simple"):
             raise ValueError(f"unknown interpolation_function {interpolation_function!r}")
@@ -518,6 +537,10 @@ class GPUSimulationEngine(SimulationEngine):
             basis_matrix = (basis_matrix / utils.speed_of_light).astype(real_dtype)
         else:
             R, bls, is_coplanar = prepare_array(ants, baselines, flat_array_tol, real_dtype)
+        if adjoint_path == "type2" and not is_gridded:
+            raise ValueError(
+                "adjoint_path='type2' needs the lattice path: a flat, griddable array without force_use_type3 and "
+                "without basis beams (adjoint_path='auto' falls back to the type-3 transform)")
         antnums = list(ants.keys())
         use_basis = beam_coefs is not None
         if use_basis:
@@ -572,6 +595,8 @@ class GPUSimulationEngine(SimulationEngine):
             if adjoint_of is not None:
                 if use_basis != (len(adjoint_of) == 3):
                     raise ValueError("adjoint_of: (g, gflux, gcoefs) with beam_coefs, (g, gflux) without")
+                if not use_basis:  # (a cached handle keeps its last setting)
+                    h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
                 result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr,
                                       gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis)
                 ok = True

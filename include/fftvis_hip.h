@@ -245,7 +245,8 @@ int fv_sim_run_into(fv_sim *h, int t0, int t1, int f0, int f1, void *out, int64_
  * lane, fp64 accumulators of at most FFTVIS_HIP_ADJ_ACC_BYTES per lane -- channel blocks --, staged host buffers) is
  * given back when it exceeds FFTVIS_HIP_ADJ_KEEP_BYTES (default 256 MiB); the second transforms' tables and
  * per-baseline arrays stay with the handle.  Lattice
- * arrays use the type-3 transform here as well.  A handle with basis beams (fv_sim_set_basis) and NaN in G fail with
+ * arrays use the type-3 transform here as well unless fv_sim_set_adjoint_path selects the type-2 transform (its planes
+ * and entry records fall under the same give-back rule).  A handle with basis beams (fv_sim_set_basis) and NaN in G fail with
  * FV_ERR_ARG.  Sums run in fp64, per lane in a fixed order, so that a run is
  * bitwise reproducible for a given FFTVIS_HIP_LANES.                                                                   */
 int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
@@ -266,6 +267,18 @@ int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gv
  * outputs NULL, *_on_device flags other than 0 or 1 and NaN in G fail with FV_ERR_ARG.                                  */
 int fv_sim_run_basis_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate);
+/* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
+ * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
+ * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2
+ * transform -- the runs' strengths go to their integer modes (deconvolved, as :259-269 picks them), the forward's n2 x n2
+ * planes are transformed the other way round (n_modes + 1 inputs, every output) and gathered periodically at the
+ * (source, channel) entries the forward spreads from; frequency batches as in fv_sim_run (FFTVIS_HIP_GRID_BYTES).  Both
+ * compute the same map to the handle's tolerance.  The setting stays with the handle.  Any other value fails with
+ * FV_ERR_ARG; path 1 on a handle that is not a lattice handle fails the next fv_sim_run_adjoint with FV_ERR_ARG.          */
+int fv_sim_set_adjoint_path(fv_sim *h, int path);
+/* The transform the last successful fv_sim_run_adjoint of this handle took: 0 none yet, 2 the type-2 transform, 3 the
+ * type-3 transform.  A null handle returns FV_ERR_ARG (1), which is none of these.                                        */
+int fv_sim_last_adjoint_path(fv_sim *h);
 int fv_sim_sync(fv_sim *h);
 
 /* Introspection for bench/roofline: fills up to n doubles:
