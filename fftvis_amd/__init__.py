@@ -4,7 +4,8 @@ Mirrors the reference package's public surface for the gpu backend
 (src/fftvis/__init__.py:1-31): ``simulate_vis``, the engine / evaluator factories and the
 ``gpu`` sub-package; beyond it, the adjoint of ``simulate_vis`` with respect to the fluxes
 (``simulate_vis_adjoint``) and a torch autograd entry point (``torch_simulate_vis``), and for basis beams the gradients
-with respect to the fluxes and the coefficients (``simulate_vis_basis_adjoint``, ``torch_simulate_vis_basis``).
+with respect to the fluxes and the coefficients (``simulate_vis_basis_adjoint``, ``torch_simulate_vis_basis``), and the
+gradient with respect to the antenna positions (``simulate_vis_position_adjoint``, ``torch_simulate_vis_array``).
 """
 
 __version__ = "0.1.0"
@@ -14,8 +15,11 @@ from .core.beam_basis import compute_beam_basis, compute_beam_basis_per_freq  # 
 from .core.simulate import SimulationEngine, default_accuracy_dict  # noqa: F401
 from .wrapper import create_beam_evaluator, create_simulation_engine, simulate_vis  # noqa: F401
 from .adjoint import (  # noqa: F401
+    baseline_to_antenna_gradient,
     simulate_vis_adjoint,
     simulate_vis_basis_adjoint,
+    simulate_vis_position_adjoint,
     torch_simulate_vis,
+    torch_simulate_vis_array,
     torch_simulate_vis_basis,
 )

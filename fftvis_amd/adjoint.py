@@ -12,6 +12,10 @@ with the roles of the forward's type-3 transform swapped (``fv_sim_run_adjoint``
 Basis beams (``beam_coefs``) have entry points of their own, ``simulate_vis_basis_adjoint`` and ``torch_simulate_vis_basis``:
 the same adjoint with respect to the fluxes, and the gradient with respect to the coefficients, in which the map is
 sesquilinear (``fv_sim_run_basis_adjoint``).
+
+The antenna positions have theirs as well, ``simulate_vis_position_adjoint`` and ``torch_simulate_vis_array``: the
+gradient of the exact sum every forward path approximates, from forward transforms of the strengths times the sources'
+coordinates (``fv_sim_run_position_adjoint``).
 """
 
 from __future__ import annotations
@@ -422,3 +426,223 @@ def torch_simulate_vis_basis(fluxes, beam_coefs, **kwargs):
     if _FN_BASIS is None:
         _FN_BASIS = _basis_autograd_function()
     return _FN_BASIS.apply(fluxes, beam_coefs, kwargs)
+
+
+def baseline_to_antenna_gradient(gbls, ants: dict, baselines: list):
+    """Scatter a gradient with respect to the baseline vectors, ``gbls`` (nbls, 3), to the antennas: baseline (i, j) is
+    ``ants[j] - ants[i]``, so row j receives ``+gbls[k]`` and row i ``-gbls[k]``.  Returns (nant, 3) with rows in
+    ``ants``' iteration order, numpy for numpy input and a tensor on ``gbls``' device for a tensor.  An auto-correlation
+    contributes nothing, and the rows sum to zero: a common shift of the array changes no visibility."""
+    row = {a: i for i, a in enumerate(ants)}
+    i0 = np.array([row[b[0]] for b in baselines], dtype=np.int64)
+    i1 = np.array([row[b[1]] for b in baselines], dtype=np.int64)
+    if tuple(gbls.shape) != (len(baselines), 3):
+        raise ValueError(f"gbls must have shape ({len(baselines)}, 3), got {tuple(gbls.shape)}")
+    if _is_tensor(gbls):
+        import torch
+
+        out = torch.zeros((len(row), 3), dtype=gbls.dtype, device=gbls.device)
+        out.index_add_(0, torch.as_tensor(i1, device=gbls.device), gbls)
+        out.index_add_(0, torch.as_tensor(i0, device=gbls.device), -gbls)
+        return out
+    out = np.zeros((len(row), 3), dtype=np.float64)
+    np.add.at(out, i1, gbls)
+    np.subtract.at(out, i0, gbls)
+    return out
+
+
+def simulate_vis_position_adjoint(
+    vis,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    wrt="ants",
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    beam_coefs: np.ndarray = None,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """Gradient of ``simulate_vis(ants, fluxes, ...)`` with respect to the antenna positions, for a visibility-shaped
+    ``vis`` (G = dL/dV, dL = Re sum conj(G) dV), in ENU metres^-1.
+
+    Every path of the simulation approximates V_k = cj_k(sum_j c_j exp(2 pi i nu s_k b_k . topo_j / c)),
+    b_k = ants[j] - ants[i]; the strengths c do not depend on the positions, so dV_k / db_k,d = i (2 pi nu / c) D_d with D_d
+    the simulation of the fluxes times topo_d, and
+    ``gbls[k, d] = -sum_{f,t,r} (2 pi nu_f / c) Im(conj(G) D_d)``: the gradient of the smooth exact map.  Which path the
+    forward takes is a piecewise decision and does not enter; on a coplanar array, where the forward drops the heights,
+    the up component is still returned (someone fitting antenna heights starts from a flat model).
+
+    * ``wrt="baselines"``: (nbls, 3) float64, every listed baseline an independent vector;
+    * ``wrt="ants"``: (nant, 3) float64, rows in ``ants``' iteration order: ``baseline_to_antenna_gradient`` of the
+      baseline result, formed on the host;
+    * a tuple of both names returns a tuple in that order.
+
+    ``fluxes`` is the forward's, (nsrc, nfreqs) or (nsrc, nfreqs, 4).  ``vis`` is a numpy array or a torch tensor on the
+    run's device (handed over by pointer; the results are then tensors on that device).  Every other keyword means what it
+    means for ``simulate_vis``, ``reference_compat`` included; ``force_use_type3`` is accepted and always on: the pass runs
+    the type-3 transform (about three forward runs whatever the number of antennas), so an ideal lattice array works and
+    takes its redundant runs.  Not covered: ``beam_coefs`` (NotImplementedError), a type-1 (lattice) form of the pass."""
+    single = isinstance(wrt, str)
+    names = (wrt,) if single else tuple(wrt)
+    if not names or any(n not in ("ants", "baselines") for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"wrt must name 'ants', 'baselines' or both, got {wrt!r}")
+    if beam_coefs is not None:
+        raise NotImplementedError("simulate_vis_position_adjoint does not support basis beams (beam_coefs)")
+    if backend != "gpu":
+        raise ValueError(f"Unsupported backend: {backend}")
+    if eps is None:
+        eps = default_accuracy_dict[precision]
+    ants = {k: np.array(v) for k, v in ants.items()}
+    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
+    beam_idx = validate_beam_idx(beam_idx, None, len(beam_list), len(ants))
+    feed_index(use_feed)
+    if baselines is None:
+        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
+    nsrc = int(np.size(ra))
+    nfreqs = int(np.size(freqs))
+    ntimes = len(julian_dates(times))
+    nbls = len(baselines)
+    if _is_tensor(fluxes):
+        fluxes = fluxes.detach().cpu().numpy()
+    fluxes = np.asarray(fluxes)
+    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
+        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
+    if fluxes.ndim == 3 and not polarized:
+        raise ValueError("a full-Stokes sky needs polarized=True")
+    want = (nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls)
+    if tuple(vis.shape) != want:
+        raise ValueError(f"vis must have simulate_vis's output shape {want}, got {tuple(vis.shape)}")
+    rdt = np.float32 if precision == 1 else np.float64
+    cdt = np.complex64 if precision == 1 else np.complex128
+    on_device = _is_tensor(vis) and vis.device.type == "cuda"
+    if on_device:
+        import torch
+
+        if (vis.device.index or 0) != int(device):
+            raise ValueError(f"vis lives on {vis.device}, the run is on cuda:{int(device)}")
+        tc = torch.complex64 if precision == 1 else torch.complex128
+        g = vis.detach().to(tc).resolve_conj().resolve_neg()  # (a lazily conjugated view's memory is not G)
+        gbls = torch.zeros((nbls, 3), dtype=torch.float64, device=vis.device)
+        torch.cuda.synchronize(vis.device)  # the library's streams do not follow torch's: g and gbls are complete
+    else:
+        g = vis.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(vis) else vis
+        g = np.asarray(g).astype(cdt, copy=False)
+        gbls = np.zeros((nbls, 3), dtype=np.float64)
+
+    from .wrapper import create_simulation_engine, device_chunks
+
+    nax = nfeed = 2 if polarized else 1
+    engine = create_simulation_engine(backend=backend, device=device)
+    nchunks = device_chunks(device, max_memory, min_chunks, beam_list, nax, nfeed, len(ants), nsrc, precision,
+                            source_buffer, nfreqs)
+    gbls = engine.simulate(
+        ants=ants, freqs=np.asarray(freqs), fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=beam_idx,
+        ra=ra, dec=dec, times=times, telescope_loc=telescope_loc, baselines=baselines,
+        precision=precision, polarized=polarized, eps=eps, upsample_factor=upsample_factor,
+        beam_spline_opts=beam_spline_opts, flat_array_tol=flat_array_tol,
+        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
+        coord_method=coord_method, coord_method_params=coord_method_params,
+        force_use_type3=True, force_use_ray=force_use_ray, trace_mem=trace_mem,
+        nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
+        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
+        adjoint_of=(g, gbls), adjoint_wrt="positions",
+    )
+    res = {"baselines": gbls}
+    if "ants" in names:
+        res["ants"] = baseline_to_antenna_gradient(gbls, ants, baselines)
+    if _is_tensor(vis) and not on_device:  # a host tensor in, host tensors out
+        import torch
+
+        res = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in res.items()}
+    return res[names[0]] if single else tuple(res[n] for n in names)
+
+
+def _array_autograd_function():
+    import torch
+
+    class _SimulateVisArray(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fluxes, antpos, antnums, kwargs):
+            from .wrapper import simulate_vis
+
+            ctx.kwargs = kwargs
+            ctx.antnums = antnums
+            ctx.full_stokes = fluxes.ndim == 3
+            ctx.flux_dtype, ctx.pos_dtype, ctx.pos_device = fluxes.dtype, antpos.dtype, antpos.device
+            ctx.save_for_backward(fluxes, antpos)
+            ants = dict(zip(antnums, antpos.detach().cpu().numpy().astype(np.float64)))
+            vis = simulate_vis(ants=ants, fluxes=fluxes.detach().cpu().numpy(), **kwargs)
+            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            fluxes, antpos = ctx.saved_tensors
+            ants = dict(zip(ctx.antnums, antpos.detach().cpu().numpy().astype(np.float64)))
+            gf = gp = None
+            if ctx.needs_input_grad[0]:
+                gf = simulate_vis_adjoint(grad_output, ants=ants, full_stokes=ctx.full_stokes, **ctx.kwargs)
+                if not _is_tensor(gf):
+                    gf = torch.from_numpy(gf)
+                gf = gf.to(device=grad_output.device, dtype=ctx.flux_dtype)
+            if ctx.needs_input_grad[1]:
+                gp = simulate_vis_position_adjoint(grad_output, ants=ants, fluxes=fluxes, wrt="ants", **ctx.kwargs)
+                if not _is_tensor(gp):
+                    gp = torch.from_numpy(gp)
+                gp = gp.to(device=ctx.pos_device, dtype=ctx.pos_dtype)
+            return gf, gp, None, None
+
+    return _SimulateVisArray
+
+
+_FN_ARRAY = None
+
+
+def torch_simulate_vis_array(fluxes, antpos, *, antnums=None, **kwargs):
+    """``simulate_vis`` as a torch operation differentiable in the fluxes and in the antenna positions: ``fluxes`` real,
+    (nsrc, nfreqs) or (nsrc, nfreqs, 4); ``antpos`` real, (nant, 3), ENU metres.  ``antnums`` gives the dictionary keys
+    ``baselines`` refers to (default ``range(nant)``); every other argument is a keyword of ``simulate_vis`` -- but for
+    ``ants``, which the two tensors replace (TypeError).  Returns the visibilities as a complex tensor on ``fluxes``'
+    device.  The backward pass runs only what autograd asks for (``ctx.needs_input_grad``): ``simulate_vis_adjoint`` for
+    the fluxes, ``simulate_vis_position_adjoint`` for the positions."""
+    global _FN_ARRAY
+    if "ants" in kwargs:
+        raise TypeError("torch_simulate_vis_array takes the antenna positions as the tensor antpos (and antnums), not ants=")
+    if kwargs.get("beam_coefs") is not None:
+        raise NotImplementedError("torch_simulate_vis_array does not support basis beams (beam_coefs)")
+    if antpos.ndim != 2 or antpos.shape[1] != 3 or antpos.is_complex():
+        raise ValueError(f"antpos must be a real (nant, 3) tensor, got {tuple(antpos.shape)} {antpos.dtype}")
+    antnums = list(range(antpos.shape[0])) if antnums is None else list(antnums)
+    if len(antnums) != antpos.shape[0] or len(set(antnums)) != len(antnums):
+        raise ValueError("antnums must give one distinct key per row of antpos")
+    if _FN_ARRAY is None:
+        _FN_ARRAY = _array_autograd_function()
+    return _FN_ARRAY.apply(fluxes, antpos, tuple(antnums), kwargs)

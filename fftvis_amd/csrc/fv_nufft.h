@@ -3063,6 +3063,9 @@ class Nufft3 {
     const cplx<T> *tw_cur[3] = {nullptr, nullptr, nullptr};
     DevBuf buf0, buf1;  // ping-pong: A -> (x-pass) B -> (transpose) Bt -> (y-pass) Ct
     DevBuf strengths;   // [M][ntrans] sorted order
+    // the set spread() reads: elements past the buffer's start (the position adjoint keeps three sets in it,
+    // k_strengths_moments); 0 everywhere else
+    int64_t strengths_off = 0;
 
     // Direct third dimension (3-D): the spread grid is na_z planes along z -- for arrays that are anywhere near flat
     // nearly all of them kernel width, not source range -- and the targets are few (10^4 - 10^5) against the 10^7
@@ -3502,7 +3505,7 @@ int Nufft3<T>::launch_spread(int ntrans, int tbegin, hipEvent_t e0, hipEvent_t e
             sm.i0s = mate->i0s.template as<int>();
             sm.bin_start = mate->bin_start.template as<int>();
             sm.kw = mate->kw.p;
-            sm.cs = mate->strengths.p;
+            sm.cs = mate->strengths.template as<cplx<T>>() + mate->strengths_off;
             sm.grid = mate->buf0.p;
         }
         // lane mapping: channel groups once a block sees a few sources (M counts the catalog before
@@ -3521,7 +3524,7 @@ int Nufft3<T>::launch_spread(int ntrans, int tbegin, hipEvent_t e0, hipEvent_t e
         hipExtLaunchKernelGGL(kern, g, dim3(SPREAD_THREADS), 0, stream, es, ee, 0, M,
                               (const int *)i0s.as<int>(), (const T *)kw.as<T>(),
                               (const int *)bin_start.as<int>(),
-                              (const cplx<T> *)strengths.as<cplx<T>>(), ntrans, tbegin,
+                              (const cplx<T> *)strengths.as<cplx<T>>() + strengths_off, ntrans, tbegin,
                               dec_cur[0], dec_cur[1],
                               buf0.as<cplx<T>>(), x.na, y.na, geo.nbin[0], ker.w,
                               order_ptr, nchunk, sm);
@@ -3530,7 +3533,7 @@ int Nufft3<T>::launch_spread(int ntrans, int tbegin, hipEvent_t e0, hipEvent_t e
         hipExtLaunchKernelGGL((k_spread3d<T, TCH>), g, dim3(SPREAD_THREADS), 0, stream, es, ee, 0, M,
                               (const int *)i0s.as<int>(), (const T *)kw.as<T>(),
                               (const int *)bin_start.as<int>(),
-                              (const cplx<T> *)strengths.as<cplx<T>>(), ntrans, tbegin, nchunk,
+                              (const cplx<T> *)strengths.as<cplx<T>>() + strengths_off, ntrans, tbegin, nchunk,
                               dec_cur[0], dec_cur[1],
                               dec_cur[2], buf0.as<cplx<T>>(), x.na, y.na, z.na,
                               geo.nbin[0], geo.nbin[1], ker.w, row_ext_ptr);
@@ -4047,7 +4050,8 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
         kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true> : k_interp<T, 2, true, 16, false, true>)
                     : (r9 ? k_interp<T, 2, false, 9, false, true> : k_interp<T, 2, false, 16, false, true>);
     if (a.gs) {  // the gradient epilogue's instantiations (basis mode: never the direct third dimension's 2-D form with height terms)
-        FV_REQUIRE(basis && a.gs_nbls > 0 && a.gs_nf >= a.gs_f0 + nfg, "gradient epilogue: a basis term and its S block");
+        // (a term without basis beams -- nbasis = 0, kk = ll = 0: the position adjoint -- adds sum_r conj(G_r) V_r to slot 0)
+        FV_REQUIRE(basis && a.gs_nbls > 0 && a.gs_nf >= a.gs_f0 + nfg, "gradient epilogue: a term and its S block");
         kern = gdim == 2 ? (herm ? (r9 ? k_interp<T, 2, true, 9, false, false, true> : k_interp<T, 2, true, 16, false, false, true>)
                                  : (r9 ? k_interp<T, 2, false, 9, false, false, true> : k_interp<T, 2, false, 16, false, false, true>))
                          : (herm ? (r9 ? k_interp<T, 3, true, 9, false, false, true> : k_interp<T, 3, true, 16, false, false, true>)

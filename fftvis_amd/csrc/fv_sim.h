@@ -712,6 +712,100 @@ __global__ void k_strengths(StrengthArgs a, const int *__restrict__ Mp, const in
     }
 }
 
+// Position adjoint (fv_sim_run_position_adjoint): k_strengths' thread mapping and strength_eval -- beams, coherency and
+// pre-phase evaluated once per (source, channel) -- written as THREE strength sets, the values times the source's three
+// coordinates x_d = 2 pi (R topo)_d (xyz: (3, M) in compacted order, absolute, not relative to the box centre; the third
+// one also where the transforms are 2-D).  Set d starts d * set_stride elements after cs, each in k_strengths' layout.
+// The factors are real: the Hermitian / all-real packings stay what they are.  With height terms the Chebyshev factor
+// of term wt_k multiplies all three sets.
+template <typename T, int ORD>
+__global__ void k_strengths_moments(StrengthArgs a, const int *__restrict__ Mp, const int *__restrict__ perm,
+                                    const int *__restrict__ src_idx, const T *__restrict__ az,
+                                    const T *__restrict__ za, const void *__restrict__ flux,
+                                    const double *__restrict__ freqs, const int *__restrict__ i0s,
+                                    const T *__restrict__ fs, cplx<T> *__restrict__ cs, const T *__restrict__ xyz,
+                                    int64_t set_stride) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= min((int64_t)*Mp, a.M) * a.nfg) return;
+    const int64_t p = idx / a.nfg;
+    const int fgi = (int)(idx % a.nfg);
+    const int fidx = a.f_first + fgi;
+    double dot = 0.0;
+    for (int d = 0; d < a.dim; ++d) {
+        const double pos = (double)i0s[(int64_t)d * a.M + p] - (double)fs[(int64_t)d * a.M + p];
+        dot += a.btc[d] * (pos - 0.5 * a.na[d]) * a.h[d];
+    }
+    cplx<double> pre = {1.0, 0.0};
+    if (dot != 0.0) sincos(freqs[fidx] * dot, &pre.im, &pre.re);
+    const int tp = a.herm ? 2 : a.polarized ? 4 : 1;
+    const int jc = perm[p];
+    cplx<T> *dst = cs + (p * a.nfg + fgi) * tp;
+    strength_eval<T, ORD>(a, jc, fidx, pre, src_idx, az, za, flux, freqs, dst);  // set 0 holds the plain values for now
+    const double x0 = (double)xyz[jc], x1 = (double)xyz[a.M + jc], x2 = (double)xyz[2 * a.M + jc];
+    double sc = 1.0;
+    if (a.wt_k > 0) {  // uniform: T_k((z - zc) / zh), as in k_strengths
+        const double t = (x2 - a.wt_zc) * a.wt_inv;
+        double prev = 1.0;
+        sc = t;
+        for (int i = 1; i < a.wt_k; ++i) {
+            const double nx = 2.0 * t * sc - prev;
+            prev = sc;
+            sc = nx;
+        }
+    }
+    const double w0 = x0 * sc, w1 = x1 * sc, w2 = x2 * sc;
+    for (int r = 0; r < tp; ++r) {
+        const double re = (double)dst[r].re, im = (double)dst[r].im;
+        dst[r] = {(T)(re * w0), (T)(im * w0)};
+        dst[set_stride + r] = {(T)(re * w1), (T)(im * w1)};
+        dst[2 * set_stride + r] = {(T)(re * w2), (T)(im * w2)};
+    }
+}
+
+// Baseline gradient from the position pass's inner products S (k_interp<.., GRAD>): S is (3, nfa, nbls) complex fp64 per
+// stream, S[d][f][k] = sum over times and products of conj(G) D'_d with D'_d the forward of the strengths times x_d.
+// 16 lanes <-> baseline k: per component the lanes sum -nu_f Im S[d][f][k] over the block's channels (dealt over the
+// lanes) and over the S buffers in lane order, a fixed butterfly combines them, and lane d < 3 adds row d of R^T / c
+// applied to the three sums -- from the transforms' frame (R b / c, seconds) to metres in the frame of b -- into
+// gbls[k][d] (fp64).  One owner per slot, no atomics: the bits do not depend on timing.
+struct PosReduceArgs {
+    const cplx<double> *S[4];
+    int nl, nfa, f_base;
+    int64_t nbls;
+    double rt[9];  // R^T / c, row-major
+};
+constexpr int POS_GROUP = 16;
+__global__ void k_posgrad_reduce(PosReduceArgs a, const double *__restrict__ freqs, double *__restrict__ gbls) {
+    const int64_t k = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / POS_GROUP;
+    const int lg = threadIdx.x & (POS_GROUP - 1);
+    if (k >= a.nbls) return;  // (whole groups exit together)
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    const int64_t ds = (int64_t)a.nfa * a.nbls;  // slots between two components
+    for (int f = lg; f < a.nfa; f += POS_GROUP) {
+        const double nu = freqs[a.f_base + f];
+        const int64_t slot = (int64_t)f * a.nbls + k;
+        double i0 = 0.0, i1 = 0.0, i2 = 0.0;
+        for (int li = 0; li < a.nl; ++li) {  // (nl <= 4, uniform; the pointer is picked without indexing the argument block)
+            const cplx<double> *S = li == 0 ? a.S[0] : li == 1 ? a.S[1] : li == 2 ? a.S[2] : a.S[3];
+            i0 += S[slot].im;
+            i1 += S[slot + ds].im;
+            i2 += S[slot + 2 * ds].im;
+        }
+        s0 -= nu * i0;
+        s1 -= nu * i1;
+        s2 -= nu * i2;
+    }
+    for (int off = POS_GROUP / 2; off > 0; off >>= 1) {
+        s0 += __shfl_xor(s0, off, 64);
+        s1 += __shfl_xor(s1, off, 64);
+        s2 += __shfl_xor(s2, off, 64);
+    }
+    const double g0 = a.rt[0] * s0 + a.rt[1] * s1 + a.rt[2] * s2;
+    const double g1 = a.rt[3] * s0 + a.rt[4] * s1 + a.rt[5] * s2;
+    const double g2 = a.rt[6] * s0 + a.rt[7] * s1 + a.rt[8] * s2;
+    if (lg < 3) gbls[3 * k + lg] += lg == 0 ? g0 : lg == 1 ? g1 : g2;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Adjoint (fv_sim_run_adjoint; DESIGN.md "Adjoint").  Per (time, frequency group, beam pair) the forward writes
 //     out[k, r] = cj_k( sum_j c_jr exp(i nu s_k b_k . x_j) ),   s_k = -1 and cj_k = conj for a flipped baseline,
@@ -1592,6 +1686,8 @@ struct SimBase {
                              int gflux_on_device, int accumulate) = 0;
     virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                                    int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate) = 0;
+    virtual void run_position_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
+                                      int gbls_on_device, int accumulate) = 0;
     // Host destination of the next run (fv_sim_run_into): `out` is then a block INSIDE a larger array -- channel f of
     // the block starts f * out_f_stride elements after `out` (0: the block is contiguous) -- and with out_shared other
     // processes write the rest of that array (a sharded run's ranks filling one shared result): the pinning helper must
@@ -3026,6 +3122,9 @@ class Sim : public SimBase {
         int nlanes = 1, nlanes_used = 1;
         bool pipe = false, gang = false;
         Chunks ch{};
+        // position adjoint (run_position_adjoint): every strengths launch writes three sets (k_strengths_moments) and
+        // every (group, pair, term) runs three rounds of spread -> FFT -> gradient gather, one per set
+        bool moments = false;
         // the plan class of height term kt: the run's own plan, or a light class's
         int cls(int kt) const { return k0 > 0 && kt >= k0 ? (kt >= k1 ? 2 : 1) : 0; }
     };
@@ -3341,7 +3440,7 @@ class Sim : public SimBase {
             }
             for (int li = 0; li < r.nlanes_used; ++li) {
                 lanes[li].plan[c]->reserve_buffers(need, na_max, n2_max);
-                lanes[li].plan[c]->strengths_buffer_reserve(r.ch.cap, (int)need_str);
+                lanes[li].plan[c]->strengths_buffer_reserve(r.ch.cap, (int)need_str * (r.moments ? 3 : 1));
             }
         }
         for (auto &cpo : col_plan_of) cpo.assign(r.groups.size() * pairs.size(), nullptr);
@@ -3372,8 +3471,10 @@ class Sim : public SimBase {
 
     // The unit loop: per (one or two time steps, source chunk) the per-time preparation, then per (frequency group, beam
     // pair, height term) strengths -> spread -> FFT -> gather.
-    // gs != nullptr (the basis adjoint's coefficient pass): o is the READ-ONLY G block and every gather adds its inner
-    // products to the S buffer of its stream -- gs[0] when all big kernels share the main stream, else the lane's.
+    // gs != nullptr (the basis adjoint's coefficient pass, the position adjoint): o is the READ-ONLY G block and every
+    // gather adds its inner products to the S buffer of its stream -- gs[0] when all big kernels share the main stream,
+    // else the lane's.  r.moments (the position adjoint): three rounds per strengths launch, round d on strength set d
+    // and into component d of S, (3, r.nf, nbls).
     void queue_units(const RunPlan &r, const OutBlock &o, Drain &dr, cplx<double> *const *gs = nullptr) {
         const int t0 = r.t0, t1 = r.t1, f0 = r.f0, nt = r.nt, D = r.D, nch = r.ch.n;
         const int64_t csz = r.ch.csz, cap = r.ch.cap;
@@ -3519,8 +3620,11 @@ class Sim : public SimBase {
                             launch_strengths(L, r, pr, fa, nfg, M, Mps[m], ls, kt, nf_);
                     }
                     // ---- NUFFT ----------------------------------------------------------
+                    const int nrounds = r.moments ? 3 : 1;
+                    for (int rd = 0; rd < nrounds; ++rd) {
                     for (int m = 0; m < nm; ++m) {
                         Nufft3<T> *P = Ls[m]->plan[c].get();
+                        P->strengths_off = r.moments ? (int64_t)rd * P->M * ntrans : 0;
                         P->arm_columns(on ? cp->tab.template as<int>() : nullptr, on ? cp->xtab.template as<int>() : nullptr, tg,
                                        on ? cp->ncc : 0, d_err.as<int>() + 3,
                                        on && cp->omask.p ? cp->omask.template as<unsigned long long>() : nullptr, on ? cp->nblk : 0);
@@ -3532,7 +3636,8 @@ class Sim : public SimBase {
                         const size_t e3 = ev_slot(TM_SPREAD);
                         nufft->spread(ntrans, ev_pool[e3].a, ev_pool[e3].b, mate);
                         spread_timed += nm;  // a gang launch serves nm time steps: counted per time step
-                    } else if (ride_heavy_done && pipe && &grp == &groups.back() && &pr == last_pair && kt + 1 >= std::max(1, r.K)) {
+                    } else if (ride_heavy_done && pipe && &grp == &groups.back() && &pr == last_pair && kt + 1 >= std::max(1, r.K) &&
+                               rd + 1 == nrounds) {
                         // the unit's last spread is the last reader of the lanes' per-time arrays (the FFT
                         // passes and the gather work on the grids): its dispatch carries the "lane scratch
                         // is free" event, which saves the main stream a marker packet per unit
@@ -3549,7 +3654,7 @@ class Sim : public SimBase {
                     // small 2-D grids: the last FFT pass serves the targets from its LDS tiles (no C
                     // buffer, no gather kernel); the output block was zeroed at the start of the run
                     const bool fused =
-                        !nbasis && !pr.herm && !r.K &&
+                        !gs && !nbasis && !pr.herm && !r.K &&
                         nufft->prepare_fused_gather(pr.n, d_bls.as<T>(), d_bls.as<T>() + nbls,
                                                     pr.trivial ? nullptr : pr.idx->template as<int>(),
                                                     pr.trivial ? nullptr : pr.flip->template as<signed char>(),
@@ -3569,7 +3674,8 @@ class Sim : public SimBase {
                     BasisTerm bt{d_coefs.p, d_ant1.as<int>(), d_ant2.as<int>(), pr.bi, pr.bj, nbasis,
                                  (int)freqs.size(), fa, 0, 0, nullptr, 0, 0, 0};
                     if (gs) {
-                        bt.gs = gs[pipe ? 0 : tu % r.nlanes];
+                        if (!nbasis) bt.kk = bt.ll = 0;  // no basis term: the one inner product sum_r conj(G_r) V_r, slot 0
+                        bt.gs = gs[pipe ? 0 : tu % r.nlanes] + (int64_t)rd * r.nf * nbls;  // (basis terms: one round)
                         bt.gs_nf = r.nf;
                         bt.gs_f0 = fa - f0;
                         bt.gs_nbls = nbls;
@@ -3588,11 +3694,12 @@ class Sim : public SimBase {
                                       pr.trivial ? nullptr : pr.idx->template as<int>(),
                                       pr.trivial ? nullptr : pr.flip->template as<signed char>(),
                                       d_freqs.as<double>() + fa, nfg, tg, obase + (int64_t)m * per_tf,
-                                      o.run, 1, pol_off.data(), accumulate || kt > 0, nbasis ? &bt : nullptr, pr.herm,
+                                      o.run, 1, pol_off.data(), accumulate || kt > 0, nbasis || gs ? &bt : nullptr, pr.herm,
                                       pr.ustart ? pr.ustart->template as<int>() : nullptr, pr.upairs ? pr.nitems : pr.nu,
                                       pr.upairs ? pr.upairs->template as<int>() : nullptr, r.K ? &wterm : nullptr);
                             }
                     ev_end(e5, ls);
+                    for (int m = 0; m < nm; ++m) Ls[m]->plan[c]->strengths_off = 0;
                     st[ST_GATHERED] += (double)(pr.upairs ? pr.nitems : pr.ustart ? pr.nu : pr.n) * ntrans * nm * (pr.herm ? 2 : 1);  // footprints gathered: distinct targets; packed transforms are read at s and -s
                     if (c == 0) {  // (the run's own plan describes the run)
                         st[ST_N2X] = nufft->geo.d[0].n2;
@@ -3602,6 +3709,7 @@ class Sim : public SimBase {
                         st[ST_NA_3] = D > 2 ? nufft->geo.d[2].na : 1;
                         st[ST_W] = nufft->ker.w;
                     }
+                    }  // rounds
                     }  // height terms
                 }
             }
@@ -4142,6 +4250,121 @@ class Sim : public SimBase {
         if (timing_level) ev_collect();
     }
 
+    // ---- positions: gbls += the gradient with respect to the baseline vectors (DESIGN.md "Adjoint") -------------------
+    // Every forward path approximates out_k = cj_k( sum_j c_j exp(i nu s_k b'_k . x_j) ), b' = R b / c the array as set,
+    // x = 2 pi R topo; the strengths do not depend on the positions, so d out_k / d b'_k,d = i nu D'_d with D'_d what the
+    // forward writes when every source's strengths are multiplied by x_j,d (a flipped baseline conjugates -i nu X to
+    // +i nu conj(X): no sign case remains).  With G = dL/dV, dL = Re sum conj(G) dV:
+    //     g'[k, d] = - sum_{f, t, r} nu_f Im( conj(G) D'_d ),     gbls[k] = R^T g'[k] / c   (per metre, in the frame of b).
+    // The pass is coef_pass's: per channel block the forward's own stages; per (time, chunk, group, pair, height term) one
+    // k_strengths_moments launch and three rounds of spread -> FFT -> gradient gather (k_interp<.., GRAD> without basis
+    // beams) into the (3, channels of the block, nbls) complex fp64 S buffer of the stream; k_posgrad_reduce contracts.
+    void run_position_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
+                              int gbls_on_device, int accumulate) override {
+        FV_HIP(hipSetDevice(device));
+        FV_REQUIRE(!type1, "the position adjoint runs the type-3 transform: set the array with fv_sim_set_array, not "
+                           "fv_sim_set_array_type1 (a lattice form of the pass does not exist)");
+        FV_REQUIRE(nbasis == 0, "the position adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        check_run(t0, t1, f0, f1);
+        const int nt = t1 - t0, nf = f1 - f0;
+        const int64_t per_tf = (int64_t)tpol * nbls;
+        // an earlier run may have the lanes busy
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipStreamSynchronize(prep_stream));
+        for (int li = 1; li < 4; ++li)
+            if (lanes[li].stream && lanes[li].own_stream) FV_HIP(hipStreamSynchronize(lanes[li].stream));
+        const int64_t g_elems = (int64_t)nf * nt * per_tf;
+        const cplx<T> *dg = (const cplx<T> *)gvis;
+        if (!gvis_on_device) {
+            upload(d_adj_g, gvis, sizeof(cplx<T>) * (size_t)g_elems, 0);
+            dg = d_adj_g.as<cplx<T>>();
+        }
+        if (g_elems > 0) {  // NaN in G fails the call before anything runs
+            hipLaunchKernelGGL(k_count_nan<T>, dim3((unsigned)std::min<int64_t>(cdiv(g_elems, 256), 4096)), dim3(256), 0, stream, dg,
+                               g_elems, d_err.as<int>() + 4);
+            check_errors();
+        }
+        const size_t gb_bytes = sizeof(double) * 3 * (size_t)nbls;
+        double *dgb = gbls;
+        if (!gbls_on_device) {
+            d_adj_gf.reserve(std::max<size_t>(gb_bytes, 16));
+            dgb = d_adj_gf.as<double>();
+            if (accumulate) FV_HIP(hipMemcpyAsync(dgb, gbls, gb_bytes, hipMemcpyHostToDevice, stream));
+        }
+        if (!accumulate) FV_HIP(hipMemsetAsync(dgb, 0, gb_bytes, stream));
+        const char *eab = std::getenv("FFTVIS_HIP_ADJ_ACC_BYTES");
+        const double acc_max = eab ? std::atof(eab) : 256.0 * 1024 * 1024;
+        const double per_chan = 16.0 * 3 * (double)std::max<int64_t>(nbls, 1);
+        const int nfb = (int)std::max<double>(1.0, std::min<double>(nf, std::floor(acc_max / per_chan)));
+        for (int b0 = f0; b0 < f1 && nt > 0 && nbls > 0; b0 += nfb) {
+            const int b1 = std::min(f1, b0 + nfb), nfa = b1 - b0;
+            if (mhist_log.size() > 65536) mhist_log.clear();
+            RunPlan r{t0, t1, b0, b1, nt, nfa};
+            r.moments = true;
+            source_box(r.xc, r.X);
+            height_terms(r);
+            pair_setup(r);
+            grid_and_groups(r);
+            light_classes(r);
+            lane_schedule(r);
+            lane_plans(r);
+            r.ch = source_chunks(r.nlanes_used);
+            lane_buffers(r);
+            // one S buffer per stream that runs gathers: the main stream's when the lanes are pipelined, else one per lane
+            const int ns = r.pipe ? 1 : r.nlanes;
+            const size_t s_bytes = sizeof(cplx<double>) * 3 * (size_t)nfa * (size_t)nbls;
+            cplx<double> *gs[4] = {nullptr, nullptr, nullptr, nullptr};
+            for (int li = 0; li < ns; ++li) {
+                lanes[li].d_gs.reserve(s_bytes);
+                gs[li] = lanes[li].d_gs.template as<cplx<double>>();
+                FV_HIP(hipMemsetAsync(gs[li], 0, s_bytes, stream));  // (the lanes start after what the main stream holds now)
+            }
+            OutBlock o{};
+            o.out = nullptr;
+            o.on_device = true;
+            o.nt = nt;
+            o.nf = nfa;
+            o.dout = const_cast<cplx<T> *>(dg) + (int64_t)(b0 - f0) * nt * per_tf;  // read only: the gradient epilogue never writes it
+            o.per_tf = per_tf;
+            o.run = (int64_t)nt * per_tf;
+            o.fs = o.run;
+            o.bytes = sizeof(cplx<T>) * (size_t)nfa * o.run;
+            o.run_bytes = sizeof(cplx<T>) * (size_t)o.run;
+            o.shared = false;
+            o.drain = false;
+            Drain dr;
+            queue_units(r, o, dr, gs);
+            PosReduceArgs pa{};
+            for (int li = 0; li < ns; ++li) pa.S[li] = gs[li];
+            pa.nl = ns;
+            pa.nfa = nfa;
+            pa.f_base = b0;
+            pa.nbls = nbls;
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) pa.rt[3 * i + j] = rplane.m[3 * j + i] / SPEED_OF_LIGHT;
+            hipLaunchKernelGGL(k_posgrad_reduce, dim3((unsigned)cdiv(nbls * POS_GROUP, 256)), dim3(256), 0, stream, pa,
+                               d_freqs.as<double>(), dgb);
+        }
+        if (!gbls_on_device) FV_HIP(hipMemcpyAsync(gbls, dgb, gb_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+        if (timing_level) ev_collect();
+        // the three strength sets belong to this pass: beyond the keep limit the lanes' strength buffers go back too (the
+        // next run's lane_buffers sizes them again before it queues anything)
+        {
+            size_t str = 0;
+            for (Lane &L : lanes)
+                for (auto &P : L.plan)
+                    if (P) str += P->strengths.cap;
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            if ((double)str > (ek ? std::atof(ek) : 256.0 * 1024 * 1024))
+                for (Lane &L : lanes)
+                    for (auto &P : L.plan)
+                        if (P) P->strengths.release();
+        }
+        adjoint_release();
+        check_errors();
+    }
+
     // beam x coherency strengths of one (frequency group, beam pair) for the lane's current sources
     void launch_strengths(Lane &L, const RunPlan &r, const Pair &pr, int fa, int nfg, int64_t M, const int *Mp, hipStream_t on,
                           int wt_k = 0, Nufft3<T> *plan = nullptr) {
@@ -4170,7 +4393,20 @@ class Sim : public SimBase {
         sa.wt_k = r.K ? wt_k : 0;
         sa.wt_zc = r.zc;
         sa.wt_inv = r.zh > 0 ? 1.0 / r.zh : 0.0;
-        cplx<T> *cs = nufft->strengths_buffer(nfg * (pr.herm ? 2 : tpol));
+        const int ntrans = nfg * (pr.herm ? 2 : tpol);
+        if (r.moments) {  // the position adjoint's three sets, each M * ntrans elements
+            cplx<T> *cs3 = nufft->strengths_buffer(3 * ntrans);
+            hipLaunchKernelGGL((beam_order == 3 ? k_strengths_moments<T, 3> : beam_order == 1 ? k_strengths_moments<T, 1>
+                                                                                            : k_strengths_moments<T, 0>),
+                               dim3(cdiv((int64_t)M * nfg, 256)), dim3(256), 0, on, sa, Mp,
+                               nufft->perm.template as<int>(), L.d_srcidx.template as<int>(),
+                               L.d_az.template as<T>(), L.d_za.template as<T>(), d_flux.p, d_freqs.as<double>(),
+                               nufft->i0s.template as<int>(), nufft->fs.template as<T>(), cs3,
+                               (const T *)L.d_xyz.template as<T>(), (int64_t)nufft->M * ntrans);
+            ev_end(e2, on);
+            return;
+        }
+        cplx<T> *cs = nufft->strengths_buffer(ntrans);
         hipLaunchKernelGGL((beam_order == 3 ? k_strengths<T, 3> : beam_order == 1 ? k_strengths<T, 1> : k_strengths<T, 0>),
                            dim3(cdiv((int64_t)M * nfg, 256)), dim3(256), 0, on, sa, Mp,
                            nufft->perm.template as<int>(), L.d_srcidx.template as<int>(),

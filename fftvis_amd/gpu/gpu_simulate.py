@@ -269,6 +269,14 @@ class SimHandle:
         _lib.check(self._L.fv_sim_run_basis_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, fp, f_dev, cp, c_dev,
                                                     int(bool(accumulate))))
 
+    def run_position_adjoint(self, t0, t1, f0, f1, g, gbls, accumulate: bool):
+        """``gbls +=`` the gradient with respect to the baseline vectors for times [t0,t1) x freqs [f0,f1)
+        (``fv_sim_run_position_adjoint``).  ``g`` as for ``run_adjoint``; ``gbls``: C-contiguous (nbls, 3) float64 at
+        either precision, per metre, in the frame the antenna positions were given in."""
+        gp, g_dev = _buffer_addr(g)
+        bp, b_dev = _buffer_addr(gbls)
+        _lib.check(self._L.fv_sim_run_position_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, bp, b_dev, int(bool(accumulate))))
+
     def run_device(self, t0, t1, f0, f1, out_ptr):
         """Enqueue only; ``out_ptr`` is a device buffer of out_shape() complex elements."""
         _lib.check(self._L.fv_sim_run(self._h, t0, t1, f0, f1, _lib.ptr(out_ptr), 1))
@@ -391,6 +399,7 @@ class GPUSimulationEngine(SimulationEngine):
         out_shared: bool = False,
         adjoint_of: tuple = None,
         adjoint_path: str = "type3",
+        adjoint_wrt: str = "fluxes",
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -456,6 +465,11 @@ class GPUSimulationEngine(SimulationEngine):
           ``simulate_vis_basis_adjoint`` passes) a triple ``(g, gflux, gcoefs)``, either output None when not wanted:
           ``SimHandle.run_basis_adjoint`` adds both gradients (``fluxes`` are then the forward's) and the call returns
           ``(gflux, gcoefs)``.
+        * ``adjoint_wrt`` (extra; with ``adjoint_of``, no basis beams): ``"fluxes"`` (default) as above; ``"positions"`` (what
+          ``simulate_vis_position_adjoint`` passes): ``adjoint_of`` is ``(g, gbls)`` and the engine adds the gradient with
+          respect to the baseline vectors into ``gbls``, (nbls, 3) float64 (``SimHandle.run_position_adjoint``), and
+          returns it.  The pass runs the type-3 transform only: ValueError on the lattice path (pass
+          ``force_use_type3=True``) and with ``beam_coefs``.
         * ``adjoint_path`` (extra; with ``adjoint_of``, no basis beams): ``"type3"`` (default) the type-3 transform with
           the roles swapped; ``"type2"`` the transpose of the lattice path's type-1 slice -- ValueError when these
           arguments do not take the lattice path (not griddable, not flat, ``force_use_type3``, basis beams);
@@ -463,6 +477,11 @@ class GPUSimulationEngine(SimulationEngine):
         """
         if adjoint_path not in ADJOINT_PATHS:
             raise ValueError(f"adjoint_path must be one of {ADJOINT_PATHS}, got {adjoint_path!r}")
+        if adjoint_wrt not in ("fluxes", "positions"):
+            raise ValueError(f"adjoint_wrt must be 'fluxes' or 'positions', got {adjoint_wrt!r}")
+        positions = adjoint_of is not None and adjoint_wrt == "positions"
+        if positions and beam_coefs is not None:
+            raise ValueError("the position adjoint does not cover basis beams (beam_coefs)")
         beam_order = checked_spline_order(beam_spline_opts)
         if interpolation_function not in ("az_za_map_coordinates", "az_za_simple"):
             raise ValueError(f"unknown interpolation_function {interpolation_function!r}")
@@ -537,6 +556,8 @@ class GPUSimulationEngine(SimulationEngine):
             basis_matrix = (basis_matrix / utils.speed_of_light).astype(real_dtype)
         else:
             R, bls, is_coplanar = prepare_array(ants, baselines, flat_array_tol, real_dtype)
+        if positions and is_gridded:
+            raise ValueError("the position adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if adjoint_path == "type2" and not is_gridded:
             raise ValueError(
                 "adjoint_path='type2' needs the lattice path: a flat, griddable array without force_use_type3 and "
@@ -598,7 +619,7 @@ class GPUSimulationEngine(SimulationEngine):
                 if not use_basis:  # (a cached handle keeps its last setting)
                     h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
                 result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr,
-                                      gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis)
+                                      gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis, positions=positions)
                 ok = True
                 return result
             if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != complex_dtype):
@@ -707,9 +728,10 @@ def _topo_from_coord_mgr(coord_mgr, time_indices):
     return np.stack(out)
 
 
-def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False):
+def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False, positions=False):
     """The adjoint's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors), each block's
-    contribution added to ``gflux`` (``basis``: and to ``gcoefs``; returns the pair).  Every ``run_adjoint`` call ends
+    contribution added to ``gflux`` (``basis``: and to ``gcoefs``; returns the pair.  ``positions``: ``gflux`` is the
+    (nbls, 3) baseline gradient and ``run_position_adjoint`` adds to it).  Every ``run_adjoint`` call ends
     synchronised."""
     on_device = not isinstance(g, np.ndarray)
     step = max(nblk_t, 1)
@@ -731,6 +753,8 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, ba
             ta, te_ = tb, te
         if basis:
             h.run_basis_adjoint(ta, te_, f0, f1, blk, gflux, gcoefs, not first)
+        elif positions:
+            h.run_position_adjoint(ta, te_, f0, f1, blk, gflux, not first)
         else:
             h.run_adjoint(ta, te_, f0, f1, blk, gflux, not first)
         first = False

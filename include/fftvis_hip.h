@@ -267,6 +267,28 @@ int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gv
  * outputs NULL, *_on_device flags other than 0 or 1 and NaN in G fail with FV_ERR_ARG.                                  */
 int fv_sim_run_basis_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate);
+/* Gradient of fv_sim_run's visibilities with respect to the baseline vectors, for times [t0, t1) x freqs [f0, f1).  Every
+ * forward path evaluates, to the handle's tolerance, out_k = cj_k( sum_j c_j exp(i nu s_k b'_k . x_j) ) with b' = R b / c the
+ * rotated baselines in seconds (src/fftvis/cpu/cpu_simulate.py:650-658, uvw = bls * freq at :972-973), x = 2 pi R topo
+ * (:961-967) and s_k = -1, cj_k = conj for a flipped baseline (:298); the beams, the horizon cut and the strengths c do not
+ * depend on the positions.  So d out_k / d b'_k,d = i nu D'_d, D'_d what fv_sim_run writes when every source's strengths
+ * are multiplied by x_j,d -- for both fv_sim_set_reference_compat forms, flipped baselines and every packing --, and with
+ * G = dL/dV, dL = Re sum conj(G) dV:
+ *     gbls[k, d] += (R^T g'[k])_d / c,     g'[k, d] = - sum_{f, t, r} nu_f Im( conj(G[f, t, r, k]) D'_d[f, t, r, k] ).
+ * gvis: G, complex of the handle's precision in fv_sim_run's output layout for that block.  gbls: (nbls, 3) float64 at
+ * either precision, per metre, in the frame of the vectors b whose image R b / c fv_sim_set_array received (R, bls: its
+ * inputs; R^T / c takes the gradient back); every listed baseline is an independent vector.  On a coplanar handle the
+ * forward drops b'_z; the third component of g' is still formed (D'_z weights by the sources' height coordinate).
+ * accumulate = 0: gbls is zeroed first.  The *_on_device flags as in fv_sim_run (device buffers must be complete when the
+ * call is made); the call synchronises.  The pass is a forward run per channel block -- one strengths launch that writes
+ * the three weighted sets, then per component spread, FFT and a gather that forms the inner products with G in fp64,
+ * (3, channels, nbls) complex per lane, at most FFTVIS_HIP_ADJ_ACC_BYTES per lane -- followed by a per-baseline sum over
+ * channels and lanes in a fixed order.  No atomics: bitwise reproducible for a given FFTVIS_HIP_LANES.  Memory is given
+ * back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule of fv_sim_run_adjoint.  A lattice handle (fv_sim_set_array_type1: set the
+ * array with fv_sim_set_array instead), a handle with basis beams, a null pointer, a flag other than 0 or 1 and NaN in G
+ * fail with FV_ERR_ARG.                                                                                                  */
+int fv_sim_run_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
+                                int gbls_on_device, int accumulate);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2

@@ -60,6 +60,7 @@ int main() {
     EXPECT(fv_sim_run(nullptr, 0, 1, 0, 1, v, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_basis_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, v, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_position_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_sync(nullptr) == FV_ERR_ARG);
     EXPECT(fv_sim_stats(nullptr, v, 12) == FV_ERR_ARG);
     EXPECT(fv_sim_reset_stats(nullptr) == FV_ERR_ARG);
@@ -109,6 +110,16 @@ int main() {
     EXPECT(fv_sim_run_basis_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 2, v, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_basis_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 0, v, 0, v, 3, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_basis_adjoint(reinterpret_cast<fv_sim *>(0x1), 0, 1, 0, 1, v, 0, nullptr, -1, v, 0, 0) == FV_ERR_ARG);
+    // and so does the position adjoint: null buffers, on_device flags and accumulate other than 0 or 1
+    {
+        fv_sim *fake = reinterpret_cast<fv_sim *>(0x1);
+        double *gb = v;
+        EXPECT(fv_sim_run_position_adjoint(fake, 0, 1, 0, 1, nullptr, 0, gb, 0, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_position_adjoint(fake, 0, 1, 0, 1, v, 0, nullptr, 0, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_position_adjoint(fake, 0, 1, 0, 1, v, 2, gb, 0, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_position_adjoint(fake, 0, 1, 0, 1, v, 0, gb, -1, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_position_adjoint(fake, 0, 1, 0, 1, v, 0, gb, 0, 2) == FV_ERR_ARG);
+    }
     // a call that gets past the argument checks reports the missing device as a HIP error, not a crash
     if (ndev == 0) {
         EXPECT(fv_sim_create(&h, 0, 2, 1e-6, 2.0, 1) == FV_ERR_HIP && h == nullptr);
