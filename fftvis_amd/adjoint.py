@@ -646,3 +646,274 @@ def torch_simulate_vis_array(fluxes, antpos, *, antnums=None, **kwargs):
     if _FN_ARRAY is None:
         _FN_ARRAY = _array_autograd_function()
     return _FN_ARRAY.apply(fluxes, antpos, tuple(antnums), kwargs)
+
+
+# Angular step [rad] of the central differences that give d n(t) / d(ra, dec) under device astrometry (``radec_jacobian``):
+# the chain is smooth on the scale of a radian, so the truncation is about h^2 / 6 = 2e-11 and the rounding of the fp64
+# vectors about 1e-16 / h = 1e-11, both relative.
+ASTROM_JACOBIAN_STEP = 1e-5
+
+
+def radec_jacobian(ra, dec, times, telescope_loc, *, astrom=None, device: int = 0) -> np.ndarray:
+    """J[t, j] = d n_j(t) / d(ra_j, dec_j), (ntimes, nsrc, 3, 2) float64: the derivative of the topocentric (east, north,
+    up) unit vectors the simulation uses with respect to the catalog's angles.  Without ``astrom`` the chain is
+    ``coord_method="SiderealRotation"``'s, n = R_t eq(ra, dec), in closed form.  With ``astrom`` ((ntimes, 31) contexts,
+    device astrometry) it is taken by central differences of ``gpu.utils.astrom_topo`` (the device's own chain, in fp64)
+    at the fixed angular step ``ASTROM_JACOBIAN_STEP``, along unit-speed great circles: towards increasing declination,
+    and along the tangent of the parallel (times cos dec)."""
+    ra = np.asarray(ra, dtype=np.float64).ravel()
+    dec = np.asarray(dec, dtype=np.float64).ravel()
+    sr, cr, sd, cd = np.sin(ra), np.cos(ra), np.sin(dec), np.cos(dec)
+    d_ra = np.stack([-cd * sr, cd * cr, np.zeros_like(ra)])   # d eq / d ra   (3, nsrc)
+    d_dec = np.stack([-sd * cr, -sd * sr, cd])                # d eq / d dec
+    if astrom is None:
+        from .core.coords import SiderealRotation
+
+        R = SiderealRotation(times, telescope_loc).matrices()  # (ntimes, 3, 3)
+        return np.stack([np.einsum("tab,bj->tja", R, d_ra), np.einsum("tab,bj->tja", R, d_dec)], axis=-1)
+    from .core.coords import eq_unit_vectors
+    from .gpu.utils import astrom_topo
+
+    astrom = np.ascontiguousarray(astrom, dtype=np.float64)
+    if astrom.ndim != 2 or astrom.shape[1] != 31:
+        raise ValueError("astrom must have shape (ntimes, 31): one eraASTROM context per time")
+    eq = eq_unit_vectors(ra, dec)
+    h = ASTROM_JACOBIAN_STEP
+    e_ra = np.stack([-sr, cr, np.zeros_like(ra)])  # unit tangent of the parallel: d eq / d ra = cos(dec) e_ra
+    out = np.empty((astrom.shape[0], ra.size, 3, 2))
+    for t, ctx in enumerate(astrom):
+        for c, (e, scale) in enumerate(((e_ra, cd), (d_dec, 1.0))):
+            plus = astrom_topo(np.cos(h) * eq + np.sin(h) * e, ctx, device)
+            minus = astrom_topo(np.cos(h) * eq - np.sin(h) * e, ctx, device)
+            out[t, :, :, c] = ((plus - minus) / (2.0 * h) * scale).T
+    return out
+
+
+def topo_to_radec_gradient(gtopo, jacobian):
+    """Chain a gradient with respect to the topocentric unit vectors, ``gtopo`` (ntimes, nsrc, 3), to the catalog's angles:
+    ``sum_t J_t^T gtopo[t]`` with ``jacobian`` = J (ntimes, nsrc, 3, 2) from ``radec_jacobian``.  Returns (nsrc, 2), columns
+    (ra, dec), numpy for numpy input and a tensor on ``gtopo``'s device for a tensor."""
+    if len(gtopo.shape) != 3 or gtopo.shape[2] != 3 or tuple(jacobian.shape) != tuple(gtopo.shape) + (2,):
+        raise ValueError(f"gtopo must be (ntimes, nsrc, 3) and jacobian (ntimes, nsrc, 3, 2), got {tuple(gtopo.shape)} and "
+                         f"{tuple(jacobian.shape)}")
+    if _is_tensor(gtopo):
+        import torch
+
+        J = torch.as_tensor(np.asarray(jacobian) if not _is_tensor(jacobian) else jacobian, dtype=gtopo.dtype, device=gtopo.device)
+        return torch.einsum("tjd,tjdc->jc", gtopo, J)
+    return np.einsum("tjd,tjdc->jc", np.asarray(gtopo, dtype=np.float64), np.asarray(jacobian, dtype=np.float64))
+
+
+def simulate_vis_source_adjoint(
+    vis,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    wrt="radec",
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    beam_coefs: np.ndarray = None,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """Gradient of ``simulate_vis(ants, fluxes, ra, dec, ...)`` with respect to the source positions, for a
+    visibility-shaped ``vis`` (G = dL/dV, dL = Re sum conj(G) dV).
+
+    Every path of the simulation approximates V_k = cj_k(sum_j c_j(n_j) exp(2 pi i nu s_k b_k . n_j / c)), n_j(t) the
+    source's topocentric (east, north, up) unit vector and c the apparent strengths, which depend on n through the beams.
+    The gradient has a phase term (transforms of the adjoint's strengths times the baseline coordinates) and a beam term
+    (central differences of the beams at a fixed angular step, with the transform's values held fixed): the gradient of the
+    smooth exact map, whichever path the forward takes.  The horizon cut is a piecewise decision and is not differentiated:
+    a source below the horizon at time t contributes exactly 0 at that t.
+
+    * ``wrt="topo"``: (ntimes, nsrc, 3) float64, ENU, tangential (n . g = 0): dL = sum g[t, j] . delta_j(t) for small
+      displacements delta perpendicular to n.  Valid with every source of coordinates -- rotation matrices, ``coord_mgr=``,
+      ``astrom=`` / ``device_astrometry=True``;
+    * ``wrt="radec"``: (nsrc, 2) float64, columns (ra, dec), per radian: ``topo_to_radec_gradient`` of the above with
+      ``radec_jacobian`` -- closed form for ``coord_method="SiderealRotation"``, central differences of the device's own
+      chain under device astrometry.  With a caller's ``coord_mgr`` (or a matvis manager the engine would build) the chain
+      from (ra, dec) to the vectors is not this package's: ValueError, ask for ``wrt="topo"`` and chain it yourself;
+    * a tuple of both names returns a tuple in that order.
+
+    ``fluxes`` is the forward's, (nsrc, nfreqs) or (nsrc, nfreqs, 4).  ``vis`` is a numpy array or a torch tensor on the
+    run's device (handed over by pointer; the results are then tensors on that device).  Every other keyword means what it
+    means for ``simulate_vis``, ``reference_compat`` included; ``force_use_type3`` is accepted and always on: the pass runs
+    the type-3 transform -- 1 + D transforms where the flux adjoint runs one, D = 2 on a flat array and 3 otherwise -- so an
+    ideal lattice array works through it.  Not covered: ``beam_coefs`` (NotImplementedError)."""
+    single = isinstance(wrt, str)
+    names = (wrt,) if single else tuple(wrt)
+    if not names or any(n not in ("topo", "radec") for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"wrt must name 'topo', 'radec' or both, got {wrt!r}")
+    if beam_coefs is not None:
+        raise NotImplementedError("simulate_vis_source_adjoint does not support basis beams (beam_coefs)")
+    if backend != "gpu":
+        raise ValueError(f"Unsupported backend: {backend}")
+    if "radec" in names:
+        if coord_mgr is not None:
+            raise ValueError("wrt='radec' needs this package's own chain from (ra, dec) to the topocentric vectors; with "
+                             "coord_mgr= the chain is the manager's: ask for wrt='topo' and apply its Jacobian")
+        if astrom is None and not device_astrometry and coord_method != "SiderealRotation":
+            raise ValueError(f"wrt='radec' needs coord_method='SiderealRotation' or device astrometry (astrom= / "
+                             f"device_astrometry=True); coord_method={coord_method!r} builds a matvis manager whose chain "
+                             "is its own: ask for wrt='topo'")
+    if eps is None:
+        eps = default_accuracy_dict[precision]
+    ants = {k: np.array(v) for k, v in ants.items()}
+    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
+    beam_idx = validate_beam_idx(beam_idx, None, len(beam_list), len(ants))
+    feed_index(use_feed)
+    if baselines is None:
+        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
+    nsrc = int(np.size(ra))
+    nfreqs = int(np.size(freqs))
+    ntimes = len(julian_dates(times))
+    nbls = len(baselines)
+    if _is_tensor(fluxes):
+        fluxes = fluxes.detach().cpu().numpy()
+    fluxes = np.asarray(fluxes)
+    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
+        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
+    if fluxes.ndim == 3 and not polarized:
+        raise ValueError("a full-Stokes sky needs polarized=True")
+    want = (nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls)
+    if tuple(vis.shape) != want:
+        raise ValueError(f"vis must have simulate_vis's output shape {want}, got {tuple(vis.shape)}")
+    rdt = np.float32 if precision == 1 else np.float64
+    cdt = np.complex64 if precision == 1 else np.complex128
+    if astrom is None and device_astrometry and coord_mgr is None and coord_method != "SiderealRotation":
+        from .core.coords import erfa_astrom_context
+
+        astrom = erfa_astrom_context(times, telescope_loc)  # (the engine and the Jacobian see the same contexts)
+    on_device = _is_tensor(vis) and vis.device.type == "cuda"
+    if on_device:
+        import torch
+
+        if (vis.device.index or 0) != int(device):
+            raise ValueError(f"vis lives on {vis.device}, the run is on cuda:{int(device)}")
+        tc = torch.complex64 if precision == 1 else torch.complex128
+        g = vis.detach().to(tc).resolve_conj().resolve_neg()  # (a lazily conjugated view's memory is not G)
+        gtopo = torch.zeros((ntimes, nsrc, 3), dtype=torch.float64, device=vis.device)
+        torch.cuda.synchronize(vis.device)  # the library's streams do not follow torch's: g and gtopo are complete
+    else:
+        g = vis.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(vis) else vis
+        g = np.asarray(g).astype(cdt, copy=False)
+        gtopo = np.zeros((ntimes, nsrc, 3), dtype=np.float64)
+
+    from .wrapper import create_simulation_engine, device_chunks
+
+    nax = nfeed = 2 if polarized else 1
+    engine = create_simulation_engine(backend=backend, device=device)
+    nchunks = device_chunks(device, max_memory, min_chunks, beam_list, nax, nfeed, len(ants), nsrc, precision,
+                            source_buffer, nfreqs)
+    gtopo = engine.simulate(
+        ants=ants, freqs=np.asarray(freqs), fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=beam_idx,
+        ra=ra, dec=dec, times=times, telescope_loc=telescope_loc, baselines=baselines,
+        precision=precision, polarized=polarized, eps=eps, upsample_factor=upsample_factor,
+        beam_spline_opts=beam_spline_opts, flat_array_tol=flat_array_tol,
+        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
+        coord_method=coord_method, coord_method_params=coord_method_params,
+        force_use_type3=True, force_use_ray=force_use_ray, trace_mem=trace_mem,
+        nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
+        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
+        adjoint_of=(g, gtopo), adjoint_wrt="sources",
+    )
+    res = {"topo": gtopo}
+    if "radec" in names:
+        # the engine rounds ra / dec to the run's precision first: the Jacobian is taken where the run was
+        jac = radec_jacobian(np.asarray(ra).astype(rdt), np.asarray(dec).astype(rdt), times, telescope_loc, astrom=astrom,
+                             device=device)
+        res["radec"] = topo_to_radec_gradient(gtopo, jac)
+    if _is_tensor(vis) and not on_device:  # a host tensor in, host tensors out
+        import torch
+
+        res = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in res.items()}
+    return res[names[0]] if single else tuple(res[n] for n in names)
+
+
+def _sky_autograd_function():
+    import torch
+
+    class _SimulateVisSky(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fluxes, radec, kwargs):
+            from .wrapper import simulate_vis
+
+            ctx.kwargs = kwargs
+            ctx.full_stokes = fluxes.ndim == 3
+            ctx.flux_dtype, ctx.pos_dtype, ctx.pos_device = fluxes.dtype, radec.dtype, radec.device
+            ctx.save_for_backward(fluxes, radec)
+            rd = radec.detach().cpu().numpy().astype(np.float64)
+            vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(), ra=rd[:, 0].copy(), dec=rd[:, 1].copy(), **kwargs)
+            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            fluxes, radec = ctx.saved_tensors
+            rd = radec.detach().cpu().numpy().astype(np.float64)
+            pos = dict(ra=rd[:, 0].copy(), dec=rd[:, 1].copy())
+            gf = gp = None
+            if ctx.needs_input_grad[0]:
+                gf = simulate_vis_adjoint(grad_output, full_stokes=ctx.full_stokes, **pos, **ctx.kwargs)
+                if not _is_tensor(gf):
+                    gf = torch.from_numpy(gf)
+                gf = gf.to(device=grad_output.device, dtype=ctx.flux_dtype)
+            if ctx.needs_input_grad[1]:
+                gp = simulate_vis_source_adjoint(grad_output, fluxes=fluxes, wrt="radec", **pos, **ctx.kwargs)
+                if not _is_tensor(gp):
+                    gp = torch.from_numpy(gp)
+                gp = gp.to(device=ctx.pos_device, dtype=ctx.pos_dtype)
+            return gf, gp, None
+
+    return _SimulateVisSky
+
+
+_FN_SKY = None
+
+
+def torch_simulate_vis_sky(fluxes, radec, **kwargs):
+    """``simulate_vis`` as a torch operation differentiable in the fluxes and in the source positions: ``fluxes`` real,
+    (nsrc, nfreqs) or (nsrc, nfreqs, 4); ``radec`` real, (nsrc, 2), columns (ra, dec) in radians.  Every other argument is a
+    keyword of ``simulate_vis`` -- but for ``ra`` and ``dec``, which the tensor replaces (TypeError).  Returns the
+    visibilities as a complex tensor on ``fluxes``' device.  The backward pass runs only what autograd asks for
+    (``ctx.needs_input_grad``): ``simulate_vis_adjoint`` for the fluxes, ``simulate_vis_source_adjoint(wrt="radec")`` for the
+    positions, which needs ``coord_method="SiderealRotation"`` or device astrometry."""
+    global _FN_SKY
+    if "ra" in kwargs or "dec" in kwargs:
+        raise TypeError("torch_simulate_vis_sky takes the source positions as the tensor radec, not ra= / dec=")
+    if kwargs.get("beam_coefs") is not None:
+        raise NotImplementedError("torch_simulate_vis_sky does not support basis beams (beam_coefs)")
+    if "adjoint_path" in kwargs:
+        raise TypeError("torch_simulate_vis_sky does not take adjoint_path: its passes run the type-3 transform")
+    if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
+        raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
+    if _FN_SKY is None:
+        _FN_SKY = _sky_autograd_function()
+    return _FN_SKY.apply(fluxes, radec, kwargs)

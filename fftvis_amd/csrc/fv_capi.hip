@@ -629,6 +629,17 @@ int fv_sim_run_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const
         h->impl->run_position_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gbls, gbls_on_device, accumulate);
     });
 }
+int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
+                              int gtopo_on_device, int accumulate) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(gvis && gtopo, "null adjoint input or output");
+        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gtopo_on_device == 0 || gtopo_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gtopo, gtopo_on_device, accumulate);
+    });
+}
 int fv_sim_sync(fv_sim *h) { FV_SIM_CALL(h->impl->sync()); }
 int fv_sim_stats(fv_sim *h, double *vals, int n) { FV_SIM_CALL(h->impl->stats(vals, n)); }
 int fv_sim_reset_stats(fv_sim *h) { FV_SIM_CALL(h->impl->reset_stats()); }

@@ -1097,6 +1097,225 @@ __global__ void k_adj_reduce(AdjReduceArgs a, T *__restrict__ out) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Source adjoint (fv_sim_run_source_adjoint; DESIGN.md "Sources"): the gradient with respect to the sources' topocentric
+// unit vectors n_j(t).  With the flux adjoint's Z (above), Re <V, G> = sum_t sum_j sum_f Re sum_r c_jr(n_j) Z_jr(x_j),
+// x = 2 pi R n, and
+//     dZ_jr / dx_d = i nu Z(d)_jr,   Z(d) the same transform of the strengths q_ur times the d-th coordinate of the run's
+//                                    sign-adjusted vector (k_src_moments),
+// so the gradient is a phase term, -nu Im sum_r c_jr Z(d)_jr in the transforms' frame, plus a beam term,
+// Re sum_r (dc_jr / dn) Z_jr with Z held fixed.
+// ---------------------------------------------------------------------------------------------
+// q is (rows, nu) row-major (k_adj_strengths' layout); set 1 + d, set_stride elements further on, gets q times pos[d][u].
+template <typename T>
+__global__ void k_src_moments(int64_t nu, int64_t rows, int D, const T *__restrict__ pos, cplx<T> *__restrict__ q,
+                              int64_t set_stride) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nu * rows) return;
+    const int64_t u = i % nu;
+    const cplx<T> v = q[i];
+    for (int d = 0; d < D; ++d) {
+        const T b = pos[(int64_t)d * nu + u];
+        q[(int64_t)(d + 1) * set_stride + i] = {v.re * b, v.im * b};
+    }
+}
+
+// Angular step of the beam term's central differences [rad], per precision of the run (profiles/MEASUREMENTS.md "Source
+// adjoint": the steps a decade either side measured against the exact reference).  The beams are evaluated in fp64 at
+// either precision; only Z differs.
+constexpr double SRC_BEAM_STEP_FP64 = 1e-6;
+constexpr double SRC_BEAM_STEP_FP32 = 1e-6;
+
+struct SrcAccArgs {
+    int64_t M;           // capacity of the per-time arrays (stride of z); live count is *Mp
+    int nfg, f_first;    // channels of the group, catalog index of its first
+    int f_base, nfa;     // first channel of the block and channels the accumulator holds
+    int nfreq;           // catalog frequency count (flux row length)
+    int polarized, pol_sky, same_beam;
+    int D;               // moment sets (2 on coplanar handles, 3 otherwise)
+    int64_t set_stride;  // elements of z between two sets
+    int64_t vstride;     // stride of vec (the catalog's source count)
+    BeamDesc bi, bj;
+    Rot9 rt;             // vec -> ENU at this time (identity for given topocentric vectors)
+    Rot9 rp;             // the plane rotation R: ENU -> the transforms' frame
+    double h;            // step of the beam term
+};
+
+// The forward's strengths of one source at the ENU unit vector (e, n, u), in fp64: strength_eval's beam and coherency
+// calls (az, za as k_horizon_compact forms them) without its packings, pre-phase and rounding.  Returns
+// s = Re sum_r c_r Z_r; c (tp values) is written when asked for.
+template <typename T, int ORD>
+__device__ inline double src_strength_dot(const SrcAccArgs &a, int fidx, double freq, int64_t js, double e, double n,
+                                          const void *__restrict__ flux, const cplx<double> *Z, cplx<double> *c) {
+    const double zeta = sqrt(fmax(0.0, 1.0 - (n * n + e * e)));
+    double azv = fmod(0.5 * M_PI - atan2(e, n), 2.0 * M_PI);
+    if (azv < 0) azv += 2.0 * M_PI;
+    const double zav = 0.5 * M_PI - asin(zeta);
+    if (!a.polarized) {
+        const double bi = eval_power<ORD>(a.bi, fidx, freq, azv, zav);
+        const double bj = a.same_beam ? bi : eval_power<ORD>(a.bj, fidx, freq, azv, zav);
+        const double I = (double)((const T *)flux)[js * a.nfreq + fidx];
+        const cplx<double> v = cscale(csqrt_principal(cplx<double>{bi * bj, 0.0}), I);
+        if (c) c[0] = v;
+        return v.re * Z[0].re - v.im * Z[0].im;
+    }
+    cplx<double> Ai[4], Aj[4], o[4];
+    eval_jones<ORD>(a.bi, fidx, freq, azv, zav, Ai);
+    if (a.same_beam) {
+        for (int i = 0; i < 4; ++i) Aj[i] = Ai[i];
+    } else {
+        eval_jones<ORD>(a.bj, fidx, freq, azv, zav, Aj);
+    }
+    if (!a.pol_sky) {
+        coh_AhB_flux(Ai, Aj, (double)((const T *)flux)[js * a.nfreq + fidx], o);
+    } else {
+        const cplx<T> *Cp = (const cplx<T> *)flux + (js * a.nfreq + fidx) * 4;
+        cplx<double> C[4];
+        for (int i = 0; i < 4; ++i) C[i] = {(double)Cp[i].re, (double)Cp[i].im};
+        const cplx<double> Fi[4] = {Ai[2], Ai[3], Ai[0], Ai[1]};
+        const cplx<double> Fj[4] = {Aj[2], Aj[3], Aj[0], Aj[1]};
+        coh_AhCB(Fi, C, Fj, o);
+    }
+    double s = 0.0;
+    for (int r = 0; r < 4; ++r) {
+        if (c) c[r] = o[r];
+        s += o[r].re * Z[r].re - o[r].im * Z[r].im;
+    }
+    return s;
+}
+
+// thread <-> (compacted source jc, channel fg), jc fastest, like k_adj_accumulate.  z holds 1 + D sets: Z, then Z(d).
+// acc (fp64, this lane's) is (nsrc, nfa, 3): per (source, channel) the gradient in the transforms' frame, WITHOUT the
+// factor 2 pi nu_f that k_srcgrad_reduce carries:
+//     acc[d] += -Im sum_r c_r Z(d)_r  +  (R g_beam)_d / (2 pi nu),
+// g_beam = D_1 e_1 + D_2 e_2 the tangential ENU gradient of s(n) = Re sum_r c_r(n) Z_r by central differences along the
+// great circles through n towards an orthonormal tangent pair (e_1, e_2), n' = cos(h) n +- sin(h) e_i (R is a rotation:
+// R^T, which the reduction applies, takes R g back to g).  The direction comes from the catalog vector in fp64, not
+// from the lane's rounded az / za.  src_idx is injective within a slice: plain read-modify-write.
+template <typename T, int ORD>
+__global__ void k_src_accumulate(SrcAccArgs a, const int *__restrict__ Mp, const int *__restrict__ src_idx,
+                                 const T *__restrict__ vec, const void *__restrict__ flux,
+                                 const double *__restrict__ freqs, const cplx<T> *__restrict__ z,
+                                 double *__restrict__ acc) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.M * a.nfg) return;
+    const int64_t jc = i % a.M;
+    const int fg = (int)(i / a.M);
+    if (jc >= (int64_t)*Mp) return;
+    const int fidx = a.f_first + fg;
+    const double freq = freqs[fidx];
+    const int64_t js = src_idx[jc];
+    const int tp = a.polarized ? 4 : 1;
+    double nv[3];
+    {
+        const double ex = vec[js], ey = vec[a.vstride + js], ez = vec[2 * a.vstride + js];
+        nv[0] = a.rt.m[0] * ex + a.rt.m[1] * ey + a.rt.m[2] * ez;
+        nv[1] = a.rt.m[3] * ex + a.rt.m[4] * ey + a.rt.m[5] * ez;
+        nv[2] = a.rt.m[6] * ex + a.rt.m[7] * ey + a.rt.m[8] * ez;
+        const double rn = 1.0 / sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+        for (int d = 0; d < 3; ++d) nv[d] *= rn;
+    }
+    cplx<double> Z[4], c[4];
+    for (int r = 0; r < tp; ++r) {
+        const cplx<T> v = z[((int64_t)fg * tp + r) * a.M + jc];
+        Z[r] = {(double)v.re, (double)v.im};
+    }
+    src_strength_dot<T, ORD>(a, fidx, freq, js, nv[0], nv[1], flux, Z, c);
+    // phase term
+    double g[3] = {0.0, 0.0, 0.0};
+    for (int d = 0; d < a.D; ++d) {
+        const cplx<T> *zd = z + (int64_t)(d + 1) * a.set_stride;
+        double s = 0.0;
+        for (int r = 0; r < tp; ++r) {
+            const cplx<T> v = zd[((int64_t)fg * tp + r) * a.M + jc];
+            s += c[r].re * (double)v.im + c[r].im * (double)v.re;
+        }
+        if (d == 0) g[0] = -s;
+        if (d == 1) g[1] = -s;
+        if (d == 2) g[2] = -s;
+    }
+    // beam term: e_1 = n x (the axis n leans on least), normalised; e_2 = n x e_1
+    double e1[3], e2[3];
+    {
+        const double a0 = fabs(nv[0]), a1 = fabs(nv[1]), a2 = fabs(nv[2]);
+        if (a0 <= a1 && a0 <= a2) {
+            e1[0] = 0.0, e1[1] = nv[2], e1[2] = -nv[1];
+        } else if (a1 <= a2) {
+            e1[0] = -nv[2], e1[1] = 0.0, e1[2] = nv[0];
+        } else {
+            e1[0] = nv[1], e1[1] = -nv[0], e1[2] = 0.0;
+        }
+        const double rn = 1.0 / sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+        for (int d = 0; d < 3; ++d) e1[d] *= rn;
+        e2[0] = nv[1] * e1[2] - nv[2] * e1[1];
+        e2[1] = nv[2] * e1[0] - nv[0] * e1[2];
+        e2[2] = nv[0] * e1[1] - nv[1] * e1[0];
+    }
+    double sh, ch;
+    sincos(a.h, &sh, &ch);
+    const double inv2h = 0.5 / a.h;
+    double d1 = 0.0, d2 = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < 4; ++k) {  // +e_1, -e_1, +e_2, -e_2: one copy of the beam code
+        const double sg = k & 1 ? -sh : sh;
+        const double te = k < 2 ? e1[0] : e2[0], tn = k < 2 ? e1[1] : e2[1];
+        const double s = src_strength_dot<T, ORD>(a, fidx, freq, js, ch * nv[0] + sg * te, ch * nv[1] + sg * tn, flux, Z, nullptr);
+        const double w = k & 1 ? -inv2h : inv2h;
+        if (k < 2) d1 += w * s;
+        else d2 += w * s;
+    }
+    const double sc = 1.0 / (2.0 * M_PI * freq);
+    const double b0 = d1 * e1[0] + d2 * e2[0], b1 = d1 * e1[1] + d2 * e2[1], b2 = d1 * e1[2] + d2 * e2[2];
+    g[0] += sc * (a.rp.m[0] * b0 + a.rp.m[1] * b1 + a.rp.m[2] * b2);
+    g[1] += sc * (a.rp.m[3] * b0 + a.rp.m[4] * b1 + a.rp.m[5] * b2);
+    g[2] += sc * (a.rp.m[6] * b0 + a.rp.m[7] * b1 + a.rp.m[8] * b2);
+    double *o = acc + (js * a.nfa + (fidx - a.f_base)) * 3;
+    o[0] += g[0];
+    o[1] += g[1];
+    o[2] += g[2];
+}
+
+// One time step's accumulator -> its rows of gtopo (nsrc, 3) fp64, ENU: thread <-> catalog source j.  The channels of the
+// block are summed in order with their factor nu_f, 2 pi R^T takes the sum from the transforms' frame to ENU, the radial
+// component goes (the direction is a unit vector: only the tangential part means anything), and the row is added to.
+// A time step belongs to one lane, so no sum runs over lanes: one owner per slot, no atomics, and the bits depend on
+// neither timing nor FFTVIS_HIP_LANES.  A source below the horizon has an untouched accumulator and adds exactly 0.
+struct SrcReduceArgs {
+    int64_t nsrc;
+    int nfa, f_base;
+    Rot9 rt, rp;
+};
+template <typename T>
+__global__ void k_srcgrad_reduce(SrcReduceArgs a, const double *__restrict__ acc, const T *__restrict__ vec,
+                                 const double *__restrict__ freqs, double *__restrict__ gtopo) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= a.nsrc) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    const double *p = acc + j * a.nfa * 3;
+    for (int f = 0; f < a.nfa; ++f) {
+        const double nu = freqs[a.f_base + f];
+        s0 += nu * p[3 * f];
+        s1 += nu * p[3 * f + 1];
+        s2 += nu * p[3 * f + 2];
+    }
+    const double twopi = 2.0 * M_PI;
+    double g0 = twopi * (a.rp.m[0] * s0 + a.rp.m[3] * s1 + a.rp.m[6] * s2);
+    double g1 = twopi * (a.rp.m[1] * s0 + a.rp.m[4] * s1 + a.rp.m[7] * s2);
+    double g2 = twopi * (a.rp.m[2] * s0 + a.rp.m[5] * s1 + a.rp.m[8] * s2);
+    const double ex = vec[j], ey = vec[a.nsrc + j], ez = vec[2 * a.nsrc + j];
+    double n0 = a.rt.m[0] * ex + a.rt.m[1] * ey + a.rt.m[2] * ez;
+    double n1 = a.rt.m[3] * ex + a.rt.m[4] * ey + a.rt.m[5] * ez;
+    double n2 = a.rt.m[6] * ex + a.rt.m[7] * ey + a.rt.m[8] * ez;
+    if (!(n2 > 0.0)) return;  // below the horizon: the row stays what it is
+    const double rn = 1.0 / sqrt(n0 * n0 + n1 * n1 + n2 * n2);
+    n0 *= rn, n1 *= rn, n2 *= rn;
+    const double rad = g0 * n0 + g1 * n1 + g2 * n2;
+    double *o = gtopo + 3 * j;
+    o[0] += g0 - rad * n0;
+    o[1] += g1 - rad * n1;
+    o[2] += g2 - rad * n2;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Type-1 path (lattice arrays): cpu_nufft2d_type1 (cpu/nufft.py:120-175), set-up
 // cpu_simulate.py:661-681, per-slice :964-965,990-992,259-269.
 // Visibility of the integer baseline (bx, by) at frequency nu is mode (bx, by) of a type-1
@@ -1688,6 +1907,8 @@ struct SimBase {
                                    int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate) = 0;
     virtual void run_position_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
                                       int gbls_on_device, int accumulate) = 0;
+    virtual void run_source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
+                                    int gtopo_on_device, int accumulate) = 0;
     // Host destination of the next run (fv_sim_run_into): `out` is then a block INSIDE a larger array -- channel f of
     // the block starts f * out_f_stride elements after `out` (0: the block is contiguous) -- and with out_shared other
     // processes write the rest of that array (a sharded run's ranks filling one shared result): the pinning helper must
@@ -4360,6 +4581,231 @@ class Sim : public SimBase {
                 for (Lane &L : lanes)
                     for (auto &P : L.plan)
                         if (P) P->strengths.release();
+        }
+        adjoint_release();
+        check_errors();
+    }
+
+    // ---- sources: gtopo[t - t0] += the tangential gradient with respect to the sources' ENU unit vectors at time t ------
+    // (DESIGN.md "Sources"; the kernels' comment above k_src_moments).  adjoint_flux's set-up and loop -- channel blocks,
+    // lanes, source chunks, horizon_step, k_adj_strengths and the type-3 transform with the roles swapped -- with 1 + D
+    // rounds of load -> spread -> FFT -> interp per (time, chunk, group, pair): the strengths q, then q times each
+    // coordinate of the run's vector (k_src_moments; D = 2 on coplanar handles, where Z does not depend on the third
+    // coordinate).  k_src_accumulate contracts with the forward's strengths and adds the beam term; the accumulator is
+    // per time step, and k_srcgrad_reduce writes the step's rows on the lane's own stream.
+    void run_source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
+                            int gtopo_on_device, int accumulate) override {
+        FV_HIP(hipSetDevice(device));
+        FV_REQUIRE(!type1, "the source adjoint runs the type-3 transform: set the array with fv_sim_set_array, not "
+                           "fv_sim_set_array_type1");
+        FV_REQUIRE(nbasis == 0, "the source adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        check_run(t0, t1, f0, f1);
+        const int nt = t1 - t0, nf = f1 - f0;
+        const int64_t per_tf = (int64_t)tpol * nbls;
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipStreamSynchronize(prep_stream));
+        if (copy_stream) FV_HIP(hipStreamSynchronize(copy_stream));
+        for (int li = 1; li < 4; ++li)
+            if (lanes[li].stream && lanes[li].own_stream) FV_HIP(hipStreamSynchronize(lanes[li].stream));
+        for (Lane &L : lanes) {
+            L.heavy_pending = false;
+            for (int &b : L.binned_ti) b = -1;
+        }
+        lane_mode = -1;
+        const double tol = dedup_tol();
+        for (Pair &p : pairs) build_unique(p, tol, 3);
+        const int D = dim(), nsets = 1 + D;
+        double xc[3] = {0.0, 0.0, 0.0}, X[3] = {0.0, 0.0, 0.0};
+        source_box(xc, X);
+        for (Pair &p : pairs) {  // the NUFFT sources of every pair (adjoint_flux's, without a mirrored set)
+            const int64_t nu = p.ustart ? p.nu : p.n;
+            if (p.n == 0 || (p.adj_pos && p.adj_serial == targets_serial && p.adj_np == nu)) continue;
+            std::vector<T> pos((size_t)D * nu);
+            for (int64_t u = 0; u < nu; ++u) {
+                const int64_t m = p.ustart ? p.h_ustart[u] : u;
+                const double sg = p.h_flip[m] ? -1.0 : 1.0;
+                for (int d = 0; d < D; ++d) pos[(size_t)d * nu + u] = (T)(sg * h_bls[(size_t)d * nbls + p.h_idx[m]]);
+            }
+            p.adj_pos.reset(new DevBuf());
+            upload(*p.adj_pos, pos.data(), sizeof(T) * pos.size(), 0);
+            p.adj_serial = targets_serial;
+            p.adj_np = nu;
+        }
+        const int64_t g_elems = (int64_t)nf * nt * per_tf;
+        const cplx<T> *dg = (const cplx<T> *)gvis;
+        if (!gvis_on_device) {
+            upload(d_adj_g, gvis, sizeof(cplx<T>) * (size_t)g_elems, 0);
+            dg = d_adj_g.as<cplx<T>>();
+        }
+        if (g_elems > 0) {  // NaN in G fails the call before anything runs
+            hipLaunchKernelGGL(k_count_nan<T>, dim3((unsigned)std::min<int64_t>(cdiv(g_elems, 256), 4096)), dim3(256), 0, stream, dg,
+                               g_elems, d_err.as<int>() + 4);
+            check_errors();
+        }
+        int64_t nu_max = 1;
+        for (const Pair &p : pairs) nu_max = std::max<int64_t>(nu_max, p.n ? p.adj_np : 0);
+        auto adj_B = [&](const Pair &p) { return (const double *)p.B; };
+        const double cells2 = cells_at_sigma2(X, D, f0, f1, adj_B);
+        const double sigma_a = this->sigma != 0.0 ? this->sigma : auto_sigma(cells2, 0.5 * (double)nsrc + (double)nu_max, D);
+        const double cells_top = 2.0 * cells2 * (sigma_a == 2.0 ? 1.0 : std::pow(1.25 / 2.0, D));
+        const char *el = std::getenv("FFTVIS_HIP_LANES");
+        const int nlanes = std::max(1, std::min(2, std::min(el ? std::atoi(el) : 2, std::max(nt, 1))));
+        const Chunks sc = source_chunks(nlanes);
+        const int nch = sc.n;
+        const int64_t csz = sc.csz, cap = sc.cap;
+        // channel blocks: a lane's accumulator holds nsrc x (channels of a block) x 3 doubles, at most
+        // FFTVIS_HIP_ADJ_ACC_BYTES; every block walks the time steps once
+        const char *eab = std::getenv("FFTVIS_HIP_ADJ_ACC_BYTES");
+        const double acc_max = eab ? std::atof(eab) : 256.0 * 1024 * 1024;
+        const int nfb = (int)std::max<double>(1.0, std::min<double>(nf, std::floor(acc_max / (24.0 * std::max<int64_t>(nsrc, 1)))));
+        struct FBlock {
+            int b0, b1;
+            std::vector<std::pair<int, int>> groups;
+        };
+        std::vector<FBlock> fblocks;
+        int nfg_max = 1;
+        for (int b0 = f0; b0 < f1; b0 += nfb) {
+            FBlock fb{b0, std::min(f1, b0 + nfb), {}};
+            fb.groups = freq_groups(fb.b0, fb.b1, cells_top, tpol);
+            for (const auto &grp : fb.groups) nfg_max = std::max(nfg_max, grp.second - grp.first);
+            fblocks.push_back(std::move(fb));
+        }
+        const size_t acc_bytes = sizeof(double) * 3 * (size_t)std::max<int64_t>(nsrc * std::min(nf, nfb), 1);
+        for (int li = 0; li < nlanes; ++li) {
+            Lane &L = lanes[li];
+            if (!L.adj || L.adj->dim != D || L.adj->sigma != sigma_a || L.adj->eps != eps)
+                L.adj.reset(new Nufft3<T>(D, eps, sigma_a, L.stream));
+            L.adj->stream = L.stream;
+            L.adj->err_oob = d_err.as<int>();
+            L.adj->disc_radius = 0.0;  // its sources are baselines
+            L.adj->transpose_flipped = false;
+            L.adj->arm_columns(nullptr, nullptr, tpol, 0);
+            // 1 + D sets of strengths and of values at the directions: the extra capacity belongs to this pass
+            L.d_adj_q.reserve(sizeof(cplx<T>) * (size_t)nu_max * nfg_max * tpol * nsets);
+            L.d_adj_z.reserve(sizeof(cplx<T>) * (size_t)cap * nfg_max * tpol * nsets);
+            L.d_adj_acc.reserve(acc_bytes);
+        }
+        const size_t gt_bytes = sizeof(double) * 3 * (size_t)nsrc * (size_t)nt;
+        double *dgt = gtopo;
+        if (!gtopo_on_device) {
+            d_adj_gf.reserve(std::max<size_t>(gt_bytes, 16));
+            dgt = d_adj_gf.as<double>();
+            if (accumulate && gt_bytes) FV_HIP(hipMemcpyAsync(dgt, gtopo, gt_bytes, hipMemcpyHostToDevice, stream));
+        }
+        if (!accumulate && gt_bytes) FV_HIP(hipMemsetAsync(dgt, 0, gt_bytes, stream));
+        // the lanes write gtopo's rows themselves: they start after the main stream has prepared it
+        FV_HIP(hipEventRecord(ev_start, stream));
+        for (int li = 0; li < nlanes; ++li)
+            if (lanes[li].stream != stream) FV_HIP(hipStreamWaitEvent(lanes[li].stream, ev_start, 0));
+        const std::array<int64_t, 16> pol_off = pol_offsets();  // the forward's output slots
+        int64_t z_off[16] = {0};
+        for (int r = 0; r < tpol; ++r) z_off[r] = (int64_t)r * cap;
+        const int ord = beam_order == 3 ? 3 : beam_order == 1 ? 1 : 0;
+        for (const FBlock &fb : fblocks) {
+            const int nfa = fb.b1 - fb.b0;
+            for (int t = t0; t < t1 && nsrc > 0; ++t) {
+                Lane &L = lanes[(t - t0) % nlanes];
+                const hipStream_t ls = L.stream;
+                Nufft3<T> &P = *L.adj;
+                double *acc = L.d_adj_acc.template as<double>();
+                FV_HIP(hipMemsetAsync(acc, 0, sizeof(double) * 3 * (size_t)nsrc * nfa, ls));
+                const T *vec = nullptr;
+                for (int ch = 0; ch < nch; ++ch) {
+                    const int64_t s0 = (int64_t)ch * csz, sn = std::min<int64_t>(csz, nsrc - s0);
+                    if (sn <= 0) continue;
+                    const int *Mp = horizon_step(L, t, cap, sc.nblk, ls, s0, sn, (int64_t)t * nch + ch);
+                    // the vectors horizon_step read (every chunk of a time step writes its own range of the lane's d_enu)
+                    vec = !astroms.empty() ? L.d_enu.template as<T>()
+                                           : ntimes_topo ? d_topo.as<T>() + (size_t)t * 3 * nsrc : d_eq.as<T>();
+                    const T *xyz = L.d_xyz.template as<T>();
+                    for (const auto &grp : fb.groups) {
+                        const int fa = grp.first, nfg = grp.second - grp.first;
+                        const double smax = fmax_of(fa, grp.second);
+                        const int ntr = nfg * tpol;
+                        for (const Pair &pr : pairs) {
+                            if (pr.n == 0) continue;
+                            const int64_t nu = pr.adj_np;
+                            const T *pos = pr.adj_pos->template as<T>();
+                            P.set_geometry(pr.btc, pr.B, xc, X, smax);
+                            P.set_sources(nu, pos, pos + nu, D > 2 ? pos + 2 * nu : nullptr);
+                            AdjStrengthArgs sa{};
+                            sa.nu = nu;
+                            sa.nfg = nfg;
+                            sa.tpol = tpol;
+                            sa.g_f_stride = (int64_t)nt * per_tf;
+                            for (int r = 0; r < 4; ++r) sa.pol_off[r] = pol_off[r];
+                            sa.transpose_flipped = !reference_compat;
+                            cplx<T> *q = L.d_adj_q.template as<cplx<T>>();
+                            hipLaunchKernelGGL(k_adj_strengths<T>, dim3((unsigned)cdiv(nu * nfg * ADJ_GROUP, 256)), dim3(256), 0, ls, sa,
+                                               dg + ((int64_t)(fa - f0) * nt + (t - t0)) * per_tf,
+                                               pr.trivial ? nullptr : pr.idx->template as<int>(),
+                                               pr.trivial ? nullptr : pr.flip->template as<signed char>(),
+                                               pr.ustart ? pr.ustart->template as<int>() : nullptr, q, d_err.as<int>() + 4);
+                            const int64_t q_set = nu * ntr, z_set = cap * ntr;
+                            hipLaunchKernelGGL(k_src_moments<T>, dim3((unsigned)cdiv(q_set, 256)), dim3(256), 0, ls, nu, (int64_t)ntr, D,
+                                               pos, q, q_set);
+                            cplx<T> *zb = L.d_adj_z.template as<cplx<T>>();
+                            for (int s = 0; s < nsets; ++s) {
+                                P.load_strengths(q + s * q_set, ntr, tpol, d_freqs.as<double>() + fa);
+                                P.spread(ntr);
+                                P.fft(ntr);
+                                // every slot of the compacted arrays is a target: slots past the live count are never read
+                                P.interp(cap, xyz, xyz + cap, D > 2 ? xyz + 2 * cap : nullptr, nullptr, nullptr,
+                                         d_freqs.as<double>() + fa, nfg, tpol, zb + s * z_set, (int64_t)tpol * cap, 1, z_off, false);
+                            }
+                            SrcAccArgs aa{};
+                            aa.M = cap;
+                            aa.nfg = nfg;
+                            aa.f_first = fa;
+                            aa.f_base = fb.b0;
+                            aa.nfa = nfa;
+                            aa.nfreq = nfreq_cat;
+                            aa.polarized = polarized;
+                            aa.pol_sky = pol_sky;
+                            aa.same_beam = pr.bi == pr.bj;
+                            aa.D = D;
+                            aa.set_stride = z_set;
+                            aa.vstride = nsrc;
+                            aa.bi = desc(pr.bi);
+                            aa.bj = desc(pr.bj);
+                            aa.rt = rots[t];
+                            aa.rp = rplane;
+                            aa.h = sizeof(T) == 8 ? SRC_BEAM_STEP_FP64 : SRC_BEAM_STEP_FP32;
+                            if (const char *eh = std::getenv("FFTVIS_HIP_SRC_BEAM_STEP")) aa.h = std::atof(eh);  // (measurements)
+                            FV_REQUIRE(aa.h > 0.0 && aa.h < 1e-2, "FFTVIS_HIP_SRC_BEAM_STEP out of range");
+                            hipLaunchKernelGGL((ord == 3 ? k_src_accumulate<T, 3> : ord == 1 ? k_src_accumulate<T, 1> : k_src_accumulate<T, 0>),
+                                               dim3((unsigned)cdiv(cap * nfg, 256)), dim3(256), 0, ls, aa, Mp,
+                                               L.d_srcidx.template as<int>(), vec, d_flux.p, d_freqs.as<double>(),
+                                               (const cplx<T> *)zb, acc);
+                        }
+                    }
+                }
+                if (vec) {
+                    SrcReduceArgs ra{};
+                    ra.nsrc = nsrc;
+                    ra.nfa = nfa;
+                    ra.f_base = fb.b0;
+                    ra.rt = rots[t];
+                    ra.rp = rplane;
+                    hipLaunchKernelGGL(k_srcgrad_reduce<T>, dim3((unsigned)cdiv(nsrc, 256)), dim3(256), 0, ls, ra, (const double *)acc, vec,
+                                       d_freqs.as<double>(), dgt + (size_t)(t - t0) * 3 * nsrc);
+                }
+            }
+        }
+        for (int li = 0; li < nlanes; ++li)  // join: the copy on the main stream sees every lane
+            if (lanes[li].stream != stream) {
+                FV_HIP(hipEventRecord(lanes[li].done, lanes[li].stream));
+                FV_HIP(hipStreamWaitEvent(stream, lanes[li].done, 0));
+            }
+        if (!gtopo_on_device && gt_bytes) FV_HIP(hipMemcpyAsync(gtopo, dgt, gt_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+        if (timing_level) ev_collect();
+        {  // the 1 + D strength sets belong to this pass: beyond the keep limit they go back with the rest
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            size_t qb = 0;
+            for (Lane &L : lanes) qb += L.d_adj_q.cap + L.d_adj_z.cap;
+            if ((double)qb > (ek ? std::atof(ek) : 256.0 * 1024 * 1024))
+                for (Lane &L : lanes) L.d_adj_q.release();
         }
         adjoint_release();
         check_errors();

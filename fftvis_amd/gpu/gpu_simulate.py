@@ -277,6 +277,14 @@ class SimHandle:
         bp, b_dev = _buffer_addr(gbls)
         _lib.check(self._L.fv_sim_run_position_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, bp, b_dev, int(bool(accumulate))))
 
+    def run_source_adjoint(self, t0, t1, f0, f1, g, gtopo, accumulate: bool):
+        """``gtopo +=`` the tangential gradient with respect to the sources' ENU unit vectors for times [t0,t1) x freqs
+        [f0,f1) (``fv_sim_run_source_adjoint``).  ``g`` as for ``run_adjoint``; ``gtopo``: C-contiguous (t1 - t0, nsrc, 3)
+        float64 at either precision.  The handle's fluxes are the forward's."""
+        gp, g_dev = _buffer_addr(g)
+        tp, t_dev = _buffer_addr(gtopo)
+        _lib.check(self._L.fv_sim_run_source_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, tp, t_dev, int(bool(accumulate))))
+
     def run_device(self, t0, t1, f0, f1, out_ptr):
         """Enqueue only; ``out_ptr`` is a device buffer of out_shape() complex elements."""
         _lib.check(self._L.fv_sim_run(self._h, t0, t1, f0, f1, _lib.ptr(out_ptr), 1))
@@ -469,7 +477,10 @@ class GPUSimulationEngine(SimulationEngine):
           ``simulate_vis_position_adjoint`` passes): ``adjoint_of`` is ``(g, gbls)`` and the engine adds the gradient with
           respect to the baseline vectors into ``gbls``, (nbls, 3) float64 (``SimHandle.run_position_adjoint``), and
           returns it.  The pass runs the type-3 transform only: ValueError on the lattice path (pass
-          ``force_use_type3=True``) and with ``beam_coefs``.
+          ``force_use_type3=True``) and with ``beam_coefs``.  ``"sources"`` (what ``simulate_vis_source_adjoint`` passes):
+          ``adjoint_of`` is ``(g, gtopo)`` and the engine fills ``gtopo``, (ntimes, nsrc, 3) float64, with the tangential
+          gradient with respect to the sources' ENU unit vectors, row t from time step t
+          (``SimHandle.run_source_adjoint``), and returns it; the same restrictions.
         * ``adjoint_path`` (extra; with ``adjoint_of``, no basis beams): ``"type3"`` (default) the type-3 transform with
           the roles swapped; ``"type2"`` the transpose of the lattice path's type-1 slice -- ValueError when these
           arguments do not take the lattice path (not griddable, not flat, ``force_use_type3``, basis beams);
@@ -477,11 +488,14 @@ class GPUSimulationEngine(SimulationEngine):
         """
         if adjoint_path not in ADJOINT_PATHS:
             raise ValueError(f"adjoint_path must be one of {ADJOINT_PATHS}, got {adjoint_path!r}")
-        if adjoint_wrt not in ("fluxes", "positions"):
-            raise ValueError(f"adjoint_wrt must be 'fluxes' or 'positions', got {adjoint_wrt!r}")
+        if adjoint_wrt not in ("fluxes", "positions", "sources"):
+            raise ValueError(f"adjoint_wrt must be 'fluxes', 'positions' or 'sources', got {adjoint_wrt!r}")
         positions = adjoint_of is not None and adjoint_wrt == "positions"
+        sources = adjoint_of is not None and adjoint_wrt == "sources"
         if positions and beam_coefs is not None:
             raise ValueError("the position adjoint does not cover basis beams (beam_coefs)")
+        if sources and beam_coefs is not None:
+            raise ValueError("the source adjoint does not cover basis beams (beam_coefs)")
         beam_order = checked_spline_order(beam_spline_opts)
         if interpolation_function not in ("az_za_map_coordinates", "az_za_simple"):
             raise ValueError(f"unknown interpolation_function {interpolation_function!r}")
@@ -558,6 +572,8 @@ class GPUSimulationEngine(SimulationEngine):
             R, bls, is_coplanar = prepare_array(ants, baselines, flat_array_tol, real_dtype)
         if positions and is_gridded:
             raise ValueError("the position adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
+        if sources and is_gridded:
+            raise ValueError("the source adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if adjoint_path == "type2" and not is_gridded:
             raise ValueError(
                 "adjoint_path='type2' needs the lattice path: a flat, griddable array without force_use_type3 and "
@@ -619,7 +635,8 @@ class GPUSimulationEngine(SimulationEngine):
                 if not use_basis:  # (a cached handle keeps its last setting)
                     h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
                 result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr,
-                                      gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis, positions=positions)
+                                      gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis, positions=positions,
+                                      sources=sources)
                 ok = True
                 return result
             if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != complex_dtype):
@@ -728,10 +745,11 @@ def _topo_from_coord_mgr(coord_mgr, time_indices):
     return np.stack(out)
 
 
-def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False, positions=False):
+def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False, positions=False, sources=False):
     """The adjoint's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors), each block's
     contribution added to ``gflux`` (``basis``: and to ``gcoefs``; returns the pair.  ``positions``: ``gflux`` is the
-    (nbls, 3) baseline gradient and ``run_position_adjoint`` adds to it).  Every ``run_adjoint`` call ends
+    (nbls, 3) baseline gradient and ``run_position_adjoint`` adds to it.  ``sources``: ``gflux`` is the (t1 - t0, nsrc, 3)
+    direction gradient and every block's ``run_source_adjoint`` fills that block's rows).  Every ``run_adjoint`` call ends
     synchronised."""
     on_device = not isinstance(g, np.ndarray)
     step = max(nblk_t, 1)
@@ -755,10 +773,12 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, ba
             h.run_basis_adjoint(ta, te_, f0, f1, blk, gflux, gcoefs, not first)
         elif positions:
             h.run_position_adjoint(ta, te_, f0, f1, blk, gflux, not first)
+        elif sources:  # (rows of a C-contiguous array: a contiguous view, written in place)
+            h.run_source_adjoint(ta, te_, f0, f1, blk, gflux[tb - t0:te - t0], False)
         else:
             h.run_adjoint(ta, te_, f0, f1, blk, gflux, not first)
         first = False
-    if first:  # no time steps: nothing contributes
+    if first and not sources:  # no time steps: nothing contributes
         for out in (gflux, gcoefs):
             if out is not None:
                 out[...] = 0

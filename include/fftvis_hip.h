@@ -289,6 +289,29 @@ int fv_sim_run_basis_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const vo
  * fail with FV_ERR_ARG.                                                                                                  */
 int fv_sim_run_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
                                 int gbls_on_device, int accumulate);
+/* Gradient of fv_sim_run's visibilities with respect to the sources' directions, for times [t0, t1) x freqs [f0, f1).
+ * Every forward path evaluates, to the handle's tolerance, out[f,t,r,k] = cj_k( sum_j c_jr(f,t; n_j(t)) exp(i nu_f s_k b'_k .
+ * x_j(t)) ), x = 2 pi R n, n_j(t) the source's topocentric unit vector (east, north, up) at time t -- R_t eq, the vectors of
+ * fv_sim_set_topo, or the astrometry context applied on the device -- and c the apparent strengths, which depend on n
+ * through the beams.  With G = dL/dV, dL = Re sum conj(G) dV, and Z the transposed transform of fv_sim_run_adjoint,
+ *     gtopo[t - t0, j, :] += P_n ( 2 pi R^T sum_f nu_f ( -Im sum_r c_jr Z(d)_jr )_d  +  sum_f grad_n Re sum_r c_jr(n) Z_jr ),
+ * Z(d) the same transform of the strengths times the d-th coordinate of the run's sign-adjusted baseline vector (the phase
+ * term), the second sum the beams' own dependence on the direction with Z held fixed, by central differences along two
+ * tangent great circles at a fixed angular step (the beam term), and P_n = 1 - n n^T: n is a unit vector, so only the
+ * tangential gradient is defined, dL = sum_{t,j} gtopo[t,j] . delta_j(t) for every small displacement delta perpendicular
+ * to n.  A source below the horizon at time t gets exactly 0 there (the cut is not differentiated).  It is the gradient of
+ * the smooth exact map, whichever path the forward takes, for both fv_sim_set_reference_compat forms.
+ * gvis: G, complex of the handle's precision in fv_sim_run's output layout for that block.  gtopo: (t1 - t0, nsrc, 3)
+ * float64 at either precision.  accumulate = 0: gtopo is zeroed first.  The *_on_device flags as in fv_sim_run; the call
+ * synchronises.  The fluxes are the forward's (fv_sim_set_sources).  The pass is fv_sim_run_adjoint's loop with 1 + D
+ * transforms per (time, frequency group, beam pair), D = 2 on a coplanar handle and 3 otherwise, and five beam evaluations
+ * per (source, channel); a lane's fp64 accumulator is (nsrc, channels of a block, 3), at most FFTVIS_HIP_ADJ_ACC_BYTES.  No
+ * atomics, one lane per time step: bitwise reproducible whatever FFTVIS_HIP_LANES.  Memory is given back under the
+ * FFTVIS_HIP_ADJ_KEEP_BYTES rule of fv_sim_run_adjoint.  FFTVIS_HIP_SRC_BEAM_STEP overrides the beam term's step (radians;
+ * for measurements).  A lattice handle (fv_sim_set_array_type1: set the array with fv_sim_set_array instead), a handle with
+ * basis beams, a null pointer, a flag other than 0 or 1 and NaN in G fail with FV_ERR_ARG.                              */
+int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
+                              int gtopo_on_device, int accumulate);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2

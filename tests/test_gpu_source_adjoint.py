@@ -1,0 +1,444 @@
+"""GPU tests of the gradient with respect to the source positions (``simulate_vis_source_adjoint``,
+``torch_simulate_vis_sky``, ``fv_sim_run_source_adjoint``).
+
+The tangential gradient ``gtopo`` (ntimes, nsrc, 3), ENU, is compared element by element with the exact reference built
+from the oracle's forward (``source_adjoint_refs.exact_gtopo``, pinned on the CPU in ``test_source_adjoint_host``): over a
+configuration matrix, with sources below the horizon and an empty time step, across source chunks and channel blocks, on
+an ideal lattice, at upsample_factor 1.25, with a coordinate manager and device astrometry, through the bare C ABI and
+through torch's gradcheck and backward.  Table beams at spline orders 0 and 1 have no reference (differences need a smooth
+interpolant): there the device is checked against itself."""
+
+import ctypes
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+
+import fftvis_amd
+from fftvis_amd import _lib, synth
+from oracle import fftvis_oracle as orc
+from tests.helpers import floored_rel, rel_l2, worst_part
+from tests.source_adjoint_refs import (exact_gtopo, margins, random_complex, sidereal_jacobian, source_config, table_config,
+                                       vis_shape)
+from tests.position_adjoint_refs import hex_positions
+from tests.test_gpu_adjoint import _up
+from tests.test_gpu_basis_adjoint import _forward_base
+from tests.test_gpu_position_adjoint import C_MAX, C_MAX32, K32, K32_PART, K64_PART
+
+pytestmark = pytest.mark.gpu
+
+# Element-wise tolerances against the exact reference, as multiples of base: test_gpu_position_adjoint's measures and
+# constants.  base = eps in fp64; in fp32 base = max(the forward's own rel l2 error against the oracle on the same
+# configuration, eps) (``_forward_base``).  rel l2 of the whole (ntimes, nsrc, 3) result <= 10 base in fp64 (20 at
+# upsample_factor = 1.25): the project's bound.  The bounds on a single ENU component (a component below 1e-3 of the whole
+# is measured against that floor), on max |err| / max |exact| and every fp32 factor start at that module's constants
+# (K64_PART 10, C_MAX 6, K32 13, K32_PART 40, C_MAX32 12) and are kept where they are at least 2 x the worst ratio
+# measured on an MI355X over this module's comparisons (FFTVIS_TEST_METRICS=<file> logs each comparison's ratios, one JSON
+# line each).  Measured, as ratio / base:
+#   fp64 over the 66 comparisons (base 6e-8): whole <= 0.32, a component <= 0.45, max |err| / max |exact| <= 0.31, all
+#   three in the matrix (unpolarized, one dish, flat array); outside the matrix at or below 0.18, 0.23, 0.18 (the ideal
+#   hex-19), upsample_factor = 1.25 at 0.03, 0.04, 0.02, device astrometry in (ra, dec) at 0.01, 0.04, 0.01.
+#   fp32 over the 54 matrix cells (base 1e-5: the forward's own error stayed below eps everywhere): whole <= 2.06,
+#   a component <= 4.03, max |err| <= 1.92 (unpolarized, one dish, flat array).
+#   Every constant keeps more than twice its measured worst: none moved.
+
+
+def _errors(got, exact):
+    got = np.asarray(got).astype(np.float64).reshape(-1, 3)
+    exact = exact.reshape(-1, 3)
+    err = got - exact
+    floor = 1e-3 * np.linalg.norm(exact)
+    return {"rel_l2": floored_rel(err, exact, floor), "component": worst_part(err, exact, 1, floor),
+            "max_abs": float(np.abs(err).max() / max(np.abs(exact).max(), 1e-300))}
+
+
+def _log(label, cfg, m, base):
+    rec = {"label": label, "precision": cfg.get("precision", 2), "base": base, **{k: v / base for k, v in m.items()}}
+    print("source-adjoint metrics", json.dumps(rec))
+    path = os.environ.get("FFTVIS_TEST_METRICS")
+    if path:
+        with open(path, "a") as fh:
+            fh.write(json.dumps(rec) + "\n")
+
+
+def _assert_close(label, cfg, got, exact, base, k64=10.0):
+    assert np.count_nonzero(exact) > 0 and np.isfinite(exact).all()
+    assert tuple(got.shape) == exact.shape and np.isfinite(np.asarray(got)).all()
+    m = _errors(got, exact)
+    _log(label, cfg, m, base)
+    fp64 = cfg.get("precision", 2) == 2
+    whole, part = (k64, K64_PART * k64 / 10.0) if fp64 else (K32, K32_PART)
+    assert m["rel_l2"] <= whole * base, (label, m, base)
+    assert m["component"] <= part * base, (label, m, base)
+    assert m["max_abs"] <= (C_MAX * k64 / 10.0 if fp64 else C_MAX32) * base, (label, m, base)
+    return m
+
+
+def _sid(cfg):
+    """The sidereal chain, asked for by name (the reference's manager is the oracle's ``SimpleCoordinateRotation``)."""
+    return dict(cfg, coord_method="SiderealRotation")
+
+
+def _gtopo(cfg, G, wrt="topo", **kw):
+    return fftvis_amd.simulate_vis_source_adjoint(G, **cfg, wrt=wrt, **kw)
+
+
+def _normals(cfg):
+    m = orc.SimpleCoordinateRotation(None, cfg["times"], cfg["telescope_loc"], cfg["ra"], cfg["dec"])
+    return np.stack([orc._topo_of(m, ti).T for ti in range(len(cfg["times"]))])
+
+
+# ---- 1. the matrix ---------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _matrix_reference(heights, sky, beams, compat):
+    """The exact gradient of a matrix cell (it does not depend on the run's precision)."""
+    cfg = source_config(heights, sky, beams, compat)
+    G = random_complex(vis_shape(cfg), 4)
+    return G, exact_gtopo(cfg, G)
+
+
+@pytest.mark.parametrize("heights", ["flat", "cm", "m"])
+@pytest.mark.parametrize("compat", [True, False])
+@pytest.mark.parametrize("beams", ["airy", "two", "complex"])
+@pytest.mark.parametrize("sky", ["unpol", "I", "full"])
+@pytest.mark.parametrize("precision", [2, 1])
+def test_source_gradient_matrix(gpu, precision, sky, beams, compat, heights):
+    cfg = _sid(source_config(heights, sky, beams, compat, precision))
+    G64, ref = _matrix_reference(heights, sky, beams, compat)
+    got = _gtopo(cfg, G64.astype(np.complex64 if precision == 1 else np.complex128))
+    assert got.shape == (2, 24, 3) and got.dtype == np.float64
+    n = _normals(cfg)
+    assert np.abs(np.einsum("tjd,tjd->tj", n, got)).max() <= (1e-12 if precision == 2 else 1e-6) * np.abs(got).max()
+    assert np.all(got[n[..., 2] <= 0] == 0)
+    _assert_close(f"matrix {precision} {sky} {beams} {compat} {heights}", cfg, got, ref, _forward_base(cfg))
+
+
+# ---- 2. edges --------------------------------------------------------------------------------------------------------
+def _edge_cfg(**kw):
+    """The perturbed hex-7 with centimetre heights, polarized, full-Stokes sky, two beams, the exact form of the flipped
+    baselines, fp64, the sidereal chain."""
+    return _sid(source_config("cm", "full", "two", False, 2, **kw))
+
+
+def _check_edge(label, cfg, k64=10.0, coord_mgr=None, ref_mgr=None, **kw):
+    G = random_complex(vis_shape(cfg), 7)
+    extra = {} if coord_mgr is None else {"coord_mgr": coord_mgr}
+    got = _gtopo(cfg, G, **extra, **kw)
+    _assert_close(label, cfg, got, exact_gtopo(cfg, G, coord_mgr=ref_mgr), cfg["eps"], k64)
+    return G, got
+
+
+def test_rows_below_the_horizon_and_an_empty_time_step(gpu):
+    """Sources around the meridian at the first time: a quarter of a sidereal day later some are below the horizon -- their
+    rows are exactly 0 --, half a day later all are, and the whole time step is 0."""
+    cfg = _edge_cfg(nsrc=20)
+    t0 = cfg["times"][0]
+    lst = orc.gmst_rad(t0) + synth.HERA_LON
+    rng = np.random.default_rng(1)
+    cfg.update(ra=lst + rng.uniform(-0.3, 0.3, 20), dec=synth.HERA_LAT + rng.uniform(-0.3, 0.3, 20),
+               times=t0 + np.array([0.0, 0.25, 0.5]))
+    up = _up(cfg)
+    assert np.all(up[0] > 0) and np.any(up[1] > 0) and np.any(up[1] <= 0) and not np.any(up[2] > 0)
+    assert margins(cfg)[0] > 1e-3
+    G, got = _check_edge("below the horizon, empty time step", cfg)
+    assert np.all(got[up <= 0] == 0) and np.all(got[2] == 0)
+    assert np.all(np.any(got[up > 0] != 0, axis=-1))
+
+
+@pytest.mark.parametrize("lanes", ["1", "2"])
+def test_source_chunks(gpu, monkeypatch, lanes):
+    monkeypatch.setenv("FFTVIS_HIP_LANES", lanes)
+    _check_edge(f"chunks lanes {lanes}", dict(_edge_cfg(nsrc=25, ntimes=4), min_chunks=3))
+
+
+@pytest.mark.parametrize("block_ch,ratio", [(1, 0.99), (2, 0.99), (2, 0.5)])
+def test_channel_blocks_cut_across_frequency_groups(gpu, monkeypatch, block_ch, ratio):
+    """nf = 5 in channel blocks of block_ch (FFTVIS_HIP_ADJ_ACC_BYTES: 24 bytes per channel and source) with frequency
+    groups cut by FFTVIS_HIP_GROUP_RATIO; the last block is short."""
+    cfg = _edge_cfg(nsrc=18, nfreq=5)
+    monkeypatch.setenv("FFTVIS_HIP_ADJ_ACC_BYTES", str(block_ch * 24 * 18))
+    monkeypatch.setenv("FFTVIS_HIP_GROUP_RATIO", str(ratio))
+    _check_edge(f"blocks {block_ch} ratio {ratio}", cfg)
+
+
+@pytest.mark.parametrize("order", [0, 1])
+def test_lane_counts_agree_on_table_beams_without_a_reference(gpu, monkeypatch, order):
+    """Spline orders 0 and 1 (no smooth interpolant, no reference): a repeat at one lane count returns the same bits, one
+    and two lanes agree to rounding, and the result is tangential and finite."""
+    cfg = _sid(table_config(order, nsrc=40, ntimes=4, seed=3))
+    G = random_complex(vis_shape(cfg), 10)
+    res = {}
+    for lanes in ("1", "2"):
+        monkeypatch.setenv("FFTVIS_HIP_LANES", lanes)
+        a, b = _gtopo(cfg, G), _gtopo(cfg, G)
+        assert np.array_equal(a, b), lanes
+        res[lanes] = a
+    assert np.isfinite(res["1"]).all() and np.count_nonzero(res["1"]) > 0
+    assert rel_l2(res["1"], res["2"]) <= 1e-12
+    n = _normals(cfg)
+    assert np.abs(np.einsum("tjd,tjd->tj", n, res["1"])).max() <= 1e-12 * np.abs(res["1"]).max()
+
+
+def test_reproducible_for_a_lane_count(gpu, monkeypatch):
+    cfg = _edge_cfg(nsrc=25, ntimes=4)
+    G = random_complex(vis_shape(cfg), 10)
+    res = {}
+    for lanes in ("1", "2"):
+        monkeypatch.setenv("FFTVIS_HIP_LANES", lanes)
+        a, b = _gtopo(cfg, G), _gtopo(cfg, G)
+        assert np.array_equal(a, b), lanes
+        res[lanes] = a
+    assert rel_l2(res["1"], res["2"]) <= 1e-12
+
+
+def test_ideal_lattice_goes_through_the_type3_transform(gpu):
+    """An exact hex-19, all baselines: the forward takes the lattice path there, the pass the type-3 transform with the
+    redundant runs."""
+    from fftvis_amd.core.antenna_gridding import check_antpos_griddability
+
+    c1 = synth.make_config("C1", nsrc=24, nfreq=3, ntimes=2, seed=2)
+    xy = 14.6 * hex_positions(2)
+    ants = {i: np.array([xy[i, 0], xy[i, 1], 0.0]) for i in range(19)}
+    assert check_antpos_griddability(ants)[0]
+    bls = [(i, j) for i in range(19) for j in range(i, 19)] + [(7, 3), (18, 0)]
+    cfg = _sid(dict(c1, ants=ants, baselines=bls, polarized=True, force_use_type3=False))
+    assert margins(cfg)[0] > 1e-3
+    G = random_complex(vis_shape(cfg), 5)
+    run = {k: v for k, v in cfg.items() if k != "force_use_type3"}
+    _assert_close("ideal hex-19", cfg, _gtopo(cfg, G), exact_gtopo(run, G), cfg["eps"])
+
+
+def test_upsample_125(gpu):
+    _check_edge("sigma 1.25", dict(_edge_cfg(), upsample_factor=1.25), k64=20.0)
+
+
+def test_coord_mgr_in_time_blocks_and_device_astrometry(gpu, monkeypatch):
+    """Per-time astrometry contexts: applied on the host and streamed one time step per block (``coord_mgr=``,
+    ``wrt="topo"``; every block fills its own rows), and applied on the device (``astrom=``, ``wrt="radec"``), the latter
+    against the reference chained through central differences of the oracle's ``astrometry.icrs_to_enu``."""
+    from fftvis_amd.gpu import gpu_simulate
+    from oracle import astrometry as oa
+
+    cfg = _edge_cfg(ntimes=3)
+    eq = orc.eq_unit_vectors(cfg["ra"], cfg["dec"])
+    ctxs = np.stack([oa.plausible_context(20 + t, synth.HERA_LAT) for t in range(3)])
+
+    class Mgr:  # the slice of matvis' manager the engine consumes
+        times = cfg["times"]
+
+        def setup(self):
+            pass
+
+        def rotate(self, ti):
+            self.all_coords_topo = oa.icrs_to_enu(eq, ctxs[ti])
+
+    assert margins(cfg, coord_mgr=Mgr())[0] > 1e-3
+    kw = dict(cfg, coord_method="CoordinateRotationERFA")
+    calls = []
+    real = gpu_simulate.SimHandle.run_source_adjoint
+    monkeypatch.setattr(gpu_simulate.SimHandle, "run_source_adjoint",
+                        lambda self, *a: calls.append((a[0], a[1], tuple(a[5].shape))) or real(self, *a))
+    monkeypatch.setattr(gpu_simulate, "_time_block", lambda *a, **k: 1)
+    G, host = _check_edge("coord_mgr, time blocks", kw, coord_mgr=Mgr(), ref_mgr=Mgr())
+    assert calls == [(0, 1, (1, 24, 3))] * 3, calls
+    monkeypatch.undo()
+    with pytest.raises(ValueError, match="wrt='topo'"):
+        _gtopo(kw, G, wrt="radec", coord_mgr=Mgr())
+    ref_topo = exact_gtopo(cfg, G, coord_mgr=Mgr())
+    dev_topo, dev_radec = _gtopo(kw, G, wrt=("topo", "radec"), astrom=ctxs, device_astrometry=True)
+    _assert_close("device astrometry, topo", cfg, dev_topo, ref_topo, cfg["eps"])
+    assert rel_l2(host, _gtopo(cfg, G)) > 1e-3  # and it is not the sidereal answer
+    h = 1e-5  # central differences of the oracle's chain: h^2 / 6 = 2e-11, rounding 1e-16 / h = 1e-11
+    J = np.empty((3, 24, 3, 2))
+    for t in range(3):
+        for c, (da, dd) in enumerate(((h, 0.0), (0.0, h))):
+            p = oa.icrs_to_enu(orc.eq_unit_vectors(cfg["ra"] + da, cfg["dec"] + dd), ctxs[t])
+            m = oa.icrs_to_enu(orc.eq_unit_vectors(cfg["ra"] - da, cfg["dec"] - dd), ctxs[t])
+            J[t, :, :, c] = ((p - m) / (2 * h)).T
+    ref_radec = np.einsum("tjd,tjdc->jc", ref_topo, J)
+    assert dev_radec.shape == (24, 2) and dev_radec.dtype == np.float64
+    m = {"rel_l2": rel_l2(dev_radec, ref_radec), "component": max(rel_l2(dev_radec[:, c], ref_radec[:, c]) for c in (0, 1)),
+         "max_abs": float(np.abs(dev_radec - ref_radec).max() / np.abs(ref_radec).max())}
+    _log("device astrometry, radec", cfg, m, cfg["eps"])
+    assert m["rel_l2"] <= 10 * cfg["eps"] and m["component"] <= K64_PART * cfg["eps"] and m["max_abs"] <= C_MAX * cfg["eps"], m
+
+
+# ---- 3. the surface --------------------------------------------------------------------------------------------------
+def test_wrt_radec_is_the_chained_topo_result(gpu):
+    cfg = _edge_cfg()
+    G = random_complex(vis_shape(cfg), 8)
+    gt = _gtopo(cfg, G)
+    gr = _gtopo(cfg, G, wrt="radec")
+    both = _gtopo(cfg, G, wrt=("radec", "topo"))
+    one = _gtopo(cfg, G, wrt=("topo",))
+    assert isinstance(both, tuple) and isinstance(one, tuple) and len(one) == 1
+    assert gr.shape == (24, 2) and gr.dtype == np.float64
+    J = fftvis_amd.radec_jacobian(cfg["ra"], cfg["dec"], cfg["times"], cfg["telescope_loc"])
+    assert np.array_equal(gr, fftvis_amd.topo_to_radec_gradient(gt, J))
+    assert np.array_equal(both[0], gr) and np.array_equal(both[1], gt) and np.array_equal(one[0], gt)
+    ref = np.einsum("tjd,tjdc->jc", exact_gtopo(cfg, G), sidereal_jacobian(cfg))
+    assert rel_l2(gr, ref) <= 10 * cfg["eps"]
+
+
+def test_raw_c_abi(gpu):
+    """fv_sim_run_source_adjoint through a bare ctypes handle configured by the engine's own setters: device and host
+    gtopo, accumulate 0 and 1, channel ranges that add up to the whole, and a basis handle and a lattice handle refused."""
+    import torch
+
+    from fftvis_amd.gpu import gpu_simulate as gs
+    from tests.basis_adjoint_refs import basis_config
+
+    cfg = _edge_cfg()
+    G = random_complex(vis_shape(cfg), 7)
+    gt = _gtopo(cfg, G)
+    nf, nt = len(cfg["freqs"]), len(cfg["times"])
+    L = _lib.lib()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    key, h = gs._acquire_handle(0, 2, cfg["eps"], 2, True)  # configured for exactly this run
+    try:
+        dG = torch.from_numpy(G).cuda()
+        dT = torch.full((nt, 24, 3), 7.0, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        assert L.fv_sim_run_source_adjoint(h._h, 0, nt, 0, nf, p(dG), 1, p(dT), 1, 0) == 0, L.fv_last_error()
+        assert np.array_equal(dT.cpu().numpy(), gt)  # accumulate = 0 zeroes first
+        assert L.fv_sim_run_source_adjoint(h._h, 0, nt, 0, nf, p(dG), 1, p(dT), 1, 1) == 0, L.fv_last_error()
+        assert rel_l2(dT.cpu().numpy(), 2 * gt) < 1e-14
+        parts = []
+        for f0, f1 in ((0, 1), (1, nf)):  # channel ranges add up to the whole
+            blk = dG[f0:f1].contiguous()
+            torch.cuda.synchronize()
+            assert L.fv_sim_run_source_adjoint(h._h, 0, nt, f0, f1, p(blk), 1, p(dT), 1, 0) == 0, L.fv_last_error()
+            parts.append(dT.cpu().numpy())
+        assert np.linalg.norm(parts[0]) > 0 and rel_l2(parts[0] + parts[1], gt) <= 10 * cfg["eps"]
+        sub = dict(cfg, freqs=cfg["freqs"][:1], fluxes=cfg["fluxes"][:, :1])
+        _assert_close("c abi, one channel", sub, parts[0], exact_gtopo(sub, G[:1]), cfg["eps"])
+        hT = np.zeros((nt, 24, 3))  # a host gtopo, accumulate 0 then 1
+        hp = hT.ctypes.data_as(ctypes.c_void_p)
+        assert L.fv_sim_run_source_adjoint(h._h, 0, nt, 0, nf, p(dG), 1, hp, 0, 0) == 0, L.fv_last_error()
+        assert np.array_equal(hT, gt)
+        assert L.fv_sim_run_source_adjoint(h._h, 0, nt, 0, nf, p(dG), 1, hp, 0, 1) == 0, L.fv_last_error()
+        assert rel_l2(hT, 2 * gt) < 1e-14
+        one = np.zeros((1, 24, 3))  # one time step of the block
+        blk = dG[:, 1:2].contiguous()
+        torch.cuda.synchronize()
+        assert L.fv_sim_run_source_adjoint(h._h, 1, 2, 0, nf, p(blk), 1, one.ctypes.data_as(ctypes.c_void_p), 0, 0) == 0
+        assert np.array_equal(one[0], gt[1])
+    finally:
+        gs._return_handle(key, h)
+    buf = torch.zeros(1 << 16, dtype=torch.complex128, device="cuda")
+    torch.cuda.synchronize()
+    xy = 14.6 * hex_positions(1)
+    lat = dict(cfg, ants={i: np.array([xy[i, 0], xy[i, 1], 0.0]) for i in range(7)}, force_use_type3=False)
+    fftvis_amd.simulate_vis(**lat)  # the lattice path
+    bcfg = basis_config()
+    for run_cfg, eps, word in ((None, cfg["eps"], b"fv_sim_set_array"), (bcfg, bcfg["eps"], b"basis")):
+        if run_cfg is not None:
+            fftvis_amd.simulate_vis(**run_cfg)
+        key, h = gs._acquire_handle(0, 2, eps, 2, True)
+        try:
+            assert L.fv_sim_run_source_adjoint(h._h, 0, 1, 0, 1, p(buf), 1, p(buf), 1, 0) == 1
+            assert word in L.fv_last_error(), L.fv_last_error()
+        finally:
+            gs._return_handle(key, h)
+
+
+def test_nan_in_g_fails_and_the_handle_stays_usable(gpu):
+    cfg = _edge_cfg()
+    G = random_complex(vis_shape(cfg), 7)
+    good = _gtopo(cfg, G)
+    bad = G.copy()
+    bad[1, 0, 1, 0, 3] = np.nan
+    with pytest.raises(_lib.FftvisHipError, match="NaN"):
+        _gtopo(cfg, bad)
+    assert np.array_equal(_gtopo(cfg, G), good)
+
+
+def test_bulk_device_memory_is_given_back(gpu, monkeypatch):
+    """Beyond FFTVIS_HIP_ADJ_KEEP_BYTES (here 0) a cached handle holds after a call no more than it held after the
+    forward: no accumulator, staged array or set of strengths stays."""
+    monkeypatch.setenv("FFTVIS_HIP_ADJ_KEEP_BYTES", "0")
+    cfg = _edge_cfg()
+    fftvis_amd.simulate_vis(**cfg)
+    held = ctypes.c_int64(0)
+    _lib.check(_lib.lib().fv_device_bytes_on(0, ctypes.byref(held)))
+    before = held.value
+    _gtopo(cfg, random_complex(vis_shape(cfg), 1))
+    _lib.check(_lib.lib().fv_device_bytes_on(0, ctypes.byref(held)))
+    assert held.value - before < 1 << 20, (before, held.value)
+
+
+def test_a_forward_call_after_the_pass_returns_the_same_bits(gpu):
+    cfg = _edge_cfg()
+    before = fftvis_amd.simulate_vis(**cfg)
+    _gtopo(cfg, random_complex(vis_shape(cfg), 3))
+    assert np.array_equal(fftvis_amd.simulate_vis(**cfg), before)
+
+
+def test_a_device_tensor_in_gives_device_tensors_out(gpu):
+    import torch
+
+    cfg = _edge_cfg()
+    G = random_complex(vis_shape(cfg), 9)
+    gt, gr = _gtopo(cfg, G, wrt=("topo", "radec"))
+    dt, dr = _gtopo(cfg, torch.from_numpy(G).cuda(), wrt=("topo", "radec"))
+    assert dt.device.type == "cuda" and dr.device.type == "cuda" and dt.dtype == torch.float64
+    assert np.array_equal(dt.cpu().numpy(), gt) and rel_l2(dr.cpu().numpy(), gr) <= 1e-14
+
+
+# ---- 4. torch --------------------------------------------------------------------------------------------------------
+def _torch_kwargs(cfg):
+    return {k: v for k, v in cfg.items() if k not in ("fluxes", "ra", "dec")}
+
+
+def test_torch_gradcheck_both_inputs(gpu):
+    """fp64, 8 sources, 1 channel (150 MHz), 1 time, eps 1e-12, angular step 1e-6 rad: the central difference's truncation
+    is (k h)^2 / 6 with k = 2 pi nu |b| / c <= 92 / rad on this array (|b| <= 29.3 m), 1.4e-9 relative, against rtol 1e-4;
+    atol 1e-6 is 1e-8 of the entries' scale k |V| ~ 1e2."""
+    import torch
+
+    cfg = _edge_cfg(nsrc=8, nfreq=1, ntimes=1)
+    cfg.update(eps=1e-12, freqs=np.array([150e6]), baselines=[(0, 1), (2, 5), (3, 6), (1, 4), (6, 0), (2, 2)])
+    _, _, cfg["fluxes"] = synth.catalog(8, cfg["freqs"], 0, polarized_sky=True)
+    assert margins(cfg)[0] > 1e-3
+    kw = _torch_kwargs(cfg)
+    F = torch.tensor(cfg["fluxes"] + np.array([1.0, 0, 0, 0]), dtype=torch.float64, device="cuda", requires_grad=True)
+    P = torch.tensor(np.stack([cfg["ra"], cfg["dec"]], axis=1), dtype=torch.float64, device="cuda", requires_grad=True)
+    assert torch.autograd.gradcheck(lambda f, p: fftvis_amd.torch_simulate_vis_sky(f, p, **kw), (F, P), eps=1e-6,
+                                    atol=1e-6, rtol=1e-4)
+    out = fftvis_amd.torch_simulate_vis_sky(F, P, **kw)
+    assert out.device == F.device and out.is_complex() and tuple(out.shape) == vis_shape(cfg)
+
+
+def test_torch_backward_equals_the_direct_calls(gpu, monkeypatch):
+    """d/d(F, P) sum |V - Dat|^2 through torch equals the direct calls on G = 2 (V - Dat); a tensor that does not require a
+    gradient gets none, and its pass does not run."""
+    import torch
+
+    import fftvis_amd.adjoint as adj
+
+    cfg = _edge_cfg()
+    kw = _torch_kwargs(cfg)
+    Dat = random_complex(vis_shape(cfg), 15)
+    F = torch.tensor(cfg["fluxes"], dtype=torch.float64, device="cuda", requires_grad=True)
+    P = torch.tensor(np.stack([cfg["ra"], cfg["dec"]], axis=1), dtype=torch.float64, device="cuda", requires_grad=True)
+    V = fftvis_amd.torch_simulate_vis_sky(F, P, **kw)
+    (V - torch.from_numpy(Dat).cuda()).abs().pow(2).sum().backward()
+    G = 2 * (V.detach().cpu().numpy() - Dat)
+    gp = _gtopo(cfg, G, wrt="radec")
+    gf = fftvis_amd.simulate_vis_adjoint(G, **{k: v for k, v in cfg.items() if k != "fluxes"}, full_stokes=True)
+    assert np.allclose(P.grad.cpu().numpy(), gp, rtol=1e-12, atol=1e-12 * np.abs(gp).max())
+    assert np.allclose(F.grad.cpu().numpy(), gf, rtol=1e-12, atol=1e-12 * np.abs(gf).max())
+    ran = []
+    real_p, real_f = adj.simulate_vis_source_adjoint, adj.simulate_vis_adjoint
+    monkeypatch.setattr(adj, "simulate_vis_source_adjoint", lambda *a, **k: ran.append("sources") or real_p(*a, **k))
+    monkeypatch.setattr(adj, "simulate_vis_adjoint", lambda *a, **k: ran.append("fluxes") or real_f(*a, **k))
+    F2 = F.detach().clone().requires_grad_(True)
+    fftvis_amd.torch_simulate_vis_sky(F2, P.detach(), **kw).abs().pow(2).sum().backward()
+    assert ran == ["fluxes"] and F2.grad is not None
+    P3 = P.detach().clone().requires_grad_(True)
+    fftvis_amd.torch_simulate_vis_sky(F.detach(), P3, **kw).abs().pow(2).sum().backward()
+    assert ran == ["fluxes", "sources"] and P3.grad is not None
+    with pytest.raises(TypeError, match="radec"):
+        fftvis_amd.torch_simulate_vis_sky(F, P, ra=cfg["ra"], **kw)
