@@ -6,7 +6,8 @@ Mirrors the reference package's public surface for the gpu backend
 (``simulate_vis_adjoint``) and a torch autograd entry point (``torch_simulate_vis``), and for basis beams the gradients
 with respect to the fluxes and the coefficients (``simulate_vis_basis_adjoint``, ``torch_simulate_vis_basis``), and the
 gradient with respect to the antenna positions (``simulate_vis_position_adjoint``, ``torch_simulate_vis_array``) and to
-the source positions (``simulate_vis_source_adjoint``, ``torch_simulate_vis_sky``).
+the source positions (``simulate_vis_source_adjoint``, ``torch_simulate_vis_sky``), and the forward-mode tangent along
+all three (``simulate_vis_jvp``).
 """
 
 __version__ = "0.1.0"
@@ -16,10 +17,12 @@ from .core.beam_basis import compute_beam_basis, compute_beam_basis_per_freq  # 
 from .core.simulate import SimulationEngine, default_accuracy_dict  # noqa: F401
 from .wrapper import create_beam_evaluator, create_simulation_engine, simulate_vis  # noqa: F401
 from .adjoint import (  # noqa: F401
+    antenna_to_baseline_tangent,
     baseline_to_antenna_gradient,
     radec_jacobian,
     simulate_vis_adjoint,
     simulate_vis_basis_adjoint,
+    simulate_vis_jvp,
     simulate_vis_position_adjoint,
     simulate_vis_source_adjoint,
     torch_simulate_vis,

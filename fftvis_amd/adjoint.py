@@ -16,6 +16,10 @@ sesquilinear (``fv_sim_run_basis_adjoint``).
 The antenna positions have theirs as well, ``simulate_vis_position_adjoint`` and ``torch_simulate_vis_array``: the
 gradient of the exact sum every forward path approximates, from forward transforms of the strengths times the sources'
 coordinates (``fv_sim_run_position_adjoint``).
+
+The other product, J v, is ``simulate_vis_jvp``: the forward-mode tangent of the visibilities along a change of the
+antenna positions, the source positions and the fluxes (``fv_sim_run_tangent``), which the three torch operations
+also offer to ``torch.autograd.forward_ad`` through their ``jvp``.
 """
 
 from __future__ import annotations
@@ -199,6 +203,17 @@ def _autograd_function():
                 g = torch.from_numpy(g)
             return g.to(device=grad_output.device, dtype=ctx.flux_dtype), None
 
+        @staticmethod
+        def jvp(ctx, d_fluxes, _):
+            # the map is linear in the fluxes: the tangent is the simulation of d_fluxes
+            from .wrapper import simulate_vis
+
+            if d_fluxes is None:
+                return None
+            dv = simulate_vis(fluxes=d_fluxes.detach().cpu().numpy(),
+                              **{k: v for k, v in ctx.kwargs.items() if k != "adjoint_path"})
+            return torch.from_numpy(np.ascontiguousarray(dv)).to(d_fluxes.device)
+
     return _SimulateVis
 
 
@@ -211,7 +226,8 @@ def torch_simulate_vis(fluxes, **kwargs):
     ``times``, ``beam``, ``telescope_loc``, ...).  Returns the visibilities as a complex tensor on ``fluxes``' device.
     The backward pass is ``simulate_vis_adjoint`` of the incoming gradient: under torch's convention for a real input
     and a complex output the gradient is Re(A^H g), the adjoint defined there.  ``adjoint_path`` ("type3" | "type2" |
-    "auto", see ``simulate_vis_adjoint``) goes to the backward pass only; ``simulate_vis`` never sees it."""
+    "auto", see ``simulate_vis_adjoint``) goes to the backward pass only; ``simulate_vis`` never sees it.  Forward mode
+    (``torch.autograd.forward_ad``): the map is linear, so the tangent is the simulation of the fluxes' tangent."""
     global _FN
     if _FN is None:
         _FN = _autograd_function()
@@ -421,7 +437,9 @@ def torch_simulate_vis_basis(fluxes, beam_coefs, **kwargs):
     (nant, nbasis, nfreqs).  Every other argument is a keyword of ``simulate_vis``.  Returns the visibilities as a complex
     tensor on ``fluxes``' device.  The backward pass is ``simulate_vis_basis_adjoint`` of the incoming gradient, with only
     the gradients autograd asks for (``ctx.needs_input_grad``): Re(A^H g) for the real fluxes, and for the complex
-    coefficients torch's convention for a complex leaf, dL = Re sum conj(grad) dC."""
+    coefficients torch's convention for a complex leaf, dL = Re sum conj(grad) dC.  Forward-mode differentiation
+    (``torch.autograd.forward_ad``) is not covered here: the operation defines no ``jvp`` (``simulate_vis_jvp`` does not
+    take ``beam_coefs``)."""
     global _FN_BASIS
     if _FN_BASIS is None:
         _FN_BASIS = _basis_autograd_function()
@@ -586,6 +604,15 @@ def simulate_vis_position_adjoint(
     return res[names[0]] if single else tuple(res[n] for n in names)
 
 
+def _tangent_tensor(dv, like):
+    """A tangent of ``simulate_vis_jvp`` as a tensor on the device of the operation's output (``like``: the fluxes)."""
+    import torch
+
+    if not _is_tensor(dv):
+        dv = torch.from_numpy(np.ascontiguousarray(dv))
+    return dv.to(like.device)
+
+
 def _array_autograd_function():
     import torch
 
@@ -599,6 +626,7 @@ def _array_autograd_function():
             ctx.full_stokes = fluxes.ndim == 3
             ctx.flux_dtype, ctx.pos_dtype, ctx.pos_device = fluxes.dtype, antpos.dtype, antpos.device
             ctx.save_for_backward(fluxes, antpos)
+            ctx.save_for_forward(fluxes, antpos)
             ants = dict(zip(antnums, antpos.detach().cpu().numpy().astype(np.float64)))
             vis = simulate_vis(ants=ants, fluxes=fluxes.detach().cpu().numpy(), **kwargs)
             return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
@@ -620,6 +648,17 @@ def _array_autograd_function():
                 gp = gp.to(device=ctx.pos_device, dtype=ctx.pos_dtype)
             return gf, gp, None, None
 
+        @staticmethod
+        def jvp(ctx, d_fluxes, d_antpos, *_):
+            # a missing tangent (None) skips its rounds
+            fluxes, antpos = ctx.saved_tensors
+            if d_fluxes is None and d_antpos is None:
+                return None
+            ants = dict(zip(ctx.antnums, antpos.detach().cpu().numpy().astype(np.float64)))
+            dv = simulate_vis_jvp(ants=ants, fluxes=fluxes, d_ants=None if d_antpos is None else d_antpos.detach(),
+                                  d_fluxes=None if d_fluxes is None else d_fluxes.detach(), **ctx.kwargs)
+            return _tangent_tensor(dv, fluxes)
+
     return _SimulateVisArray
 
 
@@ -632,7 +671,8 @@ def torch_simulate_vis_array(fluxes, antpos, *, antnums=None, **kwargs):
     ``baselines`` refers to (default ``range(nant)``); every other argument is a keyword of ``simulate_vis`` -- but for
     ``ants``, which the two tensors replace (TypeError).  Returns the visibilities as a complex tensor on ``fluxes``'
     device.  The backward pass runs only what autograd asks for (``ctx.needs_input_grad``): ``simulate_vis_adjoint`` for
-    the fluxes, ``simulate_vis_position_adjoint`` for the positions."""
+    the fluxes, ``simulate_vis_position_adjoint`` for the positions.  Forward mode (``torch.autograd.forward_ad``) runs
+    ``simulate_vis_jvp`` on the tangents present."""
     global _FN_ARRAY
     if "ants" in kwargs:
         raise TypeError("torch_simulate_vis_array takes the antenna positions as the tensor antpos (and antnums), not ants=")
@@ -858,6 +898,216 @@ def simulate_vis_source_adjoint(
     return res[names[0]] if single else tuple(res[n] for n in names)
 
 
+def antenna_to_baseline_tangent(d_ants, ants: dict, baselines: list):
+    """The change of the baseline vectors along a change ``d_ants`` (nant, 3) of the antenna positions, rows in ``ants``'
+    iteration order: baseline (i, j) is ``ants[j] - ants[i]``, so row k is ``d_ants[j_k] - d_ants[i_k]`` -- the transpose
+    of ``baseline_to_antenna_gradient``.  Returns (nbls, 3), numpy for numpy input and a tensor on ``d_ants``' device
+    for a tensor."""
+    row = {a: i for i, a in enumerate(ants)}
+    i0 = np.array([row[b[0]] for b in baselines], dtype=np.int64)
+    i1 = np.array([row[b[1]] for b in baselines], dtype=np.int64)
+    if tuple(d_ants.shape) != (len(row), 3):
+        raise ValueError(f"d_ants must have shape ({len(row)}, 3), got {tuple(d_ants.shape)}")
+    if _is_tensor(d_ants):
+        import torch
+
+        return d_ants[torch.as_tensor(i1, device=d_ants.device)] - d_ants[torch.as_tensor(i0, device=d_ants.device)]
+    d_ants = np.asarray(d_ants, dtype=np.float64)
+    return d_ants[i1] - d_ants[i0]
+
+
+def simulate_vis_jvp(
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    d_ants=None,
+    d_baselines=None,
+    d_radec=None,
+    d_topo=None,
+    d_fluxes=None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    beam_coefs: np.ndarray = None,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """Forward-mode tangent (Jacobian-vector product) of ``simulate_vis(ants, fluxes, ra, dec, ...)``: the change dV of the
+    visibilities along a direction of the parameters, an array of ``simulate_vis``'s shape and dtype,
+
+        dV = dV/d(ants) . d_ants  +  dV/d(positions of the sources) . d_radec  +  dV/d(fluxes) . d_fluxes.
+
+    Both position derivatives of the exact sum every forward path approximates are forward transforms of other strengths
+    (``fv_sim_run_tangent``): about three forward runs for the antennas and 1 + D for the sources (D = 2 on a flat array,
+    3 otherwise), whatever the number of parameters.  It is the transpose of the adjoints: for every G,
+    ``Re <dV, G> = d_baselines . gbls + d_topo . gtopo + d_fluxes . gflux`` with the gradients of
+    ``simulate_vis_position_adjoint``, ``simulate_vis_source_adjoint`` and ``simulate_vis_adjoint``.
+
+    * ``d_ants``: (nant, 3), ENU metres, rows in ``ants``' iteration order; ``d_baselines[k] = d_ants[j_k] - d_ants[i_k]``
+      is formed on the host (``antenna_to_baseline_tangent``).  ``d_baselines``: (nbls, 3), every listed baseline an
+      independent vector.  Giving both is a ValueError.  On a flat array the up component still enters.
+    * ``d_radec``: (nsrc, 2) radians, columns (ra, dec), chained on the host through ``radec_jacobian`` -- for
+      ``coord_method="SiderealRotation"`` and device astrometry; with a caller's ``coord_mgr`` (or a matvis manager the
+      engine would build) only ``d_topo`` is served: ValueError.  ``d_topo``: (ntimes, nsrc, 3), ENU; its radial part is
+      removed (the directions are unit vectors), and a source below the horizon at time t contributes exactly 0 there.
+      Giving both is a ValueError.
+    * ``d_fluxes``: ``fluxes``' shape.  The map is linear in the fluxes, so this part is one ``simulate_vis`` run on
+      ``d_fluxes``, added to the rest.
+
+    No input at all gives zeros.  numpy arrays, or torch tensors: when any of the tangents is a tensor on the run's device
+    the position tangents are handed over by pointer and the result is a tensor on that device; host tensors in, a host
+    tensor out.  Every other keyword means what it means for ``simulate_vis``, ``reference_compat`` included;
+    ``force_use_type3`` is accepted and always on for the position parts: the pass runs the type-3 transform.  Not
+    covered: ``beam_coefs`` (NotImplementedError), a type-1 (lattice) form of the pass."""
+    if beam_coefs is not None:
+        raise NotImplementedError("simulate_vis_jvp does not support basis beams (beam_coefs)")
+    if d_ants is not None and d_baselines is not None:
+        raise ValueError("give the antenna tangent as d_ants or as d_baselines, not both")
+    if d_radec is not None and d_topo is not None:
+        raise ValueError("give the source tangent as d_radec or as d_topo, not both")
+    if backend != "gpu":
+        raise ValueError(f"Unsupported backend: {backend}")
+    if d_radec is not None:
+        if coord_mgr is not None:
+            raise ValueError("d_radec needs this package's own chain from (ra, dec) to the topocentric vectors; with "
+                             "coord_mgr= the chain is the manager's: apply its Jacobian and pass d_topo")
+        if astrom is None and not device_astrometry and coord_method != "SiderealRotation":
+            raise ValueError(f"d_radec needs coord_method='SiderealRotation' or device astrometry (astrom= / "
+                             f"device_astrometry=True); coord_method={coord_method!r} builds a matvis manager whose chain "
+                             "is its own: pass d_topo")
+    if eps is None:
+        eps = default_accuracy_dict[precision]
+    ants = {k: np.array(v) for k, v in ants.items()}
+    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
+    beam_idx = validate_beam_idx(beam_idx, None, len(beam_list), len(ants))
+    feed_index(use_feed)
+    if baselines is None:
+        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
+    nsrc = int(np.size(ra))
+    nfreqs = int(np.size(freqs))
+    ntimes = len(julian_dates(times))
+    nbls = len(baselines)
+    tangents = (d_ants, d_baselines, d_radec, d_topo, d_fluxes)
+    any_tensor = any(_is_tensor(x) for x in tangents)
+    dev_tensor = next((x for x in tangents if _is_tensor(x) and x.device.type == "cuda"), None)
+    on_device = dev_tensor is not None
+    if on_device and (dev_tensor.device.index or 0) != int(device):
+        raise ValueError(f"a tangent lives on {dev_tensor.device}, the run is on cuda:{int(device)}")
+
+    def host(x):
+        return x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+
+    if _is_tensor(fluxes):
+        fluxes = fluxes.detach().cpu().numpy()
+    fluxes = np.asarray(fluxes)
+    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
+        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
+    if fluxes.ndim == 3 and not polarized:
+        raise ValueError("a full-Stokes sky needs polarized=True")
+    if d_fluxes is not None and tuple(d_fluxes.shape) != fluxes.shape:
+        raise ValueError(f"d_fluxes must have fluxes' shape {fluxes.shape}, got {tuple(d_fluxes.shape)}")
+    if d_ants is not None:
+        d_baselines = antenna_to_baseline_tangent(d_ants, ants, baselines)
+    if d_baselines is not None and tuple(d_baselines.shape) != (nbls, 3):
+        raise ValueError(f"d_baselines must have shape ({nbls}, 3), got {tuple(d_baselines.shape)}")
+    if d_radec is not None and tuple(d_radec.shape) != (nsrc, 2):
+        raise ValueError(f"d_radec must have shape ({nsrc}, 2), got {tuple(d_radec.shape)}")
+    if d_topo is not None and tuple(d_topo.shape) != (ntimes, nsrc, 3):
+        raise ValueError(f"d_topo must have shape ({ntimes}, {nsrc}, 3), got {tuple(d_topo.shape)}")
+    rdt = np.float32 if precision == 1 else np.float64
+    cdt = np.complex64 if precision == 1 else np.complex128
+    shape = (nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls)
+    if astrom is None and device_astrometry and coord_mgr is None and coord_method != "SiderealRotation":
+        from .core.coords import erfa_astrom_context
+
+        astrom = erfa_astrom_context(times, telescope_loc)  # (the engine and the Jacobian see the same contexts)
+    if d_radec is not None:
+        # the engine rounds ra / dec to the run's precision first: the Jacobian is taken where the run is
+        jac = radec_jacobian(np.asarray(ra).astype(rdt), np.asarray(dec).astype(rdt), times, telescope_loc, astrom=astrom,
+                             device=device)
+        d_topo = np.einsum("tjdc,jc->tjd", jac, host(d_radec).astype(np.float64))
+    common = dict(
+        ants=ants, ra=ra, dec=dec, freqs=freqs, times=times, telescope_loc=telescope_loc, beam_idx=beam_idx,
+        baselines=baselines, precision=precision, polarized=polarized, eps=eps, upsample_factor=upsample_factor,
+        beam_spline_opts=beam_spline_opts, use_feed=use_feed, flat_array_tol=flat_array_tol,
+        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
+        coord_method=coord_method, coord_method_params=coord_method_params, force_use_ray=force_use_ray,
+        trace_mem=trace_mem, source_buffer=source_buffer, coord_mgr=coord_mgr, reference_compat=reference_compat,
+        astrom=astrom, device_astrometry=device_astrometry,
+    )
+    if on_device:
+        import torch
+
+        tdev = dev_tensor.device
+        tc = torch.complex64 if precision == 1 else torch.complex128
+
+        def buf(x):
+            if x is None:
+                return None
+            x = x.detach() if _is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+            return x.to(device=tdev, dtype=torch.float64).contiguous()
+
+        dv = torch.zeros(shape, dtype=tc, device=tdev)
+    else:
+        def buf(x):
+            return None if x is None else np.ascontiguousarray(host(x), dtype=np.float64)
+
+        dv = np.zeros(shape, dtype=cdt)
+    db, dt_ = buf(d_baselines), buf(d_topo)
+    if db is not None or dt_ is not None:
+        if on_device:
+            torch.cuda.synchronize(tdev)  # the library's streams do not follow torch's: the inputs and dv are complete
+        from .wrapper import create_simulation_engine, device_chunks
+
+        nax = nfeed = 2 if polarized else 1
+        engine = create_simulation_engine(backend=backend, device=device)
+        nchunks = device_chunks(device, max_memory, min_chunks, beam_list, nax, nfeed, len(ants), nsrc, precision,
+                                source_buffer, nfreqs)
+        dv = engine.simulate(fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, force_use_type3=True,
+                             nchunks=nchunks, tangent_of=(db, dt_, dv), **common)
+    if d_fluxes is not None:
+        from .wrapper import simulate_vis
+
+        vf = simulate_vis(fluxes=host(d_fluxes).astype(rdt, copy=False), beam=beam_list, force_use_type3=force_use_type3,
+                          backend=backend, max_memory=max_memory, min_chunks=min_chunks, device=device, **common)
+        if on_device:
+            dv += torch.from_numpy(np.ascontiguousarray(vf)).to(dv.device)
+        else:
+            dv += vf
+    if any_tensor and not on_device:  # host tensors in, a host tensor out
+        import torch
+
+        dv = torch.from_numpy(np.ascontiguousarray(dv))
+    return dv
+
+
 def _sky_autograd_function():
     import torch
 
@@ -870,6 +1120,7 @@ def _sky_autograd_function():
             ctx.full_stokes = fluxes.ndim == 3
             ctx.flux_dtype, ctx.pos_dtype, ctx.pos_device = fluxes.dtype, radec.dtype, radec.device
             ctx.save_for_backward(fluxes, radec)
+            ctx.save_for_forward(fluxes, radec)
             rd = radec.detach().cpu().numpy().astype(np.float64)
             vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(), ra=rd[:, 0].copy(), dec=rd[:, 1].copy(), **kwargs)
             return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
@@ -892,6 +1143,18 @@ def _sky_autograd_function():
                 gp = gp.to(device=ctx.pos_device, dtype=ctx.pos_dtype)
             return gf, gp, None
 
+        @staticmethod
+        def jvp(ctx, d_fluxes, d_radec, _):
+            # a missing tangent (None) skips its rounds
+            fluxes, radec = ctx.saved_tensors
+            if d_fluxes is None and d_radec is None:
+                return None
+            rd = radec.detach().cpu().numpy().astype(np.float64)
+            dv = simulate_vis_jvp(fluxes=fluxes, ra=rd[:, 0].copy(), dec=rd[:, 1].copy(),
+                                  d_radec=None if d_radec is None else d_radec.detach(),
+                                  d_fluxes=None if d_fluxes is None else d_fluxes.detach(), **ctx.kwargs)
+            return _tangent_tensor(dv, fluxes)
+
     return _SimulateVisSky
 
 
@@ -904,7 +1167,8 @@ def torch_simulate_vis_sky(fluxes, radec, **kwargs):
     keyword of ``simulate_vis`` -- but for ``ra`` and ``dec``, which the tensor replaces (TypeError).  Returns the
     visibilities as a complex tensor on ``fluxes``' device.  The backward pass runs only what autograd asks for
     (``ctx.needs_input_grad``): ``simulate_vis_adjoint`` for the fluxes, ``simulate_vis_source_adjoint(wrt="radec")`` for the
-    positions, which needs ``coord_method="SiderealRotation"`` or device astrometry."""
+    positions, which needs ``coord_method="SiderealRotation"`` or device astrometry.  Forward mode
+    (``torch.autograd.forward_ad``) runs ``simulate_vis_jvp`` on the tangents present, under the same condition."""
     global _FN_SKY
     if "ra" in kwargs or "dec" in kwargs:
         raise TypeError("torch_simulate_vis_sky takes the source positions as the tensor radec, not ra= / dec=")

@@ -640,6 +640,18 @@ int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const v
         h->impl->run_source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gtopo, gtopo_on_device, accumulate);
     });
 }
+int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
+                       int dtopo_on_device, void *out, int out_on_device) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(out, "null output");
+        FV_REQUIRE(dbls || dtopo, "neither tangent input is given (dbls and dtopo are both null)");
+        FV_REQUIRE((dbls_on_device == 0 || dbls_on_device == 1) && (dtopo_on_device == 0 || dtopo_on_device == 1) &&
+                       (out_on_device == 0 || out_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_tangent(t0, t1, f0, f1, dbls, dbls_on_device, dtopo, dtopo_on_device, out, out_on_device);
+    });
+}
 int fv_sim_sync(fv_sim *h) { FV_SIM_CALL(h->impl->sync()); }
 int fv_sim_stats(fv_sim *h, double *vals, int n) { FV_SIM_CALL(h->impl->stats(vals, n)); }
 int fv_sim_reset_stats(fv_sim *h) { FV_SIM_CALL(h->impl->reset_stats()); }

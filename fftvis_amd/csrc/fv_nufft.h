@@ -2440,6 +2440,13 @@ struct InterpArgs {
     void *gs;
     int gs_nf, gs_f0;
     int64_t gs_nbls;
+    // Tangent epilogue (k_interp<.., TANGENT>; Sim::run_tangent): the launch gathered the transform of one of the tangent's
+    // strength sets, and every member ADDS, into its own output slot and with the value V the forward would store there
+    // (after unpacking, height factor, conjugation and feed transposition),
+    //     i nu_f tg_w[km] V     (a weighted round: tg_w fp64 by global baseline id, nu_f = scale[fg], the channel's own),
+    //     V                     (tg_w == nullptr: the beam term's round).
+    // A pair's list holds every baseline once: one owner thread per slot and launch, plain read-modify-write.
+    const double *tg_w;
 };
 
 // Bessel function of the first kind and integer order k >= 0 by its power series, (x / 2)^k / k! sum_m (-x^2 / 4)^m /
@@ -2489,7 +2496,8 @@ __device__ inline cplx<double> wterm_factor(int k, double zc, double zh, double 
 // gather spent 70 % of its time waiting for them one at a time.)
 // ZD (direct third dimension, InterpArgs::zd_n) and WT (height terms, InterpArgs::wt_k) are compile-time: carried as run-time
 // branches they cost the plain 2-D gather 47 registers (146 -> 193 fp64, 98 -> 177 fp32: a wave per SIMD, 11-24 % of its time).
-template <typename T, int DIM, bool HERM, int NR, bool ZD = false, bool WT = false, bool GRAD = false>
+// GRAD (InterpArgs::gs) and TANGENT (InterpArgs::tg_w) are epilogues of their own passes, compile-time for the same reason.
+template <typename T, int DIM, bool HERM, int NR, bool ZD = false, bool WT = false, bool GRAD = false, bool TANGENT = false>
 __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
     const cplx<T> *__restrict__ grid, int64_t N, const T *__restrict__ bt0,
     const T *__restrict__ bt1, const T *__restrict__ bt2, const int *__restrict__ bl_idx,
@@ -2730,6 +2738,17 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                     }
                     continue;
                 }
+                if constexpr (TANGENT) {  // i nu_f w V (or V) added to the member's own slot
+                    double ar = vr, ai = vim_;
+                    if (a.tg_w) {
+                        const double wq = sc * a.tg_w[km];
+                        ar = -wq * vim_;
+                        ai = wq * vr;
+                    }
+                    o->re += (T)ar;
+                    o->im += (T)ai;
+                    continue;
+                }
                 if (a.basis) {
                     const int f = a.f_first + fg;
                     const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
@@ -2821,6 +2840,17 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                         s2.re += (double)g2.re * vr + (double)g2.im * vi;
                         s2.im += (double)g2.re * vi - (double)g2.im * vr;
                     }
+                    continue;
+                }
+                if constexpr (TANGENT) {
+                    double ar = vr, ai = vi;
+                    if (a.tg_w) {
+                        const double wq = sc * a.tg_w[km];
+                        ar = -wq * vi;
+                        ai = wq * vr;
+                    }
+                    o->re += (T)ar;
+                    o->im += (T)ai;
                     continue;
                 }
                 if (a.basis) {
@@ -2935,6 +2965,11 @@ struct WTerm {
     int k;
     double zc, zh;
     const void *bz;
+};
+
+// Tangent round handed to Nufft3::interp (InterpArgs::tg_w): the round's weights, nullptr for the unweighted round
+struct TanTerm {
+    const double *w;
 };
 
 inline bool rowfft_uses_st(const DimGeom &g, bool col);
@@ -3475,7 +3510,7 @@ class Nufft3 {
                 cplx<T> *out, int64_t out_fg_stride, int64_t out_k_stride,
                 const int64_t *out_pol_off, bool accumulate, const struct BasisTerm *basis = nullptr,
                 int herm = 0, const int *ustart = nullptr, int64_t nuniq = 0, const int *upairs = nullptr,
-                const struct WTerm *wt = nullptr);
+                const struct WTerm *wt = nullptr, const struct TanTerm *tan = nullptr);
 
    private:
     void rowfft(const cplx<T> *in, cplx<T> *out, const DimGeom &g, const cplx<T> *twd,
@@ -3952,7 +3987,7 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
                        const signed char *flip, const double *scale_dev, int nfg, int tpol,
                        cplx<T> *out, int64_t out_fg_stride, int64_t out_k_stride,
                        const int64_t *out_pol_off, bool accumulate, const BasisTerm *basis, int herm,
-                       const int *ustart, int64_t nuniq, const int *upairs, const WTerm *wt) {
+                       const int *ustart, int64_t nuniq, const int *upairs, const WTerm *wt, const TanTerm *tan) {
     if (N == 0 || nfg == 0) return;
     FV_REQUIRE(!upairs || (herm && ustart), "paired runs: packed gathers over run lists");
     if (ustart) N = nuniq;  // items are the distinct targets; bl_idx / flip stay the caller's full list
@@ -4062,6 +4097,20 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
         if (wt)
             kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true, true> : k_interp<T, 2, true, 16, false, true, true>)
                         : (r9 ? k_interp<T, 2, false, 9, false, true, true> : k_interp<T, 2, false, 16, false, true, true>);
+    }
+    if (tan) {  // the tangent epilogue's instantiations (no basis beams, never together with the gradient epilogue)
+        FV_REQUIRE(!basis && !a.gs, "tangent epilogue: no basis term and no gradient epilogue");
+        a.tg_w = tan->w;
+        kern = gdim == 2 ? (herm ? (r9 ? k_interp<T, 2, true, 9, false, false, false, true> : k_interp<T, 2, true, 16, false, false, false, true>)
+                                 : (r9 ? k_interp<T, 2, false, 9, false, false, false, true> : k_interp<T, 2, false, 16, false, false, false, true>))
+                         : (herm ? (r9 ? k_interp<T, 3, true, 9, false, false, false, true> : k_interp<T, 3, true, 16, false, false, false, true>)
+                                 : (r9 ? k_interp<T, 3, false, 9, false, false, false, true> : k_interp<T, 3, false, 16, false, false, false, true>));
+        if (zd)
+            kern = herm ? (r9 ? k_interp<T, 2, true, 9, true, false, false, true> : k_interp<T, 2, true, 16, true, false, false, true>)
+                        : (r9 ? k_interp<T, 2, false, 9, true, false, false, true> : k_interp<T, 2, false, 16, true, false, false, true>);
+        if (wt)
+            kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true, false, true> : k_interp<T, 2, true, 16, false, true, false, true>)
+                        : (r9 ? k_interp<T, 2, false, 9, false, true, false, true> : k_interp<T, 2, false, 16, false, true, false, true>);
     }
     hipLaunchKernelGGL(kern, grid, dim3(INTERP_THREADS), 0, stream, (const cplx<T> *)grid_out, N, bt[0], bt[1], bt[2],
                        bl_idx, flip, scale_dev, a, ker, out, coef, ant1, ant2, ustart, upairs);

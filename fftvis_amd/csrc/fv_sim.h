@@ -1316,6 +1316,126 @@ __global__ void k_srcgrad_reduce(SrcReduceArgs a, const double *__restrict__ acc
 }
 
 // ---------------------------------------------------------------------------------------------
+// Tangent (fv_sim_run_tangent; DESIGN.md "Tangents"), the source side: the change of the visibilities along a change
+// delta_j = P_n dtopo_j of the sources' ENU unit vectors.  With out_k = cj_k( sum_j c_j(n_j) exp(i nu s_k b'_k . x_j) ),
+// x = 2 pi R n,
+//     d out_k = forward of dc_j  +  sum_d i nu b'_k,d (forward of c_j dx_j,d),    dx = 2 pi R delta,
+// (a flipped baseline conjugates -i nu b' X into +i nu b' conj(X): no sign case), so the pass needs 1 + D strength sets.
+// k_strengths' thread mapping (one thread per compacted source and channel); the sets are set_stride elements apart, each
+// in k_strengths' layout, as k_strengths_moments writes its three:
+//     set 0      dc = |delta| (c(n+) - c(n-)) / 2h,  n+- = cos(h) n +- sin(h) delta / |delta|: the beams' change along the
+//                great circle through n towards delta, with c(n) evaluated in fp64 from the catalogue vector
+//                (src_strength_dot's beam and coherency calls, two displaced evaluations), then brought into the
+//                forward's form: pre-phase and Hermitian / all-real packing (the derivative of a Hermitian matrix along a
+//                real direction is Hermitian, that of a real one real); exactly 0 where |delta| = 0;
+//     set 1 + d  the forward's own strengths (strength_eval) times dx_d, d < D (2 on coplanar handles, where b'_z = 0).
+// With height terms the Chebyshev factor of term wt_k multiplies every set.  s carries the beams and flags of a as
+// src_strength_dot reads them, the rotations and the step.  dtopo: this time step's (nsrc, 3) fp64 rows, read at the
+// compacted sources only -- a source below the horizon is in no list and its row is never read.
+template <typename T, int ORD>
+__global__ void k_strengths_tangent(StrengthArgs a, SrcAccArgs s, const int *__restrict__ Mp, const int *__restrict__ perm,
+                                    const int *__restrict__ src_idx, const T *__restrict__ az,
+                                    const T *__restrict__ za, const void *__restrict__ flux,
+                                    const double *__restrict__ freqs, const int *__restrict__ i0s,
+                                    const T *__restrict__ fs, cplx<T> *__restrict__ cs, const T *__restrict__ xyz,
+                                    const T *__restrict__ vec, const double *__restrict__ dtopo) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= min((int64_t)*Mp, a.M) * a.nfg) return;
+    const int64_t p = idx / a.nfg;
+    const int fgi = (int)(idx % a.nfg);
+    const int fidx = a.f_first + fgi;
+    double dot = 0.0;
+    for (int d = 0; d < a.dim; ++d) {
+        const double pos = (double)i0s[(int64_t)d * a.M + p] - (double)fs[(int64_t)d * a.M + p];
+        dot += a.btc[d] * (pos - 0.5 * a.na[d]) * a.h[d];
+    }
+    const double freq = freqs[fidx];
+    cplx<double> pre = {1.0, 0.0};
+    if (dot != 0.0) sincos(freq * dot, &pre.im, &pre.re);
+    const int tp = a.herm ? 2 : a.polarized ? 4 : 1;
+    const int jc = perm[p];
+    const int64_t js = src_idx[jc];
+    cplx<T> *dst = cs + (p * a.nfg + fgi) * tp;
+    cplx<T> *d1 = dst + s.set_stride;
+    strength_eval<T, ORD>(a, jc, fidx, pre, src_idx, az, za, flux, freqs, d1);  // set 1 holds the plain values for now
+    double sc = 1.0;
+    if (a.wt_k > 0) {  // uniform: T_k((z - zc) / zh), as in k_strengths
+        const double t = ((double)xyz[2 * a.M + jc] - a.wt_zc) * a.wt_inv;
+        double prev = 1.0;
+        sc = t;
+        for (int i = 1; i < a.wt_k; ++i) {
+            const double nx = 2.0 * t * sc - prev;
+            prev = sc;
+            sc = nx;
+        }
+    }
+    // n from the catalogue vector in fp64 (k_src_accumulate's), delta = P_n dtopo
+    double nv[3], dl[3];
+    {
+        const double ex = vec[js], ey = vec[s.vstride + js], ez = vec[2 * s.vstride + js];
+        nv[0] = s.rt.m[0] * ex + s.rt.m[1] * ey + s.rt.m[2] * ez;
+        nv[1] = s.rt.m[3] * ex + s.rt.m[4] * ey + s.rt.m[5] * ez;
+        nv[2] = s.rt.m[6] * ex + s.rt.m[7] * ey + s.rt.m[8] * ez;
+        const double rn = 1.0 / sqrt(nv[0] * nv[0] + nv[1] * nv[1] + nv[2] * nv[2]);
+        for (int d = 0; d < 3; ++d) nv[d] *= rn;
+        const double *dt = dtopo + 3 * js;
+        const double rad = nv[0] * dt[0] + nv[1] * dt[1] + nv[2] * dt[2];
+        for (int d = 0; d < 3; ++d) dl[d] = dt[d] - rad * nv[d];
+    }
+    const double twopi = 2.0 * M_PI;
+    const double dx0 = twopi * (s.rp.m[0] * dl[0] + s.rp.m[1] * dl[1] + s.rp.m[2] * dl[2]) * sc;
+    const double dx1 = twopi * (s.rp.m[3] * dl[0] + s.rp.m[4] * dl[1] + s.rp.m[5] * dl[2]) * sc;
+    const double dx2 = twopi * (s.rp.m[6] * dl[0] + s.rp.m[7] * dl[1] + s.rp.m[8] * dl[2]) * sc;
+    for (int r = 0; r < tp; ++r) {
+        const double re = (double)d1[r].re, im = (double)d1[r].im;
+        d1[r] = {(T)(re * dx0), (T)(im * dx0)};
+        d1[s.set_stride + r] = {(T)(re * dx1), (T)(im * dx1)};
+        if (s.D > 2) d1[2 * s.set_stride + r] = {(T)(re * dx2), (T)(im * dx2)};
+    }
+    // set 0: the beam term
+    const double mag = sqrt(dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2]);
+    cplx<double> dc[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+    if (mag > 0.0) {
+        double sh, ch;
+        sincos(s.h, &sh, &ch);
+        const double e0 = dl[0] / mag, e1 = dl[1] / mag;
+        const double wgt = sc * mag * 0.5 / s.h;
+        const cplx<double> Z[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+#pragma unroll 1
+        for (int k = 0; k < 2; ++k) {  // n+, n-: one copy of the beam code
+            const double sg = k ? -sh : sh;
+            cplx<double> c[4];
+            src_strength_dot<T, ORD>(s, fidx, freq, js, ch * nv[0] + sg * e0, ch * nv[1] + sg * e1, flux, Z, c);
+            const double w = k ? -wgt : wgt;
+            for (int r = 0; r < (a.polarized ? 4 : 1); ++r) {
+                dc[r].re += w * c[r].re;
+                dc[r].im += w * c[r].im;
+            }
+        }
+    }
+    if (a.herm == 1) {  // Hermitian: dc_00, dc_11 real, dc_10 = conj dc_01; pre = 1
+        dst[0] = {(T)dc[0].re, (T)dc[3].re};
+        dst[1] = {(T)dc[1].re, (T)dc[1].im};
+    } else if (a.herm == 2) {  // all four real
+        dst[0] = {(T)dc[0].re, (T)dc[3].re};
+        dst[1] = {(T)dc[1].re, (T)dc[2].re};
+    } else {
+        for (int r = 0; r < tp; ++r) {
+            const cplx<double> v = cmul(dc[r], pre);
+            dst[r] = {(T)v.re, (T)v.im};
+        }
+    }
+}
+
+// entries of a fp64 array that are not finite, added to *count (fv_sim_run_tangent's device-side inputs)
+__global__ void k_count_nonfinite(const double *__restrict__ v, int64_t n, int *__restrict__ count) {
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        bad += isfinite(v[i]) ? 0 : 1;
+    if (bad) atomicAdd(count, bad);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Type-1 path (lattice arrays): cpu_nufft2d_type1 (cpu/nufft.py:120-175), set-up
 // cpu_simulate.py:661-681, per-slice :964-965,990-992,259-269.
 // Visibility of the integer baseline (bx, by) at frequency nu is mode (bx, by) of a type-1
@@ -1909,6 +2029,8 @@ struct SimBase {
                                       int gbls_on_device, int accumulate) = 0;
     virtual void run_source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
                                     int gtopo_on_device, int accumulate) = 0;
+    virtual void run_tangent(int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
+                             int dtopo_on_device, void *out, int out_on_device) = 0;
     // Host destination of the next run (fv_sim_run_into): `out` is then a block INSIDE a larger array -- channel f of
     // the block starts f * out_f_stride elements after `out` (0: the block is contiguous) -- and with out_shared other
     // processes write the rest of that array (a sharded run's ranks filling one shared result): the pinning helper must
@@ -2068,6 +2190,7 @@ class Sim : public SimBase {
     DevBuf d_out, d_mhist;
     DevBuf d_adj_g, d_adj_gf;  // adjoint: host G block / host gradient staged on the device
     DevBuf d_adj_gc;           // basis adjoint: host coefficient gradient staged on the device
+    DevBuf d_tan_w, d_tan_dt;  // tangent: the rounds' weights (RunPlan::tan_w), host dtopo staged on the device
     DevBuf d_csr_start, d_csr;  // basis mode: per antenna, its baselines as 2 b + role (k_coef_reduce)
     int nant_basis = 0;
     // sticky device-side error counters, read at every host synchronisation point (check_errors):
@@ -3346,6 +3469,14 @@ class Sim : public SimBase {
         // position adjoint (run_position_adjoint): every strengths launch writes three sets (k_strengths_moments) and
         // every (group, pair, term) runs three rounds of spread -> FFT -> gradient gather, one per set
         bool moments = false;
+        // tangent (run_tangent): the gathers ADD into the output block with the tangent epilogue (k_interp<.., TANGENT>).
+        // tan_w: device (6, nbls) fp64 by global baseline id -- rows 0-2 the weights of the three moments rounds
+        // (R dbls / c), rows 3-5 the baselines' own vectors b' for the source rounds.  tan_sets: strength sets of the
+        // source side (k_strengths_tangent), 1 + tan_D after the moments sets, or 0; tan_dtopo: device (nt, nsrc, 3) fp64.
+        const double *tan_w = nullptr, *tan_dtopo = nullptr;
+        int tan_sets = 0, tan_D = 0;
+        double tan_h = 0.0;
+        int nsets() const { return (moments ? 3 : 0) + tan_sets; }  // strength sets per launch beyond the forward's one (0: the forward)
         // the plan class of height term kt: the run's own plan, or a light class's
         int cls(int kt) const { return k0 > 0 && kt >= k0 ? (kt >= k1 ? 2 : 1) : 0; }
     };
@@ -3661,7 +3792,7 @@ class Sim : public SimBase {
             }
             for (int li = 0; li < r.nlanes_used; ++li) {
                 lanes[li].plan[c]->reserve_buffers(need, na_max, n2_max);
-                lanes[li].plan[c]->strengths_buffer_reserve(r.ch.cap, (int)need_str * (r.moments ? 3 : 1));
+                lanes[li].plan[c]->strengths_buffer_reserve(r.ch.cap, (int)need_str * std::max(1, r.nsets()));
             }
         }
         for (auto &cpo : col_plan_of) cpo.assign(r.groups.size() * pairs.size(), nullptr);
@@ -3696,6 +3827,9 @@ class Sim : public SimBase {
     // gather adds its inner products to the S buffer of its stream -- gs[0] when all big kernels share the main stream,
     // else the lane's.  r.moments (the position adjoint): three rounds per strengths launch, round d on strength set d
     // and into component d of S, (3, r.nf, nbls).
+    // r.tan_w (the tangent): o is the pass's own output block, zeroed, and every round ADDS to it through the tangent
+    // epilogue -- the three moments rounds with the weights of dbls when r.moments, then the r.tan_sets source rounds (the
+    // beam term unweighted, set 1 + d with b'_d); no fused gather (it writes with atomics).
     void queue_units(const RunPlan &r, const OutBlock &o, Drain &dr, cplx<double> *const *gs = nullptr) {
         const int t0 = r.t0, t1 = r.t1, f0 = r.f0, nt = r.nt, D = r.D, nch = r.ch.n;
         const int64_t csz = r.ch.csz, cap = r.ch.cap;
@@ -3789,7 +3923,7 @@ class Sim : public SimBase {
                         L.binned_serial[0] = nufft->geom_serial;
                         // ... and so do its strengths (beam x coherency, pre-phase): they depend on this
                         // step's sources only, not on the previous step's big kernels
-                        launch_strengths(L, r, pr, groups[0].first, groups[0].second - groups[0].first, M, Mps[m], ps);
+                        launch_strengths(L, r, pr, groups[0].first, groups[0].second - groups[0].first, M, Mps[m], ps, 0, nullptr, tu + m);
                         first_pair = &pr;
                         strengths_ahead = true;
                         break;
@@ -3838,14 +3972,15 @@ class Sim : public SimBase {
                         ev_end(e1, ls);
                         // ---- strengths (already queued with the preparation for the first pair) -------
                         if (!(strengths_ahead && &grp == &groups.front() && &pr == first_pair && kt == 0))
-                            launch_strengths(L, r, pr, fa, nfg, M, Mps[m], ls, kt, nf_);
+                            launch_strengths(L, r, pr, fa, nfg, M, Mps[m], ls, kt, nf_, tu + m);
                     }
                     // ---- NUFFT ----------------------------------------------------------
-                    const int nrounds = r.moments ? 3 : 1;
+                    const int nmom = r.moments ? 3 : 0;
+                    const int nrounds = std::max(1, r.nsets());
                     for (int rd = 0; rd < nrounds; ++rd) {
                     for (int m = 0; m < nm; ++m) {
                         Nufft3<T> *P = Ls[m]->plan[c].get();
-                        P->strengths_off = r.moments ? (int64_t)rd * P->M * ntrans : 0;
+                        P->strengths_off = r.nsets() ? (int64_t)rd * P->M * ntrans : 0;
                         P->arm_columns(on ? cp->tab.template as<int>() : nullptr, on ? cp->xtab.template as<int>() : nullptr, tg,
                                        on ? cp->ncc : 0, d_err.as<int>() + 3,
                                        on && cp->omask.p ? cp->omask.template as<unsigned long long>() : nullptr, on ? cp->nblk : 0);
@@ -3875,7 +4010,7 @@ class Sim : public SimBase {
                     // small 2-D grids: the last FFT pass serves the targets from its LDS tiles (no C
                     // buffer, no gather kernel); the output block was zeroed at the start of the run
                     const bool fused =
-                        !gs && !nbasis && !pr.herm && !r.K &&
+                        !gs && !r.tan_w && !nbasis && !pr.herm && !r.K &&
                         nufft->prepare_fused_gather(pr.n, d_bls.as<T>(), d_bls.as<T>() + nbls,
                                                     pr.trivial ? nullptr : pr.idx->template as<int>(),
                                                     pr.trivial ? nullptr : pr.flip->template as<signed char>(),
@@ -3905,6 +4040,9 @@ class Sim : public SimBase {
                     // complex basis beams comes from a second gather at -b (all-real pairs: packed, exact already)
                     const int nparts = nbasis && !reference_compat && pr.bi != pr.bj && !pr.herm ? 2 : 1;
                     const WTerm wterm{kt, r.zc, r.zh, (const void *)(d_bls.as<T>() + 2 * nbls)};
+                    // tangent round rd: a moments round, the beam term's (no weights), or source set 1 + d with b'_d
+                    const TanTerm tterm{rd < nmom ? r.tan_w + (int64_t)rd * nbls
+                                                  : rd == nmom ? nullptr : r.tan_w + (int64_t)(3 + rd - nmom - 1) * nbls};
                     if (!fused)
                         for (int m = 0; m < nm; ++m)
                             for (int part = 1; part <= nparts; ++part) {
@@ -3917,7 +4055,8 @@ class Sim : public SimBase {
                                       d_freqs.as<double>() + fa, nfg, tg, obase + (int64_t)m * per_tf,
                                       o.run, 1, pol_off.data(), accumulate || kt > 0, nbasis || gs ? &bt : nullptr, pr.herm,
                                       pr.ustart ? pr.ustart->template as<int>() : nullptr, pr.upairs ? pr.nitems : pr.nu,
-                                      pr.upairs ? pr.upairs->template as<int>() : nullptr, r.K ? &wterm : nullptr);
+                                      pr.upairs ? pr.upairs->template as<int>() : nullptr, r.K ? &wterm : nullptr,
+                                      r.tan_w ? &tterm : nullptr);
                             }
                     ev_end(e5, ls);
                     for (int m = 0; m < nm; ++m) Ls[m]->plan[c]->strengths_off = 0;
@@ -4811,9 +4950,131 @@ class Sim : public SimBase {
         check_errors();
     }
 
+    // ---- tangent: out = dV, the change of the visibilities along (dbls, dtopo) (DESIGN.md "Tangents") --------------------
+    //     dV = sum_k dV/db_k . dbls[k]  +  sum_{t, j} dV/dn_j(t) . P_n dtopo[t - t0, j]
+    // Both position derivatives of the exact map are forward transforms of other strengths: with b' = R b / c, x = 2 pi R n,
+    //     baselines:  i nu (R dbls[k] / c)_d D'_d[k],             D'_d the forward of the strengths times x_d (k_strengths_moments),
+    //     sources:    forward of dc  +  i nu b'_k,d X_d[k],       X_d the forward of the strengths times dx_d (k_strengths_tangent),
+    // and a flipped baseline needs no sign case.  The pass is run_position_adjoint's: per channel block the forward's own
+    // stages; per (time, chunk, group, pair, height term) one strengths launch per input and 3 and / or 1 + D rounds of
+    // spread -> FFT -> tangent gather (k_interp<.., TANGENT>) ADDING into the zeroed output block.  A time step's slots are
+    // written by its own lane's stream only, in order: no sum over lanes, bitwise reproducible for a lane count.  A host
+    // destination receives the block in one copy at the end.
+    void run_tangent(int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
+                     int dtopo_on_device, void *out, int out_on_device) override {
+        FV_HIP(hipSetDevice(device));
+        FV_REQUIRE(!type1, "the tangent runs the type-3 transform: set the array with fv_sim_set_array, not "
+                           "fv_sim_set_array_type1 (a lattice form of the pass does not exist)");
+        FV_REQUIRE(nbasis == 0, "the tangent does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        FV_REQUIRE(dbls || dtopo, "neither tangent input is given (dbls and dtopo are both null)");
+        check_run(t0, t1, f0, f1);
+        const int nt = t1 - t0, nf = f1 - f0;
+        const int64_t per_tf = (int64_t)tpol * nbls;
+        // an earlier run may have the lanes busy
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipStreamSynchronize(prep_stream));
+        if (copy_stream) FV_HIP(hipStreamSynchronize(copy_stream));
+        for (int li = 1; li < 4; ++li)
+            if (lanes[li].stream && lanes[li].own_stream) FV_HIP(hipStreamSynchronize(lanes[li].stream));
+        // the weights: rows 0-2 R dbls / c (seconds, the transforms' frame), rows 3-5 the baselines' own vectors
+        std::vector<double> w((size_t)6 * std::max<int64_t>(nbls, 1), 0.0);
+        if (dbls && nbls > 0) {
+            std::vector<double> hb((size_t)3 * nbls);
+            if (dbls_on_device)
+                FV_HIP(hipMemcpy(hb.data(), dbls, sizeof(double) * hb.size(), hipMemcpyDeviceToHost));
+            else
+                std::memcpy(hb.data(), dbls, sizeof(double) * hb.size());
+            for (double v : hb) FV_REQUIRE(std::isfinite(v), "dbls holds a value that is not finite");
+            for (int64_t k = 0; k < nbls; ++k)
+                for (int d = 0; d < 3; ++d)
+                    w[(size_t)d * nbls + k] = (rplane.m[3 * d] * hb[3 * k] + rplane.m[3 * d + 1] * hb[3 * k + 1] +
+                                               rplane.m[3 * d + 2] * hb[3 * k + 2]) / SPEED_OF_LIGHT;
+        }
+        for (int64_t i = 0; i < 3 * nbls; ++i) w[(size_t)3 * nbls + i] = h_bls[i];
+        upload(d_tan_w, w.data(), sizeof(double) * w.size(), 0);
+        const double *ddt = nullptr;
+        const int64_t dt_elems = (int64_t)nt * nsrc * 3;
+        if (dtopo) {
+            ddt = dtopo;
+            if (!dtopo_on_device) {
+                upload(d_tan_dt, dtopo, sizeof(double) * (size_t)dt_elems, 0);
+                ddt = d_tan_dt.as<double>();
+            }
+            if (dt_elems > 0) {  // a value that is not finite fails the call before anything runs
+                hipLaunchKernelGGL(k_count_nonfinite, dim3((unsigned)std::min<int64_t>(cdiv(dt_elems, 256), 4096)), dim3(256), 0, stream,
+                                   ddt, dt_elems, d_err.as<int>() + 4);
+                int bad = 0;
+                FV_HIP(hipMemcpyAsync(&bad, d_err.as<int>() + 4, sizeof(int), hipMemcpyDeviceToHost, stream));
+                FV_HIP(hipStreamSynchronize(stream));
+                if (bad) {
+                    FV_HIP(hipMemsetAsync(d_err.as<int>() + 4, 0, sizeof(int), stream));
+                    FV_HIP(hipStreamSynchronize(stream));
+                    throw Error(FV_ERR_ARG, std::to_string(bad) + " entries of dtopo are not finite");
+                }
+            }
+        }
+        OutBlock o = out_block(nt, nf, out, out_on_device);  // on the device, zeroed
+        o.drain = false;
+        const char *eab = std::getenv("FFTVIS_HIP_ADJ_ACC_BYTES");  // channel blocks as the position pass cuts them
+        const double acc_max = eab ? std::atof(eab) : 256.0 * 1024 * 1024;
+        const double per_chan = 16.0 * 3 * (double)std::max<int64_t>(nbls, 1);
+        const int nfb = (int)std::max<double>(1.0, std::min<double>(nf, std::floor(acc_max / per_chan)));
+        for (int b0 = f0; b0 < f1 && nt > 0 && nbls > 0; b0 += nfb) {
+            const int b1 = std::min(f1, b0 + nfb), nfa = b1 - b0;
+            if (mhist_log.size() > 65536) mhist_log.clear();
+            RunPlan r{t0, t1, b0, b1, nt, nfa};
+            r.moments = dbls != nullptr;
+            r.tan_w = d_tan_w.as<double>();
+            if (ddt) {
+                r.tan_dtopo = ddt;
+                r.tan_D = dim();
+                r.tan_sets = 1 + r.tan_D;
+                r.tan_h = sizeof(T) == 8 ? SRC_BEAM_STEP_FP64 : SRC_BEAM_STEP_FP32;
+                if (const char *eh = std::getenv("FFTVIS_HIP_SRC_BEAM_STEP")) r.tan_h = std::atof(eh);  // (measurements)
+                FV_REQUIRE(r.tan_h > 0.0 && r.tan_h < 1e-2, "FFTVIS_HIP_SRC_BEAM_STEP out of range");
+            }
+            source_box(r.xc, r.X);
+            height_terms(r);
+            pair_setup(r);
+            grid_and_groups(r);
+            light_classes(r);
+            lane_schedule(r);
+            lane_plans(r);
+            r.ch = source_chunks(r.nlanes_used);
+            lane_buffers(r);
+            OutBlock ob = o;  // this block's channels of the output
+            ob.nf = nfa;
+            ob.dout = o.dout + (int64_t)(b0 - f0) * nt * per_tf;
+            ob.bytes = sizeof(cplx<T>) * (size_t)nfa * o.run;
+            Drain dr;
+            queue_units(r, ob, dr);
+        }
+        if (!o.on_device) copy_block_to_host(o, false, stream);
+        FV_HIP(hipStreamSynchronize(stream));
+        if (timing_level) ev_collect();
+        // the strength sets and the staged inputs belong to this pass: beyond the keep limit they go back (the next run's
+        // lane_buffers sizes the strength buffers again before it queues anything)
+        {
+            size_t str = d_tan_dt.cap + d_tan_w.cap;
+            for (Lane &L : lanes)
+                for (auto &P : L.plan)
+                    if (P) str += P->strengths.cap;
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            if ((double)str > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
+                for (Lane &L : lanes)
+                    for (auto &P : L.plan)
+                        if (P) P->strengths.release();
+                d_tan_dt.release();
+                d_tan_w.release();
+            }
+        }
+        adjoint_release();
+        check_errors();
+    }
+
     // beam x coherency strengths of one (frequency group, beam pair) for the lane's current sources
     void launch_strengths(Lane &L, const RunPlan &r, const Pair &pr, int fa, int nfg, int64_t M, const int *Mp, hipStream_t on,
-                          int wt_k = 0, Nufft3<T> *plan = nullptr) {
+                          int wt_k = 0, Nufft3<T> *plan = nullptr, int t = 0) {
         Nufft3<T> *nufft = plan ? plan : L.plan[0].get();
         const int D = r.D;
         RoctxRange rr("strengths");
@@ -4840,15 +5101,45 @@ class Sim : public SimBase {
         sa.wt_zc = r.zc;
         sa.wt_inv = r.zh > 0 ? 1.0 / r.zh : 0.0;
         const int ntrans = nfg * (pr.herm ? 2 : tpol);
-        if (r.moments) {  // the position adjoint's three sets, each M * ntrans elements
-            cplx<T> *cs3 = nufft->strengths_buffer(3 * ntrans);
-            hipLaunchKernelGGL((beam_order == 3 ? k_strengths_moments<T, 3> : beam_order == 1 ? k_strengths_moments<T, 1>
-                                                                                            : k_strengths_moments<T, 0>),
-                               dim3(cdiv((int64_t)M * nfg, 256)), dim3(256), 0, on, sa, Mp,
-                               nufft->perm.template as<int>(), L.d_srcidx.template as<int>(),
-                               L.d_az.template as<T>(), L.d_za.template as<T>(), d_flux.p, d_freqs.as<double>(),
-                               nufft->i0s.template as<int>(), nufft->fs.template as<T>(), cs3,
-                               (const T *)L.d_xyz.template as<T>(), (int64_t)nufft->M * ntrans);
+        if (r.nsets()) {  // the position adjoint's and the tangent's sets, each M * ntrans elements: moments, then the source side's
+            cplx<T> *cs3 = nufft->strengths_buffer(r.nsets() * ntrans);
+            const int64_t set_stride = (int64_t)nufft->M * ntrans;
+            if (r.moments) {
+                hipLaunchKernelGGL((beam_order == 3 ? k_strengths_moments<T, 3> : beam_order == 1 ? k_strengths_moments<T, 1>
+                                                                                                : k_strengths_moments<T, 0>),
+                                   dim3(cdiv((int64_t)M * nfg, 256)), dim3(256), 0, on, sa, Mp,
+                                   nufft->perm.template as<int>(), L.d_srcidx.template as<int>(),
+                                   L.d_az.template as<T>(), L.d_za.template as<T>(), d_flux.p, d_freqs.as<double>(),
+                                   nufft->i0s.template as<int>(), nufft->fs.template as<T>(), cs3,
+                                   (const T *)L.d_xyz.template as<T>(), set_stride);
+            }
+            if (r.tan_sets) {
+                SrcAccArgs aa{};
+                aa.M = M;
+                aa.nfreq = nfreq_cat;
+                aa.polarized = polarized;
+                aa.pol_sky = pol_sky;
+                aa.same_beam = pr.bi == pr.bj;
+                aa.D = r.tan_D;
+                aa.set_stride = set_stride;
+                aa.vstride = nsrc;
+                aa.bi = sa.bi;
+                aa.bj = sa.bj;
+                aa.rt = rots[t];
+                aa.rp = rplane;
+                aa.h = r.tan_h;
+                // the vectors horizon_step read for this time step (run_source_adjoint's choice)
+                const T *vec = !astroms.empty() ? L.d_enu.template as<T>()
+                                                : ntimes_topo ? d_topo.as<T>() + (size_t)t * 3 * nsrc : d_eq.as<T>();
+                hipLaunchKernelGGL((beam_order == 3 ? k_strengths_tangent<T, 3> : beam_order == 1 ? k_strengths_tangent<T, 1>
+                                                                                                : k_strengths_tangent<T, 0>),
+                                   dim3(cdiv((int64_t)M * nfg, 256)), dim3(256), 0, on, sa, aa, Mp,
+                                   nufft->perm.template as<int>(), L.d_srcidx.template as<int>(),
+                                   L.d_az.template as<T>(), L.d_za.template as<T>(), d_flux.p, d_freqs.as<double>(),
+                                   nufft->i0s.template as<int>(), nufft->fs.template as<T>(),
+                                   cs3 + (r.moments ? 3 : 0) * set_stride, (const T *)L.d_xyz.template as<T>(), vec,
+                                   r.tan_dtopo + (size_t)(t - r.t0) * 3 * nsrc);
+            }
             ev_end(e2, on);
             return;
         }

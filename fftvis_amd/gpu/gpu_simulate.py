@@ -285,6 +285,17 @@ class SimHandle:
         tp, t_dev = _buffer_addr(gtopo)
         _lib.check(self._L.fv_sim_run_source_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, tp, t_dev, int(bool(accumulate))))
 
+    def run_tangent(self, t0, t1, f0, f1, dbls, dtopo, out):
+        """``out =`` the tangent of the visibilities along ``dbls`` and / or ``dtopo`` for times [t0,t1) x freqs [f0,f1)
+        (``fv_sim_run_tangent``).  ``dbls``: C-contiguous (nbls, 3) float64, metres, in the frame the antenna positions
+        were given in; ``dtopo``: C-contiguous (t1 - t0, nsrc, 3) float64, ENU; either may be None, not both.  ``out``:
+        C-contiguous block of ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype, overwritten.  numpy arrays are
+        host buffers, torch tensors device buffers.  The call synchronises."""
+        bp, b_dev = _buffer_addr(dbls)
+        tp, t_dev = _buffer_addr(dtopo)
+        op, o_dev = _buffer_addr(out)
+        _lib.check(self._L.fv_sim_run_tangent(self._h, t0, t1, f0, f1, bp, b_dev, tp, t_dev, op, o_dev))
+
     def run_device(self, t0, t1, f0, f1, out_ptr):
         """Enqueue only; ``out_ptr`` is a device buffer of out_shape() complex elements."""
         _lib.check(self._L.fv_sim_run(self._h, t0, t1, f0, f1, _lib.ptr(out_ptr), 1))
@@ -408,6 +419,7 @@ class GPUSimulationEngine(SimulationEngine):
         adjoint_of: tuple = None,
         adjoint_path: str = "type3",
         adjoint_wrt: str = "fluxes",
+        tangent_of: tuple = None,
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -485,7 +497,18 @@ class GPUSimulationEngine(SimulationEngine):
           the roles swapped; ``"type2"`` the transpose of the lattice path's type-1 slice -- ValueError when these
           arguments do not take the lattice path (not griddable, not flat, ``force_use_type3``, basis beams);
           ``"auto"`` type 2 exactly where the forward takes type 1, type 3 elsewhere.
+        * ``tangent_of`` (extra; what ``simulate_vis_jvp`` passes): a triple ``(dbls, dtopo, dv)`` -- instead of simulating,
+          the engine fills ``dv`` (the result's shape, this precision's complex dtype) with the tangent of its
+          visibilities along a change ``dbls`` (nbls, 3) of the baseline vectors and / or ``dtopo`` (ntimes, nsrc, 3) of
+          the sources' ENU unit vectors, either None (``SimHandle.run_tangent``), and returns it.  Time blocks take
+          consecutive rows of ``dtopo``.  The pass runs the type-3 transform only: ValueError on the lattice path (pass
+          ``force_use_type3=True``) and with ``beam_coefs``.
         """
+        if tangent_of is not None:
+            if adjoint_of is not None:
+                raise ValueError("pass either adjoint_of or tangent_of, not both")
+            if beam_coefs is not None:
+                raise ValueError("the tangent does not cover basis beams (beam_coefs)")
         if adjoint_path not in ADJOINT_PATHS:
             raise ValueError(f"adjoint_path must be one of {ADJOINT_PATHS}, got {adjoint_path!r}")
         if adjoint_wrt not in ("fluxes", "positions", "sources"):
@@ -574,6 +597,8 @@ class GPUSimulationEngine(SimulationEngine):
             raise ValueError("the position adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if sources and is_gridded:
             raise ValueError("the source adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
+        if tangent_of is not None and is_gridded:
+            raise ValueError("the tangent runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if adjoint_path == "type2" and not is_gridded:
             raise ValueError(
                 "adjoint_path='type2' needs the lattice path: a flat, griddable array without force_use_type3 and "
@@ -637,6 +662,10 @@ class GPUSimulationEngine(SimulationEngine):
                 result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr,
                                       gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis, positions=positions,
                                       sources=sources)
+                ok = True
+                return result
+            if tangent_of is not None:
+                result = _run_tangent(h, tangent_of[0], tangent_of[1], tangent_of[2], t0, t1, f0, f1, nblk_t, coord_mgr)
                 ok = True
                 return result
             if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != complex_dtype):
@@ -783,6 +812,38 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, ba
             if out is not None:
                 out[...] = 0
     return (gflux, gcoefs) if basis else gflux
+
+
+def _run_tangent(h, dbls, dtopo, dv, t0, t1, f0, f1, nblk_t, coord_mgr):
+    """The tangent's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors); every block's
+    ``run_tangent`` takes its rows of ``dtopo`` and fills its slice of ``dv`` (a block that is not the whole result goes
+    through a contiguous temporary).  Every call ends synchronised."""
+    on_device = not isinstance(dv, np.ndarray)
+    step = max(nblk_t, 1)
+    for tb in range(t0, t1, step):
+        te = min(t1, tb + step)
+        whole = tb == t0 and te == t1
+        rows = None if dtopo is None else dtopo[tb - t0:te - t0]  # rows of a C-contiguous array: a contiguous view
+        if whole:
+            blk = dv
+        elif on_device:
+            import torch
+
+            blk = torch.empty_like(dv[:, tb - t0:te - t0], memory_format=torch.contiguous_format)
+            torch.cuda.synchronize(blk.device)
+        else:
+            blk = np.empty(dv[:, tb - t0:te - t0].shape, dtype=dv.dtype)
+        if coord_mgr is not None:
+            h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
+            ta, te_ = 0, te - tb
+        else:
+            ta, te_ = tb, te
+        h.run_tangent(ta, te_, f0, f1, dbls, rows, blk)
+        if not whole:
+            dv[:, tb - t0:te - t0] = blk
+    if t1 <= t0:
+        dv[...] = 0
+    return dv
 
 
 def _time_block(device, nt, nf, nbls, polarized, precision, nsrc_topo=0):

@@ -312,6 +312,36 @@ int fv_sim_run_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const
  * basis beams, a null pointer, a flag other than 0 or 1 and NaN in G fail with FV_ERR_ARG.                              */
 int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
                               int gtopo_on_device, int accumulate);
+/* Forward-mode tangent (Jacobian-vector product) of fv_sim_run's visibilities along a change of the baseline vectors
+ * and / or of the sources' directions, for times [t0, t1) x freqs [f0, f1):
+ *     out = dV = sum_k dV/db_k . dbls[k]  +  sum_{t,j} dV/dn_j(t) . P_n dtopo[t - t0, j],     P_n = 1 - n n^T.
+ * With out_k = cj_k( sum_j c_j(n_j) exp(i nu s_k b'_k . x_j) ), b' = R b / c, x = 2 pi R n as above, both derivatives of
+ * the exact map are forward transforms of other strengths:
+ *     baselines:  dV[.., k] += sum_d i nu_f (R dbls[k] / c)_d D'_d[.., k],   D'_d the forward of the strengths times x_j,d,
+ *     sources:    dV[.., k] += forward of dc_j  +  sum_d i nu_f b'_k,d (forward of c_j dx_j,d),     dx = 2 pi R P_n dtopo,
+ * dc_j = |delta| (c(n+) - c(n-)) / 2h the beams' change along the great circle through n towards delta = P_n dtopo, n+- =
+ * cos(h) n +- sin(h) delta / |delta|, evaluated in fp64 (two displaced beam evaluations per source and channel; exactly 0
+ * where delta = 0).  A flipped baseline conjugates -i nu b' X into +i nu b' conj(X): neither part has a sign case.  It is
+ * the tangent of the smooth exact map, whichever path the forward takes, for both fv_sim_set_reference_compat forms, and
+ * the transpose of the two gradients above:  Re <dV, G> = sum dbls . gbls + sum dtopo . gtopo  for EVERY input (P_n removes
+ * the radial part of dtopo), with gbls and gtopo those of fv_sim_run_position_adjoint and fv_sim_run_source_adjoint.
+ * out: complex of the handle's precision in fv_sim_run's layout for that block, always overwritten (no accumulate flag).
+ * dbls: (nbls, 3) float64 in metres, in the frame of the vectors b whose image R b / c fv_sim_set_array received (the frame
+ * gbls comes back in); every listed baseline is an independent vector.  dtopo: (t1 - t0, nsrc, 3) float64, ENU.  Either
+ * input may be NULL -- its rounds do not run --, not both.  A source below the horizon at time t contributes exactly 0
+ * there and its dtopo row is not read (the cut is not differentiated).  On a coplanar handle the up component of dbls
+ * still enters (D'_z weights by the sources' height coordinate), and the source side runs D = 2 sets, since b'_z = 0.
+ * The *_on_device flags as in fv_sim_run (device buffers must be complete when the call is made); the call synchronises.
+ * The pass is a forward run per channel block: per (time, source chunk, frequency group, beam pair, height term) one
+ * strengths launch per input, then 3 and / or 1 + D rounds of spread, FFT and a gather that ADDS i nu_f w V (or V, the
+ * beam term) into the zeroed output block, one owner thread per slot.  No atomics, one lane per time step: bitwise
+ * reproducible for a given FFTVIS_HIP_LANES.  A host destination receives the block in one copy at the end.  Memory is
+ * given back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule of fv_sim_run_adjoint.  FFTVIS_HIP_SRC_BEAM_STEP overrides the step
+ * h (radians; for measurements).  A lattice handle (fv_sim_set_array_type1), a handle with basis beams, a null handle, a
+ * null out, both inputs NULL, a flag other than 0 or 1 and a value in either input that is not finite (detected before
+ * anything runs; the handle stays usable) fail with FV_ERR_ARG.                                                          */
+int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
+                       int dtopo_on_device, void *out, int out_on_device);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2
