@@ -22,6 +22,7 @@ from .adjoint import (  # noqa: F401
     radec_jacobian,
     simulate_vis_adjoint,
     simulate_vis_basis_adjoint,
+    simulate_vis_basis_jvp,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,
     simulate_vis_source_adjoint,

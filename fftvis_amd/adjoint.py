@@ -19,7 +19,9 @@ coordinates (``fv_sim_run_position_adjoint``).
 
 The other product, J v, is ``simulate_vis_jvp``: the forward-mode tangent of the visibilities along a change of the
 antenna positions, the source positions and the fluxes (``fv_sim_run_tangent``), which the three torch operations
-also offer to ``torch.autograd.forward_ad`` through their ``jvp``.
+also offer to ``torch.autograd.forward_ad`` through their ``jvp``.  Basis beams have their own,
+``simulate_vis_basis_jvp``: the tangent along directions of the coefficients and of the fluxes
+(``fv_sim_run_basis_tangent``), several directions per call, and the ``jvp`` of ``torch_simulate_vis_basis``.
 """
 
 from __future__ import annotations
@@ -405,6 +407,7 @@ def _basis_autograd_function():
             ctx.flux_dtype, ctx.coef_dtype = fluxes.dtype, beam_coefs.dtype
             ctx.coef_device = beam_coefs.device
             ctx.save_for_backward(fluxes, beam_coefs)
+            ctx.save_for_forward(fluxes, beam_coefs)
             vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(),
                                beam_coefs=beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy(), **kwargs)
             return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
@@ -425,6 +428,17 @@ def _basis_autograd_function():
                 out.append(None if g is None else g.to(device=dev, dtype=dt))
             return out[0], out[1], None
 
+        @staticmethod
+        def jvp(ctx, d_fluxes, d_beam_coefs, *_):
+            # a missing tangent (None) skips its part
+            fluxes, beam_coefs = ctx.saved_tensors
+            if d_fluxes is None and d_beam_coefs is None:
+                return None
+            dv = simulate_vis_basis_jvp(fluxes=fluxes, beam_coefs=beam_coefs,
+                                        d_beam_coefs=None if d_beam_coefs is None else d_beam_coefs.detach(),
+                                        d_fluxes=None if d_fluxes is None else d_fluxes.detach(), **ctx.kwargs)
+            return _tangent_tensor(dv, fluxes)
+
     return _SimulateVisBasis
 
 
@@ -438,12 +452,199 @@ def torch_simulate_vis_basis(fluxes, beam_coefs, **kwargs):
     tensor on ``fluxes``' device.  The backward pass is ``simulate_vis_basis_adjoint`` of the incoming gradient, with only
     the gradients autograd asks for (``ctx.needs_input_grad``): Re(A^H g) for the real fluxes, and for the complex
     coefficients torch's convention for a complex leaf, dL = Re sum conj(grad) dC.  Forward-mode differentiation
-    (``torch.autograd.forward_ad``) is not covered here: the operation defines no ``jvp`` (``simulate_vis_jvp`` does not
-    take ``beam_coefs``)."""
+    (``torch.autograd.forward_ad``) goes through the operation's ``jvp``: ``simulate_vis_basis_jvp`` on the tangents
+    present, a missing one skipping its part."""
     global _FN_BASIS
     if _FN_BASIS is None:
         _FN_BASIS = _basis_autograd_function()
     return _FN_BASIS.apply(fluxes, beam_coefs, kwargs)
+
+
+# device bytes of one call's (ndir, ...) output: longer stacks of directions are cut into groups under it
+BASIS_TANGENT_BYTES_ENV = "FFTVIS_BASIS_TANGENT_BYTES"
+BASIS_TANGENT_BYTES_DEFAULT = 1 << 30
+
+
+def simulate_vis_basis_jvp(
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    beam_coefs,
+    telescope_loc,
+    *,
+    d_beam_coefs=None,
+    d_fluxes=None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = True,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """Forward-mode tangent (Jacobian-vector product) of the basis-beam simulation ``simulate_vis(..., beam=<K basis
+    beams>, beam_coefs=C)`` along directions of the coefficients and of the fluxes,
+
+        dV = dV[C; d_beam_coefs]  +  dV/d(fluxes) . d_fluxes,
+        dV_b[C; D] = sum_kl ( conj(D[a1,k]) C[a2,l] + conj(C[a1,k]) D[a2,l] ) M_kl(b),
+
+    M_kl the visibilities of basis beams k and l.  They depend on neither C nor D, so the coefficient part is one forward
+    run whose gather carries the differentiated weights (``fv_sim_run_basis_tangent``), and any number of directions share
+    its transforms.  It is the transpose of ``simulate_vis_basis_adjoint``: for every G,
+    ``Re <dV, G> = Re <d_beam_coefs, gcoefs> + <d_fluxes, gflux>``.
+
+    * ``d_beam_coefs``: complex, (nant, nbasis, nfreqs) -- the result has ``simulate_vis``'s shape and dtype -- or a stack
+      (ndir, nant, nbasis, nfreqs) -- the result gains a leading ``ndir`` axis, direction q equal, bit for bit, to the call
+      on ``d_beam_coefs[q]`` alone.  A long stack is cut into groups whose device output stays under
+      ``FFTVIS_BASIS_TANGENT_BYTES`` (default 1 GiB); every group is one forward run.
+    * ``d_fluxes``: ``fluxes``' shape.  The map is linear in the fluxes, so this part is one ``simulate_vis(...,
+      beam_coefs=C)`` run on ``d_fluxes``, added to the rest.  It combines with an unbatched ``d_beam_coefs`` only: with a
+      stack it is a ValueError (flux directions are plain forward runs).
+
+    No input at all gives zeros.  numpy arrays, or torch tensors: when a tangent is a tensor on the run's device
+    ``d_beam_coefs`` is handed over by pointer and the result is a tensor on that device; host tensors in, a host tensor
+    out.  Every other keyword means what it means for ``simulate_vis``, ``reference_compat`` included.  ``polarized`` must
+    be True and ``beam_idx`` None, as for the forward."""
+    import os
+
+    if backend != "gpu":
+        raise ValueError(f"Unsupported backend: {backend}")
+    if beam_coefs is None:
+        raise ValueError("simulate_vis_basis_jvp needs beam_coefs (simulate_vis_jvp covers per-antenna beam_idx)")
+    if not polarized:  # the forward's message
+        raise ValueError(
+            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
+        )
+    if eps is None:
+        eps = default_accuracy_dict[precision]
+    ants = {k: np.array(v) for k, v in ants.items()}
+    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
+    if _is_tensor(beam_coefs):
+        beam_coefs = beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy()
+    beam_coefs = np.asarray(beam_coefs)
+    validate_beam_idx(beam_idx, beam_coefs, len(beam_list), len(ants))
+    feed_index(use_feed)
+    if baselines is None:
+        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
+    nsrc = int(np.size(ra))
+    nfreqs = int(np.size(freqs))
+    ntimes = len(julian_dates(times))
+    nbls = len(baselines)
+    c_shape = (len(ants), len(beam_list), nfreqs)
+    if beam_coefs.shape != c_shape:
+        raise ValueError("beam_coefs must have shape (nant, nbasis, nfreqs)")
+    if _is_tensor(fluxes):
+        fluxes = fluxes.detach().cpu().numpy()
+    fluxes = np.asarray(fluxes)
+    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
+        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
+    if d_fluxes is not None and tuple(d_fluxes.shape) != fluxes.shape:
+        raise ValueError(f"d_fluxes must have fluxes' shape {fluxes.shape}, got {tuple(d_fluxes.shape)}")
+    stacked = False
+    if d_beam_coefs is not None:
+        dshape = tuple(d_beam_coefs.shape)
+        if dshape != c_shape and not (len(dshape) == 4 and dshape[0] >= 1 and dshape[1:] == c_shape):
+            raise ValueError(f"d_beam_coefs must have beam_coefs' shape {c_shape} or (ndir,) + that shape, got {dshape}")
+        stacked = len(dshape) == 4
+        if not (np.iscomplexobj(d_beam_coefs) if not _is_tensor(d_beam_coefs) else d_beam_coefs.is_complex()):
+            raise ValueError("d_beam_coefs must be complex, like beam_coefs")
+        if stacked and d_fluxes is not None:
+            raise ValueError("d_fluxes combines with one direction of the coefficients only, not with a stack "
+                             "(flux directions are plain simulate_vis runs)")
+    try:
+        budget = float(os.environ.get(BASIS_TANGENT_BYTES_ENV, BASIS_TANGENT_BYTES_DEFAULT))
+    except ValueError:
+        raise ValueError(f"{BASIS_TANGENT_BYTES_ENV} must be a number of bytes") from None
+    tangents = (d_beam_coefs, d_fluxes)
+    any_tensor = any(_is_tensor(x) for x in tangents)
+    dev_tensor = next((x for x in tangents if _is_tensor(x) and x.device.type == "cuda"), None)
+    on_device = dev_tensor is not None
+    if on_device and (dev_tensor.device.index or 0) != int(device):
+        raise ValueError(f"a tangent lives on {dev_tensor.device}, the run is on cuda:{int(device)}")
+    rdt = np.float32 if precision == 1 else np.float64
+    cdt = np.complex64 if precision == 1 else np.complex128
+    shape = (nfreqs, ntimes, 2, 2, nbls)
+    ndir = int(d_beam_coefs.shape[0]) if stacked else 1
+
+    def host(x):
+        return x.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+
+    common = dict(
+        ants=ants, ra=ra, dec=dec, freqs=freqs, times=times, telescope_loc=telescope_loc,
+        baselines=baselines, precision=precision, polarized=True, eps=eps, upsample_factor=upsample_factor,
+        beam_spline_opts=beam_spline_opts, use_feed=use_feed, flat_array_tol=flat_array_tol,
+        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
+        coord_method=coord_method, coord_method_params=coord_method_params, force_use_type3=force_use_type3,
+        force_use_ray=force_use_ray, trace_mem=trace_mem, source_buffer=source_buffer, coord_mgr=coord_mgr,
+        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
+    )
+    if on_device:
+        import torch
+
+        tdev = dev_tensor.device
+        tc = torch.complex64 if precision == 1 else torch.complex128
+        dv = torch.zeros((ndir,) + shape, dtype=tc, device=tdev)
+        dd = None
+        if d_beam_coefs is not None:
+            dd = d_beam_coefs.detach() if _is_tensor(d_beam_coefs) else torch.from_numpy(np.ascontiguousarray(d_beam_coefs))
+            dd = dd.to(device=tdev, dtype=tc).resolve_conj().resolve_neg().reshape((ndir,) + c_shape).contiguous()
+    else:
+        dv = np.zeros((ndir,) + shape, dtype=cdt)
+        dd = None if d_beam_coefs is None else np.ascontiguousarray(host(d_beam_coefs), dtype=cdt).reshape((ndir,) + c_shape)
+    if dd is not None:
+        if on_device:
+            torch.cuda.synchronize(tdev)  # the library's streams do not follow torch's: the inputs and dv are complete
+        from .wrapper import create_simulation_engine, device_chunks
+
+        engine = create_simulation_engine(backend=backend, device=device)
+        nchunks = device_chunks(device, max_memory, min_chunks, beam_list, 2, 2, len(ants), nsrc, precision,
+                                source_buffer, nfreqs)
+        per_dir = int(np.prod(shape)) * np.dtype(cdt).itemsize
+        group = int(max(1, min(ndir, budget // max(per_dir, 1))))
+        for q0 in range(0, ndir, group):
+            q1 = min(ndir, q0 + group)
+            engine.simulate(fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=None, nchunks=nchunks,
+                            beam_coefs=beam_coefs.astype(cdt, copy=False), basis_tangent_of=(dd[q0:q1], dv[q0:q1]),
+                            **common)
+    if d_fluxes is not None:
+        from .wrapper import simulate_vis
+
+        vf = simulate_vis(fluxes=host(d_fluxes).astype(rdt, copy=False), beam=beam_list, beam_coefs=beam_coefs,
+                          backend=backend, max_memory=max_memory, min_chunks=min_chunks, device=device, **common)
+        if on_device:
+            dv[0] += torch.from_numpy(np.ascontiguousarray(vf)).to(dv.device)
+        else:
+            dv[0] += vf
+    if not stacked:
+        dv = dv[0]
+    if any_tensor and not on_device:  # host tensors in, a host tensor out
+        import torch
+
+        dv = torch.from_numpy(np.ascontiguousarray(dv))
+    return dv
 
 
 def baseline_to_antenna_gradient(gbls, ants: dict, baselines: list):

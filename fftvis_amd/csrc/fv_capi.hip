@@ -652,6 +652,18 @@ int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *
         h->impl->run_tangent(t0, t1, f0, f1, dbls, dbls_on_device, dtopo, dtopo_on_device, out, out_on_device);
     });
 }
+int fv_sim_run_basis_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir,
+                             void *out, int out_on_device) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(out, "null output");
+        FV_REQUIRE(dcoefs, "null coefficient directions (dcoefs)");
+        FV_REQUIRE(ndir >= 1, "ndir must be at least 1");
+        FV_REQUIRE((dcoefs_on_device == 0 || dcoefs_on_device == 1) && (out_on_device == 0 || out_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_basis_tangent(t0, t1, f0, f1, dcoefs, dcoefs_on_device, ndir, out, out_on_device);
+    });
+}
 int fv_sim_sync(fv_sim *h) { FV_SIM_CALL(h->impl->sync()); }
 int fv_sim_stats(fv_sim *h, double *vals, int n) { FV_SIM_CALL(h->impl->stats(vals, n)); }
 int fv_sim_reset_stats(fv_sim *h) { FV_SIM_CALL(h->impl->reset_stats()); }

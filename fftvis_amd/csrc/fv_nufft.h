@@ -2447,6 +2447,17 @@ struct InterpArgs {
     //     V                     (tg_w == nullptr: the beam term's round).
     // A pair's list holds every baseline once: one owner thread per slot and launch, plain read-modify-write.
     const double *tg_w;
+    // Basis tangent epilogue (k_interp<.., BTAN>; Sim::run_basis_tangent): the forward's basis epilogue with differentiated
+    // weights.  Where the forward adds w1 V / w2 V, every direction q < bt_ndir adds, with D_q = bt_d + q bt_d_stride laid
+    // out like the coefficients,
+    //     w1' = conj(D_q[a1,kk]) C[a2,ll] + conj(C[a1,kk]) D_q[a2,ll]      at the member's slot,
+    //     w2' = conj(D_q[a1,ll]) C[a2,kk] + conj(C[a1,ll]) D_q[a2,kk]      at the feed-transposed slot (kk != ll),
+    // times V into direction q's copy of the output block (out + q bt_out_stride); basis_part and negate_all as in the
+    // forward.  The weights are summed in fp64 BEFORE the product with V: directions whose two halves cancel (D = i C)
+    // cancel at rounding level.  One owner thread per slot and launch: plain read-modify-write.
+    const void *bt_d;
+    int bt_ndir;
+    int64_t bt_d_stride, bt_out_stride;
 };
 
 // Bessel function of the first kind and integer order k >= 0 by its power series, (x / 2)^k / k! sum_m (-x^2 / 4)^m /
@@ -2480,6 +2491,14 @@ __device__ inline cplx<double> wterm_factor(int k, double zc, double zh, double 
     }
 }
 
+// conj(d1) c2 + conj(c1) d2 in fp64: the derivative of the basis weight conj(c1) c2 along (d1, d2) (k_interp<.., BTAN>)
+template <typename T>
+__device__ inline cplx<double> btan_weight(cplx<T> c1, cplx<T> c2, cplx<T> d1, cplx<T> d2) {
+    const cplx<double> x = cmul(cplx<double>{(double)d1.re, -(double)d1.im}, cplx<double>{(double)c2.re, (double)c2.im});
+    const cplx<double> y = cmul(cplx<double>{(double)c1.re, -(double)c1.im}, cplx<double>{(double)d2.re, (double)d2.im});
+    return {x.re + y.re, x.im + y.im};
+}
+
 // HERM (Hermitian strengths): the grid holds two transforms per frequency instead of four --
 //   T1 = F[c_00 + i c_11]  (both real),   T2 = F[c_01]   (c_10 = conj(c_01)) --
 // and the four products are rebuilt from their values at the target s and at its mirror image -s:
@@ -2496,8 +2515,10 @@ __device__ inline cplx<double> wterm_factor(int k, double zc, double zh, double 
 // gather spent 70 % of its time waiting for them one at a time.)
 // ZD (direct third dimension, InterpArgs::zd_n) and WT (height terms, InterpArgs::wt_k) are compile-time: carried as run-time
 // branches they cost the plain 2-D gather 47 registers (146 -> 193 fp64, 98 -> 177 fp32: a wave per SIMD, 11-24 % of its time).
-// GRAD (InterpArgs::gs) and TANGENT (InterpArgs::tg_w) are epilogues of their own passes, compile-time for the same reason.
-template <typename T, int DIM, bool HERM, int NR, bool ZD = false, bool WT = false, bool GRAD = false, bool TANGENT = false>
+// GRAD (InterpArgs::gs), TANGENT (InterpArgs::tg_w) and BTAN (InterpArgs::bt_d) are epilogues of their own passes, compile-time
+// for the same reason.
+template <typename T, int DIM, bool HERM, int NR, bool ZD = false, bool WT = false, bool GRAD = false, bool TANGENT = false,
+          bool BTAN = false>
 __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
     const cplx<T> *__restrict__ grid, int64_t N, const T *__restrict__ bt0,
     const T *__restrict__ bt1, const T *__restrict__ bt2, const int *__restrict__ bl_idx,
@@ -2749,6 +2770,30 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                     o->im += (T)ai;
                     continue;
                 }
+                if constexpr (BTAN) {  // (conj(D1k) C2l + conj(C1k) D2l) V per direction (+ the transposed term's)
+                    const int64_t i1k = ((int64_t)ant1[km] * a.nbasis + a.kk) * a.ncoef_freq + a.f_first + fg;
+                    const int64_t i2l = ((int64_t)ant2[km] * a.nbasis + a.ll) * a.ncoef_freq + a.f_first + fg;
+                    const int64_t i1l = ((int64_t)ant1[km] * a.nbasis + a.ll) * a.ncoef_freq + a.f_first + fg;
+                    const int64_t i2k = ((int64_t)ant2[km] * a.nbasis + a.kk) * a.ncoef_freq + a.f_first + fg;
+                    const bool t1 = a.basis_part != 2, t2 = a.kk != a.ll && a.basis_part != 1;
+                    const cplx<double> V = {vr, vim_};
+                    const int64_t po2 = a.out_pol_off[(r & 1) * 2 + (r >> 1)];  // feed-transposed slot
+                    for (int q = 0; q < a.bt_ndir; ++q) {
+                        const cplx<T> *dq = (const cplx<T> *)a.bt_d + (int64_t)q * a.bt_d_stride;
+                        cplx<T> *oq = ob + (int64_t)q * a.bt_out_stride;
+                        if (t1) {
+                            const cplx<double> v1 = cmul(btan_weight(coef[i1k], coef[i2l], dq[i1k], dq[i2l]), V);
+                            oq[po].re += (T)v1.re;
+                            oq[po].im += (T)v1.im;
+                        }
+                        if (t2) {
+                            const cplx<double> v2 = cmul(btan_weight(coef[i1l], coef[i2k], dq[i1l], dq[i2k]), V);
+                            oq[po2].re += (T)v2.re;
+                            oq[po2].im += (T)v2.im;
+                        }
+                    }
+                    continue;
+                }
                 if (a.basis) {
                     const int f = a.f_first + fg;
                     const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
@@ -2811,7 +2856,7 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
             cplx<T> *ob = out + (int64_t)fg * a.out_fg_stride + km * a.out_k_stride;
             cplx<double> w1 = {1.0, 0.0}, w2 = {0.0, 0.0};
             cplx<double> s1 = {0.0, 0.0}, s2 = {0.0, 0.0};  // GRAD: this member's inner products over the four products
-            if (a.basis && !GRAD) {  // eigenbeam term (k, l): vis += conj(C[a1,k]) C[a2,l] V  (+ the transposed (l, k) term)
+            if (a.basis && !GRAD && !BTAN) {  // eigenbeam term (k, l): vis += conj(C[a1,k]) C[a2,l] V  (+ the transposed (l, k) term)
                 const int f = a.f_first + fg;
                 const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
                 const cplx<T> c1k = coef[(cs1 + a.kk) * a.ncoef_freq + f];
@@ -2826,6 +2871,43 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
             cplx<double> wf = {1.0, 0.0};
             if constexpr (WT)  // this member's height factor, applied before the conjugation
                 wf = wterm_factor(a.wt_k, a.wt_zc, a.wt_zh, sc * (neg ? -1.0 : 1.0) * (double)((const T *)a.wt_bz)[km]);
+            if constexpr (BTAN) {  // the four products first, then per direction the differentiated weights times each
+                cplx<double> V[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double xr = o_re[r] * wf.re - o_im[r] * wf.im, xi = o_re[r] * wf.im + o_im[r] * wf.re;
+                    V[r] = {xr, neg ? -xi : xi};
+                }
+                const int64_t i1k = ((int64_t)ant1[km] * a.nbasis + a.kk) * a.ncoef_freq + a.f_first + fg;
+                const int64_t i2l = ((int64_t)ant2[km] * a.nbasis + a.ll) * a.ncoef_freq + a.f_first + fg;
+                const int64_t i1l = ((int64_t)ant1[km] * a.nbasis + a.ll) * a.ncoef_freq + a.f_first + fg;
+                const int64_t i2k = ((int64_t)ant2[km] * a.nbasis + a.kk) * a.ncoef_freq + a.f_first + fg;
+                const bool t1 = a.basis_part != 2, t2 = a.kk != a.ll && a.basis_part != 1;
+                const bool tf = a.transpose_flipped && neg;
+                for (int q = 0; q < a.bt_ndir; ++q) {
+                    const cplx<T> *dq = (const cplx<T> *)a.bt_d + (int64_t)q * a.bt_d_stride;
+                    cplx<T> *oq = ob + (int64_t)q * a.bt_out_stride;
+                    cplx<double> w1q = {0.0, 0.0}, w2q = {0.0, 0.0};
+                    if (t1) w1q = btan_weight(coef[i1k], coef[i2l], dq[i1k], dq[i2l]);
+                    if (t2) w2q = btan_weight(coef[i1l], coef[i2k], dq[i1l], dq[i2k]);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (t1) {
+                            const cplx<double> v1 = cmul(w1q, V[r]);
+                            cplx<T> *o = oq + a.out_pol_off[tf ? (r & 1) * 2 + (r >> 1) : r];
+                            o->re += (T)v1.re;
+                            o->im += (T)v1.im;
+                        }
+                        if (t2) {
+                            const cplx<double> v2 = cmul(w2q, V[r]);
+                            cplx<T> *o2 = oq + a.out_pol_off[(r & 1) * 2 + (r >> 1)];  // feed-transposed slot
+                            o2->re += (T)v2.re;
+                            o2->im += (T)v2.im;
+                        }
+                    }
+                }
+                continue;
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const double xr = o_re[r] * wf.re - o_im[r] * wf.im, xi = o_re[r] * wf.im + o_im[r] * wf.re;
@@ -2958,6 +3040,11 @@ struct BasisTerm {
     void *gs = nullptr;
     int gs_nf = 0, gs_f0 = 0;
     int64_t gs_nbls = 0;
+    // basis tangent epilogue (InterpArgs::bt_d): ndir directions of the coefficients, device (ndir, nant, K, nfreq), each
+    // added into its own copy of the output block, out_stride elements apart; nullptr: the forward's epilogue
+    const void *dcoef = nullptr;
+    int ndir = 0;
+    int64_t d_stride = 0, out_stride = 0;  // elements between directions of dcoef (nant K nfreq) and of the output
 };
 
 // Height term handed to Nufft3::interp (InterpArgs::wt_*)
@@ -4013,6 +4100,10 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
         a.gs_nf = basis->gs_nf;
         a.gs_f0 = basis->gs_f0;
         a.gs_nbls = basis->gs_nbls;
+        a.bt_d = basis->dcoef;
+        a.bt_ndir = basis->ndir;
+        a.bt_d_stride = basis->d_stride;
+        a.bt_out_stride = basis->out_stride;
     }
     a.w = ker.w;
     a.tpol = tpol;
@@ -4111,6 +4202,20 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
         if (wt)
             kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true, false, true> : k_interp<T, 2, true, 16, false, true, false, true>)
                         : (r9 ? k_interp<T, 2, false, 9, false, true, false, true> : k_interp<T, 2, false, 16, false, true, false, true>);
+    }
+    if (a.bt_d) {  // the basis tangent epilogue's instantiations (basis mode, never together with the other two epilogues)
+        FV_REQUIRE(basis && basis->nbasis > 0 && !a.gs && !tan && a.bt_ndir >= 1 && a.bt_d_stride > 0,
+                   "basis tangent epilogue: a basis term and its directions");
+        kern = gdim == 2 ? (herm ? (r9 ? k_interp<T, 2, true, 9, false, false, false, false, true> : k_interp<T, 2, true, 16, false, false, false, false, true>)
+                                 : (r9 ? k_interp<T, 2, false, 9, false, false, false, false, true> : k_interp<T, 2, false, 16, false, false, false, false, true>))
+                         : (herm ? (r9 ? k_interp<T, 3, true, 9, false, false, false, false, true> : k_interp<T, 3, true, 16, false, false, false, false, true>)
+                                 : (r9 ? k_interp<T, 3, false, 9, false, false, false, false, true> : k_interp<T, 3, false, 16, false, false, false, false, true>));
+        if (zd)
+            kern = herm ? (r9 ? k_interp<T, 2, true, 9, true, false, false, false, true> : k_interp<T, 2, true, 16, true, false, false, false, true>)
+                        : (r9 ? k_interp<T, 2, false, 9, true, false, false, false, true> : k_interp<T, 2, false, 16, true, false, false, false, true>);
+        if (wt)
+            kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true, false, false, true> : k_interp<T, 2, true, 16, false, true, false, false, true>)
+                        : (r9 ? k_interp<T, 2, false, 9, false, true, false, false, true> : k_interp<T, 2, false, 16, false, true, false, false, true>);
     }
     hipLaunchKernelGGL(kern, grid, dim3(INTERP_THREADS), 0, stream, (const cplx<T> *)grid_out, N, bt[0], bt[1], bt[2],
                        bl_idx, flip, scale_dev, a, ker, out, coef, ant1, ant2, ustart, upairs);

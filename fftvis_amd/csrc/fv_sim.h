@@ -1427,6 +1427,15 @@ __global__ void k_strengths_tangent(StrengthArgs a, SrcAccArgs s, const int *__r
     }
 }
 
+// the same for a complex array of the handle's precision (fv_sim_run_basis_tangent's directions)
+template <typename T>
+__global__ void k_count_nonfinite_c(const cplx<T> *__restrict__ v, int64_t n, int *__restrict__ count) {
+    int bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        bad += isfinite(v[i].re) && isfinite(v[i].im) ? 0 : 1;
+    if (bad) atomicAdd(count, bad);
+}
+
 // entries of a fp64 array that are not finite, added to *count (fv_sim_run_tangent's device-side inputs)
 __global__ void k_count_nonfinite(const double *__restrict__ v, int64_t n, int *__restrict__ count) {
     int bad = 0;
@@ -2031,6 +2040,8 @@ struct SimBase {
                                     int gtopo_on_device, int accumulate) = 0;
     virtual void run_tangent(int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
                              int dtopo_on_device, void *out, int out_on_device) = 0;
+    virtual void run_basis_tangent(int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir, void *out,
+                                   int out_on_device) = 0;
     // Host destination of the next run (fv_sim_run_into): `out` is then a block INSIDE a larger array -- channel f of
     // the block starts f * out_f_stride elements after `out` (0: the block is contiguous) -- and with out_shared other
     // processes write the rest of that array (a sharded run's ranks filling one shared result): the pinning helper must
@@ -2191,6 +2202,7 @@ class Sim : public SimBase {
     DevBuf d_adj_g, d_adj_gf;  // adjoint: host G block / host gradient staged on the device
     DevBuf d_adj_gc;           // basis adjoint: host coefficient gradient staged on the device
     DevBuf d_tan_w, d_tan_dt;  // tangent: the rounds' weights (RunPlan::tan_w), host dtopo staged on the device
+    DevBuf d_bt_d, d_bt_out;   // basis tangent: host directions D / the (ndir, ...) output of a host destination, on the device
     DevBuf d_csr_start, d_csr;  // basis mode: per antenna, its baselines as 2 b + role (k_coef_reduce)
     int nant_basis = 0;
     // sticky device-side error counters, read at every host synchronisation point (check_errors):
@@ -3476,6 +3488,12 @@ class Sim : public SimBase {
         const double *tan_w = nullptr, *tan_dtopo = nullptr;
         int tan_sets = 0, tan_D = 0;
         double tan_h = 0.0;
+        // basis tangent (run_basis_tangent): the gathers add, with the basis tangent epilogue (k_interp<.., BTAN>), into
+        // bt_ndir copies of the output block, bt_stride elements apart, one per direction of bt_d: device
+        // (bt_ndir, nant, K, nfreq) complex of this precision
+        const void *bt_d = nullptr;
+        int bt_ndir = 0;
+        int64_t bt_stride = 0;
         int nsets() const { return (moments ? 3 : 0) + tan_sets; }  // strength sets per launch beyond the forward's one (0: the forward)
         // the plan class of height term kt: the run's own plan, or a light class's
         int cls(int kt) const { return k0 > 0 && kt >= k0 ? (kt >= k1 ? 2 : 1) : 0; }
@@ -4035,6 +4053,12 @@ class Sim : public SimBase {
                         bt.gs_nf = r.nf;
                         bt.gs_f0 = fa - f0;
                         bt.gs_nbls = nbls;
+                    }
+                    if (r.bt_d) {
+                        bt.dcoef = r.bt_d;
+                        bt.ndir = r.bt_ndir;
+                        bt.d_stride = (int64_t)nant_basis * nbasis * (int64_t)freqs.size();
+                        bt.out_stride = r.bt_stride;
                     }
                     // exact eigenbeam symmetry (reference_compat off): the (l, k) term of an off-diagonal pair of
                     // complex basis beams comes from a second gather at -b (all-real pairs: packed, exact already)
@@ -5069,6 +5093,100 @@ class Sim : public SimBase {
             }
         }
         adjoint_release();
+        check_errors();
+    }
+
+    // ---- basis beams, forward mode: out[q] = dV[C; D_q], the change of the visibilities along the direction D_q of the
+    // coefficients (DESIGN.md "Tangents") ----------------------------------------------------------------------------------
+    // With V_b = sum_kl conj(C[a1,k]) C[a2,l] M_kl(b),
+    //     dV_b[C; D] = sum_kl ( conj(D[a1,k]) C[a2,l] + conj(C[a1,k]) D[a2,l] ) M_kl(b),
+    // and the basis visibilities M_kl depend on neither C nor D: the pass is ONE forward run -- its own stages over the
+    // (k <= l) terms, packings, mirror gathers, height terms, column plans, lanes and source chunks -- whose gathers carry
+    // the basis tangent epilogue (k_interp<.., BTAN>) and add every direction's weights times V into that direction's copy
+    // of the zeroed output block.  The directions share every transform.  A time step's slots are written by its own lane's
+    // stream only, in order: bitwise reproducible for a lane count.  A host destination receives the (ndir, ...) output in
+    // one copy at the end.
+    void run_basis_tangent(int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir, void *out,
+                           int out_on_device) override {
+        FV_HIP(hipSetDevice(device));
+        FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_tangent needs a handle with basis beams (fv_sim_set_basis)");
+        FV_REQUIRE(!type1, "basis beams never take the lattice path");
+        check_run(t0, t1, f0, f1);
+        const int nt = t1 - t0, nf = f1 - f0;
+        const int64_t per_tf = (int64_t)tpol * nbls;
+        const int64_t blk = (int64_t)nf * nt * per_tf;  // elements of one direction's output block
+        // an earlier run may have the lanes busy
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipStreamSynchronize(prep_stream));
+        if (copy_stream) FV_HIP(hipStreamSynchronize(copy_stream));
+        for (int li = 1; li < 4; ++li)
+            if (lanes[li].stream && lanes[li].own_stream) FV_HIP(hipStreamSynchronize(lanes[li].stream));
+        const int64_t d_elems = (int64_t)ndir * nant_basis * nbasis * (int64_t)freqs.size();
+        const cplx<T> *dd = (const cplx<T> *)dcoefs;
+        if (!dcoefs_on_device) {
+            upload(d_bt_d, dcoefs, sizeof(cplx<T>) * (size_t)d_elems, 0);
+            dd = d_bt_d.as<cplx<T>>();
+        }
+        {  // a value that is not finite fails the call before anything runs
+            hipLaunchKernelGGL(k_count_nonfinite_c<T>, dim3((unsigned)std::min<int64_t>(cdiv(d_elems, 256), 4096)), dim3(256), 0,
+                               stream, dd, d_elems, d_err.as<int>() + 4);
+            int bad = 0;
+            FV_HIP(hipMemcpyAsync(&bad, d_err.as<int>() + 4, sizeof(int), hipMemcpyDeviceToHost, stream));
+            FV_HIP(hipStreamSynchronize(stream));
+            if (bad) {
+                FV_HIP(hipMemsetAsync(d_err.as<int>() + 4, 0, sizeof(int), stream));
+                FV_HIP(hipStreamSynchronize(stream));
+                throw Error(FV_ERR_ARG, std::to_string(bad) + " entries of dcoefs are not finite");
+            }
+        }
+        const size_t out_bytes = sizeof(cplx<T>) * (size_t)ndir * (size_t)blk;
+        cplx<T> *dout = (cplx<T> *)out;
+        if (!out_on_device) {
+            d_bt_out.reserve(std::max<size_t>(out_bytes, 16));
+            dout = d_bt_out.as<cplx<T>>();
+        }
+        FV_HIP(hipMemsetAsync(dout, 0, out_bytes, stream));  // terms, chunks and height terms all add
+        if (blk > 0) {
+            if (mhist_log.size() > 65536) mhist_log.clear();
+            RunPlan r{t0, t1, f0, f1, nt, nf};
+            r.bt_d = dd;
+            r.bt_ndir = ndir;
+            r.bt_stride = blk;
+            source_box(r.xc, r.X);
+            height_terms(r);
+            pair_setup(r);
+            grid_and_groups(r);
+            light_classes(r);
+            lane_schedule(r);
+            lane_plans(r);
+            r.ch = source_chunks(r.nlanes_used);
+            lane_buffers(r);
+            OutBlock o{};  // direction 0's block; the epilogue reaches the others by bt_stride
+            o.out = nullptr;
+            o.on_device = true;
+            o.nt = nt;
+            o.nf = nf;
+            o.dout = dout;
+            o.per_tf = per_tf;
+            o.run = (int64_t)nt * per_tf;
+            o.fs = o.run;
+            o.bytes = sizeof(cplx<T>) * (size_t)blk;
+            o.run_bytes = sizeof(cplx<T>) * (size_t)o.run;
+            o.shared = false;
+            o.drain = false;
+            Drain dr;
+            queue_units(r, o, dr);
+        }
+        if (!out_on_device && out_bytes) FV_HIP(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+        if (timing_level) ev_collect();
+        {  // the staged directions and output belong to this pass: beyond the keep limit they go back
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            if ((double)(d_bt_d.cap + d_bt_out.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
+                d_bt_d.release();
+                d_bt_out.release();
+            }
+        }
         check_errors();
     }
 

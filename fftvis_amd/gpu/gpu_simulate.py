@@ -296,6 +296,16 @@ class SimHandle:
         op, o_dev = _buffer_addr(out)
         _lib.check(self._L.fv_sim_run_tangent(self._h, t0, t1, f0, f1, bp, b_dev, tp, t_dev, op, o_dev))
 
+    def run_basis_tangent(self, t0, t1, f0, f1, dcoefs, out):
+        """Basis beams (``set_basis``): ``out[q] =`` the tangent of the visibilities along direction ``dcoefs[q]`` of the
+        coefficients for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_basis_tangent``).  ``dcoefs``: C-contiguous
+        (ndir, nant, nbasis, nfreq) of this engine's complex dtype; ``out``: C-contiguous
+        (ndir,) + ``out_shape(t1 - t0, f1 - f0)``, the same dtype, overwritten.  numpy arrays are host buffers, torch
+        tensors device buffers.  The directions share every transform.  The call synchronises."""
+        dp, d_dev = _buffer_addr(dcoefs)
+        op, o_dev = _buffer_addr(out)
+        _lib.check(self._L.fv_sim_run_basis_tangent(self._h, t0, t1, f0, f1, dp, d_dev, int(dcoefs.shape[0]), op, o_dev))
+
     def run_device(self, t0, t1, f0, f1, out_ptr):
         """Enqueue only; ``out_ptr`` is a device buffer of out_shape() complex elements."""
         _lib.check(self._L.fv_sim_run(self._h, t0, t1, f0, f1, _lib.ptr(out_ptr), 1))
@@ -420,6 +430,7 @@ class GPUSimulationEngine(SimulationEngine):
         adjoint_path: str = "type3",
         adjoint_wrt: str = "fluxes",
         tangent_of: tuple = None,
+        basis_tangent_of: tuple = None,
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -503,7 +514,16 @@ class GPUSimulationEngine(SimulationEngine):
           the sources' ENU unit vectors, either None (``SimHandle.run_tangent``), and returns it.  Time blocks take
           consecutive rows of ``dtopo``.  The pass runs the type-3 transform only: ValueError on the lattice path (pass
           ``force_use_type3=True``) and with ``beam_coefs``.
+        * ``basis_tangent_of`` (extra; what ``simulate_vis_basis_jvp`` passes; needs ``beam_coefs``): a pair ``(dcoefs, dv)``
+          -- instead of simulating, the engine fills ``dv``, (ndir,) + the result's shape, this precision's complex dtype,
+          with the tangents of its visibilities along the ``ndir`` directions ``dcoefs`` (ndir, nant, nbasis, nfreqs) of the
+          coefficients (``SimHandle.run_basis_tangent``: one forward run, whatever ``ndir``) and returns it.
         """
+        if basis_tangent_of is not None:
+            if adjoint_of is not None or tangent_of is not None:
+                raise ValueError("pass one of adjoint_of, tangent_of and basis_tangent_of")
+            if beam_coefs is None:
+                raise ValueError("basis_tangent_of needs basis beams (beam_coefs)")
         if tangent_of is not None:
             if adjoint_of is not None:
                 raise ValueError("pass either adjoint_of or tangent_of, not both")
@@ -666,6 +686,13 @@ class GPUSimulationEngine(SimulationEngine):
                 return result
             if tangent_of is not None:
                 result = _run_tangent(h, tangent_of[0], tangent_of[1], tangent_of[2], t0, t1, f0, f1, nblk_t, coord_mgr)
+                ok = True
+                return result
+            if basis_tangent_of is not None:
+                # (the device holds every direction's copy of a time block)
+                nblk_t = _time_block(self.device, t1 - t0, (f1 - f0) * int(basis_tangent_of[0].shape[0]), len(baselines),
+                                     polarized, precision, nsrc if coord_mgr is not None else 0)
+                result = _run_basis_tangent(h, basis_tangent_of[0], basis_tangent_of[1], t0, t1, f0, f1, nblk_t, coord_mgr)
                 ok = True
                 return result
             if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != complex_dtype):
@@ -841,6 +868,37 @@ def _run_tangent(h, dbls, dtopo, dv, t0, t1, f0, f1, nblk_t, coord_mgr):
         h.run_tangent(ta, te_, f0, f1, dbls, rows, blk)
         if not whole:
             dv[:, tb - t0:te - t0] = blk
+    if t1 <= t0:
+        dv[...] = 0
+    return dv
+
+
+def _run_basis_tangent(h, dcoefs, dv, t0, t1, f0, f1, nblk_t, coord_mgr):
+    """The basis tangent's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors); every
+    block's ``run_basis_tangent`` fills its slice ``dv[:, :, block]`` of every direction (a block that is not the whole
+    result goes through a contiguous temporary).  Every call ends synchronised."""
+    on_device = not isinstance(dv, np.ndarray)
+    step = max(nblk_t, 1)
+    for tb in range(t0, t1, step):
+        te = min(t1, tb + step)
+        whole = tb == t0 and te == t1
+        if whole:
+            blk = dv
+        elif on_device:
+            import torch
+
+            blk = torch.empty_like(dv[:, :, tb - t0:te - t0], memory_format=torch.contiguous_format)
+            torch.cuda.synchronize(blk.device)
+        else:
+            blk = np.empty(dv[:, :, tb - t0:te - t0].shape, dtype=dv.dtype)
+        if coord_mgr is not None:
+            h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
+            ta, te_ = 0, te - tb
+        else:
+            ta, te_ = tb, te
+        h.run_basis_tangent(ta, te_, f0, f1, dcoefs, blk)
+        if not whole:
+            dv[:, :, tb - t0:te - t0] = blk
     if t1 <= t0:
         dv[...] = 0
     return dv

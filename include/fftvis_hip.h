@@ -342,6 +342,27 @@ int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const v
  * anything runs; the handle stays usable) fail with FV_ERR_ARG.                                                          */
 int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
                        int dtopo_on_device, void *out, int out_on_device);
+/* Forward-mode tangent of a basis-beam handle's visibilities (fv_sim_set_basis) along ndir directions of the coefficients,
+ * for times [t0, t1) x freqs [f0, f1).  With V_b = sum_kl conj(C[a1,k]) C[a2,l] M_kl(b), M_kl the visibilities of basis
+ * beams k and l, the derivative along a complex direction D of the coefficients is
+ *     dV_b[C; D] = sum_kl ( conj(D[a1,k]) C[a2,l] + conj(C[a1,k]) D[a2,l] ) M_kl(b),
+ * real-linear in D, and M_kl depends on neither C nor D: out[q] = dV[C; D_q] is ONE forward run whose gathers carry the
+ * differentiated weights, and the ndir directions share every transform.  It is the transpose of
+ * fv_sim_run_basis_adjoint's coefficient gradient, Re <dV[C; D], G> = Re <D, gcoefs>, and dV[C; D] = (V(C + D) - V(C - D)) / 2
+ * exactly (the map is sesquilinear).  fv_sim_set_reference_compat selects the form of the (l, k) terms as in fv_sim_run.
+ * dcoefs: (ndir, nant, nbasis, nfreq) complex of the handle's precision, every direction laid out like fv_sim_set_basis'
+ * coefs; only channels [f0, f1) are read.  out: (ndir, f1 - f0, t1 - t0, 2, 2, nbls) complex of the handle's precision,
+ * every direction in fv_sim_run's layout for that block, always overwritten (no accumulate flag).  The *_on_device flags as
+ * in fv_sim_run (device buffers must be complete when the call is made); the call synchronises.  The weights are summed
+ * in fp64 before the product with M_kl, so directions whose two halves cancel (D = i C) give rounding-level output.  One
+ * owner thread per slot and launch, a time step's slots written by its own lane only: no atomics, bitwise reproducible
+ * for a given FFTVIS_HIP_LANES, and a direction's output does not depend on the others in the call.  A host destination
+ * receives the output in one copy at the end.  The staged directions and output are given back under the
+ * FFTVIS_HIP_ADJ_KEEP_BYTES rule of fv_sim_run_adjoint.  A handle without fv_sim_set_basis, a null handle, a null out, a
+ * null dcoefs, ndir < 1, a flag other than 0 or 1 and an entry of dcoefs that is not finite (detected before anything runs;
+ * the handle stays usable) fail with FV_ERR_ARG.                                                                          */
+int fv_sim_run_basis_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir,
+                             void *out, int out_on_device);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2
