@@ -1124,6 +1124,15 @@ __global__ void k_src_moments(int64_t nu, int64_t rows, int D, const T *__restri
 // either precision; only Z differs.
 constexpr double SRC_BEAM_STEP_FP64 = 1e-6;
 constexpr double SRC_BEAM_STEP_FP32 = 1e-6;
+// Near the zenith az turns by h / sin(za) over the stencil and the difference's truncation grows with (h / sin za)^2 -- on
+// a bilinear table 13 (h / sin za)^2 of the beam term, 1.5e-6 of a source's row at za = 3e-3 --, while a smaller step pays
+// in the rounding of za = pi / 2 - asin(sqrt(1 - sin^2 za)), 1e-16 / (sin za . h).  So the step is at most this fraction of
+// sin(za): it takes over below za = 1.1 degrees (profiles/MEASUREMENTS.md, "Table beams at every order": the fractions
+// either side), and never falls below h / 1000 (a source within 2e-5 rad of the zenith has no usable az either way).
+constexpr double SRC_BEAM_STEP_ZENITH = 5e-5;
+__device__ inline double src_beam_step(double h, double e, double n) {
+    return fmin(h, fmax(SRC_BEAM_STEP_ZENITH * sqrt(e * e + n * n), 1e-3 * h));
+}
 
 struct SrcAccArgs {
     int64_t M;           // capacity of the per-time arrays (stride of z); live count is *Mp
@@ -1137,8 +1146,16 @@ struct SrcAccArgs {
     BeamDesc bi, bj;
     Rot9 rt;             // vec -> ENU at this time (identity for given topocentric vectors)
     Rot9 rp;             // the plane rotation R: ENU -> the transforms' frame
-    double h;            // step of the beam term
+    double h;            // step of the beam term (src_beam_step shortens it near the zenith)
 };
+
+// A table at spline order 0 is piecewise constant: its derivative is exactly 0 wherever it exists, and a difference whose
+// stencil straddles a jump returns (jump) / 2h, which is no derivative.  So with both beams of the pair such tables the
+// beam term is 0 by definition and the displaced evaluations are skipped.  A dish paired with an order-0 table keeps the
+// differences: the dish's factor varies smoothly (DESIGN.md "Sources": the limitation at a jump of that pair).
+__device__ inline bool beam_term_is_zero(const SrcAccArgs &a) {
+    return a.bi.kind == 1 && a.bi.order == 0 && (a.same_beam || (a.bj.kind == 1 && a.bj.order == 0));
+}
 
 // The forward's strengths of one source at the ENU unit vector (e, n, u), in fp64: strength_eval's beam and coherency
 // calls (az, za as k_horizon_compact forms them) without its packings, pre-phase and rounding.  Returns
@@ -1251,11 +1268,12 @@ __global__ void k_src_accumulate(SrcAccArgs a, const int *__restrict__ Mp, const
         e2[2] = nv[0] * e1[1] - nv[1] * e1[0];
     }
     double sh, ch;
-    sincos(a.h, &sh, &ch);
-    const double inv2h = 0.5 / a.h;
+    const double h = src_beam_step(a.h, nv[0], nv[1]);
+    sincos(h, &sh, &ch);
+    const double inv2h = 0.5 / h;
     double d1 = 0.0, d2 = 0.0;
 #pragma unroll 1
-    for (int k = 0; k < 4; ++k) {  // +e_1, -e_1, +e_2, -e_2: one copy of the beam code
+    for (int k = ORD == 0 && beam_term_is_zero(a) ? 4 : 0; k < 4; ++k) {  // +e_1, -e_1, +e_2, -e_2: one copy of the beam code
         const double sg = k & 1 ? -sh : sh;
         const double te = k < 2 ? e1[0] : e2[0], tn = k < 2 ? e1[1] : e2[1];
         const double s = src_strength_dot<T, ORD>(a, fidx, freq, js, ch * nv[0] + sg * te, ch * nv[1] + sg * tn, flux, Z, nullptr);
@@ -1327,7 +1345,8 @@ __global__ void k_srcgrad_reduce(SrcReduceArgs a, const double *__restrict__ acc
 //                great circle through n towards delta, with c(n) evaluated in fp64 from the catalogue vector
 //                (src_strength_dot's beam and coherency calls, two displaced evaluations), then brought into the
 //                forward's form: pre-phase and Hermitian / all-real packing (the derivative of a Hermitian matrix along a
-//                real direction is Hermitian, that of a real one real); exactly 0 where |delta| = 0;
+//                real direction is Hermitian, that of a real one real); exactly 0 where |delta| = 0 and between
+//                order-0 tables (beam_term_is_zero);
 //     set 1 + d  the forward's own strengths (strength_eval) times dx_d, d < D (2 on coplanar handles, where b'_z = 0).
 // With height terms the Chebyshev factor of term wt_k multiplies every set.  s carries the beams and flags of a as
 // src_strength_dot reads them, the rotations and the step.  dtopo: this time step's (nsrc, 3) fp64 rows, read at the
@@ -1395,11 +1414,12 @@ __global__ void k_strengths_tangent(StrengthArgs a, SrcAccArgs s, const int *__r
     // set 0: the beam term
     const double mag = sqrt(dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2]);
     cplx<double> dc[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
-    if (mag > 0.0) {
+    if (mag > 0.0 && !(ORD == 0 && beam_term_is_zero(s))) {
         double sh, ch;
-        sincos(s.h, &sh, &ch);
+        const double h = src_beam_step(s.h, nv[0], nv[1]);
+        sincos(h, &sh, &ch);
         const double e0 = dl[0] / mag, e1 = dl[1] / mag;
-        const double wgt = sc * mag * 0.5 / s.h;
+        const double wgt = sc * mag * 0.5 / h;
         const cplx<double> Z[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
 #pragma unroll 1
         for (int k = 0; k < 2; ++k) {  // n+, n-: one copy of the beam code

@@ -17,6 +17,13 @@ D(h) = (V(+h) - V(-h)) / 2h, h = 1e-5: the remainder is about (k h)^4, k = 2 pi 
 below the horizon are set to 0: the cut is not differentiated.  The phase part has a closed form as well,
     sum_d i (2 pi nu_f / c) b_k,d . oracle(fluxes x (P_n delta)_d),
 so the beam part is what remains.
+
+The differences need a beam that is smooth over n +- h delta.  A table beam is a polynomial patch between two knot lines
+at every spline order, so the condition is ``source_adjoint_refs.knot_margin``'s: the configurations with a table at
+orders 0, 1 and 2 (``order_config``) keep every source more than 1e-3 rad from a knot line, the hand-placed table-edge
+sources (``edge_table_config``) more than 1e-4 rad = 10 h (``test_tangent_host`` asserts both); orders 3 .. 5 are C^2 and
+need none.  At order 0 the beam is piecewise constant and the phase part is the whole tangent: ``frozen_beam_dv_topo``,
+closed form, valid with a source on a jump of the table.
 """
 
 import numpy as np
@@ -24,7 +31,8 @@ import numpy as np
 from oracle import fftvis_oracle as orc
 from tests.helpers import oracle_simulate
 from tests.position_adjoint_refs import _TopoAt, position_config, random_complex, vis_shape  # noqa: F401
-from tests.source_adjoint_refs import margins, source_config, tangent_pair  # noqa: F401
+from tests.source_adjoint_refs import (ORDERS, baseline_vectors, edge_table_config, jump_config, knot_margin,  # noqa: F401
+                                       margins, order_config, source_config, table_configs, tangent_pair)
 
 H_REF = 1e-5  # rad
 
@@ -49,12 +57,6 @@ def _forward_at(cfg, t, fluxes, topo):
 
 def _kf(freqs, ndim):
     return (2 * np.pi * freqs / orc.speed_of_light).reshape((-1,) + (1,) * (ndim - 2))  # per channel, over (r..., k)
-
-
-def baseline_vectors(cfg):
-    """(nbls, 3): every listed baseline's own vector ants[j] - ants[i], ENU metres."""
-    a = cfg["ants"]
-    return np.array([np.asarray(a[j], float) - np.asarray(a[i], float) for i, j in cfg["baselines"]])
 
 
 def exact_dv_baselines(cfg, dbls, coord_mgr=None, sub=None):
@@ -93,9 +95,6 @@ def exact_dv_topo(cfg, dtopo, coord_mgr=None, h=H_REF):
     freqs, times, fluxes, mgr = _setup(cfg, coord_mgr)
     shape = vis_shape(cfg)
     dV = np.zeros(shape, dtype=np.complex128)
-    pterms = [np.zeros(shape, dtype=np.complex128) for _ in range(3)]
-    kf = _kf(freqs, len(shape))
-    b = baseline_vectors(cfg)
     for ti, t in enumerate(times):
         topo = orc._topo_of(mgr, ti)
         n, delta = project(topo, dtopo[ti])
@@ -111,11 +110,29 @@ def exact_dv_topo(cfg, dtopo, coord_mgr=None, h=H_REF):
             return (_forward_at(cfg, t, fluxes, p.T) - _forward_at(cfg, t, fluxes, m.T)) / (2.0 * step)
 
         dV[:, ti] = s * (4.0 * D(0.5 * h) - D(h)) / 3.0
+    phase, pterms = frozen_beam_dv_topo(cfg, dtopo, coord_mgr)
+    return dV, phase, pterms + [dV - phase]
+
+
+def frozen_beam_dv_topo(cfg, dtopo, coord_mgr=None):
+    """(dV, terms): the tangent along ``dtopo`` with the strengths held fixed -- the phase part, in closed form, and its
+    three terms (one per ENU component of delta = P_n dtopo).  At spline order 0, where the beam is piecewise constant,
+    this is the whole tangent; it stays valid with a source on a jump of the table."""
+    dtopo = np.asarray(dtopo, dtype=float)
+    freqs, times, fluxes, mgr = _setup(cfg, coord_mgr)
+    shape = vis_shape(cfg)
+    terms = [np.zeros(shape, dtype=np.complex128) for _ in range(3)]
+    kf = _kf(freqs, len(shape))
+    b = baseline_vectors(cfg)
+    for ti, t in enumerate(times):
+        topo = orc._topo_of(mgr, ti)
+        _, delta = project(topo, dtopo[ti])
+        if not delta.any():
+            continue
         for d in range(3):
             w = delta[:, d].reshape((-1,) + (1,) * (fluxes.ndim - 1))
-            pterms[d][:, ti] = 1j * kf * b[:, d] * _forward_at(cfg, t, fluxes * w, topo)
-    phase = pterms[0] + pterms[1] + pterms[2]
-    return dV, phase, pterms + [dV - phase]
+            terms[d][:, ti] = 1j * kf * b[:, d] * _forward_at(cfg, t, fluxes * w, topo)
+    return terms[0] + terms[1] + terms[2], terms
 
 
 def kappa(dV, terms):
@@ -181,8 +198,10 @@ def empty_step_config():
 
 
 def all_configs():
-    """(label, cfg, dbls, dtopo) of every comparison of the GPU module with a reference (fp64 inputs; the references do
-    not depend on the run's precision).  HERA-350: the baselines tangent on the seeded subset."""
+    """(label, cfg, dbls, dtopo, manager, order, knot bound) of every comparison of the GPU module with a reference (fp64
+    inputs; the references do not depend on the run's precision).  HERA-350: the baselines tangent on the seeded subset.
+    The table configurations beyond order 3's matrix (``table_configs``: the direction tangent alone) carry their manager,
+    spline order and the bound ``knot_margin`` has to exceed; the others None."""
     out = []
     for cell in matrix_cells():
         cfg = source_config(*cell)
@@ -202,4 +221,7 @@ def all_configs():
         sub = hera_subset(cfg)
         out.append((f"hera350 {kind}", dict(cfg, baselines=[cfg["baselines"][i] for i in sub]),
                     random_dbls(cfg, DB_SEED)[sub], None))
+    out = [c + (None, None, None) for c in out]
+    for label, cfg, order, mgr, bound in table_configs():
+        out.append((label, cfg, None, random_dtopo(cfg, DT_SEED), mgr, order, bound))
     return out

@@ -5,8 +5,13 @@ The tangential gradient ``gtopo`` (ntimes, nsrc, 3), ENU, is compared element by
 from the oracle's forward (``source_adjoint_refs.exact_gtopo``, pinned on the CPU in ``test_source_adjoint_host``): over a
 configuration matrix, with sources below the horizon and an empty time step, across source chunks and channel blocks, on
 an ideal lattice, at upsample_factor 1.25, with a coordinate manager and device astrometry, through the bare C ABI and
-through torch's gradcheck and backward.  Table beams at spline orders 0 and 1 have no reference (differences need a smooth
-interpolant): there the device is checked against itself."""
+through torch's gradcheck and backward.  Table beams are compared at every spline order, 0 .. 5: between two knot lines
+an interpolant of any order is a polynomial patch, so the reference's differences hold wherever no source sits within
+their stencil of a line -- a condition on the configurations (``source_adjoint_refs.knot_margin``, asserted in
+``test_source_adjoint_host``), met by ``order_config``'s catalog seed.  The table's edges (the azimuth wrap, the first and
+the last za cell, a table that ends at the horizon) are compared source by source at orders 1 and 3, and at order 0,
+where the beam term is 0 by definition, sources within the device's stencil of a jump are compared with the closed form
+that holds the beam fixed (``frozen_beam_gtopo``)."""
 
 import ctypes
 import functools
@@ -19,9 +24,10 @@ import pytest
 import fftvis_amd
 from fftvis_amd import _lib, synth
 from oracle import fftvis_oracle as orc
-from tests.helpers import floored_rel, rel_l2, worst_part
-from tests.source_adjoint_refs import (exact_gtopo, margins, random_complex, sidereal_jacobian, source_config, table_config,
-                                       vis_shape)
+from tests.helpers import floored_rel, rel_l2, spline_order, worst_part
+from tests.source_adjoint_refs import (ORDERS, edge_table_config, exact_gtopo, frozen_beam_gtopo, gradcheck_config,
+                                       jump_config, knot_margin, margins, order_config, random_complex,
+                                       sidereal_jacobian, source_config, table_config, vis_shape)
 from tests.position_adjoint_refs import hex_positions
 from tests.test_gpu_adjoint import _up
 from tests.test_gpu_basis_adjoint import _forward_base
@@ -42,7 +48,16 @@ pytestmark = pytest.mark.gpu
 #   hex-19), upsample_factor = 1.25 at 0.03, 0.04, 0.02, device astrometry in (ra, dec) at 0.01, 0.04, 0.01.
 #   fp32 over the 54 matrix cells (base 1e-5: the forward's own error stayed below eps everywhere): whole <= 2.06,
 #   a component <= 4.03, max |err| <= 1.92 (unpolarized, one dish, flat array).
-#   Every constant keeps more than twice its measured worst: none moved.
+#   Table beams beyond order 3's matrix, 65 comparisons.  The cell at orders 0, 1, 2, 4, 5 and unpolarized at order 1:
+#   fp64 whole <= 0.06, a component <= 0.07, max |err| <= 0.10 (order 0); fp32 0.34, 0.35, 0.32 (orders 0 and 4).  The
+#   table edges, fp64, whole results and single rows: 2.66, 2.90, 2.70, all three in the row of the source 0.3 of a cell
+#   above az = 0 on the full-sky table at order 3 taken alone (its row is 1e-3 of the result's norm, and the transform's
+#   error follows the whole); the four whole results at or below 0.23, 0.40, 0.27.  Order 0 on a jump, whole and rows: 0.51,
+#   1.34, 0.56 (a row), the whole at 0.06, 0.07, 0.10.  On the parent commit the whole of that run measured 6.9e9 (rel l2 412): the
+#   difference across the jump, gone since the beam term of order-0 tables is 0; and the full-sky edges at order 1
+#   measured 23.5, 28.2, 21.1 at the fixed step 1e-6 rad, the truncation at za = 3e-3, gone since the step follows sin(za)
+#   near the zenith (profiles/MEASUREMENTS.md, "Table beams at every order").
+#   Every constant keeps more than twice its measured worst (the closest: fp64 max |err|, 6 against 2.70): none moved.
 
 
 def _errors(got, exact):
@@ -115,6 +130,68 @@ def test_source_gradient_matrix(gpu, precision, sky, beams, compat, heights):
     _assert_close(f"matrix {precision} {sky} {beams} {compat} {heights}", cfg, got, ref, _forward_base(cfg))
 
 
+# ---- 1b. table beams at every spline order, the table's edges, order 0 on a jump -------------------------------------
+@functools.lru_cache(maxsize=None)
+def _order_reference(order, sky):
+    """The exact gradient of ``order_config(order, sky)`` (it does not depend on the run's precision)."""
+    cfg = order_config(order, sky)
+    G = random_complex(vis_shape(cfg), 4)
+    return G, exact_gtopo(cfg, G)
+
+
+@pytest.mark.parametrize("order,sky", [(o, "full") for o in ORDERS] + [(1, "unpol")])
+@pytest.mark.parametrize("precision", [2, 1])
+def test_source_gradient_table_orders(gpu, precision, order, sky):
+    """The cell "cm heights, full Stokes, exact flips, complex table" at the orders the matrix does not run: 1 (bilinear,
+    the default, unrolled) and 0, 2, 4, 5 (the run-time path); unpolarized at order 1, the power table's bilinear branch."""
+    cfg = _sid(order_config(order, sky, precision))
+    G64, ref = _order_reference(order, sky)
+    got = _gtopo(cfg, G64.astype(np.complex64 if precision == 1 else np.complex128))
+    assert got.shape == (2, 24, 3) and got.dtype == np.float64
+    n = _normals(cfg)
+    assert np.abs(np.einsum("tjd,tjd->tj", n, got)).max() <= (1e-12 if precision == 2 else 1e-6) * np.abs(got).max()
+    assert np.all(got[n[..., 2] <= 0] == 0)
+    _assert_close(f"table order {order} {sky} {precision}", cfg, got, ref, _forward_base(cfg))
+
+
+def _assert_rows_close(label, cfg, got, exact, base):
+    """Every row (t, j) of an above-horizon source on its own, to the bounds of the whole."""
+    for t, j in zip(*np.nonzero(np.any(exact != 0, axis=-1))):
+        _assert_close(f"{label}, row {t} {j}", cfg, got[t:t + 1, j:j + 1], exact[t:t + 1, j:j + 1], base)
+
+
+@pytest.mark.parametrize("order", [1, 3])
+@pytest.mark.parametrize("kind", ["fullsky", "horizon"])
+def test_table_edges_source_by_source(gpu, kind, order):
+    """Sources placed by hand at the edges of a table (``edge_table_config``: the azimuth wrap from both sides and, at
+    order 3, across it, the first za cell at za = 1e-2 and 3e-3, the last cell above the horizon; a table that ends at
+    the horizon), one time step, their vectors through a coordinate manager.  Each source is one edge, so every row is
+    held to the bounds on its own."""
+    cfg, mgr = edge_table_config(kind, order)
+    assert margins(cfg, coord_mgr=mgr)[0] > 1e-3 and (order == 3 or knot_margin(cfg, order, coord_mgr=mgr) > 1e-4)
+    G = random_complex(vis_shape(cfg), 7)
+    got = _gtopo(cfg, G, coord_mgr=mgr)
+    ref = exact_gtopo(cfg, G, coord_mgr=mgr)
+    assert np.all(np.any(ref[0] != 0, axis=-1))
+    _assert_close(f"table edges {kind} order {order}", cfg, got, ref, cfg["eps"])
+    _assert_rows_close(f"table edges {kind} order {order}", cfg, got, ref, cfg["eps"])
+
+
+def test_order_0_with_sources_on_a_jump(gpu):
+    """Order 0 is piecewise constant: the beam term is 0 by definition, also for a source whose difference stencil
+    (1e-6 rad) straddles a jump of the table -- one 3e-7 rad from a za half-node line, one 3e-7 rad from an az half-node
+    line, the others of ``order_config(0)`` where they were.  Reference: the closed form with the beam held fixed.
+    (A difference across the jump would put (jump) / 2e-6, some 1e4 times the strength, into those two rows.)"""
+    cfg, mgr, rows = jump_config()
+    assert knot_margin(cfg, 0, coord_mgr=mgr) < 1e-6 and margins(cfg, coord_mgr=mgr)[0] > 1e-3
+    G = random_complex(vis_shape(cfg), 4)
+    got = _gtopo(cfg, G, coord_mgr=mgr)
+    ref = frozen_beam_gtopo(cfg, G, coord_mgr=mgr)
+    assert np.all(np.any(ref[0, rows] != 0, axis=-1))
+    _assert_close("order 0 on a jump", cfg, got, ref, cfg["eps"])
+    _assert_rows_close("order 0 on a jump", cfg, got, ref, cfg["eps"])
+
+
 # ---- 2. edges --------------------------------------------------------------------------------------------------------
 def _edge_cfg(**kw):
     """The perturbed hex-7 with centimetre heights, polarized, full-Stokes sky, two beams, the exact form of the flipped
@@ -165,8 +242,9 @@ def test_channel_blocks_cut_across_frequency_groups(gpu, monkeypatch, block_ch, 
 
 @pytest.mark.parametrize("order", [0, 1])
 def test_lane_counts_agree_on_table_beams_without_a_reference(gpu, monkeypatch, order):
-    """Spline orders 0 and 1 (no smooth interpolant, no reference): a repeat at one lane count returns the same bits, one
-    and two lanes agree to rounding, and the result is tangential and finite."""
+    """Spline orders 0 and 1 on a catalog whose sources are not held away from the knot lines (the comparisons with the
+    reference are ``test_source_gradient_table_orders``): a repeat at one lane count returns the same bits, one and two
+    lanes agree to rounding, and the result is tangential and finite."""
     cfg = _sid(table_config(order, nsrc=40, ntimes=4, seed=3))
     G = random_complex(vis_shape(cfg), 10)
     res = {}
@@ -409,6 +487,22 @@ def test_torch_gradcheck_both_inputs(gpu):
                                     atol=1e-6, rtol=1e-4)
     out = fftvis_amd.torch_simulate_vis_sky(F, P, **kw)
     assert out.device == F.device and out.is_complex() and tuple(out.shape) == vis_shape(cfg)
+
+
+def test_torch_gradcheck_default_order_table(gpu):
+    """The gradcheck above on a table beam at the default spline order (no ``beam_spline_opts``: bilinear), catalog seed 3:
+    the nearest knot line is 4.5e-4 rad away (asserted > 1e-4), the perturbation step 1e-6 rad, so torch's differences
+    stay inside one bilinear patch, where they are exact up to the smooth map from (ra, dec) to (az, za)."""
+    import torch
+
+    cfg = gradcheck_config()
+    assert "beam_spline_opts" not in cfg and spline_order(cfg.get("beam_spline_opts")) == 1
+    assert margins(cfg)[0] > 1e-3 and knot_margin(cfg, 1) > 1e-4
+    kw = _torch_kwargs(cfg)
+    F = torch.tensor(cfg["fluxes"] + np.array([1.0, 0, 0, 0]), dtype=torch.float64, device="cuda", requires_grad=True)
+    P = torch.tensor(np.stack([cfg["ra"], cfg["dec"]], axis=1), dtype=torch.float64, device="cuda", requires_grad=True)
+    assert torch.autograd.gradcheck(lambda f, p: fftvis_amd.torch_simulate_vis_sky(f, p, **kw), (F, P), eps=1e-6,
+                                    atol=1e-6, rtol=1e-4)
 
 
 def test_torch_backward_equals_the_direct_calls(gpu, monkeypatch):

@@ -6,7 +6,11 @@ the oracle's forward (``tangent_refs.exact_dv_baselines``, closed form; ``tangen
 differences with all sources moved at once; both pinned in ``test_tangent_host``): over a configuration matrix, on an
 ideal lattice with redundant runs, at HERA-350's size with the packed transforms and the column plan, at the edges of the
 device's slicing, through the Python surface and the bare C ABI, against the two position adjoints through
-Re <J v, G> = <v, J^T G>, and through torch's forward-mode AD.
+Re <J v, G> = <v, J^T G>, and through torch's forward-mode AD.  The direction tangent through a table beam is compared
+at every spline order, 0 .. 5, on configurations that keep every source away from the table's knot lines
+(``source_adjoint_refs.knot_margin``, asserted in ``test_tangent_host``), at the table's edges one source at a time, and
+at order 0 -- where the beam term is 0 by definition -- with sources within the device's stencil of a jump against the
+closed form that holds the beam fixed (``frozen_beam_dv_topo``).
 
 Tolerances, as multiples of base: base = eps in fp64; in fp32 base = max(the forward's own rel l2 error against the oracle
 on the same configuration, eps) (``_forward_base``).  Every term of dV is one forward transform, which the project holds
@@ -23,8 +27,14 @@ line each).  Measured over the 243 comparisons, as ratio / (base kappa):
   ideal hex-19 at 0.06, 0.23, 0.06, upsample_factor = 1.25 at 0.15, 2.35, 0.26 (bounds 20, 20, 12 there).
   fp32 over the 108 matrix comparisons (base 1e-5: the forward's own error stayed below eps everywhere): whole <= 0.63,
   a part <= 1.64, max |err| <= 1.06, all on the flat array with the complex table, the directions.
+  Table beams beyond order 3's matrix, the directions, 38 comparisons: the cell at orders 0, 1, 2, 4, 5 and unpolarized at
+  order 1, fp64 whole <= 0.25, a part <= 0.43, max |err| <= 0.44, fp32 0.26, 0.35, 0.23 (order 0); the table edges, all
+  sources and one at a time, 0.34, 0.53, 0.69 (the sources either side of az = 0 on the full-sky table); order 0 on a
+  jump 0.25, 0.55, 0.43 -- on the parent commit 5.3e9 (rel l2 453): the difference across the jump, gone since the beam
+  term of order-0 tables is 0.
   Every constant keeps more than twice its measured worst (the closest: fp64 max |err|, 6 against 1.81): none moved.
-The dot identity between the tangent and the two adjoint passes came out at or below 1e-3 of its bound.
+The dot identity between the tangent and the two adjoint passes came out at or below 1e-3 of its bound (the order-1 and
+order-0 tables: 3e-4).
 """
 
 import ctypes
@@ -39,9 +49,10 @@ import fftvis_amd
 from fftvis_amd import _lib, synth
 from oracle import fftvis_oracle as orc
 from tests.helpers import floored_rel, rel_l2, worst_part
-from tests.tangent_refs import (DB_SEED, DT_SEED, edge_config, empty_step_config, exact_dv_baselines, exact_dv_topo,
-                                hera_subset, hex19_config, kappa, margins, random_complex, random_dbls, random_dtopo,
-                                source_config, vis_shape)
+from tests.tangent_refs import (DB_SEED, DT_SEED, ORDERS, edge_config, edge_table_config, empty_step_config,
+                                exact_dv_baselines, exact_dv_topo, frozen_beam_dv_topo, hera_subset, hex19_config,
+                                jump_config, kappa, knot_margin, margins, order_config, random_complex, random_dbls,
+                                random_dtopo, source_config, vis_shape)
 from tests.test_gpu_basis_adjoint import _forward_base
 from tests.test_gpu_position_adjoint import C_MAX, C_MAX32, HERA_EPS, K32, K32_PART, K64_PART, _hera350
 
@@ -133,6 +144,63 @@ def test_tangent_matrix(gpu, precision, sky, beams, compat, heights):
         flat = db.copy()
         flat[:, 2] = 0.0
         assert rel_l2(_jvp(cfg, d_baselines=flat), gb) > 1e-3
+
+
+# ---- 1b. table beams at every spline order, the table's edges, order 0 on a jump -------------------------------------
+@functools.lru_cache(maxsize=None)
+def _order_reference(order, sky):
+    """The exact direction tangent of ``order_config(order, sky)`` (it does not depend on the run's precision)."""
+    cfg = order_config(order, sky)
+    dt = random_dtopo(cfg, DT_SEED)
+    return dt, exact_dv_topo(cfg, dt)
+
+
+@pytest.mark.parametrize("order,sky", [(o, "full") for o in ORDERS] + [(1, "unpol")])
+@pytest.mark.parametrize("precision", [2, 1])
+def test_direction_tangent_table_orders(gpu, precision, order, sky):
+    """The cell "cm heights, full Stokes, exact flips, complex table" at the orders the matrix does not run: 1 (bilinear,
+    the default, unrolled) and 0, 2, 4, 5 (the run-time path); unpolarized at order 1, the power table's bilinear branch."""
+    cfg = order_config(order, sky, precision)
+    dt, (et, phase, tt) = _order_reference(order, sky)
+    gt = _jvp(cfg, d_topo=dt)
+    assert gt.shape == vis_shape(cfg) and gt.dtype == (np.complex64 if precision == 1 else np.complex128)
+    _assert_close(f"table order {order} {sky} {precision}", cfg, gt, et, tt, _forward_base(cfg))
+    if order > 0:  # the beam part is a visible share of the whole
+        assert np.linalg.norm(et - phase) > 1e-3 * np.linalg.norm(et)
+
+
+def _one_row(dt, t, j):
+    out = np.zeros_like(dt)
+    out[t, j] = dt[t, j]
+    return out
+
+
+@pytest.mark.parametrize("order", [1, 3])
+@pytest.mark.parametrize("kind", ["fullsky", "horizon"])
+def test_table_edges_source_by_source(gpu, kind, order):
+    """Sources placed by hand at the edges of a table (``edge_table_config``: the azimuth wrap from both sides and, at
+    order 3, across it, the first za cell at za = 1e-2 and 3e-3, the last cell above the horizon; a table that ends at
+    the horizon), one time step, their vectors through a coordinate manager: all moved at once, and -- each source is one
+    edge -- one at a time (kappa 1.2 .. 1.7 for each)."""
+    cfg, mgr = edge_table_config(kind, order)
+    assert margins(cfg, coord_mgr=mgr)[0] > 1e-3 and (order == 3 or knot_margin(cfg, order, coord_mgr=mgr) > 1e-4)
+    dt = random_dtopo(cfg, DT_SEED)
+    for label, d in [("all", dt)] + [(f"source {j}", _one_row(dt, 0, j)) for j in range(dt.shape[1])]:
+        et, _, tt = exact_dv_topo(cfg, d, coord_mgr=mgr)
+        _assert_close(f"table edges {kind} order {order}, {label}", cfg, _jvp(cfg, d_topo=d, coord_mgr=mgr), et, tt, cfg["eps"])
+
+
+def test_order_0_with_sources_on_a_jump(gpu):
+    """Order 0 is piecewise constant: the beam term is 0 by definition, also for a source whose difference stencil
+    (1e-6 rad) straddles a jump of the table -- one 3e-7 rad from a za half-node line, one 3e-7 rad from an az half-node
+    line, the others of ``order_config(0)`` where they were.  Reference: the closed form with the beam held fixed; all
+    sources moved at once, and the two on a jump one at a time."""
+    cfg, mgr, rows = jump_config()
+    assert knot_margin(cfg, 0, coord_mgr=mgr) < 1e-6 and margins(cfg, coord_mgr=mgr)[0] > 1e-3
+    dt = random_dtopo(cfg, DT_SEED)
+    for label, d in [("all", dt)] + [(f"source {j}", _one_row(dt, 0, j)) for j in rows]:
+        et, tt = frozen_beam_dv_topo(cfg, d, coord_mgr=mgr)
+        _assert_close(f"order 0 on a jump, {label}", cfg, _jvp(cfg, d_topo=d, coord_mgr=mgr), et, tt, cfg["eps"])
 
 
 @pytest.mark.parametrize("heights,terms", [("flat", False), ("m", False), ("cm", True)])
@@ -478,12 +546,14 @@ def test_device_tensors_in_give_a_device_tensor_out(gpu):
 
 # ---- 6. against the adjoints -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("precision", [2, 1])
-@pytest.mark.parametrize("cell", [("cm", "full", "complex", False), ("flat", "unpol", "two", True), ("m", "I", "airy", True)])
+@pytest.mark.parametrize("cell", [("cm", "full", "complex", False), ("flat", "unpol", "two", True), ("m", "I", "airy", True),
+                                  ("order", 1), ("order", 0)])
 def test_dot_identity_with_the_device_adjoints(gpu, cell, precision):
     """Re <dV, G> = sum dbls . gbls + sum dtopo . gtopo between independently written passes.  Secondary: each side is one
     pass held to 10 base (fp32: K32 base) times its cancellation, so the difference is held to the sum of the two bounds,
-    relative to sum |conj(G) dV| and sum |v . g|, the sums the two sides are rounded in."""
-    cfg = source_config(*cell, precision)
+    relative to sum |conj(G) dV| and sum |v . g|, the sums the two sides are rounded in.  ("order", n): the complex table at
+    spline order n, ``order_config``."""
+    cfg = order_config(cell[1], precision=precision) if cell[0] == "order" else source_config(*cell, precision)
     cdt = np.complex64 if precision == 1 else np.complex128
     G = random_complex(vis_shape(cfg), 4).astype(cdt)
     db, dt = random_dbls(cfg, DB_SEED), random_dtopo(cfg, DT_SEED)

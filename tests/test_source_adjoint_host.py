@@ -7,6 +7,13 @@ remainder is about (k h)^4 with k = 2 pi nu |b| / c <~ 500 on these arrays (a fe
 here, the extrapolations from (h, h / 2) and from (h / 2, h / 4) agree to 5.8e-11 rel l2 of the whole (ntimes, nsrc, 3)
 result and 4.5e-11 of its largest entry at worst over the three cells below, and the reference taken in (ra, dec) agrees
 with the chained one to 5.1e-11: more than twice better than 1e-8, which is therefore the bound kept.
+
+A table beam has a reference at every spline order wherever no source sits within the stencil of a knot line
+(``knot_margin``; the condition is asserted here for every configuration the GPU modules use).  Measured here on the
+cell "cm, full Stokes, exact flips, complex table" at catalog seed 3, the two extrapolations agree to 7.4e-11 of the whole
+and 9.3e-11 at worst over the orders 0, 1, 2, 4 and 5 (G of seed 4); on the table-edge configurations every single row
+agrees to 1.5e-9 (full-sky table, order 1; 2.3e-10 at order 3) and 2.5e-10 (the table that ends at the horizon).  At
+order 0 the closed form with the beam frozen equals the differences to 2.7e-11 of the whole, 2.9e-11 of the largest entry.
 """
 
 import ctypes
@@ -17,8 +24,10 @@ import pytest
 
 import fftvis_amd
 from fftvis_amd import _lib
-from tests.source_adjoint_refs import (H_REF, exact_gradec, exact_gtopo, margins, random_complex, sidereal_jacobian,
-                                       source_config, table_config, vis_shape)
+from tests.source_adjoint_refs import (H_REF, JUMP_OFFSET, ORDERS, GivenTopo, edge_table_config, exact_gradec, exact_gtopo,
+                                       frozen_beam_gtopo, gradcheck_config, jump_config, knot_margin, margins,
+                                       order_config, random_complex, sidereal_jacobian, source_config, table_config,
+                                       table_configs, vis_shape)
 
 REF_BOUND = 1e-8
 
@@ -128,51 +137,117 @@ def test_chain_helper_against_its_closed_form():
 
 
 def _all_configs():
-    """Every configuration the GPU tests compare with the reference (``test_gpu_source_adjoint`` builds them the same way)."""
+    """(cfg, manager or None, spline order, knot bound) of every configuration the GPU tests compare with the reference
+    (``test_gpu_source_adjoint`` builds them the same way).  knot bound: what ``knot_margin`` has to exceed, None where no
+    table is differenced below order 3."""
     out = []
     for heights in ("flat", "cm", "m"):
         for sky in ("unpol", "I", "full"):
             for beams in ("airy", "two", "complex"):
-                out.append(source_config(heights, sky, beams))
-    out.append(source_config("cm", "full", "two", False, nsrc=25, ntimes=4))
-    out.append(source_config("cm", "full", "two", False, nsrc=18, nfreq=5))
-    out.append(source_config("cm", "full", "two", False, ntimes=3))
-    out.append(source_config("cm", "full", "two", False, nsrc=8, nfreq=1, ntimes=1))
-    out.append(table_config(0, nsrc=40, ntimes=4, seed=3))  # (the lane-agreement runs: no reference, the same condition)
+                out.append((source_config(heights, sky, beams), None, 3, None))
+    out.append((source_config("cm", "full", "two", False, nsrc=25, ntimes=4), None, 3, None))
+    out.append((source_config("cm", "full", "two", False, nsrc=18, nfreq=5), None, 3, None))
+    out.append((source_config("cm", "full", "two", False, ntimes=3), None, 3, None))
+    out.append((source_config("cm", "full", "two", False, nsrc=8, nfreq=1, ntimes=1), None, 3, None))
+    # (the lane-agreement runs: the device against itself, only the horizon's condition)
+    out.append((table_config(0, nsrc=40, ntimes=4, seed=3), None, 0, None))
+    out += [(cfg, mgr, order, bound) for _, cfg, order, mgr, bound in table_configs()]
+    out.append((gradcheck_config(), None, 1, 1e-4))  # a hundred times its perturbation step of 1e-6 rad
     return out
 
 
 def test_no_source_of_a_test_configuration_is_near_the_horizon_or_a_null():
-    for cfg in _all_configs():
-        hor, null = margins(cfg)
+    """... nor, where a table below order 3 is differenced, near one of its knot lines."""
+    for cfg, mgr, order, bound in _all_configs():
+        hor, null = margins(cfg, coord_mgr=mgr)
         assert hor > 1e-3 and null > 1e-3, (hor, null)
+        if bound is not None:
+            knot = knot_margin(cfg, order, coord_mgr=mgr)
+            assert knot > bound, (order, knot, bound)
+
+
+def test_knot_margin_against_hand_placed_sources():
+    """The margin finds what was placed: the figures of the seeded cell, odd and even orders half a node apart, the
+    az distance scaled by sin(za), the grid taken from the beam; and the two sources of the order-0 jump configuration
+    are the only ones near a line."""
+    assert abs(knot_margin(order_config(0), 0) - 1.30e-3) < 1e-5 and abs(knot_margin(order_config(1), 1) - 2.29e-3) < 1e-5
+    assert knot_margin(order_config(2), 2) == knot_margin(order_config(0), 0)
+    assert knot_margin(table_config(1), 1) < 1e-3  # the catalog seed of the other configurations does not satisfy it
+    assert knot_margin(source_config(), 1) == np.inf  # no table
+    cfg, mgr = edge_table_config("fullsky", 3)
+    assert abs(knot_margin(cfg, 3, mgr) - 1e-7 * np.sin(12.6 * np.pi / 45)) < 1e-12  # the source at az = 1e-7
+    assert knot_margin(cfg, 2, mgr) < 1e-12  # the near-zenith sources' mid-cell az is ON an even order's line
+    cfg, mgr = edge_table_config("horizon", 1)
+    want = 0.45 * (2 * np.pi / 90) * np.sin(0.6 * np.pi / 46)  # az 80.45 nodes at za 0.6 nodes of pi / 46
+    assert abs(knot_margin(cfg, 1, mgr) - want) < 1e-9
+    cfg, mgr, rows = jump_config()
+    assert abs(knot_margin(cfg, 0, mgr) - JUMP_OFFSET) < 1e-9 and margins(cfg, mgr)[0] > 1e-3
+    topos = mgr.topos.copy()
+    topos[0, :, rows] = [0.0, 0.0, -1.0]
+    assert knot_margin(cfg, 0, GivenTopo(cfg["times"], topos)) > 1e-3
 
 
 CELLS = [("cm", "full", "complex", False), ("flat", "unpol", "two", True), ("m", "I", "airy", True)]
+ORDER_CELLS = [("order", o) for o in ORDERS]
+EDGE_CELLS = [("fullsky", 1), ("fullsky", 3), ("horizon", 1), ("horizon", 3)]
 
 
 @functools.lru_cache(maxsize=None)
-def _cell(heights, sky, beams, compat):
-    cfg = source_config(heights, sky, beams, compat)
+def _cell(*cell):
+    """(cfg, manager or None, G, exact gtopo) of a matrix cell, of ("order", n) or of a table-edge configuration."""
+    mgr = None
+    if cell[0] == "order":
+        cfg = order_config(cell[1])
+    elif cell[0] in ("fullsky", "horizon"):
+        cfg, mgr = edge_table_config(*cell)
+    else:
+        cfg = source_config(*cell)
     G = random_complex(vis_shape(cfg), 4)
-    return cfg, G, exact_gtopo(cfg, G)
+    return cfg, mgr, G, exact_gtopo(cfg, G, coord_mgr=mgr)
 
 
-@pytest.mark.parametrize("cell", CELLS)
+@pytest.mark.parametrize("cell", CELLS + ORDER_CELLS + EDGE_CELLS)
 def test_reference_extrapolations_agree(cell):
-    """(h, h / 2) against (h / 2, h / 4): rel l2 of the whole and max |difference| / max |value| within REF_BOUND / 2."""
-    cfg, G, g1 = _cell(*cell)
-    g2 = exact_gtopo(cfg, G, h=H_REF / 2)
+    """(h, h / 2) against (h / 2, h / 4): rel l2 of the whole and max |difference| / max |value| within REF_BOUND / 2; on
+    the table-edge configurations, whose sources are placed by hand one per edge, every row's rel l2 as well."""
+    cfg, mgr, G, g1 = _cell(*cell)
+    g2 = exact_gtopo(cfg, G, coord_mgr=mgr, h=H_REF / 2)
     assert np.count_nonzero(g1) > 0 and np.isfinite(g1).all()
     whole = np.linalg.norm(g1 - g2) / np.linalg.norm(g1)
     worst = np.abs(g1 - g2).max() / np.abs(g1).max()
     print("source reference, extrapolations", cell, whole, worst)
     assert whole <= 0.5 * REF_BOUND and worst <= 0.5 * REF_BOUND, (whole, worst)
+    if cell in EDGE_CELLS:
+        rows = np.linalg.norm(g1 - g2, axis=-1) / np.linalg.norm(g1, axis=-1)
+        print("source reference, extrapolations, rows", cell, rows.max())
+        assert rows.max() <= 0.5 * REF_BOUND, rows
+
+
+def test_frozen_beam_closed_form_is_the_whole_gradient_at_order_0():
+    """Away from the jumps a piecewise-constant beam has no beam term: the closed form equals the differences.  At order 1
+    it does not (the beam term is a visible share of the gradient), and on a jump it stays finite and tangential."""
+    cfg, mgr, G, g1 = _cell("order", 0)
+    fz = frozen_beam_gtopo(cfg, G)
+    whole = np.linalg.norm(fz - g1) / np.linalg.norm(g1)
+    worst = np.abs(fz - g1).max() / np.abs(g1).max()
+    print("source reference, frozen beam at order 0", whole, worst)
+    assert whole <= REF_BOUND and worst <= REF_BOUND, (whole, worst)
+    assert np.array_equal(fz == 0, g1 == 0)
+    cfg1, _, G1, g11 = _cell("order", 1)
+    assert np.linalg.norm(frozen_beam_gtopo(cfg1, G1) - g11) > 1e-3 * np.linalg.norm(g11)
+    jcfg, jmgr, rows = jump_config()
+    fj = frozen_beam_gtopo(jcfg, G, coord_mgr=jmgr)
+    n = jmgr.topos[0].T
+    assert np.isfinite(fj).all() and np.all(np.any(fj[0, rows] != 0, axis=-1))
+    assert np.abs(np.einsum("jd,jd->j", n, fj[0])).max() <= 1e-12 * np.abs(fj).max()
+    keep = np.ones(24, bool)
+    keep[rows] = False
+    assert np.array_equal(fj[0, keep], fz[0, keep]) and np.array_equal(fj[1], fz[1])  # the others did not move
 
 
 @pytest.mark.parametrize("cell", CELLS)
 def test_reference_in_radec_is_the_chained_reference(cell):
-    cfg, G, g1 = _cell(*cell)
+    cfg, _, G, g1 = _cell(*cell)
     direct = exact_gradec(cfg, G)
     chained = np.einsum("tjd,tjdc->jc", g1, sidereal_jacobian(cfg))
     d = np.linalg.norm(direct - chained) / np.linalg.norm(direct)
@@ -184,7 +259,7 @@ def test_reference_in_radec_is_the_chained_reference(cell):
 def test_reference_is_tangential_and_zero_below_the_horizon(cell):
     from oracle import fftvis_oracle as orc
 
-    cfg, G, g1 = _cell(*cell)
+    cfg, _, G, g1 = _cell(*cell)
     m = orc.SimpleCoordinateRotation(None, cfg["times"], cfg["telescope_loc"], cfg["ra"], cfg["dec"])
     n = np.stack([orc._topo_of(m, ti).T for ti in range(len(cfg["times"]))])
     assert np.abs(np.einsum("tjd,tjd->tj", n, g1)).max() <= 1e-12 * np.abs(g1).max()
