@@ -4,7 +4,8 @@ Mirrors the reference package's public surface for the gpu backend
 (src/fftvis/__init__.py:1-31): ``simulate_vis``, the engine / evaluator factories and the
 ``gpu`` sub-package; beyond it, the adjoint of ``simulate_vis`` with respect to the fluxes
 (``simulate_vis_adjoint``) and a torch autograd entry point (``torch_simulate_vis``), and for basis beams the gradients
-with respect to the fluxes and the coefficients (``simulate_vis_basis_adjoint``, ``torch_simulate_vis_basis``), and the
+with respect to the fluxes, the coefficients and the antenna positions (``simulate_vis_basis_adjoint``,
+``torch_simulate_vis_basis``, ``torch_simulate_vis_basis_array``), and the
 gradient with respect to the antenna positions (``simulate_vis_position_adjoint``, ``torch_simulate_vis_array``) and to
 the source positions (``simulate_vis_source_adjoint``, ``torch_simulate_vis_sky``), and the forward-mode tangent along
 all three (``simulate_vis_jvp``).
@@ -29,6 +30,7 @@ from .adjoint import (  # noqa: F401
     torch_simulate_vis,
     torch_simulate_vis_array,
     torch_simulate_vis_basis,
+    torch_simulate_vis_basis_array,
     torch_simulate_vis_sky,
     topo_to_radec_gradient,
 )

@@ -282,7 +282,8 @@ def simulate_vis_basis_adjoint(
     device_astrometry: bool = False,
 ):
     """Gradients of the basis-beam simulation ``simulate_vis(..., beam=<K basis beams>, beam_coefs=C)`` with respect to
-    ``fluxes`` and to ``beam_coefs``, for a visibility-shaped ``vis`` (G = dL/dV, dL = Re sum conj(G) dV).
+    ``fluxes``, to ``beam_coefs`` and to the antenna positions, for a visibility-shaped ``vis`` (G = dL/dV,
+    dL = Re sum conj(G) dV).
 
     * ``"fluxes"``: ``A^T vis`` as ``simulate_vis_adjoint`` defines it, A the map from the fluxes to the visibilities for
       the given coefficients: Re <simulate_vis(F), vis> = <F, result> for every real F; shape and dtype of the fluxes
@@ -290,6 +291,15 @@ def simulate_vis_basis_adjoint(
     * ``"beam_coefs"``: the complex ``gcoefs`` (nant, nbasis, nfreqs) with Re <dV[C; D], vis> = Re <D, gcoefs> for every
       complex direction D, dV[C; D] the derivative of the visibilities along D (they are sesquilinear in C): what torch
       returns for a complex leaf.  It needs ``fluxes``, the forward's input.
+    * ``"baselines"``: (nbls, 3) float64, ENU per metre, every listed baseline an independent vector, with the meaning of
+      ``simulate_vis_position_adjoint``: every basis visibility M_kl is a sum over sources of strengths that do not depend
+      on the positions, so ``gbls[k, d] = -sum_{f,t,r} (2 pi nu_f / c) Im(conj(G) D_d)`` with D_d the basis simulation of
+      the fluxes times topo_d (``fv_sim_run_basis_position_adjoint``: about three forward runs whatever the number of
+      antennas).  On a coplanar array the up component is still returned.
+    * ``"ants"``: (nant, 3) float64, rows in ``ants``' iteration order: ``baseline_to_antenna_gradient`` of the baseline
+      result.
+
+    Not covered: source-position derivatives through basis beams, a lattice form, multi-GPU.
 
     ``wrt`` names the gradients wanted -- a name, or a tuple of names; the result is that gradient, or a tuple in
     ``wrt``'s order.  Only the passes asked for run; a gradient computed alone equals the one from a joint call bit for
@@ -299,8 +309,9 @@ def simulate_vis_basis_adjoint(
     the forward."""
     single = isinstance(wrt, str)
     names = (wrt,) if single else tuple(wrt)
-    if not names or any(n not in ("fluxes", "beam_coefs") for n in names) or len(set(names)) != len(names):
-        raise ValueError(f"wrt must name 'fluxes', 'beam_coefs' or both, got {wrt!r}")
+    if (not names or any(n not in ("fluxes", "beam_coefs", "ants", "baselines") for n in names)
+            or len(set(names)) != len(names)):
+        raise ValueError(f"wrt must name some of 'fluxes', 'beam_coefs', 'ants' and 'baselines', got {wrt!r}")
     if backend != "gpu":
         raise ValueError(f"Unsupported backend: {backend}")
     if beam_coefs is None:
@@ -341,10 +352,11 @@ def simulate_vis_basis_adjoint(
     rdt = np.float32 if precision == 1 else np.float64
     cdt = np.complex64 if precision == 1 else np.complex128
     want_f, want_c = "fluxes" in names, "beam_coefs" in names
+    want_p = "ants" in names or "baselines" in names
     f_shape = (nsrc, nfreqs, 2, 2) if full_stokes else (nsrc, nfreqs)
     c_shape = (len(ants), len(beam_list), nfreqs)
     on_device = _is_tensor(vis) and vis.device.type == "cuda"
-    gflux = gcoefs = None
+    gflux = gcoefs = gbls = None
     if on_device:
         import torch
 
@@ -357,6 +369,8 @@ def simulate_vis_basis_adjoint(
                                 device=vis.device)
         if want_c:
             gcoefs = torch.zeros(c_shape, dtype=tc, device=vis.device)
+        if want_p:
+            gbls = torch.zeros((nbls, 3), dtype=torch.float64, device=vis.device)
         torch.cuda.synchronize(vis.device)  # the library's streams do not follow torch's: g and the outputs are complete
     else:
         g = vis.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(vis) else vis
@@ -365,13 +379,15 @@ def simulate_vis_basis_adjoint(
             gflux = np.zeros(f_shape, dtype=cdt if full_stokes else rdt)
         if want_c:
             gcoefs = np.zeros(c_shape, dtype=cdt)
+        if want_p:
+            gbls = np.zeros((nbls, 3), dtype=np.float64)
 
     from .wrapper import create_simulation_engine, device_chunks
 
     engine = create_simulation_engine(backend=backend, device=device)
     nchunks = device_chunks(device, max_memory, min_chunks, beam_list, 2, 2, len(ants), nsrc, precision,
                             source_buffer, nfreqs)
-    gc, gk = engine.simulate(
+    got = engine.simulate(  # (gflux, gcoefs[, gbls]): the buffers above, filled in place
         ants=ants, freqs=np.asarray(freqs), fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=None,
         ra=ra, dec=dec, times=times, telescope_loc=telescope_loc, baselines=baselines,
         precision=precision, polarized=True, eps=eps, upsample_factor=upsample_factor,
@@ -381,13 +397,18 @@ def simulate_vis_basis_adjoint(
         force_use_type3=force_use_type3, force_use_ray=force_use_ray, trace_mem=trace_mem,
         nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
         reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
-        beam_coefs=beam_coefs.astype(cdt, copy=False), adjoint_of=(g, gflux, gcoefs),
+        beam_coefs=beam_coefs.astype(cdt, copy=False), adjoint_of=(g, gflux, gcoefs, gbls),
     )
+    gc, gk = got[0], got[1]
     res = {}
     if want_f:
         res["fluxes"] = stokes_adjoint(gc, full_stokes)
     if want_c:
         res["beam_coefs"] = gk
+    if "baselines" in names:
+        res["baselines"] = gbls
+    if "ants" in names:
+        res["ants"] = baseline_to_antenna_gradient(gbls, ants, baselines)
     if _is_tensor(vis) and not on_device:  # a host tensor in, host tensors out
         import torch
 
@@ -460,6 +481,85 @@ def torch_simulate_vis_basis(fluxes, beam_coefs, **kwargs):
     return _FN_BASIS.apply(fluxes, beam_coefs, kwargs)
 
 
+def _basis_array_autograd_function():
+    import torch
+
+    class _SimulateVisBasisArray(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fluxes, beam_coefs, antpos, antnums, kwargs):
+            from .wrapper import simulate_vis
+
+            ctx.kwargs = kwargs
+            ctx.antnums = antnums
+            ctx.flux_dtype, ctx.coef_dtype, ctx.pos_dtype = fluxes.dtype, beam_coefs.dtype, antpos.dtype
+            ctx.coef_device, ctx.pos_device = beam_coefs.device, antpos.device
+            ctx.save_for_backward(fluxes, beam_coefs, antpos)
+            ctx.save_for_forward(fluxes, beam_coefs, antpos)
+            ants = dict(zip(antnums, antpos.detach().cpu().numpy().astype(np.float64)))
+            vis = simulate_vis(ants=ants, fluxes=fluxes.detach().cpu().numpy(),
+                               beam_coefs=beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy(), **kwargs)
+            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            fluxes, beam_coefs, antpos = ctx.saved_tensors
+            wrt = tuple(n for n, need in zip(("fluxes", "beam_coefs", "ants"), ctx.needs_input_grad[:3]) if need)
+            if not wrt:
+                return None, None, None, None, None
+            ants = dict(zip(ctx.antnums, antpos.detach().cpu().numpy().astype(np.float64)))
+            got = dict(zip(wrt, simulate_vis_basis_adjoint(grad_output, ants=ants, fluxes=fluxes, beam_coefs=beam_coefs,
+                                                           wrt=wrt, **ctx.kwargs)))
+            out = []
+            for name, dt, dev in (("fluxes", ctx.flux_dtype, grad_output.device), ("beam_coefs", ctx.coef_dtype, ctx.coef_device),
+                                  ("ants", ctx.pos_dtype, ctx.pos_device)):
+                g = got.get(name)
+                if g is not None and not _is_tensor(g):
+                    g = torch.from_numpy(g)
+                out.append(None if g is None else g.to(device=dev, dtype=dt))
+            return out[0], out[1], out[2], None, None
+
+        @staticmethod
+        def jvp(ctx, d_fluxes, d_beam_coefs, d_antpos, *_):
+            # a missing tangent (None) skips its part
+            fluxes, beam_coefs, antpos = ctx.saved_tensors
+            if d_fluxes is None and d_beam_coefs is None and d_antpos is None:
+                return None
+            ants = dict(zip(ctx.antnums, antpos.detach().cpu().numpy().astype(np.float64)))
+            dv = simulate_vis_basis_jvp(ants=ants, fluxes=fluxes, beam_coefs=beam_coefs,
+                                        d_beam_coefs=None if d_beam_coefs is None else d_beam_coefs.detach(),
+                                        d_fluxes=None if d_fluxes is None else d_fluxes.detach(),
+                                        d_ants=None if d_antpos is None else d_antpos.detach(), **ctx.kwargs)
+            return _tangent_tensor(dv, fluxes)
+
+    return _SimulateVisBasisArray
+
+
+_FN_BASIS_ARRAY = None
+
+
+def torch_simulate_vis_basis_array(fluxes, beam_coefs, antpos, *, antnums=None, **kwargs):
+    """The basis-beam simulation as a torch operation differentiable in the fluxes, the coefficients and the antenna
+    positions -- the three unknowns of a joint beam and array fit: ``fluxes`` real, (nsrc, nfreqs) or (nsrc, nfreqs, 4);
+    ``beam_coefs`` complex, (nant, nbasis, nfreqs); ``antpos`` real, (nant, 3), ENU metres.  ``antnums`` gives the
+    dictionary keys ``baselines`` refers to (default ``range(nant)``); every other argument is a keyword of
+    ``simulate_vis`` -- but for ``ants``, which ``antpos`` replaces (TypeError).  Returns the visibilities as a complex
+    tensor on ``fluxes``' device.  The backward pass is one ``simulate_vis_basis_adjoint`` call with only the gradients
+    autograd asks for (``ctx.needs_input_grad``); forward mode (``torch.autograd.forward_ad``) runs
+    ``simulate_vis_basis_jvp`` on the tangents present."""
+    global _FN_BASIS_ARRAY
+    if "ants" in kwargs:
+        raise TypeError("torch_simulate_vis_basis_array takes the antenna positions as the tensor antpos (and antnums), "
+                        "not ants=")
+    if antpos.ndim != 2 or antpos.shape[1] != 3 or antpos.is_complex():
+        raise ValueError(f"antpos must be a real (nant, 3) tensor, got {tuple(antpos.shape)} {antpos.dtype}")
+    antnums = list(range(antpos.shape[0])) if antnums is None else list(antnums)
+    if len(antnums) != antpos.shape[0] or len(set(antnums)) != len(antnums):
+        raise ValueError("antnums must give one distinct key per row of antpos")
+    if _FN_BASIS_ARRAY is None:
+        _FN_BASIS_ARRAY = _basis_array_autograd_function()
+    return _FN_BASIS_ARRAY.apply(fluxes, beam_coefs, antpos, tuple(antnums), kwargs)
+
+
 # device bytes of one call's (ndir, ...) output: longer stacks of directions are cut into groups under it
 BASIS_TANGENT_BYTES_ENV = "FFTVIS_BASIS_TANGENT_BYTES"
 BASIS_TANGENT_BYTES_DEFAULT = 1 << 30
@@ -478,6 +578,8 @@ def simulate_vis_basis_jvp(
     *,
     d_beam_coefs=None,
     d_fluxes=None,
+    d_ants=None,
+    d_baselines=None,
     beam_idx: np.ndarray = None,
     baselines: list = None,
     precision: int = 2,
@@ -506,15 +608,15 @@ def simulate_vis_basis_jvp(
     device_astrometry: bool = False,
 ):
     """Forward-mode tangent (Jacobian-vector product) of the basis-beam simulation ``simulate_vis(..., beam=<K basis
-    beams>, beam_coefs=C)`` along directions of the coefficients and of the fluxes,
+    beams>, beam_coefs=C)`` along directions of the coefficients, of the fluxes and of the antenna positions,
 
-        dV = dV[C; d_beam_coefs]  +  dV/d(fluxes) . d_fluxes,
+        dV = dV[C; d_beam_coefs]  +  dV/d(fluxes) . d_fluxes  +  dV/d(ants) . d_ants,
         dV_b[C; D] = sum_kl ( conj(D[a1,k]) C[a2,l] + conj(C[a1,k]) D[a2,l] ) M_kl(b),
 
     M_kl the visibilities of basis beams k and l.  They depend on neither C nor D, so the coefficient part is one forward
     run whose gather carries the differentiated weights (``fv_sim_run_basis_tangent``), and any number of directions share
     its transforms.  It is the transpose of ``simulate_vis_basis_adjoint``: for every G,
-    ``Re <dV, G> = Re <d_beam_coefs, gcoefs> + <d_fluxes, gflux>``.
+    ``Re <dV, G> = Re <d_beam_coefs, gcoefs> + <d_fluxes, gflux> + d_baselines . gbls``.
 
     * ``d_beam_coefs``: complex, (nant, nbasis, nfreqs) -- the result has ``simulate_vis``'s shape and dtype -- or a stack
       (ndir, nant, nbasis, nfreqs) -- the result gains a leading ``ndir`` axis, direction q equal, bit for bit, to the call
@@ -523,6 +625,13 @@ def simulate_vis_basis_jvp(
     * ``d_fluxes``: ``fluxes``' shape.  The map is linear in the fluxes, so this part is one ``simulate_vis(...,
       beam_coefs=C)`` run on ``d_fluxes``, added to the rest.  It combines with an unbatched ``d_beam_coefs`` only: with a
       stack it is a ValueError (flux directions are plain forward runs).
+    * ``d_ants``: (nant, 3), ENU metres, rows in ``ants``' iteration order, turned into ``d_baselines`` on the host
+      (``antenna_to_baseline_tangent``); ``d_baselines``: (nbls, 3), every listed baseline an independent vector.  Giving
+      both is a ValueError.  The part is ``sum_d i (2 pi nu / c) d_baselines[k, d] D_d`` with D_d the basis simulation of the
+      fluxes times topo_d (``fv_sim_run_basis_position_tangent``: about three forward runs), added to the rest; on a flat
+      array the up component still enters.  With a stack of ``d_beam_coefs`` it is a ValueError.
+
+    Not covered: source-position tangents through basis beams, a lattice form, several position directions per call.
 
     No input at all gives zeros.  numpy arrays, or torch tensors: when a tangent is a tensor on the run's device
     ``d_beam_coefs`` is handed over by pointer and the result is a tensor on that device; host tensors in, a host tensor
@@ -530,6 +639,8 @@ def simulate_vis_basis_jvp(
     be True and ``beam_idx`` None, as for the forward."""
     import os
 
+    if d_ants is not None and d_baselines is not None:
+        raise ValueError("give the antenna tangent as d_ants or as d_baselines, not both")
     if backend != "gpu":
         raise ValueError(f"Unsupported backend: {backend}")
     if beam_coefs is None:
@@ -574,11 +685,18 @@ def simulate_vis_basis_jvp(
         if stacked and d_fluxes is not None:
             raise ValueError("d_fluxes combines with one direction of the coefficients only, not with a stack "
                              "(flux directions are plain simulate_vis runs)")
+        if stacked and (d_ants is not None or d_baselines is not None):
+            raise ValueError("a position tangent (d_ants / d_baselines) combines with one direction of the coefficients "
+                             "only, not with a stack")
+    if d_ants is not None:
+        d_baselines = antenna_to_baseline_tangent(d_ants, ants, baselines)
+    if d_baselines is not None and tuple(d_baselines.shape) != (nbls, 3):
+        raise ValueError(f"d_baselines must have shape ({nbls}, 3), got {tuple(d_baselines.shape)}")
     try:
         budget = float(os.environ.get(BASIS_TANGENT_BYTES_ENV, BASIS_TANGENT_BYTES_DEFAULT))
     except ValueError:
         raise ValueError(f"{BASIS_TANGENT_BYTES_ENV} must be a number of bytes") from None
-    tangents = (d_beam_coefs, d_fluxes)
+    tangents = (d_beam_coefs, d_fluxes, d_ants, d_baselines)
     any_tensor = any(_is_tensor(x) for x in tangents)
     dev_tensor = next((x for x in tangents if _is_tensor(x) and x.device.type == "cuda"), None)
     on_device = dev_tensor is not None
@@ -629,6 +747,22 @@ def simulate_vis_basis_jvp(
             engine.simulate(fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=None, nchunks=nchunks,
                             beam_coefs=beam_coefs.astype(cdt, copy=False), basis_tangent_of=(dd[q0:q1], dv[q0:q1]),
                             **common)
+    if d_baselines is not None:
+        from .wrapper import create_simulation_engine, device_chunks
+
+        if on_device:
+            db = d_baselines.detach() if _is_tensor(d_baselines) else torch.from_numpy(np.ascontiguousarray(d_baselines))
+            db = db.to(device=tdev, dtype=torch.float64).contiguous()
+            dp = torch.zeros(shape, dtype=tc, device=tdev)
+            torch.cuda.synchronize(tdev)  # the library's streams do not follow torch's: db and dp are complete
+        else:
+            db = np.ascontiguousarray(host(d_baselines), dtype=np.float64)
+            dp = np.zeros(shape, dtype=cdt)
+        engine = create_simulation_engine(backend=backend, device=device)
+        nchunks = device_chunks(device, max_memory, min_chunks, beam_list, 2, 2, len(ants), nsrc, precision,
+                                source_buffer, nfreqs)
+        dv[0] += engine.simulate(fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=None, nchunks=nchunks,
+                                 beam_coefs=beam_coefs.astype(cdt, copy=False), tangent_of=(db, None, dp), **common)
     if d_fluxes is not None:
         from .wrapper import simulate_vis
 
@@ -729,13 +863,15 @@ def simulate_vis_position_adjoint(
     run's device (handed over by pointer; the results are then tensors on that device).  Every other keyword means what it
     means for ``simulate_vis``, ``reference_compat`` included; ``force_use_type3`` is accepted and always on: the pass runs
     the type-3 transform (about three forward runs whatever the number of antennas), so an ideal lattice array works and
-    takes its redundant runs.  Not covered: ``beam_coefs`` (NotImplementedError), a type-1 (lattice) form of the pass."""
+    takes its redundant runs.  Not covered: ``beam_coefs`` (NotImplementedError; ``simulate_vis_basis_adjoint`` has
+    ``wrt="ants"``), a type-1 (lattice) form of the pass."""
     single = isinstance(wrt, str)
     names = (wrt,) if single else tuple(wrt)
     if not names or any(n not in ("ants", "baselines") for n in names) or len(set(names)) != len(names):
         raise ValueError(f"wrt must name 'ants', 'baselines' or both, got {wrt!r}")
     if beam_coefs is not None:
-        raise NotImplementedError("simulate_vis_position_adjoint does not support basis beams (beam_coefs)")
+        raise NotImplementedError("simulate_vis_position_adjoint does not support basis beams (beam_coefs): "
+                                  "simulate_vis_basis_adjoint(wrt='ants') does")
     if backend != "gpu":
         raise ValueError(f"Unsupported backend: {backend}")
     if eps is None:
@@ -878,7 +1014,8 @@ def torch_simulate_vis_array(fluxes, antpos, *, antnums=None, **kwargs):
     if "ants" in kwargs:
         raise TypeError("torch_simulate_vis_array takes the antenna positions as the tensor antpos (and antnums), not ants=")
     if kwargs.get("beam_coefs") is not None:
-        raise NotImplementedError("torch_simulate_vis_array does not support basis beams (beam_coefs)")
+        raise NotImplementedError("torch_simulate_vis_array does not support basis beams (beam_coefs): "
+                                  "torch_simulate_vis_basis_array does")
     if antpos.ndim != 2 or antpos.shape[1] != 3 or antpos.is_complex():
         raise ValueError(f"antpos must be a real (nant, 3) tensor, got {tuple(antpos.shape)} {antpos.dtype}")
     antnums = list(range(antpos.shape[0])) if antnums is None else list(antnums)
@@ -1186,9 +1323,11 @@ def simulate_vis_jvp(
     the position tangents are handed over by pointer and the result is a tensor on that device; host tensors in, a host
     tensor out.  Every other keyword means what it means for ``simulate_vis``, ``reference_compat`` included;
     ``force_use_type3`` is accepted and always on for the position parts: the pass runs the type-3 transform.  Not
-    covered: ``beam_coefs`` (NotImplementedError), a type-1 (lattice) form of the pass."""
+    covered: ``beam_coefs`` (NotImplementedError; ``simulate_vis_basis_jvp`` takes ``d_ants`` / ``d_baselines``), a type-1
+    (lattice) form of the pass."""
     if beam_coefs is not None:
-        raise NotImplementedError("simulate_vis_jvp does not support basis beams (beam_coefs)")
+        raise NotImplementedError("simulate_vis_jvp does not support basis beams (beam_coefs): "
+                                  "simulate_vis_basis_jvp(d_ants=) does")
     if d_ants is not None and d_baselines is not None:
         raise ValueError("give the antenna tangent as d_ants or as d_baselines, not both")
     if d_radec is not None and d_topo is not None:

@@ -626,7 +626,7 @@ int fv_sim_run_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const
                    "on_device flags must be 0 or 1");
         FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->run_position_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gbls, gbls_on_device, accumulate);
+        h->impl->run_position_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gbls, gbls_on_device, accumulate, false);
     });
 }
 int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
@@ -649,7 +649,7 @@ int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *
                        (out_on_device == 0 || out_on_device == 1),
                    "on_device flags must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->run_tangent(t0, t1, f0, f1, dbls, dbls_on_device, dtopo, dtopo_on_device, out, out_on_device);
+        h->impl->run_tangent(t0, t1, f0, f1, dbls, dbls_on_device, dtopo, dtopo_on_device, out, out_on_device, false);
     });
 }
 int fv_sim_run_basis_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir,
@@ -662,6 +662,28 @@ int fv_sim_run_basis_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const vo
                    "on_device flags must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_basis_tangent(t0, t1, f0, f1, dcoefs, dcoefs_on_device, ndir, out, out_on_device);
+    });
+}
+int fv_sim_run_basis_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device,
+                                      double *gbls, int gbls_on_device, int accumulate) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(gvis && gbls, "null adjoint input or output");
+        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gbls_on_device == 0 || gbls_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_position_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gbls, gbls_on_device, accumulate, true);
+    });
+}
+int fv_sim_run_basis_position_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device,
+                                      void *out, int out_on_device) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(out, "null output");
+        FV_REQUIRE(dbls, "null baseline directions (dbls)");
+        FV_REQUIRE((dbls_on_device == 0 || dbls_on_device == 1) && (out_on_device == 0 || out_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_tangent(t0, t1, f0, f1, dbls, dbls_on_device, nullptr, 0, out, out_on_device, true);
     });
 }
 int fv_sim_sync(fv_sim *h) { FV_SIM_CALL(h->impl->sync()); }

@@ -2446,6 +2446,13 @@ struct InterpArgs {
     //     i nu_f tg_w[km] V     (a weighted round: tg_w fp64 by global baseline id, nu_f = scale[fg], the channel's own),
     //     V                     (tg_w == nullptr: the beam term's round).
     // A pair's list holds every baseline once: one owner thread per slot and launch, plain read-modify-write.
+    // With basis beams (k_interp<.., BPOS>; Sim::run_basis_position_adjoint / _tangent; weighted rounds only) the two
+    // epilogues carry the forward's basis weights w1 = conj(C[a1,kk]) C[a2,ll] and w2 = conj(C[a1,ll]) C[a2,kk], formed
+    // and applied in fp64; basis_part and negate_all as in the forward:
+    //   BPOS 1:  S += sum_r conj(G_r) w1 V_r + sum_r conj(G_rs) w2 V_r  into the member's ONE slot of gs, here
+    //            (gs_nf, gs_nbls) complex fp64 -- slot (gs_f0 + fg) gs_nbls + baseline, whatever the term: the terms of a
+    //            round add up across launches (one owner thread per slot and launch, one stream per buffer);
+    //   BPOS 2:  i nu_f tg_w[km] w1 V at the member's slot and i nu_f tg_w[km] w2 V at the feed-transposed slot.
     const double *tg_w;
     // Basis tangent epilogue (k_interp<.., BTAN>; Sim::run_basis_tangent): the forward's basis epilogue with differentiated
     // weights.  Where the forward adds w1 V / w2 V, every direction q < bt_ndir adds, with D_q = bt_d + q bt_d_stride laid
@@ -2499,6 +2506,12 @@ __device__ inline cplx<double> btan_weight(cplx<T> c1, cplx<T> c2, cplx<T> d1, c
     return {x.re + y.re, x.im + y.im};
 }
 
+// conj(c1) c2 in fp64: the basis weight of one term (k_interp<.., BPOS>)
+template <typename T>
+__device__ inline cplx<double> basis_weight(cplx<T> c1, cplx<T> c2) {
+    return cmul(cplx<double>{(double)c1.re, -(double)c1.im}, cplx<double>{(double)c2.re, (double)c2.im});
+}
+
 // HERM (Hermitian strengths): the grid holds two transforms per frequency instead of four --
 //   T1 = F[c_00 + i c_11]  (both real),   T2 = F[c_01]   (c_10 = conj(c_01)) --
 // and the four products are rebuilt from their values at the target s and at its mirror image -s:
@@ -2516,9 +2529,10 @@ __device__ inline cplx<double> btan_weight(cplx<T> c1, cplx<T> c2, cplx<T> d1, c
 // ZD (direct third dimension, InterpArgs::zd_n) and WT (height terms, InterpArgs::wt_k) are compile-time: carried as run-time
 // branches they cost the plain 2-D gather 47 registers (146 -> 193 fp64, 98 -> 177 fp32: a wave per SIMD, 11-24 % of its time).
 // GRAD (InterpArgs::gs), TANGENT (InterpArgs::tg_w) and BTAN (InterpArgs::bt_d) are epilogues of their own passes, compile-time
-// for the same reason.
+// for the same reason.  BPOS: the position passes through basis beams (Sim::run_basis_position_adjoint / _tangent) -- 1 the
+// gradient epilogue, 2 the tangent epilogue, each with the basis weights applied in the gather (InterpArgs::gs / tg_w).
 template <typename T, int DIM, bool HERM, int NR, bool ZD = false, bool WT = false, bool GRAD = false, bool TANGENT = false,
-          bool BTAN = false>
+          bool BTAN = false, int BPOS = 0>
 __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
     const cplx<T> *__restrict__ grid, int64_t N, const T *__restrict__ bt0,
     const T *__restrict__ bt1, const T *__restrict__ bt2, const int *__restrict__ bl_idx,
@@ -2794,6 +2808,43 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                     }
                     continue;
                 }
+                if constexpr (BPOS != 0) {  // the position passes' epilogues with the basis weights (+ the transposed term's)
+                    const int f = a.f_first + fg;
+                    const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
+                    const bool t1 = a.basis_part != 2, t2 = a.kk != a.ll && a.basis_part != 1;
+                    const cplx<double> V = {vr, vim_};
+                    cplx<double> v1 = {0.0, 0.0}, v2 = {0.0, 0.0};
+                    if (t1) v1 = cmul(basis_weight(coef[(cs1 + a.kk) * a.ncoef_freq + f], coef[(cs2 + a.ll) * a.ncoef_freq + f]), V);
+                    if (t2) v2 = cmul(basis_weight(coef[(cs1 + a.ll) * a.ncoef_freq + f], coef[(cs2 + a.kk) * a.ncoef_freq + f]), V);
+                    cplx<T> *o2 = ob + a.out_pol_off[(r & 1) * 2 + (r >> 1)];  // feed-transposed slot
+                    if constexpr (BPOS == 1) {  // conj(G) (w V) over both slots into the member's one slot of S
+                        cplx<double> sum = {0.0, 0.0};
+                        if (t1) {
+                            const cplx<T> g1 = *o;
+                            sum.re += (double)g1.re * v1.re + (double)g1.im * v1.im;
+                            sum.im += (double)g1.re * v1.im - (double)g1.im * v1.re;
+                        }
+                        if (t2) {
+                            const cplx<T> g2 = *o2;
+                            sum.re += (double)g2.re * v2.re + (double)g2.im * v2.im;
+                            sum.im += (double)g2.re * v2.im - (double)g2.im * v2.re;
+                        }
+                        cplx<double> *s = (cplx<double> *)a.gs + ((int64_t)(a.gs_f0 + fg)) * a.gs_nbls + km;
+                        s->re += sum.re;
+                        s->im += sum.im;
+                    } else {  // i nu_f w (w1 V) and i nu_f w (w2 V)
+                        const double wq = sc * a.tg_w[km];
+                        if (t1) {
+                            o->re += (T)(-wq * v1.im);
+                            o->im += (T)(wq * v1.re);
+                        }
+                        if (t2) {
+                            o2->re += (T)(-wq * v2.im);
+                            o2->im += (T)(wq * v2.re);
+                        }
+                    }
+                    continue;
+                }
                 if (a.basis) {
                     const int f = a.f_first + fg;
                     const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
@@ -2856,7 +2907,7 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
             cplx<T> *ob = out + (int64_t)fg * a.out_fg_stride + km * a.out_k_stride;
             cplx<double> w1 = {1.0, 0.0}, w2 = {0.0, 0.0};
             cplx<double> s1 = {0.0, 0.0}, s2 = {0.0, 0.0};  // GRAD: this member's inner products over the four products
-            if (a.basis && !GRAD && !BTAN) {  // eigenbeam term (k, l): vis += conj(C[a1,k]) C[a2,l] V  (+ the transposed (l, k) term)
+            if (a.basis && !GRAD && !BTAN && BPOS == 0) {  // eigenbeam term (k, l): vis += conj(C[a1,k]) C[a2,l] V  (+ the transposed (l, k) term)
                 const int f = a.f_first + fg;
                 const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
                 const cplx<T> c1k = coef[(cs1 + a.kk) * a.ncoef_freq + f];
@@ -2905,6 +2956,53 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                             o2->im += (T)v2.im;
                         }
                     }
+                }
+                continue;
+            }
+            if constexpr (BPOS != 0) {  // the position passes' epilogues with the basis weights, over the four products
+                const int f = a.f_first + fg;
+                const int64_t cs1 = (int64_t)ant1[km] * a.nbasis, cs2 = (int64_t)ant2[km] * a.nbasis;
+                const bool t1 = a.basis_part != 2, t2 = a.kk != a.ll && a.basis_part != 1;
+                const bool tf = a.transpose_flipped && neg;
+                cplx<double> w1p = {0.0, 0.0}, w2p = {0.0, 0.0};
+                if (t1) w1p = basis_weight(coef[(cs1 + a.kk) * a.ncoef_freq + f], coef[(cs2 + a.ll) * a.ncoef_freq + f]);
+                if (t2) w2p = basis_weight(coef[(cs1 + a.ll) * a.ncoef_freq + f], coef[(cs2 + a.kk) * a.ncoef_freq + f]);
+                double wq = 0.0;
+                if constexpr (BPOS == 2) wq = sc * a.tg_w[km];
+                cplx<double> sum = {0.0, 0.0};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double xr = o_re[r] * wf.re - o_im[r] * wf.im, xi = o_re[r] * wf.im + o_im[r] * wf.re;
+                    const cplx<double> V = {xr, neg ? -xi : xi};
+                    cplx<T> *o = ob + a.out_pol_off[tf ? (r & 1) * 2 + (r >> 1) : r];
+                    cplx<T> *o2 = ob + a.out_pol_off[(r & 1) * 2 + (r >> 1)];  // feed-transposed slot
+                    if (t1) {
+                        const cplx<double> v1 = cmul(w1p, V);
+                        if constexpr (BPOS == 1) {
+                            const cplx<T> g1 = *o;
+                            sum.re += (double)g1.re * v1.re + (double)g1.im * v1.im;
+                            sum.im += (double)g1.re * v1.im - (double)g1.im * v1.re;
+                        } else {
+                            o->re += (T)(-wq * v1.im);
+                            o->im += (T)(wq * v1.re);
+                        }
+                    }
+                    if (t2) {
+                        const cplx<double> v2 = cmul(w2p, V);
+                        if constexpr (BPOS == 1) {
+                            const cplx<T> g2 = *o2;
+                            sum.re += (double)g2.re * v2.re + (double)g2.im * v2.im;
+                            sum.im += (double)g2.re * v2.im - (double)g2.im * v2.re;
+                        } else {
+                            o2->re += (T)(-wq * v2.im);
+                            o2->im += (T)(wq * v2.re);
+                        }
+                    }
+                }
+                if constexpr (BPOS == 1) {
+                    cplx<double> *s = (cplx<double> *)a.gs + ((int64_t)(a.gs_f0 + fg)) * a.gs_nbls + km;
+                    s->re += sum.re;
+                    s->im += sum.im;
                 }
                 continue;
             }
@@ -3040,6 +3138,9 @@ struct BasisTerm {
     void *gs = nullptr;
     int gs_nf = 0, gs_f0 = 0;
     int64_t gs_nbls = 0;
+    // the position adjoint through basis beams (k_interp<.., BPOS = 1>): gs is one round's (gs_nf, gs_nbls) block and the
+    // gather applies the basis weights itself
+    bool gs_weighted = false;
     // basis tangent epilogue (InterpArgs::bt_d): ndir directions of the coefficients, device (ndir, nant, K, nfreq), each
     // added into its own copy of the output block, out_stride elements apart; nullptr: the forward's epilogue
     const void *dcoef = nullptr;
@@ -4069,6 +4170,24 @@ bool Nufft3<T>::prepare_fused_gather(int64_t N, const T *btx, const T *bty, cons
     return true;
 }
 
+// k_interp<.., BPOS>'s instantiation for a launch: the forward's choice of (dimension, packing, rows, direct third
+// dimension | height terms)
+template <typename T, int BPOS>
+auto interp_bpos_kernel(int gdim, bool herm, bool r9, bool zd, bool wt) {
+    constexpr bool F = false;
+    auto kern = gdim == 2 ? (herm ? (r9 ? k_interp<T, 2, true, 9, F, F, F, F, F, BPOS> : k_interp<T, 2, true, 16, F, F, F, F, F, BPOS>)
+                                  : (r9 ? k_interp<T, 2, false, 9, F, F, F, F, F, BPOS> : k_interp<T, 2, false, 16, F, F, F, F, F, BPOS>))
+                          : (herm ? (r9 ? k_interp<T, 3, true, 9, F, F, F, F, F, BPOS> : k_interp<T, 3, true, 16, F, F, F, F, F, BPOS>)
+                                  : (r9 ? k_interp<T, 3, false, 9, F, F, F, F, F, BPOS> : k_interp<T, 3, false, 16, F, F, F, F, F, BPOS>));
+    if (zd)
+        kern = herm ? (r9 ? k_interp<T, 2, true, 9, true, F, F, F, F, BPOS> : k_interp<T, 2, true, 16, true, F, F, F, F, BPOS>)
+                    : (r9 ? k_interp<T, 2, false, 9, true, F, F, F, F, BPOS> : k_interp<T, 2, false, 16, true, F, F, F, F, BPOS>);
+    if (wt)
+        kern = herm ? (r9 ? k_interp<T, 2, true, 9, F, true, F, F, F, BPOS> : k_interp<T, 2, true, 16, F, true, F, F, F, BPOS>)
+                    : (r9 ? k_interp<T, 2, false, 9, F, true, F, F, F, BPOS> : k_interp<T, 2, false, 16, F, true, F, F, F, BPOS>);
+    return kern;
+}
+
 template <typename T>
 void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, const int *bl_idx,
                        const signed char *flip, const double *scale_dev, int nfg, int tpol,
@@ -4189,7 +4308,8 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
             kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true, true> : k_interp<T, 2, true, 16, false, true, true>)
                         : (r9 ? k_interp<T, 2, false, 9, false, true, true> : k_interp<T, 2, false, 16, false, true, true>);
     }
-    if (tan) {  // the tangent epilogue's instantiations (no basis beams, never together with the gradient epilogue)
+    const int bpos = basis && basis->nbasis > 0 ? (a.gs && basis->gs_weighted ? 1 : tan ? 2 : 0) : 0;
+    if (tan && !bpos) {  // the tangent epilogue's instantiations (no basis beams, never together with the gradient epilogue)
         FV_REQUIRE(!basis && !a.gs, "tangent epilogue: no basis term and no gradient epilogue");
         a.tg_w = tan->w;
         kern = gdim == 2 ? (herm ? (r9 ? k_interp<T, 2, true, 9, false, false, false, true> : k_interp<T, 2, true, 16, false, false, false, true>)
@@ -4216,6 +4336,13 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
         if (wt)
             kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true, false, false, true> : k_interp<T, 2, true, 16, false, true, false, false, true>)
                         : (r9 ? k_interp<T, 2, false, 9, false, true, false, false, true> : k_interp<T, 2, false, 16, false, true, false, false, true>);
+    }
+    if (bpos) {  // the position passes through basis beams: a basis term, and either S or a weighted tangent round
+        FV_REQUIRE(!a.bt_d && (bpos == 1 ? !tan && a.gs_nbls > 0 && a.gs_nf >= a.gs_f0 + nfg : !a.gs && tan->w != nullptr),
+                   "basis position epilogue: a basis term with its S block or its round's weights");
+        if (bpos == 2) a.tg_w = tan->w;
+        kern = bpos == 1 ? interp_bpos_kernel<T, 1>(gdim, herm != 0, r9, zd, wt != nullptr)
+                         : interp_bpos_kernel<T, 2>(gdim, herm != 0, r9, zd, wt != nullptr);
     }
     hipLaunchKernelGGL(kern, grid, dim3(INTERP_THREADS), 0, stream, (const cplx<T> *)grid_out, N, bt[0], bt[1], bt[2],
                        bl_idx, flip, scale_dev, a, ker, out, coef, ant1, ant2, ustart, upairs);

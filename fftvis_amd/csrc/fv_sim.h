@@ -2054,12 +2054,14 @@ struct SimBase {
                              int gflux_on_device, int accumulate) = 0;
     virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                                    int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate) = 0;
+    // basis: the entry point's kind of handle -- false fv_sim_run_position_adjoint / fv_sim_run_tangent (no basis beams),
+    // true fv_sim_run_basis_position_adjoint / fv_sim_run_basis_position_tangent (a handle with fv_sim_set_basis)
     virtual void run_position_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
-                                      int gbls_on_device, int accumulate) = 0;
+                                      int gbls_on_device, int accumulate, bool basis) = 0;
     virtual void run_source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
                                     int gtopo_on_device, int accumulate) = 0;
     virtual void run_tangent(int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
-                             int dtopo_on_device, void *out, int out_on_device) = 0;
+                             int dtopo_on_device, void *out, int out_on_device, bool basis) = 0;
     virtual void run_basis_tangent(int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir, void *out,
                                    int out_on_device) = 0;
     // Host destination of the next run (fv_sim_run_into): `out` is then a block INSIDE a larger array -- channel f of
@@ -4073,6 +4075,7 @@ class Sim : public SimBase {
                         bt.gs_nf = r.nf;
                         bt.gs_f0 = fa - f0;
                         bt.gs_nbls = nbls;
+                        bt.gs_weighted = nbasis && r.moments;  // positions through basis beams: every term into round rd's block
                     }
                     if (r.bt_d) {
                         bt.dcoef = r.bt_d;
@@ -4663,12 +4666,20 @@ class Sim : public SimBase {
     // The pass is coef_pass's: per channel block the forward's own stages; per (time, chunk, group, pair, height term) one
     // k_strengths_moments launch and three rounds of spread -> FFT -> gradient gather (k_interp<.., GRAD> without basis
     // beams) into the (3, channels of the block, nbls) complex fp64 S buffer of the stream; k_posgrad_reduce contracts.
+    // Basis beams (fv_sim_run_basis_position_adjoint): V_b = sum_kl conj(C[a1,k]) C[a2,l] M_kl(b) and every M_kl is such a
+    // sum with strengths that do not depend on the positions, so D'_d is the basis forward of the strengths times x_d: the
+    // same rounds per (k <= l) term (and per form of the (l, k) term, as in the forward), the gather applying the basis
+    // weights (k_interp<.., BPOS = 1>) and every term adding into the SAME (3, channels, nbls) S -- it does not grow by K^2.
     void run_position_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
-                              int gbls_on_device, int accumulate) override {
+                              int gbls_on_device, int accumulate, bool basis) override {
         FV_HIP(hipSetDevice(device));
         FV_REQUIRE(!type1, "the position adjoint runs the type-3 transform: set the array with fv_sim_set_array, not "
                            "fv_sim_set_array_type1 (a lattice form of the pass does not exist)");
-        FV_REQUIRE(nbasis == 0, "the position adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        if (basis)
+            FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_position_adjoint needs a handle with basis beams (fv_sim_set_basis); "
+                                   "without them fv_sim_run_position_adjoint is the pass");
+        else
+            FV_REQUIRE(nbasis == 0, "the position adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs)");
         check_run(t0, t1, f0, f1);
         const int nt = t1 - t0, nf = f1 - f0;
         const int64_t per_tf = (int64_t)tpol * nbls;
@@ -5004,12 +5015,20 @@ class Sim : public SimBase {
     // spread -> FFT -> tangent gather (k_interp<.., TANGENT>) ADDING into the zeroed output block.  A time step's slots are
     // written by its own lane's stream only, in order: no sum over lanes, bitwise reproducible for a lane count.  A host
     // destination receives the block in one copy at the end.
+    // Basis beams (fv_sim_run_basis_position_tangent; dbls only): the moments rounds per (k <= l) term as in
+    // run_position_adjoint, the gather adding i nu w (w1 V, w2 V) with the basis weights (k_interp<.., BPOS = 2>).
     void run_tangent(int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
-                     int dtopo_on_device, void *out, int out_on_device) override {
+                     int dtopo_on_device, void *out, int out_on_device, bool basis) override {
         FV_HIP(hipSetDevice(device));
         FV_REQUIRE(!type1, "the tangent runs the type-3 transform: set the array with fv_sim_set_array, not "
                            "fv_sim_set_array_type1 (a lattice form of the pass does not exist)");
-        FV_REQUIRE(nbasis == 0, "the tangent does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        if (basis) {
+            FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_position_tangent needs a handle with basis beams (fv_sim_set_basis); "
+                                   "without them fv_sim_run_tangent is the pass");
+            FV_REQUIRE(dbls && !dtopo, "the tangent through basis beams takes baseline directions only");
+        } else {
+            FV_REQUIRE(nbasis == 0, "the tangent does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        }
         FV_REQUIRE(dbls || dtopo, "neither tangent input is given (dbls and dtopo are both null)");
         check_run(t0, t1, f0, f1);
         const int nt = t1 - t0, nf = f1 - f0;

@@ -277,6 +277,14 @@ class SimHandle:
         bp, b_dev = _buffer_addr(gbls)
         _lib.check(self._L.fv_sim_run_position_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, bp, b_dev, int(bool(accumulate))))
 
+    def run_basis_position_adjoint(self, t0, t1, f0, f1, g, gbls, accumulate: bool):
+        """Basis beams (``set_basis``): ``gbls +=`` the gradient with respect to the baseline vectors for times [t0,t1) x
+        freqs [f0,f1) (``fv_sim_run_basis_position_adjoint``).  ``g`` and ``gbls`` as for ``run_position_adjoint``."""
+        gp, g_dev = _buffer_addr(g)
+        bp, b_dev = _buffer_addr(gbls)
+        _lib.check(self._L.fv_sim_run_basis_position_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, bp, b_dev,
+                                                             int(bool(accumulate))))
+
     def run_source_adjoint(self, t0, t1, f0, f1, g, gtopo, accumulate: bool):
         """``gtopo +=`` the tangential gradient with respect to the sources' ENU unit vectors for times [t0,t1) x freqs
         [f0,f1) (``fv_sim_run_source_adjoint``).  ``g`` as for ``run_adjoint``; ``gtopo``: C-contiguous (t1 - t0, nsrc, 3)
@@ -295,6 +303,13 @@ class SimHandle:
         tp, t_dev = _buffer_addr(dtopo)
         op, o_dev = _buffer_addr(out)
         _lib.check(self._L.fv_sim_run_tangent(self._h, t0, t1, f0, f1, bp, b_dev, tp, t_dev, op, o_dev))
+
+    def run_basis_position_tangent(self, t0, t1, f0, f1, dbls, out):
+        """Basis beams (``set_basis``): ``out =`` the tangent of the visibilities along ``dbls`` for times [t0,t1) x freqs
+        [f0,f1) (``fv_sim_run_basis_position_tangent``).  ``dbls`` and ``out`` as for ``run_tangent``."""
+        bp, b_dev = _buffer_addr(dbls)
+        op, o_dev = _buffer_addr(out)
+        _lib.check(self._L.fv_sim_run_basis_position_tangent(self._h, t0, t1, f0, f1, bp, b_dev, op, o_dev))
 
     def run_basis_tangent(self, t0, t1, f0, f1, dcoefs, out):
         """Basis beams (``set_basis``): ``out[q] =`` the tangent of the visibilities along direction ``dcoefs[q]`` of the
@@ -495,7 +510,9 @@ class GPUSimulationEngine(SimulationEngine):
           into ``gflux`` (``SimHandle.run_adjoint``) and returns ``gflux``.  With ``beam_coefs`` (what
           ``simulate_vis_basis_adjoint`` passes) a triple ``(g, gflux, gcoefs)``, either output None when not wanted:
           ``SimHandle.run_basis_adjoint`` adds both gradients (``fluxes`` are then the forward's) and the call returns
-          ``(gflux, gcoefs)``.
+          ``(gflux, gcoefs)``.  A fourth entry ``gbls``, (nbls, 3) float64 or None, also asks for the gradient with respect
+          to the baseline vectors (``SimHandle.run_basis_position_adjoint``, per time block after the other two) and the
+          call returns ``(gflux, gcoefs, gbls)``; every pass runs only when its output is given.
         * ``adjoint_wrt`` (extra; with ``adjoint_of``, no basis beams): ``"fluxes"`` (default) as above; ``"positions"`` (what
           ``simulate_vis_position_adjoint`` passes): ``adjoint_of`` is ``(g, gbls)`` and the engine adds the gradient with
           respect to the baseline vectors into ``gbls``, (nbls, 3) float64 (``SimHandle.run_position_adjoint``), and
@@ -513,7 +530,8 @@ class GPUSimulationEngine(SimulationEngine):
           visibilities along a change ``dbls`` (nbls, 3) of the baseline vectors and / or ``dtopo`` (ntimes, nsrc, 3) of
           the sources' ENU unit vectors, either None (``SimHandle.run_tangent``), and returns it.  Time blocks take
           consecutive rows of ``dtopo``.  The pass runs the type-3 transform only: ValueError on the lattice path (pass
-          ``force_use_type3=True``) and with ``beam_coefs``.
+          ``force_use_type3=True``).  With ``beam_coefs`` (what ``simulate_vis_basis_jvp`` passes for a position tangent)
+          only ``dbls`` is served (``SimHandle.run_basis_position_tangent``); a ``dtopo`` there is a ValueError.
         * ``basis_tangent_of`` (extra; what ``simulate_vis_basis_jvp`` passes; needs ``beam_coefs``): a pair ``(dcoefs, dv)``
           -- instead of simulating, the engine fills ``dv``, (ndir,) + the result's shape, this precision's complex dtype,
           with the tangents of its visibilities along the ``ndir`` directions ``dcoefs`` (ndir, nant, nbasis, nfreqs) of the
@@ -527,8 +545,9 @@ class GPUSimulationEngine(SimulationEngine):
         if tangent_of is not None:
             if adjoint_of is not None:
                 raise ValueError("pass either adjoint_of or tangent_of, not both")
-            if beam_coefs is not None:
-                raise ValueError("the tangent does not cover basis beams (beam_coefs)")
+            if beam_coefs is not None and (tangent_of[1] is not None or tangent_of[0] is None):
+                raise ValueError("the tangent through basis beams (beam_coefs) takes baseline directions only: source "
+                                 "directions are not covered")
         if adjoint_path not in ADJOINT_PATHS:
             raise ValueError(f"adjoint_path must be one of {ADJOINT_PATHS}, got {adjoint_path!r}")
         if adjoint_wrt not in ("fluxes", "positions", "sources"):
@@ -675,17 +694,18 @@ class GPUSimulationEngine(SimulationEngine):
             if coord_mgr is not None:
                 coord_mgr.setup()
             if adjoint_of is not None:
-                if use_basis != (len(adjoint_of) == 3):
-                    raise ValueError("adjoint_of: (g, gflux, gcoefs) with beam_coefs, (g, gflux) without")
+                if use_basis != (len(adjoint_of) in (3, 4)):
+                    raise ValueError("adjoint_of: (g, gflux, gcoefs[, gbls]) with beam_coefs, (g, gflux) without")
                 if not use_basis:  # (a cached handle keeps its last setting)
                     h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
                 result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr,
                                       gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis, positions=positions,
-                                      sources=sources)
+                                      sources=sources, gbls=adjoint_of[3] if len(adjoint_of) == 4 else None)
                 ok = True
                 return result
             if tangent_of is not None:
-                result = _run_tangent(h, tangent_of[0], tangent_of[1], tangent_of[2], t0, t1, f0, f1, nblk_t, coord_mgr)
+                result = _run_tangent(h, tangent_of[0], tangent_of[1], tangent_of[2], t0, t1, f0, f1, nblk_t, coord_mgr,
+                                      basis=use_basis)
                 ok = True
                 return result
             if basis_tangent_of is not None:
@@ -801,9 +821,11 @@ def _topo_from_coord_mgr(coord_mgr, time_indices):
     return np.stack(out)
 
 
-def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False, positions=False, sources=False):
+def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False, positions=False, sources=False,
+                 gbls=None):
     """The adjoint's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors), each block's
-    contribution added to ``gflux`` (``basis``: and to ``gcoefs``; returns the pair.  ``positions``: ``gflux`` is the
+    contribution added to ``gflux`` (``basis``: and to ``gcoefs``; returns the pair -- with ``gbls`` the block's
+    ``run_basis_position_adjoint`` follows and the triple is returned.  ``positions``: ``gflux`` is the
     (nbls, 3) baseline gradient and ``run_position_adjoint`` adds to it.  ``sources``: ``gflux`` is the (t1 - t0, nsrc, 3)
     direction gradient and every block's ``run_source_adjoint`` fills that block's rows).  Every ``run_adjoint`` call ends
     synchronised."""
@@ -826,7 +848,10 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, ba
         else:
             ta, te_ = tb, te
         if basis:
-            h.run_basis_adjoint(ta, te_, f0, f1, blk, gflux, gcoefs, not first)
+            if gflux is not None or gcoefs is not None:
+                h.run_basis_adjoint(ta, te_, f0, f1, blk, gflux, gcoefs, not first)
+            if gbls is not None:
+                h.run_basis_position_adjoint(ta, te_, f0, f1, blk, gbls, not first)
         elif positions:
             h.run_position_adjoint(ta, te_, f0, f1, blk, gflux, not first)
         elif sources:  # (rows of a C-contiguous array: a contiguous view, written in place)
@@ -835,16 +860,18 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, ba
             h.run_adjoint(ta, te_, f0, f1, blk, gflux, not first)
         first = False
     if first and not sources:  # no time steps: nothing contributes
-        for out in (gflux, gcoefs):
+        for out in (gflux, gcoefs, gbls):
             if out is not None:
                 out[...] = 0
+    if basis and gbls is not None:
+        return gflux, gcoefs, gbls
     return (gflux, gcoefs) if basis else gflux
 
 
-def _run_tangent(h, dbls, dtopo, dv, t0, t1, f0, f1, nblk_t, coord_mgr):
+def _run_tangent(h, dbls, dtopo, dv, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False):
     """The tangent's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors); every block's
     ``run_tangent`` takes its rows of ``dtopo`` and fills its slice of ``dv`` (a block that is not the whole result goes
-    through a contiguous temporary).  Every call ends synchronised."""
+    through a contiguous temporary).  ``basis``: ``run_basis_position_tangent`` on ``dbls``.  Every call ends synchronised."""
     on_device = not isinstance(dv, np.ndarray)
     step = max(nblk_t, 1)
     for tb in range(t0, t1, step):
@@ -865,7 +892,10 @@ def _run_tangent(h, dbls, dtopo, dv, t0, t1, f0, f1, nblk_t, coord_mgr):
             ta, te_ = 0, te - tb
         else:
             ta, te_ = tb, te
-        h.run_tangent(ta, te_, f0, f1, dbls, rows, blk)
+        if basis:
+            h.run_basis_position_tangent(ta, te_, f0, f1, dbls, blk)
+        else:
+            h.run_tangent(ta, te_, f0, f1, dbls, rows, blk)
         if not whole:
             dv[:, tb - t0:te - t0] = blk
     if t1 <= t0:

@@ -285,8 +285,8 @@ int fv_sim_run_basis_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const vo
  * (3, channels, nbls) complex per lane, at most FFTVIS_HIP_ADJ_ACC_BYTES per lane -- followed by a per-baseline sum over
  * channels and lanes in a fixed order.  No atomics: bitwise reproducible for a given FFTVIS_HIP_LANES.  Memory is given
  * back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule of fv_sim_run_adjoint.  A lattice handle (fv_sim_set_array_type1: set the
- * array with fv_sim_set_array instead), a handle with basis beams, a null pointer, a flag other than 0 or 1 and NaN in G
- * fail with FV_ERR_ARG.                                                                                                  */
+ * array with fv_sim_set_array instead), a handle with basis beams (fv_sim_run_basis_position_adjoint is the pass there),
+ * a null pointer, a flag other than 0 or 1 and NaN in G fail with FV_ERR_ARG.                                            */
 int fv_sim_run_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
                                 int gbls_on_device, int accumulate);
 /* Gradient of fv_sim_run's visibilities with respect to the sources' directions, for times [t0, t1) x freqs [f0, f1).
@@ -337,7 +337,8 @@ int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const v
  * beam term) into the zeroed output block, one owner thread per slot.  No atomics, one lane per time step: bitwise
  * reproducible for a given FFTVIS_HIP_LANES.  A host destination receives the block in one copy at the end.  Memory is
  * given back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule of fv_sim_run_adjoint.  FFTVIS_HIP_SRC_BEAM_STEP overrides the step
- * h (radians; for measurements).  A lattice handle (fv_sim_set_array_type1), a handle with basis beams, a null handle, a
+ * h (radians; for measurements).  A lattice handle (fv_sim_set_array_type1), a handle with basis beams
+ * (fv_sim_run_basis_position_tangent serves dbls there), a null handle, a
  * null out, both inputs NULL, a flag other than 0 or 1 and a value in either input that is not finite (detected before
  * anything runs; the handle stays usable) fail with FV_ERR_ARG.                                                          */
 int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
@@ -363,6 +364,36 @@ int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *
  * the handle stays usable) fail with FV_ERR_ARG.                                                                          */
 int fv_sim_run_basis_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir,
                              void *out, int out_on_device);
+/* Gradient of a basis-beam handle's visibilities (fv_sim_set_basis) with respect to the baseline vectors, for times
+ * [t0, t1) x freqs [f0, f1): fv_sim_run_position_adjoint's quantity for V_b = sum_kl conj(C[a1,k]) C[a2,l] M_kl(b).
+ * Every M_kl is a sum over sources of strengths that do not depend on the positions times exp(i nu s_b b' . x_j), so
+ *     dV_b / db'_d = i nu D'_d(b),   D'_d the basis forward of the strengths times x_j,d,
+ *     gbls[k, d] += - sum_{f, t, r} (2 pi nu_f / c) Im( conj(G) D_d ).
+ * gvis, gbls, the flags and accumulate as in fv_sim_run_position_adjoint: gbls is (nbls, 3) float64 per metre in the
+ * frame of the vectors given to fv_sim_set_array, and the third component is also returned on a coplanar handle.  The
+ * pass is the basis forward run per channel block -- every (k <= l) term, fv_sim_set_reference_compat's two forms of the
+ * (l, k) term, source chunks, lanes, height terms -- with three strength sets per launch and three transforms per term;
+ * the gather applies the basis weights in fp64 and every term adds into ONE (3, channels of the block, nbls) complex fp64
+ * buffer per stream (it does not grow with the number of basis beams), cut into channel blocks under
+ * FFTVIS_HIP_ADJ_ACC_BYTES.  One owner thread per slot and launch, buffers summed in lane order: no atomics, bitwise
+ * reproducible for a given FFTVIS_HIP_LANES.  Memory is given back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule of
+ * fv_sim_run_adjoint.  Not covered: source-position derivatives through basis beams, lattice handles.  A handle without
+ * fv_sim_set_basis (fv_sim_run_position_adjoint is the pass there), a lattice handle, a null handle, a null gvis or gbls,
+ * a flag other than 0 or 1 and NaN in gvis (detected before anything runs; the handle stays usable) fail with
+ * FV_ERR_ARG.                                                                                                            */
+int fv_sim_run_basis_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device,
+                                      double *gbls, int gbls_on_device, int accumulate);
+/* Forward-mode tangent of a basis-beam handle's visibilities along a direction of the baseline vectors, the transpose of
+ * fv_sim_run_basis_position_adjoint:  out[.., k] = sum_d i (2 pi nu_f / c) dbls[k, d] D_d[.., k],  Re <out, G> = sum
+ * dbls . gbls.  dbls: (nbls, 3) float64 in metres, in the frame of fv_sim_set_array's vectors.  out: fv_sim_run's layout
+ * for the block, complex of the handle's precision, always overwritten.  The pass is that of the adjoint, the gather
+ * adding i nu w (w1 V, w2 V) with the basis weights formed in fp64 into the zeroed block; a time step's slots are written
+ * by its own lane only: bitwise reproducible for a given FFTVIS_HIP_LANES.  Channel blocks and memory as in
+ * fv_sim_run_tangent.  A handle without fv_sim_set_basis (fv_sim_run_tangent is the pass there), a lattice handle, a null
+ * handle, a null out or dbls, a flag other than 0 or 1 and a value of dbls that is not finite (detected before anything
+ * runs; the handle stays usable) fail with FV_ERR_ARG.                                                                    */
+int fv_sim_run_basis_position_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device,
+                                      void *out, int out_on_device);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2
