@@ -26,6 +26,8 @@ also offer to ``torch.autograd.forward_ad`` through their ``jvp``.  Basis beams 
 
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 
 from .core.beams import feed_index
@@ -39,6 +41,237 @@ def _is_tensor(x) -> bool:
 
     torch = sys.modules.get("torch")
     return torch is not None and isinstance(x, torch.Tensor)
+
+
+# ---- the host layer every pass below shares ("Host layer of the derivative passes") ----
+
+# keywords a pass hands to ``engine.simulate`` and to ``simulate_vis`` as its caller gave them
+_PASS_THROUGH = ("ra", "dec", "freqs", "times", "telescope_loc", "precision", "polarized", "upsample_factor",
+                 "beam_spline_opts", "use_feed", "flat_array_tol", "interpolation_function", "nprocesses", "nthreads",
+                 "coord_method", "coord_method_params", "force_use_ray", "trace_mem", "source_buffer", "coord_mgr",
+                 "reference_compat", "device_astrometry")
+
+
+@dataclasses.dataclass(frozen=True)
+class _Run:
+    """One call of a pass: the arguments as given (``args``: the public function's ``locals()``), and what every pass
+    derives from them before any device work."""
+
+    args: dict
+    ants: dict
+    beam_list: list
+    beam_idx: np.ndarray
+    beam_coefs: np.ndarray  # on the host; None without basis beams
+    baselines: list
+    eps: float
+    astrom: np.ndarray
+    nsrc: int
+    nfreqs: int
+    ntimes: int
+    nbls: int
+    rdt: type
+    cdt: type
+    vis_shape: tuple
+
+    def dtype(self, kind):
+        """numpy dtype of a buffer: "real" and "complex" of the run's precision, or "float64"."""
+        return {"real": self.rdt, "complex": self.cdt, "float64": np.float64}[kind]
+
+
+def _describe_run(args) -> _Run:
+    """The run a pass's arguments describe, normalised as ``simulate_vis`` normalises them; ValueError for what no run
+    takes.  A pass that refuses ``beam_coefs`` does so before: here they mean basis beams."""
+    if args["backend"] != "gpu":
+        raise ValueError(f"Unsupported backend: {args['backend']}")
+    precision, polarized = args["precision"], args["polarized"]
+    ants = {k: np.array(v) for k, v in args["ants"].items()}
+    beam = args["beam"]
+    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
+    beam_coefs = None if args["beam_coefs"] is None else _host(args["beam_coefs"])
+    beam_idx = validate_beam_idx(args["beam_idx"], beam_coefs, len(beam_list), len(ants))
+    feed_index(args["use_feed"])
+    baselines = args["baselines"]
+    if baselines is None:
+        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
+    nfreqs, ntimes, nbls = int(np.size(args["freqs"])), len(julian_dates(args["times"])), len(baselines)
+    if beam_coefs is not None and beam_coefs.shape != (len(ants), len(beam_list), nfreqs):
+        raise ValueError("beam_coefs must have shape (nant, nbasis, nfreqs)")
+    return _Run(
+        args=args, ants=ants, beam_list=beam_list, beam_idx=beam_idx, beam_coefs=beam_coefs, baselines=baselines,
+        eps=default_accuracy_dict[precision] if args["eps"] is None else args["eps"], astrom=args["astrom"],
+        nsrc=int(np.size(args["ra"])), nfreqs=nfreqs, ntimes=ntimes, nbls=nbls,
+        rdt=np.float32 if precision == 1 else np.float64, cdt=np.complex64 if precision == 1 else np.complex128,
+        vis_shape=(nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls),
+    )
+
+
+def _shared_keywords(run: _Run) -> dict:
+    """What ``engine.simulate`` and ``simulate_vis`` take alike."""
+    return dict({k: run.args[k] for k in _PASS_THROUGH}, ants=run.ants, beam_idx=run.beam_idx, baselines=run.baselines,
+                eps=run.eps, astrom=run.astrom)
+
+
+def _engine_simulate(run: _Run, fluxes, *, force_use_type3=None, **mode):
+    """One ``engine.simulate`` call of the run on the host array ``fluxes``; ``mode`` is the pass's own keyword
+    (``adjoint_of=``, ``tangent_of=``, ...).  ``force_use_type3`` defaults to the caller's."""
+    from .wrapper import create_simulation_engine, device_chunks
+
+    a = run.args
+    nfeed = 2 if a["polarized"] else 1
+    engine = create_simulation_engine(backend=a["backend"], device=a["device"])
+    nchunks = device_chunks(a["device"], a["max_memory"], a["min_chunks"], run.beam_list, nfeed, nfeed, len(run.ants),
+                            run.nsrc, a["precision"], a["source_buffer"], run.nfreqs)
+    return engine.simulate(
+        fluxes=fluxes.astype(run.rdt, copy=False), beam_list=run.beam_list, nchunks=nchunks,
+        beam_coefs=None if run.beam_coefs is None else run.beam_coefs.astype(run.cdt, copy=False),
+        force_use_type3=a["force_use_type3"] if force_use_type3 is None else force_use_type3,
+        **_shared_keywords(run), **mode)
+
+
+def _forward_simulate(run: _Run, fluxes, out):
+    """Add ``simulate_vis`` of the run on the fluxes' tangent to ``out``: the map is linear in the fluxes."""
+    from .wrapper import simulate_vis
+
+    a = run.args
+    vf = simulate_vis(fluxes=_host(fluxes).astype(run.rdt, copy=False), beam=run.beam_list, beam_coefs=run.beam_coefs,
+                      force_use_type3=a["force_use_type3"], backend=a["backend"], max_memory=a["max_memory"],
+                      min_chunks=a["min_chunks"], device=a["device"], **_shared_keywords(run))
+    if _is_tensor(out):
+        import torch
+
+        vf = torch.from_numpy(np.ascontiguousarray(vf)).to(out.device)
+    out += vf
+
+
+def _host(x) -> np.ndarray:
+    """An array or a tensor as a host array (a lazily conjugated or negated view's memory is not its value)."""
+    return x.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(x) else np.asarray(x)
+
+
+def _on(device, x, dtype):
+    """``x`` as a contiguous tensor of the numpy ``dtype`` on the torch ``device``, for the library to read by pointer."""
+    import torch
+
+    x = x.detach() if _is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+    return x.to(device=device, dtype=getattr(torch, np.dtype(dtype).name)).resolve_conj().resolve_neg().contiguous()
+
+
+def _zeros(device, shape, dtype):
+    """A zeroed buffer: a tensor on the torch ``device``, a numpy array when that is None."""
+    if device is None:
+        return np.zeros(shape, dtype=dtype)
+    import torch
+
+    return torch.zeros(shape, dtype=getattr(torch, np.dtype(dtype).name), device=device)
+
+
+def _synchronize(device):
+    """The library's streams do not follow torch's: what torch queued on ``device`` (inputs, zeroed outputs) is complete
+    before the library touches it."""
+    if device is not None:
+        import torch
+
+        torch.cuda.synchronize(device)
+
+
+def _run_device(run: _Run, tensors, what):
+    """The torch device the run's buffers live on: that of the first device tensor among ``tensors``, None when there is
+    none (host buffers).  ``what`` names it in the error when it is not the run's device."""
+    t = next((x for x in tensors if _is_tensor(x) and x.device.type == "cuda"), None)
+    if t is None:
+        return None
+    if (t.device.index or 0) != int(run.args["device"]):
+        raise ValueError(f"{what} lives on {t.device}, the run is on cuda:{int(run.args['device'])}")
+    return t.device
+
+
+def _gradient_buffers(run: _Run, vis, wanted):
+    """``vis`` as the library reads it and one zeroed output per entry of ``wanted`` -- (shape, "real" | "complex" |
+    "float64"), or None for an output not asked for: tensors on ``vis``' device for a device tensor (complete before the
+    call returns), numpy arrays otherwise.  Returns (g, outputs, on_device)."""
+    if tuple(vis.shape) != run.vis_shape:
+        raise ValueError(f"vis must have simulate_vis's output shape {run.vis_shape}, got {tuple(vis.shape)}")
+    device = _run_device(run, (vis,), "vis")
+    g = _host(vis).astype(run.cdt, copy=False) if device is None else _on(device, vis, run.cdt)
+    outs = [None if w is None else _zeros(device, w[0], run.dtype(w[1])) for w in wanted]
+    _synchronize(device)
+    return g, outs, device is not None
+
+
+def _buffer(run: _Run, device, x, kind):
+    """A tangent as the library reads it: None stays None."""
+    if x is None:
+        return None
+    return np.ascontiguousarray(_host(x), dtype=run.dtype(kind)) if device is None else _on(device, x, run.dtype(kind))
+
+
+def _host_fluxes(run: _Run, fluxes, d_fluxes=None) -> np.ndarray:
+    """The forward's fluxes as a host array, checked against the catalog (and their tangent's shape against theirs)."""
+    fluxes = _host(fluxes)
+    if fluxes.shape not in ((run.nsrc, run.nfreqs), (run.nsrc, run.nfreqs, 4)):
+        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
+    if fluxes.ndim == 3 and not run.args["polarized"]:
+        raise ValueError("a full-Stokes sky needs polarized=True")
+    if d_fluxes is not None and tuple(d_fluxes.shape) != fluxes.shape:
+        raise ValueError(f"d_fluxes must have fluxes' shape {fluxes.shape}, got {tuple(d_fluxes.shape)}")
+    return fluxes
+
+
+def _baseline_tangent(run: _Run, d_ants, d_baselines):
+    """The baselines' tangent from ``d_ants`` or ``d_baselines`` (not both), (nbls, 3) or None."""
+    if d_ants is not None and d_baselines is not None:
+        raise ValueError("give the antenna tangent as d_ants or as d_baselines, not both")
+    if d_ants is not None:
+        d_baselines = antenna_to_baseline_tangent(d_ants, run.ants, run.baselines)
+    if d_baselines is not None and tuple(d_baselines.shape) != (run.nbls, 3):
+        raise ValueError(f"d_baselines must have shape ({run.nbls}, 3), got {tuple(d_baselines.shape)}")
+    return d_baselines
+
+
+def _parse_wrt(wrt, allowed, describe):
+    """``wrt`` -- a name or a tuple of distinct names out of ``allowed`` -- as (single, names)."""
+    single = isinstance(wrt, str)
+    names = (wrt,) if single else tuple(wrt)
+    if not names or any(n not in allowed for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"wrt must name {describe}, got {wrt!r}")
+    return single, names
+
+
+def _select(res: dict, single, names, like, on_device):
+    """The gradients asked for out of ``res``, in ``wrt``'s order; a host tensor (``like``) in, host tensors out."""
+    if _is_tensor(like) and not on_device:
+        import torch
+
+        res = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in res.items()}
+    return res[names[0]] if single else tuple(res[n] for n in names)
+
+
+def _own_radec_chain(run: _Run, asked, needed, with_mgr, with_matvis) -> _Run:
+    """For a pass that chains (ra, dec) to the topocentric vectors itself (``needed``; ``asked`` names the argument that
+    asks for it): ValueError where the chain is a coordinate manager's, with the pass's advice.  Under device astrometry
+    the run gets its contexts here, so that the engine and ``radec_jacobian`` see the same."""
+    a = run.args
+    own_rotation = a["coord_method"] == "SiderealRotation"
+    if needed:
+        if a["coord_mgr"] is not None:
+            raise ValueError(f"{asked} needs this package's own chain from (ra, dec) to the topocentric vectors; with "
+                             f"coord_mgr= the chain is the manager's: {with_mgr}")
+        if run.astrom is None and not a["device_astrometry"] and not own_rotation:
+            raise ValueError(f"{asked} needs coord_method='SiderealRotation' or device astrometry (astrom= / "
+                             f"device_astrometry=True); coord_method={a['coord_method']!r} builds a matvis manager whose "
+                             f"chain is its own: {with_matvis}")
+    if run.astrom is None and a["device_astrometry"] and a["coord_mgr"] is None and not own_rotation:
+        from .core.coords import erfa_astrom_context
+
+        return dataclasses.replace(run, astrom=erfa_astrom_context(a["times"], a["telescope_loc"]))
+    return run
+
+
+def _radec_jacobian_of(run: _Run):
+    """``radec_jacobian`` where the run is: the engine rounds ra / dec to the run's precision first."""
+    a = run.args
+    return radec_jacobian(np.asarray(a["ra"]).astype(run.rdt), np.asarray(a["dec"]).astype(run.rdt), a["times"],
+                          a["telescope_loc"], astrom=run.astrom, device=a["device"])
 
 
 def simulate_vis_adjoint(
@@ -96,74 +329,21 @@ def simulate_vis_adjoint(
     to ``eps``.  Sources below the horizon at every time get exactly 0.  Not covered: ``beam_coefs``
     (NotImplementedError), a sharded multi-GPU adjoint.
     """
+    args = locals()
     if adjoint_path not in ("type3", "type2", "auto"):
         raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {adjoint_path!r}")
     if beam_coefs is not None:
         raise NotImplementedError("simulate_vis_adjoint does not support basis beams (beam_coefs)")
-    if backend != "gpu":
-        raise ValueError(f"Unsupported backend: {backend}")
     if full_stokes and not polarized:
         raise ValueError("full_stokes=True needs polarized=True (a full-Stokes sky needs a polarized simulation)")
-    if eps is None:
-        eps = default_accuracy_dict[precision]
-    ants = {k: np.array(v) for k, v in ants.items()}
-    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
-    beam_idx = validate_beam_idx(beam_idx, beam_coefs, len(beam_list), len(ants))
-    feed_index(use_feed)
-    if baselines is None:
-        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
-    nsrc = int(np.size(ra))
-    nfreqs = int(np.size(freqs))
-    ntimes = len(julian_dates(times))
-    nbls = len(baselines)
-    want = (nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls)
-    if tuple(vis.shape) != want:
-        raise ValueError(f"vis must have simulate_vis's output shape {want}, got {tuple(vis.shape)}")
-    rdt = np.float32 if precision == 1 else np.float64
-    cdt = np.complex64 if precision == 1 else np.complex128
-    on_device = _is_tensor(vis) and vis.device.type == "cuda"
-    if on_device:
-        import torch
-
-        if (vis.device.index or 0) != int(device):
-            raise ValueError(f"vis lives on {vis.device}, the run is on cuda:{int(device)}")
-        tc = torch.complex64 if precision == 1 else torch.complex128
-        g = vis.detach().to(tc).resolve_conj().resolve_neg()  # (a lazily conjugated view's memory is not G)
-        gflux = torch.zeros((nsrc, nfreqs, 2, 2) if full_stokes else (nsrc, nfreqs),
-                            dtype=tc if full_stokes else (torch.float32 if precision == 1 else torch.float64),
-                            device=vis.device)
-        torch.cuda.synchronize(vis.device)  # the library's streams do not follow torch's: g and gflux are complete
-    else:
-        g = vis.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(vis) else vis
-        g = np.asarray(g).astype(cdt, copy=False)
-        gflux = np.zeros((nsrc, nfreqs, 2, 2) if full_stokes else (nsrc, nfreqs), dtype=cdt if full_stokes else rdt)
+    run = _describe_run(args)
+    f_shape = (run.nsrc, run.nfreqs)
+    g, (gflux,), on_device = _gradient_buffers(
+        run, vis, [(f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real")])
     # the catalog's shape is all the engine needs of the fluxes
-    fluxes = np.zeros((nsrc, nfreqs, 4) if full_stokes else (nsrc, nfreqs), dtype=rdt)
-
-    from .wrapper import create_simulation_engine, device_chunks
-
-    nax = nfeed = 2 if polarized else 1
-    engine = create_simulation_engine(backend=backend, device=device)
-    nchunks = device_chunks(device, max_memory, min_chunks, beam_list, nax, nfeed, len(ants), nsrc, precision,
-                            source_buffer, nfreqs)
-    gc = engine.simulate(
-        ants=ants, freqs=np.asarray(freqs), fluxes=fluxes, beam_list=beam_list, beam_idx=beam_idx,
-        ra=ra, dec=dec, times=times, telescope_loc=telescope_loc, baselines=baselines,
-        precision=precision, polarized=polarized, eps=eps, upsample_factor=upsample_factor,
-        beam_spline_opts=beam_spline_opts, flat_array_tol=flat_array_tol,
-        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
-        coord_method=coord_method, coord_method_params=coord_method_params,
-        force_use_type3=force_use_type3, force_use_ray=force_use_ray, trace_mem=trace_mem,
-        nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
-        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
-        adjoint_of=(g, gflux), adjoint_path=adjoint_path,
-    )
-    out = stokes_adjoint(gc, full_stokes)
-    if _is_tensor(vis) and not on_device:  # a host tensor in, a host tensor out
-        import torch
-
-        return torch.from_numpy(np.ascontiguousarray(out))
-    return out
+    fluxes = np.zeros(f_shape + (4,) if full_stokes else f_shape, dtype=run.rdt)
+    gc = _engine_simulate(run, fluxes, adjoint_of=(g, gflux), adjoint_path=adjoint_path)
+    return _select({"fluxes": stokes_adjoint(gc, full_stokes)}, True, ("fluxes",), vis, on_device)
 
 
 def stokes_adjoint(gc, full_stokes: bool):
@@ -181,45 +361,83 @@ def stokes_adjoint(gc, full_stokes: bool):
     return np.stack(parts, axis=-1)
 
 
+_FUNCTIONS = {}
+
+
+def _function(factory):
+    """The ``torch.autograd.Function`` class ``factory`` builds, built on first use: torch is imported only then."""
+    if factory not in _FUNCTIONS:
+        _FUNCTIONS[factory] = factory()
+    return _FUNCTIONS[factory]
+
+
+def _forward_tensor(kwargs, *, fluxes, **tensors):
+    """``simulate_vis(**kwargs)`` on host copies of the operation's tensors, as a tensor on the fluxes' device."""
+    import torch
+
+    from .wrapper import simulate_vis
+
+    vis = simulate_vis(fluxes=_host(fluxes), **{k: _host(v) for k, v in tensors.items()}, **kwargs)
+    return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+
+
+def _as_grad(x, device, dtype):
+    """A pass's gradient as the tensor autograd expects for an input of that device and dtype; None stays None."""
+    import torch
+
+    if x is None:
+        return None
+    return (x if _is_tensor(x) else torch.from_numpy(x)).to(device=device, dtype=dtype)
+
+
+def _detached(**tangents):
+    """The tangents autograd hands to a ``jvp``, detached; a missing one (None) stays None and skips its part."""
+    return {k: None if v is None else v.detach() for k, v in tangents.items()}
+
+
+def _ants_of(antnums, antpos) -> dict:
+    return dict(zip(antnums, antpos.detach().cpu().numpy().astype(np.float64)))
+
+
+def _checked_antnums(name, antpos, antnums, kwargs) -> tuple:
+    """The keys of the rows of the tensor ``antpos`` for the torch operation ``name``, which takes no ``ants=``."""
+    if "ants" in kwargs:
+        raise TypeError(f"{name} takes the antenna positions as the tensor antpos (and antnums), not ants=")
+    if antpos.ndim != 2 or antpos.shape[1] != 3 or antpos.is_complex():
+        raise ValueError(f"antpos must be a real (nant, 3) tensor, got {tuple(antpos.shape)} {antpos.dtype}")
+    antnums = list(range(antpos.shape[0])) if antnums is None else list(antnums)
+    if len(antnums) != antpos.shape[0] or len(set(antnums)) != len(antnums):
+        raise ValueError("antnums must give one distinct key per row of antpos")
+    return tuple(antnums)
+
+
 def _autograd_function():
     import torch
 
     class _SimulateVis(torch.autograd.Function):
         @staticmethod
         def forward(ctx, fluxes, kwargs):
-            from .wrapper import simulate_vis
-
             ctx.kwargs = kwargs
             ctx.full_stokes = fluxes.ndim == 3
             ctx.flux_dtype = fluxes.dtype
             # adjoint_path belongs to the backward pass alone
-            vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(), **{k: v for k, v in kwargs.items() if k != "adjoint_path"})
-            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+            return _forward_tensor({k: v for k, v in kwargs.items() if k != "adjoint_path"}, fluxes=fluxes)
 
         @staticmethod
         def backward(ctx, grad_output):
             if not ctx.needs_input_grad[0]:
                 return None, None
             g = simulate_vis_adjoint(grad_output, full_stokes=ctx.full_stokes, **ctx.kwargs)
-            if not _is_tensor(g):
-                g = torch.from_numpy(g)
-            return g.to(device=grad_output.device, dtype=ctx.flux_dtype), None
+            return _as_grad(g, grad_output.device, ctx.flux_dtype), None
 
         @staticmethod
         def jvp(ctx, d_fluxes, _):
             # the map is linear in the fluxes: the tangent is the simulation of d_fluxes
-            from .wrapper import simulate_vis
-
             if d_fluxes is None:
                 return None
-            dv = simulate_vis(fluxes=d_fluxes.detach().cpu().numpy(),
-                              **{k: v for k, v in ctx.kwargs.items() if k != "adjoint_path"})
-            return torch.from_numpy(np.ascontiguousarray(dv)).to(d_fluxes.device)
+            return _forward_tensor({k: v for k, v in ctx.kwargs.items() if k != "adjoint_path"}, fluxes=d_fluxes)
 
     return _SimulateVis
-
-
-_FN = None
 
 
 def torch_simulate_vis(fluxes, **kwargs):
@@ -230,14 +448,11 @@ def torch_simulate_vis(fluxes, **kwargs):
     and a complex output the gradient is Re(A^H g), the adjoint defined there.  ``adjoint_path`` ("type3" | "type2" |
     "auto", see ``simulate_vis_adjoint``) goes to the backward pass only; ``simulate_vis`` never sees it.  Forward mode
     (``torch.autograd.forward_ad``): the map is linear, so the tangent is the simulation of the fluxes' tangent."""
-    global _FN
-    if _FN is None:
-        _FN = _autograd_function()
     if kwargs.get("beam_coefs") is not None:
         raise NotImplementedError("torch_simulate_vis does not support basis beams (beam_coefs)")
     if kwargs.get("adjoint_path", "type3") not in ("type3", "type2", "auto"):
         raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {kwargs['adjoint_path']!r}")
-    return _FN.apply(fluxes, kwargs)
+    return _function(_autograd_function).apply(fluxes, kwargs)
 
 
 def simulate_vis_basis_adjoint(
@@ -307,113 +522,34 @@ def simulate_vis_basis_adjoint(
     device (handed over by pointer; the results are then tensors on that device); every other argument means what it
     means for ``simulate_vis``, ``reference_compat`` included.  ``polarized`` must be True and ``beam_idx`` None, as for
     the forward."""
-    single = isinstance(wrt, str)
-    names = (wrt,) if single else tuple(wrt)
-    if (not names or any(n not in ("fluxes", "beam_coefs", "ants", "baselines") for n in names)
-            or len(set(names)) != len(names)):
-        raise ValueError(f"wrt must name some of 'fluxes', 'beam_coefs', 'ants' and 'baselines', got {wrt!r}")
-    if backend != "gpu":
-        raise ValueError(f"Unsupported backend: {backend}")
+    args = locals()
+    single, names = _parse_wrt(wrt, ("fluxes", "beam_coefs", "ants", "baselines"),
+                               "some of 'fluxes', 'beam_coefs', 'ants' and 'baselines'")
     if beam_coefs is None:
         raise ValueError("simulate_vis_basis_adjoint needs beam_coefs (simulate_vis_adjoint covers per-antenna beam_idx)")
     if not polarized:  # the forward's message
         raise ValueError(
             "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
         )
-    if eps is None:
-        eps = default_accuracy_dict[precision]
-    ants = {k: np.array(v) for k, v in ants.items()}
-    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
-    if _is_tensor(beam_coefs):
-        beam_coefs = beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy()
-    beam_coefs = np.asarray(beam_coefs)
-    validate_beam_idx(beam_idx, beam_coefs, len(beam_list), len(ants))
-    feed_index(use_feed)
-    if baselines is None:
-        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
-    nsrc = int(np.size(ra))
-    nfreqs = int(np.size(freqs))
-    ntimes = len(julian_dates(times))
-    nbls = len(baselines)
-    if beam_coefs.shape != (len(ants), len(beam_list), nfreqs):
-        raise ValueError("beam_coefs must have shape (nant, nbasis, nfreqs)")
-    if _is_tensor(fluxes):
-        fluxes = fluxes.detach().cpu().numpy()
-    fluxes = np.asarray(fluxes)
-    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
-        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
+    run = _describe_run(args)
+    fluxes = _host_fluxes(run, fluxes)
     if full_stokes is None:
         full_stokes = fluxes.ndim == 3
     if bool(full_stokes) != (fluxes.ndim == 3):
         raise ValueError(f"full_stokes={full_stokes} does not match fluxes of shape {fluxes.shape}")
-    want = (nfreqs, ntimes, 2, 2, nbls)
-    if tuple(vis.shape) != want:
-        raise ValueError(f"vis must have simulate_vis's output shape {want}, got {tuple(vis.shape)}")
-    rdt = np.float32 if precision == 1 else np.float64
-    cdt = np.complex64 if precision == 1 else np.complex128
-    want_f, want_c = "fluxes" in names, "beam_coefs" in names
-    want_p = "ants" in names or "baselines" in names
-    f_shape = (nsrc, nfreqs, 2, 2) if full_stokes else (nsrc, nfreqs)
-    c_shape = (len(ants), len(beam_list), nfreqs)
-    on_device = _is_tensor(vis) and vis.device.type == "cuda"
-    gflux = gcoefs = gbls = None
-    if on_device:
-        import torch
-
-        if (vis.device.index or 0) != int(device):
-            raise ValueError(f"vis lives on {vis.device}, the run is on cuda:{int(device)}")
-        tc = torch.complex64 if precision == 1 else torch.complex128
-        g = vis.detach().to(tc).resolve_conj().resolve_neg()  # (a lazily conjugated view's memory is not G)
-        if want_f:
-            gflux = torch.zeros(f_shape, dtype=tc if full_stokes else (torch.float32 if precision == 1 else torch.float64),
-                                device=vis.device)
-        if want_c:
-            gcoefs = torch.zeros(c_shape, dtype=tc, device=vis.device)
-        if want_p:
-            gbls = torch.zeros((nbls, 3), dtype=torch.float64, device=vis.device)
-        torch.cuda.synchronize(vis.device)  # the library's streams do not follow torch's: g and the outputs are complete
-    else:
-        g = vis.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(vis) else vis
-        g = np.asarray(g).astype(cdt, copy=False)
-        if want_f:
-            gflux = np.zeros(f_shape, dtype=cdt if full_stokes else rdt)
-        if want_c:
-            gcoefs = np.zeros(c_shape, dtype=cdt)
-        if want_p:
-            gbls = np.zeros((nbls, 3), dtype=np.float64)
-
-    from .wrapper import create_simulation_engine, device_chunks
-
-    engine = create_simulation_engine(backend=backend, device=device)
-    nchunks = device_chunks(device, max_memory, min_chunks, beam_list, 2, 2, len(ants), nsrc, precision,
-                            source_buffer, nfreqs)
-    got = engine.simulate(  # (gflux, gcoefs[, gbls]): the buffers above, filled in place
-        ants=ants, freqs=np.asarray(freqs), fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=None,
-        ra=ra, dec=dec, times=times, telescope_loc=telescope_loc, baselines=baselines,
-        precision=precision, polarized=True, eps=eps, upsample_factor=upsample_factor,
-        beam_spline_opts=beam_spline_opts, flat_array_tol=flat_array_tol,
-        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
-        coord_method=coord_method, coord_method_params=coord_method_params,
-        force_use_type3=force_use_type3, force_use_ray=force_use_ray, trace_mem=trace_mem,
-        nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
-        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
-        beam_coefs=beam_coefs.astype(cdt, copy=False), adjoint_of=(g, gflux, gcoefs, gbls),
-    )
-    gc, gk = got[0], got[1]
-    res = {}
-    if want_f:
+    f_shape = (run.nsrc, run.nfreqs)
+    g, (gflux, gcoefs, gbls), on_device = _gradient_buffers(run, vis, [
+        None if "fluxes" not in names else (f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real"),
+        None if "beam_coefs" not in names else (run.beam_coefs.shape, "complex"),
+        None if "ants" not in names and "baselines" not in names else ((run.nbls, 3), "float64")])
+    # (gflux, gcoefs[, gbls]): the buffers above, filled in place
+    gc, gk = _engine_simulate(run, fluxes, adjoint_of=(g, gflux, gcoefs, gbls))[:2]
+    res = {"beam_coefs": gk, "baselines": gbls}
+    if "fluxes" in names:
         res["fluxes"] = stokes_adjoint(gc, full_stokes)
-    if want_c:
-        res["beam_coefs"] = gk
-    if "baselines" in names:
-        res["baselines"] = gbls
     if "ants" in names:
-        res["ants"] = baseline_to_antenna_gradient(gbls, ants, baselines)
-    if _is_tensor(vis) and not on_device:  # a host tensor in, host tensors out
-        import torch
-
-        res = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in res.items()}
-    return res[names[0]] if single else tuple(res[n] for n in names)
+        res["ants"] = baseline_to_antenna_gradient(gbls, run.ants, run.baselines)
+    return _select({k: v for k, v in res.items() if k in names}, single, names, vis, on_device)
 
 
 def _basis_autograd_function():
@@ -422,16 +558,12 @@ def _basis_autograd_function():
     class _SimulateVisBasis(torch.autograd.Function):
         @staticmethod
         def forward(ctx, fluxes, beam_coefs, kwargs):
-            from .wrapper import simulate_vis
-
             ctx.kwargs = kwargs
             ctx.flux_dtype, ctx.coef_dtype = fluxes.dtype, beam_coefs.dtype
             ctx.coef_device = beam_coefs.device
             ctx.save_for_backward(fluxes, beam_coefs)
             ctx.save_for_forward(fluxes, beam_coefs)
-            vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(),
-                               beam_coefs=beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy(), **kwargs)
-            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+            return _forward_tensor(kwargs, fluxes=fluxes, beam_coefs=beam_coefs)
 
         @staticmethod
         def backward(ctx, grad_output):
@@ -441,29 +573,19 @@ def _basis_autograd_function():
                 return None, None, None
             got = dict(zip(wrt, simulate_vis_basis_adjoint(grad_output, fluxes=fluxes, beam_coefs=beam_coefs, wrt=wrt,
                                                            **ctx.kwargs)))
-            out = []
-            for name, dt, dev in (("fluxes", ctx.flux_dtype, grad_output.device), ("beam_coefs", ctx.coef_dtype, ctx.coef_device)):
-                g = got.get(name)
-                if g is not None and not _is_tensor(g):
-                    g = torch.from_numpy(g)
-                out.append(None if g is None else g.to(device=dev, dtype=dt))
-            return out[0], out[1], None
+            return (_as_grad(got.get("fluxes"), grad_output.device, ctx.flux_dtype),
+                    _as_grad(got.get("beam_coefs"), ctx.coef_device, ctx.coef_dtype), None)
 
         @staticmethod
         def jvp(ctx, d_fluxes, d_beam_coefs, *_):
-            # a missing tangent (None) skips its part
             fluxes, beam_coefs = ctx.saved_tensors
             if d_fluxes is None and d_beam_coefs is None:
                 return None
             dv = simulate_vis_basis_jvp(fluxes=fluxes, beam_coefs=beam_coefs,
-                                        d_beam_coefs=None if d_beam_coefs is None else d_beam_coefs.detach(),
-                                        d_fluxes=None if d_fluxes is None else d_fluxes.detach(), **ctx.kwargs)
+                                        **_detached(d_beam_coefs=d_beam_coefs, d_fluxes=d_fluxes), **ctx.kwargs)
             return _tangent_tensor(dv, fluxes)
 
     return _SimulateVisBasis
-
-
-_FN_BASIS = None
 
 
 def torch_simulate_vis_basis(fluxes, beam_coefs, **kwargs):
@@ -475,10 +597,7 @@ def torch_simulate_vis_basis(fluxes, beam_coefs, **kwargs):
     coefficients torch's convention for a complex leaf, dL = Re sum conj(grad) dC.  Forward-mode differentiation
     (``torch.autograd.forward_ad``) goes through the operation's ``jvp``: ``simulate_vis_basis_jvp`` on the tangents
     present, a missing one skipping its part."""
-    global _FN_BASIS
-    if _FN_BASIS is None:
-        _FN_BASIS = _basis_autograd_function()
-    return _FN_BASIS.apply(fluxes, beam_coefs, kwargs)
+    return _function(_basis_autograd_function).apply(fluxes, beam_coefs, kwargs)
 
 
 def _basis_array_autograd_function():
@@ -487,18 +606,13 @@ def _basis_array_autograd_function():
     class _SimulateVisBasisArray(torch.autograd.Function):
         @staticmethod
         def forward(ctx, fluxes, beam_coefs, antpos, antnums, kwargs):
-            from .wrapper import simulate_vis
-
             ctx.kwargs = kwargs
             ctx.antnums = antnums
             ctx.flux_dtype, ctx.coef_dtype, ctx.pos_dtype = fluxes.dtype, beam_coefs.dtype, antpos.dtype
             ctx.coef_device, ctx.pos_device = beam_coefs.device, antpos.device
             ctx.save_for_backward(fluxes, beam_coefs, antpos)
             ctx.save_for_forward(fluxes, beam_coefs, antpos)
-            ants = dict(zip(antnums, antpos.detach().cpu().numpy().astype(np.float64)))
-            vis = simulate_vis(ants=ants, fluxes=fluxes.detach().cpu().numpy(),
-                               beam_coefs=beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy(), **kwargs)
-            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+            return _forward_tensor(dict(kwargs, ants=_ants_of(antnums, antpos)), fluxes=fluxes, beam_coefs=beam_coefs)
 
         @staticmethod
         def backward(ctx, grad_output):
@@ -506,35 +620,23 @@ def _basis_array_autograd_function():
             wrt = tuple(n for n, need in zip(("fluxes", "beam_coefs", "ants"), ctx.needs_input_grad[:3]) if need)
             if not wrt:
                 return None, None, None, None, None
-            ants = dict(zip(ctx.antnums, antpos.detach().cpu().numpy().astype(np.float64)))
-            got = dict(zip(wrt, simulate_vis_basis_adjoint(grad_output, ants=ants, fluxes=fluxes, beam_coefs=beam_coefs,
-                                                           wrt=wrt, **ctx.kwargs)))
-            out = []
-            for name, dt, dev in (("fluxes", ctx.flux_dtype, grad_output.device), ("beam_coefs", ctx.coef_dtype, ctx.coef_device),
-                                  ("ants", ctx.pos_dtype, ctx.pos_device)):
-                g = got.get(name)
-                if g is not None and not _is_tensor(g):
-                    g = torch.from_numpy(g)
-                out.append(None if g is None else g.to(device=dev, dtype=dt))
-            return out[0], out[1], out[2], None, None
+            got = dict(zip(wrt, simulate_vis_basis_adjoint(grad_output, ants=_ants_of(ctx.antnums, antpos), fluxes=fluxes,
+                                                           beam_coefs=beam_coefs, wrt=wrt, **ctx.kwargs)))
+            return (_as_grad(got.get("fluxes"), grad_output.device, ctx.flux_dtype),
+                    _as_grad(got.get("beam_coefs"), ctx.coef_device, ctx.coef_dtype),
+                    _as_grad(got.get("ants"), ctx.pos_device, ctx.pos_dtype), None, None)
 
         @staticmethod
         def jvp(ctx, d_fluxes, d_beam_coefs, d_antpos, *_):
-            # a missing tangent (None) skips its part
             fluxes, beam_coefs, antpos = ctx.saved_tensors
             if d_fluxes is None and d_beam_coefs is None and d_antpos is None:
                 return None
-            ants = dict(zip(ctx.antnums, antpos.detach().cpu().numpy().astype(np.float64)))
-            dv = simulate_vis_basis_jvp(ants=ants, fluxes=fluxes, beam_coefs=beam_coefs,
-                                        d_beam_coefs=None if d_beam_coefs is None else d_beam_coefs.detach(),
-                                        d_fluxes=None if d_fluxes is None else d_fluxes.detach(),
-                                        d_ants=None if d_antpos is None else d_antpos.detach(), **ctx.kwargs)
+            dv = simulate_vis_basis_jvp(ants=_ants_of(ctx.antnums, antpos), fluxes=fluxes, beam_coefs=beam_coefs,
+                                        **_detached(d_beam_coefs=d_beam_coefs, d_fluxes=d_fluxes, d_ants=d_antpos),
+                                        **ctx.kwargs)
             return _tangent_tensor(dv, fluxes)
 
     return _SimulateVisBasisArray
-
-
-_FN_BASIS_ARRAY = None
 
 
 def torch_simulate_vis_basis_array(fluxes, beam_coefs, antpos, *, antnums=None, **kwargs):
@@ -546,18 +648,8 @@ def torch_simulate_vis_basis_array(fluxes, beam_coefs, antpos, *, antnums=None, 
     tensor on ``fluxes``' device.  The backward pass is one ``simulate_vis_basis_adjoint`` call with only the gradients
     autograd asks for (``ctx.needs_input_grad``); forward mode (``torch.autograd.forward_ad``) runs
     ``simulate_vis_basis_jvp`` on the tangents present."""
-    global _FN_BASIS_ARRAY
-    if "ants" in kwargs:
-        raise TypeError("torch_simulate_vis_basis_array takes the antenna positions as the tensor antpos (and antnums), "
-                        "not ants=")
-    if antpos.ndim != 2 or antpos.shape[1] != 3 or antpos.is_complex():
-        raise ValueError(f"antpos must be a real (nant, 3) tensor, got {tuple(antpos.shape)} {antpos.dtype}")
-    antnums = list(range(antpos.shape[0])) if antnums is None else list(antnums)
-    if len(antnums) != antpos.shape[0] or len(set(antnums)) != len(antnums):
-        raise ValueError("antnums must give one distinct key per row of antpos")
-    if _FN_BASIS_ARRAY is None:
-        _FN_BASIS_ARRAY = _basis_array_autograd_function()
-    return _FN_BASIS_ARRAY.apply(fluxes, beam_coefs, antpos, tuple(antnums), kwargs)
+    antnums = _checked_antnums("torch_simulate_vis_basis_array", antpos, antnums, kwargs)
+    return _function(_basis_array_autograd_function).apply(fluxes, beam_coefs, antpos, antnums, kwargs)
 
 
 # device bytes of one call's (ndir, ...) output: longer stacks of directions are cut into groups under it
@@ -639,41 +731,16 @@ def simulate_vis_basis_jvp(
     be True and ``beam_idx`` None, as for the forward."""
     import os
 
-    if d_ants is not None and d_baselines is not None:
-        raise ValueError("give the antenna tangent as d_ants or as d_baselines, not both")
-    if backend != "gpu":
-        raise ValueError(f"Unsupported backend: {backend}")
+    args = locals()
     if beam_coefs is None:
         raise ValueError("simulate_vis_basis_jvp needs beam_coefs (simulate_vis_jvp covers per-antenna beam_idx)")
     if not polarized:  # the forward's message
         raise ValueError(
             "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
         )
-    if eps is None:
-        eps = default_accuracy_dict[precision]
-    ants = {k: np.array(v) for k, v in ants.items()}
-    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
-    if _is_tensor(beam_coefs):
-        beam_coefs = beam_coefs.detach().resolve_conj().resolve_neg().cpu().numpy()
-    beam_coefs = np.asarray(beam_coefs)
-    validate_beam_idx(beam_idx, beam_coefs, len(beam_list), len(ants))
-    feed_index(use_feed)
-    if baselines is None:
-        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
-    nsrc = int(np.size(ra))
-    nfreqs = int(np.size(freqs))
-    ntimes = len(julian_dates(times))
-    nbls = len(baselines)
-    c_shape = (len(ants), len(beam_list), nfreqs)
-    if beam_coefs.shape != c_shape:
-        raise ValueError("beam_coefs must have shape (nant, nbasis, nfreqs)")
-    if _is_tensor(fluxes):
-        fluxes = fluxes.detach().cpu().numpy()
-    fluxes = np.asarray(fluxes)
-    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
-        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
-    if d_fluxes is not None and tuple(d_fluxes.shape) != fluxes.shape:
-        raise ValueError(f"d_fluxes must have fluxes' shape {fluxes.shape}, got {tuple(d_fluxes.shape)}")
+    run = _describe_run(args)
+    c_shape = run.beam_coefs.shape
+    fluxes = _host_fluxes(run, fluxes, d_fluxes)
     stacked = False
     if d_beam_coefs is not None:
         dshape = tuple(d_beam_coefs.shape)
@@ -688,93 +755,34 @@ def simulate_vis_basis_jvp(
         if stacked and (d_ants is not None or d_baselines is not None):
             raise ValueError("a position tangent (d_ants / d_baselines) combines with one direction of the coefficients "
                              "only, not with a stack")
-    if d_ants is not None:
-        d_baselines = antenna_to_baseline_tangent(d_ants, ants, baselines)
-    if d_baselines is not None and tuple(d_baselines.shape) != (nbls, 3):
-        raise ValueError(f"d_baselines must have shape ({nbls}, 3), got {tuple(d_baselines.shape)}")
+    tangents = (d_beam_coefs, d_fluxes, d_ants, d_baselines)
+    d_baselines = _baseline_tangent(run, d_ants, d_baselines)
     try:
         budget = float(os.environ.get(BASIS_TANGENT_BYTES_ENV, BASIS_TANGENT_BYTES_DEFAULT))
     except ValueError:
         raise ValueError(f"{BASIS_TANGENT_BYTES_ENV} must be a number of bytes") from None
-    tangents = (d_beam_coefs, d_fluxes, d_ants, d_baselines)
-    any_tensor = any(_is_tensor(x) for x in tangents)
-    dev_tensor = next((x for x in tangents if _is_tensor(x) and x.device.type == "cuda"), None)
-    on_device = dev_tensor is not None
-    if on_device and (dev_tensor.device.index or 0) != int(device):
-        raise ValueError(f"a tangent lives on {dev_tensor.device}, the run is on cuda:{int(device)}")
-    rdt = np.float32 if precision == 1 else np.float64
-    cdt = np.complex64 if precision == 1 else np.complex128
-    shape = (nfreqs, ntimes, 2, 2, nbls)
+    device = _run_device(run, tangents, "a tangent")
     ndir = int(d_beam_coefs.shape[0]) if stacked else 1
-
-    def host(x):
-        return x.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(x) else np.asarray(x)
-
-    common = dict(
-        ants=ants, ra=ra, dec=dec, freqs=freqs, times=times, telescope_loc=telescope_loc,
-        baselines=baselines, precision=precision, polarized=True, eps=eps, upsample_factor=upsample_factor,
-        beam_spline_opts=beam_spline_opts, use_feed=use_feed, flat_array_tol=flat_array_tol,
-        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
-        coord_method=coord_method, coord_method_params=coord_method_params, force_use_type3=force_use_type3,
-        force_use_ray=force_use_ray, trace_mem=trace_mem, source_buffer=source_buffer, coord_mgr=coord_mgr,
-        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
-    )
-    if on_device:
-        import torch
-
-        tdev = dev_tensor.device
-        tc = torch.complex64 if precision == 1 else torch.complex128
-        dv = torch.zeros((ndir,) + shape, dtype=tc, device=tdev)
-        dd = None
-        if d_beam_coefs is not None:
-            dd = d_beam_coefs.detach() if _is_tensor(d_beam_coefs) else torch.from_numpy(np.ascontiguousarray(d_beam_coefs))
-            dd = dd.to(device=tdev, dtype=tc).resolve_conj().resolve_neg().reshape((ndir,) + c_shape).contiguous()
-    else:
-        dv = np.zeros((ndir,) + shape, dtype=cdt)
-        dd = None if d_beam_coefs is None else np.ascontiguousarray(host(d_beam_coefs), dtype=cdt).reshape((ndir,) + c_shape)
+    dv = _zeros(device, (ndir,) + run.vis_shape, run.cdt)
+    dd = _buffer(run, device, d_beam_coefs, "complex")
     if dd is not None:
-        if on_device:
-            torch.cuda.synchronize(tdev)  # the library's streams do not follow torch's: the inputs and dv are complete
-        from .wrapper import create_simulation_engine, device_chunks
-
-        engine = create_simulation_engine(backend=backend, device=device)
-        nchunks = device_chunks(device, max_memory, min_chunks, beam_list, 2, 2, len(ants), nsrc, precision,
-                                source_buffer, nfreqs)
-        per_dir = int(np.prod(shape)) * np.dtype(cdt).itemsize
+        dd = dd.reshape((ndir,) + c_shape)
+        _synchronize(device)
+        per_dir = int(np.prod(run.vis_shape)) * np.dtype(run.cdt).itemsize
         group = int(max(1, min(ndir, budget // max(per_dir, 1))))
         for q0 in range(0, ndir, group):
             q1 = min(ndir, q0 + group)
-            engine.simulate(fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=None, nchunks=nchunks,
-                            beam_coefs=beam_coefs.astype(cdt, copy=False), basis_tangent_of=(dd[q0:q1], dv[q0:q1]),
-                            **common)
+            _engine_simulate(run, fluxes, basis_tangent_of=(dd[q0:q1], dv[q0:q1]))
     if d_baselines is not None:
-        from .wrapper import create_simulation_engine, device_chunks
-
-        if on_device:
-            db = d_baselines.detach() if _is_tensor(d_baselines) else torch.from_numpy(np.ascontiguousarray(d_baselines))
-            db = db.to(device=tdev, dtype=torch.float64).contiguous()
-            dp = torch.zeros(shape, dtype=tc, device=tdev)
-            torch.cuda.synchronize(tdev)  # the library's streams do not follow torch's: db and dp are complete
-        else:
-            db = np.ascontiguousarray(host(d_baselines), dtype=np.float64)
-            dp = np.zeros(shape, dtype=cdt)
-        engine = create_simulation_engine(backend=backend, device=device)
-        nchunks = device_chunks(device, max_memory, min_chunks, beam_list, 2, 2, len(ants), nsrc, precision,
-                                source_buffer, nfreqs)
-        dv[0] += engine.simulate(fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=None, nchunks=nchunks,
-                                 beam_coefs=beam_coefs.astype(cdt, copy=False), tangent_of=(db, None, dp), **common)
+        db = _buffer(run, device, d_baselines, "float64")
+        dp = _zeros(device, run.vis_shape, run.cdt)
+        _synchronize(device)
+        dv[0] += _engine_simulate(run, fluxes, tangent_of=(db, None, dp))
     if d_fluxes is not None:
-        from .wrapper import simulate_vis
-
-        vf = simulate_vis(fluxes=host(d_fluxes).astype(rdt, copy=False), beam=beam_list, beam_coefs=beam_coefs,
-                          backend=backend, max_memory=max_memory, min_chunks=min_chunks, device=device, **common)
-        if on_device:
-            dv[0] += torch.from_numpy(np.ascontiguousarray(vf)).to(dv.device)
-        else:
-            dv[0] += vf
+        _forward_simulate(run, d_fluxes, dv[0])
     if not stacked:
         dv = dv[0]
-    if any_tensor and not on_device:  # host tensors in, a host tensor out
+    if device is None and any(_is_tensor(x) for x in tangents):  # host tensors in, a host tensor out
         import torch
 
         dv = torch.from_numpy(np.ascontiguousarray(dv))
@@ -865,80 +873,19 @@ def simulate_vis_position_adjoint(
     the type-3 transform (about three forward runs whatever the number of antennas), so an ideal lattice array works and
     takes its redundant runs.  Not covered: ``beam_coefs`` (NotImplementedError; ``simulate_vis_basis_adjoint`` has
     ``wrt="ants"``), a type-1 (lattice) form of the pass."""
-    single = isinstance(wrt, str)
-    names = (wrt,) if single else tuple(wrt)
-    if not names or any(n not in ("ants", "baselines") for n in names) or len(set(names)) != len(names):
-        raise ValueError(f"wrt must name 'ants', 'baselines' or both, got {wrt!r}")
+    args = locals()
+    single, names = _parse_wrt(wrt, ("ants", "baselines"), "'ants', 'baselines' or both")
     if beam_coefs is not None:
         raise NotImplementedError("simulate_vis_position_adjoint does not support basis beams (beam_coefs): "
                                   "simulate_vis_basis_adjoint(wrt='ants') does")
-    if backend != "gpu":
-        raise ValueError(f"Unsupported backend: {backend}")
-    if eps is None:
-        eps = default_accuracy_dict[precision]
-    ants = {k: np.array(v) for k, v in ants.items()}
-    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
-    beam_idx = validate_beam_idx(beam_idx, None, len(beam_list), len(ants))
-    feed_index(use_feed)
-    if baselines is None:
-        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
-    nsrc = int(np.size(ra))
-    nfreqs = int(np.size(freqs))
-    ntimes = len(julian_dates(times))
-    nbls = len(baselines)
-    if _is_tensor(fluxes):
-        fluxes = fluxes.detach().cpu().numpy()
-    fluxes = np.asarray(fluxes)
-    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
-        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
-    if fluxes.ndim == 3 and not polarized:
-        raise ValueError("a full-Stokes sky needs polarized=True")
-    want = (nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls)
-    if tuple(vis.shape) != want:
-        raise ValueError(f"vis must have simulate_vis's output shape {want}, got {tuple(vis.shape)}")
-    rdt = np.float32 if precision == 1 else np.float64
-    cdt = np.complex64 if precision == 1 else np.complex128
-    on_device = _is_tensor(vis) and vis.device.type == "cuda"
-    if on_device:
-        import torch
-
-        if (vis.device.index or 0) != int(device):
-            raise ValueError(f"vis lives on {vis.device}, the run is on cuda:{int(device)}")
-        tc = torch.complex64 if precision == 1 else torch.complex128
-        g = vis.detach().to(tc).resolve_conj().resolve_neg()  # (a lazily conjugated view's memory is not G)
-        gbls = torch.zeros((nbls, 3), dtype=torch.float64, device=vis.device)
-        torch.cuda.synchronize(vis.device)  # the library's streams do not follow torch's: g and gbls are complete
-    else:
-        g = vis.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(vis) else vis
-        g = np.asarray(g).astype(cdt, copy=False)
-        gbls = np.zeros((nbls, 3), dtype=np.float64)
-
-    from .wrapper import create_simulation_engine, device_chunks
-
-    nax = nfeed = 2 if polarized else 1
-    engine = create_simulation_engine(backend=backend, device=device)
-    nchunks = device_chunks(device, max_memory, min_chunks, beam_list, nax, nfeed, len(ants), nsrc, precision,
-                            source_buffer, nfreqs)
-    gbls = engine.simulate(
-        ants=ants, freqs=np.asarray(freqs), fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=beam_idx,
-        ra=ra, dec=dec, times=times, telescope_loc=telescope_loc, baselines=baselines,
-        precision=precision, polarized=polarized, eps=eps, upsample_factor=upsample_factor,
-        beam_spline_opts=beam_spline_opts, flat_array_tol=flat_array_tol,
-        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
-        coord_method=coord_method, coord_method_params=coord_method_params,
-        force_use_type3=True, force_use_ray=force_use_ray, trace_mem=trace_mem,
-        nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
-        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
-        adjoint_of=(g, gbls), adjoint_wrt="positions",
-    )
+    run = _describe_run(args)
+    fluxes = _host_fluxes(run, fluxes)
+    g, (gbls,), on_device = _gradient_buffers(run, vis, [((run.nbls, 3), "float64")])
+    gbls = _engine_simulate(run, fluxes, force_use_type3=True, adjoint_of=(g, gbls), adjoint_wrt="positions")
     res = {"baselines": gbls}
     if "ants" in names:
-        res["ants"] = baseline_to_antenna_gradient(gbls, ants, baselines)
-    if _is_tensor(vis) and not on_device:  # a host tensor in, host tensors out
-        import torch
-
-        res = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in res.items()}
-    return res[names[0]] if single else tuple(res[n] for n in names)
+        res["ants"] = baseline_to_antenna_gradient(gbls, run.ants, run.baselines)
+    return _select(res, single, names, vis, on_device)
 
 
 def _tangent_tensor(dv, like):
@@ -956,50 +903,36 @@ def _array_autograd_function():
     class _SimulateVisArray(torch.autograd.Function):
         @staticmethod
         def forward(ctx, fluxes, antpos, antnums, kwargs):
-            from .wrapper import simulate_vis
-
             ctx.kwargs = kwargs
             ctx.antnums = antnums
             ctx.full_stokes = fluxes.ndim == 3
             ctx.flux_dtype, ctx.pos_dtype, ctx.pos_device = fluxes.dtype, antpos.dtype, antpos.device
             ctx.save_for_backward(fluxes, antpos)
             ctx.save_for_forward(fluxes, antpos)
-            ants = dict(zip(antnums, antpos.detach().cpu().numpy().astype(np.float64)))
-            vis = simulate_vis(ants=ants, fluxes=fluxes.detach().cpu().numpy(), **kwargs)
-            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+            return _forward_tensor(dict(kwargs, ants=_ants_of(antnums, antpos)), fluxes=fluxes)
 
         @staticmethod
         def backward(ctx, grad_output):
             fluxes, antpos = ctx.saved_tensors
-            ants = dict(zip(ctx.antnums, antpos.detach().cpu().numpy().astype(np.float64)))
+            ants = _ants_of(ctx.antnums, antpos)
             gf = gp = None
             if ctx.needs_input_grad[0]:
                 gf = simulate_vis_adjoint(grad_output, ants=ants, full_stokes=ctx.full_stokes, **ctx.kwargs)
-                if not _is_tensor(gf):
-                    gf = torch.from_numpy(gf)
-                gf = gf.to(device=grad_output.device, dtype=ctx.flux_dtype)
             if ctx.needs_input_grad[1]:
                 gp = simulate_vis_position_adjoint(grad_output, ants=ants, fluxes=fluxes, wrt="ants", **ctx.kwargs)
-                if not _is_tensor(gp):
-                    gp = torch.from_numpy(gp)
-                gp = gp.to(device=ctx.pos_device, dtype=ctx.pos_dtype)
-            return gf, gp, None, None
+            return (_as_grad(gf, grad_output.device, ctx.flux_dtype), _as_grad(gp, ctx.pos_device, ctx.pos_dtype),
+                    None, None)
 
         @staticmethod
         def jvp(ctx, d_fluxes, d_antpos, *_):
-            # a missing tangent (None) skips its rounds
             fluxes, antpos = ctx.saved_tensors
             if d_fluxes is None and d_antpos is None:
                 return None
-            ants = dict(zip(ctx.antnums, antpos.detach().cpu().numpy().astype(np.float64)))
-            dv = simulate_vis_jvp(ants=ants, fluxes=fluxes, d_ants=None if d_antpos is None else d_antpos.detach(),
-                                  d_fluxes=None if d_fluxes is None else d_fluxes.detach(), **ctx.kwargs)
+            dv = simulate_vis_jvp(ants=_ants_of(ctx.antnums, antpos), fluxes=fluxes,
+                                  **_detached(d_ants=d_antpos, d_fluxes=d_fluxes), **ctx.kwargs)
             return _tangent_tensor(dv, fluxes)
 
     return _SimulateVisArray
-
-
-_FN_ARRAY = None
 
 
 def torch_simulate_vis_array(fluxes, antpos, *, antnums=None, **kwargs):
@@ -1010,20 +943,11 @@ def torch_simulate_vis_array(fluxes, antpos, *, antnums=None, **kwargs):
     device.  The backward pass runs only what autograd asks for (``ctx.needs_input_grad``): ``simulate_vis_adjoint`` for
     the fluxes, ``simulate_vis_position_adjoint`` for the positions.  Forward mode (``torch.autograd.forward_ad``) runs
     ``simulate_vis_jvp`` on the tangents present."""
-    global _FN_ARRAY
-    if "ants" in kwargs:
-        raise TypeError("torch_simulate_vis_array takes the antenna positions as the tensor antpos (and antnums), not ants=")
+    antnums = _checked_antnums("torch_simulate_vis_array", antpos, antnums, kwargs)
     if kwargs.get("beam_coefs") is not None:
         raise NotImplementedError("torch_simulate_vis_array does not support basis beams (beam_coefs): "
                                   "torch_simulate_vis_basis_array does")
-    if antpos.ndim != 2 or antpos.shape[1] != 3 or antpos.is_complex():
-        raise ValueError(f"antpos must be a real (nant, 3) tensor, got {tuple(antpos.shape)} {antpos.dtype}")
-    antnums = list(range(antpos.shape[0])) if antnums is None else list(antnums)
-    if len(antnums) != antpos.shape[0] or len(set(antnums)) != len(antnums):
-        raise ValueError("antnums must give one distinct key per row of antpos")
-    if _FN_ARRAY is None:
-        _FN_ARRAY = _array_autograd_function()
-    return _FN_ARRAY.apply(fluxes, antpos, tuple(antnums), kwargs)
+    return _function(_array_autograd_function).apply(fluxes, antpos, antnums, kwargs)
 
 
 # Angular step [rad] of the central differences that give d n(t) / d(ra, dec) under device astrometry (``radec_jacobian``):
@@ -1146,94 +1070,20 @@ def simulate_vis_source_adjoint(
     means for ``simulate_vis``, ``reference_compat`` included; ``force_use_type3`` is accepted and always on: the pass runs
     the type-3 transform -- 1 + D transforms where the flux adjoint runs one, D = 2 on a flat array and 3 otherwise -- so an
     ideal lattice array works through it.  Not covered: ``beam_coefs`` (NotImplementedError)."""
-    single = isinstance(wrt, str)
-    names = (wrt,) if single else tuple(wrt)
-    if not names or any(n not in ("topo", "radec") for n in names) or len(set(names)) != len(names):
-        raise ValueError(f"wrt must name 'topo', 'radec' or both, got {wrt!r}")
+    args = locals()
+    single, names = _parse_wrt(wrt, ("topo", "radec"), "'topo', 'radec' or both")
     if beam_coefs is not None:
         raise NotImplementedError("simulate_vis_source_adjoint does not support basis beams (beam_coefs)")
-    if backend != "gpu":
-        raise ValueError(f"Unsupported backend: {backend}")
-    if "radec" in names:
-        if coord_mgr is not None:
-            raise ValueError("wrt='radec' needs this package's own chain from (ra, dec) to the topocentric vectors; with "
-                             "coord_mgr= the chain is the manager's: ask for wrt='topo' and apply its Jacobian")
-        if astrom is None and not device_astrometry and coord_method != "SiderealRotation":
-            raise ValueError(f"wrt='radec' needs coord_method='SiderealRotation' or device astrometry (astrom= / "
-                             f"device_astrometry=True); coord_method={coord_method!r} builds a matvis manager whose chain "
-                             "is its own: ask for wrt='topo'")
-    if eps is None:
-        eps = default_accuracy_dict[precision]
-    ants = {k: np.array(v) for k, v in ants.items()}
-    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
-    beam_idx = validate_beam_idx(beam_idx, None, len(beam_list), len(ants))
-    feed_index(use_feed)
-    if baselines is None:
-        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
-    nsrc = int(np.size(ra))
-    nfreqs = int(np.size(freqs))
-    ntimes = len(julian_dates(times))
-    nbls = len(baselines)
-    if _is_tensor(fluxes):
-        fluxes = fluxes.detach().cpu().numpy()
-    fluxes = np.asarray(fluxes)
-    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
-        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
-    if fluxes.ndim == 3 and not polarized:
-        raise ValueError("a full-Stokes sky needs polarized=True")
-    want = (nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls)
-    if tuple(vis.shape) != want:
-        raise ValueError(f"vis must have simulate_vis's output shape {want}, got {tuple(vis.shape)}")
-    rdt = np.float32 if precision == 1 else np.float64
-    cdt = np.complex64 if precision == 1 else np.complex128
-    if astrom is None and device_astrometry and coord_mgr is None and coord_method != "SiderealRotation":
-        from .core.coords import erfa_astrom_context
-
-        astrom = erfa_astrom_context(times, telescope_loc)  # (the engine and the Jacobian see the same contexts)
-    on_device = _is_tensor(vis) and vis.device.type == "cuda"
-    if on_device:
-        import torch
-
-        if (vis.device.index or 0) != int(device):
-            raise ValueError(f"vis lives on {vis.device}, the run is on cuda:{int(device)}")
-        tc = torch.complex64 if precision == 1 else torch.complex128
-        g = vis.detach().to(tc).resolve_conj().resolve_neg()  # (a lazily conjugated view's memory is not G)
-        gtopo = torch.zeros((ntimes, nsrc, 3), dtype=torch.float64, device=vis.device)
-        torch.cuda.synchronize(vis.device)  # the library's streams do not follow torch's: g and gtopo are complete
-    else:
-        g = vis.detach().resolve_conj().resolve_neg().cpu().numpy() if _is_tensor(vis) else vis
-        g = np.asarray(g).astype(cdt, copy=False)
-        gtopo = np.zeros((ntimes, nsrc, 3), dtype=np.float64)
-
-    from .wrapper import create_simulation_engine, device_chunks
-
-    nax = nfeed = 2 if polarized else 1
-    engine = create_simulation_engine(backend=backend, device=device)
-    nchunks = device_chunks(device, max_memory, min_chunks, beam_list, nax, nfeed, len(ants), nsrc, precision,
-                            source_buffer, nfreqs)
-    gtopo = engine.simulate(
-        ants=ants, freqs=np.asarray(freqs), fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, beam_idx=beam_idx,
-        ra=ra, dec=dec, times=times, telescope_loc=telescope_loc, baselines=baselines,
-        precision=precision, polarized=polarized, eps=eps, upsample_factor=upsample_factor,
-        beam_spline_opts=beam_spline_opts, flat_array_tol=flat_array_tol,
-        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
-        coord_method=coord_method, coord_method_params=coord_method_params,
-        force_use_type3=True, force_use_ray=force_use_ray, trace_mem=trace_mem,
-        nchunks=nchunks, source_buffer=source_buffer, coord_mgr=coord_mgr, use_feed=use_feed,
-        reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry,
-        adjoint_of=(g, gtopo), adjoint_wrt="sources",
-    )
+    run = _describe_run(args)
+    run = _own_radec_chain(run, "wrt='radec'", "radec" in names, "ask for wrt='topo' and apply its Jacobian",
+                           "ask for wrt='topo'")
+    fluxes = _host_fluxes(run, fluxes)
+    g, (gtopo,), on_device = _gradient_buffers(run, vis, [((run.ntimes, run.nsrc, 3), "float64")])
+    gtopo = _engine_simulate(run, fluxes, force_use_type3=True, adjoint_of=(g, gtopo), adjoint_wrt="sources")
     res = {"topo": gtopo}
     if "radec" in names:
-        # the engine rounds ra / dec to the run's precision first: the Jacobian is taken where the run was
-        jac = radec_jacobian(np.asarray(ra).astype(rdt), np.asarray(dec).astype(rdt), times, telescope_loc, astrom=astrom,
-                             device=device)
-        res["radec"] = topo_to_radec_gradient(gtopo, jac)
-    if _is_tensor(vis) and not on_device:  # a host tensor in, host tensors out
-        import torch
-
-        res = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in res.items()}
-    return res[names[0]] if single else tuple(res[n] for n in names)
+        res["radec"] = topo_to_radec_gradient(gtopo, _radec_jacobian_of(run))
+    return _select(res, single, names, vis, on_device)
 
 
 def antenna_to_baseline_tangent(d_ants, ants: dict, baselines: list):
@@ -1325,127 +1175,41 @@ def simulate_vis_jvp(
     ``force_use_type3`` is accepted and always on for the position parts: the pass runs the type-3 transform.  Not
     covered: ``beam_coefs`` (NotImplementedError; ``simulate_vis_basis_jvp`` takes ``d_ants`` / ``d_baselines``), a type-1
     (lattice) form of the pass."""
+    args = locals()
     if beam_coefs is not None:
         raise NotImplementedError("simulate_vis_jvp does not support basis beams (beam_coefs): "
                                   "simulate_vis_basis_jvp(d_ants=) does")
-    if d_ants is not None and d_baselines is not None:
-        raise ValueError("give the antenna tangent as d_ants or as d_baselines, not both")
     if d_radec is not None and d_topo is not None:
         raise ValueError("give the source tangent as d_radec or as d_topo, not both")
-    if backend != "gpu":
-        raise ValueError(f"Unsupported backend: {backend}")
-    if d_radec is not None:
-        if coord_mgr is not None:
-            raise ValueError("d_radec needs this package's own chain from (ra, dec) to the topocentric vectors; with "
-                             "coord_mgr= the chain is the manager's: apply its Jacobian and pass d_topo")
-        if astrom is None and not device_astrometry and coord_method != "SiderealRotation":
-            raise ValueError(f"d_radec needs coord_method='SiderealRotation' or device astrometry (astrom= / "
-                             f"device_astrometry=True); coord_method={coord_method!r} builds a matvis manager whose chain "
-                             "is its own: pass d_topo")
-    if eps is None:
-        eps = default_accuracy_dict[precision]
-    ants = {k: np.array(v) for k, v in ants.items()}
-    beam_list = list(beam) if isinstance(beam, (list, tuple)) else [beam]
-    beam_idx = validate_beam_idx(beam_idx, None, len(beam_list), len(ants))
-    feed_index(use_feed)
-    if baselines is None:
-        baselines = [red[0] for red in get_pos_reds(ants, include_autos=True)]
-    nsrc = int(np.size(ra))
-    nfreqs = int(np.size(freqs))
-    ntimes = len(julian_dates(times))
-    nbls = len(baselines)
+    run = _describe_run(args)
+    run = _own_radec_chain(run, "d_radec", d_radec is not None, "apply its Jacobian and pass d_topo", "pass d_topo")
     tangents = (d_ants, d_baselines, d_radec, d_topo, d_fluxes)
-    any_tensor = any(_is_tensor(x) for x in tangents)
-    dev_tensor = next((x for x in tangents if _is_tensor(x) and x.device.type == "cuda"), None)
-    on_device = dev_tensor is not None
-    if on_device and (dev_tensor.device.index or 0) != int(device):
-        raise ValueError(f"a tangent lives on {dev_tensor.device}, the run is on cuda:{int(device)}")
-
-    def host(x):
-        return x.detach().cpu().numpy() if _is_tensor(x) else np.asarray(x)
-
-    if _is_tensor(fluxes):
-        fluxes = fluxes.detach().cpu().numpy()
-    fluxes = np.asarray(fluxes)
-    if fluxes.shape not in ((nsrc, nfreqs), (nsrc, nfreqs, 4)):
-        raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
-    if fluxes.ndim == 3 and not polarized:
-        raise ValueError("a full-Stokes sky needs polarized=True")
-    if d_fluxes is not None and tuple(d_fluxes.shape) != fluxes.shape:
-        raise ValueError(f"d_fluxes must have fluxes' shape {fluxes.shape}, got {tuple(d_fluxes.shape)}")
-    if d_ants is not None:
-        d_baselines = antenna_to_baseline_tangent(d_ants, ants, baselines)
-    if d_baselines is not None and tuple(d_baselines.shape) != (nbls, 3):
-        raise ValueError(f"d_baselines must have shape ({nbls}, 3), got {tuple(d_baselines.shape)}")
-    if d_radec is not None and tuple(d_radec.shape) != (nsrc, 2):
-        raise ValueError(f"d_radec must have shape ({nsrc}, 2), got {tuple(d_radec.shape)}")
-    if d_topo is not None and tuple(d_topo.shape) != (ntimes, nsrc, 3):
-        raise ValueError(f"d_topo must have shape ({ntimes}, {nsrc}, 3), got {tuple(d_topo.shape)}")
-    rdt = np.float32 if precision == 1 else np.float64
-    cdt = np.complex64 if precision == 1 else np.complex128
-    shape = (nfreqs, ntimes, 2, 2, nbls) if polarized else (nfreqs, ntimes, nbls)
-    if astrom is None and device_astrometry and coord_mgr is None and coord_method != "SiderealRotation":
-        from .core.coords import erfa_astrom_context
-
-        astrom = erfa_astrom_context(times, telescope_loc)  # (the engine and the Jacobian see the same contexts)
+    device = _run_device(run, tangents, "a tangent")
+    fluxes = _host_fluxes(run, fluxes, d_fluxes)
+    d_baselines = _baseline_tangent(run, d_ants, d_baselines)
+    if d_radec is not None and tuple(d_radec.shape) != (run.nsrc, 2):
+        raise ValueError(f"d_radec must have shape ({run.nsrc}, 2), got {tuple(d_radec.shape)}")
+    if d_topo is not None and tuple(d_topo.shape) != (run.ntimes, run.nsrc, 3):
+        raise ValueError(f"d_topo must have shape ({run.ntimes}, {run.nsrc}, 3), got {tuple(d_topo.shape)}")
     if d_radec is not None:
-        # the engine rounds ra / dec to the run's precision first: the Jacobian is taken where the run is
-        jac = radec_jacobian(np.asarray(ra).astype(rdt), np.asarray(dec).astype(rdt), times, telescope_loc, astrom=astrom,
-                             device=device)
-        d_topo = np.einsum("tjdc,jc->tjd", jac, host(d_radec).astype(np.float64))
-    common = dict(
-        ants=ants, ra=ra, dec=dec, freqs=freqs, times=times, telescope_loc=telescope_loc, beam_idx=beam_idx,
-        baselines=baselines, precision=precision, polarized=polarized, eps=eps, upsample_factor=upsample_factor,
-        beam_spline_opts=beam_spline_opts, use_feed=use_feed, flat_array_tol=flat_array_tol,
-        interpolation_function=interpolation_function, nprocesses=nprocesses, nthreads=nthreads,
-        coord_method=coord_method, coord_method_params=coord_method_params, force_use_ray=force_use_ray,
-        trace_mem=trace_mem, source_buffer=source_buffer, coord_mgr=coord_mgr, reference_compat=reference_compat,
-        astrom=astrom, device_astrometry=device_astrometry,
-    )
-    if on_device:
-        import torch
-
-        tdev = dev_tensor.device
-        tc = torch.complex64 if precision == 1 else torch.complex128
-
-        def buf(x):
-            if x is None:
-                return None
-            x = x.detach() if _is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-            return x.to(device=tdev, dtype=torch.float64).contiguous()
-
-        dv = torch.zeros(shape, dtype=tc, device=tdev)
-    else:
-        def buf(x):
-            return None if x is None else np.ascontiguousarray(host(x), dtype=np.float64)
-
-        dv = np.zeros(shape, dtype=cdt)
-    db, dt_ = buf(d_baselines), buf(d_topo)
+        d_topo = np.einsum("tjdc,jc->tjd", _radec_jacobian_of(run), _host(d_radec).astype(np.float64))
+    db, dt_ = _buffer(run, device, d_baselines, "float64"), _buffer(run, device, d_topo, "float64")
+    dv = _zeros(device, run.vis_shape, run.cdt)
     if db is not None or dt_ is not None:
-        if on_device:
-            torch.cuda.synchronize(tdev)  # the library's streams do not follow torch's: the inputs and dv are complete
-        from .wrapper import create_simulation_engine, device_chunks
-
-        nax = nfeed = 2 if polarized else 1
-        engine = create_simulation_engine(backend=backend, device=device)
-        nchunks = device_chunks(device, max_memory, min_chunks, beam_list, nax, nfeed, len(ants), nsrc, precision,
-                                source_buffer, nfreqs)
-        dv = engine.simulate(fluxes=fluxes.astype(rdt, copy=False), beam_list=beam_list, force_use_type3=True,
-                             nchunks=nchunks, tangent_of=(db, dt_, dv), **common)
+        _synchronize(device)
+        dv = _engine_simulate(run, fluxes, force_use_type3=True, tangent_of=(db, dt_, dv))
     if d_fluxes is not None:
-        from .wrapper import simulate_vis
-
-        vf = simulate_vis(fluxes=host(d_fluxes).astype(rdt, copy=False), beam=beam_list, force_use_type3=force_use_type3,
-                          backend=backend, max_memory=max_memory, min_chunks=min_chunks, device=device, **common)
-        if on_device:
-            dv += torch.from_numpy(np.ascontiguousarray(vf)).to(dv.device)
-        else:
-            dv += vf
-    if any_tensor and not on_device:  # host tensors in, a host tensor out
+        _forward_simulate(run, d_fluxes, dv)
+    if device is None and any(_is_tensor(x) for x in tangents):  # host tensors in, a host tensor out
         import torch
 
         dv = torch.from_numpy(np.ascontiguousarray(dv))
     return dv
+
+
+def _radec_columns(radec) -> dict:
+    rd = radec.detach().cpu().numpy().astype(np.float64)
+    return dict(ra=rd[:, 0].copy(), dec=rd[:, 1].copy())
 
 
 def _sky_autograd_function():
@@ -1454,51 +1218,34 @@ def _sky_autograd_function():
     class _SimulateVisSky(torch.autograd.Function):
         @staticmethod
         def forward(ctx, fluxes, radec, kwargs):
-            from .wrapper import simulate_vis
-
             ctx.kwargs = kwargs
             ctx.full_stokes = fluxes.ndim == 3
             ctx.flux_dtype, ctx.pos_dtype, ctx.pos_device = fluxes.dtype, radec.dtype, radec.device
             ctx.save_for_backward(fluxes, radec)
             ctx.save_for_forward(fluxes, radec)
-            rd = radec.detach().cpu().numpy().astype(np.float64)
-            vis = simulate_vis(fluxes=fluxes.detach().cpu().numpy(), ra=rd[:, 0].copy(), dec=rd[:, 1].copy(), **kwargs)
-            return torch.from_numpy(np.ascontiguousarray(vis)).to(fluxes.device)
+            return _forward_tensor(dict(kwargs, **_radec_columns(radec)), fluxes=fluxes)
 
         @staticmethod
         def backward(ctx, grad_output):
             fluxes, radec = ctx.saved_tensors
-            rd = radec.detach().cpu().numpy().astype(np.float64)
-            pos = dict(ra=rd[:, 0].copy(), dec=rd[:, 1].copy())
+            pos = _radec_columns(radec)
             gf = gp = None
             if ctx.needs_input_grad[0]:
                 gf = simulate_vis_adjoint(grad_output, full_stokes=ctx.full_stokes, **pos, **ctx.kwargs)
-                if not _is_tensor(gf):
-                    gf = torch.from_numpy(gf)
-                gf = gf.to(device=grad_output.device, dtype=ctx.flux_dtype)
             if ctx.needs_input_grad[1]:
                 gp = simulate_vis_source_adjoint(grad_output, fluxes=fluxes, wrt="radec", **pos, **ctx.kwargs)
-                if not _is_tensor(gp):
-                    gp = torch.from_numpy(gp)
-                gp = gp.to(device=ctx.pos_device, dtype=ctx.pos_dtype)
-            return gf, gp, None
+            return _as_grad(gf, grad_output.device, ctx.flux_dtype), _as_grad(gp, ctx.pos_device, ctx.pos_dtype), None
 
         @staticmethod
         def jvp(ctx, d_fluxes, d_radec, _):
-            # a missing tangent (None) skips its rounds
             fluxes, radec = ctx.saved_tensors
             if d_fluxes is None and d_radec is None:
                 return None
-            rd = radec.detach().cpu().numpy().astype(np.float64)
-            dv = simulate_vis_jvp(fluxes=fluxes, ra=rd[:, 0].copy(), dec=rd[:, 1].copy(),
-                                  d_radec=None if d_radec is None else d_radec.detach(),
-                                  d_fluxes=None if d_fluxes is None else d_fluxes.detach(), **ctx.kwargs)
+            dv = simulate_vis_jvp(fluxes=fluxes, **_radec_columns(radec),
+                                  **_detached(d_radec=d_radec, d_fluxes=d_fluxes), **ctx.kwargs)
             return _tangent_tensor(dv, fluxes)
 
     return _SimulateVisSky
-
-
-_FN_SKY = None
 
 
 def torch_simulate_vis_sky(fluxes, radec, **kwargs):
@@ -1509,7 +1256,6 @@ def torch_simulate_vis_sky(fluxes, radec, **kwargs):
     (``ctx.needs_input_grad``): ``simulate_vis_adjoint`` for the fluxes, ``simulate_vis_source_adjoint(wrt="radec")`` for the
     positions, which needs ``coord_method="SiderealRotation"`` or device astrometry.  Forward mode
     (``torch.autograd.forward_ad``) runs ``simulate_vis_jvp`` on the tangents present, under the same condition."""
-    global _FN_SKY
     if "ra" in kwargs or "dec" in kwargs:
         raise TypeError("torch_simulate_vis_sky takes the source positions as the tensor radec, not ra= / dec=")
     if kwargs.get("beam_coefs") is not None:
@@ -1518,6 +1264,4 @@ def torch_simulate_vis_sky(fluxes, radec, **kwargs):
         raise TypeError("torch_simulate_vis_sky does not take adjoint_path: its passes run the type-3 transform")
     if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
         raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
-    if _FN_SKY is None:
-        _FN_SKY = _sky_autograd_function()
-    return _FN_SKY.apply(fluxes, radec, kwargs)
+    return _function(_sky_autograd_function).apply(fluxes, radec, kwargs)

@@ -724,13 +724,8 @@ class GPUSimulationEngine(SimulationEngine):
                 # every time block lands in its slice of the result (fv_sim_run_into): no block-sized temporary, no
                 # second host copy
                 vis = out if out is not None else np.empty(h.out_shape(t1 - t0, f1 - f0), dtype=complex_dtype)
-                for tb in range(t0, t1, max(nblk_t, 1)):
-                    te = min(t1, tb + max(nblk_t, 1))
-                    if coord_mgr is not None:
-                        h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
-                        h.run(0, te - tb, f0, f1, out=vis[:, tb - t0:te - t0], shared=out_shared)
-                    else:
-                        h.run(tb, te, f0, f1, out=vis[:, tb - t0:te - t0], shared=out_shared)
+                for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+                    h.run(ta, te_, f0, f1, out=vis[:, tb - t0:te - t0], shared=out_shared)
             ok = True
         finally:
             if ok:
@@ -821,6 +816,35 @@ def _topo_from_coord_mgr(coord_mgr, time_indices):
     return np.stack(out)
 
 
+def _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+    """The time blocks of a run, ``nblk_t`` steps each: yields (tb, te, ta, te_) -- the block [tb, te) of the time axis and
+    the range [ta, te_) the handle ``h`` runs for it: the same, or with a coordinate manager (0, te - tb), after the
+    block's vectors have been streamed to the handle (``set_topo``)."""
+    step = max(nblk_t, 1)
+    for tb in range(t0, t1, step):
+        te = min(t1, tb + step)
+        if coord_mgr is not None:
+            h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
+            yield tb, te, 0, te - tb
+        else:
+            yield tb, te, tb, te
+
+
+def _result_block(dv, axis, lo, hi, whole):
+    """Where a run writes the steps [lo, hi) of ``dv``'s time ``axis``: ``dv`` itself when that is the whole result
+    (returns (dv, None)), else a contiguous scratch block and the slice of ``dv`` it is copied to afterwards."""
+    if whole:
+        return dv, None
+    dst = dv[(slice(None),) * axis + (slice(lo, hi),)]
+    if isinstance(dv, np.ndarray):
+        return np.empty(dst.shape, dtype=dv.dtype), dst
+    import torch
+
+    blk = torch.empty_like(dst, memory_format=torch.contiguous_format)
+    torch.cuda.synchronize(blk.device)
+    return blk, dst
+
+
 def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False, positions=False, sources=False,
                  gbls=None):
     """The adjoint's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors), each block's
@@ -830,10 +854,8 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, ba
     direction gradient and every block's ``run_source_adjoint`` fills that block's rows).  Every ``run_adjoint`` call ends
     synchronised."""
     on_device = not isinstance(g, np.ndarray)
-    step = max(nblk_t, 1)
     first = True
-    for tb in range(t0, t1, step):
-        te = min(t1, tb + step)
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
         blk = g[:, tb - t0:te - t0]
         if on_device:
             import torch
@@ -842,11 +864,6 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, ba
             torch.cuda.synchronize(blk.device)  # a copy .contiguous() queued on torch's stream is done before the library reads
         else:
             blk = np.ascontiguousarray(blk)
-        if coord_mgr is not None:
-            h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
-            ta, te_ = 0, te - tb
-        else:
-            ta, te_ = tb, te
         if basis:
             if gflux is not None or gcoefs is not None:
                 h.run_basis_adjoint(ta, te_, f0, f1, blk, gflux, gcoefs, not first)
@@ -872,32 +889,14 @@ def _run_tangent(h, dbls, dtopo, dv, t0, t1, f0, f1, nblk_t, coord_mgr, basis=Fa
     """The tangent's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors); every block's
     ``run_tangent`` takes its rows of ``dtopo`` and fills its slice of ``dv`` (a block that is not the whole result goes
     through a contiguous temporary).  ``basis``: ``run_basis_position_tangent`` on ``dbls``.  Every call ends synchronised."""
-    on_device = not isinstance(dv, np.ndarray)
-    step = max(nblk_t, 1)
-    for tb in range(t0, t1, step):
-        te = min(t1, tb + step)
-        whole = tb == t0 and te == t1
-        rows = None if dtopo is None else dtopo[tb - t0:te - t0]  # rows of a C-contiguous array: a contiguous view
-        if whole:
-            blk = dv
-        elif on_device:
-            import torch
-
-            blk = torch.empty_like(dv[:, tb - t0:te - t0], memory_format=torch.contiguous_format)
-            torch.cuda.synchronize(blk.device)
-        else:
-            blk = np.empty(dv[:, tb - t0:te - t0].shape, dtype=dv.dtype)
-        if coord_mgr is not None:
-            h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
-            ta, te_ = 0, te - tb
-        else:
-            ta, te_ = tb, te
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+        blk, dst = _result_block(dv, 1, tb - t0, te - t0, tb == t0 and te == t1)
         if basis:
             h.run_basis_position_tangent(ta, te_, f0, f1, dbls, blk)
-        else:
-            h.run_tangent(ta, te_, f0, f1, dbls, rows, blk)
-        if not whole:
-            dv[:, tb - t0:te - t0] = blk
+        else:  # (rows of a C-contiguous array: a contiguous view)
+            h.run_tangent(ta, te_, f0, f1, dbls, None if dtopo is None else dtopo[tb - t0:te - t0], blk)
+        if dst is not None:
+            dst[...] = blk
     if t1 <= t0:
         dv[...] = 0
     return dv
@@ -907,28 +906,11 @@ def _run_basis_tangent(h, dcoefs, dv, t0, t1, f0, f1, nblk_t, coord_mgr):
     """The basis tangent's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors); every
     block's ``run_basis_tangent`` fills its slice ``dv[:, :, block]`` of every direction (a block that is not the whole
     result goes through a contiguous temporary).  Every call ends synchronised."""
-    on_device = not isinstance(dv, np.ndarray)
-    step = max(nblk_t, 1)
-    for tb in range(t0, t1, step):
-        te = min(t1, tb + step)
-        whole = tb == t0 and te == t1
-        if whole:
-            blk = dv
-        elif on_device:
-            import torch
-
-            blk = torch.empty_like(dv[:, :, tb - t0:te - t0], memory_format=torch.contiguous_format)
-            torch.cuda.synchronize(blk.device)
-        else:
-            blk = np.empty(dv[:, :, tb - t0:te - t0].shape, dtype=dv.dtype)
-        if coord_mgr is not None:
-            h.set_topo(_topo_from_coord_mgr(coord_mgr, range(tb, te)))
-            ta, te_ = 0, te - tb
-        else:
-            ta, te_ = tb, te
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+        blk, dst = _result_block(dv, 2, tb - t0, te - t0, tb == t0 and te == t1)
         h.run_basis_tangent(ta, te_, f0, f1, dcoefs, blk)
-        if not whole:
-            dv[:, :, tb - t0:te - t0] = blk
+        if dst is not None:
+            dst[...] = blk
     if t1 <= t0:
         dv[...] = 0
     return dv

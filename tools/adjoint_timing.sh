@@ -23,20 +23,20 @@ step() {  # output file, seconds, command...
         exit $rc
     fi
 }
-step "$OUT/timing_c2.json" 300 python tools/adjoint_timing.py --config C2
-step "$OUT/timing_c3.json" 600 python tools/adjoint_timing.py --config C3
+step "$OUT/timing_c2.json" 300 python tools/pass_timing.py --family adjoint --config C2
+step "$OUT/timing_c3.json" 600 python tools/pass_timing.py --family adjoint --config C3
 step "$OUT/rocprof.log" 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o adj_c3 -- \
-    python tools/adjoint_timing.py --config C3 --adjoint-only
+    python tools/pass_timing.py --family adjoint --config C3 --profile adjoint
 find "$OUT/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/c3_adjoint_kernel_stats.csv" \;
 for c in "C2 2" "C3 2" "C3 32"; do
     set -- $c
     tag=$(echo "$1" | tr A-Z a-z)_${2}ch
     if [ -n "${PARENT:-}" ]; then
-        step "$OUT/lattice_parent_${tag}.json" 600 python tools/adjoint_timing.py --config "$1" --nfreq "$2" --lattice --package "$PARENT"
+        step "$OUT/lattice_parent_${tag}.json" 600 python tools/pass_timing.py --family adjoint --config "$1" --nfreq "$2" --lattice --package "$PARENT"
     fi
-    step "$OUT/lattice_type3_${tag}.json" 600 python tools/adjoint_timing.py --config "$1" --nfreq "$2" --lattice --adjoint-path type3
-    step "$OUT/lattice_type2_${tag}.json" 600 python tools/adjoint_timing.py --config "$1" --nfreq "$2" --lattice --adjoint-path type2
+    step "$OUT/lattice_type3_${tag}.json" 600 python tools/pass_timing.py --family adjoint --config "$1" --nfreq "$2" --lattice --adjoint-path type3
+    step "$OUT/lattice_type2_${tag}.json" 600 python tools/pass_timing.py --family adjoint --config "$1" --nfreq "$2" --lattice --adjoint-path type2
 done
 step "$OUT/rocprof_type2.log" 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_type2" -o adj2_c3 -- \
-    python tools/adjoint_timing.py --config C3 --lattice --adjoint-path type2 --adjoint-only
+    python tools/pass_timing.py --family adjoint --config C3 --lattice --adjoint-path type2 --profile adjoint
 find "$OUT/trace_type2" -name "*kernel_stats.csv" -exec cp {} "$OUT/c3_type2_adjoint_kernel_stats.csv" \;

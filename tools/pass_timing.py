@@ -1,0 +1,224 @@
+"""Time per time step of the forward run and of the derivative passes, one family of passes per call.
+
+    python tools/pass_timing.py --family FAMILY [--config C] [--nsrc N] [--nfreq F] [--ntimes T] [--repeats R]
+                                [--only PASS ...] [--profile PASS] [--package DIR]
+
+    family          passes                                                          default configuration
+    adjoint         forward adjoint                                                 C3, 2 channels
+    basis_adjoint   forward fluxes beam_coefs both                                  C5, 4 channels  (--small: HERA-37, K = 3)
+    position        forward position                                                C3, 8 channels  (--array)
+    source          forward fluxes sources                                          C3, 8 channels
+    tangent         forward position source tangent_baselines tangent_directions
+                    tangent_both                                                    C3, 8 channels  (--array)
+    basis_tangent   forward tangent_1 tangent_n beam_coefs                          C5, 8 channels  (--ndir)
+    basis_position  forward adjoint tangent                                         C5, 8 channels
+
+Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
+steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
+has always printed.  --only PASS (repeatable) times those passes alone: ``--only forward`` is what runs on a checkout from
+before the family's passes.  --profile PASS: one call of that pass on a cold handle and nothing else, for a kernel trace
+(rocprofv3 --kernel-trace --stats -- python tools/pass_timing.py --family source --profile sources).  --package: the
+checkout whose fftvis_amd is measured (an earlier commit's, built in place; default: this one).  --array surveyed
+(position, tangent): seeded N(0, 2 cm) errors in x, y and 3 cm in z on the ideal array.  --lattice (adjoint): the
+reference's default call on a griddable array (force_use_type3=False: the forward is the type-1 transform);
+--adjoint-path (adjoint): the adjoint's transform there.  A flag of another family is an error.
+tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+
+def surveyed(ants, seed=2):
+    """The array with seeded survey errors: N(0, 2 cm) in x and y, N(0, 3 cm) in z."""
+    rng = np.random.default_rng(seed)
+    err = rng.normal(size=(len(ants), 3)) * np.array([0.02, 0.02, 0.03])
+    return {k: np.asarray(p, float) + err[i] for i, (k, p) in enumerate(ants.items())}
+
+
+def small_basis_config(fv, nfreq, ntimes):
+    """HERA-37 (C2's array), 1e4 sources, three Airy dishes as basis beams, random coefficients, fp64, eps 6e-8."""
+    cfg = fv.synth.make_config("C2", nfreq=nfreq, ntimes=ntimes)
+    rng = np.random.default_rng(1)
+    nant = len(cfg["ants"])
+    coefs = 0.05 * (rng.normal(size=(nant, 3, nfreq)) + 1j * rng.normal(size=(nant, 3, nfreq)))
+    coefs[:, 0, :] += 1.0
+    cfg.update(polarized=True, beam=[fv.AiryBeam(d) for d in (14.0, 13.0, 15.0)], beam_coefs=coefs)
+    return cfg
+
+
+# Every family: (head, calls) from the parsed arguments, the package, the configuration and a seeded generator.  ``head``
+# holds the JSON line's leading keys, ``calls`` the passes by name; the gradient G is drawn first, as it always was.
+
+def _g(a, cfg, rng, cast=False):
+    nbls = len(cfg["baselines"])
+    g = rng.normal(size=(a.nfreq, a.ntimes, 2, 2, nbls) if cfg["polarized"] else (a.nfreq, a.ntimes, nbls)) + 0j
+    return g.astype(np.complex64 if cfg["precision"] == 1 else np.complex128) if cast else g
+
+
+def adjoint(a, fv, cfg, rng):
+    if a.lattice:
+        cfg["force_use_type3"] = False
+    g = _g(a, cfg, rng)
+    kw = {k: v for k, v in cfg.items() if k != "fluxes"}
+    if a.adjoint_path != "type3":  # (the default is left out: a checkout from before the keyword takes the same call)
+        kw["adjoint_path"] = a.adjoint_path
+    head = {"config": a.config, "polarized": bool(cfg["polarized"]), "lattice": bool(a.lattice), "adjoint_path": a.adjoint_path}
+    return head, {"forward": lambda: fv.simulate_vis(**cfg), "adjoint": lambda: fv.simulate_vis_adjoint(g, **kw)}
+
+
+def basis_adjoint(a, fv, cfg, rng):
+    g = _g(a, cfg, rng, cast=True)
+    calls = {"forward": lambda: fv.simulate_vis(**cfg)}
+    for name, wrt in (("fluxes", "fluxes"), ("beam_coefs", "beam_coefs"), ("both", ("fluxes", "beam_coefs"))):
+        calls[name] = lambda wrt=wrt: fv.simulate_vis_basis_adjoint(g, **cfg, wrt=wrt)
+    return {"config": "small" if a.small else a.config, "nbasis": len(cfg["beam"]), "precision": cfg["precision"]}, calls
+
+
+def position(a, fv, cfg, rng):
+    g = _g(a, cfg, rng)
+    return {"array": a.array, "precision": cfg["precision"]}, {
+        "forward": lambda: fv.simulate_vis(**cfg),
+        "position": lambda: fv.simulate_vis_position_adjoint(g, **cfg, wrt="ants")}
+
+
+def source(a, fv, cfg, rng):
+    g = _g(a, cfg, rng)
+    no_flux = {k: v for k, v in cfg.items() if k != "fluxes"}
+    return {"precision": cfg["precision"], "polarized": bool(cfg["polarized"])}, {
+        "forward": lambda: fv.simulate_vis(**cfg),
+        "fluxes": lambda: fv.simulate_vis_adjoint(g, **no_flux, full_stokes=np.ndim(cfg["fluxes"]) == 3),
+        "sources": lambda: fv.simulate_vis_source_adjoint(g, **cfg, wrt="radec")}
+
+
+def tangent(a, fv, cfg, rng):
+    g = _g(a, cfg, rng)
+    db, dt = rng.normal(size=(len(cfg["baselines"]), 3)), rng.normal(size=(a.ntimes, np.size(cfg["ra"]), 3))
+    head = {"array": a.array, "precision": cfg["precision"], "lib": os.environ.get("FFTVIS_HIP_LIB", "in-tree")}
+    return head, {
+        "forward": lambda: fv.simulate_vis(**cfg),
+        "position": lambda: fv.simulate_vis_position_adjoint(g, **cfg, wrt="baselines"),
+        "source": lambda: fv.simulate_vis_source_adjoint(g, **cfg, wrt="topo"),
+        "tangent_baselines": lambda: fv.simulate_vis_jvp(**cfg, d_baselines=db),
+        "tangent_directions": lambda: fv.simulate_vis_jvp(**cfg, d_topo=dt),
+        "tangent_both": lambda: fv.simulate_vis_jvp(**cfg, d_baselines=db, d_topo=dt)}
+
+
+def basis_tangent(a, fv, cfg, rng):
+    g = _g(a, cfg, rng, cast=True)
+    shape = (a.ndir,) + np.shape(cfg["beam_coefs"])
+    d = (rng.normal(size=shape) + 1j * rng.normal(size=shape)).astype(g.dtype)
+    head = {"config": a.config, "nbasis": len(cfg["beam"]), "precision": cfg["precision"], "ndir": a.ndir}
+    return head, {
+        "forward": lambda: fv.simulate_vis(**cfg),
+        "tangent_1": lambda: fv.simulate_vis_basis_jvp(**cfg, d_beam_coefs=d[0]),
+        "tangent_n": lambda: fv.simulate_vis_basis_jvp(**cfg, d_beam_coefs=d),
+        "beam_coefs": lambda: fv.simulate_vis_basis_adjoint(g, **cfg, wrt="beam_coefs")}
+
+
+def basis_position(a, fv, cfg, rng):
+    g = _g(a, cfg, rng, cast=True)
+    db = rng.normal(size=(len(cfg["baselines"]), 3))
+    return {"config": a.config, "nbasis": len(cfg["beam"]), "precision": cfg["precision"]}, {
+        "forward": lambda: fv.simulate_vis(**cfg),
+        "adjoint": lambda: fv.simulate_vis_basis_adjoint(g, **cfg, wrt="baselines"),
+        "tangent": lambda: fv.simulate_vis_basis_jvp(**cfg, d_baselines=db)}
+
+
+# family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
+#          ratios {key: (pass, pass it is divided by)})
+FAMILIES = {
+    "adjoint": (adjoint, "C3", 2, ("lattice", "adjoint_path"), "range", {"adjoint_over_forward": ("adjoint", "forward")}),
+    "basis_adjoint": (basis_adjoint, "C5", 4, ("small",), None, {}),
+    "position": (position, "C3", 8, ("array",), "runs", {"position_over_forward": ("position", "forward")}),
+    "source": (source, "C3", 8, (), "runs", {"sources_over_fluxes": ("sources", "fluxes"),
+                                            "sources_over_forward": ("sources", "forward")}),
+    "tangent": (tangent, "C3", 8, ("array",), "runs", {}),
+    "basis_tangent": (basis_tangent, "C5", 8, ("ndir",), "runs", {}),
+    "basis_position": (basis_position, "C5", 8, (), "runs", {"adjoint_over_forward": ("adjoint", "forward"),
+                                                            "tangent_over_forward": ("tangent", "forward")}),
+}
+OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8}  # and their defaults
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--family", choices=list(FAMILIES), required=True)
+    ap.add_argument("--config", default=None)
+    ap.add_argument("--nsrc", type=int, default=None)
+    ap.add_argument("--nfreq", type=int, default=None)
+    ap.add_argument("--ntimes", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--only", action="append", default=None, metavar="PASS")
+    ap.add_argument("--profile", default=None, metavar="PASS")
+    ap.add_argument("--package", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                    help="checkout whose fftvis_amd is measured (default: this one)")
+    ap.add_argument("--array", choices=["ideal", "surveyed"], default=None)
+    ap.add_argument("--lattice", action="store_true", default=None, help="force_use_type3=False: the type-1 forward")
+    ap.add_argument("--adjoint-path", choices=["type3", "type2", "auto"], default=None)
+    ap.add_argument("--small", action="store_true", default=None, help="HERA-37, K = 3 Airy dishes, fp64")
+    ap.add_argument("--ndir", type=int, default=None)
+    a = ap.parse_args()
+    build, config, nfreq, own, spread, ratios = FAMILIES[a.family]
+    for flag, default in OWN_FLAGS.items():
+        if flag not in own and getattr(a, flag) is not None:
+            ap.error(f"--{flag.replace('_', '-')} does not apply to --family {a.family}")
+        if getattr(a, flag) is None:
+            setattr(a, flag, default)
+    a.config, a.nfreq = a.config or config, a.nfreq or nfreq
+    sys.path.insert(0, os.path.abspath(a.package))
+    import fftvis_amd as fv
+    from fftvis_amd import synth  # noqa: F401  (fv.synth)
+
+    cfg = small_basis_config(fv, a.nfreq, a.ntimes) if a.small else synth.make_config(a.config, nsrc=a.nsrc, nfreq=a.nfreq,
+                                                                                      ntimes=a.ntimes)
+    if a.array == "surveyed":
+        cfg["ants"] = surveyed(cfg["ants"])
+    cfg["upsample_factor"] = "auto"  # the benchmark's setting
+    head, calls = build(a, fv, cfg, np.random.default_rng(0))
+    for name in (a.only or []) + ([a.profile] if a.profile else []):
+        if name not in calls:
+            ap.error(f"--family {a.family} has the passes {', '.join(calls)}, not {name!r}")
+    if a.profile:
+        calls[a.profile]()
+        return
+
+    def timed(fn):
+        fn()  # warm: handle, plans, tables
+        ts = []
+        for _ in range(a.repeats):
+            t = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t)
+        return [round(1e3 * t / a.ntimes, 3) for t in ts]
+
+    out = dict(head, nsrc=int(np.size(cfg["ra"])), nbls=len(cfg["baselines"]), nfreq=a.nfreq, ntimes=a.ntimes)
+    for name, fn in calls.items():
+        if a.only and name not in a.only:
+            continue
+        runs = timed(fn)
+        out[name + "_ms_per_step"] = round(float(np.median(runs)), 3)
+        if spread == "runs":
+            out[name + "_runs"] = runs
+        elif spread == "range":
+            out[name + "_range"] = [min(runs), max(runs)]
+        print(json.dumps({name: runs}), file=sys.stderr, flush=True)
+    for key, (num, den) in ratios.items():
+        if num + "_ms_per_step" in out and den + "_ms_per_step" in out:
+            out[key] = round(out[num + "_ms_per_step"] / out[den + "_ms_per_step"], 3)
+    if all(k + "_ms_per_step" in out for k in ("forward", "tangent_1", "tangent_n")):  # (basis_tangent)
+        # per direction, against TWO forward runs: what (V(C + D) - V(C - D)) / 2 costs a caller without the pass
+        two = 2.0 * out["forward_ms_per_step"]
+        out["tangent_1_over_two_forwards"] = round(out["tangent_1_ms_per_step"] / two, 3)
+        out["tangent_n_per_direction_over_two_forwards"] = round(out["tangent_n_ms_per_step"] / a.ndir / two, 3)
+        out["further_direction_ms_per_step"] = round((out["tangent_n_ms_per_step"] - out["tangent_1_ms_per_step"]) /
+                                                     max(a.ndir - 1, 1), 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
