@@ -8,7 +8,8 @@ with respect to the fluxes, the coefficients and the antenna positions (``simula
 ``torch_simulate_vis_basis``, ``torch_simulate_vis_basis_array``), and the
 gradient with respect to the antenna positions (``simulate_vis_position_adjoint``, ``torch_simulate_vis_array``) and to
 the source positions (``simulate_vis_source_adjoint``, ``torch_simulate_vis_sky``), and the forward-mode tangent along
-all three (``simulate_vis_jvp``).
+all three (``simulate_vis_jvp``), and the source positions through basis beams
+(``simulate_vis_basis_source_adjoint``, ``simulate_vis_basis_source_jvp``, ``torch_simulate_vis_basis_sky``).
 """
 
 __version__ = "0.1.0"
@@ -24,6 +25,8 @@ from .adjoint import (  # noqa: F401
     simulate_vis_adjoint,
     simulate_vis_basis_adjoint,
     simulate_vis_basis_jvp,
+    simulate_vis_basis_source_adjoint,
+    simulate_vis_basis_source_jvp,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,
     simulate_vis_source_adjoint,
@@ -31,6 +34,7 @@ from .adjoint import (  # noqa: F401
     torch_simulate_vis_array,
     torch_simulate_vis_basis,
     torch_simulate_vis_basis_array,
+    torch_simulate_vis_basis_sky,
     torch_simulate_vis_sky,
     topo_to_radec_gradient,
 )

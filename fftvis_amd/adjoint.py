@@ -514,7 +514,8 @@ def simulate_vis_basis_adjoint(
     * ``"ants"``: (nant, 3) float64, rows in ``ants``' iteration order: ``baseline_to_antenna_gradient`` of the baseline
       result.
 
-    Not covered: source-position derivatives through basis beams, a lattice form, multi-GPU.
+    The source positions have a pass of their own, ``simulate_vis_basis_source_adjoint``.  Not covered: a lattice form,
+    multi-GPU.
 
     ``wrt`` names the gradients wanted -- a name, or a tuple of names; the result is that gradient, or a tuple in
     ``wrt``'s order.  Only the passes asked for run; a gradient computed alone equals the one from a joint call bit for
@@ -723,7 +724,8 @@ def simulate_vis_basis_jvp(
       fluxes times topo_d (``fv_sim_run_basis_position_tangent``: about three forward runs), added to the rest; on a flat
       array the up component still enters.  With a stack of ``d_beam_coefs`` it is a ValueError.
 
-    Not covered: source-position tangents through basis beams, a lattice form, several position directions per call.
+    The source positions have a pass of their own, ``simulate_vis_basis_source_jvp``.  Not covered: a lattice form, several
+    position directions per call.
 
     No input at all gives zeros.  numpy arrays, or torch tensors: when a tangent is a tensor on the run's device
     ``d_beam_coefs`` is handed over by pointer and the result is a tensor on that device; host tensors in, a host tensor
@@ -1265,3 +1267,239 @@ def torch_simulate_vis_sky(fluxes, radec, **kwargs):
     if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
         raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
     return _function(_sky_autograd_function).apply(fluxes, radec, kwargs)
+
+
+def _basis_run(name, args) -> _Run:
+    """The run of a source pass through basis beams: the forward's refusals first."""
+    if args["beam_coefs"] is None:
+        raise ValueError(f"{name} needs beam_coefs (without basis beams simulate_vis_source_adjoint and simulate_vis_jvp "
+                         "are the passes)")
+    if not args["polarized"]:  # the forward's message
+        raise ValueError(
+            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
+        )
+    return _describe_run(args)
+
+
+def simulate_vis_basis_source_adjoint(
+    vis,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    beam_coefs,
+    telescope_loc,
+    *,
+    wrt="radec",
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = True,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """Gradient of the basis-beam simulation ``simulate_vis(..., beam=<K basis beams>, beam_coefs=C)`` with respect to the
+    source positions, for a visibility-shaped ``vis`` (G = dL/dV, dL = Re sum conj(G) dV): ``simulate_vis_source_adjoint``'s
+    quantity through basis beams.
+
+    V_b = sum_{k<=l} (w1 M_kl(b) + w2 M_kl(b) at the feed-transposed slot), w1 = conj(C[a1,k]) C[a2,l],
+    w2 = conj(C[a1,l]) C[a2,k] (``reference_compat=False``: the (l, k) part of an off-diagonal term of complex beams is
+    conj(M_kl(-b))^T), and every M_kl is a sum over sources of the strengths of basis beams k and l times the phase: the
+    gradient is the source pass's, once per term -- a phase term and a beam term, summed over the terms
+    (``fv_sim_run_basis_source_adjoint``).  Tangential, exactly 0 below the horizon; the horizon cut and the path choice
+    are not differentiated; between two order-0 tables the beam term is 0 by definition, decided per term.
+
+    * ``wrt="topo"``: (ntimes, nsrc, 3) float64, ENU, tangential; valid with every source of coordinates;
+    * ``wrt="radec"``: (nsrc, 2) float64, columns (ra, dec), per radian: ``topo_to_radec_gradient`` of the above with
+      ``radec_jacobian`` -- for ``coord_method="SiderealRotation"`` and device astrometry; with a ``coord_mgr`` (or a matvis
+      manager the engine would build) ValueError: ask for ``wrt="topo"``;
+    * a tuple of both names returns a tuple in that order.
+
+    ``fluxes`` and ``beam_coefs`` are the forward's.  ``vis`` is a numpy array or a torch tensor on the run's device
+    (handed over by pointer; the results are then tensors on that device).  Every other keyword means what it means for
+    ``simulate_vis``, ``reference_compat`` included; ``polarized`` must be True and ``beam_idx`` None, as for the forward.
+    The cost is 1 + D transforms per term where ``simulate_vis_basis_adjoint(wrt="fluxes")`` runs one (D = 2 on a flat
+    array, 3 otherwise) plus five beam evaluations per (source, channel, term).  Not covered: a lattice form, several
+    directions per call, multi-GPU, a joint call with the flux gradient that shares its transforms."""
+    args = locals()
+    single, names = _parse_wrt(wrt, ("topo", "radec"), "'topo', 'radec' or both")
+    run = _basis_run("simulate_vis_basis_source_adjoint", args)
+    run = _own_radec_chain(run, "wrt='radec'", "radec" in names, "ask for wrt='topo' and apply its Jacobian",
+                           "ask for wrt='topo'")
+    fluxes = _host_fluxes(run, fluxes)
+    g, (gtopo,), on_device = _gradient_buffers(run, vis, [((run.ntimes, run.nsrc, 3), "float64")])
+    gtopo = _engine_simulate(run, fluxes, basis_source_of=("adjoint", g, gtopo))
+    res = {"topo": gtopo}
+    if "radec" in names:
+        res["radec"] = topo_to_radec_gradient(gtopo, _radec_jacobian_of(run))
+    return _select(res, single, names, vis, on_device)
+
+
+def simulate_vis_basis_source_jvp(
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    beam_coefs,
+    telescope_loc,
+    *,
+    d_radec=None,
+    d_topo=None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = True,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """Forward-mode tangent of the basis-beam simulation ``simulate_vis(..., beam=<K basis beams>, beam_coefs=C)`` along a
+    change of the source positions: dV in ``simulate_vis``'s shape and dtype, the transpose of
+    ``simulate_vis_basis_source_adjoint`` -- ``Re <dV, G> = sum d_topo . gtopo`` for every G.
+
+    * ``d_radec``: (nsrc, 2) radians, columns (ra, dec), chained on the host through ``radec_jacobian`` -- for
+      ``coord_method="SiderealRotation"`` and device astrometry; with a ``coord_mgr`` (or a matvis manager the engine would
+      build) only ``d_topo`` is served: ValueError;
+    * ``d_topo``: (ntimes, nsrc, 3), ENU; its radial part is removed, and a source below the horizon at time t contributes
+      exactly 0 there.  Giving both is a ValueError.
+
+    Per (k <= l) term the 1 + D strength sets of ``simulate_vis_jvp``'s source side with the term's beams, and 1 + D rounds
+    whose gathers carry the basis weights (``fv_sim_run_basis_source_tangent``).  With neither input: zeros and no device
+    work.  numpy arrays, or torch tensors: a tangent on the run's device is handed over by pointer and the result is a
+    tensor on that device; host tensors in, a host tensor out.  Every other keyword means what it means for
+    ``simulate_vis``.  Not covered: a lattice form, several directions per call."""
+    args = locals()
+    if d_radec is not None and d_topo is not None:
+        raise ValueError("give the source tangent as d_radec or as d_topo, not both")
+    run = _basis_run("simulate_vis_basis_source_jvp", args)
+    run = _own_radec_chain(run, "d_radec", d_radec is not None, "apply its Jacobian and pass d_topo", "pass d_topo")
+    tangents = (d_radec, d_topo)
+    device = _run_device(run, tangents, "a tangent")
+    fluxes = _host_fluxes(run, fluxes)
+    if d_radec is not None and tuple(d_radec.shape) != (run.nsrc, 2):
+        raise ValueError(f"d_radec must have shape ({run.nsrc}, 2), got {tuple(d_radec.shape)}")
+    if d_topo is not None and tuple(d_topo.shape) != (run.ntimes, run.nsrc, 3):
+        raise ValueError(f"d_topo must have shape ({run.ntimes}, {run.nsrc}, 3), got {tuple(d_topo.shape)}")
+    if d_radec is not None:
+        d_topo = np.einsum("tjdc,jc->tjd", _radec_jacobian_of(run), _host(d_radec).astype(np.float64))
+    dt_ = _buffer(run, device, d_topo, "float64")
+    dv = _zeros(device, run.vis_shape, run.cdt)
+    if dt_ is not None:
+        _synchronize(device)
+        dv = _engine_simulate(run, fluxes, basis_source_of=("tangent", dt_, dv))
+    if device is None and any(_is_tensor(x) for x in tangents):  # host tensors in, a host tensor out
+        import torch
+
+        dv = torch.from_numpy(np.ascontiguousarray(dv))
+    return dv
+
+
+def _basis_sky_autograd_function():
+    import torch
+
+    class _SimulateVisBasisSky(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fluxes, beam_coefs, radec, kwargs):
+            ctx.kwargs = kwargs
+            ctx.flux_dtype, ctx.coef_dtype, ctx.pos_dtype = fluxes.dtype, beam_coefs.dtype, radec.dtype
+            ctx.coef_device, ctx.pos_device = beam_coefs.device, radec.device
+            ctx.save_for_backward(fluxes, beam_coefs, radec)
+            ctx.save_for_forward(fluxes, beam_coefs, radec)
+            return _forward_tensor(dict(kwargs, **_radec_columns(radec)), fluxes=fluxes, beam_coefs=beam_coefs)
+
+        @staticmethod
+        def backward(ctx, grad_output):
+            fluxes, beam_coefs, radec = ctx.saved_tensors
+            pos = _radec_columns(radec)
+            wrt = tuple(n for n, need in zip(("fluxes", "beam_coefs"), ctx.needs_input_grad[:2]) if need)
+            got, gp = {}, None
+            if wrt:
+                got = dict(zip(wrt, simulate_vis_basis_adjoint(grad_output, fluxes=fluxes, beam_coefs=beam_coefs, wrt=wrt,
+                                                               **pos, **ctx.kwargs)))
+            if ctx.needs_input_grad[2]:
+                gp = simulate_vis_basis_source_adjoint(grad_output, fluxes=fluxes, beam_coefs=beam_coefs, wrt="radec",
+                                                       **pos, **ctx.kwargs)
+            return (_as_grad(got.get("fluxes"), grad_output.device, ctx.flux_dtype),
+                    _as_grad(got.get("beam_coefs"), ctx.coef_device, ctx.coef_dtype),
+                    _as_grad(gp, ctx.pos_device, ctx.pos_dtype), None)
+
+        @staticmethod
+        def jvp(ctx, d_fluxes, d_beam_coefs, d_radec, _):
+            fluxes, beam_coefs, radec = ctx.saved_tensors
+            pos = _radec_columns(radec)
+            if d_fluxes is None and d_beam_coefs is None and d_radec is None:
+                return None
+            dv = None
+            if d_fluxes is not None or d_beam_coefs is not None:
+                dv = _tangent_tensor(simulate_vis_basis_jvp(fluxes=fluxes, beam_coefs=beam_coefs, **pos,
+                                                            **_detached(d_beam_coefs=d_beam_coefs, d_fluxes=d_fluxes),
+                                                            **ctx.kwargs), fluxes)
+            if d_radec is not None:
+                ds = _tangent_tensor(simulate_vis_basis_source_jvp(fluxes=fluxes, beam_coefs=beam_coefs, **pos,
+                                                                   **_detached(d_radec=d_radec), **ctx.kwargs), fluxes)
+                dv = ds if dv is None else dv + ds
+            return dv
+
+    return _SimulateVisBasisSky
+
+
+def torch_simulate_vis_basis_sky(fluxes, beam_coefs, radec, **kwargs):
+    """The basis-beam simulation as a torch operation differentiable in the fluxes, the coefficients and the source
+    positions -- the unknowns of a joint beam and catalogue fit: ``fluxes`` real, (nsrc, nfreqs) or (nsrc, nfreqs, 4);
+    ``beam_coefs`` complex, (nant, nbasis, nfreqs); ``radec`` real, (nsrc, 2), columns (ra, dec) in radians.  Every other
+    argument is a keyword of ``simulate_vis`` -- but for ``ra`` and ``dec``, which the tensor replaces (TypeError).  Returns
+    the visibilities as a complex tensor on ``fluxes``' device.  The backward pass runs only what autograd asks for
+    (``ctx.needs_input_grad``): one ``simulate_vis_basis_adjoint`` call for the fluxes and / or the coefficients,
+    ``simulate_vis_basis_source_adjoint(wrt="radec")`` for the positions, which needs ``coord_method="SiderealRotation"`` or
+    device astrometry.  Forward mode (``torch.autograd.forward_ad``) runs ``simulate_vis_basis_jvp`` and
+    ``simulate_vis_basis_source_jvp`` on the tangents present, under the same condition."""
+    if "ra" in kwargs or "dec" in kwargs:
+        raise TypeError("torch_simulate_vis_basis_sky takes the source positions as the tensor radec, not ra= / dec=")
+    if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
+        raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
+    return _function(_basis_sky_autograd_function).apply(fluxes, beam_coefs, radec, kwargs)

@@ -637,7 +637,7 @@ int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const v
                    "on_device flags must be 0 or 1");
         FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->run_source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gtopo, gtopo_on_device, accumulate);
+        h->impl->run_source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gtopo, gtopo_on_device, accumulate, false);
     });
 }
 int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
@@ -684,6 +684,28 @@ int fv_sim_run_basis_position_tangent(fv_sim *h, int t0, int t1, int f0, int f1,
                    "on_device flags must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_tangent(t0, t1, f0, f1, dbls, dbls_on_device, nullptr, 0, out, out_on_device, true);
+    });
+}
+int fv_sim_run_basis_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device,
+                                    double *gtopo, int gtopo_on_device, int accumulate) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(gvis && gtopo, "null adjoint input or output");
+        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gtopo_on_device == 0 || gtopo_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gtopo, gtopo_on_device, accumulate, true);
+    });
+}
+int fv_sim_run_basis_source_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dtopo, int dtopo_on_device,
+                                    void *out, int out_on_device) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(out, "null output");
+        FV_REQUIRE(dtopo, "null source directions (dtopo)");
+        FV_REQUIRE((dtopo_on_device == 0 || dtopo_on_device == 1) && (out_on_device == 0 || out_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_tangent(t0, t1, f0, f1, nullptr, 0, dtopo, dtopo_on_device, out, out_on_device, true);
     });
 }
 int fv_sim_sync(fv_sim *h) { FV_SIM_CALL(h->impl->sync()); }

@@ -2446,7 +2446,8 @@ struct InterpArgs {
     //     i nu_f tg_w[km] V     (a weighted round: tg_w fp64 by global baseline id, nu_f = scale[fg], the channel's own),
     //     V                     (tg_w == nullptr: the beam term's round).
     // A pair's list holds every baseline once: one owner thread per slot and launch, plain read-modify-write.
-    // With basis beams (k_interp<.., BPOS>; Sim::run_basis_position_adjoint / _tangent; weighted rounds only) the two
+    // With basis beams (k_interp<.., BPOS>; Sim::run_basis_position_adjoint / _tangent; weighted rounds only -- the beam
+    // term's round of the source tangent through basis beams is the forward's basis epilogue itself) the two
     // epilogues carry the forward's basis weights w1 = conj(C[a1,kk]) C[a2,ll] and w2 = conj(C[a1,ll]) C[a2,kk], formed
     // and applied in fp64; basis_part and negate_all as in the forward:
     //   BPOS 1:  S += sum_r conj(G_r) w1 V_r + sum_r conj(G_rs) w2 V_r  into the member's ONE slot of gs, here
@@ -4308,8 +4309,12 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
             kern = herm ? (r9 ? k_interp<T, 2, true, 9, false, true, true> : k_interp<T, 2, true, 16, false, true, true>)
                         : (r9 ? k_interp<T, 2, false, 9, false, true, true> : k_interp<T, 2, false, 16, false, true, true>);
     }
-    const int bpos = basis && basis->nbasis > 0 ? (a.gs && basis->gs_weighted ? 1 : tan ? 2 : 0) : 0;
-    if (tan && !bpos) {  // the tangent epilogue's instantiations (no basis beams, never together with the gradient epilogue)
+    // (a basis term's unweighted tangent round -- the beam term of Sim::run_tangent's source side -- adds (w1 V, w2 V) as
+    // they are: the forward's own basis gather, chosen above)
+    const bool btan_plain = basis && basis->nbasis > 0 && tan && !tan->w;
+    const int bpos = basis && basis->nbasis > 0 ? (a.gs && basis->gs_weighted ? 1 : tan && tan->w ? 2 : 0) : 0;
+    FV_REQUIRE(!btan_plain || (!a.gs && !a.bt_d), "basis beam-term round: no other epilogue");
+    if (tan && !bpos && !btan_plain) {  // the tangent epilogue's instantiations (no basis beams, never together with the gradient epilogue)
         FV_REQUIRE(!basis && !a.gs, "tangent epilogue: no basis term and no gradient epilogue");
         a.tg_w = tan->w;
         kern = gdim == 2 ? (herm ? (r9 ? k_interp<T, 2, true, 9, false, false, false, true> : k_interp<T, 2, true, 16, false, false, false, true>)

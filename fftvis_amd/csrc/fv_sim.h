@@ -2055,11 +2055,12 @@ struct SimBase {
     virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                                    int gflux_on_device, void *gcoefs, int gcoefs_on_device, int accumulate) = 0;
     // basis: the entry point's kind of handle -- false fv_sim_run_position_adjoint / fv_sim_run_tangent (no basis beams),
-    // true fv_sim_run_basis_position_adjoint / fv_sim_run_basis_position_tangent (a handle with fv_sim_set_basis)
+    // true fv_sim_run_basis_position_adjoint / fv_sim_run_basis_position_tangent and fv_sim_run_basis_source_adjoint /
+    // fv_sim_run_basis_source_tangent (a handle with fv_sim_set_basis)
     virtual void run_position_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gbls,
                                       int gbls_on_device, int accumulate, bool basis) = 0;
     virtual void run_source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
-                                    int gtopo_on_device, int accumulate) = 0;
+                                    int gtopo_on_device, int accumulate, bool basis) = 0;
     virtual void run_tangent(int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
                              int dtopo_on_device, void *out, int out_on_device, bool basis) = 0;
     virtual void run_basis_tangent(int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir, void *out,
@@ -4211,6 +4212,32 @@ class Sim : public SimBase {
         p.t2_na = na;
     }
 
+    // The NUFFT sources of the transposed type-3 transforms (adjoint_flux, run_source_adjoint): per pair its runs' distinct
+    // sign-adjusted vectors, (D, adj_np) on the device in p.adj_pos; exact basis form (reference_compat off): an
+    // off-diagonal term's sources at b, then the same at -b.  Rebuilt when the targets or the count changed; both passes
+    // go through here, so what one leaves is what the other expects.
+    bool adj_mirrored(const Pair &p) const { return nbasis && !reference_compat && p.bi != p.bj; }
+    void adj_sources(int D) {
+        for (Pair &p : pairs) {
+            const int64_t nu = p.ustart ? p.nu : p.n;
+            const int64_t np = nu * (adj_mirrored(p) ? 2 : 1);
+            if (p.n == 0 || (p.adj_pos && p.adj_serial == targets_serial && p.adj_np == np)) continue;
+            std::vector<T> pos((size_t)D * np);
+            for (int64_t u = 0; u < nu; ++u) {
+                const int64_t m = p.ustart ? p.h_ustart[u] : u;
+                const double sg = p.h_flip[m] ? -1.0 : 1.0;
+                for (int d = 0; d < D; ++d) {
+                    pos[(size_t)d * np + u] = (T)(sg * h_bls[(size_t)d * nbls + p.h_idx[m]]);
+                    if (np > nu) pos[(size_t)d * np + nu + u] = -pos[(size_t)d * np + u];
+                }
+            }
+            p.adj_pos.reset(new DevBuf());
+            upload(*p.adj_pos, pos.data(), sizeof(T) * pos.size(), 0);
+            p.adj_serial = targets_serial;
+            p.adj_np = np;
+        }
+    }
+
     // The loop of run_adjoint.  Basis mode (run_basis_adjoint's flux pass): the pairs are the (k <= l) terms over all
     // baselines, the strengths carry every member's coefficient weights (k_adj_strengths_basis) and, in the exact form
     // (reference_compat off), an off-diagonal term has a second set of sources at -b.  Ends synchronised.
@@ -4254,31 +4281,12 @@ class Sim : public SimBase {
         } else {
             source_box(xc, X);
         }
-        // the NUFFT sources of every pair; exact basis form: an off-diagonal term's sources at b, then the same at -b
-        auto mirrored = [&](const Pair &p) { return nbasis && !reference_compat && p.bi != p.bj; };
-        auto adj_c = [&](const Pair &p) { return mirrored(p) ? (const double *)zero3 : (const double *)p.btc; };
-        auto adj_B = [&](const Pair &p) { return mirrored(p) ? (const double *)p.Bs : (const double *)p.B; };
-        for (Pair &p : pairs) {
-            const int64_t nu = p.ustart ? p.nu : p.n;
-            const int64_t np = nu * (mirrored(p) ? 2 : 1);
-            if (t2) {
-                p.adj_np = nu;
-                continue;
-            }
-            if (p.n == 0 || (p.adj_pos && p.adj_serial == targets_serial && p.adj_np == np)) continue;
-            std::vector<T> pos((size_t)D * np);
-            for (int64_t u = 0; u < nu; ++u) {
-                const int64_t m = p.ustart ? p.h_ustart[u] : u;
-                const double sg = p.h_flip[m] ? -1.0 : 1.0;
-                for (int d = 0; d < D; ++d) {
-                    pos[(size_t)d * np + u] = (T)(sg * h_bls[(size_t)d * nbls + p.h_idx[m]]);
-                    if (np > nu) pos[(size_t)d * np + nu + u] = -pos[(size_t)d * np + u];
-                }
-            }
-            p.adj_pos.reset(new DevBuf());
-            upload(*p.adj_pos, pos.data(), sizeof(T) * pos.size(), 0);
-            p.adj_serial = targets_serial;
-            p.adj_np = np;
+        auto adj_c = [&](const Pair &p) { return adj_mirrored(p) ? (const double *)zero3 : (const double *)p.btc; };
+        auto adj_B = [&](const Pair &p) { return adj_mirrored(p) ? (const double *)p.Bs : (const double *)p.B; };
+        if (t2) {
+            for (Pair &p : pairs) p.adj_np = p.ustart ? p.nu : p.n;
+        } else {
+            adj_sources(D);
         }
         // the G block on the device
         const size_t g_bytes = sizeof(cplx<T>) * (size_t)nf * nt * per_tf;
@@ -4787,12 +4795,22 @@ class Sim : public SimBase {
     // coordinate of the run's vector (k_src_moments; D = 2 on coplanar handles, where Z does not depend on the third
     // coordinate).  k_src_accumulate contracts with the forward's strengths and adds the beam term; the accumulator is
     // per time step, and k_srcgrad_reduce writes the step's rows on the lane's own stream.
+    // Basis beams (fv_sim_run_basis_source_adjoint): V_b = sum_kl (w1 M_kl(b), w2 M_kl(b) or conj(M_kl(-b))^T) and every
+    // M_kl is such a sum with the strengths c^{kl} of basis beams k and l, so the pairs are the (k <= l) terms as in
+    // adjoint_flux's basis mode: k_adj_strengths_basis writes the term's weighted q -- in the exact form the mirrored half
+    // at -b follows the plain one, and the moments take its coordinates -b like any other source's --, the 1 + D rounds
+    // run over nu or 2 nu sources, and k_src_accumulate contracts with the term's beams.  Every term adds into the lane's
+    // accumulator in stream order; the reduction runs once per time step, after the last term.
     void run_source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
-                            int gtopo_on_device, int accumulate) override {
+                            int gtopo_on_device, int accumulate, bool basis) override {
         FV_HIP(hipSetDevice(device));
         FV_REQUIRE(!type1, "the source adjoint runs the type-3 transform: set the array with fv_sim_set_array, not "
                            "fv_sim_set_array_type1");
-        FV_REQUIRE(nbasis == 0, "the source adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        if (basis)
+            FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_source_adjoint needs a handle with basis beams (fv_sim_set_basis); "
+                                   "without them fv_sim_run_source_adjoint is the pass");
+        else
+            FV_REQUIRE(nbasis == 0, "the source adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs)");
         check_run(t0, t1, f0, f1);
         const int nt = t1 - t0, nf = f1 - f0;
         const int64_t per_tf = (int64_t)tpol * nbls;
@@ -4811,20 +4829,11 @@ class Sim : public SimBase {
         const int D = dim(), nsets = 1 + D;
         double xc[3] = {0.0, 0.0, 0.0}, X[3] = {0.0, 0.0, 0.0};
         source_box(xc, X);
-        for (Pair &p : pairs) {  // the NUFFT sources of every pair (adjoint_flux's, without a mirrored set)
-            const int64_t nu = p.ustart ? p.nu : p.n;
-            if (p.n == 0 || (p.adj_pos && p.adj_serial == targets_serial && p.adj_np == nu)) continue;
-            std::vector<T> pos((size_t)D * nu);
-            for (int64_t u = 0; u < nu; ++u) {
-                const int64_t m = p.ustart ? p.h_ustart[u] : u;
-                const double sg = p.h_flip[m] ? -1.0 : 1.0;
-                for (int d = 0; d < D; ++d) pos[(size_t)d * nu + u] = (T)(sg * h_bls[(size_t)d * nbls + p.h_idx[m]]);
-            }
-            p.adj_pos.reset(new DevBuf());
-            upload(*p.adj_pos, pos.data(), sizeof(T) * pos.size(), 0);
-            p.adj_serial = targets_serial;
-            p.adj_np = nu;
-        }
+        // the NUFFT sources of every pair are adjoint_flux's (adj_sources): in the exact basis form an off-diagonal term's
+        // mirrored set follows the plain one, in a box symmetric about 0
+        auto adj_c = [&](const Pair &p) { return adj_mirrored(p) ? (const double *)zero3 : (const double *)p.btc; };
+        auto adj_B = [&](const Pair &p) { return adj_mirrored(p) ? (const double *)p.Bs : (const double *)p.B; };
+        adj_sources(D);
         const int64_t g_elems = (int64_t)nf * nt * per_tf;
         const cplx<T> *dg = (const cplx<T> *)gvis;
         if (!gvis_on_device) {
@@ -4838,7 +4847,6 @@ class Sim : public SimBase {
         }
         int64_t nu_max = 1;
         for (const Pair &p : pairs) nu_max = std::max<int64_t>(nu_max, p.n ? p.adj_np : 0);
-        auto adj_B = [&](const Pair &p) { return (const double *)p.B; };
         const double cells2 = cells_at_sigma2(X, D, f0, f1, adj_B);
         const double sigma_a = this->sigma != 0.0 ? this->sigma : auto_sigma(cells2, 0.5 * (double)nsrc + (double)nu_max, D);
         const double cells_top = 2.0 * cells2 * (sigma_a == 2.0 ? 1.0 : std::pow(1.25 / 2.0, D));
@@ -4918,23 +4926,33 @@ class Sim : public SimBase {
                         const int ntr = nfg * tpol;
                         for (const Pair &pr : pairs) {
                             if (pr.n == 0) continue;
-                            const int64_t nu = pr.adj_np;
+                            const int64_t nu = pr.adj_np;                        // sources of the transform
+                            const int64_t nr = pr.ustart ? pr.nu : pr.n;         // runs of the list (nu / 2 with a mirrored set)
                             const T *pos = pr.adj_pos->template as<T>();
-                            P.set_geometry(pr.btc, pr.B, xc, X, smax);
+                            P.set_geometry(adj_c(pr), adj_B(pr), xc, X, smax);
                             P.set_sources(nu, pos, pos + nu, D > 2 ? pos + 2 * nu : nullptr);
                             AdjStrengthArgs sa{};
-                            sa.nu = nu;
+                            sa.nu = nr;
                             sa.nfg = nfg;
                             sa.tpol = tpol;
                             sa.g_f_stride = (int64_t)nt * per_tf;
                             for (int r = 0; r < 4; ++r) sa.pol_off[r] = pol_off[r];
                             sa.transpose_flipped = !reference_compat;
                             cplx<T> *q = L.d_adj_q.template as<cplx<T>>();
-                            hipLaunchKernelGGL(k_adj_strengths<T>, dim3((unsigned)cdiv(nu * nfg * ADJ_GROUP, 256)), dim3(256), 0, ls, sa,
-                                               dg + ((int64_t)(fa - f0) * nt + (t - t0)) * per_tf,
-                                               pr.trivial ? nullptr : pr.idx->template as<int>(),
-                                               pr.trivial ? nullptr : pr.flip->template as<signed char>(),
-                                               pr.ustart ? pr.ustart->template as<int>() : nullptr, q, d_err.as<int>() + 4);
+                            if (nbasis) {
+                                const AdjBasisArgs ba{pr.bi, pr.bj, nbasis, (int)freqs.size(), fa, nu > nr ? 1 : 0};
+                                hipLaunchKernelGGL(k_adj_strengths_basis<T>, dim3((unsigned)cdiv(nr * nfg * ADJ_GROUP, 256)), dim3(256), 0,
+                                                   ls, sa, ba, dg + ((int64_t)(fa - f0) * nt + (t - t0)) * per_tf,
+                                                   pr.trivial ? nullptr : pr.idx->template as<int>(),
+                                                   pr.ustart ? pr.ustart->template as<int>() : nullptr,
+                                                   d_coefs.as<cplx<T>>(), d_ant1.as<int>(), d_ant2.as<int>(), q, d_err.as<int>() + 4);
+                            } else {
+                                hipLaunchKernelGGL(k_adj_strengths<T>, dim3((unsigned)cdiv(nr * nfg * ADJ_GROUP, 256)), dim3(256), 0, ls, sa,
+                                                   dg + ((int64_t)(fa - f0) * nt + (t - t0)) * per_tf,
+                                                   pr.trivial ? nullptr : pr.idx->template as<int>(),
+                                                   pr.trivial ? nullptr : pr.flip->template as<signed char>(),
+                                                   pr.ustart ? pr.ustart->template as<int>() : nullptr, q, d_err.as<int>() + 4);
+                            }
                             const int64_t q_set = nu * ntr, z_set = cap * ntr;
                             hipLaunchKernelGGL(k_src_moments<T>, dim3((unsigned)cdiv(q_set, 256)), dim3(256), 0, ls, nu, (int64_t)ntr, D,
                                                pos, q, q_set);
@@ -5015,17 +5033,21 @@ class Sim : public SimBase {
     // spread -> FFT -> tangent gather (k_interp<.., TANGENT>) ADDING into the zeroed output block.  A time step's slots are
     // written by its own lane's stream only, in order: no sum over lanes, bitwise reproducible for a lane count.  A host
     // destination receives the block in one copy at the end.
-    // Basis beams (fv_sim_run_basis_position_tangent; dbls only): the moments rounds per (k <= l) term as in
-    // run_position_adjoint, the gather adding i nu w (w1 V, w2 V) with the basis weights (k_interp<.., BPOS = 2>).
+    // Basis beams (fv_sim_run_basis_position_tangent: dbls; fv_sim_run_basis_source_tangent: dtopo; one of them per call):
+    // the rounds per (k <= l) term as in run_position_adjoint, k_strengths_tangent with the term's beams, a weighted
+    // round's gather adding i nu w (w1 V, w2 V) with the basis weights (k_interp<.., BPOS = 2>) and the beam term's
+    // round adding (w1 V, w2 V) as they are -- which is the forward's own basis gather on the set dc.
     void run_tangent(int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
                      int dtopo_on_device, void *out, int out_on_device, bool basis) override {
         FV_HIP(hipSetDevice(device));
         FV_REQUIRE(!type1, "the tangent runs the type-3 transform: set the array with fv_sim_set_array, not "
                            "fv_sim_set_array_type1 (a lattice form of the pass does not exist)");
         if (basis) {
-            FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_position_tangent needs a handle with basis beams (fv_sim_set_basis); "
+            FV_REQUIRE(nbasis > 0, "the tangents through basis beams (fv_sim_run_basis_position_tangent, "
+                                   "fv_sim_run_basis_source_tangent) need a handle with basis beams (fv_sim_set_basis); "
                                    "without them fv_sim_run_tangent is the pass");
-            FV_REQUIRE(dbls && !dtopo, "the tangent through basis beams takes baseline directions only");
+            FV_REQUIRE(!(dbls && dtopo), "the tangents through basis beams take baseline directions or source directions, "
+                                         "one per call (no entry point passes both)");
         } else {
             FV_REQUIRE(nbasis == 0, "the tangent does not cover basis beams (fv_sim_set_basis / beam_coefs)");
         }

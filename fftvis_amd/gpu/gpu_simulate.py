@@ -311,6 +311,22 @@ class SimHandle:
         op, o_dev = _buffer_addr(out)
         _lib.check(self._L.fv_sim_run_basis_position_tangent(self._h, t0, t1, f0, f1, bp, b_dev, op, o_dev))
 
+    def run_basis_source_adjoint(self, t0, t1, f0, f1, g, gtopo, accumulate: bool):
+        """Basis beams (``set_basis``): ``gtopo +=`` the tangential gradient with respect to the sources' ENU unit vectors
+        for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_basis_source_adjoint``).  ``g`` and ``gtopo`` as for
+        ``run_source_adjoint``."""
+        gp, g_dev = _buffer_addr(g)
+        tp, t_dev = _buffer_addr(gtopo)
+        _lib.check(self._L.fv_sim_run_basis_source_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, tp, t_dev,
+                                                           int(bool(accumulate))))
+
+    def run_basis_source_tangent(self, t0, t1, f0, f1, dtopo, out):
+        """Basis beams (``set_basis``): ``out =`` the tangent of the visibilities along ``dtopo`` for times [t0,t1) x freqs
+        [f0,f1) (``fv_sim_run_basis_source_tangent``).  ``dtopo`` and ``out`` as for ``run_tangent``."""
+        tp, t_dev = _buffer_addr(dtopo)
+        op, o_dev = _buffer_addr(out)
+        _lib.check(self._L.fv_sim_run_basis_source_tangent(self._h, t0, t1, f0, f1, tp, t_dev, op, o_dev))
+
     def run_basis_tangent(self, t0, t1, f0, f1, dcoefs, out):
         """Basis beams (``set_basis``): ``out[q] =`` the tangent of the visibilities along direction ``dcoefs[q]`` of the
         coefficients for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_basis_tangent``).  ``dcoefs``: C-contiguous
@@ -446,6 +462,7 @@ class GPUSimulationEngine(SimulationEngine):
         adjoint_wrt: str = "fluxes",
         tangent_of: tuple = None,
         basis_tangent_of: tuple = None,
+        basis_source_of: tuple = None,
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -536,7 +553,20 @@ class GPUSimulationEngine(SimulationEngine):
           -- instead of simulating, the engine fills ``dv``, (ndir,) + the result's shape, this precision's complex dtype,
           with the tangents of its visibilities along the ``ndir`` directions ``dcoefs`` (ndir, nant, nbasis, nfreqs) of the
           coefficients (``SimHandle.run_basis_tangent``: one forward run, whatever ``ndir``) and returns it.
+        * ``basis_source_of`` (extra; what ``simulate_vis_basis_source_adjoint`` / ``_jvp`` pass; needs ``beam_coefs``): the
+          source-direction passes through basis beams.  ``("adjoint", g, gtopo)``: the engine fills ``gtopo``,
+          (ntimes, nsrc, 3) float64, with the tangential gradient with respect to the sources' ENU unit vectors, row t
+          from time step t (``SimHandle.run_basis_source_adjoint``), and returns it.  ``("tangent", dtopo, dv)``: it fills
+          ``dv`` (the result's shape) with the tangent along ``dtopo`` (ntimes, nsrc, 3)
+          (``SimHandle.run_basis_source_tangent``) and returns it.  Time blocks take consecutive rows.
         """
+        if basis_source_of is not None:
+            if adjoint_of is not None or tangent_of is not None or basis_tangent_of is not None:
+                raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of and basis_source_of")
+            if beam_coefs is None:
+                raise ValueError("basis_source_of needs basis beams (beam_coefs)")
+            if len(basis_source_of) != 3 or basis_source_of[0] not in ("adjoint", "tangent"):
+                raise ValueError("basis_source_of: ('adjoint', g, gtopo) or ('tangent', dtopo, dv)")
         if basis_tangent_of is not None:
             if adjoint_of is not None or tangent_of is not None:
                 raise ValueError("pass one of adjoint_of, tangent_of and basis_tangent_of")
@@ -706,6 +736,10 @@ class GPUSimulationEngine(SimulationEngine):
             if tangent_of is not None:
                 result = _run_tangent(h, tangent_of[0], tangent_of[1], tangent_of[2], t0, t1, f0, f1, nblk_t, coord_mgr,
                                       basis=use_basis)
+                ok = True
+                return result
+            if basis_source_of is not None:
+                result = _run_basis_source(h, *basis_source_of, t0, t1, f0, f1, nblk_t, coord_mgr)
                 ok = True
                 return result
             if basis_tangent_of is not None:
@@ -900,6 +934,33 @@ def _run_tangent(h, dbls, dtopo, dv, t0, t1, f0, f1, nblk_t, coord_mgr, basis=Fa
     if t1 <= t0:
         dv[...] = 0
     return dv
+
+
+def _run_basis_source(h, mode, a, b, t0, t1, f0, f1, nblk_t, coord_mgr):
+    """The time loop of the source passes through basis beams, over the forward's blocks (and, with a coordinate manager,
+    its streamed vectors).  ``mode == "adjoint"``: ``a`` is g and every block's ``run_basis_source_adjoint`` fills that
+    block's rows of ``b``, the (t1 - t0, nsrc, 3) direction gradient.  ``mode == "tangent"``: ``a`` is dtopo, and every
+    block's ``run_basis_source_tangent`` takes its rows and fills its slice of ``b`` (a block that is not the whole result
+    goes through a contiguous temporary).  Every call ends synchronised."""
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+        if mode == "adjoint":
+            blk = a[:, tb - t0:te - t0]
+            if isinstance(a, np.ndarray):
+                blk = np.ascontiguousarray(blk)
+            else:
+                import torch
+
+                blk = blk.contiguous()
+                torch.cuda.synchronize(blk.device)  # a copy .contiguous() queued on torch's stream is done before the library reads
+            h.run_basis_source_adjoint(ta, te_, f0, f1, blk, b[tb - t0:te - t0], False)
+        else:
+            blk, dst = _result_block(b, 1, tb - t0, te - t0, tb == t0 and te == t1)
+            h.run_basis_source_tangent(ta, te_, f0, f1, a[tb - t0:te - t0], blk)
+            if dst is not None:
+                dst[...] = blk
+    if t1 <= t0 and mode == "tangent":
+        b[...] = 0
+    return b
 
 
 def _run_basis_tangent(h, dcoefs, dv, t0, t1, f0, f1, nblk_t, coord_mgr):

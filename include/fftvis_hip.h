@@ -377,7 +377,7 @@ int fv_sim_run_basis_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const vo
  * buffer per stream (it does not grow with the number of basis beams), cut into channel blocks under
  * FFTVIS_HIP_ADJ_ACC_BYTES.  One owner thread per slot and launch, buffers summed in lane order: no atomics, bitwise
  * reproducible for a given FFTVIS_HIP_LANES.  Memory is given back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule of
- * fv_sim_run_adjoint.  Not covered: source-position derivatives through basis beams, lattice handles.  A handle without
+ * fv_sim_run_adjoint.  Not covered: lattice handles.  A handle without
  * fv_sim_set_basis (fv_sim_run_position_adjoint is the pass there), a lattice handle, a null handle, a null gvis or gbls,
  * a flag other than 0 or 1 and NaN in gvis (detected before anything runs; the handle stays usable) fail with
  * FV_ERR_ARG.                                                                                                            */
@@ -394,6 +394,39 @@ int fv_sim_run_basis_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1,
  * runs; the handle stays usable) fail with FV_ERR_ARG.                                                                    */
 int fv_sim_run_basis_position_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device,
                                       void *out, int out_on_device);
+/* Gradient of a basis-beam handle's visibilities (fv_sim_set_basis) with respect to the sources' directions, for times
+ * [t0, t1) x freqs [f0, f1): fv_sim_run_source_adjoint's quantity for V_b = sum_{k<=l} (w1 M_kl(b) at slot r + w2 M_kl(b)
+ * at the feed-transposed slot), w1 = conj(C[a1,k]) C[a2,l], w2 = conj(C[a1,l]) C[a2,k]; with fv_sim_set_reference_compat
+ * off the (l, k) part of an off-diagonal term is conj(M_kl(-b))^T.  Every M_kl is a sum over sources of the strengths
+ * c^{kl}(n_j) of basis beams k and l times exp(i nu b' . x_j), so per term the gradient is that of the source pass:
+ *     gtopo[t - t0, j, :] += P_n sum_terms ( 2 pi R^T sum_f nu_f ( -Im sum_r c^{kl}_jr Z(d)_jr )_d
+ *                                            +  sum_f grad_n Re sum_r c^{kl}_jr(n) Z_jr ),
+ * Z the transposed transform of the term's weighted strengths as fv_sim_run_basis_adjoint's flux pass forms them (in the
+ * exact form with a mirrored half at -b, whose moments take the coordinates -b), Z(d) that of the strengths times the d-th
+ * coordinate.  Tangential, exactly 0 below the horizon, the cut not differentiated; the beam term is 0 by definition
+ * between two order-0 tables, decided per term.  gvis, gtopo, the flags and accumulate as in fv_sim_run_source_adjoint.
+ * The pass is that one's loop over the (k <= l) terms: 1 + D transforms and five beam evaluations per (term, time,
+ * frequency group), every term adding into the lane's (nsrc, channels of a block, 3) fp64 accumulator in stream order,
+ * one reduction per time step.  No atomics: bitwise reproducible whatever FFTVIS_HIP_LANES.  Channel blocks
+ * (FFTVIS_HIP_ADJ_ACC_BYTES), source chunks, lanes and the FFTVIS_HIP_ADJ_KEEP_BYTES rule as there.  Not covered: lattice
+ * handles.  A handle without fv_sim_set_basis (fv_sim_run_source_adjoint is the pass there), a lattice handle, a null
+ * handle, a null gvis or gtopo, a flag other than 0 or 1 and NaN in gvis (detected before anything runs; the handle stays
+ * usable) fail with FV_ERR_ARG.                                                                                          */
+int fv_sim_run_basis_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device,
+                                    double *gtopo, int gtopo_on_device, int accumulate);
+/* Forward-mode tangent of a basis-beam handle's visibilities along a change of the sources' directions, the transpose of
+ * fv_sim_run_basis_source_adjoint:  out = sum_{t,j} dV/dn_j(t) . P_n dtopo[t - t0, j],  Re <out, G> = sum dtopo . gtopo.
+ * dtopo: (t1 - t0, nsrc, 3) float64, ENU; a row of a source below the horizon is not read.  out: fv_sim_run's layout for
+ * the block, complex of the handle's precision, always overwritten.  The pass is the basis forward run per channel block:
+ * per (k <= l) term the 1 + D strength sets of fv_sim_run_tangent with the term's beams, and 1 + D rounds of spread, FFT
+ * and a gather that adds i nu_f b'_d (w1 V, w2 V) with the basis weights formed in fp64 -- (w1 V, w2 V) as they are in
+ * the beam term's round -- into the zeroed block, for both forms of the (l, k) term; a time step's slots are written by
+ * its own lane only: bitwise reproducible for a given FFTVIS_HIP_LANES.  Channel blocks and memory as in
+ * fv_sim_run_tangent.  A handle without fv_sim_set_basis (fv_sim_run_tangent is the pass there), a lattice handle, a null
+ * handle, a null out or dtopo, a flag other than 0 or 1 and a value of dtopo that is not finite (detected before anything
+ * runs; the handle stays usable) fail with FV_ERR_ARG.                                                                    */
+int fv_sim_run_basis_source_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dtopo, int dtopo_on_device,
+                                    void *out, int out_on_device);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2

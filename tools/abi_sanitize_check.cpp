@@ -66,6 +66,8 @@ int main() {
     EXPECT(fv_sim_run_basis_tangent(nullptr, 0, 1, 0, 1, v, 0, 1, v, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_basis_position_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_basis_position_tangent(nullptr, 0, 1, 0, 1, v, 0, v, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_basis_source_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_basis_source_tangent(nullptr, 0, 1, 0, 1, v, 0, v, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_sync(nullptr) == FV_ERR_ARG);
     EXPECT(fv_sim_stats(nullptr, v, 12) == FV_ERR_ARG);
     EXPECT(fv_sim_reset_stats(nullptr) == FV_ERR_ARG);
@@ -156,6 +158,19 @@ int main() {
         EXPECT(fv_sim_run_basis_position_tangent(fake, 0, 1, 0, 1, nullptr, 0, v, 0) == FV_ERR_ARG);
         EXPECT(fv_sim_run_basis_position_tangent(fake, 0, 1, 0, 1, v, 2, v, 0) == FV_ERR_ARG);
         EXPECT(fv_sim_run_basis_position_tangent(fake, 0, 1, 0, 1, v, 0, v, 3) == FV_ERR_ARG);
+    }
+    // and the source passes through basis beams
+    {
+        fv_sim *fake = reinterpret_cast<fv_sim *>(0x1);
+        EXPECT(fv_sim_run_basis_source_adjoint(fake, 0, 1, 0, 1, nullptr, 0, v, 0, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_basis_source_adjoint(fake, 0, 1, 0, 1, v, 0, nullptr, 0, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_basis_source_adjoint(fake, 0, 1, 0, 1, v, 2, v, 0, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_basis_source_adjoint(fake, 0, 1, 0, 1, v, 0, v, -1, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_basis_source_adjoint(fake, 0, 1, 0, 1, v, 0, v, 0, 2) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_basis_source_tangent(fake, 0, 1, 0, 1, v, 0, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_basis_source_tangent(fake, 0, 1, 0, 1, nullptr, 0, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_basis_source_tangent(fake, 0, 1, 0, 1, v, 2, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_run_basis_source_tangent(fake, 0, 1, 0, 1, v, 0, v, 3) == FV_ERR_ARG);
     }
     // and the basis tangent: a null output, null directions, ndir < 1, on_device flags other than 0 or 1
     {

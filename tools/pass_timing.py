@@ -12,6 +12,7 @@
                     tangent_both                                                    C3, 8 channels  (--array)
     basis_tangent   forward tangent_1 tangent_n beam_coefs                          C5, 8 channels  (--ndir)
     basis_position  forward adjoint tangent                                         C5, 8 channels
+    basis_source    forward fluxes tangent_ants source_adjoint source_tangent       C5, 8 channels  (--precision)
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -129,6 +130,20 @@ def basis_position(a, fv, cfg, rng):
         "tangent": lambda: fv.simulate_vis_basis_jvp(**cfg, d_baselines=db)}
 
 
+def basis_source(a, fv, cfg, rng):
+    if a.precision == 2:  # C5 is fp32 at eps 1e-4: its fp64 variant at the fp64 default of the benchmark configurations
+        cfg.update(precision=2, eps=6e-8)
+    g = _g(a, cfg, rng, cast=True)
+    da = rng.normal(size=(len(cfg["ants"]), 3))
+    dt = rng.normal(size=(a.ntimes, np.size(cfg["ra"]), 3))
+    return {"config": a.config, "nbasis": len(cfg["beam"]), "precision": cfg["precision"]}, {
+        "forward": lambda: fv.simulate_vis(**cfg),
+        "fluxes": lambda: fv.simulate_vis_basis_adjoint(g, **cfg, wrt="fluxes"),
+        "tangent_ants": lambda: fv.simulate_vis_basis_jvp(**cfg, d_ants=da),
+        "source_adjoint": lambda: fv.simulate_vis_basis_source_adjoint(g, **cfg, wrt="topo"),
+        "source_tangent": lambda: fv.simulate_vis_basis_source_jvp(**cfg, d_topo=dt)}
+
+
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
 #          ratios {key: (pass, pass it is divided by)})
 FAMILIES = {
@@ -141,8 +156,13 @@ FAMILIES = {
     "basis_tangent": (basis_tangent, "C5", 8, ("ndir",), "runs", {}),
     "basis_position": (basis_position, "C5", 8, (), "runs", {"adjoint_over_forward": ("adjoint", "forward"),
                                                             "tangent_over_forward": ("tangent", "forward")}),
+    "basis_source": (basis_source, "C5", 8, ("precision",), "runs", {
+        "source_adjoint_over_fluxes": ("source_adjoint", "fluxes"), "source_adjoint_over_forward": ("source_adjoint", "forward"),
+        "source_tangent_over_forward": ("source_tangent", "forward"),
+        "source_tangent_over_tangent_ants": ("source_tangent", "tangent_ants")}),
 }
-OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8}  # and their defaults
+OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
+             "precision": 1}  # and their defaults
 
 
 def main():
@@ -162,6 +182,7 @@ def main():
     ap.add_argument("--adjoint-path", choices=["type3", "type2", "auto"], default=None)
     ap.add_argument("--small", action="store_true", default=None, help="HERA-37, K = 3 Airy dishes, fp64")
     ap.add_argument("--ndir", type=int, default=None)
+    ap.add_argument("--precision", type=int, choices=[1, 2], default=None, help="2: the configuration in fp64 at eps 6e-8")
     a = ap.parse_args()
     build, config, nfreq, own, spread, ratios = FAMILIES[a.family]
     for flag, default in OWN_FLAGS.items():
