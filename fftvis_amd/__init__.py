@@ -9,7 +9,8 @@ with respect to the fluxes, the coefficients and the antenna positions (``simula
 gradient with respect to the antenna positions (``simulate_vis_position_adjoint``, ``torch_simulate_vis_array``) and to
 the source positions (``simulate_vis_source_adjoint``, ``torch_simulate_vis_sky``), and the forward-mode tangent along
 all three (``simulate_vis_jvp``), and the source positions through basis beams
-(``simulate_vis_basis_source_adjoint``, ``simulate_vis_basis_source_jvp``, ``torch_simulate_vis_basis_sky``).
+(``simulate_vis_basis_source_adjoint``, ``simulate_vis_basis_source_jvp``, ``torch_simulate_vis_basis_sky``), and the fluxes'
+and the source positions' gradients from one pass (``simulate_vis_sky_adjoint``, ``simulate_vis_basis_sky_adjoint``).
 """
 
 __version__ = "0.1.0"
@@ -25,10 +26,12 @@ from .adjoint import (  # noqa: F401
     simulate_vis_adjoint,
     simulate_vis_basis_adjoint,
     simulate_vis_basis_jvp,
+    simulate_vis_basis_sky_adjoint,
     simulate_vis_basis_source_adjoint,
     simulate_vis_basis_source_jvp,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,
+    simulate_vis_sky_adjoint,
     simulate_vis_source_adjoint,
     torch_simulate_vis,
     torch_simulate_vis_array,

@@ -75,6 +75,9 @@ SYMBOLS = {
     "fv_sim_run_basis_position_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int]),
     "fv_sim_run_basis_position_tangent": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int]),
     "fv_sim_run_basis_source_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int]),
+    "fv_sim_run_sky_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int]),
+    "fv_sim_run_basis_sky_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                             c_int]),
     "fv_sim_run_basis_source_tangent": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int]),
     "fv_comm_unique_id": (c_int, [c_void_p]),
     "fv_comm_init": (c_int, [POINTER(c_void_p), c_int, c_int, c_int, c_void_p]),

@@ -1232,9 +1232,11 @@ def _sky_autograd_function():
             fluxes, radec = ctx.saved_tensors
             pos = _radec_columns(radec)
             gf = gp = None
-            if ctx.needs_input_grad[0]:
+            if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:  # one pass for both
+                gf, gp = simulate_vis_sky_adjoint(grad_output, fluxes=fluxes, wrt=("fluxes", "radec"), **pos, **ctx.kwargs)
+            elif ctx.needs_input_grad[0]:
                 gf = simulate_vis_adjoint(grad_output, full_stokes=ctx.full_stokes, **pos, **ctx.kwargs)
-            if ctx.needs_input_grad[1]:
+            elif ctx.needs_input_grad[1]:
                 gp = simulate_vis_source_adjoint(grad_output, fluxes=fluxes, wrt="radec", **pos, **ctx.kwargs)
             return _as_grad(gf, grad_output.device, ctx.flux_dtype), _as_grad(gp, ctx.pos_device, ctx.pos_dtype), None
 
@@ -1256,7 +1258,8 @@ def torch_simulate_vis_sky(fluxes, radec, **kwargs):
     keyword of ``simulate_vis`` -- but for ``ra`` and ``dec``, which the tensor replaces (TypeError).  Returns the
     visibilities as a complex tensor on ``fluxes``' device.  The backward pass runs only what autograd asks for
     (``ctx.needs_input_grad``): ``simulate_vis_adjoint`` for the fluxes, ``simulate_vis_source_adjoint(wrt="radec")`` for the
-    positions, which needs ``coord_method="SiderealRotation"`` or device astrometry.  Forward mode
+    positions, which needs ``coord_method="SiderealRotation"`` or device astrometry, and when both are asked for one
+    ``simulate_vis_sky_adjoint`` call, whose pass shares the transforms.  Forward mode
     (``torch.autograd.forward_ad``) runs ``simulate_vis_jvp`` on the tangents present, under the same condition."""
     if "ra" in kwargs or "dec" in kwargs:
         raise TypeError("torch_simulate_vis_sky takes the source positions as the tensor radec, not ra= / dec=")
@@ -1342,8 +1345,8 @@ def simulate_vis_basis_source_adjoint(
     (handed over by pointer; the results are then tensors on that device).  Every other keyword means what it means for
     ``simulate_vis``, ``reference_compat`` included; ``polarized`` must be True and ``beam_idx`` None, as for the forward.
     The cost is 1 + D transforms per term where ``simulate_vis_basis_adjoint(wrt="fluxes")`` runs one (D = 2 on a flat
-    array, 3 otherwise) plus five beam evaluations per (source, channel, term).  Not covered: a lattice form, several
-    directions per call, multi-GPU, a joint call with the flux gradient that shares its transforms."""
+    array, 3 otherwise) plus five beam evaluations per (source, channel, term).  ``simulate_vis_basis_sky_adjoint`` returns
+    the flux gradient from the same transforms.  Not covered: a lattice form, several directions per call, multi-GPU."""
     args = locals()
     single, names = _parse_wrt(wrt, ("topo", "radec"), "'topo', 'radec' or both")
     run = _basis_run("simulate_vis_basis_source_adjoint", args)
@@ -1439,6 +1442,183 @@ def simulate_vis_basis_source_jvp(
     return dv
 
 
+_SKY_WRT = ("fluxes", "topo", "radec")
+
+
+def _sky_adjoint(run: _Run, vis, fluxes, full_stokes, single, names, basis: bool):
+    """The joint pass of ``simulate_vis_sky_adjoint`` / ``simulate_vis_basis_sky_adjoint``: one device call per time block
+    for the flux gradient and the direction gradient together."""
+    run = _own_radec_chain(run, "wrt='radec'", "radec" in names, "ask for wrt='topo' and apply its Jacobian",
+                           "ask for wrt='topo'")
+    f_shape = (run.nsrc, run.nfreqs)
+    g, (gflux, gtopo), on_device = _gradient_buffers(run, vis, [
+        (f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real"), ((run.ntimes, run.nsrc, 3), "float64")])
+    gc, gtopo = _engine_simulate(run, fluxes, force_use_type3=None if basis else True, sky_of=(g, gflux, gtopo))
+    res = {"fluxes": stokes_adjoint(gc, full_stokes), "topo": gtopo}
+    if "radec" in names:
+        res["radec"] = topo_to_radec_gradient(gtopo, _radec_jacobian_of(run))
+    return _select({k: v for k, v in res.items() if k in names}, single, names, vis, on_device)
+
+
+def _sky_full_stokes(run: _Run, fluxes, full_stokes):
+    """The forward's fluxes on the host and what their shape says about ``full_stokes`` (a mismatch: ValueError)."""
+    fluxes = _host_fluxes(run, fluxes)
+    if full_stokes is None:
+        full_stokes = fluxes.ndim == 3
+    if bool(full_stokes) != (fluxes.ndim == 3):
+        raise ValueError(f"full_stokes={full_stokes} does not match fluxes of shape {fluxes.shape}")
+    return fluxes, bool(full_stokes)
+
+
+def simulate_vis_sky_adjoint(
+    vis,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    wrt=("fluxes", "radec"),
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    beam_coefs: np.ndarray = None,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """Gradients of ``simulate_vis(ants, fluxes, ra, dec, ...)`` with respect to the fluxes AND the source positions from
+    one pass, for a visibility-shaped ``vis`` (G = dL/dV, dL = Re sum conj(G) dV) -- what a fit with each source's flux and
+    position unknown together needs per step.
+
+    * ``"fluxes"``: ``A^T vis`` as ``simulate_vis_adjoint`` defines it; the fluxes' shape, (nsrc, nfreqs) or
+      (nsrc, nfreqs, 4), real, of the run's precision;
+    * ``"topo"``: (ntimes, nsrc, 3) float64, ENU, tangential, as ``simulate_vis_source_adjoint`` defines it;
+    * ``"radec"``: (nsrc, 2) float64, columns (ra, dec), per radian, under that function's rules: for
+      ``coord_method="SiderealRotation"`` and device astrometry; with a ``coord_mgr`` (or a matvis manager the engine would
+      build) ValueError: ask for ``"topo"``.
+
+    ``wrt`` is a name or a tuple of distinct names; the result is that gradient, or a tuple in ``wrt``'s order.  With
+    ``"fluxes"`` and a position name one joint device call runs per time block (``fv_sim_run_sky_adjoint``): the source
+    pass's first transform per (time, frequency group, beam pair) is the flux adjoint's, so its 1 + D transforms serve
+    both, where the two separate calls run 2 + D and set up twice.  The flux part is the flux adjoint's own arithmetic on
+    those values (it agrees with ``simulate_vis_adjoint`` to rounding in the order of the per-lane sums) and the position
+    part is the source pass's, bit for bit.  A ``wrt`` without ``"fluxes"``, or with it alone, runs the single-purpose pass
+    and returns its bits.  ``full_stokes`` defaults to what ``fluxes``' shape says.  ``vis`` is a numpy array or a torch
+    tensor on the run's device (handed over by pointer; the results are then tensors on that device); host tensors in,
+    host tensors out.  Every other keyword means what it means for ``simulate_vis``; ``force_use_type3`` is accepted and
+    always on in the joint pass, which runs the type-3 transform (there is no ``adjoint_path``).  Not covered:
+    ``beam_coefs`` (NotImplementedError: ``simulate_vis_basis_sky_adjoint``), the antenna positions, multi-GPU."""
+    args = locals()
+    single, names = _parse_wrt(wrt, _SKY_WRT, "some of 'fluxes', 'topo' and 'radec'")
+    if beam_coefs is not None:
+        raise NotImplementedError("simulate_vis_sky_adjoint does not support basis beams (beam_coefs): "
+                                  "simulate_vis_basis_sky_adjoint does")
+    run = _describe_run(args)
+    fluxes, full_stokes = _sky_full_stokes(run, fluxes, full_stokes)
+    own = {k: v for k, v in args.items() if k not in ("vis", "wrt", "full_stokes", "fluxes", "args")}
+    if "fluxes" not in names:
+        return simulate_vis_source_adjoint(vis, fluxes=fluxes, wrt=wrt, **own)
+    if names == ("fluxes",):
+        gf = simulate_vis_adjoint(vis, full_stokes=full_stokes, **own)
+        return gf if single else (gf,)
+    return _sky_adjoint(run, vis, fluxes, full_stokes, single, names, basis=False)
+
+
+def simulate_vis_basis_sky_adjoint(
+    vis,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    beam_coefs,
+    telescope_loc,
+    *,
+    wrt=("fluxes", "radec"),
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = True,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """``simulate_vis_sky_adjoint`` through basis beams: the gradients of ``simulate_vis(..., beam=<K basis beams>,
+    beam_coefs=C)`` with respect to the fluxes and the source positions from one pass
+    (``fv_sim_run_basis_sky_adjoint``): the 1 + D transforms per (k <= l) term of ``simulate_vis_basis_source_adjoint``
+    also give ``simulate_vis_basis_adjoint(wrt="fluxes")``'s gradient, one transform per term fewer than the two calls.
+
+    ``wrt``, ``full_stokes``, ``vis`` and the results as for ``simulate_vis_sky_adjoint``, the gradients with the meaning
+    those two functions give them; a ``wrt`` without ``"fluxes"``, or with it alone, runs the single-purpose pass and
+    returns its bits.  ``fluxes`` and ``beam_coefs`` are the forward's; ``polarized`` must be True and ``beam_idx`` None,
+    as for the forward.  The coefficients' gradient stays ``simulate_vis_basis_adjoint(wrt="beam_coefs")``'s: its
+    transforms run the other way.  Not covered: a lattice form, the antenna positions, multi-GPU."""
+    args = locals()
+    single, names = _parse_wrt(wrt, _SKY_WRT, "some of 'fluxes', 'topo' and 'radec'")
+    if beam_coefs is None:
+        raise ValueError("simulate_vis_basis_sky_adjoint needs beam_coefs (without basis beams simulate_vis_sky_adjoint is "
+                         "the pass)")
+    if not polarized:  # the forward's message
+        raise ValueError(
+            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
+        )
+    run = _describe_run(args)
+    fluxes, full_stokes = _sky_full_stokes(run, fluxes, full_stokes)
+    own = {k: v for k, v in args.items() if k not in ("vis", "wrt", "full_stokes", "fluxes", "args")}
+    if "fluxes" not in names:
+        return simulate_vis_basis_source_adjoint(vis, fluxes=fluxes, wrt=wrt, **own)
+    if names == ("fluxes",):
+        return simulate_vis_basis_adjoint(vis, fluxes=fluxes, wrt=wrt, full_stokes=full_stokes, **own)
+    return _sky_adjoint(run, vis, fluxes, full_stokes, single, names, basis=True)
+
+
 def _basis_sky_autograd_function():
     import torch
 
@@ -1458,10 +1638,17 @@ def _basis_sky_autograd_function():
             pos = _radec_columns(radec)
             wrt = tuple(n for n, need in zip(("fluxes", "beam_coefs"), ctx.needs_input_grad[:2]) if need)
             got, gp = {}, None
+            if ctx.needs_input_grad[0] and ctx.needs_input_grad[2]:  # one pass for the fluxes and the positions
+                got["fluxes"], gp = simulate_vis_basis_sky_adjoint(grad_output, fluxes=fluxes, beam_coefs=beam_coefs,
+                                                                   wrt=("fluxes", "radec"), **pos, **ctx.kwargs)
+                if ctx.needs_input_grad[1]:
+                    got["beam_coefs"], = simulate_vis_basis_adjoint(grad_output, fluxes=fluxes, beam_coefs=beam_coefs,
+                                                                    wrt=("beam_coefs",), **pos, **ctx.kwargs)
+                wrt = ()
             if wrt:
                 got = dict(zip(wrt, simulate_vis_basis_adjoint(grad_output, fluxes=fluxes, beam_coefs=beam_coefs, wrt=wrt,
                                                                **pos, **ctx.kwargs)))
-            if ctx.needs_input_grad[2]:
+            if ctx.needs_input_grad[2] and gp is None:
                 gp = simulate_vis_basis_source_adjoint(grad_output, fluxes=fluxes, beam_coefs=beam_coefs, wrt="radec",
                                                        **pos, **ctx.kwargs)
             return (_as_grad(got.get("fluxes"), grad_output.device, ctx.flux_dtype),
@@ -1496,7 +1683,8 @@ def torch_simulate_vis_basis_sky(fluxes, beam_coefs, radec, **kwargs):
     the visibilities as a complex tensor on ``fluxes``' device.  The backward pass runs only what autograd asks for
     (``ctx.needs_input_grad``): one ``simulate_vis_basis_adjoint`` call for the fluxes and / or the coefficients,
     ``simulate_vis_basis_source_adjoint(wrt="radec")`` for the positions, which needs ``coord_method="SiderealRotation"`` or
-    device astrometry.  Forward mode (``torch.autograd.forward_ad``) runs ``simulate_vis_basis_jvp`` and
+    device astrometry; when the fluxes and the positions are both asked for, one ``simulate_vis_basis_sky_adjoint`` call
+    serves the two (and ``simulate_vis_basis_adjoint(wrt=("beam_coefs",))`` the coefficients).  Forward mode (``torch.autograd.forward_ad``) runs ``simulate_vis_basis_jvp`` and
     ``simulate_vis_basis_source_jvp`` on the tangents present, under the same condition."""
     if "ra" in kwargs or "dec" in kwargs:
         raise TypeError("torch_simulate_vis_basis_sky takes the source positions as the tensor radec, not ra= / dec=")

@@ -697,6 +697,32 @@ int fv_sim_run_basis_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, c
         h->impl->run_source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gtopo, gtopo_on_device, accumulate, true);
     });
 }
+int fv_sim_run_sky_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                           int gflux_on_device, double *gtopo, int gtopo_on_device, int accumulate) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(gvis && gflux && gtopo, "null adjoint input or output");
+        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gflux_on_device == 0 || gflux_on_device == 1) &&
+                       (gtopo_on_device == 0 || gtopo_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_sky_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, gtopo, gtopo_on_device, accumulate,
+                                 false);
+    });
+}
+int fv_sim_run_basis_sky_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                                 int gflux_on_device, double *gtopo, int gtopo_on_device, int accumulate) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(gvis && gflux && gtopo, "null adjoint input or output");
+        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gflux_on_device == 0 || gflux_on_device == 1) &&
+                       (gtopo_on_device == 0 || gtopo_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_sky_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, gtopo, gtopo_on_device, accumulate,
+                                 true);
+    });
+}
 int fv_sim_run_basis_source_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dtopo, int dtopo_on_device,
                                     void *out, int out_on_device) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)

@@ -2061,6 +2061,9 @@ struct SimBase {
                                       int gbls_on_device, int accumulate, bool basis) = 0;
     virtual void run_source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
                                     int gtopo_on_device, int accumulate, bool basis) = 0;
+    // fv_sim_run_sky_adjoint / fv_sim_run_basis_sky_adjoint: run_source_adjoint's pass with the flux gradient from its Z
+    virtual void run_sky_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                                 int gflux_on_device, double *gtopo, int gtopo_on_device, int accumulate, bool basis) = 0;
     virtual void run_tangent(int t0, int t1, int f0, int f1, const double *dbls, int dbls_on_device, const double *dtopo,
                              int dtopo_on_device, void *out, int out_on_device, bool basis) = 0;
     virtual void run_basis_tangent(int t0, int t1, int f0, int f1, const void *dcoefs, int dcoefs_on_device, int ndir, void *out,
@@ -4801,16 +4804,42 @@ class Sim : public SimBase {
     // at -b follows the plain one, and the moments take its coordinates -b like any other source's --, the 1 + D rounds
     // run over nu or 2 nu sources, and k_src_accumulate contracts with the term's beams.  Every term adds into the lane's
     // accumulator in stream order; the reduction runs once per time step, after the last term.
+    //
+    // Joint pass (fv_sim_run_sky_adjoint, fv_sim_run_basis_sky_adjoint: gflux given): set 0 of the 1 + D rounds is the Z
+    // adjoint_flux computes -- the same strengths, plan parameters and targets --, so k_adj_accumulate contracts it with the
+    // pair's or term's beams at the lane's az / za into a flux accumulator of the lane's own, which follows the lane's 3
+    // doubles per (source, channel) in d_adj_acc and lives for a channel block; k_adj_reduce then sums the lanes in lane
+    // order into gflux on the main stream, as in adjoint_flux.  Without gflux nothing here differs from the pass above.
     void run_source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, double *gtopo,
                             int gtopo_on_device, int accumulate, bool basis) override {
+        source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, nullptr, 0, gtopo, gtopo_on_device, accumulate, basis);
+    }
+    void run_sky_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux, int gflux_on_device,
+                         double *gtopo, int gtopo_on_device, int accumulate, bool basis) override {
+        FV_REQUIRE(gflux, "null flux gradient");
+        source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, gtopo, gtopo_on_device, accumulate, basis);
+    }
+    void source_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux, int gflux_on_device,
+                        double *gtopo, int gtopo_on_device, int accumulate, bool basis) {
         FV_HIP(hipSetDevice(device));
-        FV_REQUIRE(!type1, "the source adjoint runs the type-3 transform: set the array with fv_sim_set_array, not "
-                           "fv_sim_set_array_type1");
-        if (basis)
-            FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_source_adjoint needs a handle with basis beams (fv_sim_set_basis); "
-                                   "without them fv_sim_run_source_adjoint is the pass");
-        else
-            FV_REQUIRE(nbasis == 0, "the source adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        if (gflux) {
+            FV_REQUIRE(!type1, "the sky adjoint runs the type-3 transform: set the array with fv_sim_set_array, not "
+                               "fv_sim_set_array_type1");
+            if (basis)
+                FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_sky_adjoint needs a handle with basis beams (fv_sim_set_basis); "
+                                       "without them fv_sim_run_sky_adjoint is the pass");
+            else
+                FV_REQUIRE(nbasis == 0, "the sky adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs): "
+                                        "fv_sim_run_basis_sky_adjoint does");
+        } else {
+            FV_REQUIRE(!type1, "the source adjoint runs the type-3 transform: set the array with fv_sim_set_array, not "
+                               "fv_sim_set_array_type1");
+            if (basis)
+                FV_REQUIRE(nbasis > 0, "fv_sim_run_basis_source_adjoint needs a handle with basis beams (fv_sim_set_basis); "
+                                       "without them fv_sim_run_source_adjoint is the pass");
+            else
+                FV_REQUIRE(nbasis == 0, "the source adjoint does not cover basis beams (fv_sim_set_basis / beam_coefs)");
+        }
         check_run(t0, t1, f0, f1);
         const int nt = t1 - t0, nf = f1 - f0;
         const int64_t per_tf = (int64_t)tpol * nbls;
@@ -4856,10 +4885,12 @@ class Sim : public SimBase {
         const int nch = sc.n;
         const int64_t csz = sc.csz, cap = sc.cap;
         // channel blocks: a lane's accumulator holds nsrc x (channels of a block) x 3 doubles, at most
-        // FFTVIS_HIP_ADJ_ACC_BYTES; every block walks the time steps once
+        // FFTVIS_HIP_ADJ_ACC_BYTES; every block walks the time steps once.  Joint pass: comps more for the fluxes
+        const int comps = pol_sky ? 8 : 1;
+        const double acc_per = gflux ? 24.0 + 8.0 * comps : 24.0;
         const char *eab = std::getenv("FFTVIS_HIP_ADJ_ACC_BYTES");
         const double acc_max = eab ? std::atof(eab) : 256.0 * 1024 * 1024;
-        const int nfb = (int)std::max<double>(1.0, std::min<double>(nf, std::floor(acc_max / (24.0 * std::max<int64_t>(nsrc, 1)))));
+        const int nfb = (int)std::max<double>(1.0, std::min<double>(nf, std::floor(acc_max / (acc_per * std::max<int64_t>(nsrc, 1)))));
         struct FBlock {
             int b0, b1;
             std::vector<std::pair<int, int>> groups;
@@ -4872,7 +4903,10 @@ class Sim : public SimBase {
             for (const auto &grp : fb.groups) nfg_max = std::max(nfg_max, grp.second - grp.first);
             fblocks.push_back(std::move(fb));
         }
-        const size_t acc_bytes = sizeof(double) * 3 * (size_t)std::max<int64_t>(nsrc * std::min(nf, nfb), 1);
+        // the flux accumulator (joint pass) starts facc_off doubles into the lane's d_adj_acc
+        const size_t facc_off = 3 * (size_t)std::max<int64_t>(nsrc * std::min(nf, nfb), 1);
+        const size_t acc_bytes =
+            sizeof(double) * (facc_off + (gflux ? (size_t)std::max<int64_t>(nsrc * std::min(nf, nfb) * comps, 1) : 0));
         for (int li = 0; li < nlanes; ++li) {
             Lane &L = lanes[li];
             if (!L.adj || L.adj->dim != D || L.adj->sigma != sigma_a || L.adj->eps != eps)
@@ -4889,12 +4923,23 @@ class Sim : public SimBase {
         }
         const size_t gt_bytes = sizeof(double) * 3 * (size_t)nsrc * (size_t)nt;
         double *dgt = gtopo;
+        // joint pass: gflux on the device as in adjoint_flux; a host gflux is staged behind a host gtopo in d_adj_gf
+        const size_t gf_bytes = gflux ? sizeof(T) * (size_t)nsrc * nfreq_cat * comps : 0;
+        const size_t gt_stage = gtopo_on_device ? 0 : std::max<size_t>(gt_bytes, 16);
+        const size_t gf_stage = gflux && !gflux_on_device ? std::max<size_t>(gf_bytes, 16) : 0;
+        const size_t gf_at = (gt_stage + 255) / 256 * 256;
+        T *dgf = (T *)gflux;
+        if (gt_stage + gf_stage) d_adj_gf.reserve(gf_stage ? gf_at + gf_stage : gt_stage);
         if (!gtopo_on_device) {
-            d_adj_gf.reserve(std::max<size_t>(gt_bytes, 16));
             dgt = d_adj_gf.as<double>();
             if (accumulate && gt_bytes) FV_HIP(hipMemcpyAsync(dgt, gtopo, gt_bytes, hipMemcpyHostToDevice, stream));
         }
         if (!accumulate && gt_bytes) FV_HIP(hipMemsetAsync(dgt, 0, gt_bytes, stream));
+        if (gflux && !gflux_on_device) {
+            dgf = (T *)((char *)d_adj_gf.p + gf_at);
+            if (accumulate && gf_bytes) FV_HIP(hipMemcpyAsync(dgf, gflux, gf_bytes, hipMemcpyHostToDevice, stream));
+        }
+        if (gflux && !accumulate && gf_bytes) FV_HIP(hipMemsetAsync(dgf, 0, gf_bytes, stream));
         // the lanes write gtopo's rows themselves: they start after the main stream has prepared it
         FV_HIP(hipEventRecord(ev_start, stream));
         for (int li = 0; li < nlanes; ++li)
@@ -4903,8 +4948,17 @@ class Sim : public SimBase {
         int64_t z_off[16] = {0};
         for (int r = 0; r < tpol; ++r) z_off[r] = (int64_t)r * cap;
         const int ord = beam_order == 3 ? 3 : beam_order == 1 ? 1 : 0;
-        for (const FBlock &fb : fblocks) {
+        for (size_t bi = 0; bi < fblocks.size(); ++bi) {
+            const FBlock &fb = fblocks[bi];
             const int nfa = fb.b1 - fb.b0;
+            for (int li = 0; gflux && li < nlanes; ++li) {  // the lanes' flux accumulators, as adjoint_flux starts a block
+                if (bi > 0 && lanes[li].stream != stream) {  // the previous block's reduction has read this accumulator
+                    FV_HIP(hipEventRecord(ev_start, stream));
+                    FV_HIP(hipStreamWaitEvent(lanes[li].stream, ev_start, 0));
+                }
+                FV_HIP(hipMemsetAsync(lanes[li].d_adj_acc.template as<double>() + facc_off, 0,
+                                      sizeof(double) * (size_t)std::max<int64_t>(nsrc * nfa * comps, 1), lanes[li].stream));
+            }
             for (int t = t0; t < t1 && nsrc > 0; ++t) {
                 Lane &L = lanes[(t - t0) % nlanes];
                 const hipStream_t ls = L.stream;
@@ -4989,6 +5043,23 @@ class Sim : public SimBase {
                                                dim3((unsigned)cdiv(cap * nfg, 256)), dim3(256), 0, ls, aa, Mp,
                                                L.d_srcidx.template as<int>(), vec, d_flux.p, d_freqs.as<double>(),
                                                (const cplx<T> *)zb, acc);
+                            if (gflux) {  // set 0 is Z in k_adj_accumulate's layout: adjoint_flux's contraction
+                                AdjAccArgs fx{};
+                                fx.M = cap;
+                                fx.nfg = nfg;
+                                fx.f_first = fa;
+                                fx.f_base = fb.b0;
+                                fx.nfa = nfa;
+                                fx.polarized = polarized;
+                                fx.pol_sky = pol_sky;
+                                fx.same_beam = pr.bi == pr.bj;
+                                fx.bi = desc(pr.bi);
+                                fx.bj = desc(pr.bj);
+                                hipLaunchKernelGGL((ord == 3 ? k_adj_accumulate<T, 3> : ord == 1 ? k_adj_accumulate<T, 1> : k_adj_accumulate<T, 0>),
+                                                   dim3((unsigned)cdiv(cap * nfg, 256)), dim3(256), 0, ls, fx, Mp,
+                                                   L.d_srcidx.template as<int>(), L.d_az.template as<T>(), L.d_za.template as<T>(),
+                                                   d_freqs.as<double>(), zb, acc + facc_off);
+                            }
                         }
                     }
                 }
@@ -5003,6 +5074,23 @@ class Sim : public SimBase {
                                        d_freqs.as<double>(), dgt + (size_t)(t - t0) * 3 * nsrc);
                 }
             }
+            if (gflux) {  // the block's flux gradient: the lanes joined and summed in lane order on the main stream
+                for (int li = 0; li < nlanes; ++li)
+                    if (lanes[li].stream != stream) {
+                        FV_HIP(hipEventRecord(lanes[li].done, lanes[li].stream));
+                        FV_HIP(hipStreamWaitEvent(stream, lanes[li].done, 0));
+                    }
+                AdjReduceArgs ra{};
+                for (int li = 0; li < nlanes; ++li) ra.acc[li] = lanes[li].d_adj_acc.template as<double>() + facc_off;
+                ra.nl = nlanes;
+                ra.nfa = nfa;
+                ra.f_base = fb.b0;
+                ra.nfreq = nfreq_cat;
+                ra.comps = comps;
+                ra.nsrc = nsrc;
+                const int64_t ne = nsrc * nfa * comps;
+                if (ne > 0) hipLaunchKernelGGL(k_adj_reduce<T>, dim3((unsigned)cdiv(ne, 256)), dim3(256), 0, stream, ra, dgf);
+            }
         }
         for (int li = 0; li < nlanes; ++li)  // join: the copy on the main stream sees every lane
             if (lanes[li].stream != stream) {
@@ -5010,6 +5098,7 @@ class Sim : public SimBase {
                 FV_HIP(hipStreamWaitEvent(stream, lanes[li].done, 0));
             }
         if (!gtopo_on_device && gt_bytes) FV_HIP(hipMemcpyAsync(gtopo, dgt, gt_bytes, hipMemcpyDeviceToHost, stream));
+        if (gf_stage && gf_bytes) FV_HIP(hipMemcpyAsync(gflux, dgf, gf_bytes, hipMemcpyDeviceToHost, stream));
         FV_HIP(hipStreamSynchronize(stream));
         if (timing_level) ev_collect();
         {  // the 1 + D strength sets belong to this pass: beyond the keep limit they go back with the rest

@@ -320,6 +320,17 @@ class SimHandle:
         _lib.check(self._L.fv_sim_run_basis_source_adjoint(self._h, t0, t1, f0, f1, gp, g_dev, tp, t_dev,
                                                            int(bool(accumulate))))
 
+    def run_sky_adjoint(self, t0, t1, f0, f1, g, gflux, gtopo, accumulate: bool, basis: bool = False):
+        """``gflux += A^T g`` and ``gtopo +=`` the sources' tangential gradient from one pass for times [t0,t1) x freqs
+        [f0,f1) (``fv_sim_run_sky_adjoint``; ``basis``: ``fv_sim_run_basis_sky_adjoint``, a handle with ``set_basis``).
+        ``g`` and ``gflux`` as for ``run_adjoint``, ``gtopo`` as for ``run_source_adjoint``; ``accumulate`` applies to
+        both outputs."""
+        gp, g_dev = _buffer_addr(g)
+        fp, f_dev = _buffer_addr(gflux)
+        tp, t_dev = _buffer_addr(gtopo)
+        fn = self._L.fv_sim_run_basis_sky_adjoint if basis else self._L.fv_sim_run_sky_adjoint
+        _lib.check(fn(self._h, t0, t1, f0, f1, gp, g_dev, fp, f_dev, tp, t_dev, int(bool(accumulate))))
+
     def run_basis_source_tangent(self, t0, t1, f0, f1, dtopo, out):
         """Basis beams (``set_basis``): ``out =`` the tangent of the visibilities along ``dtopo`` for times [t0,t1) x freqs
         [f0,f1) (``fv_sim_run_basis_source_tangent``).  ``dtopo`` and ``out`` as for ``run_tangent``."""
@@ -463,6 +474,7 @@ class GPUSimulationEngine(SimulationEngine):
         tangent_of: tuple = None,
         basis_tangent_of: tuple = None,
         basis_source_of: tuple = None,
+        sky_of: tuple = None,
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -559,7 +571,17 @@ class GPUSimulationEngine(SimulationEngine):
           from time step t (``SimHandle.run_basis_source_adjoint``), and returns it.  ``("tangent", dtopo, dv)``: it fills
           ``dv`` (the result's shape) with the tangent along ``dtopo`` (ntimes, nsrc, 3)
           (``SimHandle.run_basis_source_tangent``) and returns it.  Time blocks take consecutive rows.
+        * ``sky_of`` (extra; what ``simulate_vis_sky_adjoint`` / ``simulate_vis_basis_sky_adjoint`` pass): a triple
+          ``(g, gflux, gtopo)`` -- the joint sky adjoint, with or without ``beam_coefs``: one pass per time block
+          (``SimHandle.run_sky_adjoint``) adds the flux gradient of ``adjoint_of`` into ``gflux`` and fills the block's rows
+          of ``gtopo`` as ``adjoint_wrt="sources"`` / ``basis_source_of`` do; returns ``(gflux, gtopo)``.  The pass runs the
+          type-3 transform only: ValueError on the lattice path (pass ``force_use_type3=True``).
         """
+        if sky_of is not None:
+            if adjoint_of is not None or tangent_of is not None or basis_tangent_of is not None or basis_source_of is not None:
+                raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of and sky_of")
+            if len(sky_of) != 3:
+                raise ValueError("sky_of: (g, gflux, gtopo)")
         if basis_source_of is not None:
             if adjoint_of is not None or tangent_of is not None or basis_tangent_of is not None:
                 raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of and basis_source_of")
@@ -666,6 +688,8 @@ class GPUSimulationEngine(SimulationEngine):
             raise ValueError("the position adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if sources and is_gridded:
             raise ValueError("the source adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
+        if sky_of is not None and is_gridded:
+            raise ValueError("the sky adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if tangent_of is not None and is_gridded:
             raise ValueError("the tangent runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if adjoint_path == "type2" and not is_gridded:
@@ -740,6 +764,10 @@ class GPUSimulationEngine(SimulationEngine):
                 return result
             if basis_source_of is not None:
                 result = _run_basis_source(h, *basis_source_of, t0, t1, f0, f1, nblk_t, coord_mgr)
+                ok = True
+                return result
+            if sky_of is not None:
+                result = _run_sky_adjoint(h, *sky_of, t0, t1, f0, f1, nblk_t, coord_mgr, basis=use_basis)
                 ok = True
                 return result
             if basis_tangent_of is not None:
@@ -961,6 +989,30 @@ def _run_basis_source(h, mode, a, b, t0, t1, f0, f1, nblk_t, coord_mgr):
     if t1 <= t0 and mode == "tangent":
         b[...] = 0
     return b
+
+
+def _run_sky_adjoint(h, g, gflux, gtopo, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False):
+    """The joint sky adjoint's time loop, over the forward's blocks (and, with a coordinate manager, its streamed vectors):
+    every block's ``run_sky_adjoint`` adds its contribution to ``gflux`` -- the first block overwrites -- and fills its rows
+    of ``gtopo``, the (t1 - t0, nsrc, 3) direction gradient.  The two outputs share one ``accumulate`` flag, so a later
+    block adds to its rows of the caller's zeroed buffer.  Every call ends synchronised."""
+    on_device = not isinstance(g, np.ndarray)
+    first = True
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+        blk = g[:, tb - t0:te - t0]
+        if on_device:
+            import torch
+
+            blk = blk.contiguous()
+            torch.cuda.synchronize(blk.device)  # a copy .contiguous() queued on torch's stream is done before the library reads
+        else:
+            blk = np.ascontiguousarray(blk)
+        # (rows of a C-contiguous array: a contiguous view, written in place)
+        h.run_sky_adjoint(ta, te_, f0, f1, blk, gflux, gtopo[tb - t0:te - t0], not first, basis=basis)
+        first = False
+    if first:  # no time steps: nothing contributes
+        gflux[...] = 0
+    return gflux, gtopo
 
 
 def _run_basis_tangent(h, dcoefs, dv, t0, t1, f0, f1, nblk_t, coord_mgr):

@@ -414,6 +414,33 @@ int fv_sim_run_basis_position_tangent(fv_sim *h, int t0, int t1, int f0, int f1,
  * usable) fail with FV_ERR_ARG.                                                                                          */
 int fv_sim_run_basis_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device,
                                     double *gtopo, int gtopo_on_device, int accumulate);
+/* Joint sky adjoint: fv_sim_run_adjoint's flux gradient AND fv_sim_run_source_adjoint's direction gradient of the same G in
+ * one pass, for times [t0, t1) x freqs [f0, f1) -- what a fit of the sources' fluxes and positions together needs per
+ * step.  The source pass's first transform per (time, frequency group, beam pair) is the flux adjoint's Z -- the same
+ * strengths, plan and targets --, so the 1 + D transforms of that pass serve both: after them Z is contracted with the
+ * beams exactly as fv_sim_run_adjoint does (its kernel on the same values) into a flux accumulator per lane, summed in lane
+ * order into gflux after each channel block, and gtopo comes from the source pass's own kernels unchanged.  gflux: the
+ * shape and type fv_sim_run_adjoint documents, only channels [f0, f1) receive a contribution.  gtopo: (t1 - t0, nsrc, 3)
+ * float64 as in fv_sim_run_source_adjoint.  accumulate = 0: both outputs are zeroed first; 1: both are added to.  The
+ * *_on_device flags per buffer as in fv_sim_run; the call synchronises once, at its end.  A lane's fp64 accumulators take
+ * 24 + 8 comps bytes per (source, channel of a block), comps = 1 for Stokes-I catalogs and 8 for coherency catalogs, at
+ * most FFTVIS_HIP_ADJ_ACC_BYTES (channel blocks).  No atomics, fixed orders: bitwise reproducible for a given
+ * FFTVIS_HIP_LANES, and gtopo whatever it is.  Memory is given back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule of
+ * fv_sim_run_adjoint.  A lattice handle (fv_sim_set_array_type1: set the array with fv_sim_set_array instead), a handle
+ * with basis beams (fv_sim_run_basis_sky_adjoint is the pass there), a null handle, a null gvis, gflux or gtopo, a flag
+ * other than 0 or 1 and NaN in gvis (detected before anything runs; the handle stays usable) fail with FV_ERR_ARG.         */
+int fv_sim_run_sky_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                           int gflux_on_device, double *gtopo, int gtopo_on_device, int accumulate);
+/* The same for a handle with basis beams (fv_sim_set_basis): fv_sim_run_basis_adjoint's gflux and
+ * fv_sim_run_basis_source_adjoint's gtopo from that pass's 1 + D transforms per (k <= l) term, one transform per term
+ * fewer than the two calls.  The term's Z is contracted with its pair of basis beams as in fv_sim_run_basis_adjoint's flux
+ * pass; fv_sim_set_reference_compat selects the form of the (l, k) terms as in fv_sim_run.  Arguments, accumulators, channel
+ * blocks and memory as in fv_sim_run_sky_adjoint.  The coefficients' gradient is fv_sim_run_basis_adjoint's (its transforms
+ * run the other way).  A handle without fv_sim_set_basis (fv_sim_run_sky_adjoint is the pass there), a lattice handle, a
+ * null handle, a null gvis, gflux or gtopo, a flag other than 0 or 1 and NaN in gvis (detected before anything runs; the
+ * handle stays usable) fail with FV_ERR_ARG.                                                                              */
+int fv_sim_run_basis_sky_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
+                                 int gflux_on_device, double *gtopo, int gtopo_on_device, int accumulate);
 /* Forward-mode tangent of a basis-beam handle's visibilities along a change of the sources' directions, the transpose of
  * fv_sim_run_basis_source_adjoint:  out = sum_{t,j} dV/dn_j(t) . P_n dtopo[t - t0, j],  Re <out, G> = sum dtopo . gtopo.
  * dtopo: (t1 - t0, nsrc, 3) float64, ENU; a row of a source below the horizon is not read.  out: fv_sim_run's layout for

@@ -68,6 +68,8 @@ int main() {
     EXPECT(fv_sim_run_basis_position_tangent(nullptr, 0, 1, 0, 1, v, 0, v, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_basis_source_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_run_basis_source_tangent(nullptr, 0, 1, 0, 1, v, 0, v, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_sky_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, v, 0, 0) == FV_ERR_ARG);
+    EXPECT(fv_sim_run_basis_sky_adjoint(nullptr, 0, 1, 0, 1, v, 0, v, 0, v, 0, 0) == FV_ERR_ARG);
     EXPECT(fv_sim_sync(nullptr) == FV_ERR_ARG);
     EXPECT(fv_sim_stats(nullptr, v, 12) == FV_ERR_ARG);
     EXPECT(fv_sim_reset_stats(nullptr) == FV_ERR_ARG);
@@ -171,6 +173,19 @@ int main() {
         EXPECT(fv_sim_run_basis_source_tangent(fake, 0, 1, 0, 1, nullptr, 0, v, 0) == FV_ERR_ARG);
         EXPECT(fv_sim_run_basis_source_tangent(fake, 0, 1, 0, 1, v, 2, v, 0) == FV_ERR_ARG);
         EXPECT(fv_sim_run_basis_source_tangent(fake, 0, 1, 0, 1, v, 0, v, 3) == FV_ERR_ARG);
+    }
+    // and the joint sky adjoints: any null buffer, each on_device flag and accumulate other than 0 or 1
+    {
+        fv_sim *fake = reinterpret_cast<fv_sim *>(0x1);
+        for (auto fn : {fv_sim_run_sky_adjoint, fv_sim_run_basis_sky_adjoint}) {
+            EXPECT(fn(fake, 0, 1, 0, 1, nullptr, 0, v, 0, v, 0, 0) == FV_ERR_ARG);
+            EXPECT(fn(fake, 0, 1, 0, 1, v, 0, nullptr, 0, v, 0, 0) == FV_ERR_ARG);
+            EXPECT(fn(fake, 0, 1, 0, 1, v, 0, v, 0, nullptr, 0, 0) == FV_ERR_ARG);
+            EXPECT(fn(fake, 0, 1, 0, 1, v, 2, v, 0, v, 0, 0) == FV_ERR_ARG);
+            EXPECT(fn(fake, 0, 1, 0, 1, v, 0, v, -1, v, 0, 0) == FV_ERR_ARG);
+            EXPECT(fn(fake, 0, 1, 0, 1, v, 0, v, 0, v, 3, 0) == FV_ERR_ARG);
+            EXPECT(fn(fake, 0, 1, 0, 1, v, 0, v, 0, v, 0, 2) == FV_ERR_ARG);
+        }
     }
     // and the basis tangent: a null output, null directions, ndir < 1, on_device flags other than 0 or 1
     {

@@ -7,12 +7,13 @@
     adjoint         forward adjoint                                                 C3, 2 channels
     basis_adjoint   forward fluxes beam_coefs both                                  C5, 4 channels  (--small: HERA-37, K = 3)
     position        forward position                                                C3, 8 channels  (--array)
-    source          forward fluxes sources                                          C3, 8 channels
+    source          forward fluxes sources joint                                    C3, 8 channels
     tangent         forward position source tangent_baselines tangent_directions
                     tangent_both                                                    C3, 8 channels  (--array)
     basis_tangent   forward tangent_1 tangent_n beam_coefs                          C5, 8 channels  (--ndir)
     basis_position  forward adjoint tangent                                         C5, 8 channels
-    basis_source    forward fluxes tangent_ants source_adjoint source_tangent       C5, 8 channels  (--precision)
+    basis_source    forward fluxes tangent_ants source_adjoint source_tangent
+                    joint                                                           C5, 8 channels  (--precision)
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -93,7 +94,8 @@ def source(a, fv, cfg, rng):
     return {"precision": cfg["precision"], "polarized": bool(cfg["polarized"])}, {
         "forward": lambda: fv.simulate_vis(**cfg),
         "fluxes": lambda: fv.simulate_vis_adjoint(g, **no_flux, full_stokes=np.ndim(cfg["fluxes"]) == 3),
-        "sources": lambda: fv.simulate_vis_source_adjoint(g, **cfg, wrt="radec")}
+        "sources": lambda: fv.simulate_vis_source_adjoint(g, **cfg, wrt="radec"),
+        "joint": lambda: fv.simulate_vis_sky_adjoint(g, **cfg, wrt=("fluxes", "radec"))}
 
 
 def tangent(a, fv, cfg, rng):
@@ -141,17 +143,19 @@ def basis_source(a, fv, cfg, rng):
         "fluxes": lambda: fv.simulate_vis_basis_adjoint(g, **cfg, wrt="fluxes"),
         "tangent_ants": lambda: fv.simulate_vis_basis_jvp(**cfg, d_ants=da),
         "source_adjoint": lambda: fv.simulate_vis_basis_source_adjoint(g, **cfg, wrt="topo"),
-        "source_tangent": lambda: fv.simulate_vis_basis_source_jvp(**cfg, d_topo=dt)}
+        "source_tangent": lambda: fv.simulate_vis_basis_source_jvp(**cfg, d_topo=dt),
+        "joint": lambda: fv.simulate_vis_basis_sky_adjoint(g, **cfg, wrt=("fluxes", "topo"))}
 
 
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
-#          ratios {key: (pass, pass it is divided by)})
+#          ratios {key: (pass, pass it is divided by -- or a tuple of passes, for their sum)})
 FAMILIES = {
     "adjoint": (adjoint, "C3", 2, ("lattice", "adjoint_path"), "range", {"adjoint_over_forward": ("adjoint", "forward")}),
     "basis_adjoint": (basis_adjoint, "C5", 4, ("small",), None, {}),
     "position": (position, "C3", 8, ("array",), "runs", {"position_over_forward": ("position", "forward")}),
     "source": (source, "C3", 8, (), "runs", {"sources_over_fluxes": ("sources", "fluxes"),
-                                            "sources_over_forward": ("sources", "forward")}),
+                                            "sources_over_forward": ("sources", "forward"),
+                                            "joint_over_fluxes_plus_sources": ("joint", ("fluxes", "sources"))}),
     "tangent": (tangent, "C3", 8, ("array",), "runs", {}),
     "basis_tangent": (basis_tangent, "C5", 8, ("ndir",), "runs", {}),
     "basis_position": (basis_position, "C5", 8, (), "runs", {"adjoint_over_forward": ("adjoint", "forward"),
@@ -159,7 +163,8 @@ FAMILIES = {
     "basis_source": (basis_source, "C5", 8, ("precision",), "runs", {
         "source_adjoint_over_fluxes": ("source_adjoint", "fluxes"), "source_adjoint_over_forward": ("source_adjoint", "forward"),
         "source_tangent_over_forward": ("source_tangent", "forward"),
-        "source_tangent_over_tangent_ants": ("source_tangent", "tangent_ants")}),
+        "source_tangent_over_tangent_ants": ("source_tangent", "tangent_ants"),
+        "joint_over_fluxes_plus_source_adjoint": ("joint", ("fluxes", "source_adjoint"))}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
              "precision": 1}  # and their defaults
@@ -229,8 +234,9 @@ def main():
             out[name + "_range"] = [min(runs), max(runs)]
         print(json.dumps({name: runs}), file=sys.stderr, flush=True)
     for key, (num, den) in ratios.items():
-        if num + "_ms_per_step" in out and den + "_ms_per_step" in out:
-            out[key] = round(out[num + "_ms_per_step"] / out[den + "_ms_per_step"], 3)
+        den = (den,) if isinstance(den, str) else den
+        if all(k + "_ms_per_step" in out for k in (num,) + den):
+            out[key] = round(out[num + "_ms_per_step"] / sum(out[k + "_ms_per_step"] for k in den), 3)
     if all(k + "_ms_per_step" in out for k in ("forward", "tangent_1", "tangent_n")):  # (basis_tangent)
         # per direction, against TWO forward runs: what (V(C + D) - V(C - D)) / 2 costs a caller without the pass
         two = 2.0 * out["forward_ms_per_step"]
