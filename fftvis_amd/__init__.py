@@ -10,7 +10,9 @@ gradient with respect to the antenna positions (``simulate_vis_position_adjoint`
 the source positions (``simulate_vis_source_adjoint``, ``torch_simulate_vis_sky``), and the forward-mode tangent along
 all three (``simulate_vis_jvp``), and the source positions through basis beams
 (``simulate_vis_basis_source_adjoint``, ``simulate_vis_basis_source_jvp``, ``torch_simulate_vis_basis_sky``), and the fluxes'
-and the source positions' gradients from one pass (``simulate_vis_sky_adjoint``, ``simulate_vis_basis_sky_adjoint``).
+and the source positions' gradients from one pass (``simulate_vis_sky_adjoint``, ``simulate_vis_basis_sky_adjoint``), and
+the fit objective with its gradients from one call that keeps the visibilities on the device (``simulate_vis_chi2``,
+``torch_simulate_vis_chi2``).
 """
 
 __version__ = "0.1.0"
@@ -29,6 +31,7 @@ from .adjoint import (  # noqa: F401
     simulate_vis_basis_sky_adjoint,
     simulate_vis_basis_source_adjoint,
     simulate_vis_basis_source_jvp,
+    simulate_vis_chi2,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,
     simulate_vis_sky_adjoint,
@@ -38,6 +41,7 @@ from .adjoint import (  # noqa: F401
     torch_simulate_vis_basis,
     torch_simulate_vis_basis_array,
     torch_simulate_vis_basis_sky,
+    torch_simulate_vis_chi2,
     torch_simulate_vis_sky,
     topo_to_radec_gradient,
 )

@@ -22,6 +22,10 @@ antenna positions, the source positions and the fluxes (``fv_sim_run_tangent``),
 also offer to ``torch.autograd.forward_ad`` through their ``jvp``.  Basis beams have their own,
 ``simulate_vis_basis_jvp``: the tangent along directions of the coefficients and of the fluxes
 (``fv_sim_run_basis_tangent``), several directions per call, and the ``jvp`` of ``torch_simulate_vis_basis``.
+
+A fit's G is 2 w (V - d).  ``simulate_vis_chi2`` and ``torch_simulate_vis_chi2`` form it on the device, behind the forward
+run of the same handle (``fv_sim_run_residual``), and run the passes above on it where it lies: chi2 and its gradients
+from one call, one set-up, with the visibilities never copied to the host.
 """
 
 from __future__ import annotations
@@ -1691,3 +1695,209 @@ def torch_simulate_vis_basis_sky(fluxes, beam_coefs, radec, **kwargs):
     if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
         raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
     return _function(_basis_sky_autograd_function).apply(fluxes, beam_coefs, radec, kwargs)
+
+
+_CHI2_WRT = ("fluxes", "ants", "baselines", "topo", "radec", "beam_coefs")
+
+
+def simulate_vis_chi2(
+    data,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    weights=None,
+    wrt=("fluxes",),
+    beam_coefs=None,
+    chi2_per: str = "total",
+    return_gvis: bool = False,
+    adjoint_path: str = "type3",
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """The fit objective and its gradients in one call: ``chi2 = sum w |V - data|^2`` with ``V = simulate_vis(ants, fluxes,
+    ra, dec, ...)`` of the same arguments, and the gradients of chi2 (not of chi2 / 2) with respect to the parameters
+    named in ``wrt``.  One handle and one set-up serve the forward run and every derivative pass, and the visibilities
+    never leave the device: per time block the forward writes them into a device buffer, a residual kernel replaces them
+    by ``G = 2 w (V - data) = d chi2 / dV`` and adds up chi2 (``fv_sim_run_residual``), and the handle passes of the
+    public adjoints read G where it lies.  Returns ``(chi2, grads)``, with ``return_gvis=True`` ``(chi2, grads, G)``.
+
+    * ``data``: ``simulate_vis``'s output shape.  ``weights``: None (every weight 1) or a real array of that shape, inverse
+      variances; a weight of exactly 0 flags its sample: it adds nothing, G is exactly 0 there and the datum is not used
+      (it may be NaN).  A negative or non-finite weight, or a non-finite datum at a positive weight, fails the call.  Both
+      may be numpy arrays or torch tensors; tensors on the run's device are read by pointer and may stay resident across
+      the iterations of a fit (ValueError for another device).  The outputs follow ``data`` as the outputs of the other
+      passes follow ``vis``: tensors on its device for a device tensor, host tensors for a host tensor, numpy otherwise.
+    * ``wrt``: a name or a tuple of distinct names out of ``"fluxes"``, ``"ants"``, ``"baselines"``, ``"topo"``, ``"radec"``
+      and, with ``beam_coefs`` (basis beams; ``polarized=True``), ``"beam_coefs"``; ``grads`` is that gradient, or a tuple in
+      ``wrt``'s order.  Shapes, units and the coordinate rules of ``"radec"`` are those of the public pass that owns the
+      name (``simulate_vis_sky_adjoint``, ``simulate_vis_position_adjoint``, ``simulate_vis_basis_adjoint``,
+      ``simulate_vis_basis_sky_adjoint``), whose handle pass runs here on G, so the gradients are those functions' results
+      for ``vis = G``.  ``wrt=()`` gives the value alone (a line search) and ``grads == ()``.
+    * ``chi2_per="total"``: a Python float, the sum of the (nfreqs, ntimes) array in row-major order; ``"freq_time"``: that
+      float64 array, one value per (frequency, time) -- bitwise reproducible for a given forward result (no
+      floating-point atomics).
+    * ``return_gvis=True`` appends G in ``data``'s shape, what a Gauss-Newton step needs: ``J^T W r = J^T G / 2``.
+    * ``adjoint_path``: as for ``simulate_vis_adjoint``, for ``wrt`` within ``{"fluxes"}``.
+    * ``force_use_type3`` is honoured for ``wrt`` within ``{"fluxes"}`` -- a lattice array then takes the type-1 forward --
+      and is ON FOR THE WHOLE CALL otherwise: the position passes run the type-3 transform and share the handle with the
+      forward, so the forward of such a call is the type-3 one (equal to the type-1 result to ``eps``).
+
+    Every other keyword means what it means for ``simulate_vis``.  Not covered: forward-mode derivatives, a tangent or
+    J^T J product in the same call, sharding over GPUs."""
+    args = locals()
+    single = isinstance(wrt, str)
+    names = (wrt,) if single else tuple(wrt)
+    if names:
+        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec' and 'beam_coefs'")
+    if chi2_per not in ("total", "freq_time"):
+        raise ValueError(f"chi2_per must be 'total' or 'freq_time', got {chi2_per!r}")
+    if adjoint_path not in ("type3", "type2", "auto"):
+        raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {adjoint_path!r}")
+    if "beam_coefs" in names and beam_coefs is None:
+        raise ValueError("wrt='beam_coefs' needs beam_coefs (basis beams)")
+    if beam_coefs is not None and not polarized:  # the forward's message
+        raise ValueError(
+            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
+        )
+    run = _describe_run(args)
+    run = _own_radec_chain(run, "wrt='radec'", "radec" in names, "ask for wrt='topo' and apply its Jacobian",
+                           "ask for wrt='topo'")
+    fluxes, full_stokes = _sky_full_stokes(run, fluxes, full_stokes)
+    _run_device(run, (data,), "data")
+    if tuple(data.shape) != run.vis_shape:
+        raise ValueError(f"data must have simulate_vis's output shape {run.vis_shape}, got {tuple(data.shape)}")
+    if weights is not None:
+        if tuple(weights.shape) != run.vis_shape:
+            raise ValueError(f"weights must have data's shape {run.vis_shape}, got {tuple(weights.shape)}")
+        if weights.is_complex() if _is_tensor(weights) else np.iscomplexobj(weights):
+            raise ValueError("weights must be real (inverse variances; 0 flags a sample)")
+    f_shape = (run.nsrc, run.nfreqs)
+    d, (gflux, gcoefs, gbls, gtopo), on_device = _gradient_buffers(run, data, [
+        None if "fluxes" not in names else (f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real"),
+        None if "beam_coefs" not in names else (run.beam_coefs.shape, "complex"),
+        None if "ants" not in names and "baselines" not in names else ((run.nbls, 3), "float64"),
+        None if "topo" not in names and "radec" not in names else ((run.ntimes, run.nsrc, 3), "float64")])
+    w = None
+    if weights is not None:
+        w_device = _run_device(run, (weights,), "weights")
+        w = _host(weights).astype(run.rdt, copy=False) if w_device is None else _on(w_device, weights, run.rdt)
+        _synchronize(w_device)
+    gvis = None
+    if return_gvis:
+        import torch
+
+        gvis = _zeros(torch.device("cuda", int(device)), run.vis_shape, run.cdt)
+        _synchronize(gvis.device)
+    chi2_ft = _engine_simulate(
+        run, fluxes, force_use_type3=None if set(names) <= {"fluxes"} else True, adjoint_path=adjoint_path,
+        objective_of=(d, w, dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis)))
+    res = {"topo": gtopo, "baselines": gbls, "beam_coefs": gcoefs}
+    if "fluxes" in names:
+        res["fluxes"] = stokes_adjoint(gflux, full_stokes)
+    if "radec" in names:
+        res["radec"] = topo_to_radec_gradient(gtopo, _radec_jacobian_of(run))
+    if "ants" in names:
+        res["ants"] = baseline_to_antenna_gradient(gbls, run.ants, run.baselines)
+    grads = _select({k: v for k, v in res.items() if k in names}, single, names, data, on_device) if names else ()
+    if chi2_per == "total":
+        chi2 = float(np.cumsum(chi2_ft.ravel())[-1])  # (added in row-major order)
+    else:
+        chi2 = chi2_ft
+        if _is_tensor(data):
+            import torch
+
+            chi2 = torch.from_numpy(chi2_ft).to(data.device)
+    if not return_gvis:
+        return chi2, grads
+    if not on_device:
+        gvis = gvis.cpu().numpy()
+        if _is_tensor(data):
+            import torch
+
+            gvis = torch.from_numpy(gvis)
+    return chi2, grads, gvis
+
+
+def _chi2_autograd_function():
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _SimulateVisChi2(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, fluxes, beam_coefs, antpos, radec, data, weights, antnums, kwargs):
+            inputs = (("fluxes", fluxes), ("beam_coefs", beam_coefs), ("ants", antpos), ("radec", radec))
+            wrt = tuple(n for (n, _), need in zip(inputs, ctx.needs_input_grad[:4]) if need)
+            kw = dict(kwargs)
+            if antpos is not None:
+                kw["ants"] = _ants_of(antnums, antpos)
+            if radec is not None:
+                kw.update(_radec_columns(radec))
+            chi2, grads = simulate_vis_chi2(data, fluxes=fluxes, weights=weights, beam_coefs=beam_coefs, wrt=wrt,
+                                            chi2_per="total", **kw)
+            got = dict(zip(wrt, grads))
+            ctx.grads = tuple(None if got.get(n) is None else _as_grad(got[n], x.device, x.dtype) for n, x in inputs)
+            return torch.tensor(chi2, dtype=torch.float64, device=fluxes.device)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_output):
+            return tuple(None if g is None else g * grad_output.to(device=g.device, dtype=g.real.dtype)
+                         for g in ctx.grads) + (None,) * 4
+
+    return _SimulateVisChi2
+
+
+def torch_simulate_vis_chi2(data, fluxes, *, weights=None, beam_coefs=None, antpos=None, antnums=None, radec=None, **kwargs):
+    """``simulate_vis_chi2`` as a torch loss: ``chi2 = sum w |V - data|^2`` as a scalar float64 tensor on ``fluxes``' device,
+    differentiable in ``fluxes`` (real, (nsrc, nfreqs) or (nsrc, nfreqs, 4)) and in the optional tensors ``beam_coefs``
+    (complex, (nant, nbasis, nfreqs): basis beams), ``antpos`` (real, (nant, 3), ENU metres, replacing ``ants=``; ``antnums``
+    gives the keys ``baselines`` refers to) and ``radec`` (real, (nsrc, 2), replacing ``ra=`` / ``dec=``; needs
+    ``coord_method="SiderealRotation"`` or device astrometry).  ``data`` and ``weights`` are constants, numpy arrays or
+    tensors -- tensors on the run's device stay there; every other argument is a keyword of ``simulate_vis_chi2``.  The
+    forward reads ``ctx.needs_input_grad`` and makes ONE ``simulate_vis_chi2`` call with exactly the inputs that need a
+    gradient, keeping the gradients; the backward pass multiplies them by the incoming scalar (once differentiable).
+    Not covered: forward-mode differentiation, double backward."""
+    for taken, by in (("wrt", "what requires a gradient"), ("chi2_per", "the scalar loss"), ("return_gvis", "the scalar loss")):
+        if taken in kwargs:
+            raise TypeError(f"torch_simulate_vis_chi2 does not take {taken}=: {by} decides")
+    if antpos is not None:
+        antnums = _checked_antnums("torch_simulate_vis_chi2", antpos, antnums, kwargs)
+    elif antnums is not None:
+        raise TypeError("antnums goes with the tensor antpos")
+    if radec is not None:
+        if "ra" in kwargs or "dec" in kwargs:
+            raise TypeError("torch_simulate_vis_chi2 takes the source positions as the tensor radec or as ra= / dec=, not both")
+        if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
+            raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
+    return _function(_chi2_autograd_function).apply(fluxes, beam_coefs, antpos, radec, data, weights, antnums, kwargs)

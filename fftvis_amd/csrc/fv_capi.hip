@@ -325,6 +325,40 @@ static void coherency_host(int device, int variant, int64_t n, const void *bi, c
 }
 
 template <typename T>
+static void residual_chi2_host(int device, int64_t nrows, int64_t row_len, void *vis, const void *data, const void *weights,
+                               double *chi2_rows) {
+    FV_REQUIRE(nrows >= 0 && row_len >= 0, "fv_residual_chi2: negative shape");
+    FV_REQUIRE((nrows == 0 || row_len == 0 || (vis && data)) && (nrows == 0 || chi2_rows), "fv_residual_chi2: null vis, data or chi2_rows");
+    FV_HIP(hipSetDevice(device));
+    if (nrows == 0) return;
+    if (row_len == 0) {
+        for (int64_t i = 0; i < nrows; ++i) chi2_rows[i] = 0.0;
+        return;
+    }
+    StreamGuard sg;
+    const size_t n = (size_t)nrows * (size_t)row_len;
+    const int nblk = residual_blocks_per_row<T>(row_len);
+    DevBuf dv, dd, dw, ds;
+    dv.reserve(sizeof(cplx<T>) * n);
+    dd.reserve(sizeof(cplx<T>) * n);
+    if (weights) dw.reserve(sizeof(T) * n);
+    ds.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
+    double *partials = ds.as<double>(), *sums = partials + (size_t)nrows * nblk;
+    int *bad = reinterpret_cast<int *>(sums + nrows);
+    FV_HIP(hipMemcpyAsync(dv.p, vis, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    FV_HIP(hipMemcpyAsync(dd.p, data, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    if (weights) FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
+    launch_residual<T>(sg.s, dv.as<cplx<T>>(), dd.as<cplx<T>>(), weights ? dw.as<T>() : nullptr, nrows, row_len, partials, sums, bad);
+    int hbad[2] = {0, 0};
+    FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(chi2_rows, sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+    throw_if_bad_residual_input(hbad);
+}
+
+template <typename T>
 static void inplace_rot_host(int device, const double *rot, void *b, int64_t n) {
     FV_REQUIRE(rot && n >= 0 && (b || n == 0), "bad inplace_rot arrays");
     FV_HIP(hipSetDevice(device));
@@ -467,6 +501,17 @@ int fv_apparent_coherency(int device, int precision, int variant, int64_t n, con
     });
 }
 
+int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, void *vis, const void *data,
+                     const void *weights, double *chi2_rows) {
+    return guarded([&] {
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        if (precision == 2)
+            residual_chi2_host<double>(device, nrows, row_len, vis, data, weights, chi2_rows);
+        else
+            residual_chi2_host<float>(device, nrows, row_len, vis, data, weights, chi2_rows);
+    });
+}
+
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n) {
     return guarded([&] {
         FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
@@ -582,6 +627,17 @@ int fv_sim_run_into(fv_sim *h, int t0, int t1, int f0, int f1, void *out, int64_
             h->impl->out_shared = 0;
             throw;
         }
+    });
+}
+int fv_sim_run_residual(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                        int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(data && gvis && chi2_ft, "null data, gvis or chi2_ft");
+        FV_REQUIRE((data_on_device == 0 || data_on_device == 1) && (weights_on_device == 0 || weights_on_device == 1) &&
+                       (gvis_on_device == 0 || gvis_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_residual(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, gvis, gvis_on_device, chi2_ft);
     });
 }
 int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,

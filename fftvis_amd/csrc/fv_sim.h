@@ -1465,6 +1465,126 @@ __global__ void k_count_nonfinite(const double *__restrict__ v, int64_t n, int *
 }
 
 // ---------------------------------------------------------------------------------------------
+// Fused objective (fv_residual_chi2, fv_sim_run_residual; DESIGN.md "Fused objective").  The block of visibilities V is
+// nrows = nf nt rows of L = tpol nbls contiguous complex values; in place, per element,
+//     delta = V - d (T),   G = 2 w delta (T: two roundings and an exact doubling),   row sum += w |delta|^2 (fp64),
+// w = 1 without weights.  w == 0 flags the sample: G = 0 exactly, nothing is added and d is not used (a select, so NaN or
+// Inf there do not propagate).  One thread <-> one chunk of RES_W<T> = 16 / sizeof(T) elements aligned in the BLOCK's own
+// index (not the row's): 16 bytes of weights and twice 16 bytes of V and of d, read and written as 16-byte vectors when
+// the three arrays are 16-byte aligned (vec) and the chunk lies inside the row; the first and the last chunk of a row are
+// clipped to it and go element by element.  A block takes RES_CHUNKS consecutive groups of 256 chunks of its row, the
+// grid is (blocks per row, rows) -- rows beyond the grid's y limit are walked with its stride -- and every block writes
+// ONE fp64 partial, partials[row][block]: per thread in chunk order, an __shfl_xor tree inside the wave, then the waves
+// in order through LDS.  k_chi2_rows_reduce adds a row's partials in index order.  No floating-point atomics: the sums'
+// bits depend on the input alone.  Bad input is counted on the way (int atomics): bad[0] weights that are negative or not
+// finite, bad[1] data that are not finite where w > 0.
+template <typename T>
+constexpr int RES_W = 16 / (int)sizeof(T);
+constexpr int RES_CHUNKS = 4;
+template <typename T>
+__device__ __forceinline__ double residual_element(cplx<T> &v, const cplx<T> &d, T w, int &bad_w, int &bad_d) {
+    if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
+    if (!(w > (T)0)) {  // flagged (or counted above)
+        v = {(T)0, (T)0};
+        return 0.0;
+    }
+    if (!isfinite(d.re) || !isfinite(d.im)) ++bad_d;
+    const T dr = v.re - d.re, di = v.im - d.im;
+    v = {(T)2 * (w * dr), (T)2 * (w * di)};
+    return (double)w * ((double)dr * (double)dr + (double)di * (double)di);
+}
+template <typename T>
+__global__ void __launch_bounds__(256) k_residual_rows(cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data,
+                                                       const T *__restrict__ weights, int64_t nrows, int64_t L, int vec,
+                                                       double *__restrict__ partials, int *__restrict__ bad) {
+    constexpr int W = RES_W<T>;
+    constexpr int NV = W * (int)sizeof(cplx<T>) / 16;  // 16-byte vectors of V (and of d) per chunk: 2
+    __shared__ double wave_sum[4];
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const int64_t lo = row * L, hi = lo + L;  // the row in the block's index
+        const int64_t c0 = lo / W;                // its first chunk
+        double s = 0.0;
+        int bad_w = 0, bad_d = 0;
+        for (int i = 0; i < RES_CHUNKS; ++i) {
+            const int64_t c = c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x;
+            const int64_t e0 = c * W;
+            if (e0 >= hi) break;
+            if (vec && e0 >= lo && e0 + W <= hi) {
+                union {
+                    uint4 q[NV];
+                    cplx<T> c[W];
+                } v, d;
+                union {
+                    uint4 q;
+                    T w[W];
+                } ww;
+#pragma unroll
+                for (int k = 0; k < NV; ++k) {
+                    v.q[k] = reinterpret_cast<const uint4 *>(vis + e0)[k];
+                    d.q[k] = reinterpret_cast<const uint4 *>(data + e0)[k];
+                }
+                if (weights) ww.q = *reinterpret_cast<const uint4 *>(weights + e0);
+#pragma unroll
+                for (int k = 0; k < W; ++k) s += residual_element<T>(v.c[k], d.c[k], weights ? ww.w[k] : (T)1, bad_w, bad_d);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) reinterpret_cast<uint4 *>(vis + e0)[k] = v.q[k];
+            } else {
+                const int64_t a = e0 > lo ? e0 : lo, b = e0 + W < hi ? e0 + W : hi;
+                for (int64_t e = a; e < b; ++e) {
+                    cplx<T> v = vis[e];
+                    s += residual_element<T>(v, data[e], weights ? weights[e] : (T)1, bad_w, bad_d);
+                    vis[e] = v;
+                }
+            }
+        }
+        if (bad_w) atomicAdd(bad, bad_w);
+        if (bad_d) atomicAdd(bad + 1, bad_d);
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+        __syncthreads();  // (the next row of this block writes wave_sum again)
+    }
+}
+// chi2_rows[row] = a row's partials added in index order (k_residual_rows)
+__global__ void k_chi2_rows_reduce(const double *__restrict__ partials, int64_t nrows, int nblk, double *__restrict__ chi2_rows) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= nrows) return;
+    double s = 0.0;
+    for (int b = 0; b < nblk; ++b) s += partials[row * nblk + b];
+    chi2_rows[row] = s;
+}
+// blocks per row of k_residual_rows: the chunks a row of L elements can touch (one more than its own when it starts
+// inside a chunk), RES_CHUNKS * 256 per block
+template <typename T>
+inline int residual_blocks_per_row(int64_t L) {
+    return (int)std::max<int64_t>(1, cdiv(cdiv(L, RES_W<T>) + 1, (int64_t)RES_CHUNKS * 256));
+}
+// Queues the two kernels on `on`: vis (nrows, L) in place, chi2_rows nrows doubles, partials nrows * blocks-per-row
+// doubles, bad two ints (zeroed here).  All device pointers; weights may be null.
+template <typename T>
+inline void launch_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *data, const T *weights, int64_t nrows, int64_t L,
+                            double *partials, double *chi2_rows, int *bad) {
+    const int nblk = residual_blocks_per_row<T>(L);
+    const int vec = ((reinterpret_cast<uintptr_t>(vis) | reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;
+    FV_HIP(hipMemsetAsync(bad, 0, 2 * sizeof(int), on));
+    hipLaunchKernelGGL(k_residual_rows<T>, dim3((unsigned)nblk, (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, on, vis,
+                       data, weights, nrows, L, vec, partials, bad);
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
+                       chi2_rows);
+}
+// the message of a call that met bad input (k_residual_rows' counters)
+inline void throw_if_bad_residual_input(const int bad[2]) {
+    if (bad[0])
+        throw Error(FV_ERR_ARG, std::to_string(bad[0]) + " weights are negative or not finite (weights are inverse variances; 0 "
+                                                         "flags a sample)");
+    if (bad[1])
+        throw Error(FV_ERR_ARG, std::to_string(bad[1]) + " entries of data are not finite where the weight is positive (flag "
+                                                         "them with weight 0)");
+}
+
+// ---------------------------------------------------------------------------------------------
 // Type-1 path (lattice arrays): cpu_nufft2d_type1 (cpu/nufft.py:120-175), set-up
 // cpu_simulate.py:661-681, per-slice :964-965,990-992,259-269.
 // Visibility of the integer baseline (bx, by) at frequency nu is mode (bx, by) of a type-1
@@ -2050,6 +2170,8 @@ struct SimBase {
                            const int *ant2) = 0;
     virtual void set_chunking(int nchunks, double source_buffer) = 0;
     virtual void run(int t0, int t1, int f0, int f1, void *out, int out_on_device) = 0;
+    virtual void run_residual(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                              int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft) = 0;
     virtual void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, int accumulate) = 0;
     virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
@@ -2228,6 +2350,8 @@ class Sim : public SimBase {
     DevBuf d_adj_g, d_adj_gf;  // adjoint: host G block / host gradient staged on the device
     DevBuf d_adj_gc;           // basis adjoint: host coefficient gradient staged on the device
     DevBuf d_tan_w, d_tan_dt;  // tangent: the rounds' weights (RunPlan::tan_w), host dtopo staged on the device
+    DevBuf d_res_d, d_res_w;   // fused objective: host data / host weights staged on the device
+    DevBuf d_res_sum;          // fused objective: the blocks' partial sums, the rows' sums and the two bad-input counters
     DevBuf d_bt_d, d_bt_out;   // basis tangent: host directions D / the (ndir, ...) output of a host destination, on the device
     DevBuf d_csr_start, d_csr;  // basis mode: per antenna, its baselines as 2 b + role (k_coef_reduce)
     int nant_basis = 0;
@@ -3555,6 +3679,58 @@ class Sim : public SimBase {
         if (dr.dbg) std::fprintf(stderr, "run: buffers and column plans %.3f s\n", dr.pin.since());
         queue_units(r, o, dr);
         finish_output(o, dr);
+    }
+
+    // ---- fused objective: gvis = 2 w (V - d) and chi2_ft = the (frequency, time) rows of sum w |V - d|^2, V this handle's
+    // forward run of the block, which never leaves the device (DESIGN.md "Fused objective") -------------------------------
+    // run() fills the block on the device -- the caller's buffer, or d_out for a host destination -- on whichever path the
+    // handle takes (type 1, type 3, basis beams, source chunks, height terms) and leaves the main stream behind every lane;
+    // k_residual_rows and k_chi2_rows_reduce follow on it.  Host data and weights are staged first.  One synchronisation at
+    // the end brings the rows' sums, the bad-input counters and, for a host destination, the block in one copy.
+    void run_residual(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                      int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft) override {
+        check_run(t0, t1, f0, f1);
+        FV_REQUIRE(t1 > t0 && f1 > f0, "fv_sim_run_residual: empty range of times or frequencies");
+        const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
+        const size_t n = (size_t)nrows * (size_t)L;
+        const cplx<T> *dd = static_cast<const cplx<T> *>(data);
+        const T *dw = static_cast<const T *>(weights);
+        if (!data_on_device) {
+            upload(d_res_d, data, sizeof(cplx<T>) * n, 0);
+            dd = d_res_d.as<cplx<T>>();
+        }
+        if (weights && !weights_on_device) {
+            upload(d_res_w, weights, sizeof(T) * n, 0);
+            dw = d_res_w.as<T>();
+        }
+        cplx<T> *dg = static_cast<cplx<T> *>(gvis);
+        if (!gvis_on_device) {
+            d_out.reserve(std::max<size_t>(sizeof(cplx<T>) * n, 16));
+            dg = d_out.as<cplx<T>>();
+        }
+        const int nblk = residual_blocks_per_row<T>(L);
+        const size_t part_bytes = sizeof(double) * (size_t)nrows * nblk, sum_bytes = sizeof(double) * (size_t)nrows;
+        d_res_sum.reserve(part_bytes + sum_bytes + 16);
+        double *partials = d_res_sum.as<double>(), *sums = partials + (size_t)nrows * nblk;
+        int *bad = reinterpret_cast<int *>(sums + nrows);
+        run(t0, t1, f0, f1, dg, 1);
+        launch_residual<T>(stream, dg, dd, dw, nrows, L, partials, sums, bad);
+        int hbad[2] = {0, 0};
+        FV_HIP(hipMemcpyAsync(chi2_ft, sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, stream));
+        if (!gvis_on_device) FV_HIP(hipMemcpyAsync(gvis, dg, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipGetLastError());
+        if (timing_level) ev_collect();
+        {  // the staged inputs belong to this pass: beyond the keep limit they go back (fv_sim_run_adjoint's rule)
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            if ((double)(d_res_d.cap + d_res_w.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
+                d_res_d.release();
+                d_res_w.release();
+            }
+        }
+        check_errors();
+        throw_if_bad_residual_input(hbad);
     }
 
     // Height terms ("w-term expansion"): a non-coplanar array whose heights are small against the wavelength -- every

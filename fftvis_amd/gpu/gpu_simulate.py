@@ -241,6 +241,20 @@ class SimHandle:
                                                out.strides[0] // out.itemsize, int(bool(shared))))
         return out
 
+    def run_residual(self, t0, t1, f0, f1, data, weights, gvis):
+        """The fit objective of times [t0,t1) x freqs [f0,f1) (``fv_sim_run_residual``): the forward run of the block goes
+        into ``gvis`` and stays on the device, where ``gvis = 2 w (V - data)`` replaces it; returns the (f1 - f0, t1 - t0)
+        float64 host array of ``sum w |V - data|^2`` per (frequency, time).  ``data`` and ``gvis``: C-contiguous blocks of
+        ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype; ``weights``: the same shape, this engine's real
+        dtype, or None (every weight 1; 0 flags a sample).  numpy arrays are host buffers, torch tensors device buffers.
+        ``gvis`` is what every ``run_*_adjoint`` takes as ``g``.  The call synchronises."""
+        dp, d_dev = _buffer_addr(data)
+        wp, w_dev = _buffer_addr(weights)
+        gp, g_dev = _buffer_addr(gvis)
+        chi2 = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
+        _lib.check(self._L.fv_sim_run_residual(self._h, t0, t1, f0, f1, dp, d_dev, wp, w_dev, gp, g_dev, _lib.ptr(chi2)))
+        return chi2
+
     def run_adjoint(self, t0, t1, f0, f1, g, gflux, accumulate: bool):
         """``gflux += A^T g`` for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_adjoint``).  ``g``: C-contiguous block of
         ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype; ``gflux``: C-contiguous (nsrc, nfreq) real or
@@ -475,6 +489,7 @@ class GPUSimulationEngine(SimulationEngine):
         basis_tangent_of: tuple = None,
         basis_source_of: tuple = None,
         sky_of: tuple = None,
+        objective_of: tuple = None,
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -576,7 +591,28 @@ class GPUSimulationEngine(SimulationEngine):
           (``SimHandle.run_sky_adjoint``) adds the flux gradient of ``adjoint_of`` into ``gflux`` and fills the block's rows
           of ``gtopo`` as ``adjoint_wrt="sources"`` / ``basis_source_of`` do; returns ``(gflux, gtopo)``.  The pass runs the
           type-3 transform only: ValueError on the lattice path (pass ``force_use_type3=True``).
+        * ``objective_of`` (extra; what ``simulate_vis_chi2`` passes): a triple ``(data, weights, outputs)`` -- the fit
+          objective chi2 = sum w |V - data|^2 and its gradients from one handle and one set-up, V never leaving the
+          device.  ``data`` (the result's shape, this precision's complex dtype) and ``weights`` (the same shape, real, or
+          None) are numpy arrays or tensors on this device.  ``outputs`` is a dict of zeroed buffers, each optional:
+          ``"gflux"``, ``"gcoefs"``, ``"gbls"`` and ``"gtopo"`` as the modes above take them, and ``"gvis"`` (a tensor on
+          this device, the result's shape) for G = 2 w (V - data).  Per time block ``SimHandle.run_residual`` fills a device
+          block with G, then the handle passes the public functions run for the same outputs follow on it, with their
+          accumulate rule: ``run_adjoint`` for ``gflux`` alone (``adjoint_path`` honoured; the only form a lattice handle
+          takes), ``run_sky_adjoint`` for ``gflux`` with ``gtopo``, ``run_source_adjoint`` for ``gtopo`` alone,
+          ``run_position_adjoint`` for ``gbls``; with ``beam_coefs`` ``run_basis_adjoint``, ``run_basis_position_adjoint``
+          and ``run_basis_source_adjoint`` / ``run_sky_adjoint(basis=True)``, split as ``torch_simulate_vis_basis_sky``'s
+          backward splits them.  The forward and the passes share the handle: with any output but ``gflux`` the lattice
+          path is a ValueError (pass ``force_use_type3=True``).  Returns the (nfreqs, ntimes) float64 array of chi2 per
+          (frequency, time) of the block.
         """
+        if objective_of is not None:
+            if any(m is not None for m in (adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of)):
+                raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of and objective_of")
+            if len(objective_of) != 3 or not isinstance(objective_of[2], dict) or set(objective_of[2]) - set(_OBJECTIVE_OUTPUTS):
+                raise ValueError(f"objective_of: (data, weights, outputs) with outputs a dict over {_OBJECTIVE_OUTPUTS}")
+            if objective_of[2].get("gcoefs") is not None and beam_coefs is None:
+                raise ValueError("objective_of: gcoefs needs basis beams (beam_coefs)")
         if sky_of is not None:
             if adjoint_of is not None or tangent_of is not None or basis_tangent_of is not None or basis_source_of is not None:
                 raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of and sky_of")
@@ -690,6 +726,10 @@ class GPUSimulationEngine(SimulationEngine):
             raise ValueError("the source adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if sky_of is not None and is_gridded:
             raise ValueError("the sky adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
+        if objective_of is not None and is_gridded and any(
+                objective_of[2].get(k) is not None for k in ("gcoefs", "gbls", "gtopo")):
+            raise ValueError("the objective's position passes run the type-3 transform: pass force_use_type3=True on a "
+                             "lattice array")
         if tangent_of is not None and is_gridded:
             raise ValueError("the tangent runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if adjoint_path == "type2" and not is_gridded:
@@ -747,6 +787,16 @@ class GPUSimulationEngine(SimulationEngine):
                                  nsrc if coord_mgr is not None else 0)
             if coord_mgr is not None:
                 coord_mgr.setup()
+            if objective_of is not None:
+                if not use_basis:  # (a cached handle keeps its last setting)
+                    h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
+                # (a block's G, data and weights are on the device together: 2.5 blocks, 2 without weights)
+                scale = 2.0 if objective_of[1] is None else 2.5
+                nblk_t = _time_block(self.device, t1 - t0, int(np.ceil((f1 - f0) * scale)), len(baselines), polarized,
+                                     precision, nsrc if coord_mgr is not None else 0)
+                result = _run_objective(h, self.device, *objective_of, t0, t1, f0, f1, nblk_t, coord_mgr, basis=use_basis)
+                ok = True
+                return result
             if adjoint_of is not None:
                 if use_basis != (len(adjoint_of) in (3, 4)):
                     raise ValueError("adjoint_of: (g, gflux, gcoefs[, gbls]) with beam_coefs, (g, gflux) without")
@@ -1013,6 +1063,68 @@ def _run_sky_adjoint(h, g, gflux, gtopo, t0, t1, f0, f1, nblk_t, coord_mgr, basi
     if first:  # no time steps: nothing contributes
         gflux[...] = 0
     return gflux, gtopo
+
+
+_OBJECTIVE_OUTPUTS = ("gflux", "gcoefs", "gbls", "gtopo", "gvis")
+
+
+def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False):
+    """The fused objective's time loop, over the forward's blocks (and, with a coordinate manager, its streamed vectors):
+    every block's ``run_residual`` leaves G = 2 w (V - data) in a device block -- ``outputs["gvis"]`` itself when one block
+    is the whole result -- and its rows of chi2; the handle passes for the outputs given follow on that block as
+    ``_run_adjoint``, ``_run_sky_adjoint`` and ``_run_basis_source`` run them: the first block overwrites ``gflux``,
+    ``gcoefs`` and ``gbls``, later ones add, and every block fills its rows of ``gtopo``.  Returns chi2, (f1 - f0, t1 - t0)
+    float64 on the host.  Every call ends synchronised."""
+    import torch
+
+    gflux, gcoefs, gbls, gtopo, gvis = (outputs.get(k) for k in _OBJECTIVE_OUTPUTS)
+    dev = torch.device("cuda", int(device))
+    cdt = getattr(torch, np.dtype(h.cdt).name)
+
+    def block(x, tb, te):  # x's time steps [tb, te), contiguous, complete before the library reads
+        if x is None:
+            return None
+        blk = x[:, tb - t0:te - t0]
+        if isinstance(x, np.ndarray):
+            return np.ascontiguousarray(blk)
+        blk = blk.contiguous()
+        torch.cuda.synchronize(blk.device)
+        return blk
+
+    chi2 = np.zeros((f1 - f0, t1 - t0), dtype=np.float64)
+    first = True
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+        whole = tb == t0 and te == t1
+        if gvis is not None and whole:
+            g = gvis
+        else:
+            g = torch.empty(h.out_shape(te - tb, f1 - f0), dtype=cdt, device=dev)
+            torch.cuda.synchronize(dev)
+        chi2[:, tb - t0:te - t0] = h.run_residual(ta, te_, f0, f1, block(data, tb, te), block(weights, tb, te), g)
+        if gvis is not None and not whole:
+            gvis[:, tb - t0:te - t0] = g
+            torch.cuda.synchronize(dev)
+        rows = None if gtopo is None else gtopo[tb - t0:te - t0]  # (rows of a C-contiguous array: a contiguous view)
+        if gflux is not None and gtopo is not None:  # one pass for both
+            h.run_sky_adjoint(ta, te_, f0, f1, g, gflux, rows, not first, basis=basis)
+            if gcoefs is not None:
+                h.run_basis_adjoint(ta, te_, f0, f1, g, None, gcoefs, not first)
+        elif basis:
+            if gflux is not None or gcoefs is not None:
+                h.run_basis_adjoint(ta, te_, f0, f1, g, gflux, gcoefs, not first)
+            if gtopo is not None:
+                h.run_basis_source_adjoint(ta, te_, f0, f1, g, rows, False)
+        elif gflux is not None:
+            h.run_adjoint(ta, te_, f0, f1, g, gflux, not first)
+        elif gtopo is not None:
+            h.run_source_adjoint(ta, te_, f0, f1, g, rows, False)
+        if gbls is not None:
+            if basis:
+                h.run_basis_position_adjoint(ta, te_, f0, f1, g, gbls, not first)
+            else:
+                h.run_position_adjoint(ta, te_, f0, f1, g, gbls, not first)
+        first = False
+    return chi2
 
 
 def _run_basis_tangent(h, dcoefs, dv, t0, t1, f0, f1, nblk_t, coord_mgr):

@@ -80,6 +80,17 @@ int fv_beam_eval(int device, int precision, int polarized, int kind, double diam
                  int freq_index, double freq, int64_t n, const void *az, const void *za, void *out);
 int fv_apparent_coherency(int device, int precision, int variant, int64_t n, const void *beam_i,
                           const void *beam_j, const void *flux, void *out);
+/* fv_residual_chi2: the residual step of a fit on its own (the kernel pair fv_sim_run_residual queues behind its forward
+ * run).  vis, data: (nrows, row_len) complex of `precision`, C-contiguous; weights: (nrows, row_len) real of `precision`,
+ * or NULL (every weight 1).  In place  vis <- G = 2 w (vis - data):  delta = vis - data and G = 2 w delta in that
+ * precision (two roundings and an exact doubling).  chi2_rows[i] = sum over row i of w |delta|^2 with every term formed
+ * and added in fp64: per block of the row an __shfl_xor tree and a pass through LDS, the blocks' partials then added in
+ * index order -- no floating-point atomics, the same input gives the same bits.  A weight of exactly 0 flags its sample:
+ * G is exactly 0 there, nothing is added and the datum is not used (NaN or Inf there do not propagate).  A weight that
+ * is negative or not finite, and a datum that is not finite where the weight is positive, are counted in the same pass
+ * and fail the call with FV_ERR_ARG and a message that says which; vis and chi2_rows are then invalid.  Host pointers. */
+int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, void *vis, const void *data,
+                     const void *weights, double *chi2_rows);
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n);
 /* fv_astrom_topo: one time step of the device-side coordinate manager (see fv_sim_set_astrom): eq (3, n) ICRS unit
  * vectors -> topo (3, n) topocentric (east, north, up) unit vectors under one 31-double context -- what matvis'
@@ -454,6 +465,24 @@ int fv_sim_run_basis_sky_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, cons
  * runs; the handle stays usable) fail with FV_ERR_ARG.                                                                    */
 int fv_sim_run_basis_source_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *dtopo, int dtopo_on_device,
                                     void *out, int out_on_device);
+/* Fit objective of the block times [t0, t1) x freqs [f0, f1):  gvis = G = 2 w (V - data) = d chi2 / dV  and
+ * chi2_ft[(f - f0) (t1 - t0) + (t - t0)] = sum over the (time, frequency) row of w |V - data|^2,  V what fv_sim_run
+ * computes for the block -- which never leaves the device.  The call is fv_sim_run into gvis (a device buffer, or for a
+ * host destination the handle's staged block, copied back once at the end as fv_sim_run_tangent does), then the two
+ * kernels of fv_residual_chi2 on the handle's main stream behind the joined lanes, then one synchronisation that brings
+ * chi2_ft, (f1 - f0) (t1 - t0) HOST doubles.  data: fv_sim_run's layout for the block, complex of the handle's
+ * precision; weights: the same shape, real of that precision, or NULL (every weight 1); inverse variances, 0 flags a
+ * sample with fv_residual_chi2's rules (G exactly 0, the datum not used).  gvis is what every fv_sim_run_*_adjoint of
+ * this handle takes as its input.  The *_on_device flags as in fv_sim_run (device buffers must be complete when the call
+ * is made); host data and weights are staged on the device, and their bytes are given back under the
+ * FFTVIS_HIP_ADJ_KEEP_BYTES rule of fv_sim_run_adjoint.  Works on every handle fv_sim_run works on: lattice handles (the
+ * type-1 forward), basis beams, source chunks, height terms.  The rows' sums are bitwise reproducible for a given
+ * forward result.  A null handle, a null data, gvis or chi2_ft, a flag other than 0 or 1 and an empty range fail with
+ * FV_ERR_ARG before anything runs; a weight that is negative or not finite, or a datum that is not finite at a positive
+ * weight, fails the call with FV_ERR_ARG after it ran (counted by the residual kernel itself: no extra pass over data and
+ * weights): gvis and chi2_ft are then invalid and the handle stays usable.                                                */
+int fv_sim_run_residual(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                        int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2

@@ -14,6 +14,8 @@
     basis_position  forward adjoint tangent                                         C5, 8 channels
     basis_source    forward fluxes tangent_ants source_adjoint source_tangent
                     joint                                                           C5, 8 channels  (--precision)
+    objective       forward separate separate_torch fused fused_device              C3, 8 channels  (--wrt, --lattice;
+                                                                                    --config C5: through K = 4)
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -23,7 +25,12 @@ before the family's passes.  --profile PASS: one call of that pass on a cold han
 checkout whose fftvis_amd is measured (an earlier commit's, built in place; default: this one).  --array surveyed
 (position, tangent): seeded N(0, 2 cm) errors in x, y and 3 cm in z on the ideal array.  --lattice (adjoint): the
 reference's default call on a griddable array (force_use_type3=False: the forward is the type-1 transform);
---adjoint-path (adjoint): the adjoint's transform there.  A flag of another family is an error.
+--adjoint-path (adjoint): the adjoint's transform there.  objective: one iteration of a fit, chi2 = sum w |V - d|^2 and its
+gradients -- ``separate`` is simulate_vis, then numpy, then the public adjoint on the host result (runs on a checkout from
+before the fused call, as ``forward`` does: --package DIR --only forward --only separate), ``separate_torch`` the torch
+operation, a torch loss and .backward() (fluxes only), ``fused`` simulate_vis_chi2 on host data and ``fused_device`` on
+resident tensors; --wrt NAMES (comma-separated, default fluxes) selects the gradients, --lattice the type-1 forward; the
+line also holds the bytes each variant moves across PCIe per call, from the shapes.  A flag of another family is an error.
 tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
 
 import argparse
@@ -147,6 +154,63 @@ def basis_source(a, fv, cfg, rng):
         "joint": lambda: fv.simulate_vis_basis_sky_adjoint(g, **cfg, wrt=("fluxes", "topo"))}
 
 
+def objective(a, fv, cfg, rng):
+    if a.lattice:
+        cfg["force_use_type3"] = False
+    names = tuple(a.wrt.split(","))
+    basis = cfg.get("beam_coefs") is not None
+    p = cfg["precision"]
+    cdt, rdt = (np.complex64, np.float32) if p == 1 else (np.complex128, np.float64)
+    nbls = len(cfg["baselines"])
+    shape = (a.nfreq, a.ntimes, 2, 2, nbls) if cfg["polarized"] else (a.nfreq, a.ntimes, nbls)
+    d = (rng.normal(size=shape) + 1j * rng.normal(size=shape)).astype(cdt)
+    w = rng.uniform(0.5, 2.0, size=shape).astype(rdt)
+    sky = tuple(n for n in names if n in ("fluxes", "topo", "radec"))
+    rest = tuple(n for n in names if n not in sky)
+
+    def separate():
+        g = (2 * w * (fv.simulate_vis(**cfg) - d)).astype(cdt)
+        out = []
+        if sky:
+            out.append((fv.simulate_vis_basis_sky_adjoint if basis else fv.simulate_vis_sky_adjoint)(g, **cfg, wrt=sky))
+        if rest:
+            out.append((fv.simulate_vis_basis_adjoint if basis else fv.simulate_vis_position_adjoint)(g, **cfg, wrt=rest))
+        return out
+
+    calls = {"forward": lambda: fv.simulate_vis(**cfg), "separate": separate}
+    if names == ("fluxes",) and not basis:
+        def separate_torch():
+            import torch
+
+            kw = {k: v for k, v in cfg.items() if k != "fluxes"}
+            F = torch.tensor(cfg["fluxes"], dtype=torch.float64, device="cuda", requires_grad=True)
+            D, W = torch.from_numpy(d).cuda(), torch.from_numpy(w).cuda()
+            loss = (W * (fv.torch_simulate_vis(F, **kw) - D).abs() ** 2).sum()
+            loss.backward()
+            torch.cuda.synchronize()
+            return F.grad
+
+        calls["separate_torch"] = separate_torch
+    if hasattr(fv, "simulate_vis_chi2"):
+        resident = []
+
+        def fused_device():
+            import torch
+
+            if not resident:
+                resident.extend((torch.from_numpy(d).cuda(), torch.from_numpy(w).cuda()))
+                torch.cuda.synchronize()
+            return fv.simulate_vis_chi2(resident[0], **cfg, weights=resident[1], wrt=names)
+
+        calls["fused"] = lambda: fv.simulate_vis_chi2(d, **cfg, weights=w, wrt=names)
+        calls["fused_device"] = fused_device
+    head = {"config": a.config, "precision": p, "polarized": bool(cfg["polarized"]), "lattice": bool(a.lattice), "wrt": list(names),
+            # per call, from the shapes: V to the host and G back / d and w to the device / the gradients and chi2 alone
+            "pcie_bytes": {"separate": 2 * d.nbytes, "fused": d.nbytes + w.nbytes, "fused_device": 0},
+            "vis_bytes": d.nbytes}
+    return head, calls
+
+
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
 #          ratios {key: (pass, pass it is divided by -- or a tuple of passes, for their sum)})
 FAMILIES = {
@@ -165,9 +229,13 @@ FAMILIES = {
         "source_tangent_over_forward": ("source_tangent", "forward"),
         "source_tangent_over_tangent_ants": ("source_tangent", "tangent_ants"),
         "joint_over_fluxes_plus_source_adjoint": ("joint", ("fluxes", "source_adjoint"))}),
+    "objective": (objective, "C3", 8, ("lattice", "wrt"), "runs", {
+        "separate_over_forward": ("separate", "forward"), "fused_over_separate": ("fused", "separate"),
+        "fused_device_over_separate": ("fused_device", "separate"), "fused_device_over_forward": ("fused_device", "forward"),
+        "separate_torch_over_separate": ("separate_torch", "separate")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
-             "precision": 1}  # and their defaults
+             "precision": 1, "wrt": "fluxes"}  # and their defaults
 
 
 def main():
@@ -187,6 +255,7 @@ def main():
     ap.add_argument("--adjoint-path", choices=["type3", "type2", "auto"], default=None)
     ap.add_argument("--small", action="store_true", default=None, help="HERA-37, K = 3 Airy dishes, fp64")
     ap.add_argument("--ndir", type=int, default=None)
+    ap.add_argument("--wrt", default=None, help="objective: the gradients, comma-separated (default fluxes)")
     ap.add_argument("--precision", type=int, choices=[1, 2], default=None, help="2: the configuration in fp64 at eps 6e-8")
     a = ap.parse_args()
     build, config, nfreq, own, spread, ratios = FAMILIES[a.family]
