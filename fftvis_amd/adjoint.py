@@ -1773,8 +1773,8 @@ def simulate_vis_chi2(
       and is ON FOR THE WHOLE CALL otherwise: the position passes run the type-3 transform and share the handle with the
       forward, so the forward of such a call is the type-3 one (equal to the type-1 result to ``eps``).
 
-    Every other keyword means what it means for ``simulate_vis``.  Not covered: forward-mode derivatives, a tangent or
-    J^T J product in the same call, sharding over GPUs."""
+    Every other keyword means what it means for ``simulate_vis``.  Not covered: forward-mode derivatives, a tangent in
+    the same call (``simulate_vis_gauss_newton`` is the J^T W J product), sharding over GPUs."""
     args = locals()
     single = isinstance(wrt, str)
     names = (wrt,) if single else tuple(wrt)
@@ -1901,3 +1901,205 @@ def torch_simulate_vis_chi2(data, fluxes, *, weights=None, beam_coefs=None, antp
         if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
             raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
     return _function(_chi2_autograd_function).apply(fluxes, beam_coefs, antpos, radec, data, weights, antnums, kwargs)
+
+
+_GAUSS_NEWTON_NAMES = (("d_ants", "ants"), ("d_baselines", "baselines"), ("d_radec", "radec"), ("d_topo", "topo"),
+                       ("d_fluxes", "fluxes"), ("d_beam_coefs", "beam_coefs"))
+
+
+def simulate_vis_gauss_newton(
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    d_fluxes=None,
+    d_ants=None,
+    d_baselines=None,
+    d_radec=None,
+    d_topo=None,
+    d_beam_coefs=None,
+    weights=None,
+    wrt=None,
+    quad_per: str = "total",
+    return_gvis: bool = False,
+    adjoint_path: str = "type3",
+    beam_coefs=None,
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """The Gauss-Newton product in one call: with J the Jacobian of ``V = simulate_vis(ants, fluxes, ra, dec, ...)`` and
+    ``U = J p`` the tangent along the direction ``p`` given by the ``d_*`` arguments -- the sum of the tangents exactly as
+    ``simulate_vis_jvp``, ``simulate_vis_basis_jvp`` and ``simulate_vis_basis_source_jvp`` define them -- returns
+    ``(quad, prods)``, with ``return_gvis=True`` ``(quad, prods, G)``:
+
+    * ``quad = sum w |U|^2``: a Python float, or with ``quad_per="freq_time"`` the (nfreqs, ntimes) float64 array, one value
+      per (frequency, time), bitwise reproducible for given tangents (no floating-point atomics); the total is the sum of
+      that array in row-major order;
+    * ``G = 2 w U`` in ``simulate_vis``'s shape;
+    * ``prods``: the public adjoints' results for ``vis = G``, for the names in ``wrt`` -- that is ``H p`` restricted to
+      those parameter blocks, ``H = 2 J^T W J`` the Gauss-Newton Hessian of ``simulate_vis_chi2``'s chi2: ``x`` solving
+      ``H x = -grad`` is the Gauss-Newton step, and ``<p, H p> = 2 quad``.
+
+    One handle and one set-up serve every pass, and U never leaves the device: per time block every tangent pass fills a
+    device block -- the forward on ``d_fluxes``, ``fv_sim_run_basis_tangent``, ``fv_sim_run_tangent`` or
+    ``fv_sim_run_basis_position_tangent``, ``fv_sim_run_basis_source_tangent`` --, one kernel sums them in that order,
+    weights the sum into G and adds up the rows of ``quad`` (``fv_sim_weight_block``), and the handle passes of the public
+    adjoints read G where it lies, as in ``simulate_vis_chi2``.
+
+    * Directions, with the shapes and rules of the jvp functions: ``d_fluxes`` (``fluxes``' shape); ``d_ants`` (nant, 3) or
+      ``d_baselines`` (nbls, 3), not both; ``d_radec`` (nsrc, 2) -- ``coord_method="SiderealRotation"`` or device astrometry
+      -- or ``d_topo`` (ntimes, nsrc, 3), not both; ``d_beam_coefs``, complex (nant, nbasis, nfreqs), with ``beam_coefs``
+      (basis beams; ``polarized=True``) -- one direction: a stack is a ValueError.  No direction at all is a ValueError.
+    * ``weights``: None (every weight 1) or a real array of ``simulate_vis``'s output shape, inverse variances; a weight of
+      exactly 0 flags its sample (G exactly 0, nothing added, U not used there); a negative or non-finite weight fails
+      the call.
+    * ``wrt``: ``simulate_vis_chi2``'s names, rules and shapes, ``"radec"``'s coordinate rules included; ``prods`` is that
+      product, or a tuple in ``wrt``'s order.  ``wrt=None``: the names whose directions were given (``d_ants`` ->
+      ``"ants"``, ``d_baselines`` -> ``"baselines"``, ``d_radec`` -> ``"radec"``, ``d_topo`` -> ``"topo"``, ``d_fluxes`` ->
+      ``"fluxes"``, ``d_beam_coefs`` -> ``"beam_coefs"``), in that order, always a tuple.
+    * Weights and directions may be numpy arrays or torch tensors; tensors on the run's device are read by pointer
+      (``d_fluxes``, ``d_ants`` and ``d_radec`` pass through the host).  The outputs follow them as ``simulate_vis_chi2``'s
+      follow ``data``: tensors on the run's device when any of them is one, host tensors for host tensors, numpy otherwise.
+    * ``adjoint_path`` and ``force_use_type3`` are honoured when ``d_fluxes`` is the only direction and ``wrt`` is within
+      ``{"fluxes"}`` -- a lattice array then takes the type-1 forward --; with any other direction or name the whole call
+      runs the type-3 transform.
+
+    Every other keyword means what it means for ``simulate_vis``.  Not covered: the gradient in the same call
+    (``simulate_vis_chi2``), damping (``H + lambda D`` is an axpy on the host), several directions per call, torch ``hvp``,
+    sharding over GPUs."""
+    args = locals()
+    given = tuple(name for d, name in _GAUSS_NEWTON_NAMES if args[d] is not None)
+    if not given:
+        raise ValueError("simulate_vis_gauss_newton needs a direction: d_fluxes, d_ants, d_baselines, d_radec, d_topo or "
+                         "d_beam_coefs")
+    if d_ants is not None and d_baselines is not None:
+        raise ValueError("give the antenna tangent as d_ants or as d_baselines, not both")
+    if d_radec is not None and d_topo is not None:
+        raise ValueError("give the source tangent as d_radec or as d_topo, not both")
+    if wrt is None:
+        wrt = given
+    single = isinstance(wrt, str)
+    names = (wrt,) if single else tuple(wrt)
+    if names:
+        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec' and 'beam_coefs'")
+    if quad_per not in ("total", "freq_time"):
+        raise ValueError(f"quad_per must be 'total' or 'freq_time', got {quad_per!r}")
+    if adjoint_path not in ("type3", "type2", "auto"):
+        raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {adjoint_path!r}")
+    if d_beam_coefs is not None and beam_coefs is None:
+        raise ValueError("d_beam_coefs needs beam_coefs (basis beams)")
+    if "beam_coefs" in names and beam_coefs is None:
+        raise ValueError("wrt='beam_coefs' needs beam_coefs (basis beams)")
+    if beam_coefs is not None and not polarized:  # the forward's message
+        raise ValueError(
+            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
+        )
+    run = _describe_run(args)
+    run = _own_radec_chain(run, "d_radec" if d_radec is not None else "wrt='radec'", d_radec is not None or "radec" in names,
+                           "pass d_topo and ask for wrt='topo', and apply its Jacobian", "pass d_topo and ask for wrt='topo'")
+    fluxes, full_stokes = _sky_full_stokes(run, fluxes, full_stokes)
+    _host_fluxes(run, fluxes, d_fluxes)
+    d_baselines = _baseline_tangent(run, d_ants, d_baselines)
+    if d_radec is not None and tuple(d_radec.shape) != (run.nsrc, 2):
+        raise ValueError(f"d_radec must have shape ({run.nsrc}, 2), got {tuple(d_radec.shape)}")
+    if d_topo is not None and tuple(d_topo.shape) != (run.ntimes, run.nsrc, 3):
+        raise ValueError(f"d_topo must have shape ({run.ntimes}, {run.nsrc}, 3), got {tuple(d_topo.shape)}")
+    if d_beam_coefs is not None:
+        if tuple(d_beam_coefs.shape) != run.beam_coefs.shape:
+            raise ValueError(f"d_beam_coefs must be one direction of beam_coefs' shape {run.beam_coefs.shape} (a stack is not "
+                             f"covered), got {tuple(d_beam_coefs.shape)}")
+        if not (d_beam_coefs.is_complex() if _is_tensor(d_beam_coefs) else np.iscomplexobj(d_beam_coefs)):
+            raise ValueError("d_beam_coefs must be complex, like beam_coefs")
+    if weights is not None:
+        if tuple(weights.shape) != run.vis_shape:
+            raise ValueError(f"weights must have simulate_vis's output shape {run.vis_shape}, got {tuple(weights.shape)}")
+        if weights.is_complex() if _is_tensor(weights) else np.iscomplexobj(weights):
+            raise ValueError("weights must be real (inverse variances; 0 flags a sample)")
+    inputs = (d_fluxes, d_ants, d_baselines, d_radec, d_topo, d_beam_coefs, weights)
+    dev = _run_device(run, inputs, "a direction or the weights")
+    like = next((x for x in inputs if _is_tensor(x)), None)
+    if d_radec is not None:
+        d_topo = np.einsum("tjdc,jc->tjd", _radec_jacobian_of(run), _host(d_radec).astype(np.float64))
+    dc = _buffer(run, dev, d_beam_coefs, "complex")
+    directions = dict(d_fluxes=None if d_fluxes is None else _host(d_fluxes),
+                      d_beam_coefs=None if dc is None else dc.reshape((1,) + run.beam_coefs.shape),
+                      d_baselines=_buffer(run, dev, d_baselines, "float64"), d_topo=_buffer(run, dev, d_topo, "float64"))
+    f_shape = (run.nsrc, run.nfreqs)
+    gflux, gcoefs, gbls, gtopo = (None if w_ is None else _zeros(dev, w_[0], run.dtype(w_[1])) for w_ in [
+        None if "fluxes" not in names else (f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real"),
+        None if "beam_coefs" not in names else (run.beam_coefs.shape, "complex"),
+        None if "ants" not in names and "baselines" not in names else ((run.nbls, 3), "float64"),
+        None if "topo" not in names and "radec" not in names else ((run.ntimes, run.nsrc, 3), "float64")])
+    w = None
+    if weights is not None:
+        w = _host(weights).astype(run.rdt, copy=False) if dev is None or not _is_tensor(weights) or weights.device.type != "cuda" \
+            else _on(dev, weights, run.rdt)
+    gvis = None
+    if return_gvis:
+        import torch
+
+        gvis = _zeros(torch.device("cuda", int(device)), run.vis_shape, run.cdt)
+        _synchronize(gvis.device)
+    _synchronize(dev)
+    fluxes_only = given == ("fluxes",) and set(names) <= {"fluxes"}
+    quad_ft = _engine_simulate(
+        run, fluxes, force_use_type3=None if fluxes_only else True, adjoint_path=adjoint_path,
+        gauss_newton_of=(directions, w, dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis)))
+    on_device = dev is not None
+    res = {"topo": gtopo, "baselines": gbls, "beam_coefs": gcoefs}
+    if "fluxes" in names:
+        res["fluxes"] = stokes_adjoint(gflux, full_stokes)
+    if "radec" in names:
+        res["radec"] = topo_to_radec_gradient(gtopo, _radec_jacobian_of(run))
+    if "ants" in names:
+        res["ants"] = baseline_to_antenna_gradient(gbls, run.ants, run.baselines)
+    prods = _select({k: v for k, v in res.items() if k in names}, single, names, like, on_device) if names else ()
+    if quad_per == "total":
+        quad = float(np.cumsum(quad_ft.ravel())[-1]) if quad_ft.size else 0.0  # (added in row-major order)
+    else:
+        quad = quad_ft
+        if like is not None:
+            import torch
+
+            quad = torch.from_numpy(quad_ft)
+            if on_device:
+                quad = quad.to(dev)
+    if not return_gvis:
+        return quad, prods
+    if not on_device:
+        gvis = gvis.cpu().numpy()
+        if like is not None:
+            import torch
+
+            gvis = torch.from_numpy(gvis)
+    return quad, prods, gvis

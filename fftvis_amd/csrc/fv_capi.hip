@@ -359,6 +359,42 @@ static void residual_chi2_host(int device, int64_t nrows, int64_t row_len, void 
 }
 
 template <typename T>
+static void weight_rows_host(int device, int64_t nrows, int64_t row_len, int nparts, const void *const *parts, const void *weights,
+                             double *q_rows) {
+    FV_HIP(hipSetDevice(device));
+    if (nrows == 0) return;
+    if (row_len == 0) {
+        for (int64_t i = 0; i < nrows; ++i) q_rows[i] = 0.0;
+        return;
+    }
+    StreamGuard sg;
+    const size_t n = (size_t)nrows * (size_t)row_len;
+    const int nblk = residual_blocks_per_row<T>(row_len);
+    DevBuf dp[4], dw, ds;
+    cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int j = 0; j < nparts; ++j) {
+        dp[j].reserve(sizeof(cplx<T>) * n);
+        dparts[j] = dp[j].as<cplx<T>>();
+        FV_HIP(hipMemcpyAsync(dp[j].p, parts[j], sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    }
+    if (weights) {
+        dw.reserve(sizeof(T) * n);
+        FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
+    }
+    ds.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
+    double *partials = ds.as<double>(), *sums = partials + (size_t)nrows * nblk;
+    int *bad = reinterpret_cast<int *>(sums + nrows);
+    launch_weight_rows<T>(sg.s, nparts, dparts, weights ? dw.as<T>() : nullptr, nrows, row_len, partials, sums, bad);
+    int hbad[2] = {0, 0};
+    FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(q_rows, sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+    throw_if_bad_residual_input(hbad);
+}
+
+template <typename T>
 static void inplace_rot_host(int device, const double *rot, void *b, int64_t n) {
     FV_REQUIRE(rot && n >= 0 && (b || n == 0), "bad inplace_rot arrays");
     FV_HIP(hipSetDevice(device));
@@ -512,6 +548,21 @@ int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, 
     });
 }
 
+int fv_weight_rows(int device, int precision, int64_t nrows, int64_t row_len, int nparts, const void *const *parts,
+                   const void *weights, double *q_rows) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(nrows >= 0 && row_len >= 0, "fv_weight_rows: negative shape");
+        FV_REQUIRE(nparts >= 1 && nparts <= 4 && parts, "fv_weight_rows: nparts must be 1 .. 4");
+        for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts[j], "fv_weight_rows: null part");
+        FV_REQUIRE(nrows == 0 || q_rows, "fv_weight_rows: null q_rows");
+        if (precision == 2)
+            weight_rows_host<double>(device, nrows, row_len, nparts, parts, weights, q_rows);
+        else
+            weight_rows_host<float>(device, nrows, row_len, nparts, parts, weights, q_rows);
+    });
+}
+
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n) {
     return guarded([&] {
         FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
@@ -638,6 +689,17 @@ int fv_sim_run_residual(fv_sim *h, int t0, int t1, int f0, int f1, const void *d
                    "on_device flags must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_residual(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, gvis, gvis_on_device, chi2_ft);
+    });
+}
+int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,
+                        int weights_on_device, double *q_ft) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(nparts >= 1 && nparts <= 4 && parts_dev, "nparts must be 1 .. 4");
+        for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts_dev[j], "null part");
+        FV_REQUIRE(q_ft, "null q_ft");
+        FV_REQUIRE(weights_on_device == 0 || weights_on_device == 1, "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->weight_block(t0, t1, f0, f1, nparts, parts_dev, weights, weights_on_device, q_ft);
     });
 }
 int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,

@@ -1585,6 +1585,115 @@ inline void throw_if_bad_residual_input(const int bad[2]) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Gauss-Newton product (fv_weight_rows, fv_sim_weight_block; DESIGN.md "Gauss-Newton product").  The tangent J p of a
+// block arrives as NP = 1 .. 4 part blocks P_0 .. P_{NP-1} of k_residual_rows' shape (one per tangent pass); per element,
+// in the run's precision T and in this order,
+//     U = ((P_0 + P_1) + P_2) + P_3 (component-wise, only the parts given),   G = 2 (w U) (one rounding per component
+//     and an exact doubling),   row sum += w |U|^2 (every term formed and added in fp64),
+// w = 1 without weights; G replaces P_0.  w == 0 flags the sample: G = 0 exactly, nothing is added and the parts are not
+// used there (a select).  Chunks, clipping, the vector path (every part and the weights 16-byte aligned), the grid, the
+// one fp64 partial per block and the reduction (k_chi2_rows_reduce) are k_residual_rows'; bad[0] counts the weights that
+// are negative or not finite, bad[1] stays 0.
+template <typename T>
+struct WeightParts {
+    cplx<T> *p[4];
+};
+template <typename T>
+__device__ __forceinline__ double weight_element(cplx<T> &u, T w, int &bad_w) {
+    if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
+    if (!(w > (T)0)) {  // flagged (or counted above)
+        u = {(T)0, (T)0};
+        return 0.0;
+    }
+    const T ur = u.re, ui = u.im;
+    u = {(T)2 * (w * ur), (T)2 * (w * ui)};
+    return (double)w * ((double)ur * (double)ur + (double)ui * (double)ui);
+}
+template <typename T, int NP>
+__global__ void __launch_bounds__(256) k_weight_rows(WeightParts<T> parts, const T *__restrict__ weights, int64_t nrows, int64_t L,
+                                                     int vec, double *__restrict__ partials, int *__restrict__ bad) {
+    constexpr int W = RES_W<T>;
+    constexpr int NV = W * (int)sizeof(cplx<T>) / 16;  // 16-byte vectors of a part per chunk: 2
+    __shared__ double wave_sum[4];
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const int64_t lo = row * L, hi = lo + L;  // the row in the block's index
+        const int64_t c0 = lo / W;                // its first chunk
+        double s = 0.0;
+        int bad_w = 0;
+        for (int i = 0; i < RES_CHUNKS; ++i) {
+            const int64_t c = c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x;
+            const int64_t e0 = c * W;
+            if (e0 >= hi) break;
+            if (vec && e0 >= lo && e0 + W <= hi) {
+                union {
+                    uint4 q[NV];
+                    cplx<T> c[W];
+                } u, a;
+                union {
+                    uint4 q;
+                    T w[W];
+                } ww;
+#pragma unroll
+                for (int k = 0; k < NV; ++k) u.q[k] = reinterpret_cast<const uint4 *>(parts.p[0] + e0)[k];
+#pragma unroll
+                for (int j = 1; j < NP; ++j) {
+#pragma unroll
+                    for (int k = 0; k < NV; ++k) a.q[k] = reinterpret_cast<const uint4 *>(parts.p[j] + e0)[k];
+#pragma unroll
+                    for (int k = 0; k < W; ++k) u.c[k] = {u.c[k].re + a.c[k].re, u.c[k].im + a.c[k].im};
+                }
+                if (weights) ww.q = *reinterpret_cast<const uint4 *>(weights + e0);
+#pragma unroll
+                for (int k = 0; k < W; ++k) s += weight_element<T>(u.c[k], weights ? ww.w[k] : (T)1, bad_w);
+#pragma unroll
+                for (int k = 0; k < NV; ++k) reinterpret_cast<uint4 *>(parts.p[0] + e0)[k] = u.q[k];
+            } else {
+                const int64_t a = e0 > lo ? e0 : lo, b = e0 + W < hi ? e0 + W : hi;
+                for (int64_t e = a; e < b; ++e) {
+                    cplx<T> u = parts.p[0][e];
+#pragma unroll
+                    for (int j = 1; j < NP; ++j) u = {u.re + parts.p[j][e].re, u.im + parts.p[j][e].im};
+                    s += weight_element<T>(u, weights ? weights[e] : (T)1, bad_w);
+                    parts.p[0][e] = u;
+                }
+            }
+        }
+        if (bad_w) atomicAdd(bad, bad_w);
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+        __syncthreads();  // (the next row of this block writes wave_sum again)
+    }
+}
+// Queues the two kernels on `on`: parts[0 .. nparts) device blocks (nrows, L), G in place in parts[0], q_rows nrows
+// doubles, partials nrows * blocks-per-row doubles, bad two ints (zeroed here).  weights may be null.
+template <typename T>
+inline void launch_weight_rows(hipStream_t on, int nparts, cplx<T> *const *parts, const T *weights, int64_t nrows, int64_t L,
+                               double *partials, double *q_rows, int *bad) {
+    const int nblk = residual_blocks_per_row<T>(L);
+    WeightParts<T> wp{};
+    uintptr_t bits = reinterpret_cast<uintptr_t>(weights);
+    for (int j = 0; j < nparts; ++j) {
+        wp.p[j] = parts[j];
+        bits |= reinterpret_cast<uintptr_t>(parts[j]);
+    }
+    const int vec = (bits & 15) == 0;
+    const dim3 grid((unsigned)nblk, (unsigned)std::min<int64_t>(nrows, 65535));
+    FV_HIP(hipMemsetAsync(bad, 0, 2 * sizeof(int), on));
+    switch (nparts) {
+    case 1: hipLaunchKernelGGL((k_weight_rows<T, 1>), grid, dim3(256), 0, on, wp, weights, nrows, L, vec, partials, bad); break;
+    case 2: hipLaunchKernelGGL((k_weight_rows<T, 2>), grid, dim3(256), 0, on, wp, weights, nrows, L, vec, partials, bad); break;
+    case 3: hipLaunchKernelGGL((k_weight_rows<T, 3>), grid, dim3(256), 0, on, wp, weights, nrows, L, vec, partials, bad); break;
+    case 4: hipLaunchKernelGGL((k_weight_rows<T, 4>), grid, dim3(256), 0, on, wp, weights, nrows, L, vec, partials, bad); break;
+    default: throw Error(FV_ERR_ARG, "nparts must be 1 .. 4");
+    }
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
+                       q_rows);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Type-1 path (lattice arrays): cpu_nufft2d_type1 (cpu/nufft.py:120-175), set-up
 // cpu_simulate.py:661-681, per-slice :964-965,990-992,259-269.
 // Visibility of the integer baseline (bx, by) at frequency nu is mode (bx, by) of a type-1
@@ -2172,6 +2281,8 @@ struct SimBase {
     virtual void run(int t0, int t1, int f0, int f1, void *out, int out_on_device) = 0;
     virtual void run_residual(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
                               int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft) = 0;
+    virtual void weight_block(int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,
+                              int weights_on_device, double *q_ft) = 0;
     virtual void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, int accumulate) = 0;
     virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
@@ -3723,6 +3834,49 @@ class Sim : public SimBase {
         FV_HIP(hipGetLastError());
         if (timing_level) ev_collect();
         {  // the staged inputs belong to this pass: beyond the keep limit they go back (fv_sim_run_adjoint's rule)
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            if ((double)(d_res_d.cap + d_res_w.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
+                d_res_d.release();
+                d_res_w.release();
+            }
+        }
+        check_errors();
+        throw_if_bad_residual_input(hbad);
+    }
+
+    // ---- Gauss-Newton product: the tangent blocks of [t0, t1) x [f0, f1) -- nparts device blocks in run()'s layout, one
+    // per tangent pass of this handle -- become G = 2 w (sum of the parts), in place in parts_dev[0], and q_ft = the
+    // (frequency, time) rows of sum w |sum of the parts|^2 (DESIGN.md "Gauss-Newton product") -----------------------------
+    // k_weight_rows and k_chi2_rows_reduce run on the main stream, which every pass that filled a part has left behind its
+    // lanes.  Host weights are staged first and given back under run_residual's rule.  One synchronisation at the end
+    // brings the rows' sums and the bad-weight counter.
+    void weight_block(int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,
+                      int weights_on_device, double *q_ft) override {
+        check_run(t0, t1, f0, f1);
+        FV_REQUIRE(t1 > t0 && f1 > f0, "fv_sim_weight_block: empty range of times or frequencies");
+        const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
+        const size_t n = (size_t)nrows * (size_t)L;
+        const T *dw = static_cast<const T *>(weights);
+        if (weights && !weights_on_device) {
+            upload(d_res_w, weights, sizeof(T) * n, 0);
+            dw = d_res_w.as<T>();
+        }
+        cplx<T> *parts[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int j = 0; j < nparts; ++j) parts[j] = static_cast<cplx<T> *>(parts_dev[j]);
+        const int nblk = residual_blocks_per_row<T>(L);
+        const size_t part_bytes = sizeof(double) * (size_t)nrows * nblk, sum_bytes = sizeof(double) * (size_t)nrows;
+        d_res_sum.reserve(part_bytes + sum_bytes + 16);
+        double *partials = d_res_sum.as<double>(), *sums = partials + (size_t)nrows * nblk;
+        int *bad = reinterpret_cast<int *>(sums + nrows);
+        launch_weight_rows<T>(stream, nparts, parts, dw, nrows, L, partials, sums, bad);
+        int hbad[2] = {0, 0};
+        FV_HIP(hipMemcpyAsync(q_ft, sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipGetLastError());
+        if (timing_level) ev_collect();
+        {  // run_residual's rule, over the same two buffers: what a handle holds afterwards does not depend on which of the
+           // two calls came last
             const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
             if ((double)(d_res_d.cap + d_res_w.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
                 d_res_d.release();

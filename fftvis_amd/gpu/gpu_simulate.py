@@ -255,6 +255,19 @@ class SimHandle:
         _lib.check(self._L.fv_sim_run_residual(self._h, t0, t1, f0, f1, dp, d_dev, wp, w_dev, gp, g_dev, _lib.ptr(chi2)))
         return chi2
 
+    def weight_block(self, t0, t1, f0, f1, parts, weights):
+        """The weighting step of a Gauss-Newton product for times [t0,t1) x freqs [f0,f1) (``fv_sim_weight_block``):
+        ``parts`` -- one to four device tensors, each a C-contiguous block of ``out_shape(t1 - t0, f1 - f0)`` of this
+        engine's complex dtype that a forward or tangent pass of this handle filled -- are summed in order, and
+        ``parts[0] = 2 w (sum)`` replaces the first; returns the (f1 - f0, t1 - t0) float64 host array of ``sum w |sum|^2``
+        per (frequency, time).  ``weights`` as for ``run_residual``.  ``parts[0]`` is then what every ``run_*_adjoint``
+        takes as ``g``.  The call synchronises."""
+        ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
+        wp, w_dev = _buffer_addr(weights)
+        q = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
+        _lib.check(self._L.fv_sim_weight_block(self._h, t0, t1, f0, f1, len(parts), ptrs, wp, w_dev, _lib.ptr(q)))
+        return q
+
     def run_adjoint(self, t0, t1, f0, f1, g, gflux, accumulate: bool):
         """``gflux += A^T g`` for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_adjoint``).  ``g``: C-contiguous block of
         ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype; ``gflux``: C-contiguous (nsrc, nfreq) real or
@@ -490,6 +503,7 @@ class GPUSimulationEngine(SimulationEngine):
         basis_source_of: tuple = None,
         sky_of: tuple = None,
         objective_of: tuple = None,
+        gauss_newton_of: tuple = None,
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -605,7 +619,37 @@ class GPUSimulationEngine(SimulationEngine):
           backward splits them.  The forward and the passes share the handle: with any output but ``gflux`` the lattice
           path is a ValueError (pass ``force_use_type3=True``).  Returns the (nfreqs, ntimes) float64 array of chi2 per
           (frequency, time) of the block.
+        * ``gauss_newton_of`` (extra; what ``simulate_vis_gauss_newton`` passes): a triple ``(directions, weights, outputs)``
+          -- the Gauss-Newton product H p, H = 2 J^T W J, from one handle and one set-up, the tangent U = J p never
+          leaving the device.  ``directions`` is a dict, each entry optional, at least one given: ``"d_fluxes"`` (a host
+          array of ``fluxes``' shape), ``"d_beam_coefs"`` ((1, nant, nbasis, nfreqs) complex; needs ``beam_coefs``),
+          ``"d_baselines"`` ((nbls, 3) float64) and ``"d_topo"`` ((ntimes, nsrc, 3) float64), the last three numpy arrays
+          or tensors on this device.  ``weights`` and ``outputs`` as for ``objective_of``; ``"gvis"`` receives
+          G = 2 w U.  Per time block one device block per direction is filled, in this order: the forward
+          (``SimHandle.run_device``) with the catalog's fluxes replaced by ``d_fluxes`` -- ``set_sources`` before and,
+          with the real fluxes, after it, so every other pass sees the forward's --, ``run_basis_tangent``,
+          ``run_tangent`` (``d_baselines`` and ``d_topo`` in one call) or with ``beam_coefs`` ``run_basis_position_tangent``,
+          and with ``beam_coefs`` ``run_basis_source_tangent``.  ``SimHandle.weight_block`` sums them into G and the
+          rows of sum w |U|^2, and ``objective_of``'s adjoint passes follow on G with its rules: the lattice path is
+          taken by a call whose only direction is ``d_fluxes`` and whose only output is ``gflux`` (or none), a
+          ValueError for any other on a lattice array (pass ``force_use_type3=True``).  Not with ``catalog_device``.
+          Returns the (nfreqs, ntimes) float64 array of sum w |U|^2 per (frequency, time) of the block.
         """
+        if gauss_newton_of is not None:
+            if any(m is not None for m in (adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of)):
+                raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of "
+                                 "and gauss_newton_of")
+            if (len(gauss_newton_of) != 3 or not isinstance(gauss_newton_of[0], dict) or not isinstance(gauss_newton_of[2], dict)
+                    or set(gauss_newton_of[0]) - set(_GAUSS_NEWTON_DIRECTIONS) or set(gauss_newton_of[2]) - set(_OBJECTIVE_OUTPUTS)):
+                raise ValueError(f"gauss_newton_of: (directions, weights, outputs) with directions a dict over "
+                                 f"{_GAUSS_NEWTON_DIRECTIONS} and outputs a dict over {_OBJECTIVE_OUTPUTS}")
+            if all(gauss_newton_of[0].get(k) is None for k in _GAUSS_NEWTON_DIRECTIONS):
+                raise ValueError("gauss_newton_of: no direction given")
+            if beam_coefs is None and (gauss_newton_of[0].get("d_beam_coefs") is not None
+                                       or gauss_newton_of[2].get("gcoefs") is not None):
+                raise ValueError("gauss_newton_of: d_beam_coefs and gcoefs need basis beams (beam_coefs)")
+            if catalog_device is not None:
+                raise ValueError("gauss_newton_of does not take a device-resident catalog (catalog_device)")
         if objective_of is not None:
             if any(m is not None for m in (adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of)):
                 raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of and objective_of")
@@ -730,6 +774,11 @@ class GPUSimulationEngine(SimulationEngine):
                 objective_of[2].get(k) is not None for k in ("gcoefs", "gbls", "gtopo")):
             raise ValueError("the objective's position passes run the type-3 transform: pass force_use_type3=True on a "
                              "lattice array")
+        if gauss_newton_of is not None and is_gridded and (
+                any(gauss_newton_of[0].get(k) is not None for k in ("d_beam_coefs", "d_baselines", "d_topo"))
+                or any(gauss_newton_of[2].get(k) is not None for k in ("gcoefs", "gbls", "gtopo"))):
+            raise ValueError("the Gauss-Newton product's position passes run the type-3 transform: pass force_use_type3=True "
+                             "on a lattice array")
         if tangent_of is not None and is_gridded:
             raise ValueError("the tangent runs the type-3 transform: pass force_use_type3=True on a lattice array")
         if adjoint_path == "type2" and not is_gridded:
@@ -795,6 +844,28 @@ class GPUSimulationEngine(SimulationEngine):
                 nblk_t = _time_block(self.device, t1 - t0, int(np.ceil((f1 - f0) * scale)), len(baselines), polarized,
                                      precision, nsrc if coord_mgr is not None else 0)
                 result = _run_objective(h, self.device, *objective_of, t0, t1, f0, f1, nblk_t, coord_mgr, basis=use_basis)
+                ok = True
+                return result
+            if gauss_newton_of is not None:
+                directions, gn_weights, gn_outputs = gauss_newton_of
+                if not use_basis:  # (a cached handle keeps its last setting)
+                    h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
+                set_fluxes = None
+                if directions.get("d_fluxes") is not None:
+                    d_coherency, _ = utils.prepare_source_catalog(np.asarray(directions["d_fluxes"]), polarized)
+                    if d_coherency.shape != coherency.shape:  # (the same shape: the same kind of sky)
+                        raise ValueError(f"d_fluxes must have fluxes' shape, got {np.shape(directions['d_fluxes'])}")
+                    eq = eq_unit_vectors(ra.astype(float), dec.astype(float))
+
+                    def set_fluxes(tangent):  # the catalog's fluxes: the direction's for the forward part, else the real ones
+                        h.set_sources(eq, d_coherency if tangent else coherency, polarized_sky)
+                # (a block's parts and weights are on the device together: one block per part, half a block of weights)
+                nparts = _gauss_newton_nparts(directions, use_basis)
+                scale = nparts + (0.0 if gn_weights is None else 0.5)
+                nblk_t = _time_block(self.device, t1 - t0, int(np.ceil((f1 - f0) * scale)), len(baselines), polarized,
+                                     precision, nsrc if coord_mgr is not None else 0)
+                result = _run_gauss_newton(h, self.device, directions, gn_weights, gn_outputs, set_fluxes, t0, t1, f0, f1,
+                                           nblk_t, coord_mgr, basis=use_basis)
                 ok = True
                 return result
             if adjoint_of is not None:
@@ -1105,26 +1176,104 @@ def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, co
             gvis[:, tb - t0:te - t0] = g
             torch.cuda.synchronize(dev)
         rows = None if gtopo is None else gtopo[tb - t0:te - t0]  # (rows of a C-contiguous array: a contiguous view)
-        if gflux is not None and gtopo is not None:  # one pass for both
-            h.run_sky_adjoint(ta, te_, f0, f1, g, gflux, rows, not first, basis=basis)
-            if gcoefs is not None:
-                h.run_basis_adjoint(ta, te_, f0, f1, g, None, gcoefs, not first)
-        elif basis:
-            if gflux is not None or gcoefs is not None:
-                h.run_basis_adjoint(ta, te_, f0, f1, g, gflux, gcoefs, not first)
-            if gtopo is not None:
-                h.run_basis_source_adjoint(ta, te_, f0, f1, g, rows, False)
-        elif gflux is not None:
-            h.run_adjoint(ta, te_, f0, f1, g, gflux, not first)
-        elif gtopo is not None:
-            h.run_source_adjoint(ta, te_, f0, f1, g, rows, False)
-        if gbls is not None:
-            if basis:
-                h.run_basis_position_adjoint(ta, te_, f0, f1, g, gbls, not first)
-            else:
-                h.run_position_adjoint(ta, te_, f0, f1, g, gbls, not first)
+        _adjoints_of_block(h, g, gflux, gcoefs, gbls, rows, ta, te_, f0, f1, first, basis)
         first = False
     return chi2
+
+
+def _adjoints_of_block(h, g, gflux, gcoefs, gbls, rows, ta, te_, f0, f1, first, basis):
+    """The handle passes of one time block for the outputs given, on the device block ``g`` (``_run_objective``,
+    ``_run_gauss_newton``): ``rows`` are the block's rows of ``gtopo``; the ``first`` block overwrites the other outputs."""
+    if gflux is not None and rows is not None:  # one pass for both
+        h.run_sky_adjoint(ta, te_, f0, f1, g, gflux, rows, not first, basis=basis)
+        if gcoefs is not None:
+            h.run_basis_adjoint(ta, te_, f0, f1, g, None, gcoefs, not first)
+    elif basis:
+        if gflux is not None or gcoefs is not None:
+            h.run_basis_adjoint(ta, te_, f0, f1, g, gflux, gcoefs, not first)
+        if rows is not None:
+            h.run_basis_source_adjoint(ta, te_, f0, f1, g, rows, False)
+    elif gflux is not None:
+        h.run_adjoint(ta, te_, f0, f1, g, gflux, not first)
+    elif rows is not None:
+        h.run_source_adjoint(ta, te_, f0, f1, g, rows, False)
+    if gbls is not None:
+        if basis:
+            h.run_basis_position_adjoint(ta, te_, f0, f1, g, gbls, not first)
+        else:
+            h.run_position_adjoint(ta, te_, f0, f1, g, gbls, not first)
+
+
+_GAUSS_NEWTON_DIRECTIONS = ("d_fluxes", "d_beam_coefs", "d_baselines", "d_topo")
+
+
+def _gauss_newton_nparts(directions, basis):
+    """Device blocks a time block of the Gauss-Newton product holds, one per tangent pass: without basis beams
+    ``d_baselines`` and ``d_topo`` share one."""
+    given = [directions.get(k) is not None for k in _GAUSS_NEWTON_DIRECTIONS]
+    return sum(given) if basis else int(given[0]) + int(given[2] or given[3])
+
+
+def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False):
+    """The Gauss-Newton product's time loop, over the forward's blocks (and, with a coordinate manager, its streamed
+    vectors).  Per block one device block per tangent pass, filled by pointer in this order: the forward on ``d_fluxes``
+    (``set_fluxes(True)`` before, ``set_fluxes(False)`` after: every other pass sees the real fluxes), ``run_basis_tangent``
+    on ``d_beam_coefs``, the position tangent on ``d_baselines`` (without basis beams ``d_topo`` rides in the same
+    ``run_tangent``), ``run_basis_source_tangent`` on ``d_topo``.  ``weight_block`` leaves G = 2 w (their sum) in the first
+    -- ``outputs["gvis"]`` itself when one block is the whole result -- and the block's rows of sum w |U|^2; the adjoint
+    passes follow on G as in ``_run_objective``.  Returns the rows, (f1 - f0, t1 - t0) float64 on the host.  Every call
+    ends synchronised."""
+    import torch
+
+    gflux, gcoefs, gbls, gtopo, gvis = (outputs.get(k) for k in _OBJECTIVE_OUTPUTS)
+    d_fluxes, d_coefs, d_bls, d_topo = (directions.get(k) for k in _GAUSS_NEWTON_DIRECTIONS)
+    dev = torch.device("cuda", int(device))
+    cdt = getattr(torch, np.dtype(h.cdt).name)
+    nparts = _gauss_newton_nparts(directions, basis)
+
+    def block(x, tb, te):  # x's time steps [tb, te), contiguous, complete before the library reads
+        if x is None:
+            return None
+        blk = x[:, tb - t0:te - t0]
+        if isinstance(x, np.ndarray):
+            return np.ascontiguousarray(blk)
+        blk = blk.contiguous()
+        torch.cuda.synchronize(blk.device)
+        return blk
+
+    quad = np.zeros((f1 - f0, t1 - t0), dtype=np.float64)
+    first = True
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+        whole = tb == t0 and te == t1
+        shape = h.out_shape(te - tb, f1 - f0)
+        parts = [gvis if gvis is not None and whole and j == 0 else torch.empty(shape, dtype=cdt, device=dev)
+                 for j in range(nparts)]
+        torch.cuda.synchronize(dev)
+        rows_in = None if d_topo is None else d_topo[tb - t0:te - t0]  # (rows of a C-contiguous array: a contiguous view)
+        todo = iter(parts)
+        if d_fluxes is not None:
+            set_fluxes(True)
+            h.run_device(ta, te_, f0, f1, next(todo).data_ptr())
+            h.sync()  # (run_device only queues: the forward has read the direction before the real fluxes come back)
+            set_fluxes(False)
+        if d_coefs is not None:
+            h.run_basis_tangent(ta, te_, f0, f1, d_coefs, next(todo))
+        if basis:
+            if d_bls is not None:
+                h.run_basis_position_tangent(ta, te_, f0, f1, d_bls, next(todo))
+            if d_topo is not None:
+                h.run_basis_source_tangent(ta, te_, f0, f1, rows_in, next(todo))
+        elif d_bls is not None or d_topo is not None:
+            h.run_tangent(ta, te_, f0, f1, d_bls, rows_in, next(todo))
+        g = parts[0]
+        quad[:, tb - t0:te - t0] = h.weight_block(ta, te_, f0, f1, parts, block(weights, tb, te))
+        if gvis is not None and not whole:
+            gvis[:, tb - t0:te - t0] = g
+            torch.cuda.synchronize(dev)
+        rows = None if gtopo is None else gtopo[tb - t0:te - t0]
+        _adjoints_of_block(h, g, gflux, gcoefs, gbls, rows, ta, te_, f0, f1, first, basis)
+        first = False
+    return quad
 
 
 def _run_basis_tangent(h, dcoefs, dv, t0, t1, f0, f1, nblk_t, coord_mgr):

@@ -91,6 +91,19 @@ int fv_apparent_coherency(int device, int precision, int variant, int64_t n, con
  * and fail the call with FV_ERR_ARG and a message that says which; vis and chi2_rows are then invalid.  Host pointers. */
 int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, void *vis, const void *data,
                      const void *weights, double *chi2_rows);
+/* fv_weight_rows: the weighting step of a Gauss-Newton product on its own (the kernel pair fv_sim_weight_block queues).
+ * parts: nparts = 1 .. 4 blocks P_0 .. P_{nparts-1}, each (nrows, row_len) complex of `precision`, C-contiguous -- the
+ * parts of a tangent J p; weights: (nrows, row_len) real of `precision`, or NULL (every weight 1).  Per element, in that
+ * precision and in this order:  U = ((P_0 + P_1) + P_2) + P_3  (component-wise, only the parts given),  G = 2 (w U)  (one
+ * rounding per component and an exact doubling), written in place into parts[0] (the other parts are read only);
+ * q_rows[i] = sum over row i of w |U|^2 with every term formed and added in fp64, reduced as fv_residual_chi2 reduces --
+ * no floating-point atomics, the same input gives the same bits.  A weight of exactly 0 flags its sample: G is exactly 0
+ * there, nothing is added and the parts are not used (NaN or Inf there do not propagate).  A weight that is negative or
+ * not finite is counted in the same pass and fails the call with FV_ERR_ARG and fv_residual_chi2's message; parts[0] and
+ * q_rows are then invalid.  nparts outside 1 .. 4, a null part and a null q_rows with nrows > 0 fail with FV_ERR_ARG
+ * before anything runs.  Host pointers. */
+int fv_weight_rows(int device, int precision, int64_t nrows, int64_t row_len, int nparts, const void *const *parts,
+                   const void *weights, double *q_rows);
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n);
 /* fv_astrom_topo: one time step of the device-side coordinate manager (see fv_sim_set_astrom): eq (3, n) ICRS unit
  * vectors -> topo (3, n) topocentric (east, north, up) unit vectors under one 31-double context -- what matvis'
@@ -483,6 +496,21 @@ int fv_sim_run_basis_source_tangent(fv_sim *h, int t0, int t1, int f0, int f1, c
  * weights): gvis and chi2_ft are then invalid and the handle stays usable.                                                */
 int fv_sim_run_residual(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
                         int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft);
+/* Gauss-Newton product of the block times [t0, t1) x freqs [f0, f1): the tangent U = J p arrives as nparts = 1 .. 4 DEVICE
+ * blocks parts_dev[j] in fv_sim_run's layout for the block, complex of the handle's precision -- what fv_sim_run and the
+ * fv_sim_run_*_tangent calls of this handle wrote with out_on_device = 1 -- and the two kernels of fv_weight_rows on the
+ * handle's main stream leave  G = 2 w U  in parts_dev[0]  and
+ * q_ft[(f - f0) (t1 - t0) + (t - t0)] = sum over the (time, frequency) row of w |U|^2,  (f1 - f0) (t1 - t0) HOST doubles,
+ * brought by the call's one synchronisation.  weights: the block's shape, real of that precision, or NULL (every weight
+ * 1); inverse variances, 0 flags a sample with fv_weight_rows' rules.  weights_on_device as in fv_sim_run_residual; host
+ * weights are staged on the device, and their bytes are given back under the FFTVIS_HIP_ADJ_KEEP_BYTES rule of
+ * fv_sim_run_adjoint.  parts_dev[0] is then what every fv_sim_run_*_adjoint of this handle takes as its input: H p of the
+ * Gauss-Newton Hessian H = 2 J^T W J of fv_sim_run_residual's chi2.  The rows' sums are bitwise reproducible for given
+ * parts.  A null handle, nparts outside 1 .. 4, a null part or q_ft, a flag other than 0 or 1 and an empty range fail with
+ * FV_ERR_ARG before anything runs; a weight that is negative or not finite fails the call with FV_ERR_ARG after it ran
+ * (counted by the kernel itself): parts_dev[0] and q_ft are then invalid and the handle stays usable.                     */
+int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,
+                        int weights_on_device, double *q_ft);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2

@@ -197,6 +197,27 @@ int main() {
         EXPECT(fv_sim_run_basis_tangent(fake, 0, 1, 0, 1, v, 2, 1, v, 0) == FV_ERR_ARG);
         EXPECT(fv_sim_run_basis_tangent(fake, 0, 1, 0, 1, v, 0, 1, v, -1) == FV_ERR_ARG);
     }
+    // and the Gauss-Newton weighting: nparts outside 1 .. 4, a null part, a null q, a negative shape, a flag other than 0 or 1
+    {
+        fv_sim *fake = reinterpret_cast<fv_sim *>(0x1);
+        const void *parts[4] = {v, v, v, v}, *hole[2] = {v, nullptr};
+        void *dparts[4] = {v, v, v, v}, *dhole[2] = {v, nullptr};
+        EXPECT(fv_weight_rows(0, 2, 1, 4, 0, parts, nullptr, v) == FV_ERR_ARG);
+        EXPECT(fv_weight_rows(0, 2, 1, 4, 5, parts, nullptr, v) == FV_ERR_ARG);
+        EXPECT(fv_weight_rows(0, 2, 1, 4, 1, nullptr, nullptr, v) == FV_ERR_ARG);
+        EXPECT(fv_weight_rows(0, 2, 1, 4, 2, hole, nullptr, v) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "null part") != nullptr);
+        EXPECT(fv_weight_rows(0, 2, 1, 4, 1, parts, nullptr, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_weight_rows(0, 2, -1, 4, 1, parts, nullptr, v) == FV_ERR_ARG);
+        EXPECT(fv_weight_rows(0, 3, 1, 4, 1, parts, nullptr, v) == FV_ERR_ARG);
+        EXPECT(fv_sim_weight_block(nullptr, 0, 1, 0, 1, 1, dparts, nullptr, 0, v) == FV_ERR_ARG);
+        EXPECT(fv_sim_weight_block(fake, 0, 1, 0, 1, 0, dparts, nullptr, 0, v) == FV_ERR_ARG);
+        EXPECT(fv_sim_weight_block(fake, 0, 1, 0, 1, 5, dparts, nullptr, 0, v) == FV_ERR_ARG);
+        EXPECT(fv_sim_weight_block(fake, 0, 1, 0, 1, 1, nullptr, nullptr, 0, v) == FV_ERR_ARG);
+        EXPECT(fv_sim_weight_block(fake, 0, 1, 0, 1, 2, dhole, nullptr, 0, v) == FV_ERR_ARG);
+        EXPECT(fv_sim_weight_block(fake, 0, 1, 0, 1, 1, dparts, nullptr, 0, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_sim_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, 2, v) == FV_ERR_ARG);
+    }
     // a call that gets past the argument checks reports the missing device as a HIP error, not a crash
     if (ndev == 0) {
         EXPECT(fv_sim_create(&h, 0, 2, 1e-6, 2.0, 1) == FV_ERR_HIP && h == nullptr);

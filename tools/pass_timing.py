@@ -16,6 +16,8 @@
                     joint                                                           C5, 8 channels  (--precision)
     objective       forward separate separate_torch fused fused_device              C3, 8 channels  (--wrt, --lattice;
                                                                                     --config C5: through K = 4)
+    gauss_newton    forward composed fused fused_device                             C3, 8 channels  (--case; beam_coefs:
+                                                                                    --config C5)
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -30,7 +32,12 @@ gradients -- ``separate`` is simulate_vis, then numpy, then the public adjoint o
 before the fused call, as ``forward`` does: --package DIR --only forward --only separate), ``separate_torch`` the torch
 operation, a torch loss and .backward() (fluxes only), ``fused`` simulate_vis_chi2 on host data and ``fused_device`` on
 resident tensors; --wrt NAMES (comma-separated, default fluxes) selects the gradients, --lattice the type-1 forward; the
-line also holds the bytes each variant moves across PCIe per call, from the shapes.  A flag of another family is an error.
+line also holds the bytes each variant moves across PCIe per call, from the shapes.  gauss_newton: one product
+2 J^T W J p of a conjugate-gradient solve -- ``composed`` is the public tangent to the host, numpy's 2 w U and the public adjoint
+on the host result (runs on a checkout from before the fused call: --package DIR --only forward --only composed), ``fused``
+simulate_vis_gauss_newton on host weights and ``fused_device`` on resident weights; --case fluxes | ants | fluxes_radec |
+beam_coefs names the direction and the products; ``--profile kernels`` runs k_weight_rows and k_residual_rows alone on the
+block's shape, six times each, alternating.  A flag of another family is an error.
 tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
 
 import argparse
@@ -211,6 +218,83 @@ def objective(a, fv, cfg, rng):
     return head, calls
 
 
+GAUSS_NEWTON_CASES = {"fluxes": ("fluxes",), "ants": ("ants",), "fluxes_radec": ("fluxes", "radec"), "beam_coefs": ("beam_coefs",)}
+
+
+def gauss_newton(a, fv, cfg, rng):
+    names = GAUSS_NEWTON_CASES[a.case]
+    basis = cfg.get("beam_coefs") is not None
+    if "radec" in names:
+        cfg["coord_method"] = "SiderealRotation"
+    p = cfg["precision"]
+    cdt, rdt = (np.complex64, np.float32) if p == 1 else (np.complex128, np.float64)
+    nbls = len(cfg["baselines"])
+    shape = (a.nfreq, a.ntimes, 2, 2, nbls) if cfg["polarized"] else (a.nfreq, a.ntimes, nbls)
+    w = rng.uniform(0.5, 2.0, size=shape).astype(rdt)
+    F = np.asarray(cfg["fluxes"])
+    dirs = {}
+    if "fluxes" in names:
+        dirs["d_fluxes"] = F * 0.3 * rng.normal(size=(F.shape[0],) + (1,) * (F.ndim - 1))
+    if "ants" in names:
+        dirs["d_ants"] = 1e-2 * rng.normal(size=(len(cfg["ants"]), 3))
+    if "radec" in names:
+        dirs["d_radec"] = 1e-3 * rng.normal(size=(F.shape[0], 2))
+    if "beam_coefs" in names:
+        c = np.shape(cfg["beam_coefs"])
+        dirs["d_beam_coefs"] = (0.1 * (rng.normal(size=c) + 1j * rng.normal(size=c))).astype(cdt)
+    sky = tuple(n for n in names if n in ("fluxes", "radec"))
+    rest = tuple(n for n in names if n not in sky)
+
+    def composed():  # the two public calls: the tangent to the host, numpy's 2 w U, the adjoint on the host result
+        # (quad is not formed: a conjugate-gradient caller has <p, H p> as a dot product of what it holds)
+        u = (fv.simulate_vis_basis_jvp if basis else fv.simulate_vis_jvp)(**cfg, **dirs)
+        g = (2 * w * u).astype(cdt)
+        out = []
+        if sky:
+            out.append((fv.simulate_vis_basis_sky_adjoint if basis else fv.simulate_vis_sky_adjoint)(g, **cfg, wrt=sky))
+        if rest:
+            out.append((fv.simulate_vis_basis_adjoint if basis else fv.simulate_vis_position_adjoint)(g, **cfg, wrt=rest))
+        return out
+
+    calls = {"forward": lambda: fv.simulate_vis(**cfg), "composed": composed}
+    if a.profile == "kernels":  # (for a kernel trace only) the two streaming kernels alone on the block's shape, alternating
+        def kernels():
+            import ctypes
+            import importlib
+
+            _lib = importlib.import_module(fv.__name__ + "._lib")
+            lib = _lib.lib()
+            rows, L = a.nfreq * a.ntimes, w.size // (a.nfreq * a.ntimes)
+            u = (rng.normal(size=(rows, L)) + 1j * rng.normal(size=(rows, L))).astype(cdt)
+            d, w2, q = u[::-1].copy(), w.reshape(rows, L), np.zeros(rows)
+            for _ in range(6):
+                part = u.copy()
+                ptrs = (ctypes.c_void_p * 1)(part.ctypes.data)
+                _lib.check(lib.fv_weight_rows(0, p, rows, L, 1, ptrs, _lib.ptr(w2), _lib.ptr(q)))
+                g = u.copy()
+                _lib.check(lib.fv_residual_chi2(0, p, rows, L, _lib.ptr(g), _lib.ptr(d), _lib.ptr(w2), _lib.ptr(q)))
+
+        calls["kernels"] = kernels
+    if hasattr(fv, "simulate_vis_gauss_newton"):
+        resident = []
+
+        def fused_device():
+            import torch
+
+            if not resident:
+                resident.append(torch.from_numpy(w).cuda())
+                torch.cuda.synchronize()
+            return fv.simulate_vis_gauss_newton(**cfg, **dirs, weights=resident[0], wrt=names)
+
+        calls["fused"] = lambda: fv.simulate_vis_gauss_newton(**cfg, **dirs, weights=w, wrt=names)
+        calls["fused_device"] = fused_device
+    vis_bytes = w.size * np.dtype(cdt).itemsize
+    head = {"config": a.config, "case": a.case, "precision": p, "polarized": bool(cfg["polarized"]), "wrt": list(names),
+            # per call, from the shapes: U to the host and G back / w to the device / the directions and products alone
+            "pcie_bytes": {"composed": 2 * vis_bytes, "fused": w.nbytes, "fused_device": 0}, "vis_bytes": vis_bytes}
+    return head, calls
+
+
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
 #          ratios {key: (pass, pass it is divided by -- or a tuple of passes, for their sum)})
 FAMILIES = {
@@ -233,9 +317,12 @@ FAMILIES = {
         "separate_over_forward": ("separate", "forward"), "fused_over_separate": ("fused", "separate"),
         "fused_device_over_separate": ("fused_device", "separate"), "fused_device_over_forward": ("fused_device", "forward"),
         "separate_torch_over_separate": ("separate_torch", "separate")}),
+    "gauss_newton": (gauss_newton, "C3", 8, ("case",), "runs", {
+        "composed_over_forward": ("composed", "forward"), "fused_over_composed": ("fused", "composed"),
+        "fused_device_over_composed": ("fused_device", "composed"), "fused_device_over_forward": ("fused_device", "forward")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
-             "precision": 1, "wrt": "fluxes"}  # and their defaults
+             "precision": 1, "wrt": "fluxes", "case": "fluxes"}  # and their defaults
 
 
 def main():
@@ -257,6 +344,8 @@ def main():
     ap.add_argument("--ndir", type=int, default=None)
     ap.add_argument("--wrt", default=None, help="objective: the gradients, comma-separated (default fluxes)")
     ap.add_argument("--precision", type=int, choices=[1, 2], default=None, help="2: the configuration in fp64 at eps 6e-8")
+    ap.add_argument("--case", choices=list(GAUSS_NEWTON_CASES), default=None,
+                    help="gauss_newton: the direction and the products (default fluxes; beam_coefs: --config C5)")
     a = ap.parse_args()
     build, config, nfreq, own, spread, ratios = FAMILIES[a.family]
     for flag, default in OWN_FLAGS.items():
