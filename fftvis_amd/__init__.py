@@ -12,7 +12,8 @@ all three (``simulate_vis_jvp``), and the source positions through basis beams
 (``simulate_vis_basis_source_adjoint``, ``simulate_vis_basis_source_jvp``, ``torch_simulate_vis_basis_sky``), and the fluxes'
 and the source positions' gradients from one pass (``simulate_vis_sky_adjoint``, ``simulate_vis_basis_sky_adjoint``), and
 the fit objective with its gradients from one call that keeps the visibilities on the device (``simulate_vis_chi2``,
-``torch_simulate_vis_chi2``), and the Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the tangent
+``torch_simulate_vis_chi2``; ``simulate_vis_gain_chi2`` for uncalibrated data: per-antenna complex gains in the data model
+and their gradient), and the Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the tangent
 on the device (``simulate_vis_gauss_newton``).
 """
 
@@ -33,6 +34,7 @@ from .adjoint import (  # noqa: F401
     simulate_vis_basis_source_adjoint,
     simulate_vis_basis_source_jvp,
     simulate_vis_chi2,
+    simulate_vis_gain_chi2,
     simulate_vis_gauss_newton,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,

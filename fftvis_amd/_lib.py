@@ -42,6 +42,8 @@ SYMBOLS = {
     "fv_apparent_coherency": (c_int, [c_int, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                       c_void_p]),
     "fv_residual_chi2": (c_int, [c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_gain_residual_chi2": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
     "fv_weight_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "fv_inplace_rot": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64]),
     "fv_astrom_topo": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
@@ -67,6 +69,9 @@ SYMBOLS = {
     "fv_sim_run_into": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int]),
     "fv_sim_run_residual": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                     c_void_p]),
+    "fv_sim_set_gain_pairs": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "fv_sim_run_residual_gains": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                          c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "fv_sim_weight_block": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fv_sim_run_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int]),
     "fv_sim_set_adjoint_path": (c_int, [c_void_p, c_int]),

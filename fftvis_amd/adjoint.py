@@ -25,7 +25,9 @@ also offer to ``torch.autograd.forward_ad`` through their ``jvp``.  Basis beams 
 
 A fit's G is 2 w (V - d).  ``simulate_vis_chi2`` and ``torch_simulate_vis_chi2`` form it on the device, behind the forward
 run of the same handle (``fv_sim_run_residual``), and run the passes above on it where it lies: chi2 and its gradients
-from one call, one set-up, with the visibilities never copied to the host.
+from one call, one set-up, with the visibilities never copied to the host.  ``simulate_vis_gain_chi2`` is that
+call with ``gains=``: the data model is conj(g[a1]) g[a2] V, one complex gain per antenna, feed, channel and optionally time, applied on the device in the same
+block (``fv_sim_run_residual_gains``), and ``wrt="gains"`` gives the gradient with respect to them.
 """
 
 from __future__ import annotations
@@ -1697,7 +1699,37 @@ def torch_simulate_vis_basis_sky(fluxes, beam_coefs, radec, **kwargs):
     return _function(_basis_sky_autograd_function).apply(fluxes, beam_coefs, radec, kwargs)
 
 
-_CHI2_WRT = ("fluxes", "ants", "baselines", "topo", "radec", "beam_coefs")
+_CHI2_WRT = ("fluxes", "ants", "baselines", "topo", "radec", "beam_coefs", "gains")
+
+
+def _gain_block(run: _Run, gains) -> np.ndarray:
+    """``simulate_vis_gain_chi2``'s ``gains`` -- (nant, [2,] nfreqs[, ntimes]) complex, rows in ``ants``' order -- checked and
+    broadcast to the block layout the engine takes: (nfreqs, ntimes, nfeed, nant), C-contiguous, the run's complex dtype."""
+    g = _host(gains)
+    nant, nfeed = len(run.ants), 2 if run.args["polarized"] else 1
+    lead = (nant, 2) if nfeed == 2 else (nant,)
+    shapes = (lead + (run.nfreqs,), lead + (run.nfreqs, run.ntimes))
+    if not np.iscomplexobj(g):
+        raise ValueError("gains must be complex (one gain per antenna, feed and channel)")
+    if g.shape not in shapes:
+        raise ValueError(f"gains must have shape {shapes[0]} or {shapes[1]}, got {g.shape}")
+    if not np.isfinite(g).all():
+        raise ValueError("gains must be finite")
+    g = g.reshape(nant, nfeed, run.nfreqs, -1)
+    g = np.broadcast_to(g, (nant, nfeed, run.nfreqs, run.ntimes))
+    return np.ascontiguousarray(g.transpose(2, 3, 1, 0), dtype=run.cdt)
+
+
+def _gain_gradient(run: _Run, ggains: np.ndarray, shape) -> np.ndarray:
+    """The engine's (nfreqs, ntimes, nfeed, nant) gain gradient in the shape the gains were given in; for time-constant
+    gains the per-time gradients are added in time order."""
+    g = ggains.transpose(3, 2, 0, 1)  # (nant, nfeed, nfreqs, ntimes)
+    if len(shape) == g.ndim - (0 if run.args["polarized"] else 1):  # per-time gains
+        return np.ascontiguousarray(g).reshape(shape)
+    total = np.zeros(g.shape[:-1], dtype=np.complex128)
+    for t in range(g.shape[-1]):
+        total += g[..., t]
+    return total.reshape(shape)
 
 
 def simulate_vis_chi2(
@@ -1773,13 +1805,92 @@ def simulate_vis_chi2(
       and is ON FOR THE WHOLE CALL otherwise: the position passes run the type-3 transform and share the handle with the
       forward, so the forward of such a call is the type-3 one (equal to the type-1 result to ``eps``).
 
-    Every other keyword means what it means for ``simulate_vis``.  Not covered: forward-mode derivatives, a tangent in
-    the same call (``simulate_vis_gauss_newton`` is the J^T W J product), sharding over GPUs."""
+    Every other keyword means what it means for ``simulate_vis``.  Uncalibrated data -- per-antenna complex gains in the data
+    model, and the gradient with respect to them -- are ``simulate_vis_gain_chi2``'s, this call with ``gains=``.  Not
+    covered: forward-mode derivatives, a tangent in the same call (``simulate_vis_gauss_newton`` is the J^T W J product),
+    sharding over GPUs."""
+    own = locals()
+    if isinstance(wrt, str) or tuple(wrt):  # (its own names: "gains" is simulate_vis_gain_chi2's)
+        _parse_wrt(wrt, _CHI2_WRT[:-1], "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec' and 'beam_coefs'")
+    return simulate_vis_gain_chi2(gains=None, **own)
+
+
+def simulate_vis_gain_chi2(
+    data,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    gains,
+    weights=None,
+    wrt=("fluxes",),
+    beam_coefs=None,
+    chi2_per: str = "total",
+    return_gvis: bool = False,
+    adjoint_path: str = "type3",
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """``simulate_vis_chi2`` for uncalibrated data: one complex gain per antenna, feed, channel and optionally time in the
+    data model.  Baseline (a1, a2) is modelled as ``V' = conj(g[a1]) g[a2] V`` -- the first antenna is the conjugated one, as
+    for ``beam_coefs`` --, ``chi2 = sum w |V' - data|^2``, and ``"gains"`` is one more name ``wrt`` takes.  The product is
+    applied on the device to the block the residual kernel touches (``fv_sim_run_residual_gains``), whatever path produced
+    V; everything else -- ``data``, ``weights``, the other names of ``wrt``, ``chi2_per``, ``adjoint_path``,
+    ``force_use_type3``, the returned tuple -- is ``simulate_vis_chi2``'s, which is this call with ``gains=None``.
+
+    * ``gains``: ``(nant, nfreqs)`` or per time ``(nant, nfreqs, ntimes)``; polarized ``(nant, 2, nfreqs)`` or
+      ``(nant, 2, nfreqs, ntimes)``, one gain per feed: the polarized output ``[f, t, x, y, k]`` is multiplied by
+      ``conj(g[a1, y]) g[a2, x]``, which is what replacing each antenna's Jones matrix ``A_a[ax, feed]`` by
+      ``A_a diag(g[a])`` does.  Rows follow ``ants``' iteration order.  Complex, finite; numpy or a tensor on any device (it
+      is small and goes through the host).
+    * ``"gains"`` in ``wrt`` gives the gradient in ``gains``' own shape, complex128, in torch's convention for a complex leaf,
+      ``d chi2 = Re sum conj(grad) d gains`` (the convention of the ``beam_coefs`` gradient), following ``data`` as the
+      other gradients do; for time-constant gains it is the per-time gradients added on the host in time order.  Every
+      other gradient is its public pass's result for ``vis = G``.
+    * ``return_gvis=True`` gives that ``G = d chi2 / dV = conj(m) 2 w (V' - data)``, ``m`` the gain product -- NOT
+      ``2 w (V' - data)``.
+    * With the default ``baselines=None`` there is one baseline per redundant group and the gains applied are those of each
+      group's representative pair: a calibration passes explicit ``baselines``.
+
+    Not covered: ``simulate_vis_gauss_newton`` with gains or a gain direction, gains in ``simulate_vis`` itself, full 2x2
+    Jones (leakage) gains, sharding over GPUs."""
     args = locals()
     single = isinstance(wrt, str)
     names = (wrt,) if single else tuple(wrt)
     if names:
-        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec' and 'beam_coefs'")
+        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec', 'beam_coefs' and 'gains'")
+    if "gains" in names and gains is None:
+        raise ValueError("wrt='gains' needs gains=")
     if chi2_per not in ("total", "freq_time"):
         raise ValueError(f"chi2_per must be 'total' or 'freq_time', got {chi2_per!r}")
     if adjoint_path not in ("type3", "type2", "auto"):
@@ -1802,6 +1913,8 @@ def simulate_vis_chi2(
             raise ValueError(f"weights must have data's shape {run.vis_shape}, got {tuple(weights.shape)}")
         if weights.is_complex() if _is_tensor(weights) else np.iscomplexobj(weights):
             raise ValueError("weights must be real (inverse variances; 0 flags a sample)")
+    gain_block = None if gains is None else _gain_block(run, gains)
+    ggains = np.zeros(gain_block.shape, dtype=np.complex128) if "gains" in names else None
     f_shape = (run.nsrc, run.nfreqs)
     d, (gflux, gcoefs, gbls, gtopo), on_device = _gradient_buffers(run, data, [
         None if "fluxes" not in names else (f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real"),
@@ -1821,8 +1934,15 @@ def simulate_vis_chi2(
         _synchronize(gvis.device)
     chi2_ft = _engine_simulate(
         run, fluxes, force_use_type3=None if set(names) <= {"fluxes"} else True, adjoint_path=adjoint_path,
-        objective_of=(d, w, dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis)))
+        objective_of=(d, w, dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis)) if gains is None else
+        (d, w, dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis, ggains=ggains), gain_block))
     res = {"topo": gtopo, "baselines": gbls, "beam_coefs": gcoefs}
+    if "gains" in names:
+        res["gains"] = _gain_gradient(run, ggains, tuple(gains.shape))
+        if on_device:
+            import torch
+
+            res["gains"] = torch.from_numpy(res["gains"]).to(data.device)
     if "fluxes" in names:
         res["fluxes"] = stokes_adjoint(gflux, full_stokes)
     if "radec" in names:
@@ -1855,16 +1975,18 @@ def _chi2_autograd_function():
 
     class _SimulateVisChi2(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, fluxes, beam_coefs, antpos, radec, data, weights, antnums, kwargs):
-            inputs = (("fluxes", fluxes), ("beam_coefs", beam_coefs), ("ants", antpos), ("radec", radec))
-            wrt = tuple(n for (n, _), need in zip(inputs, ctx.needs_input_grad[:4]) if need)
+        def forward(ctx, fluxes, beam_coefs, antpos, radec, gains, data, weights, antnums, kwargs):
+            inputs = (("fluxes", fluxes), ("beam_coefs", beam_coefs), ("ants", antpos), ("radec", radec), ("gains", gains))
+            wrt = tuple(n for (n, _), need in zip(inputs, ctx.needs_input_grad[:5]) if need)
             kw = dict(kwargs)
+            call = simulate_vis_chi2
+            if gains is not None:
+                call, kw["gains"] = simulate_vis_gain_chi2, gains
             if antpos is not None:
                 kw["ants"] = _ants_of(antnums, antpos)
             if radec is not None:
                 kw.update(_radec_columns(radec))
-            chi2, grads = simulate_vis_chi2(data, fluxes=fluxes, weights=weights, beam_coefs=beam_coefs, wrt=wrt,
-                                            chi2_per="total", **kw)
+            chi2, grads = call(data, fluxes=fluxes, weights=weights, beam_coefs=beam_coefs, wrt=wrt, chi2_per="total", **kw)
             got = dict(zip(wrt, grads))
             ctx.grads = tuple(None if got.get(n) is None else _as_grad(got[n], x.device, x.dtype) for n, x in inputs)
             return torch.tensor(chi2, dtype=torch.float64, device=fluxes.device)
@@ -1887,7 +2009,9 @@ def torch_simulate_vis_chi2(data, fluxes, *, weights=None, beam_coefs=None, antp
     tensors -- tensors on the run's device stay there; every other argument is a keyword of ``simulate_vis_chi2``.  The
     forward reads ``ctx.needs_input_grad`` and makes ONE ``simulate_vis_chi2`` call with exactly the inputs that need a
     gradient, keeping the gradients; the backward pass multiplies them by the incoming scalar (once differentiable).
-    Not covered: forward-mode differentiation, double backward."""
+    ``gains=`` (``simulate_vis_gain_chi2``'s per-antenna gains, whose call the forward then makes) may be a complex tensor on any device: one that requires a
+    gradient adds ``"gains"`` to that one call and receives its ``.grad`` in its own dtype and on its own device; a
+    constant tensor or an array is passed through.  Not covered: forward-mode differentiation, double backward."""
     for taken, by in (("wrt", "what requires a gradient"), ("chi2_per", "the scalar loss"), ("return_gvis", "the scalar loss")):
         if taken in kwargs:
             raise TypeError(f"torch_simulate_vis_chi2 does not take {taken}=: {by} decides")
@@ -1900,7 +2024,9 @@ def torch_simulate_vis_chi2(data, fluxes, *, weights=None, beam_coefs=None, antp
             raise TypeError("torch_simulate_vis_chi2 takes the source positions as the tensor radec or as ra= / dec=, not both")
         if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
             raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
-    return _function(_chi2_autograd_function).apply(fluxes, beam_coefs, antpos, radec, data, weights, antnums, kwargs)
+    kwargs = dict(kwargs)
+    gains = kwargs.pop("gains", None)
+    return _function(_chi2_autograd_function).apply(fluxes, beam_coefs, antpos, radec, gains, data, weights, antnums, kwargs)
 
 
 _GAUSS_NEWTON_NAMES = (("d_ants", "ants"), ("d_baselines", "baselines"), ("d_radec", "radec"), ("d_topo", "topo"),

@@ -359,6 +359,50 @@ static void residual_chi2_host(int device, int64_t nrows, int64_t row_len, void 
 }
 
 template <typename T>
+static void gain_residual_chi2_host(int device, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1, const int *ant2,
+                                    const void *gains, void *vis, const void *data, const void *weights, double *chi2_rows,
+                                    void *ggains) {
+    const int nfeed = tpol == 4 ? 2 : 1;
+    const size_t ng = (size_t)nrows * nfeed * (size_t)nant;
+    if (nrows == 0) return;
+    if (nbls == 0) {
+        for (int64_t i = 0; i < nrows; ++i) chi2_rows[i] = 0.0;
+        if (ggains) std::memset(ggains, 0, sizeof(cplx<double>) * ng);
+        return;
+    }
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const int64_t row_len = (int64_t)tpol * nbls;
+    const size_t n = (size_t)nrows * (size_t)row_len;
+    const int nblk = residual_blocks_per_row<T>(row_len);
+    GainPairs gp;
+    gp.set(sg.s, nant, nbls, ant1, ant2);
+    DevBuf dv, dd, dw, ds, dgn, dgg;
+    dv.reserve(sizeof(cplx<T>) * n);
+    dd.reserve(sizeof(cplx<T>) * n);
+    if (weights) dw.reserve(sizeof(T) * n);
+    dgn.reserve(sizeof(cplx<T>) * ng);
+    if (ggains) dgg.reserve(sizeof(cplx<double>) * ng);
+    ds.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
+    double *partials = ds.as<double>(), *sums = partials + (size_t)nrows * nblk;
+    int *bad = reinterpret_cast<int *>(sums + nrows);
+    FV_HIP(hipMemcpyAsync(dv.p, vis, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    FV_HIP(hipMemcpyAsync(dd.p, data, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    if (weights) FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
+    FV_HIP(hipMemcpyAsync(dgn.p, gains, sizeof(cplx<T>) * ng, hipMemcpyHostToDevice, sg.s));
+    launch_gain_residual<T>(sg.s, dv.as<cplx<T>>(), dd.as<cplx<T>>(), weights ? dw.as<T>() : nullptr, dgn.as<cplx<T>>(), gp, nrows,
+                            tpol, partials, sums, bad, ggains ? dgg.as<cplx<double>>() : nullptr);
+    int hbad[2] = {0, 0};
+    FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(chi2_rows, sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    if (ggains) FV_HIP(hipMemcpyAsync(ggains, dgg.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+    throw_if_bad_residual_input(hbad);
+}
+
+template <typename T>
 static void weight_rows_host(int device, int64_t nrows, int64_t row_len, int nparts, const void *const *parts, const void *weights,
                              double *q_rows) {
     FV_HIP(hipSetDevice(device));
@@ -548,6 +592,27 @@ int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, 
     });
 }
 
+int fv_gain_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                          const int *ant2, const void *gains, void *vis, const void *data, const void *weights,
+                          double *chi2_rows, void *ggains) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_gain_residual_chi2: tpol must be 1 or 4");
+        FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_gain_residual_chi2: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_gain_residual_chi2: nant must be positive");
+        FV_REQUIRE(gains || nrows == 0, "fv_gain_residual_chi2: null gains");
+        FV_REQUIRE((nrows == 0 || nbls == 0 || (vis && data && ant1 && ant2)) && (nrows == 0 || chi2_rows),
+                   "fv_gain_residual_chi2: null pairs, vis, data or chi2_rows");
+        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
+            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                       "fv_gain_residual_chi2: antenna index outside [0, nant)");
+        if (precision == 2)
+            gain_residual_chi2_host<double>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, chi2_rows, ggains);
+        else
+            gain_residual_chi2_host<float>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, chi2_rows, ggains);
+    });
+}
+
 int fv_weight_rows(int device, int precision, int64_t nrows, int64_t row_len, int nparts, const void *const *parts,
                    const void *weights, double *q_rows) {
     return guarded([&] {  // (everything is checked before anything runs)
@@ -689,6 +754,23 @@ int fv_sim_run_residual(fv_sim *h, int t0, int t1, int f0, int f1, const void *d
                    "on_device flags must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_residual(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, gvis, gvis_on_device, chi2_ft);
+    });
+}
+int fv_sim_set_gain_pairs(fv_sim *h, int nant, const int *ant1, const int *ant2) {
+    FV_SIM_CALL(FV_REQUIRE(nant >= 1 && ant1 && ant2, "bad gain pairs"); h->impl->set_gain_pairs(nant, ant1, ant2));
+}
+int fv_sim_run_residual_gains(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                              int weights_on_device, const void *gains, int gains_on_device, void *gvis, int gvis_on_device,
+                              double *chi2_ft, void *ggains, int ggains_on_device) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(data && gains && gvis && chi2_ft, "null data, gains, gvis or chi2_ft");
+        FV_REQUIRE((data_on_device == 0 || data_on_device == 1) && (weights_on_device == 0 || weights_on_device == 1) &&
+                       (gains_on_device == 0 || gains_on_device == 1) && (gvis_on_device == 0 || gvis_on_device == 1) &&
+                       (ggains_on_device == 0 || ggains_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_residual_gains(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, gains, gains_on_device, gvis,
+                                    gvis_on_device, chi2_ft, ggains, ggains_on_device);
     });
 }
 int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,

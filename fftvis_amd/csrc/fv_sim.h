@@ -1694,6 +1694,242 @@ inline void launch_weight_rows(hipStream_t on, int nparts, cplx<T> *const *parts
 }
 
 // ---------------------------------------------------------------------------------------------
+// Per-antenna gains in the fused objective (fv_gain_residual_chi2, fv_sim_run_residual_gains; DESIGN.md "Gains").  The
+// block is k_residual_rows': nrows rows of L = tpol nbls values, element e of a row has pol = e / nbls, k = e % nbls.
+// Baseline k = (a1, a2) = (ant1[k], ant2[k]); a row's gains are nfeed nant complex values of the run's precision,
+// g[feed nant + ant], nfeed = 1 (tpol 1) or 2 (tpol 4).  Of the polarized output's two feed axes the MINOR one is
+// antenna a1's (the conjugated one; out[.., x, y, k] = (A_a1^H C A_a2)[y, x]): pol = 2 q + p with p a1's feed and q a2's.
+//     m = conj(g[a1, p]) g[a2, q],   V' = m V,   delta = V' - d,   G' = 2 (w delta),   stored G = conj(m) G',
+//     row sum += w |delta|^2,   ggains[a, f] = sum_{k: a1 = a, p = f} conj(G') g[a2, q] V + sum_{k: a2 = a, q = f} G' g[a1, p] conj(V).
+// Two kernels, no floating-point atomics.  k_gain_gradient runs first, while the block still holds V: a gather over the
+// per-antenna incidence lists (CSR; entry = 2 k + side, ascending, side 0 = "a is a1"), one wave per (row, feed, antenna),
+// lane l takes the entries l, l + 64, ... in order, everything in fp64 from the T-typed inputs, an __shfl_xor tree, one
+// complex128 per wave.  k_gain_residual_rows is k_residual_rows with the product folded in (all in T; the row sum's terms
+// in fp64): the same chunks, vector path, clipping, grid, partials and counters; a chunk finds (pol, k) of its first
+// element with one division and carries them; the row's gains are staged in LDS when they fit GAIN_LDS_BYTES.
+constexpr size_t GAIN_LDS_BYTES = 32768;
+__device__ __forceinline__ void gain_feeds(int pol, int nfeed, int &p, int &q) {  // p: a1's feed, q: a2's
+    p = nfeed == 2 ? (pol & 1) : 0;
+    q = nfeed == 2 ? (pol >> 1) : 0;
+}
+template <typename T>
+__device__ __forceinline__ double gain_residual_element(cplx<T> &v, const cplx<T> &d, T w, const cplx<T> &g1, const cplx<T> &g2,
+                                                        int &bad_w, int &bad_d) {
+    if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
+    if (!(w > (T)0)) {  // flagged (or counted above)
+        v = {(T)0, (T)0};
+        return 0.0;
+    }
+    if (!isfinite(d.re) || !isfinite(d.im)) ++bad_d;
+    T dr, di;
+    {
+        // In T every operation rounds on its own (no contraction): the same arithmetic on any compiler, reproducible
+        // operation by operation in a test.  The products are written out: the pragma is lexical and would not reach cmul.
+#pragma clang fp contract(off)
+        const T mr = g1.re * g2.re + g1.im * g2.im, mi = g1.re * g2.im - g1.im * g2.re;  // m = conj(g1) g2
+        dr = (mr * v.re - mi * v.im) - d.re;                                             // delta = m V - d
+        di = (mr * v.im + mi * v.re) - d.im;
+        const T gr = (T)2 * (w * dr), gi = (T)2 * (w * di);  // G'
+        v = {mr * gr + mi * gi, mr * gi - mi * gr};          // conj(m) G'
+    }
+    // (residual_element's expression, compiled as it is there: with unit gains the two kernels give the same bits)
+    return (double)w * ((double)dr * (double)dr + (double)di * (double)di);
+}
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_gain_residual_rows(cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
+                         const cplx<T> *__restrict__ gains, const int *__restrict__ ant1, const int *__restrict__ ant2,
+                         int64_t nrows, int nbls, int tpol, int nant, int in_lds, int vec, double *__restrict__ partials,
+                         int *__restrict__ bad) {
+    constexpr int W = RES_W<T>;
+    constexpr int NV = W * (int)sizeof(cplx<T>) / 16;  // 16-byte vectors of V (and of d) per chunk: 2
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    __shared__ double wave_sum[4];
+    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
+    const int64_t L = (int64_t)tpol * nbls;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<T> *g = gains + row * ng;
+        if (in_lds) {
+            cplx<T> *gl = reinterpret_cast<cplx<T> *>(gain_lds);
+            for (int i = threadIdx.x; i < ng; i += 256) gl[i] = g[i];
+            g = gl;
+            __syncthreads();
+        }
+        const int64_t lo = row * L, hi = lo + L;  // the row in the block's index
+        const int64_t c0 = lo / W;                // its first chunk
+        double s = 0.0;
+        int bad_w = 0, bad_d = 0;
+        for (int i = 0; i < RES_CHUNKS; ++i) {
+            const int64_t c = c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x;
+            const int64_t e0 = c * W;
+            if (e0 >= hi) break;
+            const int64_t a = e0 > lo ? e0 : lo, b = e0 + W < hi ? e0 + W : hi;
+            int pol = (int)((a - lo) / nbls), k = (int)((a - lo) - (int64_t)pol * nbls);  // of element a; carried below
+            int p, q;
+            gain_feeds(pol, nfeed, p, q);
+            if (vec && e0 >= lo && e0 + W <= hi) {
+                union {
+                    uint4 q[NV];
+                    cplx<T> c[W];
+                } v, d;
+                union {
+                    uint4 q;
+                    T w[W];
+                } ww;
+#pragma unroll
+                for (int j = 0; j < NV; ++j) {
+                    v.q[j] = reinterpret_cast<const uint4 *>(vis + e0)[j];
+                    d.q[j] = reinterpret_cast<const uint4 *>(data + e0)[j];
+                }
+                if (weights) ww.q = *reinterpret_cast<const uint4 *>(weights + e0);
+#pragma unroll
+                for (int j = 0; j < W; ++j) {
+                    s += gain_residual_element<T>(v.c[j], d.c[j], weights ? ww.w[j] : (T)1, g[p * nant + ant1[k]],
+                                                  g[q * nant + ant2[k]], bad_w, bad_d);
+                    if (++k == nbls) {
+                        k = 0;
+                        gain_feeds(++pol, nfeed, p, q);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < NV; ++j) reinterpret_cast<uint4 *>(vis + e0)[j] = v.q[j];
+            } else {
+                for (int64_t e = a; e < b; ++e) {
+                    cplx<T> v = vis[e];
+                    s += gain_residual_element<T>(v, data[e], weights ? weights[e] : (T)1, g[p * nant + ant1[k]],
+                                                  g[q * nant + ant2[k]], bad_w, bad_d);
+                    vis[e] = v;
+                    if (++k == nbls) {
+                        k = 0;
+                        gain_feeds(++pol, nfeed, p, q);
+                    }
+                }
+            }
+        }
+        if (bad_w) atomicAdd(bad, bad_w);
+        if (bad_d) atomicAdd(bad + 1, bad_d);
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+        __syncthreads();  // (the next row of this block writes wave_sum and the staged gains again)
+    }
+}
+// ggains[(row nfeed + feed) nant + a]: one wave per (row, feed, antenna); see above.  vis still holds V.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_gain_gradient(const cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
+                    const cplx<T> *__restrict__ gains, const int *__restrict__ ant1, const int *__restrict__ ant2,
+                    const int *__restrict__ inc_off, const int *__restrict__ inc, int64_t nrows, int nbls, int tpol, int nant,
+                    cplx<double> *__restrict__ ggains) {
+    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
+    const int wave = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (wave >= ng) return;  // (whole waves: the tree below stays inside one)
+    const int feed = wave / nant, ant = wave - feed * nant;
+    const int i0 = inc_off[ant], i1 = inc_off[ant + 1];
+    const int64_t L = (int64_t)tpol * nbls;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<T> *g = gains + row * ng;
+        double sr = 0.0, si = 0.0;
+        for (int i = i0 + lane; i < i1; i += 64) {
+            const int k = inc[i] >> 1, side = inc[i] & 1;
+            const int a1 = ant1[k], a2 = ant2[k];
+            for (int o = 0; o < nfeed; ++o) {  // the other antenna's feed
+                const int p = side ? o : feed, q = side ? feed : o;
+                const int64_t e = row * L + (int64_t)(nfeed == 2 ? 2 * q + p : 0) * nbls + k;
+                const T wt = weights ? weights[e] : (T)1;
+                if (!(wt > (T)0)) continue;  // flagged: nothing is added, the datum is not read
+                const cplx<double> g1 = {(double)g[p * nant + a1].re, (double)g[p * nant + a1].im};
+                const cplx<double> g2 = {(double)g[q * nant + a2].re, (double)g[q * nant + a2].im};
+                const cplx<double> v = {(double)vis[e].re, (double)vis[e].im};
+                const cplx<double> vp = cmul(cmul(cconj(g1), g2), v);
+                const double w2 = 2.0 * (double)wt;
+                const cplx<double> gp = {w2 * (vp.re - (double)data[e].re), w2 * (vp.im - (double)data[e].im)};
+                // side 0: conj(G') g2 V;  side 1: G' g1 conj(V)
+                const cplx<double> t = side ? cmul(gp, cmul(g1, cconj(v))) : cmul(cconj(gp), cmul(g2, v));
+                sr += t.re;
+                si += t.im;
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            sr += __shfl_xor(sr, off, 64);
+            si += __shfl_xor(si, off, 64);
+        }
+        if (lane == 0) ggains[(row * nfeed + feed) * nant + ant] = {sr, si};
+    }
+}
+// The per-antenna incidence lists of the pairs (ant1[k], ant2[k]), k < nbls: off[a] .. off[a + 1] are antenna a's entries
+// 2 k + side in ascending order (side 0: a is ant1[k]; an auto-correlation has both).  An index outside [0, nant) is
+// FV_ERR_ARG.
+inline void gain_incidence(int nant, int64_t nbls, const int *ant1, const int *ant2, std::vector<int> &off, std::vector<int> &inc) {
+    FV_REQUIRE(nant >= 1 && nbls >= 0 && nbls < ((int64_t)1 << 30) && (nbls == 0 || (ant1 && ant2)), "gain pairs: bad nant, nbls or null pairs");
+    for (int64_t k = 0; k < nbls; ++k)
+        FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant, "gain pairs: antenna index outside [0, nant)");
+    off.assign((size_t)nant + 1, 0);
+    for (int64_t k = 0; k < nbls; ++k) {
+        ++off[ant1[k] + 1];
+        ++off[ant2[k] + 1];
+    }
+    for (int a = 0; a < nant; ++a) off[a + 1] += off[a];
+    inc.assign((size_t)2 * nbls, 0);
+    std::vector<int> at(off.begin(), off.end() - 1);
+    for (int64_t k = 0; k < nbls; ++k) {
+        inc[at[ant1[k]]++] = (int)(2 * k);
+        inc[at[ant2[k]]++] = (int)(2 * k + 1);
+    }
+}
+// The pairs and their incidence lists on the device (one set per handle, or per fv_gain_residual_chi2 call)
+struct GainPairs {
+    DevBuf d_ant1, d_ant2, d_off, d_inc;
+    int nant = 0;
+    int64_t nbls = -1;  // -1: not set
+    void set(hipStream_t on, int nant_, int64_t nbls_, const int *ant1, const int *ant2) {
+        std::vector<int> off, inc;
+        gain_incidence(nant_, nbls_, ant1, ant2, off, inc);
+        nbls = -1;
+        const size_t nb = sizeof(int) * (size_t)nbls_;
+        d_ant1.reserve(std::max<size_t>(nb, 16));
+        d_ant2.reserve(std::max<size_t>(nb, 16));
+        d_off.reserve(sizeof(int) * off.size());
+        d_inc.reserve(std::max<size_t>(2 * nb, 16));
+        if (nb) {
+            FV_HIP(hipMemcpyAsync(d_ant1.p, ant1, nb, hipMemcpyHostToDevice, on));
+            FV_HIP(hipMemcpyAsync(d_ant2.p, ant2, nb, hipMemcpyHostToDevice, on));
+            FV_HIP(hipMemcpyAsync(d_inc.p, inc.data(), 2 * nb, hipMemcpyHostToDevice, on));
+        }
+        FV_HIP(hipMemcpyAsync(d_off.p, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, on));
+        FV_HIP(hipStreamSynchronize(on));  // (off and inc are this call's)
+        nant = nant_;
+        nbls = nbls_;
+    }
+};
+// Queues the gather (when ggains is not null), the in-place kernel and the rows' reduction on `on`: launch_residual's
+// arguments, the row's gains (nrows, nfeed nant) and the pairs; ggains (nrows, nfeed nant) complex128.  All device
+// pointers; weights and ggains may be null.
+template <typename T>
+inline void launch_gain_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *data, const T *weights, const cplx<T> *gains,
+                                 const GainPairs &gp, int64_t nrows, int tpol, double *partials, double *chi2_rows, int *bad,
+                                 cplx<double> *ggains) {
+    const int nbls = (int)gp.nbls, nant = gp.nant, ng = (tpol == 4 ? 2 : 1) * nant;
+    const int64_t L = (int64_t)tpol * nbls;
+    const int nblk = residual_blocks_per_row<T>(L);
+    const int vec = ((reinterpret_cast<uintptr_t>(vis) | reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;
+    const unsigned rows_y = (unsigned)std::min<int64_t>(nrows, 65535);
+    FV_HIP(hipMemsetAsync(bad, 0, 2 * sizeof(int), on));
+    if (ggains)
+        hipLaunchKernelGGL(k_gain_gradient<T>, dim3((unsigned)cdiv(ng, 4), rows_y), dim3(256), 0, on, (const cplx<T> *)vis, data,
+                           weights, gains, gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), gp.d_off.as<int>(), gp.d_inc.as<int>(), nrows,
+                           nbls, tpol, nant, ggains);
+    const size_t lds = sizeof(cplx<T>) * (size_t)ng;
+    const int in_lds = lds <= GAIN_LDS_BYTES;
+    hipLaunchKernelGGL(k_gain_residual_rows<T>, dim3((unsigned)nblk, rows_y), dim3(256), in_lds ? lds : 0, on, vis, data, weights,
+                       gains, gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), nrows, nbls, tpol, nant, in_lds, vec, partials, bad);
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
+                       chi2_rows);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Type-1 path (lattice arrays): cpu_nufft2d_type1 (cpu/nufft.py:120-175), set-up
 // cpu_simulate.py:661-681, per-slice :964-965,990-992,259-269.
 // Visibility of the integer baseline (bx, by) at frequency nu is mode (bx, by) of a type-1
@@ -2283,6 +2519,10 @@ struct SimBase {
                               int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft) = 0;
     virtual void weight_block(int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,
                               int weights_on_device, double *q_ft) = 0;
+    virtual void set_gain_pairs(int nant, const int *ant1, const int *ant2) = 0;
+    virtual void run_residual_gains(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                                    int weights_on_device, const void *gains, int gains_on_device, void *gvis, int gvis_on_device,
+                                    double *chi2_ft, void *ggains, int ggains_on_device) = 0;
     virtual void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, int accumulate) = 0;
     virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
@@ -2463,6 +2703,8 @@ class Sim : public SimBase {
     DevBuf d_tan_w, d_tan_dt;  // tangent: the rounds' weights (RunPlan::tan_w), host dtopo staged on the device
     DevBuf d_res_d, d_res_w;   // fused objective: host data / host weights staged on the device
     DevBuf d_res_sum;          // fused objective: the blocks' partial sums, the rows' sums and the two bad-input counters
+    DevBuf d_res_g, d_res_gg;  // gains: a block's host gains staged on the device / the gain gradient of a host destination
+    GainPairs gain_pairs;      // gains: the antenna pair of every baseline and the incidence lists (fv_sim_set_gain_pairs)
     DevBuf d_bt_d, d_bt_out;   // basis tangent: host directions D / the (ndir, ...) output of a host destination, on the device
     DevBuf d_csr_start, d_csr;  // basis mode: per antenna, its baselines as 2 b + role (k_coef_reduce)
     int nant_basis = 0;
@@ -2647,6 +2889,7 @@ class Sim : public SimBase {
         for (int64_t i = 0; i < 3 * nb; ++i) tmp[i] = (T)bls[i];
         upload(d_bls, tmp.data(), sizeof(T) * 3 * nb, 0);
         pairs.clear();
+        gain_pairs.nbls = -1;  // (the pairs belonged to the previous baselines)
     }
     // Lattice array (cpu_simulate.py:661-681): integer baselines, n_modes = 2 max|bl| + 1 and the
     // basis matrix in seconds; topo is rotated by basis^T instead of the plane rotation (:964-965).
@@ -2661,6 +2904,7 @@ class Sim : public SimBase {
         coplanar = true;
         type1 = true;
         t1_nmodes = n_modes;
+        gain_pairs.nbls = -1;  // (the pairs belonged to the previous baselines)
         h_bls.assign(3 * nb, 0.0);
         for (int64_t k = 0; k < nb; ++k) {
             FV_REQUIRE(std::abs(bls_int[k]) <= n_modes / 2 && std::abs(bls_int[nb + k]) <= n_modes / 2,
@@ -3881,6 +4125,79 @@ class Sim : public SimBase {
             if ((double)(d_res_d.cap + d_res_w.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
                 d_res_d.release();
                 d_res_w.release();
+            }
+        }
+        check_errors();
+        throw_if_bad_residual_input(hbad);
+    }
+
+    // ---- per-antenna gains in the fused objective (DESIGN.md "Gains") ----------------------------------------------------
+    // The antenna pair of every baseline of the configured array, uploaded once with the incidence lists built from them.
+    void set_gain_pairs(int nant, const int *ant1, const int *ant2) override {
+        FV_HIP(hipSetDevice(device));
+        FV_REQUIRE(nbls > 0, "fv_sim_set_gain_pairs: set the array first");
+        gain_pairs.set(stream, nant, nbls, ant1, ant2);
+    }
+    // run_residual's sequence with the gain kernels: gains is the block's (f1 - f0, t1 - t0, nfeed, nant) array of the
+    // handle's precision, ggains the same shape in complex128 or null (the gather does not run).  Host gains are staged and
+    // given back with the data and the weights; one synchronisation at the end brings everything a host asked for.
+    void run_residual_gains(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                            int weights_on_device, const void *gains, int gains_on_device, void *gvis, int gvis_on_device,
+                            double *chi2_ft, void *ggains, int ggains_on_device) override {
+        check_run(t0, t1, f0, f1);
+        FV_REQUIRE(t1 > t0 && f1 > f0, "fv_sim_run_residual_gains: empty range of times or frequencies");
+        FV_REQUIRE(gain_pairs.nbls == nbls, "fv_sim_run_residual_gains: fv_sim_set_gain_pairs first (after the array is set)");
+        const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
+        const size_t n = (size_t)nrows * (size_t)L;
+        const size_t ng = (size_t)nrows * (size_t)(tpol == 4 ? 2 : 1) * (size_t)gain_pairs.nant;
+        const cplx<T> *dd = static_cast<const cplx<T> *>(data);
+        const T *dw = static_cast<const T *>(weights);
+        const cplx<T> *dgn = static_cast<const cplx<T> *>(gains);
+        if (!data_on_device) {
+            upload(d_res_d, data, sizeof(cplx<T>) * n, 0);
+            dd = d_res_d.as<cplx<T>>();
+        }
+        if (weights && !weights_on_device) {
+            upload(d_res_w, weights, sizeof(T) * n, 0);
+            dw = d_res_w.as<T>();
+        }
+        if (!gains_on_device) {
+            upload(d_res_g, gains, sizeof(cplx<T>) * ng, 0);
+            dgn = d_res_g.as<cplx<T>>();
+        }
+        cplx<T> *dg = static_cast<cplx<T> *>(gvis);
+        if (!gvis_on_device) {
+            d_out.reserve(std::max<size_t>(sizeof(cplx<T>) * n, 16));
+            dg = d_out.as<cplx<T>>();
+        }
+        cplx<double> *dgg = static_cast<cplx<double> *>(ggains);
+        if (ggains && !ggains_on_device) {
+            d_res_gg.reserve(std::max<size_t>(sizeof(cplx<double>) * ng, 16));
+            dgg = d_res_gg.as<cplx<double>>();
+        }
+        const int nblk = residual_blocks_per_row<T>(L);
+        const size_t part_bytes = sizeof(double) * (size_t)nrows * nblk, sum_bytes = sizeof(double) * (size_t)nrows;
+        d_res_sum.reserve(part_bytes + sum_bytes + 16);
+        double *partials = d_res_sum.as<double>(), *sums = partials + (size_t)nrows * nblk;
+        int *bad = reinterpret_cast<int *>(sums + nrows);
+        run(t0, t1, f0, f1, dg, 1);
+        launch_gain_residual<T>(stream, dg, dd, dw, dgn, gain_pairs, nrows, tpol, partials, sums, bad, dgg);
+        int hbad[2] = {0, 0};
+        FV_HIP(hipMemcpyAsync(chi2_ft, sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, stream));
+        if (!gvis_on_device) FV_HIP(hipMemcpyAsync(gvis, dg, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, stream));
+        if (ggains && !ggains_on_device)
+            FV_HIP(hipMemcpyAsync(ggains, dgg, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipGetLastError());
+        if (timing_level) ev_collect();
+        {  // run_residual's rule, the staged gains and the gradient's block included
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            if ((double)(d_res_d.cap + d_res_w.cap + d_res_g.cap + d_res_gg.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
+                d_res_d.release();
+                d_res_w.release();
+                d_res_g.release();
+                d_res_gg.release();
             }
         }
         check_errors();

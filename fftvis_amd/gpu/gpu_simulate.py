@@ -255,6 +255,29 @@ class SimHandle:
         _lib.check(self._L.fv_sim_run_residual(self._h, t0, t1, f0, f1, dp, d_dev, wp, w_dev, gp, g_dev, _lib.ptr(chi2)))
         return chi2
 
+    def set_gain_pairs(self, nant, ant1_idxs, ant2_idxs):
+        """The antenna pair of every baseline, as rows of the gains ``run_gain_residual`` takes (``fv_sim_set_gain_pairs``):
+        after ``set_array`` / ``set_array_type1``, once per configured handle."""
+        a1 = np.ascontiguousarray(ant1_idxs, dtype=np.int32)
+        a2 = np.ascontiguousarray(ant2_idxs, dtype=np.int32)
+        _lib.check(self._L.fv_sim_set_gain_pairs(self._h, int(nant), _lib.ptr(a1), _lib.ptr(a2)))
+
+    def run_gain_residual(self, t0, t1, f0, f1, data, weights, gains, gvis, ggains=None):
+        """``run_residual`` with per-antenna gains (``fv_sim_run_residual_gains``; ``set_gain_pairs`` first): the data model
+        is ``V' = conj(g[a1]) g[a2] V``, ``gvis`` receives ``d chi2 / dV`` and the returned rows are
+        ``sum w |V' - data|^2``.  ``gains``: C-contiguous (f1 - f0, t1 - t0, nfeed, nant), this engine's complex dtype;
+        ``ggains``: the same shape, complex128, filled with the gradient with respect to the gains, or None (its kernel
+        does not run).  numpy arrays are host buffers, torch tensors device buffers.  The call synchronises."""
+        dp, d_dev = _buffer_addr(data)
+        wp, w_dev = _buffer_addr(weights)
+        np_, n_dev = _buffer_addr(gains)
+        gp, g_dev = _buffer_addr(gvis)
+        ggp, gg_dev = _buffer_addr(ggains)
+        chi2 = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
+        _lib.check(self._L.fv_sim_run_residual_gains(self._h, t0, t1, f0, f1, dp, d_dev, wp, w_dev, np_, n_dev, gp, g_dev,
+                                                     _lib.ptr(chi2), ggp, gg_dev))
+        return chi2
+
     def weight_block(self, t0, t1, f0, f1, parts, weights):
         """The weighting step of a Gauss-Newton product for times [t0,t1) x freqs [f0,f1) (``fv_sim_weight_block``):
         ``parts`` -- one to four device tensors, each a C-contiguous block of ``out_shape(t1 - t0, f1 - f0)`` of this
@@ -618,7 +641,11 @@ class GPUSimulationEngine(SimulationEngine):
           and ``run_basis_source_adjoint`` / ``run_sky_adjoint(basis=True)``, split as ``torch_simulate_vis_basis_sky``'s
           backward splits them.  The forward and the passes share the handle: with any output but ``gflux`` the lattice
           path is a ValueError (pass ``force_use_type3=True``).  Returns the (nfreqs, ntimes) float64 array of chi2 per
-          (frequency, time) of the block.
+          (frequency, time) of the block.  An optional fourth element ``gains`` -- a host array (nfreqs, ntimes, nfeed,
+          nant) of this precision's complex dtype, rows in ``ants``' order -- makes the data model
+          ``conj(g[a1]) g[a2] V``: ``SimHandle.run_gain_residual`` replaces ``run_residual``, G is d chi2 / dV, and
+          ``outputs["ggains"]`` (a host complex128 array of the gains' shape, optional) receives every block's rows of
+          the gain gradient.
         * ``gauss_newton_of`` (extra; what ``simulate_vis_gauss_newton`` passes): a triple ``(directions, weights, outputs)``
           -- the Gauss-Newton product H p, H = 2 J^T W J, from one handle and one set-up, the tangent U = J p never
           leaving the device.  ``directions`` is a dict, each entry optional, at least one given: ``"d_fluxes"`` (a host
@@ -653,10 +680,13 @@ class GPUSimulationEngine(SimulationEngine):
         if objective_of is not None:
             if any(m is not None for m in (adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of)):
                 raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of and objective_of")
-            if len(objective_of) != 3 or not isinstance(objective_of[2], dict) or set(objective_of[2]) - set(_OBJECTIVE_OUTPUTS):
+            if (len(objective_of) not in (3, 4) or not isinstance(objective_of[2], dict)
+                    or set(objective_of[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT}):
                 raise ValueError(f"objective_of: (data, weights, outputs) with outputs a dict over {_OBJECTIVE_OUTPUTS}")
             if objective_of[2].get("gcoefs") is not None and beam_coefs is None:
                 raise ValueError("objective_of: gcoefs needs basis beams (beam_coefs)")
+            if objective_of[2].get(_GAIN_OUTPUT) is not None and (len(objective_of) == 3 or objective_of[3] is None):
+                raise ValueError("objective_of: ggains needs the gains (a fourth element)")
         if sky_of is not None:
             if adjoint_of is not None or tangent_of is not None or basis_tangent_of is not None or basis_source_of is not None:
                 raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of and sky_of")
@@ -843,7 +873,21 @@ class GPUSimulationEngine(SimulationEngine):
                 scale = 2.0 if objective_of[1] is None else 2.5
                 nblk_t = _time_block(self.device, t1 - t0, int(np.ceil((f1 - f0) * scale)), len(baselines), polarized,
                                      precision, nsrc if coord_mgr is not None else 0)
-                result = _run_objective(h, self.device, *objective_of, t0, t1, f0, f1, nblk_t, coord_mgr, basis=use_basis)
+                obj_gains = objective_of[3] if len(objective_of) == 4 else None
+                if obj_gains is not None:
+                    # (a block's gains and their gradient add (8 + 16) nfeed nant bytes per row to the 2.5 blocks of
+                    # 8 tpol nbls: under 0.1 % once nbls >= nant, so nblk_t above stands)
+                    nfeed = 2 if polarized else 1
+                    if (not isinstance(obj_gains, np.ndarray) or obj_gains.dtype != complex_dtype
+                            or obj_gains.shape != (f1 - f0, t1 - t0, nfeed, nant)):
+                        raise ValueError(f"objective_of: gains must be a {np.dtype(complex_dtype).name} array of shape "
+                                         f"{(f1 - f0, t1 - t0, nfeed, nant)}")
+                    row = {a: i for i, a in enumerate(antnums)}  # (list.index per baseline is 0.2 s at HERA-350's 61 075)
+                    nb = len(baselines)
+                    h.set_gain_pairs(nant, np.fromiter((row[bl[0]] for bl in baselines), np.int32, count=nb),
+                                     np.fromiter((row[bl[1]] for bl in baselines), np.int32, count=nb))
+                result = _run_objective(h, self.device, *objective_of[:3], t0, t1, f0, f1, nblk_t, coord_mgr, basis=use_basis,
+                                        gains=obj_gains)
                 ok = True
                 return result
             if gauss_newton_of is not None:
@@ -1137,18 +1181,22 @@ def _run_sky_adjoint(h, g, gflux, gtopo, t0, t1, f0, f1, nblk_t, coord_mgr, basi
 
 
 _OBJECTIVE_OUTPUTS = ("gflux", "gcoefs", "gbls", "gtopo", "gvis")
+_GAIN_OUTPUT = "ggains"  # (objective_of with gains only)
 
 
-def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False):
+def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False, gains=None):
     """The fused objective's time loop, over the forward's blocks (and, with a coordinate manager, its streamed vectors):
     every block's ``run_residual`` leaves G = 2 w (V - data) in a device block -- ``outputs["gvis"]`` itself when one block
     is the whole result -- and its rows of chi2; the handle passes for the outputs given follow on that block as
     ``_run_adjoint``, ``_run_sky_adjoint`` and ``_run_basis_source`` run them: the first block overwrites ``gflux``,
-    ``gcoefs`` and ``gbls``, later ones add, and every block fills its rows of ``gtopo``.  Returns chi2, (f1 - f0, t1 - t0)
-    float64 on the host.  Every call ends synchronised."""
+    ``gcoefs`` and ``gbls``, later ones add, and every block fills its rows of ``gtopo``.  With ``gains`` (host, (f1 - f0,
+    t1 - t0, nfeed, nant)) every block's ``run_gain_residual`` takes its time steps of them instead and fills its time
+    steps of ``outputs["ggains"]``; the passes read its G unchanged.  Returns chi2, (f1 - f0, t1 - t0) float64 on the
+    host.  Every call ends synchronised."""
     import torch
 
     gflux, gcoefs, gbls, gtopo, gvis = (outputs.get(k) for k in _OBJECTIVE_OUTPUTS)
+    ggains = outputs.get(_GAIN_OUTPUT)
     dev = torch.device("cuda", int(device))
     cdt = getattr(torch, np.dtype(h.cdt).name)
 
@@ -1171,7 +1219,14 @@ def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, co
         else:
             g = torch.empty(h.out_shape(te - tb, f1 - f0), dtype=cdt, device=dev)
             torch.cuda.synchronize(dev)
-        chi2[:, tb - t0:te - t0] = h.run_residual(ta, te_, f0, f1, block(data, tb, te), block(weights, tb, te), g)
+        if gains is None:
+            chi2[:, tb - t0:te - t0] = h.run_residual(ta, te_, f0, f1, block(data, tb, te), block(weights, tb, te), g)
+        else:
+            gg = None if ggains is None else np.empty(gains[:, tb - t0:te - t0].shape, dtype=np.complex128)
+            chi2[:, tb - t0:te - t0] = h.run_gain_residual(ta, te_, f0, f1, block(data, tb, te), block(weights, tb, te),
+                                                           block(gains, tb, te), g, gg)
+            if gg is not None:
+                ggains[:, tb - t0:te - t0] = gg
         if gvis is not None and not whole:
             gvis[:, tb - t0:te - t0] = g
             torch.cuda.synchronize(dev)

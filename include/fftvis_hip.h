@@ -91,6 +91,22 @@ int fv_apparent_coherency(int device, int precision, int variant, int64_t n, con
  * and fail the call with FV_ERR_ARG and a message that says which; vis and chi2_rows are then invalid.  Host pointers. */
 int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, void *vis, const void *data,
                      const void *weights, double *chi2_rows);
+/* fv_gain_residual_chi2: fv_residual_chi2 with one complex gain per antenna and feed folded in (the kernels
+ * fv_sim_run_residual_gains queues behind its forward run).  vis, data, weights: nrows rows of tpol nbls values, element
+ * e of a row has pol = e / nbls and baseline k = e % nbls = (ant1[k], ant2[k]); gains: (nrows, nfeed, nant) complex of
+ * `precision`, nfeed = 1 for tpol = 1 and 2 for tpol = 4.  Of the two feed axes of a polarized row the minor one is the
+ * first antenna's: pol = 2 q + p, p the feed of ant1[k] and q of ant2[k].  Per element, in that precision and this order,
+ *   m = conj(g[p, ant1]) g[q, ant2],  V' = m vis,  delta = V' - data,  G' = 2 (w delta),  vis <- G = conj(m) G' = d chi2 / dV,
+ * chi2_rows[i] = sum over row i of w |delta|^2, formed, added and reduced as fv_residual_chi2 does, with its rules for
+ * flagged samples and bad input.  ggains: (nrows, nfeed, nant) complex128, or NULL (its kernel does not run):
+ *   ggains[i, f, a] = sum_{k: ant1[k] = a, p = f} conj(G') g[q, ant2] V  +  sum_{k: ant2[k] = a, q = f} G' g[p, ant1] conj(V),
+ * d chi2 = Re sum conj(ggains) dg, every term formed in fp64 from the inputs of `precision` and added in fp64 over the
+ * antenna's incidence list (ascending k, "a is ant1" first) by one wave with a fixed lane <-> entry assignment and an
+ * __shfl_xor tree -- no floating-point atomics; an antenna without a baseline gets exactly 0.  tpol not in {1, 4}, an
+ * antenna index outside [0, nant) and a null gains fail with FV_ERR_ARG before anything runs.  Host pointers. */
+int fv_gain_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                          const int *ant2, const void *gains, void *vis, const void *data, const void *weights,
+                          double *chi2_rows, void *ggains);
 /* fv_weight_rows: the weighting step of a Gauss-Newton product on its own (the kernel pair fv_sim_weight_block queues).
  * parts: nparts = 1 .. 4 blocks P_0 .. P_{nparts-1}, each (nrows, row_len) complex of `precision`, C-contiguous -- the
  * parts of a tangent J p; weights: (nrows, row_len) real of `precision`, or NULL (every weight 1).  Per element, in that
@@ -496,6 +512,22 @@ int fv_sim_run_basis_source_tangent(fv_sim *h, int t0, int t1, int f0, int f1, c
  * weights): gvis and chi2_ft are then invalid and the handle stays usable.                                                */
 int fv_sim_run_residual(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
                         int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft);
+/* The antenna pair (ant1[k], ant2[k]) of every baseline of the configured array, indices into the nant rows of the gains
+ * fv_sim_run_residual_gains takes: uploaded once, with the per-antenna incidence lists its gain gradient walks.  Call
+ * it after fv_sim_set_array / fv_sim_set_array_type1; setting other baselines invalidates it.  An index outside
+ * [0, nant) fails with FV_ERR_ARG.                                                                                        */
+int fv_sim_set_gain_pairs(fv_sim *h, int nant, const int *ant1, const int *ant2);
+/* fv_sim_run_residual with per-antenna gains: the data model is V' = conj(g[ant1]) g[ant2] V.  The call is
+ * fv_sim_run_residual's -- forward into gvis, kernels on the main stream, one synchronisation -- with the two kernels of
+ * fv_gain_residual_chi2: gvis = G = d chi2 / dV (NOT 2 w (V' - data): the gain product's transpose is applied), chi2_ft
+ * the rows of sum w |V' - data|^2.  gains: (f1 - f0, t1 - t0, nfeed, nant) complex of the handle's precision; ggains: the
+ * same shape in complex128, the gradient with respect to the gains (d chi2 = Re sum conj(ggains) dg), or NULL.  Host gains
+ * are staged and given back with host data and weights under the FFTVIS_HIP_ADJ_KEEP_BYTES rule.  A null handle, a null
+ * data, gains, gvis or chi2_ft, a flag other than 0 or 1, an empty range and missing pairs fail with FV_ERR_ARG before
+ * anything runs; bad weights and data as for fv_sim_run_residual.                                                        */
+int fv_sim_run_residual_gains(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device,
+                              const void *weights, int weights_on_device, const void *gains, int gains_on_device, void *gvis,
+                              int gvis_on_device, double *chi2_ft, void *ggains, int ggains_on_device);
 /* Gauss-Newton product of the block times [t0, t1) x freqs [f0, f1): the tangent U = J p arrives as nparts = 1 .. 4 DEVICE
  * blocks parts_dev[j] in fv_sim_run's layout for the block, complex of the handle's precision -- what fv_sim_run and the
  * fv_sim_run_*_tangent calls of this handle wrote with out_on_device = 1 -- and the two kernels of fv_weight_rows on the

@@ -14,8 +14,8 @@
     basis_position  forward adjoint tangent                                         C5, 8 channels
     basis_source    forward fluxes tangent_ants source_adjoint source_tangent
                     joint                                                           C5, 8 channels  (--precision)
-    objective       forward separate separate_torch fused fused_device              C3, 8 channels  (--wrt, --lattice;
-                                                                                    --config C5: through K = 4)
+    objective       forward separate separate_torch fused fused_device              C3, 8 channels  (--wrt, --lattice,
+                                                                                    --gains; --config C5: through K = 4)
     gauss_newton    forward composed fused fused_device                             C3, 8 channels  (--case; beam_coefs:
                                                                                     --config C5)
 
@@ -32,7 +32,11 @@ gradients -- ``separate`` is simulate_vis, then numpy, then the public adjoint o
 before the fused call, as ``forward`` does: --package DIR --only forward --only separate), ``separate_torch`` the torch
 operation, a torch loss and .backward() (fluxes only), ``fused`` simulate_vis_chi2 on host data and ``fused_device`` on
 resident tensors; --wrt NAMES (comma-separated, default fluxes) selects the gradients, --lattice the type-1 forward; the
-line also holds the bytes each variant moves across PCIe per call, from the shapes.  gauss_newton: one product
+line also holds the bytes each variant moves across PCIe per call, from the shapes; --gains puts per-antenna gains into
+the data model (``gains`` may then be one of --wrt's names): ``fused`` and ``fused_device`` call ``simulate_vis_gain_chi2`` (resident gains
+for the latter), ``separate`` becomes the forward to the host, the gain product and the loss in torch, .backward() and the
+public adjoints on the host result, and ``--profile gain_kernels`` runs the gain kernels and k_residual_rows alone on the
+block's shape, six times each, alternating.  gauss_newton: one product
 2 J^T W J p of a conjugate-gradient solve -- ``composed`` is the public tangent to the host, numpy's 2 w U and the public adjoint
 on the host result (runs on a checkout from before the fused call: --package DIR --only forward --only composed), ``fused``
 simulate_vis_gauss_newton on host weights and ``fused_device`` on resident weights; --case fluxes | ants | fluxes_radec |
@@ -185,7 +189,61 @@ def objective(a, fv, cfg, rng):
         return out
 
     calls = {"forward": lambda: fv.simulate_vis(**cfg), "separate": separate}
-    if names == ("fluxes",) and not basis:
+    gains = {}
+    if a.gains:  # per-antenna gains 1 + 0.1 N(0, 1), constant in time; "gains" may be one of --wrt's names
+        nant, nums = len(cfg["ants"]), list(cfg["ants"])
+        gshape = (nant, 2, a.nfreq) if cfg["polarized"] else (nant, a.nfreq)
+        g0 = (1 + 0.1 * (rng.normal(size=gshape) + 1j * rng.normal(size=gshape))).astype(cdt)
+        gains = {"gains": g0}
+        a1 = [nums.index(b[0]) for b in cfg["baselines"]]
+        a2 = [nums.index(b[1]) for b in cfg["baselines"]]
+        sky = tuple(n for n in sky if n != "gains")
+        rest = tuple(n for n in rest if n != "gains")
+
+        def separate():  # what a caller composes without gains=: the forward to the host, the gain product and the loss in
+            # torch, .backward() for d chi2 / dV and the gain gradient, then the public adjoints on the host result
+            import torch
+
+            V = torch.from_numpy(fv.simulate_vis(**cfg)).cuda().requires_grad_(True)
+            G = torch.from_numpy(g0).cuda().requires_grad_("gains" in names)
+            D, W = torch.from_numpy(d).cuda(), torch.from_numpy(w).cuda()
+            g1, g2 = G[a1].conj(), G[a2]  # (nbls, [2,] nf)
+            if cfg["polarized"]:  # out[f, t, x, y, k]: y is the first antenna's feed
+                m = (g2.permute(2, 1, 0)[:, :, None, :] * g1.permute(2, 1, 0)[:, None, :, :])[:, None]
+            else:
+                m = (g1 * g2).T[:, None]
+            (W * (m * V - D).abs() ** 2).sum().backward()
+            g = V.grad.cpu().numpy()
+            out = [G.grad]
+            if sky:
+                out.append((fv.simulate_vis_basis_sky_adjoint if basis else fv.simulate_vis_sky_adjoint)(g, **cfg, wrt=sky))
+            if rest:
+                out.append((fv.simulate_vis_basis_adjoint if basis else fv.simulate_vis_position_adjoint)(g, **cfg, wrt=rest))
+            return out
+
+        calls["separate"] = separate
+        if a.profile == "gain_kernels":  # (for a kernel trace only) the gain kernels and k_residual_rows alone, alternating
+            def gain_kernels():
+                import importlib
+
+                _lib = importlib.import_module(fv.__name__ + "._lib")
+                lib = _lib.lib()
+                rows, tpol = a.nfreq * a.ntimes, 4 if cfg["polarized"] else 1
+                nfeed = 2 if cfg["polarized"] else 1
+                gb = np.ascontiguousarray(np.broadcast_to(g0.reshape(nant, nfeed, a.nfreq, 1), (nant, nfeed, a.nfreq, a.ntimes))
+                                          .transpose(2, 3, 1, 0))
+                i1, i2 = np.array(a1, np.int32), np.array(a2, np.int32)
+                v0 = (rng.normal(size=(rows, tpol * nbls)) + 1j * rng.normal(size=(rows, tpol * nbls))).astype(cdt)
+                d2, w2, q, gg = d.reshape(rows, -1), w.reshape(rows, -1), np.zeros(rows), np.zeros(gb.shape, np.complex128)
+                for _ in range(6):
+                    v = v0.copy()
+                    _lib.check(lib.fv_gain_residual_chi2(0, p, rows, nbls, tpol, nant, _lib.ptr(i1), _lib.ptr(i2), _lib.ptr(gb),
+                                                         _lib.ptr(v), _lib.ptr(d2), _lib.ptr(w2), _lib.ptr(q), _lib.ptr(gg)))
+                    v = v0.copy()
+                    _lib.check(lib.fv_residual_chi2(0, p, rows, tpol * nbls, _lib.ptr(v), _lib.ptr(d2), _lib.ptr(w2), _lib.ptr(q)))
+
+            calls["gain_kernels"] = gain_kernels
+    if names == ("fluxes",) and not basis and not a.gains:
         def separate_torch():
             import torch
 
@@ -206,12 +264,18 @@ def objective(a, fv, cfg, rng):
 
             if not resident:
                 resident.extend((torch.from_numpy(d).cuda(), torch.from_numpy(w).cuda()))
+                if gains:
+                    resident.append(torch.from_numpy(gains["gains"]).cuda())
                 torch.cuda.synchronize()
+            if gains:
+                return fv.simulate_vis_gain_chi2(resident[0], **cfg, weights=resident[1], wrt=names, gains=resident[2])
             return fv.simulate_vis_chi2(resident[0], **cfg, weights=resident[1], wrt=names)
 
-        calls["fused"] = lambda: fv.simulate_vis_chi2(d, **cfg, weights=w, wrt=names)
+        chi2_call = fv.simulate_vis_gain_chi2 if gains else fv.simulate_vis_chi2
+        calls["fused"] = lambda: chi2_call(d, **cfg, weights=w, wrt=names, **gains)
         calls["fused_device"] = fused_device
     head = {"config": a.config, "precision": p, "polarized": bool(cfg["polarized"]), "lattice": bool(a.lattice), "wrt": list(names),
+            "gains": bool(a.gains),
             # per call, from the shapes: V to the host and G back / d and w to the device / the gradients and chi2 alone
             "pcie_bytes": {"separate": 2 * d.nbytes, "fused": d.nbytes + w.nbytes, "fused_device": 0},
             "vis_bytes": d.nbytes}
@@ -313,7 +377,7 @@ FAMILIES = {
         "source_tangent_over_forward": ("source_tangent", "forward"),
         "source_tangent_over_tangent_ants": ("source_tangent", "tangent_ants"),
         "joint_over_fluxes_plus_source_adjoint": ("joint", ("fluxes", "source_adjoint"))}),
-    "objective": (objective, "C3", 8, ("lattice", "wrt"), "runs", {
+    "objective": (objective, "C3", 8, ("lattice", "wrt", "gains"), "runs", {
         "separate_over_forward": ("separate", "forward"), "fused_over_separate": ("fused", "separate"),
         "fused_device_over_separate": ("fused_device", "separate"), "fused_device_over_forward": ("fused_device", "forward"),
         "separate_torch_over_separate": ("separate_torch", "separate")}),
@@ -322,7 +386,7 @@ FAMILIES = {
         "fused_device_over_composed": ("fused_device", "composed"), "fused_device_over_forward": ("fused_device", "forward")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
-             "precision": 1, "wrt": "fluxes", "case": "fluxes"}  # and their defaults
+             "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False}  # and their defaults
 
 
 def main():
@@ -343,6 +407,8 @@ def main():
     ap.add_argument("--small", action="store_true", default=None, help="HERA-37, K = 3 Airy dishes, fp64")
     ap.add_argument("--ndir", type=int, default=None)
     ap.add_argument("--wrt", default=None, help="objective: the gradients, comma-separated (default fluxes)")
+    ap.add_argument("--gains", action="store_true", default=None,
+                    help="objective: per-antenna gains in the data model (gains may then be one of --wrt's names)")
     ap.add_argument("--precision", type=int, choices=[1, 2], default=None, help="2: the configuration in fp64 at eps 6e-8")
     ap.add_argument("--case", choices=list(GAUSS_NEWTON_CASES), default=None,
                     help="gauss_newton: the direction and the products (default fluxes; beam_coefs: --config C5)")
