@@ -14,7 +14,8 @@ and the source positions' gradients from one pass (``simulate_vis_sky_adjoint``,
 the fit objective with its gradients from one call that keeps the visibilities on the device (``simulate_vis_chi2``,
 ``torch_simulate_vis_chi2``; ``simulate_vis_gain_chi2`` for uncalibrated data: per-antenna complex gains in the data model
 and their gradient), and the Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the tangent
-on the device (``simulate_vis_gauss_newton``).
+on the device (``simulate_vis_gauss_newton``; ``simulate_vis_gain_gauss_newton`` with the gains in the data model, a gain
+direction and the gain block of the product).
 """
 
 __version__ = "0.1.0"
@@ -35,6 +36,7 @@ from .adjoint import (  # noqa: F401
     simulate_vis_basis_source_jvp,
     simulate_vis_chi2,
     simulate_vis_gain_chi2,
+    simulate_vis_gain_gauss_newton,
     simulate_vis_gauss_newton,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,

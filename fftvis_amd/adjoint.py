@@ -28,6 +28,9 @@ run of the same handle (``fv_sim_run_residual``), and run the passes above on it
 from one call, one set-up, with the visibilities never copied to the host.  ``simulate_vis_gain_chi2`` is that
 call with ``gains=``: the data model is conj(g[a1]) g[a2] V, one complex gain per antenna, feed, channel and optionally time, applied on the device in the same
 block (``fv_sim_run_residual_gains``), and ``wrt="gains"`` gives the gradient with respect to them.
+``simulate_vis_gauss_newton`` is the Gauss-Newton product 2 J^T W J p of that chi2 from one call that keeps the tangent on
+the device (``fv_sim_weight_block``), and ``simulate_vis_gain_gauss_newton`` that product with the gains in the data model,
+a gain direction and the gain block of the product (``fv_sim_gain_weight_block``).
 """
 
 from __future__ import annotations
@@ -1882,8 +1885,8 @@ def simulate_vis_gain_chi2(
     * With the default ``baselines=None`` there is one baseline per redundant group and the gains applied are those of each
       group's representative pair: a calibration passes explicit ``baselines``.
 
-    Not covered: ``simulate_vis_gauss_newton`` with gains or a gain direction, gains in ``simulate_vis`` itself, full 2x2
-    Jones (leakage) gains, sharding over GPUs."""
+    The Gauss-Newton product of this chi2 is ``simulate_vis_gain_gauss_newton``'s (``simulate_vis_gauss_newton`` itself
+    takes no gains).  Not covered: gains in ``simulate_vis`` itself, full 2x2 Jones (leakage) gains, sharding over GPUs."""
     args = locals()
     single = isinstance(wrt, str)
     names = (wrt,) if single else tuple(wrt)
@@ -2120,12 +2123,103 @@ def simulate_vis_gauss_newton(
       ``{"fluxes"}`` -- a lattice array then takes the type-1 forward --; with any other direction or name the whole call
       runs the type-3 transform.
 
-    Every other keyword means what it means for ``simulate_vis``.  Not covered: the gradient in the same call
+    Every other keyword means what it means for ``simulate_vis``.  Uncalibrated data -- per-antenna gains in the data
+    model, a gain direction and the gain block of ``H p`` -- are ``simulate_vis_gain_gauss_newton``'s, this call with
+    ``gains=`` and ``d_gains=``.  Not covered: the gradient in the same call
     (``simulate_vis_chi2``), damping (``H + lambda D`` is an axpy on the host), several directions per call, torch ``hvp``,
     sharding over GPUs."""
+    own = locals()
+    if wrt is not None and (isinstance(wrt, str) or tuple(wrt)):  # (its own names: "gains" is simulate_vis_gain_gauss_newton's)
+        _parse_wrt(wrt, _CHI2_WRT[:-1], "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec' and 'beam_coefs'")
+    return simulate_vis_gain_gauss_newton(gains=None, **own)
+
+
+def simulate_vis_gain_gauss_newton(
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    gains,
+    d_fluxes=None,
+    d_ants=None,
+    d_baselines=None,
+    d_radec=None,
+    d_topo=None,
+    d_beam_coefs=None,
+    d_gains=None,
+    weights=None,
+    wrt=None,
+    quad_per: str = "total",
+    return_gvis: bool = False,
+    adjoint_path: str = "type3",
+    beam_coefs=None,
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """``simulate_vis_gauss_newton`` for uncalibrated data: the Gauss-Newton product of ``simulate_vis_gain_chi2``'s chi2,
+    whose data model is ``V' = conj(g[a1]) g[a2] V``, along a joint direction ``p = (sky directions, d_gains)``, the gain
+    block of ``H p`` included.  With ``m`` the gain product, ``dm = conj(dg[a1]) g[a2] + conj(g[a1]) dg[a2]`` its tangent and
+    ``U`` the sky tangent as ``simulate_vis_gauss_newton`` defines it, the tangent of the data model is
+    ``U' = m U + dm V``; ``quad = sum w |U'|^2``, ``H = 2 J'^T W J'`` with ``J'`` the Jacobian of V', and
+    ``<p, H p> = 2 quad``, the gains' part of the inner product being ``Re sum conj(d_gains) prod``.  The product is applied
+    on the device to the blocks the weighting kernel touches (``fv_sim_gain_weight_block``), whatever path produced them;
+    everything else -- the ``d_*`` directions, ``weights``, the other names of ``wrt``, ``quad_per``, ``adjoint_path``,
+    ``force_use_type3``, the returned tuple -- is ``simulate_vis_gauss_newton``'s, which is this call with ``gains=None``.
+
+    * ``gains``: ``simulate_vis_gain_chi2``'s, with its shapes and rules.  ``d_gains``: the gain direction, ``gains``' own
+      shape -- time-constant or per time as ``gains`` is --, complex and finite, or None.  ``d_gains`` alone is a valid
+      call: no tangent pass runs, only the forward.
+    * ``"gains"`` in ``wrt`` gives the gain block of ``H p`` in ``gains``' own shape, complex128, in torch's convention for a
+      complex leaf (the convention of ``simulate_vis_gain_chi2``'s gradient), following the inputs as the other products
+      do; for time-constant gains it is the per-time products added on the host in time order.  ``wrt=None`` appends
+      ``"gains"`` when ``d_gains`` is given.  Every other product is its public pass's result for ``vis = G``.
+    * ``return_gvis=True`` gives that ``G = conj(m) 2 w U'``, ``m`` the gain product -- NOT ``2 w U'``.
+    * The forward V is computed only when ``d_gains`` is given or ``"gains"`` is asked for (one more device block); under
+      fixed gains with sky directions and sky products alone the call costs ``simulate_vis_gauss_newton``'s passes.
+    * Gains alone do not force the type-3 transform: ``adjoint_path`` and ``force_use_type3`` are honoured when the sky
+      part of the call is within fluxes, as for ``simulate_vis_gauss_newton``.
+
+    Not covered: keeping V resident across the calls of a gains-only solve (every call reruns the forward), several
+    directions per call, the gradient in the same call (``simulate_vis_gain_chi2``), full 2x2 Jones (leakage) gains,
+    torch ``hvp``, sharding over GPUs."""
     args = locals()
     given = tuple(name for d, name in _GAUSS_NEWTON_NAMES if args[d] is not None)
-    if not given:
+    if d_gains is not None and gains is None:
+        raise ValueError("d_gains needs gains=")
+    if not given and d_gains is None:
+        if gains is not None:
+            raise ValueError("simulate_vis_gain_gauss_newton needs a direction: d_fluxes, d_ants, d_baselines, d_radec, d_topo, "
+                             "d_beam_coefs or d_gains")
         raise ValueError("simulate_vis_gauss_newton needs a direction: d_fluxes, d_ants, d_baselines, d_radec, d_topo or "
                          "d_beam_coefs")
     if d_ants is not None and d_baselines is not None:
@@ -2133,11 +2227,13 @@ def simulate_vis_gauss_newton(
     if d_radec is not None and d_topo is not None:
         raise ValueError("give the source tangent as d_radec or as d_topo, not both")
     if wrt is None:
-        wrt = given
+        wrt = given + (("gains",) if d_gains is not None else ())
     single = isinstance(wrt, str)
     names = (wrt,) if single else tuple(wrt)
     if names:
-        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec' and 'beam_coefs'")
+        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec', 'beam_coefs' and 'gains'")
+    if "gains" in names and gains is None:
+        raise ValueError("wrt='gains' needs gains=")
     if quad_per not in ("total", "freq_time"):
         raise ValueError(f"quad_per must be 'total' or 'freq_time', got {quad_per!r}")
     if adjoint_path not in ("type3", "type2", "auto"):
@@ -2171,9 +2267,21 @@ def simulate_vis_gauss_newton(
             raise ValueError(f"weights must have simulate_vis's output shape {run.vis_shape}, got {tuple(weights.shape)}")
         if weights.is_complex() if _is_tensor(weights) else np.iscomplexobj(weights):
             raise ValueError("weights must be real (inverse variances; 0 flags a sample)")
+    gain_block = dgain_block = None
+    if gains is not None:
+        gain_block = _gain_block(run, gains)
+        if d_gains is not None:
+            if tuple(d_gains.shape) != tuple(gains.shape):
+                raise ValueError(f"d_gains must have gains' shape {tuple(gains.shape)}, got {tuple(d_gains.shape)}")
+            if not np.iscomplexobj(_host(d_gains)):
+                raise ValueError("d_gains must be complex, like gains")
+            if not np.isfinite(_host(d_gains)).all():
+                raise ValueError("d_gains must be finite")
+            dgain_block = _gain_block(run, d_gains)
+    hgains = np.zeros(gain_block.shape, dtype=np.complex128) if "gains" in names else None
     inputs = (d_fluxes, d_ants, d_baselines, d_radec, d_topo, d_beam_coefs, weights)
     dev = _run_device(run, inputs, "a direction or the weights")
-    like = next((x for x in inputs if _is_tensor(x)), None)
+    like = next((x for x in inputs + (d_gains,) if _is_tensor(x)), None)
     if d_radec is not None:
         d_topo = np.einsum("tjdc,jc->tjd", _radec_jacobian_of(run), _host(d_radec).astype(np.float64))
     dc = _buffer(run, dev, d_beam_coefs, "complex")
@@ -2197,12 +2305,21 @@ def simulate_vis_gauss_newton(
         gvis = _zeros(torch.device("cuda", int(device)), run.vis_shape, run.cdt)
         _synchronize(gvis.device)
     _synchronize(dev)
-    fluxes_only = given == ("fluxes",) and set(names) <= {"fluxes"}
+    # (the gains act on the output block whatever path produced it: they do not force the type-3 transform)
+    fluxes_only = set(given) <= {"fluxes"} and set(names) <= {"fluxes", "gains"}
+    outputs = dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis)
     quad_ft = _engine_simulate(
         run, fluxes, force_use_type3=None if fluxes_only else True, adjoint_path=adjoint_path,
-        gauss_newton_of=(directions, w, dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis)))
+        gauss_newton_of=(directions, w, outputs) if gains is None else
+        (directions, w, dict(outputs, ggains=hgains), (gain_block, dgain_block)))
     on_device = dev is not None
     res = {"topo": gtopo, "baselines": gbls, "beam_coefs": gcoefs}
+    if "gains" in names:
+        res["gains"] = _gain_gradient(run, hgains, tuple(gains.shape))
+        if on_device:
+            import torch
+
+            res["gains"] = torch.from_numpy(res["gains"]).to(dev)
     if "fluxes" in names:
         res["fluxes"] = stokes_adjoint(gflux, full_stokes)
     if "radec" in names:

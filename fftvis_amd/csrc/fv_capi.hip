@@ -439,6 +439,66 @@ static void weight_rows_host(int device, int64_t nrows, int64_t row_len, int npa
 }
 
 template <typename T>
+static void gain_weight_rows_host(int device, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1, const int *ant2,
+                                  const void *gains, const void *d_gains, int nparts, const void *const *parts, void *vis,
+                                  const void *weights, double *q_rows, void *hgains) {
+    const int nfeed = tpol == 4 ? 2 : 1;
+    const size_t ng = (size_t)nrows * nfeed * (size_t)nant;
+    if (nrows == 0) return;
+    if (nbls == 0) {
+        for (int64_t i = 0; i < nrows; ++i) q_rows[i] = 0.0;
+        if (hgains) std::memset(hgains, 0, sizeof(cplx<double>) * ng);
+        return;
+    }
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const int64_t row_len = (int64_t)tpol * nbls;
+    const size_t n = (size_t)nrows * (size_t)row_len;
+    const int nblk = residual_blocks_per_row<T>(row_len);
+    GainPairs gp;
+    gp.set(sg.s, nant, nbls, ant1, ant2);
+    DevBuf dp[4], dv, dw, ds, dgn, ddg, dhg;
+    cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int j = 0; j < nparts; ++j) {
+        dp[j].reserve(sizeof(cplx<T>) * n);
+        dparts[j] = dp[j].as<cplx<T>>();
+        FV_HIP(hipMemcpyAsync(dp[j].p, parts[j], sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    }
+    if (vis) {
+        dv.reserve(sizeof(cplx<T>) * n);
+        FV_HIP(hipMemcpyAsync(dv.p, vis, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    }
+    if (weights) {
+        dw.reserve(sizeof(T) * n);
+        FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
+    }
+    dgn.reserve(sizeof(cplx<T>) * ng);
+    FV_HIP(hipMemcpyAsync(dgn.p, gains, sizeof(cplx<T>) * ng, hipMemcpyHostToDevice, sg.s));
+    if (d_gains) {
+        ddg.reserve(sizeof(cplx<T>) * ng);
+        FV_HIP(hipMemcpyAsync(ddg.p, d_gains, sizeof(cplx<T>) * ng, hipMemcpyHostToDevice, sg.s));
+    }
+    if (hgains) dhg.reserve(sizeof(cplx<double>) * ng);
+    ds.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
+    double *partials = ds.as<double>(), *sums = partials + (size_t)nrows * nblk;
+    int *bad = reinterpret_cast<int *>(sums + nrows);
+    launch_gain_weight_rows<T>(sg.s, nparts, dparts, vis ? dv.as<cplx<T>>() : nullptr, weights ? dw.as<T>() : nullptr,
+                               dgn.as<cplx<T>>(), d_gains ? ddg.as<cplx<T>>() : nullptr, gp, nrows, tpol, partials, sums, bad,
+                               hgains ? dhg.as<cplx<double>>() : nullptr);
+    int hbad[2] = {0, 0};
+    if (nparts)  // G replaces P_0, or V for the gains-only direction
+        FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    else
+        FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(q_rows, sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    if (hgains) FV_HIP(hipMemcpyAsync(hgains, dhg.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+    throw_if_bad_residual_input(hbad);
+}
+
+template <typename T>
 static void inplace_rot_host(int device, const double *rot, void *b, int64_t n) {
     FV_REQUIRE(rot && n >= 0 && (b || n == 0), "bad inplace_rot arrays");
     FV_HIP(hipSetDevice(device));
@@ -628,6 +688,32 @@ int fv_weight_rows(int device, int precision, int64_t nrows, int64_t row_len, in
     });
 }
 
+int fv_gain_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                        const int *ant2, const void *gains, const void *d_gains, int nparts, const void *const *parts, void *vis,
+                        const void *weights, double *q_rows, void *hgains) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_gain_weight_rows: tpol must be 1 or 4");
+        FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_gain_weight_rows: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_gain_weight_rows: nant must be positive");
+        FV_REQUIRE(gains || nrows == 0, "fv_gain_weight_rows: null gains");
+        FV_REQUIRE(nparts >= 0 && nparts <= 4 && (parts || nparts == 0), "fv_gain_weight_rows: nparts must be 0 .. 4");
+        FV_REQUIRE(nparts > 0 || d_gains, "fv_gain_weight_rows: nparts == 0 needs d_gains");
+        for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts[j], "fv_gain_weight_rows: null part");
+        FV_REQUIRE(vis || !(d_gains || hgains), "fv_gain_weight_rows: d_gains and hgains need vis");
+        FV_REQUIRE((nrows == 0 || nbls == 0 || (ant1 && ant2)) && (nrows == 0 || q_rows), "fv_gain_weight_rows: null pairs or q_rows");
+        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
+            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                       "fv_gain_weight_rows: antenna index outside [0, nant)");
+        if (precision == 2)
+            gain_weight_rows_host<double>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, d_gains, nparts, parts, vis, weights,
+                                          q_rows, hgains);
+        else
+            gain_weight_rows_host<float>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, d_gains, nparts, parts, vis, weights,
+                                         q_rows, hgains);
+    });
+}
+
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n) {
     return guarded([&] {
         FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
@@ -782,6 +868,23 @@ int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, v
         FV_REQUIRE(weights_on_device == 0 || weights_on_device == 1, "on_device flags must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->weight_block(t0, t1, f0, f1, nparts, parts_dev, weights, weights_on_device, q_ft);
+    });
+}
+int fv_sim_gain_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
+                             const void *weights, int weights_on_device, const void *gains, int gains_on_device,
+                             const void *d_gains, int d_gains_on_device, double *q_ft, void *hgains, int hgains_on_device) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(nparts >= 0 && nparts <= 4 && (parts_dev || nparts == 0), "nparts must be 0 .. 4");
+        FV_REQUIRE(nparts > 0 || d_gains, "nparts == 0 needs d_gains");
+        for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts_dev[j], "null part");
+        FV_REQUIRE(gains && q_ft, "null gains or q_ft");
+        FV_REQUIRE(vis_dev || !(d_gains || hgains), "d_gains and hgains need vis");
+        FV_REQUIRE((weights_on_device == 0 || weights_on_device == 1) && (gains_on_device == 0 || gains_on_device == 1) &&
+                       (d_gains_on_device == 0 || d_gains_on_device == 1) && (hgains_on_device == 0 || hgains_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->gain_weight_block(t0, t1, f0, f1, nparts, parts_dev, vis_dev, weights, weights_on_device, gains, gains_on_device,
+                                   d_gains, d_gains_on_device, q_ft, hgains, hgains_on_device);
     });
 }
 int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,

@@ -1884,10 +1884,16 @@ struct GainPairs {
     DevBuf d_ant1, d_ant2, d_off, d_inc;
     int nant = 0;
     int64_t nbls = -1;  // -1: not set
+    std::vector<int> h_ant1, h_ant2;  // what the device holds while nbls >= 0: the same pairs again cost two compares
     void set(hipStream_t on, int nant_, int64_t nbls_, const int *ant1, const int *ant2) {
+        if (nbls >= 0 && nbls_ == nbls && nant_ == nant && (nbls_ == 0 || (ant1 && ant2)) &&
+            std::equal(h_ant1.begin(), h_ant1.end(), ant1) && std::equal(h_ant2.begin(), h_ant2.end(), ant2))
+            return;  // (a solver's inner loop sets the same pairs on every call: nothing to rebuild or upload)
         std::vector<int> off, inc;
         gain_incidence(nant_, nbls_, ant1, ant2, off, inc);
         nbls = -1;
+        h_ant1.assign(ant1, ant1 + nbls_);
+        h_ant2.assign(ant2, ant2 + nbls_);
         const size_t nb = sizeof(int) * (size_t)nbls_;
         d_ant1.reserve(std::max<size_t>(nb, 16));
         d_ant2.reserve(std::max<size_t>(nb, 16));
@@ -1927,6 +1933,289 @@ inline void launch_gain_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *da
                        gains, gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), nrows, nbls, tpol, nant, in_lds, vec, partials, bad);
     hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
                        chi2_rows);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gauss-Newton product with per-antenna gains and a gain direction (fv_gain_weight_rows, fv_sim_gain_weight_block;
+// DESIGN.md "Gains in the Gauss-Newton product").  The block, the pairs, the feeds and the gains' layout are the gain
+// kernels' above; dg is the gain direction in the gains' layout, or null.  Per element of baseline k = (a1, a2), with
+// g1 = g[p, a1], g2 = g[q, a2], h1 = dg[p, a1], h2 = dg[q, a2], U the sum of the NP = 0 .. 4 sky tangent parts as in
+// k_weight_rows (U = 0 for NP = 0, the gains-only direction) and V the forward at the real parameters,
+//     m = conj(g1) g2,   dm = conj(h1) g2 + conj(g1) h2 (dm = 0 without a gain direction),   U' = m U + dm V,
+//     G' = 2 (w U'),   stored G = conj(m) G',   row sum += w |U'|^2 (terms formed and added in fp64),
+//     hgains[a, f] = sum_{k: a1 = a, p = f} conj(G') g2 V + sum_{k: a2 = a, q = f} G' g1 conj(V).
+// Two kernels, no floating-point atomics.  k_gain_weight_gather is k_gain_gradient with this G' in place of
+// 2 w (V' - d): it runs first, while the blocks still hold the parts and V, one wave per (row, feed, antenna) over the
+// incidence lists, everything in fp64 from the T-typed inputs (U summed in fp64 in the parts' order), an __shfl_xor tree,
+// one complex128 per wave; a flagged sample is skipped before its parts and V are read.  k_gain_weight_rows is
+// k_weight_rows with the product folded in: its chunks, clipping, vector path, grid, partials, reduction and bad-weight
+// counter, k_gain_residual_rows' (pol, k) bookkeeping and staging of the row's gains -- and of the direction, when both
+// together fit GAIN_LDS_BYTES.  V is read only with a gain direction; G replaces P_0, or V for NP = 0.  In T every
+// operation rounds on its own, in the order written above: with unit gains and no direction m = 1, m U = U and
+// conj(m) G' = G' exactly, and the bits are k_weight_rows'.
+constexpr bool GAIN_WEIGHT_RE_FIRST[3] = {true, true, false};  // vector path / element by element, NP = 1 / NP = 2 .. 4
+template <typename T>
+__device__ __forceinline__ double gain_weight_element(cplx<T> &u, const cplx<T> &v, T w, const cplx<T> &g1, const cplx<T> &g2,
+                                                      const cplx<T> &h1, const cplx<T> &h2, bool sky, bool dir, bool re_first,
+                                                      int &bad_w) {
+    if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
+    if (!(w > (T)0)) {  // flagged (or counted above)
+        u = {(T)0, (T)0};
+        return 0.0;
+    }
+    T ur, ui;
+    {
+        // (no contraction, the products written out: see gain_residual_element)
+#pragma clang fp contract(off)
+        const T mr = g1.re * g2.re + g1.im * g2.im, mi = g1.re * g2.im - g1.im * g2.re;  // m = conj(g1) g2
+        ur = mr * u.re - mi * u.im;                                                      // m U
+        ui = mr * u.im + mi * u.re;
+        if (dir) {
+            const T dmr = (h1.re * g2.re + h1.im * g2.im) + (g1.re * h2.re + g1.im * h2.im);  // dm = conj(h1) g2 + conj(g1) h2
+            const T dmi = (h1.re * g2.im - h1.im * g2.re) + (g1.re * h2.im - g1.im * h2.re);
+            const T tr = dmr * v.re - dmi * v.im, ti = dmr * v.im + dmi * v.re;  // dm V
+            ur = sky ? ur + tr : tr;                                             // U' = m U + dm V (dm V alone for NP = 0)
+            ui = sky ? ui + ti : ti;
+        }
+        const T gr = (T)2 * (w * ur), gi = (T)2 * (w * ui);  // G'
+        u = {mr * gr + mi * gi, mr * gi - mi * gr};          // conj(m) G'
+    }
+    // weight_element's w (ur^2 + ui^2), which the compiler contracts there into one fused multiply-add whose choice of
+    // the fused square differs between k_weight_rows' instances and paths (in fp64; the squares of fp32 values are exact
+    // in fp64): spelled out here, the caller says which (GAIN_WEIGHT_RE_FIRST), so that with unit gains the two kernels
+    // give the same bits
+    const double dr = (double)ur, di = (double)ui;
+    double t;
+    {
+#pragma clang fp contract(off)
+        t = (double)w * (re_first ? __builtin_fma(dr, dr, di * di) : __builtin_fma(di, di, dr * dr));
+    }
+    return t;
+}
+template <typename T, int NP>
+__global__ void __launch_bounds__(256)
+    k_gain_weight_rows(WeightParts<T> parts, cplx<T> *__restrict__ vis, const T *__restrict__ weights,
+                       const cplx<T> *__restrict__ gains, const cplx<T> *__restrict__ dgains, const int *__restrict__ ant1,
+                       const int *__restrict__ ant2, int64_t nrows, int nbls, int tpol, int nant, int in_lds, int vec,
+                       double *__restrict__ partials, int *__restrict__ bad) {
+    constexpr int W = RES_W<T>;
+    constexpr int NV = W * (int)sizeof(cplx<T>) / 16;  // 16-byte vectors of a part (and of V) per chunk: 2
+    // the fused square of the rows' terms as k_weight_rows<T, NP> is compiled: the real part's on the vector path of
+    // every instance and element by element for NP = 1, the imaginary part's element by element for NP = 2 .. 4
+    // (tests/test_gpu_gain_gauss_newton.py holds every instance to it on both paths)
+    constexpr bool re_vec = GAIN_WEIGHT_RE_FIRST[0], re_one = NP == 1 ? GAIN_WEIGHT_RE_FIRST[1] : GAIN_WEIGHT_RE_FIRST[2];
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    __shared__ double wave_sum[4];
+    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
+    const int64_t L = (int64_t)tpol * nbls;
+    const bool dir = dgains != nullptr;
+    cplx<T> *const out = NP ? parts.p[0] : vis;  // where G goes
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<T> *g = gains + row * ng;
+        const cplx<T> *h = dir ? dgains + row * ng : nullptr;
+        if (in_lds) {
+            cplx<T> *gl = reinterpret_cast<cplx<T> *>(gain_lds);
+            for (int i = threadIdx.x; i < ng; i += 256) gl[i] = g[i];
+            g = gl;
+            if (dir) {
+                for (int i = threadIdx.x; i < ng; i += 256) gl[ng + i] = h[i];
+                h = gl + ng;
+            }
+            __syncthreads();
+        }
+        const int64_t lo = row * L, hi = lo + L;  // the row in the block's index
+        const int64_t c0 = lo / W;                // its first chunk
+        double s = 0.0;
+        int bad_w = 0;
+        for (int i = 0; i < RES_CHUNKS; ++i) {
+            const int64_t c = c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x;
+            const int64_t e0 = c * W;
+            if (e0 >= hi) break;
+            const int64_t a = e0 > lo ? e0 : lo, b = e0 + W < hi ? e0 + W : hi;
+            int pol = (int)((a - lo) / nbls), k = (int)((a - lo) - (int64_t)pol * nbls);  // of element a; carried below
+            int p, q;
+            gain_feeds(pol, nfeed, p, q);
+            const cplx<T> zero = {(T)0, (T)0};
+            if (vec && e0 >= lo && e0 + W <= hi) {
+                union {
+                    uint4 q[NV];
+                    cplx<T> c[W];
+                } u, t;
+                union {
+                    uint4 q;
+                    T w[W];
+                } ww;
+                if (NP) {
+#pragma unroll
+                    for (int j = 0; j < NV; ++j) u.q[j] = reinterpret_cast<const uint4 *>(parts.p[0] + e0)[j];
+#pragma unroll
+                    for (int n = 1; n < NP; ++n) {
+#pragma unroll
+                        for (int j = 0; j < NV; ++j) t.q[j] = reinterpret_cast<const uint4 *>(parts.p[n] + e0)[j];
+#pragma unroll
+                        for (int j = 0; j < W; ++j) u.c[j] = {u.c[j].re + t.c[j].re, u.c[j].im + t.c[j].im};
+                    }
+                }
+                if (dir) {
+#pragma unroll
+                    for (int j = 0; j < NV; ++j) t.q[j] = reinterpret_cast<const uint4 *>(vis + e0)[j];
+                }
+                if (weights) ww.q = *reinterpret_cast<const uint4 *>(weights + e0);
+#pragma unroll
+                for (int j = 0; j < W; ++j) {
+                    const int i1 = p * nant + ant1[k], i2 = q * nant + ant2[k];
+                    if (!NP) u.c[j] = zero;
+                    s += gain_weight_element<T>(u.c[j], dir ? t.c[j] : zero, weights ? ww.w[j] : (T)1, g[i1], g[i2],
+                                                dir ? h[i1] : zero, dir ? h[i2] : zero, NP != 0, dir, re_vec, bad_w);
+                    if (++k == nbls) {
+                        k = 0;
+                        gain_feeds(++pol, nfeed, p, q);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < NV; ++j) reinterpret_cast<uint4 *>(out + e0)[j] = u.q[j];
+            } else {
+                for (int64_t e = a; e < b; ++e) {
+                    cplx<T> u = zero;
+                    if (NP) u = parts.p[0][e];
+#pragma unroll
+                    for (int n = 1; n < NP; ++n) u = {u.re + parts.p[n][e].re, u.im + parts.p[n][e].im};
+                    const int i1 = p * nant + ant1[k], i2 = q * nant + ant2[k];
+                    s += gain_weight_element<T>(u, dir ? vis[e] : zero, weights ? weights[e] : (T)1, g[i1], g[i2],
+                                                dir ? h[i1] : zero, dir ? h[i2] : zero, NP != 0, dir, re_one, bad_w);
+                    out[e] = u;
+                    if (++k == nbls) {
+                        k = 0;
+                        gain_feeds(++pol, nfeed, p, q);
+                    }
+                }
+            }
+        }
+        if (bad_w) atomicAdd(bad, bad_w);
+        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+        __syncthreads();
+        if (threadIdx.x == 0)
+            partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+        __syncthreads();  // (the next row of this block writes wave_sum and the staged gains again)
+    }
+}
+// hgains[(row nfeed + feed) nant + a]: one wave per (row, feed, antenna); see above.  The parts and vis still hold the
+// tangent parts and V.
+template <typename T, int NP>
+__global__ void __launch_bounds__(256)
+    k_gain_weight_gather(WeightParts<T> parts, const cplx<T> *__restrict__ vis, const T *__restrict__ weights,
+                         const cplx<T> *__restrict__ gains, const cplx<T> *__restrict__ dgains, const int *__restrict__ ant1,
+                         const int *__restrict__ ant2, const int *__restrict__ inc_off, const int *__restrict__ inc,
+                         int64_t nrows, int nbls, int tpol, int nant, cplx<double> *__restrict__ hgains) {
+    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
+    const int wave = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (wave >= ng) return;  // (whole waves: the tree below stays inside one)
+    const int feed = wave / nant, ant = wave - feed * nant;
+    const int i0 = inc_off[ant], i1 = inc_off[ant + 1];
+    const int64_t L = (int64_t)tpol * nbls;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<T> *g = gains + row * ng;
+        const cplx<T> *h = dgains ? dgains + row * ng : nullptr;
+        double sr = 0.0, si = 0.0;
+        for (int i = i0 + lane; i < i1; i += 64) {
+            const int k = inc[i] >> 1, side = inc[i] & 1;
+            const int a1 = ant1[k], a2 = ant2[k];
+            for (int o = 0; o < nfeed; ++o) {  // the other antenna's feed
+                const int p = side ? o : feed, q = side ? feed : o;
+                const int64_t e = row * L + (int64_t)(nfeed == 2 ? 2 * q + p : 0) * nbls + k;
+                const T wt = weights ? weights[e] : (T)1;
+                if (!(wt > (T)0)) continue;  // flagged: nothing is added, the parts and V are not read
+                const cplx<double> g1 = {(double)g[p * nant + a1].re, (double)g[p * nant + a1].im};
+                const cplx<double> g2 = {(double)g[q * nant + a2].re, (double)g[q * nant + a2].im};
+                const cplx<double> v = {(double)vis[e].re, (double)vis[e].im};
+                const cplx<double> m = cmul(cconj(g1), g2);
+                cplx<double> up = {0.0, 0.0};  // U' = m U + dm V
+                if (NP) {
+                    cplx<double> u = {(double)parts.p[0][e].re, (double)parts.p[0][e].im};
+#pragma unroll
+                    for (int n = 1; n < NP; ++n) u = {u.re + (double)parts.p[n][e].re, u.im + (double)parts.p[n][e].im};
+                    up = cmul(m, u);
+                }
+                if (h) {
+                    const cplx<double> h1 = {(double)h[p * nant + a1].re, (double)h[p * nant + a1].im};
+                    const cplx<double> h2 = {(double)h[q * nant + a2].re, (double)h[q * nant + a2].im};
+                    const cplx<double> m1 = cmul(cconj(h1), g2), m2 = cmul(cconj(g1), h2);
+                    const cplx<double> t = cmul(cplx<double>{m1.re + m2.re, m1.im + m2.im}, v);
+                    up = {up.re + t.re, up.im + t.im};
+                }
+                const double w2 = 2.0 * (double)wt;
+                const cplx<double> gp = {w2 * up.re, w2 * up.im};
+                // side 0: conj(G') g2 V;  side 1: G' g1 conj(V)
+                const cplx<double> t = side ? cmul(gp, cmul(g1, cconj(v))) : cmul(cconj(gp), cmul(g2, v));
+                sr += t.re;
+                si += t.im;
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            sr += __shfl_xor(sr, off, 64);
+            si += __shfl_xor(si, off, 64);
+        }
+        if (lane == 0) hgains[(row * nfeed + feed) * nant + ant] = {sr, si};
+    }
+}
+// Queues the gather (when hgains is not null), the in-place kernel and the rows' reduction on `on`: launch_weight_rows'
+// arguments with nparts = 0 .. 4, the forward block vis (needed with dgains, with hgains and for nparts = 0, where G
+// replaces it; else it may be null), the row's gains and their direction (nrows, nfeed nant; dgains may be null) and the
+// pairs; hgains (nrows, nfeed nant) complex128.  All device pointers; weights, dgains and hgains may be null.
+template <typename T>
+inline void launch_gain_weight_rows(hipStream_t on, int nparts, cplx<T> *const *parts, cplx<T> *vis, const T *weights,
+                                    const cplx<T> *gains, const cplx<T> *dgains, const GainPairs &gp, int64_t nrows, int tpol,
+                                    double *partials, double *q_rows, int *bad, cplx<double> *hgains) {
+    if (nparts < 0 || nparts > 4 || (nparts == 0 && !dgains)) throw Error(FV_ERR_ARG, "nparts must be 0 .. 4, and 0 needs d_gains");
+    if ((dgains || hgains || nparts == 0) && !vis) throw Error(FV_ERR_ARG, "d_gains and hgains need vis");
+    const int nbls = (int)gp.nbls, nant = gp.nant, ng = (tpol == 4 ? 2 : 1) * nant;
+    const int64_t L = (int64_t)tpol * nbls;
+    const int nblk = residual_blocks_per_row<T>(L);
+    WeightParts<T> wp{};
+    uintptr_t bits = reinterpret_cast<uintptr_t>(weights);
+    if (dgains || nparts == 0) bits |= reinterpret_cast<uintptr_t>(vis);
+    for (int j = 0; j < nparts; ++j) {
+        wp.p[j] = parts[j];
+        bits |= reinterpret_cast<uintptr_t>(parts[j]);
+    }
+    const int vec = (bits & 15) == 0;
+    const unsigned rows_y = (unsigned)std::min<int64_t>(nrows, 65535);
+    const int *a1 = gp.d_ant1.as<int>(), *a2 = gp.d_ant2.as<int>();
+    FV_HIP(hipMemsetAsync(bad, 0, 2 * sizeof(int), on));
+    if (hgains) {
+        const dim3 grid((unsigned)cdiv(ng, 4), rows_y);
+        const int *off = gp.d_off.as<int>(), *inc = gp.d_inc.as<int>();
+        const cplx<T> *v = vis;
+#define FV_GATHER(NP)                                                                                                        \
+    hipLaunchKernelGGL((k_gain_weight_gather<T, NP>), grid, dim3(256), 0, on, wp, v, weights, gains, dgains, a1, a2, off, inc, \
+                       nrows, nbls, tpol, nant, hgains)
+        switch (nparts) {
+        case 0: FV_GATHER(0); break;
+        case 1: FV_GATHER(1); break;
+        case 2: FV_GATHER(2); break;
+        case 3: FV_GATHER(3); break;
+        default: FV_GATHER(4); break;
+        }
+#undef FV_GATHER
+    }
+    const size_t lds = sizeof(cplx<T>) * (size_t)ng * (dgains ? 2 : 1);
+    const int in_lds = lds <= GAIN_LDS_BYTES;
+    const dim3 grid((unsigned)nblk, rows_y);
+    const size_t shm = in_lds ? lds : 0;
+#define FV_ROWS(NP)                                                                                                          \
+    hipLaunchKernelGGL((k_gain_weight_rows<T, NP>), grid, dim3(256), shm, on, wp, vis, weights, gains, dgains, a1, a2, nrows, \
+                       nbls, tpol, nant, in_lds, vec, partials, bad)
+    switch (nparts) {
+    case 0: FV_ROWS(0); break;
+    case 1: FV_ROWS(1); break;
+    case 2: FV_ROWS(2); break;
+    case 3: FV_ROWS(3); break;
+    default: FV_ROWS(4); break;
+    }
+#undef FV_ROWS
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
+                       q_rows);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2523,6 +2812,10 @@ struct SimBase {
     virtual void run_residual_gains(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
                                     int weights_on_device, const void *gains, int gains_on_device, void *gvis, int gvis_on_device,
                                     double *chi2_ft, void *ggains, int ggains_on_device) = 0;
+    virtual void gain_weight_block(int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
+                                   const void *weights, int weights_on_device, const void *gains, int gains_on_device,
+                                   const void *d_gains, int d_gains_on_device, double *q_ft, void *hgains,
+                                   int hgains_on_device) = 0;
     virtual void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, int accumulate) = 0;
     virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
@@ -2704,6 +2997,7 @@ class Sim : public SimBase {
     DevBuf d_res_d, d_res_w;   // fused objective: host data / host weights staged on the device
     DevBuf d_res_sum;          // fused objective: the blocks' partial sums, the rows' sums and the two bad-input counters
     DevBuf d_res_g, d_res_gg;  // gains: a block's host gains staged on the device / the gain gradient of a host destination
+    DevBuf d_res_dg;           // gains: a block's host gain direction staged on the device (fv_sim_gain_weight_block)
     GainPairs gain_pairs;      // gains: the antenna pair of every baseline and the incidence lists (fv_sim_set_gain_pairs)
     DevBuf d_bt_d, d_bt_out;   // basis tangent: host directions D / the (ndir, ...) output of a host destination, on the device
     DevBuf d_csr_start, d_csr;  // basis mode: per antenna, its baselines as 2 b + role (k_coef_reduce)
@@ -4198,6 +4492,72 @@ class Sim : public SimBase {
                 d_res_w.release();
                 d_res_g.release();
                 d_res_gg.release();
+            }
+        }
+        check_errors();
+        throw_if_bad_residual_input(hbad);
+    }
+
+    // ---- Gauss-Newton product with gains (DESIGN.md "Gains in the Gauss-Newton product") ------------------------------
+    // weight_block's sequence with the kernels of fv_gain_weight_rows: nparts = 0 .. 4 tangent blocks, vis_dev the forward
+    // block at the real parameters (needed with d_gains, with hgains and for nparts = 0, where G replaces it), gains and
+    // d_gains the block's (f1 - f0, t1 - t0, nfeed, nant) arrays of the handle's precision, hgains the same shape in
+    // complex128 or null (the gather does not run).  Host gains, direction and hgains are staged and given back under
+    // run_residual_gains' rule; one synchronisation at the end brings everything a host asked for.
+    void gain_weight_block(int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev, const void *weights,
+                           int weights_on_device, const void *gains, int gains_on_device, const void *d_gains,
+                           int d_gains_on_device, double *q_ft, void *hgains, int hgains_on_device) override {
+        check_run(t0, t1, f0, f1);
+        FV_REQUIRE(t1 > t0 && f1 > f0, "fv_sim_gain_weight_block: empty range of times or frequencies");
+        FV_REQUIRE(gain_pairs.nbls == nbls, "fv_sim_gain_weight_block: fv_sim_set_gain_pairs first (after the array is set)");
+        const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
+        const size_t n = (size_t)nrows * (size_t)L;
+        const size_t ng = (size_t)nrows * (size_t)(tpol == 4 ? 2 : 1) * (size_t)gain_pairs.nant;
+        const T *dw = static_cast<const T *>(weights);
+        const cplx<T> *dgn = static_cast<const cplx<T> *>(gains), *ddg = static_cast<const cplx<T> *>(d_gains);
+        if (weights && !weights_on_device) {
+            upload(d_res_w, weights, sizeof(T) * n, 0);
+            dw = d_res_w.as<T>();
+        }
+        if (!gains_on_device) {
+            upload(d_res_g, gains, sizeof(cplx<T>) * ng, 0);
+            dgn = d_res_g.as<cplx<T>>();
+        }
+        if (d_gains && !d_gains_on_device) {
+            upload(d_res_dg, d_gains, sizeof(cplx<T>) * ng, 0);
+            ddg = d_res_dg.as<cplx<T>>();
+        }
+        cplx<double> *dhg = static_cast<cplx<double> *>(hgains);
+        if (hgains && !hgains_on_device) {
+            d_res_gg.reserve(std::max<size_t>(sizeof(cplx<double>) * ng, 16));
+            dhg = d_res_gg.as<cplx<double>>();
+        }
+        cplx<T> *parts[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int j = 0; j < nparts; ++j) parts[j] = static_cast<cplx<T> *>(parts_dev[j]);
+        const int nblk = residual_blocks_per_row<T>(L);
+        const size_t part_bytes = sizeof(double) * (size_t)nrows * nblk, sum_bytes = sizeof(double) * (size_t)nrows;
+        d_res_sum.reserve(part_bytes + sum_bytes + 16);
+        double *partials = d_res_sum.as<double>(), *sums = partials + (size_t)nrows * nblk;
+        int *bad = reinterpret_cast<int *>(sums + nrows);
+        launch_gain_weight_rows<T>(stream, nparts, parts, static_cast<cplx<T> *>(vis_dev), dw, dgn, ddg, gain_pairs, nrows, tpol,
+                                   partials, sums, bad, dhg);
+        int hbad[2] = {0, 0};
+        FV_HIP(hipMemcpyAsync(q_ft, sums, sum_bytes, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, stream));
+        if (hgains && !hgains_on_device)
+            FV_HIP(hipMemcpyAsync(hgains, dhg, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, stream));
+        FV_HIP(hipStreamSynchronize(stream));
+        FV_HIP(hipGetLastError());
+        if (timing_level) ev_collect();
+        {  // run_residual_gains' rule, the staged direction included
+            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+            if ((double)(d_res_d.cap + d_res_w.cap + d_res_g.cap + d_res_gg.cap + d_res_dg.cap) >
+                (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
+                d_res_d.release();
+                d_res_w.release();
+                d_res_g.release();
+                d_res_gg.release();
+                d_res_dg.release();
             }
         }
         check_errors();

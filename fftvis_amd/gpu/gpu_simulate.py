@@ -291,6 +291,27 @@ class SimHandle:
         _lib.check(self._L.fv_sim_weight_block(self._h, t0, t1, f0, f1, len(parts), ptrs, wp, w_dev, _lib.ptr(q)))
         return q
 
+    def gain_weight_block(self, t0, t1, f0, f1, parts, vis, weights, gains, d_gains=None, hgains=None):
+        """``weight_block`` with per-antenna gains and a gain direction (``fv_sim_gain_weight_block``; ``set_gain_pairs``
+        first): with ``m = conj(g[a1]) g[a2]``, ``dm`` its tangent along ``d_gains`` and U the sum of ``parts`` -- none to
+        four device tensors; none is the gains-only direction --, ``U' = m U + dm V`` is the tangent of the data model,
+        ``G = conj(m) 2 w U'`` replaces ``parts[0]`` (``vis`` when there are no parts) and the returned rows are
+        ``sum w |U'|^2``.  ``vis``: the device tensor a forward run of this handle filled with V, needed with ``d_gains``,
+        with ``hgains`` and without parts, else None.  ``gains``, ``d_gains`` (or None): C-contiguous (f1 - f0, t1 - t0,
+        nfeed, nant), this engine's complex dtype; ``hgains``: the same shape, complex128, filled with the gain block of
+        H p, or None (its kernel does not run).  numpy arrays are host buffers, torch tensors device buffers.  The
+        stored G is what every ``run_*_adjoint`` takes as ``g``.  The call synchronises."""
+        ptrs = (ctypes.c_void_p * max(len(parts), 1))(*[p.data_ptr() for p in parts])
+        vp, _ = _buffer_addr(vis)
+        wp, w_dev = _buffer_addr(weights)
+        np_, n_dev = _buffer_addr(gains)
+        dp, d_dev = _buffer_addr(d_gains)
+        hp, h_dev = _buffer_addr(hgains)
+        q = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
+        _lib.check(self._L.fv_sim_gain_weight_block(self._h, t0, t1, f0, f1, len(parts), ptrs, vp, wp, w_dev, np_, n_dev, dp,
+                                                    d_dev, _lib.ptr(q), hp, h_dev))
+        return q
+
     def run_adjoint(self, t0, t1, f0, f1, g, gflux, accumulate: bool):
         """``gflux += A^T g`` for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_adjoint``).  ``g``: C-contiguous block of
         ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype; ``gflux``: C-contiguous (nsrc, nfreq) real or
@@ -660,17 +681,31 @@ class GPUSimulationEngine(SimulationEngine):
           rows of sum w |U|^2, and ``objective_of``'s adjoint passes follow on G with its rules: the lattice path is
           taken by a call whose only direction is ``d_fluxes`` and whose only output is ``gflux`` (or none), a
           ValueError for any other on a lattice array (pass ``force_use_type3=True``).  Not with ``catalog_device``.
-          Returns the (nfreqs, ntimes) float64 array of sum w |U|^2 per (frequency, time) of the block.
+          Returns the (nfreqs, ntimes) float64 array of sum w |U|^2 per (frequency, time) of the block.  An optional
+          fourth element ``(gains, d_gains)`` -- host arrays (nfreqs, ntimes, nfeed, nant) of this precision's complex
+          dtype, rows in ``ants``' order, ``d_gains`` or None -- makes it the product of ``objective_of``'s chi2 with
+          gains: the tangent is ``U' = m U + dm V``, ``SimHandle.gain_weight_block`` replaces ``weight_block``, G is
+          ``conj(m) 2 w U'`` and the rows are sum w |U'|^2.  A gain direction counts as a direction (alone, no tangent
+          pass runs), and ``outputs["ggains"]`` (a host complex128 array of the gains' shape, optional) receives the gain
+          block of H p.  Only with ``d_gains`` or ``"ggains"`` one more block holds V, a forward run at the real fluxes.
+          The lattice rule is unchanged: the product acts on the block whatever path produced it.
         """
         if gauss_newton_of is not None:
             if any(m is not None for m in (adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of)):
                 raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of "
                                  "and gauss_newton_of")
-            if (len(gauss_newton_of) != 3 or not isinstance(gauss_newton_of[0], dict) or not isinstance(gauss_newton_of[2], dict)
-                    or set(gauss_newton_of[0]) - set(_GAUSS_NEWTON_DIRECTIONS) or set(gauss_newton_of[2]) - set(_OBJECTIVE_OUTPUTS)):
+            if (len(gauss_newton_of) not in (3, 4) or not isinstance(gauss_newton_of[0], dict)
+                    or not isinstance(gauss_newton_of[2], dict) or set(gauss_newton_of[0]) - set(_GAUSS_NEWTON_DIRECTIONS)
+                    or set(gauss_newton_of[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT}):
                 raise ValueError(f"gauss_newton_of: (directions, weights, outputs) with directions a dict over "
                                  f"{_GAUSS_NEWTON_DIRECTIONS} and outputs a dict over {_OBJECTIVE_OUTPUTS}")
-            if all(gauss_newton_of[0].get(k) is None for k in _GAUSS_NEWTON_DIRECTIONS):
+            gn_gains = gauss_newton_of[3] if len(gauss_newton_of) == 4 else None
+            if gn_gains is not None and (not isinstance(gn_gains, tuple) or len(gn_gains) != 2 or gn_gains[0] is None):
+                raise ValueError("gauss_newton_of: the fourth element is (gains, d_gains), d_gains or None")
+            if gauss_newton_of[2].get(_GAIN_OUTPUT) is not None and gn_gains is None:
+                raise ValueError("gauss_newton_of: ggains needs the gains (a fourth element)")
+            if (all(gauss_newton_of[0].get(k) is None for k in _GAUSS_NEWTON_DIRECTIONS)
+                    and (gn_gains is None or gn_gains[1] is None)):
                 raise ValueError("gauss_newton_of: no direction given")
             if beam_coefs is None and (gauss_newton_of[0].get("d_beam_coefs") is not None
                                        or gauss_newton_of[2].get("gcoefs") is not None):
@@ -891,7 +926,7 @@ class GPUSimulationEngine(SimulationEngine):
                 ok = True
                 return result
             if gauss_newton_of is not None:
-                directions, gn_weights, gn_outputs = gauss_newton_of
+                directions, gn_weights, gn_outputs = gauss_newton_of[:3]
                 if not use_basis:  # (a cached handle keeps its last setting)
                     h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
                 set_fluxes = None
@@ -906,10 +941,23 @@ class GPUSimulationEngine(SimulationEngine):
                 # (a block's parts and weights are on the device together: one block per part, half a block of weights)
                 nparts = _gauss_newton_nparts(directions, use_basis)
                 scale = nparts + (0.0 if gn_weights is None else 0.5)
+                if gn_gains is not None:
+                    nfeed = 2 if polarized else 1
+                    for name, x in zip(("gains", "d_gains"), gn_gains):
+                        if x is not None and (not isinstance(x, np.ndarray) or x.dtype != complex_dtype
+                                              or x.shape != (f1 - f0, t1 - t0, nfeed, nant)):
+                            raise ValueError(f"gauss_newton_of: {name} must be a {np.dtype(complex_dtype).name} array of "
+                                             f"shape {(f1 - f0, t1 - t0, nfeed, nant)}")
+                    row = {a: i for i, a in enumerate(antnums)}  # (as objective_of sets them)
+                    nb = len(baselines)
+                    h.set_gain_pairs(nant, np.fromiter((row[bl[0]] for bl in baselines), np.int32, count=nb),
+                                     np.fromiter((row[bl[1]] for bl in baselines), np.int32, count=nb))
+                    # (one more block when V is held; the gains, their direction and the product are under 0.1 % of one)
+                    scale += 1.0 if gn_gains[1] is not None or gn_outputs.get(_GAIN_OUTPUT) is not None else 0.0
                 nblk_t = _time_block(self.device, t1 - t0, int(np.ceil((f1 - f0) * scale)), len(baselines), polarized,
                                      precision, nsrc if coord_mgr is not None else 0)
                 result = _run_gauss_newton(h, self.device, directions, gn_weights, gn_outputs, set_fluxes, t0, t1, f0, f1,
-                                           nblk_t, coord_mgr, basis=use_basis)
+                                           nblk_t, coord_mgr, basis=use_basis, gains=gn_gains)
                 ok = True
                 return result
             if adjoint_of is not None:
@@ -1269,19 +1317,25 @@ def _gauss_newton_nparts(directions, basis):
     return sum(given) if basis else int(given[0]) + int(given[2] or given[3])
 
 
-def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False):
+def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False,
+                      gains=None):
     """The Gauss-Newton product's time loop, over the forward's blocks (and, with a coordinate manager, its streamed
     vectors).  Per block one device block per tangent pass, filled by pointer in this order: the forward on ``d_fluxes``
     (``set_fluxes(True)`` before, ``set_fluxes(False)`` after: every other pass sees the real fluxes), ``run_basis_tangent``
     on ``d_beam_coefs``, the position tangent on ``d_baselines`` (without basis beams ``d_topo`` rides in the same
     ``run_tangent``), ``run_basis_source_tangent`` on ``d_topo``.  ``weight_block`` leaves G = 2 w (their sum) in the first
     -- ``outputs["gvis"]`` itself when one block is the whole result -- and the block's rows of sum w |U|^2; the adjoint
-    passes follow on G as in ``_run_objective``.  Returns the rows, (f1 - f0, t1 - t0) float64 on the host.  Every call
-    ends synchronised."""
+    passes follow on G as in ``_run_objective``.  With ``gains = (gains, d_gains)`` (host, (f1 - f0, t1 - t0, nfeed, nant);
+    ``d_gains`` or None) ``gain_weight_block`` takes the block's time steps of them instead, G is ``conj(m) 2 w U'`` and the
+    rows are sum w |U'|^2; only with ``d_gains`` or ``outputs["ggains"]`` one more block is filled with V -- ``run_device``
+    at the real fluxes, after the parts -- and the block's time steps of ``ggains`` are filled; without a sky direction V's
+    block receives G.  Returns the rows, (f1 - f0, t1 - t0) float64 on the host.  Every call ends synchronised."""
     import torch
 
     gflux, gcoefs, gbls, gtopo, gvis = (outputs.get(k) for k in _OBJECTIVE_OUTPUTS)
+    ggains = outputs.get(_GAIN_OUTPUT)
     d_fluxes, d_coefs, d_bls, d_topo = (directions.get(k) for k in _GAUSS_NEWTON_DIRECTIONS)
+    hold_v = gains is not None and (gains[1] is not None or ggains is not None)
     dev = torch.device("cuda", int(device))
     cdt = getattr(torch, np.dtype(h.cdt).name)
     nparts = _gauss_newton_nparts(directions, basis)
@@ -1301,8 +1355,10 @@ def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t
     for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
         whole = tb == t0 and te == t1
         shape = h.out_shape(te - tb, f1 - f0)
+        # (block 0 receives G: the first part, or V for a gains-only direction)
         parts = [gvis if gvis is not None and whole and j == 0 else torch.empty(shape, dtype=cdt, device=dev)
-                 for j in range(nparts)]
+                 for j in range(nparts + int(hold_v))]
+        vis = parts.pop(0 if nparts == 0 else -1) if hold_v else None
         torch.cuda.synchronize(dev)
         rows_in = None if d_topo is None else d_topo[tb - t0:te - t0]  # (rows of a C-contiguous array: a contiguous view)
         todo = iter(parts)
@@ -1320,8 +1376,18 @@ def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t
                 h.run_basis_source_tangent(ta, te_, f0, f1, rows_in, next(todo))
         elif d_bls is not None or d_topo is not None:
             h.run_tangent(ta, te_, f0, f1, d_bls, rows_in, next(todo))
-        g = parts[0]
-        quad[:, tb - t0:te - t0] = h.weight_block(ta, te_, f0, f1, parts, block(weights, tb, te))
+        if hold_v:  # (the real fluxes are back)
+            h.run_device(ta, te_, f0, f1, vis.data_ptr())
+        if gains is None:
+            g = parts[0]
+            quad[:, tb - t0:te - t0] = h.weight_block(ta, te_, f0, f1, parts, block(weights, tb, te))
+        else:
+            g = parts[0] if parts else vis
+            hg = None if ggains is None else np.empty(gains[0][:, tb - t0:te - t0].shape, dtype=np.complex128)
+            quad[:, tb - t0:te - t0] = h.gain_weight_block(ta, te_, f0, f1, parts, vis, block(weights, tb, te),
+                                                           block(gains[0], tb, te), block(gains[1], tb, te), hg)
+            if hg is not None:
+                ggains[:, tb - t0:te - t0] = hg
         if gvis is not None and not whole:
             gvis[:, tb - t0:te - t0] = g
             torch.cuda.synchronize(dev)

@@ -120,6 +120,32 @@ int fv_gain_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls
  * before anything runs.  Host pointers. */
 int fv_weight_rows(int device, int precision, int64_t nrows, int64_t row_len, int nparts, const void *const *parts,
                    const void *weights, double *q_rows);
+/* fv_gain_weight_rows: fv_weight_rows with per-antenna gains and a gain direction folded in (the kernel pair
+ * fv_sim_gain_weight_block queues): the weighting step of a Gauss-Newton product of fv_gain_residual_chi2's chi2.  The
+ * rows, the pairs, the feeds (pol = 2 q + p) and gains are fv_gain_residual_chi2's; d_gains: the gain direction dg in
+ * gains' layout, or NULL; parts: nparts = 0 .. 4 blocks as for fv_weight_rows (nparts = 0, the gains-only direction,
+ * needs d_gains); vis: the forward V at the real parameters, needed with d_gains or hgains, else it may be NULL.  Per
+ * element of baseline k = (a1, a2), with g1 = g[p, a1], g2 = g[q, a2], h1 = dg[p, a1], h2 = dg[q, a2] and
+ * U = ((P_0 + P_1) + P_2) + P_3 (0 for nparts = 0), in `precision`, every operation rounded on its own, in this order:
+ *   m  = conj(g1) g2                     dm = conj(h1) g2 + conj(g1) h2      (dm = 0 without a gain direction)
+ *   U' = m U + dm V                      (the tangent of V' along p = (sky directions, dg))
+ *   G' = 2 (w U')                        quad row += w |U'|^2  (terms formed and added in fp64)
+ *   stored G = conj(m) G'                (what the public sky adjoints read: their result on it is H p for their block)
+ *   hgains[a, f] = sum_{k: a1=a, p=f} conj(G') g2 V  +  sum_{k: a2=a, q=f} G' g1 conj(V)
+ * G is written in place into parts[0], or into vis for nparts = 0 (everything else is read only); q_rows[i] is row i's
+ * sum, reduced as fv_residual_chi2 reduces; over all rows <p, H p> = 2 sum q_rows, the gains' inner product being
+ * Re sum conj(dg) hgains.  hgains: (nrows, nfeed, nant) complex128, the gain block of H p in the convention of ggains, or
+ * NULL (its kernel does not run); every term is formed in fp64 from the inputs of `precision` (U' = m U + dm V and G' in
+ * fp64) and added as fv_gain_residual_chi2 adds ggains -- no floating-point atomics, the same input gives the same
+ * bits; an antenna without a baseline gets exactly 0.  With unit gains and no direction G and q_rows are fv_weight_rows'
+ * bit for bit.  A weight of exactly 0 flags its sample: G is exactly 0 there, nothing is added anywhere and neither the
+ * parts nor V are used (NaN or Inf there do not propagate).  A weight that is negative or not finite fails the call
+ * with FV_ERR_ARG and fv_residual_chi2's message after it ran.  tpol not in {1, 4}, an antenna index outside [0, nant), a
+ * null gains, nparts outside 0 .. 4, nparts = 0 without d_gains, a null part, d_gains or hgains without vis and a null
+ * q_rows fail with FV_ERR_ARG before anything runs.  Host pointers. */
+int fv_gain_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                        const int *ant2, const void *gains, const void *d_gains, int nparts, const void *const *parts, void *vis,
+                        const void *weights, double *q_rows, void *hgains);
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n);
 /* fv_astrom_topo: one time step of the device-side coordinate manager (see fv_sim_set_astrom): eq (3, n) ICRS unit
  * vectors -> topo (3, n) topocentric (east, north, up) unit vectors under one 31-double context -- what matvis'
@@ -543,6 +569,21 @@ int fv_sim_run_residual_gains(fv_sim *h, int t0, int t1, int f0, int f1, const v
  * (counted by the kernel itself): parts_dev[0] and q_ft are then invalid and the handle stays usable.                     */
 int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,
                         int weights_on_device, double *q_ft);
+/* fv_sim_weight_block with per-antenna gains and a gain direction: the Gauss-Newton product of
+ * fv_sim_run_residual_gains' chi2.  The call is fv_sim_weight_block's -- kernels on the main stream, one synchronisation
+ * -- with the two kernels of fv_gain_weight_rows, whose formulas hold element by element: parts_dev are nparts = 0 .. 4
+ * DEVICE tangent blocks, vis_dev the DEVICE block fv_sim_run wrote at the real parameters (needed with d_gains, with
+ * hgains and for nparts = 0; else it may be NULL), and  stored G = conj(m) G',  G' = 2 (w U'),  U' = m U + dm V,  is left
+ * in parts_dev[0] (in vis_dev for nparts = 0): what every fv_sim_run_*_adjoint of this handle takes as its input.  q_ft
+ * as for fv_sim_weight_block, the rows of sum w |U'|^2.  gains, d_gains: (f1 - f0, t1 - t0, nfeed, nant) complex of the
+ * handle's precision, d_gains or NULL; hgains: the same shape in complex128, the gain block of H p, or NULL.  Host gains,
+ * direction and hgains are staged and given back with host weights under the FFTVIS_HIP_ADJ_KEEP_BYTES rule.  Needs
+ * fv_sim_set_gain_pairs.  A null handle, nparts outside 0 .. 4, nparts = 0 without d_gains, a null part, gains or q_ft,
+ * d_gains or hgains without vis_dev, a flag other than 0 or 1, an empty range and missing pairs fail with FV_ERR_ARG
+ * before anything runs; bad weights as for fv_sim_weight_block.                                                          */
+int fv_sim_gain_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
+                             const void *weights, int weights_on_device, const void *gains, int gains_on_device,
+                             const void *d_gains, int d_gains_on_device, double *q_ft, void *hgains, int hgains_on_device);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2

@@ -218,6 +218,54 @@ int main() {
         EXPECT(fv_sim_weight_block(fake, 0, 1, 0, 1, 1, dparts, nullptr, 0, nullptr) == FV_ERR_ARG);
         EXPECT(fv_sim_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, 2, v) == FV_ERR_ARG);
     }
+    // and the Gauss-Newton weighting with gains: tpol, shapes, nant, null gains, nparts outside 0 .. 4 or 0 without a
+    // direction, a null part, a direction or a gain product without V, null pairs or q, antenna indices, flags
+    {
+        fv_sim *fake = reinterpret_cast<fv_sim *>(0x1);
+        const void *parts[4] = {v, v, v, v}, *hole[2] = {v, nullptr};
+        void *dparts[4] = {v, v, v, v}, *dhole[2] = {v, nullptr};
+        const int a[3] = {0, 1, 2}, low[3] = {0, -1, 2}, high[3] = {0, 1, 3};
+        EXPECT(fv_gain_weight_rows(0, 3, 1, 3, 1, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 2, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "tpol must be 1 or 4") != nullptr);
+        EXPECT(fv_gain_weight_rows(0, 2, -1, 3, 1, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, -3, 1, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 0, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, nullptr, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "null gains") != nullptr);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, v, nullptr, -1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, v, nullptr, 5, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, v, nullptr, 1, nullptr, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, v, nullptr, 0, parts, v, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "nparts == 0 needs d_gains") != nullptr);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, v, nullptr, 2, hole, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "null part") != nullptr);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, v, v, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "d_gains and hgains need vis") != nullptr);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, nullptr, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, nullptr, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 1, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, nullptr, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 4, 3, low, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_weight_rows(0, 2, 1, 3, 4, 3, a, high, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "antenna index outside [0, nant)") != nullptr);
+        EXPECT(fv_sim_gain_weight_block(nullptr, 0, 1, 0, 1, 1, dparts, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "null handle") != nullptr);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, -1, dparts, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 5, dparts, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, nullptr, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 0, nullptr, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 2, dhole, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, nullptr, 0, nullptr, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, nullptr, 0, v, 0, nullptr, 0, nullptr, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, nullptr, nullptr, 0, v, 0, v, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, nullptr, nullptr, 0, v, 0, nullptr, 0, v, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 2, v, 0, v, 0, v, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, -1, v, 0, v, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, 0, v, 3, v, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, 0, v, 0, v, v, 2) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "on_device") != nullptr);
+    }
     // a call that gets past the argument checks reports the missing device as a HIP error, not a crash
     if (ndev == 0) {
         EXPECT(fv_sim_create(&h, 0, 2, 1e-6, 2.0, 1) == FV_ERR_HIP && h == nullptr);

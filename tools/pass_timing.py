@@ -16,8 +16,8 @@
                     joint                                                           C5, 8 channels  (--precision)
     objective       forward separate separate_torch fused fused_device              C3, 8 channels  (--wrt, --lattice,
                                                                                     --gains; --config C5: through K = 4)
-    gauss_newton    forward composed fused fused_device                             C3, 8 channels  (--case; beam_coefs:
-                                                                                    --config C5)
+    gauss_newton    forward composed fused fused_device                             C3, 8 channels  (--case, --gains,
+                                                                                    --d-gains; beam_coefs: --config C5)
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -40,8 +40,13 @@ block's shape, six times each, alternating.  gauss_newton: one product
 2 J^T W J p of a conjugate-gradient solve -- ``composed`` is the public tangent to the host, numpy's 2 w U and the public adjoint
 on the host result (runs on a checkout from before the fused call: --package DIR --only forward --only composed), ``fused``
 simulate_vis_gauss_newton on host weights and ``fused_device`` on resident weights; --case fluxes | ants | fluxes_radec |
-beam_coefs names the direction and the products; ``--profile kernels`` runs k_weight_rows and k_residual_rows alone on the
-block's shape, six times each, alternating.  A flag of another family is an error.
+beam_coefs | gains names the direction and the products; ``--profile kernels`` runs k_weight_rows and k_residual_rows alone on the
+block's shape, six times each, alternating.  --gains puts per-antenna gains into the data model and --d-gains adds a gain
+direction and the gain block of the product (``--case gains``: that direction alone): ``fused`` and ``fused_device`` call
+``simulate_vis_gain_gauss_newton``, ``composed`` becomes the tangent and, with --d-gains, the forward to the host, the gain
+product, its tangent, conj(m) 2 w U' and the antennas' sums in torch on the device and the public adjoint on the host
+result, and ``--profile gain_kernels`` runs the kernels of fv_gain_weight_rows, fv_weight_rows and fv_gain_residual_chi2 alone
+on the block's shape, six times each, alternating.  A flag of another family is an error.
 tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
 
 import argparse
@@ -282,7 +287,8 @@ def objective(a, fv, cfg, rng):
     return head, calls
 
 
-GAUSS_NEWTON_CASES = {"fluxes": ("fluxes",), "ants": ("ants",), "fluxes_radec": ("fluxes", "radec"), "beam_coefs": ("beam_coefs",)}
+GAUSS_NEWTON_CASES = {"fluxes": ("fluxes",), "ants": ("ants",), "fluxes_radec": ("fluxes", "radec"), "beam_coefs": ("beam_coefs",),
+                      "gains": ()}  # (no sky direction: --gains --d-gains)
 
 
 def gauss_newton(a, fv, cfg, rng):
@@ -321,6 +327,99 @@ def gauss_newton(a, fv, cfg, rng):
         return out
 
     calls = {"forward": lambda: fv.simulate_vis(**cfg), "composed": composed}
+    gains = {}
+    if a.d_gains and not a.gains:
+        raise SystemExit("--d-gains needs --gains")
+    if not names and not a.d_gains:
+        raise SystemExit("--case gains needs --gains --d-gains")
+    if a.gains:
+        nums = list(cfg["ants"])
+        nant, nfeed = len(nums), 2 if cfg["polarized"] else 1
+        gshape = ((nant, 2) if cfg["polarized"] else (nant,)) + (a.nfreq,)
+        g0 = (1 + 0.1 * (rng.normal(size=gshape) + 1j * rng.normal(size=gshape))).astype(cdt)
+        gains = {"gains": g0}
+        if a.d_gains:
+            gains["d_gains"] = (0.1 * (rng.normal(size=gshape) + 1j * rng.normal(size=gshape))).astype(cdt)
+        a1 = [nums.index(b[0]) for b in cfg["baselines"]]
+        a2 = [nums.index(b[1]) for b in cfg["baselines"]]
+        out_names = names + (("gains",) if a.d_gains else ())
+
+        def composed():  # what a caller composes without the new call: V and U to the host, the gain product, its tangent
+            # and conj(m) 2 w U' in torch on the device, the public adjoint on the host result, the antennas' sums in torch
+            import torch
+
+            def product(x, y):  # conj(x[a1]) y[a2] in the block's shape
+                x1, y2 = x[a1].conj(), y[a2]  # (nbls, [2,] nf)
+                if cfg["polarized"]:  # out[f, t, x, y, k]: y is the first antenna's feed
+                    return (y2.permute(2, 1, 0)[:, :, None, :] * x1.permute(2, 1, 0)[:, None, :, :])[:, None]
+                return (x1 * y2).T[:, None]
+
+            G0, W = torch.from_numpy(g0).cuda(), torch.from_numpy(w).cuda()
+            m = product(G0, G0)
+            up = 0
+            if dirs:
+                up = m * torch.from_numpy((fv.simulate_vis_basis_jvp if basis else fv.simulate_vis_jvp)(**cfg, **dirs)).cuda()
+            out = []
+            if a.d_gains:
+                V = torch.from_numpy(fv.simulate_vis(**cfg)).cuda()
+                H = torch.from_numpy(gains["d_gains"]).cuda()
+                up = up + (product(H, G0) + product(G0, H)) * V
+            gp = 2 * W * up
+            if a.d_gains:  # the antennas' sums of conj(G') g2 V (first antenna's feed y) and G' g1 conj(V) (second's, x)
+                hg = torch.zeros((nant, nfeed, a.nfreq), dtype=torch.complex128, device="cuda")
+                i1, i2 = torch.tensor(a1, device="cuda"), torch.tensor(a2, device="cuda")
+                g1, g2 = G0[a1], G0[a2]
+                if cfg["polarized"]:
+                    first = (gp.conj() * V * g2.permute(2, 1, 0)[:, None, :, None, :]).sum(dim=(1, 2))   # (f, y, k)
+                    second = (gp * V.conj() * g1.permute(2, 1, 0)[:, None, None, :, :]).sum(dim=(1, 3))  # (f, x, k)
+                    hg.index_add_(0, i1, first.permute(2, 1, 0).to(torch.complex128))
+                    hg.index_add_(0, i2, second.permute(2, 1, 0).to(torch.complex128))
+                else:
+                    first, second = (gp.conj() * V * g2.T[:, None]).sum(dim=1), (gp * V.conj() * g1.T[:, None]).sum(dim=1)
+                    hg[:, 0].index_add_(0, i1, first.T.to(torch.complex128))
+                    hg[:, 0].index_add_(0, i2, second.T.to(torch.complex128))
+                out.append(hg.cpu().numpy())
+            g = (m.conj() * gp).cpu().numpy().astype(cdt)
+            if sky:
+                out.append((fv.simulate_vis_basis_sky_adjoint if basis else fv.simulate_vis_sky_adjoint)(g, **cfg, wrt=sky))
+            if rest:
+                out.append((fv.simulate_vis_basis_adjoint if basis else fv.simulate_vis_position_adjoint)(g, **cfg, wrt=rest))
+            return out
+
+        calls["composed"] = composed
+        if a.profile == "gain_kernels":  # (for a kernel trace only) the gain weighting kernels next to k_weight_rows and the
+            # objective's gain kernels, alone on the block's shape, alternating
+            def gain_kernels():
+                import ctypes
+                import importlib
+
+                _lib = importlib.import_module(fv.__name__ + "._lib")
+                lib = _lib.lib()
+                rows, tpol = a.nfreq * a.ntimes, 4 if cfg["polarized"] else 1
+                L = tpol * nbls
+
+                def block(x):
+                    return np.ascontiguousarray(np.broadcast_to(x.reshape(nant, nfeed, a.nfreq, 1), (nant, nfeed, a.nfreq, a.ntimes))
+                                                .transpose(2, 3, 1, 0))
+
+                gb = block(g0)
+                hb = block(gains["d_gains"]) if a.d_gains else None
+                i1, i2 = np.array(a1, np.int32), np.array(a2, np.int32)
+                u = (rng.normal(size=(rows, L)) + 1j * rng.normal(size=(rows, L))).astype(cdt)
+                v0, w2, q, hg = u[::-1].copy(), w.reshape(rows, L), np.zeros(rows), np.zeros(gb.shape, np.complex128)
+                for _ in range(6):
+                    part, v = u.copy(), v0.copy()
+                    ptrs = (ctypes.c_void_p * 1)(part.ctypes.data)
+                    _lib.check(lib.fv_gain_weight_rows(0, p, rows, nbls, tpol, nant, _lib.ptr(i1), _lib.ptr(i2), _lib.ptr(gb),
+                                                       _lib.ptr(hb), 1, ptrs, _lib.ptr(v), _lib.ptr(w2), _lib.ptr(q), _lib.ptr(hg)))
+                    part = u.copy()
+                    ptrs = (ctypes.c_void_p * 1)(part.ctypes.data)
+                    _lib.check(lib.fv_weight_rows(0, p, rows, L, 1, ptrs, _lib.ptr(w2), _lib.ptr(q)))
+                    v = v0.copy()
+                    _lib.check(lib.fv_gain_residual_chi2(0, p, rows, nbls, tpol, nant, _lib.ptr(i1), _lib.ptr(i2), _lib.ptr(gb),
+                                                         _lib.ptr(v), _lib.ptr(u), _lib.ptr(w2), _lib.ptr(q), _lib.ptr(hg)))
+
+            calls["gain_kernels"] = gain_kernels
     if a.profile == "kernels":  # (for a kernel trace only) the two streaming kernels alone on the block's shape, alternating
         def kernels():
             import ctypes
@@ -348,12 +447,18 @@ def gauss_newton(a, fv, cfg, rng):
             if not resident:
                 resident.append(torch.from_numpy(w).cuda())
                 torch.cuda.synchronize()
+            if gains:
+                return fv.simulate_vis_gain_gauss_newton(**cfg, **dirs, **gains, weights=resident[0], wrt=out_names)
             return fv.simulate_vis_gauss_newton(**cfg, **dirs, weights=resident[0], wrt=names)
 
-        calls["fused"] = lambda: fv.simulate_vis_gauss_newton(**cfg, **dirs, weights=w, wrt=names)
+        if gains:
+            calls["fused"] = lambda: fv.simulate_vis_gain_gauss_newton(**cfg, **dirs, **gains, weights=w, wrt=out_names)
+        else:
+            calls["fused"] = lambda: fv.simulate_vis_gauss_newton(**cfg, **dirs, weights=w, wrt=names)
         calls["fused_device"] = fused_device
     vis_bytes = w.size * np.dtype(cdt).itemsize
     head = {"config": a.config, "case": a.case, "precision": p, "polarized": bool(cfg["polarized"]), "wrt": list(names),
+            "gains": bool(a.gains), "d_gains": bool(a.d_gains),
             # per call, from the shapes: U to the host and G back / w to the device / the directions and products alone
             "pcie_bytes": {"composed": 2 * vis_bytes, "fused": w.nbytes, "fused_device": 0}, "vis_bytes": vis_bytes}
     return head, calls
@@ -381,12 +486,12 @@ FAMILIES = {
         "separate_over_forward": ("separate", "forward"), "fused_over_separate": ("fused", "separate"),
         "fused_device_over_separate": ("fused_device", "separate"), "fused_device_over_forward": ("fused_device", "forward"),
         "separate_torch_over_separate": ("separate_torch", "separate")}),
-    "gauss_newton": (gauss_newton, "C3", 8, ("case",), "runs", {
+    "gauss_newton": (gauss_newton, "C3", 8, ("case", "gains", "d_gains"), "runs", {
         "composed_over_forward": ("composed", "forward"), "fused_over_composed": ("fused", "composed"),
         "fused_device_over_composed": ("fused_device", "composed"), "fused_device_over_forward": ("fused_device", "forward")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
-             "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False}  # and their defaults
+             "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False}  # and their defaults
 
 
 def main():
@@ -408,10 +513,14 @@ def main():
     ap.add_argument("--ndir", type=int, default=None)
     ap.add_argument("--wrt", default=None, help="objective: the gradients, comma-separated (default fluxes)")
     ap.add_argument("--gains", action="store_true", default=None,
-                    help="objective: per-antenna gains in the data model (gains may then be one of --wrt's names)")
+                    help="objective: per-antenna gains in the data model (gains may then be one of --wrt's names); "
+                         "gauss_newton: the gains in the data model (simulate_vis_gain_gauss_newton)")
+    ap.add_argument("--d-gains", action="store_true", default=None,
+                    help="gauss_newton, with --gains: a gain direction, and the gain block among the products")
     ap.add_argument("--precision", type=int, choices=[1, 2], default=None, help="2: the configuration in fp64 at eps 6e-8")
     ap.add_argument("--case", choices=list(GAUSS_NEWTON_CASES), default=None,
-                    help="gauss_newton: the direction and the products (default fluxes; beam_coefs: --config C5)")
+                    help="gauss_newton: the direction and the products (default fluxes; beam_coefs: --config C5; gains: no "
+                         "sky direction, with --gains --d-gains)")
     a = ap.parse_args()
     build, config, nfreq, own, spread, ratios = FAMILIES[a.family]
     for flag, default in OWN_FLAGS.items():
