@@ -15,7 +15,8 @@ the fit objective with its gradients from one call that keeps the visibilities o
 ``torch_simulate_vis_chi2``; ``simulate_vis_gain_chi2`` for uncalibrated data: per-antenna complex gains in the data model
 and their gradient), and the Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the tangent
 on the device (``simulate_vis_gauss_newton``; ``simulate_vis_gain_gauss_newton`` with the gains in the data model, a gain
-direction and the gain block of the product).
+direction and the gain block of the product), and the gains themselves for a fixed model, solved on the device against
+a resident model (``simulate_vis_gain_solve``).
 """
 
 __version__ = "0.1.0"
@@ -37,6 +38,7 @@ from .adjoint import (  # noqa: F401
     simulate_vis_chi2,
     simulate_vis_gain_chi2,
     simulate_vis_gain_gauss_newton,
+    simulate_vis_gain_solve,
     simulate_vis_gauss_newton,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,

@@ -44,6 +44,11 @@ SYMBOLS = {
     "fv_residual_chi2": (c_int, [c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fv_gain_residual_chi2": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_gain_normal_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_gain_solve": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                              c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
     "fv_weight_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "fv_gain_weight_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

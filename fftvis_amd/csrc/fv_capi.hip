@@ -403,6 +403,117 @@ static void gain_residual_chi2_host(int device, int64_t nrows, int64_t nbls, int
 }
 
 template <typename T>
+static void gain_normal_rows_host(int device, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1, const int *ant2,
+                                  const void *gains, const void *vis, const void *data, const void *weights, void *num, double *den) {
+    const int nfeed = tpol == 4 ? 2 : 1;
+    const size_t ng = (size_t)nrows * nfeed * (size_t)nant;
+    if (nrows == 0) return;
+    if (nbls == 0) {
+        std::memset(num, 0, sizeof(cplx<double>) * ng);
+        std::memset(den, 0, sizeof(double) * ng);
+        return;
+    }
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const size_t n = (size_t)nrows * (size_t)tpol * (size_t)nbls;
+    GainPairs gp;
+    gp.set(sg.s, nant, nbls, ant1, ant2);
+    DevBuf dv, dd, dw, dgn, dnum, dden;
+    dv.reserve(sizeof(cplx<T>) * n);
+    dd.reserve(sizeof(cplx<T>) * n);
+    if (weights) dw.reserve(sizeof(T) * n);
+    dgn.reserve(sizeof(cplx<double>) * ng);
+    dnum.reserve(sizeof(cplx<double>) * ng);
+    dden.reserve(sizeof(double) * ng);
+    FV_HIP(hipMemcpyAsync(dv.p, vis, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    FV_HIP(hipMemcpyAsync(dd.p, data, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
+    if (weights) FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
+    FV_HIP(hipMemcpyAsync(dgn.p, gains, sizeof(cplx<double>) * ng, hipMemcpyHostToDevice, sg.s));
+    launch_gain_normal<T>(sg.s, dv.as<cplx<T>>(), dd.as<cplx<T>>(), weights ? dw.as<T>() : nullptr, dgn.as<cplx<double>>(), gp, nrows,
+                          1, tpol, dnum.as<cplx<double>>(), dden.as<double>(), nullptr);
+    FV_HIP(hipMemcpyAsync(num, dnum.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(den, dden.p, sizeof(double) * ng, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+}
+
+// The whole alternating solve (DESIGN.md "Gain solve"): device blocks are used where they lie, host blocks are staged
+// once; the iterate lives in two device buffers and only the units' change comes back per iteration.
+template <typename T>
+static void gain_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1, const int *ant2,
+                            int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
+                            const void *weights, int weights_on_device, void *gains, int max_iter, double tol, int *niter_out,
+                            double *change_out, double *chi2_ft_out, int *solved_out) {
+    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
+    const int64_t nrows = (int64_t)nfreqs * ntimes, rows_per_unit = per_time ? 1 : ntimes;
+    const int64_t nunits = per_time ? nrows : nfreqs;
+    *niter_out = 0;
+    if (nrows == 0) return;  // (no unit: gains, change and solved are empty)
+    std::fill(change_out, change_out + nunits, 0.0);
+    std::fill(chi2_ft_out, chi2_ft_out + nrows, 0.0);
+    std::fill(solved_out, solved_out + nunits * ng, 0);
+    if (nbls == 0) return;  // (the start gains, chi2 0, nothing solved)
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const size_t n = (size_t)nrows * (size_t)tpol * (size_t)nbls, ngu = (size_t)nunits * ng, ngr = (size_t)nrows * ng;
+    GainPairs gp;
+    gp.set(sg.s, nant, nbls, ant1, ant2);
+    DevBuf sv, sd, sw, dg[2], dnum, dden, dchange, dsolved, dchi2, dbad;
+    const auto staged = [&](DevBuf &buf, const void *x, int on_device, size_t bytes) -> const void * {
+        if (!x || on_device) return x;
+        buf.reserve(bytes);
+        FV_HIP(hipMemcpyAsync(buf.p, x, bytes, hipMemcpyHostToDevice, sg.s));
+        return buf.p;
+    };
+    const cplx<T> *dv = static_cast<const cplx<T> *>(staged(sv, vis, vis_on_device, sizeof(cplx<T>) * n));
+    const cplx<T> *dd = static_cast<const cplx<T> *>(staged(sd, data, data_on_device, sizeof(cplx<T>) * n));
+    const T *dw = static_cast<const T *>(staged(sw, weights, weights_on_device, sizeof(T) * n));
+    for (auto &b : dg) b.reserve(sizeof(cplx<double>) * ngu);
+    dnum.reserve(sizeof(cplx<double>) * ngr);
+    dden.reserve(sizeof(double) * ngr);
+    dchange.reserve(sizeof(double) * (size_t)nunits);
+    dsolved.reserve(sizeof(int) * ngu);
+    dchi2.reserve(sizeof(double) * (size_t)nrows);
+    dbad.reserve(16);
+    FV_HIP(hipMemcpyAsync(dg[0].p, gains, sizeof(cplx<double>) * ngu, hipMemcpyHostToDevice, sg.s));
+    int *bad = dbad.as<int>();
+    int hbad[3] = {0, 0, 0};
+    FV_HIP(hipMemsetAsync(bad, 0, sizeof(hbad), sg.s));
+    hipLaunchKernelGGL(k_gain_solve_check<T>, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)n, 256), 4096)), dim3(256), 0, sg.s, dv, dd,
+                       dw, gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), (int64_t)n, (int)nbls, bad);
+    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+    throw_if_bad_solve_input(hbad);
+    int cur = 0, niter = 0;
+    while (niter < max_iter) {
+        ++niter;
+        launch_gain_normal<T>(sg.s, dv, dd, dw, dg[cur].as<cplx<double>>(), gp, nrows, rows_per_unit, tpol, dnum.as<cplx<double>>(),
+                              dden.as<double>(), nullptr);
+        hipLaunchKernelGGL(k_gain_update, dim3((unsigned)nunits), dim3(256), 0, sg.s, (const cplx<double> *)dnum.as<cplx<double>>(),
+                           (const double *)dden.as<double>(), (const cplx<double> *)dg[cur].as<cplx<double>>(),
+                           dg[cur ^ 1].as<cplx<double>>(), rows_per_unit, ng, niter & 1, dchange.as<double>(), dsolved.as<int>());
+        cur ^= 1;
+        FV_HIP(hipMemcpyAsync(change_out, dchange.p, sizeof(double) * (size_t)nunits, hipMemcpyDeviceToHost, sg.s));
+        FV_HIP(hipStreamSynchronize(sg.s));  // (the one small synchronisation per iteration: the host decides)
+        bool done = true;
+        for (int64_t u = 0; u < nunits; ++u) done = done && change_out[u] < tol;
+        if (done) break;
+    }
+    // the chi2 at the final gains: num's buffer (nrows, ng complex128) holds the waves' partials
+    double *part = dnum.as<double>();
+    launch_gain_normal<T>(sg.s, dv, dd, dw, dg[cur].as<cplx<double>>(), gp, nrows, rows_per_unit, tpol, nullptr, nullptr, part);
+    hipLaunchKernelGGL(k_gain_chi2_rows, dim3((unsigned)cdiv(nrows, 4)), dim3(256), 0, sg.s, (const double *)part, nrows, ng,
+                       dchi2.as<double>());
+    FV_HIP(hipMemcpyAsync(chi2_ft_out, dchi2.p, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(gains, dg[cur].p, sizeof(cplx<double>) * ngu, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(solved_out, dsolved.p, sizeof(int) * ngu, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+    *niter_out = niter;
+}
+
+template <typename T>
 static void weight_rows_host(int device, int64_t nrows, int64_t row_len, int nparts, const void *const *parts, const void *weights,
                              double *q_rows) {
     FV_HIP(hipSetDevice(device));
@@ -670,6 +781,58 @@ int fv_gain_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls
             gain_residual_chi2_host<double>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, chi2_rows, ggains);
         else
             gain_residual_chi2_host<float>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, chi2_rows, ggains);
+    });
+}
+
+int fv_gain_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                        const int *ant2, const void *gains, const void *vis, const void *data, const void *weights, void *num,
+                        double *den) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_gain_normal_rows: tpol must be 1 or 4");
+        FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_gain_normal_rows: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_gain_normal_rows: nant must be positive");
+        FV_REQUIRE(nrows == 0 || (gains && num && den), "fv_gain_normal_rows: null gains, num or den");
+        FV_REQUIRE(nrows == 0 || nbls == 0 || (vis && data && ant1 && ant2), "fv_gain_normal_rows: null pairs, vis or data");
+        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
+            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                       "fv_gain_normal_rows: antenna index outside [0, nant)");
+        if (precision == 2)
+            gain_normal_rows_host<double>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, num, den);
+        else
+            gain_normal_rows_host<float>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, num, den);
+    });
+}
+
+int fv_gain_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1,
+                  const int *ant2, int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
+                  const void *weights, int weights_on_device, void *gains, int max_iter, double tol, int *niter_out,
+                  double *change_out, double *chi2_ft_out, int *solved_out) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_gain_solve: tpol must be 1 or 4");
+        FV_REQUIRE(nfreqs >= 0 && ntimes >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_gain_solve: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_gain_solve: nant must be positive");
+        FV_REQUIRE(max_iter >= 1, "fv_gain_solve: max_iter must be positive");
+        FV_REQUIRE(tol >= 0.0, "fv_gain_solve: tol must be non-negative");  // (a NaN fails the comparison)
+        FV_REQUIRE(((per_time | vis_on_device | data_on_device | weights_on_device) & ~1) == 0,
+                   "fv_gain_solve: per_time and the on_device flags must be 0 or 1");
+        FV_REQUIRE(niter_out, "fv_gain_solve: null niter_out");
+        const bool empty = nfreqs == 0 || ntimes == 0;
+        FV_REQUIRE(empty || (gains && change_out && chi2_ft_out && solved_out),
+                   "fv_gain_solve: null gains, change_out, chi2_ft_out or solved_out");
+        FV_REQUIRE(empty || nbls == 0 || (vis && data && ant1 && ant2), "fv_gain_solve: null pairs, vis or data");
+        for (int64_t k = 0; k < nbls && !empty; ++k)
+            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                       "fv_gain_solve: antenna index outside [0, nant)");
+        if (precision == 2)
+            gain_solve_host<double>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, per_time, vis, vis_on_device, data,
+                                    data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out, change_out,
+                                    chi2_ft_out, solved_out);
+        else
+            gain_solve_host<float>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, per_time, vis, vis_on_device, data,
+                                   data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out, change_out,
+                                   chi2_ft_out, solved_out);
     });
 }
 

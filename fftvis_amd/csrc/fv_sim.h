@@ -1936,6 +1936,187 @@ inline void launch_gain_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *da
 }
 
 // ---------------------------------------------------------------------------------------------
+// Gain solve on a resident model (fv_gain_normal_rows, fv_gain_solve; DESIGN.md "Gain solve").  The block, the pairs, the
+// feeds and the incidence lists are the gain kernels' above; V, d and w are read only.  The iterate is complex128
+// whatever T is: (nunits, nfeed nant), row `row` reads unit row / rows_per_unit (a unit is a frequency for time-constant
+// gains, rows_per_unit = ntimes, and a row for per-time gains).  A sample is used when w > 0 and a1 != a2; a flagged
+// sample is skipped before V and d are read.  For fixed V the least-squares problem in one antenna's gain, the others
+// held, is linear; its normal sums per (row, feed f, antenna a) are
+//     side 0 (a = a1, f = p, every q):  num += w g[q, a2] V conj(d),   den += w |g[q, a2]|^2 |V|^2
+//     side 1 (a = a2, f = q, every p):  num += w g[p, a1] conj(V) d,   den += w |g[p, a1]|^2 |V|^2
+// and with autos flagged ggains = 2 (den g - num).  k_gain_normal is k_gain_gradient's gather: one wave per (row, feed,
+// antenna), lane l takes the entries l, l + 64, ... in order, every term formed and added in fp64, an __shfl_xor tree,
+// one complex128 and one float64 per wave; the row's gains are staged in LDS when they fit GAIN_LDS_BYTES (a wave reads
+// the other antennas' at random), which is why a wave without an antenna stays for the barriers instead of leaving.
+// CHI2 = true writes instead the wave's sum of w |conj(g[p, a1]) g[q, a2] V - d|^2 over its side-0 entries -- every
+// baseline once -- into part[(row nfeed + feed) nant + a]; k_gain_chi2_rows adds a row's, a wave per row in a fixed order.
+// k_gain_update, one block per unit: the sums of the unit's rows in ascending order, g^ = num / den where den > 0 (else
+// the antenna keeps its value and is not solved), g <- g^ on odd iterations and (g^ + g) / 2 on even ones, written into
+// the OTHER buffer, and change[unit] = max |g_new - g| / max |g_new| (a max: any order gives the same bits).  No
+// floating-point atomics anywhere.
+template <typename T, bool CHI2>
+__global__ void __launch_bounds__(256)
+    k_gain_normal(const cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
+                  const cplx<double> *__restrict__ gains, const int *__restrict__ ant1, const int *__restrict__ ant2,
+                  const int *__restrict__ inc_off, const int *__restrict__ inc, int64_t nrows, int64_t rows_per_unit, int nbls,
+                  int tpol, int nant, int in_lds, cplx<double> *__restrict__ num, double *__restrict__ den) {
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
+    const int wave = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const bool active = wave < ng;  // (whole waves: the tree below stays inside one)
+    const int feed = active ? wave / nant : 0, ant = active ? wave - feed * nant : 0;
+    const int i0 = active ? inc_off[ant] : 0, i1 = active ? inc_off[ant + 1] : 0;
+    const int64_t L = (int64_t)tpol * nbls;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<double> *g = gains + (row / rows_per_unit) * ng;
+        if (in_lds) {
+            cplx<double> *gl = reinterpret_cast<cplx<double> *>(gain_lds);
+            for (int i = threadIdx.x; i < ng; i += 256) gl[i] = g[i];
+            g = gl;
+            __syncthreads();
+        }
+        double sr = 0.0, si = 0.0, sd = 0.0;
+        for (int i = i0 + lane; i < i1; i += 64) {
+            const int k = inc[i] >> 1, side = inc[i] & 1;
+            const int a1 = ant1[k], a2 = ant2[k];
+            if (a1 == a2 || (CHI2 && side)) continue;  // an auto-correlation is flagged; chi2 counts a baseline once
+            for (int o = 0; o < nfeed; ++o) {          // the other antenna's feed
+                const int p = side ? o : feed, q = side ? feed : o;
+                const int64_t e = row * L + (int64_t)(nfeed == 2 ? 2 * q + p : 0) * nbls + k;
+                const T wt = weights ? weights[e] : (T)1;
+                if (!(wt > (T)0)) continue;  // flagged: nothing is added, V and the datum are not read
+                const cplx<double> go = side ? g[p * nant + a1] : g[q * nant + a2];  // the other antenna's gain
+                const cplx<double> v = {(double)vis[e].re, (double)vis[e].im};
+                const cplx<double> d = {(double)data[e].re, (double)data[e].im};
+                if (CHI2) {
+                    const cplx<double> vp = cmul(cmul(cconj(g[feed * nant + ant]), go), v);
+                    const double dr = vp.re - d.re, di = vp.im - d.im;
+                    sd += (double)wt * (dr * dr + di * di);
+                } else {
+                    // side 0: g2 V conj(d);  side 1: g1 conj(V) d
+                    const cplx<double> t = side ? cmul(cmul(go, cconj(v)), d) : cmul(cmul(go, v), cconj(d));
+                    sr += (double)wt * t.re;
+                    si += (double)wt * t.im;
+                    sd += (double)wt * ((go.re * go.re + go.im * go.im) * (v.re * v.re + v.im * v.im));
+                }
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            if (!CHI2) {
+                sr += __shfl_xor(sr, off, 64);
+                si += __shfl_xor(si, off, 64);
+            }
+            sd += __shfl_xor(sd, off, 64);
+        }
+        if (active && lane == 0) {
+            const int64_t at = (row * nfeed + feed) * nant + ant;
+            if (!CHI2) num[at] = {sr, si};
+            den[at] = sd;
+        }
+        if (in_lds) __syncthreads();  // (the next row of this block stages its gains again)
+    }
+}
+// One block per solve unit; see above.  num, den: (nunits rows_per_unit, ng); g_old, g_new: (nunits, ng), two buffers;
+// odd: the iteration's parity; solved[unit ng + i] = den > 0.
+__global__ void __launch_bounds__(256)
+    k_gain_update(const cplx<double> *__restrict__ num, const double *__restrict__ den, const cplx<double> *__restrict__ g_old,
+                  cplx<double> *__restrict__ g_new, int64_t rows_per_unit, int ng, int odd, double *__restrict__ change,
+                  int *__restrict__ solved) {
+    __shared__ double wave_max[2][4];
+    const int64_t unit = blockIdx.x;
+    double md = 0.0, mn = 0.0;  // max |g_new - g|^2, max |g_new|^2 (the square root is monotone: taken once, at the end)
+    for (int i = threadIdx.x; i < ng; i += 256) {
+        double nr = 0.0, ni = 0.0, dn = 0.0;
+        for (int64_t r = 0; r < rows_per_unit; ++r) {  // ascending time
+            const int64_t at = (unit * rows_per_unit + r) * ng + i;
+            nr += num[at].re;
+            ni += num[at].im;
+            dn += den[at];
+        }
+        const cplx<double> g = g_old[unit * ng + i];
+        cplx<double> gn = g;
+        if (dn > 0.0) {
+            gn = {nr / dn, ni / dn};
+            if (!odd) gn = {0.5 * (gn.re + g.re), 0.5 * (gn.im + g.im)};
+        }
+        g_new[unit * ng + i] = gn;
+        solved[unit * ng + i] = dn > 0.0 ? 1 : 0;
+        const double dr = gn.re - g.re, di = gn.im - g.im;
+        md = fmax(md, dr * dr + di * di);
+        mn = fmax(mn, gn.re * gn.re + gn.im * gn.im);
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        md = fmax(md, __shfl_xor(md, off, 64));
+        mn = fmax(mn, __shfl_xor(mn, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wave_max[0][threadIdx.x >> 6] = md;
+        wave_max[1][threadIdx.x >> 6] = mn;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        md = fmax(fmax(wave_max[0][0], wave_max[0][1]), fmax(wave_max[0][2], wave_max[0][3]));
+        mn = fmax(fmax(wave_max[1][0], wave_max[1][1]), fmax(wave_max[1][2], wave_max[1][3]));
+        change[unit] = mn > 0.0 ? sqrt(md) / sqrt(mn) : 0.0;
+    }
+}
+// chi2_rows[row] = the sum of a row's n partials of the chi2 pass (n = nfeed nant: hundreds, where k_chi2_rows_reduce's one
+// thread per row would run as many dependent adds): one wave per row, lane l adds the partials l, l + 64, ... in order,
+// then an __shfl_xor tree -- a fixed order, the same bits on every run.
+__global__ void __launch_bounds__(256)
+    k_gain_chi2_rows(const double *__restrict__ part, int64_t nrows, int n, double *__restrict__ chi2_rows) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = (int)(threadIdx.x & 63);
+    if (row >= nrows) return;  // (whole waves)
+    double s = 0.0;
+    for (int i = lane; i < n; i += 64) s += part[row * n + i];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) chi2_rows[row] = s;
+}
+// The counting pass of a solve: bad[0] weights that are negative or not finite, bad[1] data that are not finite at a
+// used sample (w > 0, a1 != a2), bad[2] model values that are not finite.  n = nrows tpol nbls elements, read only.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_gain_solve_check(const cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
+                       const int *__restrict__ ant1, const int *__restrict__ ant2, int64_t n, int nbls, int *__restrict__ bad) {
+    int bad_w = 0, bad_d = 0, bad_v = 0;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int k = (int)(e % nbls);
+        const T w = weights ? weights[e] : (T)1;
+        if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
+        if (w > (T)0 && ant1[k] != ant2[k] && (!isfinite(data[e].re) || !isfinite(data[e].im))) ++bad_d;
+        if (!isfinite(vis[e].re) || !isfinite(vis[e].im)) ++bad_v;
+    }
+    if (bad_w) atomicAdd(bad, bad_w);
+    if (bad_d) atomicAdd(bad + 1, bad_d);
+    if (bad_v) atomicAdd(bad + 2, bad_v);
+}
+// Queues one evaluation of the normal sums (num, den: (nrows, ng)) or, with chi2_part, of the chi2 partials on `on`.
+// All device pointers; weights may be null.
+template <typename T>
+inline void launch_gain_normal(hipStream_t on, const cplx<T> *vis, const cplx<T> *data, const T *weights, const cplx<double> *gains,
+                               const GainPairs &gp, int64_t nrows, int64_t rows_per_unit, int tpol, cplx<double> *num, double *den,
+                               double *chi2_part) {
+    const int nbls = (int)gp.nbls, nant = gp.nant, ng = (tpol == 4 ? 2 : 1) * nant;
+    const size_t lds = sizeof(cplx<double>) * (size_t)ng;
+    const int in_lds = lds <= GAIN_LDS_BYTES;
+    const dim3 grid((unsigned)cdiv(ng, 4), (unsigned)std::min<int64_t>(nrows, 65535));
+    if (chi2_part)
+        hipLaunchKernelGGL((k_gain_normal<T, true>), grid, dim3(256), in_lds ? lds : 0, on, vis, data, weights, gains,
+                           gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), gp.d_off.as<int>(), gp.d_inc.as<int>(), nrows, rows_per_unit,
+                           nbls, tpol, nant, in_lds, (cplx<double> *)nullptr, chi2_part);
+    else
+        hipLaunchKernelGGL((k_gain_normal<T, false>), grid, dim3(256), in_lds ? lds : 0, on, vis, data, weights, gains,
+                           gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), gp.d_off.as<int>(), gp.d_inc.as<int>(), nrows, rows_per_unit,
+                           nbls, tpol, nant, in_lds, num, den);
+}
+// the message of a solve that met bad input (k_gain_solve_check's counters)
+inline void throw_if_bad_solve_input(const int bad[3]) {
+    throw_if_bad_residual_input(bad);
+    if (bad[2]) throw Error(FV_ERR_ARG, std::to_string(bad[2]) + " values of the model are not finite");
+}
+
+// ---------------------------------------------------------------------------------------------
 // Gauss-Newton product with per-antenna gains and a gain direction (fv_gain_weight_rows, fv_sim_gain_weight_block;
 // DESIGN.md "Gains in the Gauss-Newton product").  The block, the pairs, the feeds and the gains' layout are the gain
 // kernels' above; dg is the gain direction in the gains' layout, or null.  Per element of baseline k = (a1, a2), with

@@ -548,6 +548,7 @@ class GPUSimulationEngine(SimulationEngine):
         sky_of: tuple = None,
         objective_of: tuple = None,
         gauss_newton_of: tuple = None,
+        forward_to=None,
     ) -> np.ndarray:
         """Simulate visibilities on the GPU.
 
@@ -689,7 +690,14 @@ class GPUSimulationEngine(SimulationEngine):
           pass runs), and ``outputs["ggains"]`` (a host complex128 array of the gains' shape, optional) receives the gain
           block of H p.  Only with ``d_gains`` or ``"ggains"`` one more block holds V, a forward run at the real fluxes.
           The lattice rule is unchanged: the product acts on the block whatever path produced it.
+        * ``forward_to`` (extra; what ``simulate_vis_gain_solve`` passes): a C-contiguous tensor on this device of the
+          result's shape and this run's complex dtype, or True for a new one.  The plain forward run fills it by pointer,
+          time block by time block (``SimHandle.run_device``), and stays there: nothing comes to the host, and the tensor
+          is returned.
         """
+        if forward_to is not None and any(m is not None for m in (
+                adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of, gauss_newton_of, out)):
+            raise ValueError("forward_to is the plain forward run: no other pass and no out= with it")
         if gauss_newton_of is not None:
             if any(m is not None for m in (adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of)):
                 raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of "
@@ -988,6 +996,14 @@ class GPUSimulationEngine(SimulationEngine):
                 nblk_t = _time_block(self.device, t1 - t0, (f1 - f0) * int(basis_tangent_of[0].shape[0]), len(baselines),
                                      polarized, precision, nsrc if coord_mgr is not None else 0)
                 result = _run_basis_tangent(h, basis_tangent_of[0], basis_tangent_of[1], t0, t1, f0, f1, nblk_t, coord_mgr)
+                ok = True
+                return result
+            if forward_to is not None:
+                forward_to = _forward_target(h, self.device, forward_to, t1 - t0, f1 - f0)
+                # (sized again now that the whole model is on the device: a block's temporary has to fit next to it)
+                nblk_t = _time_block(self.device, t1 - t0, f1 - f0, len(baselines), polarized, precision,
+                                     nsrc if coord_mgr is not None else 0)
+                result = _run_forward_to(h, forward_to, t0, t1, f0, f1, nblk_t, coord_mgr)
                 ok = True
                 return result
             if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != complex_dtype):
@@ -1395,6 +1411,39 @@ def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t
         _adjoints_of_block(h, g, gflux, gcoefs, gbls, rows, ta, te_, f0, f1, first, basis)
         first = False
     return quad
+
+
+def _forward_target(h, device, vis, nt, nf):
+    """``forward_to`` as the tensor the forward fills: the caller's, checked, or for True a new one.  It holds the whole
+    (nf, nt, ...) result, so it is made before the time blocks are sized: ``_time_block`` then sees the memory left."""
+    import torch
+
+    cdt = getattr(torch, np.dtype(h.cdt).name)
+    if vis is True:
+        vis = torch.empty(h.out_shape(nt, nf), dtype=cdt, device=torch.device("cuda", int(device)))
+        torch.cuda.synchronize(vis.device)
+    if (not isinstance(vis, torch.Tensor) or vis.device != torch.device("cuda", int(device)) or vis.dtype != cdt
+            or tuple(vis.shape) != h.out_shape(nt, nf) or not vis.is_contiguous()):
+        raise ValueError(f"forward_to must be a C-contiguous {np.dtype(h.cdt).name} tensor on cuda:{int(device)} of shape "
+                         f"{h.out_shape(nt, nf)}")
+    return vis
+
+
+def _run_forward_to(h, vis, t0, t1, f0, f1, nblk_t, coord_mgr):
+    """The forward run into the device tensor ``vis`` (``_forward_target``'s): the forward's time blocks (and, with a
+    coordinate manager, its streamed vectors); every block's ``run_device`` fills its slice ``vis[:, block]`` (a block
+    that is not the whole result goes through a contiguous temporary).  Every call ends synchronised."""
+    import torch
+
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+        blk, dst = _result_block(vis, 1, tb - t0, te - t0, tb == t0 and te == t1)
+        torch.cuda.synchronize(vis.device)
+        h.run_device(ta, te_, f0, f1, blk.data_ptr())
+        h.sync()  # (run_device only queues)
+        if dst is not None:
+            dst[...] = blk
+            torch.cuda.synchronize(vis.device)
+    return vis
 
 
 def _run_basis_tangent(h, dcoefs, dv, t0, t1, f0, f1, nblk_t, coord_mgr):

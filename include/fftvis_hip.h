@@ -107,6 +107,48 @@ int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, 
 int fv_gain_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
                           const int *ant2, const void *gains, void *vis, const void *data, const void *weights,
                           double *chi2_rows, void *ggains);
+/* fv_gain_normal_rows: one evaluation of the normal sums of the gain solve (the gather fv_gain_solve iterates).  The rows,
+ * the pairs and the feeds (pol = 2 q + p) are fv_gain_residual_chi2's; vis, data, weights are read only; gains:
+ * (nrows, nfeed, nant) complex128 whatever `precision` is.  A sample is used when w > 0 and ant1[k] != ant2[k]: an
+ * auto-correlation is quadratic in one gain and counts as flagged; a flagged sample is not read (NaN or Inf there do not
+ * propagate).  For fixed V the least-squares problem in one antenna's gain, the others held, is linear, and its normal
+ * sums over the used samples are, per row i, feed f and antenna a,
+ *   side 0 (a = ant1[k], f = p, every q):  num += w g[q, ant2] V conj(d)      den += w |g[q, ant2]|^2 |V|^2
+ *   side 1 (a = ant2[k], f = q, every p):  num += w g[p, ant1] conj(V) d      den += w |g[p, ant1]|^2 |V|^2
+ * num: (nrows, nfeed, nant) complex128, den: the same shape in float64; with the autos flagged fv_gain_residual_chi2's
+ * ggains = 2 (den g - num).  Every term is formed in fp64 from the inputs of `precision` and added in fp64 over the
+ * antenna's incidence list as ggains is added (one wave, lane l takes entries l, l + 64, ..., an __shfl_xor tree) -- no
+ * floating-point atomics, the same input gives the same bits; an antenna without a used sample gets exactly 0 in both.
+ * tpol not in {1, 4}, a negative shape, nant < 1, an antenna index outside [0, nant) and a null pointer fail with
+ * FV_ERR_ARG before anything runs.  Host pointers. */
+int fv_gain_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                        const int *ant2, const void *gains, const void *vis, const void *data, const void *weights, void *num,
+                        double *den);
+/* fv_gain_solve: the gains that minimise sum w |conj(g[p, ant1]) g[q, ant2] V - d|^2 over the used samples for a FIXED
+ * model V, by the alternating per-antenna solve (StefCal), entirely on the device.  vis, data, weights: the
+ * (nfreqs, ntimes) rows (row = f ntimes + t, as fv_sim_run lays them out) of tpol nbls values of `precision`, each a host
+ * block (staged once per call) or, with its on_device flag, a device block that is read where it lies and never
+ * modified; weights may be NULL (every weight 1).  gains: host, complex128, (nfreqs, per_time ? ntimes : 1, nfeed, nant);
+ * in: the start, out: the result.  A solve unit is a frequency for time-constant gains (per_time = 0) and a
+ * (frequency, time) for per-time gains.  Iteration i = 1, 2, ...: the normal sums of fv_gain_normal_rows at the current
+ * gains, for time-constant gains added over the unit's times in ascending order; g^ = num / den where den > 0 (an antenna
+ * with den == 0 keeps its value and is not solved); g <- g^ for odd i and (g^ + g) / 2 for even i, written into the other
+ * of two buffers; change[unit] = max |g_new - g| / max |g_new| over the unit's feeds and antennas.  The loop ends after
+ * the first iteration at which every unit has change < tol, or at max_iter; every unit iterates until then (tol = 0 runs
+ * exactly max_iter iterations).  The iterate is complex128 on the device and only the units' change comes to the host per
+ * iteration.  niter_out: the iterations run; change_out: (units) the last iteration's change; chi2_ft_out:
+ * (nfreqs, ntimes) sum w |V' - d|^2 over the used samples at the returned gains, from one more pass of the gather over
+ * each antenna's side-0 entries (every baseline once) and a per-row sum in a fixed order; solved_out: int32 in gains'
+ * shape, 0 where den == 0 at the last iteration.  The common phase is left where the iteration puts it.  One counting
+ * pass before the loop fails the call with FV_ERR_ARG for a weight that is negative or not finite and a datum that is not
+ * finite at a used sample (fv_residual_chi2's messages) and for a model value that is not finite; gains is then
+ * untouched.  tpol not in {1, 4}, a negative shape, nant < 1, an antenna index outside [0, nant), a null pointer, a flag
+ * that is not 0 or 1, max_iter < 1 and a negative or NaN tol fail with FV_ERR_ARG before anything runs.  nbls == 0: the
+ * start gains, chi2 0, nothing solved, niter 0. */
+int fv_gain_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1,
+                  const int *ant2, int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
+                  const void *weights, int weights_on_device, void *gains, int max_iter, double tol, int *niter_out,
+                  double *change_out, double *chi2_ft_out, int *solved_out);
 /* fv_weight_rows: the weighting step of a Gauss-Newton product on its own (the kernel pair fv_sim_weight_block queues).
  * parts: nparts = 1 .. 4 blocks P_0 .. P_{nparts-1}, each (nrows, row_len) complex of `precision`, C-contiguous -- the
  * parts of a tangent J p; weights: (nrows, row_len) real of `precision`, or NULL (every weight 1).  Per element, in that

@@ -266,6 +266,61 @@ int main() {
         EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, 0, v, 0, v, v, 2) == FV_ERR_ARG);
         EXPECT(std::strstr(fv_last_error(), "on_device") != nullptr);
     }
+    // and the gain solve: tpol, shapes, nant, antenna indices, null pointers, flags, max_iter, tol; without a baseline
+    // both return before any device call
+    {
+        const int a[3] = {0, 1, 2}, low[3] = {0, -1, 2}, high[3] = {0, 1, 3};
+        int niter = -1, solved[6] = {7, 7, 7, 7, 7, 7};
+        EXPECT(fv_gain_normal_rows(0, 3, 1, 3, 1, 3, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 2, 3, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "fv_gain_normal_rows: tpol must be 1 or 4") != nullptr);
+        EXPECT(fv_gain_normal_rows(0, 2, -1, 3, 1, 3, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, -3, 1, 3, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 1, 0, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 1, 3, a, a, nullptr, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 1, 3, a, a, v, v, v, nullptr, nullptr, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 1, 3, a, a, v, v, v, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 1, 3, nullptr, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 1, 3, a, a, v, nullptr, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 1, 3, a, a, v, v, nullptr, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 4, 3, low, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_gain_normal_rows(0, 2, 1, 3, 4, 3, a, high, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "antenna index outside [0, nant)") != nullptr);
+        double num[12], den[6];
+        EXPECT(fv_gain_normal_rows(0, 2, 2, 0, 1, 3, nullptr, nullptr, v, nullptr, nullptr, nullptr, num, den) == FV_OK);
+        EXPECT(num[11] == 0.0 && den[5] == 0.0);
+        EXPECT(fv_gain_solve(0, 3, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 2, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, -1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, -1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, -3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 0, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 0, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "max_iter must be positive") != nullptr);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, -1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, __builtin_nan(""), &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "tol must be non-negative") != nullptr);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 2, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 2, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, -1, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 3, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "must be 0 or 1") != nullptr);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, nullptr, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, nullptr, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, nullptr, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, nullptr, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, nullptr, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, nullptr, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 1, 3, a, a, 0, v, 0, nullptr, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 4, 3, low, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_gain_solve(0, 2, 1, 1, 3, 4, 3, a, high, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(niter == -1);
+        double gains[12] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12}, change[2] = {7, 7}, chi2[2] = {7, 7};
+        EXPECT(fv_gain_solve(0, 1, 1, 2, 0, 1, 3, nullptr, nullptr, 1, nullptr, 0, nullptr, 0, nullptr, 0, gains, 5, 0.0, &niter, change,
+                             chi2, solved) == FV_OK);
+        EXPECT(niter == 0 && gains[11] == 12 && change[1] == 0 && chi2[1] == 0 && solved[5] == 0);
+    }
     // a call that gets past the argument checks reports the missing device as a HIP error, not a crash
     if (ndev == 0) {
         EXPECT(fv_sim_create(&h, 0, 2, 1e-6, 2.0, 1) == FV_ERR_HIP && h == nullptr);

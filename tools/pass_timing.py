@@ -18,6 +18,7 @@
                                                                                     --gains; --config C5: through K = 4)
     gauss_newton    forward composed fused fused_device                             C3, 8 channels  (--case, --gains,
                                                                                     --d-gains; beam_coefs: --config C5)
+    gain_solve      forward solve solve_with_forward gauss_newton_products          C3, 8 channels
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -46,7 +47,11 @@ direction and the gain block of the product (``--case gains``: that direction al
 ``simulate_vis_gain_gauss_newton``, ``composed`` becomes the tangent and, with --d-gains, the forward to the host, the gain
 product, its tangent, conj(m) 2 w U' and the antennas' sums in torch on the device and the public adjoint on the host
 result, and ``--profile gain_kernels`` runs the kernels of fv_gain_weight_rows, fv_weight_rows and fv_gain_residual_chi2 alone
-on the block's shape, six times each, alternating.  A flag of another family is an error.
+on the block's shape, six times each, alternating.  gain_solve: the gains-only solve against a fixed model, 50 iterations
+per call (every value is the call's wall clock divided by the time steps, as everywhere) -- ``solve`` is
+simulate_vis_gain_solve on a resident model with resident data and weights, ``solve_with_forward`` the same from the sky (one
+forward, then the iterations), ``gauss_newton_products`` as many gains-only products of simulate_vis_gain_gauss_newton, each
+of which reruns the forward (``--profile solve`` for a kernel trace).  A flag of another family is an error.
 tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
 
 import argparse
@@ -464,6 +469,72 @@ def gauss_newton(a, fv, cfg, rng):
     return head, calls
 
 
+GAIN_SOLVE_ITERATIONS = 50
+
+
+def gain_solve(a, fv, cfg, rng):
+    """The gains-only solve against a fixed model: GAIN_SOLVE_ITERATIONS iterations of ``simulate_vis_gain_solve`` on a
+    resident model with resident data and weights (host to host: the gains go up and come back), next to as many gains-only
+    products of ``simulate_vis_gain_gauss_newton(d_gains=...)`` -- what an iteration of such a solve costs without it, every
+    call rerunning the forward.  ``--profile solve`` is one solve on a resident model, for a kernel trace (the forward and the
+    one-iteration solve that make the model are the only other work of the process)."""
+    import torch
+
+    p = cfg["precision"]
+    cdt, rdt = (np.complex64, np.float32) if p == 1 else (np.complex128, np.float64)
+    nums = list(cfg["ants"])
+    nant = len(nums)
+    gshape = ((nant, 2) if cfg["polarized"] else (nant,)) + (a.nfreq,)
+    g_true = 1 + 0.1 * (rng.normal(size=gshape) + 1j * rng.normal(size=gshape))
+    d_gains = (0.1 * (rng.normal(size=gshape) + 1j * rng.normal(size=gshape))).astype(cdt)
+    state = {}
+
+    def resident():  # the model from one forward, data = the gained model plus noise, the cross-hands flagged
+        if not state:
+            _, _, model = fv.simulate_vis_gain_solve(_zeros_like_vis(), **cfg, max_iter=1, tol=0.0, return_model=True)
+            G = torch.from_numpy(g_true).cuda()
+            a1 = torch.tensor([nums.index(b[0]) for b in cfg["baselines"]], device="cuda")
+            a2 = torch.tensor([nums.index(b[1]) for b in cfg["baselines"]], device="cuda")
+            if cfg["polarized"]:  # out[f, t, x, y, k]: y is the first antenna's feed
+                m = (G[a2].permute(2, 1, 0)[:, :, None, :] * G[a1].conj().permute(2, 1, 0)[:, None, :, :])[:, None]
+            else:
+                m = (G[a1].conj() * G[a2]).T[:, None]
+            data = m * model
+            noise = 0.05 * data.abs().mean()
+            data = (data + noise * torch.randn_like(data)).to(model.dtype)
+            w = torch.ones(model.shape, dtype=getattr(torch, np.dtype(rdt).name), device="cuda")
+            if cfg["polarized"]:
+                w[:, :, 0, 1] = 0
+                w[:, :, 1, 0] = 0
+            torch.cuda.synchronize()
+            state.update(model=model, data=data, w=w)
+        return state
+
+    def _zeros_like_vis():
+        nbls = len(cfg["baselines"])
+        return np.zeros((a.nfreq, a.ntimes, 2, 2, nbls) if cfg["polarized"] else (a.nfreq, a.ntimes, nbls), dtype=cdt)
+
+    def solve():
+        s = resident()
+        return fv.simulate_vis_gain_solve(s["data"], **dict(cfg, fluxes=None), weights=s["w"], model=s["model"],
+                                          max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    def solve_with_forward():  # the same from the sky: one forward, then the iterations
+        s = resident()
+        return fv.simulate_vis_gain_solve(s["data"], **cfg, weights=s["w"], max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    def products():
+        s = resident()
+        g = np.ones(gshape, dtype=cdt)
+        for _ in range(GAIN_SOLVE_ITERATIONS):
+            fv.simulate_vis_gain_gauss_newton(**cfg, gains=g, d_gains=d_gains, weights=s["w"], wrt="gains")
+
+    calls = {"forward": lambda: fv.simulate_vis(**cfg), "solve": solve, "solve_with_forward": solve_with_forward,
+             "gauss_newton_products": products}
+    head = {"config": a.config, "precision": p, "polarized": bool(cfg["polarized"]), "iterations": GAIN_SOLVE_ITERATIONS}
+    return head, calls
+
+
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
 #          ratios {key: (pass, pass it is divided by -- or a tuple of passes, for their sum)})
 FAMILIES = {
@@ -489,6 +560,8 @@ FAMILIES = {
     "gauss_newton": (gauss_newton, "C3", 8, ("case", "gains", "d_gains"), "runs", {
         "composed_over_forward": ("composed", "forward"), "fused_over_composed": ("fused", "composed"),
         "fused_device_over_composed": ("fused_device", "composed"), "fused_device_over_forward": ("fused_device", "forward")}),
+    "gain_solve": (gain_solve, "C3", 8, (), "runs", {
+        "solve_over_forward": ("solve", "forward"), "products_over_solve": ("gauss_newton_products", "solve")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
              "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False}  # and their defaults
