@@ -324,6 +324,17 @@ static void coherency_host(int device, int variant, int64_t n, const void *bi, c
     FV_HIP(hipGetLastError());
 }
 
+// The row passes on host arrays (fv_residual_chi2, fv_gain_residual_chi2, fv_weight_rows, fv_gain_weight_rows): every
+// array is copied into a buffer of its own on the call's stream (null stays null), the launcher queues the kernels, what
+// was computed in place is copied back and collect_rows ends the call.
+template <typename X>
+static X *to_device(hipStream_t s, DevBuf &buf, const void *host, size_t n) {
+    if (!host) return nullptr;
+    buf.reserve(sizeof(X) * n);
+    FV_HIP(hipMemcpyAsync(buf.p, host, sizeof(X) * n, hipMemcpyHostToDevice, s));
+    return buf.as<X>();
+}
+
 template <typename T>
 static void residual_chi2_host(int device, int64_t nrows, int64_t row_len, void *vis, const void *data, const void *weights,
                                double *chi2_rows) {
@@ -337,24 +348,13 @@ static void residual_chi2_host(int device, int64_t nrows, int64_t row_len, void 
     }
     StreamGuard sg;
     const size_t n = (size_t)nrows * (size_t)row_len;
-    const int nblk = residual_blocks_per_row<T>(row_len);
     DevBuf dv, dd, dw, ds;
-    dv.reserve(sizeof(cplx<T>) * n);
-    dd.reserve(sizeof(cplx<T>) * n);
-    if (weights) dw.reserve(sizeof(T) * n);
-    ds.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
-    double *partials = ds.as<double>(), *sums = partials + (size_t)nrows * nblk;
-    int *bad = reinterpret_cast<int *>(sums + nrows);
-    FV_HIP(hipMemcpyAsync(dv.p, vis, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
-    FV_HIP(hipMemcpyAsync(dd.p, data, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
-    if (weights) FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
-    launch_residual<T>(sg.s, dv.as<cplx<T>>(), dd.as<cplx<T>>(), weights ? dw.as<T>() : nullptr, nrows, row_len, partials, sums, bad);
-    int hbad[2] = {0, 0};
+    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
+    launch_residual<T>(sg.s, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<cplx<T>>(sg.s, dd, data, n),
+                       to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs);
     FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(chi2_rows, sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipStreamSynchronize(sg.s));
-    FV_HIP(hipGetLastError());
+    int hbad[2];
+    collect_rows(sg.s, rs, nrows, chi2_rows, hbad);
     throw_if_bad_residual_input(hbad);
 }
 
@@ -374,31 +374,18 @@ static void gain_residual_chi2_host(int device, int64_t nrows, int64_t nbls, int
     StreamGuard sg;
     const int64_t row_len = (int64_t)tpol * nbls;
     const size_t n = (size_t)nrows * (size_t)row_len;
-    const int nblk = residual_blocks_per_row<T>(row_len);
     GainPairs gp;
     gp.set(sg.s, nant, nbls, ant1, ant2);
     DevBuf dv, dd, dw, ds, dgn, dgg;
-    dv.reserve(sizeof(cplx<T>) * n);
-    dd.reserve(sizeof(cplx<T>) * n);
-    if (weights) dw.reserve(sizeof(T) * n);
-    dgn.reserve(sizeof(cplx<T>) * ng);
     if (ggains) dgg.reserve(sizeof(cplx<double>) * ng);
-    ds.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
-    double *partials = ds.as<double>(), *sums = partials + (size_t)nrows * nblk;
-    int *bad = reinterpret_cast<int *>(sums + nrows);
-    FV_HIP(hipMemcpyAsync(dv.p, vis, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
-    FV_HIP(hipMemcpyAsync(dd.p, data, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
-    if (weights) FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
-    FV_HIP(hipMemcpyAsync(dgn.p, gains, sizeof(cplx<T>) * ng, hipMemcpyHostToDevice, sg.s));
-    launch_gain_residual<T>(sg.s, dv.as<cplx<T>>(), dd.as<cplx<T>>(), weights ? dw.as<T>() : nullptr, dgn.as<cplx<T>>(), gp, nrows,
-                            tpol, partials, sums, bad, ggains ? dgg.as<cplx<double>>() : nullptr);
-    int hbad[2] = {0, 0};
+    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
+    launch_residual<T>(sg.s, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<cplx<T>>(sg.s, dd, data, n),
+                       to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs,
+                       {&gp, to_device<cplx<T>>(sg.s, dgn, gains, ng), nullptr, dgg.as<cplx<double>>()});
     FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(chi2_rows, sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
     if (ggains) FV_HIP(hipMemcpyAsync(ggains, dgg.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipStreamSynchronize(sg.s));
-    FV_HIP(hipGetLastError());
+    int hbad[2];
+    collect_rows(sg.s, rs, nrows, chi2_rows, hbad);
     throw_if_bad_residual_input(hbad);
 }
 
@@ -524,28 +511,14 @@ static void weight_rows_host(int device, int64_t nrows, int64_t row_len, int npa
     }
     StreamGuard sg;
     const size_t n = (size_t)nrows * (size_t)row_len;
-    const int nblk = residual_blocks_per_row<T>(row_len);
     DevBuf dp[4], dw, ds;
     cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < nparts; ++j) {
-        dp[j].reserve(sizeof(cplx<T>) * n);
-        dparts[j] = dp[j].as<cplx<T>>();
-        FV_HIP(hipMemcpyAsync(dp[j].p, parts[j], sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
-    }
-    if (weights) {
-        dw.reserve(sizeof(T) * n);
-        FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
-    }
-    ds.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
-    double *partials = ds.as<double>(), *sums = partials + (size_t)nrows * nblk;
-    int *bad = reinterpret_cast<int *>(sums + nrows);
-    launch_weight_rows<T>(sg.s, nparts, dparts, weights ? dw.as<T>() : nullptr, nrows, row_len, partials, sums, bad);
-    int hbad[2] = {0, 0};
+    for (int j = 0; j < nparts; ++j) dparts[j] = to_device<cplx<T>>(sg.s, dp[j], parts[j], n);
+    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
+    launch_weight_rows<T>(sg.s, nparts, dparts, to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs);
     FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(q_rows, sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipStreamSynchronize(sg.s));
-    FV_HIP(hipGetLastError());
+    int hbad[2];
+    collect_rows(sg.s, rs, nrows, q_rows, hbad);
     throw_if_bad_residual_input(hbad);
 }
 
@@ -565,47 +538,24 @@ static void gain_weight_rows_host(int device, int64_t nrows, int64_t nbls, int t
     StreamGuard sg;
     const int64_t row_len = (int64_t)tpol * nbls;
     const size_t n = (size_t)nrows * (size_t)row_len;
-    const int nblk = residual_blocks_per_row<T>(row_len);
     GainPairs gp;
     gp.set(sg.s, nant, nbls, ant1, ant2);
     DevBuf dp[4], dv, dw, ds, dgn, ddg, dhg;
     cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < nparts; ++j) {
-        dp[j].reserve(sizeof(cplx<T>) * n);
-        dparts[j] = dp[j].as<cplx<T>>();
-        FV_HIP(hipMemcpyAsync(dp[j].p, parts[j], sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
-    }
-    if (vis) {
-        dv.reserve(sizeof(cplx<T>) * n);
-        FV_HIP(hipMemcpyAsync(dv.p, vis, sizeof(cplx<T>) * n, hipMemcpyHostToDevice, sg.s));
-    }
-    if (weights) {
-        dw.reserve(sizeof(T) * n);
-        FV_HIP(hipMemcpyAsync(dw.p, weights, sizeof(T) * n, hipMemcpyHostToDevice, sg.s));
-    }
-    dgn.reserve(sizeof(cplx<T>) * ng);
-    FV_HIP(hipMemcpyAsync(dgn.p, gains, sizeof(cplx<T>) * ng, hipMemcpyHostToDevice, sg.s));
-    if (d_gains) {
-        ddg.reserve(sizeof(cplx<T>) * ng);
-        FV_HIP(hipMemcpyAsync(ddg.p, d_gains, sizeof(cplx<T>) * ng, hipMemcpyHostToDevice, sg.s));
-    }
+    for (int j = 0; j < nparts; ++j) dparts[j] = to_device<cplx<T>>(sg.s, dp[j], parts[j], n);
     if (hgains) dhg.reserve(sizeof(cplx<double>) * ng);
-    ds.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
-    double *partials = ds.as<double>(), *sums = partials + (size_t)nrows * nblk;
-    int *bad = reinterpret_cast<int *>(sums + nrows);
-    launch_gain_weight_rows<T>(sg.s, nparts, dparts, vis ? dv.as<cplx<T>>() : nullptr, weights ? dw.as<T>() : nullptr,
-                               dgn.as<cplx<T>>(), d_gains ? ddg.as<cplx<T>>() : nullptr, gp, nrows, tpol, partials, sums, bad,
-                               hgains ? dhg.as<cplx<double>>() : nullptr);
-    int hbad[2] = {0, 0};
+    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
+    launch_weight_rows<T>(sg.s, nparts, dparts, to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs,
+                          {&gp, to_device<cplx<T>>(sg.s, dgn, gains, ng), to_device<cplx<T>>(sg.s, ddg, d_gains, ng),
+                           dhg.as<cplx<double>>()},
+                          to_device<cplx<T>>(sg.s, dv, vis, n));
     if (nparts)  // G replaces P_0, or V for the gains-only direction
         FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
     else
         FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(q_rows, sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
     if (hgains) FV_HIP(hipMemcpyAsync(hgains, dhg.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipStreamSynchronize(sg.s));
-    FV_HIP(hipGetLastError());
+    int hbad[2];
+    collect_rows(sg.s, rs, nrows, q_rows, hbad);
     throw_if_bad_residual_input(hbad);
 }
 

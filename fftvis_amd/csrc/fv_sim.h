@@ -1465,89 +1465,216 @@ __global__ void k_count_nonfinite(const double *__restrict__ v, int64_t n, int *
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fused objective (fv_residual_chi2, fv_sim_run_residual; DESIGN.md "Fused objective").  The block of visibilities V is
-// nrows = nf nt rows of L = tpol nbls contiguous complex values; in place, per element,
-//     delta = V - d (T),   G = 2 w delta (T: two roundings and an exact doubling),   row sum += w |delta|^2 (fp64),
-// w = 1 without weights.  w == 0 flags the sample: G = 0 exactly, nothing is added and d is not used (a select, so NaN or
-// Inf there do not propagate).  One thread <-> one chunk of RES_W<T> = 16 / sizeof(T) elements aligned in the BLOCK's own
-// index (not the row's): 16 bytes of weights and twice 16 bytes of V and of d, read and written as 16-byte vectors when
-// the three arrays are 16-byte aligned (vec) and the chunk lies inside the row; the first and the last chunk of a row are
-// clipped to it and go element by element.  A block takes RES_CHUNKS consecutive groups of 256 chunks of its row, the
-// grid is (blocks per row, rows) -- rows beyond the grid's y limit are walked with its stride -- and every block writes
-// ONE fp64 partial, partials[row][block]: per thread in chunk order, an __shfl_xor tree inside the wave, then the waves
-// in order through LDS.  k_chi2_rows_reduce adds a row's partials in index order.  No floating-point atomics: the sums'
-// bits depend on the input alone.  Bad input is counted on the way (int atomics): bad[0] weights that are negative or not
-// finite, bad[1] data that are not finite where w > 0.
+// Row passes of a fit (DESIGN.md "Fused objective": the row walk).  A block of visibilities is nrows = nf nt rows of
+// L = tpol nbls contiguous complex values.  k_residual_rows (the objective) and k_weight_rows (the Gauss-Newton product)
+// walk it the same way, with and without per-antenna gains, and differ in their element function alone.  The pieces of
+// the walk stand here, once:
+//   Chunks (row_chunk, ChunkC, ChunkW).  One thread <-> one chunk of RES_W<T> = 16 / sizeof(T) elements aligned in the
+// BLOCK's own index (not the row's): 16 bytes of weights and twice 16 bytes of every complex array, read and written as
+// 16-byte vectors when all the arrays are 16-byte aligned (vec) and the chunk lies inside the row; the first and the last
+// chunk of a row are clipped to it and go element by element.  A block takes RES_CHUNKS consecutive groups of 256 chunks
+// of its row; the grid is (blocks per row, rows), and rows beyond the grid's y limit are walked with its stride.
+//   Row term (row_term).  What an element adds to its row's sum, w |x|^2, is formed in fp64 with one fused multiply-add,
+// the real part's square the fused one, written out so that every kernel, instance and path rounds it alike.
+//   Row tail (row_tail).  Every block writes ONE fp64 partial, partials[row][block]: per thread in chunk order, an
+// __shfl_xor tree inside the wave, then the waves in order through LDS.  k_chi2_rows_reduce adds a row's partials in
+// index order.  No floating-point atomics: the sums' bits depend on the input alone.  Bad input is counted on the way
+// (int atomics): bad[0] weights that are negative or not finite, bad[1] data that are not finite where w > 0.
+//   Gain view (GainView; the gains' layout and the feeds: "Per-antenna gains" below).  Element e of a row has
+// pol = e / nbls, k = e % nbls: a chunk finds (pol, k) of its first element with one division and carries them.  The
+// row's gains -- and their direction, when both fit GAIN_LDS_BYTES together -- are staged in dynamic LDS.  With
+// GAINS = false every member function is empty: no division, no index loads, no dynamic LDS.
 template <typename T>
 constexpr int RES_W = 16 / (int)sizeof(T);
 constexpr int RES_CHUNKS = 4;
+constexpr size_t GAIN_LDS_BYTES = 32768;
+struct RowChunk {
+    int64_t e0, a, b;  // the chunk's first element in the block's index, and its part [a, b) inside the row
+    bool whole;        // all of it inside the row, and vectors allowed
+};
+// chunk i (< RES_CHUNKS) of this thread in the row [lo, hi) of the block's index, c0 = lo / RES_W<T> the row's first
+// chunk; e0 >= hi: at or past the row's end, and so are the thread's later chunks.  (By value, with c0 from the kernel:
+// filling a reference and returning "ended" cost k_residual_rows<double, true> two VGPRs and with them occupancy 8.)
 template <typename T>
-__device__ __forceinline__ double residual_element(cplx<T> &v, const cplx<T> &d, T w, int &bad_w, int &bad_d) {
+__device__ __forceinline__ RowChunk row_chunk(int64_t c0, int64_t lo, int64_t hi, int i, int vec) {
+    constexpr int W = RES_W<T>;
+    const int64_t e0 = (c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x) * W;
+    return {e0, e0 > lo ? e0 : lo, e0 + W < hi ? e0 + W : hi, vec && e0 >= lo && e0 + W <= hi};
+}
+template <typename T>
+union ChunkC {  // a whole chunk of complex values: two 16-byte vectors
+    static constexpr int NV = RES_W<T> * (int)sizeof(cplx<T>) / 16;
+    uint4 q[NV];
+    cplx<T> c[RES_W<T>];
+    __device__ __forceinline__ void load(const cplx<T> *p) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) q[k] = reinterpret_cast<const uint4 *>(p)[k];
+    }
+    __device__ __forceinline__ void store(cplx<T> *p) const {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) reinterpret_cast<uint4 *>(p)[k] = q[k];
+    }
+};
+template <typename T>
+union ChunkW {  // a whole chunk of weights: one 16-byte vector
+    uint4 q;
+    T w[RES_W<T>];
+    __device__ __forceinline__ void load(const T *p) { q = *reinterpret_cast<const uint4 *>(p); }
+};
+template <typename T>
+__device__ __forceinline__ double row_term(T w, T xr, T xi) {
+#pragma clang fp contract(off)
+    const double dr = (double)xr, di = (double)xi;
+    return (double)w * __builtin_fma(dr, dr, di * di);
+}
+// a thread's sum s and its counts of bad input -> the block's partial of `row` and the counters; the closing barrier
+// lets the next row of this block write wave_sum, and the staged gains, again
+__device__ __forceinline__ void row_tail(double s, int bad_w, int bad_d, int64_t row, double *__restrict__ partials,
+                                         int *__restrict__ bad) {
+    __shared__ double wave_sum[4];
+    if (bad_w) atomicAdd(bad, bad_w);
+    if (bad_d) atomicAdd(bad + 1, bad_d);
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+    __syncthreads();
+}
+__device__ __forceinline__ void gain_feeds(int pol, int nfeed, int &p, int &q) {  // p: a1's feed, q: a2's
+    p = nfeed == 2 ? (pol & 1) : 0;
+    q = nfeed == 2 ? (pol >> 1) : 0;
+}
+template <typename T>
+struct PairGains {  // of one element: g1 = g[p, a1], g2 = g[q, a2], and the direction's h1, h2 (0 without one)
+    cplx<T> g1, g2, h1, h2;
+};
+template <typename T, bool GAINS>
+struct GainView {
+    const cplx<T> *gains, *dgains;  // the block's (nrows, nfeed nant); dgains null: no direction
+    const int *ant1, *ant2;
+    int nbls, nant, nfeed, in_lds;
+    const cplx<T> *g, *h;  // the row's, after stage()
+    int pol, k, p, q;      // of the current element, after seek()
+    __device__ __forceinline__ void stage(int64_t row) {
+        if constexpr (GAINS) {
+            extern __shared__ __align__(16) unsigned char gain_lds[];
+            const int ng = nfeed * nant;
+            g = gains + row * ng;
+            h = dgains ? dgains + row * ng : nullptr;
+            if (in_lds) {
+                cplx<T> *gl = reinterpret_cast<cplx<T> *>(gain_lds);
+                for (int i = threadIdx.x; i < ng; i += 256) gl[i] = g[i];
+                g = gl;
+                if (h) {
+                    for (int i = threadIdx.x; i < ng; i += 256) gl[ng + i] = h[i];
+                    h = gl + ng;
+                }
+                __syncthreads();
+            }
+        }
+    }
+    __device__ __forceinline__ void seek(int64_t e) {  // to element e of the row
+        if constexpr (GAINS) {
+            pol = (int)(e / nbls);
+            k = (int)(e - (int64_t)pol * nbls);
+            gain_feeds(pol, nfeed, p, q);
+        }
+    }
+    __device__ __forceinline__ void next() {
+        if constexpr (GAINS) {
+            if (++k == nbls) {
+                k = 0;
+                gain_feeds(++pol, nfeed, p, q);
+            }
+        }
+    }
+    __device__ __forceinline__ PairGains<T> pair() const {
+        const cplx<T> zero = {(T)0, (T)0};
+        if constexpr (GAINS) {
+            const int i1 = p * nant + ant1[k], i2 = q * nant + ant2[k];
+            return {g[i1], g[i2], h ? h[i1] : zero, h ? h[i2] : zero};
+        }
+        return {zero, zero, zero, zero};
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// Fused objective (fv_residual_chi2, fv_sim_run_residual) and per-antenna gains in it (fv_gain_residual_chi2,
+// fv_sim_run_residual_gains); DESIGN.md "Fused objective", "Gains".  In place, per element of the block V,
+//     delta = V - d (T),   G = 2 w delta (T: two roundings and an exact doubling),   row sum += w |delta|^2 (row_term),
+// w = 1 without weights.  w == 0 flags the sample: G = 0 exactly, nothing is added and d is not used (a select, so NaN or
+// Inf there do not propagate).  With gains (GAINS; g1, g2 of the element's baseline: "Per-antenna gains" below)
+//     m = conj(g1) g2,   V' = m V,   delta = V' - d,   G' = 2 (w delta),   stored G = conj(m) G',   row sum += w |delta|^2.
+// In T every operation rounds on its own (no contraction): the same arithmetic on any compiler, reproducible operation
+// by operation in a test.  The products are written out: the pragma is lexical and would not reach cmul.  With unit
+// gains m = 1 and the two instances give the same bits.
+template <typename T, bool GAINS>
+__device__ __forceinline__ double residual_element(cplx<T> &v, const cplx<T> &d, T w, const PairGains<T> &pg, int &bad_w,
+                                                   int &bad_d) {
+#pragma clang fp contract(off)
     if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
     if (!(w > (T)0)) {  // flagged (or counted above)
         v = {(T)0, (T)0};
         return 0.0;
     }
     if (!isfinite(d.re) || !isfinite(d.im)) ++bad_d;
-    const T dr = v.re - d.re, di = v.im - d.im;
-    v = {(T)2 * (w * dr), (T)2 * (w * di)};
-    return (double)w * ((double)dr * (double)dr + (double)di * (double)di);
+    T dr, di;
+    if constexpr (GAINS) {
+        const cplx<T> &g1 = pg.g1, &g2 = pg.g2;
+        const T mr = g1.re * g2.re + g1.im * g2.im, mi = g1.re * g2.im - g1.im * g2.re;  // m = conj(g1) g2
+        dr = (mr * v.re - mi * v.im) - d.re;                                             // delta = m V - d
+        di = (mr * v.im + mi * v.re) - d.im;
+        const T gr = (T)2 * (w * dr), gi = (T)2 * (w * di);  // G'
+        v = {mr * gr + mi * gi, mr * gi - mi * gr};          // conj(m) G'
+    } else {
+        dr = v.re - d.re;
+        di = v.im - d.im;
+        v = {(T)2 * (w * dr), (T)2 * (w * di)};
+    }
+    return row_term<T>(w, dr, di);
 }
-template <typename T>
-__global__ void __launch_bounds__(256) k_residual_rows(cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data,
-                                                       const T *__restrict__ weights, int64_t nrows, int64_t L, int vec,
-                                                       double *__restrict__ partials, int *__restrict__ bad) {
+template <typename T, bool GAINS>
+__global__ void __launch_bounds__(256)
+    k_residual_rows(cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
+                    const cplx<T> *__restrict__ gains, const int *__restrict__ ant1, const int *__restrict__ ant2, int64_t nrows,
+                    int64_t L, int nbls, int nant, int nfeed, int in_lds, int vec, double *__restrict__ partials,
+                    int *__restrict__ bad) {
     constexpr int W = RES_W<T>;
-    constexpr int NV = W * (int)sizeof(cplx<T>) / 16;  // 16-byte vectors of V (and of d) per chunk: 2
-    __shared__ double wave_sum[4];
+    GainView<T, GAINS> gv{gains, nullptr, ant1, ant2, nbls, nant, nfeed, in_lds};
     for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
-        const int64_t lo = row * L, hi = lo + L;  // the row in the block's index
-        const int64_t c0 = lo / W;                // its first chunk
+        gv.stage(row);
+        const int64_t lo = row * L, hi = lo + L, c0 = lo / W;  // the row in the block's index, and its first chunk
         double s = 0.0;
         int bad_w = 0, bad_d = 0;
         for (int i = 0; i < RES_CHUNKS; ++i) {
-            const int64_t c = c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x;
-            const int64_t e0 = c * W;
-            if (e0 >= hi) break;
-            if (vec && e0 >= lo && e0 + W <= hi) {
-                union {
-                    uint4 q[NV];
-                    cplx<T> c[W];
-                } v, d;
-                union {
-                    uint4 q;
-                    T w[W];
-                } ww;
+            const RowChunk c = row_chunk<T>(c0, lo, hi, i, vec);
+            if (c.e0 >= hi) break;
+            gv.seek(c.a - lo);
+            if (c.whole) {
+                ChunkC<T> v, d;
+                ChunkW<T> ww;
+                v.load(vis + c.e0);
+                d.load(data + c.e0);
+                if (weights) ww.load(weights + c.e0);
 #pragma unroll
-                for (int k = 0; k < NV; ++k) {
-                    v.q[k] = reinterpret_cast<const uint4 *>(vis + e0)[k];
-                    d.q[k] = reinterpret_cast<const uint4 *>(data + e0)[k];
+                for (int j = 0; j < W; ++j) {
+                    s += residual_element<T, GAINS>(v.c[j], d.c[j], weights ? ww.w[j] : (T)1, gv.pair(), bad_w, bad_d);
+                    gv.next();
                 }
-                if (weights) ww.q = *reinterpret_cast<const uint4 *>(weights + e0);
-#pragma unroll
-                for (int k = 0; k < W; ++k) s += residual_element<T>(v.c[k], d.c[k], weights ? ww.w[k] : (T)1, bad_w, bad_d);
-#pragma unroll
-                for (int k = 0; k < NV; ++k) reinterpret_cast<uint4 *>(vis + e0)[k] = v.q[k];
+                v.store(vis + c.e0);
             } else {
-                const int64_t a = e0 > lo ? e0 : lo, b = e0 + W < hi ? e0 + W : hi;
-                for (int64_t e = a; e < b; ++e) {
+                for (int64_t e = c.a; e < c.b; ++e) {
                     cplx<T> v = vis[e];
-                    s += residual_element<T>(v, data[e], weights ? weights[e] : (T)1, bad_w, bad_d);
+                    s += residual_element<T, GAINS>(v, data[e], weights ? weights[e] : (T)1, gv.pair(), bad_w, bad_d);
                     vis[e] = v;
+                    gv.next();
                 }
             }
         }
-        if (bad_w) atomicAdd(bad, bad_w);
-        if (bad_d) atomicAdd(bad + 1, bad_d);
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
-        __syncthreads();  // (the next row of this block writes wave_sum again)
+        row_tail(s, bad_w, bad_d, row, partials, bad);
     }
 }
-// chi2_rows[row] = a row's partials added in index order (k_residual_rows)
+// chi2_rows[row] = a row's partials added in index order (row_tail)
 __global__ void k_chi2_rows_reduce(const double *__restrict__ partials, int64_t nrows, int nblk, double *__restrict__ chi2_rows) {
     const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= nrows) return;
@@ -1555,26 +1682,27 @@ __global__ void k_chi2_rows_reduce(const double *__restrict__ partials, int64_t 
     for (int b = 0; b < nblk; ++b) s += partials[row * nblk + b];
     chi2_rows[row] = s;
 }
-// blocks per row of k_residual_rows: the chunks a row of L elements can touch (one more than its own when it starts
-// inside a chunk), RES_CHUNKS * 256 per block
+// blocks per row of a row pass: the chunks a row of L elements can touch (one more than its own when it starts inside a
+// chunk), RES_CHUNKS * 256 per block
 template <typename T>
 inline int residual_blocks_per_row(int64_t L) {
     return (int)std::max<int64_t>(1, cdiv(cdiv(L, RES_W<T>) + 1, (int64_t)RES_CHUNKS * 256));
 }
-// Queues the two kernels on `on`: vis (nrows, L) in place, chi2_rows nrows doubles, partials nrows * blocks-per-row
-// doubles, bad two ints (zeroed here).  All device pointers; weights may be null.
+// A row pass's scratch, carved out of one buffer (reserved here): partials nrows * nblk doubles, the rows' sums nrows
+// doubles, then the two counters.
+struct RowScratch {
+    int nblk;  // blocks per row
+    double *partials, *sums;
+    int *bad;
+};
 template <typename T>
-inline void launch_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *data, const T *weights, int64_t nrows, int64_t L,
-                            double *partials, double *chi2_rows, int *bad) {
+inline RowScratch row_scratch(DevBuf &buf, int64_t nrows, int64_t L) {
     const int nblk = residual_blocks_per_row<T>(L);
-    const int vec = ((reinterpret_cast<uintptr_t>(vis) | reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;
-    FV_HIP(hipMemsetAsync(bad, 0, 2 * sizeof(int), on));
-    hipLaunchKernelGGL(k_residual_rows<T>, dim3((unsigned)nblk, (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, on, vis,
-                       data, weights, nrows, L, vec, partials, bad);
-    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
-                       chi2_rows);
+    buf.reserve(sizeof(double) * (size_t)nrows * (nblk + 1) + 16);
+    double *partials = buf.as<double>(), *sums = partials + (size_t)nrows * nblk;
+    return {nblk, partials, sums, reinterpret_cast<int *>(sums + nrows)};
 }
-// the message of a call that met bad input (k_residual_rows' counters)
+// the message of a call that met bad input (row_tail's counters)
 inline void throw_if_bad_residual_input(const int bad[2]) {
     if (bad[0])
         throw Error(FV_ERR_ARG, std::to_string(bad[0]) + " weights are negative or not finite (weights are inverse variances; 0 "
@@ -1583,239 +1711,136 @@ inline void throw_if_bad_residual_input(const int bad[2]) {
         throw Error(FV_ERR_ARG, std::to_string(bad[1]) + " entries of data are not finite where the weight is positive (flag "
                                                          "them with weight 0)");
 }
+// What every row pass ends with: the rows' sums and the counters come to the host (hbad) behind whatever else the caller
+// queued on `on`, with one synchronisation.
+inline void collect_rows(hipStream_t on, const RowScratch &rs, int64_t nrows, double *rows_host, int hbad[2]) {
+    hbad[0] = hbad[1] = 0;
+    FV_HIP(hipMemcpyAsync(rows_host, rs.sums, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, on));
+    FV_HIP(hipMemcpyAsync(hbad, rs.bad, 2 * sizeof(int), hipMemcpyDeviceToHost, on));
+    FV_HIP(hipStreamSynchronize(on));
+    FV_HIP(hipGetLastError());
+}
 
 // ---------------------------------------------------------------------------------------------
-// Gauss-Newton product (fv_weight_rows, fv_sim_weight_block; DESIGN.md "Gauss-Newton product").  The tangent J p of a
-// block arrives as NP = 1 .. 4 part blocks P_0 .. P_{NP-1} of k_residual_rows' shape (one per tangent pass); per element,
-// in the run's precision T and in this order,
+// Gauss-Newton product (fv_weight_rows, fv_sim_weight_block) and the same with per-antenna gains and a gain direction
+// (fv_gain_weight_rows, fv_sim_gain_weight_block); DESIGN.md "Gauss-Newton product", "Gains in the Gauss-Newton product".
+// The tangent J p of a block arrives as NP part blocks P_0 .. P_{NP-1} of the block's shape (one per tangent pass); per
+// element, in the run's precision T and in this order,
 //     U = ((P_0 + P_1) + P_2) + P_3 (component-wise, only the parts given),   G = 2 (w U) (one rounding per component
-//     and an exact doubling),   row sum += w |U|^2 (every term formed and added in fp64),
+//     and an exact doubling),   row sum += w |U|^2 (row_term),
 // w = 1 without weights; G replaces P_0.  w == 0 flags the sample: G = 0 exactly, nothing is added and the parts are not
-// used there (a select).  Chunks, clipping, the vector path (every part and the weights 16-byte aligned), the grid, the
-// one fp64 partial per block and the reduction (k_chi2_rows_reduce) are k_residual_rows'; bad[0] counts the weights that
-// are negative or not finite, bad[1] stays 0.
+// used there (a select).  NP = 1 .. 4.  With gains (GAINS; NP = 0 .. 4, U = 0 for NP = 0, the gains-only direction), V the
+// forward at the real parameters and h1, h2 the direction's entries where the gains have g1, g2,
+//     m = conj(g1) g2,   dm = conj(h1) g2 + conj(g1) h2 (dm = 0 without a gain direction),   U' = m U + dm V,
+//     G' = 2 (w U'),   stored G = conj(m) G',   row sum += w |U'|^2.
+// V is read only with a gain direction; G replaces P_0, or V for NP = 0.  In T every operation rounds on its own, in the
+// order written (residual_element): with unit gains and no direction m = 1, m U = U and conj(m) G' = G' exactly, and the
+// two instances give the same bits.  bad[0] counts the weights that are negative or not finite, bad[1] stays 0.
 template <typename T>
 struct WeightParts {
     cplx<T> *p[4];
 };
-template <typename T>
-__device__ __forceinline__ double weight_element(cplx<T> &u, T w, int &bad_w) {
+template <typename T, bool GAINS>
+__device__ __forceinline__ double weight_element(cplx<T> &u, const cplx<T> &v, T w, const PairGains<T> &pg, bool sky, bool dir,
+                                                 int &bad_w) {
+#pragma clang fp contract(off)
     if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
     if (!(w > (T)0)) {  // flagged (or counted above)
         u = {(T)0, (T)0};
         return 0.0;
     }
-    const T ur = u.re, ui = u.im;
-    u = {(T)2 * (w * ur), (T)2 * (w * ui)};
-    return (double)w * ((double)ur * (double)ur + (double)ui * (double)ui);
+    T ur = u.re, ui = u.im;
+    if constexpr (GAINS) {
+        const cplx<T> &g1 = pg.g1, &g2 = pg.g2, &h1 = pg.h1, &h2 = pg.h2;
+        const T mr = g1.re * g2.re + g1.im * g2.im, mi = g1.re * g2.im - g1.im * g2.re;  // m = conj(g1) g2
+        ur = mr * u.re - mi * u.im;                                                      // m U
+        ui = mr * u.im + mi * u.re;
+        if (dir) {
+            const T dmr = (h1.re * g2.re + h1.im * g2.im) + (g1.re * h2.re + g1.im * h2.im);  // dm = conj(h1) g2 + conj(g1) h2
+            const T dmi = (h1.re * g2.im - h1.im * g2.re) + (g1.re * h2.im - g1.im * h2.re);
+            const T tr = dmr * v.re - dmi * v.im, ti = dmr * v.im + dmi * v.re;  // dm V
+            ur = sky ? ur + tr : tr;                                             // U' = m U + dm V (dm V alone for NP = 0)
+            ui = sky ? ui + ti : ti;
+        }
+        const T gr = (T)2 * (w * ur), gi = (T)2 * (w * ui);  // G'
+        u = {mr * gr + mi * gi, mr * gi - mi * gr};          // conj(m) G'
+    } else {
+        u = {(T)2 * (w * ur), (T)2 * (w * ui)};
+    }
+    return row_term<T>(w, ur, ui);
 }
-template <typename T, int NP>
-__global__ void __launch_bounds__(256) k_weight_rows(WeightParts<T> parts, const T *__restrict__ weights, int64_t nrows, int64_t L,
-                                                     int vec, double *__restrict__ partials, int *__restrict__ bad) {
+template <typename T, int NP, bool GAINS>
+__global__ void __launch_bounds__(256)
+    k_weight_rows(WeightParts<T> parts, cplx<T> *__restrict__ vis, const T *__restrict__ weights, const cplx<T> *__restrict__ gains,
+                  const cplx<T> *__restrict__ dgains, const int *__restrict__ ant1, const int *__restrict__ ant2, int64_t nrows,
+                  int64_t L, int nbls, int nant, int nfeed, int in_lds, int vec, double *__restrict__ partials,
+                  int *__restrict__ bad) {
+    static_assert(NP >= (GAINS ? 0 : 1) && NP <= 4, "NP = 1 .. 4, or 0 .. 4 with gains");
     constexpr int W = RES_W<T>;
-    constexpr int NV = W * (int)sizeof(cplx<T>) / 16;  // 16-byte vectors of a part per chunk: 2
-    __shared__ double wave_sum[4];
+    GainView<T, GAINS> gv{gains, dgains, ant1, ant2, nbls, nant, nfeed, in_lds};
+    const bool dir = GAINS && dgains != nullptr;
+    cplx<T> *const out = NP ? parts.p[0] : vis;  // where G goes
+    const cplx<T> zero = {(T)0, (T)0};
     for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
-        const int64_t lo = row * L, hi = lo + L;  // the row in the block's index
-        const int64_t c0 = lo / W;                // its first chunk
+        gv.stage(row);
+        const int64_t lo = row * L, hi = lo + L, c0 = lo / W;  // the row in the block's index, and its first chunk
         double s = 0.0;
         int bad_w = 0;
         for (int i = 0; i < RES_CHUNKS; ++i) {
-            const int64_t c = c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x;
-            const int64_t e0 = c * W;
-            if (e0 >= hi) break;
-            if (vec && e0 >= lo && e0 + W <= hi) {
-                union {
-                    uint4 q[NV];
-                    cplx<T> c[W];
-                } u, a;
-                union {
-                    uint4 q;
-                    T w[W];
-                } ww;
+            const RowChunk c = row_chunk<T>(c0, lo, hi, i, vec);
+            if (c.e0 >= hi) break;
+            gv.seek(c.a - lo);
+            if (c.whole) {
+                ChunkC<T> u, t;
+                ChunkW<T> ww;
+                if (NP) {
+                    u.load(parts.p[0] + c.e0);
 #pragma unroll
-                for (int k = 0; k < NV; ++k) u.q[k] = reinterpret_cast<const uint4 *>(parts.p[0] + e0)[k];
+                    for (int n = 1; n < NP; ++n) {
+                        t.load(parts.p[n] + c.e0);
 #pragma unroll
-                for (int j = 1; j < NP; ++j) {
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) a.q[k] = reinterpret_cast<const uint4 *>(parts.p[j] + e0)[k];
-#pragma unroll
-                    for (int k = 0; k < W; ++k) u.c[k] = {u.c[k].re + a.c[k].re, u.c[k].im + a.c[k].im};
+                        for (int j = 0; j < W; ++j) u.c[j] = {u.c[j].re + t.c[j].re, u.c[j].im + t.c[j].im};
+                    }
                 }
-                if (weights) ww.q = *reinterpret_cast<const uint4 *>(weights + e0);
+                if (dir) t.load(vis + c.e0);
+                if (weights) ww.load(weights + c.e0);
 #pragma unroll
-                for (int k = 0; k < W; ++k) s += weight_element<T>(u.c[k], weights ? ww.w[k] : (T)1, bad_w);
-#pragma unroll
-                for (int k = 0; k < NV; ++k) reinterpret_cast<uint4 *>(parts.p[0] + e0)[k] = u.q[k];
+                for (int j = 0; j < W; ++j) {
+                    if (!NP) u.c[j] = zero;
+                    s += weight_element<T, GAINS>(u.c[j], dir ? t.c[j] : zero, weights ? ww.w[j] : (T)1, gv.pair(), NP != 0, dir,
+                                                  bad_w);
+                    gv.next();
+                }
+                u.store(out + c.e0);
             } else {
-                const int64_t a = e0 > lo ? e0 : lo, b = e0 + W < hi ? e0 + W : hi;
-                for (int64_t e = a; e < b; ++e) {
-                    cplx<T> u = parts.p[0][e];
+                for (int64_t e = c.a; e < c.b; ++e) {
+                    cplx<T> u = zero;
+                    if (NP) u = parts.p[0][e];
 #pragma unroll
-                    for (int j = 1; j < NP; ++j) u = {u.re + parts.p[j][e].re, u.im + parts.p[j][e].im};
-                    s += weight_element<T>(u, weights ? weights[e] : (T)1, bad_w);
-                    parts.p[0][e] = u;
+                    for (int n = 1; n < NP; ++n) u = {u.re + parts.p[n][e].re, u.im + parts.p[n][e].im};
+                    s += weight_element<T, GAINS>(u, dir ? vis[e] : zero, weights ? weights[e] : (T)1, gv.pair(), NP != 0, dir,
+                                                  bad_w);
+                    out[e] = u;
+                    gv.next();
                 }
             }
         }
-        if (bad_w) atomicAdd(bad, bad_w);
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
-        __syncthreads();  // (the next row of this block writes wave_sum again)
+        row_tail(s, bad_w, 0, row, partials, bad);
     }
-}
-// Queues the two kernels on `on`: parts[0 .. nparts) device blocks (nrows, L), G in place in parts[0], q_rows nrows
-// doubles, partials nrows * blocks-per-row doubles, bad two ints (zeroed here).  weights may be null.
-template <typename T>
-inline void launch_weight_rows(hipStream_t on, int nparts, cplx<T> *const *parts, const T *weights, int64_t nrows, int64_t L,
-                               double *partials, double *q_rows, int *bad) {
-    const int nblk = residual_blocks_per_row<T>(L);
-    WeightParts<T> wp{};
-    uintptr_t bits = reinterpret_cast<uintptr_t>(weights);
-    for (int j = 0; j < nparts; ++j) {
-        wp.p[j] = parts[j];
-        bits |= reinterpret_cast<uintptr_t>(parts[j]);
-    }
-    const int vec = (bits & 15) == 0;
-    const dim3 grid((unsigned)nblk, (unsigned)std::min<int64_t>(nrows, 65535));
-    FV_HIP(hipMemsetAsync(bad, 0, 2 * sizeof(int), on));
-    switch (nparts) {
-    case 1: hipLaunchKernelGGL((k_weight_rows<T, 1>), grid, dim3(256), 0, on, wp, weights, nrows, L, vec, partials, bad); break;
-    case 2: hipLaunchKernelGGL((k_weight_rows<T, 2>), grid, dim3(256), 0, on, wp, weights, nrows, L, vec, partials, bad); break;
-    case 3: hipLaunchKernelGGL((k_weight_rows<T, 3>), grid, dim3(256), 0, on, wp, weights, nrows, L, vec, partials, bad); break;
-    case 4: hipLaunchKernelGGL((k_weight_rows<T, 4>), grid, dim3(256), 0, on, wp, weights, nrows, L, vec, partials, bad); break;
-    default: throw Error(FV_ERR_ARG, "nparts must be 1 .. 4");
-    }
-    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
-                       q_rows);
 }
 
 // ---------------------------------------------------------------------------------------------
-// Per-antenna gains in the fused objective (fv_gain_residual_chi2, fv_sim_run_residual_gains; DESIGN.md "Gains").  The
-// block is k_residual_rows': nrows rows of L = tpol nbls values, element e of a row has pol = e / nbls, k = e % nbls.
+// Per-antenna gains (fv_gain_residual_chi2, fv_sim_run_residual_gains; DESIGN.md "Gains").  The block is the row
+// passes': nrows rows of L = tpol nbls values, element e of a row has pol = e / nbls, k = e % nbls.
 // Baseline k = (a1, a2) = (ant1[k], ant2[k]); a row's gains are nfeed nant complex values of the run's precision,
 // g[feed nant + ant], nfeed = 1 (tpol 1) or 2 (tpol 4).  Of the polarized output's two feed axes the MINOR one is
 // antenna a1's (the conjugated one; out[.., x, y, k] = (A_a1^H C A_a2)[y, x]): pol = 2 q + p with p a1's feed and q a2's.
-//     m = conj(g[a1, p]) g[a2, q],   V' = m V,   delta = V' - d,   G' = 2 (w delta),   stored G = conj(m) G',
-//     row sum += w |delta|^2,   ggains[a, f] = sum_{k: a1 = a, p = f} conj(G') g[a2, q] V + sum_{k: a2 = a, q = f} G' g[a1, p] conj(V).
+// With m, V', delta and G' of k_residual_rows<T, true>,
+//     ggains[a, f] = sum_{k: a1 = a, p = f} conj(G') g[a2, q] V + sum_{k: a2 = a, q = f} G' g[a1, p] conj(V).
 // Two kernels, no floating-point atomics.  k_gain_gradient runs first, while the block still holds V: a gather over the
 // per-antenna incidence lists (CSR; entry = 2 k + side, ascending, side 0 = "a is a1"), one wave per (row, feed, antenna),
 // lane l takes the entries l, l + 64, ... in order, everything in fp64 from the T-typed inputs, an __shfl_xor tree, one
-// complex128 per wave.  k_gain_residual_rows is k_residual_rows with the product folded in (all in T; the row sum's terms
-// in fp64): the same chunks, vector path, clipping, grid, partials and counters; a chunk finds (pol, k) of its first
-// element with one division and carries them; the row's gains are staged in LDS when they fit GAIN_LDS_BYTES.
-constexpr size_t GAIN_LDS_BYTES = 32768;
-__device__ __forceinline__ void gain_feeds(int pol, int nfeed, int &p, int &q) {  // p: a1's feed, q: a2's
-    p = nfeed == 2 ? (pol & 1) : 0;
-    q = nfeed == 2 ? (pol >> 1) : 0;
-}
-template <typename T>
-__device__ __forceinline__ double gain_residual_element(cplx<T> &v, const cplx<T> &d, T w, const cplx<T> &g1, const cplx<T> &g2,
-                                                        int &bad_w, int &bad_d) {
-    if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
-    if (!(w > (T)0)) {  // flagged (or counted above)
-        v = {(T)0, (T)0};
-        return 0.0;
-    }
-    if (!isfinite(d.re) || !isfinite(d.im)) ++bad_d;
-    T dr, di;
-    {
-        // In T every operation rounds on its own (no contraction): the same arithmetic on any compiler, reproducible
-        // operation by operation in a test.  The products are written out: the pragma is lexical and would not reach cmul.
-#pragma clang fp contract(off)
-        const T mr = g1.re * g2.re + g1.im * g2.im, mi = g1.re * g2.im - g1.im * g2.re;  // m = conj(g1) g2
-        dr = (mr * v.re - mi * v.im) - d.re;                                             // delta = m V - d
-        di = (mr * v.im + mi * v.re) - d.im;
-        const T gr = (T)2 * (w * dr), gi = (T)2 * (w * di);  // G'
-        v = {mr * gr + mi * gi, mr * gi - mi * gr};          // conj(m) G'
-    }
-    // (residual_element's expression, compiled as it is there: with unit gains the two kernels give the same bits)
-    return (double)w * ((double)dr * (double)dr + (double)di * (double)di);
-}
-template <typename T>
-__global__ void __launch_bounds__(256)
-    k_gain_residual_rows(cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
-                         const cplx<T> *__restrict__ gains, const int *__restrict__ ant1, const int *__restrict__ ant2,
-                         int64_t nrows, int nbls, int tpol, int nant, int in_lds, int vec, double *__restrict__ partials,
-                         int *__restrict__ bad) {
-    constexpr int W = RES_W<T>;
-    constexpr int NV = W * (int)sizeof(cplx<T>) / 16;  // 16-byte vectors of V (and of d) per chunk: 2
-    extern __shared__ __align__(16) unsigned char gain_lds[];
-    __shared__ double wave_sum[4];
-    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
-    const int64_t L = (int64_t)tpol * nbls;
-    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
-        const cplx<T> *g = gains + row * ng;
-        if (in_lds) {
-            cplx<T> *gl = reinterpret_cast<cplx<T> *>(gain_lds);
-            for (int i = threadIdx.x; i < ng; i += 256) gl[i] = g[i];
-            g = gl;
-            __syncthreads();
-        }
-        const int64_t lo = row * L, hi = lo + L;  // the row in the block's index
-        const int64_t c0 = lo / W;                // its first chunk
-        double s = 0.0;
-        int bad_w = 0, bad_d = 0;
-        for (int i = 0; i < RES_CHUNKS; ++i) {
-            const int64_t c = c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x;
-            const int64_t e0 = c * W;
-            if (e0 >= hi) break;
-            const int64_t a = e0 > lo ? e0 : lo, b = e0 + W < hi ? e0 + W : hi;
-            int pol = (int)((a - lo) / nbls), k = (int)((a - lo) - (int64_t)pol * nbls);  // of element a; carried below
-            int p, q;
-            gain_feeds(pol, nfeed, p, q);
-            if (vec && e0 >= lo && e0 + W <= hi) {
-                union {
-                    uint4 q[NV];
-                    cplx<T> c[W];
-                } v, d;
-                union {
-                    uint4 q;
-                    T w[W];
-                } ww;
-#pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    v.q[j] = reinterpret_cast<const uint4 *>(vis + e0)[j];
-                    d.q[j] = reinterpret_cast<const uint4 *>(data + e0)[j];
-                }
-                if (weights) ww.q = *reinterpret_cast<const uint4 *>(weights + e0);
-#pragma unroll
-                for (int j = 0; j < W; ++j) {
-                    s += gain_residual_element<T>(v.c[j], d.c[j], weights ? ww.w[j] : (T)1, g[p * nant + ant1[k]],
-                                                  g[q * nant + ant2[k]], bad_w, bad_d);
-                    if (++k == nbls) {
-                        k = 0;
-                        gain_feeds(++pol, nfeed, p, q);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < NV; ++j) reinterpret_cast<uint4 *>(vis + e0)[j] = v.q[j];
-            } else {
-                for (int64_t e = a; e < b; ++e) {
-                    cplx<T> v = vis[e];
-                    s += gain_residual_element<T>(v, data[e], weights ? weights[e] : (T)1, g[p * nant + ant1[k]],
-                                                  g[q * nant + ant2[k]], bad_w, bad_d);
-                    vis[e] = v;
-                    if (++k == nbls) {
-                        k = 0;
-                        gain_feeds(++pol, nfeed, p, q);
-                    }
-                }
-            }
-        }
-        if (bad_w) atomicAdd(bad, bad_w);
-        if (bad_d) atomicAdd(bad + 1, bad_d);
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
-        __syncthreads();  // (the next row of this block writes wave_sum and the staged gains again)
-    }
-}
+// complex128 per wave.  k_residual_rows<T, true> follows.
 // ggains[(row nfeed + feed) nant + a]: one wave per (row, feed, antenna); see above.  vis still holds V.
 template <typename T>
 __global__ void __launch_bounds__(256)
@@ -1910,30 +1935,6 @@ struct GainPairs {
         nbls = nbls_;
     }
 };
-// Queues the gather (when ggains is not null), the in-place kernel and the rows' reduction on `on`: launch_residual's
-// arguments, the row's gains (nrows, nfeed nant) and the pairs; ggains (nrows, nfeed nant) complex128.  All device
-// pointers; weights and ggains may be null.
-template <typename T>
-inline void launch_gain_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *data, const T *weights, const cplx<T> *gains,
-                                 const GainPairs &gp, int64_t nrows, int tpol, double *partials, double *chi2_rows, int *bad,
-                                 cplx<double> *ggains) {
-    const int nbls = (int)gp.nbls, nant = gp.nant, ng = (tpol == 4 ? 2 : 1) * nant;
-    const int64_t L = (int64_t)tpol * nbls;
-    const int nblk = residual_blocks_per_row<T>(L);
-    const int vec = ((reinterpret_cast<uintptr_t>(vis) | reinterpret_cast<uintptr_t>(data) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;
-    const unsigned rows_y = (unsigned)std::min<int64_t>(nrows, 65535);
-    FV_HIP(hipMemsetAsync(bad, 0, 2 * sizeof(int), on));
-    if (ggains)
-        hipLaunchKernelGGL(k_gain_gradient<T>, dim3((unsigned)cdiv(ng, 4), rows_y), dim3(256), 0, on, (const cplx<T> *)vis, data,
-                           weights, gains, gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), gp.d_off.as<int>(), gp.d_inc.as<int>(), nrows,
-                           nbls, tpol, nant, ggains);
-    const size_t lds = sizeof(cplx<T>) * (size_t)ng;
-    const int in_lds = lds <= GAIN_LDS_BYTES;
-    hipLaunchKernelGGL(k_gain_residual_rows<T>, dim3((unsigned)nblk, rows_y), dim3(256), in_lds ? lds : 0, on, vis, data, weights,
-                       gains, gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), nrows, nbls, tpol, nant, in_lds, vec, partials, bad);
-    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
-                       chi2_rows);
-}
 
 // ---------------------------------------------------------------------------------------------
 // Gain solve on a resident model (fv_gain_normal_rows, fv_gain_solve; DESIGN.md "Gain solve").  The block, the pairs, the
@@ -2117,170 +2118,15 @@ inline void throw_if_bad_solve_input(const int bad[3]) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Gauss-Newton product with per-antenna gains and a gain direction (fv_gain_weight_rows, fv_sim_gain_weight_block;
-// DESIGN.md "Gains in the Gauss-Newton product").  The block, the pairs, the feeds and the gains' layout are the gain
-// kernels' above; dg is the gain direction in the gains' layout, or null.  Per element of baseline k = (a1, a2), with
-// g1 = g[p, a1], g2 = g[q, a2], h1 = dg[p, a1], h2 = dg[q, a2], U the sum of the NP = 0 .. 4 sky tangent parts as in
-// k_weight_rows (U = 0 for NP = 0, the gains-only direction) and V the forward at the real parameters,
-//     m = conj(g1) g2,   dm = conj(h1) g2 + conj(g1) h2 (dm = 0 without a gain direction),   U' = m U + dm V,
-//     G' = 2 (w U'),   stored G = conj(m) G',   row sum += w |U'|^2 (terms formed and added in fp64),
+// The gain gradient of the Gauss-Newton product with gains (fv_gain_weight_rows, fv_sim_gain_weight_block; DESIGN.md
+// "Gains in the Gauss-Newton product").  The block, the pairs, the feeds and the gains' layout are the gain kernels'
+// above; dg is the gain direction in the gains' layout, or null.  With g1, g2, h1, h2, m, dm, U' and G' of
+// k_weight_rows<T, NP, true>,
 //     hgains[a, f] = sum_{k: a1 = a, p = f} conj(G') g2 V + sum_{k: a2 = a, q = f} G' g1 conj(V).
-// Two kernels, no floating-point atomics.  k_gain_weight_gather is k_gain_gradient with this G' in place of
-// 2 w (V' - d): it runs first, while the blocks still hold the parts and V, one wave per (row, feed, antenna) over the
-// incidence lists, everything in fp64 from the T-typed inputs (U summed in fp64 in the parts' order), an __shfl_xor tree,
-// one complex128 per wave; a flagged sample is skipped before its parts and V are read.  k_gain_weight_rows is
-// k_weight_rows with the product folded in: its chunks, clipping, vector path, grid, partials, reduction and bad-weight
-// counter, k_gain_residual_rows' (pol, k) bookkeeping and staging of the row's gains -- and of the direction, when both
-// together fit GAIN_LDS_BYTES.  V is read only with a gain direction; G replaces P_0, or V for NP = 0.  In T every
-// operation rounds on its own, in the order written above: with unit gains and no direction m = 1, m U = U and
-// conj(m) G' = G' exactly, and the bits are k_weight_rows'.
-constexpr bool GAIN_WEIGHT_RE_FIRST[3] = {true, true, false};  // vector path / element by element, NP = 1 / NP = 2 .. 4
-template <typename T>
-__device__ __forceinline__ double gain_weight_element(cplx<T> &u, const cplx<T> &v, T w, const cplx<T> &g1, const cplx<T> &g2,
-                                                      const cplx<T> &h1, const cplx<T> &h2, bool sky, bool dir, bool re_first,
-                                                      int &bad_w) {
-    if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
-    if (!(w > (T)0)) {  // flagged (or counted above)
-        u = {(T)0, (T)0};
-        return 0.0;
-    }
-    T ur, ui;
-    {
-        // (no contraction, the products written out: see gain_residual_element)
-#pragma clang fp contract(off)
-        const T mr = g1.re * g2.re + g1.im * g2.im, mi = g1.re * g2.im - g1.im * g2.re;  // m = conj(g1) g2
-        ur = mr * u.re - mi * u.im;                                                      // m U
-        ui = mr * u.im + mi * u.re;
-        if (dir) {
-            const T dmr = (h1.re * g2.re + h1.im * g2.im) + (g1.re * h2.re + g1.im * h2.im);  // dm = conj(h1) g2 + conj(g1) h2
-            const T dmi = (h1.re * g2.im - h1.im * g2.re) + (g1.re * h2.im - g1.im * h2.re);
-            const T tr = dmr * v.re - dmi * v.im, ti = dmr * v.im + dmi * v.re;  // dm V
-            ur = sky ? ur + tr : tr;                                             // U' = m U + dm V (dm V alone for NP = 0)
-            ui = sky ? ui + ti : ti;
-        }
-        const T gr = (T)2 * (w * ur), gi = (T)2 * (w * ui);  // G'
-        u = {mr * gr + mi * gi, mr * gi - mi * gr};          // conj(m) G'
-    }
-    // weight_element's w (ur^2 + ui^2), which the compiler contracts there into one fused multiply-add whose choice of
-    // the fused square differs between k_weight_rows' instances and paths (in fp64; the squares of fp32 values are exact
-    // in fp64): spelled out here, the caller says which (GAIN_WEIGHT_RE_FIRST), so that with unit gains the two kernels
-    // give the same bits
-    const double dr = (double)ur, di = (double)ui;
-    double t;
-    {
-#pragma clang fp contract(off)
-        t = (double)w * (re_first ? __builtin_fma(dr, dr, di * di) : __builtin_fma(di, di, dr * dr));
-    }
-    return t;
-}
-template <typename T, int NP>
-__global__ void __launch_bounds__(256)
-    k_gain_weight_rows(WeightParts<T> parts, cplx<T> *__restrict__ vis, const T *__restrict__ weights,
-                       const cplx<T> *__restrict__ gains, const cplx<T> *__restrict__ dgains, const int *__restrict__ ant1,
-                       const int *__restrict__ ant2, int64_t nrows, int nbls, int tpol, int nant, int in_lds, int vec,
-                       double *__restrict__ partials, int *__restrict__ bad) {
-    constexpr int W = RES_W<T>;
-    constexpr int NV = W * (int)sizeof(cplx<T>) / 16;  // 16-byte vectors of a part (and of V) per chunk: 2
-    // the fused square of the rows' terms as k_weight_rows<T, NP> is compiled: the real part's on the vector path of
-    // every instance and element by element for NP = 1, the imaginary part's element by element for NP = 2 .. 4
-    // (tests/test_gpu_gain_gauss_newton.py holds every instance to it on both paths)
-    constexpr bool re_vec = GAIN_WEIGHT_RE_FIRST[0], re_one = NP == 1 ? GAIN_WEIGHT_RE_FIRST[1] : GAIN_WEIGHT_RE_FIRST[2];
-    extern __shared__ __align__(16) unsigned char gain_lds[];
-    __shared__ double wave_sum[4];
-    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
-    const int64_t L = (int64_t)tpol * nbls;
-    const bool dir = dgains != nullptr;
-    cplx<T> *const out = NP ? parts.p[0] : vis;  // where G goes
-    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
-        const cplx<T> *g = gains + row * ng;
-        const cplx<T> *h = dir ? dgains + row * ng : nullptr;
-        if (in_lds) {
-            cplx<T> *gl = reinterpret_cast<cplx<T> *>(gain_lds);
-            for (int i = threadIdx.x; i < ng; i += 256) gl[i] = g[i];
-            g = gl;
-            if (dir) {
-                for (int i = threadIdx.x; i < ng; i += 256) gl[ng + i] = h[i];
-                h = gl + ng;
-            }
-            __syncthreads();
-        }
-        const int64_t lo = row * L, hi = lo + L;  // the row in the block's index
-        const int64_t c0 = lo / W;                // its first chunk
-        double s = 0.0;
-        int bad_w = 0;
-        for (int i = 0; i < RES_CHUNKS; ++i) {
-            const int64_t c = c0 + ((int64_t)blockIdx.x * RES_CHUNKS + i) * 256 + threadIdx.x;
-            const int64_t e0 = c * W;
-            if (e0 >= hi) break;
-            const int64_t a = e0 > lo ? e0 : lo, b = e0 + W < hi ? e0 + W : hi;
-            int pol = (int)((a - lo) / nbls), k = (int)((a - lo) - (int64_t)pol * nbls);  // of element a; carried below
-            int p, q;
-            gain_feeds(pol, nfeed, p, q);
-            const cplx<T> zero = {(T)0, (T)0};
-            if (vec && e0 >= lo && e0 + W <= hi) {
-                union {
-                    uint4 q[NV];
-                    cplx<T> c[W];
-                } u, t;
-                union {
-                    uint4 q;
-                    T w[W];
-                } ww;
-                if (NP) {
-#pragma unroll
-                    for (int j = 0; j < NV; ++j) u.q[j] = reinterpret_cast<const uint4 *>(parts.p[0] + e0)[j];
-#pragma unroll
-                    for (int n = 1; n < NP; ++n) {
-#pragma unroll
-                        for (int j = 0; j < NV; ++j) t.q[j] = reinterpret_cast<const uint4 *>(parts.p[n] + e0)[j];
-#pragma unroll
-                        for (int j = 0; j < W; ++j) u.c[j] = {u.c[j].re + t.c[j].re, u.c[j].im + t.c[j].im};
-                    }
-                }
-                if (dir) {
-#pragma unroll
-                    for (int j = 0; j < NV; ++j) t.q[j] = reinterpret_cast<const uint4 *>(vis + e0)[j];
-                }
-                if (weights) ww.q = *reinterpret_cast<const uint4 *>(weights + e0);
-#pragma unroll
-                for (int j = 0; j < W; ++j) {
-                    const int i1 = p * nant + ant1[k], i2 = q * nant + ant2[k];
-                    if (!NP) u.c[j] = zero;
-                    s += gain_weight_element<T>(u.c[j], dir ? t.c[j] : zero, weights ? ww.w[j] : (T)1, g[i1], g[i2],
-                                                dir ? h[i1] : zero, dir ? h[i2] : zero, NP != 0, dir, re_vec, bad_w);
-                    if (++k == nbls) {
-                        k = 0;
-                        gain_feeds(++pol, nfeed, p, q);
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < NV; ++j) reinterpret_cast<uint4 *>(out + e0)[j] = u.q[j];
-            } else {
-                for (int64_t e = a; e < b; ++e) {
-                    cplx<T> u = zero;
-                    if (NP) u = parts.p[0][e];
-#pragma unroll
-                    for (int n = 1; n < NP; ++n) u = {u.re + parts.p[n][e].re, u.im + parts.p[n][e].im};
-                    const int i1 = p * nant + ant1[k], i2 = q * nant + ant2[k];
-                    s += gain_weight_element<T>(u, dir ? vis[e] : zero, weights ? weights[e] : (T)1, g[i1], g[i2],
-                                                dir ? h[i1] : zero, dir ? h[i2] : zero, NP != 0, dir, re_one, bad_w);
-                    out[e] = u;
-                    if (++k == nbls) {
-                        k = 0;
-                        gain_feeds(++pol, nfeed, p, q);
-                    }
-                }
-            }
-        }
-        if (bad_w) atomicAdd(bad, bad_w);
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            partials[row * gridDim.x + blockIdx.x] = ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
-        __syncthreads();  // (the next row of this block writes wave_sum and the staged gains again)
-    }
-}
+// k_gain_weight_gather is k_gain_gradient with this G' in place of 2 w (V' - d): it runs first, while the blocks still
+// hold the parts and V, one wave per (row, feed, antenna) over the incidence lists, everything in fp64 from the T-typed
+// inputs (U summed in fp64 in the parts' order), an __shfl_xor tree, one complex128 per wave; a flagged sample is skipped
+// before its parts and V are read.  k_weight_rows<T, NP, true> follows.
 // hgains[(row nfeed + feed) nant + a]: one wave per (row, feed, antenna); see above.  The parts and vis still hold the
 // tangent parts and V.
 template <typename T, int NP>
@@ -2340,37 +2186,86 @@ __global__ void __launch_bounds__(256)
         if (lane == 0) hgains[(row * nfeed + feed) * nant + ant] = {sr, si};
     }
 }
-// Queues the gather (when hgains is not null), the in-place kernel and the rows' reduction on `on`: launch_weight_rows'
-// arguments with nparts = 0 .. 4, the forward block vis (needed with dgains, with hgains and for nparts = 0, where G
-// replaces it; else it may be null), the row's gains and their direction (nrows, nfeed nant; dgains may be null) and the
-// pairs; hgains (nrows, nfeed nant) complex128.  All device pointers; weights, dgains and hgains may be null.
+// The gains of a row pass, all device pointers: the pairs (null: a pass without gains), the rows' gains and their
+// direction (nrows, nfeed nant; dgains null: no direction, and none in the objective) and where the gain gradient goes
+// (ggains or hgains, (nrows, nfeed nant) complex128; null: the gather does not run).
 template <typename T>
-inline void launch_gain_weight_rows(hipStream_t on, int nparts, cplx<T> *const *parts, cplx<T> *vis, const T *weights,
-                                    const cplx<T> *gains, const cplx<T> *dgains, const GainPairs &gp, int64_t nrows, int tpol,
-                                    double *partials, double *q_rows, int *bad, cplx<double> *hgains) {
-    if (nparts < 0 || nparts > 4 || (nparts == 0 && !dgains)) throw Error(FV_ERR_ARG, "nparts must be 0 .. 4, and 0 needs d_gains");
-    if ((dgains || hgains || nparts == 0) && !vis) throw Error(FV_ERR_ARG, "d_gains and hgains need vis");
-    const int nbls = (int)gp.nbls, nant = gp.nant, ng = (tpol == 4 ? 2 : 1) * nant;
-    const int64_t L = (int64_t)tpol * nbls;
-    const int nblk = residual_blocks_per_row<T>(L);
-    WeightParts<T> wp{};
-    uintptr_t bits = reinterpret_cast<uintptr_t>(weights);
-    if (dgains || nparts == 0) bits |= reinterpret_cast<uintptr_t>(vis);
-    for (int j = 0; j < nparts; ++j) {
-        wp.p[j] = parts[j];
-        bits |= reinterpret_cast<uintptr_t>(parts[j]);
+struct RowGains {
+    const GainPairs *pairs = nullptr;
+    const cplx<T> *gains = nullptr, *dgains = nullptr;
+    cplx<double> *grad = nullptr;
+};
+// what the launchers share: vectors are allowed when every array's pointer is 16-byte aligned (null counts as aligned)
+inline int rows_vec(std::initializer_list<const void *> arrays) {
+    uintptr_t bits = 0;
+    for (const void *a : arrays) bits |= reinterpret_cast<uintptr_t>(a);
+    return (bits & 15) == 0;
+}
+// of a row pass with gains: the launch's numbers and the dynamic LDS of its staged gains
+template <typename T>
+struct RowGainShape {
+    int nbls = 0, nant = 0, nfeed = 1, tpol = 1, ng = 0, in_lds = 0;
+    size_t shm = 0;
+    const int *a1 = nullptr, *a2 = nullptr;
+    RowGainShape(const RowGains<T> &rg, int64_t L) {
+        if (!rg.pairs) return;
+        nbls = (int)rg.pairs->nbls, nant = rg.pairs->nant, tpol = (int)(L / nbls), nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
+        a1 = rg.pairs->d_ant1.template as<int>(), a2 = rg.pairs->d_ant2.template as<int>();
+        const size_t lds = sizeof(cplx<T>) * (size_t)ng * (rg.dgains ? 2 : 1);
+        in_lds = lds <= GAIN_LDS_BYTES;
+        shm = in_lds ? lds : 0;
     }
-    const int vec = (bits & 15) == 0;
+};
+// Queues the objective's kernels on `on`: the gather k_gain_gradient (with gains, when rg.grad is not null), the in-place
+// kernel and the rows' reduction.  vis (nrows, L) in place, rs from row_scratch (the counters are zeroed here).  All
+// device pointers; weights may be null.
+template <typename T>
+inline void launch_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *data, const T *weights, int64_t nrows, int64_t L,
+                            const RowScratch &rs, const RowGains<T> &rg = {}) {
+    const RowGainShape<T> gs(rg, L);
+    const int vec = rows_vec({vis, data, weights});
     const unsigned rows_y = (unsigned)std::min<int64_t>(nrows, 65535);
-    const int *a1 = gp.d_ant1.as<int>(), *a2 = gp.d_ant2.as<int>();
-    FV_HIP(hipMemsetAsync(bad, 0, 2 * sizeof(int), on));
-    if (hgains) {
-        const dim3 grid((unsigned)cdiv(ng, 4), rows_y);
-        const int *off = gp.d_off.as<int>(), *inc = gp.d_inc.as<int>();
+    const dim3 grid((unsigned)rs.nblk, rows_y);
+    FV_HIP(hipMemsetAsync(rs.bad, 0, 2 * sizeof(int), on));
+    if (rg.pairs && rg.grad)
+        hipLaunchKernelGGL(k_gain_gradient<T>, dim3((unsigned)cdiv(gs.ng, 4), rows_y), dim3(256), 0, on, (const cplx<T> *)vis, data,
+                           weights, rg.gains, gs.a1, gs.a2, rg.pairs->d_off.template as<int>(), rg.pairs->d_inc.template as<int>(),
+                           nrows, gs.nbls, gs.tpol, gs.nant, rg.grad);
+#define FV_ROWS(GAINS)                                                                                                        \
+    hipLaunchKernelGGL((k_residual_rows<T, GAINS>), grid, dim3(256), gs.shm, on, vis, data, weights, rg.gains, gs.a1, gs.a2, nrows, \
+                       L, gs.nbls, gs.nant, gs.nfeed, gs.in_lds, vec, rs.partials, rs.bad)
+    if (rg.pairs)
+        FV_ROWS(true);
+    else
+        FV_ROWS(false);
+#undef FV_ROWS
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)rs.partials, nrows,
+                       rs.nblk, rs.sums);
+}
+// Queues the product's kernels on `on`: the gather k_gain_weight_gather (with gains, when rg.grad is not null), the
+// in-place kernel and the rows' reduction.  parts[0 .. nparts) device blocks (nrows, L), nparts = 1 .. 4, or 0 .. 4 with
+// gains; vis the forward block (needed with a gain direction, with rg.grad and for nparts = 0; else it may be null); G in
+// place in parts[0], or in vis for nparts = 0; rs from row_scratch (the counters are zeroed here).  weights may be null.
+template <typename T>
+inline void launch_weight_rows(hipStream_t on, int nparts, cplx<T> *const *parts, const T *weights, int64_t nrows, int64_t L,
+                               const RowScratch &rs, const RowGains<T> &rg = {}, cplx<T> *vis = nullptr) {
+    if (!rg.pairs && (nparts < 1 || nparts > 4)) throw Error(FV_ERR_ARG, "nparts must be 1 .. 4");
+    if (rg.pairs && (nparts < 0 || nparts > 4 || (nparts == 0 && !rg.dgains)))
+        throw Error(FV_ERR_ARG, "nparts must be 0 .. 4, and 0 needs d_gains");
+    if (rg.pairs && (rg.dgains || rg.grad || nparts == 0) && !vis) throw Error(FV_ERR_ARG, "d_gains and hgains need vis");
+    const RowGainShape<T> gs(rg, L);
+    WeightParts<T> wp{};
+    for (int j = 0; j < nparts; ++j) wp.p[j] = parts[j];
+    const int vec = rows_vec({weights, rg.dgains || nparts == 0 ? vis : nullptr, wp.p[0], wp.p[1], wp.p[2], wp.p[3]});
+    const unsigned rows_y = (unsigned)std::min<int64_t>(nrows, 65535);
+    FV_HIP(hipMemsetAsync(rs.bad, 0, 2 * sizeof(int), on));
+    if (rg.pairs && rg.grad) {
+        const dim3 grid((unsigned)cdiv(gs.ng, 4), rows_y);
+        const int *off = rg.pairs->d_off.template as<int>(), *inc = rg.pairs->d_inc.template as<int>();
         const cplx<T> *v = vis;
 #define FV_GATHER(NP)                                                                                                        \
-    hipLaunchKernelGGL((k_gain_weight_gather<T, NP>), grid, dim3(256), 0, on, wp, v, weights, gains, dgains, a1, a2, off, inc, \
-                       nrows, nbls, tpol, nant, hgains)
+    hipLaunchKernelGGL((k_gain_weight_gather<T, NP>), grid, dim3(256), 0, on, wp, v, weights, rg.gains, rg.dgains, gs.a1, gs.a2, \
+                       off, inc, nrows, gs.nbls, gs.tpol, gs.nant, rg.grad)
         switch (nparts) {
         case 0: FV_GATHER(0); break;
         case 1: FV_GATHER(1); break;
@@ -2380,23 +2275,26 @@ inline void launch_gain_weight_rows(hipStream_t on, int nparts, cplx<T> *const *
         }
 #undef FV_GATHER
     }
-    const size_t lds = sizeof(cplx<T>) * (size_t)ng * (dgains ? 2 : 1);
-    const int in_lds = lds <= GAIN_LDS_BYTES;
-    const dim3 grid((unsigned)nblk, rows_y);
-    const size_t shm = in_lds ? lds : 0;
-#define FV_ROWS(NP)                                                                                                          \
-    hipLaunchKernelGGL((k_gain_weight_rows<T, NP>), grid, dim3(256), shm, on, wp, vis, weights, gains, dgains, a1, a2, nrows, \
-                       nbls, tpol, nant, in_lds, vec, partials, bad)
-    switch (nparts) {
-    case 0: FV_ROWS(0); break;
-    case 1: FV_ROWS(1); break;
-    case 2: FV_ROWS(2); break;
-    case 3: FV_ROWS(3); break;
-    default: FV_ROWS(4); break;
-    }
+    const dim3 grid((unsigned)rs.nblk, rows_y);
+#define FV_ROWS(NP, GAINS)                                                                                                   \
+    hipLaunchKernelGGL((k_weight_rows<T, NP, GAINS>), grid, dim3(256), gs.shm, on, wp, vis, weights, rg.gains, rg.dgains, gs.a1, \
+                       gs.a2, nrows, L, gs.nbls, gs.nant, gs.nfeed, gs.in_lds, vec, rs.partials, rs.bad)
+    if (rg.pairs) switch (nparts) {
+        case 0: FV_ROWS(0, true); break;
+        case 1: FV_ROWS(1, true); break;
+        case 2: FV_ROWS(2, true); break;
+        case 3: FV_ROWS(3, true); break;
+        default: FV_ROWS(4, true); break;
+        }
+    else switch (nparts) {
+        case 1: FV_ROWS(1, false); break;
+        case 2: FV_ROWS(2, false); break;
+        case 3: FV_ROWS(3, false); break;
+        default: FV_ROWS(4, false); break;
+        }
 #undef FV_ROWS
-    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)partials, nrows, nblk,
-                       q_rows);
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)rs.partials, nrows,
+                       rs.nblk, rs.sums);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4523,42 +4421,47 @@ class Sim : public SimBase {
         FV_REQUIRE(t1 > t0 && f1 > f0, "fv_sim_run_residual: empty range of times or frequencies");
         const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
         const size_t n = (size_t)nrows * (size_t)L;
-        const cplx<T> *dd = static_cast<const cplx<T> *>(data);
-        const T *dw = static_cast<const T *>(weights);
-        if (!data_on_device) {
-            upload(d_res_d, data, sizeof(cplx<T>) * n, 0);
-            dd = d_res_d.as<cplx<T>>();
-        }
-        if (weights && !weights_on_device) {
-            upload(d_res_w, weights, sizeof(T) * n, 0);
-            dw = d_res_w.as<T>();
-        }
-        cplx<T> *dg = static_cast<cplx<T> *>(gvis);
-        if (!gvis_on_device) {
-            d_out.reserve(std::max<size_t>(sizeof(cplx<T>) * n, 16));
-            dg = d_out.as<cplx<T>>();
-        }
-        const int nblk = residual_blocks_per_row<T>(L);
-        const size_t part_bytes = sizeof(double) * (size_t)nrows * nblk, sum_bytes = sizeof(double) * (size_t)nrows;
-        d_res_sum.reserve(part_bytes + sum_bytes + 16);
-        double *partials = d_res_sum.as<double>(), *sums = partials + (size_t)nrows * nblk;
-        int *bad = reinterpret_cast<int *>(sums + nrows);
+        const cplx<T> *dd = staged<cplx<T>>(d_res_d, data, data_on_device, n);
+        const T *dw = staged<T>(d_res_w, weights, weights_on_device, n);
+        cplx<T> *dg = staged_out<cplx<T>>(d_out, gvis, gvis_on_device, n);
+        const RowScratch rs = row_scratch<T>(d_res_sum, nrows, L);
         run(t0, t1, f0, f1, dg, 1);
-        launch_residual<T>(stream, dg, dd, dw, nrows, L, partials, sums, bad);
-        int hbad[2] = {0, 0};
-        FV_HIP(hipMemcpyAsync(chi2_ft, sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-        FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, stream));
+        launch_residual<T>(stream, dg, dd, dw, nrows, L, rs);
         if (!gvis_on_device) FV_HIP(hipMemcpyAsync(gvis, dg, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, stream));
-        FV_HIP(hipStreamSynchronize(stream));
-        FV_HIP(hipGetLastError());
+        finish_rows(rs, nrows, chi2_ft, {&d_res_d, &d_res_w});
+    }
+    // What the four row passes share on the host.  An input of n values: the device array as it is, or the host array
+    // staged in `buf` (null stays null).  An output: the device array, or `buf` reserved for it.
+    template <typename X>
+    const X *staged(DevBuf &buf, const void *src, int on_device, size_t n) {
+        if (!src || on_device) return static_cast<const X *>(src);
+        upload(buf, src, sizeof(X) * n, 0);
+        return buf.as<X>();
+    }
+    template <typename X>
+    X *staged_out(DevBuf &buf, void *dst, int on_device, size_t n) {
+        if (!dst || on_device) return static_cast<X *>(dst);
+        buf.reserve(std::max<size_t>(sizeof(X) * n, 16));
+        return buf.as<X>();
+    }
+    // The staged inputs of a pass belong to it: when together they exceed FFTVIS_HIP_ADJ_KEEP_BYTES (default 256 MiB) they
+    // go back (fv_sim_run_adjoint's rule).  Every row pass names the set it counts and gives back: the buffers it can
+    // have staged into, and for weight_block run_residual's two, so that what a handle holds afterwards does not depend on
+    // which of the two calls came last.
+    void release_beyond_keep(std::initializer_list<DevBuf *> staged) {
+        size_t held = 0;
+        for (const DevBuf *b : staged) held += b->cap;
+        const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
+        if ((double)held > (ek ? std::atof(ek) : 256.0 * 1024 * 1024))
+            for (DevBuf *b : staged) b->release();
+    }
+    // The ending of every row pass: the rows' sums and the counters come back behind what the caller queued, with one
+    // synchronisation; then the timers, the staged buffers' release, the run's error flags and the bad-input message.
+    void finish_rows(const RowScratch &rs, int64_t nrows, double *rows_host, std::initializer_list<DevBuf *> staged) {
+        int hbad[2];
+        collect_rows(stream, rs, nrows, rows_host, hbad);
         if (timing_level) ev_collect();
-        {  // the staged inputs belong to this pass: beyond the keep limit they go back (fv_sim_run_adjoint's rule)
-            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
-            if ((double)(d_res_d.cap + d_res_w.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
-                d_res_d.release();
-                d_res_w.release();
-            }
-        }
+        release_beyond_keep(staged);
         check_errors();
         throw_if_bad_residual_input(hbad);
     }
@@ -4575,35 +4478,12 @@ class Sim : public SimBase {
         FV_REQUIRE(t1 > t0 && f1 > f0, "fv_sim_weight_block: empty range of times or frequencies");
         const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
         const size_t n = (size_t)nrows * (size_t)L;
-        const T *dw = static_cast<const T *>(weights);
-        if (weights && !weights_on_device) {
-            upload(d_res_w, weights, sizeof(T) * n, 0);
-            dw = d_res_w.as<T>();
-        }
+        const T *dw = staged<T>(d_res_w, weights, weights_on_device, n);
         cplx<T> *parts[4] = {nullptr, nullptr, nullptr, nullptr};
         for (int j = 0; j < nparts; ++j) parts[j] = static_cast<cplx<T> *>(parts_dev[j]);
-        const int nblk = residual_blocks_per_row<T>(L);
-        const size_t part_bytes = sizeof(double) * (size_t)nrows * nblk, sum_bytes = sizeof(double) * (size_t)nrows;
-        d_res_sum.reserve(part_bytes + sum_bytes + 16);
-        double *partials = d_res_sum.as<double>(), *sums = partials + (size_t)nrows * nblk;
-        int *bad = reinterpret_cast<int *>(sums + nrows);
-        launch_weight_rows<T>(stream, nparts, parts, dw, nrows, L, partials, sums, bad);
-        int hbad[2] = {0, 0};
-        FV_HIP(hipMemcpyAsync(q_ft, sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-        FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, stream));
-        FV_HIP(hipStreamSynchronize(stream));
-        FV_HIP(hipGetLastError());
-        if (timing_level) ev_collect();
-        {  // run_residual's rule, over the same two buffers: what a handle holds afterwards does not depend on which of the
-           // two calls came last
-            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
-            if ((double)(d_res_d.cap + d_res_w.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
-                d_res_d.release();
-                d_res_w.release();
-            }
-        }
-        check_errors();
-        throw_if_bad_residual_input(hbad);
+        const RowScratch rs = row_scratch<T>(d_res_sum, nrows, L);
+        launch_weight_rows<T>(stream, nparts, parts, dw, nrows, L, rs);
+        finish_rows(rs, nrows, q_ft, {&d_res_d, &d_res_w});  // (run_residual's two buffers)
     }
 
     // ---- per-antenna gains in the fused objective (DESIGN.md "Gains") ----------------------------------------------------
@@ -4625,58 +4505,18 @@ class Sim : public SimBase {
         const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
         const size_t n = (size_t)nrows * (size_t)L;
         const size_t ng = (size_t)nrows * (size_t)(tpol == 4 ? 2 : 1) * (size_t)gain_pairs.nant;
-        const cplx<T> *dd = static_cast<const cplx<T> *>(data);
-        const T *dw = static_cast<const T *>(weights);
-        const cplx<T> *dgn = static_cast<const cplx<T> *>(gains);
-        if (!data_on_device) {
-            upload(d_res_d, data, sizeof(cplx<T>) * n, 0);
-            dd = d_res_d.as<cplx<T>>();
-        }
-        if (weights && !weights_on_device) {
-            upload(d_res_w, weights, sizeof(T) * n, 0);
-            dw = d_res_w.as<T>();
-        }
-        if (!gains_on_device) {
-            upload(d_res_g, gains, sizeof(cplx<T>) * ng, 0);
-            dgn = d_res_g.as<cplx<T>>();
-        }
-        cplx<T> *dg = static_cast<cplx<T> *>(gvis);
-        if (!gvis_on_device) {
-            d_out.reserve(std::max<size_t>(sizeof(cplx<T>) * n, 16));
-            dg = d_out.as<cplx<T>>();
-        }
-        cplx<double> *dgg = static_cast<cplx<double> *>(ggains);
-        if (ggains && !ggains_on_device) {
-            d_res_gg.reserve(std::max<size_t>(sizeof(cplx<double>) * ng, 16));
-            dgg = d_res_gg.as<cplx<double>>();
-        }
-        const int nblk = residual_blocks_per_row<T>(L);
-        const size_t part_bytes = sizeof(double) * (size_t)nrows * nblk, sum_bytes = sizeof(double) * (size_t)nrows;
-        d_res_sum.reserve(part_bytes + sum_bytes + 16);
-        double *partials = d_res_sum.as<double>(), *sums = partials + (size_t)nrows * nblk;
-        int *bad = reinterpret_cast<int *>(sums + nrows);
+        const cplx<T> *dd = staged<cplx<T>>(d_res_d, data, data_on_device, n);
+        const T *dw = staged<T>(d_res_w, weights, weights_on_device, n);
+        const cplx<T> *dgn = staged<cplx<T>>(d_res_g, gains, gains_on_device, ng);
+        cplx<T> *dg = staged_out<cplx<T>>(d_out, gvis, gvis_on_device, n);
+        cplx<double> *dgg = staged_out<cplx<double>>(d_res_gg, ggains, ggains_on_device, ng);
+        const RowScratch rs = row_scratch<T>(d_res_sum, nrows, L);
         run(t0, t1, f0, f1, dg, 1);
-        launch_gain_residual<T>(stream, dg, dd, dw, dgn, gain_pairs, nrows, tpol, partials, sums, bad, dgg);
-        int hbad[2] = {0, 0};
-        FV_HIP(hipMemcpyAsync(chi2_ft, sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-        FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, stream));
+        launch_residual<T>(stream, dg, dd, dw, nrows, L, rs, {&gain_pairs, dgn, nullptr, dgg});
         if (!gvis_on_device) FV_HIP(hipMemcpyAsync(gvis, dg, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, stream));
         if (ggains && !ggains_on_device)
             FV_HIP(hipMemcpyAsync(ggains, dgg, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, stream));
-        FV_HIP(hipStreamSynchronize(stream));
-        FV_HIP(hipGetLastError());
-        if (timing_level) ev_collect();
-        {  // run_residual's rule, the staged gains and the gradient's block included
-            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
-            if ((double)(d_res_d.cap + d_res_w.cap + d_res_g.cap + d_res_gg.cap) > (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
-                d_res_d.release();
-                d_res_w.release();
-                d_res_g.release();
-                d_res_gg.release();
-            }
-        }
-        check_errors();
-        throw_if_bad_residual_input(hbad);
+        finish_rows(rs, nrows, chi2_ft, {&d_res_d, &d_res_w, &d_res_g, &d_res_gg});  // (the gains and the gradient's block too)
     }
 
     // ---- Gauss-Newton product with gains (DESIGN.md "Gains in the Gauss-Newton product") ------------------------------
@@ -4694,55 +4534,17 @@ class Sim : public SimBase {
         const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
         const size_t n = (size_t)nrows * (size_t)L;
         const size_t ng = (size_t)nrows * (size_t)(tpol == 4 ? 2 : 1) * (size_t)gain_pairs.nant;
-        const T *dw = static_cast<const T *>(weights);
-        const cplx<T> *dgn = static_cast<const cplx<T> *>(gains), *ddg = static_cast<const cplx<T> *>(d_gains);
-        if (weights && !weights_on_device) {
-            upload(d_res_w, weights, sizeof(T) * n, 0);
-            dw = d_res_w.as<T>();
-        }
-        if (!gains_on_device) {
-            upload(d_res_g, gains, sizeof(cplx<T>) * ng, 0);
-            dgn = d_res_g.as<cplx<T>>();
-        }
-        if (d_gains && !d_gains_on_device) {
-            upload(d_res_dg, d_gains, sizeof(cplx<T>) * ng, 0);
-            ddg = d_res_dg.as<cplx<T>>();
-        }
-        cplx<double> *dhg = static_cast<cplx<double> *>(hgains);
-        if (hgains && !hgains_on_device) {
-            d_res_gg.reserve(std::max<size_t>(sizeof(cplx<double>) * ng, 16));
-            dhg = d_res_gg.as<cplx<double>>();
-        }
+        const T *dw = staged<T>(d_res_w, weights, weights_on_device, n);
+        const cplx<T> *dgn = staged<cplx<T>>(d_res_g, gains, gains_on_device, ng);
+        const cplx<T> *ddg = staged<cplx<T>>(d_res_dg, d_gains, d_gains_on_device, ng);
+        cplx<double> *dhg = staged_out<cplx<double>>(d_res_gg, hgains, hgains_on_device, ng);
         cplx<T> *parts[4] = {nullptr, nullptr, nullptr, nullptr};
         for (int j = 0; j < nparts; ++j) parts[j] = static_cast<cplx<T> *>(parts_dev[j]);
-        const int nblk = residual_blocks_per_row<T>(L);
-        const size_t part_bytes = sizeof(double) * (size_t)nrows * nblk, sum_bytes = sizeof(double) * (size_t)nrows;
-        d_res_sum.reserve(part_bytes + sum_bytes + 16);
-        double *partials = d_res_sum.as<double>(), *sums = partials + (size_t)nrows * nblk;
-        int *bad = reinterpret_cast<int *>(sums + nrows);
-        launch_gain_weight_rows<T>(stream, nparts, parts, static_cast<cplx<T> *>(vis_dev), dw, dgn, ddg, gain_pairs, nrows, tpol,
-                                   partials, sums, bad, dhg);
-        int hbad[2] = {0, 0};
-        FV_HIP(hipMemcpyAsync(q_ft, sums, sum_bytes, hipMemcpyDeviceToHost, stream));
-        FV_HIP(hipMemcpyAsync(hbad, bad, sizeof(hbad), hipMemcpyDeviceToHost, stream));
+        const RowScratch rs = row_scratch<T>(d_res_sum, nrows, L);
+        launch_weight_rows<T>(stream, nparts, parts, dw, nrows, L, rs, {&gain_pairs, dgn, ddg, dhg}, static_cast<cplx<T> *>(vis_dev));
         if (hgains && !hgains_on_device)
             FV_HIP(hipMemcpyAsync(hgains, dhg, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, stream));
-        FV_HIP(hipStreamSynchronize(stream));
-        FV_HIP(hipGetLastError());
-        if (timing_level) ev_collect();
-        {  // run_residual_gains' rule, the staged direction included
-            const char *ek = std::getenv("FFTVIS_HIP_ADJ_KEEP_BYTES");
-            if ((double)(d_res_d.cap + d_res_w.cap + d_res_g.cap + d_res_gg.cap + d_res_dg.cap) >
-                (ek ? std::atof(ek) : 256.0 * 1024 * 1024)) {
-                d_res_d.release();
-                d_res_w.release();
-                d_res_g.release();
-                d_res_gg.release();
-                d_res_dg.release();
-            }
-        }
-        check_errors();
-        throw_if_bad_residual_input(hbad);
+        finish_rows(rs, nrows, q_ft, {&d_res_d, &d_res_w, &d_res_g, &d_res_gg, &d_res_dg});  // (run_residual_gains' and the direction)
     }
 
     // Height terms ("w-term expansion"): a non-coplanar array whose heights are small against the wavelength -- every

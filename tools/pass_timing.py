@@ -36,13 +36,14 @@ resident tensors; --wrt NAMES (comma-separated, default fluxes) selects the grad
 line also holds the bytes each variant moves across PCIe per call, from the shapes; --gains puts per-antenna gains into
 the data model (``gains`` may then be one of --wrt's names): ``fused`` and ``fused_device`` call ``simulate_vis_gain_chi2`` (resident gains
 for the latter), ``separate`` becomes the forward to the host, the gain product and the loss in torch, .backward() and the
-public adjoints on the host result, and ``--profile gain_kernels`` runs the gain kernels and k_residual_rows alone on the
+public adjoints on the host result, and ``--profile gain_kernels`` runs the kernels of fv_gain_residual_chi2 (k_gain_gradient,
+k_residual_rows<T, true>) and of fv_residual_chi2 (k_residual_rows<T, false>) alone on the
 block's shape, six times each, alternating.  gauss_newton: one product
 2 J^T W J p of a conjugate-gradient solve -- ``composed`` is the public tangent to the host, numpy's 2 w U and the public adjoint
 on the host result (runs on a checkout from before the fused call: --package DIR --only forward --only composed), ``fused``
 simulate_vis_gauss_newton on host weights and ``fused_device`` on resident weights; --case fluxes | ants | fluxes_radec |
-beam_coefs | gains names the direction and the products; ``--profile kernels`` runs k_weight_rows and k_residual_rows alone on the
-block's shape, six times each, alternating.  --gains puts per-antenna gains into the data model and --d-gains adds a gain
+beam_coefs | gains names the direction and the products; ``--profile kernels`` runs k_weight_rows<T, 1, false> and
+k_residual_rows<T, false> alone on the block's shape, six times each, alternating.  --gains puts per-antenna gains into the data model and --d-gains adds a gain
 direction and the gain block of the product (``--case gains``: that direction alone): ``fused`` and ``fused_device`` call
 ``simulate_vis_gain_gauss_newton``, ``composed`` becomes the tangent and, with --d-gains, the forward to the host, the gain
 product, its tangent, conj(m) 2 w U' and the antennas' sums in torch on the device and the public adjoint on the host
