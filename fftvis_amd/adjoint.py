@@ -1737,6 +1737,116 @@ def _gain_gradient(run: _Run, ggains: np.ndarray, shape) -> np.ndarray:
     return total.reshape(shape)
 
 
+# ---- what the fit entry points share: simulate_vis_gain_chi2, simulate_vis_gain_gauss_newton, simulate_vis_gain_solve ----
+
+def _fit_keywords(wrt, gains, per_name, per, adjoint_path, beam_coefs, polarized, d_beam_coefs=None):
+    """The keywords ``simulate_vis_gain_chi2`` and ``simulate_vis_gain_gauss_newton`` check alike, before the run is
+    described; ``per_name`` names the caller's ``chi2_per`` / ``quad_per``.  Returns ``wrt`` as (single, names)."""
+    single = isinstance(wrt, str)
+    names = (wrt,) if single else tuple(wrt)
+    if names:
+        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec', 'beam_coefs' and 'gains'")
+    if "gains" in names and gains is None:
+        raise ValueError("wrt='gains' needs gains=")
+    if per not in ("total", "freq_time"):
+        raise ValueError(f"{per_name} must be 'total' or 'freq_time', got {per!r}")
+    if adjoint_path not in ("type3", "type2", "auto"):
+        raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {adjoint_path!r}")
+    if d_beam_coefs is not None and beam_coefs is None:
+        raise ValueError("d_beam_coefs needs beam_coefs (basis beams)")
+    if "beam_coefs" in names and beam_coefs is None:
+        raise ValueError("wrt='beam_coefs' needs beam_coefs (basis beams)")
+    if beam_coefs is not None and not polarized:  # the forward's message
+        raise ValueError(
+            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
+        )
+    return single, names
+
+
+def _check_vis_block(run: _Run, x, name):
+    """``data`` or ``model``: on the host or on the run's device, in ``simulate_vis``'s output shape."""
+    _run_device(run, (x,), name)
+    if tuple(x.shape) != run.vis_shape:
+        raise ValueError(f"{name} must have simulate_vis's output shape {run.vis_shape}, got {tuple(x.shape)}")
+
+
+def _check_weights(run: _Run, weights, whose):
+    """``weights`` (not None): real, in the shape the caller's message calls ``whose`` shape."""
+    if tuple(weights.shape) != run.vis_shape:
+        raise ValueError(f"weights must have {whose} shape {run.vis_shape}, got {tuple(weights.shape)}")
+    if weights.is_complex() if _is_tensor(weights) else np.iscomplexobj(weights):
+        raise ValueError("weights must be real (inverse variances; 0 flags a sample)")
+
+
+def _fit_outputs(run: _Run, names, full_stokes):
+    """``_gradient_buffers``' specification of the fit passes' four gradient buffers -- gflux, gcoefs, gbls, gtopo --, None
+    for one no name of ``wrt`` needs."""
+    f_shape = (run.nsrc, run.nfreqs)
+    return [
+        None if "fluxes" not in names else (f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real"),
+        None if "beam_coefs" not in names else (run.beam_coefs.shape, "complex"),
+        None if "ants" not in names and "baselines" not in names else ((run.nbls, 3), "float64"),
+        None if "topo" not in names and "radec" not in names else ((run.ntimes, run.nsrc, 3), "float64")]
+
+
+def _gvis_buffer(run: _Run, return_gvis):
+    """The zeroed device tensor G is returned in, complete before the library writes it; None when it is not asked for."""
+    if not return_gvis:
+        return None
+    import torch
+
+    gvis = _zeros(torch.device("cuda", int(run.args["device"])), run.vis_shape, run.cdt)
+    _synchronize(gvis.device)
+    return gvis
+
+
+def _fit_gradients(run: _Run, single, names, buffers, full_stokes, ggains, gains, like, device):
+    """What a fit call returns for ``wrt`` out of the engine's ``buffers`` (gflux, gcoefs, gbls, gtopo) and its gain block
+    ``ggains``: the gains' gradient in ``gains``' own shape, Stokes fluxes, the radec chain, the antenna fold.  The
+    outputs follow ``like`` (the tensor among the inputs, or None) and live on the torch ``device`` (None: the host)."""
+    gflux, gcoefs, gbls, gtopo = buffers
+    res = {"topo": gtopo, "baselines": gbls, "beam_coefs": gcoefs}
+    if "gains" in names:
+        res["gains"] = _gain_gradient(run, ggains, tuple(gains.shape))
+        if device is not None:
+            import torch
+
+            res["gains"] = torch.from_numpy(res["gains"]).to(device)
+    if "fluxes" in names:
+        res["fluxes"] = stokes_adjoint(gflux, full_stokes)
+    if "radec" in names:
+        res["radec"] = topo_to_radec_gradient(gtopo, _radec_jacobian_of(run))
+    if "ants" in names:
+        res["ants"] = baseline_to_antenna_gradient(gbls, run.ants, run.baselines)
+    return _select({k: v for k, v in res.items() if k in names}, single, names, like, device is not None) if names else ()
+
+
+def _fit_value(rows: np.ndarray, per, like, device):
+    """The engine's (nfreqs, ntimes) float64 ``rows`` as the caller's ``chi2_per`` / ``quad_per`` asks: "total" their sum as
+    a Python float, added in row-major order, else the array itself, following ``like`` and ``device`` as the gradients
+    do."""
+    if per == "total":
+        return float(np.cumsum(rows.ravel())[-1])
+    if like is None:
+        return rows
+    import torch
+
+    value = torch.from_numpy(rows)
+    return value if device is None else value.to(device)
+
+
+def _gvis_home(gvis, like, device):
+    """G as it is returned: the device tensor for a run on the device, else on the host, a tensor when ``like`` is one."""
+    if device is not None:
+        return gvis
+    gvis = gvis.cpu().numpy()
+    if like is not None:
+        import torch
+
+        gvis = torch.from_numpy(gvis)
+    return gvis
+
+
 def simulate_vis_chi2(
     data,
     ants: dict,
@@ -1891,88 +2001,31 @@ def simulate_vis_gain_chi2(
     takes no gains), and the gains that minimise it for a fixed model are ``simulate_vis_gain_solve``'s.  Not covered:
     gains in ``simulate_vis`` itself, ``model=`` in this call, full 2x2 Jones (leakage) gains, sharding over GPUs."""
     args = locals()
-    single = isinstance(wrt, str)
-    names = (wrt,) if single else tuple(wrt)
-    if names:
-        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec', 'beam_coefs' and 'gains'")
-    if "gains" in names and gains is None:
-        raise ValueError("wrt='gains' needs gains=")
-    if chi2_per not in ("total", "freq_time"):
-        raise ValueError(f"chi2_per must be 'total' or 'freq_time', got {chi2_per!r}")
-    if adjoint_path not in ("type3", "type2", "auto"):
-        raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {adjoint_path!r}")
-    if "beam_coefs" in names and beam_coefs is None:
-        raise ValueError("wrt='beam_coefs' needs beam_coefs (basis beams)")
-    if beam_coefs is not None and not polarized:  # the forward's message
-        raise ValueError(
-            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
-        )
+    single, names = _fit_keywords(wrt, gains, "chi2_per", chi2_per, adjoint_path, beam_coefs, polarized)
     run = _describe_run(args)
     run = _own_radec_chain(run, "wrt='radec'", "radec" in names, "ask for wrt='topo' and apply its Jacobian",
                            "ask for wrt='topo'")
     fluxes, full_stokes = _sky_full_stokes(run, fluxes, full_stokes)
-    _run_device(run, (data,), "data")
-    if tuple(data.shape) != run.vis_shape:
-        raise ValueError(f"data must have simulate_vis's output shape {run.vis_shape}, got {tuple(data.shape)}")
+    _check_vis_block(run, data, "data")
     if weights is not None:
-        if tuple(weights.shape) != run.vis_shape:
-            raise ValueError(f"weights must have data's shape {run.vis_shape}, got {tuple(weights.shape)}")
-        if weights.is_complex() if _is_tensor(weights) else np.iscomplexobj(weights):
-            raise ValueError("weights must be real (inverse variances; 0 flags a sample)")
+        _check_weights(run, weights, "data's")
     gain_block = None if gains is None else _gain_block(run, gains)
     ggains = np.zeros(gain_block.shape, dtype=np.complex128) if "gains" in names else None
-    f_shape = (run.nsrc, run.nfreqs)
-    d, (gflux, gcoefs, gbls, gtopo), on_device = _gradient_buffers(run, data, [
-        None if "fluxes" not in names else (f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real"),
-        None if "beam_coefs" not in names else (run.beam_coefs.shape, "complex"),
-        None if "ants" not in names and "baselines" not in names else ((run.nbls, 3), "float64"),
-        None if "topo" not in names and "radec" not in names else ((run.ntimes, run.nsrc, 3), "float64")])
+    d, buffers, on_device = _gradient_buffers(run, data, _fit_outputs(run, names, full_stokes))
     w = None
     if weights is not None:
         w_device = _run_device(run, (weights,), "weights")
         w = _host(weights).astype(run.rdt, copy=False) if w_device is None else _on(w_device, weights, run.rdt)
         _synchronize(w_device)
-    gvis = None
-    if return_gvis:
-        import torch
-
-        gvis = _zeros(torch.device("cuda", int(device)), run.vis_shape, run.cdt)
-        _synchronize(gvis.device)
+    gvis = _gvis_buffer(run, return_gvis)
+    outputs = dict(zip(("gflux", "gcoefs", "gbls", "gtopo"), buffers), gvis=gvis)
     chi2_ft = _engine_simulate(
         run, fluxes, force_use_type3=None if set(names) <= {"fluxes"} else True, adjoint_path=adjoint_path,
-        objective_of=(d, w, dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis)) if gains is None else
-        (d, w, dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis, ggains=ggains), gain_block))
-    res = {"topo": gtopo, "baselines": gbls, "beam_coefs": gcoefs}
-    if "gains" in names:
-        res["gains"] = _gain_gradient(run, ggains, tuple(gains.shape))
-        if on_device:
-            import torch
-
-            res["gains"] = torch.from_numpy(res["gains"]).to(data.device)
-    if "fluxes" in names:
-        res["fluxes"] = stokes_adjoint(gflux, full_stokes)
-    if "radec" in names:
-        res["radec"] = topo_to_radec_gradient(gtopo, _radec_jacobian_of(run))
-    if "ants" in names:
-        res["ants"] = baseline_to_antenna_gradient(gbls, run.ants, run.baselines)
-    grads = _select({k: v for k, v in res.items() if k in names}, single, names, data, on_device) if names else ()
-    if chi2_per == "total":
-        chi2 = float(np.cumsum(chi2_ft.ravel())[-1])  # (added in row-major order)
-    else:
-        chi2 = chi2_ft
-        if _is_tensor(data):
-            import torch
-
-            chi2 = torch.from_numpy(chi2_ft).to(data.device)
-    if not return_gvis:
-        return chi2, grads
-    if not on_device:
-        gvis = gvis.cpu().numpy()
-        if _is_tensor(data):
-            import torch
-
-            gvis = torch.from_numpy(gvis)
-    return chi2, grads, gvis
+        objective_of=(d, w, outputs) if gains is None else (d, w, dict(outputs, ggains=ggains), gain_block))
+    like, dev = data if _is_tensor(data) else None, data.device if on_device else None
+    grads = _fit_gradients(run, single, names, buffers, full_stokes, ggains, gains, like, dev)
+    chi2 =_fit_value(chi2_ft, chi2_per, like, dev)
+    return (chi2, grads, _gvis_home(gvis, like, dev)) if return_gvis else (chi2, grads)
 
 
 def _chi2_autograd_function():
@@ -2232,24 +2285,7 @@ def simulate_vis_gain_gauss_newton(
         raise ValueError("give the source tangent as d_radec or as d_topo, not both")
     if wrt is None:
         wrt = given + (("gains",) if d_gains is not None else ())
-    single = isinstance(wrt, str)
-    names = (wrt,) if single else tuple(wrt)
-    if names:
-        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec', 'beam_coefs' and 'gains'")
-    if "gains" in names and gains is None:
-        raise ValueError("wrt='gains' needs gains=")
-    if quad_per not in ("total", "freq_time"):
-        raise ValueError(f"quad_per must be 'total' or 'freq_time', got {quad_per!r}")
-    if adjoint_path not in ("type3", "type2", "auto"):
-        raise ValueError(f"adjoint_path must be 'type3', 'type2' or 'auto', got {adjoint_path!r}")
-    if d_beam_coefs is not None and beam_coefs is None:
-        raise ValueError("d_beam_coefs needs beam_coefs (basis beams)")
-    if "beam_coefs" in names and beam_coefs is None:
-        raise ValueError("wrt='beam_coefs' needs beam_coefs (basis beams)")
-    if beam_coefs is not None and not polarized:  # the forward's message
-        raise ValueError(
-            "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
-        )
+    single, names = _fit_keywords(wrt, gains, "quad_per", quad_per, adjoint_path, beam_coefs, polarized, d_beam_coefs)
     run = _describe_run(args)
     run = _own_radec_chain(run, "d_radec" if d_radec is not None else "wrt='radec'", d_radec is not None or "radec" in names,
                            "pass d_topo and ask for wrt='topo', and apply its Jacobian", "pass d_topo and ask for wrt='topo'")
@@ -2267,10 +2303,7 @@ def simulate_vis_gain_gauss_newton(
         if not (d_beam_coefs.is_complex() if _is_tensor(d_beam_coefs) else np.iscomplexobj(d_beam_coefs)):
             raise ValueError("d_beam_coefs must be complex, like beam_coefs")
     if weights is not None:
-        if tuple(weights.shape) != run.vis_shape:
-            raise ValueError(f"weights must have simulate_vis's output shape {run.vis_shape}, got {tuple(weights.shape)}")
-        if weights.is_complex() if _is_tensor(weights) else np.iscomplexobj(weights):
-            raise ValueError("weights must be real (inverse variances; 0 flags a sample)")
+        _check_weights(run, weights, "simulate_vis's output")
     gain_block = dgain_block = None
     if gains is not None:
         gain_block = _gain_block(run, gains)
@@ -2292,64 +2325,24 @@ def simulate_vis_gain_gauss_newton(
     directions = dict(d_fluxes=None if d_fluxes is None else _host(d_fluxes),
                       d_beam_coefs=None if dc is None else dc.reshape((1,) + run.beam_coefs.shape),
                       d_baselines=_buffer(run, dev, d_baselines, "float64"), d_topo=_buffer(run, dev, d_topo, "float64"))
-    f_shape = (run.nsrc, run.nfreqs)
-    gflux, gcoefs, gbls, gtopo = (None if w_ is None else _zeros(dev, w_[0], run.dtype(w_[1])) for w_ in [
-        None if "fluxes" not in names else (f_shape + (2, 2), "complex") if full_stokes else (f_shape, "real"),
-        None if "beam_coefs" not in names else (run.beam_coefs.shape, "complex"),
-        None if "ants" not in names and "baselines" not in names else ((run.nbls, 3), "float64"),
-        None if "topo" not in names and "radec" not in names else ((run.ntimes, run.nsrc, 3), "float64")])
+    buffers = [None if w_ is None else _zeros(dev, w_[0], run.dtype(w_[1])) for w_ in _fit_outputs(run, names, full_stokes)]
     w = None
     if weights is not None:
         w = _host(weights).astype(run.rdt, copy=False) if dev is None or not _is_tensor(weights) or weights.device.type != "cuda" \
             else _on(dev, weights, run.rdt)
-    gvis = None
-    if return_gvis:
-        import torch
-
-        gvis = _zeros(torch.device("cuda", int(device)), run.vis_shape, run.cdt)
-        _synchronize(gvis.device)
+    gvis = _gvis_buffer(run, return_gvis)
     _synchronize(dev)
     # (the gains act on the output block whatever path produced it: they do not force the type-3 transform)
     fluxes_only = set(given) <= {"fluxes"} and set(names) <= {"fluxes", "gains"}
-    outputs = dict(gflux=gflux, gcoefs=gcoefs, gbls=gbls, gtopo=gtopo, gvis=gvis)
+    outputs = dict(zip(("gflux", "gcoefs", "gbls", "gtopo"), buffers), gvis=gvis)
     quad_ft = _engine_simulate(
         run, fluxes, force_use_type3=None if fluxes_only else True, adjoint_path=adjoint_path,
         gauss_newton_of=(directions, w, outputs) if gains is None else
         (directions, w, dict(outputs, ggains=hgains), (gain_block, dgain_block)))
-    on_device = dev is not None
-    res = {"topo": gtopo, "baselines": gbls, "beam_coefs": gcoefs}
-    if "gains" in names:
-        res["gains"] = _gain_gradient(run, hgains, tuple(gains.shape))
-        if on_device:
-            import torch
-
-            res["gains"] = torch.from_numpy(res["gains"]).to(dev)
-    if "fluxes" in names:
-        res["fluxes"] = stokes_adjoint(gflux, full_stokes)
-    if "radec" in names:
-        res["radec"] = topo_to_radec_gradient(gtopo, _radec_jacobian_of(run))
-    if "ants" in names:
-        res["ants"] = baseline_to_antenna_gradient(gbls, run.ants, run.baselines)
-    prods = _select({k: v for k, v in res.items() if k in names}, single, names, like, on_device) if names else ()
-    if quad_per == "total":
-        quad = float(np.cumsum(quad_ft.ravel())[-1]) if quad_ft.size else 0.0  # (added in row-major order)
-    else:
-        quad = quad_ft
-        if like is not None:
-            import torch
-
-            quad = torch.from_numpy(quad_ft)
-            if on_device:
-                quad = quad.to(dev)
-    if not return_gvis:
-        return quad, prods
-    if not on_device:
-        gvis = gvis.cpu().numpy()
-        if like is not None:
-            import torch
-
-            gvis = torch.from_numpy(gvis)
-    return quad, prods, gvis
+    prods = _fit_gradients(run, single, names, buffers, full_stokes, hgains, gains, like, dev)
+    # (no time steps: no rows to add)
+    quad = 0.0 if quad_per == "total" and not quad_ft.size else _fit_value(quad_ft, quad_per, like, dev)
+    return (quad, prods, _gvis_home(gvis, like, dev)) if return_gvis else (quad, prods)
 
 
 def _solve_start(run: _Run, gains, per_time: bool):
@@ -2479,19 +2472,12 @@ def simulate_vis_gain_solve(
         raise ValueError(f"ref_ant must be a key of ants, got {ref_ant!r}")
     if model is None:
         fluxes, _ = _sky_full_stokes(run, fluxes, full_stokes)
-    _run_device(run, (data,), "data")
-    if tuple(data.shape) != run.vis_shape:
-        raise ValueError(f"data must have simulate_vis's output shape {run.vis_shape}, got {tuple(data.shape)}")
+    _check_vis_block(run, data, "data")
     if weights is not None:
-        if tuple(weights.shape) != run.vis_shape:
-            raise ValueError(f"weights must have data's shape {run.vis_shape}, got {tuple(weights.shape)}")
-        if weights.is_complex() if _is_tensor(weights) else np.iscomplexobj(weights):
-            raise ValueError("weights must be real (inverse variances; 0 flags a sample)")
+        _check_weights(run, weights, "data's")
         _run_device(run, (weights,), "weights")
     if model is not None:
-        _run_device(run, (model,), "model")
-        if tuple(model.shape) != run.vis_shape:
-            raise ValueError(f"model must have simulate_vis's output shape {run.vis_shape}, got {tuple(model.shape)}")
+        _check_vis_block(run, model, "model")
     block, shape, own_time = _solve_start(run, gains, per_time)
 
     import torch

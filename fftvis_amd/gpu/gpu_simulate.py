@@ -13,7 +13,10 @@ from __future__ import annotations
 
 import ctypes
 import atexit
+import contextlib
 import logging
+import types
+import typing
 import warnings
 
 import numpy as np
@@ -607,6 +610,10 @@ class GPUSimulationEngine(SimulationEngine):
           of the block's shape and dtype, only its channel axis strided; it is pinned in place and filled while the
           run computes.  ``out_shared`` (extra): the underlying array is shared memory that other ranks fill too
           (``parallel.simulate_vis_sharded``).
+        * The eight mode keywords below -- ``adjoint_of``, ``tangent_of``, ``basis_tangent_of``, ``basis_source_of``,
+          ``sky_of``, ``objective_of``, ``gauss_newton_of``, ``forward_to`` -- each replace the forward run by another pass of
+          the engine these arguments configure, and exclude each other: two of them in one call are a ValueError whose
+          message is the later one's in that order, raised before anything else is looked at.
         * ``adjoint_of`` (extra; what ``simulate_vis_adjoint`` passes): a pair ``(g, gflux)`` -- instead of simulating,
           the engine configured by these arguments adds the adjoint of its map from ``fluxes`` (which then only give
           the catalog's shape) to visibilities, applied to ``g`` (the result's shape, this precision's complex dtype),
@@ -695,335 +702,53 @@ class GPUSimulationEngine(SimulationEngine):
           time block by time block (``SimHandle.run_device``), and stays there: nothing comes to the host, and the tensor
           is returned.
         """
-        if forward_to is not None and any(m is not None for m in (
-                adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of, gauss_newton_of, out)):
-            raise ValueError("forward_to is the plain forward run: no other pass and no out= with it")
-        if gauss_newton_of is not None:
-            if any(m is not None for m in (adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of)):
-                raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of, objective_of "
-                                 "and gauss_newton_of")
-            if (len(gauss_newton_of) not in (3, 4) or not isinstance(gauss_newton_of[0], dict)
-                    or not isinstance(gauss_newton_of[2], dict) or set(gauss_newton_of[0]) - set(_GAUSS_NEWTON_DIRECTIONS)
-                    or set(gauss_newton_of[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT}):
-                raise ValueError(f"gauss_newton_of: (directions, weights, outputs) with directions a dict over "
-                                 f"{_GAUSS_NEWTON_DIRECTIONS} and outputs a dict over {_OBJECTIVE_OUTPUTS}")
-            gn_gains = gauss_newton_of[3] if len(gauss_newton_of) == 4 else None
-            if gn_gains is not None and (not isinstance(gn_gains, tuple) or len(gn_gains) != 2 or gn_gains[0] is None):
-                raise ValueError("gauss_newton_of: the fourth element is (gains, d_gains), d_gains or None")
-            if gauss_newton_of[2].get(_GAIN_OUTPUT) is not None and gn_gains is None:
-                raise ValueError("gauss_newton_of: ggains needs the gains (a fourth element)")
-            if (all(gauss_newton_of[0].get(k) is None for k in _GAUSS_NEWTON_DIRECTIONS)
-                    and (gn_gains is None or gn_gains[1] is None)):
-                raise ValueError("gauss_newton_of: no direction given")
-            if beam_coefs is None and (gauss_newton_of[0].get("d_beam_coefs") is not None
-                                       or gauss_newton_of[2].get("gcoefs") is not None):
-                raise ValueError("gauss_newton_of: d_beam_coefs and gcoefs need basis beams (beam_coefs)")
-            if catalog_device is not None:
-                raise ValueError("gauss_newton_of does not take a device-resident catalog (catalog_device)")
-        if objective_of is not None:
-            if any(m is not None for m in (adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of)):
-                raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of, sky_of and objective_of")
-            if (len(objective_of) not in (3, 4) or not isinstance(objective_of[2], dict)
-                    or set(objective_of[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT}):
-                raise ValueError(f"objective_of: (data, weights, outputs) with outputs a dict over {_OBJECTIVE_OUTPUTS}")
-            if objective_of[2].get("gcoefs") is not None and beam_coefs is None:
-                raise ValueError("objective_of: gcoefs needs basis beams (beam_coefs)")
-            if objective_of[2].get(_GAIN_OUTPUT) is not None and (len(objective_of) == 3 or objective_of[3] is None):
-                raise ValueError("objective_of: ggains needs the gains (a fourth element)")
-        if sky_of is not None:
-            if adjoint_of is not None or tangent_of is not None or basis_tangent_of is not None or basis_source_of is not None:
-                raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of, basis_source_of and sky_of")
-            if len(sky_of) != 3:
-                raise ValueError("sky_of: (g, gflux, gtopo)")
-        if basis_source_of is not None:
-            if adjoint_of is not None or tangent_of is not None or basis_tangent_of is not None:
-                raise ValueError("pass one of adjoint_of, tangent_of, basis_tangent_of and basis_source_of")
-            if beam_coefs is None:
-                raise ValueError("basis_source_of needs basis beams (beam_coefs)")
-            if len(basis_source_of) != 3 or basis_source_of[0] not in ("adjoint", "tangent"):
-                raise ValueError("basis_source_of: ('adjoint', g, gtopo) or ('tangent', dtopo, dv)")
-        if basis_tangent_of is not None:
-            if adjoint_of is not None or tangent_of is not None:
-                raise ValueError("pass one of adjoint_of, tangent_of and basis_tangent_of")
-            if beam_coefs is None:
-                raise ValueError("basis_tangent_of needs basis beams (beam_coefs)")
-        if tangent_of is not None:
-            if adjoint_of is not None:
-                raise ValueError("pass either adjoint_of or tangent_of, not both")
-            if beam_coefs is not None and (tangent_of[1] is not None or tangent_of[0] is None):
-                raise ValueError("the tangent through basis beams (beam_coefs) takes baseline directions only: source "
-                                 "directions are not covered")
+        name, payload = _which_pass(dict(
+            adjoint_of=adjoint_of, tangent_of=tangent_of, basis_tangent_of=basis_tangent_of, basis_source_of=basis_source_of,
+            sky_of=sky_of, objective_of=objective_of, gauss_newton_of=gauss_newton_of, forward_to=forward_to), out, out_shared)
         if adjoint_path not in ADJOINT_PATHS:
             raise ValueError(f"adjoint_path must be one of {ADJOINT_PATHS}, got {adjoint_path!r}")
-        if adjoint_wrt not in ("fluxes", "positions", "sources"):
+        if adjoint_wrt not in _ADJOINT_WRT:
             raise ValueError(f"adjoint_wrt must be 'fluxes', 'positions' or 'sources', got {adjoint_wrt!r}")
-        positions = adjoint_of is not None and adjoint_wrt == "positions"
-        sources = adjoint_of is not None and adjoint_wrt == "sources"
-        if positions and beam_coefs is not None:
-            raise ValueError("the position adjoint does not cover basis beams (beam_coefs)")
-        if sources and beam_coefs is not None:
-            raise ValueError("the source adjoint does not cover basis beams (beam_coefs)")
-        beam_order = checked_spline_order(beam_spline_opts)
-        if interpolation_function not in ("az_za_map_coordinates", "az_za_simple"):
-            raise ValueError(f"unknown interpolation_function {interpolation_function!r}")
-        feed_index(use_feed)  # 'x' or 'y', else ValueError
-        nchunks = int(nchunks)
-        if nchunks < 1:
-            raise ValueError("nchunks must be >= 1")
-        if not 0.0 < float(source_buffer) <= 1.0:
-            raise ValueError("source_buffer must be in (0, 1]")
-        if astrom is None and device_astrometry and coord_mgr is None and coord_method != "SiderealRotation":
-            from ..core.coords import erfa_astrom_context
-
-            astrom = erfa_astrom_context(times, telescope_loc)
-        if astrom is not None:
-            astrom = np.ascontiguousarray(astrom, dtype=np.float64)
-            if astrom.ndim != 2 or astrom.shape[1] != 31 or astrom.shape[0] != len(julian_dates(times)):
-                raise ValueError("astrom must have shape (ntimes, 31): one eraASTROM context per time")
-            if coord_mgr is not None:
-                raise ValueError("pass either astrom= (device astrometry) or coord_mgr=, not both")
-        if coord_mgr is None and astrom is None and coord_method != "SiderealRotation" and catalog_device is not None:
-            raise ValueError(
-                "a device-resident catalog carries no ra / dec for a matvis coordinate manager: pass coord_mgr= "
-                "or coord_method='SiderealRotation'")
-        freqs = np.asarray(freqs)
-        nfreqs, ntimes, nbeam, nant = np.size(freqs), len(julian_dates(times)), len(beam_list), len(ants)
-        real_dtype = np.float32 if precision == 1 else np.float64
-        complex_dtype = np.complex64 if precision == 1 else np.complex128
-        if eps is None:
-            eps = default_accuracy_dict[precision]
-        if upsample_factor == 1.25 and eps < (1e-8 if precision == 2 else 1e-4):
-            # finufft's upsampfac = 1.25 has the same floor (its kernel width is capped likewise)
-            warnings.warn(
-                f"upsample_factor=1.25 delivers about {1e-8 if precision == 2 else 1e-4:g} at best "
-                f"(eps={eps:g} was asked for); use upsample_factor=2 or 'auto' for tighter tolerances.",
-                RuntimeWarning, stacklevel=2)
-        # precision = 1 rounds ra/dec/freqs to float32 first (reference cpu_simulate.py:601-606)
-        if catalog_device is None:
-            ra = np.asarray(ra).astype(real_dtype)
-            dec = np.asarray(dec).astype(real_dtype)
-            nsrc = int(ra.size)
-        else:
-            nsrc = int(catalog_device.nsrc)
-        freqs = freqs.astype(real_dtype)
-        ants = {k: np.asarray(v) for k, v in ants.items()}
-
-        beam_idx = utils.validate_beam_idx(beam_idx, beam_coefs, nbeam, nant)
-        if baselines is None:
-            baselines = [red[0] for red in utils.get_pos_reds(ants, include_autos=True)]
-        if catalog_device is None:
-            coherency, polarized_sky = utils.prepare_source_catalog(np.asarray(fluxes), polarized)
-            if coherency.shape[0] != nsrc or coherency.shape[1] != nfreqs:
-                raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
-        else:
-            _check_device_catalog(catalog_device, nfreqs, polarized, precision, self.device)
-
-        if coord_mgr is None and astrom is None and coord_method != "SiderealRotation":
-            # the reference's own call (wrapper.py:308-336 passes no manager): build matvis' manager exactly
-            # as the CPU engine does (cpu_simulate.py:686-709) and stream its vectors like a caller's
-            coord_mgr = build_coord_mgr(coord_method, coord_method_params, coherency.astype(complex_dtype, copy=False),
-                                        times, telescope_loc, ra, dec, precision, source_buffer, nchunks)
-
-        # lattice arrays -> type 1 (reference cpu_simulate.py:634-637, 661-681)
-        antvecs = np.array([ants[a] for a in ants], dtype=real_dtype)
-        is_gridded = False
-        if not force_use_type3 and beam_coefs is None and np.abs(antvecs[:, -1]).max() <= flat_array_tol:
-            is_gridded, gridded_antpos, basis_matrix = check_antpos_griddability(ants)
-        if is_gridded:
-            bls_int = np.round(np.array(
-                [gridded_antpos[bl[1]] - gridded_antpos[bl[0]] for bl in baselines]).T).astype(int)
-            bls_int = bls_int.reshape(3, len(baselines))
-            n_modes = 2 * int(np.round(np.max(np.abs(bls_int)))) + 1 if len(baselines) else 1
-            basis_matrix = (basis_matrix / utils.speed_of_light).astype(real_dtype)
-        else:
-            R, bls, is_coplanar = prepare_array(ants, baselines, flat_array_tol, real_dtype)
-        if positions and is_gridded:
-            raise ValueError("the position adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
-        if sources and is_gridded:
-            raise ValueError("the source adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
-        if sky_of is not None and is_gridded:
-            raise ValueError("the sky adjoint runs the type-3 transform: pass force_use_type3=True on a lattice array")
-        if objective_of is not None and is_gridded and any(
-                objective_of[2].get(k) is not None for k in ("gcoefs", "gbls", "gtopo")):
-            raise ValueError("the objective's position passes run the type-3 transform: pass force_use_type3=True on a "
-                             "lattice array")
-        if gauss_newton_of is not None and is_gridded and (
-                any(gauss_newton_of[0].get(k) is not None for k in ("d_beam_coefs", "d_baselines", "d_topo"))
-                or any(gauss_newton_of[2].get(k) is not None for k in ("gcoefs", "gbls", "gtopo"))):
-            raise ValueError("the Gauss-Newton product's position passes run the type-3 transform: pass force_use_type3=True "
-                             "on a lattice array")
-        if tangent_of is not None and is_gridded:
-            raise ValueError("the tangent runs the type-3 transform: pass force_use_type3=True on a lattice array")
-        if adjoint_path == "type2" and not is_gridded:
+        if name == "adjoint_of":  # three passes share the keyword
+            name = _ADJOINT_WRT[adjoint_wrt]
+        spec = _PASSES[name]
+        if spec.needs_basis and beam_coefs is None:
+            raise ValueError(f"{name} needs basis beams (beam_coefs)")
+        if spec.check is not None:
+            spec.check(payload, beam_coefs is not None)
+        if spec.host_catalog and catalog_device is not None:
+            raise ValueError(f"{name} does not take a device-resident catalog (catalog_device)")
+        s = _host_setup(
+            self.device, ants=ants, freqs=freqs, fluxes=fluxes, beam_list=beam_list, ra=ra, dec=dec, times=times,
+            telescope_loc=telescope_loc, baselines=baselines, beam_idx=beam_idx, precision=precision, polarized=polarized,
+            eps=eps, upsample_factor=upsample_factor, beam_spline_opts=beam_spline_opts, flat_array_tol=flat_array_tol,
+            interpolation_function=interpolation_function, coord_method=coord_method, coord_method_params=coord_method_params,
+            force_use_type3=force_use_type3, nchunks=nchunks, source_buffer=source_buffer, beam_coefs=beam_coefs,
+            coord_mgr=coord_mgr, time_idx=time_idx, freq_idx=freq_idx, use_feed=use_feed, catalog_device=catalog_device,
+            reference_compat=reference_compat, astrom=astrom, device_astrometry=device_astrometry)
+        if s.is_gridded and spec.type3 is not None and spec.type3(payload):
+            raise ValueError(f"{spec.refusal} the type-3 transform: pass force_use_type3=True on a lattice array")
+        if adjoint_path == "type2" and not s.is_gridded:
             raise ValueError(
                 "adjoint_path='type2' needs the lattice path: a flat, griddable array without force_use_type3 and "
                 "without basis beams (adjoint_path='auto' falls back to the type-3 transform)")
-        antnums = list(ants.keys())
-        use_basis = beam_coefs is not None
-        if use_basis:
-            if not polarized:  # reference wrapper.py:280-283
-                raise ValueError(
-                    "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
-                )
-            beam_coefs = np.asarray(beam_coefs)
-            if beam_coefs.shape != (nant, nbeam, nfreqs):
-                raise ValueError("beam_coefs must have shape (nant, nbasis, nfreqs)")
-            # per-baseline antenna rows of beam_coefs (reference cpu_simulate.py:920-921)
-            ant1_idxs = np.array([antnums.index(bl[0]) for bl in baselines])
-            ant2_idxs = np.array([antnums.index(bl[1]) for bl in baselines])
-        else:
-            pairs, pair_idx, pair_flip = utils.prepare_beam_evaluation(antnums, baselines, beam_idx)
-
-        key, h = _acquire_handle(self.device, precision, eps, upsample_factor, polarized)
-        ok = False
-        try:
-            if catalog_device is None:
-                h.set_sources(eq_unit_vectors(ra.astype(float), dec.astype(float)), coherency, polarized_sky)
-            else:
-                h.set_sources_device(nsrc, nfreqs, catalog_device.eq.data_ptr(), catalog_device.flux.data_ptr(),
-                                     catalog_device.polarized_sky)
-            if astrom is not None:
-                h.set_astrom(astrom)
-            elif coord_mgr is None:
-                h.set_times(SiderealRotation(times, telescope_loc).matrices())
-            h.set_freqs(freqs.astype(float))
-            if is_gridded:
-                logger.info("Using gridded coordinates for the array. Type 1 transform will be used.")
-                h.set_array_type1(basis_matrix.astype(float), bls_int, n_modes)
-            else:
-                h.set_array(R.astype(float), bls.astype(float), is_coplanar)
-            h.set_beams(beam_list, freqs.astype(float), beam_order, use_feed)
-            h.set_chunking(min(nchunks, max(nsrc, 1)), float(source_buffer))
-            h.set_reference_compat(reference_compat)
-            if use_basis:
-                h.set_basis(beam_coefs, ant1_idxs, ant2_idxs)
-            else:
-                h.set_beam_pairs(pairs, pair_idx, pair_flip)
-            t0, t1, _ = time_idx.indices(ntimes)
-            f0, f1, _ = freq_idx.indices(nfreqs)
+        t0, t1, f0, f1 = s.span
+        with _handle(self.device, precision, s.eps, upsample_factor, polarized) as h:
+            _configure(h, s)
+            if s.coord_mgr is not None:
+                s.coord_mgr.setup()
+            if spec.sets_adjoint_path and not s.use_basis:  # (a cached handle keeps its last setting)
+                h.set_adjoint_path("type2" if s.is_gridded and adjoint_path != "type3" else "type3")
+            if spec.prepare is not None:  # what of the payload needs the handle, or the device
+                payload = spec.prepare(h, s, payload)
             # Walk the time axis in blocks whose output fits comfortably in free device memory (the
             # reference holds the whole (nt, nbls, nfeeds, nfeeds, nf) block in host RAM,
             # cpu_simulate.py:909-911); a coordinate manager's vectors are streamed block by block
-            # instead of being stacked for all times on the host.
-            nblk_t = _time_block(self.device, t1 - t0, f1 - f0, len(baselines), polarized, precision,
-                                 nsrc if coord_mgr is not None else 0)
-            if coord_mgr is not None:
-                coord_mgr.setup()
-            if objective_of is not None:
-                if not use_basis:  # (a cached handle keeps its last setting)
-                    h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
-                # (a block's G, data and weights are on the device together: 2.5 blocks, 2 without weights)
-                scale = 2.0 if objective_of[1] is None else 2.5
-                nblk_t = _time_block(self.device, t1 - t0, int(np.ceil((f1 - f0) * scale)), len(baselines), polarized,
-                                     precision, nsrc if coord_mgr is not None else 0)
-                obj_gains = objective_of[3] if len(objective_of) == 4 else None
-                if obj_gains is not None:
-                    # (a block's gains and their gradient add (8 + 16) nfeed nant bytes per row to the 2.5 blocks of
-                    # 8 tpol nbls: under 0.1 % once nbls >= nant, so nblk_t above stands)
-                    nfeed = 2 if polarized else 1
-                    if (not isinstance(obj_gains, np.ndarray) or obj_gains.dtype != complex_dtype
-                            or obj_gains.shape != (f1 - f0, t1 - t0, nfeed, nant)):
-                        raise ValueError(f"objective_of: gains must be a {np.dtype(complex_dtype).name} array of shape "
-                                         f"{(f1 - f0, t1 - t0, nfeed, nant)}")
-                    row = {a: i for i, a in enumerate(antnums)}  # (list.index per baseline is 0.2 s at HERA-350's 61 075)
-                    nb = len(baselines)
-                    h.set_gain_pairs(nant, np.fromiter((row[bl[0]] for bl in baselines), np.int32, count=nb),
-                                     np.fromiter((row[bl[1]] for bl in baselines), np.int32, count=nb))
-                result = _run_objective(h, self.device, *objective_of[:3], t0, t1, f0, f1, nblk_t, coord_mgr, basis=use_basis,
-                                        gains=obj_gains)
-                ok = True
-                return result
-            if gauss_newton_of is not None:
-                directions, gn_weights, gn_outputs = gauss_newton_of[:3]
-                if not use_basis:  # (a cached handle keeps its last setting)
-                    h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
-                set_fluxes = None
-                if directions.get("d_fluxes") is not None:
-                    d_coherency, _ = utils.prepare_source_catalog(np.asarray(directions["d_fluxes"]), polarized)
-                    if d_coherency.shape != coherency.shape:  # (the same shape: the same kind of sky)
-                        raise ValueError(f"d_fluxes must have fluxes' shape, got {np.shape(directions['d_fluxes'])}")
-                    eq = eq_unit_vectors(ra.astype(float), dec.astype(float))
-
-                    def set_fluxes(tangent):  # the catalog's fluxes: the direction's for the forward part, else the real ones
-                        h.set_sources(eq, d_coherency if tangent else coherency, polarized_sky)
-                # (a block's parts and weights are on the device together: one block per part, half a block of weights)
-                nparts = _gauss_newton_nparts(directions, use_basis)
-                scale = nparts + (0.0 if gn_weights is None else 0.5)
-                if gn_gains is not None:
-                    nfeed = 2 if polarized else 1
-                    for name, x in zip(("gains", "d_gains"), gn_gains):
-                        if x is not None and (not isinstance(x, np.ndarray) or x.dtype != complex_dtype
-                                              or x.shape != (f1 - f0, t1 - t0, nfeed, nant)):
-                            raise ValueError(f"gauss_newton_of: {name} must be a {np.dtype(complex_dtype).name} array of "
-                                             f"shape {(f1 - f0, t1 - t0, nfeed, nant)}")
-                    row = {a: i for i, a in enumerate(antnums)}  # (as objective_of sets them)
-                    nb = len(baselines)
-                    h.set_gain_pairs(nant, np.fromiter((row[bl[0]] for bl in baselines), np.int32, count=nb),
-                                     np.fromiter((row[bl[1]] for bl in baselines), np.int32, count=nb))
-                    # (one more block when V is held; the gains, their direction and the product are under 0.1 % of one)
-                    scale += 1.0 if gn_gains[1] is not None or gn_outputs.get(_GAIN_OUTPUT) is not None else 0.0
-                nblk_t = _time_block(self.device, t1 - t0, int(np.ceil((f1 - f0) * scale)), len(baselines), polarized,
-                                     precision, nsrc if coord_mgr is not None else 0)
-                result = _run_gauss_newton(h, self.device, directions, gn_weights, gn_outputs, set_fluxes, t0, t1, f0, f1,
-                                           nblk_t, coord_mgr, basis=use_basis, gains=gn_gains)
-                ok = True
-                return result
-            if adjoint_of is not None:
-                if use_basis != (len(adjoint_of) in (3, 4)):
-                    raise ValueError("adjoint_of: (g, gflux, gcoefs[, gbls]) with beam_coefs, (g, gflux) without")
-                if not use_basis:  # (a cached handle keeps its last setting)
-                    h.set_adjoint_path("type2" if is_gridded and adjoint_path != "type3" else "type3")
-                result = _run_adjoint(h, adjoint_of[0], adjoint_of[1], t0, t1, f0, f1, nblk_t, coord_mgr,
-                                      gcoefs=adjoint_of[2] if use_basis else None, basis=use_basis, positions=positions,
-                                      sources=sources, gbls=adjoint_of[3] if len(adjoint_of) == 4 else None)
-                ok = True
-                return result
-            if tangent_of is not None:
-                result = _run_tangent(h, tangent_of[0], tangent_of[1], tangent_of[2], t0, t1, f0, f1, nblk_t, coord_mgr,
-                                      basis=use_basis)
-                ok = True
-                return result
-            if basis_source_of is not None:
-                result = _run_basis_source(h, *basis_source_of, t0, t1, f0, f1, nblk_t, coord_mgr)
-                ok = True
-                return result
-            if sky_of is not None:
-                result = _run_sky_adjoint(h, *sky_of, t0, t1, f0, f1, nblk_t, coord_mgr, basis=use_basis)
-                ok = True
-                return result
-            if basis_tangent_of is not None:
-                # (the device holds every direction's copy of a time block)
-                nblk_t = _time_block(self.device, t1 - t0, (f1 - f0) * int(basis_tangent_of[0].shape[0]), len(baselines),
-                                     polarized, precision, nsrc if coord_mgr is not None else 0)
-                result = _run_basis_tangent(h, basis_tangent_of[0], basis_tangent_of[1], t0, t1, f0, f1, nblk_t, coord_mgr)
-                ok = True
-                return result
-            if forward_to is not None:
-                forward_to = _forward_target(h, self.device, forward_to, t1 - t0, f1 - f0)
-                # (sized again now that the whole model is on the device: a block's temporary has to fit next to it)
-                nblk_t = _time_block(self.device, t1 - t0, f1 - f0, len(baselines), polarized, precision,
-                                     nsrc if coord_mgr is not None else 0)
-                result = _run_forward_to(h, forward_to, t0, t1, f0, f1, nblk_t, coord_mgr)
-                ok = True
-                return result
-            if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != complex_dtype):
-                raise ValueError(f"out must be a {np.dtype(complex_dtype).name} array of shape "
-                                 f"{h.out_shape(t1 - t0, f1 - f0)}, got {out.dtype} {out.shape}")
-            if nblk_t >= t1 - t0 and coord_mgr is None:
-                vis = h.run(t0, t1, f0, f1, out=out, shared=out_shared)
-            else:
-                # every time block lands in its slice of the result (fv_sim_run_into): no block-sized temporary, no
-                # second host copy
-                vis = out if out is not None else np.empty(h.out_shape(t1 - t0, f1 - f0), dtype=complex_dtype)
-                for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
-                    h.run(ta, te_, f0, f1, out=vis[:, tb - t0:te - t0], shared=out_shared)
-            ok = True
-        finally:
-            if ok:
-                _return_handle(key, h)
-            else:  # an error may have left it half configured
-                h.close()
-        return vis if out is not None else vis.astype(complex_dtype, copy=False)
+            # instead of being stacked for all times on the host.  ``spec.blocks``: the blocks of the output's size
+            # that the pass holds on the device per time step.
+            nblk_t = _time_block(self.device, t1 - t0, int(np.ceil((f1 - f0) * spec.blocks(payload, s))), len(s.baselines),
+                                 polarized, precision, s.nsrc if s.coord_mgr is not None else 0)
+            return spec.run(h, s, payload, nblk_t)
 
     def _evaluate_vis_chunk(self, time_idx: slice, freq_idx: slice, **kw) -> np.ndarray:
         """One (time x freq) block in the reference's scratch layout
@@ -1034,6 +759,163 @@ class GPUSimulationEngine(SimulationEngine):
         if polarized:  # inverse of np.transpose(vis, (4, 0, 2, 3, 1)), cpu_simulate.py:851
             return np.transpose(final, (1, 4, 2, 3, 0))
         return np.moveaxis(final, 0, 2)[:, :, None, None, :]
+
+
+def _host_setup(device, *, ants, freqs, fluxes, beam_list, ra, dec, times, telescope_loc, baselines, beam_idx, precision,
+                polarized, eps, upsample_factor, beam_spline_opts, flat_array_tol, interpolation_function, coord_method,
+                coord_method_params, force_use_type3, nchunks, source_buffer, beam_coefs, coord_mgr, time_idx, freq_idx,
+                use_feed, catalog_device, reference_compat, astrom, device_astrometry):
+    """``simulate``'s plain arguments, checked, as everything a handle will be told (``_configure``) and the loops need:
+    one record.  Host work only: no handle, no device."""
+    beam_order = checked_spline_order(beam_spline_opts)
+    if interpolation_function not in ("az_za_map_coordinates", "az_za_simple"):
+        raise ValueError(f"unknown interpolation_function {interpolation_function!r}")
+    feed_index(use_feed)  # 'x' or 'y', else ValueError
+    nchunks = int(nchunks)
+    if nchunks < 1:
+        raise ValueError("nchunks must be >= 1")
+    if not 0.0 < float(source_buffer) <= 1.0:
+        raise ValueError("source_buffer must be in (0, 1]")
+    if astrom is None and device_astrometry and coord_mgr is None and coord_method != "SiderealRotation":
+        from ..core.coords import erfa_astrom_context
+
+        astrom = erfa_astrom_context(times, telescope_loc)
+    if astrom is not None:
+        astrom = np.ascontiguousarray(astrom, dtype=np.float64)
+        if astrom.ndim != 2 or astrom.shape[1] != 31 or astrom.shape[0] != len(julian_dates(times)):
+            raise ValueError("astrom must have shape (ntimes, 31): one eraASTROM context per time")
+        if coord_mgr is not None:
+            raise ValueError("pass either astrom= (device astrometry) or coord_mgr=, not both")
+    if coord_mgr is None and astrom is None and coord_method != "SiderealRotation" and catalog_device is not None:
+        raise ValueError(
+            "a device-resident catalog carries no ra / dec for a matvis coordinate manager: pass coord_mgr= "
+            "or coord_method='SiderealRotation'")
+    freqs = np.asarray(freqs)
+    nfreqs, ntimes, nbeam, nant = np.size(freqs), len(julian_dates(times)), len(beam_list), len(ants)
+    real_dtype = np.float32 if precision == 1 else np.float64
+    complex_dtype = np.complex64 if precision == 1 else np.complex128
+    if eps is None:
+        eps = default_accuracy_dict[precision]
+    if upsample_factor == 1.25 and eps < (1e-8 if precision == 2 else 1e-4):
+        # finufft's upsampfac = 1.25 has the same floor (its kernel width is capped likewise)
+        warnings.warn(
+            f"upsample_factor=1.25 delivers about {1e-8 if precision == 2 else 1e-4:g} at best "
+            f"(eps={eps:g} was asked for); use upsample_factor=2 or 'auto' for tighter tolerances.",
+            RuntimeWarning, stacklevel=3)  # (simulate's caller)
+    # precision = 1 rounds ra/dec/freqs to float32 first (reference cpu_simulate.py:601-606)
+    eq = coherency = polarized_sky = None
+    if catalog_device is None:
+        ra = np.asarray(ra).astype(real_dtype)
+        dec = np.asarray(dec).astype(real_dtype)
+        nsrc = int(ra.size)
+    else:
+        nsrc = int(catalog_device.nsrc)
+    freqs = freqs.astype(real_dtype)
+    ants = {k: np.asarray(v) for k, v in ants.items()}
+
+    beam_idx = utils.validate_beam_idx(beam_idx, beam_coefs, nbeam, nant)
+    if baselines is None:
+        baselines = [red[0] for red in utils.get_pos_reds(ants, include_autos=True)]
+    if catalog_device is None:
+        coherency, polarized_sky = utils.prepare_source_catalog(np.asarray(fluxes), polarized)
+        if coherency.shape[0] != nsrc or coherency.shape[1] != nfreqs:
+            raise ValueError("fluxes must have shape (nsources, nfreqs[, 4])")
+        eq = eq_unit_vectors(ra.astype(float), dec.astype(float))
+    else:
+        _check_device_catalog(catalog_device, nfreqs, polarized, precision, device)
+
+    if coord_mgr is None and astrom is None and coord_method != "SiderealRotation":
+        # the reference's own call (wrapper.py:308-336 passes no manager): build matvis' manager exactly
+        # as the CPU engine does (cpu_simulate.py:686-709) and stream its vectors like a caller's
+        coord_mgr = build_coord_mgr(coord_method, coord_method_params, coherency.astype(complex_dtype, copy=False),
+                                    times, telescope_loc, ra, dec, precision, source_buffer, nchunks)
+
+    # lattice arrays -> type 1 (reference cpu_simulate.py:634-637, 661-681)
+    antvecs = np.array([ants[a] for a in ants], dtype=real_dtype)
+    is_gridded = False
+    if not force_use_type3 and beam_coefs is None and np.abs(antvecs[:, -1]).max() <= flat_array_tol:
+        is_gridded, gridded_antpos, basis_matrix = check_antpos_griddability(ants)
+    if is_gridded:
+        bls_int = np.round(np.array(
+            [gridded_antpos[bl[1]] - gridded_antpos[bl[0]] for bl in baselines]).T).astype(int)
+        bls_int = bls_int.reshape(3, len(baselines))
+        n_modes = 2 * int(np.round(np.max(np.abs(bls_int)))) + 1 if len(baselines) else 1
+        array = ((basis_matrix / utils.speed_of_light).astype(real_dtype).astype(float), bls_int, n_modes)
+    else:
+        R, bls, is_coplanar = prepare_array(ants, baselines, flat_array_tol, real_dtype)
+        array = (R.astype(float), bls.astype(float), is_coplanar)
+    antnums = list(ants.keys())
+    use_basis = beam_coefs is not None
+    if use_basis:
+        if not polarized:  # reference wrapper.py:280-283
+            raise ValueError(
+                "Basis decomposition is not compatible with unpolarized simulations. Set polarized=True to use beam_coefs."
+            )
+        beam_coefs = np.asarray(beam_coefs)
+        if beam_coefs.shape != (nant, nbeam, nfreqs):
+            raise ValueError("beam_coefs must have shape (nant, nbasis, nfreqs)")
+        # per-baseline antenna rows of beam_coefs (reference cpu_simulate.py:920-921)
+        beams = (beam_coefs, np.array([antnums.index(bl[0]) for bl in baselines]),
+                 np.array([antnums.index(bl[1]) for bl in baselines]))
+    else:
+        beams = utils.prepare_beam_evaluation(antnums, baselines, beam_idx)  # (pairs, pair_idx, pair_flip)
+    t0, t1, _ = time_idx.indices(ntimes)
+    f0, f1, _ = freq_idx.indices(nfreqs)
+    return types.SimpleNamespace(
+        device=device, polarized=polarized, eps=eps, cdt=complex_dtype, nsrc=nsrc, nfreqs=nfreqs, nant=nant, antnums=antnums,
+        baselines=baselines, span=(t0, t1, f0, f1),
+        # the catalog: host arrays, or the device-resident one
+        eq=eq, coherency=coherency, polarized_sky=polarized_sky, catalog_device=catalog_device,
+        # the sources' directions per time: contexts, a manager's streamed vectors, or the sidereal rotations
+        astrom=astrom, coord_mgr=coord_mgr,
+        rotations=SiderealRotation(times, telescope_loc).matrices() if astrom is None and coord_mgr is None else None,
+        freqs=freqs.astype(float),
+        # set_array_type1's arguments on the lattice path (is_gridded), else set_array's
+        is_gridded=is_gridded, array=array,
+        beam_list=beam_list, beam_order=beam_order, use_feed=use_feed, nchunks=min(nchunks, max(nsrc, 1)),
+        source_buffer=float(source_buffer), reference_compat=reference_compat,
+        # set_basis' arguments with basis beams (use_basis), else set_beam_pairs'
+        use_basis=use_basis, beams=beams)
+
+
+def _configure(h, s):
+    """Tell the handle ``h`` the run ``s`` (``_host_setup``'s record).  Every ``set_*`` fully replaces what it configures,
+    so a cached handle serves any run of its creation parameters."""
+    if s.catalog_device is None:
+        h.set_sources(s.eq, s.coherency, s.polarized_sky)
+    else:
+        h.set_sources_device(s.nsrc, s.nfreqs, s.catalog_device.eq.data_ptr(), s.catalog_device.flux.data_ptr(),
+                             s.catalog_device.polarized_sky)
+    if s.astrom is not None:
+        h.set_astrom(s.astrom)
+    elif s.coord_mgr is None:
+        h.set_times(s.rotations)
+    h.set_freqs(s.freqs)
+    if s.is_gridded:
+        logger.info("Using gridded coordinates for the array. Type 1 transform will be used.")
+        h.set_array_type1(*s.array)
+    else:
+        h.set_array(*s.array)
+    h.set_beams(s.beam_list, s.freqs, s.beam_order, s.use_feed)
+    h.set_chunking(s.nchunks, s.source_buffer)
+    h.set_reference_compat(s.reference_compat)
+    if s.use_basis:
+        h.set_basis(*s.beams)
+    else:
+        h.set_beam_pairs(*s.beams)
+
+
+@contextlib.contextmanager
+def _handle(device, precision, eps, upsample_factor, polarized):
+    """A handle for one run: back among the idle handles when the block ends, closed when it raises (an error may have
+    left it half configured)."""
+    key, h = _acquire_handle(device, precision, eps, upsample_factor, polarized)
+    try:
+        yield h
+    except BaseException:
+        h.close()
+        raise
+    _return_handle(key, h)
 
 
 def build_coord_mgr(coord_method, coord_method_params, coherency, times, telescope_loc, ra, dec, precision,
@@ -1136,6 +1018,33 @@ def _result_block(dv, axis, lo, hi, whole):
     return blk, dst
 
 
+def _block_input(x, lo, hi):
+    """The time steps [lo, hi) (axis 1) of a pass's input ``x``, a numpy array or a tensor, as the library reads them:
+    contiguous, and complete before the call that follows.  None stays None."""
+    if x is None:
+        return None
+    blk = x[:, lo:hi]
+    if isinstance(x, np.ndarray):
+        return np.ascontiguousarray(blk)
+    import torch
+
+    blk = blk.contiguous()
+    torch.cuda.synchronize(blk.device)  # a copy .contiguous() queued on torch's stream is done before the library reads
+    return blk
+
+
+def _run_forward(h, out, shared, t0, t1, f0, f1, nblk_t, coord_mgr):
+    """The forward's time loop: one ``run`` when a block is the whole result and no coordinate manager streams its
+    vectors, else every time block lands in its slice of the result (``fv_sim_run_into``): no block-sized temporary, no
+    second host copy.  ``out``: the caller's array, or None for a new one."""
+    if nblk_t >= t1 - t0 and coord_mgr is None:
+        return h.run(t0, t1, f0, f1, out=out, shared=shared)
+    vis = out if out is not None else np.empty(h.out_shape(t1 - t0, f1 - f0), dtype=h.cdt)
+    for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
+        h.run(ta, te_, f0, f1, out=vis[:, tb - t0:te - t0], shared=shared)
+    return vis
+
+
 def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, basis=False, positions=False, sources=False,
                  gbls=None):
     """The adjoint's time loop: the forward's blocks (and, with a coordinate manager, its streamed vectors), each block's
@@ -1144,17 +1053,9 @@ def _run_adjoint(h, g, gflux, t0, t1, f0, f1, nblk_t, coord_mgr, gcoefs=None, ba
     (nbls, 3) baseline gradient and ``run_position_adjoint`` adds to it.  ``sources``: ``gflux`` is the (t1 - t0, nsrc, 3)
     direction gradient and every block's ``run_source_adjoint`` fills that block's rows).  Every ``run_adjoint`` call ends
     synchronised."""
-    on_device = not isinstance(g, np.ndarray)
     first = True
     for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
-        blk = g[:, tb - t0:te - t0]
-        if on_device:
-            import torch
-
-            blk = blk.contiguous()
-            torch.cuda.synchronize(blk.device)  # a copy .contiguous() queued on torch's stream is done before the library reads
-        else:
-            blk = np.ascontiguousarray(blk)
+        blk = _block_input(g, tb - t0, te - t0)
         if basis:
             if gflux is not None or gcoefs is not None:
                 h.run_basis_adjoint(ta, te_, f0, f1, blk, gflux, gcoefs, not first)
@@ -1201,15 +1102,7 @@ def _run_basis_source(h, mode, a, b, t0, t1, f0, f1, nblk_t, coord_mgr):
     goes through a contiguous temporary).  Every call ends synchronised."""
     for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
         if mode == "adjoint":
-            blk = a[:, tb - t0:te - t0]
-            if isinstance(a, np.ndarray):
-                blk = np.ascontiguousarray(blk)
-            else:
-                import torch
-
-                blk = blk.contiguous()
-                torch.cuda.synchronize(blk.device)  # a copy .contiguous() queued on torch's stream is done before the library reads
-            h.run_basis_source_adjoint(ta, te_, f0, f1, blk, b[tb - t0:te - t0], False)
+            h.run_basis_source_adjoint(ta, te_, f0, f1, _block_input(a, tb - t0, te - t0), b[tb - t0:te - t0], False)
         else:
             blk, dst = _result_block(b, 1, tb - t0, te - t0, tb == t0 and te == t1)
             h.run_basis_source_tangent(ta, te_, f0, f1, a[tb - t0:te - t0], blk)
@@ -1225,17 +1118,9 @@ def _run_sky_adjoint(h, g, gflux, gtopo, t0, t1, f0, f1, nblk_t, coord_mgr, basi
     every block's ``run_sky_adjoint`` adds its contribution to ``gflux`` -- the first block overwrites -- and fills its rows
     of ``gtopo``, the (t1 - t0, nsrc, 3) direction gradient.  The two outputs share one ``accumulate`` flag, so a later
     block adds to its rows of the caller's zeroed buffer.  Every call ends synchronised."""
-    on_device = not isinstance(g, np.ndarray)
     first = True
     for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
-        blk = g[:, tb - t0:te - t0]
-        if on_device:
-            import torch
-
-            blk = blk.contiguous()
-            torch.cuda.synchronize(blk.device)  # a copy .contiguous() queued on torch's stream is done before the library reads
-        else:
-            blk = np.ascontiguousarray(blk)
+        blk = _block_input(g, tb - t0, te - t0)
         # (rows of a C-contiguous array: a contiguous view, written in place)
         h.run_sky_adjoint(ta, te_, f0, f1, blk, gflux, gtopo[tb - t0:te - t0], not first, basis=basis)
         first = False
@@ -1257,52 +1142,56 @@ def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, co
     t1 - t0, nfeed, nant)) every block's ``run_gain_residual`` takes its time steps of them instead and fills its time
     steps of ``outputs["ggains"]``; the passes read its G unchanged.  Returns chi2, (f1 - f0, t1 - t0) float64 on the
     host.  Every call ends synchronised."""
-    import torch
-
-    gflux, gcoefs, gbls, gtopo, gvis = (outputs.get(k) for k in _OBJECTIVE_OUTPUTS)
     ggains = outputs.get(_GAIN_OUTPUT)
-    dev = torch.device("cuda", int(device))
-    cdt = getattr(torch, np.dtype(h.cdt).name)
-
-    def block(x, tb, te):  # x's time steps [tb, te), contiguous, complete before the library reads
-        if x is None:
-            return None
-        blk = x[:, tb - t0:te - t0]
-        if isinstance(x, np.ndarray):
-            return np.ascontiguousarray(blk)
-        blk = blk.contiguous()
-        torch.cuda.synchronize(blk.device)
-        return blk
-
     chi2 = np.zeros((f1 - f0, t1 - t0), dtype=np.float64)
-    first = True
     for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
-        whole = tb == t0 and te == t1
-        if gvis is not None and whole:
-            g = gvis
-        else:
-            g = torch.empty(h.out_shape(te - tb, f1 - f0), dtype=cdt, device=dev)
-            torch.cuda.synchronize(dev)
+        lo, hi = tb - t0, te - t0
+        g, = _device_blocks(h, device, 1, outputs, lo, hi, t1 - t0, f1 - f0)
+        d, w = _block_input(data, lo, hi), _block_input(weights, lo, hi)
         if gains is None:
-            chi2[:, tb - t0:te - t0] = h.run_residual(ta, te_, f0, f1, block(data, tb, te), block(weights, tb, te), g)
+            chi2[:, lo:hi] = h.run_residual(ta, te_, f0, f1, d, w, g)
         else:
-            gg = None if ggains is None else np.empty(gains[:, tb - t0:te - t0].shape, dtype=np.complex128)
-            chi2[:, tb - t0:te - t0] = h.run_gain_residual(ta, te_, f0, f1, block(data, tb, te), block(weights, tb, te),
-                                                           block(gains, tb, te), g, gg)
+            gg = _gain_output_block(ggains, lo, hi)
+            chi2[:, lo:hi] = h.run_gain_residual(ta, te_, f0, f1, d, w, _block_input(gains, lo, hi), g, gg)
             if gg is not None:
-                ggains[:, tb - t0:te - t0] = gg
-        if gvis is not None and not whole:
-            gvis[:, tb - t0:te - t0] = g
-            torch.cuda.synchronize(dev)
-        rows = None if gtopo is None else gtopo[tb - t0:te - t0]  # (rows of a C-contiguous array: a contiguous view)
-        _adjoints_of_block(h, g, gflux, gcoefs, gbls, rows, ta, te_, f0, f1, first, basis)
-        first = False
+                ggains[:, lo:hi] = gg
+        _adjoints_of_block(h, g, outputs, lo, hi, t1 - t0, ta, te_, f0, f1, basis)
     return chi2
 
 
-def _adjoints_of_block(h, g, gflux, gcoefs, gbls, rows, ta, te_, f0, f1, first, basis):
-    """The handle passes of one time block for the outputs given, on the device block ``g`` (``_run_objective``,
-    ``_run_gauss_newton``): ``rows`` are the block's rows of ``gtopo``; the ``first`` block overwrites the other outputs."""
+def _device_blocks(h, device, n, outputs, lo, hi, nt, nf):
+    """``n`` device blocks for the time steps [lo, hi) of a fit pass (``_run_objective``, ``_run_gauss_newton``), each a new
+    C-contiguous tensor of ``out_shape(hi - lo, nf)`` in the handle's complex dtype -- but the first, which receives G, is
+    ``outputs["gvis"]`` itself when that is given and the block is the whole result of ``nt`` steps.  Complete before the
+    library writes them."""
+    import torch
+
+    dev = torch.device("cuda", int(device))
+    whole_gvis = outputs.get("gvis") if (lo, hi) == (0, nt) else None
+    blocks = [torch.empty(h.out_shape(hi - lo, nf), dtype=getattr(torch, np.dtype(h.cdt).name), device=dev)
+              for _ in range(n - int(whole_gvis is not None))]
+    torch.cuda.synchronize(dev)
+    return blocks if whole_gvis is None else [whole_gvis] + blocks
+
+
+def _gain_output_block(ggains, lo, hi):
+    """A contiguous host block for the time steps [lo, hi) of the gain output ``ggains`` (complex128, the gains' block
+    layout), which the caller copies to ``ggains[:, lo:hi]`` once the library has filled it; None stays None."""
+    return None if ggains is None else np.empty(ggains[:, lo:hi].shape, dtype=np.complex128)
+
+
+def _adjoints_of_block(h, g, outputs, lo, hi, nt, ta, te_, f0, f1, basis):
+    """What follows G of the time steps [lo, hi) out of ``nt``, in the device block ``g`` (``_run_objective``,
+    ``_run_gauss_newton``): its copy into ``outputs["gvis"]`` unless ``g`` is that tensor, then the handle passes for the
+    outputs given, which take the block's rows of ``gtopo``; the first block overwrites the other outputs, later ones add."""
+    gflux, gcoefs, gbls, gtopo, gvis = (outputs.get(k) for k in _OBJECTIVE_OUTPUTS)
+    if gvis is not None and g is not gvis:
+        import torch
+
+        gvis[:, lo:hi] = g
+        torch.cuda.synchronize(g.device)
+    first = lo == 0
+    rows = None if gtopo is None else gtopo[lo:hi]  # (rows of a C-contiguous array: a contiguous view)
     if gflux is not None and rows is not None:  # one pass for both
         h.run_sky_adjoint(ta, te_, f0, f1, g, gflux, rows, not first, basis=basis)
         if gcoefs is not None:
@@ -1333,6 +1222,12 @@ def _gauss_newton_nparts(directions, basis):
     return sum(given) if basis else int(given[0]) + int(given[2] or given[3])
 
 
+def _gauss_newton_holds_v(outputs, gains):
+    """Whether a time block of the Gauss-Newton product holds V in one more device block: only with a gain direction or
+    the gain block of H p as an output.  ``gains``: (gains, d_gains) or None."""
+    return gains is not None and (gains[1] is not None or outputs.get(_GAIN_OUTPUT) is not None)
+
+
 def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False,
                       gains=None):
     """The Gauss-Newton product's time loop, over the forward's blocks (and, with a coordinate manager, its streamed
@@ -1346,37 +1241,17 @@ def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t
     rows are sum w |U'|^2; only with ``d_gains`` or ``outputs["ggains"]`` one more block is filled with V -- ``run_device``
     at the real fluxes, after the parts -- and the block's time steps of ``ggains`` are filled; without a sky direction V's
     block receives G.  Returns the rows, (f1 - f0, t1 - t0) float64 on the host.  Every call ends synchronised."""
-    import torch
-
-    gflux, gcoefs, gbls, gtopo, gvis = (outputs.get(k) for k in _OBJECTIVE_OUTPUTS)
     ggains = outputs.get(_GAIN_OUTPUT)
     d_fluxes, d_coefs, d_bls, d_topo = (directions.get(k) for k in _GAUSS_NEWTON_DIRECTIONS)
-    hold_v = gains is not None and (gains[1] is not None or ggains is not None)
-    dev = torch.device("cuda", int(device))
-    cdt = getattr(torch, np.dtype(h.cdt).name)
+    hold_v = _gauss_newton_holds_v(outputs, gains)
     nparts = _gauss_newton_nparts(directions, basis)
-
-    def block(x, tb, te):  # x's time steps [tb, te), contiguous, complete before the library reads
-        if x is None:
-            return None
-        blk = x[:, tb - t0:te - t0]
-        if isinstance(x, np.ndarray):
-            return np.ascontiguousarray(blk)
-        blk = blk.contiguous()
-        torch.cuda.synchronize(blk.device)
-        return blk
-
     quad = np.zeros((f1 - f0, t1 - t0), dtype=np.float64)
-    first = True
     for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
-        whole = tb == t0 and te == t1
-        shape = h.out_shape(te - tb, f1 - f0)
+        lo, hi = tb - t0, te - t0
         # (block 0 receives G: the first part, or V for a gains-only direction)
-        parts = [gvis if gvis is not None and whole and j == 0 else torch.empty(shape, dtype=cdt, device=dev)
-                 for j in range(nparts + int(hold_v))]
+        parts = _device_blocks(h, device, nparts + int(hold_v), outputs, lo, hi, t1 - t0, f1 - f0)
         vis = parts.pop(0 if nparts == 0 else -1) if hold_v else None
-        torch.cuda.synchronize(dev)
-        rows_in = None if d_topo is None else d_topo[tb - t0:te - t0]  # (rows of a C-contiguous array: a contiguous view)
+        rows_in = None if d_topo is None else d_topo[lo:hi]  # (rows of a C-contiguous array: a contiguous view)
         todo = iter(parts)
         if d_fluxes is not None:
             set_fluxes(True)
@@ -1394,22 +1269,16 @@ def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t
             h.run_tangent(ta, te_, f0, f1, d_bls, rows_in, next(todo))
         if hold_v:  # (the real fluxes are back)
             h.run_device(ta, te_, f0, f1, vis.data_ptr())
+        w = _block_input(weights, lo, hi)
         if gains is None:
-            g = parts[0]
-            quad[:, tb - t0:te - t0] = h.weight_block(ta, te_, f0, f1, parts, block(weights, tb, te))
+            quad[:, lo:hi] = h.weight_block(ta, te_, f0, f1, parts, w)
         else:
-            g = parts[0] if parts else vis
-            hg = None if ggains is None else np.empty(gains[0][:, tb - t0:te - t0].shape, dtype=np.complex128)
-            quad[:, tb - t0:te - t0] = h.gain_weight_block(ta, te_, f0, f1, parts, vis, block(weights, tb, te),
-                                                           block(gains[0], tb, te), block(gains[1], tb, te), hg)
+            hg = _gain_output_block(ggains, lo, hi)
+            quad[:, lo:hi] = h.gain_weight_block(ta, te_, f0, f1, parts, vis, w, _block_input(gains[0], lo, hi),
+                                                 _block_input(gains[1], lo, hi), hg)
             if hg is not None:
-                ggains[:, tb - t0:te - t0] = hg
-        if gvis is not None and not whole:
-            gvis[:, tb - t0:te - t0] = g
-            torch.cuda.synchronize(dev)
-        rows = None if gtopo is None else gtopo[tb - t0:te - t0]
-        _adjoints_of_block(h, g, gflux, gcoefs, gbls, rows, ta, te_, f0, f1, first, basis)
-        first = False
+                ggains[:, lo:hi] = hg
+        _adjoints_of_block(h, parts[0] if parts else vis, outputs, lo, hi, t1 - t0, ta, te_, f0, f1, basis)
     return quad
 
 
@@ -1458,6 +1327,207 @@ def _run_basis_tangent(h, dcoefs, dv, t0, t1, f0, f1, nblk_t, coord_mgr):
     if t1 <= t0:
         dv[...] = 0
     return dv
+
+
+# ---- the passes of ``simulate``: which one a call asks for, and what ``simulate`` has to know about each ----
+
+# the mode keywords, in the order they were added: two of them in one call are refused in the name of the later one
+_MODES = ("adjoint_of", "tangent_of", "basis_tangent_of", "basis_source_of", "sky_of", "objective_of", "gauss_newton_of",
+          "forward_to")
+_ADJOINT_WRT = {"fluxes": "adjoint_of", "positions": "position_adjoint", "sources": "source_adjoint"}  # adjoint_of's passes
+
+
+def _which_pass(modes: dict, out, out_shared):
+    """(name, payload) of the pass a call asks for: the one mode keyword given (``modes``: every keyword of ``_MODES`` with
+    its value) with its value, or ("forward", (out, out_shared)).  ValueError for more than one."""
+    given = [k for k in _MODES if modes[k] is not None]
+    if "forward_to" in given and (len(given) > 1 or out is not None):
+        raise ValueError("forward_to is the plain forward run: no other pass and no out= with it")
+    if len(given) > 1:
+        earlier = _MODES[:_MODES.index(given[-1])]
+        if len(earlier) == 1:
+            raise ValueError(f"pass either {earlier[0]} or {given[-1]}, not both")
+        raise ValueError(f"pass one of {', '.join(earlier)} and {given[-1]}")
+    return (given[0], modes[given[0]]) if given else ("forward", (out, out_shared))
+
+
+def _check_adjoint(p, basis):
+    if basis != (len(p) in (3, 4)):
+        raise ValueError("adjoint_of: (g, gflux, gcoefs[, gbls]) with beam_coefs, (g, gflux) without")
+
+
+def _no_basis_beams(what):
+    def check(p, basis):
+        if basis:
+            raise ValueError(f"the {what} adjoint does not cover basis beams (beam_coefs)")
+        _check_adjoint(p, basis)
+    return check
+
+
+def _check_tangent(p, basis):
+    if basis and (p[1] is not None or p[0] is None):
+        raise ValueError("the tangent through basis beams (beam_coefs) takes baseline directions only: source "
+                         "directions are not covered")
+
+
+def _check_basis_source(p, basis):
+    if len(p) != 3 or p[0] not in ("adjoint", "tangent"):
+        raise ValueError("basis_source_of: ('adjoint', g, gtopo) or ('tangent', dtopo, dv)")
+
+
+def _check_sky(p, basis):
+    if len(p) != 3:
+        raise ValueError("sky_of: (g, gflux, gtopo)")
+
+
+def _check_objective(p, basis):
+    if len(p) not in (3, 4) or not isinstance(p[2], dict) or set(p[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT}:
+        raise ValueError(f"objective_of: (data, weights, outputs) with outputs a dict over {_OBJECTIVE_OUTPUTS}")
+    if p[2].get("gcoefs") is not None and not basis:
+        raise ValueError("objective_of: gcoefs needs basis beams (beam_coefs)")
+    if p[2].get(_GAIN_OUTPUT) is not None and (len(p) == 3 or p[3] is None):
+        raise ValueError("objective_of: ggains needs the gains (a fourth element)")
+
+
+def _check_gauss_newton(p, basis):
+    if (len(p) not in (3, 4) or not isinstance(p[0], dict) or not isinstance(p[2], dict)
+            or set(p[0]) - set(_GAUSS_NEWTON_DIRECTIONS) or set(p[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT}):
+        raise ValueError(f"gauss_newton_of: (directions, weights, outputs) with directions a dict over "
+                         f"{_GAUSS_NEWTON_DIRECTIONS} and outputs a dict over {_OBJECTIVE_OUTPUTS}")
+    gains = p[3] if len(p) == 4 else None
+    if gains is not None and (not isinstance(gains, tuple) or len(gains) != 2 or gains[0] is None):
+        raise ValueError("gauss_newton_of: the fourth element is (gains, d_gains), d_gains or None")
+    if p[2].get(_GAIN_OUTPUT) is not None and gains is None:
+        raise ValueError("gauss_newton_of: ggains needs the gains (a fourth element)")
+    if all(p[0].get(k) is None for k in _GAUSS_NEWTON_DIRECTIONS) and (gains is None or gains[1] is None):
+        raise ValueError("gauss_newton_of: no direction given")
+    if not basis and (p[0].get("d_beam_coefs") is not None or p[2].get("gcoefs") is not None):
+        raise ValueError("gauss_newton_of: d_beam_coefs and gcoefs need basis beams (beam_coefs)")
+
+
+def _position_outputs(outputs):
+    return any(outputs.get(k) is not None for k in ("gcoefs", "gbls", "gtopo"))
+
+
+def _prepare_forward(h, s, p):
+    t0, t1, f0, f1 = s.span
+    out = p[0]
+    if out is not None and (out.shape != h.out_shape(t1 - t0, f1 - f0) or out.dtype != s.cdt):
+        raise ValueError(f"out must be a {np.dtype(s.cdt).name} array of shape "
+                         f"{h.out_shape(t1 - t0, f1 - f0)}, got {out.dtype} {out.shape}")
+    return p
+
+
+def _set_gain_pairs(h, s, keyword, named_gains):
+    """The fit passes' gains: every block of ``named_gains`` -- (name, host array or None) -- checked against the run's
+    (nf, nt, nfeed, nant) layout, then the antenna pair of every baseline, as rows of ``ants``' order, told to the handle."""
+    t0, t1, f0, f1 = s.span
+    shape = (f1 - f0, t1 - t0, 2 if s.polarized else 1, s.nant)
+    for name, x in named_gains:
+        if x is not None and (not isinstance(x, np.ndarray) or x.dtype != s.cdt or x.shape != shape):
+            raise ValueError(f"{keyword}: {name} must be a {np.dtype(s.cdt).name} array of shape {shape}")
+    row = {a: i for i, a in enumerate(s.antnums)}  # (list.index per baseline is 0.2 s at HERA-350's 61 075)
+    nb = len(s.baselines)
+    h.set_gain_pairs(s.nant, np.fromiter((row[bl[0]] for bl in s.baselines), np.int32, count=nb),
+                     np.fromiter((row[bl[1]] for bl in s.baselines), np.int32, count=nb))
+
+
+def _prepare_objective(h, s, p):
+    """``objective_of`` as (data, weights, outputs, gains or None), the handle told the gain pairs."""
+    gains = p[3] if len(p) == 4 else None
+    if gains is not None:
+        _set_gain_pairs(h, s, "objective_of", [("gains", gains)])
+    return p[0], p[1], p[2], gains
+
+
+def _prepare_gauss_newton(h, s, p):
+    """``gauss_newton_of`` as (directions, weights, outputs, set_fluxes, (gains, d_gains) or None), the handle told the
+    gain pairs.  ``set_fluxes(tangent)`` (None without ``d_fluxes``) sets the catalog's fluxes: the direction's for the
+    forward part, else the real ones."""
+    directions, gains = p[0], p[3] if len(p) == 4 else None
+    set_fluxes = None
+    if directions.get("d_fluxes") is not None:
+        d_coherency, _ = utils.prepare_source_catalog(np.asarray(directions["d_fluxes"]), s.polarized)
+        if d_coherency.shape != s.coherency.shape:  # (the same shape: the same kind of sky)
+            raise ValueError(f"d_fluxes must have fluxes' shape, got {np.shape(directions['d_fluxes'])}")
+
+        def set_fluxes(tangent):
+            h.set_sources(s.eq, d_coherency if tangent else s.coherency, s.polarized_sky)
+    if gains is not None:
+        _set_gain_pairs(h, s, "gauss_newton_of", zip(("gains", "d_gains"), gains))
+    return directions, p[1], p[2], set_fluxes, gains
+
+
+def _prepare_forward_to(h, s, p):
+    # (the target holds the whole model: made before the time blocks are sized, so that a block's temporary fits next to it)
+    return _forward_target(h, s.device, p, s.span[1] - s.span[0], s.span[3] - s.span[2])
+
+
+class _Pass(typing.NamedTuple):
+    """What ``simulate`` has to know about one pass.  ``p`` is the pass's payload -- its mode keyword's value, or what
+    ``prepare`` made of it --, ``s`` the run (``_host_setup``'s record), ``h`` the configured handle."""
+
+    run: typing.Callable  # (h, s, p, nblk_t) -> the call's result: the pass's time loop
+    check: typing.Callable = None  # (p, basis): ValueError for a payload the pass does not take, before any set-up
+    needs_basis: bool = False  # refused without beam_coefs
+    host_catalog: bool = False  # refused with catalog_device
+    type3: typing.Callable = None  # (p) -> whether the pass, given its payload, runs the type-3 transform only ...
+    refusal: str = None  # ... and how its refusal of a lattice array begins
+    sets_adjoint_path: bool = False  # adjoint_path is told to the handle (no basis beams)
+    prepare: typing.Callable = None  # (h, s, p) -> p: the checks and the set-up of the payload that need the handle
+    blocks: typing.Callable = lambda p, s: 1  # (p, s) -> device blocks of the output's size a time step holds
+
+
+def _always(p):
+    return True
+
+
+_PASSES = {
+    "forward": _Pass(
+        run=lambda h, s, p, n: _run_forward(h, p[0], p[1], *s.span, n, s.coord_mgr), prepare=_prepare_forward),
+    "adjoint_of": _Pass(
+        run=lambda h, s, p, n: _run_adjoint(h, p[0], p[1], *s.span, n, s.coord_mgr, gcoefs=p[2] if s.use_basis else None,
+                                            basis=s.use_basis, gbls=p[3] if len(p) == 4 else None),
+        check=_check_adjoint, sets_adjoint_path=True),
+    "position_adjoint": _Pass(
+        run=lambda h, s, p, n: _run_adjoint(h, p[0], p[1], *s.span, n, s.coord_mgr, positions=True),
+        check=_no_basis_beams("position"), type3=_always, refusal="the position adjoint runs", sets_adjoint_path=True),
+    "source_adjoint": _Pass(
+        run=lambda h, s, p, n: _run_adjoint(h, p[0], p[1], *s.span, n, s.coord_mgr, sources=True),
+        check=_no_basis_beams("source"), type3=_always, refusal="the source adjoint runs", sets_adjoint_path=True),
+    "tangent_of": _Pass(
+        run=lambda h, s, p, n: _run_tangent(h, p[0], p[1], p[2], *s.span, n, s.coord_mgr, basis=s.use_basis),
+        check=_check_tangent, type3=_always, refusal="the tangent runs"),
+    "basis_tangent_of": _Pass(
+        run=lambda h, s, p, n: _run_basis_tangent(h, p[0], p[1], *s.span, n, s.coord_mgr), needs_basis=True,
+        blocks=lambda p, s: int(p[0].shape[0])),  # (the device holds every direction's copy of a time block)
+    "basis_source_of": _Pass(
+        run=lambda h, s, p, n: _run_basis_source(h, *p, *s.span, n, s.coord_mgr), check=_check_basis_source,
+        needs_basis=True),
+    "sky_of": _Pass(
+        run=lambda h, s, p, n: _run_sky_adjoint(h, *p, *s.span, n, s.coord_mgr, basis=s.use_basis), check=_check_sky,
+        type3=_always, refusal="the sky adjoint runs"),
+    # (a block's G, data and weights are on the device together: 2.5 blocks, 2 without weights; a block's gains and their
+    # gradient add (8 + 16) nfeed nant bytes per row to the 2.5 blocks of 8 tpol nbls: under 0.1 % once nbls >= nant)
+    "objective_of": _Pass(
+        run=lambda h, s, p, n: _run_objective(h, s.device, p[0], p[1], p[2], *s.span, n, s.coord_mgr, basis=s.use_basis,
+                                              gains=p[3]),
+        check=_check_objective, type3=lambda p: _position_outputs(p[2]), refusal="the objective's position passes run",
+        sets_adjoint_path=True, prepare=_prepare_objective, blocks=lambda p, s: 2.0 if p[1] is None else 2.5),
+    # (a block's parts and weights are on the device together: one block per part, half a block of weights, one more
+    # block when V is held; the gains, their direction and the product are under 0.1 % of one)
+    "gauss_newton_of": _Pass(
+        run=lambda h, s, p, n: _run_gauss_newton(h, s.device, p[0], p[1], p[2], p[3], *s.span, n, s.coord_mgr,
+                                                 basis=s.use_basis, gains=p[4]),
+        check=_check_gauss_newton, host_catalog=True,
+        type3=lambda p: (any(p[0].get(k) is not None for k in ("d_beam_coefs", "d_baselines", "d_topo"))
+                         or _position_outputs(p[2])),
+        refusal="the Gauss-Newton product's position passes run", sets_adjoint_path=True, prepare=_prepare_gauss_newton,
+        blocks=lambda p, s: (_gauss_newton_nparts(p[0], s.use_basis) + (0.0 if p[1] is None else 0.5)
+                             + (1.0 if _gauss_newton_holds_v(p[2], p[4]) else 0.0))),
+    "forward_to": _Pass(
+        run=lambda h, s, p, n: _run_forward_to(h, p, *s.span, n, s.coord_mgr), prepare=_prepare_forward_to),
+}
 
 
 def _time_block(device, nt, nf, nbls, polarized, precision, nsrc_topo=0):
