@@ -13,7 +13,8 @@ all three (``simulate_vis_jvp``), and the source positions through basis beams
 and the source positions' gradients from one pass (``simulate_vis_sky_adjoint``, ``simulate_vis_basis_sky_adjoint``), and
 the fit objective with its gradients from one call that keeps the visibilities on the device (``simulate_vis_chi2``,
 ``torch_simulate_vis_chi2``; ``simulate_vis_gain_chi2`` for uncalibrated data: per-antenna complex gains in the data model
-and their gradient), and the Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the tangent
+and their gradient; ``simulate_vis_jones_chi2`` for full 2 x 2 Jones matrices per antenna, leakage included), and the
+Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the tangent
 on the device (``simulate_vis_gauss_newton``; ``simulate_vis_gain_gauss_newton`` with the gains in the data model, a gain
 direction and the gain block of the product), and the gains themselves for a fixed model, solved on the device against
 a resident model (``simulate_vis_gain_solve``).
@@ -40,6 +41,7 @@ from .adjoint import (  # noqa: F401
     simulate_vis_gain_gauss_newton,
     simulate_vis_gain_solve,
     simulate_vis_gauss_newton,
+    simulate_vis_jones_chi2,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,
     simulate_vis_sky_adjoint,

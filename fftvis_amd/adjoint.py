@@ -28,6 +28,8 @@ run of the same handle (``fv_sim_run_residual``), and run the passes above on it
 from one call, one set-up, with the visibilities never copied to the host.  ``simulate_vis_gain_chi2`` is that
 call with ``gains=``: the data model is conj(g[a1]) g[a2] V, one complex gain per antenna, feed, channel and optionally time, applied on the device in the same
 block (``fv_sim_run_residual_gains``), and ``wrt="gains"`` gives the gradient with respect to them.
+``simulate_vis_jones_chi2`` takes a full 2 x 2 matrix per antenna instead -- the two gains and the leakage between the
+feeds -- with ``wrt="jones"`` (``fv_sim_run_residual_jones``).
 ``simulate_vis_gauss_newton`` is the Gauss-Newton product 2 J^T W J p of that chi2 from one call that keeps the tangent on
 the device (``fv_sim_weight_block``), and ``simulate_vis_gain_gauss_newton`` that product with the gains in the data model,
 a gain direction and the gain block of the product (``fv_sim_gain_weight_block``).  ``simulate_vis_gain_solve`` solves
@@ -1737,17 +1739,47 @@ def _gain_gradient(run: _Run, ggains: np.ndarray, shape) -> np.ndarray:
     return total.reshape(shape)
 
 
+def _jones_block(run: _Run, jones) -> np.ndarray:
+    """``simulate_vis_jones_chi2``'s ``jones`` -- (nant, 2, 2, nfreqs[, ntimes]) complex, rows in ``ants``' order -- checked
+    and broadcast to the block layout the engine takes: (nfreqs, ntimes, 2, 2, nant), C-contiguous, the run's complex dtype."""
+    j = _host(jones)
+    nant = len(run.ants)
+    shapes = ((nant, 2, 2, run.nfreqs), (nant, 2, 2, run.nfreqs, run.ntimes))
+    if not np.iscomplexobj(j):
+        raise ValueError("jones must be complex (one 2 x 2 matrix per antenna and channel)")
+    if j.shape not in shapes:
+        raise ValueError(f"jones must have shape {shapes[0]} or {shapes[1]}, got {j.shape}")
+    if not np.isfinite(j).all():
+        raise ValueError("jones must be finite")
+    j = np.broadcast_to(j.reshape(nant, 2, 2, run.nfreqs, -1), (nant, 2, 2, run.nfreqs, run.ntimes))
+    return np.ascontiguousarray(j.transpose(3, 4, 1, 2, 0), dtype=run.cdt)
+
+
+def _jones_gradient(run: _Run, gjones: np.ndarray, shape) -> np.ndarray:
+    """The engine's (nfreqs, ntimes, 2, 2, nant) gradient in the shape the matrices were given in; for time-constant
+    matrices the per-time gradients are added in time order."""
+    g = gjones.transpose(4, 2, 3, 0, 1)  # (nant, 2, 2, nfreqs, ntimes)
+    if len(shape) == g.ndim:  # per-time matrices
+        return np.ascontiguousarray(g)
+    total = np.zeros(g.shape[:-1], dtype=np.complex128)
+    for t in range(g.shape[-1]):
+        total += g[..., t]
+    return total
+
+
 # ---- what the fit entry points share: simulate_vis_gain_chi2, simulate_vis_gain_gauss_newton, simulate_vis_gain_solve ----
 
-def _fit_keywords(wrt, gains, per_name, per, adjoint_path, beam_coefs, polarized, d_beam_coefs=None):
-    """The keywords ``simulate_vis_gain_chi2`` and ``simulate_vis_gain_gauss_newton`` check alike, before the run is
-    described; ``per_name`` names the caller's ``chi2_per`` / ``quad_per``.  Returns ``wrt`` as (single, names)."""
+def _fit_keywords(wrt, gains, per_name, per, adjoint_path, beam_coefs, polarized, d_beam_coefs=None, kind="gains"):
+    """The keywords ``simulate_vis_gain_chi2``, ``simulate_vis_jones_chi2`` and ``simulate_vis_gain_gauss_newton`` check
+    alike, before the run is described; ``per_name`` names the caller's ``chi2_per`` / ``quad_per``, ``kind`` the keyword
+    ``gains`` came by and the name ``wrt`` has for it.  Returns ``wrt`` as (single, names)."""
     single = isinstance(wrt, str)
     names = (wrt,) if single else tuple(wrt)
     if names:
-        _parse_wrt(wrt, _CHI2_WRT, "some of 'fluxes', 'ants', 'baselines', 'topo', 'radec', 'beam_coefs' and 'gains'")
-    if "gains" in names and gains is None:
-        raise ValueError("wrt='gains' needs gains=")
+        _parse_wrt(wrt, _CHI2_WRT[:-1] + (kind,),
+                   f"some of 'fluxes', 'ants', 'baselines', 'topo', 'radec', 'beam_coefs' and '{kind}'")
+    if kind in names and gains is None:
+        raise ValueError(f"wrt='{kind}' needs {kind}=")
     if per not in ("total", "freq_time"):
         raise ValueError(f"{per_name} must be 'total' or 'freq_time', got {per!r}")
     if adjoint_path not in ("type3", "type2", "auto"):
@@ -1800,18 +1832,19 @@ def _gvis_buffer(run: _Run, return_gvis):
     return gvis
 
 
-def _fit_gradients(run: _Run, single, names, buffers, full_stokes, ggains, gains, like, device):
+def _fit_gradients(run: _Run, single, names, buffers, full_stokes, ggains, gains, like, device, kind="gains"):
     """What a fit call returns for ``wrt`` out of the engine's ``buffers`` (gflux, gcoefs, gbls, gtopo) and its gain block
-    ``ggains``: the gains' gradient in ``gains``' own shape, Stokes fluxes, the radec chain, the antenna fold.  The
-    outputs follow ``like`` (the tensor among the inputs, or None) and live on the torch ``device`` (None: the host)."""
+    ``ggains``: the gains' gradient in ``gains``' own shape (``kind="jones"``: the matrices'), Stokes fluxes, the radec
+    chain, the antenna fold.  The outputs follow ``like`` (the tensor among the inputs, or None) and live on the torch
+    ``device`` (None: the host)."""
     gflux, gcoefs, gbls, gtopo = buffers
     res = {"topo": gtopo, "baselines": gbls, "beam_coefs": gcoefs}
-    if "gains" in names:
-        res["gains"] = _gain_gradient(run, ggains, tuple(gains.shape))
+    if kind in names:
+        res[kind] = (_jones_gradient if kind == "jones" else _gain_gradient)(run, ggains, tuple(gains.shape))
         if device is not None:
             import torch
 
-            res["gains"] = torch.from_numpy(res["gains"]).to(device)
+            res[kind] = torch.from_numpy(res[kind]).to(device)
     if "fluxes" in names:
         res["fluxes"] = stokes_adjoint(gflux, full_stokes)
     if "radec" in names:
@@ -1999,18 +2032,30 @@ def simulate_vis_gain_chi2(
 
     The Gauss-Newton product of this chi2 is ``simulate_vis_gain_gauss_newton``'s (``simulate_vis_gauss_newton`` itself
     takes no gains), and the gains that minimise it for a fixed model are ``simulate_vis_gain_solve``'s.  Not covered:
-    gains in ``simulate_vis`` itself, ``model=`` in this call, full 2x2 Jones (leakage) gains, sharding over GPUs."""
-    args = locals()
-    single, names = _fit_keywords(wrt, gains, "chi2_per", chi2_per, adjoint_path, beam_coefs, polarized)
+    gains in ``simulate_vis`` itself, ``model=`` in this call, sharding over GPUs.  Full 2x2 Jones (leakage) matrices per
+    antenna are ``simulate_vis_jones_chi2``'s."""
+    return _gain_chi2(locals(), "gains")
+
+
+def _gain_chi2(args: dict, kind: str):
+    """``simulate_vis_gain_chi2`` (``kind="gains"``) and ``simulate_vis_jones_chi2`` (``kind="jones"``): ``args`` is the
+    public function's ``locals()``, ``args[kind]`` its gains or matrices (None: neither, ``simulate_vis_chi2``).  The two
+    differ in the block the engine's objective pass is given, in the output that receives its gradient and in the name
+    ``wrt`` has for it."""
+    gains, data, weights, return_gvis = args[kind], args["data"], args["weights"], args["return_gvis"]
+    single, names = _fit_keywords(args["wrt"], gains, "chi2_per", args["chi2_per"], args["adjoint_path"], args["beam_coefs"],
+                                  args["polarized"], kind=kind)
+    if kind == "jones" and not args["polarized"]:
+        raise ValueError("jones needs polarized=True: a 2 x 2 matrix per antenna mixes the two feeds")
     run = _describe_run(args)
     run = _own_radec_chain(run, "wrt='radec'", "radec" in names, "ask for wrt='topo' and apply its Jacobian",
                            "ask for wrt='topo'")
-    fluxes, full_stokes = _sky_full_stokes(run, fluxes, full_stokes)
+    fluxes, full_stokes = _sky_full_stokes(run, args["fluxes"], args["full_stokes"])
     _check_vis_block(run, data, "data")
     if weights is not None:
         _check_weights(run, weights, "data's")
-    gain_block = None if gains is None else _gain_block(run, gains)
-    ggains = np.zeros(gain_block.shape, dtype=np.complex128) if "gains" in names else None
+    gain_block = None if gains is None else (_jones_block if kind == "jones" else _gain_block)(run, gains)
+    ggains = np.zeros(gain_block.shape, dtype=np.complex128) if kind in names else None
     d, buffers, on_device = _gradient_buffers(run, data, _fit_outputs(run, names, full_stokes))
     w = None
     if weights is not None:
@@ -2019,13 +2064,98 @@ def simulate_vis_gain_chi2(
         _synchronize(w_device)
     gvis = _gvis_buffer(run, return_gvis)
     outputs = dict(zip(("gflux", "gcoefs", "gbls", "gtopo"), buffers), gvis=gvis)
+    if gains is None:
+        objective_of = (d, w, outputs)
+    elif kind == "jones":
+        objective_of = (d, w, dict(outputs, gjones=ggains), ("jones", gain_block))
+    else:
+        objective_of = (d, w, dict(outputs, ggains=ggains), gain_block)
     chi2_ft = _engine_simulate(
-        run, fluxes, force_use_type3=None if set(names) <= {"fluxes"} else True, adjoint_path=adjoint_path,
-        objective_of=(d, w, outputs) if gains is None else (d, w, dict(outputs, ggains=ggains), gain_block))
+        run, fluxes, force_use_type3=None if set(names) <= {"fluxes"} else True, adjoint_path=args["adjoint_path"],
+        objective_of=objective_of)
     like, dev = data if _is_tensor(data) else None, data.device if on_device else None
-    grads = _fit_gradients(run, single, names, buffers, full_stokes, ggains, gains, like, dev)
-    chi2 =_fit_value(chi2_ft, chi2_per, like, dev)
+    grads = _fit_gradients(run, single, names, buffers, full_stokes, ggains, gains, like, dev, kind=kind)
+    chi2 = _fit_value(chi2_ft, args["chi2_per"], like, dev)
     return (chi2, grads, _gvis_home(gvis, like, dev)) if return_gvis else (chi2, grads)
+
+
+def simulate_vis_jones_chi2(
+    data,
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    jones,
+    weights=None,
+    wrt=("fluxes",),
+    beam_coefs=None,
+    chi2_per: str = "total",
+    return_gvis: bool = False,
+    adjoint_path: str = "type3",
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """``simulate_vis_chi2`` with one 2 x 2 complex matrix per antenna, channel and optionally time in the data model: the
+    gains of the two feeds on its diagonal and the leakage of each feed into the other (D-terms) off it.  Antenna ``a``'s
+    Jones matrix ``A_a[ax, feed]`` becomes ``A_a jones[a]``, so that on the polarized output ``[f, t, x, y, k]`` of baseline
+    ``k = (a1, a2)``
+
+        ``V'[x, y] = sum_{x', y'} conj(jones[a1][y', y]) jones[a2][x', x] V[x', y']``,
+
+    ``chi2 = sum w |V' - data|^2``, and ``"jones"`` is one more name ``wrt`` takes.  The product is applied on the device to
+    the block the residual kernel touches (``fv_sim_run_residual_jones``), whatever path produced V; everything else --
+    ``data``, ``weights``, the other names of ``wrt``, ``chi2_per``, ``adjoint_path``, ``force_use_type3``, the returned
+    tuple -- is ``simulate_vis_chi2``'s.  ``jones[a] = diag(gains[a])`` is ``simulate_vis_gain_chi2``.
+
+    * Needs ``polarized=True`` (ValueError otherwise).
+    * ``jones``: ``(nant, 2, 2, nfreqs)`` or per time ``(nant, 2, 2, nfreqs, ntimes)``; ``jones[a, i, j]`` has ``i`` the feed
+      of the ideal antenna and ``j`` the measured feed.  Rows follow ``ants``' iteration order.  Complex, finite; numpy or a
+      tensor on any device (it is small and goes through the host).
+    * ``"jones"`` in ``wrt`` gives the gradient in ``jones``' own shape, complex128, in torch's convention for a complex
+      leaf, ``d chi2 = Re sum conj(grad) d jones`` (the convention of the ``gains`` and ``beam_coefs`` gradients), following
+      ``data`` as the other gradients do; for time-constant matrices it is the per-time gradients added on the host in time
+      order.  Every other gradient is its public pass's result for ``vis = G``.
+    * ``return_gvis=True`` gives that ``G = d chi2 / dV``, the transposed product applied to ``2 w (V' - data)`` -- NOT
+      ``2 w (V' - data)`` itself.
+    * A weight of 0 flags that one ``(x, y)`` sample; the baseline's other samples still use all four model values.
+    * With the default ``baselines=None`` there is one baseline per redundant group and the matrices applied are those of
+      each group's representative pair: a calibration passes explicit ``baselines``.
+    * The device holds one more fp64 value per visibility of a time block (the rows' terms of chi2), which the time
+      blocks are sized for.
+
+    Not covered: Jones matrices in the Gauss-Newton product or the gain solve, ``model=`` in this call, sharding over
+    GPUs."""
+    return _gain_chi2(locals(), "jones")
 
 
 def _chi2_autograd_function():
@@ -2034,13 +2164,13 @@ def _chi2_autograd_function():
 
     class _SimulateVisChi2(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, fluxes, beam_coefs, antpos, radec, gains, data, weights, antnums, kwargs):
-            inputs = (("fluxes", fluxes), ("beam_coefs", beam_coefs), ("ants", antpos), ("radec", radec), ("gains", gains))
+        def forward(ctx, fluxes, beam_coefs, antpos, radec, gains, data, weights, antnums, kwargs, kind):
+            inputs = (("fluxes", fluxes), ("beam_coefs", beam_coefs), ("ants", antpos), ("radec", radec), (kind, gains))
             wrt = tuple(n for (n, _), need in zip(inputs, ctx.needs_input_grad[:5]) if need)
             kw = dict(kwargs)
             call = simulate_vis_chi2
             if gains is not None:
-                call, kw["gains"] = simulate_vis_gain_chi2, gains
+                call, kw[kind] = (simulate_vis_jones_chi2 if kind == "jones" else simulate_vis_gain_chi2), gains
             if antpos is not None:
                 kw["ants"] = _ants_of(antnums, antpos)
             if radec is not None:
@@ -2054,7 +2184,7 @@ def _chi2_autograd_function():
         @once_differentiable
         def backward(ctx, grad_output):
             return tuple(None if g is None else g * grad_output.to(device=g.device, dtype=g.real.dtype)
-                         for g in ctx.grads) + (None,) * 4
+                         for g in ctx.grads) + (None,) * 5
 
     return _SimulateVisChi2
 
@@ -2070,7 +2200,9 @@ def torch_simulate_vis_chi2(data, fluxes, *, weights=None, beam_coefs=None, antp
     gradient, keeping the gradients; the backward pass multiplies them by the incoming scalar (once differentiable).
     ``gains=`` (``simulate_vis_gain_chi2``'s per-antenna gains, whose call the forward then makes) may be a complex tensor on any device: one that requires a
     gradient adds ``"gains"`` to that one call and receives its ``.grad`` in its own dtype and on its own device; a
-    constant tensor or an array is passed through.  Not covered: forward-mode differentiation, double backward."""
+    constant tensor or an array is passed through.  ``jones=`` (``simulate_vis_jones_chi2``'s 2 x 2 matrices per antenna)
+    is taken the same way, with ``"jones"`` in place of ``"gains"``; ``gains=`` and ``jones=`` together are a TypeError.  Not
+    covered: forward-mode differentiation, double backward."""
     for taken, by in (("wrt", "what requires a gradient"), ("chi2_per", "the scalar loss"), ("return_gvis", "the scalar loss")):
         if taken in kwargs:
             raise TypeError(f"torch_simulate_vis_chi2 does not take {taken}=: {by} decides")
@@ -2084,8 +2216,12 @@ def torch_simulate_vis_chi2(data, fluxes, *, weights=None, beam_coefs=None, antp
         if radec.ndim != 2 or radec.shape[1] != 2 or radec.is_complex():
             raise ValueError(f"radec must be a real (nsrc, 2) tensor, got {tuple(radec.shape)} {radec.dtype}")
     kwargs = dict(kwargs)
-    gains = kwargs.pop("gains", None)
-    return _function(_chi2_autograd_function).apply(fluxes, beam_coefs, antpos, radec, gains, data, weights, antnums, kwargs)
+    gains, jones = kwargs.pop("gains", None), kwargs.pop("jones", None)
+    if gains is not None and jones is not None:
+        raise TypeError("torch_simulate_vis_chi2 takes gains= or jones=, not both (diagonal matrices are the gains)")
+    kind = "gains" if jones is None else "jones"
+    return _function(_chi2_autograd_function).apply(fluxes, beam_coefs, antpos, radec, gains if jones is None else jones,
+                                                    data, weights, antnums, kwargs, kind)
 
 
 _GAUSS_NEWTON_NAMES = (("d_ants", "ants"), ("d_baselines", "baselines"), ("d_radec", "radec"), ("d_topo", "topo"),

@@ -324,9 +324,9 @@ static void coherency_host(int device, int variant, int64_t n, const void *bi, c
     FV_HIP(hipGetLastError());
 }
 
-// The row passes on host arrays (fv_residual_chi2, fv_gain_residual_chi2, fv_weight_rows, fv_gain_weight_rows): every
-// array is copied into a buffer of its own on the call's stream (null stays null), the launcher queues the kernels, what
-// was computed in place is copied back and collect_rows ends the call.
+// The row passes on host arrays (fv_residual_chi2, fv_gain_residual_chi2, fv_jones_residual_chi2, fv_weight_rows,
+// fv_gain_weight_rows): every array is copied into a buffer of its own on the call's stream (null stays null), the launcher
+// queues the kernels, what was computed in place is copied back and collect_rows ends the call.
 template <typename X>
 static X *to_device(hipStream_t s, DevBuf &buf, const void *host, size_t n) {
     if (!host) return nullptr;
@@ -384,6 +384,37 @@ static void gain_residual_chi2_host(int device, int64_t nrows, int64_t nbls, int
                        {&gp, to_device<cplx<T>>(sg.s, dgn, gains, ng), nullptr, dgg.as<cplx<double>>()});
     FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
     if (ggains) FV_HIP(hipMemcpyAsync(ggains, dgg.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
+    int hbad[2];
+    collect_rows(sg.s, rs, nrows, chi2_rows, hbad);
+    throw_if_bad_residual_input(hbad);
+}
+
+template <typename T>
+static void jones_residual_chi2_host(int device, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                                     const void *jones, void *vis, const void *data, const void *weights, double *chi2_rows,
+                                     void *gjones) {
+    const size_t nj = (size_t)nrows * 4 * (size_t)nant;
+    if (nrows == 0) return;
+    if (nbls == 0) {
+        for (int64_t i = 0; i < nrows; ++i) chi2_rows[i] = 0.0;
+        if (gjones) std::memset(gjones, 0, sizeof(cplx<double>) * nj);
+        return;
+    }
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const int64_t row_len = 4 * nbls;
+    const size_t n = (size_t)nrows * (size_t)row_len;
+    GainPairs gp;
+    gp.set(sg.s, nant, nbls, ant1, ant2);
+    DevBuf dv, dd, dw, ds, djn, dgj, dt;
+    if (gjones) dgj.reserve(sizeof(cplx<double>) * nj);
+    dt.reserve(sizeof(double) * n);
+    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
+    launch_jones_residual<T>(sg.s, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<cplx<T>>(sg.s, dd, data, n),
+                             to_device<T>(sg.s, dw, weights, n), nrows, rs,
+                             {&gp, to_device<cplx<T>>(sg.s, djn, jones, nj), dgj.as<cplx<double>>(), dt.as<double>()});
+    FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    if (gjones) FV_HIP(hipMemcpyAsync(gjones, dgj.p, sizeof(cplx<double>) * nj, hipMemcpyDeviceToHost, sg.s));
     int hbad[2];
     collect_rows(sg.s, rs, nrows, chi2_rows, hbad);
     throw_if_bad_residual_input(hbad);
@@ -734,6 +765,26 @@ int fv_gain_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls
     });
 }
 
+int fv_jones_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                           const void *jones, void *vis, const void *data, const void *weights, double *chi2_rows,
+                           void *gjones) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_jones_residual_chi2: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_jones_residual_chi2: nant must be positive");
+        FV_REQUIRE(jones || nrows == 0, "fv_jones_residual_chi2: null jones");
+        FV_REQUIRE((nrows == 0 || nbls == 0 || (vis && data && ant1 && ant2)) && (nrows == 0 || chi2_rows),
+                   "fv_jones_residual_chi2: null pairs, vis, data or chi2_rows");
+        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
+            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                       "fv_jones_residual_chi2: antenna index outside [0, nant)");
+        if (precision == 2)
+            jones_residual_chi2_host<double>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, chi2_rows, gjones);
+        else
+            jones_residual_chi2_host<float>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, chi2_rows, gjones);
+    });
+}
+
 int fv_gain_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
                         const int *ant2, const void *gains, const void *vis, const void *data, const void *weights, void *num,
                         double *den) {
@@ -970,6 +1021,20 @@ int fv_sim_run_residual_gains(fv_sim *h, int t0, int t1, int f0, int f1, const v
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_residual_gains(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, gains, gains_on_device, gvis,
                                     gvis_on_device, chi2_ft, ggains, ggains_on_device);
+    });
+}
+int fv_sim_run_residual_jones(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                              int weights_on_device, const void *jones, int jones_on_device, void *gvis, int gvis_on_device,
+                              double *chi2_ft, void *gjones, int gjones_on_device) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(data && jones && gvis && chi2_ft, "null data, jones, gvis or chi2_ft");
+        FV_REQUIRE((data_on_device == 0 || data_on_device == 1) && (weights_on_device == 0 || weights_on_device == 1) &&
+                       (jones_on_device == 0 || jones_on_device == 1) && (gvis_on_device == 0 || gvis_on_device == 1) &&
+                       (gjones_on_device == 0 || gjones_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->run_residual_jones(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, jones, jones_on_device, gvis,
+                                    gvis_on_device, chi2_ft, gjones, gjones_on_device);
     });
 }
 int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,

@@ -1937,6 +1937,289 @@ struct GainPairs {
 };
 
 // ---------------------------------------------------------------------------------------------
+// Jones gains (fv_jones_residual_chi2, fv_sim_run_residual_jones; DESIGN.md "Jones gains"): one 2 x 2 complex matrix per
+// antenna in the data model of a polarized block.  The block, the pairs and the incidence lists are the gain kernels'
+// above, tpol = 4: value pol nbls + k of a row is V[x, y] of baseline k = (a1, a2), pol = 2 x + y, y the feed of a1 (the
+// conjugated antenna) and x of a2.  A row's matrices are 4 nant complex values of the run's precision,
+// J[(2 i + j) nant + a] = Gamma_a[i, j], i the feed of the ideal antenna and j the measured one: antenna a's Jones matrix
+// A_a[ax, feed] becomes A_a Gamma_a, and diagonal gains are Gamma_a = diag(g[a]).  With G1 = Gamma[a1], G2 = Gamma[a2],
+//     V'[x, y]  = sum_{x', y'} conj(G1[y', y]) G2[x', x] V[x', y'],   delta = V' - d,   G'[x, y] = 2 w[x, y] delta[x, y],
+//     G[x', y'] = sum_{x, y} conj(G2[x', x]) G'[x, y] G1[y', y]  (= d chi2 / dV),   row sum += w |delta|^2,
+//     gjones[a, y', y] += sum_x conj(G'[x, y]) (G2^T V)[x, y']   for every k with a1[k] = a  (side 0),
+//     gjones[a, x', x] += sum_y G'[x, y] conj((V conj G1)[x', y])  for every k with a2[k] = a  (side 1),
+// d chi2 = Re sum conj(gjones) dGamma.  w == 0 flags that one (x, y) sample: G' = 0 exactly there, the datum is not used
+// (a select), nothing is added to chi2 or gjones, and the baseline's other samples still use all four model values; a
+// baseline with all four samples flagged stores G = 0 exactly.
+//   Three kernels, no floating-point atomics.  k_jones_gradient runs first, while the block still holds V.
+// k_jones_residual_rows follows, in place; the unit of its work is a baseline, whose four values are coupled: a thread takes
+// a run of consecutive baselines in all four planes, as many as one 16-byte vector of a plane holds -- one in fp64, where
+// every value is such a vector wherever the row starts, two in fp32 when every array is 16-byte aligned and nbls is even,
+// so that the four planes are aligned alike in the block's own index; else, and for the clipped runs at a row's ends,
+// baseline by baseline.  Consecutive lanes take consecutive runs: every access is coalesced.  A block takes
+// RES_CHUNKS * 256 * RES_W<T> baselines.  The row's matrices are staged in dynamic LDS when they fit GAIN_LDS_BYTES.  In T every
+// operation rounds on its own (no contraction), in this order, every sum of two products left to right:
+//     B[x', y]  = V[x', 0] conj(G1[0, y]) + V[x', 1] conj(G1[1, y]),      V'[x, y]  = G2[0, x] B[0, y] + G2[1, x] B[1, y],
+//     delta = V' - d,   G' = 2 (w delta),
+//     C[x', y]  = conj(G2[x', 0]) G'[0, y] + conj(G2[x', 1]) G'[1, y],    G[x', y'] = C[x', 0] G1[y', 0] + C[x', 1] G1[y', 1],
+// a complex product as (ar br - ai bi, ar bi + ai br) and a conj(b) as (ar br + ai bi, ai br - ar bi).  With identity
+// matrices B = V' = V and G = G' exactly: k_residual_rows<T, false>'s bits.  A thread's baselines are not the row walk's
+// chunks, so the row terms (row_term, 0 for a flagged sample) go to `terms`, an fp64 block in the block's own index, and
+// k_jones_rows_sum adds them exactly as k_residual_rows adds its own -- per thread in chunk order, row_tail, then
+// k_chi2_rows_reduce -- which makes chi2 the plain kernel's bit for bit whenever delta is.
+template <typename T>
+__device__ __forceinline__ cplx<T> jones_mul(const cplx<T> &a, const cplx<T> &b) {  // a b
+#pragma clang fp contract(off)
+    return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
+}
+template <typename T>
+__device__ __forceinline__ cplx<T> jones_mulc(const cplx<T> &a, const cplx<T> &b) {  // a conj(b)
+#pragma clang fp contract(off)
+    return {a.re * b.re + a.im * b.im, a.im * b.re - a.re * b.im};
+}
+template <typename T>
+__device__ __forceinline__ cplx<T> jones_add(const cplx<T> &a, const cplx<T> &b) {
+#pragma clang fp contract(off)
+    return {a.re + b.re, a.im + b.im};
+}
+// One baseline (a1, a2) in place: v[2 x + y] = V -> G, the row terms of its four samples, the counts of bad input.  J: the
+// row's matrices (staged or global), entry [2 i + j] of antenna a at J[(2 i + j) nant + a].
+template <typename T>
+__device__ __forceinline__ void jones_residual_baseline(cplx<T> (&v)[4], const cplx<T> (&d)[4], const T (&w)[4],
+                                                        const cplx<T> *J, int nant, int a1, int a2, double (&term)[4],
+                                                        int &bad_w, int &bad_d) {
+#pragma clang fp contract(off)
+    const cplx<T> g1[4] = {J[a1], J[nant + a1], J[2 * nant + a1], J[3 * nant + a1]};
+    const cplx<T> g2[4] = {J[a2], J[nant + a2], J[2 * nant + a2], J[3 * nant + a2]};
+    cplx<T> b[4], gp[4];  // B[x', y] at [2 x' + y], G'[x, y] at [2 x + y]
+#pragma unroll
+    for (int xs = 0; xs < 2; ++xs)
+#pragma unroll
+        for (int y = 0; y < 2; ++y)
+            b[2 * xs + y] = jones_add(jones_mulc(v[2 * xs], g1[y]), jones_mulc(v[2 * xs + 1], g1[2 + y]));
+    bool any = false;
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+            const int s = 2 * x + y;
+            const cplx<T> vp = jones_add(jones_mul(g2[x], b[y]), jones_mul(g2[2 + x], b[2 + y]));
+            if (!(w[s] >= (T)0) || !isfinite(w[s])) ++bad_w;
+            if (w[s] > (T)0) {
+                if (!isfinite(d[s].re) || !isfinite(d[s].im)) ++bad_d;
+                const T dr = vp.re - d[s].re, di = vp.im - d[s].im;
+                gp[s] = {(T)2 * (w[s] * dr), (T)2 * (w[s] * di)};
+                term[s] = row_term<T>(w[s], dr, di);
+                any = true;
+            } else {  // flagged (or counted above)
+                gp[s] = {(T)0, (T)0};
+                term[s] = 0.0;
+            }
+        }
+#pragma unroll
+    for (int xs = 0; xs < 2; ++xs) {
+        // C[x', y] = conj(G2[x', 0]) G'[0, y] + conj(G2[x', 1]) G'[1, y]
+        const cplx<T> c0 = jones_add(jones_mulc(gp[0], g2[2 * xs]), jones_mulc(gp[2], g2[2 * xs + 1]));
+        const cplx<T> c1 = jones_add(jones_mulc(gp[1], g2[2 * xs]), jones_mulc(gp[3], g2[2 * xs + 1]));
+#pragma unroll
+        for (int ys = 0; ys < 2; ++ys) {
+            const cplx<T> g = jones_add(jones_mul(c0, g1[2 * ys]), jones_mul(c1, g1[2 * ys + 1]));
+            v[2 * xs + ys] = any ? g : cplx<T>{(T)0, (T)0};  // (every sample flagged: exactly 0 whatever the matrices hold)
+        }
+    }
+}
+// One baseline of a row: its four values at e, e + nbls, ... of the block's index.
+template <typename T>
+__device__ __forceinline__ void jones_residual_at(int64_t e, int nbls, int a1, int a2, const cplx<T> *J, int nant,
+                                                  cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data,
+                                                  const T *__restrict__ weights, double *__restrict__ terms, int &bad_w,
+                                                  int &bad_d) {
+    cplx<T> v[4], d[4];
+    T w[4];
+    double term[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        v[p] = vis[e + (int64_t)p * nbls];
+        d[p] = data[e + (int64_t)p * nbls];
+        w[p] = weights ? weights[e + (int64_t)p * nbls] : (T)1;
+    }
+    jones_residual_baseline<T>(v, d, w, J, nant, a1, a2, term, bad_w, bad_d);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        vis[e + (int64_t)p * nbls] = v[p];
+        terms[e + (int64_t)p * nbls] = term[p];
+    }
+}
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_jones_residual_rows(cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
+                          const cplx<T> *__restrict__ jones, const int *__restrict__ ant1, const int *__restrict__ ant2,
+                          int64_t nrows, int nbls, int nant, int in_lds, int vec, double *__restrict__ terms,
+                          int *__restrict__ bad) {
+    constexpr int W = RES_W<T>;
+    constexpr int R = 16 / (int)sizeof(cplx<T>);  // the baselines of one 16-byte vector of a plane: 1 (fp64) or 2 (fp32)
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    const int nj = 4 * nant;
+    const int64_t L = 4 * (int64_t)nbls;
+    // runs of R baselines, when the four planes of a run are aligned alike; else -- and always in fp64, where a value is a
+    // 16-byte vector -- one baseline at a time.  Consecutive lanes take consecutive runs.
+    const bool runs = R > 1 && vec && nbls % R == 0;
+    const int step = runs ? R : 1, nit = RES_CHUNKS * W / step;
+    int bad_w = 0, bad_d = 0;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<T> *J = jones + row * nj;
+        if (in_lds) {
+            cplx<T> *jl = reinterpret_cast<cplx<T> *>(gain_lds);
+            for (int i = threadIdx.x; i < nj; i += 256) jl[i] = J[i];
+            J = jl;
+            __syncthreads();
+        }
+        const int64_t lo = row * L;
+        const int shift = runs ? (int)(lo % R) : 0;  // run r holds the baselines [r R - shift, r R - shift + R)
+        const int64_t kblock = (int64_t)blockIdx.x * (RES_CHUNKS * 256 * W) - shift;
+        for (int i = 0; i < nit; ++i) {
+            const int64_t k0 = kblock + ((int64_t)i * 256 + threadIdx.x) * step;
+            if (k0 >= nbls) break;
+            if constexpr (R > 1) {
+                if (runs && k0 >= 0 && k0 + R <= nbls) {
+                    union {
+                        uint4 q;
+                        cplx<T> c[R];
+                    } v[4], d[4];
+                    T w[4][R];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const int64_t e = lo + (int64_t)p * nbls + k0;
+                        v[p].q = *reinterpret_cast<const uint4 *>(vis + e);
+                        d[p].q = *reinterpret_cast<const uint4 *>(data + e);
+#pragma unroll
+                        for (int j = 0; j < R; ++j) w[p][j] = weights ? weights[e + j] : (T)1;
+                    }
+#pragma unroll
+                    for (int j = 0; j < R; ++j) {
+                        cplx<T> vv[4] = {v[0].c[j], v[1].c[j], v[2].c[j], v[3].c[j]};
+                        const cplx<T> dd[4] = {d[0].c[j], d[1].c[j], d[2].c[j], d[3].c[j]};
+                        const T w4[4] = {w[0][j], w[1][j], w[2][j], w[3][j]};
+                        double term[4];
+                        jones_residual_baseline<T>(vv, dd, w4, J, nant, ant1[k0 + j], ant2[k0 + j], term, bad_w, bad_d);
+#pragma unroll
+                        for (int p = 0; p < 4; ++p) {
+                            v[p].c[j] = vv[p];
+                            terms[lo + (int64_t)p * nbls + k0 + j] = term[p];
+                        }
+                    }
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) *reinterpret_cast<uint4 *>(vis + lo + (int64_t)p * nbls + k0) = v[p].q;
+                    continue;
+                }
+            }
+            const int64_t kb = k0 + step < nbls ? k0 + step : nbls;
+            for (int64_t k = k0 > 0 ? k0 : 0; k < kb; ++k)
+                jones_residual_at<T>(lo + k, nbls, ant1[k], ant2[k], J, nant, vis, data, weights, terms, bad_w, bad_d);
+        }
+        if (in_lds) __syncthreads();  // (the next row of this block stages its matrices again)
+    }
+    if (bad_w) atomicAdd(bad, bad_w);
+    if (bad_d) atomicAdd(bad + 1, bad_d);
+}
+// The rows' sums of k_jones_residual_rows' terms, added as k_residual_rows adds its own: the row walk's chunks, per thread
+// in chunk order, then row_tail.  partials[row][block] as there.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_jones_rows_sum(const double *__restrict__ terms, int64_t nrows, int64_t L, double *__restrict__ partials,
+                     int *__restrict__ bad) {
+    constexpr int W = RES_W<T>;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const int64_t lo = row * L, hi = lo + L, c0 = lo / W;
+        double s = 0.0;
+        for (int i = 0; i < RES_CHUNKS; ++i) {
+            const RowChunk c = row_chunk<T>(c0, lo, hi, i, 0);
+            if (c.e0 >= hi) break;
+            for (int64_t e = c.a; e < c.b; ++e) s += terms[e];
+        }
+        row_tail(s, 0, 0, row, partials, bad);
+    }
+}
+// gjones[((row 2 + i) 2 + j) nant + a]: one wave per (row, antenna), all four entries of the antenna's matrix in fp64 (8
+// doubles per lane), so each incident baseline's four samples are read once per side.  Lane l takes the entries l, l + 64,
+// ... of the antenna's incidence list in order; everything is formed in fp64 from the T-typed inputs; an __shfl_xor tree;
+// an antenna without a baseline gets exactly 0.  vis still holds V.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_jones_gradient(const cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
+                     const cplx<T> *__restrict__ jones, const int *__restrict__ ant1, const int *__restrict__ ant2,
+                     const int *__restrict__ inc_off, const int *__restrict__ inc, int64_t nrows, int nbls, int nant,
+                     cplx<double> *__restrict__ gjones) {
+    const int ant = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (ant >= nant) return;  // (whole waves: the tree below stays inside one)
+    const int i0 = inc_off[ant], i1 = inc_off[ant + 1];
+    const int64_t L = 4 * (int64_t)nbls;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<T> *J = jones + row * 4 * nant;
+        cplx<double> acc[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+        for (int i = i0 + lane; i < i1; i += 64) {
+            const int k = inc[i] >> 1, side = inc[i] & 1;
+            const int a1 = ant1[k], a2 = ant2[k];
+            const int64_t e = row * L + k;
+            cplx<double> v[4], g1[4], g2[4], m[4], gp[4];
+            double w2[4];
+            bool any = false;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const T wt = weights ? weights[e + (int64_t)p * nbls] : (T)1;
+                w2[p] = wt > (T)0 ? 2.0 * (double)wt : 0.0;
+                any = any || wt > (T)0;
+            }
+            if (!any) continue;  // every sample flagged: nothing is added, nothing more is read
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                v[p] = {(double)vis[e + (int64_t)p * nbls].re, (double)vis[e + (int64_t)p * nbls].im};
+                g1[p] = {(double)J[p * nant + a1].re, (double)J[p * nant + a1].im};
+                g2[p] = {(double)J[p * nant + a2].re, (double)J[p * nant + a2].im};
+            }
+            // side 0: M[x, y'] = (G2^T V)[x, y'] at [2 x + y'], V'[x, y] = sum_y' M[x, y'] conj(G1[y', y]);
+            // side 1: M[x', y] = (V conj G1)[x', y] at [2 x' + y], V'[x, y] = sum_x' G2[x', x] M[x', y]
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+                    m[2 * r + c] = side ? cadd(cmul(v[2 * r], cconj(g1[c])), cmul(v[2 * r + 1], cconj(g1[2 + c])))
+                                        : cadd(cmul(g2[r], v[c]), cmul(g2[2 + r], v[2 + c]));
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y) {
+                    const int s = 2 * x + y;
+                    gp[s] = {0.0, 0.0};
+                    if (w2[s] > 0.0) {  // (a flagged datum is not read)
+                        const cplx<double> vp = side ? cadd(cmul(g2[x], m[y]), cmul(g2[2 + x], m[2 + y]))
+                                                     : cadd(cmul(m[2 * x], cconj(g1[y])), cmul(m[2 * x + 1], cconj(g1[2 + y])));
+                        gp[s] = {w2[s] * (vp.re - (double)data[e + (int64_t)s * nbls].re),
+                                 w2[s] * (vp.im - (double)data[e + (int64_t)s * nbls].im)};
+                    }
+                }
+            // side 0: acc[y', y] += sum_x conj(G'[x, y]) M[x, y'];  side 1: acc[x', x] += sum_y G'[x, y] conj(M[x', y])
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const cplx<double> t = side ? cadd(cmul(gp[2 * c], cconj(m[2 * r])), cmul(gp[2 * c + 1], cconj(m[2 * r + 1])))
+                                                : cadd(cmul(cconj(gp[c]), m[r]), cmul(cconj(gp[2 + c]), m[2 + r]));
+                    acc[2 * r + c].re += t.re;
+                    acc[2 * r + c].im += t.im;
+                }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            for (int off = 32; off > 0; off >>= 1) {
+                acc[s].re += __shfl_xor(acc[s].re, off, 64);
+                acc[s].im += __shfl_xor(acc[s].im, off, 64);
+            }
+            if (lane == 0) gjones[(row * 4 + s) * nant + ant] = acc[s];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Gain solve on a resident model (fv_gain_normal_rows, fv_gain_solve; DESIGN.md "Gain solve").  The block, the pairs, the
 // feeds and the incidence lists are the gain kernels' above; V, d and w are read only.  The iterate is complex128
 // whatever T is: (nunits, nfeed nant), row `row` reads unit row / rows_per_unit (a unit is a frequency for time-constant
@@ -2239,6 +2522,43 @@ inline void launch_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *data, c
     else
         FV_ROWS(false);
 #undef FV_ROWS
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)rs.partials, nrows,
+                       rs.nblk, rs.sums);
+}
+// The matrices of a row pass with Jones gains, all device pointers: the pairs, the rows' matrices (nrows, 2, 2, nant), where
+// the gradient goes ((nrows, 2, 2, nant) complex128; null: the gather does not run) and the rows' terms (nrows, 4 nbls) fp64.
+template <typename T>
+struct RowJones {
+    const GainPairs *pairs = nullptr;
+    const cplx<T> *jones = nullptr;
+    cplx<double> *grad = nullptr;
+    double *terms = nullptr;
+};
+// Queues the Jones objective's kernels on `on`: the gather k_jones_gradient (when rj.grad is not null), the in-place kernel,
+// the rows' sums and their reduction.  vis (nrows, 4 nbls) in place, rs from row_scratch for that shape (the counters are
+// zeroed here).  All device pointers; weights may be null.
+template <typename T>
+inline void launch_jones_residual(hipStream_t on, cplx<T> *vis, const cplx<T> *data, const T *weights, int64_t nrows,
+                                  const RowScratch &rs, const RowJones<T> &rj) {
+    constexpr int W = RES_W<T>;
+    const int nbls = (int)rj.pairs->nbls, nant = rj.pairs->nant;
+    const int64_t L = 4 * (int64_t)nbls;
+    const int *a1 = rj.pairs->d_ant1.template as<int>(), *a2 = rj.pairs->d_ant2.template as<int>();
+    const size_t lds = sizeof(cplx<T>) * 4 * (size_t)nant;
+    const int in_lds = lds <= GAIN_LDS_BYTES;
+    const int vec = rows_vec({vis, data, weights});
+    const unsigned rows_y = (unsigned)std::min<int64_t>(nrows, 65535);
+    // (a row's runs: one more than its own when it starts inside a chunk)
+    const unsigned nblk = (unsigned)std::max<int64_t>(1, cdiv(cdiv((int64_t)nbls, W) + 1, (int64_t)RES_CHUNKS * 256));
+    FV_HIP(hipMemsetAsync(rs.bad, 0, 2 * sizeof(int), on));
+    if (rj.grad)
+        hipLaunchKernelGGL(k_jones_gradient<T>, dim3((unsigned)cdiv(nant, 4), rows_y), dim3(256), 0, on, (const cplx<T> *)vis, data,
+                           weights, rj.jones, a1, a2, rj.pairs->d_off.template as<int>(), rj.pairs->d_inc.template as<int>(), nrows,
+                           nbls, nant, rj.grad);
+    hipLaunchKernelGGL(k_jones_residual_rows<T>, dim3(nblk, rows_y), dim3(256), in_lds ? lds : 0, on, vis, data, weights, rj.jones,
+                       a1, a2, nrows, nbls, nant, in_lds, vec, rj.terms, rs.bad);
+    hipLaunchKernelGGL(k_jones_rows_sum<T>, dim3((unsigned)rs.nblk, rows_y), dim3(256), 0, on, (const double *)rj.terms, nrows, L,
+                       rs.partials, rs.bad);
     hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)rs.partials, nrows,
                        rs.nblk, rs.sums);
 }
@@ -2891,6 +3211,9 @@ struct SimBase {
     virtual void run_residual_gains(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
                                     int weights_on_device, const void *gains, int gains_on_device, void *gvis, int gvis_on_device,
                                     double *chi2_ft, void *ggains, int ggains_on_device) = 0;
+    virtual void run_residual_jones(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                                    int weights_on_device, const void *jones, int jones_on_device, void *gvis, int gvis_on_device,
+                                    double *chi2_ft, void *gjones, int gjones_on_device) = 0;
     virtual void gain_weight_block(int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
                                    const void *weights, int weights_on_device, const void *gains, int gains_on_device,
                                    const void *d_gains, int d_gains_on_device, double *q_ft, void *hgains,
@@ -3077,6 +3400,7 @@ class Sim : public SimBase {
     DevBuf d_res_sum;          // fused objective: the blocks' partial sums, the rows' sums and the two bad-input counters
     DevBuf d_res_g, d_res_gg;  // gains: a block's host gains staged on the device / the gain gradient of a host destination
     DevBuf d_res_dg;           // gains: a block's host gain direction staged on the device (fv_sim_gain_weight_block)
+    DevBuf d_res_terms;        // Jones gains: the rows' fp64 terms of a block (fv_sim_run_residual_jones)
     GainPairs gain_pairs;      // gains: the antenna pair of every baseline and the incidence lists (fv_sim_set_gain_pairs)
     DevBuf d_bt_d, d_bt_out;   // basis tangent: host directions D / the (ndir, ...) output of a host destination, on the device
     DevBuf d_csr_start, d_csr;  // basis mode: per antenna, its baselines as 2 b + role (k_coef_reduce)
@@ -4517,6 +4841,36 @@ class Sim : public SimBase {
         if (ggains && !ggains_on_device)
             FV_HIP(hipMemcpyAsync(ggains, dgg, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, stream));
         finish_rows(rs, nrows, chi2_ft, {&d_res_d, &d_res_w, &d_res_g, &d_res_gg});  // (the gains and the gradient's block too)
+    }
+
+    // ---- Jones gains in the fused objective (DESIGN.md "Jones gains") ---------------------------------------------------
+    // run_residual_gains' sequence with the Jones kernels, on a polarized handle: jones is the block's (f1 - f0, t1 - t0, 2,
+    // 2, nant) array of the handle's precision, gjones the same shape in complex128 or null (the gather does not run).  The
+    // rows' terms take one more buffer, 8 bytes per value of the block; host matrices are staged and given back with the
+    // data and the weights, and the terms with them.
+    void run_residual_jones(int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
+                            int weights_on_device, const void *jones, int jones_on_device, void *gvis, int gvis_on_device,
+                            double *chi2_ft, void *gjones, int gjones_on_device) override {
+        check_run(t0, t1, f0, f1);
+        FV_REQUIRE(tpol == 4, "fv_sim_run_residual_jones: Jones gains need a polarized handle");
+        FV_REQUIRE(t1 > t0 && f1 > f0, "fv_sim_run_residual_jones: empty range of times or frequencies");
+        FV_REQUIRE(gain_pairs.nbls == nbls, "fv_sim_run_residual_jones: fv_sim_set_gain_pairs first (after the array is set)");
+        const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
+        const size_t n = (size_t)nrows * (size_t)L;
+        const size_t nj = (size_t)nrows * 4 * (size_t)gain_pairs.nant;
+        const cplx<T> *dd = staged<cplx<T>>(d_res_d, data, data_on_device, n);
+        const T *dw = staged<T>(d_res_w, weights, weights_on_device, n);
+        const cplx<T> *djn = staged<cplx<T>>(d_res_g, jones, jones_on_device, nj);
+        cplx<T> *dg = staged_out<cplx<T>>(d_out, gvis, gvis_on_device, n);
+        cplx<double> *dgj = staged_out<cplx<double>>(d_res_gg, gjones, gjones_on_device, nj);
+        const RowScratch rs = row_scratch<T>(d_res_sum, nrows, L);
+        d_res_terms.reserve(sizeof(double) * n);
+        run(t0, t1, f0, f1, dg, 1);
+        launch_jones_residual<T>(stream, dg, dd, dw, nrows, rs, {&gain_pairs, djn, dgj, d_res_terms.as<double>()});
+        if (!gvis_on_device) FV_HIP(hipMemcpyAsync(gvis, dg, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, stream));
+        if (gjones && !gjones_on_device)
+            FV_HIP(hipMemcpyAsync(gjones, dgj, sizeof(cplx<double>) * nj, hipMemcpyDeviceToHost, stream));
+        finish_rows(rs, nrows, chi2_ft, {&d_res_d, &d_res_w, &d_res_g, &d_res_gg, &d_res_terms});
     }
 
     // ---- Gauss-Newton product with gains (DESIGN.md "Gains in the Gauss-Newton product") ------------------------------

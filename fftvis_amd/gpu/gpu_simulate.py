@@ -281,6 +281,24 @@ class SimHandle:
                                                      _lib.ptr(chi2), ggp, gg_dev))
         return chi2
 
+    def run_jones_residual(self, t0, t1, f0, f1, data, weights, jones, gvis, gjones=None):
+        """``run_gain_residual`` with one 2 x 2 complex matrix per antenna (``fv_sim_run_residual_jones``; ``set_gain_pairs``
+        first, a polarized handle): antenna a's Jones matrix ``A_a[ax, feed]`` becomes ``A_a jones[a]``, on the output
+        ``V'[x, y] = sum conj(J[a1][y', y]) J[a2][x', x] V[x', y']``; ``gvis`` receives ``d chi2 / dV`` and the returned rows
+        are ``sum w |V' - data|^2``.  ``jones``: C-contiguous (f1 - f0, t1 - t0, 2, 2, nant), this engine's complex dtype,
+        ``jones[f, t, i, j, a]`` with i the feed of the ideal antenna and j the measured one; ``gjones``: the same shape,
+        complex128, filled with the gradient with respect to the matrices, or None (its kernel does not run).  numpy arrays
+        are host buffers, torch tensors device buffers.  The call synchronises."""
+        dp, d_dev = _buffer_addr(data)
+        wp, w_dev = _buffer_addr(weights)
+        jp, j_dev = _buffer_addr(jones)
+        gp, g_dev = _buffer_addr(gvis)
+        gjp, gj_dev = _buffer_addr(gjones)
+        chi2 = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
+        _lib.check(self._L.fv_sim_run_residual_jones(self._h, t0, t1, f0, f1, dp, d_dev, wp, w_dev, jp, j_dev, gp, g_dev,
+                                                     _lib.ptr(chi2), gjp, gj_dev))
+        return chi2
+
     def weight_block(self, t0, t1, f0, f1, parts, weights):
         """The weighting step of a Gauss-Newton product for times [t0,t1) x freqs [f0,f1) (``fv_sim_weight_block``):
         ``parts`` -- one to four device tensors, each a C-contiguous block of ``out_shape(t1 - t0, f1 - f0)`` of this
@@ -674,7 +692,10 @@ class GPUSimulationEngine(SimulationEngine):
           nant) of this precision's complex dtype, rows in ``ants``' order -- makes the data model
           ``conj(g[a1]) g[a2] V``: ``SimHandle.run_gain_residual`` replaces ``run_residual``, G is d chi2 / dV, and
           ``outputs["ggains"]`` (a host complex128 array of the gains' shape, optional) receives every block's rows of
-          the gain gradient.
+          the gain gradient.  The fourth element ``("jones", block)`` -- ``block`` a host array (nfreqs, ntimes, 2, 2, nant)
+          of this precision's complex dtype, ``block[f, t, i, j, a]`` the matrix of antenna ``a`` (``polarized=True``) --
+          makes the data model ``A_a -> A_a block[a]`` instead: ``SimHandle.run_jones_residual`` runs per time block, and
+          ``outputs["gjones"]`` (a host complex128 array of the block's shape, optional) receives the gradient rows.
         * ``gauss_newton_of`` (extra; what ``simulate_vis_gauss_newton`` passes): a triple ``(directions, weights, outputs)``
           -- the Gauss-Newton product H p, H = 2 J^T W J, from one handle and one set-up, the tangent U = J p never
           leaving the device.  ``directions`` is a dict, each entry optional, at least one given: ``"d_fluxes"`` (a host
@@ -1131,6 +1152,13 @@ def _run_sky_adjoint(h, g, gflux, gtopo, t0, t1, f0, f1, nblk_t, coord_mgr, basi
 
 _OBJECTIVE_OUTPUTS = ("gflux", "gcoefs", "gbls", "gtopo", "gvis")
 _GAIN_OUTPUT = "ggains"  # (objective_of with gains only)
+_JONES_OUTPUT = "gjones"  # (objective_of with Jones matrices only)
+
+
+def _is_jones(gains):
+    """Whether the fourth element of ``objective_of`` holds Jones matrices: ``("jones", block)``, which no array of gains
+    can be mistaken for."""
+    return isinstance(gains, tuple) and len(gains) == 2 and isinstance(gains[0], str) and gains[0] == "jones"
 
 
 def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, coord_mgr, basis=False, gains=None):
@@ -1140,9 +1168,13 @@ def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, co
     ``_run_adjoint``, ``_run_sky_adjoint`` and ``_run_basis_source`` run them: the first block overwrites ``gflux``,
     ``gcoefs`` and ``gbls``, later ones add, and every block fills its rows of ``gtopo``.  With ``gains`` (host, (f1 - f0,
     t1 - t0, nfeed, nant)) every block's ``run_gain_residual`` takes its time steps of them instead and fills its time
-    steps of ``outputs["ggains"]``; the passes read its G unchanged.  Returns chi2, (f1 - f0, t1 - t0) float64 on the
-    host.  Every call ends synchronised."""
-    ggains = outputs.get(_GAIN_OUTPUT)
+    steps of ``outputs["ggains"]``; the passes read its G unchanged.  With ``gains = ("jones", block)`` (host, (f1 - f0,
+    t1 - t0, 2, 2, nant)) it is ``run_jones_residual`` and ``outputs["gjones"]``.  Returns chi2, (f1 - f0, t1 - t0) float64
+    on the host.  Every call ends synchronised."""
+    jones = _is_jones(gains)
+    if jones:
+        gains = gains[1]
+    ggains = outputs.get(_JONES_OUTPUT if jones else _GAIN_OUTPUT)
     chi2 = np.zeros((f1 - f0, t1 - t0), dtype=np.float64)
     for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
         lo, hi = tb - t0, te - t0
@@ -1152,7 +1184,8 @@ def _run_objective(h, device, data, weights, outputs, t0, t1, f0, f1, nblk_t, co
             chi2[:, lo:hi] = h.run_residual(ta, te_, f0, f1, d, w, g)
         else:
             gg = _gain_output_block(ggains, lo, hi)
-            chi2[:, lo:hi] = h.run_gain_residual(ta, te_, f0, f1, d, w, _block_input(gains, lo, hi), g, gg)
+            residual = h.run_jones_residual if jones else h.run_gain_residual
+            chi2[:, lo:hi] = residual(ta, te_, f0, f1, d, w, _block_input(gains, lo, hi), g, gg)
             if gg is not None:
                 ggains[:, lo:hi] = gg
         _adjoints_of_block(h, g, outputs, lo, hi, t1 - t0, ta, te_, f0, f1, basis)
@@ -1381,12 +1414,18 @@ def _check_sky(p, basis):
 
 
 def _check_objective(p, basis):
-    if len(p) not in (3, 4) or not isinstance(p[2], dict) or set(p[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT}:
+    if (len(p) not in (3, 4) or not isinstance(p[2], dict)
+            or set(p[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT, _JONES_OUTPUT}):
         raise ValueError(f"objective_of: (data, weights, outputs) with outputs a dict over {_OBJECTIVE_OUTPUTS}")
     if p[2].get("gcoefs") is not None and not basis:
         raise ValueError("objective_of: gcoefs needs basis beams (beam_coefs)")
-    if p[2].get(_GAIN_OUTPUT) is not None and (len(p) == 3 or p[3] is None):
+    fourth = p[3] if len(p) == 4 else None
+    if isinstance(fourth, tuple) and not _is_jones(fourth):
+        raise ValueError("objective_of: the fourth element is the gains, or ('jones', block)")
+    if p[2].get(_GAIN_OUTPUT) is not None and (fourth is None or _is_jones(fourth)):
         raise ValueError("objective_of: ggains needs the gains (a fourth element)")
+    if p[2].get(_JONES_OUTPUT) is not None and not _is_jones(fourth):
+        raise ValueError("objective_of: gjones needs the matrices (a fourth element ('jones', block))")
 
 
 def _check_gauss_newton(p, basis):
@@ -1418,11 +1457,12 @@ def _prepare_forward(h, s, p):
     return p
 
 
-def _set_gain_pairs(h, s, keyword, named_gains):
+def _set_gain_pairs(h, s, keyword, named_gains, jones=False):
     """The fit passes' gains: every block of ``named_gains`` -- (name, host array or None) -- checked against the run's
-    (nf, nt, nfeed, nant) layout, then the antenna pair of every baseline, as rows of ``ants``' order, told to the handle."""
+    (nf, nt, nfeed, nant) layout -- (nf, nt, 2, 2, nant) for Jones matrices --, then the antenna pair of every baseline, as
+    rows of ``ants``' order, told to the handle."""
     t0, t1, f0, f1 = s.span
-    shape = (f1 - f0, t1 - t0, 2 if s.polarized else 1, s.nant)
+    shape = (f1 - f0, t1 - t0) + ((2, 2) if jones else (2 if s.polarized else 1,)) + (s.nant,)
     for name, x in named_gains:
         if x is not None and (not isinstance(x, np.ndarray) or x.dtype != s.cdt or x.shape != shape):
             raise ValueError(f"{keyword}: {name} must be a {np.dtype(s.cdt).name} array of shape {shape}")
@@ -1433,9 +1473,13 @@ def _set_gain_pairs(h, s, keyword, named_gains):
 
 
 def _prepare_objective(h, s, p):
-    """``objective_of`` as (data, weights, outputs, gains or None), the handle told the gain pairs."""
+    """``objective_of`` as (data, weights, outputs, gains, ("jones", block) or None), the handle told the gain pairs."""
     gains = p[3] if len(p) == 4 else None
-    if gains is not None:
+    if _is_jones(gains):
+        if not s.polarized:
+            raise ValueError("objective_of: Jones matrices need polarized=True")
+        _set_gain_pairs(h, s, "objective_of", [("jones", gains[1])], jones=True)
+    elif gains is not None:
         _set_gain_pairs(h, s, "objective_of", [("gains", gains)])
     return p[0], p[1], p[2], gains
 
@@ -1508,12 +1552,14 @@ _PASSES = {
         run=lambda h, s, p, n: _run_sky_adjoint(h, *p, *s.span, n, s.coord_mgr, basis=s.use_basis), check=_check_sky,
         type3=_always, refusal="the sky adjoint runs"),
     # (a block's G, data and weights are on the device together: 2.5 blocks, 2 without weights; a block's gains and their
-    # gradient add (8 + 16) nfeed nant bytes per row to the 2.5 blocks of 8 tpol nbls: under 0.1 % once nbls >= nant)
+    # gradient add (8 + 16) nfeed nant bytes per row to the 2.5 blocks of 8 tpol nbls: under 0.1 % once nbls >= nant; Jones
+    # matrices add the rows' fp64 terms, 8 bytes per value: half a block in fp64, a whole one in fp32)
     "objective_of": _Pass(
         run=lambda h, s, p, n: _run_objective(h, s.device, p[0], p[1], p[2], *s.span, n, s.coord_mgr, basis=s.use_basis,
                                               gains=p[3]),
         check=_check_objective, type3=lambda p: _position_outputs(p[2]), refusal="the objective's position passes run",
-        sets_adjoint_path=True, prepare=_prepare_objective, blocks=lambda p, s: 2.0 if p[1] is None else 2.5),
+        sets_adjoint_path=True, prepare=_prepare_objective,
+        blocks=lambda p, s: (2.0 if p[1] is None else 2.5) + (8.0 / np.dtype(s.cdt).itemsize if _is_jones(p[3]) else 0.0)),
     # (a block's parts and weights are on the device together: one block per part, half a block of weights, one more
     # block when V is held; the gains, their direction and the product are under 0.1 % of one)
     "gauss_newton_of": _Pass(

@@ -107,6 +107,37 @@ int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, 
 int fv_gain_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
                           const int *ant2, const void *gains, void *vis, const void *data, const void *weights,
                           double *chi2_rows, void *ggains);
+/* fv_jones_residual_chi2: fv_residual_chi2 with one 2 x 2 complex (Jones) matrix per antenna folded in: leakage between the
+ * feeds as well as their gains (the kernels fv_sim_run_residual_jones queues behind its forward run).  vis, data, weights:
+ * nrows rows of 4 nbls values, value pol nbls + k of a row is V[x, y] of baseline k = (ant1[k], ant2[k]), pol = 2 x + y, y
+ * the feed of ant1[k] (the conjugated antenna) and x of ant2[k], as for fv_gain_residual_chi2.  jones: (nrows, 2, 2, nant)
+ * complex of `precision`, jones[r, i, j, a] = Gamma_a[i, j] with i the feed of the ideal antenna and j the measured one:
+ * antenna a's Jones matrix A_a[ax, feed] becomes A_a Gamma_a, and Gamma_a = diag(g[a]) are fv_gain_residual_chi2's gains.
+ * With G1 = Gamma[ant1[k]] and G2 = Gamma[ant2[k]], per baseline,
+ *   V'[x, y]  = sum_{x', y'} conj(G1[y', y]) G2[x', x] V[x', y'],   delta = V' - data,   G'[x, y] = 2 w[x, y] delta[x, y],
+ *   vis <- G[x', y'] = sum_{x, y} conj(G2[x', x]) G'[x, y] G1[y', y] = d chi2 / dV,
+ * chi2_rows[i] = sum over row i of w |delta|^2.  In that precision every operation rounds on its own, in this order, each
+ * sum of two products left to right:
+ *   B[x', y] = V[x', 0] conj(G1[0, y]) + V[x', 1] conj(G1[1, y]),     V'[x, y]  = G2[0, x] B[0, y] + G2[1, x] B[1, y],
+ *   delta = V' - data,   G' = 2 (w delta),
+ *   C[x', y] = conj(G2[x', 0]) G'[0, y] + conj(G2[x', 1]) G'[1, y],   G[x', y'] = C[x', 0] G1[y', 0] + C[x', 1] G1[y', 1],
+ * so that identity matrices give fv_residual_chi2's bits, in vis and in chi2_rows: the row terms are formed as there and
+ * added in its order (they pass through an fp64 block of the rows' shape on the device) -- no floating-point atomics, the
+ * same input gives the same bits.  A weight of exactly 0 flags that one (x, y) sample: G' is exactly 0 there, the datum is
+ * not used (NaN or Inf there do not propagate), nothing is added to chi2_rows or gjones, and the baseline's other samples
+ * still use all four model values; a baseline with all four samples flagged stores G = 0 exactly.  Bad weights and data
+ * are counted and reported as fv_residual_chi2 does.  gjones: (nrows, 2, 2, nant) complex128, or NULL (its kernel does
+ * not run):
+ *   gjones[r, y', y, a] += sum_x conj(G'[x, y]) (G2^T V)[x, y']      for every k with ant1[k] = a,
+ *   gjones[r, x', x, a] += sum_y G'[x, y] conj((V conj G1)[x', y])   for every k with ant2[k] = a,
+ * d chi2 = Re sum conj(gjones) dGamma (an auto-correlation adds to both), every term formed in fp64 from the inputs of
+ * `precision` and added in fp64 over the antenna's incidence list (ascending k, "a is ant1" first) by one wave per (row,
+ * antenna) that holds all four entries, with a fixed lane <-> entry assignment and an __shfl_xor tree; an antenna without
+ * a baseline gets exactly 0.  An antenna index outside [0, nant) and a null jones fail with FV_ERR_ARG before anything
+ * runs.  Host pointers. */
+int fv_jones_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1,
+                           const int *ant2, const void *jones, void *vis, const void *data, const void *weights,
+                           double *chi2_rows, void *gjones);
 /* fv_gain_normal_rows: one evaluation of the normal sums of the gain solve (the gather fv_gain_solve iterates).  The rows,
  * the pairs and the feeds (pol = 2 q + p) are fv_gain_residual_chi2's; vis, data, weights are read only; gains:
  * (nrows, nfeed, nant) complex128 whatever `precision` is.  A sample is used when w > 0 and ant1[k] != ant2[k]: an
@@ -596,6 +627,19 @@ int fv_sim_set_gain_pairs(fv_sim *h, int nant, const int *ant1, const int *ant2)
 int fv_sim_run_residual_gains(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device,
                               const void *weights, int weights_on_device, const void *gains, int gains_on_device, void *gvis,
                               int gvis_on_device, double *chi2_ft, void *ggains, int ggains_on_device);
+/* fv_sim_run_residual with one 2 x 2 complex (Jones) matrix per antenna: the data model is fv_jones_residual_chi2's
+ * V' = G2^T V conj(G1) on the [x, y] block of every baseline.  The call is fv_sim_run_residual_gains' -- forward into gvis,
+ * kernels on the main stream, one synchronisation -- with the kernels of fv_jones_residual_chi2: gvis = G = d chi2 / dV,
+ * chi2_ft the rows of sum w |V' - data|^2.  jones: (f1 - f0, t1 - t0, 2, 2, nant) complex of the handle's precision;
+ * gjones: the same shape in complex128, the gradient with respect to the matrices (d chi2 = Re sum conj(gjones) dGamma),
+ * or NULL.  Needs fv_sim_set_gain_pairs and a polarized handle.  Host matrices are staged and given back with host data
+ * and weights under the FFTVIS_HIP_ADJ_KEEP_BYTES rule, and so is the fp64 block of row terms the handle holds for the
+ * call.  A null handle, a null data, jones, gvis or chi2_ft, a flag other than 0 or 1, an empty range, missing pairs and
+ * a handle that is not polarized fail with FV_ERR_ARG before anything runs; bad weights and data as for
+ * fv_sim_run_residual.                                                                                                    */
+int fv_sim_run_residual_jones(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device,
+                              const void *weights, int weights_on_device, const void *jones, int jones_on_device, void *gvis,
+                              int gvis_on_device, double *chi2_ft, void *gjones, int gjones_on_device);
 /* Gauss-Newton product of the block times [t0, t1) x freqs [f0, f1): the tangent U = J p arrives as nparts = 1 .. 4 DEVICE
  * blocks parts_dev[j] in fv_sim_run's layout for the block, complex of the handle's precision -- what fv_sim_run and the
  * fv_sim_run_*_tangent calls of this handle wrote with out_on_device = 1 -- and the two kernels of fv_weight_rows on the

@@ -38,7 +38,10 @@ the data model (``gains`` may then be one of --wrt's names): ``fused`` and ``fus
 for the latter), ``separate`` becomes the forward to the host, the gain product and the loss in torch, .backward() and the
 public adjoints on the host result, and ``--profile gain_kernels`` runs the kernels of fv_gain_residual_chi2 (k_gain_gradient,
 k_residual_rows<T, true>) and of fv_residual_chi2 (k_residual_rows<T, false>) alone on the
-block's shape, six times each, alternating.  gauss_newton: one product
+block's shape, six times each, alternating; --jones puts one 2 x 2 matrix per antenna there instead (``jones`` among
+--wrt's names): ``fused`` and ``fused_device`` call ``simulate_vis_jones_chi2``, there is no ``separate``, and ``--profile
+jones_kernels`` runs the kernels of fv_jones_residual_chi2, fv_gain_residual_chi2 and fv_residual_chi2 alone the same way.
+gauss_newton: one product
 2 J^T W J p of a conjugate-gradient solve -- ``composed`` is the public tangent to the host, numpy's 2 w U and the public adjoint
 on the host result (runs on a checkout from before the fused call: --package DIR --only forward --only composed), ``fused``
 simulate_vis_gauss_newton on host weights and ``fused_device`` on resident weights; --case fluxes | ants | fluxes_radec |
@@ -254,7 +257,42 @@ def objective(a, fv, cfg, rng):
                     _lib.check(lib.fv_residual_chi2(0, p, rows, tpol * nbls, _lib.ptr(v), _lib.ptr(d2), _lib.ptr(w2), _lib.ptr(q)))
 
             calls["gain_kernels"] = gain_kernels
-    if names == ("fluxes",) and not basis and not a.gains:
+    if a.jones:  # one 2 x 2 matrix per antenna, identity + 0.1 N(0, 1), constant in time; "jones" may be one of --wrt's names
+        nant, nums = len(cfg["ants"]), list(cfg["ants"])
+        j0 = 0.1 * (rng.normal(size=(nant, 2, 2, a.nfreq)) + 1j * rng.normal(size=(nant, 2, 2, a.nfreq)))
+        j0[:, 0, 0] += 1
+        j0[:, 1, 1] += 1
+        gains = {"jones": j0.astype(cdt)}
+        a1 = [nums.index(b[0]) for b in cfg["baselines"]]
+        a2 = [nums.index(b[1]) for b in cfg["baselines"]]
+        del calls["separate"]  # (no composition to compare with: the diagonal gains' is --gains)
+        if a.profile == "jones_kernels":  # (for a kernel trace only) the Jones kernels next to the gain kernels and
+            # k_residual_rows alone, alternating, on host-uploaded blocks of the run's shape
+            def jones_kernels():
+                import importlib
+
+                _lib = importlib.import_module(fv.__name__ + "._lib")
+                lib = _lib.lib()
+                rows = a.nfreq * a.ntimes
+                jb = np.ascontiguousarray(np.broadcast_to(gains["jones"][..., None], (nant, 2, 2, a.nfreq, a.ntimes))
+                                          .transpose(3, 4, 1, 2, 0))
+                gb = np.ascontiguousarray(np.stack([jb[:, :, 0, 0], jb[:, :, 1, 1]], axis=2))
+                i1, i2 = np.array(a1, np.int32), np.array(a2, np.int32)
+                v0 = (rng.normal(size=(rows, 4 * nbls)) + 1j * rng.normal(size=(rows, 4 * nbls))).astype(cdt)
+                d2, w2, q = d.reshape(rows, -1), w.reshape(rows, -1), np.zeros(rows)
+                gj, gg = np.zeros(jb.shape, np.complex128), np.zeros(gb.shape, np.complex128)
+                for _ in range(6):
+                    v = v0.copy()
+                    _lib.check(lib.fv_jones_residual_chi2(0, p, rows, nbls, nant, _lib.ptr(i1), _lib.ptr(i2), _lib.ptr(jb),
+                                                          _lib.ptr(v), _lib.ptr(d2), _lib.ptr(w2), _lib.ptr(q), _lib.ptr(gj)))
+                    v = v0.copy()
+                    _lib.check(lib.fv_gain_residual_chi2(0, p, rows, nbls, 4, nant, _lib.ptr(i1), _lib.ptr(i2), _lib.ptr(gb),
+                                                         _lib.ptr(v), _lib.ptr(d2), _lib.ptr(w2), _lib.ptr(q), _lib.ptr(gg)))
+                    v = v0.copy()
+                    _lib.check(lib.fv_residual_chi2(0, p, rows, 4 * nbls, _lib.ptr(v), _lib.ptr(d2), _lib.ptr(w2), _lib.ptr(q)))
+
+            calls["jones_kernels"] = jones_kernels
+    if names == ("fluxes",) and not basis and not a.gains and not a.jones:
         def separate_torch():
             import torch
 
@@ -276,17 +314,19 @@ def objective(a, fv, cfg, rng):
             if not resident:
                 resident.extend((torch.from_numpy(d).cuda(), torch.from_numpy(w).cuda()))
                 if gains:
-                    resident.append(torch.from_numpy(gains["gains"]).cuda())
+                    resident.append(torch.from_numpy(next(iter(gains.values()))).cuda())
                 torch.cuda.synchronize()
+            if a.jones:
+                return fv.simulate_vis_jones_chi2(resident[0], **cfg, weights=resident[1], wrt=names, jones=resident[2])
             if gains:
                 return fv.simulate_vis_gain_chi2(resident[0], **cfg, weights=resident[1], wrt=names, gains=resident[2])
             return fv.simulate_vis_chi2(resident[0], **cfg, weights=resident[1], wrt=names)
 
-        chi2_call = fv.simulate_vis_gain_chi2 if gains else fv.simulate_vis_chi2
+        chi2_call = fv.simulate_vis_jones_chi2 if a.jones else fv.simulate_vis_gain_chi2 if gains else fv.simulate_vis_chi2
         calls["fused"] = lambda: chi2_call(d, **cfg, weights=w, wrt=names, **gains)
         calls["fused_device"] = fused_device
     head = {"config": a.config, "precision": p, "polarized": bool(cfg["polarized"]), "lattice": bool(a.lattice), "wrt": list(names),
-            "gains": bool(a.gains),
+            "gains": bool(a.gains), "jones": bool(a.jones),
             # per call, from the shapes: V to the host and G back / d and w to the device / the gradients and chi2 alone
             "pcie_bytes": {"separate": 2 * d.nbytes, "fused": d.nbytes + w.nbytes, "fused_device": 0},
             "vis_bytes": d.nbytes}
@@ -554,7 +594,7 @@ FAMILIES = {
         "source_tangent_over_forward": ("source_tangent", "forward"),
         "source_tangent_over_tangent_ants": ("source_tangent", "tangent_ants"),
         "joint_over_fluxes_plus_source_adjoint": ("joint", ("fluxes", "source_adjoint"))}),
-    "objective": (objective, "C3", 8, ("lattice", "wrt", "gains"), "runs", {
+    "objective": (objective, "C3", 8, ("lattice", "wrt", "gains", "jones"), "runs", {
         "separate_over_forward": ("separate", "forward"), "fused_over_separate": ("fused", "separate"),
         "fused_device_over_separate": ("fused_device", "separate"), "fused_device_over_forward": ("fused_device", "forward"),
         "separate_torch_over_separate": ("separate_torch", "separate")}),
@@ -565,7 +605,7 @@ FAMILIES = {
         "solve_over_forward": ("solve", "forward"), "products_over_solve": ("gauss_newton_products", "solve")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
-             "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False}  # and their defaults
+             "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False, "jones": False}  # and their defaults
 
 
 def main():
@@ -589,6 +629,9 @@ def main():
     ap.add_argument("--gains", action="store_true", default=None,
                     help="objective: per-antenna gains in the data model (gains may then be one of --wrt's names); "
                          "gauss_newton: the gains in the data model (simulate_vis_gain_gauss_newton)")
+    ap.add_argument("--jones", action="store_true", default=None,
+                    help="objective: one 2 x 2 matrix per antenna in the data model (simulate_vis_jones_chi2; jones may then "
+                         "be one of --wrt's names; a polarized configuration)")
     ap.add_argument("--d-gains", action="store_true", default=None,
                     help="gauss_newton, with --gains: a gain direction, and the gain block among the products")
     ap.add_argument("--precision", type=int, choices=[1, 2], default=None, help="2: the configuration in fp64 at eps 6e-8")
