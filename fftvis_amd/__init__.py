@@ -17,7 +17,7 @@ and their gradient; ``simulate_vis_jones_chi2`` for full 2 x 2 Jones matrices pe
 Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the tangent
 on the device (``simulate_vis_gauss_newton``; ``simulate_vis_gain_gauss_newton`` with the gains in the data model, a gain
 direction and the gain block of the product), and the gains themselves for a fixed model, solved on the device against
-a resident model (``simulate_vis_gain_solve``).
+a resident model (``simulate_vis_gain_solve``; ``simulate_vis_jones_solve`` for the full 2 x 2 matrices).
 """
 
 __version__ = "0.1.0"
@@ -42,6 +42,7 @@ from .adjoint import (  # noqa: F401
     simulate_vis_gain_solve,
     simulate_vis_gauss_newton,
     simulate_vis_jones_chi2,
+    simulate_vis_jones_solve,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,
     simulate_vis_sky_adjoint,

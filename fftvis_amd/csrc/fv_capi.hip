@@ -455,28 +455,38 @@ static void gain_normal_rows_host(int device, int64_t nrows, int64_t nbls, int t
     FV_HIP(hipGetLastError());
 }
 
-// The whole alternating solve (DESIGN.md "Gain solve"): device blocks are used where they lie, host blocks are staged
-// once; the iterate lives in two device buffers and only the units' change comes back per iteration.
-template <typename T>
-static void gain_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1, const int *ant2,
-                            int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
-                            const void *weights, int weights_on_device, void *gains, int max_iter, double tol, int *niter_out,
-                            double *change_out, double *chi2_ft_out, int *solved_out) {
-    const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
+// The alternating solve that fv_gain_solve and fv_jones_solve run (DESIGN.md "Gain solve", "Jones solve"): device blocks
+// are used where they lie, host blocks are staged once; the iterate lives in two device buffers and only the units' change
+// comes back per iteration.  What differs comes from the caller: the values of a row (row_len), the complex128 entries
+// of a unit's iterate (nx) and the ints of its `solved` (ns), the bytes a row's normal sums take in the two scratch
+// buffers, the partials per row of the chi2 pass (npart doubles, in the first scratch buffer), and the three launches.
+struct SolveBlocks {  // what the launches are given: all device pointers, weights may be null
+    hipStream_t on;
+    const GainPairs &gp;
+    const void *vis, *data, *weights;
+    int64_t nrows, rows_per_unit;
+    void *sums0, *sums1;
+};
+template <typename T, typename Normal, typename Update, typename Chi2>
+static void alternating_solve(int device, int nfreqs, int ntimes, int64_t nbls, int nant, const int *ant1, const int *ant2, int per_time,
+                              int64_t row_len, int nx, int ns, size_t row_bytes0, size_t row_bytes1, int npart, const void *vis,
+                              int vis_on_device, const void *data, int data_on_device, const void *weights, int weights_on_device,
+                              void *x, int max_iter, double tol, int *niter_out, double *change_out, double *chi2_ft_out,
+                              int *solved_out, Normal normal, Update update, Chi2 chi2) {
     const int64_t nrows = (int64_t)nfreqs * ntimes, rows_per_unit = per_time ? 1 : ntimes;
     const int64_t nunits = per_time ? nrows : nfreqs;
     *niter_out = 0;
-    if (nrows == 0) return;  // (no unit: gains, change and solved are empty)
+    if (nrows == 0) return;  // (no unit: the iterate, change and solved are empty)
     std::fill(change_out, change_out + nunits, 0.0);
     std::fill(chi2_ft_out, chi2_ft_out + nrows, 0.0);
-    std::fill(solved_out, solved_out + nunits * ng, 0);
-    if (nbls == 0) return;  // (the start gains, chi2 0, nothing solved)
+    std::fill(solved_out, solved_out + nunits * ns, 0);
+    if (nbls == 0) return;  // (the start, chi2 0, nothing solved)
     FV_HIP(hipSetDevice(device));
     StreamGuard sg;
-    const size_t n = (size_t)nrows * (size_t)tpol * (size_t)nbls, ngu = (size_t)nunits * ng, ngr = (size_t)nrows * ng;
+    const size_t n = (size_t)nrows * (size_t)row_len, nxu = (size_t)nunits * nx, nsu = (size_t)nunits * ns;
     GainPairs gp;
     gp.set(sg.s, nant, nbls, ant1, ant2);
-    DevBuf sv, sd, sw, dg[2], dnum, dden, dchange, dsolved, dchi2, dbad;
+    DevBuf sv, sd, sw, dx[2], sums0, sums1, dchange, dsolved, dchi2, dbad;
     const auto staged = [&](DevBuf &buf, const void *x, int on_device, size_t bytes) -> const void * {
         if (!x || on_device) return x;
         buf.reserve(bytes);
@@ -486,14 +496,14 @@ static void gain_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, in
     const cplx<T> *dv = static_cast<const cplx<T> *>(staged(sv, vis, vis_on_device, sizeof(cplx<T>) * n));
     const cplx<T> *dd = static_cast<const cplx<T> *>(staged(sd, data, data_on_device, sizeof(cplx<T>) * n));
     const T *dw = static_cast<const T *>(staged(sw, weights, weights_on_device, sizeof(T) * n));
-    for (auto &b : dg) b.reserve(sizeof(cplx<double>) * ngu);
-    dnum.reserve(sizeof(cplx<double>) * ngr);
-    dden.reserve(sizeof(double) * ngr);
+    for (auto &b : dx) b.reserve(sizeof(cplx<double>) * nxu);
+    sums0.reserve(row_bytes0 * (size_t)nrows);
+    sums1.reserve(row_bytes1 * (size_t)nrows);
     dchange.reserve(sizeof(double) * (size_t)nunits);
-    dsolved.reserve(sizeof(int) * ngu);
+    dsolved.reserve(sizeof(int) * nsu);
     dchi2.reserve(sizeof(double) * (size_t)nrows);
     dbad.reserve(16);
-    FV_HIP(hipMemcpyAsync(dg[0].p, gains, sizeof(cplx<double>) * ngu, hipMemcpyHostToDevice, sg.s));
+    FV_HIP(hipMemcpyAsync(dx[0].p, x, sizeof(cplx<double>) * nxu, hipMemcpyHostToDevice, sg.s));
     int *bad = dbad.as<int>();
     int hbad[3] = {0, 0, 0};
     FV_HIP(hipMemsetAsync(bad, 0, sizeof(hbad), sg.s));
@@ -503,14 +513,13 @@ static void gain_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, in
     FV_HIP(hipStreamSynchronize(sg.s));
     FV_HIP(hipGetLastError());
     throw_if_bad_solve_input(hbad);
+    const SolveBlocks blk{sg.s, gp, dv, dd, dw, nrows, rows_per_unit, sums0.p, sums1.p};
     int cur = 0, niter = 0;
     while (niter < max_iter) {
         ++niter;
-        launch_gain_normal<T>(sg.s, dv, dd, dw, dg[cur].as<cplx<double>>(), gp, nrows, rows_per_unit, tpol, dnum.as<cplx<double>>(),
-                              dden.as<double>(), nullptr);
-        hipLaunchKernelGGL(k_gain_update, dim3((unsigned)nunits), dim3(256), 0, sg.s, (const cplx<double> *)dnum.as<cplx<double>>(),
-                           (const double *)dden.as<double>(), (const cplx<double> *)dg[cur].as<cplx<double>>(),
-                           dg[cur ^ 1].as<cplx<double>>(), rows_per_unit, ng, niter & 1, dchange.as<double>(), dsolved.as<int>());
+        normal(blk, dx[cur].as<cplx<double>>());
+        update(blk, (const cplx<double> *)dx[cur].as<cplx<double>>(), dx[cur ^ 1].as<cplx<double>>(), niter & 1, dchange.as<double>(),
+               dsolved.as<int>());
         cur ^= 1;
         FV_HIP(hipMemcpyAsync(change_out, dchange.p, sizeof(double) * (size_t)nunits, hipMemcpyDeviceToHost, sg.s));
         FV_HIP(hipStreamSynchronize(sg.s));  // (the one small synchronisation per iteration: the host decides)
@@ -518,17 +527,90 @@ static void gain_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, in
         for (int64_t u = 0; u < nunits; ++u) done = done && change_out[u] < tol;
         if (done) break;
     }
-    // the chi2 at the final gains: num's buffer (nrows, ng complex128) holds the waves' partials
-    double *part = dnum.as<double>();
-    launch_gain_normal<T>(sg.s, dv, dd, dw, dg[cur].as<cplx<double>>(), gp, nrows, rows_per_unit, tpol, nullptr, nullptr, part);
-    hipLaunchKernelGGL(k_gain_chi2_rows, dim3((unsigned)cdiv(nrows, 4)), dim3(256), 0, sg.s, (const double *)part, nrows, ng,
+    // the chi2 at the final iterate: the first scratch buffer holds the waves' partials
+    chi2(blk, dx[cur].as<cplx<double>>());
+    hipLaunchKernelGGL(k_gain_chi2_rows, dim3((unsigned)cdiv(nrows, 4)), dim3(256), 0, sg.s, (const double *)sums0.p, nrows, npart,
                        dchi2.as<double>());
     FV_HIP(hipMemcpyAsync(chi2_ft_out, dchi2.p, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(gains, dg[cur].p, sizeof(cplx<double>) * ngu, hipMemcpyDeviceToHost, sg.s));
-    FV_HIP(hipMemcpyAsync(solved_out, dsolved.p, sizeof(int) * ngu, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(x, dx[cur].p, sizeof(cplx<double>) * nxu, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(solved_out, dsolved.p, sizeof(int) * nsu, hipMemcpyDeviceToHost, sg.s));
     FV_HIP(hipStreamSynchronize(sg.s));
     FV_HIP(hipGetLastError());
     *niter_out = niter;
+}
+
+// Per-antenna gains: num (complex128) and den (float64) per (row, feed, antenna), k_gain_normal and k_gain_update.
+template <typename T>
+static void gain_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1, const int *ant2,
+                            int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
+                            const void *weights, int weights_on_device, void *gains, int max_iter, double tol, int *niter_out,
+                            double *change_out, double *chi2_ft_out, int *solved_out) {
+    const int ng = (tpol == 4 ? 2 : 1) * nant;
+    const auto gather = [=](const SolveBlocks &b, const cplx<double> *g, bool chi2) {
+        launch_gain_normal<T>(b.on, (const cplx<T> *)b.vis, (const cplx<T> *)b.data, (const T *)b.weights, g, b.gp, b.nrows,
+                              b.rows_per_unit, tpol, chi2 ? nullptr : (cplx<double> *)b.sums0, chi2 ? nullptr : (double *)b.sums1,
+                              chi2 ? (double *)b.sums0 : nullptr);
+    };
+    alternating_solve<T>(
+        device, nfreqs, ntimes, nbls, nant, ant1, ant2, per_time, (int64_t)tpol * nbls, ng, ng, sizeof(cplx<double>) * ng,
+        sizeof(double) * ng, ng, vis, vis_on_device, data, data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out,
+        change_out, chi2_ft_out, solved_out, [=](const SolveBlocks &b, const cplx<double> *g) { gather(b, g, false); },
+        [=](const SolveBlocks &b, const cplx<double> *g_old, cplx<double> *g_new, int odd, double *change, int *solved) {
+            hipLaunchKernelGGL(k_gain_update, dim3((unsigned)(b.nrows / b.rows_per_unit)), dim3(256), 0, b.on,
+                               (const cplx<double> *)b.sums0, (const double *)b.sums1, g_old, g_new, b.rows_per_unit, ng, odd, change,
+                               solved);
+        },
+        [=](const SolveBlocks &b, const cplx<double> *g) { gather(b, g, true); });
+}
+
+template <typename T>
+static void jones_normal_rows_host(int device, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                                   const void *jones, const void *vis, const void *data, const void *weights, double *A_out,
+                                   void *b_out) {
+    const size_t nj = (size_t)nrows * 4 * (size_t)nant;
+    if (nrows == 0) return;
+    if (nbls == 0) {
+        std::memset(A_out, 0, sizeof(double) * 2 * nj);
+        std::memset(b_out, 0, sizeof(cplx<double>) * nj);
+        return;
+    }
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const size_t n = (size_t)nrows * 4 * (size_t)nbls;
+    GainPairs gp;
+    gp.set(sg.s, nant, nbls, ant1, ant2);
+    DevBuf dv, dd, dw, djn, dA, db;
+    dA.reserve(sizeof(double) * 2 * nj);
+    db.reserve(sizeof(cplx<double>) * nj);
+    launch_jones_normal<T>(sg.s, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<cplx<T>>(sg.s, dd, data, n),
+                           to_device<T>(sg.s, dw, weights, n), to_device<cplx<double>>(sg.s, djn, jones, nj), gp, nrows, 1,
+                           dA.as<double>(), db.as<cplx<double>>(), nullptr);
+    FV_HIP(hipMemcpyAsync(A_out, dA.p, sizeof(double) * 2 * nj, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(b_out, db.p, sizeof(cplx<double>) * nj, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+}
+
+// 2 x 2 matrices: A (8 float64) and b (4 complex128) per (row, antenna), k_jones_normal and k_jones_update.
+template <typename T>
+static void jones_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                             int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
+                             const void *weights, int weights_on_device, void *jones, int max_iter, double tol, int *niter_out,
+                             double *change_out, double *chi2_ft_out, int *solved_out) {
+    const auto gather = [=](const SolveBlocks &b, const cplx<double> *j, bool chi2) {
+        launch_jones_normal<T>(b.on, (const cplx<T> *)b.vis, (const cplx<T> *)b.data, (const T *)b.weights, j, b.gp, b.nrows,
+                               b.rows_per_unit, chi2 ? nullptr : (double *)b.sums0, chi2 ? nullptr : (cplx<double> *)b.sums1,
+                               chi2 ? (double *)b.sums0 : nullptr);
+    };
+    alternating_solve<T>(
+        device, nfreqs, ntimes, nbls, nant, ant1, ant2, per_time, 4 * nbls, 4 * nant, 2 * nant, sizeof(double) * 8 * nant,
+        sizeof(cplx<double>) * 4 * nant, nant, vis, vis_on_device, data, data_on_device, weights, weights_on_device, jones, max_iter, tol,
+        niter_out, change_out, chi2_ft_out, solved_out, [=](const SolveBlocks &b, const cplx<double> *j) { gather(b, j, false); },
+        [=](const SolveBlocks &b, const cplx<double> *j_old, cplx<double> *j_new, int odd, double *change, int *solved) {
+            hipLaunchKernelGGL(k_jones_update, dim3((unsigned)(b.nrows / b.rows_per_unit)), dim3(256), 0, b.on, (const double *)b.sums0,
+                               (const cplx<double> *)b.sums1, j_old, j_new, b.rows_per_unit, nant, odd, change, solved);
+        },
+        [=](const SolveBlocks &b, const cplx<double> *j) { gather(b, j, true); });
 }
 
 template <typename T>
@@ -834,6 +916,55 @@ int fv_gain_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbl
             gain_solve_host<float>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, per_time, vis, vis_on_device, data,
                                    data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out, change_out,
                                    chi2_ft_out, solved_out);
+    });
+}
+
+int fv_jones_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                         const void *jones, const void *vis, const void *data, const void *weights, double *A_out, void *b_out) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_jones_normal_rows: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_jones_normal_rows: nant must be positive");
+        FV_REQUIRE(nrows == 0 || (jones && A_out && b_out), "fv_jones_normal_rows: null jones, A_out or b_out");
+        FV_REQUIRE(nrows == 0 || nbls == 0 || (vis && data && ant1 && ant2), "fv_jones_normal_rows: null pairs, vis or data");
+        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
+            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                       "fv_jones_normal_rows: antenna index outside [0, nant)");
+        if (precision == 2)
+            jones_normal_rows_host<double>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, A_out, b_out);
+        else
+            jones_normal_rows_host<float>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, A_out, b_out);
+    });
+}
+
+int fv_jones_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                   int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device, const void *weights,
+                   int weights_on_device, void *jones, int max_iter, double tol, int *niter_out, double *change_out,
+                   double *chi2_ft_out, int *solved_out) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(nfreqs >= 0 && ntimes >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_jones_solve: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_jones_solve: nant must be positive");
+        FV_REQUIRE(max_iter >= 1, "fv_jones_solve: max_iter must be positive");
+        FV_REQUIRE(tol >= 0.0, "fv_jones_solve: tol must be non-negative");  // (a NaN fails the comparison)
+        FV_REQUIRE(((per_time | vis_on_device | data_on_device | weights_on_device) & ~1) == 0,
+                   "fv_jones_solve: per_time and the on_device flags must be 0 or 1");
+        FV_REQUIRE(niter_out, "fv_jones_solve: null niter_out");
+        const bool empty = nfreqs == 0 || ntimes == 0;
+        FV_REQUIRE(empty || (jones && change_out && chi2_ft_out && solved_out),
+                   "fv_jones_solve: null jones, change_out, chi2_ft_out or solved_out");
+        FV_REQUIRE(empty || nbls == 0 || (vis && data && ant1 && ant2), "fv_jones_solve: null pairs, vis or data");
+        for (int64_t k = 0; k < nbls && !empty; ++k)
+            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                       "fv_jones_solve: antenna index outside [0, nant)");
+        if (precision == 2)
+            jones_solve_host<double>(device, nfreqs, ntimes, nbls, nant, ant1, ant2, per_time, vis, vis_on_device, data,
+                                     data_on_device, weights, weights_on_device, jones, max_iter, tol, niter_out, change_out,
+                                     chi2_ft_out, solved_out);
+        else
+            jones_solve_host<float>(device, nfreqs, ntimes, nbls, nant, ant1, ant2, per_time, vis, vis_on_device, data,
+                                    data_on_device, weights, weights_on_device, jones, max_iter, tol, niter_out, change_out,
+                                    chi2_ft_out, solved_out);
     });
 }
 

@@ -2401,6 +2401,212 @@ inline void throw_if_bad_solve_input(const int bad[3]) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Jones solve on a resident model (fv_jones_normal_rows, fv_jones_solve; DESIGN.md "Jones solve"): the gain solve above
+// with one 2 x 2 matrix per antenna.  The block, the pairs and the incidence lists are the Jones kernels', tpol = 4; V, d
+// and w are read only; a sample is used when w > 0 and a1 != a2.  The iterate is complex128 whatever T is, (nunits, 2, 2,
+// nant) in the Jones layout J[(2 i + j) nant + a] = Gamma_a[i, j]; row `row` reads unit row / rows_per_unit.  For fixed V
+// the least-squares problem in one antenna's matrix, the others held, is linear and splits into one 2 x 2 Hermitian system
+// per measured feed (column) c of Gamma_a:
+//     side 1 (a = a2, c = x), Z[x', y] = sum_{y'} V[x', y'] conj(G1[y', y]):  u[i] = conj(Z[i, y]),  t = d[x, y],
+//     side 0 (a = a1, c = y), Y[x, y'] = sum_{x'} G2[x', x] V[x', y']:        u[i] = Y[x, i],        t = conj(d[x, y]),
+//     A[i, j] += w[x, y] u[i] conj(u[j]),   b[i] += w[x, y] u[i] t      over the column's used samples,
+// and with autos flagged gjones[:, c, a] = 2 (A Gamma_a[:, c] - b).  Both sides are one formula in the OTHER antenna's
+// matrix Go: u_o[i] = Go[0, o] X[0, i] + Go[1, o] X[1, i], o the other antenna's measured feed, with X = V on side 0 and
+// X = V^H on side 1.  So a lane reads the planes of V transposed and conjugated on side 1, those of d and w transposed
+// on side 0 (d conjugated there), and from then on every lane runs the same code on sample (c, o) -- no index into a
+// register array depends on the side.  k_jones_normal is k_jones_gradient's gather: one wave per (row, antenna), lane l
+// takes the entries l, l + 64, ... in order, a baseline's four V, its used d and its w read once for both columns, every
+// term formed and added in fp64 (16 accumulators: per column A00, A11, Re A01, Im A01, b[0], b[1]), an __shfl_xor tree,
+// one store per value and wave.  The row's matrices are staged in LDS when they fit GAIN_LDS_BYTES; a wave without an
+// antenna stays for the barriers.  CHI2 = true writes instead the wave's sum of w |V' - d|^2 over its side-0 entries --
+// every baseline once -- into part[row nant + a], for k_gain_chi2_rows.  k_jones_update, one block per unit: the sums of
+// the unit's rows in ascending order; a column is solved when A00 > 0, A11 > 0 and det = A00 A11 - |A01|^2 >
+// 2^-30 A00 A11 (else both of its entries keep their values), Gamma^[:, c] = A^-1 b in closed form, Gamma <- Gamma^ on
+// odd iterations and (Gamma^ + Gamma) / 2 on even ones, written into the OTHER buffer, and change[unit] =
+// max |new - old| / max |new| over the 4 nant entries.  No floating-point atomics anywhere.
+// A_out[((row 4 + q) 2 + c) nant + a], q = A00, A11, Re A01, Im A01;  b_out[((row 2 + i) 2 + c) nant + a].
+template <typename T, bool CHI2>
+__global__ void __launch_bounds__(256)
+    k_jones_normal(const cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
+                   const cplx<double> *__restrict__ jones, const int *__restrict__ ant1, const int *__restrict__ ant2,
+                   const int *__restrict__ inc_off, const int *__restrict__ inc, int64_t nrows, int64_t rows_per_unit, int nbls,
+                   int nant, int in_lds, double *__restrict__ A_out, cplx<double> *__restrict__ b_out) {
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    const int nj = 4 * nant;
+    const int ant_w = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const bool active = ant_w < nant;  // (whole waves: the tree below stays inside one)
+    const int ant = active ? ant_w : 0;
+    const int i0 = active ? inc_off[ant] : 0, i1 = active ? inc_off[ant + 1] : 0;
+    const int64_t L = 4 * (int64_t)nbls;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<double> *J = jones + (row / rows_per_unit) * nj;
+        if (in_lds) {
+            cplx<double> *jl = reinterpret_cast<cplx<double> *>(gain_lds);
+            for (int i = threadIdx.x; i < nj; i += 256) jl[i] = J[i];
+            J = jl;
+            __syncthreads();
+        }
+        double acc[2][8];  // per column: A00, A11, Re A01, Im A01, b[0], b[1]  (CHI2: acc[0][0] alone)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc[c][q] = 0.0;
+        for (int i = i0 + lane; i < i1; i += 64) {
+            const int k = inc[i] >> 1, side = inc[i] & 1;
+            const int a1 = ant1[k], a2 = ant2[k];
+            if (a1 == a2 || (CHI2 && side)) continue;  // an auto-correlation is flagged; chi2 counts a baseline once
+            const int64_t e = row * L + k;
+            // sample (c, o) = (this antenna's measured feed, the other's) lies in plane 2 x + y: 2 c + o on side 1, 2 o + c
+            // on side 0; X[k', i] = V[k', i] (plane 2 k' + i) on side 0 and conj(V[i, k']) (plane 2 i + k') on side 1
+            const int64_t ps = (int64_t)(side ? 1 : 2) * nbls, pt = (int64_t)(side ? 2 : 1) * nbls;
+            const int64_t plane_s[4] = {0, ps, pt, 3 * (int64_t)nbls};  // of sample 2 c + o
+            const int64_t plane_x[4] = {0, pt, ps, 3 * (int64_t)nbls};  // of X[k', i] at 2 k' + i
+            double w[4];
+            bool any = false;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const T wt = weights ? weights[e + plane_s[s]] : (T)1;
+                w[s] = wt > (T)0 ? (double)wt : 0.0;
+                any = any || wt > (T)0;
+            }
+            if (!any) continue;  // every sample flagged: nothing is added, V is not read
+            const int other = side ? a1 : a2;
+            const double sx = side ? -1.0 : 1.0;  // X = V^H on side 1;  t = conj(d) on side 0
+            cplx<double> x[4], go[4], u[4];       // u_o[i] at [2 o + i]
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                x[p] = {(double)vis[e + plane_x[p]].re, sx * (double)vis[e + plane_x[p]].im};
+                go[p] = J[p * nant + other];
+            }
+#pragma unroll
+            for (int o = 0; o < 2; ++o)
+#pragma unroll
+                for (int n = 0; n < 2; ++n) u[2 * o + n] = cadd(cmul(go[o], x[n]), cmul(go[2 + o], x[2 + n]));
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int o = 0; o < 2; ++o) {
+                    const int s = 2 * c + o;
+                    if (!(w[s] > 0.0)) continue;  // (a flagged datum is not read)
+                    const cplx<double> t = {(double)data[e + plane_s[s]].re, -sx * (double)data[e + plane_s[s]].im};
+                    const cplx<double> u0 = u[2 * o], u1 = u[2 * o + 1];
+                    if (CHI2) {  // side 0: conj(V'[x = o, y = c]) = sum_i conj(u_o[i]) Gamma_a[i, c], and t = conj(d)
+                        const cplx<double> vp = cadd(cmul(cconj(u0), J[c * nant + ant]), cmul(cconj(u1), J[(2 + c) * nant + ant]));
+                        const double dr = vp.re - t.re, di = vp.im - t.im;
+                        acc[0][0] += w[s] * (dr * dr + di * di);
+                    } else {
+                        const cplx<double> a01 = cmul(u0, cconj(u1)), b0 = cmul(u0, t), b1 = cmul(u1, t);
+                        acc[c][0] += w[s] * (u0.re * u0.re + u0.im * u0.im);
+                        acc[c][1] += w[s] * (u1.re * u1.re + u1.im * u1.im);
+                        acc[c][2] += w[s] * a01.re;
+                        acc[c][3] += w[s] * a01.im;
+                        acc[c][4] += w[s] * b0.re;
+                        acc[c][5] += w[s] * b0.im;
+                        acc[c][6] += w[s] * b1.re;
+                        acc[c][7] += w[s] * b1.im;
+                    }
+                }
+        }
+        if (CHI2) {
+            for (int off = 32; off > 0; off >>= 1) acc[0][0] += __shfl_xor(acc[0][0], off, 64);
+            if (active && lane == 0) A_out[row * nant + ant] = acc[0][0];
+        } else {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    for (int off = 32; off > 0; off >>= 1) acc[c][q] += __shfl_xor(acc[c][q], off, 64);
+                if (active && lane == 0) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) A_out[((row * 4 + q) * 2 + c) * nant + ant] = acc[c][q];
+                    b_out[((row * 2 + 0) * 2 + c) * nant + ant] = {acc[c][4], acc[c][5]};
+                    b_out[((row * 2 + 1) * 2 + c) * nant + ant] = {acc[c][6], acc[c][7]};
+                }
+            }
+        }
+        if (in_lds) __syncthreads();  // (the next row of this block stages its matrices again)
+    }
+}
+// One block per solve unit; see above.  A, b: k_jones_normal's, (nunits rows_per_unit, ...); j_old, j_new: (nunits, 4 nant),
+// two buffers; odd: the iteration's parity; solved[(unit 2 + c) nant + a].  A thread takes a (column, antenna).
+__global__ void __launch_bounds__(256)
+    k_jones_update(const double *__restrict__ A, const cplx<double> *__restrict__ b, const cplx<double> *__restrict__ j_old,
+                   cplx<double> *__restrict__ j_new, int64_t rows_per_unit, int nant, int odd, double *__restrict__ change,
+                   int *__restrict__ solved) {
+    __shared__ double wave_max[2][4];
+    const int64_t unit = blockIdx.x;
+    double md = 0.0, mn = 0.0;  // max |new - old|^2, max |new|^2 (the square root is monotone: taken once, at the end)
+    for (int i = threadIdx.x; i < 2 * nant; i += 256) {
+        const int c = i / nant, a = i - c * nant;
+        double s[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // A00, A11, Re A01, Im A01, b[0], b[1]
+        for (int64_t r = 0; r < rows_per_unit; ++r) {  // ascending time
+            const int64_t row = unit * rows_per_unit + r;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) s[q] += A[((row * 4 + q) * 2 + c) * nant + a];
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                s[4 + 2 * n] += b[((row * 2 + n) * 2 + c) * nant + a].re;
+                s[5 + 2 * n] += b[((row * 2 + n) * 2 + c) * nant + a].im;
+            }
+        }
+        const int64_t at0 = unit * 4 * nant + (int64_t)c * nant + a, at1 = at0 + 2 * (int64_t)nant;  // Gamma_a[0, c], [1, c]
+        const cplx<double> g0 = j_old[at0], g1 = j_old[at1];
+        cplx<double> n0 = g0, n1 = g1;
+        const double det = s[0] * s[1] - (s[2] * s[2] + s[3] * s[3]);
+        const bool ok = s[0] > 0.0 && s[1] > 0.0 && det > 0x1p-30 * (s[0] * s[1]);
+        if (ok) {  // A^-1 = [[A11, -A01], [-conj(A01), A00]] / det
+            const cplx<double> a01 = {s[2], s[3]}, b0 = {s[4], s[5]}, b1 = {s[6], s[7]};
+            const cplx<double> m0 = cmul(a01, b1), m1 = cmul(cconj(a01), b0);
+            n0 = {(s[1] * b0.re - m0.re) / det, (s[1] * b0.im - m0.im) / det};
+            n1 = {(s[0] * b1.re - m1.re) / det, (s[0] * b1.im - m1.im) / det};
+            if (!odd) {
+                n0 = {0.5 * (n0.re + g0.re), 0.5 * (n0.im + g0.im)};
+                n1 = {0.5 * (n1.re + g1.re), 0.5 * (n1.im + g1.im)};
+            }
+        }
+        j_new[at0] = n0;
+        j_new[at1] = n1;
+        solved[(unit * 2 + c) * nant + a] = ok ? 1 : 0;
+        const double d0r = n0.re - g0.re, d0i = n0.im - g0.im, d1r = n1.re - g1.re, d1i = n1.im - g1.im;
+        md = fmax(md, fmax(d0r * d0r + d0i * d0i, d1r * d1r + d1i * d1i));
+        mn = fmax(mn, fmax(n0.re * n0.re + n0.im * n0.im, n1.re * n1.re + n1.im * n1.im));
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        md = fmax(md, __shfl_xor(md, off, 64));
+        mn = fmax(mn, __shfl_xor(mn, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        wave_max[0][threadIdx.x >> 6] = md;
+        wave_max[1][threadIdx.x >> 6] = mn;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        md = fmax(fmax(wave_max[0][0], wave_max[0][1]), fmax(wave_max[0][2], wave_max[0][3]));
+        mn = fmax(fmax(wave_max[1][0], wave_max[1][1]), fmax(wave_max[1][2], wave_max[1][3]));
+        change[unit] = mn > 0.0 ? sqrt(md) / sqrt(mn) : 0.0;
+    }
+}
+// Queues one evaluation of the 2 x 2 normal systems (A, b) or, with chi2_part (nrows, nant), of the chi2 partials on `on`.
+// All device pointers; weights may be null.
+template <typename T>
+inline void launch_jones_normal(hipStream_t on, const cplx<T> *vis, const cplx<T> *data, const T *weights, const cplx<double> *jones,
+                                const GainPairs &gp, int64_t nrows, int64_t rows_per_unit, double *A, cplx<double> *b,
+                                double *chi2_part) {
+    const int nbls = (int)gp.nbls, nant = gp.nant;
+    const size_t lds = sizeof(cplx<double>) * 4 * (size_t)nant;
+    const int in_lds = lds <= GAIN_LDS_BYTES;
+    const dim3 grid((unsigned)cdiv(nant, 4), (unsigned)std::min<int64_t>(nrows, 65535));
+    if (chi2_part)
+        hipLaunchKernelGGL((k_jones_normal<T, true>), grid, dim3(256), in_lds ? lds : 0, on, vis, data, weights, jones,
+                           gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), gp.d_off.as<int>(), gp.d_inc.as<int>(), nrows, rows_per_unit,
+                           nbls, nant, in_lds, chi2_part, (cplx<double> *)nullptr);
+    else
+        hipLaunchKernelGGL((k_jones_normal<T, false>), grid, dim3(256), in_lds ? lds : 0, on, vis, data, weights, jones,
+                           gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), gp.d_off.as<int>(), gp.d_inc.as<int>(), nrows, rows_per_unit,
+                           nbls, nant, in_lds, A, b);
+}
+
+// ---------------------------------------------------------------------------------------------
 // The gain gradient of the Gauss-Newton product with gains (fv_gain_weight_rows, fv_sim_gain_weight_block; DESIGN.md
 // "Gains in the Gauss-Newton product").  The block, the pairs, the feeds and the gains' layout are the gain kernels'
 // above; dg is the gain direction in the gains' layout, or null.  With g1, g2, h1, h2, m, dm, U' and G' of

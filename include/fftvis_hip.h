@@ -180,6 +180,41 @@ int fv_gain_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbl
                   const int *ant2, int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
                   const void *weights, int weights_on_device, void *gains, int max_iter, double tol, int *niter_out,
                   double *change_out, double *chi2_ft_out, int *solved_out);
+/* fv_jones_normal_rows: one evaluation of the 2 x 2 normal systems of the Jones solve (the gather fv_jones_solve
+ * iterates).  The rows, the pairs and the layout of the matrices are fv_jones_residual_chi2's; vis, data, weights are
+ * read only; jones: (nrows, 2, 2, nant) complex128 whatever `precision` is.  A sample is used when w > 0 and
+ * ant1[k] != ant2[k]; a flagged datum is not read, and a baseline without a used sample is skipped before V is read.  For
+ * fixed V the least-squares problem in one antenna's matrix, the others held, is linear and splits into one Hermitian
+ * 2 x 2 system per measured feed (column) c of Gamma_a.  With G1 = Gamma[ant1[k]], G2 = Gamma[ant2[k]],
+ *   side 1 (a = ant2[k], c = x), Z[x', y] = sum_{y'} V[x', y'] conj(G1[y', y]):
+ *     A[i, j] += w[x, y] conj(Z[i, y]) Z[j, y]      b[i] += w[x, y] conj(Z[i, y]) d[x, y]      summed over y
+ *   side 0 (a = ant1[k], c = y), Y[x, y'] = sum_{x'} G2[x', x] V[x', y']:
+ *     A[i, j] += w[x, y] Y[x, i] conj(Y[x, j])      b[i] += w[x, y] Y[x, i] conj(d[x, y])      summed over x
+ * A_out: (nrows, 4, 2, nant) float64 = [A00, A11, Re A01, Im A01] x column x antenna; b_out: (nrows, 2, 2, nant)
+ * complex128, [i, column, a]; with the autos flagged fv_jones_residual_chi2's gjones[:, c, a] = 2 (A Gamma_a[:, c] - b).
+ * Every term is formed in fp64 from the inputs of `precision` and added in fp64 over the antenna's incidence list as
+ * gjones is added (one wave per (row, antenna), lane l takes entries l, l + 64, ..., an __shfl_xor tree) -- no
+ * floating-point atomics, the same input gives the same bits; an antenna without a used sample gets exactly 0 in both.
+ * A negative shape, nant < 1, an antenna index outside [0, nant) and a null pointer fail with FV_ERR_ARG before anything
+ * runs; nrows or nbls == 0 return zeros.  Host pointers. */
+int fv_jones_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                         const void *jones, const void *vis, const void *data, const void *weights, double *A_out, void *b_out);
+/* fv_jones_solve: the 2 x 2 matrices that minimise sum w |V' - d|^2, V' = G2^T V conj(G1), over the used samples for a
+ * FIXED polarized model V, by the alternating per-antenna solve (StefCal for full Jones matrices), entirely on the
+ * device.  fv_gain_solve argument for argument, without tpol (the rows hold 4 nbls values).  jones: host, complex128,
+ * (nfreqs, per_time ? ntimes : 1, 2, 2, nant); in: the start, out: the result.  Iteration i = 1, 2, ...: the systems of
+ * fv_jones_normal_rows at the current matrices, for time-constant matrices added over the unit's times in ascending
+ * order; a column is solved when A00 > 0, A11 > 0 and det = A00 A11 - |A01|^2 > 2^-30 A00 A11, else both of its entries
+ * keep their values; Gamma^[:, c] = A^-1 b by the closed form; Gamma <- Gamma^ for odd i and (Gamma^ + Gamma) / 2 for even
+ * i, written into the other of two buffers; change[unit] = max |new - old| / max |new| over the unit's 4 nant entries.
+ * The loop ends as fv_gain_solve's does.  niter_out, change_out, chi2_ft_out: as there, chi2 at the returned matrices;
+ * solved_out: int32 (units, 2, nant), per column and antenna, at the last iteration.  The counting pass, its messages
+ * and the argument checks are fv_gain_solve's; jones is untouched when the call fails.  nbls == 0: the start matrices,
+ * chi2 0, nothing solved, niter 0. */
+int fv_jones_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                   int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device, const void *weights,
+                   int weights_on_device, void *jones, int max_iter, double tol, int *niter_out, double *change_out,
+                   double *chi2_ft_out, int *solved_out);
 /* fv_weight_rows: the weighting step of a Gauss-Newton product on its own (the kernel pair fv_sim_weight_block queues).
  * parts: nparts = 1 .. 4 blocks P_0 .. P_{nparts-1}, each (nrows, row_len) complex of `precision`, C-contiguous -- the
  * parts of a tangent J p; weights: (nrows, row_len) real of `precision`, or NULL (every weight 1).  Per element, in that

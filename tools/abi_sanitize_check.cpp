@@ -321,6 +321,61 @@ int main() {
                              chi2, solved) == FV_OK);
         EXPECT(niter == 0 && gains[11] == 12 && change[1] == 0 && chi2[1] == 0 && solved[5] == 0);
     }
+    // and the Jones solve: the same checks without tpol; without a baseline both return before any device call
+    {
+        const int a[3] = {0, 1, 2}, low[3] = {0, -1, 2}, high[3] = {0, 1, 3};
+        int niter = -1, solved[12];
+        EXPECT(fv_jones_normal_rows(0, 3, 1, 3, 3, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, -1, 3, 3, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, -3, 3, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "fv_jones_normal_rows: negative shape") != nullptr);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 0, a, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 3, a, a, nullptr, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 3, a, a, v, v, v, nullptr, nullptr, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 3, a, a, v, v, v, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 3, nullptr, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 3, a, a, v, nullptr, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 3, a, a, v, v, nullptr, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 3, low, a, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(fv_jones_normal_rows(0, 2, 1, 3, 3, a, high, v, v, v, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "antenna index outside [0, nant)") != nullptr);
+        double A[48], b[48];
+        A[47] = b[47] = 7.0;
+        EXPECT(fv_jones_normal_rows(0, 2, 2, 0, 3, nullptr, nullptr, v, nullptr, nullptr, nullptr, A, b) == FV_OK);
+        EXPECT(A[47] == 0.0 && b[47] == 0.0);
+        EXPECT(fv_jones_solve(0, 3, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, -1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, -1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, -3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 0, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 0, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "fv_jones_solve: max_iter must be positive") != nullptr);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, -1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, __builtin_nan(""), &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "tol must be non-negative") != nullptr);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 2, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 2, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, -1, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 3, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "must be 0 or 1") != nullptr);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, nullptr, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, nullptr, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, nullptr, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, nullptr, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, nullptr, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, nullptr, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, a, 0, v, 0, nullptr, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, low, a, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(fv_jones_solve(0, 2, 1, 1, 3, 3, a, high, 0, v, 0, v, 0, nullptr, 0, v, 5, 1e-8, &niter, v, v, solved) == FV_ERR_ARG);
+        EXPECT(niter == -1);
+        double jones[48], change[2] = {7, 7}, chi2[2] = {7, 7};
+        for (int i = 0; i < 48; ++i) jones[i] = i + 1;
+        for (int i = 0; i < 12; ++i) solved[i] = 7;
+        EXPECT(fv_jones_solve(0, 1, 1, 2, 0, 3, nullptr, nullptr, 1, nullptr, 0, nullptr, 0, nullptr, 0, jones, 5, 0.0, &niter, change,
+                              chi2, solved) == FV_OK);
+        EXPECT(niter == 0 && jones[47] == 48 && change[1] == 0 && chi2[1] == 0 && solved[11] == 0);
+    }
     // a call that gets past the argument checks reports the missing device as a HIP error, not a crash
     if (ndev == 0) {
         EXPECT(fv_sim_create(&h, 0, 2, 1e-6, 2.0, 1) == FV_ERR_HIP && h == nullptr);

@@ -19,6 +19,7 @@
     gauss_newton    forward composed fused fused_device                             C3, 8 channels  (--case, --gains,
                                                                                     --d-gains; beam_coefs: --config C5)
     gain_solve      forward solve solve_with_forward gauss_newton_products          C3, 8 channels
+    jones_solve     forward solve solve_with_forward jones_chi2_steps               C3, 8 channels
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -55,7 +56,9 @@ on the block's shape, six times each, alternating.  gain_solve: the gains-only s
 per call (every value is the call's wall clock divided by the time steps, as everywhere) -- ``solve`` is
 simulate_vis_gain_solve on a resident model with resident data and weights, ``solve_with_forward`` the same from the sky (one
 forward, then the iterations), ``gauss_newton_products`` as many gains-only products of simulate_vis_gain_gauss_newton, each
-of which reruns the forward (``--profile solve`` for a kernel trace).  A flag of another family is an error.
+of which reruns the forward (``--profile solve`` for a kernel trace).  jones_solve: the same for the 2 x 2 matrices --
+``solve`` and ``solve_with_forward`` call simulate_vis_jones_solve with no sample flagged, ``jones_chi2_steps`` is as many
+calls of simulate_vis_jones_chi2 with its gradient, each of which reruns the forward.  A flag of another family is an error.
 tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
 
 import argparse
@@ -576,6 +579,62 @@ def gain_solve(a, fv, cfg, rng):
     return head, calls
 
 
+def jones_solve(a, fv, cfg, rng):
+    """The Jones solve against a fixed model: GAIN_SOLVE_ITERATIONS iterations of ``simulate_vis_jones_solve`` on a resident
+    model with resident data and weights (host to host: the matrices go up and come back), next to as many steps of what
+    such a fit costs without it, ``simulate_vis_jones_chi2`` with its gradient, each of which reruns the forward.  No sample
+    is flagged: the solve uses the cross-hands.  ``--profile solve`` is one solve on a resident model, for a kernel trace."""
+    import torch
+
+    p = cfg["precision"]
+    cdt, rdt = (np.complex64, np.float32) if p == 1 else (np.complex128, np.float64)
+    nums = list(cfg["ants"])
+    nant = len(nums)
+    jshape = (nant, 2, 2, a.nfreq)
+    j_true = 0.1 * (rng.normal(size=jshape) + 1j * rng.normal(size=jshape))
+    j_true[:, 0, 0] += 1
+    j_true[:, 1, 1] += 1
+    state = {}
+
+    def resident():  # the model from one forward, data = the model under the true matrices plus noise
+        if not state:
+            nbls = len(cfg["baselines"])
+            zeros = np.zeros((a.nfreq, a.ntimes, 2, 2, nbls), dtype=cdt)
+            _, _, model = fv.simulate_vis_jones_solve(zeros, **cfg, max_iter=1, tol=0.0, return_model=True)
+            G = torch.from_numpy(j_true).cuda()  # [a, i, j, f]
+            a1 = torch.tensor([nums.index(b[0]) for b in cfg["baselines"]], device="cuda")
+            a2 = torch.tensor([nums.index(b[1]) for b in cfg["baselines"]], device="cuda")
+            # V'[f, t, x, y, k] = sum conj(G1[y', y]) G2[x', x] V[x', y']
+            data = torch.einsum("kbdf,kacf,ftabk->ftcdk", G[a1].conj(), G[a2], model.to(G.dtype))
+            noise = 0.05 * data.abs().mean()
+            data = (data + noise * torch.randn_like(data)).to(model.dtype).contiguous()
+            w = torch.ones(model.shape, dtype=getattr(torch, np.dtype(rdt).name), device="cuda")
+            torch.cuda.synchronize()
+            state.update(model=model, data=data, w=w)
+        return state
+
+    def solve():
+        s = resident()
+        return fv.simulate_vis_jones_solve(s["data"], **dict(cfg, fluxes=None), weights=s["w"], model=s["model"],
+                                           max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    def solve_with_forward():  # the same from the sky: one forward, then the iterations
+        s = resident()
+        return fv.simulate_vis_jones_solve(s["data"], **cfg, weights=s["w"], max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    def chi2_steps():
+        s = resident()
+        eye = np.zeros(jshape, dtype=cdt)
+        eye[:, 0, 0] = eye[:, 1, 1] = 1
+        for _ in range(GAIN_SOLVE_ITERATIONS):
+            fv.simulate_vis_jones_chi2(s["data"], **cfg, jones=eye, weights=s["w"], wrt="jones")
+
+    calls = {"forward": lambda: fv.simulate_vis(**cfg), "solve": solve, "solve_with_forward": solve_with_forward,
+             "jones_chi2_steps": chi2_steps}
+    head = {"config": a.config, "precision": p, "polarized": True, "iterations": GAIN_SOLVE_ITERATIONS}
+    return head, calls
+
+
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
 #          ratios {key: (pass, pass it is divided by -- or a tuple of passes, for their sum)})
 FAMILIES = {
@@ -603,6 +662,8 @@ FAMILIES = {
         "fused_device_over_composed": ("fused_device", "composed"), "fused_device_over_forward": ("fused_device", "forward")}),
     "gain_solve": (gain_solve, "C3", 8, (), "runs", {
         "solve_over_forward": ("solve", "forward"), "products_over_solve": ("gauss_newton_products", "solve")}),
+    "jones_solve": (jones_solve, "C3", 8, (), "runs", {
+        "solve_over_forward": ("solve", "forward"), "chi2_steps_over_solve": ("jones_chi2_steps", "solve")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
              "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False, "jones": False}  # and their defaults
