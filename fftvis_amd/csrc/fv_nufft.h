@@ -33,6 +33,7 @@
 #pragma once
 
 #include "fv_eskernel.h"
+#include "fv_ydirect.h"
 
 #include <hip/hip_ext.h>
 
@@ -2466,6 +2467,13 @@ struct InterpArgs {
     const void *bt_d;
     int bt_ndir;
     int64_t bt_d_stride, bt_out_stride;
+    // Values variant (k_interp<.., VALS>; Nufft3::arm_ydirect): the transform's value at the item's target (and, packed
+    // runs, at its mirror image) was summed directly by k_ydirect; yd_vals holds yd_nslices partial sums (one per row
+    // slice, yd_sstride elements apart) per (frequency, transform, evaluation point), yd_map[2 item + side] the point.
+    const cplx<double> *yd_vals;
+    const int *yd_map;
+    int yd_nslices;
+    int64_t yd_npts, yd_sstride;
 };
 
 // Bessel function of the first kind and integer order k >= 0 by its power series, (x / 2)^k / k! sum_m (-x^2 / 4)^m /
@@ -2532,8 +2540,10 @@ __device__ inline cplx<double> basis_weight(cplx<T> c1, cplx<T> c2) {
 // GRAD (InterpArgs::gs), TANGENT (InterpArgs::tg_w) and BTAN (InterpArgs::bt_d) are epilogues of their own passes, compile-time
 // for the same reason.  BPOS: the position passes through basis beams (Sim::run_basis_position_adjoint / _tangent) -- 1 the
 // gradient epilogue, 2 the tangent epilogue, each with the basis weights applied in the gather (InterpArgs::gs / tg_w).
+// VALS: no footprint at all -- the values come from k_ydirect's partial sums (InterpArgs::yd_vals), everything after them
+// (both dimensions' kernel transforms, post-phase, unpacking, the member loop) is the plain gather's.
 template <typename T, int DIM, bool HERM, int NR, bool ZD = false, bool WT = false, bool GRAD = false, bool TANGENT = false,
-          bool BTAN = false, int BPOS = 0>
+          bool BTAN = false, int BPOS = 0, bool VALS = false>
 __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
     const cplx<T> *__restrict__ grid, int64_t N, const T *__restrict__ bt0,
     const T *__restrict__ bt1, const T *__restrict__ bt2, const int *__restrict__ bl_idx,
@@ -2628,10 +2638,10 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
     // Both sides' footprints first -- origins, this lane's kernel values, the row offsets (with a column plan: NR table
     // lookups per side) -- so that the two sides' lookups travel together, then the sides' row loads: a wave's time is
     // its chain of dependent round trips (PMC: 65 % of a gather wave's 31 us is spent waiting)
-    int j0s[NSIDE][DIM], roffs[NSIDE][NR], gcols[NSIDE];
-    T kvs[NSIDE][DIM];
+    int j0s[NSIDE][DIM], roffs[NSIDE][NR], gcols[NSIDE] = {};
+    T kvs[NSIDE][DIM] = {};
 #pragma unroll
-    for (int side = 0; side < NSIDE; ++side) {
+    for (int side = 0; side < (VALS ? 0 : NSIDE); ++side) {
         const double sgn = side ? -1.0 : 1.0;
         int (&j0)[DIM] = j0s[side];
         T (&kv)[DIM] = kvs[side];  // this lane's kernel value along each dimension (lane = footprint offset)
@@ -2676,13 +2686,23 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
         const int gcol = gcols[side];
         T k1[NR];  // row weights: zero beyond the footprint (kv of lanes >= w is zero)
 #pragma unroll
-        for (int r = 0; r < NR; ++r) k1[r] = __shfl(kv[1], lane_base + r, 64);
+        for (int r = 0; r < (VALS ? 0 : NR); ++r) k1[r] = __shfl(kv[1], lane_base + r, 64);
         const double pis = side ? -pi_ : pi_;  // exp(i (-s) . x_c) = conj
         constexpr int RUNROLL = HERM ? NVAL : 1;  // HERM: two transforms, compile-time indexed results
 #pragma unroll RUNROLL
         for (int r = 0; r < (HERM ? NVAL : a.tpol); ++r) {
             const cplx<T> *plane = grid + ((int64_t)fg * a.tpol + r) * (zd ? plane_sz * a.zd_n : plane_sz) + gcol;
             T sr = T(0), si = T(0);
+            if constexpr (VALS) {  // the row slices' partial sums, in order (every lane of the group reads the same)
+                const cplx<double> *vp = a.yd_vals + ((int64_t)fg * a.tpol + r) * a.yd_npts + a.yd_map[2 * ui0 + side];
+                double xr = 0.0, xi = 0.0;
+                for (int s = 0; s < a.yd_nslices; ++s) {
+                    xr += vp[(int64_t)s * a.yd_sstride].re;
+                    xi += vp[(int64_t)s * a.yd_sstride].im;
+                }
+                sr = (T)xr;
+                si = (T)xi;
+            }
             if (zd) {
                 // the zd_n planes of this transform, each gathered like a 2-D transform and turned by its phase
                 // exp(i (k - zd_n / 2) theta_z) (at the mirror target: -theta_z); the rotation walks from plane to plane
@@ -2710,7 +2730,7 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                 sr = (T)ar_;
                 si = (T)ai_;
             }
-            for (int ro = 0; ro < (zd ? 0 : nouter); ++ro) {
+            for (int ro = 0; ro < (zd || VALS ? 0 : nouter); ++ro) {
                 T k2 = T(1);
                 const cplx<T> *slab = plane;
                 if (DIM == 3) {
@@ -2729,12 +2749,14 @@ __global__ __launch_bounds__(INTERP_THREADS) void k_interp(
                 sr += tr * k2;
                 si += ti * k2;
             }
-            sr *= kv[0];
-            si *= kv[0];
+            if constexpr (!VALS) {
+                sr *= kv[0];
+                si *= kv[0];
 #pragma unroll
-            for (int off = GROUP / 2; off > 0; off >>= 1) {
-                sr += __shfl_xor(sr, off, 64);
-                si += __shfl_xor(si, off, 64);
+                for (int off = GROUP / 2; off > 0; off >>= 1) {
+                    sr += __shfl_xor(sr, off, 64);
+                    si += __shfl_xor(si, off, 64);
+                }
             }
             const double vr0 = (double)sr * pr - (double)si * pis;
             const double vi0 = (double)sr * pis + (double)si * pr;
@@ -3230,6 +3252,50 @@ class Nufft3 {
         col_omask_nblk = omask_nblk;
         col_out_cells = 0;
     }
+    // Direct y sums (fv_ydirect.h; 2-D, fp64, stand-alone gather, no gang launch): armed by the caller before spread() with
+    // the tables of its plan (Sim::ydirect_plan) for the geometry and column plan in force.  The spread then takes a
+    // table of ones for y, fft() stops after the x-pass and sums the targets' values from B into yd_vals (this plan's
+    // own: free-running lanes each have theirs), and interp() runs the values variant of the gather.  nullptr: off.
+    bool yd_on = false;
+    YdArgs yd_args{};
+    const int *yd_map = nullptr;
+    double yd_cells = 0, yd_pairs = 0;  // cells of B the sums read / (point, row) pairs, per transform
+    DevBuf yd_vals, yd_ones;
+    int yd_ones_n = 0;
+    const double *yd_scale = nullptr;
+    void arm_ydirect(const YdArgs *a, const int *map, double b_cells, const double *scale_dev = nullptr) {
+        yd_on = a != nullptr && sizeof(T) == 8 && dim == 2;
+        if (!yd_on) return;
+        yd_args = *a;
+        yd_map = map;
+        yd_scale = scale_dev;
+        yd_cells = b_cells;
+        yd_pairs = (double)a->npts * geo.d[1].na;
+    }
+    // slices of the rows for a launch over nfg frequencies: enough workgroups to fill the chip a few times over
+    static void yd_slices(int na_y, int nwg, int nfg, int &rps, int &nslices) {
+        const int want = (int)std::min<int64_t>(16, std::max<int64_t>(1, cdiv(2048, std::max(1, nwg * nfg))));
+        rps = (int)cdiv(cdiv(na_y, want), YD_RT) * YD_RT;
+        nslices = (int)cdiv(na_y, rps);
+    }
+    static size_t yd_vals_bytes(int na_y, int nwg, int nfg, int tg, int64_t npts) {
+        int rps, ns;
+        yd_slices(na_y, nwg, nfg, rps, ns);
+        return sizeof(cplx<double>) * (size_t)ns * nfg * tg * (size_t)npts;
+    }
+    const T *spread_dec_y() {  // the y table the spread applies: the inner deconvolution, or ones under direct y sums
+        if (!yd_on) return dec_cur[1];
+        const int n = geo.d[1].na;
+        if (yd_ones_n < n) {
+            if (yd_ones.p) FV_HIP(hipStreamSynchronize(stream));  // (an earlier launch may still read the smaller table)
+            const int cap = std::max(n, 16384);
+            yd_ones.reserve(sizeof(double) * (size_t)cap);
+            hipLaunchKernelGGL(k_yd_ones, dim3((unsigned)cdiv(cap, 256)), dim3(256), 0, stream, yd_ones.as<double>(), cap);
+            yd_ones_n = cap;
+        }
+        return reinterpret_cast<const T *>(yd_ones.p);
+    }
+    void ydirect_sum(int ntrans, const cplx<T> *B);
     int ypass_cols_log() const {  // log2 of the columns a y-pass workgroup owns (column mode)
         int tpr, rpw;
         rowfft_shape(geo.d[1], true, tpr, rpw);
@@ -3258,6 +3324,9 @@ class Nufft3 {
     }
     int xcols() const { return col_tab ? col_ncc : geo.d[0].nos(); }  // columns of B / rows of C per transform
     int b_block_log_public() const { return b_block_log(); }
+    // columns and row pitch of B with a column plan of ncc compact columns armed (0: none), whatever is armed now
+    int xcols_with(int ncc) const { return ncc ? ncc : geo.d[0].nos(); }
+    int64_t b_pitch_with(int ncc) const { return y_reads_columns() ? (xcols_with(ncc) + 7) / 8 * 8 : xcols_with(ncc); }
     // (3-D with the direct third dimension: every (transform, z) plane is a 2-D transform read by the same targets)
     bool columns_possible() const { return (dim == 2 || zdirect) && b_block_log() != 0 && y_reads_columns() && !fused_possible(); }
     bool fused_possible() const;
@@ -3685,6 +3754,7 @@ class Nufft3 {
         const DimGeom &x = geo.d[0], &y = geo.d[1], &z = geo.d[2];
         const double zin = dim > 2 ? z.na : 1;
         auto f = [](const DimGeom &g) { return 5.0 * g.n2 * std::log2((double)g.n2); };
+        if (yd_on) return zin * y.na * f(x) + 4.0 * yd_cells + 8.0 * yd_pairs;  // direct y sums: contraction + one complex FMA per (point, row)
         double c = zin * y.na * f(x) + zin * (double)xcols() * f(y);
         if (dim > 2 && !zdirect) c += (double)x.nos() * y.nos() * f(z);
         return c;
@@ -3736,6 +3806,8 @@ int Nufft3<T>::launch_spread(int ntrans, int tbegin, hipEvent_t e0, hipEvent_t e
         // the horizon cut), lane per cell on sparse grids; FFTVIS_HIP_SPREAD_CELL = 1 / 0 forces one
         const char *force_cell = std::getenv("FFTVIS_HIP_SPREAD_CELL");
         const bool dense = (double)M >= 3.0 * (double)geo.nbin[0] * (double)geo.nbin[1];
+        FV_REQUIRE(!yd_on || !mate, "direct y sums: no gang launches");
+        const T *dec_y = spread_dec_y();
         auto kern = k_spread2d<T, TCH>;
         if constexpr (TCH >= 8) {
             if (force_cell ? std::atoi(force_cell) == 0 : dense) kern = k_spread2d_cg<T, TCH>;
@@ -3749,7 +3821,7 @@ int Nufft3<T>::launch_spread(int ntrans, int tbegin, hipEvent_t e0, hipEvent_t e
                               (const int *)i0s.as<int>(), (const T *)kw.as<T>(),
                               (const int *)bin_start.as<int>(),
                               (const cplx<T> *)strengths.as<cplx<T>>() + strengths_off, ntrans, tbegin,
-                              dec_cur[0], dec_cur[1],
+                              dec_cur[0], dec_y,
                               buf0.as<cplx<T>>(), x.na, y.na, geo.nbin[0], ker.w,
                               order_ptr, nchunk, sm);
     } else {
@@ -4023,6 +4095,7 @@ double Nufft3<T>::fft_traffic_cells() const {
     const double xo = col_tab ? (double)col_ncc : (double)x.no;          // columns stored by the x-pass (column plan: those a target reads)
     const double ain = row_ext_ptr ? (double)order_cells : (double)x.na * y.na;  // cells of A inside the source disc
     double c = zin * (ain + xo * y.na);                                  // x-pass
+    if (yd_on) return c + yd_cells;                                      // direct y sums: the cells of B they read, no C
     if (!y_reads_columns()) c += zin * 2.0 * x.no * y.na;                 // transpose
     c += zin * (xo * y.na + (last_fft_fused ? 0.0 : col_tab && col_omask && col_out_cells > 0 ? col_out_cells : xo * y.no));  // y-pass (no C when fused)
     if (dim > 2 && !zdirect) c += (double)x.no * y.no * (z.na + z.no);   // z-pass
@@ -4054,6 +4127,13 @@ void Nufft3<T>::fft(int ntrans, Nufft3 *mate) {
     first_pass_ext = nullptr;
     std::swap(cur, oth);
     std::swap(cur1, oth1);
+    if (yd_on) {  // direct y sums: no y-pass and no grid C; the gather's values variant reads yd_vals
+        FV_REQUIRE(!mate && !fused_active && dim == 2, "direct y sums: 2-D, stand-alone gather, no gang launch");
+        ydirect_sum(ntrans, cur);
+        grid_out = cur;
+        last_fft_fused = false;
+        return;
+    }
     if (y_reads_columns()) {
         // the y-pass reads rpw adjacent columns of B at once (32-128 B segments; neighbouring workgroups share lines),
         // which fuses the transpose:  B -> C [p][no_x][no_y]; the xp - no_x padding columns of a
@@ -4084,6 +4164,42 @@ void Nufft3<T>::fft(int ntrans, Nufft3 *mate) {
         mate->last_fft_fused = fused_active;
     }
     fused_active = false;
+}
+
+// The targets' values from the x-pass output B (k_ydirect): one launch over (group ranges, frequencies, row slices).
+template <typename T>
+void Nufft3<T>::ydirect_sum(int ntrans, const cplx<T> *B) {
+    if constexpr (sizeof(T) == 8) {
+        const DimGeom &y = geo.d[1];
+        YdArgs a = yd_args;
+        const int tg = ntrans / std::max(1, a.nfg);
+        FV_REQUIRE(a.nfg >= 1 && tg * a.nfg == ntrans && (tg == 1 || tg == 2 || tg == 4), "direct y sums: 1, 2 or 4 transforms per frequency");
+        const int blk = b_block_log();
+        FV_REQUIRE(a.na_y == y.na && a.xp == (int)b_pitch() && a.blk == (blk ? blk : 2) && a.w == ker.w,
+                   "direct y sums: the tables were built for another geometry");
+        a.plane = (int64_t)y.na * b_pitch();
+        a.blk_stride = blk ? ((int64_t)y.na << blk) : 4;
+        a.row_stride = blk ? (1 << blk) : b_pitch();
+        yd_slices(y.na, a.nwg, a.nfg, a.rps, a.nslices);
+        const size_t need = sizeof(cplx<double>) * (size_t)a.nslices * a.nfg * tg * (size_t)a.npts;
+        if (yd_vals.cap < need) {  // (the caller reserves it before the run: never in the middle of one)
+            FV_HIP(hipStreamSynchronize(stream));
+            yd_vals.reserve(need);
+        }
+        yd_args.rps = a.rps;
+        yd_args.nslices = a.nslices;
+        const size_t smem = yd_smem_bytes(tg);
+        const dim3 grid((unsigned)a.nwg, (unsigned)a.nfg, (unsigned)a.nslices);
+        auto kern = tg == 1 ? k_ydirect<1> : tg == 2 ? k_ydirect<2> : k_ydirect<4>;
+        // per device, so not cached in a process-wide flag (handles may sit on several GPUs)
+        FV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        hipLaunchKernelGGL(kern, grid, dim3(YD_THREADS), smem, stream, reinterpret_cast<const cplx<double> *>(B), yd_scale, a,
+                           yd_vals.as<cplx<double>>());
+    } else {
+        (void)ntrans;
+        (void)B;
+        FV_REQUIRE(false, "direct y sums: fp64 only");
+    }
 }
 
 template <typename T>
@@ -4348,6 +4464,20 @@ void Nufft3<T>::interp(int64_t N, const T *btx, const T *bty, const T *btz, cons
         if (bpos == 2) a.tg_w = tan->w;
         kern = bpos == 1 ? interp_bpos_kernel<T, 1>(gdim, herm != 0, r9, zd, wt != nullptr)
                          : interp_bpos_kernel<T, 2>(gdim, herm != 0, r9, zd, wt != nullptr);
+    }
+    if (yd_on) {  // direct y sums: the values variant of the plain epilogues (k_interp<.., VALS>)
+        FV_REQUIRE(gdim == 2 && !zd && !wt && !basis && !tan && !a.gs && !a.bt_d && (herm || tpol <= 4),
+                   "direct y sums: plain 2-D forward gathers only");
+        if constexpr (sizeof(T) == 8) {
+            constexpr bool F = false;
+            a.yd_vals = yd_vals.as<cplx<double>>();
+            a.yd_map = yd_map;
+            a.yd_nslices = yd_args.nslices;
+            a.yd_npts = yd_args.npts;
+            a.yd_sstride = (int64_t)nfg * tpol * yd_args.npts;
+            a.ctab = nullptr;
+            kern = herm ? k_interp<T, 2, true, 9, F, F, F, F, F, 0, true> : k_interp<T, 2, false, 9, F, F, F, F, F, 0, true>;
+        }
     }
     hipLaunchKernelGGL(kern, grid, dim3(INTERP_THREADS), 0, stream, (const cplx<T> *)grid_out, N, bt[0], bt[1], bt[2],
                        bl_idx, flip, scale_dev, a, ker, out, coef, ant1, ant2, ustart, upairs);

@@ -3519,7 +3519,7 @@ class Sim : public SimBase {
         std::unique_ptr<DevBuf> idx0, flip0;
         // Redundant baselines: runs of the (u, v)-ordered list whose sign-adjusted vectors agree (build_unique) are ONE
         // target of the gather.  h_idx / h_flip: the list as visited (host copy); ustart: nu + 1 run starts (device).
-        std::vector<int> h_idx, h_ustart;
+        std::vector<int> h_idx, h_ustart, h_upairs;  // (h_upairs: host copy of upairs, for the direct y sums' point map)
         std::vector<signed char> h_flip;
         bool sorted = false;  // the list is visited in (u, v) order
         std::unique_ptr<DevBuf> ustart, upairs;  // run starts; (packed runs) pairs of runs b / -b that share one gather item
@@ -3991,6 +3991,7 @@ class Sim : public SimBase {
         p.ustart.reset();
         p.upairs.reset();
         p.upairs_herm = -1;  // (pair_mirror_runs starts over on the new runs)
+        p.h_upairs.clear();
         p.h_ustart.clear();
         p.nu = p.nitems = p.n;
         ++targets_serial;  // column plans were built from the old runs
@@ -4021,6 +4022,7 @@ class Sim : public SimBase {
         if (p.upairs_herm == (want ? nd : 0)) return;
         p.upairs_herm = want ? nd : 0;
         p.upairs.reset();
+        p.h_upairs.clear();
         p.nitems = p.nu;
         ++targets_serial;
         if (!want) return;
@@ -4070,6 +4072,7 @@ class Sim : public SimBase {
         p.upairs.reset(new DevBuf());
         upload(*p.upairs, items.data(), sizeof(int) * items.size(), 0);
         p.nitems = (int64_t)items.size() / 2;
+        p.h_upairs = std::move(items);
     }
 
     // Column plan (Nufft3::arm_columns): which columns of the transform's first dimension the targets of one (frequency
@@ -4085,6 +4088,7 @@ class Sim : public SimBase {
         double h, btc;
         bool both;
         DevBuf tab, xtab;  // the gather's table (1 + compact column) and the x-pass's (1 + element index of that column)
+        std::vector<int> h_tab;  // host copy of tab (Sim::ydirect_plan locates its columns through it)
         int yna = 0, blk = 0;
         int ncc = 0;
         bool use = false;
@@ -4145,6 +4149,7 @@ class Sim : public SimBase {
         c->blk = n0->b_block_log_public();
         if (c->use) {
             upload(c->tab, tab.data(), sizeof(int) * tab.size(), 0);
+            c->h_tab = tab;
             // the x-pass stores compact column cc of a row at element (cc >> b) (na_y << b) + (cc & (2^b - 1)) of the row's
             // blocked output (RowDifArgs::out_blk): tabulated, so that a store index is one subtraction
             {
@@ -4177,6 +4182,207 @@ class Sim : public SimBase {
         }
         col_plans.push_back(std::move(c));
         return col_plans.back().get();
+    }
+
+    // Direct y sums (fv_ydirect.h): the tables of one (frequency group, beam pair) for the geometry and column plan in
+    // force.  The evaluation points -- every gather item's target and, packed runs, its mirror image -- are grouped by u
+    // and then by v with the redundant-baseline tolerance (dedup_tol; compared with a cluster's first entry, so clusters
+    // cannot drift), whatever FFTVIS_HIP_NO_TARGET_DEDUP says: the points, their groups and the decision below depend on
+    // the geometry alone, and a run that gathers every baseline by itself maps its items to the same points.  A group's
+    // first u fixes its footprint (origin and x-weights per frequency, placed as k_interp places them); its columns
+    // are located through the column plan's table when one is armed, else through out_pos.  Contiguous groups form the
+    // work ranges of k_ydirect: at most YD_NG groups, 1024 points and as many distinct column blocks as its LDS tile holds.
+    // Taken (use) when the points' (point, row) pairs are at most ydirect_gate() times the butterflies of the y-pass they
+    // replace, columns x n2_y / 2 x log2 n2_y, on grids of the column plan's size class; FFTVIS_HIP_YDIRECT=1 takes it
+    // wherever the tables can be built, 0 never.  Host arithmetic, once per (targets, group geometry); kept for later runs.
+    struct YPlan {
+        int64_t serial;
+        int pair, fa, fb;
+        const ColPlan *cp;
+        int herm, blk, xp, w;
+        int xn2, xno, xsP, xcnt, yna, yn2;
+        double xh, xbtc, yh, ybtc;
+        bool built = false, use = false;  // use: by the geometric rule (the switch is read per run)
+        YdArgs a{};
+        double cells = 0;  // cells of B per transform the sums read (mean over the frequencies)
+        DevBuf wg, blkcnt, blkid, cref, xw, ptv, ptg, map;
+    };
+    std::vector<std::unique_ptr<YPlan>> y_plans;
+    std::vector<YPlan *> y_plan_of;  // [group * pairs + pair] of the current run (class 0)
+    static double ydirect_gate() { return 1.0; }  // C3: 0.59 (taken); the same antennas scattered: about 2.3 (kept on the FFT y-pass)
+    YPlan *ydirect_plan(int pi, const Pair &pr, int fa, int fb, Nufft3<T> *n0, const ColPlan *cp, bool forced) {
+        const DimGeom &x = n0->geo.d[0], &y = n0->geo.d[1];
+        const int w = n0->ker.w, blkB = n0->b_block_log_public(), blk = blkB ? blkB : 2;
+        const int xp = (int)n0->b_pitch_with(cp && cp->use ? cp->ncc : 0);
+        for (auto &c : y_plans)
+            if (c->serial == targets_serial && c->pair == pi && c->fa == fa && c->fb == fb && c->cp == cp && c->herm == pr.herm &&
+                c->blk == (blkB ? blkB : -2) && c->xp == xp && c->w == w && c->xn2 == x.n2 && c->xno == x.no && c->xsP == x.sP() &&
+                c->xcnt == x.cnt() && c->yna == y.na && c->yn2 == y.n2 && c->xh == x.h && c->xbtc == x.btc && c->yh == y.h &&
+                c->ybtc == y.btc)
+                return c.get();
+        std::unique_ptr<YPlan> c(new YPlan{targets_serial, pi, fa, fb, cp, pr.herm, blkB ? blkB : -2, xp, w, x.n2, x.no, x.sP(), x.cnt(),
+                                           y.na, y.n2, x.h, x.btc, y.h, y.btc});
+        y_plans.push_back(std::move(c));
+        YPlan *yp = y_plans.back().get();
+        const bool dbg = std::getenv("FFTVIS_HIP_DEBUG_YDIRECT") != nullptr;
+        auto skip = [&](const char *why) {
+            if (dbg) std::fprintf(stderr, "ydirect plan pair %d channels [%d, %d): not built: %s\n", pi, fa, fb, why);
+            return yp;
+        };
+        const int nfg = fb - fa, BE = 1 << blk, sides = pr.herm ? 2 : 1;
+        const int64_t N = !pr.h_upairs.empty() ? (int64_t)pr.h_upairs.size() / 2 : !pr.h_ustart.empty() ? (int64_t)pr.h_ustart.size() - 1 : pr.n;
+        if (N == 0 || nfg == 0 || w > MAX_W || (pr.herm && (x.btc != 0.0 || y.btc != 0.0))) return skip("no items, or a packed run off centre");
+        // the items' evaluation points
+        const size_t NP = (size_t)N * sides;
+        std::vector<double> pu(NP), pv(NP);
+        for (int64_t i = 0; i < N; ++i) {
+            const int64_t ui = !pr.h_upairs.empty() ? pr.h_upairs[2 * i] : i;
+            const int64_t kl = pr.h_ustart.empty() ? ui : pr.h_ustart[ui];
+            const int64_t k = pr.h_idx[kl];
+            const double sg = pr.h_flip[kl] ? -1.0 : 1.0;
+            for (int sd = 0; sd < sides; ++sd) {
+                const double s2 = sd ? -sg : sg;
+                pu[(size_t)i * sides + sd] = s2 * (double)(T)h_bls[k];
+                pv[(size_t)i * sides + sd] = s2 * (double)(T)h_bls[(size_t)nbls + k];
+            }
+        }
+        const double tol = std::max(dedup_tol(), 0.0);
+        std::vector<int> ord(NP), grp(NP), map(2 * (size_t)N, 0);
+        for (size_t i = 0; i < NP; ++i) ord[i] = (int)i;
+        std::sort(ord.begin(), ord.end(), [&](int p, int q) { return pu[p] < pu[q] || (pu[p] == pu[q] && (pv[p] < pv[q] || (pv[p] == pv[q] && p < q))); });
+        std::vector<double> gu;  // a group's u: its first entry's
+        for (size_t i = 0; i < NP; ++i) {
+            if (gu.empty() || pu[ord[i]] - gu.back() > tol) gu.push_back(pu[ord[i]]);
+            grp[ord[i]] = (int)gu.size() - 1;
+        }
+        const int G = (int)gu.size();
+        std::sort(ord.begin(), ord.end(), [&](int p, int q) { return grp[p] < grp[q] || (grp[p] == grp[q] && (pv[p] < pv[q] || (pv[p] == pv[q] && p < q))); });
+        std::vector<double> ptv;
+        std::vector<int> ptg, gstart(G + 1, 0);
+        for (size_t i = 0; i < NP; ++i) {
+            const int q = ord[i];
+            if (ptv.empty() || ptg.back() != grp[q] || pv[q] - ptv.back() > tol) {
+                ptv.push_back(pv[q]);
+                ptg.push_back(grp[q]);
+                ++gstart[grp[q] + 1];
+            }
+            map[(size_t)(q / sides) * 2 + (q % sides)] = (int)ptv.size() - 1;
+        }
+        for (int g = 0; g < G; ++g) gstart[g + 1] += gstart[g];
+        const int64_t npts = (int64_t)ptv.size();
+        // (the rule below cannot hold even if every group's columns are distinct: no tables)
+        if (!forced && (double)npts * y.na > ydirect_gate() * ((double)G * w) * 0.5 * y.n2 * std::log2((double)y.n2)) return skip("too many points per u");
+        if (blk > 4) return skip("column blocks wider than 16 elements");
+        // footprints per (frequency, group): compact (or stored) column of every footprint cell, x-weights
+        const int P = x.sP(), cnt = x.cnt(), stride = x.nos(), ncols = n0->xcols_with(cp && cp->use ? cp->ncc : 0);
+        const double beta = n0->ker.beta, c4 = n0->ker.c;
+        std::vector<int> col((size_t)nfg * G * w);
+        std::vector<double> xw((size_t)nfg * G * w);
+        for (int fg = 0; fg < nfg; ++fg) {
+            const double sc = freqs[fa + fg];
+            for (int g = 0; g < G; ++g) {
+                const double sv = sc * gu[g], th = x.h * (sv - sc * x.btc);
+                const double e = th * x.n2 * (0.5 / M_PI) + 0.5 * x.no;
+                const int j = std::max(0, std::min(x.no - w, (int)std::ceil(e - 0.5 * w)));
+                for (int q = 0; q < w; ++q) {
+                    const int pos = out_pos(std::min(j + q, x.no - 1), P, cnt);
+                    int cc = pos;
+                    if (cp && cp->use) {
+                        const int t = cp->h_tab[(size_t)fg * stride + pos];
+                        if (t == 0) return skip("a footprint column the column plan left out");  // (never met; the FFT y-pass then)
+                        cc = t - 1;
+                    }
+                    if (cc < 0 || cc >= ncols || cc >= xp) return skip("a column outside B");
+                    col[((size_t)fg * G + g) * w + q] = cc;
+                    xw[((size_t)fg * G + g) * w + q] = es_eval<double>((double)(j + q) - e, beta, c4);
+                }
+            }
+        }
+        // work ranges: contiguous groups whose distinct blocks fit the tile at every frequency
+        const int nbcap = std::min({YD_NBMAX, YD_RAWROW / (BE + 1), (8 * YD_NLD) >> blk});
+        std::vector<int> wg;
+        std::vector<std::vector<int>> cur(nfg), trial(nfg);
+        auto blocks_with = [&](int g) {
+            int worst = 0;
+            for (int fg = 0; fg < nfg; ++fg) {
+                trial[fg] = cur[fg];
+                for (int q = 0; q < w; ++q) trial[fg].push_back(col[((size_t)fg * G + g) * w + q] >> blk);
+                std::sort(trial[fg].begin(), trial[fg].end());
+                trial[fg].erase(std::unique(trial[fg].begin(), trial[fg].end()), trial[fg].end());
+                worst = std::max(worst, (int)trial[fg].size());
+            }
+            return worst;
+        };
+        std::vector<std::vector<int>> range_blocks;  // [range * nfg + fg]
+        int g0 = 0;
+        while (g0 < G) {
+            for (auto &v : cur) v.clear();
+            int ng = 0;
+            while (g0 + ng < G && ng < YD_NG && gstart[g0 + ng + 1] - gstart[g0] <= YD_THREADS * YD_PTM) {
+                if (blocks_with(g0 + ng) > nbcap) break;
+                cur.swap(trial);
+                ++ng;
+            }
+            if (ng == 0) return skip("one u-group alone does not fit a workgroup");
+            wg.insert(wg.end(), {g0, ng, gstart[g0], gstart[g0 + ng] - gstart[g0]});
+            for (int fg = 0; fg < nfg; ++fg) range_blocks.push_back(cur[fg]);
+            g0 += ng;
+        }
+        const int nwg = (int)wg.size() / 4;
+        std::vector<int> blkcnt((size_t)nfg * nwg), blkid((size_t)nfg * nwg * YD_NBMAX, 0), cref(col.size());
+        double cells = 0;
+        for (int r = 0; r < nwg; ++r)
+            for (int fg = 0; fg < nfg; ++fg) {
+                const std::vector<int> &bl = range_blocks[(size_t)r * nfg + fg];
+                blkcnt[(size_t)fg * nwg + r] = (int)bl.size();
+                cells += (double)bl.size() * BE * y.na / nfg;
+                for (size_t i = 0; i < bl.size(); ++i) blkid[((size_t)fg * nwg + r) * YD_NBMAX + i] = bl[i];
+                for (int g = wg[4 * r]; g < wg[4 * r] + wg[4 * r + 1]; ++g)
+                    for (int q = 0; q < w; ++q) {
+                        const int cc = col[((size_t)fg * G + g) * w + q];
+                        const int slot = (int)(std::lower_bound(bl.begin(), bl.end(), cc >> blk) - bl.begin());
+                        cref[((size_t)fg * G + g) * w + q] = (slot << 4) | (cc & (BE - 1));
+                    }
+            }
+        upload(yp->wg, wg.data(), sizeof(int) * wg.size(), 0);
+        upload(yp->blkcnt, blkcnt.data(), sizeof(int) * blkcnt.size(), 0);
+        upload(yp->blkid, blkid.data(), sizeof(int) * blkid.size(), 0);
+        upload(yp->cref, cref.data(), sizeof(int) * cref.size(), 0);
+        upload(yp->xw, xw.data(), sizeof(double) * xw.size(), 0);
+        upload(yp->ptv, ptv.data(), sizeof(double) * ptv.size(), 0);
+        upload(yp->ptg, ptg.data(), sizeof(int) * ptg.size(), 0);
+        upload(yp->map, map.data(), sizeof(int) * map.size(), 0);
+        YdArgs &a = yp->a;
+        a.w = w;
+        a.nfg = nfg;
+        a.nwg = nwg;
+        a.ngroups = G;
+        a.na_y = y.na;
+        a.xp = xp;
+        a.blk = blk;
+        a.npts = npts;
+        a.hy = y.h;
+        a.btcy = y.btc;
+        a.wg = yp->wg.template as<int>();
+        a.blkcnt = yp->blkcnt.template as<int>();
+        a.blkid = yp->blkid.template as<int>();
+        a.cref = yp->cref.template as<int>();
+        a.xw = yp->xw.template as<double>();
+        a.ptv = yp->ptv.template as<double>();
+        a.ptg = yp->ptg.template as<int>();
+        yp->cells = cells;
+        yp->built = true;
+        // the geometric rule: distinct columns read at the group's last frequency, whatever is stored
+        std::vector<int> dc(col.begin() + (size_t)(nfg - 1) * G * w, col.end());
+        std::sort(dc.begin(), dc.end());
+        const double columns = (double)(std::unique(dc.begin(), dc.end()) - dc.begin());
+        const double direct = (double)npts * y.na, ypass = columns * 0.5 * y.n2 * std::log2((double)y.n2);
+        yp->use = n0->columns_possible() && n0->geo.cells_o() >= 4000000 && direct <= ydirect_gate() * ypass;
+        if (dbg)
+            std::fprintf(stderr, "ydirect plan pair %d channels [%d, %d): %lld items, %lld points on %d u-groups, %d work ranges, %.0f columns, "
+                         "B cells read %.3g of %.3g needed, na_y %d, blocks of %d, plan %d, rule %.2f -> %s\n", pi, fa, fb, (long long)N,
+                         (long long)npts, G, nwg, columns, cells, columns * y.na, y.na, BE, cp ? 1 : 0, direct / ypass, yp->use ? "taken" : "not taken");
+        return yp;
     }
 
     // Eigenbeam mode (cpu_simulate.py:303-470): beams 0..K-1 are basis beams; every (k <= l) term
@@ -4902,6 +5108,7 @@ class Sim : public SimBase {
         const void *bt_d = nullptr;
         int bt_ndir = 0;
         int64_t bt_stride = 0;
+        bool forward = false;  // the plain forward run (run()): the only pass that may take the direct y sums
         int nsets() const { return (moments ? 3 : 0) + tan_sets; }  // strength sets per launch beyond the forward's one (0: the forward)
         // the plan class of height term kt: the run's own plan, or a light class's
         int cls(int kt) const { return k0 > 0 && kt >= k0 ? (kt >= k1 ? 2 : 1) : 0; }
@@ -4924,6 +5131,7 @@ class Sim : public SimBase {
         if (o.drain && pin_early) pin_output(o, dr);
 
         RunPlan r{t0, t1, f0, f1, t1 - t0, f1 - f0};
+        r.forward = true;
         source_box(r.xc, r.X);
         height_terms(r);
         pair_setup(r);
@@ -5307,6 +5515,10 @@ class Sim : public SimBase {
         // pair still runs beside this pair's big kernels.  FFTVIS_HIP_GANG=0 turns it off.
         const char *eg = std::getenv("FFTVIS_HIP_GANG");
         r.gang = r.pipe && r.D == 2 && r.nt >= 2 && timing_level != 2 && !(eg && std::atoi(eg) == 0);
+        {  // forced direct y sums (FFTVIS_HIP_YDIRECT=1) run one time step per launch: they have no gang form
+            const char *ey = std::getenv("FFTVIS_HIP_YDIRECT");
+            if (ey && std::atoi(ey) == 1 && r.forward && sizeof(T) == 8 && !nbasis && !r.K) r.gang = false;
+        }
         r.nlanes_used = r.gang ? 4 : nlanes;
         // Lane scratch outlives a run: with a device-side output buffer nothing synchronises between
         // two fv_sim_run calls, so the "last big kernels of this lane" events carry over (the next
@@ -5395,9 +5607,15 @@ class Sim : public SimBase {
         if (col_plans.size() > 512) {
             FV_HIP(hipDeviceSynchronize());
             col_plans.clear();
+            y_plans.clear();  // (they point at column plans)
         }
-        if (std::getenv("FFTVIS_HIP_NO_COLUMN_PLAN")) return;
+        if (y_plans.size() > 512) {
+            FV_HIP(hipDeviceSynchronize());
+            y_plans.clear();
+        }
+        y_plan_of.assign(r.groups.size() * pairs.size(), nullptr);
         for (int c = 0; c < r.ncls; ++c) {
+            if (std::getenv("FFTVIS_HIP_NO_COLUMN_PLAN")) break;
             Nufft3<T> *n0 = lanes[0].plan[c].get();
             if (n0->dim != 2 && !n0->zdirect) continue;
             for (size_t gi = 0; gi < r.groups.size(); ++gi) {
@@ -5413,6 +5631,35 @@ class Sim : public SimBase {
             }
             FV_HIP(hipStreamSynchronize(n0->stream));  // the table kernels of these set_geometry calls are done before the run's own
         }
+        // direct y sums (ydirect_plan): forward runs of the run's own 2-D fp64 plan, one time step per launch; the tables
+        // follow the geometry each (group, pair) will set -- a column plan's, or the plain one
+        const char *ey = std::getenv("FFTVIS_HIP_YDIRECT");  // read per run: tests flip it
+        const int ymode = ey ? std::atoi(ey) : -1;
+        if (!r.forward || ymode == 0 || sizeof(T) != 8 || r.D != 2 || r.gang || nbasis || r.K || r.nsets()) return;
+        Nufft3<T> *n0 = lanes[0].plan[0].get();
+        size_t vals_need = 0;
+        for (size_t gi = 0; gi < r.groups.size(); ++gi) {
+            const int fa = r.groups[gi].first, fb = r.groups[gi].second;
+            const double smax = fmax_of(fa, fb);
+            for (size_t pi = 0; pi < pairs.size(); ++pi) {
+                const Pair &pr = pairs[pi];
+                const int tg = pr.herm ? 2 : tpol;
+                if (pr.n == 0 || tg > 4 || pr.mirror) continue;
+                const ColPlan *cp = col_plan_of[0][gi * pairs.size() + pi];
+                if (cp && !cp->use) cp = nullptr;
+                n0->grid_slack = cp ? 0.0 : -1.0;
+                n0->set_geometry(r.xc, r.X, pr.box_c(), pr.box_B(), smax);
+                if (ymode != 1 && (!n0->columns_possible() || n0->geo.cells_o() < 4000000)) continue;
+                if (n0->fused_possible() && ymode != 1) continue;
+                YPlan *yp = ydirect_plan((int)pi, pr, fa, fb, n0, cp, ymode == 1);
+                if (!yp->built || !(ymode == 1 || yp->use)) continue;
+                y_plan_of[gi * pairs.size() + pi] = yp;
+                vals_need = std::max(vals_need, Nufft3<T>::yd_vals_bytes(yp->a.na_y, yp->a.nwg, fb - fa, tg, yp->a.npts));
+            }
+        }
+        FV_HIP(hipStreamSynchronize(n0->stream));
+        if (vals_need)
+            for (int li = 0; li < r.nlanes_used; ++li) lanes[li].plan[0]->yd_vals.reserve(vals_need);
     }
 
     // The unit loop: per (one or two time steps, source chunk) the per-time preparation, then per (frequency group, beam
@@ -5571,6 +5818,9 @@ class Sim : public SimBase {
                     // ---- NUFFT ----------------------------------------------------------
                     const int nmom = r.moments ? 3 : 0;
                     const int nrounds = std::max(1, r.nsets());
+                    // direct y sums for this (group, pair): lane_buffers decided (forward runs, the run's own plan)
+                    YPlan *yp = c == 0 && !gs && !r.tan_w && nm == 1 && !y_plan_of.empty()
+                                    ? y_plan_of[(size_t)(&grp - groups.data()) * pairs.size() + (size_t)(&pr - pairs.data())] : nullptr;
                     for (int rd = 0; rd < nrounds; ++rd) {
                     for (int m = 0; m < nm; ++m) {
                         Nufft3<T> *P = Ls[m]->plan[c].get();
@@ -5579,6 +5829,8 @@ class Sim : public SimBase {
                                        on ? cp->ncc : 0, d_err.as<int>() + 3,
                                        on && cp->omask.p ? cp->omask.template as<unsigned long long>() : nullptr, on ? cp->nblk : 0);
                         P->col_out_cells = on && cp->omask.p ? cp->out_cells : 0.0;
+                        P->arm_ydirect(yp ? &yp->a : nullptr, yp ? yp->map.template as<int>() : nullptr, yp ? yp->cells : 0.0,
+                                       d_freqs.as<double>() + fa);
                     }
                     {
                     RoctxRange rr("spread");
@@ -5604,7 +5856,7 @@ class Sim : public SimBase {
                     // small 2-D grids: the last FFT pass serves the targets from its LDS tiles (no C
                     // buffer, no gather kernel); the output block was zeroed at the start of the run
                     const bool fused =
-                        !gs && !r.tan_w && !nbasis && !pr.herm && !r.K &&
+                        !yp && !gs && !r.tan_w && !nbasis && !pr.herm && !r.K &&
                         nufft->prepare_fused_gather(pr.n, d_bls.as<T>(), d_bls.as<T>() + nbls,
                                                     pr.trivial ? nullptr : pr.idx->template as<int>(),
                                                     pr.trivial ? nullptr : pr.flip->template as<signed char>(),
