@@ -16,7 +16,8 @@ the fit objective with its gradients from one call that keeps the visibilities o
 and their gradient; ``simulate_vis_jones_chi2`` for full 2 x 2 Jones matrices per antenna, leakage included), and the
 Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the tangent
 on the device (``simulate_vis_gauss_newton``; ``simulate_vis_gain_gauss_newton`` with the gains in the data model, a gain
-direction and the gain block of the product), and the gains themselves for a fixed model, solved on the device against
+direction and the gain block of the product; ``simulate_vis_jones_gauss_newton`` the same with 2 x 2 Jones matrices and a
+direction of such matrices), and the gains themselves for a fixed model, solved on the device against
 a resident model (``simulate_vis_gain_solve``; ``simulate_vis_jones_solve`` for the full 2 x 2 matrices).
 """
 
@@ -42,6 +43,7 @@ from .adjoint import (  # noqa: F401
     simulate_vis_gain_solve,
     simulate_vis_gauss_newton,
     simulate_vis_jones_chi2,
+    simulate_vis_jones_gauss_newton,
     simulate_vis_jones_solve,
     simulate_vis_jvp,
     simulate_vis_position_adjoint,

@@ -59,6 +59,8 @@ SYMBOLS = {
     "fv_weight_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "fv_gain_weight_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_jones_weight_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fv_inplace_rot": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64]),
     "fv_astrom_topo": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "fv_sim_create": (c_int, [POINTER(c_void_p), c_int, c_int, c_double, c_double, c_int]),
@@ -91,6 +93,8 @@ SYMBOLS = {
     "fv_sim_weight_block": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "fv_sim_gain_weight_block": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                          c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    "fv_sim_jones_weight_block": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int]),
     "fv_sim_run_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int]),
     "fv_sim_set_adjoint_path": (c_int, [c_void_p, c_int]),
     "fv_sim_last_adjoint_path": (c_int, [c_void_p]),

@@ -32,7 +32,8 @@ block (``fv_sim_run_residual_gains``), and ``wrt="gains"`` gives the gradient wi
 feeds -- with ``wrt="jones"`` (``fv_sim_run_residual_jones``).
 ``simulate_vis_gauss_newton`` is the Gauss-Newton product 2 J^T W J p of that chi2 from one call that keeps the tangent on
 the device (``fv_sim_weight_block``), and ``simulate_vis_gain_gauss_newton`` that product with the gains in the data model,
-a gain direction and the gain block of the product (``fv_sim_gain_weight_block``).  ``simulate_vis_gain_solve`` solves
+a gain direction and the gain block of the product (``fv_sim_gain_weight_block``); ``simulate_vis_jones_gauss_newton`` is
+the same with 2 x 2 matrices and a direction of such matrices (``fv_sim_jones_weight_block``).  ``simulate_vis_gain_solve`` solves
 the gains themselves against a fixed model: one forward into a device tensor, or a resident ``model=``, and the alternating
 per-antenna solve on the device (``fv_gain_solve``).  ``simulate_vis_jones_solve`` is that solve for the full 2 x 2 matrices
 (``fv_jones_solve``).
@@ -2154,8 +2155,8 @@ def simulate_vis_jones_chi2(
     * The device holds one more fp64 value per visibility of a time block (the rows' terms of chi2), which the time
       blocks are sized for.
 
-    The matrices that minimise chi2 for a fixed model are ``simulate_vis_jones_solve``'s.  Not covered: Jones matrices in
-    the Gauss-Newton product, ``model=`` in this call, sharding over GPUs."""
+    The Gauss-Newton product of this chi2 is ``simulate_vis_jones_gauss_newton``'s, and the matrices that minimise it for a
+    fixed model are ``simulate_vis_jones_solve``'s.  Not covered: ``model=`` in this call, sharding over GPUs."""
     return _gain_chi2(locals(), "jones")
 
 
@@ -2404,16 +2405,31 @@ def simulate_vis_gain_gauss_newton(
 
     A gains-only solve against a fixed model is ``simulate_vis_gain_solve``'s: one forward, or a resident ``model=``, and
     the iterations on the device -- here every call reruns the forward.  Not covered: ``model=`` in this call, several
-    directions per call, the gradient in the same call (``simulate_vis_gain_chi2``), full 2x2 Jones (leakage) gains,
-    torch ``hvp``, sharding over GPUs."""
-    args = locals()
+    directions per call, the gradient in the same call (``simulate_vis_gain_chi2``), torch ``hvp``, sharding over GPUs.
+    Full 2x2 Jones (leakage) matrices per antenna are ``simulate_vis_jones_gauss_newton``'s."""
+    return _gain_gauss_newton(locals(), "gains")
+
+
+def _gain_gauss_newton(args: dict, kind: str):
+    """``simulate_vis_gain_gauss_newton`` (``kind="gains"``) and ``simulate_vis_jones_gauss_newton`` (``kind="jones"``):
+    ``args`` is the public function's ``locals()``, ``args[kind]`` its gains or matrices (None: neither,
+    ``simulate_vis_gauss_newton``) and ``args["d_" + kind]`` their direction.  The two differ in the blocks the engine's
+    pass is given, in the output that receives the product and in the name ``wrt`` has for it."""
+    gains, d_gains = args[kind], args["d_" + kind]
+    d_fluxes, d_ants, d_baselines, d_radec, d_topo, d_beam_coefs = (
+        args[k] for k in ("d_fluxes", "d_ants", "d_baselines", "d_radec", "d_topo", "d_beam_coefs"))
+    weights, wrt, quad_per, fluxes, full_stokes = (args[k] for k in ("weights", "wrt", "quad_per", "fluxes", "full_stokes"))
+    adjoint_path, beam_coefs, polarized, return_gvis = (
+        args[k] for k in ("adjoint_path", "beam_coefs", "polarized", "return_gvis"))
     given = tuple(name for d, name in _GAUSS_NEWTON_NAMES if args[d] is not None)
     if d_gains is not None and gains is None:
-        raise ValueError("d_gains needs gains=")
+        raise ValueError(f"d_{kind} needs {kind}=")
+    if kind == "jones" and not polarized:
+        raise ValueError("jones needs polarized=True: a 2 x 2 matrix per antenna mixes the two feeds")
     if not given and d_gains is None:
         if gains is not None:
-            raise ValueError("simulate_vis_gain_gauss_newton needs a direction: d_fluxes, d_ants, d_baselines, d_radec, d_topo, "
-                             "d_beam_coefs or d_gains")
+            raise ValueError(f"simulate_vis_{'jones' if kind == 'jones' else 'gain'}_gauss_newton needs a direction: d_fluxes, "
+                             f"d_ants, d_baselines, d_radec, d_topo, d_beam_coefs or d_{kind}")
         raise ValueError("simulate_vis_gauss_newton needs a direction: d_fluxes, d_ants, d_baselines, d_radec, d_topo or "
                          "d_beam_coefs")
     if d_ants is not None and d_baselines is not None:
@@ -2421,8 +2437,8 @@ def simulate_vis_gain_gauss_newton(
     if d_radec is not None and d_topo is not None:
         raise ValueError("give the source tangent as d_radec or as d_topo, not both")
     if wrt is None:
-        wrt = given + (("gains",) if d_gains is not None else ())
-    single, names = _fit_keywords(wrt, gains, "quad_per", quad_per, adjoint_path, beam_coefs, polarized, d_beam_coefs)
+        wrt = given + ((kind,) if d_gains is not None else ())
+    single, names = _fit_keywords(wrt, gains, "quad_per", quad_per, adjoint_path, beam_coefs, polarized, d_beam_coefs, kind=kind)
     run = _describe_run(args)
     run = _own_radec_chain(run, "d_radec" if d_radec is not None else "wrt='radec'", d_radec is not None or "radec" in names,
                            "pass d_topo and ask for wrt='topo', and apply its Jacobian", "pass d_topo and ask for wrt='topo'")
@@ -2443,16 +2459,17 @@ def simulate_vis_gain_gauss_newton(
         _check_weights(run, weights, "simulate_vis's output")
     gain_block = dgain_block = None
     if gains is not None:
-        gain_block = _gain_block(run, gains)
+        as_block = _jones_block if kind == "jones" else _gain_block
+        gain_block = as_block(run, gains)
         if d_gains is not None:
             if tuple(d_gains.shape) != tuple(gains.shape):
-                raise ValueError(f"d_gains must have gains' shape {tuple(gains.shape)}, got {tuple(d_gains.shape)}")
+                raise ValueError(f"d_{kind} must have {kind}' shape {tuple(gains.shape)}, got {tuple(d_gains.shape)}")
             if not np.iscomplexobj(_host(d_gains)):
-                raise ValueError("d_gains must be complex, like gains")
+                raise ValueError(f"d_{kind} must be complex, like {kind}")
             if not np.isfinite(_host(d_gains)).all():
-                raise ValueError("d_gains must be finite")
-            dgain_block = _gain_block(run, d_gains)
-    hgains = np.zeros(gain_block.shape, dtype=np.complex128) if "gains" in names else None
+                raise ValueError(f"d_{kind} must be finite")
+            dgain_block = as_block(run, d_gains)
+    hgains = np.zeros(gain_block.shape, dtype=np.complex128) if kind in names else None
     inputs = (d_fluxes, d_ants, d_baselines, d_radec, d_topo, d_beam_coefs, weights)
     dev = _run_device(run, inputs, "a direction or the weights")
     like = next((x for x in inputs + (d_gains,) if _is_tensor(x)), None)
@@ -2470,16 +2487,109 @@ def simulate_vis_gain_gauss_newton(
     gvis = _gvis_buffer(run, return_gvis)
     _synchronize(dev)
     # (the gains act on the output block whatever path produced it: they do not force the type-3 transform)
-    fluxes_only = set(given) <= {"fluxes"} and set(names) <= {"fluxes", "gains"}
+    fluxes_only = set(given) <= {"fluxes"} and set(names) <= {"fluxes", kind}
     outputs = dict(zip(("gflux", "gcoefs", "gbls", "gtopo"), buffers), gvis=gvis)
+    if gains is None:
+        gauss_newton_of = (directions, w, outputs)
+    elif kind == "jones":
+        gauss_newton_of = (directions, w, dict(outputs, gjones=hgains), ("jones", (gain_block, dgain_block)))
+    else:
+        gauss_newton_of = (directions, w, dict(outputs, ggains=hgains), (gain_block, dgain_block))
     quad_ft = _engine_simulate(
-        run, fluxes, force_use_type3=None if fluxes_only else True, adjoint_path=adjoint_path,
-        gauss_newton_of=(directions, w, outputs) if gains is None else
-        (directions, w, dict(outputs, ggains=hgains), (gain_block, dgain_block)))
-    prods = _fit_gradients(run, single, names, buffers, full_stokes, hgains, gains, like, dev)
+        run, fluxes, force_use_type3=None if fluxes_only else True, adjoint_path=adjoint_path, gauss_newton_of=gauss_newton_of)
+    prods = _fit_gradients(run, single, names, buffers, full_stokes, hgains, gains, like, dev, kind=kind)
     # (no time steps: no rows to add)
     quad = 0.0 if quad_per == "total" and not quad_ft.size else _fit_value(quad_ft, quad_per, like, dev)
     return (quad, prods, _gvis_home(gvis, like, dev)) if return_gvis else (quad, prods)
+
+
+def simulate_vis_jones_gauss_newton(
+    ants: dict,
+    fluxes,
+    ra: np.ndarray,
+    dec: np.ndarray,
+    freqs: np.ndarray,
+    times,
+    beam,
+    telescope_loc,
+    *,
+    jones,
+    d_fluxes=None,
+    d_ants=None,
+    d_baselines=None,
+    d_radec=None,
+    d_topo=None,
+    d_beam_coefs=None,
+    d_jones=None,
+    weights=None,
+    wrt=None,
+    quad_per: str = "total",
+    return_gvis: bool = False,
+    adjoint_path: str = "type3",
+    beam_coefs=None,
+    full_stokes: bool = None,
+    beam_idx: np.ndarray = None,
+    baselines: list = None,
+    precision: int = 2,
+    polarized: bool = False,
+    eps: float = None,
+    upsample_factor=2,
+    beam_spline_opts: dict = None,
+    use_feed: str = "x",
+    flat_array_tol: float = 1e-6,
+    interpolation_function: str = "az_za_map_coordinates",
+    nprocesses: int | None = 1,
+    nthreads: int | None = None,
+    coord_method: str = "CoordinateRotationERFA",
+    coord_method_params: dict | None = None,
+    force_use_type3: bool = False,
+    force_use_ray: bool = False,
+    trace_mem: bool = False,
+    backend: str = "gpu",
+    max_memory=np.inf,
+    min_chunks: int = 1,
+    source_buffer=1.0,
+    device: int = 0,
+    coord_mgr=None,
+    reference_compat: bool = True,
+    astrom: np.ndarray = None,
+    device_astrometry: bool = False,
+):
+    """``simulate_vis_gauss_newton`` with one 2 x 2 complex matrix per antenna in the data model: the Gauss-Newton product
+    of ``simulate_vis_jones_chi2``'s chi2, whose data model is ``V'[x, y] = sum conj(jones[a1][y', y]) jones[a2][x', x]
+    V[x', y']``, along a joint direction ``p = (sky directions, d_jones)``, the matrices' block of ``H p`` included.  With
+    ``S(X; A, B)[x, y] = sum conj(A[y', y]) B[x', x] X[x', y']`` that product and ``U`` the sky tangent as
+    ``simulate_vis_gauss_newton`` defines it, the tangent of the data model is
+
+        ``U' = S(U; J[a1], J[a2]) + S(V; dJ[a1], J[a2]) + S(V; J[a1], dJ[a2])``;
+
+    ``quad = sum w |U'|^2``, ``H = 2 J'^T W J'`` with ``J'`` the Jacobian of V', and ``<p, H p> = 2 quad``, the matrices'
+    part of the inner product being ``Re sum conj(d_jones) prod``.  The product is applied on the device to the blocks the
+    weighting kernel touches (``fv_sim_jones_weight_block``), whatever path produced them; everything else -- the ``d_*``
+    directions, ``weights``, the other names of ``wrt``, ``quad_per``, ``adjoint_path``, ``force_use_type3``, the returned
+    tuple -- is ``simulate_vis_gauss_newton``'s.  ``jones[a] = diag(gains[a])`` and ``d_jones[a] = diag(d_gains[a])`` is
+    ``simulate_vis_gain_gauss_newton``.
+
+    * Needs ``polarized=True`` (ValueError otherwise).
+    * ``jones``: ``simulate_vis_jones_chi2``'s, with its shapes and rules.  ``d_jones``: the direction, ``jones``' own shape
+      -- time-constant or per time as ``jones`` is --, complex and finite, or None.  ``d_jones`` alone is a valid call: no
+      tangent pass runs, only the forward.
+    * ``"jones"`` in ``wrt`` gives the matrices' block of ``H p`` in ``jones``' own shape, complex128, in the convention of
+      ``simulate_vis_jones_chi2``'s gradient, following the inputs as the other products do; for time-constant matrices it
+      is the per-time products added on the host in time order.  ``wrt=None`` appends ``"jones"`` when ``d_jones`` is given.
+      Every other product is its public pass's result for ``vis = G``.
+    * ``return_gvis=True`` gives that G, the transposed product applied to ``2 w U'`` -- NOT ``2 w U'`` itself.
+    * A weight of 0 flags that one ``(x, y)`` sample; the baseline's other samples still use all four values of U and V.
+    * The forward V is computed only when ``d_jones`` is given or ``"jones"`` is asked for (one more device block); the
+      device also holds one more fp64 value per visibility of a time block (the rows' terms of quad), which the time
+      blocks are sized for.
+    * Jones matrices alone do not force the type-3 transform: ``adjoint_path`` and ``force_use_type3`` are honoured when
+      the sky part of the call is within fluxes, as for ``simulate_vis_gauss_newton``.
+
+    A matrices-only solve against a fixed model is ``simulate_vis_jones_solve``'s.  Not covered: ``model=`` in this call,
+    several directions per call, the gradient in the same call (``simulate_vis_jones_chi2``), torch ``hvp``, sharding over
+    GPUs."""
+    return _gain_gauss_newton(locals(), "jones")
 
 
 def _solve_start(run: _Run, gains, per_time: bool):
@@ -2796,6 +2906,6 @@ def simulate_vis_jones_solve(
       group's representative pair: a calibration passes explicit ``baselines``.
 
     Every other keyword means what it means for ``simulate_vis``.  Not differentiable, and no torch operation.  Not covered:
-    Jones matrices in the Gauss-Newton product, a joint sky and Jones solve, ``model=`` in the chi2 and Gauss-Newton
-    calls, sharding over GPUs."""
+    a joint sky and Jones solve (the CG loop over ``simulate_vis_jones_gauss_newton``), ``model=`` in the chi2 and
+    Gauss-Newton calls, sharding over GPUs."""
     return _gain_solve(locals(), "jones")

@@ -325,7 +325,7 @@ static void coherency_host(int device, int variant, int64_t n, const void *bi, c
 }
 
 // The row passes on host arrays (fv_residual_chi2, fv_gain_residual_chi2, fv_jones_residual_chi2, fv_weight_rows,
-// fv_gain_weight_rows): every array is copied into a buffer of its own on the call's stream (null stays null), the launcher
+// fv_gain_weight_rows, fv_jones_weight_rows): every array is copied into a buffer of its own on the call's stream (null stays null), the launcher
 // queues the kernels, what was computed in place is copied back and collect_rows ends the call.
 template <typename X>
 static X *to_device(hipStream_t s, DevBuf &buf, const void *host, size_t n) {
@@ -673,6 +673,42 @@ static void gain_weight_rows_host(int device, int64_t nrows, int64_t nbls, int t
 }
 
 template <typename T>
+static void jones_weight_rows_host(int device, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                                   const void *jones, const void *d_jones, int nparts, const void *const *parts, void *vis,
+                                   const void *weights, double *q_rows, void *hjones) {
+    const size_t nj = (size_t)nrows * 4 * (size_t)nant;
+    if (nrows == 0) return;
+    if (nbls == 0) {
+        for (int64_t i = 0; i < nrows; ++i) q_rows[i] = 0.0;
+        if (hjones) std::memset(hjones, 0, sizeof(cplx<double>) * nj);
+        return;
+    }
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const int64_t row_len = 4 * nbls;
+    const size_t n = (size_t)nrows * (size_t)row_len;
+    GainPairs gp;
+    gp.set(sg.s, nant, nbls, ant1, ant2);
+    DevBuf dp[4], dv, dw, ds, djn, ddj, dhj, dt;
+    cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int j = 0; j < nparts; ++j) dparts[j] = to_device<cplx<T>>(sg.s, dp[j], parts[j], n);
+    if (hjones) dhj.reserve(sizeof(cplx<double>) * nj);
+    dt.reserve(sizeof(double) * n);
+    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
+    const cplx<T> *jn = to_device<cplx<T>>(sg.s, djn, jones, nj), *dj = to_device<cplx<T>>(sg.s, ddj, d_jones, nj);
+    launch_jones_weight_rows<T>(sg.s, nparts, dparts, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<T>(sg.s, dw, weights, n),
+                                nrows, rs, {&gp, jn, dhj.as<cplx<double>>(), dt.as<double>(), dj});
+    if (nparts)  // G replaces P_0, or V for the matrices-only direction
+        FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    else
+        FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    if (hjones) FV_HIP(hipMemcpyAsync(hjones, dhj.p, sizeof(cplx<double>) * nj, hipMemcpyDeviceToHost, sg.s));
+    int hbad[2];
+    collect_rows(sg.s, rs, nrows, q_rows, hbad);
+    throw_if_bad_residual_input(hbad);
+}
+
+template <typename T>
 static void inplace_rot_host(int device, const double *rot, void *b, int64_t n) {
     FV_REQUIRE(rot && n >= 0 && (b || n == 0), "bad inplace_rot arrays");
     FV_HIP(hipSetDevice(device));
@@ -1009,6 +1045,31 @@ int fv_gain_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, 
     });
 }
 
+int fv_jones_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                         const void *jones, const void *d_jones, int nparts, const void *const *parts, void *vis,
+                         const void *weights, double *q_rows, void *hjones) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+        FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_jones_weight_rows: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_jones_weight_rows: nant must be positive");
+        FV_REQUIRE(jones || nrows == 0, "fv_jones_weight_rows: null jones");
+        FV_REQUIRE(nparts >= 0 && nparts <= 4 && (parts || nparts == 0), "fv_jones_weight_rows: nparts must be 0 .. 4");
+        FV_REQUIRE(nparts > 0 || d_jones, "fv_jones_weight_rows: nparts == 0 needs d_jones");
+        for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts[j], "fv_jones_weight_rows: null part");
+        FV_REQUIRE(vis || !(d_jones || hjones), "fv_jones_weight_rows: d_jones and hjones need vis");
+        FV_REQUIRE((nrows == 0 || nbls == 0 || (ant1 && ant2)) && (nrows == 0 || q_rows), "fv_jones_weight_rows: null pairs or q_rows");
+        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
+            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                       "fv_jones_weight_rows: antenna index outside [0, nant)");
+        if (precision == 2)
+            jones_weight_rows_host<double>(device, nrows, nbls, nant, ant1, ant2, jones, d_jones, nparts, parts, vis, weights,
+                                           q_rows, hjones);
+        else
+            jones_weight_rows_host<float>(device, nrows, nbls, nant, ant1, ant2, jones, d_jones, nparts, parts, vis, weights,
+                                          q_rows, hjones);
+    });
+}
+
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n) {
     return guarded([&] {
         FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
@@ -1194,6 +1255,23 @@ int fv_sim_gain_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int npar
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->gain_weight_block(t0, t1, f0, f1, nparts, parts_dev, vis_dev, weights, weights_on_device, gains, gains_on_device,
                                    d_gains, d_gains_on_device, q_ft, hgains, hgains_on_device);
+    });
+}
+int fv_sim_jones_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
+                              const void *weights, int weights_on_device, const void *jones, int jones_on_device,
+                              const void *d_jones, int d_jones_on_device, double *q_ft, void *hjones, int hjones_on_device) {
+    return guarded([&] {  // (the buffers are checked before the handle is looked at)
+        FV_REQUIRE(nparts >= 0 && nparts <= 4 && (parts_dev || nparts == 0), "nparts must be 0 .. 4");
+        FV_REQUIRE(nparts > 0 || d_jones, "nparts == 0 needs d_jones");
+        for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts_dev[j], "null part");
+        FV_REQUIRE(jones && q_ft, "null jones or q_ft");
+        FV_REQUIRE(vis_dev || !(d_jones || hjones), "d_jones and hjones need vis");
+        FV_REQUIRE((weights_on_device == 0 || weights_on_device == 1) && (jones_on_device == 0 || jones_on_device == 1) &&
+                       (d_jones_on_device == 0 || d_jones_on_device == 1) && (hjones_on_device == 0 || hjones_on_device == 1),
+                   "on_device flags must be 0 or 1");
+        FV_REQUIRE(h && h->impl, "null handle");
+        h->impl->jones_weight_block(t0, t1, f0, f1, nparts, parts_dev, vis_dev, weights, weights_on_device, jones, jones_on_device,
+                                    d_jones, d_jones_on_device, q_ft, hjones, hjones_on_device);
     });
 }
 int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,

@@ -1981,6 +1981,24 @@ __device__ __forceinline__ cplx<T> jones_add(const cplx<T> &a, const cplx<T> &b)
 #pragma clang fp contract(off)
     return {a.re + b.re, a.im + b.im};
 }
+// The stored G of one baseline from its G' (the Jones objective and the Gauss-Newton product with Jones gains share it):
+//     C[x', y] = conj(G2[x', 0]) G'[0, y] + conj(G2[x', 1]) G'[1, y],    G[x', y'] = C[x', 0] G1[y', 0] + C[x', 1] G1[y', 1],
+// every operation rounding on its own; `any` false (every sample flagged): exactly 0 whatever the matrices hold.
+template <typename T>
+__device__ __forceinline__ void jones_stored_g(const cplx<T> (&gp)[4], const cplx<T> (&g1)[4], const cplx<T> (&g2)[4], bool any,
+                                               cplx<T> (&g_out)[4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int xs = 0; xs < 2; ++xs) {
+        const cplx<T> c0 = jones_add(jones_mulc(gp[0], g2[2 * xs]), jones_mulc(gp[2], g2[2 * xs + 1]));
+        const cplx<T> c1 = jones_add(jones_mulc(gp[1], g2[2 * xs]), jones_mulc(gp[3], g2[2 * xs + 1]));
+#pragma unroll
+        for (int ys = 0; ys < 2; ++ys) {
+            const cplx<T> g = jones_add(jones_mul(c0, g1[2 * ys]), jones_mul(c1, g1[2 * ys + 1]));
+            g_out[2 * xs + ys] = any ? g : cplx<T>{(T)0, (T)0};
+        }
+    }
+}
 // One baseline (a1, a2) in place: v[2 x + y] = V -> G, the row terms of its four samples, the counts of bad input.  J: the
 // row's matrices (staged or global), entry [2 i + j] of antenna a at J[(2 i + j) nant + a].
 template <typename T>
@@ -2015,17 +2033,7 @@ __device__ __forceinline__ void jones_residual_baseline(cplx<T> (&v)[4], const c
                 term[s] = 0.0;
             }
         }
-#pragma unroll
-    for (int xs = 0; xs < 2; ++xs) {
-        // C[x', y] = conj(G2[x', 0]) G'[0, y] + conj(G2[x', 1]) G'[1, y]
-        const cplx<T> c0 = jones_add(jones_mulc(gp[0], g2[2 * xs]), jones_mulc(gp[2], g2[2 * xs + 1]));
-        const cplx<T> c1 = jones_add(jones_mulc(gp[1], g2[2 * xs]), jones_mulc(gp[3], g2[2 * xs + 1]));
-#pragma unroll
-        for (int ys = 0; ys < 2; ++ys) {
-            const cplx<T> g = jones_add(jones_mul(c0, g1[2 * ys]), jones_mul(c1, g1[2 * ys + 1]));
-            v[2 * xs + ys] = any ? g : cplx<T>{(T)0, (T)0};  // (every sample flagged: exactly 0 whatever the matrices hold)
-        }
-    }
+    jones_stored_g<T>(gp, g1, g2, any, v);
 }
 // One baseline of a row: its four values at e, e + nbls, ... of the block's index.
 template <typename T>
@@ -2675,6 +2683,297 @@ __global__ void __launch_bounds__(256)
         if (lane == 0) hgains[(row * nfeed + feed) * nant + ant] = {sr, si};
     }
 }
+// ---------------------------------------------------------------------------------------------
+// Gauss-Newton product with Jones gains (fv_jones_weight_rows, fv_sim_jones_weight_block; DESIGN.md "Jones matrices in the
+// Gauss-Newton product"): the product of the Jones objective's chi2 along a joint direction (sky directions, dGamma).  The
+// block, the pairs, the incidence lists and the matrices' layout are the Jones kernels' above, tpol = 4; H1 = dGamma[a1],
+// H2 = dGamma[a2] are the direction's matrices in the same layout (or none), U the sum of the NP tangent parts (0 for NP = 0,
+// the matrices-only direction), V the forward at the real parameters.  With S(X; A, B)[x, y] = sum_{x', y'} conj(A[y', y])
+// B[x', x] X[x', y'] the data model's product (V' = S(V; G1, G2)),
+//     U' = S(U; G1, G2) + S(V; H1, G2) + S(V; G1, H2)   (the first term alone without a direction, the last two for NP = 0),
+//     G'[x, y] = 2 (w[x, y] U'[x, y]),   row sum += w |U'|^2,   stored G = the Jones objective's G of this G' (jones_stored_g),
+//     hjones = gjones' two sums with this G' (M = G2^T V on side 0, V conj G1 on side 1).
+// Flags are the Jones objective's: w == 0 flags that one (x, y) sample -- G' = 0 exactly there, nothing is added to the rows
+// or to hjones, the baseline's other samples still use all four values of U and V --, and a baseline with all four samples
+// flagged stores G = 0 exactly whatever its parts and V hold.  V is read only with a direction; G replaces P_0, or V for
+// NP = 0.  Two kernels, no floating-point atomics.  k_jones_weight_gather runs first, while the blocks still hold the parts
+// and V; k_jones_weight_rows follows, in place, with k_jones_residual_rows' thread-to-baseline mapping; its row terms go to
+// `terms` and k_jones_rows_sum and k_chi2_rows_reduce add them.  In T every operation rounds on its own (no contraction), in
+// this order, every sum of two products left to right and the products as jones_mul / jones_mulc write them:
+//     U = ((P_0 + P_1) + P_2) + P_3 (component-wise, only the parts given),
+//     S(X; A, B):  B'[x', y] = X[x', 0] conj(A[0, y]) + X[x', 1] conj(A[1, y]),   S[x, y] = B[0, x] B'[0, y] + B[1, x] B'[1, y]
+//     (jones_residual_baseline's V'),   U' = (S(U; G1, G2) + S(V; H1, G2)) + S(V; G1, H2)  (component-wise),
+//     G' = 2 (w U'),   then jones_stored_g.
+// With identity matrices and no direction S(U) = U and G = G' exactly: k_weight_rows<T, NP, false>'s bits, rows included.
+template <typename T>
+__device__ __forceinline__ void jones_sandwich(const cplx<T> (&x)[4], const cplx<T> (&ga)[4], const cplx<T> (&gb)[4],
+                                               cplx<T> (&s)[4]) {  // S(X; A, B), see above
+#pragma clang fp contract(off)
+    cplx<T> b[4];
+#pragma unroll
+    for (int xs = 0; xs < 2; ++xs)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) b[2 * xs + y] = jones_add(jones_mulc(x[2 * xs], ga[y]), jones_mulc(x[2 * xs + 1], ga[2 + y]));
+#pragma unroll
+    for (int xx = 0; xx < 2; ++xx)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) s[2 * xx + y] = jones_add(jones_mul(gb[xx], b[y]), jones_mul(gb[2 + xx], b[2 + y]));
+}
+// One baseline (a1, a2) in place: u[2 x + y] = U -> G (U is ignored when SKY is false), v = V (read only with H), the row
+// terms of its four samples, the count of bad weights.  J, H: the row's matrices and direction (staged or global; H null: no
+// direction), entry [2 i + j] of antenna a at [(2 i + j) nant + a].
+template <typename T, bool SKY>
+__device__ __forceinline__ void jones_weight_baseline(cplx<T> (&u)[4], const cplx<T> (&v)[4], const T (&w)[4], const cplx<T> *J,
+                                                      const cplx<T> *H, int nant, int a1, int a2, double (&term)[4], int &bad_w) {
+#pragma clang fp contract(off)
+    const cplx<T> g1[4] = {J[a1], J[nant + a1], J[2 * nant + a1], J[3 * nant + a1]};
+    const cplx<T> g2[4] = {J[a2], J[nant + a2], J[2 * nant + a2], J[3 * nant + a2]};
+    cplx<T> up[4], gp[4];  // U'[x, y], G'[x, y] at [2 x + y]
+    if constexpr (SKY) jones_sandwich<T>(u, g1, g2, up);
+    if (H) {
+        cplx<T> d[4];
+        {
+            const cplx<T> h1[4] = {H[a1], H[nant + a1], H[2 * nant + a1], H[3 * nant + a1]};
+            jones_sandwich<T>(v, h1, g2, d);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) up[s] = SKY ? jones_add(up[s], d[s]) : d[s];
+        {
+            const cplx<T> h2[4] = {H[a2], H[nant + a2], H[2 * nant + a2], H[3 * nant + a2]};
+            jones_sandwich<T>(v, g1, h2, d);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) up[s] = jones_add(up[s], d[s]);
+    } else if constexpr (!SKY) {  // (the launcher refuses NP = 0 without a direction)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) up[s] = {(T)0, (T)0};
+    }
+    bool any = false;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        if (!(w[s] >= (T)0) || !isfinite(w[s])) ++bad_w;
+        if (w[s] > (T)0) {
+            gp[s] = {(T)2 * (w[s] * up[s].re), (T)2 * (w[s] * up[s].im)};
+            term[s] = row_term<T>(w[s], up[s].re, up[s].im);
+            any = true;
+        } else {  // flagged (or counted above)
+            gp[s] = {(T)0, (T)0};
+            term[s] = 0.0;
+        }
+    }
+    jones_stored_g<T>(gp, g1, g2, any, u);
+}
+// One baseline of a row: its four values at e, e + nbls, ... of the block's index.
+template <typename T, int NP>
+__device__ __forceinline__ void jones_weight_at(int64_t e, int nbls, int a1, int a2, const cplx<T> *J, const cplx<T> *H, int nant,
+                                                const WeightParts<T> &parts, cplx<T> *vis, cplx<T> *out,
+                                                const T *__restrict__ weights, double *__restrict__ terms, int &bad_w) {
+#pragma clang fp contract(off)
+    cplx<T> u[4], v[4];
+    T w[4];
+    double term[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int64_t ep = e + (int64_t)p * nbls;
+        u[p] = {(T)0, (T)0};
+        if constexpr (NP > 0) u[p] = parts.p[0][ep];
+#pragma unroll
+        for (int n = 1; n < NP; ++n) u[p] = {u[p].re + parts.p[n][ep].re, u[p].im + parts.p[n][ep].im};
+        v[p] = H ? vis[ep] : cplx<T>{(T)0, (T)0};
+        w[p] = weights ? weights[ep] : (T)1;
+    }
+    jones_weight_baseline<T, (NP > 0)>(u, v, w, J, H, nant, a1, a2, term, bad_w);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        out[e + (int64_t)p * nbls] = u[p];
+        terms[e + (int64_t)p * nbls] = term[p];
+    }
+}
+// In place over (nrows, 4 nbls) blocks; see above.  lds_j: the row's matrices are staged in dynamic LDS; lds_h: the
+// direction too, behind them (only with lds_j).  vec: every array is 16-byte aligned.
+template <typename T, int NP>
+__global__ void __launch_bounds__(256)
+    k_jones_weight_rows(WeightParts<T> parts, cplx<T> *vis, const T *__restrict__ weights, const cplx<T> *__restrict__ jones,
+                        const cplx<T> *__restrict__ djones, const int *__restrict__ ant1, const int *__restrict__ ant2,
+                        int64_t nrows, int nbls, int nant, int lds_j, int lds_h, int vec, double *__restrict__ terms,
+                        int *__restrict__ bad) {
+    static_assert(NP >= 0 && NP <= 4, "NP = 0 .. 4");
+    constexpr int W = RES_W<T>;
+    constexpr int R = 16 / (int)sizeof(cplx<T>);  // the baselines of one 16-byte vector of a plane: 1 (fp64) or 2 (fp32)
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    const int nj = 4 * nant;
+    const int64_t L = 4 * (int64_t)nbls;
+    cplx<T> *const out = NP ? parts.p[0] : vis;  // where G goes
+    const bool runs = R > 1 && vec && nbls % R == 0;  // (k_jones_residual_rows' runs)
+    const int step = runs ? R : 1, nit = RES_CHUNKS * W / step;
+    int bad_w = 0;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<T> *J = jones + row * nj;
+        const cplx<T> *H = djones ? djones + row * nj : nullptr;
+        if (lds_j) {
+            cplx<T> *jl = reinterpret_cast<cplx<T> *>(gain_lds);
+            for (int i = threadIdx.x; i < nj; i += 256) jl[i] = J[i];
+            J = jl;
+            if (H && lds_h) {
+                for (int i = threadIdx.x; i < nj; i += 256) jl[nj + i] = H[i];
+                H = jl + nj;
+            }
+            __syncthreads();
+        }
+        const int64_t lo = row * L;
+        const int shift = runs ? (int)(lo % R) : 0;  // run r holds the baselines [r R - shift, r R - shift + R)
+        const int64_t kblock = (int64_t)blockIdx.x * (RES_CHUNKS * 256 * W) - shift;
+        for (int i = 0; i < nit; ++i) {
+            const int64_t k0 = kblock + ((int64_t)i * 256 + threadIdx.x) * step;
+            if (k0 >= nbls) break;
+            if constexpr (R > 1) {
+                if (runs && k0 >= 0 && k0 + R <= nbls) {
+                    union {
+                        uint4 q;
+                        cplx<T> c[R];
+                    } u[4], v[4], t;
+                    T w[4][R];
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const int64_t e = lo + (int64_t)p * nbls + k0;
+                        if constexpr (NP > 0) u[p].q = *reinterpret_cast<const uint4 *>(parts.p[0] + e);
+#pragma unroll
+                        for (int n = 1; n < NP; ++n) {
+                            t.q = *reinterpret_cast<const uint4 *>(parts.p[n] + e);
+#pragma unroll
+                            for (int j = 0; j < R; ++j) u[p].c[j] = {u[p].c[j].re + t.c[j].re, u[p].c[j].im + t.c[j].im};
+                        }
+                        if (H) v[p].q = *reinterpret_cast<const uint4 *>(vis + e);
+#pragma unroll
+                        for (int j = 0; j < R; ++j) w[p][j] = weights ? weights[e + j] : (T)1;
+                    }
+#pragma unroll
+                    for (int j = 0; j < R; ++j) {
+                        const cplx<T> zero = {(T)0, (T)0};
+                        cplx<T> uu[4] = {zero, zero, zero, zero};
+                        if constexpr (NP > 0) {
+#pragma unroll
+                            for (int p = 0; p < 4; ++p) uu[p] = u[p].c[j];
+                        }
+                        const cplx<T> vv[4] = {H ? v[0].c[j] : zero, H ? v[1].c[j] : zero, H ? v[2].c[j] : zero,
+                                               H ? v[3].c[j] : zero};
+                        const T w4[4] = {w[0][j], w[1][j], w[2][j], w[3][j]};
+                        double term[4];
+                        jones_weight_baseline<T, (NP > 0)>(uu, vv, w4, J, H, nant, ant1[k0 + j], ant2[k0 + j], term, bad_w);
+#pragma unroll
+                        for (int p = 0; p < 4; ++p) {
+                            u[p].c[j] = uu[p];
+                            terms[lo + (int64_t)p * nbls + k0 + j] = term[p];
+                        }
+                    }
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) *reinterpret_cast<uint4 *>(out + lo + (int64_t)p * nbls + k0) = u[p].q;
+                    continue;
+                }
+            }
+            const int64_t kb = k0 + step < nbls ? k0 + step : nbls;
+            for (int64_t k = k0 > 0 ? k0 : 0; k < kb; ++k)
+                jones_weight_at<T, NP>(lo + k, nbls, ant1[k], ant2[k], J, H, nant, parts, vis, out, weights, terms, bad_w);
+        }
+        if (lds_j) __syncthreads();  // (the next row of this block stages its matrices again)
+    }
+    if (bad_w) atomicAdd(bad, bad_w);
+}
+// hjones[((row 2 + i) 2 + j) nant + a]: k_jones_gradient with the G' above in place of 2 w (V' - d): one wave per (row,
+// antenna) holds all four entries of the antenna's matrix, lane l takes the entries l, l + 64, ... of the incidence list in
+// order, everything is formed in fp64 from the T-typed inputs (U summed in fp64 in the parts' order), an __shfl_xor tree,
+// four complex128 per wave; a baseline whose four samples are all flagged is skipped before anything of it is read; an
+// antenna without a baseline gets exactly 0.  The parts and vis still hold the tangent parts and V.
+template <typename T, int NP>
+__global__ void __launch_bounds__(256)
+    k_jones_weight_gather(WeightParts<T> parts, const cplx<T> *__restrict__ vis, const T *__restrict__ weights,
+                          const cplx<T> *__restrict__ jones, const cplx<T> *__restrict__ djones, const int *__restrict__ ant1,
+                          const int *__restrict__ ant2, const int *__restrict__ inc_off, const int *__restrict__ inc,
+                          int64_t nrows, int nbls, int nant, cplx<double> *__restrict__ hjones) {
+    const int ant = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (ant >= nant) return;  // (whole waves: the tree below stays inside one)
+    const int i0 = inc_off[ant], i1 = inc_off[ant + 1];
+    const int64_t L = 4 * (int64_t)nbls;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<T> *J = jones + row * 4 * nant;
+        const cplx<T> *H = djones ? djones + row * 4 * nant : nullptr;
+        cplx<double> acc[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+        for (int i = i0 + lane; i < i1; i += 64) {
+            const int k = inc[i] >> 1, side = inc[i] & 1;
+            const int a1 = ant1[k], a2 = ant2[k];
+            const int64_t e = row * L + k;
+            cplx<double> v[4], g1[4], g2[4], m[4], up[4], gp[4];
+            double w2[4];
+            bool any = false;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const T wt = weights ? weights[e + (int64_t)p * nbls] : (T)1;
+                w2[p] = wt > (T)0 ? 2.0 * (double)wt : 0.0;
+                any = any || wt > (T)0;
+            }
+            if (!any) continue;  // every sample flagged: nothing is added, nothing more is read
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                v[p] = {(double)vis[e + (int64_t)p * nbls].re, (double)vis[e + (int64_t)p * nbls].im};
+                g1[p] = {(double)J[p * nant + a1].re, (double)J[p * nant + a1].im};
+                g2[p] = {(double)J[p * nant + a2].re, (double)J[p * nant + a2].im};
+                up[p] = {0.0, 0.0};
+            }
+            if constexpr (NP > 0) {
+                cplx<double> u[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) {
+                    const int64_t ep = e + (int64_t)p * nbls;
+                    u[p] = {(double)parts.p[0][ep].re, (double)parts.p[0][ep].im};
+#pragma unroll
+                    for (int n = 1; n < NP; ++n) u[p] = {u[p].re + (double)parts.p[n][ep].re, u[p].im + (double)parts.p[n][ep].im};
+                }
+                jones_sandwich<double>(u, g1, g2, up);
+            }
+            if (H) {
+                cplx<double> h[4], d[4];
+#pragma unroll
+                for (int p = 0; p < 4; ++p) h[p] = {(double)H[p * nant + a1].re, (double)H[p * nant + a1].im};
+                jones_sandwich<double>(v, h, g2, d);
+#pragma unroll
+                for (int p = 0; p < 4; ++p) up[p] = cadd(up[p], d[p]);
+#pragma unroll
+                for (int p = 0; p < 4; ++p) h[p] = {(double)H[p * nant + a2].re, (double)H[p * nant + a2].im};
+                jones_sandwich<double>(v, g1, h, d);
+#pragma unroll
+                for (int p = 0; p < 4; ++p) up[p] = cadd(up[p], d[p]);
+            }
+            // side 0: M[x, y'] = (G2^T V)[x, y'] at [2 x + y'];  side 1: M[x', y] = (V conj G1)[x', y] at [2 x' + y]
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+                    m[2 * r + c] = side ? cadd(cmul(v[2 * r], cconj(g1[c])), cmul(v[2 * r + 1], cconj(g1[2 + c])))
+                                        : cadd(cmul(g2[r], v[c]), cmul(g2[2 + r], v[2 + c]));
+#pragma unroll
+            for (int s = 0; s < 4; ++s)  // (a select: exactly 0 where flagged)
+                gp[s] = w2[s] > 0.0 ? cplx<double>{w2[s] * up[s].re, w2[s] * up[s].im} : cplx<double>{0.0, 0.0};
+            // side 0: acc[y', y] += sum_x conj(G'[x, y]) M[x, y'];  side 1: acc[x', x] += sum_y G'[x, y] conj(M[x', y])
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const cplx<double> t = side ? cadd(cmul(gp[2 * c], cconj(m[2 * r])), cmul(gp[2 * c + 1], cconj(m[2 * r + 1])))
+                                                : cadd(cmul(cconj(gp[c]), m[r]), cmul(cconj(gp[2 + c]), m[2 + r]));
+                    acc[2 * r + c].re += t.re;
+                    acc[2 * r + c].im += t.im;
+                }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            for (int off = 32; off > 0; off >>= 1) {
+                acc[s].re += __shfl_xor(acc[s].re, off, 64);
+                acc[s].im += __shfl_xor(acc[s].im, off, 64);
+            }
+            if (lane == 0) hjones[(row * 4 + s) * nant + ant] = acc[s];
+        }
+    }
+}
 // The gains of a row pass, all device pointers: the pairs (null: a pass without gains), the rows' gains and their
 // direction (nrows, nfeed nant; dgains null: no direction, and none in the objective) and where the gain gradient goes
 // (ggains or hgains, (nrows, nfeed nant) complex128; null: the gather does not run).
@@ -2739,6 +3038,7 @@ struct RowJones {
     const cplx<T> *jones = nullptr;
     cplx<double> *grad = nullptr;
     double *terms = nullptr;
+    const cplx<T> *djones = nullptr;  // the direction's matrices (the Gauss-Newton product only; null: no direction)
 };
 // Queues the Jones objective's kernels on `on`: the gather k_jones_gradient (when rj.grad is not null), the in-place kernel,
 // the rows' sums and their reduction.  vis (nrows, 4 nbls) in place, rs from row_scratch for that shape (the counters are
@@ -2819,6 +3119,53 @@ inline void launch_weight_rows(hipStream_t on, int nparts, cplx<T> *const *parts
         default: FV_ROWS(4, false); break;
         }
 #undef FV_ROWS
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)rs.partials, nrows,
+                       rs.nblk, rs.sums);
+}
+// Queues the product's kernels with Jones gains on `on`: the gather k_jones_weight_gather (when rj.grad is not null), the
+// in-place kernel, the rows' sums and their reduction.  parts[0 .. nparts) device blocks (nrows, 4 nbls), nparts = 0 .. 4
+// (0 needs rj.djones); vis the forward block (needed with rj.djones, with rj.grad and for nparts = 0; else it may be null);
+// G in place in parts[0], or in vis for nparts = 0; rs from row_scratch for that shape (the counters are zeroed here).  The
+// row's matrices are staged in LDS when they fit GAIN_LDS_BYTES, the direction too when both fit together.  weights may be
+// null.
+template <typename T>
+inline void launch_jones_weight_rows(hipStream_t on, int nparts, cplx<T> *const *parts, cplx<T> *vis, const T *weights,
+                                     int64_t nrows, const RowScratch &rs, const RowJones<T> &rj) {
+    if (nparts < 0 || nparts > 4 || (nparts == 0 && !rj.djones)) throw Error(FV_ERR_ARG, "nparts must be 0 .. 4, and 0 needs d_jones");
+    if ((rj.djones || rj.grad || nparts == 0) && !vis) throw Error(FV_ERR_ARG, "d_jones and hjones need vis");
+    constexpr int W = RES_W<T>;
+    const int nbls = (int)rj.pairs->nbls, nant = rj.pairs->nant;
+    const int64_t L = 4 * (int64_t)nbls;
+    const int *a1 = rj.pairs->d_ant1.template as<int>(), *a2 = rj.pairs->d_ant2.template as<int>();
+    const size_t lds1 = sizeof(cplx<T>) * 4 * (size_t)nant;
+    const int lds_j = lds1 <= GAIN_LDS_BYTES, lds_h = rj.djones && 2 * lds1 <= GAIN_LDS_BYTES;
+    const size_t shm = lds_j ? (lds_h ? 2 * lds1 : lds1) : 0;
+    WeightParts<T> wp{};
+    for (int j = 0; j < nparts; ++j) wp.p[j] = parts[j];
+    const int vec = rows_vec({weights, rj.djones || nparts == 0 ? vis : nullptr, wp.p[0], wp.p[1], wp.p[2], wp.p[3]});
+    const unsigned rows_y = (unsigned)std::min<int64_t>(nrows, 65535);
+    // (a row's runs: one more than its own when it starts inside a chunk)
+    const unsigned nblk = (unsigned)std::max<int64_t>(1, cdiv(cdiv((int64_t)nbls, W) + 1, (int64_t)RES_CHUNKS * 256));
+    FV_HIP(hipMemsetAsync(rs.bad, 0, 2 * sizeof(int), on));
+#define FV_JONES_WEIGHT(NP)                                                                                                   \
+    do {                                                                                                                       \
+        if (rj.grad)                                                                                                           \
+            hipLaunchKernelGGL((k_jones_weight_gather<T, NP>), dim3((unsigned)cdiv(nant, 4), rows_y), dim3(256), 0, on, wp,    \
+                               (const cplx<T> *)vis, weights, rj.jones, rj.djones, a1, a2, rj.pairs->d_off.template as<int>(), \
+                               rj.pairs->d_inc.template as<int>(), nrows, nbls, nant, rj.grad);                                \
+        hipLaunchKernelGGL((k_jones_weight_rows<T, NP>), dim3(nblk, rows_y), dim3(256), shm, on, wp, vis, weights, rj.jones,   \
+                           rj.djones, a1, a2, nrows, nbls, nant, lds_j, lds_h, vec, rj.terms, rs.bad);                         \
+    } while (0)
+    switch (nparts) {
+    case 0: FV_JONES_WEIGHT(0); break;
+    case 1: FV_JONES_WEIGHT(1); break;
+    case 2: FV_JONES_WEIGHT(2); break;
+    case 3: FV_JONES_WEIGHT(3); break;
+    default: FV_JONES_WEIGHT(4); break;
+    }
+#undef FV_JONES_WEIGHT
+    hipLaunchKernelGGL(k_jones_rows_sum<T>, dim3((unsigned)rs.nblk, rows_y), dim3(256), 0, on, (const double *)rj.terms, nrows, L,
+                       rs.partials, rs.bad);
     hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, on, (const double *)rs.partials, nrows,
                        rs.nblk, rs.sums);
 }
@@ -3424,6 +3771,10 @@ struct SimBase {
                                    const void *weights, int weights_on_device, const void *gains, int gains_on_device,
                                    const void *d_gains, int d_gains_on_device, double *q_ft, void *hgains,
                                    int hgains_on_device) = 0;
+    virtual void jones_weight_block(int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
+                                    const void *weights, int weights_on_device, const void *jones, int jones_on_device,
+                                    const void *d_jones, int d_jones_on_device, double *q_ft, void *hjones,
+                                    int hjones_on_device) = 0;
     virtual void run_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                              int gflux_on_device, int accumulate) = 0;
     virtual void run_basis_adjoint(int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
@@ -5313,6 +5664,36 @@ class Sim : public SimBase {
         if (hgains && !hgains_on_device)
             FV_HIP(hipMemcpyAsync(hgains, dhg, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, stream));
         finish_rows(rs, nrows, q_ft, {&d_res_d, &d_res_w, &d_res_g, &d_res_gg, &d_res_dg});  // (run_residual_gains' and the direction)
+    }
+
+    // ---- Gauss-Newton product with Jones gains (DESIGN.md "Jones matrices in the Gauss-Newton product") ----------------
+    // gain_weight_block's sequence with the kernels of fv_jones_weight_rows, on a polarized handle: jones and d_jones are
+    // the block's (f1 - f0, t1 - t0, 2, 2, nant) arrays of the handle's precision, hjones the same shape in complex128 or
+    // null (the gather does not run).  The rows' terms take run_residual_jones' buffer; host matrices, direction and hjones
+    // are staged and given back under gain_weight_block's rule, and the terms with them.
+    void jones_weight_block(int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev, const void *weights,
+                            int weights_on_device, const void *jones, int jones_on_device, const void *d_jones,
+                            int d_jones_on_device, double *q_ft, void *hjones, int hjones_on_device) override {
+        check_run(t0, t1, f0, f1);
+        FV_REQUIRE(tpol == 4, "fv_sim_jones_weight_block: Jones gains need a polarized handle");
+        FV_REQUIRE(t1 > t0 && f1 > f0, "fv_sim_jones_weight_block: empty range of times or frequencies");
+        FV_REQUIRE(gain_pairs.nbls == nbls, "fv_sim_jones_weight_block: fv_sim_set_gain_pairs first (after the array is set)");
+        const int64_t nrows = (int64_t)(f1 - f0) * (t1 - t0), L = (int64_t)tpol * nbls;
+        const size_t n = (size_t)nrows * (size_t)L;
+        const size_t nj = (size_t)nrows * 4 * (size_t)gain_pairs.nant;
+        const T *dw = staged<T>(d_res_w, weights, weights_on_device, n);
+        const cplx<T> *djn = staged<cplx<T>>(d_res_g, jones, jones_on_device, nj);
+        const cplx<T> *ddj = staged<cplx<T>>(d_res_dg, d_jones, d_jones_on_device, nj);
+        cplx<double> *dhj = staged_out<cplx<double>>(d_res_gg, hjones, hjones_on_device, nj);
+        cplx<T> *parts[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int j = 0; j < nparts; ++j) parts[j] = static_cast<cplx<T> *>(parts_dev[j]);
+        const RowScratch rs = row_scratch<T>(d_res_sum, nrows, L);
+        d_res_terms.reserve(sizeof(double) * n);
+        launch_jones_weight_rows<T>(stream, nparts, parts, static_cast<cplx<T> *>(vis_dev), dw, nrows, rs,
+                                    {&gain_pairs, djn, dhj, d_res_terms.as<double>(), ddj});
+        if (hjones && !hjones_on_device)
+            FV_HIP(hipMemcpyAsync(hjones, dhj, sizeof(cplx<double>) * nj, hipMemcpyDeviceToHost, stream));
+        finish_rows(rs, nrows, q_ft, {&d_res_d, &d_res_w, &d_res_g, &d_res_gg, &d_res_dg, &d_res_terms});
     }
 
     // Height terms ("w-term expansion"): a non-coplanar array whose heights are small against the wavelength -- every

@@ -333,6 +333,29 @@ class SimHandle:
                                                     d_dev, _lib.ptr(q), hp, h_dev))
         return q
 
+    def jones_weight_block(self, t0, t1, f0, f1, parts, vis, weights, jones, d_jones=None, hjones=None):
+        """``gain_weight_block`` with one 2 x 2 complex matrix per antenna and a direction of such matrices
+        (``fv_sim_jones_weight_block``; ``set_gain_pairs`` first, a polarized handle): with ``S(X; A, B)[x, y] = sum
+        conj(A[y', y]) B[x', x] X[x', y']`` the data model's product and U the sum of ``parts`` -- none to four device
+        tensors; none is the matrices-only direction --, ``U' = S(U; J[a1], J[a2]) + S(V; dJ[a1], J[a2]) + S(V; J[a1],
+        dJ[a2])`` is the tangent of the data model, the transposed product applied to ``2 w U'`` replaces ``parts[0]``
+        (``vis`` when there are no parts) and the returned rows are ``sum w |U'|^2``.  ``vis``: the device tensor a forward
+        run of this handle filled with V, needed with ``d_jones``, with ``hjones`` and without parts, else None.  ``jones``,
+        ``d_jones`` (or None): C-contiguous (f1 - f0, t1 - t0, 2, 2, nant), this engine's complex dtype; ``hjones``: the same
+        shape, complex128, filled with the matrices' block of H p, or None (its kernel does not run).  numpy arrays are host
+        buffers, torch tensors device buffers.  The stored G is what every ``run_*_adjoint`` takes as ``g``.  The call
+        synchronises."""
+        ptrs = (ctypes.c_void_p * max(len(parts), 1))(*[p.data_ptr() for p in parts])
+        vp, _ = _buffer_addr(vis)
+        wp, w_dev = _buffer_addr(weights)
+        jp, j_dev = _buffer_addr(jones)
+        dp, d_dev = _buffer_addr(d_jones)
+        hp, h_dev = _buffer_addr(hjones)
+        q = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
+        _lib.check(self._L.fv_sim_jones_weight_block(self._h, t0, t1, f0, f1, len(parts), ptrs, vp, wp, w_dev, jp, j_dev, dp,
+                                                     d_dev, _lib.ptr(q), hp, h_dev))
+        return q
+
     def run_adjoint(self, t0, t1, f0, f1, g, gflux, accumulate: bool):
         """``gflux += A^T g`` for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_adjoint``).  ``g``: C-contiguous block of
         ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype; ``gflux``: C-contiguous (nsrc, nfreq) real or
@@ -717,7 +740,11 @@ class GPUSimulationEngine(SimulationEngine):
           ``conj(m) 2 w U'`` and the rows are sum w |U'|^2.  A gain direction counts as a direction (alone, no tangent
           pass runs), and ``outputs["ggains"]`` (a host complex128 array of the gains' shape, optional) receives the gain
           block of H p.  Only with ``d_gains`` or ``"ggains"`` one more block holds V, a forward run at the real fluxes.
-          The lattice rule is unchanged: the product acts on the block whatever path produced it.
+          The lattice rule is unchanged: the product acts on the block whatever path produced it.  A fourth element
+          ``("jones", (jones, d_jones))`` -- host arrays (nfreqs, ntimes, 2, 2, nant), ``d_jones`` or None; a polarized run
+          -- makes it the product of ``objective_of``'s chi2 with Jones matrices under the same rules:
+          ``SimHandle.jones_weight_block`` runs per time block and ``outputs["gjones"]`` receives the matrices' block of
+          H p.
         * ``forward_to`` (extra; what ``simulate_vis_gain_solve`` passes): a C-contiguous tensor on this device of the
           result's shape and this run's complex dtype, or True for a new one.  The plain forward run fills it by pointer,
           time block by time block (``SimHandle.run_device``), and stays there: nothing comes to the host, and the tensor
@@ -1257,7 +1284,9 @@ def _gauss_newton_nparts(directions, basis):
 
 def _gauss_newton_holds_v(outputs, gains):
     """Whether a time block of the Gauss-Newton product holds V in one more device block: only with a gain direction or
-    the gain block of H p as an output.  ``gains``: (gains, d_gains) or None."""
+    the gain block of H p as an output.  ``gains``: (gains, d_gains), ("jones", (jones, d_jones)) or None."""
+    if _is_jones(gains):
+        return gains[1][1] is not None or outputs.get(_JONES_OUTPUT) is not None
     return gains is not None and (gains[1] is not None or outputs.get(_GAIN_OUTPUT) is not None)
 
 
@@ -1273,10 +1302,15 @@ def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t
     ``d_gains`` or None) ``gain_weight_block`` takes the block's time steps of them instead, G is ``conj(m) 2 w U'`` and the
     rows are sum w |U'|^2; only with ``d_gains`` or ``outputs["ggains"]`` one more block is filled with V -- ``run_device``
     at the real fluxes, after the parts -- and the block's time steps of ``ggains`` are filled; without a sky direction V's
-    block receives G.  Returns the rows, (f1 - f0, t1 - t0) float64 on the host.  Every call ends synchronised."""
-    ggains = outputs.get(_GAIN_OUTPUT)
-    d_fluxes, d_coefs, d_bls, d_topo = (directions.get(k) for k in _GAUSS_NEWTON_DIRECTIONS)
+    block receives G.  With ``gains = ("jones", (jones, d_jones))`` (host, (f1 - f0, t1 - t0, 2, 2, nant)) it is
+    ``jones_weight_block`` and ``outputs["gjones"]``, under the same rules.  Returns the rows, (f1 - f0, t1 - t0) float64 on
+    the host.  Every call ends synchronised."""
     hold_v = _gauss_newton_holds_v(outputs, gains)
+    jones = _is_jones(gains)
+    if jones:
+        gains = gains[1]
+    ggains = outputs.get(_JONES_OUTPUT if jones else _GAIN_OUTPUT)
+    d_fluxes, d_coefs, d_bls, d_topo = (directions.get(k) for k in _GAUSS_NEWTON_DIRECTIONS)
     nparts = _gauss_newton_nparts(directions, basis)
     quad = np.zeros((f1 - f0, t1 - t0), dtype=np.float64)
     for tb, te, ta, te_ in _time_blocks(h, t0, t1, nblk_t, coord_mgr):
@@ -1307,8 +1341,9 @@ def _run_gauss_newton(h, device, directions, weights, outputs, set_fluxes, t0, t
             quad[:, lo:hi] = h.weight_block(ta, te_, f0, f1, parts, w)
         else:
             hg = _gain_output_block(ggains, lo, hi)
-            quad[:, lo:hi] = h.gain_weight_block(ta, te_, f0, f1, parts, vis, w, _block_input(gains[0], lo, hi),
-                                                 _block_input(gains[1], lo, hi), hg)
+            weight = h.jones_weight_block if jones else h.gain_weight_block
+            quad[:, lo:hi] = weight(ta, te_, f0, f1, parts, vis, w, _block_input(gains[0], lo, hi),
+                                    _block_input(gains[1], lo, hi), hg)
             if hg is not None:
                 ggains[:, lo:hi] = hg
         _adjoints_of_block(h, parts[0] if parts else vis, outputs, lo, hi, t1 - t0, ta, te_, f0, f1, basis)
@@ -1430,14 +1465,21 @@ def _check_objective(p, basis):
 
 def _check_gauss_newton(p, basis):
     if (len(p) not in (3, 4) or not isinstance(p[0], dict) or not isinstance(p[2], dict)
-            or set(p[0]) - set(_GAUSS_NEWTON_DIRECTIONS) or set(p[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT}):
+            or set(p[0]) - set(_GAUSS_NEWTON_DIRECTIONS)
+            or set(p[2]) - set(_OBJECTIVE_OUTPUTS) - {_GAIN_OUTPUT, _JONES_OUTPUT}):
         raise ValueError(f"gauss_newton_of: (directions, weights, outputs) with directions a dict over "
                          f"{_GAUSS_NEWTON_DIRECTIONS} and outputs a dict over {_OBJECTIVE_OUTPUTS}")
     gains = p[3] if len(p) == 4 else None
+    jones = _is_jones(gains)
+    if jones:  # (the same pair, tagged)
+        gains = gains[1]
     if gains is not None and (not isinstance(gains, tuple) or len(gains) != 2 or gains[0] is None):
-        raise ValueError("gauss_newton_of: the fourth element is (gains, d_gains), d_gains or None")
-    if p[2].get(_GAIN_OUTPUT) is not None and gains is None:
+        raise ValueError("gauss_newton_of: the fourth element is (gains, d_gains), d_gains or None"
+                         + (", tagged ('jones', (jones, d_jones)) for Jones matrices" if jones else ""))
+    if p[2].get(_GAIN_OUTPUT) is not None and (gains is None or jones):
         raise ValueError("gauss_newton_of: ggains needs the gains (a fourth element)")
+    if p[2].get(_JONES_OUTPUT) is not None and not jones:
+        raise ValueError("gauss_newton_of: gjones needs the matrices (a fourth element ('jones', (jones, d_jones)))")
     if all(p[0].get(k) is None for k in _GAUSS_NEWTON_DIRECTIONS) and (gains is None or gains[1] is None):
         raise ValueError("gauss_newton_of: no direction given")
     if not basis and (p[0].get("d_beam_coefs") is not None or p[2].get("gcoefs") is not None):
@@ -1497,7 +1539,11 @@ def _prepare_gauss_newton(h, s, p):
 
         def set_fluxes(tangent):
             h.set_sources(s.eq, d_coherency if tangent else s.coherency, s.polarized_sky)
-    if gains is not None:
+    if _is_jones(gains):
+        if not s.polarized:
+            raise ValueError("gauss_newton_of: Jones matrices need polarized=True")
+        _set_gain_pairs(h, s, "gauss_newton_of", zip(("jones", "d_jones"), gains[1]), jones=True)
+    elif gains is not None:
         _set_gain_pairs(h, s, "gauss_newton_of", zip(("gains", "d_gains"), gains))
     return directions, p[1], p[2], set_fluxes, gains
 
@@ -1561,7 +1607,8 @@ _PASSES = {
         sets_adjoint_path=True, prepare=_prepare_objective,
         blocks=lambda p, s: (2.0 if p[1] is None else 2.5) + (8.0 / np.dtype(s.cdt).itemsize if _is_jones(p[3]) else 0.0)),
     # (a block's parts and weights are on the device together: one block per part, half a block of weights, one more
-    # block when V is held; the gains, their direction and the product are under 0.1 % of one)
+    # block when V is held; the gains, their direction and the product are under 0.1 % of one; Jones matrices add the rows'
+    # fp64 terms as in objective_of)
     "gauss_newton_of": _Pass(
         run=lambda h, s, p, n: _run_gauss_newton(h, s.device, p[0], p[1], p[2], p[3], *s.span, n, s.coord_mgr,
                                                  basis=s.use_basis, gains=p[4]),
@@ -1570,7 +1617,8 @@ _PASSES = {
                          or _position_outputs(p[2])),
         refusal="the Gauss-Newton product's position passes run", sets_adjoint_path=True, prepare=_prepare_gauss_newton,
         blocks=lambda p, s: (_gauss_newton_nparts(p[0], s.use_basis) + (0.0 if p[1] is None else 0.5)
-                             + (1.0 if _gauss_newton_holds_v(p[2], p[4]) else 0.0))),
+                             + (1.0 if _gauss_newton_holds_v(p[2], p[4]) else 0.0)
+                             + (8.0 / np.dtype(s.cdt).itemsize if _is_jones(p[4]) else 0.0))),
     "forward_to": _Pass(
         run=lambda h, s, p, n: _run_forward_to(h, p, *s.span, n, s.coord_mgr), prepare=_prepare_forward_to),
 }

@@ -254,6 +254,35 @@ int fv_weight_rows(int device, int precision, int64_t nrows, int64_t row_len, in
 int fv_gain_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
                         const int *ant2, const void *gains, const void *d_gains, int nparts, const void *const *parts, void *vis,
                         const void *weights, double *q_rows, void *hgains);
+/* fv_jones_weight_rows: fv_gain_weight_rows with one 2 x 2 complex (Jones) matrix per antenna and a direction of such
+ * matrices (the kernel pair fv_sim_jones_weight_block queues): the weighting step of a Gauss-Newton product of
+ * fv_jones_residual_chi2's chi2.  The rows (tpol = 4: 4 nbls values, V[x, y] at pol = 2 x + y), the pairs and jones are
+ * fv_jones_residual_chi2's; d_jones: the direction dGamma in jones' layout (nrows, 2, 2, nant), or NULL; parts:
+ * nparts = 0 .. 4 blocks as for fv_weight_rows (nparts = 0, the matrices-only direction, needs d_jones); vis: the forward V
+ * at the real parameters, needed with d_jones or hjones, else it may be NULL.  Per baseline k = (a1, a2), with
+ * G1 = Gamma[a1], G2 = Gamma[a2], H1 = dGamma[a1], H2 = dGamma[a2], U = ((P_0 + P_1) + P_2) + P_3 (0 for nparts = 0) and
+ * S(X; A, B)[x, y] = sum_{x', y'} conj(A[y', y]) B[x', x] X[x', y'] formed as fv_jones_residual_chi2 forms V' = S(V; G1, G2)
+ * (X conj(A) first, then B^T times it), in `precision`, every operation rounded on its own, in this order:
+ *   U' = (S(U; G1, G2) + S(V; H1, G2)) + S(V; G1, H2)    (the first term alone without a direction; the tangent of V')
+ *   G'[x, y] = 2 (w[x, y] U'[x, y])                       quad row += w |U'|^2  (terms formed and added in fp64)
+ *   stored G[x', y'] = sum_{x, y} conj(G2[x', x]) G'[x, y] G1[y', y]   (what the public sky adjoints read)
+ *   hjones[a, y', y] += sum_x conj(G'[x, y]) (G2^T V)[x, y']        for every k with a1[k] = a
+ *   hjones[a, x', x] += sum_y G'[x, y] conj((V conj G1)[x', y])     for every k with a2[k] = a
+ * G is written in place into parts[0], or into vis for nparts = 0 (everything else is read only); q_rows[i] is row i's
+ * sum, reduced as fv_jones_residual_chi2 reduces; over all rows <p, H p> = 2 sum q_rows, the matrices' inner product being
+ * Re sum conj(dGamma) hjones.  hjones: (nrows, 2, 2, nant) complex128, the matrices' block of H p in the convention of
+ * gjones, or NULL (its kernel does not run); every term is formed in fp64 from the inputs of `precision` and added as
+ * fv_jones_residual_chi2 adds gjones -- no floating-point atomics, the same input gives the same bits; an antenna without
+ * a baseline gets exactly 0.  With identity matrices and no direction G and q_rows are fv_weight_rows' bit for bit.  A
+ * weight of exactly 0 flags that one (x, y) sample: G' is exactly 0 there and nothing is added, while the baseline's other
+ * samples still use all four values of U and V; a baseline with all four samples flagged stores G = 0 exactly and neither
+ * its parts nor V are used (NaN or Inf there do not propagate).  A weight that is negative or not finite fails the call
+ * with FV_ERR_ARG and fv_residual_chi2's message after it ran.  An antenna index outside [0, nant), a null jones, nparts
+ * outside 0 .. 4, nparts = 0 without d_jones, a null part, d_jones or hjones without vis and a null q_rows fail with
+ * FV_ERR_ARG before anything runs.  Host pointers. */
+int fv_jones_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
+                         const void *jones, const void *d_jones, int nparts, const void *const *parts, void *vis,
+                         const void *weights, double *q_rows, void *hjones);
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n);
 /* fv_astrom_topo: one time step of the device-side coordinate manager (see fv_sim_set_astrom): eq (3, n) ICRS unit
  * vectors -> topo (3, n) topocentric (east, north, up) unit vectors under one 31-double context -- what matvis'
@@ -705,6 +734,19 @@ int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, v
 int fv_sim_gain_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
                              const void *weights, int weights_on_device, const void *gains, int gains_on_device,
                              const void *d_gains, int d_gains_on_device, double *q_ft, void *hgains, int hgains_on_device);
+/* fv_sim_gain_weight_block with one 2 x 2 complex (Jones) matrix per antenna and a direction of such matrices: the
+ * Gauss-Newton product of fv_sim_run_residual_jones' chi2, on a polarized handle.  The call is fv_sim_gain_weight_block's,
+ * argument for argument, with the two kernels of fv_jones_weight_rows, whose formulas hold baseline by baseline: the stored
+ * G of G' = 2 (w U') is left in parts_dev[0] (in vis_dev for nparts = 0), q_ft are the rows of sum w |U'|^2.  jones,
+ * d_jones: (f1 - f0, t1 - t0, 2, 2, nant) complex of the handle's precision, d_jones or NULL; hjones: the same shape in
+ * complex128, the matrices' block of H p, or NULL.  The device holds one more fp64 value per value of the block (the rows'
+ * terms).  Host matrices, direction and hjones are staged and given back with host weights under the
+ * FFTVIS_HIP_ADJ_KEEP_BYTES rule.  Needs fv_sim_set_gain_pairs.  A null handle, nparts outside 0 .. 4, nparts = 0 without
+ * d_jones, a null part, jones or q_ft, d_jones or hjones without vis_dev, a flag other than 0 or 1, an empty range, missing
+ * pairs and an unpolarized handle fail with FV_ERR_ARG before anything runs; bad weights as for fv_sim_weight_block.      */
+int fv_sim_jones_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
+                              const void *weights, int weights_on_device, const void *jones, int jones_on_device,
+                              const void *d_jones, int d_jones_on_device, double *q_ft, void *hjones, int hjones_on_device);
 /* Which transform fv_sim_run_adjoint uses on a lattice handle (fv_sim_set_array_type1; the forward there is the type-1
  * transform of src/fftvis/cpu/nufft.py:120-175, chosen at cpu_simulate.py:634-637).  path 0 (default): the type-3
  * transform with the roles swapped, as on every other array.  path 1: the transpose of the type-1 slice itself, a type-2

@@ -265,6 +265,51 @@ int main() {
         EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, 0, v, 3, v, v, 0) == FV_ERR_ARG);
         EXPECT(fv_sim_gain_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, 0, v, 0, v, v, 2) == FV_ERR_ARG);
         EXPECT(std::strstr(fv_last_error(), "on_device") != nullptr);
+        // ... and the same with Jones matrices (no tpol: the block is polarized)
+        EXPECT(fv_jones_weight_rows(0, 3, 1, 3, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, -1, 3, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, -3, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "fv_jones_weight_rows: negative shape") != nullptr);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 0, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, nullptr, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "null jones") != nullptr);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, v, nullptr, -1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, v, nullptr, 5, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, v, nullptr, 1, nullptr, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, v, nullptr, 0, parts, v, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "nparts == 0 needs d_jones") != nullptr);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, v, nullptr, 2, hole, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "null part") != nullptr);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, v, v, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, v, v) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "d_jones and hjones need vis") != nullptr);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, nullptr, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, nullptr, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, a, v, nullptr, 1, parts, nullptr, nullptr, nullptr, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, low, a, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(fv_jones_weight_rows(0, 2, 1, 3, 3, a, high, v, nullptr, 1, parts, nullptr, nullptr, v, nullptr) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "fv_jones_weight_rows: antenna index outside [0, nant)") != nullptr);
+        // (no rows and no baselines return before any device call)
+        EXPECT(fv_jones_weight_rows(0, 2, 0, 3, 3, a, a, nullptr, nullptr, 1, parts, nullptr, nullptr, nullptr, nullptr) == FV_OK);
+        EXPECT(fv_sim_jones_weight_block(nullptr, 0, 1, 0, 1, 1, dparts, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "null handle") != nullptr);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, -1, dparts, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 5, dparts, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, nullptr, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 0, nullptr, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "nparts == 0 needs d_jones") != nullptr);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 2, dhole, v, nullptr, 0, v, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, nullptr, 0, nullptr, 0, nullptr, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, nullptr, 0, v, 0, nullptr, 0, nullptr, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "null jones or q_ft") != nullptr);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, dparts, nullptr, nullptr, 0, v, 0, v, 0, v, nullptr, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, dparts, nullptr, nullptr, 0, v, 0, nullptr, 0, v, v, 0) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "d_jones and hjones need vis") != nullptr);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 2, v, 0, v, 0, v, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, -1, v, 0, v, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, 0, v, 3, v, v, 0) == FV_ERR_ARG);
+        EXPECT(fv_sim_jones_weight_block(fake, 0, 1, 0, 1, 1, dparts, v, v, 0, v, 0, v, 0, v, v, 2) == FV_ERR_ARG);
+        EXPECT(std::strstr(fv_last_error(), "on_device") != nullptr);
     }
     // and the gain solve: tpol, shapes, nant, antenna indices, null pointers, flags, max_iter, tol; without a baseline
     // both return before any device call

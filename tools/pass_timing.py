@@ -17,7 +17,8 @@
     objective       forward separate separate_torch fused fused_device              C3, 8 channels  (--wrt, --lattice,
                                                                                     --gains; --config C5: through K = 4)
     gauss_newton    forward composed fused fused_device                             C3, 8 channels  (--case, --gains,
-                                                                                    --d-gains; beam_coefs: --config C5)
+                                                                                    --d-gains, --jones, --d-jones;
+                                                                                    beam_coefs: --config C5)
     gain_solve      forward solve solve_with_forward gauss_newton_products          C3, 8 channels
     jones_solve     forward solve solve_with_forward jones_chi2_steps               C3, 8 channels
 
@@ -52,7 +53,14 @@ direction and the gain block of the product (``--case gains``: that direction al
 ``simulate_vis_gain_gauss_newton``, ``composed`` becomes the tangent and, with --d-gains, the forward to the host, the gain
 product, its tangent, conj(m) 2 w U' and the antennas' sums in torch on the device and the public adjoint on the host
 result, and ``--profile gain_kernels`` runs the kernels of fv_gain_weight_rows, fv_weight_rows and fv_gain_residual_chi2 alone
-on the block's shape, six times each, alternating.  gain_solve: the gains-only solve against a fixed model, 50 iterations
+on the block's shape, six times each, alternating.  --jones puts one 2 x 2 matrix per antenna there instead and --d-jones adds
+a direction of such matrices and the matrices' block of the product (``--case jones``: that direction alone): ``fused`` and
+``fused_device`` call ``simulate_vis_jones_gauss_newton``, ``gain_fused_device`` is ``simulate_vis_gain_gauss_newton`` with the
+diagonal of the same matrices and of the same direction in the same job, ``composed`` becomes the tangent and, with
+--d-jones, the forward to the host, the 2 x 2 products, 2 w U', the transposed product and the antennas' sums in numpy and the
+public adjoint on the host result (on a checkout from before the call: --package DIR --only composed --only
+gain_fused_device), and ``--profile jones_kernels`` runs the kernels of fv_jones_weight_rows, fv_gain_weight_rows and
+fv_weight_rows alone on the block's shape, six times each, alternating.  gain_solve: the gains-only solve against a fixed model, 50 iterations
 per call (every value is the call's wall clock divided by the time steps, as everywhere) -- ``solve`` is
 simulate_vis_gain_solve on a resident model with resident data and weights, ``solve_with_forward`` the same from the sky (one
 forward, then the iterations), ``gauss_newton_products`` as many gains-only products of simulate_vis_gain_gauss_newton, each
@@ -337,7 +345,7 @@ def objective(a, fv, cfg, rng):
 
 
 GAUSS_NEWTON_CASES = {"fluxes": ("fluxes",), "ants": ("ants",), "fluxes_radec": ("fluxes", "radec"), "beam_coefs": ("beam_coefs",),
-                      "gains": ()}  # (no sky direction: --gains --d-gains)
+                      "gains": (), "jones": ()}  # (no sky direction: --gains --d-gains, --jones --d-jones)
 
 
 def gauss_newton(a, fv, cfg, rng):
@@ -379,8 +387,8 @@ def gauss_newton(a, fv, cfg, rng):
     gains = {}
     if a.d_gains and not a.gains:
         raise SystemExit("--d-gains needs --gains")
-    if not names and not a.d_gains:
-        raise SystemExit("--case gains needs --gains --d-gains")
+    if not names and not a.d_gains and not a.d_jones:
+        raise SystemExit("--case gains needs --gains --d-gains, --case jones --jones --d-jones")
     if a.gains:
         nums = list(cfg["ants"])
         nant, nfeed = len(nums), 2 if cfg["polarized"] else 1
@@ -469,6 +477,104 @@ def gauss_newton(a, fv, cfg, rng):
                                                          _lib.ptr(v), _lib.ptr(u), _lib.ptr(w2), _lib.ptr(q), _lib.ptr(hg)))
 
             calls["gain_kernels"] = gain_kernels
+    if a.d_jones and not a.jones:
+        raise SystemExit("--d-jones needs --jones")
+    if a.jones and a.gains:
+        raise SystemExit("--jones or --gains, not both")
+    if a.jones:  # one 2 x 2 matrix per antenna, identity + 0.1 N(0, 1), constant in time, and a direction of 0.1 N(0, 1)
+        nums = list(cfg["ants"])
+        nant = len(nums)
+        jshape = (nant, 2, 2, a.nfreq)
+        j0 = 0.1 * (rng.normal(size=jshape) + 1j * rng.normal(size=jshape))
+        j0[:, 0, 0] += 1
+        j0[:, 1, 1] += 1
+        gains = {"jones": j0.astype(cdt)}
+        if a.d_jones:
+            gains["d_jones"] = (0.1 * (rng.normal(size=jshape) + 1j * rng.normal(size=jshape))).astype(cdt)
+        a1 = [nums.index(b[0]) for b in cfg["baselines"]]
+        a2 = [nums.index(b[1]) for b in cfg["baselines"]]
+        out_names = names + (("jones",) if a.d_jones else ())
+
+        def jones_block(x):  # (nf, nt, 2, 2, nant)
+            return np.ascontiguousarray(np.broadcast_to(x[..., None], jshape + (a.ntimes,)).transpose(3, 4, 1, 2, 0))
+
+        def composed():  # what a caller composes without the new call: U and, with --d-jones, V to the host, the 2 x 2
+            # products, 2 w U', the transposed product and the antennas' sums in numpy, the public adjoint on the host result
+            def product(x, ga, gb):  # sum conj(ga[a1][y', y]) gb[a2][x', x] x[x', y']
+                return np.einsum("...bdk,...ack,...abk->...cdk", np.conj(ga[..., a1]), gb[..., a2], x)
+
+            jb = jones_block(gains["jones"])
+            up = 0
+            if dirs:
+                up = product((fv.simulate_vis_basis_jvp if basis else fv.simulate_vis_jvp)(**cfg, **dirs), jb, jb)
+            out = []
+            if a.d_jones:
+                v = fv.simulate_vis(**cfg)
+                hb = jones_block(gains["d_jones"])
+                up = up + product(v, hb, jb) + product(v, jb, hb)
+            gp = 2 * w * up
+            g1, g2 = jb[..., a1], jb[..., a2]
+            if a.d_jones:  # the antennas' sums of the two sides
+                hj = np.zeros(jb.shape, dtype=np.complex128)
+                m = np.einsum("...ack,...abk->...cbk", g2, v)
+                np.add.at(hj, (Ellipsis, a1), np.einsum("...cdk,...cbk->...bdk", np.conj(gp), m))
+                b = np.einsum("...abk,...bdk->...adk", v, np.conj(g1))
+                np.add.at(hj, (Ellipsis, a2), np.einsum("...cdk,...adk->...ack", gp, np.conj(b)))
+                out.append(hj.sum(axis=1).transpose(3, 1, 2, 0))
+            g = np.einsum("...ack,...cdk,...bdk->...abk", np.conj(g2), gp, g1).astype(cdt)
+            if sky:
+                out.append((fv.simulate_vis_basis_sky_adjoint if basis else fv.simulate_vis_sky_adjoint)(g, **cfg, wrt=sky))
+            if rest:
+                out.append((fv.simulate_vis_basis_adjoint if basis else fv.simulate_vis_position_adjoint)(g, **cfg, wrt=rest))
+            return out
+
+        calls["composed"] = composed
+        if hasattr(fv, "simulate_vis_gain_gauss_newton"):  # the diagonal of the same matrices, in the same job
+            diag = {k.replace("jones", "gains"): np.ascontiguousarray(np.stack([v[:, 0, 0], v[:, 1, 1]], axis=1))
+                    for k, v in gains.items()}
+            gain_names = names + (("gains",) if a.d_jones else ())
+            resident_w = []
+
+            def gain_fused_device():
+                import torch
+
+                if not resident_w:
+                    resident_w.append(torch.from_numpy(w).cuda())
+                    torch.cuda.synchronize()
+                return fv.simulate_vis_gain_gauss_newton(**cfg, **dirs, **diag, weights=resident_w[0], wrt=gain_names)
+
+            calls["gain_fused_device"] = gain_fused_device
+        if a.profile == "jones_kernels":  # (for a kernel trace only) the Jones weighting kernels next to the gain weighting
+            # kernels (the diagonal of the same matrices) and k_weight_rows, alone on the block's shape, alternating
+            def jones_kernels():
+                import ctypes
+                import importlib
+
+                _lib = importlib.import_module(fv.__name__ + "._lib")
+                lib = _lib.lib()
+                rows, L = a.nfreq * a.ntimes, 4 * nbls
+                jb = jones_block(gains["jones"]).reshape(rows, 2, 2, nant)
+                hb = jones_block(gains["d_jones"]).reshape(rows, 2, 2, nant) if a.d_jones else None
+                gb = np.ascontiguousarray(np.stack([jb[:, 0, 0], jb[:, 1, 1]], axis=1))
+                dgb = np.ascontiguousarray(np.stack([hb[:, 0, 0], hb[:, 1, 1]], axis=1)) if a.d_jones else None
+                i1, i2 = np.array(a1, np.int32), np.array(a2, np.int32)
+                u = (rng.normal(size=(rows, L)) + 1j * rng.normal(size=(rows, L))).astype(cdt)
+                v0, w2, q = u[::-1].copy(), w.reshape(rows, L), np.zeros(rows)
+                hj, hg = np.zeros(jb.shape, np.complex128), np.zeros(gb.shape, np.complex128)
+                for _ in range(6):
+                    part, v = u.copy(), v0.copy()
+                    ptrs = (ctypes.c_void_p * 1)(part.ctypes.data)
+                    _lib.check(lib.fv_jones_weight_rows(0, p, rows, nbls, nant, _lib.ptr(i1), _lib.ptr(i2), _lib.ptr(jb),
+                                                        _lib.ptr(hb), 1, ptrs, _lib.ptr(v), _lib.ptr(w2), _lib.ptr(q), _lib.ptr(hj)))
+                    part, v = u.copy(), v0.copy()
+                    ptrs = (ctypes.c_void_p * 1)(part.ctypes.data)
+                    _lib.check(lib.fv_gain_weight_rows(0, p, rows, nbls, 4, nant, _lib.ptr(i1), _lib.ptr(i2), _lib.ptr(gb),
+                                                       _lib.ptr(dgb), 1, ptrs, _lib.ptr(v), _lib.ptr(w2), _lib.ptr(q), _lib.ptr(hg)))
+                    part = u.copy()
+                    ptrs = (ctypes.c_void_p * 1)(part.ctypes.data)
+                    _lib.check(lib.fv_weight_rows(0, p, rows, L, 1, ptrs, _lib.ptr(w2), _lib.ptr(q)))
+
+            calls["jones_kernels"] = jones_kernels
     if a.profile == "kernels":  # (for a kernel trace only) the two streaming kernels alone on the block's shape, alternating
         def kernels():
             import ctypes
@@ -497,17 +603,21 @@ def gauss_newton(a, fv, cfg, rng):
                 resident.append(torch.from_numpy(w).cuda())
                 torch.cuda.synchronize()
             if gains:
-                return fv.simulate_vis_gain_gauss_newton(**cfg, **dirs, **gains, weights=resident[0], wrt=out_names)
+                return with_gains(**cfg, **dirs, **gains, weights=resident[0], wrt=out_names)
             return fv.simulate_vis_gauss_newton(**cfg, **dirs, weights=resident[0], wrt=names)
 
-        if gains:
-            calls["fused"] = lambda: fv.simulate_vis_gain_gauss_newton(**cfg, **dirs, **gains, weights=w, wrt=out_names)
+        if a.jones and not hasattr(fv, "simulate_vis_jones_gauss_newton"):
+            pass  # (a checkout from before the call has ``composed`` and ``gain_fused_device`` alone)
+        elif gains:
+            with_gains = fv.simulate_vis_jones_gauss_newton if a.jones else fv.simulate_vis_gain_gauss_newton
+            calls["fused"] = lambda: with_gains(**cfg, **dirs, **gains, weights=w, wrt=out_names)
+            calls["fused_device"] = fused_device
         else:
             calls["fused"] = lambda: fv.simulate_vis_gauss_newton(**cfg, **dirs, weights=w, wrt=names)
-        calls["fused_device"] = fused_device
+            calls["fused_device"] = fused_device
     vis_bytes = w.size * np.dtype(cdt).itemsize
     head = {"config": a.config, "case": a.case, "precision": p, "polarized": bool(cfg["polarized"]), "wrt": list(names),
-            "gains": bool(a.gains), "d_gains": bool(a.d_gains),
+            "gains": bool(a.gains), "d_gains": bool(a.d_gains), "jones": bool(a.jones), "d_jones": bool(a.d_jones),
             # per call, from the shapes: U to the host and G back / w to the device / the directions and products alone
             "pcie_bytes": {"composed": 2 * vis_bytes, "fused": w.nbytes, "fused_device": 0}, "vis_bytes": vis_bytes}
     return head, calls
@@ -657,16 +767,18 @@ FAMILIES = {
         "separate_over_forward": ("separate", "forward"), "fused_over_separate": ("fused", "separate"),
         "fused_device_over_separate": ("fused_device", "separate"), "fused_device_over_forward": ("fused_device", "forward"),
         "separate_torch_over_separate": ("separate_torch", "separate")}),
-    "gauss_newton": (gauss_newton, "C3", 8, ("case", "gains", "d_gains"), "runs", {
+    "gauss_newton": (gauss_newton, "C3", 8, ("case", "gains", "d_gains", "jones", "d_jones"), "runs", {
         "composed_over_forward": ("composed", "forward"), "fused_over_composed": ("fused", "composed"),
-        "fused_device_over_composed": ("fused_device", "composed"), "fused_device_over_forward": ("fused_device", "forward")}),
+        "fused_device_over_composed": ("fused_device", "composed"), "fused_device_over_forward": ("fused_device", "forward"),
+        "fused_device_over_gain_fused_device": ("fused_device", "gain_fused_device")}),
     "gain_solve": (gain_solve, "C3", 8, (), "runs", {
         "solve_over_forward": ("solve", "forward"), "products_over_solve": ("gauss_newton_products", "solve")}),
     "jones_solve": (jones_solve, "C3", 8, (), "runs", {
         "solve_over_forward": ("solve", "forward"), "chi2_steps_over_solve": ("jones_chi2_steps", "solve")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
-             "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False, "jones": False}  # and their defaults
+             "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False, "jones": False,
+             "d_jones": False}  # and their defaults
 
 
 def main():
@@ -692,9 +804,12 @@ def main():
                          "gauss_newton: the gains in the data model (simulate_vis_gain_gauss_newton)")
     ap.add_argument("--jones", action="store_true", default=None,
                     help="objective: one 2 x 2 matrix per antenna in the data model (simulate_vis_jones_chi2; jones may then "
-                         "be one of --wrt's names; a polarized configuration)")
+                         "be one of --wrt's names; a polarized configuration); gauss_newton: the matrices in the data model "
+                         "(simulate_vis_jones_gauss_newton)")
     ap.add_argument("--d-gains", action="store_true", default=None,
                     help="gauss_newton, with --gains: a gain direction, and the gain block among the products")
+    ap.add_argument("--d-jones", action="store_true", default=None,
+                    help="gauss_newton, with --jones: a direction of 2 x 2 matrices, and the matrices' block among the products")
     ap.add_argument("--precision", type=int, choices=[1, 2], default=None, help="2: the configuration in fp64 at eps 6e-8")
     ap.add_argument("--case", choices=list(GAUSS_NEWTON_CASES), default=None,
                     help="gauss_newton: the direction and the products (default fluxes; beam_coefs: --config C5; gains: no "
