@@ -3272,15 +3272,51 @@ class Nufft3 {
         yd_cells = b_cells;
         yd_pairs = (double)a->npts * geo.d[1].na;
     }
-    // slices of the rows for a launch over nfg frequencies: enough workgroups to fill the chip a few times over
-    static void yd_slices(int na_y, int nwg, int nfg, int &rps, int &nslices) {
-        const int want = (int)std::min<int64_t>(16, std::max<int64_t>(1, cdiv(2048, std::max(1, nwg * nfg))));
-        rps = (int)cdiv(cdiv(na_y, want), YD_RT) * YD_RT;
+    // Resident workgroups of k_ydirect on this plan's device (occupancy x compute units): asked once, kept here; the
+    // caller hands one plan's answer to the other plans of its device (yd_slots).
+    int yd_slots = 0;
+    int yd_slot_count() {
+        if (!yd_slots) {
+            const int smem = (int)yd_smem_bytes();
+            int dev = 0, cus = 0, per_cu = 0;
+            FV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ydirect), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+            FV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ydirect, YD_THREADS, (size_t)smem));
+            FV_HIP(hipGetDevice(&dev));
+            FV_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+            yd_slots = std::max(1, per_cu * cus);
+        }
+        return yd_slots;
+    }
+    // Slices of the rows for a launch of nwg ranges x nft (frequency, transform) planes.  Slices are whole tiles.  A
+    // workgroup's time goes with its tiles (plus about one tile of set-up and of its first, uncovered request), and the
+    // launch runs in rounds of the resident slots, whose workgroups do not end together (half a workgroup's time more,
+    // on average): the count with the least rounds x (tiles + 1) + (tiles + 1) / 2 is taken, the smaller count on a
+    // tie.  FFTVIS_HIP_YD_SLICES=n (read per run) forces n, clamped to what the rows allow.  Serves the buffer's size
+    // and the launch alike.
+    static constexpr int YD_MAX_SLICES = 32;
+    void yd_slices(int na_y, int nwg, int nft, int &rps, int &nslices) {
+        const int tiles = (int)cdiv(na_y, YD_RT);
+        const char *e = std::getenv("FFTVIS_HIP_YD_SLICES");
+        int want = e ? std::atoi(e) : 0;
+        if (want < 1) {
+            const int64_t slots = yd_slot_count(), base = (int64_t)std::max(1, nwg) * std::max(1, nft);
+            int64_t best = 0;
+            for (int n = 1; n <= std::min(tiles, YD_MAX_SLICES); ++n) {
+                const int tps = (int)cdiv(tiles, n), ns = (int)cdiv(tiles, tps);
+                const int64_t cost = (2 * cdiv(base * ns, slots) + 1) * (tps + 1);  // twice the estimate
+                if (!want || cost < best) {
+                    best = cost;
+                    want = n;
+                }
+            }
+        }
+        want = std::max(1, std::min(want, tiles));
+        rps = (int)cdiv(tiles, want) * YD_RT;
         nslices = (int)cdiv(na_y, rps);
     }
-    static size_t yd_vals_bytes(int na_y, int nwg, int nfg, int tg, int64_t npts) {
+    size_t yd_vals_bytes(int na_y, int nwg, int nfg, int tg, int64_t npts) {
         int rps, ns;
-        yd_slices(na_y, nwg, nfg, rps, ns);
+        yd_slices(na_y, nwg, nfg * tg, rps, ns);
         return sizeof(cplx<double>) * (size_t)ns * nfg * tg * (size_t)npts;
     }
     const T *spread_dec_y() {  // the y table the spread applies: the inner deconvolution, or ones under direct y sums
@@ -4166,7 +4202,7 @@ void Nufft3<T>::fft(int ntrans, Nufft3 *mate) {
     fused_active = false;
 }
 
-// The targets' values from the x-pass output B (k_ydirect): one launch over (group ranges, frequencies, row slices).
+// The targets' values from the x-pass output B (k_ydirect): one launch over (group ranges, transforms, row slices).
 template <typename T>
 void Nufft3<T>::ydirect_sum(int ntrans, const cplx<T> *B) {
     if constexpr (sizeof(T) == 8) {
@@ -4180,21 +4216,20 @@ void Nufft3<T>::ydirect_sum(int ntrans, const cplx<T> *B) {
         a.plane = (int64_t)y.na * b_pitch();
         a.blk_stride = blk ? ((int64_t)y.na << blk) : 4;
         a.row_stride = blk ? (1 << blk) : b_pitch();
-        yd_slices(y.na, a.nwg, a.nfg, a.rps, a.nslices);
-        const size_t need = sizeof(cplx<double>) * (size_t)a.nslices * a.nfg * tg * (size_t)a.npts;
+        a.tg = tg;
+        FV_REQUIRE(a.blk >= 2 && a.blk <= 4 && a.plane < ((int64_t)1 << 31), "direct y sums: blocks of 4 to 16 elements, 32-bit cell offsets");
+        yd_slices(y.na, a.nwg, ntrans, a.rps, a.nslices);
+        const size_t need = sizeof(cplx<double>) * (size_t)a.nslices * ntrans * (size_t)a.npts;
         if (yd_vals.cap < need) {  // (the caller reserves it before the run: never in the middle of one)
             FV_HIP(hipStreamSynchronize(stream));
             yd_vals.reserve(need);
         }
         yd_args.rps = a.rps;
         yd_args.nslices = a.nslices;
-        const size_t smem = yd_smem_bytes(tg);
-        const dim3 grid((unsigned)a.nwg, (unsigned)a.nfg, (unsigned)a.nslices);
-        auto kern = tg == 1 ? k_ydirect<1> : tg == 2 ? k_ydirect<2> : k_ydirect<4>;
-        // per device, so not cached in a process-wide flag (handles may sit on several GPUs)
-        FV_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(kern, grid, dim3(YD_THREADS), smem, stream, reinterpret_cast<const cplx<double> *>(B), yd_scale, a,
-                           yd_vals.as<cplx<double>>());
+        yd_slot_count();  // (sets the kernel's LDS limit on this device, once)
+        const dim3 grid((unsigned)a.nwg, (unsigned)ntrans, (unsigned)a.nslices);
+        hipLaunchKernelGGL(k_ydirect, grid, dim3(YD_THREADS), yd_smem_bytes(), stream, reinterpret_cast<const cplx<double> *>(B),
+                           yd_scale, a, yd_vals.as<cplx<double>>());
     } else {
         (void)ntrans;
         (void)B;

@@ -4623,7 +4623,8 @@ class Sim : public SimBase {
         const int64_t npts = (int64_t)ptv.size();
         // (the rule below cannot hold even if every group's columns are distinct: no tables)
         if (!forced && (double)npts * y.na > ydirect_gate() * ((double)G * w) * 0.5 * y.n2 * std::log2((double)y.n2)) return skip("too many points per u");
-        if (blk > 4) return skip("column blocks wider than 16 elements");
+        if (blk < 2 || blk > 4) return skip("column blocks of fewer than 4 or more than 16 elements");
+        if ((int64_t)y.na * xp >= ((int64_t)1 << 31)) return skip("a plane of B past the kernel's 32-bit cell offsets");
         // footprints per (frequency, group): compact (or stored) column of every footprint cell, x-weights
         const int P = x.sP(), cnt = x.cnt(), stride = x.nos(), ncols = n0->xcols_with(cp && cp->use ? cp->ncc : 0);
         const double beta = n0->ker.beta, c4 = n0->ker.c;
@@ -4650,7 +4651,7 @@ class Sim : public SimBase {
             }
         }
         // work ranges: contiguous groups whose distinct blocks fit the tile at every frequency
-        const int nbcap = std::min({YD_NBMAX, YD_RAWROW / (BE + 1), (8 * YD_NLD) >> blk});
+        const int nbcap = yd_nbcap(blk);
         std::vector<int> wg;
         std::vector<std::vector<int>> cur(nfg), trial(nfg);
         auto blocks_with = [&](int g) {
@@ -6035,12 +6036,22 @@ class Sim : public SimBase {
                 YPlan *yp = ydirect_plan((int)pi, pr, fa, fb, n0, cp, ymode == 1);
                 if (!yp->built || !(ymode == 1 || yp->use)) continue;
                 y_plan_of[gi * pairs.size() + pi] = yp;
-                vals_need = std::max(vals_need, Nufft3<T>::yd_vals_bytes(yp->a.na_y, yp->a.nwg, fb - fa, tg, yp->a.npts));
+                vals_need = std::max(vals_need, n0->yd_vals_bytes(yp->a.na_y, yp->a.nwg, fb - fa, tg, yp->a.npts));
+                if (std::getenv("FFTVIS_HIP_DEBUG_YDIRECT")) {
+                    int rps, ns;
+                    n0->yd_slices(yp->a.na_y, yp->a.nwg, (fb - fa) * tg, rps, ns);
+                    const int wgs = yp->a.nwg * (fb - fa) * tg * ns;
+                    std::fprintf(stderr, "ydirect launch pair %d channels [%d, %d): %d slices of %d rows (na_y %d), %d workgroups, %d per round\n",
+                                 (int)pi, fa, fb, ns, rps, yp->a.na_y, wgs, n0->yd_slot_count());
+                }
             }
         }
         FV_HIP(hipStreamSynchronize(n0->stream));
         if (vals_need)
-            for (int li = 0; li < r.nlanes_used; ++li) lanes[li].plan[0]->yd_vals.reserve(vals_need);
+            for (int li = 0; li < r.nlanes_used; ++li) {
+                lanes[li].plan[0]->yd_vals.reserve(vals_need);
+                lanes[li].plan[0]->yd_slots = n0->yd_slots;  // one device: asked once
+            }
     }
 
     // The unit loop: per (one or two time steps, source chunk) the per-time preparation, then per (frequency group, beam

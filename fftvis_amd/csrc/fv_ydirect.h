@@ -11,12 +11,13 @@
 // (k_interp<.., VALS>) still divides by the source kernel's transform in BOTH dimensions, like Nufft3::zdirect does for z.
 //
 // Work split: a workgroup takes a range of adjacent u-groups (<= YD_NG; their footprints share B's 64-byte column
-// blocks), one frequency of the group with all its transforms, and a slice of the rows.  Per tile of YD_RT rows it
-//   (a) streams the range's distinct column blocks of B through LDS (whole blocks: rows of a block are contiguous) and
-//       contracts each group's w columns into D[group][row][transform],
-//   (b) lets every thread carry exp(i theta row) for its <= YD_PTM points by multiplication -- re-seeded from sincos
+// blocks), one transform of one frequency of the group, and a slice of the rows.  Per tile of YD_RT rows it
+//   (a) moves the range's distinct column blocks of B (whole blocks: rows of a block are contiguous) from the registers
+//       they were loaded into to LDS, and at once requests the next tile's -- that request is outstanding during (b), (c),
+//   (b) contracts each group's w columns into D[group][row],
+//   (c) lets every thread carry exp(i theta row) for its <= YD_PTM points by multiplication -- re-seeded from sincos
 //       every YD_RESEED rows -- and add D's rows from LDS,
-//   (c) and at the end writes one partial sum per (row slice, transform, point); the gather adds the slices in order.
+// and at the end writes one partial sum per (row slice, transform, point); the gather adds the slices in order.
 // All tables are host-built per (targets, group geometry): Sim::ydirect_plan.
 #pragma once
 
@@ -24,18 +25,27 @@
 
 namespace fv {
 
-constexpr int YD_THREADS = 256;
+constexpr int YD_THREADS = 512;
 constexpr int YD_RT = 32;       // rows per tile
-constexpr int YD_NG = 8;        // u-groups per workgroup: YD_NG * YD_RT contraction items = one per thread
-constexpr int YD_PTM = 4;       // evaluation points per thread
+constexpr int YD_NG = 8;        // u-groups per workgroup: YD_NG * YD_RT contraction items, re and im on a thread each
+constexpr int YD_PTM = 2;       // evaluation points per thread
 constexpr int YD_NBMAX = 20;    // distinct column blocks per workgroup (table width)
 constexpr int YD_RAWROW = 100;  // LDS cells per tile row: blocks * (block elements + 1 of padding) <= this
 constexpr int YD_RAW = YD_RAWROW * YD_RT;
-constexpr int YD_NLD = 11;      // cells of a tile a thread loads per transform: blocks * block elements <= 8 YD_NLD
+constexpr int YD_NLD = 5;       // cells of a tile a thread loads: blocks * block elements <= YD_NLD * YD_THREADS / YD_RT
 constexpr int YD_RESEED = 128;  // rows between two sincos seeds of a point's phase (a multiple of YD_RT)
-static_assert(YD_NG * YD_RT == YD_THREADS, "one contraction item per thread");
+constexpr int YD_WCH = 4;       // footprint cells the contraction requests from LDS at a time
+constexpr int YD_RCH = 4;       // rows of D the walk requests from LDS at a time
+static_assert(2 * YD_NG * YD_RT == YD_THREADS, "one contraction item per pair of threads");
 static_assert(YD_RESEED % YD_RT == 0, "seeds fall on tile starts");
-static_assert(YD_RT == 32, "a tile row index is five bits (k_ydirect's shifts)");
+static_assert(YD_RT == 32 && YD_RT % YD_RCH == 0, "a tile row index is five bits (k_ydirect's shifts)");
+static_assert(MAX_W % YD_WCH == 0, "whole chunks of footprint cells");
+
+// distinct column blocks of 1 << blk elements a workgroup's tile holds (the range builder of Sim::ydirect_plan and the kernel)
+__host__ __device__ constexpr int yd_nbcap(int blk) {
+    const int a = YD_RAWROW / ((1 << blk) + 1), b = (YD_NLD * YD_THREADS / YD_RT) >> blk;
+    return a < b ? (a < YD_NBMAX ? a : YD_NBMAX) : (b < YD_NBMAX ? b : YD_NBMAX);
+}
 
 struct YdArgs {
     int w, nfg, nwg, ngroups;
@@ -43,7 +53,8 @@ struct YdArgs {
     int blk;              // log2 of the block width in elements (plain planes: pseudo-blocks of 4 inside a row)
     int64_t blk_stride, row_stride;  // element (bid, row, el) of a plane sits at bid blk_stride + row row_stride + el
     int rps, nslices;     // rows per slice (whole tiles), slices
-    int64_t plane;        // elements between two transforms of B
+    int tg;               // transforms per frequency
+    int64_t plane;        // elements between two transforms of B (below 2^31: the kernel's cell offsets are 32-bit)
     int64_t npts;         // evaluation points
     double hy, btcy;
     const int *wg;        // [nwg][4]: first group, groups, first point, points
@@ -55,36 +66,37 @@ struct YdArgs {
     const int *ptg;       // [npts] its u-group
 };
 
-inline size_t yd_smem_bytes(int tg) {
-    return sizeof(cplx<double>) * (size_t)(YD_RAW + YD_NG * YD_RT * tg) + sizeof(double) * YD_NG * MAX_W +
+inline size_t yd_smem_bytes() {
+    return sizeof(cplx<double>) * (size_t)(YD_RAW + YD_NG * YD_RT) + sizeof(double) * YD_NG * MAX_W +
            sizeof(int) * (YD_NG * MAX_W + YD_NBMAX);
 }
 
-template <int TG>
-__global__ __launch_bounds__(YD_THREADS, 2) void k_ydirect(const cplx<double> *__restrict__ B, const double *__restrict__ scale,
+__global__ __launch_bounds__(YD_THREADS, 4) void k_ydirect(const cplx<double> *__restrict__ B, const double *__restrict__ scale,
                                                           YdArgs a, cplx<double> *__restrict__ vals) {
     extern __shared__ __attribute__((aligned(16))) unsigned char yd_smem[];
     cplx<double> *raw = reinterpret_cast<cplx<double> *>(yd_smem);
     cplx<double> *D = raw + YD_RAW;
-    double *xw_s = reinterpret_cast<double *>(D + YD_NG * YD_RT * TG);
+    double *xw_s = reinterpret_cast<double *>(D + YD_NG * YD_RT);
     int *cref_s = reinterpret_cast<int *>(xw_s + YD_NG * MAX_W);
     int *bid_s = cref_s + YD_NG * MAX_W;
-    const int tid = threadIdx.x, wgi = blockIdx.x, fg = blockIdx.y, sl = blockIdx.z;
+    const int tid = threadIdx.x, wgi = blockIdx.x, ft = blockIdx.y, fg = ft / a.tg, sl = blockIdx.z;  // ft: (frequency, transform)
     const int g0 = a.wg[4 * wgi], ng = min(a.wg[4 * wgi + 1], YD_NG), p0 = a.wg[4 * wgi + 2],
               np = min(a.wg[4 * wgi + 3], YD_THREADS * YD_PTM);
     const int BE = 1 << a.blk, BEP = BE + 1;
-    const int nb = min(a.blkcnt[fg * a.nwg + wgi], min(YD_NBMAX, min(YD_RAWROW / BEP, (8 * YD_NLD) >> a.blk)));
+    const int nb = min(a.blkcnt[fg * a.nwg + wgi], yd_nbcap(a.blk));
     const int rbeg = sl * a.rps, rend = min(a.na_y, rbeg + a.rps);
     for (int i = tid; i < ng * a.w; i += YD_THREADS) {
         const int gi = i / a.w, g = i - gi * a.w;
         const int64_t src = ((int64_t)fg * a.ngroups + g0 + gi) * a.w + g;
+        const int c = a.cref[src];
         xw_s[gi * MAX_W + g] = a.xw[src];
-        cref_s[gi * MAX_W + g] = a.cref[src];
+        // where the cell's tile row 0 sits in raw, in bytes: the contraction adds its row and its half
+        cref_s[gi * MAX_W + g] = (min(c >> 4, nb - 1) * YD_RT * BEP + (c & (BE - 1))) * (int)sizeof(cplx<double>);
     }
     if (tid < nb) bid_s[tid] = a.blkid[((int64_t)fg * a.nwg + wgi) * YD_NBMAX + tid];
     // this thread's points: phase step, slot of its group's D rows
     const double sc = scale[fg];
-    double th[YD_PTM], dr[YD_PTM], di[YD_PTM], er[YD_PTM], ei[YD_PTM], accr[YD_PTM][TG], acci[YD_PTM][TG];
+    double th[YD_PTM], dr[YD_PTM], di[YD_PTM], er[YD_PTM], ei[YD_PTM], accr[YD_PTM], acci[YD_PTM];
     int dofs[YD_PTM];
     bool kon[YD_PTM];  // wave-uniform: some lane of this wave owns a k-th point
 #pragma unroll
@@ -93,94 +105,107 @@ __global__ __launch_bounds__(YD_THREADS, 2) void k_ydirect(const cplx<double> *_
         kon[k] = k * YD_THREADS + (tid & ~63) < np;
         const int gp = p0 + (p < np ? p : 0);
         th[k] = a.hy * (sc * a.ptv[gp] - sc * a.btcy);
-        dofs[k] = min(max(a.ptg[gp] - g0, 0), YD_NG - 1) * YD_RT * TG;
+        dofs[k] = min(max(a.ptg[gp] - g0, 0), YD_NG - 1) * YD_RT;
         sincos(th[k], &di[k], &dr[k]);
         er[k] = 1.0;
         ei[k] = 0.0;
-#pragma unroll
-        for (int t = 0; t < TG; ++t) accr[k][t] = acci[k][t] = 0.0;
+        accr[k] = acci[k] = 0.0;
     }
-    const int cgi = tid / YD_RT, crow = tid % YD_RT;  // this thread's contraction item
+    const int citem = tid >> 1, cpart = tid & 1;  // this thread's contraction item, and its half of it: re or im
+    const int cgi = citem / YD_RT, crow = citem % YD_RT;
     const int half = a.na_y / 2;
     const int per = YD_RT << a.blk, pshift = a.blk + 5;  // cells of a block's tile rows (YD_RT = 32)
-    const int nitems = min(nb * per, YD_NLD * YD_THREADS);
-    // A tile's cells of one transform, YD_NLD per thread: every load is issued before the first one is used, and the
-    // next (tile, transform)'s are issued as soon as this one's have gone to LDS -- in flight under the contraction
-    // and the sums.  (One load per loop trip, each waited for, cost ten memory round trips per tile and transform.)
-    cplx<double> pf[YD_NLD];
-    auto issue = [&](int r0, int t) {
-        const cplx<double> *pl = B + ((int64_t)fg * TG + t) * a.plane;
+    __syncthreads();  // the tables are in place
+    // This thread's YD_NLD cells of a tile.  A block's tile rows are `per` cells and per divides YD_THREADS (2 <= blk <= 4),
+    // so the cells share their tile row and block element and sit YD_THREADS / per blocks apart: one row, one place in
+    // LDS and a fixed step, and per cell the offset in the plane of B relative to the tile's first row -- the same for
+    // every tile.  A cell past the range's blocks or the row's end has no bit in `live`: it loads the tile's first cell
+    // instead and zero is stored for it.  Every slot lies inside raw.
+    const int lrow = (tid & (per - 1)) >> a.blk, lel = tid & (BE - 1), lbstep = YD_THREADS >> pshift;
+    const int lofs = ((tid >> pshift) * YD_RT + lrow) * BEP + lel, lstep = lbstep * YD_RT * BEP;
+    unsigned goff[YD_NLD], live = 0;
 #pragma unroll
-        for (int j = 0; j < YD_NLD; ++j) {
-            const int i = tid + j * YD_THREADS;
-            const int lb = i >> pshift, rem = i & (per - 1), row = rem >> a.blk, el = rem & (BE - 1);
-            pf[j] = {0.0, 0.0};
-            if (i < nitems) {
-                const int bid = bid_s[lb];
-                if (r0 + row < rend && (bid << a.blk) + el < a.xp)
-                    pf[j] = pl[(int64_t)bid * a.blk_stride + (int64_t)(r0 + row) * a.row_stride + el];
+    for (int j = 0; j < YD_NLD; ++j) {
+        const int lb = (tid >> pshift) + j * lbstep;
+        goff[j] = 0;
+        if (lb < nb) {
+            const int bid = bid_s[lb];
+            if ((bid << a.blk) + lel < a.xp) {
+                goff[j] = (unsigned)((int64_t)bid * a.blk_stride + (int64_t)lrow * a.row_stride + lel);
+                live |= 1u << j;
             }
         }
-    };
-    __syncthreads();  // the tables are in place
-    if (rbeg < rend) issue(rbeg, 0);
-    for (int r0 = rbeg, tile = 0; r0 < rend; r0 += YD_RT, ++tile) {
-        for (int t = 0; t < TG; ++t) {
-            __syncthreads();  // the last contraction has read its raw cells, the last tile's sums their D rows
+    }
+    // Tile r0 stores its cells -- requested one tile earlier -- to LDS and requests the next tile's before it contracts
+    // and walks, so a whole request is outstanding under both.  (The loop starts one tile early so that the load
+    // sequence exists once; the first trip only requests.)
+    const cplx<double> *plane = B + (int64_t)ft * a.plane;
+    cplx<double> pf[YD_NLD];
+    for (int r0 = rbeg - YD_RT; r0 < rend; r0 += YD_RT) {
+        if (r0 >= rbeg) {
+            // (the last contraction's reads of raw ended before its barrier; the barrier below ends the last walk's of D)
+            const unsigned ok = r0 + lrow < rend ? live : 0;
 #pragma unroll
-            for (int j = 0; j < YD_NLD; ++j) {
-                const int i = tid + j * YD_THREADS;
-                const int lb = i >> pshift, rem = i & (per - 1), row = rem >> a.blk, el = rem & (BE - 1);
-                if (i < nitems) raw[(lb * YD_RT + row) * BEP + el] = pf[j];
-            }
-            {
-                const int nt = t + 1 < TG ? t + 1 : 0, nr0 = t + 1 < TG ? r0 : r0 + YD_RT;
-                if (nr0 < rend) issue(nr0, nt);
-            }
-            __syncthreads();
-            if (cgi < ng) {
-                double sr = 0.0, si = 0.0;
-                for (int g = 0; g < a.w; ++g) {
-                    const int c = cref_s[cgi * MAX_W + g];
-                    const cplx<double> v = raw[(min(c >> 4, nb - 1) * YD_RT + crow) * BEP + (c & (BE - 1))];
-                    const double wv = xw_s[cgi * MAX_W + g];
-                    sr += v.re * wv;
-                    si += v.im * wv;
+            for (int j = 0; j < YD_NLD; ++j) raw[lofs + j * lstep] = (ok >> j) & 1 ? pf[j] : cplx<double>{0.0, 0.0};
+        }
+        if (r0 + YD_RT < rend) {
+            const cplx<double> *base = plane + (int64_t)(r0 + YD_RT) * a.row_stride;  // uniform; a row below rend
+            const bool rowin = r0 + YD_RT + lrow < rend;
+#pragma unroll
+            for (int j = 0; j < YD_NLD; ++j) pf[j] = base[rowin ? goff[j] : 0u];
+        }
+        if (r0 < rbeg) continue;
+        __syncthreads();
+        if (cgi < ng) {  // D[group][row] = sum over the footprint, cells in increasing g; YD_WCH requested at a time
+            const char *mine = reinterpret_cast<const char *>(raw) + (crow * BEP * 2 + cpart) * (int)sizeof(double);
+            double sum = 0.0;
+            for (int gb = 0; gb < a.w; gb += YD_WCH) {
+                int c[YD_WCH];
+                double wv[YD_WCH], v[YD_WCH];
+#pragma unroll
+                for (int q = 0; q < YD_WCH; ++q) {
+                    c[q] = cref_s[cgi * MAX_W + gb + q];
+                    wv[q] = xw_s[cgi * MAX_W + gb + q];
                 }
-                D[(cgi * YD_RT + crow) * TG + t] = {sr, si};
+#pragma unroll
+                for (int q = 0; q < YD_WCH; ++q)  // (table cells past w are never written: cell 0 then, unused)
+                    v[q] = *reinterpret_cast<const double *>(mine + (gb + q < a.w ? c[q] : 0));
+#pragma unroll
+                for (int q = 0; q < YD_WCH; ++q)
+                    if (gb + q < a.w) sum += v[q] * wv[q];
             }
+            reinterpret_cast<double *>(D)[2 * (cgi * YD_RT + crow) + cpart] = sum;
         }
         __syncthreads();
-        if (tile % (YD_RESEED / YD_RT) == 0) {
+        if ((r0 - rbeg) % YD_RESEED == 0) {
 #pragma unroll
             for (int k = 0; k < YD_PTM; ++k)
                 if (kon[k]) sincos(th[k] * (double)(r0 - half), &ei[k], &er[k]);
         }
-#pragma unroll 2
-        for (int row = 0; row < YD_RT; ++row) {
 #pragma unroll
-            for (int k = 0; k < YD_PTM; ++k) {
-                if (!kon[k]) continue;  // wave-uniform
-                const cplx<double> *d = D + dofs[k] + row * TG;
+        for (int k = 0; k < YD_PTM; ++k) {
+            if (!kon[k]) continue;  // wave-uniform
+            const cplx<double> *d = D + dofs[k];
+#pragma unroll 1
+            for (int rb = 0; rb < YD_RT; rb += YD_RCH) {  // YD_RCH rows of D requested at a time
+                cplx<double> v[YD_RCH];
 #pragma unroll
-                for (int t = 0; t < TG; ++t) {
-                    const cplx<double> v = d[t];
-                    accr[k][t] += v.re * er[k] - v.im * ei[k];
-                    acci[k][t] += v.re * ei[k] + v.im * er[k];
+                for (int q = 0; q < YD_RCH; ++q) v[q] = d[rb + q];
+#pragma unroll
+                for (int q = 0; q < YD_RCH; ++q) {
+                    accr[k] += v[q].re * er[k] - v[q].im * ei[k];
+                    acci[k] += v[q].re * ei[k] + v[q].im * er[k];
+                    const double e2 = er[k] * dr[k] - ei[k] * di[k];
+                    ei[k] = er[k] * di[k] + ei[k] * dr[k];
+                    er[k] = e2;
                 }
-                const double e2 = er[k] * dr[k] - ei[k] * di[k];
-                ei[k] = er[k] * di[k] + ei[k] * dr[k];
-                er[k] = e2;
             }
         }
     }
 #pragma unroll
     for (int k = 0; k < YD_PTM; ++k) {
         const int p = tid + k * YD_THREADS;
-        if (p >= np) continue;
-#pragma unroll
-        for (int t = 0; t < TG; ++t)
-            vals[(((int64_t)sl * a.nfg + fg) * TG + t) * a.npts + p0 + p] = {accr[k][t], acci[k][t]};
+        if (p < np) vals[((int64_t)sl * a.nfg * a.tg + ft) * a.npts + p0 + p] = {accr[k], acci[k]};
     }
 }
 
