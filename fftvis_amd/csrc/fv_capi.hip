@@ -29,6 +29,31 @@ static int guarded(F &&f) {
     }
 }
 
+// What the entry points' checks share.  f(T{}), T the real type of `precision`: a body is written once for both
+template <typename F>
+static void with_precision(int precision, F &&f) {
+    FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    if (precision == 1)
+        f(float{});
+    else
+        f(double{});
+}
+template <typename F>
+static int guarded(int precision, F &&f) {
+    return guarded([&] { with_precision(precision, f); });
+}
+static void require_on_device_flags(std::initializer_list<int> flags) {
+    int bits = 0;
+    for (int f : flags) bits |= f;
+    FV_REQUIRE((bits & ~1) == 0, "on_device flags must be 0 or 1");
+}
+// every baseline's antenna pair lies in [0, nant); `entry` names the caller in the message
+static void require_pairs(const char *entry, int64_t nbls, int nant, const int *ant1, const int *ant2) {
+    for (int64_t k = 0; k < nbls; ++k)
+        FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
+                   std::string(entry) + ": antenna index outside [0, nant)");
+}
+
 struct StreamGuard {
     hipStream_t s = nullptr;
     StreamGuard() { FV_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
@@ -325,8 +350,8 @@ static void coherency_host(int device, int variant, int64_t n, const void *bi, c
 }
 
 // The row passes on host arrays (fv_residual_chi2, fv_gain_residual_chi2, fv_jones_residual_chi2, fv_weight_rows,
-// fv_gain_weight_rows, fv_jones_weight_rows): every array is copied into a buffer of its own on the call's stream (null stays null), the launcher
-// queues the kernels, what was computed in place is copied back and collect_rows ends the call.
+// fv_gain_weight_rows, fv_jones_weight_rows): every array is copied into a buffer of its own on the call's stream (null
+// stays null), the launcher queues the kernels, what was computed in place is copied back and collect_rows ends the call.
 template <typename X>
 static X *to_device(hipStream_t s, DevBuf &buf, const void *host, size_t n) {
     if (!host) return nullptr;
@@ -334,90 +359,85 @@ static X *to_device(hipStream_t s, DevBuf &buf, const void *host, size_t n) {
     FV_HIP(hipMemcpyAsync(buf.p, host, sizeof(X) * n, hipMemcpyHostToDevice, s));
     return buf.as<X>();
 }
+// a call's calibration as the caller gave it: the pairs, the rows' gains or matrices x, their direction dx (or null) and
+// where the gradient goes (complex128, the shape of x; or null)
+struct HostCal {
+    Cal kind = Cal::None;
+    int tpol = 1, nant = 0;
+    int64_t nbls = 0;
+    const int *ant1 = nullptr, *ant2 = nullptr;
+    const void *x = nullptr, *dx = nullptr;
+    void *grad = nullptr;
+};
+// ... and on the device, for a block of n values with nx entries of x: the pairs of this call, x and dx copied, the
+// gradient's block and (Jones) the rows' terms reserved
+template <typename T>
+struct DeviceCal {
+    GainPairs gp;
+    DevBuf dx, ddx, dgrad, dterms;
+    RowCal<T> cal;
+    DeviceCal(hipStream_t s, const HostCal &c, size_t n, size_t nx) {
+        if (c.kind == Cal::None) return;
+        gp.set(s, c.nant, c.nbls, c.ant1, c.ant2);
+        if (c.grad) dgrad.reserve(sizeof(cplx<double>) * nx);
+        if (c.kind == Cal::Jones) dterms.reserve(sizeof(double) * n);
+        cal = {c.kind, &gp, to_device<cplx<T>>(s, dx, c.x, nx), to_device<cplx<T>>(s, ddx, c.dx, nx), dgrad.as<cplx<double>>(),
+               dterms.as<double>()};
+    }
+};
+// what both passes do with an empty block (true: done): no rows, or rows of no values, whose sums and gradient are zero
+static bool empty_rows(int64_t nrows, int64_t row_len, double *rows, void *grad, size_t nx) {
+    if (nrows > 0 && row_len == 0) {
+        for (int64_t i = 0; i < nrows; ++i) rows[i] = 0.0;
+        if (grad) std::memset(grad, 0, sizeof(cplx<double>) * nx);
+    }
+    return nrows == 0 || row_len == 0;
+}
+// ... and at their end: the gradient's block and the rows' sums come back, and bad input is reported
+template <typename T>
+static void finish_rows_host(hipStream_t s, const DeviceCal<T> &dc, void *grad, size_t nx, const RowScratch &rs, int64_t nrows,
+                             double *rows) {
+    if (grad) FV_HIP(hipMemcpyAsync(grad, dc.dgrad.p, sizeof(cplx<double>) * nx, hipMemcpyDeviceToHost, s));
+    int hbad[2];
+    collect_rows(s, rs, nrows, rows, hbad);
+    throw_if_bad_residual_input(hbad);
+}
 
 template <typename T>
-static void residual_chi2_host(int device, int64_t nrows, int64_t row_len, void *vis, const void *data, const void *weights,
-                               double *chi2_rows) {
-    FV_REQUIRE(nrows >= 0 && row_len >= 0, "fv_residual_chi2: negative shape");
-    FV_REQUIRE((nrows == 0 || row_len == 0 || (vis && data)) && (nrows == 0 || chi2_rows), "fv_residual_chi2: null vis, data or chi2_rows");
+static void residual_rows_host(int device, int64_t nrows, int64_t row_len, void *vis, const void *data, const void *weights,
+                               double *chi2_rows, const HostCal &c = {}) {
+    const size_t n = (size_t)nrows * (size_t)row_len, nx = (size_t)nrows * (size_t)cal_entries(c.kind, c.tpol, c.nant);
+    if (empty_rows(nrows, row_len, chi2_rows, c.grad, nx)) return;
     FV_HIP(hipSetDevice(device));
-    if (nrows == 0) return;
-    if (row_len == 0) {
-        for (int64_t i = 0; i < nrows; ++i) chi2_rows[i] = 0.0;
-        return;
-    }
     StreamGuard sg;
-    const size_t n = (size_t)nrows * (size_t)row_len;
+    DeviceCal<T> dc(sg.s, c, n, nx);
     DevBuf dv, dd, dw, ds;
     const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
     launch_residual<T>(sg.s, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<cplx<T>>(sg.s, dd, data, n),
-                       to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs);
+                       to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs, dc.cal);
     FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    int hbad[2];
-    collect_rows(sg.s, rs, nrows, chi2_rows, hbad);
-    throw_if_bad_residual_input(hbad);
+    finish_rows_host(sg.s, dc, c.grad, nx, rs, nrows, chi2_rows);
 }
 
 template <typename T>
-static void gain_residual_chi2_host(int device, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1, const int *ant2,
-                                    const void *gains, void *vis, const void *data, const void *weights, double *chi2_rows,
-                                    void *ggains) {
-    const int nfeed = tpol == 4 ? 2 : 1;
-    const size_t ng = (size_t)nrows * nfeed * (size_t)nant;
-    if (nrows == 0) return;
-    if (nbls == 0) {
-        for (int64_t i = 0; i < nrows; ++i) chi2_rows[i] = 0.0;
-        if (ggains) std::memset(ggains, 0, sizeof(cplx<double>) * ng);
-        return;
-    }
+static void weight_rows_host(int device, int64_t nrows, int64_t row_len, int nparts, const void *const *parts, void *vis,
+                             const void *weights, double *q_rows, const HostCal &c = {}) {
+    const size_t n = (size_t)nrows * (size_t)row_len, nx = (size_t)nrows * (size_t)cal_entries(c.kind, c.tpol, c.nant);
+    if (empty_rows(nrows, row_len, q_rows, c.grad, nx)) return;
     FV_HIP(hipSetDevice(device));
     StreamGuard sg;
-    const int64_t row_len = (int64_t)tpol * nbls;
-    const size_t n = (size_t)nrows * (size_t)row_len;
-    GainPairs gp;
-    gp.set(sg.s, nant, nbls, ant1, ant2);
-    DevBuf dv, dd, dw, ds, dgn, dgg;
-    if (ggains) dgg.reserve(sizeof(cplx<double>) * ng);
+    DeviceCal<T> dc(sg.s, c, n, nx);
+    DevBuf dp[4], dv, dw, ds;
+    cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int j = 0; j < nparts; ++j) dparts[j] = to_device<cplx<T>>(sg.s, dp[j], parts[j], n);
     const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
-    launch_residual<T>(sg.s, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<cplx<T>>(sg.s, dd, data, n),
-                       to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs,
-                       {&gp, to_device<cplx<T>>(sg.s, dgn, gains, ng), nullptr, dgg.as<cplx<double>>()});
-    FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    if (ggains) FV_HIP(hipMemcpyAsync(ggains, dgg.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
-    int hbad[2];
-    collect_rows(sg.s, rs, nrows, chi2_rows, hbad);
-    throw_if_bad_residual_input(hbad);
-}
-
-template <typename T>
-static void jones_residual_chi2_host(int device, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
-                                     const void *jones, void *vis, const void *data, const void *weights, double *chi2_rows,
-                                     void *gjones) {
-    const size_t nj = (size_t)nrows * 4 * (size_t)nant;
-    if (nrows == 0) return;
-    if (nbls == 0) {
-        for (int64_t i = 0; i < nrows; ++i) chi2_rows[i] = 0.0;
-        if (gjones) std::memset(gjones, 0, sizeof(cplx<double>) * nj);
-        return;
-    }
-    FV_HIP(hipSetDevice(device));
-    StreamGuard sg;
-    const int64_t row_len = 4 * nbls;
-    const size_t n = (size_t)nrows * (size_t)row_len;
-    GainPairs gp;
-    gp.set(sg.s, nant, nbls, ant1, ant2);
-    DevBuf dv, dd, dw, ds, djn, dgj, dt;
-    if (gjones) dgj.reserve(sizeof(cplx<double>) * nj);
-    dt.reserve(sizeof(double) * n);
-    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
-    launch_jones_residual<T>(sg.s, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<cplx<T>>(sg.s, dd, data, n),
-                             to_device<T>(sg.s, dw, weights, n), nrows, rs,
-                             {&gp, to_device<cplx<T>>(sg.s, djn, jones, nj), dgj.as<cplx<double>>(), dt.as<double>()});
-    FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    if (gjones) FV_HIP(hipMemcpyAsync(gjones, dgj.p, sizeof(cplx<double>) * nj, hipMemcpyDeviceToHost, sg.s));
-    int hbad[2];
-    collect_rows(sg.s, rs, nrows, chi2_rows, hbad);
-    throw_if_bad_residual_input(hbad);
+    launch_weight_rows<T>(sg.s, nparts, dparts, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<T>(sg.s, dw, weights, n), nrows,
+                          row_len, rs, dc.cal);
+    if (nparts)  // G replaces P_0, or V for the direction of the gains or matrices alone
+        FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    else
+        FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
+    finish_rows_host(sg.s, dc, c.grad, nx, rs, nrows, q_rows);
 }
 
 template <typename T>
@@ -614,101 +634,6 @@ static void jones_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, i
 }
 
 template <typename T>
-static void weight_rows_host(int device, int64_t nrows, int64_t row_len, int nparts, const void *const *parts, const void *weights,
-                             double *q_rows) {
-    FV_HIP(hipSetDevice(device));
-    if (nrows == 0) return;
-    if (row_len == 0) {
-        for (int64_t i = 0; i < nrows; ++i) q_rows[i] = 0.0;
-        return;
-    }
-    StreamGuard sg;
-    const size_t n = (size_t)nrows * (size_t)row_len;
-    DevBuf dp[4], dw, ds;
-    cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < nparts; ++j) dparts[j] = to_device<cplx<T>>(sg.s, dp[j], parts[j], n);
-    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
-    launch_weight_rows<T>(sg.s, nparts, dparts, to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs);
-    FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    int hbad[2];
-    collect_rows(sg.s, rs, nrows, q_rows, hbad);
-    throw_if_bad_residual_input(hbad);
-}
-
-template <typename T>
-static void gain_weight_rows_host(int device, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1, const int *ant2,
-                                  const void *gains, const void *d_gains, int nparts, const void *const *parts, void *vis,
-                                  const void *weights, double *q_rows, void *hgains) {
-    const int nfeed = tpol == 4 ? 2 : 1;
-    const size_t ng = (size_t)nrows * nfeed * (size_t)nant;
-    if (nrows == 0) return;
-    if (nbls == 0) {
-        for (int64_t i = 0; i < nrows; ++i) q_rows[i] = 0.0;
-        if (hgains) std::memset(hgains, 0, sizeof(cplx<double>) * ng);
-        return;
-    }
-    FV_HIP(hipSetDevice(device));
-    StreamGuard sg;
-    const int64_t row_len = (int64_t)tpol * nbls;
-    const size_t n = (size_t)nrows * (size_t)row_len;
-    GainPairs gp;
-    gp.set(sg.s, nant, nbls, ant1, ant2);
-    DevBuf dp[4], dv, dw, ds, dgn, ddg, dhg;
-    cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < nparts; ++j) dparts[j] = to_device<cplx<T>>(sg.s, dp[j], parts[j], n);
-    if (hgains) dhg.reserve(sizeof(cplx<double>) * ng);
-    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
-    launch_weight_rows<T>(sg.s, nparts, dparts, to_device<T>(sg.s, dw, weights, n), nrows, row_len, rs,
-                          {&gp, to_device<cplx<T>>(sg.s, dgn, gains, ng), to_device<cplx<T>>(sg.s, ddg, d_gains, ng),
-                           dhg.as<cplx<double>>()},
-                          to_device<cplx<T>>(sg.s, dv, vis, n));
-    if (nparts)  // G replaces P_0, or V for the gains-only direction
-        FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    else
-        FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    if (hgains) FV_HIP(hipMemcpyAsync(hgains, dhg.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
-    int hbad[2];
-    collect_rows(sg.s, rs, nrows, q_rows, hbad);
-    throw_if_bad_residual_input(hbad);
-}
-
-template <typename T>
-static void jones_weight_rows_host(int device, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
-                                   const void *jones, const void *d_jones, int nparts, const void *const *parts, void *vis,
-                                   const void *weights, double *q_rows, void *hjones) {
-    const size_t nj = (size_t)nrows * 4 * (size_t)nant;
-    if (nrows == 0) return;
-    if (nbls == 0) {
-        for (int64_t i = 0; i < nrows; ++i) q_rows[i] = 0.0;
-        if (hjones) std::memset(hjones, 0, sizeof(cplx<double>) * nj);
-        return;
-    }
-    FV_HIP(hipSetDevice(device));
-    StreamGuard sg;
-    const int64_t row_len = 4 * nbls;
-    const size_t n = (size_t)nrows * (size_t)row_len;
-    GainPairs gp;
-    gp.set(sg.s, nant, nbls, ant1, ant2);
-    DevBuf dp[4], dv, dw, ds, djn, ddj, dhj, dt;
-    cplx<T> *dparts[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int j = 0; j < nparts; ++j) dparts[j] = to_device<cplx<T>>(sg.s, dp[j], parts[j], n);
-    if (hjones) dhj.reserve(sizeof(cplx<double>) * nj);
-    dt.reserve(sizeof(double) * n);
-    const RowScratch rs = row_scratch<T>(ds, nrows, row_len);
-    const cplx<T> *jn = to_device<cplx<T>>(sg.s, djn, jones, nj), *dj = to_device<cplx<T>>(sg.s, ddj, d_jones, nj);
-    launch_jones_weight_rows<T>(sg.s, nparts, dparts, to_device<cplx<T>>(sg.s, dv, vis, n), to_device<T>(sg.s, dw, weights, n),
-                                nrows, rs, {&gp, jn, dhj.as<cplx<double>>(), dt.as<double>(), dj});
-    if (nparts)  // G replaces P_0, or V for the matrices-only direction
-        FV_HIP(hipMemcpyAsync(const_cast<void *>(parts[0]), dp[0].p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    else
-        FV_HIP(hipMemcpyAsync(vis, dv.p, sizeof(cplx<T>) * n, hipMemcpyDeviceToHost, sg.s));
-    if (hjones) FV_HIP(hipMemcpyAsync(hjones, dhj.p, sizeof(cplx<double>) * nj, hipMemcpyDeviceToHost, sg.s));
-    int hbad[2];
-    collect_rows(sg.s, rs, nrows, q_rows, hbad);
-    throw_if_bad_residual_input(hbad);
-}
-
-template <typename T>
 static void inplace_rot_host(int device, const double *rot, void *b, int64_t n) {
     FV_REQUIRE(rot && n >= 0 && (b || n == 0), "bad inplace_rot arrays");
     FV_HIP(hipSetDevice(device));
@@ -803,123 +728,87 @@ const char *fv_last_error(void) { return g_last_error.c_str(); }
 int fv_nufft3(int device, int precision, int dim, int64_t M, const void *x, const void *y,
               const void *z, const void *c, int ntrans, int64_t N, const void *s, const void *t,
               const void *u, double eps, double upsampfac, void *out) {
-    return guarded([&] {
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {
         const void *xs[3] = {x, y, z}, *ss[3] = {s, t, u};
-        if (precision == 2)
-            nufft3_host<double>(device, dim, M, xs, c, ntrans, N, ss, eps, upsampfac, out, false);
-        else
-            nufft3_host<float>(device, dim, M, xs, c, ntrans, N, ss, eps, upsampfac, out, false);
+        nufft3_host<decltype(real)>(device, dim, M, xs, c, ntrans, N, ss, eps, upsampfac, out, false);
     });
 }
 
 int fv_nudft3_direct(int device, int precision, int dim, int64_t M, const void *x, const void *y,
                      const void *z, const void *c, int ntrans, int64_t N, const void *s,
                      const void *t, const void *u, void *out) {
-    return guarded([&] {
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {
         const void *xs[3] = {x, y, z}, *ss[3] = {s, t, u};
-        if (precision == 2)
-            nufft3_host<double>(device, dim, M, xs, c, ntrans, N, ss, 0, 2.0, out, true);
-        else
-            nufft3_host<float>(device, dim, M, xs, c, ntrans, N, ss, 0, 2.0, out, true);
+        nufft3_host<decltype(real)>(device, dim, M, xs, c, ntrans, N, ss, 0, 2.0, out, true);
     });
 }
 
 int fv_beam_eval(int device, int precision, int polarized, int kind, double diameter,
                  int nfreq_tab, int nza, int naz, double za_max, const void *table, int order,
                  int freq_index, double freq, int64_t n, const void *az, const void *za, void *out) {
-    return guarded([&] {
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
-        if (precision == 2)
-            beam_eval_host<double>(device, polarized, kind, diameter, nfreq_tab, nza, naz, za_max,
-                                   table, order, freq_index, freq, n, az, za, out);
-        else
-            beam_eval_host<float>(device, polarized, kind, diameter, nfreq_tab, nza, naz, za_max,
-                                  table, order, freq_index, freq, n, az, za, out);
+    return guarded(precision, [&](auto real) {
+        beam_eval_host<decltype(real)>(device, polarized, kind, diameter, nfreq_tab, nza, naz, za_max, table, order, freq_index,
+                                       freq, n, az, za, out);
     });
 }
 
 int fv_apparent_coherency(int device, int precision, int variant, int64_t n, const void *beam_i,
                           const void *beam_j, const void *flux, void *out) {
-    return guarded([&] {
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
-        if (precision == 2)
-            coherency_host<double>(device, variant, n, beam_i, beam_j, flux, out);
-        else
-            coherency_host<float>(device, variant, n, beam_i, beam_j, flux, out);
-    });
+    return guarded(precision, [&](auto real) { coherency_host<decltype(real)>(device, variant, n, beam_i, beam_j, flux, out); });
 }
 
 int fv_residual_chi2(int device, int precision, int64_t nrows, int64_t row_len, void *vis, const void *data,
                      const void *weights, double *chi2_rows) {
-    return guarded([&] {
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
-        if (precision == 2)
-            residual_chi2_host<double>(device, nrows, row_len, vis, data, weights, chi2_rows);
-        else
-            residual_chi2_host<float>(device, nrows, row_len, vis, data, weights, chi2_rows);
+    return guarded(precision, [&](auto real) {
+        FV_REQUIRE(nrows >= 0 && row_len >= 0, "fv_residual_chi2: negative shape");
+        FV_REQUIRE((nrows == 0 || row_len == 0 || (vis && data)) && (nrows == 0 || chi2_rows), "fv_residual_chi2: null vis, data or chi2_rows");
+        FV_HIP(hipSetDevice(device));  // (asked of an empty call too)
+        residual_rows_host<decltype(real)>(device, nrows, row_len, vis, data, weights, chi2_rows);
     });
 }
 
 int fv_gain_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
                           const int *ant2, const void *gains, void *vis, const void *data, const void *weights,
                           double *chi2_rows, void *ggains) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(tpol == 1 || tpol == 4, "fv_gain_residual_chi2: tpol must be 1 or 4");
         FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_gain_residual_chi2: negative shape");
         FV_REQUIRE(nant >= 1, "fv_gain_residual_chi2: nant must be positive");
         FV_REQUIRE(gains || nrows == 0, "fv_gain_residual_chi2: null gains");
         FV_REQUIRE((nrows == 0 || nbls == 0 || (vis && data && ant1 && ant2)) && (nrows == 0 || chi2_rows),
                    "fv_gain_residual_chi2: null pairs, vis, data or chi2_rows");
-        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
-            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
-                       "fv_gain_residual_chi2: antenna index outside [0, nant)");
-        if (precision == 2)
-            gain_residual_chi2_host<double>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, chi2_rows, ggains);
-        else
-            gain_residual_chi2_host<float>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, chi2_rows, ggains);
+        if (nrows > 0) require_pairs("fv_gain_residual_chi2", nbls, nant, ant1, ant2);
+        residual_rows_host<decltype(real)>(device, nrows, tpol * nbls, vis, data, weights, chi2_rows,
+                                           {Cal::Gains, tpol, nant, nbls, ant1, ant2, gains, nullptr, ggains});
     });
 }
 
 int fv_jones_residual_chi2(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
                            const void *jones, void *vis, const void *data, const void *weights, double *chi2_rows,
                            void *gjones) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_jones_residual_chi2: negative shape");
         FV_REQUIRE(nant >= 1, "fv_jones_residual_chi2: nant must be positive");
         FV_REQUIRE(jones || nrows == 0, "fv_jones_residual_chi2: null jones");
         FV_REQUIRE((nrows == 0 || nbls == 0 || (vis && data && ant1 && ant2)) && (nrows == 0 || chi2_rows),
                    "fv_jones_residual_chi2: null pairs, vis, data or chi2_rows");
-        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
-            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
-                       "fv_jones_residual_chi2: antenna index outside [0, nant)");
-        if (precision == 2)
-            jones_residual_chi2_host<double>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, chi2_rows, gjones);
-        else
-            jones_residual_chi2_host<float>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, chi2_rows, gjones);
+        if (nrows > 0) require_pairs("fv_jones_residual_chi2", nbls, nant, ant1, ant2);
+        residual_rows_host<decltype(real)>(device, nrows, 4 * nbls, vis, data, weights, chi2_rows,
+                                           {Cal::Jones, 4, nant, nbls, ant1, ant2, jones, nullptr, gjones});
     });
 }
 
 int fv_gain_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
                         const int *ant2, const void *gains, const void *vis, const void *data, const void *weights, void *num,
                         double *den) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(tpol == 1 || tpol == 4, "fv_gain_normal_rows: tpol must be 1 or 4");
         FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_gain_normal_rows: negative shape");
         FV_REQUIRE(nant >= 1, "fv_gain_normal_rows: nant must be positive");
         FV_REQUIRE(nrows == 0 || (gains && num && den), "fv_gain_normal_rows: null gains, num or den");
         FV_REQUIRE(nrows == 0 || nbls == 0 || (vis && data && ant1 && ant2), "fv_gain_normal_rows: null pairs, vis or data");
-        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
-            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
-                       "fv_gain_normal_rows: antenna index outside [0, nant)");
-        if (precision == 2)
-            gain_normal_rows_host<double>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, num, den);
-        else
-            gain_normal_rows_host<float>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, num, den);
+        if (nrows > 0) require_pairs("fv_gain_normal_rows", nbls, nant, ant1, ant2);
+        gain_normal_rows_host<decltype(real)>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, vis, data, weights, num, den);
     });
 }
 
@@ -927,8 +816,7 @@ int fv_gain_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbl
                   const int *ant2, int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
                   const void *weights, int weights_on_device, void *gains, int max_iter, double tol, int *niter_out,
                   double *change_out, double *chi2_ft_out, int *solved_out) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(tpol == 1 || tpol == 4, "fv_gain_solve: tpol must be 1 or 4");
         FV_REQUIRE(nfreqs >= 0 && ntimes >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_gain_solve: negative shape");
         FV_REQUIRE(nant >= 1, "fv_gain_solve: nant must be positive");
@@ -941,35 +829,22 @@ int fv_gain_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbl
         FV_REQUIRE(empty || (gains && change_out && chi2_ft_out && solved_out),
                    "fv_gain_solve: null gains, change_out, chi2_ft_out or solved_out");
         FV_REQUIRE(empty || nbls == 0 || (vis && data && ant1 && ant2), "fv_gain_solve: null pairs, vis or data");
-        for (int64_t k = 0; k < nbls && !empty; ++k)
-            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
-                       "fv_gain_solve: antenna index outside [0, nant)");
-        if (precision == 2)
-            gain_solve_host<double>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, per_time, vis, vis_on_device, data,
-                                    data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out, change_out,
-                                    chi2_ft_out, solved_out);
-        else
-            gain_solve_host<float>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, per_time, vis, vis_on_device, data,
-                                   data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out, change_out,
-                                   chi2_ft_out, solved_out);
+        if (!empty) require_pairs("fv_gain_solve", nbls, nant, ant1, ant2);
+        gain_solve_host<decltype(real)>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, per_time, vis, vis_on_device, data,
+                                        data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out, change_out,
+                                        chi2_ft_out, solved_out);
     });
 }
 
 int fv_jones_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
                          const void *jones, const void *vis, const void *data, const void *weights, double *A_out, void *b_out) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_jones_normal_rows: negative shape");
         FV_REQUIRE(nant >= 1, "fv_jones_normal_rows: nant must be positive");
         FV_REQUIRE(nrows == 0 || (jones && A_out && b_out), "fv_jones_normal_rows: null jones, A_out or b_out");
         FV_REQUIRE(nrows == 0 || nbls == 0 || (vis && data && ant1 && ant2), "fv_jones_normal_rows: null pairs, vis or data");
-        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
-            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
-                       "fv_jones_normal_rows: antenna index outside [0, nant)");
-        if (precision == 2)
-            jones_normal_rows_host<double>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, A_out, b_out);
-        else
-            jones_normal_rows_host<float>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, A_out, b_out);
+        if (nrows > 0) require_pairs("fv_jones_normal_rows", nbls, nant, ant1, ant2);
+        jones_normal_rows_host<decltype(real)>(device, nrows, nbls, nant, ant1, ant2, jones, vis, data, weights, A_out, b_out);
     });
 }
 
@@ -977,8 +852,7 @@ int fv_jones_solve(int device, int precision, int nfreqs, int ntimes, int64_t nb
                    int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device, const void *weights,
                    int weights_on_device, void *jones, int max_iter, double tol, int *niter_out, double *change_out,
                    double *chi2_ft_out, int *solved_out) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(nfreqs >= 0 && ntimes >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_jones_solve: negative shape");
         FV_REQUIRE(nant >= 1, "fv_jones_solve: nant must be positive");
         FV_REQUIRE(max_iter >= 1, "fv_jones_solve: max_iter must be positive");
@@ -990,40 +864,29 @@ int fv_jones_solve(int device, int precision, int nfreqs, int ntimes, int64_t nb
         FV_REQUIRE(empty || (jones && change_out && chi2_ft_out && solved_out),
                    "fv_jones_solve: null jones, change_out, chi2_ft_out or solved_out");
         FV_REQUIRE(empty || nbls == 0 || (vis && data && ant1 && ant2), "fv_jones_solve: null pairs, vis or data");
-        for (int64_t k = 0; k < nbls && !empty; ++k)
-            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
-                       "fv_jones_solve: antenna index outside [0, nant)");
-        if (precision == 2)
-            jones_solve_host<double>(device, nfreqs, ntimes, nbls, nant, ant1, ant2, per_time, vis, vis_on_device, data,
-                                     data_on_device, weights, weights_on_device, jones, max_iter, tol, niter_out, change_out,
-                                     chi2_ft_out, solved_out);
-        else
-            jones_solve_host<float>(device, nfreqs, ntimes, nbls, nant, ant1, ant2, per_time, vis, vis_on_device, data,
-                                    data_on_device, weights, weights_on_device, jones, max_iter, tol, niter_out, change_out,
-                                    chi2_ft_out, solved_out);
+        if (!empty) require_pairs("fv_jones_solve", nbls, nant, ant1, ant2);
+        jones_solve_host<decltype(real)>(device, nfreqs, ntimes, nbls, nant, ant1, ant2, per_time, vis, vis_on_device, data,
+                                         data_on_device, weights, weights_on_device, jones, max_iter, tol, niter_out, change_out,
+                                         chi2_ft_out, solved_out);
     });
 }
 
 int fv_weight_rows(int device, int precision, int64_t nrows, int64_t row_len, int nparts, const void *const *parts,
                    const void *weights, double *q_rows) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(nrows >= 0 && row_len >= 0, "fv_weight_rows: negative shape");
         FV_REQUIRE(nparts >= 1 && nparts <= 4 && parts, "fv_weight_rows: nparts must be 1 .. 4");
         for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts[j], "fv_weight_rows: null part");
         FV_REQUIRE(nrows == 0 || q_rows, "fv_weight_rows: null q_rows");
-        if (precision == 2)
-            weight_rows_host<double>(device, nrows, row_len, nparts, parts, weights, q_rows);
-        else
-            weight_rows_host<float>(device, nrows, row_len, nparts, parts, weights, q_rows);
+        FV_HIP(hipSetDevice(device));  // (asked of an empty call too)
+        weight_rows_host<decltype(real)>(device, nrows, row_len, nparts, parts, nullptr, weights, q_rows);
     });
 }
 
 int fv_gain_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
                         const int *ant2, const void *gains, const void *d_gains, int nparts, const void *const *parts, void *vis,
                         const void *weights, double *q_rows, void *hgains) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(tpol == 1 || tpol == 4, "fv_gain_weight_rows: tpol must be 1 or 4");
         FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_gain_weight_rows: negative shape");
         FV_REQUIRE(nant >= 1, "fv_gain_weight_rows: nant must be positive");
@@ -1033,23 +896,16 @@ int fv_gain_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, 
         for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts[j], "fv_gain_weight_rows: null part");
         FV_REQUIRE(vis || !(d_gains || hgains), "fv_gain_weight_rows: d_gains and hgains need vis");
         FV_REQUIRE((nrows == 0 || nbls == 0 || (ant1 && ant2)) && (nrows == 0 || q_rows), "fv_gain_weight_rows: null pairs or q_rows");
-        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
-            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
-                       "fv_gain_weight_rows: antenna index outside [0, nant)");
-        if (precision == 2)
-            gain_weight_rows_host<double>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, d_gains, nparts, parts, vis, weights,
-                                          q_rows, hgains);
-        else
-            gain_weight_rows_host<float>(device, nrows, nbls, tpol, nant, ant1, ant2, gains, d_gains, nparts, parts, vis, weights,
-                                         q_rows, hgains);
+        if (nrows > 0) require_pairs("fv_gain_weight_rows", nbls, nant, ant1, ant2);
+        weight_rows_host<decltype(real)>(device, nrows, tpol * nbls, nparts, parts, vis, weights, q_rows,
+                                         {Cal::Gains, tpol, nant, nbls, ant1, ant2, gains, d_gains, hgains});
     });
 }
 
 int fv_jones_weight_rows(int device, int precision, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
                          const void *jones, const void *d_jones, int nparts, const void *const *parts, void *vis,
                          const void *weights, double *q_rows, void *hjones) {
-    return guarded([&] {  // (everything is checked before anything runs)
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
         FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_jones_weight_rows: negative shape");
         FV_REQUIRE(nant >= 1, "fv_jones_weight_rows: nant must be positive");
         FV_REQUIRE(jones || nrows == 0, "fv_jones_weight_rows: null jones");
@@ -1058,36 +914,18 @@ int fv_jones_weight_rows(int device, int precision, int64_t nrows, int64_t nbls,
         for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts[j], "fv_jones_weight_rows: null part");
         FV_REQUIRE(vis || !(d_jones || hjones), "fv_jones_weight_rows: d_jones and hjones need vis");
         FV_REQUIRE((nrows == 0 || nbls == 0 || (ant1 && ant2)) && (nrows == 0 || q_rows), "fv_jones_weight_rows: null pairs or q_rows");
-        for (int64_t k = 0; k < nbls && nrows > 0; ++k)
-            FV_REQUIRE(ant1[k] >= 0 && ant1[k] < nant && ant2[k] >= 0 && ant2[k] < nant,
-                       "fv_jones_weight_rows: antenna index outside [0, nant)");
-        if (precision == 2)
-            jones_weight_rows_host<double>(device, nrows, nbls, nant, ant1, ant2, jones, d_jones, nparts, parts, vis, weights,
-                                           q_rows, hjones);
-        else
-            jones_weight_rows_host<float>(device, nrows, nbls, nant, ant1, ant2, jones, d_jones, nparts, parts, vis, weights,
-                                          q_rows, hjones);
+        if (nrows > 0) require_pairs("fv_jones_weight_rows", nbls, nant, ant1, ant2);
+        weight_rows_host<decltype(real)>(device, nrows, 4 * nbls, nparts, parts, vis, weights, q_rows,
+                                         {Cal::Jones, 4, nant, nbls, ant1, ant2, jones, d_jones, hjones});
     });
 }
 
 int fv_inplace_rot(int device, int precision, const double *rot, void *b, int64_t n) {
-    return guarded([&] {
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
-        if (precision == 2)
-            inplace_rot_host<double>(device, rot, b, n);
-        else
-            inplace_rot_host<float>(device, rot, b, n);
-    });
+    return guarded(precision, [&](auto real) { inplace_rot_host<decltype(real)>(device, rot, b, n); });
 }
 
 int fv_astrom_topo(int device, int precision, const double *astrom, int64_t n, const void *eq, void *topo) {
-    return guarded([&] {
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
-        if (precision == 2)
-            astrom_topo_host<double>(device, astrom, n, eq, topo);
-        else
-            astrom_topo_host<float>(device, astrom, n, eq, topo);
-    });
+    return guarded(precision, [&](auto real) { astrom_topo_host<decltype(real)>(device, astrom, n, eq, topo); });
 }
 
 int fv_sim_create(fv_sim **h, int device, int precision, double eps, double upsampfac,
@@ -1095,16 +933,14 @@ int fv_sim_create(fv_sim **h, int device, int precision, double eps, double upsa
     return guarded([&] {
         FV_REQUIRE(h, "null handle pointer");
         *h = nullptr;
-        FV_REQUIRE(precision == 1 || precision == 2, "precision must be 1 or 2");
-        FV_REQUIRE(upsampfac == 2.0 || upsampfac == 1.25 || upsampfac == 0.0, "upsample factor must be 2, 1.25 or 0 (auto)");
-        FV_REQUIRE(eps > 0 && eps < 1, "eps must be in (0, 1)");
-        std::unique_ptr<fv_sim> s(new fv_sim());
-        s->precision = precision;
-        if (precision == 2)
-            s->impl.reset(new Sim<double>(device, eps, upsampfac, polarized));
-        else
-            s->impl.reset(new Sim<float>(device, eps, upsampfac, polarized));
-        *h = s.release();
+        with_precision(precision, [&](auto real) {
+            FV_REQUIRE(upsampfac == 2.0 || upsampfac == 1.25 || upsampfac == 0.0, "upsample factor must be 2, 1.25 or 0 (auto)");
+            FV_REQUIRE(eps > 0 && eps < 1, "eps must be in (0, 1)");
+            std::unique_ptr<fv_sim> s(new fv_sim());
+            s->precision = precision;
+            s->impl.reset(new Sim<decltype(real)>(device, eps, upsampfac, polarized));
+            *h = s.release();
+        });
     });
 }
 
@@ -1191,11 +1027,11 @@ int fv_sim_run_residual(fv_sim *h, int t0, int t1, int f0, int f1, const void *d
                         int weights_on_device, void *gvis, int gvis_on_device, double *chi2_ft) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(data && gvis && chi2_ft, "null data, gvis or chi2_ft");
-        FV_REQUIRE((data_on_device == 0 || data_on_device == 1) && (weights_on_device == 0 || weights_on_device == 1) &&
-                       (gvis_on_device == 0 || gvis_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({data_on_device, weights_on_device, gvis_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->run_residual(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, gvis, gvis_on_device, chi2_ft);
+        SimBase::FitArrays a;
+        a.data = {data, data_on_device}, a.weights = {weights, weights_on_device}, a.gvis = {gvis, gvis_on_device};
+        h->impl->residual_pass(Cal::None, t0, t1, f0, f1, a, chi2_ft);
     });
 }
 int fv_sim_set_gain_pairs(fv_sim *h, int nant, const int *ant1, const int *ant2) {
@@ -1206,13 +1042,12 @@ int fv_sim_run_residual_gains(fv_sim *h, int t0, int t1, int f0, int f1, const v
                               double *chi2_ft, void *ggains, int ggains_on_device) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(data && gains && gvis && chi2_ft, "null data, gains, gvis or chi2_ft");
-        FV_REQUIRE((data_on_device == 0 || data_on_device == 1) && (weights_on_device == 0 || weights_on_device == 1) &&
-                       (gains_on_device == 0 || gains_on_device == 1) && (gvis_on_device == 0 || gvis_on_device == 1) &&
-                       (ggains_on_device == 0 || ggains_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({data_on_device, weights_on_device, gains_on_device, gvis_on_device, ggains_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->run_residual_gains(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, gains, gains_on_device, gvis,
-                                    gvis_on_device, chi2_ft, ggains, ggains_on_device);
+        SimBase::FitArrays a;
+        a.data = {data, data_on_device}, a.weights = {weights, weights_on_device}, a.x = {gains, gains_on_device};
+        a.gvis = {gvis, gvis_on_device}, a.grad = {ggains, ggains_on_device};
+        h->impl->residual_pass(Cal::Gains, t0, t1, f0, f1, a, chi2_ft);
     });
 }
 int fv_sim_run_residual_jones(fv_sim *h, int t0, int t1, int f0, int f1, const void *data, int data_on_device, const void *weights,
@@ -1220,13 +1055,12 @@ int fv_sim_run_residual_jones(fv_sim *h, int t0, int t1, int f0, int f1, const v
                               double *chi2_ft, void *gjones, int gjones_on_device) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(data && jones && gvis && chi2_ft, "null data, jones, gvis or chi2_ft");
-        FV_REQUIRE((data_on_device == 0 || data_on_device == 1) && (weights_on_device == 0 || weights_on_device == 1) &&
-                       (jones_on_device == 0 || jones_on_device == 1) && (gvis_on_device == 0 || gvis_on_device == 1) &&
-                       (gjones_on_device == 0 || gjones_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({data_on_device, weights_on_device, jones_on_device, gvis_on_device, gjones_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->run_residual_jones(t0, t1, f0, f1, data, data_on_device, weights, weights_on_device, jones, jones_on_device, gvis,
-                                    gvis_on_device, chi2_ft, gjones, gjones_on_device);
+        SimBase::FitArrays a;
+        a.data = {data, data_on_device}, a.weights = {weights, weights_on_device}, a.x = {jones, jones_on_device};
+        a.gvis = {gvis, gvis_on_device}, a.grad = {gjones, gjones_on_device};
+        h->impl->residual_pass(Cal::Jones, t0, t1, f0, f1, a, chi2_ft);
     });
 }
 int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, const void *weights,
@@ -1235,9 +1069,11 @@ int fv_sim_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, v
         FV_REQUIRE(nparts >= 1 && nparts <= 4 && parts_dev, "nparts must be 1 .. 4");
         for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts_dev[j], "null part");
         FV_REQUIRE(q_ft, "null q_ft");
-        FV_REQUIRE(weights_on_device == 0 || weights_on_device == 1, "on_device flags must be 0 or 1");
+        require_on_device_flags({weights_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->weight_block(t0, t1, f0, f1, nparts, parts_dev, weights, weights_on_device, q_ft);
+        SimBase::FitArrays a;
+        a.weights = {weights, weights_on_device};
+        h->impl->weight_pass(Cal::None, t0, t1, f0, f1, nparts, parts_dev, nullptr, a, q_ft);
     });
 }
 int fv_sim_gain_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
@@ -1249,12 +1085,12 @@ int fv_sim_gain_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int npar
         for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts_dev[j], "null part");
         FV_REQUIRE(gains && q_ft, "null gains or q_ft");
         FV_REQUIRE(vis_dev || !(d_gains || hgains), "d_gains and hgains need vis");
-        FV_REQUIRE((weights_on_device == 0 || weights_on_device == 1) && (gains_on_device == 0 || gains_on_device == 1) &&
-                       (d_gains_on_device == 0 || d_gains_on_device == 1) && (hgains_on_device == 0 || hgains_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({weights_on_device, gains_on_device, d_gains_on_device, hgains_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->gain_weight_block(t0, t1, f0, f1, nparts, parts_dev, vis_dev, weights, weights_on_device, gains, gains_on_device,
-                                   d_gains, d_gains_on_device, q_ft, hgains, hgains_on_device);
+        SimBase::FitArrays a;
+        a.weights = {weights, weights_on_device}, a.x = {gains, gains_on_device}, a.dx = {d_gains, d_gains_on_device};
+        a.grad = {hgains, hgains_on_device};
+        h->impl->weight_pass(Cal::Gains, t0, t1, f0, f1, nparts, parts_dev, vis_dev, a, q_ft);
     });
 }
 int fv_sim_jones_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int nparts, void *const *parts_dev, void *vis_dev,
@@ -1266,20 +1102,19 @@ int fv_sim_jones_weight_block(fv_sim *h, int t0, int t1, int f0, int f1, int npa
         for (int j = 0; j < nparts; ++j) FV_REQUIRE(parts_dev[j], "null part");
         FV_REQUIRE(jones && q_ft, "null jones or q_ft");
         FV_REQUIRE(vis_dev || !(d_jones || hjones), "d_jones and hjones need vis");
-        FV_REQUIRE((weights_on_device == 0 || weights_on_device == 1) && (jones_on_device == 0 || jones_on_device == 1) &&
-                       (d_jones_on_device == 0 || d_jones_on_device == 1) && (hjones_on_device == 0 || hjones_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({weights_on_device, jones_on_device, d_jones_on_device, hjones_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
-        h->impl->jones_weight_block(t0, t1, f0, f1, nparts, parts_dev, vis_dev, weights, weights_on_device, jones, jones_on_device,
-                                    d_jones, d_jones_on_device, q_ft, hjones, hjones_on_device);
+        SimBase::FitArrays a;
+        a.weights = {weights, weights_on_device}, a.x = {jones, jones_on_device}, a.dx = {d_jones, d_jones_on_device};
+        a.grad = {hjones, hjones_on_device};
+        h->impl->weight_pass(Cal::Jones, t0, t1, f0, f1, nparts, parts_dev, vis_dev, a, q_ft);
     });
 }
 int fv_sim_run_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void *gvis, int gvis_on_device, void *gflux,
                        int gflux_on_device, int accumulate) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(gvis && gflux, "null adjoint input or output");
-        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gflux_on_device == 0 || gflux_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({gvis_on_device, gflux_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, accumulate != 0);
     });
@@ -1300,9 +1135,7 @@ int fv_sim_run_basis_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const vo
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(gvis, "null adjoint input");
         FV_REQUIRE(gflux || gcoefs, "neither gradient is wanted (gflux and gcoefs are both null)");
-        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gflux_on_device == 0 || gflux_on_device == 1) &&
-                       (gcoefs_on_device == 0 || gcoefs_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({gvis_on_device, gflux_on_device, gcoefs_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_basis_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, gcoefs, gcoefs_on_device,
                                    accumulate != 0);
@@ -1312,8 +1145,7 @@ int fv_sim_run_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const
                                 int gbls_on_device, int accumulate) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(gvis && gbls, "null adjoint input or output");
-        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gbls_on_device == 0 || gbls_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({gvis_on_device, gbls_on_device});
         FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_position_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gbls, gbls_on_device, accumulate, false);
@@ -1323,8 +1155,7 @@ int fv_sim_run_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const v
                               int gtopo_on_device, int accumulate) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(gvis && gtopo, "null adjoint input or output");
-        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gtopo_on_device == 0 || gtopo_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({gvis_on_device, gtopo_on_device});
         FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gtopo, gtopo_on_device, accumulate, false);
@@ -1335,9 +1166,7 @@ int fv_sim_run_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const double *
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(out, "null output");
         FV_REQUIRE(dbls || dtopo, "neither tangent input is given (dbls and dtopo are both null)");
-        FV_REQUIRE((dbls_on_device == 0 || dbls_on_device == 1) && (dtopo_on_device == 0 || dtopo_on_device == 1) &&
-                       (out_on_device == 0 || out_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({dbls_on_device, dtopo_on_device, out_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_tangent(t0, t1, f0, f1, dbls, dbls_on_device, dtopo, dtopo_on_device, out, out_on_device, false);
     });
@@ -1348,8 +1177,7 @@ int fv_sim_run_basis_tangent(fv_sim *h, int t0, int t1, int f0, int f1, const vo
         FV_REQUIRE(out, "null output");
         FV_REQUIRE(dcoefs, "null coefficient directions (dcoefs)");
         FV_REQUIRE(ndir >= 1, "ndir must be at least 1");
-        FV_REQUIRE((dcoefs_on_device == 0 || dcoefs_on_device == 1) && (out_on_device == 0 || out_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({dcoefs_on_device, out_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_basis_tangent(t0, t1, f0, f1, dcoefs, dcoefs_on_device, ndir, out, out_on_device);
     });
@@ -1358,8 +1186,7 @@ int fv_sim_run_basis_position_adjoint(fv_sim *h, int t0, int t1, int f0, int f1,
                                       double *gbls, int gbls_on_device, int accumulate) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(gvis && gbls, "null adjoint input or output");
-        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gbls_on_device == 0 || gbls_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({gvis_on_device, gbls_on_device});
         FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_position_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gbls, gbls_on_device, accumulate, true);
@@ -1370,8 +1197,7 @@ int fv_sim_run_basis_position_tangent(fv_sim *h, int t0, int t1, int f0, int f1,
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(out, "null output");
         FV_REQUIRE(dbls, "null baseline directions (dbls)");
-        FV_REQUIRE((dbls_on_device == 0 || dbls_on_device == 1) && (out_on_device == 0 || out_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({dbls_on_device, out_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_tangent(t0, t1, f0, f1, dbls, dbls_on_device, nullptr, 0, out, out_on_device, true);
     });
@@ -1380,8 +1206,7 @@ int fv_sim_run_basis_source_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, c
                                     double *gtopo, int gtopo_on_device, int accumulate) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(gvis && gtopo, "null adjoint input or output");
-        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gtopo_on_device == 0 || gtopo_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({gvis_on_device, gtopo_on_device});
         FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_source_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gtopo, gtopo_on_device, accumulate, true);
@@ -1391,9 +1216,7 @@ int fv_sim_run_sky_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, const void
                            int gflux_on_device, double *gtopo, int gtopo_on_device, int accumulate) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(gvis && gflux && gtopo, "null adjoint input or output");
-        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gflux_on_device == 0 || gflux_on_device == 1) &&
-                       (gtopo_on_device == 0 || gtopo_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({gvis_on_device, gflux_on_device, gtopo_on_device});
         FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_sky_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, gtopo, gtopo_on_device, accumulate,
@@ -1404,9 +1227,7 @@ int fv_sim_run_basis_sky_adjoint(fv_sim *h, int t0, int t1, int f0, int f1, cons
                                  int gflux_on_device, double *gtopo, int gtopo_on_device, int accumulate) {
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(gvis && gflux && gtopo, "null adjoint input or output");
-        FV_REQUIRE((gvis_on_device == 0 || gvis_on_device == 1) && (gflux_on_device == 0 || gflux_on_device == 1) &&
-                       (gtopo_on_device == 0 || gtopo_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({gvis_on_device, gflux_on_device, gtopo_on_device});
         FV_REQUIRE(accumulate == 0 || accumulate == 1, "accumulate must be 0 or 1");
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_sky_adjoint(t0, t1, f0, f1, gvis, gvis_on_device, gflux, gflux_on_device, gtopo, gtopo_on_device, accumulate,
@@ -1418,8 +1239,7 @@ int fv_sim_run_basis_source_tangent(fv_sim *h, int t0, int t1, int f0, int f1, c
     return guarded([&] {  // (the buffers are checked before the handle is looked at)
         FV_REQUIRE(out, "null output");
         FV_REQUIRE(dtopo, "null source directions (dtopo)");
-        FV_REQUIRE((dtopo_on_device == 0 || dtopo_on_device == 1) && (out_on_device == 0 || out_on_device == 1),
-                   "on_device flags must be 0 or 1");
+        require_on_device_flags({dtopo_on_device, out_on_device});
         FV_REQUIRE(h && h->impl, "null handle");
         h->impl->run_tangent(t0, t1, f0, f1, nullptr, 0, dtopo, dtopo_on_device, out, out_on_device, true);
     });

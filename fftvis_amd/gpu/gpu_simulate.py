@@ -244,6 +244,24 @@ class SimHandle:
                                                out.strides[0] // out.itemsize, int(bool(shared))))
         return out
 
+    def _residual_pass(self, fn, t0, t1, f0, f1, data, weights, gvis, cal=()):
+        """The body of the three objective calls, ``fn`` their entry point: ``cal`` is empty or (the gains or matrices, the
+        array of their gradient or None).  Returns the (f1 - f0, t1 - t0) float64 rows."""
+        x, grad = (_buffer_addr(c) for c in cal) if cal else ((), ())
+        chi2 = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
+        _lib.check(fn(self._h, t0, t1, f0, f1, *_buffer_addr(data), *_buffer_addr(weights), *x, *_buffer_addr(gvis),
+                      _lib.ptr(chi2), *grad))
+        return chi2
+
+    def _weight_pass(self, fn, t0, t1, f0, f1, parts, weights, cal=()):
+        """The body of the three weighting calls, ``fn`` their entry point: ``cal`` is empty or (vis, the gains or matrices,
+        their direction or None, the array of the H block or None).  Returns the (f1 - f0, t1 - t0) float64 rows."""
+        ptrs = (ctypes.c_void_p * max(len(parts), 1))(*[p.data_ptr() for p in parts])
+        vis, x, dx, grad = (_buffer_addr(c) for c in cal) if cal else ((), (), (), ())
+        q = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
+        _lib.check(fn(self._h, t0, t1, f0, f1, len(parts), ptrs, *vis[:1], *_buffer_addr(weights), *x, *dx, _lib.ptr(q), *grad))
+        return q
+
     def run_residual(self, t0, t1, f0, f1, data, weights, gvis):
         """The fit objective of times [t0,t1) x freqs [f0,f1) (``fv_sim_run_residual``): the forward run of the block goes
         into ``gvis`` and stays on the device, where ``gvis = 2 w (V - data)`` replaces it; returns the (f1 - f0, t1 - t0)
@@ -251,12 +269,7 @@ class SimHandle:
         ``out_shape(t1 - t0, f1 - f0)``, this engine's complex dtype; ``weights``: the same shape, this engine's real
         dtype, or None (every weight 1; 0 flags a sample).  numpy arrays are host buffers, torch tensors device buffers.
         ``gvis`` is what every ``run_*_adjoint`` takes as ``g``.  The call synchronises."""
-        dp, d_dev = _buffer_addr(data)
-        wp, w_dev = _buffer_addr(weights)
-        gp, g_dev = _buffer_addr(gvis)
-        chi2 = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
-        _lib.check(self._L.fv_sim_run_residual(self._h, t0, t1, f0, f1, dp, d_dev, wp, w_dev, gp, g_dev, _lib.ptr(chi2)))
-        return chi2
+        return self._residual_pass(self._L.fv_sim_run_residual, t0, t1, f0, f1, data, weights, gvis)
 
     def set_gain_pairs(self, nant, ant1_idxs, ant2_idxs):
         """The antenna pair of every baseline, as rows of the gains ``run_gain_residual`` takes (``fv_sim_set_gain_pairs``):
@@ -271,15 +284,7 @@ class SimHandle:
         ``sum w |V' - data|^2``.  ``gains``: C-contiguous (f1 - f0, t1 - t0, nfeed, nant), this engine's complex dtype;
         ``ggains``: the same shape, complex128, filled with the gradient with respect to the gains, or None (its kernel
         does not run).  numpy arrays are host buffers, torch tensors device buffers.  The call synchronises."""
-        dp, d_dev = _buffer_addr(data)
-        wp, w_dev = _buffer_addr(weights)
-        np_, n_dev = _buffer_addr(gains)
-        gp, g_dev = _buffer_addr(gvis)
-        ggp, gg_dev = _buffer_addr(ggains)
-        chi2 = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
-        _lib.check(self._L.fv_sim_run_residual_gains(self._h, t0, t1, f0, f1, dp, d_dev, wp, w_dev, np_, n_dev, gp, g_dev,
-                                                     _lib.ptr(chi2), ggp, gg_dev))
-        return chi2
+        return self._residual_pass(self._L.fv_sim_run_residual_gains, t0, t1, f0, f1, data, weights, gvis, (gains, ggains))
 
     def run_jones_residual(self, t0, t1, f0, f1, data, weights, jones, gvis, gjones=None):
         """``run_gain_residual`` with one 2 x 2 complex matrix per antenna (``fv_sim_run_residual_jones``; ``set_gain_pairs``
@@ -289,15 +294,7 @@ class SimHandle:
         ``jones[f, t, i, j, a]`` with i the feed of the ideal antenna and j the measured one; ``gjones``: the same shape,
         complex128, filled with the gradient with respect to the matrices, or None (its kernel does not run).  numpy arrays
         are host buffers, torch tensors device buffers.  The call synchronises."""
-        dp, d_dev = _buffer_addr(data)
-        wp, w_dev = _buffer_addr(weights)
-        jp, j_dev = _buffer_addr(jones)
-        gp, g_dev = _buffer_addr(gvis)
-        gjp, gj_dev = _buffer_addr(gjones)
-        chi2 = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
-        _lib.check(self._L.fv_sim_run_residual_jones(self._h, t0, t1, f0, f1, dp, d_dev, wp, w_dev, jp, j_dev, gp, g_dev,
-                                                     _lib.ptr(chi2), gjp, gj_dev))
-        return chi2
+        return self._residual_pass(self._L.fv_sim_run_residual_jones, t0, t1, f0, f1, data, weights, gvis, (jones, gjones))
 
     def weight_block(self, t0, t1, f0, f1, parts, weights):
         """The weighting step of a Gauss-Newton product for times [t0,t1) x freqs [f0,f1) (``fv_sim_weight_block``):
@@ -306,11 +303,7 @@ class SimHandle:
         ``parts[0] = 2 w (sum)`` replaces the first; returns the (f1 - f0, t1 - t0) float64 host array of ``sum w |sum|^2``
         per (frequency, time).  ``weights`` as for ``run_residual``.  ``parts[0]`` is then what every ``run_*_adjoint``
         takes as ``g``.  The call synchronises."""
-        ptrs = (ctypes.c_void_p * len(parts))(*[p.data_ptr() for p in parts])
-        wp, w_dev = _buffer_addr(weights)
-        q = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
-        _lib.check(self._L.fv_sim_weight_block(self._h, t0, t1, f0, f1, len(parts), ptrs, wp, w_dev, _lib.ptr(q)))
-        return q
+        return self._weight_pass(self._L.fv_sim_weight_block, t0, t1, f0, f1, parts, weights)
 
     def gain_weight_block(self, t0, t1, f0, f1, parts, vis, weights, gains, d_gains=None, hgains=None):
         """``weight_block`` with per-antenna gains and a gain direction (``fv_sim_gain_weight_block``; ``set_gain_pairs``
@@ -322,16 +315,7 @@ class SimHandle:
         nfeed, nant), this engine's complex dtype; ``hgains``: the same shape, complex128, filled with the gain block of
         H p, or None (its kernel does not run).  numpy arrays are host buffers, torch tensors device buffers.  The
         stored G is what every ``run_*_adjoint`` takes as ``g``.  The call synchronises."""
-        ptrs = (ctypes.c_void_p * max(len(parts), 1))(*[p.data_ptr() for p in parts])
-        vp, _ = _buffer_addr(vis)
-        wp, w_dev = _buffer_addr(weights)
-        np_, n_dev = _buffer_addr(gains)
-        dp, d_dev = _buffer_addr(d_gains)
-        hp, h_dev = _buffer_addr(hgains)
-        q = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
-        _lib.check(self._L.fv_sim_gain_weight_block(self._h, t0, t1, f0, f1, len(parts), ptrs, vp, wp, w_dev, np_, n_dev, dp,
-                                                    d_dev, _lib.ptr(q), hp, h_dev))
-        return q
+        return self._weight_pass(self._L.fv_sim_gain_weight_block, t0, t1, f0, f1, parts, weights, (vis, gains, d_gains, hgains))
 
     def jones_weight_block(self, t0, t1, f0, f1, parts, vis, weights, jones, d_jones=None, hjones=None):
         """``gain_weight_block`` with one 2 x 2 complex matrix per antenna and a direction of such matrices
@@ -345,16 +329,7 @@ class SimHandle:
         shape, complex128, filled with the matrices' block of H p, or None (its kernel does not run).  numpy arrays are host
         buffers, torch tensors device buffers.  The stored G is what every ``run_*_adjoint`` takes as ``g``.  The call
         synchronises."""
-        ptrs = (ctypes.c_void_p * max(len(parts), 1))(*[p.data_ptr() for p in parts])
-        vp, _ = _buffer_addr(vis)
-        wp, w_dev = _buffer_addr(weights)
-        jp, j_dev = _buffer_addr(jones)
-        dp, d_dev = _buffer_addr(d_jones)
-        hp, h_dev = _buffer_addr(hjones)
-        q = np.empty((f1 - f0, t1 - t0), dtype=np.float64)
-        _lib.check(self._L.fv_sim_jones_weight_block(self._h, t0, t1, f0, f1, len(parts), ptrs, vp, wp, w_dev, jp, j_dev, dp,
-                                                     d_dev, _lib.ptr(q), hp, h_dev))
-        return q
+        return self._weight_pass(self._L.fv_sim_jones_weight_block, t0, t1, f0, f1, parts, weights, (vis, jones, d_jones, hjones))
 
     def run_adjoint(self, t0, t1, f0, f1, g, gflux, accumulate: bool):
         """``gflux += A^T g`` for times [t0,t1) x freqs [f0,f1) (``fv_sim_run_adjoint``).  ``g``: C-contiguous block of
