@@ -18,7 +18,9 @@ Gauss-Newton product 2 J^T W J p of that objective from one call that keeps the 
 on the device (``simulate_vis_gauss_newton``; ``simulate_vis_gain_gauss_newton`` with the gains in the data model, a gain
 direction and the gain block of the product; ``simulate_vis_jones_gauss_newton`` the same with 2 x 2 Jones matrices and a
 direction of such matrices), and the gains themselves for a fixed model, solved on the device against
-a resident model (``simulate_vis_gain_solve``; ``simulate_vis_jones_solve`` for the full 2 x 2 matrices).
+a resident model (``simulate_vis_gain_solve``; ``simulate_vis_jones_solve`` for the full 2 x 2 matrices), and redundant
+calibration, which needs no sky: the gains together with one visibility per redundant group (``redundant_groups``,
+``redundant_gain_solve``, ``redundant_average``, ``fix_redundant_degeneracies``).
 """
 
 __version__ = "0.1.0"
@@ -57,4 +59,10 @@ from .adjoint import (  # noqa: F401
     torch_simulate_vis_chi2,
     torch_simulate_vis_sky,
     topo_to_radec_gradient,
+)
+from .redundant import (  # noqa: F401
+    fix_redundant_degeneracies,
+    redundant_average,
+    redundant_gain_solve,
+    redundant_groups,
 )

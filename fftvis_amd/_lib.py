@@ -51,6 +51,13 @@ SYMBOLS = {
     "fv_gain_solve": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                               c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
+    "fv_redundant_vis_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_redundant_normal_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_redundant_solve": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "fv_jones_normal_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
     "fv_jones_solve": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,

@@ -583,6 +583,100 @@ static void gain_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, in
         [=](const SolveBlocks &b, const cplx<double> *g) { gather(b, g, true); });
 }
 
+// The redundant solve's two halves on host arrays (fv_redundant_vis_rows, fv_redundant_normal_rows): one row per unit.
+// uvis_in: the groups' visibilities as given; the U-step copies them back with den, the gather writes num and den.
+template <typename T>
+static void redundant_rows_host(int device, bool vis_step, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                                const int *ant2, int ngroups, const int *group, const void *gains, void *uvis, const void *data,
+                                const void *weights, void *num, double *den) {
+    const int nfeed = tpol == 4 ? 2 : 1;
+    const size_t ng = (size_t)nrows * nfeed * (size_t)nant, nu = (size_t)nrows * tpol * (size_t)ngroups;
+    if (nrows == 0) return;
+    if (nbls == 0) {  // (no sample: U keeps its values)
+        if (!vis_step) std::memset(num, 0, sizeof(cplx<double>) * ng);
+        std::memset(den, 0, sizeof(double) * (vis_step ? nu : ng));
+        return;
+    }
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const size_t n = (size_t)nrows * (size_t)tpol * (size_t)nbls;
+    GainPairs gp;
+    gp.set(sg.s, nant, nbls, ant1, ant2);
+    RedGroups rg;
+    rg.set(sg.s, ngroups, nbls, group);
+    DevBuf dd, dw, dgn, du, dnum, dden;
+    const cplx<T> *d = to_device<cplx<T>>(sg.s, dd, data, n);
+    const T *w = to_device<T>(sg.s, dw, weights, n);
+    const cplx<double> *g = to_device<cplx<double>>(sg.s, dgn, gains, ng);
+    cplx<double> *u = to_device<cplx<double>>(sg.s, du, uvis, nu);
+    dden.reserve(sizeof(double) * (vis_step ? nu : ng));
+    if (vis_step) {
+        launch_red_vis<T>(sg.s, d, w, g, gp, rg, nrows, 1, tpol, u, dden.as<double>());
+        FV_HIP(hipMemcpyAsync(uvis, du.p, sizeof(cplx<double>) * nu, hipMemcpyDeviceToHost, sg.s));
+        FV_HIP(hipMemcpyAsync(den, dden.p, sizeof(double) * nu, hipMemcpyDeviceToHost, sg.s));
+    } else {
+        dnum.reserve(sizeof(cplx<double>) * ng);
+        launch_red_normal<T>(sg.s, u, d, w, g, gp, rg, nrows, 1, tpol, dnum.as<cplx<double>>(), dden.as<double>(), nullptr);
+        FV_HIP(hipMemcpyAsync(num, dnum.p, sizeof(cplx<double>) * ng, hipMemcpyDeviceToHost, sg.s));
+        FV_HIP(hipMemcpyAsync(den, dden.p, sizeof(double) * ng, hipMemcpyDeviceToHost, sg.s));
+    }
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+}
+
+// Gains and one visibility per (row, pol, group): the U-step (k_red_vis) in front of the gain solve's gather with the
+// groups' visibilities as its model, k_gain_update as it stands, and one more U-step at the returned gains before chi2.
+// U and its den live in buffers of this call; they come to the host once, at the end.
+template <typename T>
+static void redundant_solve_host(int device, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1,
+                                 const int *ant2, int ngroups, const int *group, int per_time, const void *data, int data_on_device,
+                                 const void *weights, int weights_on_device, void *gains, void *uvis_out, int max_iter, double tol,
+                                 int *niter_out, double *change_out, double *chi2_ft_out, int *solved_out, int *vis_solved_out) {
+    const int ng = (tpol == 4 ? 2 : 1) * nant;
+    const int64_t nrows = (int64_t)nfreqs * ntimes;
+    const size_t nu = (size_t)nrows * tpol * (size_t)ngroups;
+    RedGroups rg;
+    DevBuf du, dden;
+    if (nrows > 0 && nbls > 0) {
+        FV_HIP(hipSetDevice(device));
+        StreamGuard sg;
+        rg.set(sg.s, ngroups, nbls, group);
+        du.reserve(sizeof(cplx<double>) * nu);
+        dden.reserve(sizeof(double) * nu);
+        FV_HIP(hipMemsetAsync(du.p, 0, sizeof(cplx<double>) * nu, sg.s));  // the start: U = 0
+        FV_HIP(hipStreamSynchronize(sg.s));
+    }
+    cplx<double> *u = du.as<cplx<double>>();
+    double *uden = dden.as<double>();
+    const RedGroups &groups = rg;
+    const auto step = [=, &groups](const SolveBlocks &b, const cplx<double> *g, bool chi2) {
+        launch_red_vis<T>(b.on, (const cplx<T> *)b.data, (const T *)b.weights, g, b.gp, groups, b.nrows, b.rows_per_unit, tpol, u, uden);
+        launch_red_normal<T>(b.on, u, (const cplx<T> *)b.data, (const T *)b.weights, g, b.gp, groups, b.nrows, b.rows_per_unit, tpol,
+                             chi2 ? nullptr : (cplx<double> *)b.sums0, chi2 ? nullptr : (double *)b.sums1,
+                             chi2 ? (double *)b.sums0 : nullptr);
+    };
+    alternating_solve<T>(
+        device, nfreqs, ntimes, nbls, nant, ant1, ant2, per_time, (int64_t)tpol * nbls, ng, ng, sizeof(cplx<double>) * ng,
+        sizeof(double) * ng, ng, nullptr, 0, data, data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out,
+        change_out, chi2_ft_out, solved_out, [=](const SolveBlocks &b, const cplx<double> *g) { step(b, g, false); },
+        [=](const SolveBlocks &b, const cplx<double> *g_old, cplx<double> *g_new, int odd, double *change, int *solved) {
+            hipLaunchKernelGGL(k_gain_update, dim3((unsigned)(b.nrows / b.rows_per_unit)), dim3(256), 0, b.on,
+                               (const cplx<double> *)b.sums0, (const double *)b.sums1, g_old, g_new, b.rows_per_unit, ng, odd, change,
+                               solved);
+        },
+        [=](const SolveBlocks &b, const cplx<double> *g) { step(b, g, true); });
+    if (nrows == 0) return;
+    if (nbls == 0) {  // (the start: U = 0, nothing solved)
+        std::memset(uvis_out, 0, sizeof(cplx<double>) * nu);
+        std::fill(vis_solved_out, vis_solved_out + nu, 0);
+        return;
+    }
+    std::vector<double> hden(nu);  // (the solve has ended and synchronised its stream: U and den are complete)
+    FV_HIP(hipMemcpy(uvis_out, du.p, sizeof(cplx<double>) * nu, hipMemcpyDeviceToHost));
+    FV_HIP(hipMemcpy(hden.data(), dden.p, sizeof(double) * nu, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nu; ++i) vis_solved_out[i] = hden[i] > 0.0 ? 1 : 0;
+}
+
 template <typename T>
 static void jones_normal_rows_host(int device, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
                                    const void *jones, const void *vis, const void *data, const void *weights, double *A_out,
@@ -833,6 +927,72 @@ int fv_gain_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbl
         gain_solve_host<decltype(real)>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, per_time, vis, vis_on_device, data,
                                         data_on_device, weights, weights_on_device, gains, max_iter, tol, niter_out, change_out,
                                         chi2_ft_out, solved_out);
+    });
+}
+
+static void require_groups(const char *entry, int64_t nbls, int ngroups, const int *group) {
+    for (int64_t k = 0; k < nbls; ++k)
+        FV_REQUIRE(group[k] >= 0 && group[k] < ngroups, std::string(entry) + ": group index outside [0, ngroups)");
+}
+
+int fv_redundant_vis_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                          const int *ant2, int ngroups, const int *group, const void *gains, const void *data,
+                          const void *weights, void *uvis, double *den) {
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_redundant_vis_rows: tpol must be 1 or 4");
+        FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_redundant_vis_rows: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_redundant_vis_rows: nant must be positive");
+        FV_REQUIRE(ngroups >= 1, "fv_redundant_vis_rows: ngroups must be positive");
+        FV_REQUIRE(nrows == 0 || (gains && uvis && den), "fv_redundant_vis_rows: null gains, uvis or den");
+        FV_REQUIRE(nrows == 0 || nbls == 0 || (data && ant1 && ant2 && group), "fv_redundant_vis_rows: null pairs, group or data");
+        if (nrows > 0) require_pairs("fv_redundant_vis_rows", nbls, nant, ant1, ant2);
+        if (nrows > 0) require_groups("fv_redundant_vis_rows", nbls, ngroups, group);
+        redundant_rows_host<decltype(real)>(device, true, nrows, nbls, tpol, nant, ant1, ant2, ngroups, group, gains, uvis, data,
+                                            weights, nullptr, den);
+    });
+}
+
+int fv_redundant_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                             const int *ant2, int ngroups, const int *group, const void *gains, const void *uvis,
+                             const void *data, const void *weights, void *num, double *den) {
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_redundant_normal_rows: tpol must be 1 or 4");
+        FV_REQUIRE(nrows >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_redundant_normal_rows: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_redundant_normal_rows: nant must be positive");
+        FV_REQUIRE(ngroups >= 1, "fv_redundant_normal_rows: ngroups must be positive");
+        FV_REQUIRE(nrows == 0 || (gains && num && den), "fv_redundant_normal_rows: null gains, num or den");
+        FV_REQUIRE(nrows == 0 || nbls == 0 || (uvis && data && ant1 && ant2 && group),
+                   "fv_redundant_normal_rows: null pairs, group, uvis or data");
+        if (nrows > 0) require_pairs("fv_redundant_normal_rows", nbls, nant, ant1, ant2);
+        if (nrows > 0) require_groups("fv_redundant_normal_rows", nbls, ngroups, group);
+        redundant_rows_host<decltype(real)>(device, false, nrows, nbls, tpol, nant, ant1, ant2, ngroups, group, gains,
+                                            const_cast<void *>(uvis), data, weights, num, den);
+    });
+}
+
+int fv_redundant_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1,
+                       const int *ant2, int ngroups, const int *group, int per_time, const void *data, int data_on_device,
+                       const void *weights, int weights_on_device, void *gains, void *uvis_out, int max_iter, double tol,
+                       int *niter_out, double *change_out, double *chi2_ft_out, int *solved_out, int *vis_solved_out) {
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_redundant_solve: tpol must be 1 or 4");
+        FV_REQUIRE(nfreqs >= 0 && ntimes >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29), "fv_redundant_solve: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_redundant_solve: nant must be positive");
+        FV_REQUIRE(ngroups >= 1, "fv_redundant_solve: ngroups must be positive");
+        FV_REQUIRE(max_iter >= 1, "fv_redundant_solve: max_iter must be positive");
+        FV_REQUIRE(tol >= 0.0, "fv_redundant_solve: tol must be non-negative");  // (a NaN fails the comparison)
+        FV_REQUIRE(((per_time | data_on_device | weights_on_device) & ~1) == 0,
+                   "fv_redundant_solve: per_time and the on_device flags must be 0 or 1");
+        FV_REQUIRE(niter_out, "fv_redundant_solve: null niter_out");
+        const bool empty = nfreqs == 0 || ntimes == 0;
+        FV_REQUIRE(empty || (gains && uvis_out && change_out && chi2_ft_out && solved_out && vis_solved_out),
+                   "fv_redundant_solve: null gains, uvis_out, change_out, chi2_ft_out, solved_out or vis_solved_out");
+        FV_REQUIRE(empty || nbls == 0 || (data && ant1 && ant2 && group), "fv_redundant_solve: null pairs, group or data");
+        if (!empty) require_pairs("fv_redundant_solve", nbls, nant, ant1, ant2);
+        if (!empty) require_groups("fv_redundant_solve", nbls, ngroups, group);
+        redundant_solve_host<decltype(real)>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, ngroups, group, per_time, data,
+                                             data_on_device, weights, weights_on_device, gains, uvis_out, max_iter, tol, niter_out,
+                                             change_out, chi2_ft_out, solved_out, vis_solved_out);
     });
 }
 

@@ -794,12 +794,15 @@ __global__ void __launch_bounds__(256)
 // the antenna keeps its value and is not solved), g <- g^ on odd iterations and (g^ + g) / 2 on even ones, written into
 // the OTHER buffer, and change[unit] = max |g_new - g| / max |g_new| (a max: any order gives the same bits).  No
 // floating-point atomics anywhere.
-template <typename T, bool CHI2>
+// GROUPED = true is the gather of the redundant solve below: the model of baseline k is its group's visibility,
+// uvis[(row tpol + pol) ngroups + group[k]] (complex128 whatever T is), read in place of vis[e]; nothing else differs.
+template <typename T, bool CHI2, bool GROUPED = false>
 __global__ void __launch_bounds__(256)
     k_gain_normal(const cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
                   const cplx<double> *__restrict__ gains, const int *__restrict__ ant1, const int *__restrict__ ant2,
                   const int *__restrict__ inc_off, const int *__restrict__ inc, int64_t nrows, int64_t rows_per_unit, int nbls,
-                  int tpol, int nant, int in_lds, cplx<double> *__restrict__ num, double *__restrict__ den) {
+                  int tpol, int nant, int in_lds, cplx<double> *__restrict__ num, double *__restrict__ den,
+                  const cplx<double> *__restrict__ uvis = nullptr, const int *__restrict__ group = nullptr, int ngroups = 0) {
     extern __shared__ __align__(16) unsigned char gain_lds[];
     const int nfeed = tpol == 4 ? 2 : 1, ng = nfeed * nant;
     const int wave = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
@@ -826,7 +829,11 @@ __global__ void __launch_bounds__(256)
                 const T wt = weights ? weights[e] : (T)1;
                 if (!(wt > (T)0)) continue;  // flagged: nothing is added, V and the datum are not read
                 const cplx<double> go = side ? g[p * nant + a1] : g[q * nant + a2];  // the other antenna's gain
-                const cplx<double> v = {(double)vis[e].re, (double)vis[e].im};
+                cplx<double> v;
+                if (GROUPED)
+                    v = uvis[(row * tpol + (nfeed == 2 ? 2 * q + p : 0)) * ngroups + group[k]];
+                else
+                    v = {(double)vis[e].re, (double)vis[e].im};
                 const cplx<double> d = {(double)data[e].re, (double)data[e].im};
                 if (CHI2) {
                     const cplx<double> vp = cmul(cmul(cconj(g[feed * nant + ant]), go), v);
@@ -914,7 +921,8 @@ __global__ void __launch_bounds__(256)
     if (lane == 0) chi2_rows[row] = s;
 }
 // The counting pass of a solve: bad[0] weights that are negative or not finite, bad[1] data that are not finite at a
-// used sample (w > 0, a1 != a2), bad[2] model values that are not finite.  n = nrows tpol nbls elements, read only.
+// used sample (w > 0, a1 != a2), bad[2] model values that are not finite (vis null: a solve without a model, nothing is
+// counted there).  n = nrows tpol nbls elements, read only.
 template <typename T>
 __global__ void __launch_bounds__(256)
     k_gain_solve_check(const cplx<T> *__restrict__ vis, const cplx<T> *__restrict__ data, const T *__restrict__ weights,
@@ -925,7 +933,7 @@ __global__ void __launch_bounds__(256)
         const T w = weights ? weights[e] : (T)1;
         if (!(w >= (T)0) || !isfinite(w)) ++bad_w;
         if (w > (T)0 && ant1[k] != ant2[k] && (!isfinite(data[e].re) || !isfinite(data[e].im))) ++bad_d;
-        if (!isfinite(vis[e].re) || !isfinite(vis[e].im)) ++bad_v;
+        if (vis && (!isfinite(vis[e].re) || !isfinite(vis[e].im))) ++bad_v;
     }
     if (bad_w) atomicAdd(bad, bad_w);
     if (bad_d) atomicAdd(bad + 1, bad_d);
@@ -954,6 +962,161 @@ inline void launch_gain_normal(hipStream_t on, const cplx<T> *vis, const cplx<T>
 inline void throw_if_bad_solve_input(const int bad[3]) {
     throw_if_bad_residual_input(bad);
     if (bad[2]) throw Error(FV_ERR_ARG, std::to_string(bad[2]) + " values of the model are not finite");
+}
+
+// ---------------------------------------------------------------------------------------------
+// Redundant solve (fv_redundant_vis_rows, fv_redundant_normal_rows, fv_redundant_solve; DESIGN.md "Redundant solve"):
+// the gain solve above without a sky.  Every baseline k belongs to a redundant group, group[k] in [0, ngroups), and the
+// model is V'[row, pol, k] = conj(g[p, a1]) g[q, a2] U[row, pol, group[k]] with one unknown visibility U per (row, pol,
+// group), complex128 whatever T is.  The solve alternates two linear problems.  For fixed gains the best U is a weighted
+// average over the group's used samples (w > 0, a1 != a2; a flagged datum is not read): with m = conj(g[p, a1]) g[q, a2]
+//     num = sum w conj(m) d,   den = sum w |m|^2,   U = num / den where den > 0, else U keeps its value,
+// k_red_vis.  For fixed U the gains are the gain solve's with V = U[group[k]]: k_gain_normal<T, CHI2, true> and
+// k_gain_update as it stands.  The groups' members come as a CSR, goff[r] .. goff[r + 1] the baselines of group r in
+// ascending order (group_members): one wave per (row, group), lane l takes the members l, l + 64, ... in order and all tpol
+// samples of a member -- tpol complex num and tpol den in fp64 registers, every term formed in fp64 from the T-typed inputs
+// --, an __shfl_xor tree, and lane 0 writes U and den.  The row's gains are staged in LDS when they fit GAIN_LDS_BYTES, which
+// is why a wave without a group stays for the barriers.  With the baselines in group order a group's members are
+// consecutive and the loads of d and w coalesce.  No floating-point atomics: the same input gives the same bits.
+inline void group_members(int ngroups, int64_t nbls, const int *group, std::vector<int> &off, std::vector<int> &mem) {
+    FV_REQUIRE(ngroups >= 1 && nbls >= 0 && nbls < ((int64_t)1 << 30) && (nbls == 0 || group), "groups: bad ngroups, nbls or null group");
+    for (int64_t k = 0; k < nbls; ++k) FV_REQUIRE(group[k] >= 0 && group[k] < ngroups, "groups: group index outside [0, ngroups)");
+    off.assign((size_t)ngroups + 1, 0);
+    for (int64_t k = 0; k < nbls; ++k) ++off[group[k] + 1];
+    for (int r = 0; r < ngroups; ++r) off[r + 1] += off[r];
+    mem.assign((size_t)nbls, 0);
+    std::vector<int> at(off.begin(), off.end() - 1);
+    for (int64_t k = 0; k < nbls; ++k) mem[at[group[k]]++] = (int)k;
+}
+// The group of every baseline and the groups' member lists on the device (one set per call)
+struct RedGroups {
+    DevBuf d_group, d_off, d_mem;
+    int ngroups = 0;
+    int64_t nbls = -1;         // -1: not set
+    std::vector<int> h_group;  // what the device holds while nbls >= 0
+    void set(hipStream_t on, int ngroups_, int64_t nbls_, const int *group) {
+        if (nbls >= 0 && nbls_ == nbls && ngroups_ == ngroups && (nbls_ == 0 || group) && std::equal(h_group.begin(), h_group.end(), group))
+            return;
+        std::vector<int> off, mem;
+        group_members(ngroups_, nbls_, group, off, mem);
+        nbls = -1;
+        h_group.assign(group, group + nbls_);
+        const size_t nb = sizeof(int) * (size_t)nbls_;
+        d_group.reserve(std::max<size_t>(nb, 16));
+        d_mem.reserve(std::max<size_t>(nb, 16));
+        d_off.reserve(sizeof(int) * off.size());
+        if (nb) {
+            FV_HIP(hipMemcpyAsync(d_group.p, group, nb, hipMemcpyHostToDevice, on));
+            FV_HIP(hipMemcpyAsync(d_mem.p, mem.data(), nb, hipMemcpyHostToDevice, on));
+        }
+        FV_HIP(hipMemcpyAsync(d_off.p, off.data(), sizeof(int) * off.size(), hipMemcpyHostToDevice, on));
+        FV_HIP(hipStreamSynchronize(on));  // (off and mem are this call's)
+        ngroups = ngroups_;
+        nbls = nbls_;
+    }
+};
+// uvis, den: (nrows, TPOL, ngroups); den may be null.  TPOL is the template's so that the sums stay in registers.  LANES
+// lanes take a group: 64, a wave, or 16 (-DFV_RED_VIS_LANES=16: four groups per wave, lane l of a group's 16 takes the
+// members l, l + 16, ...; measured on HERA-350, whose median group has 3 members, in profiles/MEASUREMENTS.md).
+#ifndef FV_RED_VIS_LANES
+#define FV_RED_VIS_LANES 64
+#endif
+template <typename T, int TPOL, int LANES>
+__global__ void __launch_bounds__(256)
+    k_red_vis(const cplx<T> *__restrict__ data, const T *__restrict__ weights, const cplx<double> *__restrict__ gains,
+              const int *__restrict__ ant1, const int *__restrict__ ant2, const int *__restrict__ goff, const int *__restrict__ gmem,
+              int64_t nrows, int64_t rows_per_unit, int nbls, int nant, int ngroups, int in_lds, cplx<double> *__restrict__ uvis,
+              double *__restrict__ den) {
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    constexpr int nfeed = TPOL == 4 ? 2 : 1;
+    const int ng = nfeed * nant;
+    static_assert(LANES == 64 || LANES == 16, "a group takes a wave or a quarter of one");
+    const int r = (int)blockIdx.x * (256 / LANES) + (int)(threadIdx.x / LANES), lane = (int)(threadIdx.x % LANES);
+    const bool active = r < ngroups;  // (whole waves stay: the tree below is inside a group's aligned LANES lanes)
+    const int i0 = active ? goff[r] : 0, i1 = active ? goff[r + 1] : 0;
+    const int64_t L = (int64_t)TPOL * nbls;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        const cplx<double> *g = gains + (row / rows_per_unit) * ng;
+        if (in_lds) {
+            cplx<double> *gl = reinterpret_cast<cplx<double> *>(gain_lds);
+            for (int i = threadIdx.x; i < ng; i += 256) gl[i] = g[i];
+            g = gl;
+            __syncthreads();
+        }
+        double sr[TPOL], si[TPOL], sd[TPOL];
+#pragma unroll
+        for (int pol = 0; pol < TPOL; ++pol) sr[pol] = si[pol] = sd[pol] = 0.0;
+        for (int i = i0 + lane; i < i1; i += LANES) {
+            const int k = gmem[i];
+            const int a1 = ant1[k], a2 = ant2[k];
+            if (a1 == a2) continue;  // an auto-correlation is flagged
+#pragma unroll
+            for (int pol = 0; pol < TPOL; ++pol) {
+                const int p = pol & 1, q = pol >> 1;
+                const int64_t e = row * L + (int64_t)pol * nbls + k;
+                const T wt = weights ? weights[e] : (T)1;
+                if (!(wt > (T)0)) continue;  // flagged: nothing is added, the datum is not read
+                const cplx<double> m = cmul(cconj(g[p * nant + a1]), g[q * nant + a2]);
+                const cplx<double> d = {(double)data[e].re, (double)data[e].im};
+                const cplx<double> t = cmul(cconj(m), d);
+                sr[pol] += (double)wt * t.re;
+                si[pol] += (double)wt * t.im;
+                sd[pol] += (double)wt * (m.re * m.re + m.im * m.im);
+            }
+        }
+#pragma unroll
+        for (int pol = 0; pol < TPOL; ++pol)
+            for (int off = LANES / 2; off > 0; off >>= 1) {
+                sr[pol] += __shfl_xor(sr[pol], off, 64);
+                si[pol] += __shfl_xor(si[pol], off, 64);
+                sd[pol] += __shfl_xor(sd[pol], off, 64);
+            }
+        if (active && lane == 0) {
+#pragma unroll
+            for (int pol = 0; pol < TPOL; ++pol) {
+                const int64_t at = (row * TPOL + pol) * ngroups + r;
+                if (sd[pol] > 0.0) uvis[at] = {sr[pol] / sd[pol], si[pol] / sd[pol]};
+                if (den) den[at] = sd[pol];
+            }
+        }
+        if (in_lds) __syncthreads();  // (the next row of this block stages its gains again)
+    }
+}
+// Queues one U-step on `on`.  All device pointers; weights and den may be null.
+template <typename T>
+inline void launch_red_vis(hipStream_t on, const cplx<T> *data, const T *weights, const cplx<double> *gains, const GainPairs &gp,
+                           const RedGroups &rg, int64_t nrows, int64_t rows_per_unit, int tpol, cplx<double> *uvis, double *den) {
+    const int nbls = (int)gp.nbls, nant = gp.nant, ng = (tpol == 4 ? 2 : 1) * nant;
+    const size_t lds = sizeof(cplx<double>) * (size_t)ng;
+    const int in_lds = lds <= GAIN_LDS_BYTES;
+    const dim3 grid((unsigned)cdiv(rg.ngroups, 256 / FV_RED_VIS_LANES), (unsigned)std::min<int64_t>(nrows, 65535));
+    if (tpol == 4)
+        hipLaunchKernelGGL((k_red_vis<T, 4, FV_RED_VIS_LANES>), grid, dim3(256), in_lds ? lds : 0, on, data, weights, gains, gp.d_ant1.as<int>(),
+                           gp.d_ant2.as<int>(), rg.d_off.as<int>(), rg.d_mem.as<int>(), nrows, rows_per_unit, nbls, nant, rg.ngroups,
+                           in_lds, uvis, den);
+    else
+        hipLaunchKernelGGL((k_red_vis<T, 1, FV_RED_VIS_LANES>), grid, dim3(256), in_lds ? lds : 0, on, data, weights, gains, gp.d_ant1.as<int>(),
+                           gp.d_ant2.as<int>(), rg.d_off.as<int>(), rg.d_mem.as<int>(), nrows, rows_per_unit, nbls, nant, rg.ngroups,
+                           in_lds, uvis, den);
+}
+// launch_gain_normal with the groups' visibilities as the model (k_gain_normal<T, CHI2, true>)
+template <typename T>
+inline void launch_red_normal(hipStream_t on, const cplx<double> *uvis, const cplx<T> *data, const T *weights,
+                              const cplx<double> *gains, const GainPairs &gp, const RedGroups &rg, int64_t nrows,
+                              int64_t rows_per_unit, int tpol, cplx<double> *num, double *den, double *chi2_part) {
+    const int nbls = (int)gp.nbls, nant = gp.nant, ng = (tpol == 4 ? 2 : 1) * nant;
+    const size_t lds = sizeof(cplx<double>) * (size_t)ng;
+    const int in_lds = lds <= GAIN_LDS_BYTES;
+    const dim3 grid((unsigned)cdiv(ng, 4), (unsigned)std::min<int64_t>(nrows, 65535));
+    const cplx<T> *no_vis = nullptr;
+    if (chi2_part)
+        hipLaunchKernelGGL((k_gain_normal<T, true, true>), grid, dim3(256), in_lds ? lds : 0, on, no_vis, data, weights, gains,
+                           gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), gp.d_off.as<int>(), gp.d_inc.as<int>(), nrows, rows_per_unit,
+                           nbls, tpol, nant, in_lds, (cplx<double> *)nullptr, chi2_part, uvis, rg.d_group.as<int>(), rg.ngroups);
+    else
+        hipLaunchKernelGGL((k_gain_normal<T, false, true>), grid, dim3(256), in_lds ? lds : 0, on, no_vis, data, weights, gains,
+                           gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), gp.d_off.as<int>(), gp.d_inc.as<int>(), nrows, rows_per_unit,
+                           nbls, tpol, nant, in_lds, num, den, uvis, rg.d_group.as<int>(), rg.ngroups);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,0 +1,313 @@
+"""Redundant-baseline calibration on the device ("Redundant solve"): the per-antenna gains together with one
+unknown visibility per redundant group, without a sky model.
+
+The data model is ``V'[f, t, pol, k] = conj(g[p, a1]) g[q, a2] U[f, t, pol, group[k]]``.  ``redundant_groups`` builds the
+groups, ``redundant_gain_solve`` alternates the two linear halves on a device block (``fv_redundant_solve``),
+``redundant_average`` is the visibility half alone (``fv_redundant_vis_rows``) and ``fix_redundant_degeneracies`` fixes
+what the data leave free.  The host layer (shapes of the gains, their start, device buffers) is the gain solve's, in
+``adjoint``.
+"""
+
+from __future__ import annotations
+
+import dataclasses
+
+import numpy as np
+
+from .adjoint import (
+    _Run,
+    _check_vis_block,
+    _check_weights,
+    _gain_block,
+    _host,
+    _is_tensor,
+    _on,
+    _run_device,
+    _solve_result,
+    _solve_start,
+    _synchronize,
+)
+from .core.utils import get_pos_reds
+
+
+def redundant_groups(ants: dict, baselines: list = None, decimals: int = 3):
+    """The redundant groups of an array and the group of every baseline: ``(reds, baselines, group)``.
+
+    * ``reds``: ``get_pos_reds(ants, decimals, include_autos=False)``, a list of lists of antenna pairs, every pair in the
+      orientation its group measures.
+    * ``baselines``: None means every baseline, in group order (``[bl for red in reds for bl in red]``): a group's baselines
+      are then consecutive, which is what the kernels read fastest.  A list is taken as it stands.
+    * ``group``: int32, the index into ``reds`` of every baseline.
+
+    A listed baseline that appears in its group only with the opposite orientation is a ValueError: swap the pair and
+    conjugate the datum (transposing ``[x, y]`` when polarized) -- the kernels carry no flip.  An auto-correlation in
+    ``baselines`` gets a group of its own, appended to ``reds``, and counts as flagged."""
+    return _groups(ants, None, baselines, decimals)
+
+
+def _groups(ants, reds, baselines, decimals=3):
+    reds = [list(map(tuple, red)) for red in (get_pos_reds(ants, decimals, include_autos=False) if reds is None else reds)]
+    if baselines is None:  # group order: nothing to look up
+        group = np.repeat(np.arange(len(reds), dtype=np.int32), [len(red) for red in reds])
+        return reds, [bl for red in reds for bl in red], group
+    index = {bl: r for r, red in enumerate(reds) for bl in red}
+    baselines = [tuple(bl) for bl in baselines]
+    group = np.zeros(len(baselines), dtype=np.int32)
+    for k, (i, j) in enumerate(baselines):
+        if i not in ants or j not in ants:
+            raise ValueError(f"baseline {(i, j)} names an antenna that is not a key of ants")
+        if (i, j) not in index:
+            if i == j:
+                index[(i, j)] = len(reds)
+                reds.append([(i, j)])
+            elif (j, i) in index:
+                raise ValueError(
+                    f"baseline {(i, j)} is in its redundant group as {(j, i)}: swap the pair and conjugate the datum "
+                    "(transposing [x, y] when polarized); the kernels carry no flip"
+                )
+            else:
+                raise ValueError(f"baseline {(i, j)} is in no redundant group")
+        group[k] = index[(i, j)]
+    return reds, baselines, group
+
+
+def _block_run(data, ants, polarized, precision, device) -> _Run:
+    """What the gain solve's host layer reads of a run, from a data block instead of a simulation's arguments."""
+    if precision not in (1, 2):
+        raise ValueError(f"precision must be 1 or 2, got {precision!r}")
+    tail = 3 if polarized else 1
+    shape = tuple(data.shape)
+    if len(shape) != 2 + tail or (polarized and shape[2:4] != (2, 2)):
+        want = "(nfreqs, ntimes, 2, 2, nbls)" if polarized else "(nfreqs, ntimes, nbls)"
+        raise ValueError(f"data must have shape {want}, got {shape}")
+    return _Run(
+        args=dict(polarized=bool(polarized), device=device, precision=precision), ants={k: np.array(v) for k, v in ants.items()},
+        beam_list=None, beam_idx=None, beam_coefs=None, baselines=None, eps=None, astrom=None, nsrc=0, nfreqs=shape[0],
+        ntimes=shape[1], nbls=shape[-1], rdt=np.float32 if precision == 1 else np.float64,
+        cdt=np.complex64 if precision == 1 else np.complex128, vis_shape=shape,
+    )
+
+
+def _block_inputs(run: _Run, ants, reds, baselines, data, weights):
+    """The checks and the buffers both entry points share: (reds, baselines, group, a1, a2, d, w and their addresses)."""
+    reds, baselines, group = _groups(ants, reds, baselines)
+    if len(baselines) != run.nbls:
+        raise ValueError(f"data holds {run.nbls} baselines, baselines lists {len(baselines)}")
+    _check_vis_block(run, data, "data")
+    if weights is not None:
+        _check_weights(run, weights, "data's")
+        _run_device(run, (weights,), "weights")
+    row = {a: i for i, a in enumerate(run.ants)}
+    a1 = np.fromiter((row[bl[0]] for bl in baselines), np.int32, count=run.nbls)
+    a2 = np.fromiter((row[bl[1]] for bl in baselines), np.int32, count=run.nbls)
+    return reds, baselines, group, a1, a2
+
+
+def _buffer(run: _Run, x, what):
+    """As the library reads it: a tensor on the run's device by pointer, anything else as a host array."""
+    if x is None:
+        return None
+    if _is_tensor(x) and x.device.type == "cuda":
+        return _on(x.device, x, run.dtype(what))
+    return np.ascontiguousarray(_host(x), dtype=run.dtype(what))
+
+
+def _follow(data, **arrays):
+    """Outputs follow ``data``: tensors where it is a tensor, on its device."""
+    if not _is_tensor(data):
+        return arrays
+    import torch
+
+    where = data.device if data.device.type == "cuda" else "cpu"
+    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(where) for k, v in arrays.items()}
+
+
+def redundant_gain_solve(
+    data,
+    ants: dict,
+    *,
+    reds: list = None,
+    baselines: list = None,
+    gains=None,
+    per_time: bool = False,
+    weights=None,
+    max_iter: int = 200,
+    tol: float = 1e-8,
+    ref_ant=None,
+    polarized: bool = False,
+    precision: int = 2,
+    device: int = 0,
+):
+    """Redundant calibration on the device: the per-antenna gains ``g`` and one visibility ``U`` per redundant group that
+    minimise ``chi2 = sum w |conj(g[a1]) g[a2] U[group] - data|^2``, without a sky model (``fv_redundant_solve``).  The two
+    halves are linear and alternate on a block that stays on the device: for fixed gains ``U = sum w conj(m) d / sum w |m|^2``
+    over a group's used samples, ``m = conj(g[a1]) g[a2]`` (``redundant_average``); for fixed ``U`` the gains are
+    ``simulate_vis_gain_solve``'s with the model ``V[k] = U[group[k]]`` and its update: ``g^ = num / den``, taken on odd
+    iterations and averaged with ``g`` on even ones.  ``U`` starts from 0.  Returns ``(gains, vis, info)``.
+
+    * ``data``, ``weights``: ``simulate_vis``'s block over ``baselines``, ``(nfreqs, ntimes, nbls)`` or, polarized,
+      ``(nfreqs, ntimes, 2, 2, nbls)``; numpy arrays or tensors, a tensor on the run's device is read by pointer.  A sample
+      is used when its weight is positive and it is no auto-correlation; a flagged datum is not read.  A negative or
+      non-finite weight and a non-finite datum at a used sample fail the call.
+    * ``reds``, ``baselines``: ``redundant_groups``'; ``reds=None`` groups ``ants`` by position, ``baselines=None`` means
+      every baseline in group order.
+    * ``gains``, ``per_time``, ``max_iter``, ``tol``, ``ref_ant``: ``simulate_vis_gain_solve``'s -- the start in any of its
+      four shapes or None for ones, the shape rule, the solve units, the end of the loop and the reference antenna.
+    * ``vis``: complex128 ``(nfreqs, ntimes, ngroups)`` or ``(nfreqs, ntimes, 2, 2, ngroups)``, the layout of
+      ``simulate_vis(..., baselines=[red[0] for red in reds])``; per time even for time-constant gains; from one more
+      visibility step at the returned gains (before ``ref_ant``, which does not change ``conj(g[a1]) g[a2]``).
+    * ``info``: ``niter``, ``converged``, ``change``, ``chi2`` ``(nfreqs, ntimes)`` at the returned gains and visibilities,
+      ``solved`` in the gains' shape, ``vis_solved`` in ``vis``' shape (False where a group had no used sample: its ``vis`` is
+      0), ``reds`` and ``baselines`` as used.
+    * The data leave four things free per solve unit and feed -- amplitude, phase and a phase gradient across the array --
+      and the result has them wherever the iteration left them: ``fix_redundant_degeneracies``.
+    * Convergence (numpy prototype, unit start, ``tol=1e-10``, noiseless): hex-19, hex-37 and a 4 x 4 grid with gain errors
+      of 5-20 % take 40-56 iterations; small arrays are slower (hex-7: 190-260, 3 x 3 grid: 120-190).  Polarized with
+      cross-hands as strong as the parallel hands 52-54, with the cross-hands flagged 74-84; weak cross-hands that are USED
+      (10 %) take over a thousand: flag them, as for ``simulate_vis_gain_solve``.
+
+    Outputs follow ``data`` to its device.  Not differentiable.  Not covered: firstcal (a start within a phase wrap of the
+    truth is the caller's), Jones matrices, a joint sky and redundant solve, near-redundancy, sharding over GPUs."""
+    if int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"tol must be non-negative, got {tol!r}")
+    run = _block_run(data, ants, polarized, precision, device)
+    if ref_ant is not None and ref_ant not in run.ants:
+        raise ValueError(f"ref_ant must be a key of ants, got {ref_ant!r}")
+    reds, baselines, group, a1, a2 = _block_inputs(run, ants, reds, baselines, data, weights)
+    block, shape, own_time = _solve_start(run, gains, per_time)
+
+    import torch
+
+    from . import _lib
+    from .gpu.gpu_simulate import _buffer_addr
+
+    d, w = _buffer(run, data, "complex"), _buffer(run, weights, "real")  # (alive until the call returns)
+    (d_ptr, d_dev), (w_ptr, w_dev) = _buffer_addr(d), _buffer_addr(w)
+    _synchronize(torch.device("cuda", int(device)))
+    tpol, ngroups = 4 if polarized else 1, len(reds)
+    niter = np.zeros(1, dtype=np.int32)
+    change = np.zeros((run.nfreqs, run.ntimes) if own_time else (run.nfreqs,), dtype=np.float64)
+    chi2 = np.zeros((run.nfreqs, run.ntimes), dtype=np.float64)
+    solved = np.zeros(block.shape, dtype=np.int32)
+    uvis = np.zeros((run.nfreqs, run.ntimes, tpol, ngroups), dtype=np.complex128)
+    vis_solved = np.zeros(uvis.shape, dtype=np.int32)
+    _lib.check(_lib.lib().fv_redundant_solve(
+        int(device), int(precision), run.nfreqs, run.ntimes, run.nbls, tpol, len(run.ants), _lib.ptr(a1), _lib.ptr(a2), ngroups,
+        _lib.ptr(group), int(own_time), d_ptr, d_dev, w_ptr, w_dev, _lib.ptr(block), _lib.ptr(uvis), int(max_iter), float(tol),
+        _lib.ptr(niter), _lib.ptr(change), _lib.ptr(chi2), _lib.ptr(solved), _lib.ptr(vis_solved)))
+    if ref_ant is not None:  # (feed 0's phase, both feeds alike)
+        ref = block[:, :, 0, list(run.ants).index(ref_ant)]
+        block = block * np.exp(-1j * np.angle(ref))[:, :, None, None]
+    out = _follow(data, gains=_solve_result(block, shape), vis=uvis.reshape(run.vis_shape[:-1] + (ngroups,)), change=change,
+                  chi2=chi2, solved=_solve_result(solved != 0, shape), vis_solved=(vis_solved != 0).reshape(run.vis_shape[:-1] + (ngroups,)))
+    info = dict(niter=int(niter[0]), converged=bool(niter[0] > 0 and np.all(change < tol)), change=out["change"], chi2=out["chi2"],
+                solved=out["solved"], vis_solved=out["vis_solved"], reds=reds, baselines=baselines)
+    return out["gains"], out["vis"], info
+
+
+def redundant_average(
+    data,
+    ants: dict,
+    gains,
+    *,
+    reds: list = None,
+    baselines: list = None,
+    weights=None,
+    polarized: bool = False,
+    precision: int = 2,
+    device: int = 0,
+):
+    """The calibrated, redundantly averaged data at any gains: the visibility step of ``redundant_gain_solve`` alone
+    (``fv_redundant_vis_rows``).  Per (frequency, time, pol, group), over the group's used samples and with
+    ``m = conj(g[a1]) g[a2]``:  ``den = sum w |m|^2``,  ``vis = sum w conj(m) d / den`` -- the least-squares group
+    visibility for these gains, 0 where ``den == 0``.  ``data``, ``weights``, ``reds``, ``baselines`` as in
+    ``redundant_gain_solve``; ``gains`` in any of ``simulate_vis_gain_chi2``'s four shapes, used in complex128.  Returns
+    ``(vis, den)`` in ``redundant_gain_solve``'s layout of ``vis``, complex128 and float64, following ``data`` to its device."""
+    run = _block_run(data, ants, polarized, precision, device)
+    reds, baselines, group, a1, a2 = _block_inputs(run, ants, reds, baselines, data, weights)
+    g = _gain_block(dataclasses.replace(run, cdt=np.complex128), gains)
+
+    import torch
+
+    from . import _lib
+
+    # host arrays: the U-step on its own is a tool, not a loop's inner step
+    d = np.ascontiguousarray(_host(data), dtype=run.cdt)
+    w = None if weights is None else np.ascontiguousarray(_host(weights), dtype=run.rdt)
+    _synchronize(torch.device("cuda", int(device)))
+    tpol, ngroups, nrows = 4 if polarized else 1, len(reds), run.nfreqs * run.ntimes
+    uvis = np.zeros((run.nfreqs, run.ntimes, tpol, ngroups), dtype=np.complex128)
+    den = np.zeros(uvis.shape, dtype=np.float64)
+    _lib.check(_lib.lib().fv_redundant_vis_rows(
+        int(device), int(precision), nrows, run.nbls, tpol, len(run.ants), _lib.ptr(a1), _lib.ptr(a2), ngroups, _lib.ptr(group),
+        _lib.ptr(g), _lib.ptr(d), _lib.ptr(w), _lib.ptr(uvis), _lib.ptr(den)))
+    out_shape = run.vis_shape[:-1] + (ngroups,)
+    out = _follow(data, vis=uvis.reshape(out_shape), den=den.reshape(out_shape))
+    return out["vis"], out["den"]
+
+
+def fix_redundant_degeneracies(gains, ants: dict, *, ref_gains=None, solved=None, tilt: str = "per_feed"):
+    """Fix what redundant calibration leaves free.  Per solve unit and feed the data do not constrain four numbers: the
+    amplitude of the gains, their overall phase, and a phase gradient across the array (``g_a -> g_a exp(i Phi . x_a)`` only
+    moves every group's visibility by ``exp(-i Phi . b)``).  This brings them to those of ``ref_gains`` (None: ones) -- for
+    instance a sky-based solve's.  On the host, in numpy: the work is nant-sized.
+
+    * ``gains``, ``ref_gains``: ``(nant, ...)``, rows in ``ants``' order, any of the gain solve's shapes; ``solved``: a bool
+      array of the same shape (``info["solved"]``), None for all.  Only solved antennas enter the fits and are changed.
+    * Per column over the antennas: the gains are scaled by ``exp(mean log|ref| - mean log|g|)``; ``arg(g conj(ref))`` is
+      fitted by ``psi + Phi . (x_a - mean x)`` over the antennas' positions by least squares (``lstsq``: the minimum-norm
+      solution, so a flat array's ``Phi_z`` is 0), and the gains are multiplied by ``exp(-i (psi + Phi . (x_a - mean x)))``.
+    * ``tilt="per_feed"`` fits every column on its own.  ``tilt="shared"`` takes axis 1 as the feed axis (polarized gains)
+      and fits one ``Phi`` for both feeds, with a ``psi`` each: needed when cross-hands were used, which tie the feeds'
+      gradients together.
+    * The phase differences ``arg(g conj(ref))`` must lie inside ``(-pi, pi)``; there is no unwrapping.
+
+    Returns the gains only, in ``gains``' shape, complex128.  The matching group visibilities are ``redundant_average`` at the
+    returned gains."""
+    if tilt not in ("per_feed", "shared"):
+        raise ValueError(f'tilt must be "per_feed" or "shared", got {tilt!r}')
+    g = np.array(_host(gains), dtype=np.complex128)
+    nant = len(ants)
+    if g.ndim < 1 or g.shape[0] != nant:
+        raise ValueError(f"gains must have one row per antenna ({nant}), got shape {g.shape}")
+    ref = np.ones_like(g) if ref_gains is None else np.asarray(_host(ref_gains), dtype=np.complex128)
+    ok = np.ones(g.shape, dtype=bool) if solved is None else np.asarray(_host(solved), dtype=bool)
+    if ref.shape != g.shape or ok.shape != g.shape:
+        raise ValueError(f"ref_gains and solved must have gains' shape {g.shape}")
+    if tilt == "shared" and (g.ndim < 2 or g.shape[1] != 2):
+        raise ValueError(f'tilt="shared" needs polarized gains (nant, 2, ...), got shape {g.shape}')
+    pos = np.array([np.asarray(ants[k], dtype=float) for k in ants]).reshape(nant, -1)
+    nfeed = 2 if tilt == "shared" else 1
+    # columns over the antennas: (nant, nfeed, units), the feeds of a unit fitted together when the tilt is shared
+    cols = g.reshape(nant, nfeed, -1) if tilt == "shared" else g.reshape(nant, 1, -1)
+    refs, oks = ref.reshape(cols.shape), ok.reshape(cols.shape)
+    out = cols.copy()
+    for u in range(cols.shape[2]):
+        use = oks[:, :, u]
+        if not use.any():
+            continue
+        centre = pos[use.any(axis=1)].mean(axis=0)
+        x = pos - centre
+        rows, rhs = [], []
+        for f in range(nfeed):
+            s = use[:, f]
+            if not s.any():
+                continue
+            scale = np.exp(np.mean(np.log(np.abs(refs[s, f, u]))) - np.mean(np.log(np.abs(cols[s, f, u]))))
+            out[s, f, u] = cols[s, f, u] * scale
+            psi = np.zeros((int(s.sum()), nfeed))
+            psi[:, f] = 1
+            rows.append(np.hstack([psi, x[s]]))
+            rhs.append(np.angle(cols[s, f, u] * np.conj(refs[s, f, u])))
+        fit = np.linalg.lstsq(np.vstack(rows), np.concatenate(rhs), rcond=None)[0]
+        for f in range(nfeed):
+            s = use[:, f]
+            out[s, f, u] *= np.exp(-1j * (fit[f] + x[s] @ fit[nfeed:]))
+    out = out.reshape(g.shape)
+    if _is_tensor(gains):
+        import torch
+
+        return torch.from_numpy(out).to(gains.device)
+    return out

@@ -180,6 +180,49 @@ int fv_gain_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbl
                   const int *ant2, int per_time, const void *vis, int vis_on_device, const void *data, int data_on_device,
                   const void *weights, int weights_on_device, void *gains, int max_iter, double tol, int *niter_out,
                   double *change_out, double *chi2_ft_out, int *solved_out);
+/* fv_redundant_vis_rows: the visibility step (U-step) of redundant calibration on its own: the weighted average of the
+ * calibrated data over every redundant group, at fixed gains.  The rows, the pairs and the feeds (pol = 2 q + p) are
+ * fv_gain_normal_rows'; group: (nbls) int32, the redundant group of baseline k, in [0, ngroups); gains: (nrows, nfeed,
+ * nant) complex128 whatever `precision` is; data, weights: read only, weights may be NULL (every weight 1).  The data
+ * model is V'[row, pol, k] = conj(g[p, ant1]) g[q, ant2] U[row, pol, group[k]], one unknown visibility U per row, pol and
+ * group.  A sample is used when w > 0 and ant1[k] != ant2[k]; a flagged datum is not read (NaN or Inf there do not
+ * propagate).  With m = conj(g[p, ant1]) g[q, ant2], over the used samples of group r,
+ *   num = sum w conj(m) d      den = sum w |m|^2      U = num / den where den > 0, else U keeps its value
+ * uvis: (nrows, tpol, ngroups) complex128, in: the values a group without a used sample keeps, out: U; den: the same
+ * shape in float64.  Every term is formed in fp64 from the inputs of `precision` and added in fp64 over the group's
+ * members in ascending k by one wave per (row, group) (lane l takes members l, l + 64, ..., all tpol samples of a member,
+ * an __shfl_xor tree) -- no floating-point atomics, the same input gives the same bits.  The baselines carry no flip: a
+ * baseline measured in the opposite orientation is swapped and its datum conjugated by the caller.  tpol not in {1, 4}, a
+ * negative shape, nant < 1, ngroups < 1, an antenna index outside [0, nant), a group index outside [0, ngroups) and a
+ * null pointer fail with FV_ERR_ARG before anything runs; nbls == 0 returns den = 0 and leaves uvis.  Host pointers. */
+int fv_redundant_vis_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                          const int *ant2, int ngroups, const int *group, const void *gains, const void *data,
+                          const void *weights, void *uvis, double *den);
+/* fv_redundant_normal_rows: the gain step's gather of redundant calibration on its own: fv_gain_normal_rows with the model
+ * V = U[row, pol, group[k]] read from uvis, (nrows, tpol, ngroups) complex128, in place of a block vis.  The order of the
+ * sums, the flags and the outputs num, den (nrows, nfeed, nant) are fv_gain_normal_rows'; group and the argument checks are
+ * fv_redundant_vis_rows'.  Host pointers. */
+int fv_redundant_normal_rows(int device, int precision, int64_t nrows, int64_t nbls, int tpol, int nant, const int *ant1,
+                             const int *ant2, int ngroups, const int *group, const void *gains, const void *uvis,
+                             const void *data, const void *weights, void *num, double *den);
+/* fv_redundant_solve: redundant calibration, entirely on the device: the gains g and the group visibilities U that minimise
+ * sum w |conj(g[p, ant1]) g[q, ant2] U[row, pol, group[k]] - d|^2 over the used samples, without a sky model.  data,
+ * weights, gains, per_time and the solve units are fv_gain_solve's; group is fv_redundant_vis_rows'.  U is per row even
+ * when the gains are time-constant, and starts from 0.  Iteration i = 1, 2, ...: the U-step of fv_redundant_vis_rows at
+ * the current gains; then the normal sums of fv_redundant_normal_rows at these U, for time-constant gains added over the
+ * unit's times in ascending order, and fv_gain_solve's update: g^ = num / den where den > 0, g <- g^ for odd i and
+ * (g^ + g) / 2 for even i, change[unit] = max |g_new - g| / max |g_new|.  The loop ends as fv_gain_solve's does, and only
+ * the units' change comes to the host per iteration.  After the loop one more U-step at the returned gains, and chi2 at
+ * (g, U) as fv_gain_solve forms it.  uvis_out: host, complex128, (nfreqs, ntimes, tpol, ngroups); vis_solved_out: int32 in
+ * the same shape, 0 where the group had no used sample in that row and pol (U is 0 there); niter_out, change_out,
+ * chi2_ft_out, solved_out: fv_gain_solve's.  Four degrees of freedom per unit and feed are not constrained by the data
+ * (amplitude, phase and a phase gradient across the array) and are left where the iteration puts them.  The counting pass
+ * of fv_gain_solve, without a model, fails the call with its messages; gains is then untouched.  The argument checks are
+ * fv_gain_solve's and fv_redundant_vis_rows'.  nbls == 0: the start gains, U = 0, chi2 0, nothing solved, niter 0. */
+int fv_redundant_solve(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1,
+                       const int *ant2, int ngroups, const int *group, int per_time, const void *data, int data_on_device,
+                       const void *weights, int weights_on_device, void *gains, void *uvis_out, int max_iter, double tol,
+                       int *niter_out, double *change_out, double *chi2_ft_out, int *solved_out, int *vis_solved_out);
 /* fv_jones_normal_rows: one evaluation of the 2 x 2 normal systems of the Jones solve (the gather fv_jones_solve
  * iterates).  The rows, the pairs and the layout of the matrices are fv_jones_residual_chi2's; vis, data, weights are
  * read only; jones: (nrows, 2, 2, nant) complex128 whatever `precision` is.  A sample is used when w > 0 and

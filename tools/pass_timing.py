@@ -21,6 +21,7 @@
                                                                                     beam_coefs: --config C5)
     gain_solve      forward solve solve_with_forward gauss_newton_products          C3, 8 channels
     jones_solve     forward solve solve_with_forward jones_chi2_steps               C3, 8 channels
+    redundant_solve solve gain_solve both                                           C3, 8 channels
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -66,7 +67,10 @@ simulate_vis_gain_solve on a resident model with resident data and weights, ``so
 forward, then the iterations), ``gauss_newton_products`` as many gains-only products of simulate_vis_gain_gauss_newton, each
 of which reruns the forward (``--profile solve`` for a kernel trace).  jones_solve: the same for the 2 x 2 matrices --
 ``solve`` and ``solve_with_forward`` call simulate_vis_jones_solve with no sample flagged, ``jones_chi2_steps`` is as many
-calls of simulate_vis_jones_chi2 with its gradient, each of which reruns the forward.  A flag of another family is an error.
+calls of simulate_vis_jones_chi2 with its gradient, each of which reruns the forward.  redundant_solve: ``solve`` is
+redundant_gain_solve on resident data and weights, every baseline of the array in group order, ``gain_solve``
+simulate_vis_gain_solve on the same block against the resident model U[group], 50 iterations each and no forward anywhere
+(``--only solve --only gain_solve``; ``--profile both`` runs one of each for a kernel trace).  A flag of another family is an error.
 tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
 
 import argparse
@@ -745,6 +749,60 @@ def jones_solve(a, fv, cfg, rng):
     return head, calls
 
 
+def redundant_solve(a, fv, cfg, rng):
+    """Redundant calibration next to the gain solve on the same block: GAIN_SOLVE_ITERATIONS iterations of
+    ``redundant_gain_solve`` on resident data and weights (host to host: the gains go up, the gains and the groups'
+    visibilities come back), and as many of ``simulate_vis_gain_solve`` against the resident model ``U[group]``.  Every
+    baseline of the array in group order, no sample flagged; the data are drawn group by group -- no forward runs.
+    ``--profile both`` is one solve of each, for a kernel trace."""
+    import torch
+
+    p = cfg["precision"]
+    cdt, rdt = (torch.complex64, torch.float32) if p == 1 else (torch.complex128, torch.float64)
+    ants, polarized = cfg["ants"], bool(cfg["polarized"])
+    nums = list(ants)
+    reds, bls, group = fv.redundant_groups(ants)
+    cfg = dict(cfg, baselines=bls, fluxes=None)
+    gshape = ((len(nums), 2) if polarized else (len(nums),)) + (a.nfreq,)
+    g_true = 1 + 0.1 * (rng.normal(size=gshape) + 1j * rng.normal(size=gshape))
+    state = {}
+
+    def resident():  # the model is every baseline's group visibility; data = the gained model plus noise
+        if not state:
+            gen = torch.Generator(device="cuda").manual_seed(0)
+            U = torch.randn((a.nfreq, a.ntimes) + ((2, 2) if polarized else ()) + (len(reds),), dtype=torch.complex128,
+                            device="cuda", generator=gen)
+            model = U[..., torch.from_numpy(group).cuda().long()].to(cdt).contiguous()
+            G = torch.from_numpy(g_true).cuda()
+            a1 = torch.tensor([nums.index(b[0]) for b in bls], device="cuda")
+            a2 = torch.tensor([nums.index(b[1]) for b in bls], device="cuda")
+            if polarized:  # out[f, t, x, y, k]: y is the first antenna's feed
+                m = (G[a2].permute(2, 1, 0)[:, :, None, :] * G[a1].conj().permute(2, 1, 0)[:, None, :, :])[:, None]
+            else:
+                m = (G[a1].conj() * G[a2]).T[:, None]
+            data = m * model
+            data = (data + 0.05 * data.abs().mean() * torch.randn(data.shape, dtype=data.dtype, device="cuda", generator=gen))
+            state.update(model=model, data=data.to(cdt).contiguous(), w=torch.ones(model.shape, dtype=rdt, device="cuda"))
+            torch.cuda.synchronize()
+        return state
+
+    def solve():
+        s = resident()
+        return fv.redundant_gain_solve(s["data"], ants, reds=reds, weights=s["w"], polarized=polarized,  # (bls: the default)
+                                       precision=p, max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    def gain_solve_on_the_block():
+        s = resident()
+        return fv.simulate_vis_gain_solve(s["data"], **cfg, weights=s["w"], model=s["model"], max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    def both():
+        solve()
+        gain_solve_on_the_block()
+
+    head = {"config": a.config, "precision": p, "polarized": polarized, "iterations": GAIN_SOLVE_ITERATIONS, "ngroups": len(reds)}
+    return head, {"solve": solve, "gain_solve": gain_solve_on_the_block, "both": both}
+
+
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
 #          ratios {key: (pass, pass it is divided by -- or a tuple of passes, for their sum)})
 FAMILIES = {
@@ -775,6 +833,7 @@ FAMILIES = {
         "solve_over_forward": ("solve", "forward"), "products_over_solve": ("gauss_newton_products", "solve")}),
     "jones_solve": (jones_solve, "C3", 8, (), "runs", {
         "solve_over_forward": ("solve", "forward"), "chi2_steps_over_solve": ("jones_chi2_steps", "solve")}),
+    "redundant_solve": (redundant_solve, "C3", 8, (), "runs", {"solve_over_gain_solve": ("solve", "gain_solve")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
              "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False, "jones": False,
