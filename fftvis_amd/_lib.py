@@ -58,6 +58,11 @@ SYMBOLS = {
     "fv_redundant_solve": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                    c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_firstcal_pair_delays": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_firstcal_offsets": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "fv_jones_normal_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
     "fv_jones_solve": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,

@@ -677,6 +677,83 @@ static void redundant_solve_host(int device, int nfreqs, int ntimes, int64_t nbl
     for (size_t i = 0; i < nu; ++i) vis_solved_out[i] = hden[i] > 0.0 ? 1 : 0;
 }
 
+// Firstcal, stage 1 (k_firstcal_products, k_firstcal_delay): a device block is used where it lies, a host block is staged
+// once; the twiddles exp(-2 pi i j / ND) are built here in fp64; the five outputs, (nfeed, npairs), come back at the end.
+template <typename T>
+static void firstcal_pair_delays_host(int device, int nfreqs, int ntimes, int64_t nbls, int tpol, int npairs, const int *pair1,
+                                      const int *pair2, const int *ant1, const int *ant2, const void *data,
+                                      int data_on_device, const void *weights, int weights_on_device, int pad, int *peak_bin_out,
+                                      double *delay_bins_out, double *power_out, double *total_out, int *used_out) {
+    const size_t nrows = (size_t)(tpol == 4 ? 2 : 1) * (size_t)npairs;
+    if (nrows == 0) return;
+    std::fill(peak_bin_out, peak_bin_out + nrows, 0);
+    std::fill(delay_bins_out, delay_bins_out + nrows, 0.0);
+    std::fill(power_out, power_out + nrows, 0.0);
+    std::fill(total_out, total_out + nrows, 0.0);
+    std::fill(used_out, used_out + nrows, 0);
+    if (nfreqs == 0 || ntimes == 0 || nbls == 0) return;  // (no sample: no pair is used)
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const size_t n = (size_t)nfreqs * (size_t)ntimes * (size_t)tpol * (size_t)nbls;
+    const int nd = pad * nfreqs;
+    std::vector<cplx<double>> tw((size_t)nd);
+    for (int j = 0; j < nd; ++j) tw[j] = {std::cos(2.0 * M_PI * (double)j / nd), -std::sin(2.0 * M_PI * (double)j / nd)};
+    DevBuf sd, sw, da1, da2, dp1, dp2, dtw, dz, dbin, dx, dpow, dtot, dused;
+    const cplx<T> *dd = data_on_device ? static_cast<const cplx<T> *>(data) : to_device<cplx<T>>(sg.s, sd, data, n);
+    const T *dw = weights_on_device ? static_cast<const T *>(weights) : to_device<T>(sg.s, sw, weights, n);
+    const int *a1 = to_device<int>(sg.s, da1, ant1, (size_t)nbls), *a2 = to_device<int>(sg.s, da2, ant2, (size_t)nbls);
+    const int *p1 = to_device<int>(sg.s, dp1, pair1, (size_t)npairs), *p2 = to_device<int>(sg.s, dp2, pair2, (size_t)npairs);
+    const cplx<double> *dt = to_device<cplx<double>>(sg.s, dtw, tw.data(), (size_t)nd);
+    dz.reserve(sizeof(cplx<double>) * nrows * (size_t)nfreqs);
+    dbin.reserve(sizeof(int) * nrows);
+    dx.reserve(sizeof(double) * nrows);
+    dpow.reserve(sizeof(double) * nrows);
+    dtot.reserve(sizeof(double) * nrows);
+    dused.reserve(sizeof(int) * nrows);
+    launch_firstcal_delays<T>(sg.s, dd, dw, a1, a2, (int)nbls, p1, p2, nfreqs, ntimes, tpol, npairs, dt, nd, dz.as<cplx<double>>(), dbin.as<int>(),
+                              dx.as<double>(), dpow.as<double>(), dtot.as<double>(), dused.as<int>());
+    FV_HIP(hipMemcpyAsync(peak_bin_out, dbin.p, sizeof(int) * nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(delay_bins_out, dx.p, sizeof(double) * nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(power_out, dpow.p, sizeof(double) * nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(total_out, dtot.p, sizeof(double) * nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(used_out, dused.p, sizeof(int) * nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+}
+
+// Firstcal, stage 2: the block derotated by the delay model into a buffer of this call (k_firstcal_derotate; the caller's
+// data are read only), then the redundant solve on it with the whole block as one unit -- redundant_solve_host with one
+// "frequency" of nfreqs ntimes "times": the (nfreqs, ntimes) block is contiguous, U and chi2 stay per row.
+template <typename T>
+static void firstcal_offsets_host(int device, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1,
+                                  const int *ant2, int ngroups, const int *group, const double *slopes, const void *data,
+                                  int data_on_device, const void *weights, int weights_on_device, void *offsets, void *uvis_out,
+                                  int max_iter, double tol, int *niter_out, double *change_out, double *chi2_ft_out, int *solved_out,
+                                  int *vis_solved_out) {
+    const int nfeed = tpol == 4 ? 2 : 1;
+    const size_t n = (size_t)nfreqs * (size_t)ntimes * (size_t)tpol * (size_t)nbls;
+    DevBuf sd, sw, ds, rotated;
+    const void *dw = weights;
+    if (n > 0) {
+        FV_HIP(hipSetDevice(device));
+        StreamGuard sg;
+        GainPairs gp;
+        gp.set(sg.s, nant, nbls, ant1, ant2);
+        const cplx<T> *dd = data_on_device ? static_cast<const cplx<T> *>(data) : to_device<cplx<T>>(sg.s, sd, data, n);
+        dw = weights_on_device ? weights : to_device<T>(sg.s, sw, weights, n);  // (null stays null)
+        const double *dsl = to_device<double>(sg.s, ds, slopes, (size_t)nfeed * (size_t)nant);
+        rotated.reserve(sizeof(cplx<T>) * n);
+        hipLaunchKernelGGL(k_firstcal_derotate<T>, dim3((unsigned)std::min<int64_t>(cdiv((int64_t)n, 256), 65535)), dim3(256), 0, sg.s,
+                           dd, static_cast<const T *>(dw), gp.d_ant1.as<int>(), gp.d_ant2.as<int>(), dsl, (int64_t)n, nfreqs, ntimes,
+                           (int)nbls, tpol, nant, rotated.as<cplx<T>>());
+        FV_HIP(hipStreamSynchronize(sg.s));  // (the solve runs on a stream of its own)
+        FV_HIP(hipGetLastError());
+    }
+    redundant_solve_host<T>(device, nfreqs > 0 ? 1 : 0, nfreqs * ntimes, nbls, tpol, nant, ant1, ant2, ngroups, group, 0, rotated.p, 1,
+                            dw, weights ? 1 : 0, offsets, uvis_out, max_iter, tol, niter_out, change_out, chi2_ft_out, solved_out,
+                            vis_solved_out);
+}
+
 template <typename T>
 static void jones_normal_rows_host(int device, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
                                    const void *jones, const void *vis, const void *data, const void *weights, double *A_out,
@@ -993,6 +1070,55 @@ int fv_redundant_solve(int device, int precision, int nfreqs, int ntimes, int64_
         redundant_solve_host<decltype(real)>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, ngroups, group, per_time, data,
                                              data_on_device, weights, weights_on_device, gains, uvis_out, max_iter, tol, niter_out,
                                              change_out, chi2_ft_out, solved_out, vis_solved_out);
+    });
+}
+
+int fv_firstcal_pair_delays(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int tpol, int npairs, const int *pair1,
+                            const int *pair2, const int *ant1, const int *ant2, const void *data, int data_on_device,
+                            const void *weights, int weights_on_device, int pad, int *peak_bin_out, double *delay_bins_out,
+                            double *power_out, double *total_out, int *used_out) {
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_firstcal_pair_delays: tpol must be 1 or 4");
+        FV_REQUIRE(nfreqs >= 0 && ntimes >= 0 && nbls >= 0 && nbls < ((int64_t)1 << 29) && npairs >= 0 && npairs < (1 << 29),
+                   "fv_firstcal_pair_delays: negative shape");
+        FV_REQUIRE(pad >= 1 && (int64_t)pad * nfreqs < ((int64_t)1 << 20), "fv_firstcal_pair_delays: pad must be positive and pad nfreqs below 2^20");
+        FV_REQUIRE(((data_on_device | weights_on_device) & ~1) == 0, "fv_firstcal_pair_delays: the on_device flags must be 0 or 1");
+        FV_REQUIRE(npairs == 0 || (peak_bin_out && delay_bins_out && power_out && total_out && used_out),
+                   "fv_firstcal_pair_delays: null peak_bin_out, delay_bins_out, power_out, total_out or used_out");
+        const bool empty = nfreqs == 0 || ntimes == 0 || nbls == 0 || npairs == 0;
+        FV_REQUIRE(empty || (pair1 && pair2 && ant1 && ant2 && data), "fv_firstcal_pair_delays: null pairs or data");
+        for (int i = 0; !empty && i < npairs; ++i)
+            FV_REQUIRE(pair1[i] >= 0 && pair1[i] < nbls && pair2[i] >= 0 && pair2[i] < nbls,
+                       "fv_firstcal_pair_delays: baseline index outside [0, nbls)");
+        firstcal_pair_delays_host<decltype(real)>(device, nfreqs, ntimes, nbls, tpol, npairs, pair1, pair2, ant1, ant2, data,
+                                                  data_on_device, weights, weights_on_device, pad, peak_bin_out, delay_bins_out,
+                                                  power_out, total_out, used_out);
+    });
+}
+
+int fv_firstcal_offsets(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1,
+                        const int *ant2, int ngroups, const int *group, const double *slopes, const void *data, int data_on_device,
+                        const void *weights, int weights_on_device, void *offsets, void *uvis_out, int max_iter, double tol,
+                        int *niter_out, double *change_out, double *chi2_ft_out, int *solved_out, int *vis_solved_out) {
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_firstcal_offsets: tpol must be 1 or 4");
+        FV_REQUIRE(nfreqs >= 0 && ntimes >= 0 && (int64_t)nfreqs * ntimes < ((int64_t)1 << 31) && nbls >= 0 && nbls < ((int64_t)1 << 29),
+                   "fv_firstcal_offsets: negative shape");
+        FV_REQUIRE(nant >= 1, "fv_firstcal_offsets: nant must be positive");
+        FV_REQUIRE(ngroups >= 1, "fv_firstcal_offsets: ngroups must be positive");
+        FV_REQUIRE(max_iter >= 1, "fv_firstcal_offsets: max_iter must be positive");
+        FV_REQUIRE(tol >= 0.0, "fv_firstcal_offsets: tol must be non-negative");  // (a NaN fails the comparison)
+        FV_REQUIRE(((data_on_device | weights_on_device) & ~1) == 0, "fv_firstcal_offsets: the on_device flags must be 0 or 1");
+        FV_REQUIRE(niter_out, "fv_firstcal_offsets: null niter_out");
+        const bool empty = nfreqs == 0 || ntimes == 0;
+        FV_REQUIRE(empty || (offsets && uvis_out && change_out && chi2_ft_out && solved_out && vis_solved_out),
+                   "fv_firstcal_offsets: null offsets, uvis_out, change_out, chi2_ft_out, solved_out or vis_solved_out");
+        FV_REQUIRE(empty || nbls == 0 || (data && ant1 && ant2 && group && slopes), "fv_firstcal_offsets: null pairs, group, slopes or data");
+        if (!empty) require_pairs("fv_firstcal_offsets", nbls, nant, ant1, ant2);
+        if (!empty) require_groups("fv_firstcal_offsets", nbls, ngroups, group);
+        firstcal_offsets_host<decltype(real)>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, ngroups, group, slopes, data,
+                                              data_on_device, weights, weights_on_device, offsets, uvis_out, max_iter, tol, niter_out,
+                                              change_out, chi2_ft_out, solved_out, vis_solved_out);
     });
 }
 

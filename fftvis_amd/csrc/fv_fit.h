@@ -1120,6 +1120,192 @@ inline void launch_red_normal(hipStream_t on, const cplx<double> *uvis, const cp
 }
 
 // ---------------------------------------------------------------------------------------------
+// Firstcal (fv_firstcal_pair_delays, fv_firstcal_offsets; DESIGN.md "Firstcal"): the start of the redundant solve above, one
+// delay and one complex number per antenna and feed, g[a](f) = c[a] exp(i s[a] (f - (nfreqs - 1) / 2)), s = 2 pi tau dnu.
+// Stage 1, the pair delays.  A pair is two baselines k = pair1[i], k' = pair2[i] of one redundant group; feed p reads the
+// parallel hand pol = 3 p of a polarized block.  The group's visibility cancels out of
+//     z[feed, i, f] = sum_t d[f, t, pol, k] conj(d[f, t, pol, k'])   over the times at which both samples are used
+// (w > 0 and a1 != a2: weights act as flags here, a flagged datum is not read), whose phase is linear in f with the slope
+// s[a2[k]] - s[a1[k]] - s[a2[k']] + s[a1[k']].  k_firstcal_products: one thread per (feed, f, pair), the pair fastest, so
+// that with the baselines in group order -- a pair is two neighbours -- the loads of d and w coalesce; every term formed and
+// added in fp64, times ascending.  k_firstcal_delay: one wave per (feed, pair) finds the peak of the periodogram
+//     P[n] = sum_f z[f] tw[(n f) mod ND],   tw[j] = exp(-2 pi i j / ND),   ND = pad nfreqs,   n = 0 .. ND - 1:
+// lane l takes the bins l, l + 64, ... with the index n f mod ND advanced by n per channel (n < ND: one conditional
+// subtraction, no product that could overflow), keeps the first maximum of |P[n]|^2 it meets, and an __shfl_xor tree takes
+// the larger power, the lower bin on a tie.  The bin is signed, n - ND where 2 n >= ND.  Four rounds of a parabola through
+// |P(x)|^2 at x - h, x, x + h, h = 1, 1/4, 1/16, 1/64, refine it: P(x) = sum_f z[f] exp(-2 pi i x f / ND) evaluated at the
+// continuous x with sincospi in fp64, lane l adding the channels l, l + 64, ... of the three points, an __shfl_xor tree
+// (every lane ends with the same bits), den = y- - 2 y0 + y+, and where den < 0 the step 0.5 h (y- - y+) / den clipped to
+// +-h.  The wave's z row is staged in LDS when the block's four rows fit GAIN_LDS_BYTES, which is why a wave without a pair
+// stays for the barrier.  A pair is used when at least two channels have a non-zero z; one that is not reports bin 0,
+// x = 0 and power 0.  Stage 2 derotates the block by the delay model, k_firstcal_derotate,
+//     d'[f, t, pol, k] = d exp(-i (f - (nfreqs - 1) / 2) (s[q, a2] - s[p, a1])),   p = pol & 1, q = pol >> 1,
+// phase and product in fp64, into a buffer of the call (0 where the sample is not used: a flagged datum is not read), and
+// the redundant solve runs on d' with the whole block as one unit.  No floating-point atomics: the same input gives the
+// same bits.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_firstcal_products(const cplx<T> *__restrict__ data, const T *__restrict__ weights, const int *__restrict__ ant1,
+                        const int *__restrict__ ant2, const int *__restrict__ pair1, const int *__restrict__ pair2, int nfreqs,
+                        int ntimes, int nbls, int tpol, int npairs, cplx<double> *__restrict__ z) {
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= npairs) return;
+    const int k1 = pair1[i], k2 = pair2[i];
+    const bool cross = ant1[k1] != ant2[k1] && ant1[k2] != ant2[k2];  // an auto-correlation is flagged
+    const int nfeed = tpol == 4 ? 2 : 1;
+    for (int r = (int)blockIdx.y; r < nfeed * nfreqs; r += (int)gridDim.y) {
+        const int f = r % nfreqs, feed = r / nfreqs;
+        double sr = 0.0, si = 0.0;
+        for (int t = 0; cross && t < ntimes; ++t) {  // ascending time
+            const int64_t at = (((int64_t)f * ntimes + t) * tpol + 3 * feed) * nbls;
+            if (weights && !(weights[at + k1] > (T)0 && weights[at + k2] > (T)0)) continue;  // flagged: the data are not read
+            const cplx<double> a = {(double)data[at + k1].re, (double)data[at + k1].im};
+            const cplx<double> b = {(double)data[at + k2].re, (double)data[at + k2].im};
+            sr += a.re * b.re + a.im * b.im;
+            si += a.im * b.re - a.re * b.im;
+        }
+        z[((int64_t)feed * npairs + i) * nfreqs + f] = {sr, si};
+    }
+}
+// |P(x)|^2 at x - h, x and x + h for the continuous bin x: the wave's lanes split the channels; every lane returns the same bits
+__device__ inline void firstcal_three_points(const cplx<double> *__restrict__ zr, int nfreqs, int lane, double x, double h, double nd,
+                                             double y[3]) {
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int f = lane; f < nfreqs; f += 64) {
+        const cplx<double> zf = zr[f];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double sn, cs;
+            sincospi(-2.0 * (x + (j - 1) * h) * (double)f / nd, &sn, &cs);
+            s[2 * j] += zf.re * cs - zf.im * sn;
+            s[2 * j + 1] += zf.re * sn + zf.im * cs;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+        for (int off = 32; off > 0; off >>= 1) s[j] += __shfl_xor(s[j], off, 64);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) y[j] = s[2 * j] * s[2 * j] + s[2 * j + 1] * s[2 * j + 1];
+}
+// z: (nrows, nfreqs), nrows = nfeed npairs; tw: (nd); the outputs: (nrows).  Dynamic LDS: 4 nfreqs complex128 when in_lds.
+__global__ void __launch_bounds__(256)
+    k_firstcal_delay(const cplx<double> *__restrict__ z, const cplx<double> *__restrict__ tw, int nrows, int nfreqs, int nd, int in_lds,
+                     int *__restrict__ peak_bin, double *__restrict__ delay_bins, double *__restrict__ power, double *__restrict__ total,
+                     int *__restrict__ used) {
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    const int w = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const int row = (int)blockIdx.x * 4 + w;
+    const bool active = row < nrows;  // (whole waves: the trees below stay inside one)
+    const cplx<double> *zr = z + (int64_t)(active ? row : 0) * nfreqs;
+    double tot = 0.0;
+    int nonzero = 0;
+    for (int f = lane; active && f < nfreqs; f += 64) {
+        const cplx<double> zf = zr[f];
+        if (in_lds) reinterpret_cast<cplx<double> *>(gain_lds)[w * nfreqs + f] = zf;
+        tot += zf.re * zf.re + zf.im * zf.im;
+        nonzero += (zf.re != 0.0 || zf.im != 0.0) ? 1 : 0;
+    }
+    if (in_lds) {
+        __syncthreads();
+        zr = reinterpret_cast<const cplx<double> *>(gain_lds) + w * nfreqs;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        tot += __shfl_xor(tot, off, 64);
+        nonzero += __shfl_xor(nonzero, off, 64);
+    }
+    if (!active) return;  // (no barrier follows)
+    if (nonzero < 2) {
+        if (lane == 0) {
+            peak_bin[row] = 0;
+            delay_bins[row] = 0.0;
+            power[row] = 0.0;
+            total[row] = tot;
+            used[row] = 0;
+        }
+        return;
+    }
+    // the coarse peak: the first maximum of this lane's bins, then the wave's
+    double best = -1.0;
+    int best_n = 0;
+    for (int n = lane; n < nd; n += 64) {
+        double pr = 0.0, pi = 0.0;
+        int j = 0;  // n f mod nd
+        for (int f = 0; f < nfreqs; ++f) {
+            const cplx<double> zf = zr[f], t = tw[j];
+            pr += zf.re * t.re - zf.im * t.im;
+            pi += zf.re * t.im + zf.im * t.re;
+            j += n;
+            if (j >= nd) j -= nd;
+        }
+        const double y = pr * pr + pi * pi;
+        if (y > best) {
+            best = y;
+            best_n = n;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ob = __shfl_xor(best, off, 64);
+        const int on = __shfl_xor(best_n, off, 64);
+        if (ob > best || (ob == best && on < best_n)) {
+            best = ob;
+            best_n = on;
+        }
+    }
+    const int bin = 2 * best_n >= nd ? best_n - nd : best_n;
+    double x = (double)bin, y[3];
+    for (int round = 0; round < 4; ++round) {
+        const double h = 1.0 / (double)(1 << (2 * round));
+        firstcal_three_points(zr, nfreqs, lane, x, h, (double)nd, y);
+        const double den = y[0] - 2.0 * y[1] + y[2];
+        if (den < 0.0) x += fmin(fmax(0.5 * h * (y[0] - y[2]) / den, -h), h);
+    }
+    firstcal_three_points(zr, nfreqs, lane, x, 0.0, (double)nd, y);
+    if (lane == 0) {
+        peak_bin[row] = bin;
+        delay_bins[row] = x;
+        power[row] = y[1];
+        total[row] = tot;
+        used[row] = 1;
+    }
+}
+// slopes: (nfeed, nant) radians per channel; out: the block's shape.  n = nfreqs ntimes tpol nbls elements.
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_firstcal_derotate(const cplx<T> *__restrict__ data, const T *__restrict__ weights, const int *__restrict__ ant1,
+                        const int *__restrict__ ant2, const double *__restrict__ slopes, int64_t n, int nfreqs, int ntimes, int nbls,
+                        int tpol, int nant, cplx<T> *__restrict__ out) {
+    const int64_t row_len = (int64_t)tpol * nbls;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int64_t row = e / row_len;
+        const int pol = (int)((e - row * row_len) / nbls), k = (int)(e % nbls);
+        const int a1 = ant1[k], a2 = ant2[k];
+        cplx<T> o = {(T)0, (T)0};
+        if (a1 != a2 && (!weights || weights[e] > (T)0)) {  // else flagged: the datum is not read
+            const int p = tpol == 4 ? (pol & 1) : 0, q = tpol == 4 ? (pol >> 1) : 0;
+            const double c = (double)(row / ntimes) - 0.5 * (double)(nfreqs - 1);
+            double sn, cs;
+            sincos(-c * (slopes[q * nant + a2] - slopes[p * nant + a1]), &sn, &cs);
+            const double dr = (double)data[e].re, di = (double)data[e].im;
+            o = {(T)(dr * cs - di * sn), (T)(dr * sn + di * cs)};
+        }
+        out[e] = o;
+    }
+}
+// Queues the two kernels of stage 1 on `on`.  All device pointers; weights may be null.  z: (nfeed npairs, nfreqs) scratch.
+template <typename T>
+inline void launch_firstcal_delays(hipStream_t on, const cplx<T> *data, const T *weights, const int *ant1, const int *ant2,
+                                   int nbls, const int *pair1, const int *pair2, int nfreqs, int ntimes, int tpol, int npairs, const cplx<double> *tw, int nd,
+                                   cplx<double> *z, int *peak_bin, double *delay_bins, double *power, double *total, int *used) {
+    const int nfeed = tpol == 4 ? 2 : 1, nrows = nfeed * npairs;
+    hipLaunchKernelGGL(k_firstcal_products<T>, dim3((unsigned)cdiv(npairs, 256), (unsigned)std::min(nfeed * nfreqs, 65535)), dim3(256), 0, on, data,
+                       weights, ant1, ant2, pair1, pair2, nfreqs, ntimes, nbls, tpol, npairs, z);
+    const size_t lds = sizeof(cplx<double>) * 4 * (size_t)nfreqs;
+    const int in_lds = lds <= GAIN_LDS_BYTES;
+    hipLaunchKernelGGL(k_firstcal_delay, dim3((unsigned)cdiv(nrows, 4)), dim3(256), in_lds ? lds : 0, on, (const cplx<double> *)z, tw,
+                       nrows, nfreqs, nd, in_lds, peak_bin, delay_bins, power, total, used);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Jones solve on a resident model (fv_jones_normal_rows, fv_jones_solve; DESIGN.md "Jones solve"): the gain solve above
 // with one 2 x 2 matrix per antenna.  The block, the pairs and the incidence lists are the Jones kernels', tpol = 4; V, d
 // and w are read only; a sample is used when w > 0 and a1 != a2.  The iterate is complex128 whatever T is, (nunits, 2, 2,

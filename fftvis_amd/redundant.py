@@ -2,7 +2,8 @@
 unknown visibility per redundant group, without a sky model.
 
 The data model is ``V'[f, t, pol, k] = conj(g[p, a1]) g[q, a2] U[f, t, pol, group[k]]``.  ``redundant_groups`` builds the
-groups, ``redundant_gain_solve`` alternates the two linear halves on a device block (``fv_redundant_solve``),
+groups, ``redundant_firstcal`` finds the start of data with cable delays (``fv_firstcal_pair_delays``,
+``fv_firstcal_offsets``), ``redundant_gain_solve`` alternates the two linear halves on a device block (``fv_redundant_solve``),
 ``redundant_average`` is the visibility half alone (``fv_redundant_vis_rows``) and ``fix_redundant_degeneracies`` fixes
 what the data leave free.  The host layer (shapes of the gains, their start, device buffers) is the gain solve's, in
 ``adjoint``.
@@ -166,8 +167,9 @@ def redundant_gain_solve(
       cross-hands as strong as the parallel hands 52-54, with the cross-hands flagged 74-84; weak cross-hands that are USED
       (10 %) take over a thousand: flag them, as for ``simulate_vis_gain_solve``.
 
-    Outputs follow ``data`` to its device.  Not differentiable.  Not covered: firstcal (a start within a phase wrap of the
-    truth is the caller's), Jones matrices, a joint sky and redundant solve, near-redundancy, sharding over GPUs."""
+    Outputs follow ``data`` to its device.  Not differentiable.  A start within a phase wrap of the truth -- firstcal, for
+    data whose gains carry cable delays -- is ``redundant_firstcal``'s ``gains``.  Not covered: Jones matrices, a joint sky
+    and redundant solve, near-redundancy, sharding over GPUs."""
     if int(max_iter) != max_iter or max_iter < 1:
         raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
     if not float(tol) >= 0.0:
@@ -204,6 +206,148 @@ def redundant_gain_solve(
                   chi2=chi2, solved=_solve_result(solved != 0, shape), vis_solved=(vis_solved != 0).reshape(run.vis_shape[:-1] + (ngroups,)))
     info = dict(niter=int(niter[0]), converged=bool(niter[0] > 0 and np.all(change < tol)), change=out["change"], chi2=out["chi2"],
                 solved=out["solved"], vis_solved=out["vis_solved"], reds=reds, baselines=baselines)
+    return out["gains"], out["vis"], info
+
+
+def _firstcal_pairs(group):
+    """Consecutive members of every group in ascending baseline index: two int32 arrays of nbls - (groups with members)
+    baseline indices.  They span every within-group difference."""
+    order = np.argsort(group, kind="stable")
+    same = group[order][1:] == group[order][:-1]
+    return order[:-1][same].astype(np.int32), order[1:][same].astype(np.int32)
+
+
+def redundant_firstcal(
+    data,
+    ants: dict,
+    freqs,
+    *,
+    reds: list = None,
+    baselines: list = None,
+    weights=None,
+    offsets=None,
+    pad: int = 8,
+    max_iter: int = 200,
+    tol: float = 1e-8,
+    ref_ant=None,
+    polarized: bool = False,
+    precision: int = 2,
+    device: int = 0,
+):
+    """Firstcal on the device: the start ``redundant_gain_solve`` needs on data whose gains carry cable delays.  The model is
+    one delay and one complex number per antenna and feed, constant in time: ``g[a](nu) = c[a] exp(2 pi i tau[a] (nu -
+    mean(freqs)))``.  Returns ``(gains, vis, info)``; ``redundant_gain_solve(data, ants, gains=gains, ...)`` then converges in a
+    few iterations, and every channel lands on the same smooth value of the degeneracies, so that
+    ``fix_redundant_degeneracies`` applies.
+
+    * Stage 1, delays (``fv_firstcal_pair_delays``).  For two baselines ``k = (i, j)``, ``k' = (m, n)`` of one redundant group
+      the group's visibility cancels out of ``z[f] = sum_t d[k] conj(d[k'])``, whose phase winds with the delay
+      ``tau_j - tau_i - tau_n + tau_m``.  The pairs are consecutive members of every group (``nbls - ngroups`` of them);
+      polarized data use the parallel hands, feed p reads ``[p, p]``; weights act as flags here.  The delay of a pair is the
+      peak of ``|sum_f z[f] exp(-2 pi i n f / ND)|^2`` over ``ND = pad nfreqs`` bins, refined by four rounds of a parabola
+      through three points of the exact periodogram at half-widths 1, 1/4, 1/16 and 1/64 of a bin.  A pair is used when at
+      least two channels have a non-zero ``z``.  The antenna delays are the minimum-norm least-squares solution of the used
+      pairs' equations (``lstsq``, on the host: the work is nant-sized), so the common delay and the delay gradient across
+      the array, which the data leave free, are 0.  Pair delays beyond ``+-1 / (2 dnu)`` alias.
+    * Stage 2, one number per antenna (``fv_firstcal_offsets``).  The block is derotated by the delay model into a buffer of
+      the call and ``redundant_gain_solve``'s iteration runs on it with the whole block as one solve unit: ``max_iter``,
+      ``tol`` and the messages of bad input are its.  ``offsets``: the start, ``(nant,)`` or ``(nant, 2)`` complex, None for ones.
+    * ``data``, ``weights``, ``reds``, ``baselines``, ``polarized``, ``precision``, ``device``, ``ref_ant``:
+      ``redundant_gain_solve``'s; ``freqs``: ``(nfreqs,)`` in Hz, at least two, uniformly spaced (to 1e-6 of the spacing).
+    * ``gains``: complex128 ``(nant, nfreqs)`` or ``(nant, 2, nfreqs)``; ``vis``: the group visibilities at these gains in
+      ``redundant_gain_solve``'s layout.
+    * ``info``: ``delays`` ``(nant[, 2])`` in seconds, ``offsets`` (the ``c[a]``), ``pairs`` (a list of baseline pairs),
+      ``pair_delays`` and ``pair_used`` ``([2,] npairs)``, ``niter``, ``converged``, ``change``, ``chi2`` ``(nfreqs, ntimes)``,
+      ``solved`` ``(nant[, 2])`` (False for an antenna in no used pair, whose delay is 0, or without a used sample),
+      ``vis_solved``, ``reds`` and ``baselines`` as used.
+
+    Outputs follow ``data`` to its device.  Not differentiable.  Not covered: polarity flips (pi offsets of swapped feeds),
+    per-time delays, non-uniform channels, aliasing beyond ``+-1 / (2 dnu)``, Jones matrices, sharding over GPUs."""
+    if int(max_iter) != max_iter or max_iter < 1:
+        raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"tol must be non-negative, got {tol!r}")
+    run = _block_run(data, ants, polarized, precision, device)
+    nu = np.asarray(_host(freqs), dtype=np.float64)
+    if nu.shape != (run.nfreqs,):
+        raise ValueError(f"freqs must have shape ({run.nfreqs},), got {nu.shape}")
+    if run.nfreqs < 2:
+        raise ValueError("firstcal needs at least two channels")
+    dnu = (nu[-1] - nu[0]) / (run.nfreqs - 1)
+    if not (np.isfinite(dnu) and dnu != 0.0 and np.all(np.abs(np.diff(nu) - dnu) <= 1e-6 * abs(dnu))):
+        raise ValueError("freqs must be uniformly spaced (to 1e-6 of the spacing)")
+    if int(pad) != pad or pad < 1 or pad * run.nfreqs >= 1 << 20:
+        raise ValueError(f"pad must be a positive integer with pad * nfreqs < 2**20, got {pad!r}")
+    if ref_ant is not None and ref_ant not in run.ants:
+        raise ValueError(f"ref_ant must be a key of ants, got {ref_ant!r}")
+    reds, baselines, group, a1, a2 = _block_inputs(run, ants, reds, baselines, data, weights)
+    nant, nfeed = len(run.ants), 2 if polarized else 1
+    lead = (nant, 2) if polarized else (nant,)
+    if offsets is None:
+        c = np.ones((nfeed, nant), dtype=np.complex128)
+    else:
+        c = _host(offsets)
+        if not np.iscomplexobj(c) or c.shape != lead:
+            raise ValueError(f"offsets must be complex of shape {lead}, got {c.shape}")
+        if not np.isfinite(c).all():
+            raise ValueError("offsets must be finite")
+        c = np.array(c.reshape(nant, nfeed).T, dtype=np.complex128, order="C")  # a copy: the library writes the result into it
+    pair1, pair2 = _firstcal_pairs(group)
+
+    import torch
+
+    from . import _lib
+    from .gpu.gpu_simulate import _buffer_addr
+
+    # both stages read the block: a host block goes to the device once, here (alive until the calls return)
+    on = torch.device("cuda", int(device))
+    d, w = _on(on, data, run.cdt), None if weights is None else _on(on, weights, run.rdt)
+    (d_ptr, d_dev), (w_ptr, w_dev) = _buffer_addr(d), _buffer_addr(w)
+    _synchronize(on)
+    tpol, ngroups, npairs, nd = 4 if polarized else 1, len(reds), len(pair1), int(pad) * run.nfreqs
+    peak = np.zeros((nfeed, npairs), dtype=np.int32)
+    x, power, total = (np.zeros((nfeed, npairs), dtype=np.float64) for _ in range(3))
+    used = np.zeros((nfeed, npairs), dtype=np.int32)
+    _lib.check(_lib.lib().fv_firstcal_pair_delays(
+        int(device), int(precision), run.nfreqs, run.ntimes, run.nbls, tpol, npairs, _lib.ptr(pair1), _lib.ptr(pair2), _lib.ptr(a1),
+        _lib.ptr(a2), d_ptr, d_dev, w_ptr, w_dev, int(pad), _lib.ptr(peak), _lib.ptr(x), _lib.ptr(power), _lib.ptr(total),
+        _lib.ptr(used)))
+    pair_delays = x / (nd * dnu)
+    # A tau = dtau over the used pairs, per feed: +1 at a2[k] and a1[k'], -1 at a1[k] and a2[k']
+    A = np.zeros((npairs, nant))
+    for col, sign in ((a2[pair1], 1.0), (a1[pair2], 1.0), (a1[pair1], -1.0), (a2[pair2], -1.0)):
+        np.add.at(A, (np.arange(npairs), col), sign)
+    tau, in_pair = np.zeros((nfeed, nant)), np.zeros((nfeed, nant), dtype=bool)
+    alike = nfeed == 2 and np.array_equal(used[0], used[1])  # (the usual case: one factorisation for both feeds)
+    for feeds in ([[0, 1]] if alike else [[f] for f in range(nfeed)]):
+        rows = used[feeds[0]] != 0
+        if rows.any():
+            tau[feeds] = np.linalg.lstsq(A[rows], pair_delays[feeds][:, rows].T, rcond=None)[0].T
+            in_pair[feeds] = np.abs(A[rows]).sum(axis=0) > 0
+    tau[~in_pair] = 0.0
+    slopes = np.ascontiguousarray(2.0 * np.pi * tau * dnu)
+    niter, change = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.float64)
+    chi2 = np.zeros((run.nfreqs, run.ntimes), dtype=np.float64)
+    solved = np.zeros((nfeed, nant), dtype=np.int32)
+    uvis = np.zeros((run.nfreqs, run.ntimes, tpol, ngroups), dtype=np.complex128)
+    vis_solved = np.zeros(uvis.shape, dtype=np.int32)
+    _lib.check(_lib.lib().fv_firstcal_offsets(
+        int(device), int(precision), run.nfreqs, run.ntimes, run.nbls, tpol, nant, _lib.ptr(a1), _lib.ptr(a2), ngroups, _lib.ptr(group),
+        _lib.ptr(slopes), d_ptr, d_dev, w_ptr, w_dev, _lib.ptr(c), _lib.ptr(uvis), int(max_iter), float(tol), _lib.ptr(niter),
+        _lib.ptr(change), _lib.ptr(chi2), _lib.ptr(solved), _lib.ptr(vis_solved)))
+    if ref_ant is not None:  # (feed 0's phase, both feeds alike)
+        c = c * np.exp(-1j * np.angle(c[0, list(run.ants).index(ref_ant)]))
+    gains = c[:, :, None] * np.exp(2j * np.pi * tau[:, :, None] * (nu - nu.mean()))  # (nfeed, nant, nfreqs)
+    out_shape = run.vis_shape[:-1] + (ngroups,)
+    out = _follow(data, gains=np.ascontiguousarray(gains.transpose(1, 0, 2)).reshape(lead + (run.nfreqs,)), vis=uvis.reshape(out_shape),
+                  delays=np.ascontiguousarray(tau.T).reshape(lead), offsets=np.array(c.T, order="C").reshape(lead), chi2=chi2,
+                  pair_delays=pair_delays.reshape((2, npairs) if polarized else (npairs,)),
+                  pair_used=(used != 0).reshape((2, npairs) if polarized else (npairs,)),
+                  solved=np.ascontiguousarray(((solved != 0) & in_pair).T).reshape(lead), vis_solved=(vis_solved != 0).reshape(out_shape))
+    info = dict(delays=out["delays"], offsets=out["offsets"], pairs=[(baselines[i], baselines[j]) for i, j in zip(pair1, pair2)],
+                pair_delays=out["pair_delays"], pair_used=out["pair_used"], niter=int(niter[0]),
+                converged=bool(niter[0] > 0 and change[0] < tol), change=float(change[0]), chi2=out["chi2"], solved=out["solved"],
+                vis_solved=out["vis_solved"], reds=reds, baselines=baselines)
     return out["gains"], out["vis"], info
 
 

@@ -223,6 +223,42 @@ int fv_redundant_solve(int device, int precision, int nfreqs, int ntimes, int64_
                        const int *ant2, int ngroups, const int *group, int per_time, const void *data, int data_on_device,
                        const void *weights, int weights_on_device, void *gains, void *uvis_out, int max_iter, double tol,
                        int *niter_out, double *change_out, double *chi2_ft_out, int *solved_out, int *vis_solved_out);
+/* fv_firstcal_pair_delays: stage 1 of firstcal, the start of fv_redundant_solve on data whose gains carry cable delays:
+ * the delay difference of every pair of baselines of one redundant group.  The block, the weights and the on_device flags
+ * are fv_redundant_solve's; pair1, pair2: (npairs) int32, the baselines k and k' of pair i, both of one group (the caller
+ * takes consecutive members of every group); ant1, ant2 only tell which baselines are auto-correlations.  Feed p of a
+ * polarized block uses the parallel hand pol = 3 p.  A sample is used when w > 0 and ant1[k] != ant2[k]: weights act as
+ * flags here, and a flagged datum is not read.  The group's visibility cancels out of
+ *   z[feed, i, f] = sum_t d[f, t, pol, k] conj(d[f, t, pol, k'])      over the times at which both samples are used
+ * every term formed and added in fp64, times ascending.  With ND = pad nfreqs the coarse peak is the lowest n of maximal
+ * |P[n]|^2, P[n] = sum_f z[f] exp(-2 pi i n f / ND), n = 0 .. ND - 1, taken as a signed bin: n - ND where 2 n >= ND.  Four
+ * rounds of a parabola through |P(x)|^2 at x - h, x, x + h, h = 1, 1/4, 1/16, 1/64, evaluated at the continuous x, refine
+ * it: den = y- - 2 y0 + y+, and where den < 0 the step 0.5 h (y- - y+) / den clipped to +-h.  One wave per (feed, pair):
+ * the bins go over the lanes with twiddles exp(-2 pi i j / ND) built on the host in fp64 and indexed by n f mod ND; the
+ * refinement uses sincospi in fp64 with the lanes splitting the sum over f and a fixed __shfl_xor tree -- no
+ * floating-point atomics, the same input gives the same bits.  Outputs, host, (nfeed, npairs): peak_bin_out int32, the signed
+ * coarse bin; delay_bins_out float64, the refined x in bins (the pair's delay tau[a2[k]] - tau[a1[k]] - tau[a2[k']] +
+ * tau[a1[k']] is x / (ND dnu): the library needs no channel width; beyond +-ND / 2 it aliases); power_out, |P(x)|^2;
+ * total_out, sum_f |z[f]|^2; used_out int32, 1 when at least two channels have a non-zero z, else 0 with bin 0, x = 0 and
+ * power 0.  tpol not in {1, 4}, a negative shape, pad < 1 or pad nfreqs >= 2^20, an on_device flag outside {0, 1}, a
+ * baseline index outside [0, nbls) and a null pointer fail with FV_ERR_ARG before anything runs; npairs == 0 is a valid
+ * call, and nbls == 0, nfreqs == 0 or ntimes == 0 return zeros. */
+int fv_firstcal_pair_delays(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int tpol, int npairs, const int *pair1,
+                            const int *pair2, const int *ant1, const int *ant2, const void *data, int data_on_device,
+                            const void *weights, int weights_on_device, int pad, int *peak_bin_out, double *delay_bins_out,
+                            double *power_out, double *total_out, int *used_out);
+/* fv_firstcal_offsets: stage 2 of firstcal: one complex number per antenna and feed, constant in frequency and time, on
+ * the block derotated by the delay model.  slopes: host, (nfeed, nant) float64, s = 2 pi tau dnu in radians per channel;
+ *   d'[f, t, pol, k] = d exp(-i (f - (nfreqs - 1) / 2) (s[q, ant2] - s[p, ant1]))      p = pol & 1, q = pol >> 1
+ * with the phase and the product in fp64, written into a buffer of the call: the caller's data are never written, and a
+ * flagged datum is not read.  fv_redundant_solve's loop then runs on d' with the whole block as one solve unit, U per row.
+ * offsets: host, (nfeed, nant) complex128, in: the start, out: the result; change_out: one value; uvis_out, niter_out,
+ * chi2_ft_out (nfreqs, ntimes), solved_out (nfeed, nant), vis_solved_out, max_iter, tol, the counting pass, its messages
+ * and the argument checks are fv_redundant_solve's.  nbls == 0: the start, U = 0, chi2 0, nothing solved, niter 0. */
+int fv_firstcal_offsets(int device, int precision, int nfreqs, int ntimes, int64_t nbls, int tpol, int nant, const int *ant1,
+                        const int *ant2, int ngroups, const int *group, const double *slopes, const void *data, int data_on_device,
+                        const void *weights, int weights_on_device, void *offsets, void *uvis_out, int max_iter, double tol,
+                        int *niter_out, double *change_out, double *chi2_ft_out, int *solved_out, int *vis_solved_out);
 /* fv_jones_normal_rows: one evaluation of the 2 x 2 normal systems of the Jones solve (the gather fv_jones_solve
  * iterates).  The rows, the pairs and the layout of the matrices are fv_jones_residual_chi2's; vis, data, weights are
  * read only; jones: (nrows, 2, 2, nant) complex128 whatever `precision` is.  A sample is used when w > 0 and

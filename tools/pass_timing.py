@@ -22,6 +22,7 @@
     gain_solve      forward solve solve_with_forward gauss_newton_products          C3, 8 channels
     jones_solve     forward solve solve_with_forward jones_chi2_steps               C3, 8 channels
     redundant_solve solve gain_solve both                                           C3, 8 channels
+    firstcal        firstcal solve                                                  C3, 8 channels
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -70,7 +71,10 @@ of which reruns the forward (``--profile solve`` for a kernel trace).  jones_sol
 calls of simulate_vis_jones_chi2 with its gradient, each of which reruns the forward.  redundant_solve: ``solve`` is
 redundant_gain_solve on resident data and weights, every baseline of the array in group order, ``gain_solve``
 simulate_vis_gain_solve on the same block against the resident model U[group], 50 iterations each and no forward anywhere
-(``--only solve --only gain_solve``; ``--profile both`` runs one of each for a kernel trace).  A flag of another family is an error.
+(``--only solve --only gain_solve``; ``--profile both`` runs one of each for a kernel trace).  firstcal: ``firstcal`` is
+redundant_firstcal on resident data whose gains carry delays of up to 150 ns, channels of 0.5 MHz, 50 iterations of its second
+stage, ``solve`` redundant_gain_solve from the firstcal gains, 50 iterations (``--profile firstcal`` for a kernel trace).  A flag
+of another family is an error.
 tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
 
 import argparse
@@ -803,6 +807,63 @@ def redundant_solve(a, fv, cfg, rng):
     return head, {"solve": solve, "gain_solve": gain_solve_on_the_block, "both": both}
 
 
+def firstcal(a, fv, cfg, rng):
+    """Firstcal on resident data and weights (host to host): ``redundant_firstcal`` with GAIN_SOLVE_ITERATIONS iterations of
+    its second stage, and the ``redundant_gain_solve`` it starts, as many iterations from the firstcal gains.  Every baseline
+    of the array in group order, no sample flagged, channels of 0.5 MHz; the gains carry delays uniform in +-150 ns, phases
+    in +-pi and amplitudes 1 +- 0.1; the data are drawn group by group, 5 % noise -- no forward runs.  ``--profile firstcal``
+    is one call, for a kernel trace."""
+    import torch
+
+    p = cfg["precision"]
+    cdt, rdt = (torch.complex64, torch.float32) if p == 1 else (torch.complex128, torch.float64)
+    ants, polarized = cfg["ants"], bool(cfg["polarized"])
+    nums = list(ants)
+    reds, bls, group = fv.redundant_groups(ants)
+    cfg["baselines"] = bls  # (the line's nbls)
+    freqs = 150e6 + 0.5e6 * np.arange(a.nfreq)
+    lead = (len(nums), 2) if polarized else (len(nums),)
+    tau = rng.uniform(-150e-9, 150e-9, lead)
+    c = rng.uniform(0.9, 1.1, lead) * np.exp(1j * rng.uniform(-np.pi, np.pi, lead))
+    g_true = c[..., None] * np.exp(2j * np.pi * tau[..., None] * (freqs - freqs.mean()))
+    state = {}
+
+    def resident():
+        if not state:
+            gen = torch.Generator(device="cuda").manual_seed(0)
+            U = torch.randn((a.nfreq, a.ntimes) + ((2, 2) if polarized else ()) + (len(reds),), dtype=torch.complex128,
+                            device="cuda", generator=gen)
+            G = torch.from_numpy(g_true).cuda()
+            a1 = torch.tensor([nums.index(b[0]) for b in bls], device="cuda")
+            a2 = torch.tensor([nums.index(b[1]) for b in bls], device="cuda")
+            if polarized:  # out[f, t, x, y, k]: y is the first antenna's feed
+                m = (G[a2].permute(2, 1, 0)[:, :, None, :] * G[a1].conj().permute(2, 1, 0)[:, None, :, :])[:, None]
+            else:
+                m = (G[a1].conj() * G[a2]).T[:, None]
+            data = m * U[..., torch.from_numpy(group).cuda().long()]
+            data += 0.05 * torch.randn(data.shape, dtype=data.dtype, device="cuda", generator=gen)
+            state.update(data=data.to(cdt).contiguous(), w=torch.ones(data.shape, dtype=rdt, device="cuda"))
+            del data, m, U
+            torch.cuda.synchronize()
+        return state
+
+    def first():
+        s = resident()
+        return fv.redundant_firstcal(s["data"], ants, freqs, reds=reds, weights=s["w"], polarized=polarized, precision=p,
+                                     max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    def solve():
+        s = resident()
+        if "gains" not in s:
+            s["gains"] = first()[0]
+        return fv.redundant_gain_solve(s["data"], ants, reds=reds, gains=s["gains"], weights=s["w"], polarized=polarized,
+                                       precision=p, max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    head = {"config": a.config, "precision": p, "polarized": polarized, "iterations": GAIN_SOLVE_ITERATIONS, "ngroups": len(reds),
+            "npairs": len(bls) - len(reds)}
+    return head, {"firstcal": first, "solve": solve}
+
+
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
 #          ratios {key: (pass, pass it is divided by -- or a tuple of passes, for their sum)})
 FAMILIES = {
@@ -834,6 +895,7 @@ FAMILIES = {
     "jones_solve": (jones_solve, "C3", 8, (), "runs", {
         "solve_over_forward": ("solve", "forward"), "chi2_steps_over_solve": ("jones_chi2_steps", "solve")}),
     "redundant_solve": (redundant_solve, "C3", 8, (), "runs", {"solve_over_gain_solve": ("solve", "gain_solve")}),
+    "firstcal": (firstcal, "C3", 8, (), "runs", {"firstcal_over_solve": ("firstcal", "solve")}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
              "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False, "jones": False,
