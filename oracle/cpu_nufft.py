@@ -115,10 +115,13 @@ def _geom(X, S, sigma, w):
     return n1, n2, h
 
 
-def nufft_type3(coords, c, targets, eps=1e-9, sigma=2.0, isign=+1, workers=-1, use_c_kernels=True):
+def nufft_type3(coords, c, targets, eps=1e-9, sigma=2.0, isign=+1, workers=-1, use_c_kernels=True, fft=None):
     """f[t,k] ~= sum_j c[t,j] exp(isign i s_k.x_j) to relative accuracy ~eps.
 
     coords / targets: lists of d (2 or 3) 1-D arrays; c: (M,) or (ntrans, M).
+    fft: ``fft(grid, axes) -> grid`` replaces the transform stage, the unnormalised inverse-sign FFT of the deconvolved
+    fine grid ``[t][(z)][y][x]`` over ``axes`` (default: ``scipy.fft.ifftn`` in fp64) -- tests pass an extended-precision
+    FFT, or one with a fault in it; every other stage stays as it is.
     """
     c = np.asarray(c)
     squeeze = c.ndim == 1
@@ -189,7 +192,10 @@ def nufft_type3(coords, c, targets, eps=1e-9, sigma=2.0, isign=+1, workers=-1, u
 
     # unnormalised inverse-sign FFT, in place
     axes = tuple(range(1, d + 1))
-    grid = sfft.ifftn(grid, axes=axes, norm="forward", workers=workers, overwrite_x=True)
+    if fft is None:
+        grid = sfft.ifftn(grid, axes=axes, norm="forward", workers=workers, overwrite_x=True)
+    else:
+        grid = np.asarray(fft(grid, axes), dtype=complex)
 
     # interpolate at eta = theta n2 / (2 pi) + n2/2, theta = h s'
     j0, kq, dec = [], [], np.ones(N)

@@ -105,6 +105,24 @@ def phase_term(case, precision=None):
     return (2 * d - 1) * u * max_phase(case) * row_norms(case["c"])[0]
 
 
+def fft_term(case, eps, sigma, precision=None):
+    """Term 2 of ``floor`` as an absolute error per (t, k), shape (ntrans, N): ``u (sum_d log2 n2_d) A_k ||c_t||_2``, the
+    rounding of the FFT stage alone as it reaches target k (derived under ``floor``).  tests/fft_stage_refs.py holds the
+    difference of two realisations of the FFT to a multiple of this."""
+    u = unit_roundoff(case["precision"] if precision is None else precision)
+    l2 = row_norms(case["c"])[1]
+    w, beta = cpu_nufft.es_params(eps, sigma)
+    hat0 = float(cpu_nufft.es_hat(np.zeros(1), w, beta)[0])
+    amp, stages = np.ones(case["targets"][0].size), 0.0
+    for x, s in zip(case["coords"], case["targets"]):
+        x, s = np.asarray(x, float), np.asarray(s, float)
+        xc, sc = 0.5 * (x.min() + x.max()), 0.5 * (s.min() + s.max())
+        _, n2, h = cpu_nufft._geom(np.abs(x - xc).max(), np.abs(s - sc).max(), sigma, w)
+        amp *= hat0 / cpu_nufft.es_hat(h * (s - sc), w, beta)
+        stages += np.log2(n2)
+    return u * stages * amp[None, :] * l2[:, None]
+
+
 def floor(case, eps, sigma, precision=None):
     """Per (t, k), in units of ``eps ||c_t||_2``: the rounding error that a correct transform working in ``precision``
     (unit roundoff u = 2^-53 or 2^-24) cannot avoid.  Two terms, both derived:
@@ -115,12 +133,12 @@ def floor(case, eps, sigma, precision=None):
        the pre- and post-phases carry them).  ``|d/dphase exp(i phase)| = 1``, so the term of source j moves by at most
        that times ``|c_tj|``; summed over the sources by the triangle inequality: ``(2d - 1) u Phi ||c_t||_1``.
 
-    2. The FFT.  A transform of length n done in log2 n radix-2 stages leaves a relative l2 error of ``u log2 n`` per
-       dimension (each stage rounds every entry once), i.e. ``u sum_d log2 n2_d`` of the grid's norm per entry on the
-       average; the spread grid's Fourier content is ``||c_t||_2`` per mode up to the kernel's normalisation, which the
-       final division by the kernel's transform undoes at the centre of the band and OVER-undoes away from it: a target at
-       ``s'`` (centred) is divided by ``psi_hat(h_d s'_d)`` per dimension where the signal it carries was only multiplied
-       by that much, but the FFT's rounding noise was not.  So the noise reaches the output multiplied by
+    2. The FFT (``fft_term``).  A transform of length n done in log2 n radix-2 stages leaves a relative l2 error of
+       ``u log2 n`` per dimension (each stage rounds every entry once), i.e. ``u sum_d log2 n2_d`` of the grid's norm per
+       entry on the average; the spread grid's Fourier content is ``||c_t||_2`` per mode up to the kernel's normalisation,
+       which the final division by the kernel's transform undoes at the centre of the band and OVER-undoes away from it: a
+       target at ``s'`` (centred) is divided by ``psi_hat(h_d s'_d)`` per dimension where the signal it carries was only
+       multiplied by that much, but the FFT's rounding noise was not.  So the noise reaches the output multiplied by
        ``A_k = prod_d psi_hat(0) / psi_hat(h_d s'_dk)``: ``u (sum_d log2 n2_d) A_k ||c_t||_2``.  ``A_k`` is 1 at the
        centre of the target box and largest in its corners (sigma = 2: ~e^{0.14 w} per dimension; sigma = 1.25:
        ~e^{w/2}), which is the "amplified rounding at band-edge targets" of ``fv_eskernel.h``.
@@ -128,20 +146,9 @@ def floor(case, eps, sigma, precision=None):
     Width, shape and grid come from the port's ``es_params`` / ``_geom``; where long double is no wider than double,
     term 1 is counted twice (the reference's own phases)."""
     precision = case["precision"] if precision is None else precision
-    u = unit_roundoff(precision)
-    l1, l2 = row_norms(case["c"])
+    l2 = row_norms(case["c"])[1]
     t1 = phase_term(case, precision) * (1 if EXTENDED else 2)
-    w, beta = cpu_nufft.es_params(eps, sigma)
-    hat0 = float(cpu_nufft.es_hat(np.zeros(1), w, beta)[0])
-    amp, stages = np.ones(case["targets"][0].size), 0.0
-    for x, s in zip(case["coords"], case["targets"]):
-        x, s = np.asarray(x, float), np.asarray(s, float)
-        xc, sc = 0.5 * (x.min() + x.max()), 0.5 * (s.min() + s.max())
-        _, n2, h = cpu_nufft._geom(np.abs(x - xc).max(), np.abs(s - sc).max(), sigma, w)
-        amp *= hat0 / cpu_nufft.es_hat(h * (s - sc), w, beta)
-        stages += np.log2(n2)
-    t2 = u * stages * amp[None, :] * l2[:, None]
-    return (t1[:, None] + t2) / (eps * l2[:, None])
+    return (t1[:, None] + fft_term(case, eps, sigma, precision)) / (eps * l2[:, None])
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -260,8 +267,10 @@ SENSITIVITY = (("2d_plain", 2.0, 1e-6), ("2d_plain", 1.25, 1e-6), ("3d_plain", 2
 def case(name):
     """The seeded problem ``name`` (read-only arrays, built once): ``coords``, ``targets`` (lists of d arrays), ``c``
     (ntrans, M), ``kind`` per target (0 interior, 1 corner, 2 edge midpoint or centre), ``precision``, ``plain`` (the
-    yardstick case of its family)."""
-    return dict(_make(**_RECIPES[name]), name=name)
+    yardstick case of its family).  A recipe's ``make`` names another builder than ``_make`` (tests/fft_stage_refs.py
+    registers its dense cases here, so that ``exact`` / ``bound`` / ``check`` serve them unchanged)."""
+    recipe = dict(_RECIPES[name])
+    return dict(recipe.pop("make", _make)(**recipe), name=name)
 
 
 def eps_list(name, sigma):
