@@ -3290,11 +3290,14 @@ class Nufft3 {
     // Slices of the rows for a launch of nwg ranges x nft (frequency, transform) planes.  Slices are whole tiles.  A
     // workgroup's time goes with its tiles (plus about one tile of set-up and of its first, uncovered request), and the
     // launch runs in rounds of the resident slots, whose workgroups do not end together (half a workgroup's time more,
-    // on average): the count with the least rounds x (tiles + 1) + (tiles + 1) / 2 is taken, the smaller count on a
-    // tie.  FFTVIS_HIP_YD_SLICES=n (read per run) forces n, clamped to what the rows allow.  Serves the buffer's size
-    // and the launch alike.
+    // on average): rounds x (tiles + 1) + (tiles + 1) / 2.  The gather then adds the slices, so it pays for each of them
+    // what its nft x npts partial sums cost to read: measured on C3 (MEASUREMENTS, "Walk slots", the slice sweep) at 23 ps
+    // per value and slice, where a unit of the estimate below -- half a tile of one round -- is 1.65 us, so 72 000 values
+    // per unit.  The count with the least sum is taken, the smaller count on a tie.  FFTVIS_HIP_YD_SLICES=n (read per
+    // run) forces n, clamped to what the rows allow.  Serves the buffer's size and the launch alike.
     static constexpr int YD_MAX_SLICES = 32;
-    void yd_slices(int na_y, int nwg, int nft, int &rps, int &nslices) {
+    static constexpr int64_t YD_GATHER_VALUES_PER_UNIT = 72000;
+    void yd_slices(int na_y, int nwg, int nft, int64_t npts, int &rps, int &nslices) {
         const int tiles = (int)cdiv(na_y, YD_RT);
         const char *e = std::getenv("FFTVIS_HIP_YD_SLICES");
         int want = e ? std::atoi(e) : 0;
@@ -3303,7 +3306,8 @@ class Nufft3 {
             int64_t best = 0;
             for (int n = 1; n <= std::min(tiles, YD_MAX_SLICES); ++n) {
                 const int tps = (int)cdiv(tiles, n), ns = (int)cdiv(tiles, tps);
-                const int64_t cost = (2 * cdiv(base * ns, slots) + 1) * (tps + 1);  // twice the estimate
+                const int64_t cost = (2 * cdiv(base * ns, slots) + 1) * (tps + 1)  // twice the estimate
+                                     + (int64_t)ns * std::max(1, nft) * std::max<int64_t>(npts, 0) / YD_GATHER_VALUES_PER_UNIT;
                 if (!want || cost < best) {
                     best = cost;
                     want = n;
@@ -3316,7 +3320,7 @@ class Nufft3 {
     }
     size_t yd_vals_bytes(int na_y, int nwg, int nfg, int tg, int64_t npts) {
         int rps, ns;
-        yd_slices(na_y, nwg, nfg * tg, rps, ns);
+        yd_slices(na_y, nwg, nfg * tg, npts, rps, ns);
         return sizeof(cplx<double>) * (size_t)ns * nfg * tg * (size_t)npts;
     }
     const T *spread_dec_y() {  // the y table the spread applies: the inner deconvolution, or ones under direct y sums
@@ -4218,7 +4222,7 @@ void Nufft3<T>::ydirect_sum(int ntrans, const cplx<T> *B) {
         a.row_stride = blk ? (1 << blk) : b_pitch();
         a.tg = tg;
         FV_REQUIRE(a.blk >= 2 && a.blk <= 4 && a.plane < ((int64_t)1 << 31), "direct y sums: blocks of 4 to 16 elements, 32-bit cell offsets");
-        yd_slices(y.na, a.nwg, ntrans, a.rps, a.nslices);
+        yd_slices(y.na, a.nwg, ntrans, a.npts, a.rps, a.nslices);
         const size_t need = sizeof(cplx<double>) * (size_t)a.nslices * ntrans * (size_t)a.npts;
         if (yd_vals.cap < need) {  // (the caller reserves it before the run: never in the middle of one)
             FV_HIP(hipStreamSynchronize(stream));

@@ -2840,6 +2840,9 @@ class Sim : public SimBase {
     // first u fixes its footprint (origin and x-weights per frequency, placed as k_interp places them); its columns
     // are located through the column plan's table when one is armed, else through out_pos.  Contiguous groups form the
     // work ranges of k_ydirect: at most YD_NG groups, 1024 points and as many distinct column blocks as its LDS tile holds.
+    // Inside a range every point is matched with the point of its group whose v is its negative (within the same
+    // tolerance; each point in at most one pair) and the kernel walks slots, a pair or a single: FFTVIS_HIP_YD_PAIRS=0
+    // (read per run) gives every point its own.  Points, map, statistics and the rule below do not know about slots.
     // Taken (use) when the points' (point, row) pairs are at most ydirect_gate() times the butterflies of the y-pass they
     // replace, columns x n2_y / 2 x log2 n2_y, on grids of the column plan's size class; FFTVIS_HIP_YDIRECT=1 takes it
     // wherever the tables can be built, 0 never.  Host arithmetic, once per (targets, group geometry); kept for later runs.
@@ -2847,13 +2850,13 @@ class Sim : public SimBase {
         int64_t serial;
         int pair, fa, fb;
         const ColPlan *cp;
-        int herm, blk, xp, w;
+        int herm, blk, xp, w, pairing;
         int xn2, xno, xsP, xcnt, yna, yn2;
         double xh, xbtc, yh, ybtc;
         bool built = false, use = false;  // use: by the geometric rule (the switch is read per run)
         YdArgs a{};
         double cells = 0;  // cells of B per transform the sums read (mean over the frequencies)
-        DevBuf wg, blkcnt, blkid, cref, xw, ptv, ptg, map;
+        DevBuf wg, blkcnt, blkid, cref, xw, slv, slg, slp, map;
     };
     std::vector<std::unique_ptr<YPlan>> y_plans;
     std::vector<YPlan *> y_plan_of;  // [group * pairs + pair] of the current run (class 0)
@@ -2862,13 +2865,15 @@ class Sim : public SimBase {
         const DimGeom &x = n0->geo.d[0], &y = n0->geo.d[1];
         const int w = n0->ker.w, blkB = n0->b_block_log_public(), blk = blkB ? blkB : 2;
         const int xp = (int)n0->b_pitch_with(cp && cp->use ? cp->ncc : 0);
+        const char *epair = std::getenv("FFTVIS_HIP_YD_PAIRS");  // read per run: 0 gives every point a slot of its own
+        const int pairing = epair && std::atoi(epair) == 0 ? 0 : 1;
         for (auto &c : y_plans)
             if (c->serial == targets_serial && c->pair == pi && c->fa == fa && c->fb == fb && c->cp == cp && c->herm == pr.herm &&
-                c->blk == (blkB ? blkB : -2) && c->xp == xp && c->w == w && c->xn2 == x.n2 && c->xno == x.no && c->xsP == x.sP() &&
+                c->blk == (blkB ? blkB : -2) && c->xp == xp && c->w == w && c->pairing == pairing && c->xn2 == x.n2 && c->xno == x.no && c->xsP == x.sP() &&
                 c->xcnt == x.cnt() && c->yna == y.na && c->yn2 == y.n2 && c->xh == x.h && c->xbtc == x.btc && c->yh == y.h &&
                 c->ybtc == y.btc)
                 return c.get();
-        std::unique_ptr<YPlan> c(new YPlan{targets_serial, pi, fa, fb, cp, pr.herm, blkB ? blkB : -2, xp, w, x.n2, x.no, x.sP(), x.cnt(),
+        std::unique_ptr<YPlan> c(new YPlan{targets_serial, pi, fa, fb, cp, pr.herm, blkB ? blkB : -2, xp, w, pairing, x.n2, x.no, x.sP(), x.cnt(),
                                            y.na, y.n2, x.h, x.btc, y.h, y.btc});
         y_plans.push_back(std::move(c));
         YPlan *yp = y_plans.back().get();
@@ -2963,6 +2968,9 @@ class Sim : public SimBase {
             return worst;
         };
         std::vector<std::vector<int>> range_blocks;  // [range * nfg + fg]
+        std::vector<double> slv;     // walk slots (fv_ydirect.h): base v,
+        std::vector<int> slg, slp;   // group, (point at +theta, point at -theta or -1)
+        int64_t npairs = 0;
         int g0 = 0;
         while (g0 < G) {
             for (auto &v : cur) v.clear();
@@ -2973,7 +2981,32 @@ class Sim : public SimBase {
                 ++ng;
             }
             if (ng == 0) return skip("one u-group alone does not fit a workgroup");
-            wg.insert(wg.end(), {g0, ng, gstart[g0], gstart[g0 + ng] - gstart[g0]});
+            // the range's walk slots, group by group: a group's points are sorted by v, so one index walks up from the
+            // most negative and one down from the most positive; they pair when the two v cancel within the clustering
+            // tolerance, else the one further from zero stays a single.  v = 0 pairs with nothing.
+            const int s0 = (int)slv.size();
+            for (int g = g0; g < g0 + ng; ++g) {
+                auto single = [&](int p) {
+                    slv.push_back(ptv[p]);
+                    slg.push_back(g);
+                    slp.insert(slp.end(), {p, -1});
+                };
+                int lo = gstart[g], hi = gstart[g + 1] - 1;
+                while (lo <= hi) {
+                    const double sum = ptv[lo] + ptv[hi];
+                    if (pairing && lo < hi && ptv[lo] < 0.0 && ptv[hi] > 0.0 && std::fabs(sum) <= tol) {
+                        slv.push_back(ptv[hi]);
+                        slg.push_back(g);
+                        slp.insert(slp.end(), {hi--, lo++});
+                        ++npairs;
+                    } else if (pairing && lo < hi && sum > 0.0) {
+                        single(hi--);
+                    } else {
+                        single(lo++);
+                    }
+                }
+            }
+            wg.insert(wg.end(), {g0, ng, s0, (int)slv.size() - s0});
             for (int fg = 0; fg < nfg; ++fg) range_blocks.push_back(cur[fg]);
             g0 += ng;
         }
@@ -2998,8 +3031,9 @@ class Sim : public SimBase {
         upload(yp->blkid, blkid.data(), sizeof(int) * blkid.size(), 0);
         upload(yp->cref, cref.data(), sizeof(int) * cref.size(), 0);
         upload(yp->xw, xw.data(), sizeof(double) * xw.size(), 0);
-        upload(yp->ptv, ptv.data(), sizeof(double) * ptv.size(), 0);
-        upload(yp->ptg, ptg.data(), sizeof(int) * ptg.size(), 0);
+        upload(yp->slv, slv.data(), sizeof(double) * slv.size(), 0);
+        upload(yp->slg, slg.data(), sizeof(int) * slg.size(), 0);
+        upload(yp->slp, slp.data(), sizeof(int) * slp.size(), 0);
         upload(yp->map, map.data(), sizeof(int) * map.size(), 0);
         YdArgs &a = yp->a;
         a.w = w;
@@ -3017,8 +3051,9 @@ class Sim : public SimBase {
         a.blkid = yp->blkid.template as<int>();
         a.cref = yp->cref.template as<int>();
         a.xw = yp->xw.template as<double>();
-        a.ptv = yp->ptv.template as<double>();
-        a.ptg = yp->ptg.template as<int>();
+        a.slv = yp->slv.template as<double>();
+        a.slg = yp->slg.template as<int>();
+        a.slp = yp->slp.template as<int>();
         yp->cells = cells;
         yp->built = true;
         // the geometric rule: distinct columns read at the group's last frequency, whatever is stored
@@ -3031,6 +3066,9 @@ class Sim : public SimBase {
             std::fprintf(stderr, "ydirect plan pair %d channels [%d, %d): %lld items, %lld points on %d u-groups, %d work ranges, %.0f columns, "
                          "B cells read %.3g of %.3g needed, na_y %d, blocks of %d, plan %d, rule %.2f -> %s\n", pi, fa, fb, (long long)N,
                          (long long)npts, G, nwg, columns, cells, columns * y.na, y.na, BE, cp ? 1 : 0, direct / ypass, yp->use ? "taken" : "not taken");
+        if (dbg)
+            std::fprintf(stderr, "ydirect slots pair %d channels [%d, %d): %lld pairs, %lld singles, %lld walk slots for %lld points\n", pi, fa, fb,
+                         (long long)npairs, (long long)(npts - 2 * npairs), (long long)slv.size(), (long long)npts);
         return yp;
     }
 
@@ -4249,7 +4287,7 @@ class Sim : public SimBase {
                 vals_need = std::max(vals_need, n0->yd_vals_bytes(yp->a.na_y, yp->a.nwg, fb - fa, tg, yp->a.npts));
                 if (std::getenv("FFTVIS_HIP_DEBUG_YDIRECT")) {
                     int rps, ns;
-                    n0->yd_slices(yp->a.na_y, yp->a.nwg, (fb - fa) * tg, rps, ns);
+                    n0->yd_slices(yp->a.na_y, yp->a.nwg, (fb - fa) * tg, yp->a.npts, rps, ns);
                     const int wgs = yp->a.nwg * (fb - fa) * tg * ns;
                     std::fprintf(stderr, "ydirect launch pair %d channels [%d, %d): %d slices of %d rows (na_y %d), %d workgroups, %d per round\n",
                                  (int)pi, fa, fb, ns, rps, yp->a.na_y, wgs, n0->yd_slot_count());

@@ -15,9 +15,19 @@
 //   (a) moves the range's distinct column blocks of B (whole blocks: rows of a block are contiguous) from the registers
 //       they were loaded into to LDS, and at once requests the next tile's -- that request is outstanding during (b), (c),
 //   (b) contracts each group's w columns into D[group][row],
-//   (c) lets every thread carry exp(i theta row) for its <= YD_PTM points by multiplication -- re-seeded from sincos
+//   (c) lets every thread carry exp(i theta row) for its <= YD_PTM walk slots by multiplication -- re-seeded from sincos
 //       every YD_RESEED rows -- and add D's rows from LDS,
 // and at the end writes one partial sum per (row slice, transform, point); the gather adds the slices in order.
+//
+// Walk slots: a point (u, v) and its mirror image (u, -v) in the same u-group read the same column D with conjugate
+// phases.  With D = a + i b and exp(i theta (row - na_y / 2)) = c + i s, the four real sums
+//     P = sum a c,   Q = sum b s,   R = sum a s,   S = sum b c
+// give both values: (P - Q) + i (R + S) at +theta and (P + Q) + i (S - R) at -theta.  Per row that is the four FMAs and
+// the phase step one point costs, so a slot -- a pair, or a single point whose second value is not written -- is the
+// unit of the walk.  A range's slots are numbered from 0, so occupied slots fill the waves from the front and the waves
+// past them skip the walk.  (theta_v = h_y s_v - beta with beta = h_y s_c,v the same for every point: off centre, D
+// takes the factor exp(-i beta (row - na_y / 2)) as it is contracted, and theta is h_y s_v alone.  Packed runs are
+// centred: beta = 0 and D is the plain contraction.)
 // All tables are host-built per (targets, group geometry): Sim::ydirect_plan.
 #pragma once
 
@@ -28,7 +38,7 @@ namespace fv {
 constexpr int YD_THREADS = 512;
 constexpr int YD_RT = 32;       // rows per tile
 constexpr int YD_NG = 8;        // u-groups per workgroup: YD_NG * YD_RT contraction items, re and im on a thread each
-constexpr int YD_PTM = 2;       // evaluation points per thread
+constexpr int YD_PTM = 2;       // walk slots per thread
 constexpr int YD_NBMAX = 20;    // distinct column blocks per workgroup (table width)
 constexpr int YD_RAWROW = 100;  // LDS cells per tile row: blocks * (block elements + 1 of padding) <= this
 constexpr int YD_RAW = YD_RAWROW * YD_RT;
@@ -40,6 +50,7 @@ static_assert(2 * YD_NG * YD_RT == YD_THREADS, "one contraction item per pair of
 static_assert(YD_RESEED % YD_RT == 0, "seeds fall on tile starts");
 static_assert(YD_RT == 32 && YD_RT % YD_RCH == 0, "a tile row index is five bits (k_ydirect's shifts)");
 static_assert(MAX_W % YD_WCH == 0, "whole chunks of footprint cells");
+static_assert(YD_PTM <= 4 && YD_NG * YD_RT / YD_RCH <= 256, "a byte per slot holds its place in D (k_ydirect's dofs)");
 
 // distinct column blocks of 1 << blk elements a workgroup's tile holds (the range builder of Sim::ydirect_plan and the kernel)
 __host__ __device__ constexpr int yd_nbcap(int blk) {
@@ -57,17 +68,18 @@ struct YdArgs {
     int64_t plane;        // elements between two transforms of B (below 2^31: the kernel's cell offsets are 32-bit)
     int64_t npts;         // evaluation points
     double hy, btcy;
-    const int *wg;        // [nwg][4]: first group, groups, first point, points
+    const int *wg;        // [nwg][4]: first group, groups, first slot, slots
     const int *blkcnt;    // [nfg][nwg] distinct blocks
     const int *blkid;     // [nfg][nwg][YD_NBMAX]
     const int *cref;      // [nfg][ngroups][w]: (block slot << 4) | element inside the block
     const double *xw;     // [nfg][ngroups][w] x-kernel weights of the group's footprint
-    const double *ptv;    // [npts] sign-adjusted base v of every point
-    const int *ptg;       // [npts] its u-group
+    const double *slv;    // [slots] base v of the slot's phase: its +v point's (a single: its own)
+    const int *slg;       // [slots] its u-group
+    const int *slp;       // [slots][2] the point at +theta, the point at -theta or -1
 };
 
 inline size_t yd_smem_bytes() {
-    return sizeof(cplx<double>) * (size_t)(YD_RAW + YD_NG * YD_RT) + sizeof(double) * YD_NG * MAX_W +
+    return sizeof(cplx<double>) * (size_t)(YD_RAW + YD_NG * YD_RT + YD_THREADS + 1) + sizeof(double) * (YD_NG * MAX_W + YD_PTM * YD_THREADS) +
            sizeof(int) * (YD_NG * MAX_W + YD_NBMAX);
 }
 
@@ -76,8 +88,10 @@ __global__ __launch_bounds__(YD_THREADS, 4) void k_ydirect(const cplx<double> *_
     extern __shared__ __attribute__((aligned(16))) unsigned char yd_smem[];
     cplx<double> *raw = reinterpret_cast<cplx<double> *>(yd_smem);
     cplx<double> *D = raw + YD_RAW;
-    double *xw_s = reinterpret_cast<double *>(D + YD_NG * YD_RT);
-    int *cref_s = reinterpret_cast<int *>(xw_s + YD_NG * MAX_W);
+    cplx<double> *rot_s = D + YD_NG * YD_RT;  // off-centre launches: the contraction's phase factors (below)
+    double *xw_s = reinterpret_cast<double *>(rot_s + YD_THREADS + 1);
+    double *th_s = xw_s + YD_NG * MAX_W;  // the slots' phase steps: read back at every seed, so not held in registers
+    int *cref_s = reinterpret_cast<int *>(th_s + YD_PTM * YD_THREADS);
     int *bid_s = cref_s + YD_NG * MAX_W;
     const int tid = threadIdx.x, wgi = blockIdx.x, ft = blockIdx.y, fg = ft / a.tg, sl = blockIdx.z;  // ft: (frequency, transform)
     const int g0 = a.wg[4 * wgi], ng = min(a.wg[4 * wgi + 1], YD_NG), p0 = a.wg[4 * wgi + 2],
@@ -94,25 +108,39 @@ __global__ __launch_bounds__(YD_THREADS, 4) void k_ydirect(const cplx<double> *_
         cref_s[gi * MAX_W + g] = (min(c >> 4, nb - 1) * YD_RT * BEP + (c & (BE - 1))) * (int)sizeof(cplx<double>);
     }
     if (tid < nb) bid_s[tid] = a.blkid[((int64_t)fg * a.nwg + wgi) * YD_NBMAX + tid];
-    // this thread's points: phase step, slot of its group's D rows
+    // this thread's walk slots: phase step, place of its group's D rows
     const double sc = scale[fg];
-    double th[YD_PTM], dr[YD_PTM], di[YD_PTM], er[YD_PTM], ei[YD_PTM], accr[YD_PTM], acci[YD_PTM];
-    int dofs[YD_PTM];
-    bool kon[YD_PTM];  // wave-uniform: some lane of this wave owns a k-th point
+    const double beta = a.hy * (sc * a.btcy);  // the centre's share of every phase: taken out of D (below), not carried by the slots
+    if (beta != 0.0) {
+        // rot_s[tid] = exp(i beta (row - na_y / 2)) for this thread's contraction row of the slice's first tile, stepped
+        // a tile at a time by rot_s[YD_THREADS] (a slice has at most some hundred tiles: no seeds in between)
+        cplx<double> f;
+        sincos(beta * (double)(sl * a.rps + (tid >> 1) % YD_RT - a.na_y / 2), &f.im, &f.re);
+        rot_s[tid] = f;
+        if (tid == 0) {
+            sincos(beta * (double)YD_RT, &f.im, &f.re);
+            rot_s[YD_THREADS] = f;
+        }
+    }
+    double dr[YD_PTM], di[YD_PTM], er[YD_PTM], ei[YD_PTM], sp[YD_PTM], sq[YD_PTM], sr[YD_PTM], ss[YD_PTM];
+    unsigned dofs = 0;  // a byte per slot: the first of its group's D rows, in units of YD_RCH
+    bool kon[YD_PTM];  // wave-uniform: some lane of this wave owns a k-th slot
 #pragma unroll
     for (int k = 0; k < YD_PTM; ++k) {
         const int p = tid + k * YD_THREADS;
         kon[k] = k * YD_THREADS + (tid & ~63) < np;
         const int gp = p0 + (p < np ? p : 0);
-        th[k] = a.hy * (sc * a.ptv[gp] - sc * a.btcy);
-        dofs[k] = min(max(a.ptg[gp] - g0, 0), YD_NG - 1) * YD_RT;
-        sincos(th[k], &di[k], &dr[k]);
+        const double th = a.hy * (sc * a.slv[gp]);
+        th_s[p] = th;  // (read by this thread alone)
+        dofs |= (unsigned)(min(max(a.slg[gp] - g0, 0), YD_NG - 1) * (YD_RT / YD_RCH)) << (8 * k);
+        sincos(th, &di[k], &dr[k]);
         er[k] = 1.0;
         ei[k] = 0.0;
-        accr[k] = acci[k] = 0.0;
+        sp[k] = sq[k] = sr[k] = ss[k] = 0.0;
     }
     const int citem = tid >> 1, cpart = tid & 1;  // this thread's contraction item, and its half of it: re or im
-    const int cgi = citem / YD_RT, crow = citem % YD_RT;
+    // (a wave's 64 threads are the 32 rows of ONE group: its number is wave-uniform and kept in a scalar register)
+    const int cgi = __builtin_amdgcn_readfirstlane(citem / YD_RT), crow = citem % YD_RT;
     const int half = a.na_y / 2;
     const int per = YD_RT << a.blk, pshift = a.blk + 5;  // cells of a block's tile rows (YD_RT = 32)
     __syncthreads();  // the tables are in place
@@ -174,18 +202,24 @@ __global__ __launch_bounds__(YD_THREADS, 4) void k_ydirect(const cplx<double> *_
                 for (int q = 0; q < YD_WCH; ++q)
                     if (gb + q < a.w) sum += v[q] * wv[q];
             }
+            if (beta != 0.0) {  // uniform; D[row] exp(-i beta (row - na_y / 2)): the partner thread holds the other half
+                const cplx<double> f = rot_s[tid], st = rot_s[YD_THREADS];
+                const double other = __shfl_xor(sum, 1);
+                sum = cpart ? sum * f.re - other * f.im : sum * f.re + other * f.im;
+                rot_s[tid] = {f.re * st.re - f.im * st.im, f.re * st.im + f.im * st.re};  // the next tile's
+            }
             reinterpret_cast<double *>(D)[2 * (cgi * YD_RT + crow) + cpart] = sum;
         }
         __syncthreads();
         if ((r0 - rbeg) % YD_RESEED == 0) {
 #pragma unroll
             for (int k = 0; k < YD_PTM; ++k)
-                if (kon[k]) sincos(th[k] * (double)(r0 - half), &ei[k], &er[k]);
+                if (kon[k]) sincos(th_s[tid + k * YD_THREADS] * (double)(r0 - half), &ei[k], &er[k]);
         }
 #pragma unroll
         for (int k = 0; k < YD_PTM; ++k) {
             if (!kon[k]) continue;  // wave-uniform
-            const cplx<double> *d = D + dofs[k];
+            const cplx<double> *d = D + ((dofs >> (8 * k)) & 255u) * YD_RCH;
 #pragma unroll 1
             for (int rb = 0; rb < YD_RT; rb += YD_RCH) {  // YD_RCH rows of D requested at a time
                 cplx<double> v[YD_RCH];
@@ -193,8 +227,10 @@ __global__ __launch_bounds__(YD_THREADS, 4) void k_ydirect(const cplx<double> *_
                 for (int q = 0; q < YD_RCH; ++q) v[q] = d[rb + q];
 #pragma unroll
                 for (int q = 0; q < YD_RCH; ++q) {
-                    accr[k] += v[q].re * er[k] - v[q].im * ei[k];
-                    acci[k] += v[q].re * ei[k] + v[q].im * er[k];
+                    sp[k] += v[q].re * er[k];
+                    sq[k] += v[q].im * ei[k];
+                    sr[k] += v[q].re * ei[k];
+                    ss[k] += v[q].im * er[k];
                     const double e2 = er[k] * dr[k] - ei[k] * di[k];
                     ei[k] = er[k] * di[k] + ei[k] * dr[k];
                     er[k] = e2;
@@ -205,7 +241,11 @@ __global__ __launch_bounds__(YD_THREADS, 4) void k_ydirect(const cplx<double> *_
 #pragma unroll
     for (int k = 0; k < YD_PTM; ++k) {
         const int p = tid + k * YD_THREADS;
-        if (p < np) vals[((int64_t)sl * a.nfg * a.tg + ft) * a.npts + p0 + p] = {accr[k], acci[k]};
+        if (p >= np) continue;
+        cplx<double> *out = vals + ((int64_t)sl * a.nfg * a.tg + ft) * a.npts;
+        const int pp = a.slp[2 * (p0 + p)], pm = a.slp[2 * (p0 + p) + 1];
+        if (pp >= 0 && pp < a.npts) out[pp] = {sp[k] - sq[k], sr[k] + ss[k]};
+        if (pm >= 0 && pm < a.npts) out[pm] = {sp[k] + sq[k], ss[k] - sr[k]};
     }
 }
 
