@@ -21,7 +21,9 @@ direction of such matrices), and the gains themselves for a fixed model, solved 
 a resident model (``simulate_vis_gain_solve``; ``simulate_vis_jones_solve`` for the full 2 x 2 matrices), and redundant
 calibration, which needs no sky: the gains together with one visibility per redundant group (``redundant_groups``,
 ``redundant_gain_solve``, ``redundant_average``, ``fix_redundant_degeneracies``), started on data with cable delays by
-firstcal, one delay and one phase per antenna from the same redundancy (``redundant_firstcal``).
+firstcal, one delay and one phase per antenna from the same redundancy (``redundant_firstcal``), and ended by absolute
+calibration, which fits the amplitude and the phase gradient the data leave free to a model of the group visibilities
+(``redundant_abscal``).
 """
 
 __version__ = "0.1.0"
@@ -63,6 +65,7 @@ from .adjoint import (  # noqa: F401
 )
 from .redundant import (  # noqa: F401
     fix_redundant_degeneracies,
+    redundant_abscal,
     redundant_average,
     redundant_firstcal,
     redundant_gain_solve,

@@ -63,6 +63,10 @@ SYMBOLS = {
     "fv_firstcal_offsets": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                     c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_double, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_abscal_slopes": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                 c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fv_abscal_evaluate": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "fv_jones_normal_rows": (c_int, [c_int, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p]),
     "fv_jones_solve": (c_int, [c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,

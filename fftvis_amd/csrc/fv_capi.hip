@@ -754,6 +754,133 @@ static void firstcal_offsets_host(int device, int nfreqs, int ntimes, int64_t nb
                             vis_solved_out);
 }
 
+// Abscal (k_abscal_products, k_abscal_search, k_abscal_peak, k_abscal_refine, k_abscal_chi2): the groups' in-plane
+// coordinates split into x1, x2 (x2 = 0 for a line), the search's axes (the runs along 1 when n2 == 1) and its step
+// factors exp(i h_b x_b), built here in fp64.
+struct AbscalCoords {
+    DevBuf d1, d2, dstep;
+    fv::AbscalGrid ag{};
+    void set(hipStream_t s, int ngroups, const double *coords, int ndim, int n1, int n2, double h1, double h2) {
+        std::vector<double> x1((size_t)ngroups), x2((size_t)ngroups, 0.0);
+        for (int g = 0; g < ngroups; ++g) {
+            x1[g] = coords[(size_t)g * ndim];
+            if (ndim == 2) x2[g] = coords[(size_t)g * 2 + 1];
+        }
+        const bool swap = n2 == 1;
+        const double hb = swap ? h1 : h2;
+        std::vector<cplx<double>> step((size_t)ngroups);
+        for (int g = 0; g < ngroups; ++g) {
+            const double t = hb * (swap ? x1[g] : x2[g]);
+            step[g] = {std::cos(t), std::sin(t)};
+        }
+        d1.reserve(sizeof(double) * (size_t)ngroups);
+        d2.reserve(sizeof(double) * (size_t)ngroups);
+        dstep.reserve(sizeof(cplx<double>) * (size_t)ngroups);
+        // (pageable host memory: the copies have left the vectors when the calls return)
+        FV_HIP(hipMemcpyAsync(d1.p, x1.data(), sizeof(double) * (size_t)ngroups, hipMemcpyHostToDevice, s));
+        FV_HIP(hipMemcpyAsync(d2.p, x2.data(), sizeof(double) * (size_t)ngroups, hipMemcpyHostToDevice, s));
+        FV_HIP(hipMemcpyAsync(dstep.p, step.data(), sizeof(cplx<double>) * (size_t)ngroups, hipMemcpyHostToDevice, s));
+        FV_HIP(hipStreamSynchronize(s));
+        const double *a = d1.as<double>(), *b = d2.as<double>();
+        ag = {a, b, swap ? b : a, swap ? a : b, dstep.as<cplx<double>>(), ndim, n1, n2, swap ? n2 : n1, swap ? n1 : n2,
+              h1, h2, swap ? h2 : h1, hb};
+    }
+};
+template <typename T>
+static void abscal_slopes_host(int device, int nfreqs, int ntimes, int tpol, int ngroups, int per_time, const void *uvis,
+                               int uvis_on_device, const void *model, int model_on_device, const void *gweights,
+                               int gweights_on_device, const double *coords, int ndim, int n1, int n2, double h1, double h2, int refine,
+                               int *peak_out, double *slopes_out, double *amp_out, double *power_out, double *unorm_out,
+                               double *mnorm_out, int *used_out, double *chi2_ft_out) {
+    const int nfeed = tpol == 4 ? 2 : 1, nunits = per_time ? nfreqs * ntimes : nfreqs, nrows = nunits * nfeed;
+    const int64_t nft = (int64_t)nfreqs * ntimes;
+    std::fill(peak_out, peak_out + 2 * (size_t)nrows, 0);  // the neutral result
+    std::fill(slopes_out, slopes_out + 2 * (size_t)nrows, 0.0);
+    std::fill(amp_out, amp_out + nrows, 1.0);
+    std::fill(power_out, power_out + nrows, 0.0);
+    std::fill(unorm_out, unorm_out + nrows, 0.0);
+    std::fill(mnorm_out, mnorm_out + nrows, 0.0);
+    std::fill(used_out, used_out + nrows, 0);
+    std::fill(chi2_ft_out, chi2_ft_out + nft, 0.0);
+    if (nft == 0 || ngroups == 0) return;
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    const size_t n = (size_t)nft * (size_t)tpol * (size_t)ngroups, nrg = (size_t)nrows * (size_t)ngroups;
+    DevBuf su, sm, sw, dc, dng, dpg, dcnt, dbad, dtv, dti, dpi, dpeak, dsl, damp, dpow, dun, dmn, dused, drows;
+    const cplx<double> *du = uvis_on_device ? static_cast<const cplx<double> *>(uvis) : to_device<cplx<double>>(sg.s, su, uvis, n);
+    const cplx<T> *dm = model_on_device ? static_cast<const cplx<T> *>(model) : to_device<cplx<T>>(sg.s, sm, model, n);
+    const double *dw = gweights_on_device ? static_cast<const double *>(gweights) : to_device<double>(sg.s, sw, gweights, n);
+    AbscalCoords co;
+    co.set(sg.s, ngroups, coords, ndim, n1, n2, h1, h2);
+    const size_t ntiles = (size_t)abscal_tiles(co.ag);
+    dc.reserve(sizeof(cplx<double>) * nrg);
+    dng.reserve(sizeof(double) * nrg);
+    dpg.reserve(sizeof(double) * nrg);
+    dcnt.reserve(sizeof(int) * nrg);
+    dbad.reserve(16);
+    dtv.reserve(sizeof(double) * (size_t)nrows * ntiles);
+    dti.reserve(sizeof(int) * (size_t)nrows * ntiles);
+    dpi.reserve(sizeof(int) * (size_t)nrows);
+    dpeak.reserve(sizeof(int) * 2 * (size_t)nrows);
+    dsl.reserve(sizeof(double) * 2 * (size_t)nrows);
+    for (DevBuf *b : {&damp, &dpow, &dun, &dmn}) b->reserve(sizeof(double) * (size_t)nrows);
+    dused.reserve(sizeof(int) * (size_t)nrows);
+    int hbad[3] = {0, 0, 0};
+    FV_HIP(hipMemsetAsync(dbad.p, 0, sizeof(hbad), sg.s));
+    launch_abscal_fit<T>(sg.s, du, dm, dw, co.ag, nunits, ntimes, tpol, ngroups, per_time, refine, dc.as<cplx<double>>(), dng.as<double>(),
+                         dpg.as<double>(), dcnt.as<int>(), dbad.as<int>(), dtv.as<double>(), dti.as<int>(), dpi.as<int>(), dpeak.as<int>(),
+                         dsl.as<double>(), damp.as<double>(), dpow.as<double>(), dun.as<double>(), dmn.as<double>(), dused.as<int>());
+    const int nblk = (int)cdiv((int64_t)nfeed * ngroups, 256);
+    drows.reserve(sizeof(double) * (size_t)nft * ((size_t)nblk + 1));
+    double *partials = drows.as<double>(), *sums = partials + (size_t)nft * nblk;
+    hipLaunchKernelGGL(k_abscal_chi2<T>, dim3((unsigned)nblk, (unsigned)std::min<int64_t>(nft, 65535)), dim3(256), 0, sg.s, du, dm, dw,
+                       co.ag.x1, co.ag.x2, (const double *)damp.as<double>(), (const double *)dsl.as<double>(), nft, ntimes, tpol, ngroups,
+                       per_time, partials);
+    hipLaunchKernelGGL(k_chi2_rows_reduce, dim3((unsigned)cdiv(nft, 256)), dim3(256), 0, sg.s, (const double *)partials, nft, nblk, sums);
+    std::vector<int> hpeak(2 * (size_t)nrows), hused((size_t)nrows);
+    std::vector<double> hsl(2 * (size_t)nrows), hamp((size_t)nrows), hpow((size_t)nrows), hun((size_t)nrows), hmn((size_t)nrows),
+        hchi2((size_t)nft);
+    FV_HIP(hipMemcpyAsync(hbad, dbad.p, sizeof(hbad), hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hpeak.data(), dpeak.p, sizeof(int) * 2 * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hsl.data(), dsl.p, sizeof(double) * 2 * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hamp.data(), damp.p, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hpow.data(), dpow.p, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hun.data(), dun.p, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hmn.data(), dmn.p, sizeof(double) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hused.data(), dused.p, sizeof(int) * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipMemcpyAsync(hchi2.data(), sums, sizeof(double) * (size_t)nft, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+    throw_if_bad_solve_input(hbad);  // (before any output is written: a failed call leaves the neutral result)
+    std::copy(hpeak.begin(), hpeak.end(), peak_out);
+    std::copy(hsl.begin(), hsl.end(), slopes_out);
+    std::copy(hamp.begin(), hamp.end(), amp_out);
+    std::copy(hpow.begin(), hpow.end(), power_out);
+    std::copy(hun.begin(), hun.end(), unorm_out);
+    std::copy(hmn.begin(), hmn.end(), mnorm_out);
+    std::copy(hused.begin(), hused.end(), used_out);
+    std::copy(hchi2.begin(), hchi2.end(), chi2_ft_out);
+}
+static void abscal_evaluate_host(int device, int nrows, int ngroups, const void *c, const double *coords, int ndim, const double *slopes,
+                                 double *out) {
+    std::fill(out, out + 6 * (size_t)nrows, 0.0);
+    if (nrows == 0 || ngroups == 0) return;
+    FV_HIP(hipSetDevice(device));
+    StreamGuard sg;
+    DevBuf dc, dsl, dout;
+    AbscalCoords co;
+    co.set(sg.s, ngroups, coords, ndim, 1, 1, 1.0, 1.0);
+    const cplx<double> *pc = to_device<cplx<double>>(sg.s, dc, c, (size_t)nrows * (size_t)ngroups);
+    const double *ps = to_device<double>(sg.s, dsl, slopes, 2 * (size_t)nrows);
+    dout.reserve(sizeof(double) * 6 * (size_t)nrows);
+    const int in_lds = abscal_in_lds(ngroups);
+    hipLaunchKernelGGL(k_abscal_evaluate, dim3((unsigned)cdiv(nrows, 4)), dim3(256), in_lds ? sizeof(double) * 10 * (size_t)ngroups : 0, sg.s,
+                       pc, co.ag.x1, co.ag.x2, ps, nrows, ngroups, in_lds, dout.as<double>());
+    FV_HIP(hipMemcpyAsync(out, dout.p, sizeof(double) * 6 * (size_t)nrows, hipMemcpyDeviceToHost, sg.s));
+    FV_HIP(hipStreamSynchronize(sg.s));
+    FV_HIP(hipGetLastError());
+}
+
 template <typename T>
 static void jones_normal_rows_host(int device, int64_t nrows, int64_t nbls, int nant, const int *ant1, const int *ant2,
                                    const void *jones, const void *vis, const void *data, const void *weights, double *A_out,
@@ -1119,6 +1246,50 @@ int fv_firstcal_offsets(int device, int precision, int nfreqs, int ntimes, int64
         firstcal_offsets_host<decltype(real)>(device, nfreqs, ntimes, nbls, tpol, nant, ant1, ant2, ngroups, group, slopes, data,
                                               data_on_device, weights, weights_on_device, offsets, uvis_out, max_iter, tol, niter_out,
                                               change_out, chi2_ft_out, solved_out, vis_solved_out);
+    });
+}
+
+int fv_abscal_slopes(int device, int precision, int nfreqs, int ntimes, int tpol, int ngroups, int per_time, const void *uvis,
+                     int uvis_on_device, const void *model, int model_on_device, const void *gweights, int gweights_on_device,
+                     const double *coords, int ndim, int n1, int n2, double h1, double h2, int refine, int *peak_out,
+                     double *slopes_out, double *amp_out, double *power_out, double *unorm_out, double *mnorm_out, int *used_out,
+                     double *chi2_ft_out) {
+    return guarded(precision, [&](auto real) {  // (everything is checked before anything runs)
+        FV_REQUIRE(tpol == 1 || tpol == 4, "fv_abscal_slopes: tpol must be 1 or 4");
+        FV_REQUIRE(nfreqs >= 0 && ntimes >= 0 && (int64_t)nfreqs * ntimes < ((int64_t)1 << 29) && ngroups >= 0 && ngroups < (1 << 29),
+                   "fv_abscal_slopes: negative shape");
+        FV_REQUIRE(per_time == 0 || per_time == 1, "fv_abscal_slopes: per_time must be 0 or 1");
+        FV_REQUIRE(ndim == 1 || ndim == 2, "fv_abscal_slopes: ndim must be 1 or 2 (a line or a planar array)");
+        FV_REQUIRE(n1 >= 1 && n2 >= 1 && (n1 & 1) && (n2 & 1), "fv_abscal_slopes: n1 and n2 must be positive and odd");
+        FV_REQUIRE((int64_t)n1 * n2 <= ((int64_t)1 << 22), "fv_abscal_slopes: the grid n1 n2 must not exceed 2^22 points");
+        FV_REQUIRE(ndim == 2 || n2 == 1, "fv_abscal_slopes: n2 must be 1 for ndim 1");
+        FV_REQUIRE(h1 > 0.0 && std::isfinite(h1) && (ndim == 1 || (h2 > 0.0 && std::isfinite(h2))),
+                   "fv_abscal_slopes: the grid steps must be positive and finite");
+        FV_REQUIRE(refine >= 0 && refine <= 32, "fv_abscal_slopes: refine must lie in 0 .. 32");
+        FV_REQUIRE(((uvis_on_device | model_on_device | gweights_on_device) & ~1) == 0, "fv_abscal_slopes: the on_device flags must be 0 or 1");
+        const bool none = nfreqs == 0 || ntimes == 0;
+        FV_REQUIRE(none || (peak_out && slopes_out && amp_out && power_out && unorm_out && mnorm_out && used_out && chi2_ft_out),
+                   "fv_abscal_slopes: null peak_out, slopes_out, amp_out, power_out, unorm_out, mnorm_out, used_out or chi2_ft_out");
+        FV_REQUIRE(none || ngroups == 0 || (uvis && model && coords), "fv_abscal_slopes: null uvis, model or coords");
+        for (int64_t i = 0; !none && i < (int64_t)ngroups * ndim; ++i)
+            FV_REQUIRE(std::isfinite(coords[i]), "fv_abscal_slopes: coords must be finite");
+        if (none) return;
+        abscal_slopes_host<decltype(real)>(device, nfreqs, ntimes, tpol, ngroups, per_time, uvis, uvis_on_device, model, model_on_device,
+                                           gweights, gweights_on_device, coords, ndim, n1, n2, h1, h2, refine, peak_out, slopes_out,
+                                           amp_out, power_out, unorm_out, mnorm_out, used_out, chi2_ft_out);
+    });
+}
+
+int fv_abscal_evaluate(int device, int nrows, int ngroups, const void *c, const double *coords, int ndim, const double *slopes,
+                       double *out) {
+    return guarded([&] {  // (everything is checked before anything runs)
+        FV_REQUIRE(nrows >= 0 && nrows < (1 << 29) && ngroups >= 0 && ngroups < (1 << 29), "fv_abscal_evaluate: negative shape");
+        FV_REQUIRE(ndim == 1 || ndim == 2, "fv_abscal_evaluate: ndim must be 1 or 2 (a line or a planar array)");
+        FV_REQUIRE(nrows == 0 || (slopes && out), "fv_abscal_evaluate: null slopes or out");
+        FV_REQUIRE(nrows == 0 || ngroups == 0 || (c && coords), "fv_abscal_evaluate: null c or coords");
+        for (int64_t i = 0; nrows > 0 && i < (int64_t)ngroups * ndim; ++i)
+            FV_REQUIRE(std::isfinite(coords[i]), "fv_abscal_evaluate: coords must be finite");
+        abscal_evaluate_host(device, nrows, ngroups, c, coords, ndim, slopes, out);
     });
 }
 

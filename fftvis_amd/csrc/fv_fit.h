@@ -7,6 +7,7 @@
 #include "fv_common.h"
 
 #include <algorithm>
+#include <climits>
 #include <initializer_list>
 #include <type_traits>
 
@@ -1303,6 +1304,334 @@ inline void launch_firstcal_delays(hipStream_t on, const cplx<T> *data, const T 
     const int in_lds = lds <= GAIN_LDS_BYTES;
     hipLaunchKernelGGL(k_firstcal_delay, dim3((unsigned)cdiv(nrows, 4)), dim3(256), in_lds ? lds : 0, on, (const cplx<double> *)z, tw,
                        nrows, nfreqs, nd, in_lds, peak_bin, delay_bins, power, total, used);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Abscal (fv_abscal_slopes, fv_abscal_evaluate; DESIGN.md "Abscal"): what the redundant solve above leaves free, fitted to a
+// model of the group visibilities.  A row is a (solve unit, feed): a unit is a frequency (per_time = 0, its rows the
+// frequency's ntimes times) or a (frequency, time); feed p reads the parallel hand pol = 3 p of the (nfreqs, ntimes, tpol,
+// ngroups) blocks U (complex128), M (T) and W (float64, null: ones).  X: the groups' baselines in in-plane coordinates,
+// x1 and x2 of ngroups doubles each (x2 = 0 for a line, ndim = 1).  Per row the fit maximises over the slope Phi
+//     Re S(Phi),   S = sum_g c_g exp(i Phi . X_g),   c_g = sum_t W conj(U) M,   and then   eta = Re S / N,  N = sum W |U|^2.
+// k_abscal_products: one thread per (row, group), the group fastest so that the loads coalesce; the unit's times ascending,
+// every term formed and added in fp64: c_g, N_g = sum_t W |U|^2, P_g = sum_t W |M|^2 and the count of used samples.  A sample
+// is used when W > 0 and X_g != 0 (an auto-correlation's own group is never used); a flagged datum is not read.  bad[0]
+// counts weights that are negative or not finite, bad[1] values of U and bad[2] values of M that are not finite at a used
+// sample (int atomics).  k_abscal_search: Re S on the grid Phi = (j_1 h_1, j_2 h_2), j_i = i_i - (n_i - 1) / 2, i_i = 0 ..
+// n_i - 1 (n_i odd), and its argmax.  The kernel's axes are (a, b) with the runs along b: (1, 2), or (2, 1) for a line,
+// where n_2 = 1 -- the flat index i_a n_b + i_b is i_1 n_2 + i_2 either way.  A thread owns one run of ABSCAL_RUN = 8
+// consecutive i_b at one i_a; a block's 256 runs are a tile, the grid is (tiles, rows).  The groups pass through LDS in
+// chunks of ABSCAL_CHUNK = 512 -- c, x_a, x_b and the step factor exp(i h_b x_b) (built on the host in fp64), six doubles
+// a group, 24 576 bytes <= GAIN_LDS_BYTES -- and every thread reads the same group at a time (a broadcast: no bank
+// conflict).  Per (group, run): the phase Phi . X in fp64 and one sincos at the run's first point, w = c exp(i Phi . X), then
+// ABSCAL_RUN - 1 rotations w <- w step; every thread adds the groups in ascending order for its own slopes.  The argmax:
+// a thread keeps the first maximum it meets, every reduction (an __shfl_xor tree, the block's waves through LDS, and
+// k_abscal_peak, one wave per row over the tiles' winners) takes the larger value and on a tie the lower flat index.
+// k_abscal_refine: one wave per row.  abscal_six_sums -- f = Re S, its gradient g_i = -sum X_i Im(c e^{i Phi . X}) and its
+// Hessian H_ij = -sum X_i X_j Re(c e^{i Phi . X}) at the continuous Phi, sincos in fp64, lane l adding the groups l, l + 64,
+// ..., an __shfl_xor tree (every lane ends with the same bits).  `refine` rounds of Newton from the grid's peak: where H is
+// negative definite the step -H^-1 g, else g / max |eig H| (0 where H = 0), either clipped to +-h_i per dimension; one more
+// evaluation at the result gives Re S.  A row is used when N > 0, at least ndim + 1 groups have a used sample and Re S > 0;
+// one that is not reports eta = 1, Phi = 0, the peak (0, 0) and Re S = 0.  X and the four rows' c are staged in LDS when
+// they fit GAIN_LDS_BYTES (80 ngroups bytes: ngroups <= 409), which is why a wave without a row stays for the barrier.
+// k_abscal_chi2: sum W |eta e^{-i Phi . X} U - M|^2 per (frequency, time) over the feeds and the used samples, formed
+// explicitly at the returned parameters (the closed form P - (Re S)^2 / N cancels): one thread per (feed, group), the
+// block's partial by row_tail, the row's by k_chi2_rows_reduce.  No floating-point atomics: the same input gives the same
+// bits.
+constexpr int ABSCAL_RUN = 8;
+constexpr int ABSCAL_CHUNK = 512;
+static_assert(sizeof(double) * 6 * ABSCAL_CHUNK <= GAIN_LDS_BYTES, "a chunk of the search fits the staging budget");
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_abscal_products(const cplx<double> *__restrict__ uvis, const cplx<T> *__restrict__ model, const double *__restrict__ gw,
+                      const double *__restrict__ x1, const double *__restrict__ x2, int nunits, int ntimes, int tpol, int ngroups,
+                      int per_time, cplx<double> *__restrict__ c, double *__restrict__ ng, double *__restrict__ pg,
+                      int *__restrict__ cnt, int *__restrict__ bad) {
+    const int g = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (g >= ngroups) return;
+    const bool cross = x1[g] != 0.0 || x2[g] != 0.0;
+    const int nfeed = tpol == 4 ? 2 : 1;
+    int bad_w = 0, bad_u = 0, bad_m = 0;
+    for (int row = (int)blockIdx.y; row < nunits * nfeed; row += (int)gridDim.y) {
+        const int unit = row / nfeed, feed = row - unit * nfeed;
+        const int64_t r0 = per_time ? unit : (int64_t)unit * ntimes, r1 = per_time ? r0 + 1 : r0 + ntimes;
+        double cr = 0.0, ci = 0.0, sn = 0.0, sp = 0.0;
+        int n = 0;
+        for (int64_t r = r0; r < r1; ++r) {  // ascending time
+            const int64_t at = (r * tpol + 3 * feed) * ngroups + g;
+            const double w = gw ? gw[at] : 1.0;
+            if (!(w >= 0.0) || !isfinite(w)) ++bad_w;
+            if (!(w > 0.0) || !cross) continue;  // flagged: the data are not read
+            const cplx<double> u = uvis[at], m = {(double)model[at].re, (double)model[at].im};
+            if (!isfinite(u.re) || !isfinite(u.im)) ++bad_u;
+            if (!isfinite(m.re) || !isfinite(m.im)) ++bad_m;
+            cr += w * (u.re * m.re + u.im * m.im);
+            ci += w * (u.re * m.im - u.im * m.re);
+            sn += w * (u.re * u.re + u.im * u.im);
+            sp += w * (m.re * m.re + m.im * m.im);
+            ++n;
+        }
+        const int64_t o = (int64_t)row * ngroups + g;
+        c[o] = {cr, ci};
+        ng[o] = sn;
+        pg[o] = sp;
+        cnt[o] = n;
+    }
+    if (bad_w) atomicAdd(bad, bad_w);
+    if (bad_u) atomicAdd(bad + 1, bad_u);
+    if (bad_m) atomicAdd(bad + 2, bad_m);
+}
+// larger value, on a tie the lower flat index
+__device__ __forceinline__ void abscal_take(double &best, int &idx, double ob, int oi) {
+    if (ob > best || (ob == best && oi < idx)) {
+        best = ob;
+        idx = oi;
+    }
+}
+// c: (nrows, ngroups); xa, xb, step: (ngroups); tile_val, tile_idx: (nrows, gridDim.x)
+__global__ void __launch_bounds__(256)
+    k_abscal_search(const cplx<double> *__restrict__ c, const double *__restrict__ xa, const double *__restrict__ xb,
+                    const cplx<double> *__restrict__ step, int nrows, int ngroups, int na, int nb, double ha, double hb,
+                    double *__restrict__ tile_val, int *__restrict__ tile_idx) {
+    __shared__ double stage[6][ABSCAL_CHUNK];
+    __shared__ double wave_val[4];
+    __shared__ int wave_idx[4];
+    const int nruns_b = (nb + ABSCAL_RUN - 1) / ABSCAL_RUN;
+    const int64_t run = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool has = run < (int64_t)na * nruns_b;
+    const int ia = has ? (int)(run / nruns_b) : 0, ib0 = has ? (int)(run % nruns_b) * ABSCAL_RUN : 0;
+    const double pa = (double)(ia - (na - 1) / 2) * ha, pb = (double)(ib0 - (nb - 1) / 2) * hb;
+    for (int row = (int)blockIdx.y; row < nrows; row += (int)gridDim.y) {
+        double acc[ABSCAL_RUN];
+#pragma unroll
+        for (int j = 0; j < ABSCAL_RUN; ++j) acc[j] = 0.0;
+        for (int g0 = 0; g0 < ngroups; g0 += ABSCAL_CHUNK) {
+            const int m = min(ABSCAL_CHUNK, ngroups - g0);
+            __syncthreads();  // (the chunk before has been read)
+            for (int i = (int)threadIdx.x; i < m; i += 256) {
+                const cplx<double> cg = c[(int64_t)row * ngroups + g0 + i], sg = step[g0 + i];
+                stage[0][i] = cg.re;
+                stage[1][i] = cg.im;
+                stage[2][i] = xa[g0 + i];
+                stage[3][i] = xb[g0 + i];
+                stage[4][i] = sg.re;
+                stage[5][i] = sg.im;
+            }
+            __syncthreads();
+            for (int i = 0; has && i < m; ++i) {  // ascending group
+                double sn, cs;
+                sincos(pa * stage[2][i] + pb * stage[3][i], &sn, &cs);
+                const double cr = stage[0][i], ci = stage[1][i], sr = stage[4][i], si = stage[5][i];
+                double wr = cr * cs - ci * sn, wi = cr * sn + ci * cs;
+                acc[0] += wr;
+#pragma unroll
+                for (int j = 1; j < ABSCAL_RUN; ++j) {
+                    const double t = wr * sr - wi * si;
+                    wi = wr * si + wi * sr;
+                    wr = t;
+                    acc[j] += wr;
+                }
+            }
+        }
+        double best = -INFINITY;
+        int idx = has ? ia * nb + ib0 : INT_MAX;
+#pragma unroll
+        for (int j = 0; j < ABSCAL_RUN; ++j)
+            if (has && ib0 + j < nb && acc[j] > best) {  // the first maximum
+                best = acc[j];
+                idx = ia * nb + ib0 + j;
+            }
+        for (int off = 32; off > 0; off >>= 1) abscal_take(best, idx, __shfl_xor(best, off, 64), __shfl_xor(idx, off, 64));
+        if ((threadIdx.x & 63) == 0) {
+            wave_val[threadIdx.x >> 6] = best;
+            wave_idx[threadIdx.x >> 6] = idx;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < 4; ++w) abscal_take(best, idx, wave_val[w], wave_idx[w]);
+            tile_val[(int64_t)row * gridDim.x + blockIdx.x] = best;
+            tile_idx[(int64_t)row * gridDim.x + blockIdx.x] = idx;
+        }
+        __syncthreads();
+    }
+}
+// the row's winner among its tiles': one wave per row
+__global__ void __launch_bounds__(256)
+    k_abscal_peak(const double *__restrict__ tile_val, const int *__restrict__ tile_idx, int nrows, int ntiles, int *__restrict__ peak_idx) {
+    const int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (row >= nrows) return;  // (whole waves)
+    double best = -INFINITY;
+    int idx = INT_MAX;
+    for (int t = lane; t < ntiles; t += 64) abscal_take(best, idx, tile_val[(int64_t)row * ntiles + t], tile_idx[(int64_t)row * ntiles + t]);
+    for (int off = 32; off > 0; off >>= 1) abscal_take(best, idx, __shfl_xor(best, off, 64), __shfl_xor(idx, off, 64));
+    if (lane == 0) peak_idx[row] = idx;
+}
+// f, g_1, g_2, H_11, H_12, H_22 of Re S at (p1, p2): the wave's lanes split the groups; every lane returns the same bits
+__device__ inline void abscal_six_sums(const cplx<double> *__restrict__ c, const double *__restrict__ x1, const double *__restrict__ x2,
+                                       int ngroups, int lane, double p1, double p2, double s[6]) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) s[j] = 0.0;
+    for (int g = lane; g < ngroups; g += 64) {
+        const cplx<double> cg = c[g];
+        const double a = x1[g], b = x2[g];
+        double sn, cs;
+        sincos(p1 * a + p2 * b, &sn, &cs);
+        const double re = cg.re * cs - cg.im * sn, im = cg.re * sn + cg.im * cs;
+        s[0] += re;
+        s[1] -= a * im;
+        s[2] -= b * im;
+        s[3] -= a * a * re;
+        s[4] -= a * b * re;
+        s[5] -= b * b * re;
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+        for (int off = 32; off > 0; off >>= 1) s[j] += __shfl_xor(s[j], off, 64);
+}
+// The block's four rows as abscal_six_sums reads them: X and the rows' c staged in dynamic LDS when in_lds (5 ngroups
+// complex128), else where they lie.  Every thread of the block calls it (a barrier); row: this wave's, clamped.
+__device__ inline void abscal_stage(const cplx<double> *__restrict__ &c, const double *__restrict__ &x1, const double *__restrict__ &x2,
+                                    int64_t row, int ngroups, int in_lds) {
+    extern __shared__ __align__(16) unsigned char gain_lds[];
+    c += row * ngroups;
+    if (!in_lds) return;
+    double *l1 = reinterpret_cast<double *>(gain_lds), *l2 = l1 + ngroups;
+    cplx<double> *lc = reinterpret_cast<cplx<double> *>(l2 + ngroups) + (threadIdx.x >> 6) * ngroups;
+    for (int g = (int)threadIdx.x; g < ngroups; g += 256) {
+        l1[g] = x1[g];
+        l2[g] = x2[g];
+    }
+    for (int g = (int)(threadIdx.x & 63); g < ngroups; g += 64) lc[g] = c[g];
+    __syncthreads();
+    c = lc;
+    x1 = l1;
+    x2 = l2;
+}
+// slopes: (nrows, 2); out: (nrows, 6)
+__global__ void __launch_bounds__(256)
+    k_abscal_evaluate(const cplx<double> *__restrict__ c, const double *__restrict__ x1, const double *__restrict__ x2,
+                      const double *__restrict__ slopes, int nrows, int ngroups, int in_lds, double *__restrict__ out) {
+    const int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const bool active = row < nrows;
+    abscal_stage(c, x1, x2, active ? row : 0, ngroups, in_lds);
+    if (!active) return;  // (no barrier follows)
+    double s[6];
+    abscal_six_sums(c, x1, x2, ngroups, lane, slopes[2 * row], slopes[2 * row + 1], s);
+    if (lane < 6) out[6 * (int64_t)row + lane] = s[lane];
+}
+// peak_idx: (nrows) flat grid indices i_1 n_2 + i_2; the outputs: (nrows), peak and slopes (nrows, 2)
+__global__ void __launch_bounds__(256)
+    k_abscal_refine(const cplx<double> *__restrict__ c, const double *__restrict__ x1, const double *__restrict__ x2,
+                    const double *__restrict__ ng, const double *__restrict__ pg, const int *__restrict__ cnt,
+                    const int *__restrict__ peak_idx, int nrows, int ngroups, int ndim, int n1, int n2, double h1, double h2, int refine,
+                    int in_lds, int *__restrict__ peak, double *__restrict__ slopes, double *__restrict__ amp, double *__restrict__ power,
+                    double *__restrict__ unorm, double *__restrict__ mnorm, int *__restrict__ used) {
+    const int row = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    const bool active = row < nrows;
+    abscal_stage(c, x1, x2, active ? row : 0, ngroups, in_lds);
+    if (!active) return;  // (no barrier follows)
+    double N = 0.0, P = 0.0;
+    int groups_used = 0;
+    for (int g = lane; g < ngroups; g += 64) {
+        const int64_t o = (int64_t)row * ngroups + g;
+        N += ng[o];
+        P += pg[o];
+        groups_used += cnt[o] > 0 ? 1 : 0;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        N += __shfl_xor(N, off, 64);
+        P += __shfl_xor(P, off, 64);
+        groups_used += __shfl_xor(groups_used, off, 64);
+    }
+    const int j1 = peak_idx[row] / n2 - (n1 - 1) / 2, j2 = peak_idx[row] % n2 - (n2 - 1) / 2;
+    double p1 = (double)j1 * h1, p2 = ndim == 2 ? (double)j2 * h2 : 0.0, s[6];
+    for (int round = 0; round < refine; ++round) {
+        abscal_six_sums(c, x1, x2, ngroups, lane, p1, p2, s);
+        double d1, d2 = 0.0;
+        if (ndim == 1) {
+            d1 = s[3] < 0.0 ? -s[1] / s[3] : (s[3] > 0.0 ? s[1] / s[3] : 0.0);
+        } else {
+            const double det = s[3] * s[5] - s[4] * s[4];
+            if (s[3] < 0.0 && det > 0.0) {
+                d1 = -(s[5] * s[1] - s[4] * s[2]) / det;
+                d2 = -(s[3] * s[2] - s[4] * s[1]) / det;
+            } else {
+                const double hd = 0.5 * (s[3] - s[5]), big = fabs(0.5 * (s[3] + s[5])) + sqrt(hd * hd + s[4] * s[4]);
+                d1 = big > 0.0 ? s[1] / big : 0.0;
+                d2 = big > 0.0 ? s[2] / big : 0.0;
+            }
+        }
+        p1 += fmin(fmax(d1, -h1), h1);
+        if (ndim == 2) p2 += fmin(fmax(d2, -h2), h2);
+    }
+    abscal_six_sums(c, x1, x2, ngroups, lane, p1, p2, s);
+    if (lane == 0) {
+        const bool ok = N > 0.0 && groups_used >= ndim + 1 && s[0] > 0.0;
+        peak[2 * row] = ok ? j1 : 0;
+        peak[2 * row + 1] = ok ? j2 : 0;
+        slopes[2 * row] = ok ? p1 : 0.0;
+        slopes[2 * row + 1] = ok ? p2 : 0.0;
+        amp[row] = ok ? s[0] / N : 1.0;
+        power[row] = ok ? s[0] : 0.0;
+        unorm[row] = N;
+        mnorm[row] = P;
+        used[row] = ok ? 1 : 0;
+    }
+}
+// amp: (nunits nfeed), slopes: (nunits nfeed, 2); partials: (nfreqs ntimes, gridDim.x)
+template <typename T>
+__global__ void __launch_bounds__(256)
+    k_abscal_chi2(const cplx<double> *__restrict__ uvis, const cplx<T> *__restrict__ model, const double *__restrict__ gw,
+                  const double *__restrict__ x1, const double *__restrict__ x2, const double *__restrict__ amp,
+                  const double *__restrict__ slopes, int64_t nrows, int ntimes, int tpol, int ngroups, int per_time,
+                  double *__restrict__ partials) {
+    const int nfeed = tpol == 4 ? 2 : 1;
+    const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;  // (feed, group)
+    const int feed = e / ngroups, g = e - feed * ngroups;
+    for (int64_t row = blockIdx.y; row < nrows; row += gridDim.y) {
+        double term = 0.0;
+        if (feed < nfeed && (x1[g] != 0.0 || x2[g] != 0.0)) {
+            const int64_t at = (row * tpol + 3 * feed) * ngroups + g, ur = (per_time ? row : row / ntimes) * nfeed + feed;
+            const double w = gw ? gw[at] : 1.0;
+            if (w > 0.0) {  // else flagged: the data are not read
+                double sn, cs;
+                sincos(slopes[2 * ur] * x1[g] + slopes[2 * ur + 1] * x2[g], &sn, &cs);
+                const cplx<double> u = uvis[at];
+                const double dr = amp[ur] * (u.re * cs + u.im * sn) - (double)model[at].re;
+                const double di = amp[ur] * (u.im * cs - u.re * sn) - (double)model[at].im;
+                term = w * __builtin_fma(dr, dr, di * di);
+            }
+        }
+        row_tail(term, 0, 0, row, partials, nullptr);
+    }
+}
+// What the entry points hold on the device for the groups: x1, x2 and, for the search, its axes (a, b) and step factors
+struct AbscalGrid {
+    const double *x1, *x2, *xa, *xb;
+    const cplx<double> *step;
+    int ndim, n1, n2, na, nb;
+    double h1, h2, ha, hb;
+};
+inline int abscal_in_lds(int ngroups) { return sizeof(double) * 10 * (size_t)ngroups <= GAIN_LDS_BYTES; }
+inline int64_t abscal_tiles(const AbscalGrid &ag) { return cdiv((int64_t)ag.na * cdiv(ag.nb, ABSCAL_RUN), 256); }
+// Queues products, search, peak and refine on `on`.  All device pointers; gw may be null.  c: (nrows, ngroups), ng, pg, cnt
+// alike, tile_val, tile_idx: (nrows, abscal_tiles), peak_idx: (nrows), bad: three zeroed counters; nrows = nunits nfeed.
+template <typename T>
+inline void launch_abscal_fit(hipStream_t on, const cplx<double> *uvis, const cplx<T> *model, const double *gw, const AbscalGrid &ag,
+                              int nunits, int ntimes, int tpol, int ngroups, int per_time, int refine, cplx<double> *c, double *ng,
+                              double *pg, int *cnt, int *bad, double *tile_val, int *tile_idx, int *peak_idx, int *peak, double *slopes,
+                              double *amp, double *power, double *unorm, double *mnorm, int *used) {
+    const int nrows = nunits * (tpol == 4 ? 2 : 1), ntiles = (int)abscal_tiles(ag), in_lds = abscal_in_lds(ngroups);
+    const size_t lds = in_lds ? sizeof(double) * 10 * (size_t)ngroups : 0;
+    hipLaunchKernelGGL(k_abscal_products<T>, dim3((unsigned)cdiv(ngroups, 256), (unsigned)std::min(nrows, 65535)), dim3(256), 0, on, uvis,
+                       model, gw, ag.x1, ag.x2, nunits, ntimes, tpol, ngroups, per_time, c, ng, pg, cnt, bad);
+    hipLaunchKernelGGL(k_abscal_search, dim3((unsigned)ntiles, (unsigned)std::min(nrows, 65535)), dim3(256), 0, on, (const cplx<double> *)c,
+                       ag.xa, ag.xb, ag.step, nrows, ngroups, ag.na, ag.nb, ag.ha, ag.hb, tile_val, tile_idx);
+    hipLaunchKernelGGL(k_abscal_peak, dim3((unsigned)cdiv(nrows, 4)), dim3(256), 0, on, (const double *)tile_val, (const int *)tile_idx,
+                       nrows, ntiles, peak_idx);
+    hipLaunchKernelGGL(k_abscal_refine, dim3((unsigned)cdiv(nrows, 4)), dim3(256), lds, on, (const cplx<double> *)c, ag.x1, ag.x2,
+                       (const double *)ng, (const double *)pg, (const int *)cnt, (const int *)peak_idx, nrows, ngroups, ag.ndim, ag.n1,
+                       ag.n2, ag.h1, ag.h2, refine, in_lds, peak, slopes, amp, power, unorm, mnorm, used);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -4,8 +4,9 @@ unknown visibility per redundant group, without a sky model.
 The data model is ``V'[f, t, pol, k] = conj(g[p, a1]) g[q, a2] U[f, t, pol, group[k]]``.  ``redundant_groups`` builds the
 groups, ``redundant_firstcal`` finds the start of data with cable delays (``fv_firstcal_pair_delays``,
 ``fv_firstcal_offsets``), ``redundant_gain_solve`` alternates the two linear halves on a device block (``fv_redundant_solve``),
-``redundant_average`` is the visibility half alone (``fv_redundant_vis_rows``) and ``fix_redundant_degeneracies`` fixes
-what the data leave free.  The host layer (shapes of the gains, their start, device buffers) is the gain solve's, in
+``redundant_average`` is the visibility half alone (``fv_redundant_vis_rows``), ``redundant_abscal`` fits what the data leave
+free to a model of the group visibilities (``fv_abscal_slopes``) and ``fix_redundant_degeneracies`` brings it to a
+reference's gains.  The host layer (shapes of the gains, their start, device buffers) is the gain solve's, in
 ``adjoint``.
 """
 
@@ -161,7 +162,8 @@ def redundant_gain_solve(
       ``solved`` in the gains' shape, ``vis_solved`` in ``vis``' shape (False where a group had no used sample: its ``vis`` is
       0), ``reds`` and ``baselines`` as used.
     * The data leave four things free per solve unit and feed -- amplitude, phase and a phase gradient across the array --
-      and the result has them wherever the iteration left them: ``fix_redundant_degeneracies``.
+      and the result has them wherever the iteration left them: ``redundant_abscal`` (against a model of the group
+      visibilities) or ``fix_redundant_degeneracies`` (against reference gains).
     * Convergence (numpy prototype, unit start, ``tol=1e-10``, noiseless): hex-19, hex-37 and a 4 x 4 grid with gain errors
       of 5-20 % take 40-56 iterations; small arrays are slower (hex-7: 190-260, 3 x 3 grid: 120-190).  Polarized with
       cross-hands as strong as the parallel hands 52-54, with the cross-hands flagged 74-84; weak cross-hands that are USED
@@ -169,7 +171,7 @@ def redundant_gain_solve(
 
     Outputs follow ``data`` to its device.  Not differentiable.  A start within a phase wrap of the truth -- firstcal, for
     data whose gains carry cable delays -- is ``redundant_firstcal``'s ``gains``.  Not covered: Jones matrices, a joint sky
-    and redundant solve, near-redundancy, sharding over GPUs."""
+    and redundant solve, near-redundancy, sharding over GPUs; the degeneracies against a sky model are ``redundant_abscal``'s."""
     if int(max_iter) != max_iter or max_iter < 1:
         raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
     if not float(tol) >= 0.0:
@@ -262,7 +264,8 @@ def redundant_firstcal(
       ``vis_solved``, ``reds`` and ``baselines`` as used.
 
     Outputs follow ``data`` to its device.  Not differentiable.  Not covered: polarity flips (pi offsets of swapped feeds),
-    per-time delays, non-uniform channels, aliasing beyond ``+-1 / (2 dnu)``, Jones matrices, sharding over GPUs."""
+    per-time delays, non-uniform channels, aliasing beyond ``+-1 / (2 dnu)``, Jones matrices, sharding over GPUs; the
+    amplitude and the phase gradient the data leave free are ``redundant_abscal``'s."""
     if int(max_iter) != max_iter or max_iter < 1:
         raise ValueError(f"max_iter must be a positive integer, got {max_iter!r}")
     if not float(tol) >= 0.0:
@@ -390,6 +393,171 @@ def redundant_average(
     out_shape = run.vis_shape[:-1] + (ngroups,)
     out = _follow(data, vis=uvis.reshape(out_shape), den=den.reshape(out_shape))
     return out["vis"], out["den"]
+
+
+_ABSCAL_MAX_GRID = 1 << 22
+
+
+def _abscal_plane(ants: dict, reds):
+    """The groups' baselines ``b_g = x[a2] - x[a1]`` of ``reds[g][0]`` and the plane they span: ``(b (ngroups, 3), Vt (ndim, 3),
+    X = b Vt^T (ngroups, ndim))``.  ``ndim`` counts the singular values above 1e-9 of the largest (at least 1); 3 is a
+    ValueError."""
+    pos = {k: np.asarray(v, dtype=np.float64).reshape(-1)[:3] for k, v in ants.items()}
+    b = np.array([pos[red[0][1]] - pos[red[0][0]] for red in reds], dtype=np.float64).reshape(len(reds), 3)
+    cross = np.any(b != 0.0, axis=1)
+    vt = np.eye(3)[:1]
+    if cross.any():
+        _, s, rows = np.linalg.svd(b[cross], full_matrices=False)
+        ndim = max(1, int(np.sum(s > 1e-9 * s[0])))
+        if ndim == 3:
+            raise ValueError("the group baselines span three dimensions: redundant_abscal fits a slope on a line or in a plane "
+                             "(rank 1 or 2); rank-3 arrays are not covered")
+        vt = rows[:ndim]
+    X = np.ascontiguousarray(b @ vt.T)
+    X[~cross] = 0.0
+    return b, vt, X
+
+
+def _abscal_grid(X, b, max_slope, pad):
+    """The search grid of ``redundant_abscal``: ``(n (2,), h (2,), max_slope)``; ``n[1] == 1`` for a line."""
+    cross = np.any(b != 0.0, axis=1)
+    ndim = X.shape[1]
+    n, h = [1, 1], [1.0, 1.0]
+    if not cross.any():
+        return n, h, 0.0 if max_slope is None else float(max_slope)
+    if max_slope is None:
+        max_slope = np.pi / np.sqrt((b[cross] ** 2).sum(axis=1)).min()
+    for i in range(ndim):
+        extent = X[cross, i].max() - X[cross, i].min()
+        if extent == 0.0:  # (a single baseline length)
+            extent = np.abs(X[cross, i]).max()
+        h[i] = 2.0 * np.pi / (pad * extent)
+        n[i] = 2 * int(np.ceil(max_slope / h[i])) + 1
+    if n[0] * n[1] > _ABSCAL_MAX_GRID:
+        raise ValueError(f"the slope grid has {n[0]} x {n[1]} points, more than 2**22: pass a smaller max_slope (now {max_slope:.3e} "
+                         "rad/m) or a smaller pad")
+    return n, h, float(max_slope)
+
+
+def redundant_abscal(
+    vis,
+    model,
+    ants: dict,
+    gains,
+    *,
+    reds: list = None,
+    weights=None,
+    per_time: bool = False,
+    max_slope: float = None,
+    pad: int = 4,
+    refine: int = 6,
+    polarized: bool = False,
+    precision: int = 2,
+    device: int = 0,
+):
+    """Absolute calibration on the device: fixes what redundant calibration leaves free -- per solve unit and feed the
+    amplitude of the gains and a phase gradient across the array -- by fitting the group visibilities to a model of them
+    (``fv_abscal_slopes``).  ``g_a -> g_a A exp(i Phi . (x_a - c))`` leaves the data model unchanged when ``U_g -> U_g eta
+    exp(-i Phi . b_g)``, ``eta = A^-2``, ``b_g = x[a2] - x[a1]`` of ``reds[g][0] = (a1, a2)``; abscal minimises
+    ``chi2(eta, Phi) = sum W |eta exp(-i Phi . b_g) U_g - M_g|^2`` over a unit's times and groups.  With ``c_g = sum_t W conj(U) M``,
+    ``S(Phi) = sum_g c_g exp(i Phi . b_g)`` and ``N = sum W |U|^2`` the best ``eta`` is ``Re S / N`` and ``Phi`` maximises ``Re S``: a
+    search over a grid of slopes (a non-uniform DFT from the group baselines, no unwrapping) and ``refine`` rounds of Newton.
+    The overall phase cancels in every visibility and is not a parameter.  Returns ``(gains, info)``.
+
+    * ``vis``: ``redundant_gain_solve``'s or ``redundant_average``'s group visibilities, ``(nfreqs, ntimes, ngroups)`` or
+      ``(nfreqs, ntimes, 2, 2, ngroups)``, used in complex128.  ``model``: ``simulate_vis(..., baselines=[red[0] for red in reds])``
+      in the same layout, used in the run's ``precision``.  ``weights``: per group in ``vis``' shape, float64, for instance
+      ``redundant_average``'s ``den`` zeroed where ``vis_solved`` is False; None means ones.  Numpy arrays or tensors; a tensor
+      on the run's device is read by pointer.  A sample is used when its weight is positive and its group is no
+      auto-correlation's; a flagged datum is not read.  A negative or non-finite weight and a non-finite value at a used
+      sample fail the call.
+    * ``gains``: the gains to fix, in any of the gain solve's four shapes (None: ones).  Whether a unit is a frequency or a
+      (frequency, time) follows their shape, by ``simulate_vis_gain_solve``'s shape rule and ``per_time``.
+    * The slope lives in the span of the group baselines: the right singular vectors ``Vt`` of the ``(ngroups, 3)`` baseline
+      matrix whose singular value exceeds 1e-9 of the largest, one for a line, two for a planar array; the device works in
+      the in-plane coordinates ``X = B Vt^T``.  Three is a ValueError.
+    * The grid, per dimension i: step ``h_i = 2 pi / (pad extent_i)``, ``extent_i = max X_i - min X_i``, and ``n_i = 2
+      ceil(max_slope / h_i) + 1`` points centred on 0; ``max_slope`` defaults to ``pi / min |b_g|``.  On a lattice ``S`` is
+      periodic in ``Phi``: aliased peaks give the same gains at every antenna.  The box is a square along the plane's axes: on
+      a hexagonal lattice of spacing a it does not hold the corners of the reciprocal cell, at ``4 pi / (3 a)``, and
+      ``max_slope=1.4 * np.pi / a`` does.  At most 2**22 points.
+    * Polarized data fit the parallel hands, feed p reads ``[p, p]``, with one ``(eta, Phi)`` per feed.
+    * Returns the gains times ``eta^-1/2 exp(i Phi . (x_a - mean x))`` per unit and feed, complex128, in ``gains``' shape.
+      Antennas of units with ``used == False`` are unchanged.  The matching group visibilities are ``redundant_average`` at
+      the returned gains.
+    * ``info``, per unit and feed in the layout ``([2,] nfreqs[, ntimes])`` of the gains without their antenna axis: ``amp``
+      (eta), ``slopes`` ``(..., 3)`` in ENU rad/m (the in-plane ``Phi`` mapped back through ``Vt``), ``used`` (False where ``N == 0``,
+      fewer than ``ndim + 1`` groups are used or ``Re S <= 0``: eta = 1, Phi = 0), ``peak`` ``(..., 2)`` the grid point as signed
+      steps, ``power`` (``Re S``), ``unorm`` (N), ``mnorm`` (``sum W |M|^2``); ``chi2`` ``(nfreqs, ntimes)`` at the returned
+      parameters, summed over the feeds; ``grid``: a dict of ``n``, ``h`` and ``max_slope``; ``reds`` as used.
+
+    Outputs follow ``vis`` to its device.  Not differentiable.  Not covered: one slope shared by both feeds and the
+    cross-hand phase, a slope model across frequency (a delay slope), rank-3 arrays, Jones matrices, sharding over GPUs."""
+    if int(pad) != pad or pad < 1:
+        raise ValueError(f"pad must be a positive integer, got {pad!r}")
+    if int(refine) != refine or not 0 <= refine <= 32:
+        raise ValueError(f"refine must be an integer in 0 .. 32, got {refine!r}")
+    if max_slope is not None and not (float(max_slope) > 0.0 and np.isfinite(float(max_slope))):
+        raise ValueError(f"max_slope must be positive and finite (rad/m), got {max_slope!r}")
+    run = _block_run(vis, ants, polarized, precision, device)
+    reds, _, _ = _groups(ants, reds, None)
+    ngroups = len(reds)
+    if ngroups != run.nbls:
+        raise ValueError(f"vis holds {run.nbls} groups, reds lists {ngroups}")
+    _check_vis_block(run, vis, "vis")
+    _check_vis_block(run, model, "model")
+    if weights is not None:
+        _check_weights(run, weights, "vis'")
+        _run_device(run, (weights,), "weights")
+    block, shape, own_time = _solve_start(run, gains, per_time)
+    b, vt, X = _abscal_plane(run.ants, reds)
+    n, h, max_slope = _abscal_grid(X, b, max_slope, int(pad))
+    ndim = X.shape[1]
+
+    import torch
+
+    from . import _lib
+    from .gpu.gpu_simulate import _buffer_addr
+
+    def as_read(x, dtype):  # a tensor on the run's device by pointer, anything else as a host array
+        if x is None:
+            return None
+        if _is_tensor(x) and x.device.type == "cuda":
+            return _on(x.device, x, dtype)
+        return np.ascontiguousarray(_host(x), dtype=dtype)
+
+    u, m, w = as_read(vis, np.complex128), as_read(model, run.cdt), as_read(weights, np.float64)  # (alive until the call returns)
+    (u_ptr, u_dev), (m_ptr, m_dev), (w_ptr, w_dev) = _buffer_addr(u), _buffer_addr(m), _buffer_addr(w)
+    _synchronize(torch.device("cuda", int(device)))
+    tpol, nfeed = (4, 2) if polarized else (1, 1)
+    units = (run.nfreqs, run.ntimes if own_time else 1, nfeed)
+    peak = np.zeros(units + (2,), dtype=np.int32)
+    slopes = np.zeros(units + (2,), dtype=np.float64)
+    amp, power, unorm, mnorm = (np.zeros(units, dtype=np.float64) for _ in range(4))
+    used = np.zeros(units, dtype=np.int32)
+    chi2 = np.zeros((run.nfreqs, run.ntimes), dtype=np.float64)
+    _lib.check(_lib.lib().fv_abscal_slopes(
+        int(device), int(precision), run.nfreqs, run.ntimes, tpol, ngroups, int(own_time), u_ptr, u_dev, m_ptr, m_dev, w_ptr, w_dev,
+        _lib.ptr(X), ndim, n[0], n[1], float(h[0]), float(h[1]), int(refine), _lib.ptr(peak), _lib.ptr(slopes), _lib.ptr(amp),
+        _lib.ptr(power), _lib.ptr(unorm), _lib.ptr(mnorm), _lib.ptr(used), _lib.ptr(chi2)))
+    ok = used != 0
+    enu = slopes[..., :ndim] @ vt  # (nfreqs, ntimes or 1, nfeed, 3)
+    pos = np.array([run.ants[k].reshape(-1)[:3] for k in run.ants], dtype=np.float64)
+    factor = np.exp(1j * (enu @ (pos - pos.mean(axis=0)).T)) / np.sqrt(amp)[..., None]  # (..., nfeed, nant)
+    fixed = np.where(ok[..., None], block * factor, block)
+
+    def unit(x):  # (nfreqs, ntimes or 1, nfeed, ...) in the gains' layout without the antenna axis
+        tail = x.shape[3:]
+        x = np.moveaxis(x, 2, 0)  # (nfeed, nfreqs, ntimes or 1, ...)
+        lead = ((2,) if polarized else ()) + ((run.nfreqs, run.ntimes) if own_time else (run.nfreqs,))
+        return np.ascontiguousarray(x).reshape(lead + tail)
+
+    out = _follow(vis, gains=_solve_result(fixed, shape), amp=unit(amp), slopes=unit(enu), chi2=chi2, used=unit(ok), peak=unit(peak),
+                  power=unit(power), unorm=unit(unorm), mnorm=unit(mnorm))
+    info = dict(amp=out["amp"], slopes=out["slopes"], chi2=out["chi2"], used=out["used"], peak=out["peak"],
+                grid=dict(n=tuple(n), h=tuple(h), max_slope=max_slope), power=out["power"], unorm=out["unorm"], mnorm=out["mnorm"],
+                reds=reds)
+    return out["gains"], info
 
 
 def fix_redundant_degeneracies(gains, ants: dict, *, ref_gains=None, solved=None, tilt: str = "per_feed"):

@@ -259,6 +259,46 @@ int fv_firstcal_offsets(int device, int precision, int nfreqs, int ntimes, int64
                         const int *ant2, int ngroups, const int *group, const double *slopes, const void *data, int data_on_device,
                         const void *weights, int weights_on_device, void *offsets, void *uvis_out, int max_iter, double tol,
                         int *niter_out, double *change_out, double *chi2_ft_out, int *solved_out, int *vis_solved_out);
+/* fv_abscal_slopes: absolute calibration of a redundant solve: the amplitude and the phase gradient the data leave free,
+ * fitted to a model of the group visibilities.  uvis (complex128), model (complex64 / complex128 by precision) and gweights
+ * (float64, null: ones) are (nfreqs, ntimes, tpol, ngroups) blocks, fv_redundant_solve's layout of uvis_out, each on the host
+ * or, with its on_device flag 1, on `device`; all three are read only.  A solve unit is a frequency (per_time 0: the sums run
+ * over its ntimes times) or a (frequency, time) (per_time 1); a row is a (unit, feed), nfeed = 2 for tpol 4, and feed p reads
+ * the parallel hand pol = 3 p.  coords: host, (ngroups, ndim) float64, the groups' baselines X_g in in-plane coordinates, ndim
+ * 1 (a line) or 2.  A sample is used when W > 0 and X_g != 0 (an auto-correlation's own group is never used); a flagged datum
+ * is not read.  Per row, every term formed and added in fp64, times ascending,
+ *   c_g = sum_t W conj(U) M,   N = sum W |U|^2,   P = sum W |M|^2,   S(Phi) = sum_g c_g exp(i Phi . X_g)
+ * and chi2(eta, Phi) = sum W |eta exp(-i Phi . X_g) U - M|^2 is least where Re S(Phi) is largest, with eta = Re S / N.  The
+ * search evaluates Re S on the grid Phi = (j_1 h1, j_2 h2), j_i = i_i - (n_i - 1) / 2, i_i = 0 .. n_i - 1 (n2 = 1 for ndim 1) and
+ * takes the point of the largest value, on a tie the lowest flat index i_1 n2 + i_2: the phase Phi . X in fp64, one sincos at
+ * the first point of a run of 8 consecutive grid points followed by 7 rotations by exp(i h X), the groups added in
+ * ascending order.  `refine` rounds of Newton on Re S follow, at the continuous Phi with sincos in fp64: with the gradient
+ * g = -sum X Im(c e^{i Phi . X}) and the Hessian H = -sum X X^T Re(c e^{i Phi . X}) the step is -H^-1 g where H is negative
+ * definite, else g / max |eig H| (0 where H = 0), either clipped to +-h_i per dimension; one more evaluation at the result gives
+ * Re S.  No floating-point atomics: the same input gives the same bits.  Outputs, host, (nunits, nfeed, ...): peak_out int32
+ * (.., 2), the grid point (j_1, j_2); slopes_out float64 (.., 2), the refined in-plane Phi; amp_out, eta; power_out, Re S;
+ * unorm_out, N; mnorm_out, P; used_out int32, 1 when N > 0, at least ndim + 1 groups have a used sample and Re S > 0, else 0
+ * with eta = 1, Phi = 0, the peak (0, 0) and power 0; chi2_ft_out (nfreqs, ntimes) float64, sum W |eta exp(-i Phi . X) U - M|^2
+ * over the feeds and the used samples, formed explicitly at the returned parameters.  A negative or non-finite weight, and a
+ * non-finite value of uvis or model at a used sample, fail the call with FV_ERR_ARG (fv_redundant_solve's messages).  tpol
+ * not in {1, 4}, a negative shape, per_time outside {0, 1}, ndim outside {1, 2}, n1 or n2 even or not positive, n1 n2 above
+ * 2^22, n2 != 1 for ndim 1, a step that is not positive and finite, refine outside 0 .. 32, an on_device flag outside {0, 1},
+ * coords that are not finite and a null pointer fail with FV_ERR_ARG before anything runs; ngroups == 0, nfreqs == 0 and
+ * ntimes == 0 give the neutral result: eta = 1, everything else 0. */
+int fv_abscal_slopes(int device, int precision, int nfreqs, int ntimes, int tpol, int ngroups, int per_time, const void *uvis,
+                     int uvis_on_device, const void *model, int model_on_device, const void *gweights, int gweights_on_device,
+                     const double *coords, int ndim, int n1, int n2, double h1, double h2, int refine, int *peak_out,
+                     double *slopes_out, double *amp_out, double *power_out, double *unorm_out, double *mnorm_out, int *used_out,
+                     double *chi2_ft_out);
+/* fv_abscal_evaluate: the evaluation fv_abscal_slopes' refinement iterates, alone, at the caller's slopes.  All host: c
+ * (nrows, ngroups) complex128, the rows' strengths; coords (ngroups, ndim) float64; slopes (nrows, 2) float64 (the second
+ * ignored for ndim 1: x_2 = 0); out (nrows, 6) float64: f = Re S, g_1, g_2, H_11, H_12, H_22 with
+ *   S = sum_g c_g exp(i Phi . X_g),   g = -sum X Im(c e^{i Phi . X}),   H = -sum X X^T Re(c e^{i Phi . X}),
+ * one wave per row, lane l adding the groups l, l + 64, ... and a fixed __shfl_xor tree.  A negative shape, ndim outside
+ * {1, 2}, coords that are not finite and a null pointer fail with FV_ERR_ARG before anything runs; nrows == 0 is a valid call
+ * and ngroups == 0 returns zeros. */
+int fv_abscal_evaluate(int device, int nrows, int ngroups, const void *c, const double *coords, int ndim, const double *slopes,
+                       double *out);
 /* fv_jones_normal_rows: one evaluation of the 2 x 2 normal systems of the Jones solve (the gather fv_jones_solve
  * iterates).  The rows, the pairs and the layout of the matrices are fv_jones_residual_chi2's; vis, data, weights are
  * read only; jones: (nrows, 2, 2, nant) complex128 whatever `precision` is.  A sample is used when w > 0 and

@@ -23,6 +23,7 @@
     jones_solve     forward solve solve_with_forward jones_chi2_steps               C3, 8 channels
     redundant_solve solve gain_solve both                                           C3, 8 channels
     firstcal        firstcal solve                                                  C3, 8 channels
+    abscal          abscal model_groups model_all gain_solve fix                    C3, 8 channels
 
 Prints one JSON line: ms per time step of each pass (wall clock of a whole call on a warm handle, divided by the time
 steps; the median of --repeats calls, with the values or their range) and the family's ratios, under the keys the family
@@ -73,8 +74,12 @@ redundant_gain_solve on resident data and weights, every baseline of the array i
 simulate_vis_gain_solve on the same block against the resident model U[group], 50 iterations each and no forward anywhere
 (``--only solve --only gain_solve``; ``--profile both`` runs one of each for a kernel trace).  firstcal: ``firstcal`` is
 redundant_firstcal on resident data whose gains carry delays of up to 150 ns, channels of 0.5 MHz, 50 iterations of its second
-stage, ``solve`` redundant_gain_solve from the firstcal gains, 50 iterations (``--profile firstcal`` for a kernel trace).  A flag
-of another family is an error.
+stage, ``solve`` redundant_gain_solve from the firstcal gains, 50 iterations (``--profile firstcal`` for a kernel trace).
+abscal: ``abscal`` is redundant_abscal (pad 4, 6 rounds) on resident group visibilities, model and weights, one unit per
+channel; ``model_groups`` is simulate_vis on one baseline per group, the model it needs; the other three are the route to
+the same end without it: ``model_all`` simulate_vis on every baseline, ``gain_solve`` simulate_vis_gain_solve on that block
+against the resident model, 50 iterations, and ``fix`` fix_redundant_degeneracies against its gains (``--profile abscal`` for
+a kernel trace).  A flag of another family is an error.
 tools/adjoint_timing.sh runs the adjoint family for C2 and C3 and two kernel-trace profiles."""
 
 import argparse
@@ -864,8 +869,69 @@ def firstcal(a, fv, cfg, rng):
     return head, {"firstcal": first, "solve": solve}
 
 
+def abscal(a, fv, cfg, rng):
+    """Abscal on resident group visibilities, model and weights (host to host: the gains go up and come back), next to the
+    route to the same end through the sky: a forward on every baseline, ``simulate_vis_gain_solve`` (GAIN_SOLVE_ITERATIONS
+    iterations against the resident model) and ``fix_redundant_degeneracies``.  The group visibilities are the model moved by
+    a planted amplitude and slope per channel and feed, 5 % noise; the sky route's data and model are random blocks (its
+    iterations do not depend on the values).  ``--profile abscal`` is one call, for a kernel trace."""
+    import torch
+
+    p = cfg["precision"]
+    cdt, rdt = (torch.complex64, torch.float32) if p == 1 else (torch.complex128, torch.float64)
+    ants, polarized = cfg["ants"], bool(cfg["polarized"])
+    nant = len(ants)
+    reds, bls, group = fv.redundant_groups(ants)
+    pos = np.array([np.asarray(ants[k], float) for k in ants])
+    b = np.array([pos[list(ants).index(r[0][1])] - pos[list(ants).index(r[0][0])] for r in reds])
+    lead = (nant, 2) if polarized else (nant,)
+    gains = np.ones(lead + (a.nfreq,), dtype=np.complex128)
+    pol = (2, 2) if polarized else ()
+    state = {}
+
+    def resident():
+        if not state:
+            gen = torch.Generator(device="cuda").manual_seed(0)
+            M = torch.randn((a.nfreq, a.ntimes) + pol + (len(reds),), dtype=torch.complex128, device="cuda", generator=gen)
+            phi = rng.uniform(-0.3, 0.3, (a.nfreq, 1) + pol + (1, 3)) * np.pi / np.sqrt((b**2).sum(axis=1)).min() * [1, 1, 0]
+            turn = torch.from_numpy(np.exp(1j * (phi * b).sum(axis=-1)) / rng.uniform(0.5, 2.0, (a.nfreq, 1) + pol + (1,))).cuda()
+            vis = M * turn + 0.05 * torch.randn(M.shape, dtype=M.dtype, device="cuda", generator=gen)
+            state.update(vis=vis.contiguous(), model=M.to(cdt).contiguous(), w=torch.ones(M.shape, dtype=torch.float64, device="cuda"))
+            torch.cuda.synchronize()
+        return state
+
+    def sky():  # the sky route's blocks, every baseline
+        if "data" not in state:
+            gen = torch.Generator(device="cuda").manual_seed(1)
+            shape = (a.nfreq, a.ntimes) + pol + (len(bls),)
+            state.update(data=torch.randn(shape, dtype=cdt, device="cuda", generator=gen),
+                         sky_model=torch.randn(shape, dtype=cdt, device="cuda", generator=gen), sky_w=torch.ones(shape, dtype=rdt, device="cuda"))
+            torch.cuda.synchronize()
+        return state
+
+    def fit():
+        s = resident()
+        return fv.redundant_abscal(s["vis"], s["model"], ants, gains, reds=reds, weights=s["w"], polarized=polarized, precision=p)
+
+    def gain_solve_all():
+        s = sky()
+        return fv.simulate_vis_gain_solve(s["data"], **dict(cfg, baselines=bls, fluxes=None), weights=s["sky_w"], model=s["sky_model"],
+                                          max_iter=GAIN_SOLVE_ITERATIONS, tol=0.0)
+
+    def fix():
+        if "g_sky" not in state:
+            state["g_sky"] = gains * np.exp(1j * rng.uniform(-0.5, 0.5, gains.shape))
+        return fv.fix_redundant_degeneracies(gains, ants, ref_gains=state["g_sky"])
+
+    calls = {"abscal": fit, "model_groups": lambda: fv.simulate_vis(**dict(cfg, baselines=[r[0] for r in reds])),
+             "model_all": lambda: fv.simulate_vis(**dict(cfg, baselines=bls)), "gain_solve": gain_solve_all, "fix": fix}
+    cfg["baselines"] = bls  # (the line's nbls)
+    head = {"config": a.config, "precision": p, "polarized": polarized, "iterations": GAIN_SOLVE_ITERATIONS, "ngroups": len(reds)}
+    return head, calls
+
+
 # family: (its function, default --config, default --nfreq, its own flags, what goes with a median: "range" | "runs" | None,
-#          ratios {key: (pass, pass it is divided by -- or a tuple of passes, for their sum)})
+#          ratios {key: (pass, pass it is divided by -- either may be a tuple of passes, for their sum)})
 FAMILIES = {
     "adjoint": (adjoint, "C3", 2, ("lattice", "adjoint_path"), "range", {"adjoint_over_forward": ("adjoint", "forward")}),
     "basis_adjoint": (basis_adjoint, "C5", 4, ("small",), None, {}),
@@ -896,6 +962,7 @@ FAMILIES = {
         "solve_over_forward": ("solve", "forward"), "chi2_steps_over_solve": ("jones_chi2_steps", "solve")}),
     "redundant_solve": (redundant_solve, "C3", 8, (), "runs", {"solve_over_gain_solve": ("solve", "gain_solve")}),
     "firstcal": (firstcal, "C3", 8, (), "runs", {"firstcal_over_solve": ("firstcal", "solve")}),
+    "abscal": (abscal, "C3", 8, (), "runs", {"abscal_route_over_sky_route": (("abscal", "model_groups"), ("model_all", "gain_solve", "fix"))}),
 }
 OWN_FLAGS = {"array": "ideal", "lattice": False, "adjoint_path": "type3", "small": False, "ndir": 8,
              "precision": 1, "wrt": "fluxes", "case": "fluxes", "gains": False, "d_gains": False, "jones": False,
@@ -981,9 +1048,9 @@ def main():
             out[name + "_range"] = [min(runs), max(runs)]
         print(json.dumps({name: runs}), file=sys.stderr, flush=True)
     for key, (num, den) in ratios.items():
-        den = (den,) if isinstance(den, str) else den
-        if all(k + "_ms_per_step" in out for k in (num,) + den):
-            out[key] = round(out[num + "_ms_per_step"] / sum(out[k + "_ms_per_step"] for k in den), 3)
+        num, den = (num,) if isinstance(num, str) else num, (den,) if isinstance(den, str) else den
+        if all(k + "_ms_per_step" in out for k in num + den):
+            out[key] = round(sum(out[k + "_ms_per_step"] for k in num) / sum(out[k + "_ms_per_step"] for k in den), 3)
     if all(k + "_ms_per_step" in out for k in ("forward", "tangent_1", "tangent_n")):  # (basis_tangent)
         # per direction, against TWO forward runs: what (V(C + D) - V(C - D)) / 2 costs a caller without the pass
         two = 2.0 * out["forward_ms_per_step"]
